@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — headline metric of BASELINE.json: Mray/s of the path-tracing hot path.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
+  A plain run sets up, warms up, times the K steps and prints the line. --full adds what needs work of its own:
+  the other BASELINE configs (other_configs), the CPU baseline with its check of the timed canvas (cpu_baseline),
+  and for mesh workloads the instrumented dispatch whose triangle counters the roofline needs.
+  --dump-outputs DIR writes what the last timed step handed its caller as float32 .npy files (dump_outputs()).
   N > 1 either way: `python bench.py --gpus N ...` starts its own N ranks (children of
   `python -m torch.distributed.run`, before this process has touched a GPU), and
   `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
@@ -21,7 +25,7 @@ roofline: the trace kernel is VALU-issue bound, not HBM bound (SURVEY.md §8d, H
          achieved = algorithmic lane-ops (W_ops formula of SURVEY.md §8d from the
          kernel's deterministic counters) / HIP-event kernel time; the HBM side
          (W_bytes / time against 8 TB/s) is reported next to it.
-cpu_baseline: the reference's own render.cl compiled for x86-64 (oracle/_ref, kind
+cpu_baseline (--full): the reference's own render.cl compiled for x86-64 (oracle/_ref, kind
          "reference") when that prebuilt library is present, else the CPU oracle (kind "port"),
          on a bounded row sample of the same frame, rank 0, N = 1 only.
 """
@@ -199,6 +203,37 @@ def cpu_baseline(name, sky, target_seconds=15.0, spp_override=0):
     }
 
 
+DUMP_BUDGET = 60_000_000  # bytes of array data --dump-outputs may write
+
+
+def dump_outputs(out_dir, canvas, argb):
+    """--dump-outputs: what the timed path handed its caller in its last step, as finite float32 / float64 .npy files:
+    canvas.npy, the accumulated radiance (x, y, z; the float3's 4th lane is padding), and argb.npy, the resolved bytes.
+    A canvas value that is not finite (a NaN-poisoned path) is 0 in canvas.npy and a row (flat index into
+    canvas.npy, kind: 1 NaN, 2 +inf, 3 -inf) of canvas_nonfinite.npy, shape (k, 2). A frame over DUMP_BUDGET is written as a
+    fixed, seeded sample of its pixels, whose flat indices (y * width + x) go to pixel_index.npy."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    h, w = argb.shape[:2]
+    canvas = canvas[:h, :, :3].reshape(h * w, 3)
+    argb = argb.reshape(h * w, 4)
+    per_pixel = 4 * (3 + 4) + 16 * np.count_nonzero(~np.isfinite(canvas)) / (h * w)  # (+ the non-finite rows, on average)
+    shape = (h, w)
+    (out_dir / "pixel_index.npy").unlink(missing_ok=True)
+    if h * w * per_pixel > DUMP_BUDGET:
+        n = int(DUMP_BUDGET // (per_pixel + 8))
+        idx = np.sort(np.random.default_rng(12345).choice(h * w, n, replace=False))
+        np.save(out_dir / "pixel_index.npy", idx.astype(np.float64))
+        canvas, argb, shape = canvas[idx], argb[idx], (n,)
+    canvas = canvas.astype(np.float32).reshape(-1)
+    bad = np.flatnonzero(~np.isfinite(canvas))
+    kind = np.where(np.isnan(canvas[bad]), 1, np.where(canvas[bad] > 0, 2, 3))
+    np.save(out_dir / "canvas_nonfinite.npy", np.stack([bad, kind], axis=1).astype(np.float64).reshape(-1, 2))
+    canvas[bad] = 0.0
+    np.save(out_dir / "canvas.npy", canvas.reshape(*shape, 3))
+    np.save(out_dir / "argb.npy", argb.reshape(*shape, 4).astype(np.float32))
+
+
 def kernels_hash():
     """sha256 of the kernel source a measurement belongs to (profiles/traffic.json carries the one it was taken with)"""
     import hashlib
@@ -278,8 +313,11 @@ def main():
     ap.add_argument("--workload", default="spheres_1080p_1024spp", choices=sorted(WORKLOADS))
     ap.add_argument("--spp", type=int, default=0, help="override samples per pixel (development only; makes the line non-comparable)")
     ap.add_argument("--rows-per-block", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the other_configs section (the other BASELINE configs on one GPU, measured after the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what needs work of its own: other_configs, cpu_baseline, the mesh workloads' triangle counters")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/*.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline section")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the other_configs section (the other BASELINE configs on one GPU, measured after the headline)")
     ap.add_argument("--accel", default="none", choices=["none", "bvh"],
                     help="bvh = opt-in acceleration structure for model shapes (srt_set_acceleration); the headline line uses none")
     ap.add_argument("--gather", default="lib", choices=["lib", "torch"],
@@ -445,6 +483,15 @@ def main():
     elapsed_max, trace_ms_max, trace_ms_min, gather_ms_max = float(stats[0]), float(stats[1]), -float(stats[2]), float(stats[3])
     rays, paths, nsky, nan_px = (int(v) for v in cnt.tolist())
 
+    if rank == 0 and args.dump_outputs:  # rank 0's frame of the last timed step: its canvas and resolved bytes
+        if use_lib_gather:
+            out_canvas, out_argb = t.read_gathered(canvas=True, argb=True)
+        else:
+            out_canvas = (step.full if collect else canvas_t).cpu().numpy()
+            out_argb = argb_t.cpu().numpy()
+        dump_outputs(args.dump_outputs, out_canvas, out_argb)
+        del out_canvas, out_argb
+
     check = None
     if rank == 0 and collect and os.environ.get("SRT_BENCH_CHECK", "1") != "0":
         # outside the timed region: the gathered, unpermuted canvas must equal a single-handle render of the whole frame bit for bit
@@ -461,7 +508,9 @@ def main():
     if rank == 0:
         steps = max(args.steps, 1)
         per = {"rays": rays // steps, "paths": paths // steps, "sky": nsky // steps, "tri_tests": 0, "tri_pass_u": 0}
-        if (shapes["type"] == R.SHAPE_MODEL).any() and world == 1:
+        # a plain run of a mesh workload on one GPU has no triangle counters: no W_ops, no roofline figures
+        ops_known = args.full or world > 1 or not (shapes["type"] == R.SHAPE_MODEL).any()
+        if (shapes["type"] == R.SHAPE_MODEL).any() and world == 1 and args.full:
             # triangle counters come from the instrumented kernel variant, outside the timed region
             t.count_triangles(True)
             t.reset_counters()
@@ -510,13 +559,14 @@ def main():
                           "trace_plus_ordered_reduce": round(float(np.mean(trace_ms)) if trace_ms else 0.0, 3),
                           "resolve": round(float(np.mean(resolve_ms)) if resolve_ms else 0.0, 4)},
             "roofline": {
-                "bound": "valu", "achieved": round(achieved, 3), "peak": round(VALU_PEAK_LANE_OPS / 1e12, 1), "unit": "Tlane-op/s",
-                "frac": round(achieved * 1e12 / VALU_PEAK_LANE_OPS, 4), "traffic": traffic,
-                "kernel": "srt_trace_kernel", "algorithmic_ops_per_launch": int(ops // world // max(step.launches[0], 1)),
+                "bound": "valu", "achieved": round(achieved, 3) if ops_known else None, "peak": round(VALU_PEAK_LANE_OPS / 1e12, 1), "unit": "Tlane-op/s",
+                "frac": round(achieved * 1e12 / VALU_PEAK_LANE_OPS, 4) if ops_known else None, "traffic": traffic,
+                "kernel": "srt_trace_kernel", "algorithmic_ops_per_launch": int(ops // world // max(step.launches[0], 1)) if ops_known else None,
                 "launches_per_step": step.launches[0],
                 **({"launch_time": "the step's launches overlap on two streams (srt_trace): `achieved` = ops of the step / span from the first launch's start to the last one's end, "
                                    "not ops per launch / a launch's own duration (a launch shares the GPU with its neighbour for part of its life)"} if step.launches[1] else {}),
-                "note": "VALU-issue roofline (SURVEY.md §8d/H8): 256 CU x 4 SIMD x 32 lanes x 2.4 GHz; ops = W_ops formula over exact kernel counters",
+                "note": "VALU-issue roofline (SURVEY.md §8d/H8): 256 CU x 4 SIMD x 32 lanes x 2.4 GHz; ops = W_ops formula over exact kernel counters"
+                        + ("" if ops_known else "; null here: a mesh workload's triangle counters take a dispatch of their own (--full)"),
                 "hbm": {"achieved": round(nbytes / world / kt / 1e9, 2), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
                         "frac": round(nbytes / world / kt / HBM_PEAK, 6), "design_bytes_per_launch": int(nbytes // world // max(step.launches[0], 1)),
                         "algorithmic_bytes_per_launch": int(nbytes_alg // world // max(step.launches[0], 1)),
@@ -531,7 +581,7 @@ def main():
         if check is not None:
             line["gathered_equals_single_gpu"] = check
             ok = ok and check
-        if world == 1 and args.workload == "spheres_1080p_1024spp" and not args.spp and not args.no_other_configs:
+        if args.full and world == 1 and args.workload == "spheres_1080p_1024spp" and not args.spp and not args.no_other_configs:
             # The other BASELINE configs on this GPU (handles of their own; headline fields unchanged): right behind the headline's
             # timed region, while the device is busy and BEFORE anything is freed or the CPU baseline leaves it idle for 15 s --
             # round 3 measured them after both and one 0.2 ms step took 74.7 ms.
@@ -557,7 +607,7 @@ def main():
                     ok = False
             del canv
             line["other_configs"] = others
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(args.workload, sky, spp_override=args.spp)
             # the frame that was TIMED, checked where the CPU has already rendered it: the canvas of the last timed step
             # (one dispatch at the workload's full spp) against the port's rows, bit for bit

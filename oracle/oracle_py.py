@@ -19,9 +19,14 @@ COUNTER_NAMES = ["paths", "rays", "sphere_tests", "plane_tests", "aabb_tests", "
 
 
 def build(ref=False):
-    """Compile the checker(s); `ref` additionally needs /root/reference."""
+    """Compile the checker(s); `ref` additionally needs the reference's source (reference_readable())."""
     targets = ["all"] + (["ref"] if ref else [])
     subprocess.run(["make", "-C", str(HERE)] + targets, check=True, capture_output=True)
+
+
+def reference_readable():
+    """True where this user can read the reference's render.cl at the Makefile's REFERENCE (absent or unreadable: False)."""
+    return subprocess.run(["make", "-s", "-C", str(HERE), "have-ref"], capture_output=True).returncode == 0
 
 
 def ref_available():

@@ -28,7 +28,7 @@ json.dump(tj, open("$OUT/traffic.json", "w"), indent=1, sort_keys=True)
 print(open("$OUT/traffic.json").read())
 PY
 cp $OUT/traffic.json $R/profiles/traffic.json  # (on the box's copy of the tree: the bench line below carries the traffic of THIS kernel source)
-python bench.py --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+python bench.py --full --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 ( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs > $OUT/stats.log 2>&1 ); echo "stats rc=$?"
 cp $(find $OUT/stats -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats.csv
 scripts/pmc_cmd.sh ${TAG}_spp64 sq1,sq2,mix,flow,cache,grbm scripts/sched_probe.py spheres > $OUT/pmc_spp64.log 2>&1; echo "pmc rc=$?"

@@ -84,3 +84,45 @@ def render_case(render_fn, case, sky):
         rd["time"] = np.uint32(tm & 0xFFFFFFFF)
         canvas = render_fn(rd, canvas)
     return canvas
+
+
+# ---- the renders of tests/test_oracle_vs_ref.py and tests/test_oracle_statistics.py; tests/golden/ref_checks.npz holds the
+# ---- reference build's outputs for them, so both tests also run where oracle/_ref cannot be built
+AVERAGE_STEPS = (1, 3)
+STATS_SPP = 256
+STATS_SEEDS = (12345, 777)  # the compared render's seed, and the other seed of the noise floor
+
+
+def ref_check_frames():
+    """name -> (scene, width, height, spp, render_data keywords) of the frames the port and the reference build render alike."""
+    out = {"sphere_slab": (S.sphere_scene(), 256, 32, 16, {}),  # a 32-row slab of config[0]
+           "mesh": (S.mesh_scene(2), 80, 45, 2, {}),
+           "average_input": (S.sphere_scene(), 64, 48, 4, {})}
+    for tm in (1, 2**31, 0xFFFFFFFF, 1700000000123 & 0xFFFFFFFF):
+        out[f"seed_{tm}"] = (S.mixed_test_scene(), 40, 30, 2, {"time": tm})
+    return out
+
+
+def render_frame(o, frame, sky):
+    """One frame of ref_check_frames() by the checker `o`: x, y, z only (the 4th lane of an OpenCL float3 is unspecified and
+    the reference build leaves register garbage in it)."""
+    (shapes, tris, mats), w, h, spp, kw = frame
+    rd = R.render_data(w, h, spp, 10, camera_to_world=S.default_camera(), **kw)
+    sd = R.scene_data(len(shapes))
+    return o.render(rd, sd, shapes, tris, mats, sky, nthreads=4)[..., :3]
+
+
+def average_input(canvas_xyz):
+    """The canvas test_average_bytes resolves: a rendered frame plus NaN poisoning and out-of-range values."""
+    a = np.concatenate([canvas_xyz, np.zeros_like(canvas_xyz[..., :1])], axis=-1)
+    a[0, 0, :3] = np.nan  # must resolve to byte 0, not crash
+    a[0, 1, :3] = (1e9, 0.0, -1.0)
+    return a
+
+
+def stats_render(o, case, sky, time_seed):
+    """A golden case rendered by `o` at STATS_SPP samples with another seed: x, y, z (float32) of the canvas."""
+    rd = case["rd"].copy()
+    rd["num_samples"] = STATS_SPP
+    rd["time"] = np.uint32(time_seed)
+    return o.render(rd, case["sd"], case["shapes"], case["tris"], case["mats"], sky, nthreads=8)[..., :3]

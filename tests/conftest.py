@@ -51,13 +51,13 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def ref():
-    """The reference's render.cl compiled for x86-64; only where it has been built."""
+    """The reference's render.cl compiled for x86-64 where it has been built (or its source can be read to build it),
+    else None: tests then compare against that build's stored outputs (tests/golden/ref_checks.npz)."""
     from oracle import oracle_py
     if not oracle_py.ref_available():
-        if Path("/root/reference/src/render.cl").exists():
-            oracle_py.build(ref=True)
-        else:
-            pytest.skip("oracle/_ref not built and /root/reference absent")
+        if not oracle_py.reference_readable():
+            return None
+        oracle_py.build(ref=True)
     return oracle_py.Oracle("ref")
 
 

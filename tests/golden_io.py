@@ -34,6 +34,13 @@ def load_kats():
     return {k: z[k] for k in z.files if k != "detmath_revision"}
 
 
+def load_ref_checks():
+    """The reference build's outputs for tests/test_oracle_vs_ref.py ("frame/<name>", "average/<steps>") and the glibc-libm
+    build's renders for tests/test_oracle_statistics.py ("libm/<case>")."""
+    z = np.load(GOLDEN / "ref_checks.npz")
+    return {k: z[k] for k in z.files if k != "detmath_revision"}
+
+
 def load_sky_probe():
     z = np.load(GOLDEN / "sky_probe.npz")
     return int(z["checksum"][0]), z["probe"]

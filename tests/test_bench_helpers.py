@@ -41,3 +41,48 @@ def test_cpu_baseline_leg(bench, sky):
         assert r["kind"] == "reference" and r["reference_equals_port"] is True and "bit-identical" in r["sample"]
     else:
         assert r["kind"] == "port"
+
+
+def _undump(d):
+    """canvas.npy with its non-finite values put back from canvas_nonfinite.npy"""
+    c = np.load(d / "canvas.npy")
+    rows = np.load(d / "canvas_nonfinite.npy")
+    assert rows.dtype == np.float64 and rows.ndim == 2 and rows.shape[1] == 2
+    flat = c.reshape(-1)
+    flat[rows[:, 0].astype(np.int64)] = np.array([np.nan, np.inf, -np.inf], np.float32)[rows[:, 1].astype(np.int64) - 1]
+    return c
+
+
+def test_dump_outputs(bench, tmp_path, monkeypatch):
+    from conftest import bits_equal
+    rng = np.random.default_rng(7)
+    h, w = 6, 5
+    canvas = rng.standard_normal((h + 2, w, 4)).astype(np.float32)  # (a one-rank canvas may carry padding rows)
+    canvas[0, 0, :3] = np.nan  # a NaN-poisoned pixel, and overflowed channels
+    canvas[2, 3, 1], canvas[4, 1, 2] = np.inf, -np.inf
+    argb = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+    bench.dump_outputs(tmp_path / "whole", canvas, argb)
+    files = sorted(f.name for f in (tmp_path / "whole").glob("*.npy"))
+    assert files == ["argb.npy", "canvas.npy", "canvas_nonfinite.npy"]
+    for f in files:
+        a = np.load(tmp_path / "whole" / f)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), f
+    c, a = np.load(tmp_path / "whole" / "canvas.npy"), np.load(tmp_path / "whole" / "argb.npy")
+    assert c.dtype == a.dtype == np.float32 and c.shape == (h, w, 3) and a.shape == (h, w, 4)
+    assert len(np.load(tmp_path / "whole" / "canvas_nonfinite.npy")) == 5
+    assert bits_equal(_undump(tmp_path / "whole"), canvas[:h, :, :3]) and np.array_equal(a, argb.astype(np.float32))
+    # over the budget: a fixed, seeded sample of the pixels, the same on every run
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 10 * (28 + 8))
+    for d in ("s1", "s2"):
+        bench.dump_outputs(tmp_path / d, canvas, argb)
+    idx = np.load(tmp_path / "s1" / "pixel_index.npy")
+    assert idx.dtype == np.float64 and 0 < len(idx) <= 10 and np.all(np.diff(idx) > 0)
+    for f in ("pixel_index.npy", "canvas.npy", "canvas_nonfinite.npy", "argb.npy"):
+        got = np.load(tmp_path / "s1" / f)
+        assert np.isfinite(got).all() and np.array_equal(got, np.load(tmp_path / "s2" / f)), f
+    k = idx.astype(np.int64)
+    assert bits_equal(_undump(tmp_path / "s1"), canvas[:h, :, :3].reshape(-1, 3)[k])
+    assert np.array_equal(np.load(tmp_path / "s1" / "argb.npy"), argb.reshape(-1, 4)[k].astype(np.float32))
+    # a finite canvas: no rows
+    bench.dump_outputs(tmp_path / "finite", np.nan_to_num(canvas, nan=0.0, posinf=0.0, neginf=0.0), argb)
+    assert np.load(tmp_path / "finite" / "canvas_nonfinite.npy").shape == (0, 2)
