@@ -112,7 +112,7 @@ int srt_bvh_build_host(const srt_shape *model, const srt_triangle *triangles, si
 int srt_bvh_wide_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, int force_balanced, uint32_t *blocks_out,
                       size_t blocks_cap, uint32_t *dest_out, size_t dest_cap, size_t *n_blocks, uint32_t *root, uint32_t *stack_need, int *balanced);
 
-/* Tracer::clear_canvas — src/tracer.cpp:98-101. */
+/* Tracer::clear_canvas — src/tracer.cpp:98-101. With the denoiser on, also its sums and counts. */
 int srt_clear_canvas(srt_tracer *t);
 
 /* ---- the hot path -------------------------------------------------------------- */
@@ -274,6 +274,40 @@ int srt_group_get_counters(srt_group *g, srt_counters *out); /* summed over the 
 int srt_render_pipelined(srt_tracer *t, const srt_render_data *options, uint32_t ticks_stopped, uint8_t *argb_out,
                          long long *frame_delivered);
 int srt_pipeline_flush(srt_tracer *t, uint8_t *argb_out, long long *frame_delivered);
+
+/* ---- edge-aware denoiser (new; the reference's "Denoising" plan, README.md:44) -------- */
+
+/* A spatial variance-guided a-trous filter (Schied et al., HPG 2017, without the temporal part). While
+ * it is on, srt_trace / srt_render / srt_render_async / srt_render_pipelined also
+ *   - trace the first min(feature_samples, num_samples) camera rays of every pixel to their first hit and
+ *     add up the front-facing normals, hit distances, material colours (sky: 1,1,1) and hits (guide buffers),
+ *   - add (1/n) * sum over the dispatch's paths of lum(radiance)^2 to a per-pixel moments buffer,
+ *     lum(c) = 0.2126 r + 0.7152 g + 0.0722 b;
+ * and the render calls resolve through the filter instead of the plain resolve. The canvas itself is
+ * bit-for-bit what it is with the denoiser off; the filter is outside the parity contract (fast exp / pow).
+ * Not available on a partitioned handle (srt_set_partition world > 1) or through srt_group_* /
+ * srt_resolve_gathered / srt_resolve_external. */
+
+/* Host-only: K = 5, sigma_luminance = 4, sigma_normal = 128, sigma_depth = 1, sigma_albedo = 0.1,
+ * feature_samples = 1, enable = 1. */
+int srt_denoise_defaults(srt_denoise_params *out);
+/* params NULL or enable == 0: off. Turning it on, or changing feature_samples while on, clears the
+ * canvas and all accumulations (guide buffers, moments, the counts below); other changes do not.
+ * Device buffers (36 B of sums + 64 B of filter state per pixel) are allocated on the first enable and kept.
+ * SRT_ERR_INVALID: a value out of range (iterations 0..8, feature_samples 1..64, sigmas > 0 and finite,
+ * reserved != 0). SRT_ERR_STATE: the handle is partitioned (world > 1). */
+int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params);
+/* The filter over the current canvas with the divisor ticks_stopped, into the handle's ARGB image
+ * (srt_read_argb) and the HDR result (srt_read_denoised). Asynchronous, like srt_resolve.
+ * SRT_ERR_STATE when the denoiser is off or nothing has been traced since the last clear. */
+int srt_resolve_denoised(srt_tracer *t, uint32_t ticks_stopped);
+/* The last filter result before tonemapping: width*height float4 = filtered r, g, b and variance. Blocking. */
+int srt_read_denoised(srt_tracer *t, float *rgba_out);
+/* The filter's inputs since the last clear (blocking; NULL skips an output): normal_depth = width*height
+ * float4 {sum of normals over hits, sum of hit distances}; albedo_hits = width*height float4 {sum of
+ * albedos over feature rays, hits}; moments = width*height floats; counts = {T dispatches, P = sum of
+ * num_samples}. */
+int srt_read_denoise_inputs(srt_tracer *t, float *normal_depth, float *albedo_hits, float *moments, uint32_t counts[2]);
 
 /* Device self-test of the deterministic math (tests only). Walks r = 0, stride, ... over
  * all 2^32 RNG outputs: out[0..2] = mismatch counts of the kernel-local sqrt / log / cos

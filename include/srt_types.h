@@ -126,6 +126,20 @@ typedef struct srt_scene_data {
 	srt_float3 sun_direction;
 } srt_scene_data;
 
+/* Edge-aware denoiser settings (srt_set_denoise in srt_abi.h; new, no counterpart in the reference).
+ * A spatial, variance-guided a-trous filter (SVGF without its temporal part) over the canvas,
+ * guided by primary-hit normals, distances and albedos. */
+typedef struct srt_denoise_params {
+	int32_t enable;          /* 0: off (the library launches what it launches without a denoiser) */
+	int32_t iterations;      /* a-trous passes K, 0..8 (steps 1, 2, 4, ...); 0 = the plain resolve */
+	int32_t feature_samples; /* camera rays per pixel and dispatch that feed the guide buffers, 1..64 */
+	float sigma_luminance;   /* > 0 */
+	float sigma_normal;      /* > 0: exponent of the normal weight */
+	float sigma_depth;       /* > 0 */
+	float sigma_albedo;      /* > 0 */
+	int32_t reserved;        /* must be 0 */
+} srt_denoise_params;
+
 #ifdef __cplusplus
 }
 #endif
@@ -169,5 +183,10 @@ SRT_STATIC_ASSERT(offsetof(srt_scene_data, sun_focus) == 4, "SceneData.sun_focus
 SRT_STATIC_ASSERT(offsetof(srt_scene_data, horizon_color) == 16, "SceneData.horizon@16");
 SRT_STATIC_ASSERT(offsetof(srt_scene_data, sun_color) == 64, "SceneData.sun_color@64");
 SRT_STATIC_ASSERT(offsetof(srt_scene_data, sun_direction) == 80, "SceneData.sun_direction@80");
+SRT_STATIC_ASSERT(sizeof(srt_denoise_params) == 32, "DenoiseParams 32 B");
+SRT_STATIC_ASSERT(offsetof(srt_denoise_params, feature_samples) == 8, "DenoiseParams.feature_samples@8");
+SRT_STATIC_ASSERT(offsetof(srt_denoise_params, sigma_luminance) == 12, "DenoiseParams.sigma_luminance@12");
+SRT_STATIC_ASSERT(offsetof(srt_denoise_params, sigma_albedo) == 24, "DenoiseParams.sigma_albedo@24");
+SRT_STATIC_ASSERT(offsetof(srt_denoise_params, reserved) == 28, "DenoiseParams.reserved@28");
 
 #endif /* SRT_TYPES_H */

@@ -1,0 +1,313 @@
+// denoise.hip — the edge-aware denoiser (include/srt_abi.h srt_set_denoise): a spatial variance-guided a-trous filter,
+// SVGF (Schied et al., HPG 2017) without its temporal part, over the canvas the trace kernel accumulates.
+//
+// Inputs, per pixel, accumulated since the last clear while the denoiser is on:
+//   normal_depth  {sum of front-facing first-hit normals, sum of hit distances} over the hits of the feature rays
+//   albedo_hits   {sum of hit material colours (sky: 1,1,1) over all feature rays, hits}   (kernels.hip srt_features_kernel)
+//   moments       sum over dispatches of (1/n) sum_k lum(radiance_k)^2                    (kernels.hip srt_reduce_kernel<true>)
+// and the handle's counts T (dispatches), P (sum of num_samples), F (feature rays per pixel).
+//
+// Filter (tests/denoise_ref.py restates it in numpy):
+//   set-up  c0 = canvas / ticks (per channel, as srt_resolve_kernel), V0 = max(0, M/T - lum(canvas/T)^2) / P (non-finite: 0),
+//           N = normalize(sum of normals) (0 without hits), Z = sum t / hits, A = sum albedo / F, cov = hits / F
+//   pass i  step s = 2^i, 5x5 taps q = p + s (dx, dy), h = [1/16, 1/4, 3/8, 1/4, 1/16], taps outside the image skipped,
+//           w = h(dx) h(dy) exp(-|Zp - Zq| / (sz Zp s + 1e-6)) max(0, Np.Nq)^sn exp(-|Ap - Aq|^2 / sa^2)
+//               exp(-|lp - lq| / (sl sqrt(g(V)p) + 1e-10)),
+//           g = the 3x3 [1/4, 1/2, 1/4]^2 filter of the pass's input variance over in-image taps (renormalised),
+//           c' = sum w c / sum w, V' = sum w^2 V / (sum w)^2; a tap with cov = 0 or a non-finite colour has weight 0; a pixel
+//           with cov = 0 or a non-finite colour (or no weight at all) passes through unchanged
+//   last    srt_resolve_kernel's tonemap (ACES fit, sqrt, bytes A,R,G,B); K = 0 gives the plain resolve's bytes.
+// No atomics: every output is a fixed function of its inputs, so runs are bit-identical. The passes use the fast
+// exp / log instructions: this stage is outside the parity contract (DESIGN.md "Denoiser").
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "../../include/srt_abi.h"
+#include "detmath.h"
+#include "device_types.h"
+
+#include "srt_internal.h"
+
+namespace {
+
+struct FilterParams {
+	int32_t width, height;
+	uint32_t num_pixels;
+	int32_t step;
+	float sigma_l, sigma_n, sigma_z, inv_sigma_a2; // inv_sigma_a2 = 1 / sigma_albedo^2
+	const float4 *guide;                           // 2 float4 per pixel: {N, Z}, {A, cov}
+	const float4 *in;                              // {colour, variance}
+	float4 *out;
+	uint32_t *argb; // last pass only (else NULL): the tonemapped bytes
+};
+
+struct SetupParams {
+	uint32_t num_pixels;
+	float ticks, T, P, F; // the resolve's divisor, dispatches, samples, feature rays per pixel
+	const float4 *canvas;
+	const float4 *normal_depth;
+	const float4 *albedo_hits;
+	const float *moments;
+	float4 *guide;
+	float4 *out;
+	uint32_t *argb; // K = 0 only
+};
+
+// srt_resolve_kernel's expressions (kernels.hip aces1, to_uchar; sqrt_ieee there is the correctly rounded square root,
+// as __builtin_sqrtf is with hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt)
+__device__ __forceinline__ float aces1(float x) {
+	const float a = 2.51f, b = 0.03f, c = 2.43f, d = 0.59f, e = 0.14f;
+	return dm_clamp((x * (x * a + b)) / (x * (x * c + d) + e), 0.0f, 1.0f);
+}
+__device__ __forceinline__ uint32_t to_uchar(float v) { return (v == v) ? ((uint32_t)(int)v & 255u) : 0u; }
+__device__ __forceinline__ uint32_t tonemap(float x, float y, float z) {
+	const float r = __builtin_sqrtf(aces1(x)), g = __builtin_sqrtf(aces1(y)), b = __builtin_sqrtf(aces1(z));
+	return 255u | (to_uchar(r * 255.0f) << 8) | (to_uchar(g * 255.0f) << 16) | (to_uchar(b * 255.0f) << 24);
+}
+__device__ __forceinline__ float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
+__device__ __forceinline__ bool finite3(float4 c) { return __builtin_isfinite(c.x) && __builtin_isfinite(c.y) && __builtin_isfinite(c.z); }
+
+__global__ __launch_bounds__(256) void srt_denoise_setup_kernel(const SetupParams p) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= p.num_pixels) return;
+	const float4 c = p.canvas[i], nd = p.normal_depth[i], ah = p.albedo_hits[i];
+	const float m = p.moments[i];
+	const float4 c0 = make_float4(c.x / p.ticks, c.y / p.ticks, c.z / p.ticks, 0.f);
+	const float l = lum(c.x / p.T, c.y / p.T, c.z / p.T);
+	float v = m / p.T - l * l;
+	v = v > 0.f ? v : 0.f;
+	v = v / p.P;
+	if (!__builtin_isfinite(v)) v = 0.f;
+	const float hits = ah.w;
+	float nx = 0.f, ny = 0.f, nz = 0.f, z = 0.f;
+	if (hits > 0.f) {
+		const float len = sqrtf(nd.x * nd.x + nd.y * nd.y + nd.z * nd.z);
+		if (len > 0.f) nx = nd.x / len, ny = nd.y / len, nz = nd.z / len;
+		z = nd.w / hits;
+	}
+	p.guide[2 * i] = make_float4(nx, ny, nz, z);
+	p.guide[2 * i + 1] = make_float4(ah.x / p.F, ah.y / p.F, ah.z / p.F, hits / p.F);
+	p.out[i] = make_float4(c0.x, c0.y, c0.z, v);
+	if (p.argb) p.argb[i] = tonemap(c0.x, c0.y, c0.z);
+}
+
+__global__ __launch_bounds__(256) void srt_denoise_atrous_kernel(const FilterParams p) {
+	const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+	if (x >= p.width || y >= p.height) return;
+	const uint32_t i = (uint32_t)y * (uint32_t)p.width + (uint32_t)x;
+	const float4 cp = p.in[i];
+	const float4 g1p = p.guide[2 * i + 1];
+	float4 o = cp;
+	if (g1p.w > 0.f && finite3(cp)) {
+		const float4 g0p = p.guide[2 * i];
+		// g(V): 3x3 binomial prefilter of the input variance over in-image taps
+		float gv = 0.f, gw = 0.f;
+		for (int dy = -1; dy <= 1; dy++) {
+			const int qy = y + dy;
+			if (qy < 0 || qy >= p.height) continue;
+			for (int dx = -1; dx <= 1; dx++) {
+				const int qx = x + dx;
+				if (qx < 0 || qx >= p.width) continue;
+				const float k = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);
+				gv += k * p.in[(uint32_t)qy * (uint32_t)p.width + (uint32_t)qx].w;
+				gw += k;
+			}
+		}
+		gv = gv / gw;
+		const float lp = lum(cp.x, cp.y, cp.z);
+		const float inv_dl = 1.0f / (p.sigma_l * sqrtf(gv) + 1e-10f);
+		const float inv_dz = 1.0f / (p.sigma_z * g0p.w * (float)p.step + 1e-6f);
+		const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+		float sw = 0.f, sv = 0.f, sr = 0.f, sg = 0.f, sb = 0.f;
+		for (int dy = -2; dy <= 2; dy++) {
+			const int qy = y + dy * p.step;
+			if (qy < 0 || qy >= p.height) continue;
+			for (int dx = -2; dx <= 2; dx++) {
+				const int qx = x + dx * p.step;
+				if (qx < 0 || qx >= p.width) continue;
+				const uint32_t j = (uint32_t)qy * (uint32_t)p.width + (uint32_t)qx;
+				const float4 g1q = p.guide[2 * j + 1];
+				const float4 cq = p.in[j];
+				if (!(g1q.w > 0.f) || !finite3(cq)) continue;
+				const float4 g0q = p.guide[2 * j];
+				const float d = g0p.x * g0q.x + g0p.y * g0q.y + g0p.z * g0q.z;
+				if (!(d > 0.f)) continue; // max(0, d)^sigma_n = 0
+				const float wn = __expf(p.sigma_n * __logf(d));
+				const float ar = g1p.x - g1q.x, ag = g1p.y - g1q.y, ab = g1p.z - g1q.z;
+				const float e = fabsf(g0p.w - g0q.w) * inv_dz + (ar * ar + ag * ag + ab * ab) * p.inv_sigma_a2 +
+				                fabsf(lp - lum(cq.x, cq.y, cq.z)) * inv_dl;
+				const float w = h[dx + 2] * h[dy + 2] * wn * __expf(-e);
+				sw += w;
+				sv += w * w * cq.w;
+				sr += w * cq.x, sg += w * cq.y, sb += w * cq.z;
+			}
+		}
+		if (sw > 0.f) o = make_float4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
+	}
+	p.out[i] = o;
+	if (p.argb) p.argb[i] = tonemap(o.x, o.y, o.z);
+}
+
+bool params_ok(const srt_denoise_params &d) {
+	auto sigma_ok = [](float s) { return std::isfinite(s) && s > 0.0f; };
+	return d.iterations >= 0 && d.iterations <= 8 && d.feature_samples >= 1 && d.feature_samples <= 64 && sigma_ok(d.sigma_luminance) &&
+	       sigma_ok(d.sigma_normal) && sigma_ok(d.sigma_depth) && sigma_ok(d.sigma_albedo) && d.reserved == 0;
+}
+
+size_t full_pixels(const srt_tracer *t) { return (size_t)t->width * (size_t)t->height; }
+
+} // namespace
+
+// ---- host side (srt_internal.h) --------------------------------------------------------------------------------------
+
+int srt_denoise_clear(srt_tracer *t) {
+	const size_t px = full_pixels(t);
+	SRT_HIP(t, hipMemsetAsync(t->dn_nd.ptr, 0, px * 16, t->stream));
+	SRT_HIP(t, hipMemsetAsync(t->dn_ah.ptr, 0, px * 16, t->stream));
+	SRT_HIP(t, hipMemsetAsync(t->dn_mom.ptr, 0, px * 4, t->stream));
+	t->dn_T = t->dn_P = t->dn_F = 0;
+	return SRT_OK;
+}
+
+int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples) {
+	const uint32_t ns = num_samples > 0 ? (uint32_t)num_samples : 0u;
+	const uint32_t fs = (uint32_t)t->dn.feature_samples < ns ? (uint32_t)t->dn.feature_samples : ns;
+	FeatureParams fp;
+	fp.tp = p;
+	fp.normal_depth = t->dn_nd.ptr;
+	fp.albedo_hits = t->dn_ah.ptr;
+	fp.num_pixels = (uint32_t)full_pixels(t);
+	fp.feature_samples = fs;
+	srt_launch_features(fp, t->stream);
+	SRT_HIP(t, hipGetLastError());
+	t->dn_T += 1;
+	t->dn_P += ns;
+	t->dn_F += fs;
+	return SRT_OK;
+}
+
+int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
+	const size_t px = full_pixels(t);
+	if (px == 0) return SRT_OK;
+	const int K = t->dn.iterations;
+	float4 *col = reinterpret_cast<float4 *>(t->dn_col.ptr);
+	float4 *guide = reinterpret_cast<float4 *>(t->dn_guide.ptr);
+	SetupParams sp;
+	sp.num_pixels = (uint32_t)px;
+	sp.ticks = (float)ticks_stopped;
+	sp.T = (float)t->dn_T;
+	sp.P = (float)t->dn_P;
+	sp.F = (float)t->dn_F;
+	sp.canvas = reinterpret_cast<const float4 *>(t->canvas);
+	sp.normal_depth = reinterpret_cast<const float4 *>(t->dn_nd.ptr);
+	sp.albedo_hits = reinterpret_cast<const float4 *>(t->dn_ah.ptr);
+	sp.moments = t->dn_mom.ptr;
+	sp.guide = guide;
+	sp.out = col;
+	sp.argb = K == 0 ? reinterpret_cast<uint32_t *>(argb) : nullptr;
+	hipLaunchKernelGGL(srt_denoise_setup_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, t->stream, sp);
+	SRT_HIP(t, hipGetLastError());
+	FilterParams fp;
+	fp.width = t->width;
+	fp.height = t->height;
+	fp.num_pixels = (uint32_t)px;
+	fp.sigma_l = t->dn.sigma_luminance;
+	fp.sigma_n = t->dn.sigma_normal;
+	fp.sigma_z = t->dn.sigma_depth;
+	fp.inv_sigma_a2 = 1.0f / (t->dn.sigma_albedo * t->dn.sigma_albedo);
+	fp.guide = guide;
+	const dim3 grid((unsigned)((t->width + 15) / 16), (unsigned)((t->height + 15) / 16));
+	for (int k = 0; k < K; k++) {
+		fp.step = 1 << k;
+		fp.in = col + (size_t)(k & 1) * px;
+		fp.out = col + (size_t)((k + 1) & 1) * px;
+		fp.argb = k == K - 1 ? reinterpret_cast<uint32_t *>(argb) : nullptr;
+		hipLaunchKernelGGL(srt_denoise_atrous_kernel, grid, dim3(256), 0, t->stream, fp);
+		SRT_HIP(t, hipGetLastError());
+	}
+	t->dn_out = K & 1;
+	t->dn_filtered = true;
+	return SRT_OK;
+}
+
+// ---- C ABI -------------------------------------------------------------------------------------------------------------
+
+int srt_denoise_defaults(srt_denoise_params *out) {
+	if (!out) return SRT_ERR_INVALID;
+	out->enable = 1;
+	out->iterations = 5;
+	out->feature_samples = 1;
+	out->sigma_luminance = 4.0f;
+	out->sigma_normal = 128.0f;
+	out->sigma_depth = 1.0f;
+	out->sigma_albedo = 0.1f;
+	out->reserved = 0;
+	return SRT_OK;
+}
+
+int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!params || !params->enable) {
+		t->dn_on = false;
+		return SRT_OK;
+	}
+	if (!params_ok(*params))
+		return fail(t, SRT_ERR_INVALID, "srt_set_denoise: iterations 0..8, feature_samples 1..64, sigmas finite and > 0, reserved 0");
+	if (t->world > 1) return fail(t, SRT_ERR_STATE, "srt_set_denoise: not available on a partitioned handle (srt_set_partition world > 1)");
+	SRT_HIP(t, hipSetDevice(t->device));
+	const size_t px = full_pixels(t);
+	SRT_HIP(t, t->dn_nd.reserve(px * 4));
+	SRT_HIP(t, t->dn_ah.reserve(px * 4));
+	SRT_HIP(t, t->dn_mom.reserve(px));
+	SRT_HIP(t, t->dn_guide.reserve(px * 8));
+	SRT_HIP(t, t->dn_col.reserve(px * 8));
+	const bool clear = !t->dn_on || params->feature_samples != t->dn.feature_samples;
+	t->dn = *params;
+	t->dn_on = true;
+	if (clear) {
+		t->dn_filtered = false;
+		SRT_HIP(t, hipMemsetAsync(t->canvas, 0, t->canvas_bytes, t->stream)); // srt_clear_canvas
+		return srt_denoise_clear(t);
+	}
+	return SRT_OK;
+}
+
+int srt_resolve_denoised(srt_tracer *t, uint32_t ticks_stopped) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!t->dn_on) return fail(t, SRT_ERR_STATE, "srt_resolve_denoised: the denoiser is off (srt_set_denoise)");
+	if (t->dn_T == 0) return fail(t, SRT_ERR_STATE, "srt_resolve_denoised: nothing traced since the last clear");
+	SRT_HIP(t, hipSetDevice(t->device));
+	SRT_HIP(t, hipEventRecord(t->ev_r0, t->stream));
+	int rc = srt_denoise_filter(t, ticks_stopped, t->argb.ptr);
+	if (rc) return rc;
+	SRT_HIP(t, hipEventRecord(t->ev_r1, t->stream));
+	t->have_resolve_ev = true;
+	return SRT_OK;
+}
+
+int srt_read_denoised(srt_tracer *t, float *rgba_out) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!rgba_out) return fail(t, SRT_ERR_INVALID, "srt_read_denoised: rgba_out is NULL");
+	if (!t->dn_filtered) return fail(t, SRT_ERR_STATE, "srt_read_denoised: no filtered image (render or srt_resolve_denoised with the denoiser on)");
+	SRT_HIP(t, hipSetDevice(t->device));
+	const size_t px = full_pixels(t);
+	SRT_HIP(t, hipMemcpyAsync(rgba_out, t->dn_col.ptr + (size_t)t->dn_out * px * 4, px * 16, hipMemcpyDeviceToHost, t->stream));
+	SRT_HIP(t, hipStreamSynchronize(t->stream));
+	return SRT_OK;
+}
+
+int srt_read_denoise_inputs(srt_tracer *t, float *normal_depth, float *albedo_hits, float *moments, uint32_t counts[2]) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!t->dn_nd.ptr) return fail(t, SRT_ERR_STATE, "srt_read_denoise_inputs: the denoiser was never enabled");
+	SRT_HIP(t, hipSetDevice(t->device));
+	const size_t px = full_pixels(t);
+	if (normal_depth) SRT_HIP(t, hipMemcpyAsync(normal_depth, t->dn_nd.ptr, px * 16, hipMemcpyDeviceToHost, t->stream));
+	if (albedo_hits) SRT_HIP(t, hipMemcpyAsync(albedo_hits, t->dn_ah.ptr, px * 16, hipMemcpyDeviceToHost, t->stream));
+	if (moments) SRT_HIP(t, hipMemcpyAsync(moments, t->dn_mom.ptr, px * 4, hipMemcpyDeviceToHost, t->stream));
+	SRT_HIP(t, hipStreamSynchronize(t->stream));
+	if (counts) counts[0] = t->dn_T, counts[1] = t->dn_P;
+	return SRT_OK;
+}

@@ -197,8 +197,11 @@ struct ReduceParams {
 	uint32_t first_batch, last_batch;
 	unsigned long long *queue_reset; /* the work cursor the batch's trace launch used: zeroed here for the launch that uses it next (one
 	                                    command less per frame than a memset of 8 bytes in front of every trace launch) */
-	uint8_t *argb;                   /* last batch only, may be NULL: the pixel's A,R,G,B bytes as srt_resolve_kernel makes them of the new
-	                                    canvas value (srt_render: one launch less per frame) */
+	union {
+		uint8_t *argb;  /* srt_reduce_kernel<false>, last batch only, may be NULL: the pixel's A,R,G,B bytes as srt_resolve_kernel makes
+		                   them of the new canvas value (srt_render: one launch less per frame) */
+		float *moments; /* srt_reduce_kernel<true> (denoiser): per pixel, += (1/n) sum_k lum(radiance_k)^2 with the last batch */
+	};
 	uint32_t num_steps;              /* the resolve's divisor (ticks_stopped) */
 };
 
@@ -209,8 +212,22 @@ struct ResolveParams {
 	uint32_t num_pixels;
 };
 
+/* Denoiser guide buffers (kernels.hip srt_features_kernel): the primary hits of samples 0 .. feature_samples - 1 of the
+ * dispatch `tp` describes, added per pixel into normal_depth {sum of front-facing normals, sum of t over hits} and
+ * albedo_hits {sum of material colours, sky = (1,1,1); hits}. Full frame only (world == 1). */
+struct FeatureParams {
+	TraceParams tp; /* the scene buffers and camera set-up of the dispatch, as srt_trace fills them */
+	float *normal_depth;
+	float *albedo_hits;
+	uint32_t num_pixels;
+	uint32_t feature_samples; /* min(feature_samples, num_samples), > 0 */
+};
+
 void srt_launch_trace(TraceParams p, bool count_triangles, int num_waves, void *stream);
 void srt_launch_reduce(const ReduceParams &p, void *stream);
+/* the same reduction that also adds (1/n) sum_k lum(radiance_k)^2 into moments[pixel] (denoiser; `running`.w carries the sum across batches) */
+void srt_launch_reduce_moments(const ReduceParams &p, void *stream);
+void srt_launch_features(const FeatureParams &p, void *stream);
 int srt_trace_waves_per_simd(int has_models, int use_bvh);
 int srt_trace_resident_waves_per_cu(const TraceParams &p, bool count_triangles); /* from the runtime's occupancy calculator */
 int srt_scan_suspend_min(void); /* array scan: models of at least this many triangles sit alone in their block and are flagged big */

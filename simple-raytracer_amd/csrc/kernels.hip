@@ -2056,15 +2056,27 @@ __device__ __forceinline__ uint32_t to_uchar(float v) { return (v == v) ? ((uint
 // the float sums are the reference's `color += trace(...)` sequence bit for bit no matter
 // which wave traced which sample. 12 B per path in, 16 B RMW per pixel out: HBM-bound.
 // ---------------------------------------------------------------------------------
+// MOMENTS (denoiser, csrc/denoise.hip): also s2 = sum_k lum(radiance_k)^2 in the same order, carried across batches in
+// running.w, and moments[pixel] += s2 / num_samples with the last batch; no fused resolve (the filter resolves). The canvas
+// sum is the same either way.
+namespace {
+__device__ __forceinline__ float add_lum2(float s2, float r, float g, float b) {
+	const float l = 0.2126f * r + 0.7152f * g + 0.0722f * b;
+	return s2 + l * l;
+}
+} // namespace
+template <bool MOMENTS>
 __global__ __launch_bounds__(256) void srt_reduce_kernel(const ReduceParams p) {
 	const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
 	if (q == 0u && p.queue_reset) *p.queue_reset = 0ull; // the trace launch this reduction follows is over: its cursor, ready for the next one
 	if (q >= p.num_pixels) return;
 	f3 c = mk(0.f, 0.f, 0.f);
+	float s2 = 0.f;
 	float4 *run = reinterpret_cast<float4 *>(p.running) + q;
 	if (!p.first_batch) {
 		float4 v = *run;
 		c = mk(v.x, v.y, v.z);
+		if (MOMENTS) s2 = v.w;
 	}
 	const uint32_t n = p.batch_samples;
 	const float *__restrict__ r = p.radiance + (size_t)q * n * 3u;
@@ -2087,21 +2099,32 @@ __global__ __launch_bounds__(256) void srt_reduce_kernel(const ReduceParams p) {
 			for (int i = 0; i < 3 * SRT_REDUCE_DEPTH; i += 3) {
 				const float4 a = v[i], b = v[i + 1], d = v[i + 2];
 				c = c + mk(a.x, a.y, a.z);
+				if (MOMENTS) s2 = add_lum2(s2, a.x, a.y, a.z);
 				c = c + mk(a.w, b.x, b.y);
+				if (MOMENTS) s2 = add_lum2(s2, a.w, b.x, b.y);
 				c = c + mk(b.z, b.w, d.x);
+				if (MOMENTS) s2 = add_lum2(s2, b.z, b.w, d.x);
 				c = c + mk(d.y, d.z, d.w);
+				if (MOMENTS) s2 = add_lum2(s2, d.y, d.z, d.w);
 			}
 		}
 		for (; k < n; k += 4) {
 			const float4 a = r4[0], b = r4[1], d = r4[2];
 			r4 += 3;
 			c = c + mk(a.x, a.y, a.z);
+			if (MOMENTS) s2 = add_lum2(s2, a.x, a.y, a.z);
 			c = c + mk(a.w, b.x, b.y);
+			if (MOMENTS) s2 = add_lum2(s2, a.w, b.x, b.y);
 			c = c + mk(b.z, b.w, d.x);
+			if (MOMENTS) s2 = add_lum2(s2, b.z, b.w, d.x);
 			c = c + mk(d.y, d.z, d.w);
+			if (MOMENTS) s2 = add_lum2(s2, d.y, d.z, d.w);
 		}
 	} else {
-		for (; k < n; k++) c = c + mk(r[3 * k], r[3 * k + 1], r[3 * k + 2]);
+		for (; k < n; k++) {
+			c = c + mk(r[3 * k], r[3 * k + 1], r[3 * k + 2]);
+			if (MOMENTS) s2 = add_lum2(s2, r[3 * k], r[3 * k + 1], r[3 * k + 2]);
+		}
 	}
 	if (p.last_batch) {
 		c = c / (float)p.num_samples; // render.cl:520 (num_samples == 0 -> 0/0 = NaN, as the reference)
@@ -2112,14 +2135,143 @@ __global__ __launch_bounds__(256) void srt_reduce_kernel(const ReduceParams p) {
 		o.z += c.z;
 		*out = o; // render.cl:522
 		if (c.x != c.x || c.y != c.y || c.z != c.z) atomicAdd(&p.counters[SRT_CTR_NAN], 1ull);
-		if (p.argb) { // the resolve of this pixel (srt_resolve_kernel's expressions on the value just written), fused for srt_render
+		if (!MOMENTS && p.argb) { // the resolve of this pixel (srt_resolve_kernel's expressions on the value just written), fused for srt_render
 			const float n = (float)p.num_steps;
 			const float r = sqrt_ieee(aces1(o.x / n)), g = sqrt_ieee(aces1(o.y / n)), b = sqrt_ieee(aces1(o.z / n));
 			reinterpret_cast<uint32_t *>(p.argb)[q] = 255u | (to_uchar(r * 255.0f) << 8) | (to_uchar(g * 255.0f) << 16) | (to_uchar(b * 255.0f) << 24);
 		}
+		if (MOMENTS) p.moments[q] += s2 / (float)p.num_samples;
 	} else {
-		*run = make_float4(c.x, c.y, c.z, 0.f);
+		*run = make_float4(c.x, c.y, c.z, MOMENTS ? s2 : 0.f);
 	}
+}
+
+// ---------------------------------------------------------------------------------
+// Denoiser guide buffers (device_types.h FeatureParams; the filter is csrc/denoise.hip). One lane = one pixel, its first
+// feature_samples camera rays one after the other: the trace kernel's seed, jitter and camera matrix (CAMERA above), its
+// closest_intersection (EXTEND above: the same block order and the same tests, so the same closest hit) and its winner
+// normal (SHADE_WINNER). Not wave-coherent and not persistent: under SRT_ACCEL_NONE a big model costs every pixel's ray
+// a brute-force scan of the model's triangles once per feature sample (DESIGN.md "Denoiser"); with a hierarchy each lane
+// walks it with a stack of its own.
+// ---------------------------------------------------------------------------------
+namespace {
+// the normal of the hit at `pos`, before the front-face flip: a copy of SHADE_WINNER in srt_trace_kernel (global-memory form)
+template <bool HAS_MODELS, bool USE_BVH>
+__device__ __forceinline__ f3 winner_normal(const TraceParams &p, int best, uint32_t best_tri, f3 pos) {
+	const WinnerRec *__restrict__ wr = p.winners + best;
+	const int type = wr->type;
+	const f3 wv = mk(wr->vx, wr->vy, wr->vz);
+	f3 nrm = wv; // a plane's normal as stored
+	if (type == SRT_SHAPE_SPHERE) {
+		nrm = div3_by_rcp(pos - wv, wr->w, wr->inv_w);
+	} else if (HAS_MODELS && type != SRT_SHAPE_PLANE) {
+		const srt_model *__restrict__ m = &p.shapes[best].shape.model;
+		const float *__restrict__ w = USE_BVH ? p.bvh_blocks + (size_t)(best_tri >> 2) * 32u + (best_tri & 3u) * SRT_BVH_TRI_FLOATS
+		                                      : p.wtris + (size_t)(wr->first_wtri + best_tri) * SRT_WTRI_FLOATS;
+		const uint32_t tri_in_model = USE_BVH ? bvh_tri_in_model(reinterpret_cast<const float4 *>(p.bvh_blocks), best_tri) : best_tri;
+		f3 v0 = mk(w[0], w[1], w[2]);
+		f3 e1 = mk(w[3], w[4], w[5]);
+		f3 e2 = mk(w[6], w[7], w[8]);
+		f3 v2 = pos - v0;
+		float d00 = dot3(e1, e1), d01 = dot3(e1, e2), d11 = dot3(e2, e2);
+		float d20 = dot3(v2, e1), d21 = dot3(v2, e2);
+		float den = d00 * d11 - d01 * d01;
+		float w0 = (d11 * d20 - d01 * d21) / den;
+		float w1 = (d00 * d21 - d01 * d20) / den;
+		float w2 = 1.0f - w0 - w1;
+		const srt_triangle *__restrict__ tr = p.triangles + (m->triangle_index + tri_in_model);
+		f3 n = (ld3(tr->vertices[0].normal) * w2 + ld3(tr->vertices[1].normal) * w0) + ld3(tr->vertices[2].normal) * w1;
+		n = mat_by_vec(m->transform, n, 0.0f);
+		nrm = normalize3(n);
+	}
+	return nrm;
+}
+} // namespace
+
+template <bool HAS_MODELS, bool USE_BVH>
+__global__ __launch_bounds__(64) void srt_features_kernel(const FeatureParams fp) {
+	const TraceParams &p = fp.tp;
+	const uint32_t q = blockIdx.x * 64u + threadIdx.x;
+	if (q >= fp.num_pixels) return;
+#ifdef SRT_REGION_COUNT
+	__shared__ uint32_t region_ctr[2 * SRT_REGION_MAX]; // (development builds: the shared helpers count regions; nobody reads these)
+#endif
+	const int width = p.rd.width;
+	const uint32_t lrow = (__umulhi(q, p.width_magic) + q) >> p.width_shift; // q / width (full frame: the pixel id is q)
+	const int px = (int)(q - lrow * (uint32_t)width), py = (int)lrow;
+	const uint32_t ns = (uint32_t)p.rd.num_samples;
+	const f3 c0 = mk(p.rd.camera_to_world[0].x, p.rd.camera_to_world[0].y, p.rd.camera_to_world[0].z);
+	const f3 c1 = mk(p.rd.camera_to_world[1].x, p.rd.camera_to_world[1].y, p.rd.camera_to_world[1].z);
+	const f3 c2 = mk(p.rd.camera_to_world[2].x, p.rd.camera_to_world[2].y, p.rd.camera_to_world[2].z);
+	const f3 cam = mk(p.rd.camera_to_world[3].x, p.rd.camera_to_world[3].y, p.rd.camera_to_world[3].z);
+	BvhStackEntry bvh_stack[USE_BVH ? SRT_BVH_STACK_CAP + 1 : 1];
+	uint32_t n_tri = 0, n_tri_u = 0;
+	f3 nsum = mk(0.f, 0.f, 0.f), asum = mk(0.f, 0.f, 0.f);
+	float tsum = 0.f, hits = 0.f;
+	for (uint32_t sample = 0; sample < fp.feature_samples; sample++) {
+		// ---- camera ray: srt_trace_kernel CAMERA ----
+		uint32_t seed = (sample + q * ns) * p.rd.time * 5304u;
+		const float ndc_x = div_by_rcp((float)px + random_float(seed), p.f_width, p.inv_f_width);
+		const float ndc_y = div_by_rcp((float)py + random_float(seed), p.f_height, p.inv_f_height);
+		const float sx = ((2.f * ndc_x - 1.f) * p.rd.aspect_ratio) * p.rd.fov_scale;
+		const float sy = (1.f - 2.f * ndc_y) * p.rd.fov_scale;
+		const f3 org = cam;
+		const f3 dir = normalize3(mat_cols_by_vec(c0, c1, c2, cam, mk(sx, sy, -1.0f), 0.0f));
+		// ---- closest_intersection: srt_trace_kernel EXTEND (test_block), without the scan queue ----
+		float tmin = DM_INF_F;
+		int best = -1;
+		uint32_t best_tri = 0;
+		f3 inv = mk(0.f, 0.f, 0.f);
+		if (HAS_MODELS) inv = mk(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
+		auto test_block = [&](const Blk16 &b, uint32_t code, int base) {
+			const uint32_t type1 = code & 3u;
+			if (type1 == SRT_SHAPE_SPHERE + 1u) {
+				if (((code >> 2) & 7u) <= 2u) test_spheres<2>(b, org, dir, base, tmin, best);
+				else test_spheres<4>(b, org, dir, base, tmin, best);
+			} else if (type1 == SRT_SHAPE_PLANE + 1u) {
+				test_planes2(b, (code >> 2) & 7u, org, dir, base, tmin, best);
+			} else if (HAS_MODELS && type1 == SRT_SHAPE_MODEL + 1u) {
+				if (test_aabb(b.v[0], b.v[1], b.v[2], b.v[4], b.v[5], b.v[6], org, inv, tmin)) {
+					if (USE_BVH) walk_bvh<false>(reinterpret_cast<const float4 *>(p.bvh_blocks), bvh_stack, f2u(b.v[3]), org, dir, base, tmin, best, best_tri, n_tri, n_tri_u SRT_RC_ARG);
+					else test_triangles<false>(p.wtris, f2u(b.v[3]), f2u(b.v[7]), org, dir, base, tmin, best, best_tri, n_tri_u SRT_RC_ARG);
+				}
+				if (((code >> 2) & 7u) > 1u && test_aabb(b.v[8], b.v[9], b.v[10], b.v[12], b.v[13], b.v[14], org, inv, tmin)) {
+					if (USE_BVH) walk_bvh<false>(reinterpret_cast<const float4 *>(p.bvh_blocks), bvh_stack, f2u(b.v[11]), org, dir, base + 1, tmin, best, best_tri, n_tri, n_tri_u SRT_RC_ARG);
+					else test_triangles<false>(p.wtris, f2u(b.v[11]), f2u(b.v[15]), org, dir, base + 1, tmin, best, best_tri, n_tri_u SRT_RC_ARG);
+				}
+			}
+		};
+		for (int g = 0; g < p.num_runs; g++) {
+			float gh[4];
+			ld_uniform<4, 16>(reinterpret_cast<const float *>(p.runs + g), gh);
+			const uint32_t code = f2u(gh[0]);
+			const float *__restrict__ gd = p.run_data + 48 * g;
+			test_block(ld_blk16(gd), code & 255u, (int)f2u(gh[1]));
+			if ((code >> 8) & 255u) test_block(ld_blk16(gd + 16), (code >> 8) & 255u, (int)f2u(gh[2]));
+			if ((code >> 16) & 255u) test_block(ld_blk16(gd + 32), (code >> 16) & 255u, (int)f2u(gh[3]));
+		}
+		// a shape without a material counts as a miss (render.cl:404)
+		const int material = best >= 0 ? p.winners[best].material : -1;
+		if (material >= 0) {
+			f3 nrm = winner_normal<HAS_MODELS, USE_BVH>(p, best, best_tri, org + dir * tmin);
+			const bool front = dot3(nrm, dir) < 0.0f;
+			nrm = nrm * (front ? 1.0f : -1.0f);
+			nsum = nsum + nrm;
+			tsum = tsum + tmin;
+			const srt_float3 &mc = p.materials[material].color;
+			asum = asum + mk(mc.x, mc.y, mc.z);
+			hits = hits + 1.0f;
+		} else {
+			asum = asum + mk(1.f, 1.f, 1.f);
+		}
+	}
+	float4 *nd = reinterpret_cast<float4 *>(fp.normal_depth) + q;
+	float4 *ah = reinterpret_cast<float4 *>(fp.albedo_hits) + q;
+	float4 a = *nd, b = *ah;
+	a.x += nsum.x, a.y += nsum.y, a.z += nsum.z, a.w += tsum;
+	b.x += asum.x, b.y += asum.y, b.z += asum.z, b.w += hits;
+	*nd = a;
+	*ah = b;
 }
 
 // ---------------------------------------------------------------------------------
@@ -2362,7 +2514,7 @@ void srt_launch_trace(TraceParams p, bool count_triangles, int num_waves, void *
 
 void srt_launch_reduce(const ReduceParams &p, void *stream) {
 	if (p.num_pixels == 0) return;
-	hipLaunchKernelGGL(srt_reduce_kernel, dim3((p.num_pixels + 255) / 256), dim3(256), 0, (hipStream_t)stream, p);
+	hipLaunchKernelGGL(srt_reduce_kernel<false>, dim3((p.num_pixels + 255) / 256), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 void srt_launch_prepass(const PrepassParams &p, uint64_t max_tris_per_model, void *stream) {
@@ -2378,4 +2530,17 @@ void srt_launch_resolve(const ResolveParams &p, void *stream) {
 	unsigned gx = (p.num_pixels + 255) / 256;
 	if (gx > 4096) gx = 4096;
 	hipLaunchKernelGGL(srt_resolve_kernel, dim3(gx), dim3(256), 0, (hipStream_t)stream, p);
+}
+
+void srt_launch_reduce_moments(const ReduceParams &p, void *stream) {
+	if (p.num_pixels == 0) return;
+	hipLaunchKernelGGL(srt_reduce_kernel<true>, dim3((p.num_pixels + 255) / 256), dim3(256), 0, (hipStream_t)stream, p);
+}
+
+void srt_launch_features(const FeatureParams &p, void *stream) {
+	if (p.num_pixels == 0 || p.feature_samples == 0) return;
+	typedef void (*FeatureKernel)(const FeatureParams);
+	const bool models = p.tp.num_models > 0, bvh = p.tp.use_bvh != 0;
+	const FeatureKernel k = !models ? srt_features_kernel<false, false> : bvh ? srt_features_kernel<true, true> : srt_features_kernel<true, false>;
+	hipLaunchKernelGGL(k, dim3((p.num_pixels + 63u) / 64u), dim3(64), 0, (hipStream_t)stream, p);
 }

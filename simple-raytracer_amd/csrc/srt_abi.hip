@@ -504,6 +504,7 @@ size_t owned_pixels(const srt_tracer *t) { return (size_t)t->owned_rows * (size_
 int clear_canvas_impl(srt_tracer *t) {
 	// enqueue_fill_buffer with 0.0f over the whole canvas (src/tracer.cpp:98-101)
 	SRT_HIP(t, hipMemsetAsync(t->canvas, 0, t->canvas_bytes, t->stream));
+	if (t->dn_on) return srt_denoise_clear(t); // the denoiser's accumulations start again with the canvas
 	return SRT_OK;
 }
 
@@ -663,6 +664,11 @@ void srt_destroy(srt_tracer *t) {
 	t->scan_queue.release();
 	t->radiance.release();
 	t->running.release();
+	t->dn_nd.release();
+	t->dn_ah.release();
+	t->dn_mom.release();
+	t->dn_guide.release();
+	t->dn_col.release();
 	if (t->ev_t0) (void)hipEventDestroy(t->ev_t0);
 	if (t->ev_t1) (void)hipEventDestroy(t->ev_t1);
 	if (t->ev_r0) (void)hipEventDestroy(t->ev_r0);
@@ -1272,6 +1278,18 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 	rp.queue_reset = nullptr;
 	rp.argb = nullptr;
 	rp.num_steps = ticks_stopped;
+	// With the denoiser on, the reductions also collect the per-pixel moments and the render calls resolve through the filter
+	// after the feature pass (below), so no reduction resolves.
+	const bool denoise = t->dn_on;
+	auto launch_reduce = [&](uint8_t *argb) {
+		if (denoise) {
+			rp.moments = t->dn_mom.ptr;
+			srt_launch_reduce_moments(rp, t->stream);
+		} else {
+			rp.argb = argb;
+			srt_launch_reduce(rp, t->stream);
+		}
+	};
 
 	while (t->ev_k.size() < 2 * (size_t)n_batches) { // std::vector growth is the only throwing step: srt_trace's callers catch nothing
 		hipEvent_t ev = nullptr;
@@ -1289,8 +1307,7 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 		// num_samples <= 0: no paths; the reduction still applies colour = 0 / num_samples (render.cl:520-522)
 		rp.batch_samples = 0;
 		rp.first_batch = rp.last_batch = 1;
-		rp.argb = fused_argb;
-		srt_launch_reduce(rp, t->stream);
+		launch_reduce(fused_argb);
 	}
 	// Several sample batches: even and odd batches trace on two streams of their own, each into its own radiance buffer,
 	// work cursor and set of per-wave counter lines, so that the tail of a batch (its last long paths, a few lanes per wave
@@ -1400,11 +1417,15 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 		rp.first_batch = (b == 0);
 		rp.last_batch = (b == n_batches - 1);
 		rp.queue_reset = p.queue;
-		rp.argb = rp.last_batch ? fused_argb : nullptr;
-		srt_launch_reduce(rp, t->stream);
+		launch_reduce(rp.last_batch ? fused_argb : nullptr);
 		SRT_HIP(t, hipGetLastError());
 		t->queue_dirty[par] = false; // (no pixels: neither launch ran, the cursor is untouched)
 		if (overlap) SRT_HIP(t, hipEventRecord(t->ev_batch_reduced[par], t->stream));
+	}
+	if (denoise) {
+		int rc = srt_denoise_after_trace(t, p, ns);
+		if (rc == SRT_OK && fused_argb) rc = srt_denoise_filter(t, ticks_stopped, fused_argb);
+		if (rc) return rc;
 	}
 	if (timed) SRT_HIP(t, hipEventRecord(t->ev_t1, t->stream));
 	t->have_trace_ev = timed;
@@ -1622,6 +1643,7 @@ int srt_set_partition(srt_tracer *t, int rank, int world, int rows_per_block) {
 	if (!t) return SRT_ERR_INVALID;
 	if (world < 1 || rank < 0 || rank >= world || rows_per_block < 1)
 		return fail(t, SRT_ERR_INVALID, "srt_set_partition: need 0 <= rank < world and rows_per_block >= 1");
+	if (world > 1 && t->dn_on) return fail(t, SRT_ERR_STATE, "srt_set_partition: the denoiser works on the full frame only (srt_set_denoise(t, NULL) first)");
 	SRT_HIP(t, hipSetDevice(t->device));
 	SRT_HIP(t, hipStreamSynchronize(t->stream));
 	const int padded = srt_partition_padded_rows(t->height, world, rows_per_block);

@@ -90,6 +90,15 @@ struct srt_tracer {
 	bool scene_set = false;
 	bool count_tris = false;
 	int rank = 0, world = 1, rows_per_block = 8, owned_rows = 0;
+	// edge-aware denoiser (denoise.hip; srt_set_denoise). Full frame only: never on together with world > 1.
+	bool dn_on = false;
+	bool dn_filtered = false; // dn_col[dn_out] holds a filter result (srt_read_denoised)
+	srt_denoise_params dn{};
+	uint32_t dn_T = 0, dn_P = 0, dn_F = 0; // since the last clear: dispatches, sum of num_samples, feature rays per pixel
+	DevBuf<float> dn_nd, dn_ah, dn_mom;    // guide sums (float4 {normals, t}, float4 {albedos, hits}) and moments per pixel
+	DevBuf<float> dn_guide;                // filter set-up: 2 float4 per pixel {N, Z}, {A, cov}
+	DevBuf<float> dn_col;                  // two float4 images {colour, variance}, ping-pong between passes
+	int dn_out = 0;                        // the image of dn_col the last pass wrote
 	hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;
 	bool have_trace_ev = false, have_resolve_ev = false, have_kernel_ev = false;
 	std::string err;
@@ -107,6 +116,11 @@ static inline int fail(srt_tracer *t, int code, const std::string &msg) { return
 
 
 void srt_collect_release(srt_tracer *t);
+/* denoise.hip: zero the denoiser's accumulations and counts (enqueued); after a dispatch's reductions, the feature pass of
+ * that dispatch (p: its TraceParams) and the counts; the filter over the canvas into argb (device, width*height*4 bytes) */
+int srt_denoise_clear(srt_tracer *t);
+int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples);
+int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb);
 /* srt_trace whose last reduction also resolves into fused_argb (device, owned pixels x 4 bytes; NULL: plain srt_trace) */
 extern "C" int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fused_argb, uint32_t ticks_stopped);
 /* one scene for several handles: the host pass once (members[0]'s acceleration mode and hierarchy cache), the uploads of all

@@ -132,6 +132,26 @@ class Tracer {
 	/// SRT_ACCEL_BVH: models get a bounding-volume hierarchy at the next update_scene (the
 	/// reference's README.md:41 "future plan"); SRT_ACCEL_NONE (default) keeps the array-order scan
 	void set_acceleration(int mode) { check(group ? srt_group_set_acceleration(group, mode) : srt_set_acceleration(handle, mode)); }
+	/// The edge-aware denoiser (srt_set_denoise): iterations < 0 turns it off, else it is on with srt_denoise_defaults()
+	/// overridden by the arguments; render() / render_pipelined() then hand out the filtered image. Single-device tracers
+	/// only (throws on a Tracer over several devices: gathering the guide buffers is not built).
+	void set_denoise(int iterations = 5, int feature_samples = 1, float sigma_luminance = 4.0f, float sigma_normal = 128.0f,
+	                 float sigma_depth = 1.0f, float sigma_albedo = 0.1f) {
+		if (group) throw std::runtime_error("Tracer::set_denoise: single-device tracers only");
+		if (iterations < 0) {
+			check(srt_set_denoise(handle, nullptr));
+			return;
+		}
+		srt_denoise_params d;
+		check(srt_denoise_defaults(&d));
+		d.iterations = iterations;
+		d.feature_samples = feature_samples;
+		d.sigma_luminance = sigma_luminance;
+		d.sigma_normal = sigma_normal;
+		d.sigma_depth = sigma_depth;
+		d.sigma_albedo = sigma_albedo;
+		check(srt_set_denoise(handle, &d));
+	}
 	/// render() / render_pipelined() record the kernel timers' events too (off by default: they cost 10-17 us of a 150 us
 	/// frame); single-device tracers only
 	void set_kernel_timers(bool enable) {

@@ -5,7 +5,8 @@
 //
 //   srt_headless [--scene spheres|meshes|empty] [--obj f.obj]... [--stl f.stl]...
 //                [--width W --height H --spp S --bounces B --frames N --time T]
-//                [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm]
+//                [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K]
+// --denoise K: the frames go through the edge-aware denoiser with K a-trous passes (Tracer::set_denoise; one device only)
 //
 // --skybox sky.ppm: an 8-bit binary PPM (P6) as the sky, prepared the way the reference prepares assets/skybox.png
 //                   (host/skybox.hpp: four channels, rows flipped, pow(byte / 255, 2.2)); default: the synthetic sky.
@@ -99,7 +100,7 @@ int main(int argc, char **argv) {
 	int width = 256, height = 256, spp = 16, bounces = 10, frames = 1;
 	unsigned time_seed = 12345;
 	bool parse_only = false, bvh = false, pipelined = false;
-	int gpus = 1;
+	int gpus = 1, denoise = -1;
 	for (int i = 1; i < argc; i++) {
 		std::string a = argv[i];
 		auto next = [&]() -> const char * {
@@ -125,9 +126,11 @@ int main(int argc, char **argv) {
 		else if (a == "--gpus") gpus = std::atoi(next());
 		else if (a == "--pipelined") pipelined = true;
 		else if (a == "--skybox") skybox_path = next();
+		else if (a == "--denoise") denoise = std::atoi(next());
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
-			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm]\n";
+			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] "
+			             "[--denoise K]\n";
 			return 2;
 		}
 	}
@@ -193,6 +196,7 @@ int main(int argc, char **argv) {
 	// ---- tracer set-up, as src/main.cpp:114-126 ----
 	Tracer tracer(width, height, 0, gpus); // --gpus N: one Tracer over N devices (rows split, one RCCL gather per frame)
 	if (bvh) tracer.set_acceleration(SRT_ACCEL_BVH);
+	if (denoise >= 0) tracer.set_denoise(denoise);
 	tracer.options.num_samples = spp;
 	tracer.options.num_bounces = bounces;
 	tracer.options.show_normals = false;

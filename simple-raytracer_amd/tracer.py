@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "srt_group_create", "srt_group_destroy", "srt_group_last_error", "srt_group_size", "srt_group_tracer", "srt_group_set_skybox",
     "srt_group_set_acceleration", "srt_group_update_scene", "srt_group_clear_canvas", "srt_group_trace_and_gather", "srt_group_render",
     "srt_group_read_canvas", "srt_group_get_counters", "srt_render_pipelined", "srt_pipeline_flush", "srt_unpermute_device",
+    "srt_denoise_defaults", "srt_set_denoise", "srt_resolve_denoised", "srt_read_denoised", "srt_read_denoise_inputs",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -97,6 +98,26 @@ class Counters(C.Structure):
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class DenoiseParams(C.Structure):
+    """include/srt_types.h srt_denoise_params"""
+    _fields_ = [("enable", C.c_int32), ("iterations", C.c_int32), ("feature_samples", C.c_int32), ("sigma_luminance", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+assert C.sizeof(DenoiseParams) == 32
+
+
+def denoise_defaults():
+    """srt_denoise_defaults (host only, no GPU needed) as a dict."""
+    d = DenoiseParams()
+    if load_library().srt_denoise_defaults(C.byref(d)):
+        raise SrtError("srt_denoise_defaults failed")
+    return d.as_dict()
 
 
 class SrtError(RuntimeError):
@@ -203,6 +224,12 @@ def _bind(lib):
         lib.srt_group_get_counters.argtypes = [vp, C.POINTER(Counters)]
         lib.srt_render_pipelined.argtypes = [vp, vp, C.c_uint32, vp, C.POINTER(C.c_longlong)]
         lib.srt_pipeline_flush.argtypes = [vp, vp, C.POINTER(C.c_longlong)]
+    if hasattr(lib, "srt_set_denoise"):
+        lib.srt_denoise_defaults.argtypes = [C.POINTER(DenoiseParams)]
+        lib.srt_set_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
+        lib.srt_resolve_denoised.argtypes = [vp, C.c_uint32]
+        lib.srt_read_denoised.argtypes = [vp, vp]
+        lib.srt_read_denoise_inputs.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_uint32)]
     return lib
 
 
@@ -424,6 +451,40 @@ class Tracer:
         n = C.c_longlong(-1)
         self._check(self.lib.srt_pipeline_flush(self._h, _ptr(output), C.byref(n)))
         return n.value
+
+    # -- edge-aware denoiser (srt_set_denoise) --
+    def set_denoise(self, enable=True, **kw):
+        """Turn the denoiser on with srt_denoise_defaults() overridden by kw (iterations, feature_samples, sigma_luminance,
+        sigma_normal, sigma_depth, sigma_albedo), or off with enable=False."""
+        if not enable:
+            self._check(self.lib.srt_set_denoise(self._h, None))
+            return
+        d = DenoiseParams()
+        self._check(self.lib.srt_denoise_defaults(C.byref(d)))
+        for k, v in kw.items():
+            if k not in d.as_dict() or k == "enable":
+                raise TypeError(f"set_denoise: unknown parameter {k}")
+            setattr(d, k, v)
+        self._check(self.lib.srt_set_denoise(self._h, C.byref(d)))
+
+    def resolve_denoised(self, ticks_stopped):
+        """The filter over the current canvas into the handle's ARGB image (read_argb); asynchronous."""
+        self._check(self.lib.srt_resolve_denoised(self._h, ticks_stopped))
+
+    def read_denoised(self):
+        """(height, width, 4) float32: the last filter result before tonemapping (r, g, b, variance)."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self.lib.srt_read_denoised(self._h, _ptr(out)))
+        return out
+
+    def read_denoise_inputs(self):
+        """dict: normal_depth (h, w, 4), albedo_hits (h, w, 4), moments (h, w), T, P."""
+        nd = np.zeros((self.height, self.width, 4), np.float32)
+        ah = np.zeros((self.height, self.width, 4), np.float32)
+        m = np.zeros((self.height, self.width), np.float32)
+        counts = (C.c_uint32 * 2)()
+        self._check(self.lib.srt_read_denoise_inputs(self._h, _ptr(nd), _ptr(ah), _ptr(m), counts))
+        return {"normal_depth": nd, "albedo_hits": ah, "moments": m, "T": int(counts[0]), "P": int(counts[1])}
 
     def set_partition(self, rank, world, rows_per_block=8):
         self._check(self.lib.srt_set_partition(self._h, rank, world, rows_per_block))

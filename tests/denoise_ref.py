@@ -1,0 +1,138 @@
+"""numpy restatement of the denoiser's filter (simple-raytracer_amd/csrc/denoise.hip): set-up, K a-trous passes, tonemap.
+
+Inputs are what Tracer.read_canvas() and Tracer.read_denoise_inputs() return plus the feature rays per pixel F (the sum over
+dispatches of min(feature_samples, num_samples)). The set-up and the tonemap use float32 in the kernel's operation order,
+so K = 0 gives srt_resolve_kernel's bytes exactly; the passes use float64 (the kernel's fast exp / log are not
+reproduced: the comparison is within a tolerance).
+"""
+import numpy as np
+
+F32 = np.float32
+H5 = np.array([1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16])
+DEFAULTS = dict(iterations=5, sigma_luminance=4.0, sigma_normal=128.0, sigma_depth=1.0, sigma_albedo=0.1)
+
+
+def lum(c):
+    """0.2126 r + 0.7152 g + 0.0722 b in float32, in that order (no fused multiply-add)."""
+    c = np.asarray(c, F32)
+    return (F32(0.2126) * c[..., 0] + F32(0.7152) * c[..., 1]) + F32(0.0722) * c[..., 2]
+
+
+def _aces1(x):
+    a, b, c, d, e = F32(2.51), F32(0.03), F32(2.43), F32(0.59), F32(0.14)
+    with np.errstate(all="ignore"):
+        v = (x * (x * a + b)) / (x * (x * c + d) + e)
+        v = np.where(v < F32(0), F32(0), v)  # dm_max(v, 0): a NaN stays
+        v = np.where(F32(1) < v, F32(1), v)  # dm_min(v, 1)
+    return v.astype(F32)
+
+
+def _to_uchar(v):
+    with np.errstate(all="ignore"):
+        ok = v == v
+        return np.where(ok, np.trunc(np.where(ok, v, 0)).astype(np.int64) & 255, 0).astype(np.uint8)
+
+
+def tonemap(rgb):
+    """srt_resolve_kernel's bytes A, R, G, B of an HDR image that is already divided by the ticks: (h, w, 4) uint8."""
+    rgb = np.asarray(rgb, F32)
+    with np.errstate(all="ignore"):
+        ch = [_to_uchar(np.sqrt(_aces1(rgb[..., k])) * F32(255.0)) for k in range(3)]
+    out = np.empty(rgb.shape[:-1] + (4,), np.uint8)
+    out[..., 0] = 255
+    out[..., 1], out[..., 2], out[..., 3] = ch
+    return out
+
+
+def setup(canvas, normal_depth, albedo_hits, moments, T, P, F, ticks):
+    """-> colour (h, w, 3), variance (h, w), N (h, w, 3), Z (h, w), A (h, w, 3), cov (h, w): float32, as the set-up kernel."""
+    canvas, nd, ah = (np.asarray(a, F32) for a in (canvas, normal_depth, albedo_hits))
+    moments = np.asarray(moments, F32)
+    fT, fP, fF, ft = F32(T), F32(P), F32(F), F32(ticks)
+    with np.errstate(all="ignore"):
+        c0 = canvas[..., :3] / ft
+        l = lum(canvas[..., :3] / fT)
+        v = moments / fT - l * l
+        v = np.where(v > F32(0), v, F32(0)) / fP
+        v = np.where(np.isfinite(v), v, F32(0)).astype(F32)
+        hits = ah[..., 3]
+        n = nd[..., :3]
+        ln = np.sqrt(n[..., 0] * n[..., 0] + n[..., 1] * n[..., 1] + n[..., 2] * n[..., 2])
+        N = np.where(((hits > 0) & (ln > 0))[..., None], n / ln[..., None], F32(0)).astype(F32)
+        Z = np.where(hits > 0, nd[..., 3] / hits, F32(0)).astype(F32)
+        A = (ah[..., :3] / fF).astype(F32)
+        cov = (hits / fF).astype(F32)
+    return c0.astype(F32), v, N, Z, A, cov
+
+
+def _prefilter(V):
+    """3x3 [1/4, 1/2, 1/4]^2 over in-image taps, renormalised by the weights of the taps that exist."""
+    h, w = V.shape
+    k = np.array([0.25, 0.5, 0.25])
+    acc = np.zeros((h, w))
+    wsum = np.zeros((h, w))
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            ys, xs = np.arange(h) + dy, np.arange(w) + dx
+            vy, vx = (ys >= 0) & (ys < h), (xs >= 0) & (xs < w)
+            m = vy[:, None] & vx[None, :]
+            src = V[np.clip(ys, 0, h - 1)][:, np.clip(xs, 0, w - 1)]
+            kk = k[dy + 1] * k[dx + 1]
+            acc += np.where(m, kk * src, 0.0)
+            wsum += np.where(m, kk, 0.0)
+    return acc / wsum
+
+
+def atrous_pass(c, V, N, Z, A, cov, step, sigma_luminance, sigma_normal, sigma_depth, sigma_albedo):
+    """One a-trous pass of step `step` -> (colour, variance) (float64)."""
+    c = np.asarray(c, np.float64)
+    V = np.asarray(V, np.float64)
+    N, Z, A, cov = (np.asarray(a, np.float64) for a in (N, Z, A, cov))
+    h, w = V.shape
+    finite = np.all(np.isfinite(c), axis=-1)
+    valid = (cov > 0) & finite  # a pixel that takes part: as a filtered centre and as a tap
+    cz = np.where(finite[..., None], c, 0.0)
+    l = 0.2126 * cz[..., 0] + 0.7152 * cz[..., 1] + 0.0722 * cz[..., 2]
+    gv = _prefilter(V)
+    inv_dl = 1.0 / (sigma_luminance * np.sqrt(gv) + 1e-10)
+    inv_dz = 1.0 / (sigma_depth * Z * step + 1e-6)
+    sw = np.zeros((h, w))
+    sv = np.zeros((h, w))
+    sc = np.zeros((h, w, 3))
+    for dy in range(-2, 3):
+        for dx in range(-2, 3):
+            ys, xs = np.arange(h) + dy * step, np.arange(w) + dx * step
+            vy, vx = (ys >= 0) & (ys < h), (xs >= 0) & (xs < w)
+            iy, ix = np.clip(ys, 0, h - 1), np.clip(xs, 0, w - 1)
+            take = vy[:, None] & vx[None, :] & valid[iy][:, ix]
+            Nq, Zq, Aq, lq = N[iy][:, ix], Z[iy][:, ix], A[iy][:, ix], l[iy][:, ix]
+            d = np.sum(N * Nq, axis=-1)
+            take &= d > 0
+            with np.errstate(all="ignore"):
+                wn = np.where(d > 0, np.power(np.where(d > 0, d, 1.0), sigma_normal), 0.0)
+                e = np.abs(Z - Zq) * inv_dz + np.sum((A - Aq) ** 2, axis=-1) / (sigma_albedo * sigma_albedo) + np.abs(l - lq) * inv_dl
+                wgt = np.where(take, H5[dx + 2] * H5[dy + 2] * wn * np.exp(-e), 0.0)
+            sw += wgt
+            sv += wgt * wgt * V[iy][:, ix]
+            sc += wgt[..., None] * cz[iy][:, ix]
+    filt = valid & (sw > 0)
+    with np.errstate(all="ignore"):
+        c_out = np.where(filt[..., None], sc / np.where(sw > 0, sw, 1.0)[..., None], c)
+        V_out = np.where(filt, sv / np.where(sw > 0, sw * sw, 1.0), V)
+    return c_out, V_out
+
+
+def denoise(canvas, normal_depth, albedo_hits, moments, T, P, F, ticks, iterations=5, sigma_luminance=4.0, sigma_normal=128.0,
+            sigma_depth=1.0, sigma_albedo=0.1):
+    """-> (hdr (h, w, 4) float32: colour and variance, argb (h, w, 4) uint8)."""
+    c, V, N, Z, A, cov = setup(canvas, normal_depth, albedo_hits, moments, T, P, F, ticks)
+    c64, V64 = c, V
+    for i in range(iterations):
+        c64, V64 = atrous_pass(c64, V64, N, Z, A, cov, 1 << i, sigma_luminance, sigma_normal, sigma_depth, sigma_albedo)
+    hdr = np.concatenate([np.asarray(c64, F32), np.asarray(V64, F32)[..., None]], axis=-1)
+    return hdr, tonemap(hdr[..., :3])
+
+
+def psnr(a, b, peak=1.0):
+    mse = float(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2))
+    return float("inf") if mse == 0 else 10.0 * np.log10(peak * peak / mse)
