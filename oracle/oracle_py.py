@@ -127,6 +127,35 @@ class Oracle:
                                C.c_int(sky.shape[0]), _p(pixel_ids), _p(samples), C.c_int(len(pixel_ids)), _p(out))
         return out
 
+    def primary_hits(self, rd, sd, shapes, tris, mats, pixel_ids, samples):
+        """The camera rays of (pixel, sample) pairs and their closest hits (oracle only) -> dict of numpy arrays:
+        dir (n, 3) unit direction, t (n,) tmin (inf: nothing hit), normal (n, 3) front-facing (0 without a shaded hit),
+        material (n,) int (-1: sky, or a shape without a material). The origin is camera_to_world[3]."""
+        pixel_ids = np.ascontiguousarray(pixel_ids, np.int32)
+        samples = np.ascontiguousarray(samples, np.int32)
+        out = np.zeros((len(pixel_ids), 8), np.float32)
+        shapes, tris, mats, rd, sd = _scene_arrays(shapes, tris, mats, rd, sd)
+        self.lib.orc_primary_hits.restype = None
+        self.lib.orc_primary_hits(_p(rd), _p(sd), _p(shapes), _p(tris), _p(mats), _p(pixel_ids), _p(samples),
+                                  C.c_int(len(pixel_ids)), _p(out))
+        return {"dir": out[:, :3], "t": out[:, 3], "normal": out[:, 4:7], "material": out[:, 7].astype(np.int64)}
+
+    def features(self, rd, sd, shapes, tris, mats, feature_samples, normal_depth=None, albedo_hits=None, nthreads=0):
+        """One dispatch of the denoiser's feature pass (oracle only): adds its sums into normal_depth and albedo_hits
+        ((h, w, 4) float32, zeros when None) in place and returns both."""
+        shapes, tris, mats, rd, sd = _scene_arrays(shapes, tris, mats, rd, sd)
+        w, h = int(rd["width"]), int(rd["height"])
+        if normal_depth is None:
+            normal_depth = np.zeros((h, w, 4), np.float32)
+        if albedo_hits is None:
+            albedo_hits = np.zeros((h, w, 4), np.float32)
+        for a in (normal_depth, albedo_hits):
+            assert a.dtype == np.float32 and a.shape == (h, w, 4) and a.flags.c_contiguous
+        self.lib.orc_features.restype = None
+        self.lib.orc_features(_p(rd), _p(sd), _p(shapes), _p(tris), _p(mats), C.c_int(feature_samples), _p(normal_depth),
+                              _p(albedo_hits), C.c_int(nthreads))
+        return normal_depth, albedo_hits
+
     # ---- function-level known-answer entry points ------------------------------
     def random_floats(self, seed, n):
         s = C.c_uint32(seed)

@@ -222,6 +222,7 @@ typedef struct {
 typedef struct {
 	v3 position, normal;
 	int front;
+	float t; /* tmin: the distance along the (unit) ray to the closest hit, INFINITY when nothing was hit */
 } hit_t;
 
 /* render.cl:293-378 */
@@ -293,6 +294,7 @@ static int closest_intersection(const scene_t *scene, v3 org, v3 dir, hit_t *ray
 		}
 	}
 	/* render.cl:369 `tmin == FLT_MAX` never fires (tmin starts at INFINITY) */
+	rayhit->t = tmin;
 	rayhit->front = vdot(rayhit->normal, dir) < 0.0f;
 	rayhit->normal = vscale(rayhit->normal, rayhit->front ? 1.0f : -1.0f);
 	return closest;
@@ -397,19 +399,26 @@ static v3 trace(const srt_render_data *render, const scene_t *scene, v3 org, v3 
 	return color;
 }
 
+/* render.cl:489-516: the camera ray of (pixel id, sample) -> org, unit dir; returns the seed after the two jitter draws */
+static inline uint32_t camera_ray(const srt_render_data *data, uint32_t id, uint32_t sample, v3 *org, v3 *dir) {
+	int px = (int)(id % (uint32_t)data->width), py = (int)(id / (uint32_t)data->width);
+	uint32_t seed = (sample + id * (uint32_t)data->num_samples) * data->time * 5304u;
+	float ndc_x = ((float)px + orc_random_float(&seed)) / (float)data->width;
+	float ndc_y = ((float)py + orc_random_float(&seed)) / (float)data->height;
+	float sx = ((2.f * ndc_x - 1.f) * data->aspect_ratio) * data->fov_scale;
+	float sy = (1.f - 2.f * ndc_y) * data->fov_scale;
+	*org = V(data->camera_to_world[3].x, data->camera_to_world[3].y, data->camera_to_world[3].z);
+	*dir = vnormalize(mat_by_vec(data->camera_to_world, V(sx, sy, -1.0f), 0.0f));
+	return seed;
+}
+
 /* render.cl:483-523 for one pixel; returns the per-dispatch colour (already /num_samples) */
 static v3 render_pixel(const srt_render_data *data, const scene_t *scene, int px, int py, uint64_t *ctr) {
 	uint32_t id = (uint32_t)px + (uint32_t)py * (uint32_t)data->width;
-	float wx = (float)px, wy = (float)py;
 	v3 color = V(0.f, 0.f, 0.f);
 	for (int sample = 0; sample < data->num_samples; sample++) {
-		uint32_t seed = ((uint32_t)sample + id * (uint32_t)data->num_samples) * data->time * 5304u;
-		float ndc_x = (wx + orc_random_float(&seed)) / (float)data->width;
-		float ndc_y = (wy + orc_random_float(&seed)) / (float)data->height;
-		float sx = ((2.f * ndc_x - 1.f) * data->aspect_ratio) * data->fov_scale;
-		float sy = (1.f - 2.f * ndc_y) * data->fov_scale;
-		v3 org = V(data->camera_to_world[3].x, data->camera_to_world[3].y, data->camera_to_world[3].z);
-		v3 dir = vnormalize(mat_by_vec(data->camera_to_world, V(sx, sy, -1.0f), 0.0f));
+		v3 org, dir;
+		uint32_t seed = camera_ray(data, id, (uint32_t)sample, &org, &dir);
 		ctr[ORC_C_PATHS]++;
 		color = vadd(color, trace(data, scene, org, dir, seed, ctr));
 	}
@@ -477,19 +486,80 @@ void orc_trace_paths(const srt_render_data *data, const srt_scene_data *scene_da
 	uint64_t ctr[ORC_C_COUNT];
 	memset(ctr, 0, sizeof ctr);
 	for (int k = 0; k < n; k++) {
-		uint32_t id = (uint32_t)pixel_ids[k];
-		int px = (int)(id % (uint32_t)data->width), py = (int)(id / (uint32_t)data->width);
-		uint32_t seed = ((uint32_t)samples[k] + id * (uint32_t)data->num_samples) * data->time * 5304u;
-		float ndc_x = ((float)px + orc_random_float(&seed)) / (float)data->width;
-		float ndc_y = ((float)py + orc_random_float(&seed)) / (float)data->height;
-		float sx = ((2.f * ndc_x - 1.f) * data->aspect_ratio) * data->fov_scale;
-		float sy = (1.f - 2.f * ndc_y) * data->fov_scale;
-		v3 org = V(data->camera_to_world[3].x, data->camera_to_world[3].y, data->camera_to_world[3].z);
-		v3 dir = vnormalize(mat_by_vec(data->camera_to_world, V(sx, sy, -1.0f), 0.0f));
+		v3 org, dir;
+		uint32_t seed = camera_ray(data, (uint32_t)pixel_ids[k], (uint32_t)samples[k], &org, &dir);
 		v3 c = trace(data, &scene, org, dir, seed, ctr);
 		out_rgb[3 * k + 0] = c.x;
 		out_rgb[3 * k + 1] = c.y;
 		out_rgb[3 * k + 2] = c.z;
+	}
+}
+
+/* The primary hit of single (pixel, sample) camera rays, for the denoiser's guide buffers. out: 8 floats per ray:
+ * the unit direction, tmin, the front-facing normal (0 without a hit) and the material index (-1: sky, or a shape
+ * without a material -- render.cl:404 shades neither). */
+void orc_primary_hits(const srt_render_data *data, const srt_scene_data *scene_data, const srt_shape *shapes,
+                      const srt_triangle *triangles, const srt_material *materials, const int32_t *pixel_ids,
+                      const int32_t *samples, int n, float *out) {
+	scene_t scene = {scene_data, shapes, triangles, materials, NULL, 0, 0};
+	uint64_t ctr[ORC_C_COUNT];
+	memset(ctr, 0, sizeof ctr);
+	for (int k = 0; k < n; k++) {
+		v3 org, dir;
+		hit_t hit;
+		memset(&hit, 0, sizeof hit);
+		(void)camera_ray(data, (uint32_t)pixel_ids[k], (uint32_t)samples[k], &org, &dir);
+		int material = closest_intersection(&scene, org, dir, &hit, ctr);
+		v3 nrm = material >= 0 ? hit.normal : V(0.f, 0.f, 0.f);
+		float *o = out + 8 * (size_t)k;
+		o[0] = dir.x, o[1] = dir.y, o[2] = dir.z, o[3] = hit.t;
+		o[4] = nrm.x, o[5] = nrm.y, o[6] = nrm.z, o[7] = (float)material;
+	}
+}
+
+/* One dispatch's guide sums, as the denoiser's feature pass adds them (kernels.hip srt_features_kernel): for each pixel
+ * its samples 0 .. min(feature_samples, max(num_samples, 0)) - 1 in order, float32 partial sums of {front-facing normal,
+ * tmin} and {material colour, 1} over the hits and {1, 1, 1, 0} over the misses, then added into normal_depth and
+ * albedo_hits ((h, w, 4) float32 each). */
+void orc_features(const srt_render_data *data, const srt_scene_data *scene_data, const srt_shape *shapes,
+                  const srt_triangle *triangles, const srt_material *materials, int feature_samples, float *normal_depth,
+                  float *albedo_hits, int nthreads) {
+	scene_t scene = {scene_data, shapes, triangles, materials, NULL, 0, 0};
+	const int ns = data->num_samples > 0 ? data->num_samples : 0;
+	const int fs = feature_samples < ns ? feature_samples : ns;
+	const int npix = data->width * data->height;
+#ifdef _OPENMP
+	if (nthreads > 0) omp_set_num_threads(nthreads);
+#else
+	(void)nthreads;
+#endif
+#pragma omp parallel
+	{
+		uint64_t ctr[ORC_C_COUNT];
+		memset(ctr, 0, sizeof ctr);
+#pragma omp for schedule(dynamic, 64)
+		for (int id = 0; id < npix; id++) {
+			v3 nsum = V(0.f, 0.f, 0.f), asum = V(0.f, 0.f, 0.f);
+			float tsum = 0.f, hits = 0.f;
+			for (int sample = 0; sample < fs; sample++) {
+				v3 org, dir;
+				hit_t hit;
+				memset(&hit, 0, sizeof hit);
+				(void)camera_ray(data, (uint32_t)id, (uint32_t)sample, &org, &dir);
+				int material = closest_intersection(&scene, org, dir, &hit, ctr);
+				if (material >= 0) {
+					nsum = vadd(nsum, hit.normal);
+					tsum = tsum + hit.t;
+					asum = vadd(asum, f3(&scene.materials[material].color));
+					hits = hits + 1.0f;
+				} else {
+					asum = vadd(asum, V(1.f, 1.f, 1.f));
+				}
+			}
+			float *nd = normal_depth + 4 * (size_t)id, *ah = albedo_hits + 4 * (size_t)id;
+			nd[0] += nsum.x, nd[1] += nsum.y, nd[2] += nsum.z, nd[3] += tsum;
+			ah[0] += asum.x, ah[1] += asum.y, ah[2] += asum.z, ah[3] += hits;
+		}
 	}
 }
 

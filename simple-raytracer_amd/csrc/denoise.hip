@@ -21,6 +21,8 @@
 // exp / log instructions: this stage is outside the parity contract (DESIGN.md "Denoiser").
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -37,7 +39,7 @@ struct FilterParams {
 	int32_t width, height;
 	uint32_t num_pixels;
 	int32_t step;
-	float sigma_l, sigma_n, sigma_z, inv_sigma_a2; // inv_sigma_a2 = 1 / sigma_albedo^2
+	float sigma_l, sigma_n, sigma_z, inv_sigma_a2; // inv_sigma_a2 = min(1 / sigma_albedo^2, FLT_MAX)
 	const float4 *guide;                           // 2 float4 per pixel: {N, Z}, {A, cov}
 	const float4 *in;                              // {colour, variance}
 	float4 *out;
@@ -217,7 +219,9 @@ int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
 	fp.sigma_l = t->dn.sigma_luminance;
 	fp.sigma_n = t->dn.sigma_normal;
 	fp.sigma_z = t->dn.sigma_depth;
-	fp.inv_sigma_a2 = 1.0f / (t->dn.sigma_albedo * t->dn.sigma_albedo);
+	// in double, clamped to FLT_MAX: in float the square underflows for sigma_albedo below ~5.4e-20 and the inverse is
+	// inf, which turns every tap's 0 * inf albedo term into NaN (no pixel filtered); clamped, equal albedos still cost 0
+	fp.inv_sigma_a2 = (float)std::min(1.0 / ((double)t->dn.sigma_albedo * (double)t->dn.sigma_albedo), (double)FLT_MAX);
 	fp.guide = guide;
 	const dim3 grid((unsigned)((t->width + 15) / 16), (unsigned)((t->height + 15) / 16));
 	for (int k = 0; k < K; k++) {

@@ -3,7 +3,12 @@
 Inputs are what Tracer.read_canvas() and Tracer.read_denoise_inputs() return plus the feature rays per pixel F (the sum over
 dispatches of min(feature_samples, num_samples)). The set-up and the tonemap use float32 in the kernel's operation order,
 so K = 0 gives srt_resolve_kernel's bytes exactly; the passes use float64 (the kernel's fast exp / log are not
-reproduced: the comparison is within a tolerance).
+reproduced: the comparison is within a tolerance). Two operands of a pass's weights are float32, in the kernel's order:
+the normal dot product N.Nq, which is then the kernel's own value (N is the set-up's float32 normal), and the luminances,
+taken from the pass's colour rounded to float32 (in the first pass the kernel's own colour; after it, the float32
+rounding of the float64 colour, not the kernel's value). At the small end of sigma_normal and sigma_luminance the weight
+is a step in them (max(0, d)^sn -> d > 0; exp(-1e10 |lp - lq|) -> lp == lq), and near-perpendicular normals or
+near-equal colours put them within float32 rounding of the step, where a float64 restatement decides a tap the other way.
 """
 import numpy as np
 
@@ -16,6 +21,19 @@ def lum(c):
     """0.2126 r + 0.7152 g + 0.0722 b in float32, in that order (no fused multiply-add)."""
     c = np.asarray(c, F32)
     return (F32(0.2126) * c[..., 0] + F32(0.7152) * c[..., 1]) + F32(0.0722) * c[..., 2]
+
+
+def moments(radiance, acc=None):
+    """One dispatch of the moments reduction (kernels.hip srt_reduce_kernel<true>) in float32: radiance (pixels, n, 3) of the
+    dispatch's n samples, s2 = s2 + lum(r_k)^2 in sample order, then acc + s2 / n -> (pixels,)."""
+    r = np.asarray(radiance, F32)
+    s2 = np.zeros(r.shape[0], F32)
+    for k in range(r.shape[1]):
+        l = lum(r[:, k])
+        s2 = s2 + l * l
+    with np.errstate(all="ignore"):
+        m = s2 / F32(r.shape[1])
+    return m if acc is None else (np.asarray(acc, F32) + m).astype(F32)
 
 
 def _aces1(x):
@@ -87,12 +105,14 @@ def atrous_pass(c, V, N, Z, A, cov, step, sigma_luminance, sigma_normal, sigma_d
     """One a-trous pass of step `step` -> (colour, variance) (float64)."""
     c = np.asarray(c, np.float64)
     V = np.asarray(V, np.float64)
-    N, Z, A, cov = (np.asarray(a, np.float64) for a in (N, Z, A, cov))
+    N32 = np.asarray(N, F32)
+    Z, A, cov = (np.asarray(a, np.float64) for a in (Z, A, cov))
     h, w = V.shape
     finite = np.all(np.isfinite(c), axis=-1)
     valid = (cov > 0) & finite  # a pixel that takes part: as a filtered centre and as a tap
     cz = np.where(finite[..., None], c, 0.0)
-    l = 0.2126 * cz[..., 0] + 0.7152 * cz[..., 1] + 0.0722 * cz[..., 2]
+    with np.errstate(all="ignore"):
+        l = lum(cz.astype(F32)).astype(np.float64)  # float32 colour and arithmetic, the kernel's order
     gv = _prefilter(V)
     inv_dl = 1.0 / (sigma_luminance * np.sqrt(gv) + 1e-10)
     inv_dz = 1.0 / (sigma_depth * Z * step + 1e-6)
@@ -105,8 +125,8 @@ def atrous_pass(c, V, N, Z, A, cov, step, sigma_luminance, sigma_normal, sigma_d
             vy, vx = (ys >= 0) & (ys < h), (xs >= 0) & (xs < w)
             iy, ix = np.clip(ys, 0, h - 1), np.clip(xs, 0, w - 1)
             take = vy[:, None] & vx[None, :] & valid[iy][:, ix]
-            Nq, Zq, Aq, lq = N[iy][:, ix], Z[iy][:, ix], A[iy][:, ix], l[iy][:, ix]
-            d = np.sum(N * Nq, axis=-1)
+            Nq, Zq, Aq, lq = N32[iy][:, ix], Z[iy][:, ix], A[iy][:, ix], l[iy][:, ix]
+            d = ((N32[..., 0] * Nq[..., 0] + N32[..., 1] * Nq[..., 1]) + N32[..., 2] * Nq[..., 2]).astype(np.float64)  # float32, the kernel's order
             take &= d > 0
             with np.errstate(all="ignore"):
                 wn = np.where(d > 0, np.power(np.where(d > 0, d, 1.0), sigma_normal), 0.0)
@@ -122,15 +142,23 @@ def atrous_pass(c, V, N, Z, A, cov, step, sigma_luminance, sigma_normal, sigma_d
     return c_out, V_out
 
 
-def denoise(canvas, normal_depth, albedo_hits, moments, T, P, F, ticks, iterations=5, sigma_luminance=4.0, sigma_normal=128.0,
-            sigma_depth=1.0, sigma_albedo=0.1):
-    """-> (hdr (h, w, 4) float32: colour and variance, argb (h, w, 4) uint8)."""
+def denoise_steps(canvas, normal_depth, albedo_hits, moments, T, P, F, ticks, iterations=5, sigma_luminance=4.0, sigma_normal=128.0,
+                  sigma_depth=1.0, sigma_albedo=0.1):
+    """denoise() for K = 0, 1, ..., iterations passes: a list of its results, one pass after the other."""
     c, V, N, Z, A, cov = setup(canvas, normal_depth, albedo_hits, moments, T, P, F, ticks)
     c64, V64 = c, V
-    for i in range(iterations):
-        c64, V64 = atrous_pass(c64, V64, N, Z, A, cov, 1 << i, sigma_luminance, sigma_normal, sigma_depth, sigma_albedo)
-    hdr = np.concatenate([np.asarray(c64, F32), np.asarray(V64, F32)[..., None]], axis=-1)
-    return hdr, tonemap(hdr[..., :3])
+    out = []
+    for i in range(iterations + 1):
+        if i:
+            c64, V64 = atrous_pass(c64, V64, N, Z, A, cov, 1 << (i - 1), sigma_luminance, sigma_normal, sigma_depth, sigma_albedo)
+        hdr = np.concatenate([np.asarray(c64, F32), np.asarray(V64, F32)[..., None]], axis=-1)
+        out.append((hdr, tonemap(hdr[..., :3])))
+    return out
+
+
+def denoise(canvas, normal_depth, albedo_hits, moments, T, P, F, ticks, iterations=5, **sigmas):
+    """-> (hdr (h, w, 4) float32: colour and variance, argb (h, w, 4) uint8)."""
+    return denoise_steps(canvas, normal_depth, albedo_hits, moments, T, P, F, ticks, iterations, **sigmas)[-1]
 
 
 def psnr(a, b, peak=1.0):

@@ -139,10 +139,89 @@ def test_filter_matches_numpy(T, sky, name):
         argb = t.render(i + 1).reshape(64, 96, 4)
     inp = t.read_denoise_inputs()
     got = t.read_denoised()
-    hdr, want_argb = D.denoise(t.read_canvas(), inp["normal_depth"], inp["albedo_hits"], inp["moments"], inp["T"], inp["P"], 4, 2)
+    F = 2 * min(2, 4)  # two dispatches of min(feature_samples, num_samples) feature rays
+    hdr, want_argb = D.denoise(t.read_canvas(), inp["normal_depth"], inp["albedo_hits"], inp["moments"], inp["T"], inp["P"], F, 2)
     np.testing.assert_allclose(got[..., :3], hdr[..., :3], rtol=1e-4, atol=1e-6)
     np.testing.assert_allclose(got[..., 3], hdr[..., 3], rtol=1e-3, atol=1e-9)
     assert np.abs(argb.astype(int) - want_argb.astype(int)).max() <= 1
+    t.close()
+
+
+FILTER_FRAMES = [(96, 64), (37, 29), (17, 16), (1, 33), (33, 1), (130, 5)]  # tiles of 16x16: whole, ragged, one column or row
+FILTER_KS = (1, 2, 3, 4, 5, 8)  # odd and even K end in either ping-pong buffer; 8: steps up to 128, beyond every frame here
+FILTER_SIGMAS = {
+    "default": {},
+    "tight": dict(sigma_luminance=0.5, sigma_normal=16.0, sigma_depth=0.1, sigma_albedo=0.5),
+    "loose": dict(sigma_luminance=64.0, sigma_normal=1.0, sigma_depth=10.0, sigma_albedo=2.0),
+    # the small end of each sigma; sigma_albedo = 1e-20: 1 / sigma^2 is beyond float's range (the library clamps it)
+    "small_l": dict(sigma_luminance=1e-20),
+    "small_n": dict(sigma_normal=1e-20),
+    "small_z": dict(sigma_depth=1e-20),
+    "small_a": dict(sigma_albedo=1e-20),
+}
+FILTER_DISPATCHES = ((4, 900), (1, 4096), (3, 901))  # (num_samples, time)
+
+
+def check_filter(got_hdr, got_argb, want_hdr, want_argb, what):
+    np.testing.assert_allclose(got_hdr[..., :3], want_hdr[..., :3], rtol=1e-4, atol=1e-6, err_msg=what)
+    np.testing.assert_allclose(got_hdr[..., 3], want_hdr[..., 3], rtol=1e-3, atol=1e-9, err_msg=what)
+    assert np.abs(got_argb.astype(int) - want_argb.astype(int)).max() <= 1, what
+
+
+def filter_against_numpy(t, sigmas, fs, k_render, what):
+    """Dispatches through render() with k_render passes, then every K of FILTER_KS by srt_set_denoise (the same
+    feature_samples: the sums stay) and srt_resolve_denoised with a ticks value that is not the dispatch count."""
+    h, w = t.height, t.width
+    F = 0
+    for i, (ns, tm) in enumerate(FILTER_DISPATCHES):
+        t.options["num_samples"] = ns
+        t.options["time"] = tm
+        argb = t.render(i + 1).reshape(h, w, 4)
+        F += min(fs, ns)
+    inp = t.read_denoise_inputs()
+    canvas = t.read_canvas()
+    args = (canvas, inp["normal_depth"], inp["albedo_hits"], inp["moments"], inp["T"], inp["P"], F)
+    steps = D.denoise_steps(*args, len(FILTER_DISPATCHES), k_render, **sigmas)
+    check_filter(t.read_denoised(), argb, *steps[k_render], f"{what} render K={k_render}")
+    ticks = 7
+    steps = D.denoise_steps(*args, ticks, max(FILTER_KS), **sigmas)
+    for K in FILTER_KS:
+        t.set_denoise(feature_samples=fs, iterations=K, **sigmas)
+        t.resolve_denoised(ticks)
+        t.synchronize()
+        check_filter(t.read_denoised(), t.read_argb(), *steps[K], f"{what} K={K}")
+    assert t.read_denoise_inputs()["T"] == len(FILTER_DISPATCHES)
+    return canvas
+
+
+@pytest.mark.parametrize("sig", sorted(FILTER_SIGMAS))
+@pytest.mark.parametrize("w,h", FILTER_FRAMES)
+def test_filter_matrix_matches_numpy(T, sky, w, h, sig):
+    """The filter against numpy over frame shapes, K and sigma sets, with F counted from the dispatches."""
+    k_render = FILTER_KS[(FILTER_FRAMES.index((w, h)) + sorted(FILTER_SIGMAS).index(sig)) % len(FILTER_KS)]
+    sigmas = FILTER_SIGMAS[sig]
+    t = make(T, sky, "mixed", w, h, accel=1, denoise=dict(feature_samples=2, iterations=k_render, **sigmas))
+    filter_against_numpy(t, sigmas, 2, k_render, f"{w}x{h} {sig}")
+    t.close()
+
+
+def test_filter_skips_non_finite_pixels(T, sky):
+    """A material with a NaN and an inf colour: NaN and inf pixels are neither filtered nor taps, on both sides."""
+    shapes, tris, mats = S.sphere_scene()
+    mats = mats.copy()
+    mats["color"][2] = (np.nan, 0.5, np.inf)
+    w, h = 48, 40
+    t = T.Tracer(w, h)
+    t.set_skybox(sky)
+    t.set_acceleration(1)
+    t.options = R.render_data(w, h, 4, 10, camera_to_world=S.default_camera(), time=1)
+    t.scene_data = R.scene_data(len(shapes))
+    t.update_scene(shapes, tris, mats)
+    t.clear_canvas()
+    t.set_denoise(feature_samples=3, iterations=4)
+    canvas = filter_against_numpy(t, {}, 3, 4, "non-finite")
+    bad = ~np.all(np.isfinite(canvas[..., :3]), axis=-1)
+    assert bad.any() and not bad.all()
     t.close()
 
 

@@ -1,0 +1,178 @@
+"""GPU: the denoiser's inputs against independent references, bit for bit. The guide buffers (srt_features_kernel) against
+the CPU oracle's orc_features over the same dispatches; the moments (srt_reduce_kernel<true>) against the oracle's per-sample
+radiance (orc_trace_paths) reduced in float32 by denoise_ref.moments; the handle's counts and srt_set_denoise's clearing
+rule."""
+import numpy as np
+import pytest
+
+import cases as C
+import denoise_ref as D
+from conftest import bits_equal
+from simple_raytracer_amd import records as R, scenes as S
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def T():
+    from simple_raytracer_amd import build, tracer
+    build.build_hip()
+    return tracer
+
+
+def scene(name):
+    """-> shapes, tris, mats, camera"""
+    cam = S.default_camera()
+    if name == "spheres":
+        return (*S.sphere_scene(), cam)
+    if name == "mixed":
+        return (*S.mixed_test_scene(), R.camera_matrix((1.0, 1.2, 4.5), 0.25, -0.15))
+    if name == "glass":  # the camera inside a glass sphere: back faces
+        return (*C.glass_scene(), cam)
+    if name == "boxes":  # rotated, non-uniformly scaled box instances
+        return (*C.box_instances_scene(), R.camera_matrix((1.0, 1.2, 4.5), 0.25, -0.15))
+    if name == "mesh_smooth":
+        return (*S.mesh_scene(2, 10, 11, smooth=True), cam)
+    if name == "mesh_flat":
+        return (*S.mesh_scene(1, 8, 7, smooth=False), cam)
+    if name == "empty":
+        return (*C.empty_scene(), cam)
+    if name == "no_material":  # shapes without a material: their hits are misses
+        shapes, tris, mats = S.mixed_test_scene()
+        shapes = shapes.copy()
+        shapes["material"][[1, 4]] = -1
+        return shapes, tris, mats, R.camera_matrix((1.0, 1.2, 4.5), 0.25, -0.15)
+    raise ValueError(name)
+
+
+def make(T, sky, name, w, h, accel=0, **denoise):
+    shapes, tris, mats, cam = scene(name)
+    t = T.Tracer(w, h)
+    t.set_skybox(sky)
+    t.set_acceleration(accel)
+    t.options = R.render_data(w, h, 1, 10, camera_to_world=cam, time=1)
+    t.scene_data = R.scene_data(len(shapes))
+    t.update_scene(shapes, tris, mats)
+    t.clear_canvas()
+    t.set_denoise(**denoise)
+    return t, (shapes, tris, mats)
+
+
+# (num_samples, time) per dispatch: above and below every feature_samples, a dispatch without samples, the even_time seed
+DISPATCHES = ((4, 4096), (1, 77), (0, 5), (9, 123456789), (2, 31337))
+
+
+def run_features(T, sky, oracle, name, w, h, fs, accel=0, dispatches=DISPATCHES):
+    t, (shapes, tris, mats) = make(T, sky, name, w, h, accel=accel, feature_samples=fs, iterations=0)
+    want_nd = np.zeros((h, w, 4), np.float32)
+    want_ah = np.zeros((h, w, 4), np.float32)
+    for i, (ns, tm) in enumerate(dispatches):
+        t.options["num_samples"] = ns
+        t.options["time"] = tm
+        t.render(i + 1)
+        oracle.features(t.options, t.scene_data, shapes, tris, mats, fs, want_nd, want_ah)
+    got = t.read_denoise_inputs()
+    t.close()
+    # bit for bit: the feature pass reuses the trace kernel's camera and intersection code, whose hits match the oracle's
+    assert bits_equal(got["normal_depth"], want_nd), (name, fs, accel)
+    assert bits_equal(got["albedo_hits"], want_ah), (name, fs, accel)
+    assert (got["T"], got["P"]) == (len(dispatches), sum(max(ns, 0) for ns, _ in dispatches))
+    F = sum(min(fs, max(ns, 0)) for ns, _ in dispatches)
+    assert np.all(got["albedo_hits"][..., 3] <= F)
+    return got
+
+
+SCENES = [("spheres", 0), ("mixed", 0), ("mixed", 1), ("glass", 0), ("boxes", 0), ("mesh_smooth", 0), ("mesh_smooth", 1),
+          ("mesh_flat", 0), ("mesh_flat", 1), ("empty", 0), ("no_material", 0), ("no_material", 1)]
+
+
+@pytest.mark.parametrize("fs", [1, 3, 8])
+@pytest.mark.parametrize("name,accel", SCENES)
+def test_guide_buffers_equal_oracle(T, sky, oracle, name, accel, fs):
+    got = run_features(T, sky, oracle, name, 37, 29, fs, accel)
+    hits = got["albedo_hits"][..., 3]
+    if name == "empty":
+        assert not hits.any()
+    else:
+        assert hits.sum() > 0
+    if name == "no_material":
+        assert (hits < sum(min(fs, max(ns, 0)) for ns, _ in DISPATCHES)).any()
+
+
+@pytest.mark.parametrize("w,h", [(1, 33), (33, 1)])  # (37x29 is test_guide_buffers_equal_oracle[mixed-1-3])
+def test_guide_buffers_ragged_frames(T, sky, oracle, w, h):
+    run_features(T, sky, oracle, "mixed", w, h, 3, accel=1)
+
+
+def test_guide_buffers_full_hd(T, sky, oracle):
+    """1920x1080: pixel ids up to 2^21, where the kernel's magic-number division by the width must still be exact."""
+    run_features(T, sky, oracle, "spheres", 1920, 1080, 1, dispatches=((1, 4096), (1, 99)))
+
+
+def test_set_denoise_clearing_rule(T, sky, oracle):
+    """The same feature_samples again keeps the sums (and the canvas); another value clears them and the canvas."""
+    t, _ = make(T, sky, "mixed", 37, 29, feature_samples=2)
+    t.options["num_samples"] = 3
+    t.render(1)
+    before, canvas = t.read_denoise_inputs(), t.read_canvas()
+    assert before["albedo_hits"][..., 3].sum() > 0 and np.all(np.isfinite(before["moments"]))
+    t.set_denoise(feature_samples=2, iterations=3, sigma_luminance=2.0)
+    kept = t.read_denoise_inputs()
+    for k in ("normal_depth", "albedo_hits", "moments"):
+        assert bits_equal(kept[k], before[k]), k
+    assert (kept["T"], kept["P"]) == (1, 3) and bits_equal(t.read_canvas(), canvas)
+    t.set_denoise(feature_samples=3)
+    cleared = t.read_denoise_inputs()
+    for k in ("normal_depth", "albedo_hits", "moments"):
+        assert not cleared[k].any(), k
+    assert (cleared["T"], cleared["P"]) == (0, 0) and not t.read_canvas().any()
+    t.close()
+
+
+# ---- moments -----------------------------------------------------------------------------------------------------------------
+MOMENT_SAMPLES = (1, 2, 3, 4, 5, 8, 16, 20, 33)  # every path of the reduction: scalar loop, tail of four, unrolled 16, both
+BATCHES = (1, 4, 8, 16)
+
+
+@pytest.fixture(scope="module")
+def radiance(sky, oracle):
+    """(num_samples, time) -> the oracle's per-sample radiance (pixels, num_samples, 3) of the moments frame."""
+    cache = {}
+
+    def get(ns, tm):
+        if (ns, tm) not in cache:
+            shapes, tris, mats, cam = scene("mixed")
+            rd = R.render_data(40, 30, ns, 10, camera_to_world=cam, time=tm)
+            ids = np.repeat(np.arange(40 * 30), ns)
+            smp = np.tile(np.arange(ns), 40 * 30)
+            cache[(ns, tm)] = oracle.trace_paths(rd, R.scene_data(len(shapes)), shapes, tris, mats, sky, ids, smp).reshape(40 * 30, ns, 3)
+        return cache[(ns, tm)]
+    return get
+
+
+@pytest.mark.parametrize("ns", MOMENT_SAMPLES)
+def test_moments_equal_per_sample_radiance(T, sky, radiance, ns):
+    """moments = sum over dispatches of (1/n) sum_k lum(r_k)^2 from the oracle's radiance, bit for bit, with the library's own
+    batches and in sample batches of 1, 4, 8 and 16 (the batch's partial s2 is carried in the running buffer)."""
+    times = (4096, 271828)
+    want = np.zeros(40 * 30, np.float32)
+    for tm in times:
+        want = D.moments(radiance(ns, tm), want)
+    # a budget of 2b samples per pixel gives batches of b (two buffers) only where ns > 2b, so each run takes the batch sizes
+    # of BATCHES that split it (ns = 33: all four; ns <= 2: none) rather than all four
+    budgets = [None] + [b for b in BATCHES if ns > 2 * b]
+    natural = ns if ns <= 4 or ns % 4 == 0 else ns & ~3  # without a budget: batches of 4k samples (the reduction's aligned loads) and a tail
+    for b in budgets:
+        t, _ = make(T, sky, "mixed", 40, 30)
+        if b is not None:
+            t.set_radiance_budget(40 * 30 * 12 * 2 * b)
+        for i, tm in enumerate(times):
+            t.options["num_samples"] = ns
+            t.options["time"] = tm
+            t.render(i + 1)
+            assert t.last_trace_launches()[0] == -(-ns // (natural if b is None else b)), (ns, b)
+        got = t.read_denoise_inputs()
+        assert (got["T"], got["P"]) == (len(times), len(times) * ns)
+        # bit for bit (the one-sample test's bound of 1 ulp is not needed: same operations, same order)
+        assert bits_equal(got["moments"].reshape(-1), want), (ns, b, np.abs(got["moments"].reshape(-1) - want).max())
+        t.close()
