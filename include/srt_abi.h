@@ -309,6 +309,33 @@ int srt_read_denoised(srt_tracer *t, float *rgba_out);
  * num_samples}. */
 int srt_read_denoise_inputs(srt_tracer *t, float *normal_depth, float *albedo_hits, float *moments, uint32_t counts[2]);
 
+/* ---- temporal reprojection for the denoiser (new; SVGF's temporal half) ---------------------------------------------- */
+
+/* Opt-in, between the filter's set-up and its a-trous passes. At each srt_clear_canvas with something traced since the
+ * last clear, the frame being cleared (its colour and moments integrated with its own history, their sample count capped
+ * at history_limit, its guide buffers and the camera of its last dispatch) becomes the history. The filter of a later
+ * frame reprojects the history into its camera (bilinear taps, rejected on normal and distance) and blends it in,
+ * weighted by sample counts: c = (P c_cur + h c_hist) / (P + h), the moments likewise, variance from the blended moments
+ * over P + h. With temporal on the set-up divides the canvas by the dispatch count T since the clear, not by
+ * ticks_stopped (the same in the front-end's loop). A pixel without history gets exactly the spatial set-up's values.
+ * The history is dropped by srt_reset_denoise_history, turning temporal on or off, srt_set_denoise turning the denoiser
+ * off (which also turns temporal off) or clearing its accumulations, srt_set_skybox, and an srt_update_scene whose
+ * arrays or scene data differ in bytes from the previous call's. 112 B of device memory per pixel (two history sets),
+ * allocated on the first enable. Full-frame handles only, like the denoiser. */
+
+/* Host-only: enable = 1, history_limit = 32, normal_threshold = 0.9, depth_threshold = 0.05. */
+int srt_temporal_defaults(srt_temporal_params *out);
+/* params NULL or enable == 0: off. SRT_ERR_INVALID: history_limit outside 1..2^20, normal_threshold outside [-1, 1],
+ * depth_threshold not finite and > 0, reserved != 0. SRT_ERR_STATE: the denoiser is off or the handle is partitioned. */
+int srt_set_denoise_temporal(srt_tracer *t, const srt_temporal_params *params);
+/* Drop the history: the next frame is filtered as by the spatial denoiser alone. */
+int srt_reset_denoise_history(srt_tracer *t);
+/* The current history (blocking; NULL skips an output): colour_count = width*height float4 {integrated r, g, b, sample
+ * count}; moments = width*height float2 {m1, m2}; guide = width*height x 2 float4 {N, Z}, {A, coverage}; camera = the
+ * history frame's render data; *valid = 0 when there is no history (the outputs are then zero).
+ * SRT_ERR_STATE when temporal reprojection was never enabled on this handle. */
+int srt_read_denoise_history(srt_tracer *t, float *colour_count, float *moments, float *guide, srt_render_data *camera, int *valid);
+
 /* Device self-test of the deterministic math (tests only). Walks r = 0, stride, ... over
  * all 2^32 RNG outputs: out[0..2] = mismatch counts of the kernel-local sqrt / log / cos
  * specialisations against their generic definitions (must be 0); out[3..7] = sums of the

@@ -140,6 +140,17 @@ typedef struct srt_denoise_params {
 	int32_t reserved;        /* must be 0 */
 } srt_denoise_params;
 
+/* Temporal reprojection of the denoiser (srt_set_denoise_temporal in srt_abi.h; new, no counterpart in the
+ * reference). The integrated colour and moments of the frame before the last srt_clear_canvas are reprojected
+ * through the two cameras and blended into the current frame's, weighted by sample counts. */
+typedef struct srt_temporal_params {
+	int32_t enable;         /* 0: off */
+	int32_t history_limit;  /* 1..2^20: the most samples a pixel's history counts for */
+	float normal_threshold; /* -1..1: a history tap needs N . N_history >= this */
+	float depth_threshold;  /* finite, > 0: and |Z_history - D| <= this * D, D = distance from the history camera */
+	int32_t reserved[4];    /* must be 0 */
+} srt_temporal_params;
+
 #ifdef __cplusplus
 }
 #endif
@@ -188,5 +199,10 @@ SRT_STATIC_ASSERT(offsetof(srt_denoise_params, feature_samples) == 8, "DenoisePa
 SRT_STATIC_ASSERT(offsetof(srt_denoise_params, sigma_luminance) == 12, "DenoiseParams.sigma_luminance@12");
 SRT_STATIC_ASSERT(offsetof(srt_denoise_params, sigma_albedo) == 24, "DenoiseParams.sigma_albedo@24");
 SRT_STATIC_ASSERT(offsetof(srt_denoise_params, reserved) == 28, "DenoiseParams.reserved@28");
+SRT_STATIC_ASSERT(sizeof(srt_temporal_params) == 32, "TemporalParams 32 B");
+SRT_STATIC_ASSERT(offsetof(srt_temporal_params, history_limit) == 4, "TemporalParams.history_limit@4");
+SRT_STATIC_ASSERT(offsetof(srt_temporal_params, normal_threshold) == 8, "TemporalParams.normal_threshold@8");
+SRT_STATIC_ASSERT(offsetof(srt_temporal_params, depth_threshold) == 12, "TemporalParams.depth_threshold@12");
+SRT_STATIC_ASSERT(offsetof(srt_temporal_params, reserved) == 16, "TemporalParams.reserved@16");
 
 #endif /* SRT_TYPES_H */

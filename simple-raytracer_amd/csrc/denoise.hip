@@ -188,6 +188,8 @@ int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples
 	t->dn_T += 1;
 	t->dn_P += ns;
 	t->dn_F += fs;
+	t->dn_cam = p.rd;
+	t->tp_fresh = false; // temporal.hip: the staging set no longer holds what is traced since the clear
 	return SRT_OK;
 }
 
@@ -210,8 +212,14 @@ int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
 	sp.guide = guide;
 	sp.out = col;
 	sp.argb = K == 0 ? reinterpret_cast<uint32_t *>(argb) : nullptr;
-	hipLaunchKernelGGL(srt_denoise_setup_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, t->stream, sp);
-	SRT_HIP(t, hipGetLastError());
+	const float4 *fguide = guide;
+	if (t->tp_on) { // temporal.hip: the set-up with the reprojected history blended in; it writes the guide into the staging set
+		const int rc = srt_temporal_setup(t, col, sp.argb, &fguide);
+		if (rc) return rc;
+	} else {
+		hipLaunchKernelGGL(srt_denoise_setup_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, t->stream, sp);
+		SRT_HIP(t, hipGetLastError());
+	}
 	FilterParams fp;
 	fp.width = t->width;
 	fp.height = t->height;
@@ -222,7 +230,7 @@ int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
 	// in double, clamped to FLT_MAX: in float the square underflows for sigma_albedo below ~5.4e-20 and the inverse is
 	// inf, which turns every tap's 0 * inf albedo term into NaN (no pixel filtered); clamped, equal albedos still cost 0
 	fp.inv_sigma_a2 = (float)std::min(1.0 / ((double)t->dn.sigma_albedo * (double)t->dn.sigma_albedo), (double)FLT_MAX);
-	fp.guide = guide;
+	fp.guide = fguide;
 	const dim3 grid((unsigned)((t->width + 15) / 16), (unsigned)((t->height + 15) / 16));
 	for (int k = 0; k < K; k++) {
 		fp.step = 1 << k;
@@ -256,6 +264,8 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 	if (!t) return SRT_ERR_INVALID;
 	if (!params || !params->enable) {
 		t->dn_on = false;
+		t->tp_on = false; // temporal reprojection is a stage of the denoiser
+		srt_temporal_drop(t);
 		return SRT_OK;
 	}
 	if (!params_ok(*params))
@@ -273,6 +283,7 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 	t->dn_on = true;
 	if (clear) {
 		t->dn_filtered = false;
+		srt_temporal_drop(t);
 		SRT_HIP(t, hipMemsetAsync(t->canvas, 0, t->canvas_bytes, t->stream)); // srt_clear_canvas
 		return srt_denoise_clear(t);
 	}

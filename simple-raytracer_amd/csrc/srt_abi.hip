@@ -502,6 +502,8 @@ uint64_t hash_triangles(const srt_triangle *tris, size_t count) {
 size_t owned_pixels(const srt_tracer *t) { return (size_t)t->owned_rows * (size_t)t->width; }
 
 int clear_canvas_impl(srt_tracer *t) {
+	const int rc = srt_temporal_commit(t); // temporal.hip: the frame being cleared becomes the denoiser's history
+	if (rc) return rc;
 	// enqueue_fill_buffer with 0.0f over the whole canvas (src/tracer.cpp:98-101)
 	SRT_HIP(t, hipMemsetAsync(t->canvas, 0, t->canvas_bytes, t->stream));
 	if (t->dn_on) return srt_denoise_clear(t); // the denoiser's accumulations start again with the canvas
@@ -669,6 +671,8 @@ void srt_destroy(srt_tracer *t) {
 	t->dn_mom.release();
 	t->dn_guide.release();
 	t->dn_col.release();
+	t->tp_set[0].release();
+	t->tp_set[1].release();
 	if (t->ev_t0) (void)hipEventDestroy(t->ev_t0);
 	if (t->ev_t1) (void)hipEventDestroy(t->ev_t1);
 	if (t->ev_r0) (void)hipEventDestroy(t->ev_r0);
@@ -696,6 +700,7 @@ int srt_set_skybox(srt_tracer *t, const float *rgba, int width, int height) {
 	SRT_HIP(t, hipStreamSynchronize(t->stream));
 	t->sky_w = width;
 	t->sky_h = height;
+	srt_temporal_drop(t); // the denoiser's history saw the old sky
 	return SRT_OK;
 }
 
@@ -707,7 +712,24 @@ int srt_update_scene(srt_tracer *t, const srt_shape *shapes, size_t n_shapes, co
                      const srt_scene_data *scene) {
 	// the host pass allocates (std::vector): no C++ exception may cross the C ABI
 	try {
-		return update_scene_impl(t, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
+		// the denoiser's history (temporal.hip) survives only a call with the same bytes as the previous one: the front-end
+		// calls this after every clear, and without object motion vectors a moved or edited object starts from scratch
+		std::vector<uint8_t> bytes;
+		if (t && scene) {
+			const size_t nb[4] = {n_shapes * sizeof(srt_shape), n_triangles * sizeof(srt_triangle), n_materials * sizeof(srt_material), sizeof(srt_scene_data)};
+			const void *src[4] = {shapes, triangles, materials, scene};
+			bytes.resize(32 + nb[0] + nb[1] + nb[2] + nb[3]);
+			memcpy(bytes.data(), nb, 32);
+			size_t o = 32;
+			for (int k = 0; k < 4; k++) {
+				if (nb[k]) memcpy(bytes.data() + o, src[k], nb[k]);
+				o += nb[k];
+			}
+		}
+		const int rc = update_scene_impl(t, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
+		if (t && (rc != SRT_OK || bytes.empty() || bytes != t->scene_bytes)) srt_temporal_drop(t);
+		if (t) t->scene_bytes.swap(bytes);
+		return rc;
 	} catch (const std::bad_alloc &) {
 		if (t) t->err.clear(); // the message itself must not allocate much: a short literal fits the small-string buffer
 		return t ? fail(t, SRT_ERR_INVALID, "out of host memory") : SRT_ERR_INVALID;
@@ -1643,6 +1665,7 @@ int srt_set_partition(srt_tracer *t, int rank, int world, int rows_per_block) {
 	if (!t) return SRT_ERR_INVALID;
 	if (world < 1 || rank < 0 || rank >= world || rows_per_block < 1)
 		return fail(t, SRT_ERR_INVALID, "srt_set_partition: need 0 <= rank < world and rows_per_block >= 1");
+	if (world > 1 && t->tp_on) return fail(t, SRT_ERR_STATE, "srt_set_partition: temporal reprojection works on the full frame only (srt_set_denoise_temporal(t, NULL) first)");
 	if (world > 1 && t->dn_on) return fail(t, SRT_ERR_STATE, "srt_set_partition: the denoiser works on the full frame only (srt_set_denoise(t, NULL) first)");
 	SRT_HIP(t, hipSetDevice(t->device));
 	SRT_HIP(t, hipStreamSynchronize(t->stream));

@@ -99,6 +99,17 @@ struct srt_tracer {
 	DevBuf<float> dn_guide;                // filter set-up: 2 float4 per pixel {N, Z}, {A, cov}
 	DevBuf<float> dn_col;                  // two float4 images {colour, variance}, ping-pong between passes
 	int dn_out = 0;                        // the image of dn_col the last pass wrote
+	srt_render_data dn_cam{};              // the last dispatch's render data since the clear (its camera: temporal reprojection)
+	// temporal reprojection (temporal.hip; srt_set_denoise_temporal). Two history sets, each px x 14 floats: float4
+	// {colour, count}, float2 {m1, m2}, 2 float4 guide; tp_set[tp_cur] is the history, the other the frame being integrated
+	bool tp_on = false;
+	srt_temporal_params tp{};
+	DevBuf<float> tp_set[2];
+	int tp_cur = 0;
+	bool tp_valid = false;   // tp_set[tp_cur] holds a history
+	bool tp_fresh = false;   // tp_set[1 - tp_cur] holds the integration of what is traced since the clear (a filter ran after the last trace)
+	srt_render_data tp_cam{}; // the history frame's render data
+	std::vector<uint8_t> scene_bytes; // the last srt_update_scene's arrays and scene data (the history survives an unchanged scene)
 	hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;
 	bool have_trace_ev = false, have_resolve_ev = false, have_kernel_ev = false;
 	std::string err;
@@ -121,6 +132,11 @@ void srt_collect_release(srt_tracer *t);
 int srt_denoise_clear(srt_tracer *t);
 int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples);
 int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb);
+/* temporal.hip: the temporal set-up over the canvas into `col` (and argb when not NULL), *guide = the guide it wrote;
+ * the commit at srt_clear_canvas (before the canvas is zeroed); dropping the history */
+int srt_temporal_setup(srt_tracer *t, float4 *col, uint32_t *argb, const float4 **guide);
+int srt_temporal_commit(srt_tracer *t);
+void srt_temporal_drop(srt_tracer *t);
 /* srt_trace whose last reduction also resolves into fused_argb (device, owned pixels x 4 bytes; NULL: plain srt_trace) */
 extern "C" int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fused_argb, uint32_t ticks_stopped);
 /* one scene for several handles: the host pass once (members[0]'s acceleration mode and hierarchy cache), the uploads of all

@@ -152,6 +152,21 @@ class Tracer {
 		d.sigma_albedo = sigma_albedo;
 		check(srt_set_denoise(handle, &d));
 	}
+	/// The denoiser's temporal reprojection (srt_set_denoise_temporal): the frame before each clear_canvas is reprojected
+	/// into the next camera and blended in. Needs set_denoise first; enable = false turns it off. Single-device tracers only.
+	void set_denoise_temporal(bool enable = true, int history_limit = 32, float normal_threshold = 0.9f, float depth_threshold = 0.05f) {
+		if (group) throw std::runtime_error("Tracer::set_denoise_temporal: single-device tracers only");
+		if (!enable) {
+			check(srt_set_denoise_temporal(handle, nullptr));
+			return;
+		}
+		srt_temporal_params p;
+		check(srt_temporal_defaults(&p));
+		p.history_limit = history_limit;
+		p.normal_threshold = normal_threshold;
+		p.depth_threshold = depth_threshold;
+		check(srt_set_denoise_temporal(handle, &p));
+	}
 	/// render() / render_pipelined() record the kernel timers' events too (off by default: they cost 10-17 us of a 150 us
 	/// frame); single-device tracers only
 	void set_kernel_timers(bool enable) {

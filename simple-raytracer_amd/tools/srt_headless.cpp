@@ -5,8 +5,10 @@
 //
 //   srt_headless [--scene spheres|meshes|empty] [--obj f.obj]... [--stl f.stl]...
 //                [--width W --height H --spp S --bounces B --frames N --time T]
-//                [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K]
+//                [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--temporal] [--move DX]
 // --denoise K: the frames go through the edge-aware denoiser with K a-trous passes (Tracer::set_denoise; one device only)
+// --temporal: with --denoise, the denoiser's temporal reprojection (Tracer::set_denoise_temporal)
+// --move DX: the camera moves by DX along x every frame and every frame clears the canvas, as the front-end does while moving
 //
 // --skybox sky.ppm: an 8-bit binary PPM (P6) as the sky, prepared the way the reference prepares assets/skybox.png
 //                   (host/skybox.hpp: four channels, rows flipped, pow(byte / 255, 2.2)); default: the synthetic sky.
@@ -101,6 +103,9 @@ int main(int argc, char **argv) {
 	unsigned time_seed = 12345;
 	bool parse_only = false, bvh = false, pipelined = false;
 	int gpus = 1, denoise = -1;
+	bool temporal = false;
+	float move = 0.0f;
+	bool moving = false;
 	for (int i = 1; i < argc; i++) {
 		std::string a = argv[i];
 		auto next = [&]() -> const char * {
@@ -127,12 +132,19 @@ int main(int argc, char **argv) {
 		else if (a == "--pipelined") pipelined = true;
 		else if (a == "--skybox") skybox_path = next();
 		else if (a == "--denoise") denoise = std::atoi(next());
+		else if (a == "--temporal") temporal = true;
+		else if (a == "--move") move = std::strtof(next(), nullptr), moving = true;
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K]\n";
+			             "[--denoise K] [--temporal] [--move DX]\n";
 			return 2;
 		}
+	}
+
+	if (temporal && denoise < 0) {
+		std::cerr << "--temporal needs --denoise K\n";
+		return 2;
 	}
 
 	// ---- scene construction, as src/main.cpp:95-126 does it ----
@@ -197,6 +209,7 @@ int main(int argc, char **argv) {
 	Tracer tracer(width, height, 0, gpus); // --gpus N: one Tracer over N devices (rows split, one RCCL gather per frame)
 	if (bvh) tracer.set_acceleration(SRT_ACCEL_BVH);
 	if (denoise >= 0) tracer.set_denoise(denoise);
+	if (temporal) tracer.set_denoise_temporal();
 	tracer.options.num_samples = spp;
 	tracer.options.num_bounces = bounces;
 	tracer.options.show_normals = false;
@@ -236,12 +249,12 @@ int main(int argc, char **argv) {
 		auto &options = tracer.options;
 		options.aspect_ratio = (float)width / (float)height;
 		options.fov_scale = 1.0f; // tan(90deg / 2)
-		options.camera_to_world = camera_to_world;
+		options.camera_to_world = moving ? eye_matrix(glm::vec3(move * (float)frame, 0.5f, 5.0f), 0.0f, 0.0f) : camera_to_world;
 		options.time = time_seed + 7919u * (unsigned)frame;
 		options.tick = (unsigned)frame;
 		if (pipelined) tracer.render_pipelined(time_not_moved, pixels); // delivers the previous frame
 		else tracer.render(time_not_moved, pixels);
-		time_not_moved++;
+		time_not_moved = moving ? 1 : time_not_moved + 1; // a moving camera clears every frame (src/main.cpp:270-290)
 	}
 	if (pipelined) tracer.finish(pixels);
 	double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "srt_group_set_acceleration", "srt_group_update_scene", "srt_group_clear_canvas", "srt_group_trace_and_gather", "srt_group_render",
     "srt_group_read_canvas", "srt_group_get_counters", "srt_render_pipelined", "srt_pipeline_flush", "srt_unpermute_device",
     "srt_denoise_defaults", "srt_set_denoise", "srt_resolve_denoised", "srt_read_denoised", "srt_read_denoise_inputs",
+    "srt_temporal_defaults", "srt_set_denoise_temporal", "srt_reset_denoise_history", "srt_read_denoise_history",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -110,6 +111,26 @@ class DenoiseParams(C.Structure):
 
 
 assert C.sizeof(DenoiseParams) == 32
+
+
+class TemporalParams(C.Structure):
+    """include/srt_types.h srt_temporal_params"""
+    _fields_ = [("enable", C.c_int32), ("history_limit", C.c_int32), ("normal_threshold", C.c_float), ("depth_threshold", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n == "reserved" else getattr(self, n)) for n, _ in self._fields_}
+
+
+assert C.sizeof(TemporalParams) == 32
+
+
+def temporal_defaults():
+    """srt_temporal_defaults (host only, no GPU needed) as a dict."""
+    d = TemporalParams()
+    if load_library().srt_temporal_defaults(C.byref(d)):
+        raise SrtError("srt_temporal_defaults failed")
+    return d.as_dict()
 
 
 def denoise_defaults():
@@ -230,6 +251,11 @@ def _bind(lib):
         lib.srt_resolve_denoised.argtypes = [vp, C.c_uint32]
         lib.srt_read_denoised.argtypes = [vp, vp]
         lib.srt_read_denoise_inputs.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_uint32)]
+    if hasattr(lib, "srt_set_denoise_temporal"):
+        lib.srt_temporal_defaults.argtypes = [C.POINTER(TemporalParams)]
+        lib.srt_set_denoise_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
+        lib.srt_reset_denoise_history.argtypes = [vp]
+        lib.srt_read_denoise_history.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
     return lib
 
 
@@ -485,6 +511,36 @@ class Tracer:
         counts = (C.c_uint32 * 2)()
         self._check(self.lib.srt_read_denoise_inputs(self._h, _ptr(nd), _ptr(ah), _ptr(m), counts))
         return {"normal_depth": nd, "albedo_hits": ah, "moments": m, "T": int(counts[0]), "P": int(counts[1])}
+
+    def set_denoise_temporal(self, enable=True, **kw):
+        """Turn the denoiser's temporal reprojection on with srt_temporal_defaults() overridden by kw (history_limit,
+        normal_threshold, depth_threshold), or off with enable=False. Needs the denoiser on (set_denoise)."""
+        if not enable:
+            self._check(self.lib.srt_set_denoise_temporal(self._h, None))
+            return
+        d = TemporalParams()
+        self._check(self.lib.srt_temporal_defaults(C.byref(d)))
+        for k, v in kw.items():
+            if k not in ("history_limit", "normal_threshold", "depth_threshold"):
+                raise TypeError(f"set_denoise_temporal: unknown parameter {k}")
+            setattr(d, k, v)
+        self._check(self.lib.srt_set_denoise_temporal(self._h, C.byref(d)))
+
+    def reset_denoise_history(self):
+        """Drop the temporal history: the next frame is filtered as by the spatial denoiser alone."""
+        self._check(self.lib.srt_reset_denoise_history(self._h))
+
+    def read_denoise_history(self):
+        """dict: valid, colour (h, w, 3), count (h, w), m1, m2 (h, w), guide (h, w, 2, 4) {N, Z}, {A, cov}, camera (the history
+        frame's records.RENDER_DATA). Without a history every array is zero and valid is False."""
+        cc = np.zeros((self.height, self.width, 4), np.float32)
+        m = np.zeros((self.height, self.width, 2), np.float32)
+        g = np.zeros((self.height, self.width, 2, 4), np.float32)
+        cam = np.zeros((), R.RENDER_DATA)
+        valid = C.c_int(0)
+        self._check(self.lib.srt_read_denoise_history(self._h, _ptr(cc), _ptr(m), _ptr(g), _ptr(cam), C.byref(valid)))
+        return {"valid": bool(valid.value), "colour": cc[..., :3], "count": cc[..., 3], "m1": m[..., 0], "m2": m[..., 1], "guide": g,
+                "camera": cam}
 
     def set_partition(self, rank, world, rows_per_block=8):
         self._check(self.lib.srt_set_partition(self._h, rank, world, rows_per_block))
