@@ -1,12 +1,12 @@
-"""Compare the gfx950 disassembly of the trace and reduce kernels between two builds of csrc/kernels.hip (no GPU needed).
+"""Compare the gfx950 disassembly of every kernel between two builds of csrc/kernels.hip (no GPU needed).
 
     python scripts/isa_compare.py OLD_TREE NEW_TREE
 
 Each tree is a checkout's root (holding simple-raytracer_amd/csrc and include/). kernels.hip is compiled device-only with
-the product flags of build.py, the gfx950 code object is unbundled and disassembled with llvm-objdump, and every
-srt_trace_kernel instantiation and the plain ordered reduction (srt_reduce_kernel, srt_reduce_kernel<false> since the
-denoiser's moments variant made it a template) are compared instruction by instruction, branch offsets and the s_nop
-padding between functions left out. Exit status 1 on any difference.
+the product flags of build.py, the gfx950 code object is unbundled and disassembled with llvm-objdump, and every function
+in it is compared instruction by instruction, branch offsets and the s_nop padding between functions left out. A function
+that only one side has counts as a difference; the plain ordered reduction is matched across its rename to
+srt_reduce_kernel<false> (a template since the denoiser's moments variant). Exit status 1 on any difference.
 """
 import re
 import subprocess
@@ -15,7 +15,7 @@ import tempfile
 from pathlib import Path
 
 ROCM = Path("/opt/rocm")
-REDUCE = {"_Z17srt_reduce_kernel12ReduceParams", "_Z17srt_reduce_kernelILb0EEv12ReduceParams"}
+RENAMED = {"_Z17srt_reduce_kernel12ReduceParams": "_Z17srt_reduce_kernelILb0EEv12ReduceParams"}  # old name -> new name
 
 
 def build(tree, out):
@@ -62,15 +62,16 @@ def main():
         a_dir.mkdir()
         b_dir.mkdir()
         a, b = functions(build(old_tree, a_dir)), functions(build(new_tree, b_dir))
-    pairs = [(k, k) for k in a if k.startswith("_Z16srt_trace_kernel")]
-    pairs += [(ka, kb) for ka in a if ka in REDUCE for kb in b if kb in REDUCE and "ILb1" not in kb]
+    a = {RENAMED.get(k, k): v for k, v in a.items()}
+    names = sorted(a.keys() | b.keys())
     bad = 0
-    for ka, kb in pairs:
-        same = kb in b and a[ka] == b[kb]
+    for k in names:
+        same = k in a and k in b and a[k] == b[k]
         bad += not same
-        print(f"{'same' if same else 'DIFFERENT'}  {ka} -> {kb}  ({len(a[ka])} instructions)")
-    print(f"{len(pairs)} kernels compared, {bad} different")
-    sys.exit(1 if bad or not pairs else 0)
+        where = "" if k in a and k in b else f"  only in {'old' if k in a else 'new'}"
+        print(f"{'same' if same else 'DIFFERENT'}  {k}  ({len(a.get(k, b.get(k)))} instructions){where}")
+    print(f"{len(names)} kernels compared, {bad} different")
+    sys.exit(1 if bad or not names else 0)
 
 
 if __name__ == "__main__":

@@ -232,7 +232,6 @@ int srt_trace_waves_per_simd(int has_models, int use_bvh);
 int srt_trace_resident_waves_per_cu(const TraceParams &p, bool count_triangles); /* from the runtime's occupancy calculator */
 int srt_scan_suspend_min(void); /* array scan: models of at least this many triangles sit alone in their block and are flagged big */
 int srt_sub_job_items(int has_models, int use_bvh); /* items per sub-job (the unit a wave's chunk is handed to its lanes in); chunks per atomic are multiples of it */
-int srt_scan_queue_in_hbm(void); /* 1: TraceParams.scan_queue must point at SRT_SCAN_QUEUE_FLOATS floats per wave of the launch */
 /* per persistent wave: two scan stacks of SRT_SQ_CAP records x 20 fields, one park stack of SRT_PK_CAP records x 15 fields.
  * A scan stack is taken back when it holds 64 rays and one EXTEND phase pushes at most 64: 190 is the most one can hold. */
 #define SRT_SQ_CAP 192
@@ -242,7 +241,6 @@ int srt_scan_queue_in_hbm(void); /* 1: TraceParams.scan_queue must point at SRT_
 #define SRT_POOL_CTL_WORDS (16 + 2 * SRT_POOL_BLOCKS)
 #define SRT_POOL_REC_FLOATS ((size_t)2 * SRT_POOL_BLOCKS * 20 * 64)
 #define SRT_SCAN_SET_FLOATS(waves, pool) ((size_t)SRT_POOL_CTL_WORDS + ((pool) ? SRT_POOL_REC_FLOATS : (size_t)0) + (size_t)(waves) * SRT_SCAN_QUEUE_FLOATS) /* one set (pool: with the launch-end ray pool's records, 84 MB; TraceParams.pool_blocks != 0); a multiple of 4 */
-int srt_bvh_suspends(void);
 void srt_launch_prepass(const PrepassParams &p, uint64_t total_wtris, void *stream);
 void srt_launch_resolve(const ResolveParams &p, void *stream);
 void srt_launch_selftest(unsigned long long *out16, uint32_t stride, void *stream);

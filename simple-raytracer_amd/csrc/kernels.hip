@@ -115,7 +115,6 @@ __device__ __forceinline__ f3 cross3(f3 a, f3 b) {
 // flushes denormal inputs: sqrt(-denormal) must be NaN, not -0). Verified against
 // __builtin_sqrtf on all 2^32 bit patterns by srt_selftest_math.
 __device__ __forceinline__ float sqrt_ieee(float x) {
-#ifndef SRT_NO_FAST_SQRT
 	const uint32_t mag = dm_f2u(x) & 0x7fffffffu;
 	if (__builtin_expect((mag - 1u) < 0x0f7fffffu, 0)) return __builtin_sqrtf(x); // 0 < |x| < 2^-96 @rare
 	float s = __builtin_amdgcn_sqrtf(x); // within 1 ulp
@@ -126,14 +125,10 @@ __device__ __forceinline__ float sqrt_ieee(float x) {
 	s = (vp <= 0.0f) ? down : s;
 	s = (vs > 0.0f) ? up : s;
 	return s;
-#else
-	return dm_sqrtf(x);
-#endif
 }
 // sqrt_ieee without its slow-path guard, for arguments known to be 0, inf, NaN or of
 // magnitude >= 2^-96.
 __device__ __forceinline__ float sqrt_core(float x) {
-#ifndef SRT_NO_FAST_SQRT
 	float s = __builtin_amdgcn_sqrtf(x);
 	const uint32_t si = dm_f2u(s);
 	float down = dm_u2f(si - 1u), up = dm_u2f(si + 1u);
@@ -142,9 +137,6 @@ __device__ __forceinline__ float sqrt_core(float x) {
 	s = (vp <= 0.0f) ? down : s;
 	s = (vs > 0.0f) ? up : s;
 	return s;
-#else
-	return dm_sqrtf(x);
-#endif
 }
 
 // Correctly rounded sqrt of a NORMAL x >= 2^-96 from v_rsq_f32 and one residual step: y ~ 1/sqrt(x) (1 ulp), s = x y (within
@@ -177,14 +169,10 @@ __device__ __forceinline__ float sqrt_rsq_zero_ok(float x) {
 template <int N, bool ZERO_OK>
 __device__ __forceinline__ void sqrt_rsq_n(const float (&x)[N], float (&out)[N]) {
 	float y[N], s[N], h[N];
-#ifndef SRT_NO_SQRT_STAGES
 	__builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
 	for (int i = 0; i < N; i++) y[i] = __builtin_amdgcn_rsqf(x[i]);
-#ifndef SRT_NO_SQRT_STAGES
 	__builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
 	for (int i = 0; i < N; i++) {
 		if (ZERO_OK) y[i] = __builtin_amdgcn_fmed3f(y[i], 0.0f, 0x1p100f);
@@ -235,13 +223,11 @@ __device__ __forceinline__ bool div_num_ok(f3 a) {
 }
 // a / b, component-wise
 __device__ __forceinline__ f3 div3(f3 a, float b) {
-#ifndef SRT_NO_FAST_DIV
 	const float ab = dm_fabs(b);
 	if (__builtin_expect(div_num_ok(a) && ab >= 0x1p-40f && ab <= 0x1p40f, 1)) {
 		const float r = rcp_refined(b);
 		return mk(div_core(a.x, b, r), div_core(a.y, b, r), div_core(a.z, b, r));
 	}
-#endif
 	return a / b; // @rare (scripts/isa_phase_mix.py: behind a range guard, counted as never executed)
 }
 // a / b, component-wise, with y = the host's correctly rounded 1 / b, or 0 when b is outside [2^-40, 2^40] (or not a number): the
@@ -249,12 +235,8 @@ __device__ __forceinline__ f3 div3(f3 a, float b) {
 // residual steps of div_core give the IEEE quotient for y = RN(1 / b) (Markstein, see div_by_rcp) -- one transcendental and two
 // fmas fewer than refining v_rcp_f32; everything else takes the compiler's division.
 __device__ __forceinline__ f3 div3_by_rcp(f3 a, float b, float y) {
-#if !defined(SRT_NO_FAST_DIV) && !defined(SRT_NO_HOST_RCP)
 	if (__builtin_expect(div_num_ok(a) && y != 0.0f, 1)) return mk(div_core(a.x, b, y), div_core(a.y, b, y), div_core(a.z, b, y));
 	return a / b; // @rare
-#else
-	return div3(a, b);
-#endif
 }
 // the built-in normalize: a * rsqrt(dot(a, a)) with detmath.h's division-free rsqrt -- 15 plain instructions, no
 // transcendental, no guard (before: IEEE sqrt and three IEEE quotients behind a range check)
@@ -272,13 +254,9 @@ __device__ __forceinline__ f3 ld3(const float *p) { return mk(p[0], p[1], p[2]);
 // less or greater than 0 (v_cmp_lg: false for +-0 and NaN), else x where it is a zero, else 0. Five plain instructions (the
 // generic form compiles to two nested exec-mask branches); equal to dm_sign on all 2^32 bit patterns (srt_selftest_math out[14]).
 __device__ __forceinline__ float sign_fast(float x) {
-#ifndef SRT_NO_SIGN_FAST
 	const float one = dm_u2f((dm_f2u(x) & 0x80000000u) | 0x3f800000u);
 	const float zero_or_x = __builtin_amdgcn_class(x, 0x60) ? x : 0.0f; // class mask: -0 | +0
 	return __builtin_islessgreater(x, 0.0f) ? one : zero_or_x;
-#else
-	return dm_sign(x);
-#endif
 }
 
 // column-major 4x4 times (v, w): ((m0*v.x + m1*v.y) + m2*v.z) + m3*w  (render.cl:114-120)
@@ -340,18 +318,12 @@ __device__ __forceinline__ float log_unit_biased(float u) {
 	// f is +0 or a multiple of 2^-24 in [-0.293, 0.415] and 2 + f lies in [1.7, 2.42]: inside the
 	// box of div_core (which also returns the +0 the division gives for f = +0)
 	const float den = 2.0f + f;
-#if !defined(SRT_NO_FAST_DIV) && !defined(SRT_NO_LOG_DIV1)
 	// f / den from the raw v_rcp_f32 and ONE residual step. Not a general division: f takes 2^24 values here, and the quotient is
 	// the IEEE one for every single u the RNG can return (exhaustive: exact_math_probe.hip "log div D1"; srt_selftest_math
 	// out[1] compares this function with dm_logf on all 2^32 of them). 1 + 3 instructions (shared-reciprocal form: 1 + 7).
 	const float rc = __builtin_amdgcn_rcpf(den);
 	const float q0 = f * rc;
 	float s = __builtin_fmaf(__builtin_fmaf(-den, q0, f), rc, q0);
-#elif !defined(SRT_NO_FAST_DIV)
-	float s = div_core(f, den, rcp_refined(den));
-#else
-	float s = f / den;
-#endif
 	float z = s * s;
 	float R = z * dm_fmaf(z, dm_fmaf(z, dm_fmaf(z, L3, L2), L1), L0);
 	float hfsq = (0.5f * f) * f;
@@ -382,44 +354,20 @@ __device__ __forceinline__ float cos_2pi(float x) {
 	float s_res = dm_fmaf(r * z, p, r);
 	float c_res = dm_fmaf(z * z, p, dm_fmaf(-0.5f, z, 1.0f));
 	float res = odd ? s_res : c_res;
-#ifndef SRT_NO_COS_SIGN_BITS
 	// -res in quadrants 1 and 2: bit 1 of k + 1, moved to the sign position and xor-ed in (three integer ops and no compare /
 	// select pair; same bits as the select for every angle, srt_selftest_math out[2])
 	return dm_u2f(dm_f2u(res) ^ ((((uint32_t)k << 30) + 0x40000000u) & 0x80000000u));
-#else
-	return (((k + 1) >> 1) & 1) ? -res : res;
-#endif
 }
 
-// Box-Muller, theta drawn first (render.cl:150-154)
-__device__ __forceinline__ float random_normal(uint32_t &seed) {
-#if !defined(SRT_NO_COUNT_FOLD) && !defined(SRT_NO_FAST_SQRT) && !defined(SRT_NO_RSQ_SQRT)
-	float theta = (6.28318548f * 2.3283064365386963e-10f) * random_count(seed); // = 6.28318548f * random_float, bit for bit
-	// -2 log u is -0 (u = 1), +inf (u = 0) or in [1.19e-7, 44.4] for every u random_float can return: the root by sqrt_rsq_zero_ok,
-	// and u = 0 (whose logarithm is left some finite number here) selected to sqrt(+inf) = +inf afterwards. Equal to the IEEE
-	// sqrt(-2 log u) for all 2^32 u: srt_selftest_math out[10].
-	const float cnt = random_count(seed);
-	float rho = sqrt_rsq_zero_ok(-2.0f * log_unit_biased<159, false>(cnt));
-	asm volatile("" : "+v"(rho)); // keep the zero test a select (see log_unit_biased)
-	rho = cnt == 0.0f ? DM_INF_F : rho;
-#elif !defined(SRT_NO_COUNT_FOLD)
-	float theta = (6.28318548f * 2.3283064365386963e-10f) * random_count(seed); // = 6.28318548f * random_float, bit for bit
-	// -2 log u is -0, +inf or in [1.19e-7, 44.4] for every u random_float can return: no small-argument guard
-	float rho = sqrt_core(-2.0f * log_count(random_count(seed)));
-#else
-	float theta = 6.28318548f * random_float(seed);
-	float rho = sqrt_core(-2.0f * log_unit(random_float(seed)));
-#endif
-	return rho * cos_2pi(theta);
-}
-
-// Three of them (render.cl:156-158: x, y, z in that order, theta before rho each time), the three square roots side by side
+// Three Box-Muller normals (render.cl:150-158: x, y, z in that order, theta drawn before rho each time), the three square
+// roots side by side. -2 log u is -0 (u = 1), +inf (u = 0) or in [1.19e-7, 44.4] for every u random_float can return: the root
+// by sqrt_rsq_zero_ok, and u = 0 (whose logarithm is left some finite number here) selected to sqrt(+inf) = +inf afterwards.
+// Equal to the IEEE sqrt(-2 log u) for all 2^32 u: srt_selftest_math out[10].
 __device__ __forceinline__ f3 random_normal3(uint32_t &seed) {
-#if !defined(SRT_NO_COUNT_FOLD) && !defined(SRT_NO_FAST_SQRT) && !defined(SRT_NO_RSQ_SQRT) && !defined(SRT_NO_NORMAL3)
 	float th[3], cnt[3], arg[3], rho[3];
 #pragma unroll
 	for (int k = 0; k < 3; k++) {
-		th[k] = (6.28318548f * 2.3283064365386963e-10f) * random_count(seed);
+		th[k] = (6.28318548f * 2.3283064365386963e-10f) * random_count(seed); // = 6.28318548f * random_float, bit for bit
 		cnt[k] = random_count(seed);
 	}
 #pragma unroll
@@ -431,12 +379,6 @@ __device__ __forceinline__ f3 random_normal3(uint32_t &seed) {
 		rho[k] = cnt[k] == 0.0f ? DM_INF_F : rho[k];
 	}
 	return mk(rho[0] * cos_2pi(th[0]), rho[1] * cos_2pi(th[1]), rho[2] * cos_2pi(th[2]));
-#else
-	const float gx = random_normal(seed);
-	const float gy = random_normal(seed);
-	const float gz = random_normal(seed);
-	return mk(gx, gy, gz);
-#endif
 }
 
 // fp64 Schlick (render.cl:173-178); r0 = ((1-mu)/(1+mu))^2 is a per-material constant
@@ -508,7 +450,6 @@ __device__ __forceinline__ void take_if_closer(float t_key, int idx, float &tmin
 template <int N>
 __device__ __forceinline__ void test_spheres(const Blk16 &s, f3 org, f3 dir, int idx0, float &tmin, int &best) {
 	float bq[4], disc[4];
-#if !defined(SRT_NO_FAST_SQRT) && !defined(SRT_NO_RSQ_SQRT)
 	bool slow = is_neg_zero(tmin);
 #pragma unroll
 	for (int i = 0; i < N; i++) {
@@ -541,42 +482,6 @@ __device__ __forceinline__ void test_spheres(const Blk16 &s, f3 org, f3 dir, int
 			take_if_closer(dm_u2f(k), idx0 + i, tmin, best);
 		}
 	}
-#else
-	float sq[4];
-	bool tiny = false;
-#pragma unroll
-	for (int i = 0; i < N; i++) {
-		f3 L = mk(s.v[4 * i] - org.x, s.v[4 * i + 1] - org.y, s.v[4 * i + 2] - org.z);
-		bq[i] = dot3(L, dir);
-		float c = dot3(L, L) - s.v[4 * i + 3];
-		disc[i] = bq[i] * bq[i] - c;
-#ifndef SRT_NO_FAST_SQRT
-		tiny = tiny || ((dm_f2u(disc[i]) & 0x7fffffffu) - 1u) < 0x0f7fffffu; // 0 < |x| < 2^-96
-#endif
-	}
-#ifndef SRT_NO_FAST_SQRT
-	if (__builtin_expect(tiny, 0)) {
-#pragma unroll
-		for (int i = 0; i < N; i++) sq[i] = __builtin_sqrtf(disc[i]); // @rare
-	} else {
-#pragma unroll
-		for (int i = 0; i < N; i++) sq[i] = sqrt_core(disc[i]);
-	}
-#else
-#pragma unroll
-	for (int i = 0; i < N; i++) sq[i] = dm_sqrtf(disc[i]);
-#endif
-#pragma unroll
-	for (int i = 0; i < N; i++) {
-		float t = bq[i] - sq[i];
-		if (t < 0.0f) t = bq[i] + sq[i];
-		bool hit = !(disc[i] < 0.0f) && !(t < 0.0f);
-		if (hit && t < tmin) {
-			tmin = t;
-			best = idx0 + i;
-		}
-	}
-#endif
 }
 
 // render.cl:206-221 against TWO planes (one 64-byte block {p, 0, n, 0} x 2; a run's last block is filled with a
@@ -591,11 +496,7 @@ __device__ __forceinline__ void test_planes2(const Blk16 &b, uint32_t count, f3 
 		float t = dot3(n, mk(b.v[8 * i] - org.x, b.v[8 * i + 1] - org.y, b.v[8 * i + 2] - org.z)) / denom;
 		// render.cl:209 `denom == 0 -> miss` needs no test of its own: x / 0 is +-inf or NaN, and +inf or a NaN is never below
 		// tmin, -inf is below 0
-#ifndef SRT_PLANE_DENOM_TEST
 		bool hit = !(t < 0.0f);
-#else
-		bool hit = !(dm_fabs(denom) == 0.0f) && !(t < 0.0f);
-#endif
 		if (hit && t < tmin) {
 			tmin = t;
 			best = idx0 + i;
@@ -659,9 +560,7 @@ __device__ __forceinline__ bool moller_trumbore(float v0x, float v0y, float v0z,
 		f3 q = cross3(sv, e1);
 		float dv = dot3(dir, q);
 		bool reject2 = false;
-#ifndef SRT_NO_TRI_V_REJECT
 		if (!COUNT_TRIS) reject2 = ((dv * a < 0.0f) && (dm_fabs(dv) >= aa * 0.001f)) || (dm_fabs(sh + dv) > aa * 1.01f);
-#endif
 		if (!reject2) {
 			SRT_REGION(EXTEND_TRI_DIV);
 			float f = 1.0f / a;
@@ -756,9 +655,6 @@ __device__ __forceinline__ void bvh_order2(uint32_t &a, uint32_t &b) {
 	a = lo, b = hi;
 }
 
-#ifndef SRT_BVH_PUSH_FORM
-#define SRT_BVH_PUSH_FORM 1 // 0: three unconditional stores, the idle ones into a spare slot: 37.7 / 37.8 ms against 34.7 / 33.9 (measured on the float-box walk)
-#endif
 template <bool COUNT_TRIS>
 __device__ __forceinline__ void walk_bvh(const float4 *__restrict__ blocks, BvhStackEntry *__restrict__ stack, uint32_t root, f3 org, f3 dir, int idx,
                                          float &tmin, int &best, uint32_t &best_rec, uint32_t &n_tri, uint32_t &n_tri_u SRT_RC_PARAM) {
@@ -847,15 +743,10 @@ __device__ __forceinline__ void walk_bvh(const float4 *__restrict__ blocks, BvhS
 			bvh_order2(k1, k3);
 			bvh_order2(k1, k2); // nearest first; the children that are not entered (keys >= KEY_INF) last
 			// k0 is entered now. The n others wait, farthest deepest: the registers' entry goes to memory and k1 takes its place,
-			// k3 and k2 go between them.
+			// k3 and k2 go between them. (Three unconditional stores, the idle ones into a spare slot, measured 37.7 / 37.8 ms
+			// against 34.7 / 33.9 on the float-box walk.)
 			const uint32_t w1 = k1 < SRT_BVH_KEY_INF ? 1u : 0u, w2 = k2 < SRT_BVH_KEY_INF ? 1u : 0u, w3 = k3 < SRT_BVH_KEY_INF ? 1u : 0u;
 			const uint32_t n = w1 + w2 + w3;
-#if SRT_BVH_PUSH_FORM == 0
-			const uint32_t i0 = w1 ? sp : SRT_BVH_STACK_CAP, i3 = w3 ? sp + 1u : SRT_BVH_STACK_CAP, i2 = w2 ? sp + n - 1u : SRT_BVH_STACK_CAP;
-			stack[i0].key = top_key, stack[i0].first = top_first;
-			stack[i3].key = k3, stack[i3].first = first;
-			stack[i2].key = k2, stack[i2].first = first;
-#else
 			if (w1) {
 				SRT_REGION(EXTEND_BVH_SPILL);
 				stack[sp].key = top_key, stack[sp].first = top_first;
@@ -868,7 +759,6 @@ __device__ __forceinline__ void walk_bvh(const float4 *__restrict__ blocks, BvhS
 				SRT_REGION(EXTEND_BVH_PUSH2);
 				stack[sp + n - 1u].key = k2, stack[sp + n - 1u].first = first;
 			}
-#endif
 			top_key = w1 ? k1 : top_key, top_first = w1 ? first : top_first;
 			sp += n;
 			if (k0 < SRT_BVH_KEY_INF) next = first + (k0 & 3u), next_key = k0, pending = false;
@@ -884,12 +774,6 @@ __device__ __forceinline__ void walk_bvh(const float4 *__restrict__ blocks, BvhS
 		}
 		cur = next, cur_key = next_key;
 	}
-}
-
-// global y of packed local row (include/srt_abi.h srt_set_partition)
-__device__ __forceinline__ int global_row(int local_row, int rank, int world, int rpb) {
-	int lb = local_row / rpb;
-	return (lb * world + rank) * rpb + (local_row - lb * rpb);
 }
 
 // Manual float bilinear, OpenCL 3.0 §8.2 CLAMP_TO_EDGE + LINEAR, normalized coords
@@ -919,23 +803,18 @@ __device__ __forceinline__ f3 sample_sky(const float *__restrict__ sky, int W, i
 // is read through it is loaded (scalar loads, scalar-cache hits) where it is used instead of living in SGPRs for the whole
 // launch. The persistent loop has far more wave-uniform state than SGPRs; parameters only the sky and the camera rays need
 // (sun, image size, camera matrix: ~45 dwords) were being spilled to VGPR lanes and read back with a v_readlane each.
-#ifndef SRT_COLD_PARAMS_LIVE
 __device__ __forceinline__ const SRT_AS_CONST TraceParams *cold_params() {
 	const SRT_AS_CONST TraceParams *kp = (const SRT_AS_CONST TraceParams *)__builtin_amdgcn_kernarg_segment_ptr();
 	asm volatile("" : "+s"(kp));
 	return kp;
 }
 #define SRT_COLD(p) (*cold_params())
-#else
-#define SRT_COLD(p) (p)
-#endif
 
 // dm_powi (detmath.h) for a WAVE-UNIFORM exponent 1 <= n <= 32: the same squarings and products in double, in the same
 // order, but the exponent's bits steer scalar branches. Written as in detmath.h the compiler turns the loop's `first ? b :
 // r * b` and the conditional squaring into selects on 64-bit values: ~45 v_cndmask per call, in runs (which stall on gfx950),
 // for what is four squarings and two products when n = 25.
 __device__ __forceinline__ float powi_uniform(float x, int n) {
-#ifndef SRT_NO_POWI_UNIFORM
 	uint32_t un = (uint32_t)__builtin_amdgcn_readfirstlane(n);
 	double b = (double)x;
 	while (!(un & 1u)) { // (n >= 1: there is a set bit) squarings below the lowest set bit
@@ -950,9 +829,6 @@ __device__ __forceinline__ float powi_uniform(float x, int n) {
 		un >>= 1;
 	}
 	return (float)r;
-#else
-	return dm_powi(x, n);
-#endif
 }
 
 // render.cl:380-394
@@ -1061,18 +937,13 @@ __device__ __forceinline__ f3 sky_box(const TraceParams &p_live, f3 dir) {
 // L2, so a line whose other items arrive later is not read back for ownership (plain / sc1 / nt at full size with the queue
 // of 64: 116.7 / 114.4 / - ms; with the queue of 40: 122.6 / 120.9 / 122.3). Each item is stored exactly once, by whichever wave ends
 // its path (the array scan's ray pool hands paths between waves), and read by srt_reduce_kernel after the launch.
-#ifndef SRT_RADIANCE_STORE
-#define SRT_RADIANCE_STORE 1 // 0 plain, 1 sc1, 2 nt
-#endif
 namespace {
 __device__ __forceinline__ void store_radiance(float *__restrict__ radiance, uint32_t item, f3 c) {
 	typedef float f3v __attribute__((ext_vector_type(3)));
 	f3v v;
 	v.x = c.x, v.y = c.y, v.z = c.z;
 	float *g = radiance + 3ull * item;
-	if (SRT_RADIANCE_STORE == 1) asm volatile("global_store_dwordx3 %0, %1, off sc1" : : "v"(g), "v"(v) : "memory");
-	else if (SRT_RADIANCE_STORE == 2) asm volatile("global_store_dwordx3 %0, %1, off nt" : : "v"(g), "v"(v) : "memory");
-	else asm volatile("global_store_dwordx3 %0, %1, off" : : "v"(g), "v"(v) : "memory");
+	asm volatile("global_store_dwordx3 %0, %1, off sc1" : : "v"(g), "v"(v) : "memory");
 }
 
 // ---- lane sets as wave-uniform masks (round 4) --------------------------------------------------------------------------------
@@ -1113,15 +984,16 @@ __device__ __forceinline__ void resolve_ring(const TraceParams &p, const float *
 #ifndef SRT_TRACE_WAVES_PER_SIMD
 #define SRT_TRACE_WAVES_PER_SIMD 5
 #endif
-#ifndef SRT_BVH_SUSPEND
-#define SRT_BVH_SUSPEND 0 // BVH kernels gather the rays that enter a big model's box before they walk, as the array scan does
-#endif
 #ifndef SRT_TRACE_WAVES_PER_SIMD_MODELS
 #define SRT_TRACE_WAVES_PER_SIMD_MODELS 5
 #endif
 #ifndef SRT_TRACE_WAVES_PER_SIMD_BVH
 #define SRT_TRACE_WAVES_PER_SIMD_BVH 5 // (4: configs[2] 42.0 ms, configs[4] 38.0 ms; 5: 40.8 / 36.5 -- the walk waits for memory, a fifth wave fills the gaps)
 #endif
+
+// Fields of a hit-queue entry (hq in the trace kernel): org, dir, mask, color, seed, best, bounce, item, and best_tri in scenes
+// with models. srt_trace_lds_floats sizes the queue with it, and -DSRT_REGION_COUNT builds put their counters behind it.
+constexpr uint32_t hq_fields(bool has_models) { return has_models ? 17u : 16u; }
 
 // HAS_MODELS = false compiles every AABB / triangle / mesh-normal path out: scenes of
 // spheres and planes (BASELINE configs 0, 1, 3) get a leaner kernel; the host picks the
@@ -1186,10 +1058,10 @@ __global__ __launch_bounds__(64, USE_BVH ? SRT_TRACE_WAVES_PER_SIMD_BVH : HAS_MO
 	// the sub-job being handed out (wave-uniform): items [sj_next, sj_end); sj_next is sample sj_off of packed pixel sj_qpix
 	uint32_t sj_next = 0, sj_end = 0, sj_off = 0, sj_qpix = 0;
 	float *__restrict__ ring = reinterpret_cast<float *>(lds + p.stage_off); // [10][64] escaped paths awaiting their sky lookup
-	float *__restrict__ hq = ring + 10u * (uint32_t)SRT_RING_CAP; // [16..18][HQ] paths that hit, awaiting their bounce (FIFO)
+	float *__restrict__ hq = ring + 10u * (uint32_t)SRT_RING_CAP; // [hq_fields][HQ] paths that hit, awaiting their bounce (FIFO)
 	constexpr uint32_t HQ = USE_BVH ? SRT_HQ_CAP_BVH : HAS_MODELS ? SRT_HQ_CAP_MODELS : SRT_HQ_CAP;
 #ifdef SRT_REGION_COUNT
-	uint32_t *region_ctr = reinterpret_cast<uint32_t *>(hq + (HAS_MODELS ? (USE_BVH ? 18u : 17u) : 16u) * HQ);
+	uint32_t *region_ctr = reinterpret_cast<uint32_t *>(hq + hq_fields(HAS_MODELS) * HQ);
 	for (int i = lane; i < 2 * SRT_REGION_MAX; i += 64) region_ctr[i] = 0u;
 	__syncthreads();
 #endif
@@ -1204,7 +1076,7 @@ __global__ __launch_bounds__(64, USE_BVH ? SRT_TRACE_WAVES_PER_SIMD_BVH : HAS_MO
 	// least 128 triangles -- microseconds of memory latency against tens of microseconds of scanning. Stores are plain
 	// (write-through), loads bypass the vector L1 (a slot is reused, and the L1 keeps no track of this CU's own stores) and
 	// wait for the wave's stores first (REFILL below).
-	constexpr bool SUSPEND = HAS_MODELS && (!USE_BVH || SRT_BVH_SUSPEND);
+	constexpr bool SUSPEND = HAS_MODELS && !USE_BVH;
 	constexpr uint32_t SQ = (uint32_t)SRT_SQ_CAP, PK = (uint32_t)SRT_PK_CAP;
 	float *__restrict__ sq_base = SUSPEND ? const_cast<float *>((const float *)SRT_COLD(p).scan_queue) + (size_t)SRT_POOL_CTL_WORDS + (SRT_COLD(p).pool_blocks != 0u ? SRT_POOL_REC_FLOATS : (size_t)0) + (size_t)blockIdx.x * (size_t)SRT_SCAN_QUEUE_FLOATS : nullptr;
 	float *__restrict__ pk = sq_base + 2u * 20u * SQ;
@@ -1410,10 +1282,6 @@ __global__ __launch_bounds__(64, USE_BVH ? SRT_TRACE_WAVES_PER_SIMD_BVH : HAS_MO
 							}
 						} else if (!HAS_MODELS) {
 							const Blk16 b0 = ld_blk16(gd), b1 = ld_blk16(gd + 16), b2 = ld_blk16(gd + 32);
-#ifdef SRT_PHASE_CLOCK_LOADS
-							asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-							SRT_CLK(3); // (diagnosis) time until the group's scalar loads have arrived, booked on the PARK slot
-#endif
 							test_block(b0, code & 255u, (int)f2u(gh[1]), 0u, 0);
 							test_block(b1, (code >> 8) & 255u, (int)f2u(gh[2]), 0u, 1);
 							test_block(b2, (code >> 16) & 255u, (int)f2u(gh[3]), 0u, 2);
@@ -1942,7 +1810,6 @@ __global__ __launch_bounds__(64, USE_BVH ? SRT_TRACE_WAVES_PER_SIMD_BVH : HAS_MO
 				// No per-lane integer division and no IEEE division sequence here: pixel, row and sample come from multiplications
 				// by host-made magic numbers (srt_magic_u31), the two quotients by the image size from div_by_rcp.
 				const auto &c = SRT_COLD(p);
-#ifndef SRT_NO_CAMERA_DIET
 				// off < nbs + SUB: one pixel further at most when a pixel has at least SUB samples in this batch, else off / nbs by a
 				// 16-bit reciprocal (exact below 256 for divisors below 128: the error off * (magic * nbs - 2^16) stays under 2^15)
 				static_assert(SUB <= 128u, "off / nbs by the 16-bit reciprocal is exact for off < 256 and nbs < 128 only (tests/csrc/magic_check.cpp)");
@@ -1960,18 +1827,6 @@ __global__ __launch_bounds__(64, USE_BVH ? SRT_TRACE_WAVES_PER_SIMD_BVH : HAS_MO
 				seed = (sample + id * (uint32_t)ns) * c.rd.time * 5304u;
 				float ndc_x = div_by_rcp((float)px + random_float(seed), c.f_width, c.inv_f_width);
 				float ndc_y = div_by_rcp((float)py + random_float(seed), c.f_height, c.inv_f_height);
-#else
-				const uint32_t dq = (nbs >= SUB) ? (off >= nbs ? 1u : 0u) : off / nbs;
-				const uint32_t q = qpix + dq; // owned pixels < 2^31 (checked by the host)
-				const uint32_t sample = c.first_sample + (off - dq * nbs);
-				const uint32_t lrow = q / (uint32_t)width;
-				const int px = (int)(q - lrow * (uint32_t)width);
-				const int py = c.world == 1 ? (int)lrow : global_row((int)lrow, c.rank, c.world, c.rows_per_block); // (wave-uniform choice)
-				const uint32_t id = (uint32_t)px + (uint32_t)py * (uint32_t)width;
-				seed = (sample + id * (uint32_t)ns) * c.rd.time * 5304u;
-				float ndc_x = ((float)px + random_float(seed)) / c.f_width;
-				float ndc_y = ((float)py + random_float(seed)) / c.f_height;
-#endif
 				float sx = ((2.f * ndc_x - 1.f) * c.rd.aspect_ratio) * c.rd.fov_scale;
 				float sy = (1.f - 2.f * ndc_y) * c.rd.fov_scale;
 				const f3 c0 = mk(c.rd.camera_to_world[0].x, c.rd.camera_to_world[0].y, c.rd.camera_to_world[0].z);
@@ -2334,7 +2189,7 @@ __global__ __launch_bounds__(256) void srt_resolve_kernel(const ResolveParams p)
 //   out[8] div3(a, b) != a / b, or div3_by_rcp(a, b, RN(1 / b) or 0) != a / b          out[9] sum of bits of normalize(u - 0.5, 0.37 - u, (r & 0xffff) * 1e-3 - 30)
 //          (a, b: random mantissas and signs, exponents straddling the fast paths' guards,
 //           zero components mixed in)
-//   out[10] Box-Muller's rho as random_normal computes it (sqrt_rsq_zero_ok of -2 log of the raw count, u = 0 selected to +inf)
+//   out[10] Box-Muller's rho as random_normal3 computes it (sqrt_rsq_zero_ok of -2 log of the raw count, u = 0 selected to +inf)
 //           != IEEE sqrt(-2 dm_logf(u))
 //   out[11] the 2^-32 scaling folded away: log_count(r) != log_unit(u), or K' * r != 6.28318548f * u
 //   out[12] sqrt_rsq(bits r) != __builtin_sqrtf for r a float in [2^-96, +inf) (every one of them at stride 1)
@@ -2385,15 +2240,11 @@ __global__ __launch_bounds__(256) void srt_selftest_kernel(unsigned long long *o
 		const float cnt = (float)r;
 		bad_fold += (same_float(log_count(cnt), log_unit(u)) && same_float((6.28318548f * 2.3283064365386963e-10f) * cnt, th)) ? 0 : 1;
 		const float arg = -2.0f * lg;
-#if !defined(SRT_NO_COUNT_FOLD) && !defined(SRT_NO_FAST_SQRT) && !defined(SRT_NO_RSQ_SQRT)
 		{
 			float rho = sqrt_rsq_zero_ok(-2.0f * log_unit_biased<159, false>(cnt));
 			rho = cnt == 0.0f ? DM_INF_F : rho;
 			bad_rn += same_float(rho, __builtin_sqrtf(arg)) ? 0 : 1;
 		}
-#else
-		bad_rn += same_float(sqrt_core(arg), __builtin_sqrtf(arg)) ? 0 : 1;
-#endif
 		bad_sign += same_float(sign_fast(asbits), dm_sign(asbits)) ? 0 : 1;
 		bad_powi += (same_float(powi_uniform(u, pw_n), dm_powi(u, pw_n)) && same_float(powi_uniform(-u, pw_n), dm_powi(-u, pw_n)) &&
 		             same_float(powi_uniform(asbits, pw_n), dm_powi(asbits, pw_n)))
@@ -2455,13 +2306,11 @@ int srt_trace_waves_per_simd(int has_models, int use_bvh) {
 	return !has_models ? SRT_TRACE_WAVES_PER_SIMD : use_bvh ? SRT_TRACE_WAVES_PER_SIMD_BVH : SRT_TRACE_WAVES_PER_SIMD_MODELS;
 }
 int srt_scan_suspend_min(void) { return SRT_SCAN_SUSPEND_MIN; }
-int srt_scan_queue_in_hbm(void) { return 1; }
-int srt_bvh_suspends(void) { return SRT_BVH_SUSPEND; }
 int srt_sub_job_items(int has_models, int use_bvh) { return !has_models ? SRT_SUB_PLAIN : use_bvh ? SRT_SUB_BVH : SRT_SUB_MODELS; }
 
 int srt_trace_lds_floats(int has_models, int use_bvh) {
-	// the sky ring (10 fields), the hit queue (16..17 fields)
-	int n = 10 * SRT_RING_CAP + (has_models ? (use_bvh ? 17 * SRT_HQ_CAP_BVH : 17 * SRT_HQ_CAP_MODELS) : 16 * SRT_HQ_CAP);
+	// the sky ring (10 fields), the hit queue
+	int n = 10 * SRT_RING_CAP + (int)hq_fields(has_models) * (has_models ? (use_bvh ? SRT_HQ_CAP_BVH : SRT_HQ_CAP_MODELS) : SRT_HQ_CAP);
 #ifdef SRT_REGION_COUNT
 	n += 2 * SRT_REGION_MAX; // (waves, lanes) per region
 #endif

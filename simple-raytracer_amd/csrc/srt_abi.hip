@@ -23,9 +23,6 @@
 
 #include "srt_internal.h"
 
-#ifndef SRT_OVERLAP_BATCHES
-#define SRT_OVERLAP_BATCHES 1 // srt_trace: consecutive sample batches on two streams (0: one after the other, A/B only)
-#endif
 #ifndef SRT_SCAN_PAIRS_PER_LAUNCH
 #define SRT_SCAN_PAIRS_PER_LAUNCH 8e12 // srt_trace: ray-triangle pairs one array-scan launch may come to (sample batches)
 #endif
@@ -815,7 +812,7 @@ static int prepare_scene(srt_tracer *t, ScenePrep &sp, const srt_shape *shapes, 
 		if (s.type != SRT_SHAPE_SPHERE && s.type != SRT_SHAPE_PLANE && s.type != SRT_SHAPE_MODEL) continue; // ignored, as render.cl:301-366
 		const uint32_t block_cap = s.type == SRT_SHAPE_SPHERE ? 4u : 2u;
 		// array scan: a big model sits alone in its block (data_off's top bit marks the block until the headers are built)
-		const bool big_model = (!use_bvh || srt_bvh_suspends()) && s.type == SRT_SHAPE_MODEL && s.shape.model.num_triangles >= (uint32_t)srt_scan_suspend_min();
+		const bool big_model = !use_bvh && s.type == SRT_SHAPE_MODEL && s.shape.model.num_triangles >= (uint32_t)srt_scan_suspend_min();
 		const bool prev_big = !runs.empty() && (runs.back().data_off >> 31);
 		if (runs.empty() || runs.back().type != s.type || runs.back().first_shape + runs.back().count != i || runs.back().count == block_cap || big_model || prev_big) {
 			pad_run();
@@ -1229,12 +1226,12 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 		if (const char *env = dev_env("SRT_FORCE_BATCH")) // (development: sample batches smaller than the memory asks for)
 			if (atoi(env) > 0 && (uint32_t)atoi(env) < batch) batch = (uint32_t)atoi(env);
 		// several batches alternate between TWO radiance buffers (below): both must fit the budget
-		if (SRT_OVERLAP_BATCHES && batch < (uint32_t)ns && (size_t)batch * 2 > fit) batch = (uint32_t)(fit / 2 ? fit / 2 : 1);
+		if (batch < (uint32_t)ns && (size_t)batch * 2 > fit) batch = (uint32_t)(fit / 2 ? fit / 2 : 1);
 		if (batch > 4 && (batch & 3u)) batch &= ~3u; // keep the reduce kernel's 16-byte loads aligned
 	}
 	// allocate; if the device cannot give that much right now, fall back to smaller batches
 	while (batch) {
-		const size_t buffers = SRT_OVERLAP_BATCHES && batch < (uint32_t)ns ? 2 : 1;
+		const size_t buffers = batch < (uint32_t)ns ? 2 : 1;
 		hipError_t e = t->radiance.reserve(buffers * (((pixels * (size_t)batch * 3 + 4) + 3) & ~(size_t)3)); // each buffer a whole number of 16-byte units
 		if (e == hipSuccess) break;
 		(void)hipGetLastError(); // clear the sticky out-of-memory state
@@ -1260,8 +1257,8 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 	// the launch-end ray pool's records (84 MB), and a second set of both only when sample batches overlap: 320 MB for a
 	// one-launch frame on 256 CUs, 640 MB for an overlapped one. If the device cannot give that, the
 	// dispatch runs without the pool (every wave scans its own remainder: slower tails, same canvas) before it fails.
-	const bool wants_scan_queue = t->num_models > 0 && (!t->bvh_active || srt_bvh_suspends()) && srt_scan_queue_in_hbm();
-	const bool overlap_batches = SRT_OVERLAP_BATCHES && n_batches > 1;
+	const bool wants_scan_queue = t->num_models > 0 && !t->bvh_active;
+	const bool overlap_batches = n_batches > 1;
 	size_t scan_waves = (size_t)slots;
 	{
 		const unsigned long long most_items = (unsigned long long)pixels * batch;
@@ -1336,7 +1333,7 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 	// and most waves gone: half of a launch of the 10^5-triangle array scan) runs under the next batch instead of leaving
 	// the GPU idle. The ordered reductions stay on the caller's stream, in batch order; a batch's trace waits for the
 	// reduction that last read its buffer.
-	const bool overlap = SRT_OVERLAP_BATCHES && n_batches > 1;
+	const bool overlap = n_batches > 1;
 	t->batches_overlapped = overlap;
 	const size_t radiance_stride = ((pixels * (size_t)batch * 3 + 4) + 3) & ~(size_t)3; // floats per buffer: a multiple of 4, so that the second buffer's float4 stores stay 16-byte aligned for any pixel count and batch size
 	if (overlap) {
