@@ -336,6 +336,47 @@ int srt_reset_denoise_history(srt_tracer *t);
  * SRT_ERR_STATE when temporal reprojection was never enabled on this handle. */
 int srt_read_denoise_history(srt_tracer *t, float *colour_count, float *moments, float *guide, srt_render_data *camera, int *valid);
 
+/* ---- object motion for the temporal stage (new) --------------------------------------------------------------------- */
+
+/* Opt-in, on top of srt_set_denoise_temporal: the history survives an srt_update_scene that only moves shapes. While it is
+ * on, the feature pass also stores one shape index per pixel (the first hit of feature sample 0 of the latest dispatch,
+ * 0xffffffff: no hit, or a shape without a material), the handle keeps the scene the history frame was traced with, and
+ * srt_update_scene compares the new scene with *that* scene: the history is kept when n_shapes, every shape's type and
+ * material, the materials, srt_scene_data and the triangle array are the same in bytes and a model keeps its
+ * triangle_index and num_triangles. Only a sphere's position / radius, a plane's position / normal and a model's
+ * transform (with bounding_min / bounding_max, the world box the front-end derives from it) may differ. Per shape the host then derives (in double, rounded to float) a state and the maps "now -> then":
+ *   A (3x4, rows): current world position -> history world position;  B (3x3, rows): current normal -> history normal
+ *   sphere  X' = p_c + (r_c / r_h)(X - p_h)          plane  X' = p_c + R (X - p_h), R the minimal rotation n_h -> n_c
+ *   model   M_c M_h^-1 (the affine part: columns 0..2 and the translation of `transform`)
+ * (history -> current; A is the inverse, B the transpose of the linear part). A pixel of a moved shape looks its history up
+ * at the projection of A X into the history camera and accepts only taps that showed the same shape; a pixel of a static
+ * shape does what it does without object motion, except that a tap which showed a moved shape does not count. A frame in
+ * which nothing moved is bit for bit the frame without object motion. A frame traced with two different scenes (an
+ * srt_update_scene with other bytes while samples are on the canvas) does not become a history at the next clear.
+ * Lighting is not tracked: a static pixel keeps its history although a moved object's shadow or reflection on it changed;
+ * history_limit bounds the lag. 8 B of device memory per pixel, allocated on the first enable. */
+enum { SRT_MOTION_STATIC = 0, SRT_MOTION_MOVED = 1, SRT_MOTION_NO_HISTORY = 2 };
+#define SRT_MOTION_WORDS 22 /* per shape: state, A[12], B[9] (the floats' bits) */
+
+/* enable != 0: on. SRT_ERR_STATE unless temporal reprojection is on (so never on a partitioned handle). Turning temporal
+ * or the denoiser off turns it off. Every change of the switch drops the history. */
+int srt_set_denoise_object_motion(srt_tracer *t, int enable);
+/* The shape indices (blocking; NULL skips an output; width*height words each): current = what the feature pass wrote since
+ * the last clear (undefined before the first dispatch), history = the history frame's (all 0xffffffff without a history).
+ * SRT_ERR_STATE when object motion was never enabled on this handle. */
+int srt_read_denoise_shape_ids(srt_tracer *t, uint32_t *current, uint32_t *history);
+/* The table the next filter would use: *n_shapes rows of SRT_MOTION_WORDS words into table (capacity_shapes rows of room;
+ * SRT_ERR_INVALID when fewer than *n_shapes, which is still set), *any_moved != 0 when a row is not STATIC (the moved
+ * set-up kernel runs). Without a history every row is STATIC / identity. SRT_ERR_STATE when object motion is off. */
+int srt_read_denoise_motion(srt_tracer *t, uint32_t *table, size_t capacity_shapes, size_t *n_shapes, int *any_moved);
+/* Host-only (no device): the comparison and the table of the rules above for a history scene and a current scene.
+ * *keep = 0: the history would be dropped (table untouched); else table receives n_shapes rows. SRT_ERR_INVALID on NULL
+ * arguments (arrays of length 0 may be NULL). */
+int srt_motion_table_host(const srt_shape *h_shapes, size_t h_n_shapes, const srt_triangle *h_triangles, size_t h_n_triangles,
+                          const srt_material *h_materials, size_t h_n_materials, const srt_scene_data *h_scene,
+                          const srt_shape *c_shapes, size_t c_n_shapes, const srt_triangle *c_triangles, size_t c_n_triangles,
+                          const srt_material *c_materials, size_t c_n_materials, const srt_scene_data *c_scene, uint32_t *table, int *keep);
+
 /* Device self-test of the deterministic math (tests only). Walks r = 0, stride, ... over
  * all 2^32 RNG outputs: out[0..2] = mismatch counts of the kernel-local sqrt / log / cos
  * specialisations against their generic definitions (must be 0); out[3..7] = sums of the

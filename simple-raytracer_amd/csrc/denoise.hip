@@ -171,6 +171,7 @@ int srt_denoise_clear(srt_tracer *t) {
 	SRT_HIP(t, hipMemsetAsync(t->dn_ah.ptr, 0, px * 16, t->stream));
 	SRT_HIP(t, hipMemsetAsync(t->dn_mom.ptr, 0, px * 4, t->stream));
 	t->dn_T = t->dn_P = t->dn_F = 0;
+	t->om_mixed = false;
 	return SRT_OK;
 }
 
@@ -183,12 +184,14 @@ int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples
 	fp.albedo_hits = t->dn_ah.ptr;
 	fp.num_pixels = (uint32_t)full_pixels(t);
 	fp.feature_samples = fs;
-	srt_launch_features(fp, t->stream);
+	if (t->om_on) srt_launch_features_ids(fp, t->om_ids[t->om_cur].ptr, t->stream); // temporal.hip: object motion
+	else srt_launch_features(fp, t->stream);
 	SRT_HIP(t, hipGetLastError());
 	t->dn_T += 1;
 	t->dn_P += ns;
 	t->dn_F += fs;
 	t->dn_cam = p.rd;
+	if (t->om_on && fs == 0) t->om_mixed = true; // a dispatch without feature rays wrote no shape indices
 	t->tp_fresh = false; // temporal.hip: the staging set no longer holds what is traced since the clear
 	return SRT_OK;
 }
@@ -265,6 +268,7 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 	if (!params || !params->enable) {
 		t->dn_on = false;
 		t->tp_on = false; // temporal reprojection is a stage of the denoiser
+		t->om_on = false; // and object motion a stage of that
 		srt_temporal_drop(t);
 		return SRT_OK;
 	}

@@ -228,6 +228,8 @@ void srt_launch_reduce(const ReduceParams &p, void *stream);
 /* the same reduction that also adds (1/n) sum_k lum(radiance_k)^2 into moments[pixel] (denoiser; `running`.w carries the sum across batches) */
 void srt_launch_reduce_moments(const ReduceParams &p, void *stream);
 void srt_launch_features(const FeatureParams &p, void *stream);
+/* the same, also storing the shape index of feature sample 0 per pixel (0xffffffff: no hit or no material) into shape_ids */
+void srt_launch_features_ids(const FeatureParams &p, uint32_t *shape_ids, void *stream);
 int srt_trace_waves_per_simd(int has_models, int use_bvh);
 int srt_trace_resident_waves_per_cu(const TraceParams &p, bool count_triangles); /* from the runtime's occupancy calculator */
 int srt_scan_suspend_min(void); /* array scan: models of at least this many triangles sit alone in their block and are flagged big */

@@ -2045,88 +2045,17 @@ __device__ __forceinline__ f3 winner_normal(const TraceParams &p, int best, uint
 
 template <bool HAS_MODELS, bool USE_BVH>
 __global__ __launch_bounds__(64) void srt_features_kernel(const FeatureParams fp) {
-	const TraceParams &p = fp.tp;
-	const uint32_t q = blockIdx.x * 64u + threadIdx.x;
-	if (q >= fp.num_pixels) return;
-#ifdef SRT_REGION_COUNT
-	__shared__ uint32_t region_ctr[2 * SRT_REGION_MAX]; // (development builds: the shared helpers count regions; nobody reads these)
-#endif
-	const int width = p.rd.width;
-	const uint32_t lrow = (__umulhi(q, p.width_magic) + q) >> p.width_shift; // q / width (full frame: the pixel id is q)
-	const int px = (int)(q - lrow * (uint32_t)width), py = (int)lrow;
-	const uint32_t ns = (uint32_t)p.rd.num_samples;
-	const f3 c0 = mk(p.rd.camera_to_world[0].x, p.rd.camera_to_world[0].y, p.rd.camera_to_world[0].z);
-	const f3 c1 = mk(p.rd.camera_to_world[1].x, p.rd.camera_to_world[1].y, p.rd.camera_to_world[1].z);
-	const f3 c2 = mk(p.rd.camera_to_world[2].x, p.rd.camera_to_world[2].y, p.rd.camera_to_world[2].z);
-	const f3 cam = mk(p.rd.camera_to_world[3].x, p.rd.camera_to_world[3].y, p.rd.camera_to_world[3].z);
-	BvhStackEntry bvh_stack[USE_BVH ? SRT_BVH_STACK_CAP + 1 : 1];
-	uint32_t n_tri = 0, n_tri_u = 0;
-	f3 nsum = mk(0.f, 0.f, 0.f), asum = mk(0.f, 0.f, 0.f);
-	float tsum = 0.f, hits = 0.f;
-	for (uint32_t sample = 0; sample < fp.feature_samples; sample++) {
-		// ---- camera ray: srt_trace_kernel CAMERA ----
-		uint32_t seed = (sample + q * ns) * p.rd.time * 5304u;
-		const float ndc_x = div_by_rcp((float)px + random_float(seed), p.f_width, p.inv_f_width);
-		const float ndc_y = div_by_rcp((float)py + random_float(seed), p.f_height, p.inv_f_height);
-		const float sx = ((2.f * ndc_x - 1.f) * p.rd.aspect_ratio) * p.rd.fov_scale;
-		const float sy = (1.f - 2.f * ndc_y) * p.rd.fov_scale;
-		const f3 org = cam;
-		const f3 dir = normalize3(mat_cols_by_vec(c0, c1, c2, cam, mk(sx, sy, -1.0f), 0.0f));
-		// ---- closest_intersection: srt_trace_kernel EXTEND (test_block), without the scan queue ----
-		float tmin = DM_INF_F;
-		int best = -1;
-		uint32_t best_tri = 0;
-		f3 inv = mk(0.f, 0.f, 0.f);
-		if (HAS_MODELS) inv = mk(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
-		auto test_block = [&](const Blk16 &b, uint32_t code, int base) {
-			const uint32_t type1 = code & 3u;
-			if (type1 == SRT_SHAPE_SPHERE + 1u) {
-				if (((code >> 2) & 7u) <= 2u) test_spheres<2>(b, org, dir, base, tmin, best);
-				else test_spheres<4>(b, org, dir, base, tmin, best);
-			} else if (type1 == SRT_SHAPE_PLANE + 1u) {
-				test_planes2(b, (code >> 2) & 7u, org, dir, base, tmin, best);
-			} else if (HAS_MODELS && type1 == SRT_SHAPE_MODEL + 1u) {
-				if (test_aabb(b.v[0], b.v[1], b.v[2], b.v[4], b.v[5], b.v[6], org, inv, tmin)) {
-					if (USE_BVH) walk_bvh<false>(reinterpret_cast<const float4 *>(p.bvh_blocks), bvh_stack, f2u(b.v[3]), org, dir, base, tmin, best, best_tri, n_tri, n_tri_u SRT_RC_ARG);
-					else test_triangles<false>(p.wtris, f2u(b.v[3]), f2u(b.v[7]), org, dir, base, tmin, best, best_tri, n_tri_u SRT_RC_ARG);
-				}
-				if (((code >> 2) & 7u) > 1u && test_aabb(b.v[8], b.v[9], b.v[10], b.v[12], b.v[13], b.v[14], org, inv, tmin)) {
-					if (USE_BVH) walk_bvh<false>(reinterpret_cast<const float4 *>(p.bvh_blocks), bvh_stack, f2u(b.v[11]), org, dir, base + 1, tmin, best, best_tri, n_tri, n_tri_u SRT_RC_ARG);
-					else test_triangles<false>(p.wtris, f2u(b.v[11]), f2u(b.v[15]), org, dir, base + 1, tmin, best, best_tri, n_tri_u SRT_RC_ARG);
-				}
-			}
-		};
-		for (int g = 0; g < p.num_runs; g++) {
-			float gh[4];
-			ld_uniform<4, 16>(reinterpret_cast<const float *>(p.runs + g), gh);
-			const uint32_t code = f2u(gh[0]);
-			const float *__restrict__ gd = p.run_data + 48 * g;
-			test_block(ld_blk16(gd), code & 255u, (int)f2u(gh[1]));
-			if ((code >> 8) & 255u) test_block(ld_blk16(gd + 16), (code >> 8) & 255u, (int)f2u(gh[2]));
-			if ((code >> 16) & 255u) test_block(ld_blk16(gd + 32), (code >> 16) & 255u, (int)f2u(gh[3]));
-		}
-		// a shape without a material counts as a miss (render.cl:404)
-		const int material = best >= 0 ? p.winners[best].material : -1;
-		if (material >= 0) {
-			f3 nrm = winner_normal<HAS_MODELS, USE_BVH>(p, best, best_tri, org + dir * tmin);
-			const bool front = dot3(nrm, dir) < 0.0f;
-			nrm = nrm * (front ? 1.0f : -1.0f);
-			nsum = nsum + nrm;
-			tsum = tsum + tmin;
-			const srt_float3 &mc = p.materials[material].color;
-			asum = asum + mk(mc.x, mc.y, mc.z);
-			hits = hits + 1.0f;
-		} else {
-			asum = asum + mk(1.f, 1.f, 1.f);
-		}
-	}
-	float4 *nd = reinterpret_cast<float4 *>(fp.normal_depth) + q;
-	float4 *ah = reinterpret_cast<float4 *>(fp.albedo_hits) + q;
-	float4 a = *nd, b = *ah;
-	a.x += nsum.x, a.y += nsum.y, a.z += nsum.z, a.w += tsum;
-	b.x += asum.x, b.y += asum.y, b.z += asum.z, b.w += hits;
-	*nd = a;
-	*ah = b;
+#define SRT_FEATURES_IDS 0
+#include "features_body.inc"
+#undef SRT_FEATURES_IDS
+}
+
+// the same, and the shape index per pixel for the temporal stage's object motion (temporal.hip)
+template <bool HAS_MODELS, bool USE_BVH>
+__global__ __launch_bounds__(64) void srt_features_ids_kernel(const FeatureParams fp, uint32_t *__restrict__ shape_ids) {
+#define SRT_FEATURES_IDS 1
+#include "features_body.inc"
+#undef SRT_FEATURES_IDS
 }
 
 // ---------------------------------------------------------------------------------
@@ -2392,4 +2321,12 @@ void srt_launch_features(const FeatureParams &p, void *stream) {
 	const bool models = p.tp.num_models > 0, bvh = p.tp.use_bvh != 0;
 	const FeatureKernel k = !models ? srt_features_kernel<false, false> : bvh ? srt_features_kernel<true, true> : srt_features_kernel<true, false>;
 	hipLaunchKernelGGL(k, dim3((p.num_pixels + 63u) / 64u), dim3(64), 0, (hipStream_t)stream, p);
+}
+
+void srt_launch_features_ids(const FeatureParams &p, uint32_t *shape_ids, void *stream) {
+	if (p.num_pixels == 0 || p.feature_samples == 0) return;
+	typedef void (*FeatureKernel)(const FeatureParams, uint32_t *);
+	const bool models = p.tp.num_models > 0, bvh = p.tp.use_bvh != 0;
+	const FeatureKernel k = !models ? srt_features_ids_kernel<false, false> : bvh ? srt_features_ids_kernel<true, true> : srt_features_ids_kernel<true, false>;
+	hipLaunchKernelGGL(k, dim3((p.num_pixels + 63u) / 64u), dim3(64), 0, (hipStream_t)stream, p, shape_ids);
 }

@@ -670,6 +670,9 @@ void srt_destroy(srt_tracer *t) {
 	t->dn_col.release();
 	t->tp_set[0].release();
 	t->tp_set[1].release();
+	t->om_ids[0].release();
+	t->om_ids[1].release();
+	t->om_table_dev.release();
 	if (t->ev_t0) (void)hipEventDestroy(t->ev_t0);
 	if (t->ev_t1) (void)hipEventDestroy(t->ev_t1);
 	if (t->ev_r0) (void)hipEventDestroy(t->ev_r0);
@@ -724,7 +727,13 @@ int srt_update_scene(srt_tracer *t, const srt_shape *shapes, size_t n_shapes, co
 			}
 		}
 		const int rc = update_scene_impl(t, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
-		if (t && (rc != SRT_OK || bytes.empty() || bytes != t->scene_bytes)) srt_temporal_drop(t);
+		if (t && t->om_on) { // temporal.hip: object motion compares with the history's scene and keeps what only moved
+			const int mrc = srt_motion_update_scene(t, bytes, rc);
+			if (rc == SRT_OK && mrc != SRT_OK) {
+				t->scene_bytes.swap(bytes);
+				return mrc;
+			}
+		} else if (t && (rc != SRT_OK || bytes.empty() || bytes != t->scene_bytes)) srt_temporal_drop(t);
 		if (t) t->scene_bytes.swap(bytes);
 		return rc;
 	} catch (const std::bad_alloc &) {

@@ -110,6 +110,16 @@ struct srt_tracer {
 	bool tp_fresh = false;   // tp_set[1 - tp_cur] holds the integration of what is traced since the clear (a filter ran after the last trace)
 	srt_render_data tp_cam{}; // the history frame's render data
 	std::vector<uint8_t> scene_bytes; // the last srt_update_scene's arrays and scene data (the history survives an unchanged scene)
+	// object motion (temporal.hip; srt_set_denoise_object_motion): the feature pass stores a shape index per pixel into
+	// om_ids[om_cur]; the commit swaps, so om_ids[1 - om_cur] belongs to the history, traced with the scene om_hist_scene
+	bool om_on = false;
+	DevBuf<uint32_t> om_ids[2];
+	int om_cur = 0;
+	bool om_mixed = false;     // the frame on the canvas was traced with more than one scene (or without indices): it cannot become a history
+	bool om_any_moved = false; // a shape of om_table is not SRT_MOTION_STATIC (the moved set-up kernel runs)
+	std::vector<uint8_t> om_hist_scene; // scene_bytes of the history frame
+	std::vector<uint32_t> om_table;     // SRT_MOTION_WORDS per shape of the current scene: the next filter's current -> history maps
+	DevBuf<uint32_t> om_table_dev;
 	hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;
 	bool have_trace_ev = false, have_resolve_ev = false, have_kernel_ev = false;
 	std::string err;
@@ -137,6 +147,9 @@ int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb);
 int srt_temporal_setup(srt_tracer *t, float4 *col, uint32_t *argb, const float4 **guide);
 int srt_temporal_commit(srt_tracer *t);
 void srt_temporal_drop(srt_tracer *t);
+/* srt_update_scene with object motion on (`bytes`: the new scene, scene_bytes still the previous call's; rc: the update's
+ * result): keeps or drops the history and rebuilds the motion table */
+int srt_motion_update_scene(srt_tracer *t, const std::vector<uint8_t> &bytes, int rc);
 /* srt_trace whose last reduction also resolves into fused_argb (device, owned pixels x 4 bytes; NULL: plain srt_trace) */
 extern "C" int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fused_argb, uint32_t ticks_stopped);
 /* one scene for several handles: the host pass once (members[0]'s acceleration mode and hierarchy cache), the uploads of all

@@ -22,6 +22,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/srt_abi.h"
 #include "detmath.h"
@@ -72,110 +73,32 @@ __device__ __forceinline__ uint32_t tonemap(float x, float y, float z) {
 __device__ __forceinline__ float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
 __device__ __forceinline__ bool finite3(float4 c) { return __builtin_isfinite(c.x) && __builtin_isfinite(c.y) && __builtin_isfinite(c.z); }
 
+// object motion (srt_set_denoise_object_motion): per-pixel shape indices of the frame and of the history, and the table of
+// SRT_MOTION_WORDS words per shape {state, A (3x4, rows; current world -> history world), B (3x3, rows; normals)}
+struct MotionParams {
+	const uint32_t *ids, *h_ids;
+	const uint32_t *table;
+	uint32_t n_shapes;
+};
+
 __global__ __launch_bounds__(256) void srt_temporal_setup_kernel(const TemporalParams p) {
-	const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
-	if (x >= p.width || y >= p.height) return;
-	const uint32_t i = (uint32_t)y * (uint32_t)p.width + (uint32_t)x;
-	// ---- the spatial set-up (srt_denoise_setup_kernel's expressions, divisor T) ----
-	const float4 c = p.canvas[i], nd = p.normal_depth[i], ah = p.albedo_hits[i];
-	const float m = p.moments[i];
-	const float4 cc = make_float4(c.x / p.T, c.y / p.T, c.z / p.T, 0.f);
-	const float l = lum(cc.x, cc.y, cc.z);
-	const float m2c = m / p.T;
-	float v = m2c - l * l;
-	v = v > 0.f ? v : 0.f;
-	v = v / p.P;
-	if (!__builtin_isfinite(v)) v = 0.f;
-	const float hits = ah.w;
-	float nx = 0.f, ny = 0.f, nz = 0.f, z = 0.f;
-	if (hits > 0.f) {
-		const float len = sqrtf(nd.x * nd.x + nd.y * nd.y + nd.z * nd.z);
-		if (len > 0.f) nx = nd.x / len, ny = nd.y / len, nz = nd.z / len;
-		z = nd.w / hits;
-	}
-	const float4 g0 = make_float4(nx, ny, nz, z);
-	const float4 g1 = make_float4(ah.x / p.F, ah.y / p.F, ah.z / p.F, hits / p.F);
+#define SRT_TEMPORAL_MOTION 0
+#include "temporal_body.inc"
+#undef SRT_TEMPORAL_MOTION
+}
 
-	// ---- reprojection ----
-	float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sh = 0.f, s1 = 0.f, s2 = 0.f;
-	if (p.mode != TP_NONE && g1.w > 0.f && finite3(cc)) {
-		float D = z;
-		int x0 = x, y0 = y;
-		float ax = 0.f, ay = 0.f;
-		bool any = true;
-		if (p.mode == TP_PROJECT) {
-			// the camera ray through the pixel's centre (kernels.hip CAMERA with 0.5 for the jitter; its division through the
-			// host's reciprocal is the IEEE quotient)
-			const float ndc_x = ((float)x + 0.5f) / p.f_width, ndc_y = ((float)y + 0.5f) / p.f_height;
-			const float sx = ((2.f * ndc_x - 1.f) * p.aspect) * p.fov;
-			const float sy = (1.f - 2.f * ndc_y) * p.fov;
-			const float rx = ((p.c0[0] * sx + p.c1[0] * sy) + p.c2[0] * -1.0f) + p.cam[0] * 0.0f;
-			const float ry = ((p.c0[1] * sx + p.c1[1] * sy) + p.c2[1] * -1.0f) + p.cam[1] * 0.0f;
-			const float rz = ((p.c0[2] * sx + p.c1[2] * sy) + p.c2[2] * -1.0f) + p.cam[2] * 0.0f;
-			const float rs = dm_rsqrtf(rx * rx + ry * ry + rz * rz);
-			const float dx = rx * rs, dy = ry * rs, dz = rz * rs;
-			const float ex = (p.cam[0] + z * dx) - p.cam_h[0], ey = (p.cam[1] + z * dy) - p.cam_h[1], ez = (p.cam[2] + z * dz) - p.cam_h[2];
-			D = sqrtf(ex * ex + ey * ey + ez * ez);
-			const float vx = (p.rinv[0] * ex + p.rinv[1] * ey) + p.rinv[2] * ez;
-			const float vy = (p.rinv[3] * ex + p.rinv[4] * ey) + p.rinv[5] * ez;
-			const float vz = (p.rinv[6] * ex + p.rinv[7] * ey) + p.rinv[8] * ez;
-			const float qx = vx / -vz, qy = vy / -vz;
-			const float fx = ((qx / (p.aspect_h * p.fov_h) + 1.f) / 2.f) * p.f_width - 0.5f;
-			const float fy = ((1.f - qy / p.fov_h) / 2.f) * p.f_height - 0.5f;
-			// in front of the history camera, and a 2x2 that touches the image (this also keeps the conversions in range)
-			any = vz < 0.f && fx > -1.f && fx < p.f_width && fy > -1.f && fy < p.f_height;
-			if (any) {
-				const float flx = floorf(fx), fly = floorf(fy);
-				x0 = (int)flx, y0 = (int)fly;
-				ax = fx - flx, ay = fy - fly;
-			}
-		}
-		if (any) {
-			for (int k = 0; k < 4; k++) {
-				const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
-				const float w = (k & 1 ? ax : 1.f - ax) * (k >> 1 ? ay : 1.f - ay);
-				if (p.mode == TP_IDENTITY && k) break;
-				if (qx < 0 || qx >= p.width || qy < 0 || qy >= p.height) continue;
-				const uint32_t j = (uint32_t)qy * (uint32_t)p.width + (uint32_t)qx;
-				const float4 hg1 = p.h_guide[2 * j + 1];
-				const float4 hc = p.h_cc[j];
-				if (!(hg1.w > 0.f) || !finite3(hc)) continue;
-				const float4 hg0 = p.h_guide[2 * j];
-				if (!(nx * hg0.x + ny * hg0.y + nz * hg0.z >= p.normal_threshold)) continue;
-				if (!(fabsf(hg0.w - D) <= p.depth_threshold * D)) continue;
-				const float2 hm = p.h_m[j];
-				sw += w;
-				sr += w * hc.x, sg += w * hc.y, sb += w * hc.z;
-				sh += w * hc.w;
-				s1 += w * hm.x, s2 += w * hm.y;
-			}
-		}
-	}
-
-	// ---- integration ----
-	float h = 0.f;
-	if (sw >= 0.01f) h = fminf(sh / sw, p.limit);
-	float4 o = make_float4(cc.x, cc.y, cc.z, v);
-	float m1 = l, m2 = m2c, n = p.P;
-	if (h > 0.f) {
-		n = p.P + h;
-		const float hr = sr / sw, hgc = sg / sw, hb = sb / sw, h1 = s1 / sw, h2 = s2 / sw;
-		o.x = (p.P * cc.x + h * hr) / n;
-		o.y = (p.P * cc.y + h * hgc) / n;
-		o.z = (p.P * cc.z + h * hb) / n;
-		m1 = (p.P * l + h * h1) / n;
-		m2 = (p.P * m2c + h * h2) / n;
-		float V = m2 - m1 * m1;
-		V = V > 0.f ? V : 0.f;
-		V = V / n;
-		o.w = __builtin_isfinite(V) ? V : 0.f;
-	}
-	p.o_cc[i] = make_float4(o.x, o.y, o.z, fminf(n, p.limit));
-	p.o_m[i] = make_float2(m1, m2);
-	p.o_guide[2 * i] = g0;
-	p.o_guide[2 * i + 1] = g1;
-	if (p.out) p.out[i] = o;
-	if (p.argb) p.argb[i] = tonemap(o.x, o.y, o.z);
+// The set-up when object motion is on and a shape of the table is not STATIC. Per pixel p with shape index s = ids[p]:
+//   s invalid or NO_HISTORY   no history
+//   s STATIC                  the arithmetic above (the identity tap for the same camera, else the projection of X), and a
+//                             tap whose history shape index is a MOVED / NO_HISTORY shape does not count
+//   s MOVED                   X_h = A_s X (rows: ((a0 X.x + a1 X.y) + a2 X.z) + a3), projected into the history camera also
+//                             when the cameras are the same, D = |X_h - cam_h|; a tap must carry history shape index s, and
+//                             its normal is compared with normalise(B_s N_p) (zero length or not finite: no history)
+// tests/motion_ref.py restates it.
+__global__ __launch_bounds__(256) void srt_temporal_motion_kernel(const TemporalParams p, const MotionParams mp) {
+#define SRT_TEMPORAL_MOTION 1
+#include "temporal_body.inc"
+#undef SRT_TEMPORAL_MOTION
 }
 
 size_t full_pixels(const srt_tracer *t) { return (size_t)t->width * (size_t)t->height; }
@@ -209,6 +132,159 @@ bool invert_rotation(const srt_render_data &rd, float out[9]) {
 	return true;
 }
 
+// ---- object motion: the per-shape table (host, double) ----------------------------------------------------------------
+
+struct SceneView { // one scene as srt_update_scene received it
+	const srt_shape *shapes;
+	size_t n_shapes;
+	const void *tris, *mats, *scene;
+	size_t tri_bytes, mat_bytes;
+};
+
+// srt_tracer::scene_bytes: four sizes, then the shapes, triangles, materials and the scene data
+bool view_of(const std::vector<uint8_t> &bytes, SceneView &v) {
+	if (bytes.size() < 32) return false;
+	size_t nb[4];
+	memcpy(nb, bytes.data(), 32);
+	const uint8_t *b = bytes.data() + 32;
+	v.shapes = reinterpret_cast<const srt_shape *>(b);
+	v.n_shapes = nb[0] / sizeof(srt_shape);
+	v.tris = b + nb[0], v.tri_bytes = nb[1];
+	v.mats = b + nb[0] + nb[1], v.mat_bytes = nb[2];
+	v.scene = b + nb[0] + nb[1] + nb[2];
+	return true;
+}
+
+bool inv3(const double m[3][3], double out[3][3]) {
+	const double a = m[1][1] * m[2][2] - m[1][2] * m[2][1], b = m[1][2] * m[2][0] - m[1][0] * m[2][2], d = m[1][0] * m[2][1] - m[1][1] * m[2][0];
+	const double det = m[0][0] * a + m[0][1] * b + m[0][2] * d;
+	if (!(det != 0.0) || !std::isfinite(det)) return false;
+	out[0][0] = a / det, out[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det, out[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det;
+	out[1][0] = b / det, out[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det, out[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det;
+	out[2][0] = d / det, out[2][1] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det, out[2][2] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det;
+	for (int r = 0; r < 3; r++)
+		for (int c = 0; c < 3; c++)
+			if (!std::isfinite(out[r][c])) return false;
+	return true;
+}
+
+void identity_row(uint32_t *row, uint32_t state) {
+	float f[21] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1};
+	row[0] = state;
+	memcpy(row + 1, f, sizeof f);
+}
+
+// Xh = lin Xc + tr and the normal map nrm, rounded to float; false when a float is not finite
+bool store_row(uint32_t *row, const double lin[3][3], const double tr[3], const double nrm[3][3]) {
+	float f[21];
+	for (int r = 0; r < 3; r++) {
+		for (int c = 0; c < 3; c++) f[4 * r + c] = (float)lin[r][c], f[12 + 3 * r + c] = (float)nrm[r][c];
+		f[4 * r + 3] = (float)tr[r];
+	}
+	for (int k = 0; k < 21; k++)
+		if (!std::isfinite(f[k])) return false;
+	row[0] = SRT_MOTION_MOVED;
+	memcpy(row + 1, f, sizeof f);
+	return true;
+}
+
+bool sphere_row(const srt_sphere &h, const srt_sphere &c, uint32_t *row) {
+	const double rh = h.radius, rc = c.radius;
+	if (!(rh > 0.0) || !(rc > 0.0) || !std::isfinite(rh) || !std::isfinite(rc)) return false;
+	const double s = rh / rc, ph[3] = {h.position.x, h.position.y, h.position.z}, pc[3] = {c.position.x, c.position.y, c.position.z};
+	double lin[3][3] = {{s, 0, 0}, {0, s, 0}, {0, 0, s}}, nrm[3][3] = {{rc / rh, 0, 0}, {0, rc / rh, 0}, {0, 0, rc / rh}}, tr[3];
+	for (int k = 0; k < 3; k++) tr[k] = ph[k] - s * pc[k];
+	return store_row(row, lin, tr, nrm);
+}
+
+bool plane_row(const srt_plane &h, const srt_plane &c, uint32_t *row) {
+	double u[3] = {h.normal.x, h.normal.y, h.normal.z}, v[3] = {c.normal.x, c.normal.y, c.normal.z};
+	const double lu = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]), lv = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+	if (!(lu > 0.0) || !(lv > 0.0) || !std::isfinite(lu) || !std::isfinite(lv)) return false;
+	for (int k = 0; k < 3; k++) u[k] /= lu, v[k] /= lv;
+	const double k3[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
+	const double cs = u[0] * v[0] + u[1] * v[1] + u[2] * v[2];
+	if (!(cs > -1.0 + 1e-12)) return false;
+	const double K[3][3] = {{0, -k3[2], k3[1]}, {k3[2], 0, -k3[0]}, {-k3[1], k3[0], 0}};
+	double R[3][3], Rt[3][3], tr[3]; // R: history -> current
+	for (int r = 0; r < 3; r++)
+		for (int q = 0; q < 3; q++) {
+			double k2 = 0.0;
+			for (int j = 0; j < 3; j++) k2 += K[r][j] * K[j][q];
+			R[r][q] = (r == q ? 1.0 : 0.0) + K[r][q] + k2 / (1.0 + cs);
+		}
+	for (int r = 0; r < 3; r++)
+		for (int q = 0; q < 3; q++) Rt[r][q] = R[q][r];
+	const double ph[3] = {h.position.x, h.position.y, h.position.z}, pc[3] = {c.position.x, c.position.y, c.position.z};
+	for (int r = 0; r < 3; r++) tr[r] = ph[r] - (Rt[r][0] * pc[0] + Rt[r][1] * pc[1] + Rt[r][2] * pc[2]);
+	return store_row(row, Rt, tr, Rt);
+}
+
+// the affine part of `transform` (columns 0..2 and the translation, as the kernels' mat_by_vec reads it)
+bool model_row(const srt_model &h, const srt_model &c, uint32_t *row) {
+	double Lh[3][3], Lc[3][3], Lci[3][3], Lhi[3][3], lin[3][3], fwd[3][3], nrm[3][3], tr[3];
+	for (int k = 0; k < 3; k++) {
+		Lh[0][k] = h.transform[k].x, Lh[1][k] = h.transform[k].y, Lh[2][k] = h.transform[k].z;
+		Lc[0][k] = c.transform[k].x, Lc[1][k] = c.transform[k].y, Lc[2][k] = c.transform[k].z;
+	}
+	const double th[3] = {h.transform[3].x, h.transform[3].y, h.transform[3].z}, tc[3] = {c.transform[3].x, c.transform[3].y, c.transform[3].z};
+	for (int k = 0; k < 3; k++)
+		if (!std::isfinite(th[k]) || !std::isfinite(tc[k])) return false;
+	if (!inv3(Lc, Lci) || !inv3(Lh, Lhi)) return false;
+	for (int r = 0; r < 3; r++)
+		for (int q = 0; q < 3; q++) {
+			lin[r][q] = (Lh[r][0] * Lci[0][q] + Lh[r][1] * Lci[1][q]) + Lh[r][2] * Lci[2][q]; // current -> history
+			fwd[r][q] = (Lc[r][0] * Lhi[0][q] + Lc[r][1] * Lhi[1][q]) + Lc[r][2] * Lhi[2][q]; // history -> current
+		}
+	for (int r = 0; r < 3; r++) {
+		tr[r] = th[r] - ((lin[r][0] * tc[0] + lin[r][1] * tc[1]) + lin[r][2] * tc[2]);
+		for (int q = 0; q < 3; q++) nrm[r][q] = fwd[q][r];
+	}
+	return store_row(row, lin, tr, nrm);
+}
+
+// the rules of include/srt_abi.h: false = drop the history; else `table` gets SRT_MOTION_WORDS words per shape
+bool motion_table(const SceneView &h, const SceneView &c, uint32_t *table, bool *any_moved) {
+	*any_moved = false;
+	if (h.n_shapes != c.n_shapes || h.tri_bytes != c.tri_bytes || h.mat_bytes != c.mat_bytes) return false;
+	if (memcmp(h.scene, c.scene, sizeof(srt_scene_data)) != 0) return false;
+	if (h.mat_bytes && memcmp(h.mats, c.mats, h.mat_bytes) != 0) return false;
+	if (h.tri_bytes && memcmp(h.tris, c.tris, h.tri_bytes) != 0) return false;
+	for (size_t k = 0; k < c.n_shapes; k++) {
+		const srt_shape &a = h.shapes[k], &b = c.shapes[k];
+		if (a.type != b.type || a.material != b.material) return false;
+		if (a.type == SRT_SHAPE_MODEL) {
+			const srt_model &ma = a.shape.model, &mb = b.shape.model;
+			// (bounding_min / bounding_max are the world box of the transformed vertices: they move with the transform)
+			if (ma.triangle_index != mb.triangle_index || ma.num_triangles != mb.num_triangles) return false;
+		}
+	}
+	for (size_t k = 0; k < c.n_shapes; k++) {
+		const srt_shape &a = h.shapes[k], &b = c.shapes[k];
+		uint32_t *row = table + k * SRT_MOTION_WORDS;
+		if (memcmp(&a, &b, sizeof a) == 0) {
+			identity_row(row, SRT_MOTION_STATIC);
+			continue;
+		}
+		bool ok = false;
+		if (a.type == SRT_SHAPE_SPHERE) ok = sphere_row(a.shape.sphere, b.shape.sphere, row);
+		else if (a.type == SRT_SHAPE_PLANE) ok = plane_row(a.shape.plane, b.shape.plane, row);
+		else if (a.type == SRT_SHAPE_MODEL) ok = model_row(a.shape.model, b.shape.model, row);
+		if (!ok) identity_row(row, SRT_MOTION_NO_HISTORY);
+		*any_moved = true;
+	}
+	return true;
+}
+
+// every shape of the current scene STATIC (after a commit, or without a history)
+void static_table(srt_tracer *t) {
+	SceneView v;
+	const size_t n = view_of(t->scene_bytes, v) ? v.n_shapes : 0;
+	t->om_table.resize(n * SRT_MOTION_WORDS);
+	for (size_t k = 0; k < n; k++) identity_row(t->om_table.data() + k * SRT_MOTION_WORDS, SRT_MOTION_STATIC);
+	t->om_any_moved = false;
+}
+
 // the temporal set-up into the staging set (and `col` / argb when given)
 int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 	const size_t px = full_pixels(t);
@@ -236,9 +312,10 @@ int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 	p.cam_h[0] = rh.camera_to_world[3].x, p.cam_h[1] = rh.camera_to_world[3].y, p.cam_h[2] = rh.camera_to_world[3].z;
 	p.aspect_h = rh.aspect_ratio;
 	p.fov_h = rh.fov_scale;
+	const bool motion = t->om_on && t->tp_valid && t->om_any_moved; // else: what the library launches without object motion
 	p.mode = TP_NONE;
 	if (t->tp_valid) {
-		if (same_camera(rd, rh)) p.mode = TP_IDENTITY;
+		if (same_camera(rd, rh)) p.mode = (!motion || invert_rotation(rh, p.rinv)) ? TP_IDENTITY : TP_NONE; // a moved shape projects
 		else if (invert_rotation(rh, p.rinv)) p.mode = TP_PROJECT;
 	}
 	p.canvas = reinterpret_cast<const float4 *>(t->canvas);
@@ -254,7 +331,16 @@ int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 	p.out = col;
 	p.argb = argb;
 	const dim3 grid((unsigned)((t->width + 15) / 16), (unsigned)((t->height + 15) / 16));
-	hipLaunchKernelGGL(srt_temporal_setup_kernel, grid, dim3(256), 0, t->stream, p);
+	if (motion) {
+		MotionParams mp;
+		mp.ids = t->om_ids[t->om_cur].ptr;
+		mp.h_ids = t->om_ids[1 - t->om_cur].ptr;
+		mp.table = t->om_table_dev.ptr;
+		mp.n_shapes = (uint32_t)(t->om_table.size() / SRT_MOTION_WORDS);
+		hipLaunchKernelGGL(srt_temporal_motion_kernel, grid, dim3(256), 0, t->stream, p, mp);
+	} else {
+		hipLaunchKernelGGL(srt_temporal_setup_kernel, grid, dim3(256), 0, t->stream, p);
+	}
 	SRT_HIP(t, hipGetLastError());
 	return SRT_OK;
 }
@@ -294,6 +380,39 @@ int srt_temporal_commit(srt_tracer *t) {
 	t->tp_cam = t->dn_cam;
 	t->tp_valid = true;
 	t->tp_fresh = false;
+	if (t->om_on) {
+		if (t->om_mixed) { // traced with more than one scene: no single set of maps leads back to this frame
+			srt_temporal_drop(t);
+		} else {
+			t->om_cur = 1 - t->om_cur; // the frame's shape indices become the history's
+			t->om_hist_scene = t->scene_bytes;
+		}
+		static_table(t);
+	}
+	return SRT_OK;
+}
+
+int srt_motion_update_scene(srt_tracer *t, const std::vector<uint8_t> &bytes, int rc) {
+	if (rc != SRT_OK || bytes.empty()) {
+		srt_temporal_drop(t);
+		return SRT_OK;
+	}
+	if (t->dn_T > 0 && bytes != t->scene_bytes) t->om_mixed = true; // samples of the old scene are on the canvas
+	SceneView h, c;
+	view_of(bytes, c);
+	t->om_table.assign(c.n_shapes * SRT_MOTION_WORDS, 0u);
+	t->om_any_moved = false;
+	if (t->tp_valid && !(view_of(t->om_hist_scene, h) && motion_table(h, c, t->om_table.data(), &t->om_any_moved))) srt_temporal_drop(t);
+	if (!t->tp_valid) {
+		for (size_t k = 0; k < c.n_shapes; k++) identity_row(t->om_table.data() + k * SRT_MOTION_WORDS, SRT_MOTION_STATIC);
+		t->om_any_moved = false;
+	}
+	if (t->om_any_moved) { // with the scene upload; a set-up still running on the stream reads the old table first
+		SRT_HIP(t, hipSetDevice(t->device));
+		SRT_HIP(t, t->om_table_dev.reserve(t->om_table.size()));
+		SRT_HIP(t, hipMemcpyAsync(t->om_table_dev.ptr, t->om_table.data(), t->om_table.size() * 4, hipMemcpyHostToDevice, t->stream));
+		SRT_HIP(t, hipStreamSynchronize(t->stream));
+	}
 	return SRT_OK;
 }
 
@@ -314,6 +433,7 @@ int srt_set_denoise_temporal(srt_tracer *t, const srt_temporal_params *params) {
 	if (!params || !params->enable) {
 		if (t->tp_on) srt_temporal_drop(t);
 		t->tp_on = false;
+		t->om_on = false;
 		return SRT_OK;
 	}
 	if (!params_ok(*params))
@@ -327,6 +447,78 @@ int srt_set_denoise_temporal(srt_tracer *t, const srt_temporal_params *params) {
 	t->tp = *params;
 	t->tp_on = true;
 	t->tp_fresh = false; // the staging set was integrated with the old settings
+	return SRT_OK;
+}
+
+int srt_set_denoise_object_motion(srt_tracer *t, int enable) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!enable) {
+		if (t->om_on) srt_temporal_drop(t);
+		t->om_on = false;
+		return SRT_OK;
+	}
+	if (!t->tp_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_object_motion: temporal reprojection is off (srt_set_denoise_temporal)");
+	if (t->om_on) return SRT_OK;
+	SRT_HIP(t, hipSetDevice(t->device));
+	const size_t px = full_pixels(t);
+	for (int k = 0; k < 2; k++) {
+		SRT_HIP(t, t->om_ids[k].reserve(px));
+		SRT_HIP(t, hipMemsetAsync(t->om_ids[k].ptr, 0xff, px * 4, t->stream));
+	}
+	srt_temporal_drop(t);
+	t->om_on = true;
+	t->om_mixed = t->dn_T > 0; // what is on the canvas was traced without shape indices
+	static_table(t);
+	return SRT_OK;
+}
+
+int srt_read_denoise_shape_ids(srt_tracer *t, uint32_t *current, uint32_t *history) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!t->om_ids[0].ptr) return fail(t, SRT_ERR_STATE, "srt_read_denoise_shape_ids: object motion was never enabled (srt_set_denoise_object_motion)");
+	const size_t px = full_pixels(t);
+	SRT_HIP(t, hipSetDevice(t->device));
+	if (current) SRT_HIP(t, hipMemcpyAsync(current, t->om_ids[t->om_cur].ptr, px * 4, hipMemcpyDeviceToHost, t->stream));
+	if (history) {
+		if (t->tp_valid) SRT_HIP(t, hipMemcpyAsync(history, t->om_ids[1 - t->om_cur].ptr, px * 4, hipMemcpyDeviceToHost, t->stream));
+		else memset(history, 0xff, px * 4);
+	}
+	SRT_HIP(t, hipStreamSynchronize(t->stream));
+	return SRT_OK;
+}
+
+int srt_read_denoise_motion(srt_tracer *t, uint32_t *table, size_t capacity_shapes, size_t *n_shapes, int *any_moved) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!t->om_on) return fail(t, SRT_ERR_STATE, "srt_read_denoise_motion: object motion is off (srt_set_denoise_object_motion)");
+	const size_t n = t->om_table.size() / SRT_MOTION_WORDS;
+	if (n_shapes) *n_shapes = n;
+	if (any_moved) *any_moved = (t->tp_valid && t->om_any_moved) ? 1 : 0;
+	if (table) {
+		if (capacity_shapes < n) return fail(t, SRT_ERR_INVALID, "srt_read_denoise_motion: the table has more shapes than capacity_shapes");
+		if (n) memcpy(table, t->om_table.data(), n * SRT_MOTION_WORDS * 4);
+		if (!t->tp_valid)
+			for (size_t k = 0; k < n; k++) identity_row(table + k * SRT_MOTION_WORDS, SRT_MOTION_STATIC);
+	}
+	return SRT_OK;
+}
+
+int srt_motion_table_host(const srt_shape *h_shapes, size_t h_n_shapes, const srt_triangle *h_triangles, size_t h_n_triangles,
+                          const srt_material *h_materials, size_t h_n_materials, const srt_scene_data *h_scene,
+                          const srt_shape *c_shapes, size_t c_n_shapes, const srt_triangle *c_triangles, size_t c_n_triangles,
+                          const srt_material *c_materials, size_t c_n_materials, const srt_scene_data *c_scene, uint32_t *table, int *keep) {
+	if (!h_scene || !c_scene || !keep || (c_n_shapes && !table)) return SRT_ERR_INVALID;
+	if ((h_n_shapes && !h_shapes) || (c_n_shapes && !c_shapes) || (h_n_triangles && !h_triangles) || (c_n_triangles && !c_triangles) ||
+	    (h_n_materials && !h_materials) || (c_n_materials && !c_materials))
+		return SRT_ERR_INVALID;
+	const SceneView h = {h_shapes, h_n_shapes, h_triangles, h_materials, h_scene, h_n_triangles * sizeof(srt_triangle), h_n_materials * sizeof(srt_material)};
+	const SceneView c = {c_shapes, c_n_shapes, c_triangles, c_materials, c_scene, c_n_triangles * sizeof(srt_triangle), c_n_materials * sizeof(srt_material)};
+	bool any = false;
+	try {
+		std::vector<uint32_t> rows(c_n_shapes * SRT_MOTION_WORDS);
+		*keep = motion_table(h, c, rows.data(), &any) ? 1 : 0;
+		if (*keep && !rows.empty()) memcpy(table, rows.data(), rows.size() * 4);
+	} catch (...) {
+		return SRT_ERR_INVALID;
+	}
 	return SRT_OK;
 }
 

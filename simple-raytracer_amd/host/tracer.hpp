@@ -167,6 +167,13 @@ class Tracer {
 		p.depth_threshold = depth_threshold;
 		check(srt_set_denoise_temporal(handle, &p));
 	}
+	/// Object motion for the temporal stage (srt_set_denoise_object_motion): the history survives an update_scene that only
+	/// moves spheres, planes or model instances. Needs set_denoise_temporal first; the clear_canvas / update_scene / render
+	/// order of the frame loop stays as it is. Single-device tracers only.
+	void set_denoise_object_motion(bool enable = true) {
+		if (group) throw std::runtime_error("Tracer::set_denoise_object_motion: single-device tracers only");
+		check(srt_set_denoise_object_motion(handle, enable ? 1 : 0));
+	}
 	/// render() / render_pipelined() record the kernel timers' events too (off by default: they cost 10-17 us of a 150 us
 	/// frame); single-device tracers only
 	void set_kernel_timers(bool enable) {

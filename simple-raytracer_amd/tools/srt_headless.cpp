@@ -9,6 +9,9 @@
 // --denoise K: the frames go through the edge-aware denoiser with K a-trous passes (Tracer::set_denoise; one device only)
 // --temporal: with --denoise, the denoiser's temporal reprojection (Tracer::set_denoise_temporal)
 // --move DX: the camera moves by DX along x every frame and every frame clears the canvas, as the front-end does while moving
+// --move-shape I DX: with --temporal, shape I (a sphere, a plane or a model instance) moves by DX along x every frame and every
+//                frame clears the canvas, as the front-end does while a gizmo is dragged; turns object motion on
+//                (Tracer::set_denoise_object_motion)
 //
 // --skybox sky.ppm: an 8-bit binary PPM (P6) as the sky, prepared the way the reference prepares assets/skybox.png
 //                   (host/skybox.hpp: four channels, rows flipped, pow(byte / 255, 2.2)); default: the synthetic sky.
@@ -104,7 +107,8 @@ int main(int argc, char **argv) {
 	bool parse_only = false, bvh = false, pipelined = false;
 	int gpus = 1, denoise = -1;
 	bool temporal = false;
-	float move = 0.0f;
+	float move = 0.0f, shape_move = 0.0f;
+	int move_shape = -1;
 	bool moving = false;
 	for (int i = 1; i < argc; i++) {
 		std::string a = argv[i];
@@ -134,10 +138,11 @@ int main(int argc, char **argv) {
 		else if (a == "--denoise") denoise = std::atoi(next());
 		else if (a == "--temporal") temporal = true;
 		else if (a == "--move") move = std::strtof(next(), nullptr), moving = true;
+		else if (a == "--move-shape") move_shape = std::atoi(next()), shape_move = std::strtof(next(), nullptr);
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--temporal] [--move DX]\n";
+			             "[--denoise K] [--temporal] [--move DX] [--move-shape I DX]\n";
 			return 2;
 		}
 	}
@@ -210,6 +215,13 @@ int main(int argc, char **argv) {
 	if (bvh) tracer.set_acceleration(SRT_ACCEL_BVH);
 	if (denoise >= 0) tracer.set_denoise(denoise);
 	if (temporal) tracer.set_denoise_temporal();
+	if (move_shape >= 0) {
+		if (!temporal || (size_t)move_shape >= shapes.size()) {
+			std::cerr << "--move-shape needs --temporal and a shape index below " << shapes.size() << "\n";
+			return 2;
+		}
+		tracer.set_denoise_object_motion();
+	}
 	tracer.options.num_samples = spp;
 	tracer.options.num_bounces = bounces;
 	tracer.options.show_normals = false;
@@ -244,6 +256,15 @@ int main(int argc, char **argv) {
 	for (int frame = 0; frame < frames; frame++) {
 		if (time_not_moved == 1) {
 			tracer.clear_canvas();
+			if (move_shape >= 0 && frame > 0) { // the dragged shape, as the front-end's gizmo edits the record
+				Shape &s = shapes[(size_t)move_shape];
+				if (s.type == SHAPE_SPHERE) s.shape.sphere.position.x += shape_move;
+				else if (s.type == SHAPE_PLANE) s.shape.plane.position.x += shape_move;
+				else {
+					s.shape.model.transform[3].x += shape_move;
+					s.shape.model.compute_bounding_box(triangles);
+				}
+			}
 			tracer.update_scene(shapes, triangles, materials.list);
 		}
 		auto &options = tracer.options;
@@ -254,7 +275,7 @@ int main(int argc, char **argv) {
 		options.tick = (unsigned)frame;
 		if (pipelined) tracer.render_pipelined(time_not_moved, pixels); // delivers the previous frame
 		else tracer.render(time_not_moved, pixels);
-		time_not_moved = moving ? 1 : time_not_moved + 1; // a moving camera clears every frame (src/main.cpp:270-290)
+		time_not_moved = (moving || move_shape >= 0) ? 1 : time_not_moved + 1; // a moving camera clears every frame (src/main.cpp:270-290)
 	}
 	if (pipelined) tracer.finish(pixels);
 	double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

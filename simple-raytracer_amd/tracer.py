@@ -35,9 +35,42 @@ ABI_SYMBOLS = [
     "srt_group_read_canvas", "srt_group_get_counters", "srt_render_pipelined", "srt_pipeline_flush", "srt_unpermute_device",
     "srt_denoise_defaults", "srt_set_denoise", "srt_resolve_denoised", "srt_read_denoised", "srt_read_denoise_inputs",
     "srt_temporal_defaults", "srt_set_denoise_temporal", "srt_reset_denoise_history", "srt_read_denoise_history",
+    "srt_set_denoise_object_motion", "srt_read_denoise_shape_ids", "srt_read_denoise_motion", "srt_motion_table_host",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
+MOTION_STATIC, MOTION_MOVED, MOTION_NO_HISTORY = 0, 1, 2
+MOTION_WORDS = 22
+NO_SHAPE = 0xFFFFFFFF
+
+
+def _motion_rows(table):
+    """(n, 22) uint32 rows -> dict state (n,) int, A (n, 3, 4), B (n, 3, 3) float32."""
+    table = np.ascontiguousarray(table, np.uint32).reshape(-1, MOTION_WORDS)
+    f = table[:, 1:].copy().view(np.float32)
+    return {"state": table[:, 0].astype(np.int64), "A": f[:, :12].reshape(-1, 3, 4), "B": f[:, 12:].reshape(-1, 3, 3)}
+
+
+def motion_table_host(history, current):
+    """srt_motion_table_host (host only, no GPU needed). history / current: (shapes, triangles, materials, scene_data) of
+    the two scenes. None when the history would be dropped, else dict state (n,), A (n, 3, 4) current world -> history
+    world, B (n, 3, 3) current normal -> history normal."""
+    lib = load_library()
+    args, keep = [], []
+    for shapes, triangles, materials, sd in (history, current):
+        recs = [R.as_records(shapes, R.SHAPE), R.as_records(triangles, R.TRIANGLE), R.as_records(materials, R.MATERIAL)]
+        sd = R.as_records(sd, R.SCENE_DATA)
+        keep += recs + [sd]
+        for r in recs:
+            args += [_ptr(r) if len(r) else None, len(r)]
+        args.append(_ptr(sd))
+    n = len(keep[4])
+    table = np.zeros((max(n, 1), MOTION_WORDS), np.uint32)
+    kept = C.c_int(0)
+    rc = lib.srt_motion_table_host(*args, _ptr(table), C.byref(kept))
+    if rc:
+        raise SrtError(f"srt_motion_table_host failed ({rc})")
+    return _motion_rows(table[:n]) if kept.value else None
 
 
 BVH_NODE = np.dtype({"names": ["lo", "skip", "hi", "leaf"], "formats": [(np.float32, (3,)), np.uint32, (np.float32, (3,)), np.uint32],
@@ -256,6 +289,11 @@ def _bind(lib):
         lib.srt_set_denoise_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
         lib.srt_reset_denoise_history.argtypes = [vp]
         lib.srt_read_denoise_history.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
+    if hasattr(lib, "srt_set_denoise_object_motion"):
+        lib.srt_set_denoise_object_motion.argtypes = [vp, C.c_int]
+        lib.srt_read_denoise_shape_ids.argtypes = [vp, vp, vp]
+        lib.srt_read_denoise_motion.argtypes = [vp, vp, sz, C.POINTER(sz), C.POINTER(C.c_int)]
+        lib.srt_motion_table_host.argtypes = [vp, sz, vp, sz, vp, sz, vp] * 2 + [vp, C.POINTER(C.c_int)]
     return lib
 
 
@@ -541,6 +579,29 @@ class Tracer:
         self._check(self.lib.srt_read_denoise_history(self._h, _ptr(cc), _ptr(m), _ptr(g), _ptr(cam), C.byref(valid)))
         return {"valid": bool(valid.value), "colour": cc[..., :3], "count": cc[..., 3], "m1": m[..., 0], "m2": m[..., 1], "guide": g,
                 "camera": cam}
+
+    def set_denoise_object_motion(self, enable=True):
+        """Keep the temporal history across an update_scene that only moves shapes (srt_set_denoise_object_motion). Needs
+        temporal reprojection on; every change of the switch drops the history."""
+        self._check(self.lib.srt_set_denoise_object_motion(self._h, 1 if enable else 0))
+
+    def read_denoise_shape_ids(self):
+        """(current, history): (h, w) uint32 shape index of each pixel's first hit (feature sample 0 of the latest dispatch;
+        NO_SHAPE: none), for the frame since the clear and for the history frame (all NO_SHAPE without a history)."""
+        cur = np.zeros((self.height, self.width), np.uint32)
+        hist = np.zeros((self.height, self.width), np.uint32)
+        self._check(self.lib.srt_read_denoise_shape_ids(self._h, _ptr(cur), _ptr(hist)))
+        return cur, hist
+
+    def read_denoise_motion(self):
+        """The per-shape table the next filter would use: dict state (n,), A (n, 3, 4), B (n, 3, 3), any_moved."""
+        n, any_moved = C.c_size_t(0), C.c_int(0)
+        self._check(self.lib.srt_read_denoise_motion(self._h, None, 0, C.byref(n), C.byref(any_moved)))
+        table = np.zeros((max(n.value, 1), MOTION_WORDS), np.uint32)
+        self._check(self.lib.srt_read_denoise_motion(self._h, _ptr(table), n.value, C.byref(n), C.byref(any_moved)))
+        out = _motion_rows(table[:n.value])
+        out["any_moved"] = bool(any_moved.value)
+        return out
 
     def set_partition(self, rank, world, rows_per_block=8):
         self._check(self.lib.srt_set_partition(self._h, rank, world, rows_per_block))
