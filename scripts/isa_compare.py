@@ -1,12 +1,13 @@
-"""Compare the gfx950 disassembly of every kernel between two builds of csrc/kernels.hip (no GPU needed).
+"""Compare the gfx950 disassembly of every device function between two builds of csrc/ (no GPU needed).
 
     python scripts/isa_compare.py OLD_TREE NEW_TREE
 
-Each tree is a checkout's root (holding simple-raytracer_amd/csrc and include/). kernels.hip is compiled device-only with
-the product flags of build.py, the gfx950 code object is unbundled and disassembled with llvm-objdump, and every function
-in it is compared instruction by instruction, branch offsets and the s_nop padding between functions left out. A function
-that only one side has counts as a difference; the plain ordered reduction is matched across its rename to
-srt_reduce_kernel<false> (a template since the denoiser's moments variant). Exit status 1 on any difference.
+Each tree is a checkout's root (holding simple-raytracer_amd/csrc and include/). Every source of build.py SOURCES is
+compiled device-only with the product flags of build.py, its gfx950 code object is unbundled and disassembled with
+llvm-objdump, and every function in it is compared instruction by instruction, branch offsets and the s_nop padding
+between functions left out. A function that only one side has counts as a difference; the plain ordered reduction is
+matched across its rename to srt_reduce_kernel<false> (a template since the denoiser's moments variant). Exit status 1 on
+any difference.
 """
 import re
 import subprocess
@@ -18,16 +19,20 @@ ROCM = Path("/opt/rocm")
 RENAMED = {"_Z17srt_reduce_kernel12ReduceParams": "_Z17srt_reduce_kernelILb0EEv12ReduceParams"}  # old name -> new name
 
 
-def build(tree, out):
+def build_module():
     sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
     import srt_pkg
     srt_pkg.load()
     from simple_raytracer_amd import build as B
+    return B
+
+
+def build(B, tree, source, out):
     flags = [f for f in B.FLAGS if not f.startswith("-Rpass")]
-    co = out / "kernels.co"
-    subprocess.run([B.hipcc(), *flags, "--cuda-device-only", "-c", str(Path(tree) / "simple-raytracer_amd/csrc/kernels.hip"), "-o", str(co)],
+    co = out / f"{source}.co"
+    subprocess.run([B.hipcc(), *flags, "--cuda-device-only", "-c", str(Path(tree) / "simple-raytracer_amd/csrc" / source), "-o", str(co)],
                    check=True, capture_output=True)
-    elf = out / "kernels.elf"
+    elf = out / f"{source}.elf"
     subprocess.run([str(ROCM / "llvm/bin/clang-offload-bundler"), "--unbundle", "--type=o", f"--input={co}",
                     f"--targets=hipv4-amdgcn-amd-amdhsa--{B.ARCH}", f"--output={elf}"], check=True)
     return elf
@@ -57,20 +62,23 @@ def functions(elf):
 
 def main():
     old_tree, new_tree = sys.argv[1], sys.argv[2]
+    B = build_module()
+    a, b = {}, {}
     with tempfile.TemporaryDirectory() as d:
         a_dir, b_dir = Path(d) / "a", Path(d) / "b"
         a_dir.mkdir()
         b_dir.mkdir()
-        a, b = functions(build(old_tree, a_dir)), functions(build(new_tree, b_dir))
-    a = {RENAMED.get(k, k): v for k, v in a.items()}
+        for src in B.SOURCES:
+            a.update({(src, RENAMED.get(k, k)): v for k, v in functions(build(B, old_tree, src, a_dir)).items()})
+            b.update({(src, k): v for k, v in functions(build(B, new_tree, src, b_dir)).items()})
     names = sorted(a.keys() | b.keys())
     bad = 0
     for k in names:
         same = k in a and k in b and a[k] == b[k]
         bad += not same
         where = "" if k in a and k in b else f"  only in {'old' if k in a else 'new'}"
-        print(f"{'same' if same else 'DIFFERENT'}  {k}  ({len(a.get(k, b.get(k)))} instructions){where}")
-    print(f"{len(names)} kernels compared, {bad} different")
+        print(f"{'same' if same else 'DIFFERENT'}  {k[0]}  {k[1]}  ({len(a.get(k, b.get(k)))} instructions){where}")
+    print(f"{len(names)} functions of {len(B.SOURCES)} sources compared, {bad} different")
     sys.exit(1 if bad or not names else 0)
 
 

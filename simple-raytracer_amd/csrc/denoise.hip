@@ -32,6 +32,7 @@
 #include "device_types.h"
 
 #include "srt_internal.h"
+#include "tonemap.h"
 
 namespace {
 
@@ -57,20 +58,6 @@ struct SetupParams {
 	float4 *out;
 	uint32_t *argb; // K = 0 only
 };
-
-// srt_resolve_kernel's expressions (kernels.hip aces1, to_uchar; sqrt_ieee there is the correctly rounded square root,
-// as __builtin_sqrtf is with hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt)
-__device__ __forceinline__ float aces1(float x) {
-	const float a = 2.51f, b = 0.03f, c = 2.43f, d = 0.59f, e = 0.14f;
-	return dm_clamp((x * (x * a + b)) / (x * (x * c + d) + e), 0.0f, 1.0f);
-}
-__device__ __forceinline__ uint32_t to_uchar(float v) { return (v == v) ? ((uint32_t)(int)v & 255u) : 0u; }
-__device__ __forceinline__ uint32_t tonemap(float x, float y, float z) {
-	const float r = __builtin_sqrtf(aces1(x)), g = __builtin_sqrtf(aces1(y)), b = __builtin_sqrtf(aces1(z));
-	return 255u | (to_uchar(r * 255.0f) << 8) | (to_uchar(g * 255.0f) << 16) | (to_uchar(b * 255.0f) << 24);
-}
-__device__ __forceinline__ float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
-__device__ __forceinline__ bool finite3(float4 c) { return __builtin_isfinite(c.x) && __builtin_isfinite(c.y) && __builtin_isfinite(c.z); }
 
 __global__ __launch_bounds__(256) void srt_denoise_setup_kernel(const SetupParams p) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -158,8 +145,6 @@ bool params_ok(const srt_denoise_params &d) {
 	return d.iterations >= 0 && d.iterations <= 8 && d.feature_samples >= 1 && d.feature_samples <= 64 && sigma_ok(d.sigma_luminance) &&
 	       sigma_ok(d.sigma_normal) && sigma_ok(d.sigma_depth) && sigma_ok(d.sigma_albedo) && d.reserved == 0;
 }
-
-size_t full_pixels(const srt_tracer *t) { return (size_t)t->width * (size_t)t->height; }
 
 } // namespace
 

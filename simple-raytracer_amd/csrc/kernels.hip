@@ -35,6 +35,7 @@
 
 #include "detmath.h"
 #include "device_types.h"
+#include "tonemap.h" // aces1, to_uchar (the resolve), lum (the moments)
 
 // ---- regions: where the trace kernel's instructions are executed (development aid) ------------------------------
 // SRT_REGION(NAME) marks the start of a stretch of the trace kernel that runs as often as its first statement. In the
@@ -1898,14 +1899,6 @@ __global__ __launch_bounds__(64, USE_BVH ? SRT_TRACE_WAVES_PER_SIMD_BVH : HAS_MO
 #endif
 }
 
-namespace {
-__device__ __forceinline__ float aces1(float x) {
-	const float a = 2.51f, b = 0.03f, c = 2.43f, d = 0.59f, e = 0.14f;
-	return dm_clamp((x * (x * a + b)) / (x * (x * c + d) + e), 0.0f, 1.0f);
-}
-__device__ __forceinline__ uint32_t to_uchar(float v) { return (v == v) ? ((uint32_t)(int)v & 255u) : 0u; }
-} // namespace
-
 // ---------------------------------------------------------------------------------
 // Ordered reduction: lane = pixel, serial over the batch's samples in sample order, so
 // the float sums are the reference's `color += trace(...)` sequence bit for bit no matter
@@ -1916,7 +1909,7 @@ __device__ __forceinline__ uint32_t to_uchar(float v) { return (v == v) ? ((uint
 // sum is the same either way.
 namespace {
 __device__ __forceinline__ float add_lum2(float s2, float r, float g, float b) {
-	const float l = 0.2126f * r + 0.7152f * g + 0.0722f * b;
+	const float l = lum(r, g, b);
 	return s2 + l * l;
 }
 } // namespace

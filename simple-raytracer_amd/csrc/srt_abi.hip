@@ -496,8 +496,6 @@ uint64_t hash_triangles(const srt_triangle *tris, size_t count) {
 	return h;
 }
 
-size_t owned_pixels(const srt_tracer *t) { return (size_t)t->owned_rows * (size_t)t->width; }
-
 int clear_canvas_impl(srt_tracer *t) {
 	const int rc = srt_temporal_commit(t); // temporal.hip: the frame being cleared becomes the denoiser's history
 	if (rc) return rc;

@@ -127,6 +127,9 @@ struct srt_tracer {
 
 int srt_fail(srt_tracer *t, int code, const std::string &msg); // records the text for srt_last_error (t == NULL: srt_create's)
 static inline int fail(srt_tracer *t, int code, const std::string &msg) { return srt_fail(t, code, msg); }
+// pixels of the rows this handle owns (srt_set_partition) and of the whole frame (the denoiser's buffers)
+static inline size_t owned_pixels(const srt_tracer *t) { return (size_t)t->owned_rows * (size_t)t->width; }
+static inline size_t full_pixels(const srt_tracer *t) { return (size_t)t->width * (size_t)t->height; }
 
 #define SRT_HIP(t, call)                                                                              \
 	do {                                                                                              \

@@ -29,6 +29,7 @@
 #include "device_types.h"
 
 #include "srt_internal.h"
+#include "tonemap.h"
 
 namespace {
 
@@ -60,19 +61,6 @@ struct TemporalParams {
 	uint32_t *argb; // K = 0 only
 };
 
-// as denoise.hip (srt_resolve_kernel's tonemap)
-__device__ __forceinline__ float aces1(float x) {
-	const float a = 2.51f, b = 0.03f, c = 2.43f, d = 0.59f, e = 0.14f;
-	return dm_clamp((x * (x * a + b)) / (x * (x * c + d) + e), 0.0f, 1.0f);
-}
-__device__ __forceinline__ uint32_t to_uchar(float v) { return (v == v) ? ((uint32_t)(int)v & 255u) : 0u; }
-__device__ __forceinline__ uint32_t tonemap(float x, float y, float z) {
-	const float r = __builtin_sqrtf(aces1(x)), g = __builtin_sqrtf(aces1(y)), b = __builtin_sqrtf(aces1(z));
-	return 255u | (to_uchar(r * 255.0f) << 8) | (to_uchar(g * 255.0f) << 16) | (to_uchar(b * 255.0f) << 24);
-}
-__device__ __forceinline__ float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
-__device__ __forceinline__ bool finite3(float4 c) { return __builtin_isfinite(c.x) && __builtin_isfinite(c.y) && __builtin_isfinite(c.z); }
-
 // object motion (srt_set_denoise_object_motion): per-pixel shape indices of the frame and of the history, and the table of
 // SRT_MOTION_WORDS words per shape {state, A (3x4, rows; current world -> history world), B (3x3, rows; normals)}
 struct MotionParams {
@@ -94,14 +82,12 @@ __global__ __launch_bounds__(256) void srt_temporal_setup_kernel(const TemporalP
 //   s MOVED                   X_h = A_s X (rows: ((a0 X.x + a1 X.y) + a2 X.z) + a3), projected into the history camera also
 //                             when the cameras are the same, D = |X_h - cam_h|; a tap must carry history shape index s, and
 //                             its normal is compared with normalise(B_s N_p) (zero length or not finite: no history)
-// tests/motion_ref.py restates it.
+// tests/temporal_ref.py reproject with a table restates it.
 __global__ __launch_bounds__(256) void srt_temporal_motion_kernel(const TemporalParams p, const MotionParams mp) {
 #define SRT_TEMPORAL_MOTION 1
 #include "temporal_body.inc"
 #undef SRT_TEMPORAL_MOTION
 }
-
-size_t full_pixels(const srt_tracer *t) { return (size_t)t->width * (size_t)t->height; }
 
 // set offsets, in floats: {colour, count} float4, {m1, m2} float2, guide 2 float4
 size_t off_m(size_t px) { return px * 4; }
@@ -113,20 +99,29 @@ bool same_camera(const srt_render_data &a, const srt_render_data &b) {
 	       memcmp(&a.aspect_ratio, &b.aspect_ratio, sizeof(float)) == 0 && memcmp(&a.fov_scale, &b.fov_scale, sizeof(float)) == 0;
 }
 
-// R^-1 of the camera's upper 3x3 (columns camera_to_world[0..2]) in double, rounded to float, row-major; false when
-// singular or not finite
-bool invert_rotation(const srt_render_data &rd, float out[9]) {
-	double m[3][3]; // m[row][col]
-	const srt_float4 *c = rd.camera_to_world;
-	for (int k = 0; k < 3; k++) m[0][k] = c[k].x, m[1][k] = c[k].y, m[2][k] = c[k].z;
+// the adjugate inverse of m (m[row][col]) in double; false when singular or not finite
+bool inv3(const double m[3][3], double out[3][3]) {
 	const double a = m[1][1] * m[2][2] - m[1][2] * m[2][1], b = m[1][2] * m[2][0] - m[1][0] * m[2][2], d = m[1][0] * m[2][1] - m[1][1] * m[2][0];
 	const double det = m[0][0] * a + m[0][1] * b + m[0][2] * d;
 	if (!(det != 0.0) || !std::isfinite(det)) return false;
-	const double inv[9] = {a / det, (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det, (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det,
-	                       b / det, (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det, (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det,
-	                       d / det, (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det, (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det};
+	out[0][0] = a / det, out[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det, out[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det;
+	out[1][0] = b / det, out[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det, out[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det;
+	out[2][0] = d / det, out[2][1] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det, out[2][2] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det;
+	for (int r = 0; r < 3; r++)
+		for (int c = 0; c < 3; c++)
+			if (!std::isfinite(out[r][c])) return false;
+	return true;
+}
+
+// R^-1 of the camera's upper 3x3 (columns camera_to_world[0..2]): inv3, rounded to float, row-major; false when singular
+// or a float is not finite
+bool invert_rotation(const srt_render_data &rd, float out[9]) {
+	double m[3][3], inv[3][3]; // m[row][col]
+	const srt_float4 *c = rd.camera_to_world;
+	for (int k = 0; k < 3; k++) m[0][k] = c[k].x, m[1][k] = c[k].y, m[2][k] = c[k].z;
+	if (!inv3(m, inv)) return false;
 	for (int k = 0; k < 9; k++) {
-		out[k] = (float)inv[k];
+		out[k] = (float)inv[k / 3][k % 3];
 		if (!std::isfinite(out[k])) return false;
 	}
 	return true;
@@ -155,23 +150,14 @@ bool view_of(const std::vector<uint8_t> &bytes, SceneView &v) {
 	return true;
 }
 
-bool inv3(const double m[3][3], double out[3][3]) {
-	const double a = m[1][1] * m[2][2] - m[1][2] * m[2][1], b = m[1][2] * m[2][0] - m[1][0] * m[2][2], d = m[1][0] * m[2][1] - m[1][1] * m[2][0];
-	const double det = m[0][0] * a + m[0][1] * b + m[0][2] * d;
-	if (!(det != 0.0) || !std::isfinite(det)) return false;
-	out[0][0] = a / det, out[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det, out[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det;
-	out[1][0] = b / det, out[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det, out[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det;
-	out[2][0] = d / det, out[2][1] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det, out[2][2] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det;
-	for (int r = 0; r < 3; r++)
-		for (int c = 0; c < 3; c++)
-			if (!std::isfinite(out[r][c])) return false;
-	return true;
-}
-
-void identity_row(uint32_t *row, uint32_t state) {
-	float f[21] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1};
-	row[0] = state;
-	memcpy(row + 1, f, sizeof f);
+// n rows of SRT_MOTION_WORDS words: `state` and the identity maps
+void identity_rows(uint32_t *rows, size_t n, uint32_t state) {
+	const float f[21] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1};
+	for (size_t k = 0; k < n; k++) {
+		uint32_t *row = rows + k * SRT_MOTION_WORDS;
+		row[0] = state;
+		memcpy(row + 1, f, sizeof f);
+	}
 }
 
 // Xh = lin Xc + tr and the normal map nrm, rounded to float; false when a float is not finite
@@ -263,14 +249,14 @@ bool motion_table(const SceneView &h, const SceneView &c, uint32_t *table, bool 
 		const srt_shape &a = h.shapes[k], &b = c.shapes[k];
 		uint32_t *row = table + k * SRT_MOTION_WORDS;
 		if (memcmp(&a, &b, sizeof a) == 0) {
-			identity_row(row, SRT_MOTION_STATIC);
+			identity_rows(row, 1, SRT_MOTION_STATIC);
 			continue;
 		}
 		bool ok = false;
 		if (a.type == SRT_SHAPE_SPHERE) ok = sphere_row(a.shape.sphere, b.shape.sphere, row);
 		else if (a.type == SRT_SHAPE_PLANE) ok = plane_row(a.shape.plane, b.shape.plane, row);
 		else if (a.type == SRT_SHAPE_MODEL) ok = model_row(a.shape.model, b.shape.model, row);
-		if (!ok) identity_row(row, SRT_MOTION_NO_HISTORY);
+		if (!ok) identity_rows(row, 1, SRT_MOTION_NO_HISTORY);
 		*any_moved = true;
 	}
 	return true;
@@ -281,7 +267,7 @@ void static_table(srt_tracer *t) {
 	SceneView v;
 	const size_t n = view_of(t->scene_bytes, v) ? v.n_shapes : 0;
 	t->om_table.resize(n * SRT_MOTION_WORDS);
-	for (size_t k = 0; k < n; k++) identity_row(t->om_table.data() + k * SRT_MOTION_WORDS, SRT_MOTION_STATIC);
+	identity_rows(t->om_table.data(), n, SRT_MOTION_STATIC);
 	t->om_any_moved = false;
 }
 
@@ -404,7 +390,7 @@ int srt_motion_update_scene(srt_tracer *t, const std::vector<uint8_t> &bytes, in
 	t->om_any_moved = false;
 	if (t->tp_valid && !(view_of(t->om_hist_scene, h) && motion_table(h, c, t->om_table.data(), &t->om_any_moved))) srt_temporal_drop(t);
 	if (!t->tp_valid) {
-		for (size_t k = 0; k < c.n_shapes; k++) identity_row(t->om_table.data() + k * SRT_MOTION_WORDS, SRT_MOTION_STATIC);
+		identity_rows(t->om_table.data(), c.n_shapes, SRT_MOTION_STATIC);
 		t->om_any_moved = false;
 	}
 	if (t->om_any_moved) { // with the scene upload; a set-up still running on the stream reads the old table first
@@ -495,8 +481,7 @@ int srt_read_denoise_motion(srt_tracer *t, uint32_t *table, size_t capacity_shap
 	if (table) {
 		if (capacity_shapes < n) return fail(t, SRT_ERR_INVALID, "srt_read_denoise_motion: the table has more shapes than capacity_shapes");
 		if (n) memcpy(table, t->om_table.data(), n * SRT_MOTION_WORDS * 4);
-		if (!t->tp_valid)
-			for (size_t k = 0; k < n; k++) identity_row(table + k * SRT_MOTION_WORDS, SRT_MOTION_STATIC);
+		if (!t->tp_valid) identity_rows(table, n, SRT_MOTION_STATIC);
 	}
 	return SRT_OK;
 }

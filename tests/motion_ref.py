@@ -1,36 +1,20 @@
-"""numpy restatement of the temporal stage's object motion (simple-raytracer_amd/csrc/temporal.hip
-srt_temporal_motion_kernel and the host's per-shape table, include/srt_abi.h srt_set_denoise_object_motion).
+"""The host side of the temporal stage's object motion (simple-raytracer_amd/csrc/temporal.hip, include/srt_abi.h
+srt_set_denoise_object_motion) in numpy, and the moves the tests run.
 
-table_row() is the table's float64 formulas; scene_table() the comparison that keeps or drops the history. reproject()
-is temporal_ref.reproject with the per-shape maps: float32 in the kernel's operation order, so almost every value is the
-kernel's own; a pixel whose outcome hangs on the last bit is flagged `borderline` as there. With no shape moved the host
-launches the kernel it launches without object motion, and setup() calls temporal_ref's reproject.
+table_row() is the per-shape table's float64 formulas; scene_table() the comparison that keeps or drops the history. The
+moved set-up kernel itself is temporal_ref.reproject with ids and a table.
 """
 import numpy as np
 
 import temporal_ref as TR
+from temporal_ref import MOVED, NO_HISTORY, STATIC  # noqa: F401 (the table's states, for the tests)
 
 F32 = np.float32
-STATIC, MOVED, NO_HISTORY = 0, 1, 2
 NO_SHAPE = 0xFFFFFFFF
 SPHERE, PLANE, MODEL = 0, 1, 2
 
 
 # ---- the host's table ---------------------------------------------------------------------------------------------------
-def _inv3(m):
-    a = m[1][1] * m[2][2] - m[1][2] * m[2][1]
-    b = m[1][2] * m[2][0] - m[1][0] * m[2][2]
-    d = m[1][0] * m[2][1] - m[1][1] * m[2][0]
-    with np.errstate(all="ignore"):
-        det = m[0][0] * a + m[0][1] * b + m[0][2] * d
-        if not (det != 0.0) or not np.isfinite(det):
-            return None
-        inv = np.array([[a / det, (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det, (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det],
-                        [b / det, (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det, (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det],
-                        [d / det, (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det, (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det]], np.float64)
-    return inv if np.all(np.isfinite(inv)) else None
-
-
 def _model_parts(shape):
     m = np.asarray(shape["transform"], np.float64)  # (4, 4): columns
     return m[:3, :3].T.copy(), m[3, :3].copy()
@@ -72,7 +56,7 @@ def table_row(hist, cur):
             (Lh, th), (Lc, tc) = _model_parts(hist), _model_parts(cur)
             if not (np.all(np.isfinite(th)) and np.all(np.isfinite(tc))):
                 return (NO_HISTORY,) + eye
-            Lci, Lhi = _inv3(Lc), _inv3(Lh)
+            Lci, Lhi = TR.inv3(Lc), TR.inv3(Lh)
             if Lci is None or Lhi is None:
                 return (NO_HISTORY,) + eye
             lin = np.array([[(Lh[r][0] * Lci[0][q] + Lh[r][1] * Lci[1][q]) + Lh[r][2] * Lci[2][q] for q in range(3)] for r in range(3)])
@@ -106,151 +90,6 @@ def scene_table(hist, cur):
 def static_table(n):
     return dict(state=np.zeros(n, np.int64), A=np.tile(np.hstack([np.eye(3), np.zeros((3, 1))]).astype(F32), (n, 1, 1)),
                 B=np.tile(np.eye(3, dtype=F32), (n, 1, 1)))
-
-
-# ---- the kernel ---------------------------------------------------------------------------------------------------------
-def project(Z, cam_rd, cam_h_rd, width, height, A=None, dtype=F32):
-    """temporal_ref.project with the per-pixel map A (h, w, 3, 4) between the first hit and the history camera (None: none):
-    (fx, fy, D, in_front). dtype float32 is the kernel's arithmetic; float64 the same formulas in double (tests)."""
-    T = dtype
-    if T is F32:
-        rinv = TR.invert_rotation(cam_h_rd)
-    else:
-        c = np.asarray(cam_h_rd["camera_to_world"], np.float64)
-        rinv = _inv3(np.array([[c[k][r] for k in range(3)] for r in range(3)]))
-    if rinv is None:
-        return None
-    c0, c1, c2, cam, aspect, fov = (np.asarray(v, T) for v in TR.camera(cam_rd))
-    _, _, _, cam_h, aspect_h, fov_h = (np.asarray(v, T) for v in TR.camera(cam_h_rd))
-    rinv = np.asarray(rinv, T)
-    ys, xs = np.mgrid[0:height, 0:width]
-    with np.errstate(all="ignore"):
-        ndc_x = (xs.astype(T) + T(0.5)) / T(width)
-        ndc_y = (ys.astype(T) + T(0.5)) / T(height)
-        sx = ((T(2) * ndc_x - T(1)) * aspect) * fov
-        sy = (T(1) - T(2) * ndc_y) * fov
-        r = [((c0[k] * sx + c1[k] * sy) + c2[k] * T(-1)) + cam[k] * T(0) for k in range(3)]
-        n2 = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]
-        rs = TR.rsqrt(n2) if T is F32 else 1.0 / np.sqrt(n2)
-        Zt = np.asarray(Z, T)
-        X = [cam[k] + Zt * (r[k] * rs) for k in range(3)]
-        if A is not None:
-            At = np.asarray(A, T)
-            X = [((At[..., k, 0] * X[0] + At[..., k, 1] * X[1]) + At[..., k, 2] * X[2]) + At[..., k, 3] for k in range(3)]
-        e = [X[k] - cam_h[k] for k in range(3)]
-        Dist = np.sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]).astype(T)
-        v = [(rinv[k, 0] * e[0] + rinv[k, 1] * e[1]) + rinv[k, 2] * e[2] for k in range(3)]
-        qx, qy = v[0] / -v[2], v[1] / -v[2]
-        fx = ((qx / (aspect_h * fov_h) + T(1)) / T(2)) * T(width) - T(0.5)
-        fy = ((T(1) - qy / fov_h) / T(2)) * T(height) - T(0.5)
-    return fx.astype(T), fy.astype(T), Dist, v[2] < 0
-
-
-def reproject(cur, hist, cam_rd, ids, table, normal_threshold=0.9, depth_threshold=0.05):
-    """srt_temporal_motion_kernel's reprojection. cur: temporal_ref.frame(); hist: Tracer.read_denoise_history() with
-    'ids' (h, w) uint32, the history frame's shape indices; ids (h, w) uint32: the frame's; table: dict state, A, B.
-    -> temporal_ref.reproject's dict, and 'state' (h, w): each pixel's shape state (-1: no shape)."""
-    height, width = cur["Z"].shape
-    out = dict(h=np.zeros((height, width), F32), c=np.zeros((height, width, 3), F32), m1=np.zeros((height, width), F32),
-               m2=np.zeros((height, width), F32), taps=np.zeros((height, width), np.int32), borderline=np.zeros((height, width), bool),
-               state=np.full((height, width), -1, np.int64))
-    n_shapes = len(table["state"])
-    ids = np.asarray(ids, np.uint32)
-    has_shape = ids < n_shapes
-    sid = np.where(has_shape, ids, 0).astype(np.int64)
-    state = np.where(has_shape, table["state"][sid] if n_shapes else 0, -1)
-    out["state"] = state
-    if not hist["valid"]:
-        return out
-    same = TR.same_camera(cam_rd, hist["camera"])
-    if TR.invert_rotation(hist["camera"]) is None:  # TP_NONE (the moved shapes need the inverse also for the same camera)
-        return out
-    moved = state == MOVED
-    N = cur["N"]
-    B = table["B"][sid]
-    with np.errstate(all="ignore"):
-        t = [(B[..., k, 0] * N[..., 0] + B[..., k, 1] * N[..., 1]) + B[..., k, 2] * N[..., 2] for k in range(3)]
-        ln = np.sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]).astype(F32)
-        len_ok = (ln > 0) & np.isfinite(ln)
-        bn = np.stack([np.where(moved, t[k] / ln, N[..., k]) for k in range(3)], -1).astype(F32)
-    active = (cur["cov"] > 0) & np.all(np.isfinite(cur["c"]), axis=-1) & has_shape & (state != NO_HISTORY) & (~moved | len_ok)
-    ys, xs = np.mgrid[0:height, 0:width]
-    pm = project(cur["Z"], cam_rd, hist["camera"], width, height, A=table["A"][sid])
-    if same:
-        fx, fy, Dist, front = pm
-        projected = moved
-    else:
-        ps = TR.project(cur, cam_rd, hist["camera"], width, height)
-        fx, fy, Dist, front = (np.where(moved, a, b) for a, b in zip(pm, ps))
-        projected = np.ones((height, width), bool)
-    with np.errstate(all="ignore"):
-        inside = front & (fx > F32(-1)) & (fx < F32(width)) & (fy > F32(-1)) & (fy < F32(height))
-    active &= inside | ~projected
-    fxs, fys = np.where(inside & projected, fx, F32(0)).astype(F32), np.where(inside & projected, fy, F32(0)).astype(F32)
-    flx, fly = np.floor(fxs), np.floor(fys)
-    ax, ay = (fxs - flx).astype(F32), (fys - fly).astype(F32)
-    x0 = np.where(projected, flx.astype(np.int64), xs)
-    y0 = np.where(projected, fly.astype(np.int64), ys)
-    Dist = np.where(projected, Dist, cur["Z"]).astype(F32)
-    for f in (fxs, fys):
-        out["borderline"] |= active & projected & (np.abs(f - np.round(f)) < 1e-4)
-    taps = []
-    for k in range(4):
-        wx = ax if k & 1 else F32(1) - ax
-        wy = ay if k >> 1 else F32(1) - ay
-        wgt = np.where(projected, (wx * wy).astype(F32), F32(1) if k == 0 else F32(0)).astype(F32)
-        taps.append((x0 + (k & 1), y0 + (k >> 1), wgt, projected | (k == 0)))
-    hc, hcount, hm1, hm2, hg, hids = hist["colour"], hist["count"], hist["m1"], hist["m2"], hist["guide"], np.asarray(hist["ids"], np.uint32)
-    nt, dt = F32(normal_threshold), F32(depth_threshold)
-    sw = np.zeros((height, width), F32)
-    sc = np.zeros((height, width, 3), F32)
-    sh, s1, s2 = (np.zeros((height, width), F32) for _ in range(3))
-    for qx, qy, w, used in taps:
-        ok = active & used & (qx >= 0) & (qx < width) & (qy >= 0) & (qy < height)
-        jx, jy = np.clip(qx, 0, width - 1), np.clip(qy, 0, height - 1)
-        g0, g1 = hg[jy, jx, 0], hg[jy, jx, 1]
-        c = hc[jy, jx]
-        ok &= (g1[..., 3] > 0) & np.all(np.isfinite(c), axis=-1)
-        hs = hids[jy, jx]
-        hs_state = np.where(hs < n_shapes, table["state"][np.where(hs < n_shapes, hs, 0).astype(np.int64)], STATIC)
-        ok &= np.where(moved, hs == ids, hs_state == STATIC)
-        with np.errstate(all="ignore"):
-            dot = (bn[..., 0] * g0[..., 0] + bn[..., 1] * g0[..., 1]) + bn[..., 2] * g0[..., 2]
-            dz = np.abs(g0[..., 3] - Dist)
-            lim = dt * Dist
-            out["borderline"] |= ok & (np.abs(dot - nt) <= F32(1e-5) * max(abs(nt), F32(1e-5)))
-            out["borderline"] |= ok & (np.abs(dz - lim) <= F32(1e-5) * np.abs(lim))
-        ok &= (dot >= nt) & (dz <= lim)
-        wk = np.where(ok, w, F32(0)).astype(F32)
-        with np.errstate(all="ignore"):
-            sw = np.where(ok, sw + wk, sw)
-            sc = np.where(ok[..., None], sc + wk[..., None] * c, sc)
-            sh = np.where(ok, sh + wk * hcount[jy, jx], sh)
-            s1 = np.where(ok, s1 + wk * hm1[jy, jx], s1)
-            s2 = np.where(ok, s2 + wk * hm2[jy, jx], s2)
-        out["taps"] += ok
-    out["borderline"] |= (out["taps"] > 0) & (np.abs(sw - F32(0.01)) <= F32(1e-7))
-    has = sw >= F32(0.01)
-    with np.errstate(all="ignore"):
-        one = np.where(has, sw, F32(1))
-        out["h"] = np.where(has, sh / one, F32(0)).astype(F32)
-        out["c"] = np.where(has[..., None], sc / one[..., None], F32(0)).astype(F32)
-        out["m1"] = np.where(has, s1 / one, F32(0)).astype(F32)
-        out["m2"] = np.where(has, s2 / one, F32(0)).astype(F32)
-    return out
-
-
-def setup(canvas, inputs, F, hist, cam_rd, ids, table, history_limit=32, normal_threshold=0.9, depth_threshold=0.05):
-    """The whole set-up with object motion on, as temporal_ref.temporal_setup: the moved kernel when a shape of the table
-    is not STATIC and there is a history, else what the library launches without object motion."""
-    cur = TR.frame(canvas, inputs, F)
-    if hist["valid"] and np.any(table["state"] != STATIC):
-        rep = reproject(cur, hist, cam_rd, ids, table, normal_threshold, depth_threshold)
-    else:
-        rep = TR.reproject(cur, hist, cam_rd, normal_threshold, depth_threshold)
-    out = TR.integrate(cur, rep, history_limit)
-    out["rep"], out["cur"] = rep, cur
-    return out
 
 
 # ---- the moves tests/test_gpu_denoise_motion.py runs and tests/test_motion_reference.py checks the flagged share of ------
@@ -332,18 +171,3 @@ MOVES = [
     ("mixed", "mixed", 1, "move", [(1, "translate", (0.023, 0.0, 0.014)), (4, "rotate", 0.017), (7, "shift", 0.019)]),
 ]
 FRAMES, SIZE = 4, (128, 72)  # frame 0 starts the history, frames 1 .. FRAMES - 1 move
-
-
-def scene(name):
-    from simple_raytracer_amd import scenes as S
-    return S.sphere_scene() if name == "spheres" else S.mesh_scene() if name == "meshes" else S.mixed_test_scene()
-
-
-def camera_of(kind, k):
-    """camera of frame k: still (None), or the paths of tests/test_gpu_denoise_temporal.py cam_at"""
-    from simple_raytracer_amd import records as R
-    if kind is None:
-        return R.camera_matrix((0.0, 0.5, 5.0), 0.0, 0.0)
-    if kind == "move":
-        return R.camera_matrix((0.013 * k, 0.5 + 0.007 * k, 5.0 - 0.011 * k), 0.0, 0.0)
-    return R.camera_matrix((0.0, 0.5, 5.0), 0.011 * k, 0.0)

@@ -13,6 +13,7 @@ import denoise_ref as D
 
 F32 = np.float32
 DEFAULTS = dict(history_limit=32, normal_threshold=0.9, depth_threshold=0.05)
+STATIC, MOVED, NO_HISTORY = 0, 1, 2  # include/srt_abi.h SRT_MOTION_*: a shape's state in the object-motion table
 
 
 def _fma(a, b, c):
@@ -41,22 +42,37 @@ def same_camera(a, b):
     return fa.tobytes() == fb.tobytes()
 
 
-def invert_rotation(rd):
-    """The host's R^-1 (row-major (3, 3) float32) of the camera's upper 3x3, or None when singular or not finite."""
-    c = np.asarray(rd["camera_to_world"], np.float64)
-    m = np.array([[c[k][r] for k in range(3)] for r in range(3)])
+def inv3(m):
+    """The host's adjugate inverse (temporal.hip inv3) of a 3x3 m[row][col] in float64, or None when singular or not
+    finite."""
     a = m[1][1] * m[2][2] - m[1][2] * m[2][1]
     b = m[1][2] * m[2][0] - m[1][0] * m[2][2]
     d = m[1][0] * m[2][1] - m[1][1] * m[2][0]
-    det = m[0][0] * a + m[0][1] * b + m[0][2] * d
-    if not (det != 0.0) or not np.isfinite(det):
-        return None
-    inv = [a / det, (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det, (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det,
-           b / det, (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det, (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det,
-           d / det, (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det, (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det]
     with np.errstate(all="ignore"):
-        out = np.array(inv, np.float64).astype(F32)
-    return out.reshape(3, 3) if np.all(np.isfinite(out)) else None
+        det = m[0][0] * a + m[0][1] * b + m[0][2] * d
+        if not (det != 0.0) or not np.isfinite(det):
+            return None
+        inv = np.array([[a / det, (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det, (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det],
+                        [b / det, (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det, (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det],
+                        [d / det, (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det, (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det]], np.float64)
+    return inv if np.all(np.isfinite(inv)) else None
+
+
+def _rotation(rd):
+    """the camera's upper 3x3 (columns camera_to_world[0..2]) as float64 m[row][col]"""
+    c = np.asarray(rd["camera_to_world"], np.float64)
+    return np.array([[c[k][r] for k in range(3)] for r in range(3)])
+
+
+def invert_rotation(rd):
+    """The host's R^-1 (row-major (3, 3) float32) of the camera's upper 3x3: inv3 rounded to float32, or None when
+    singular or a float is not finite."""
+    inv = inv3(_rotation(rd))
+    if inv is None:
+        return None
+    with np.errstate(all="ignore"):
+        out = inv.astype(F32)
+    return out if np.all(np.isfinite(out)) else None
 
 
 def frame(canvas, inputs, F):
@@ -69,76 +85,121 @@ def frame(canvas, inputs, F):
     return dict(c=c, m1=D.lum(c), m2=m2, V=V, N=N, Z=Z, A=A, cov=cov, P=P)
 
 
-def project(cur, cam_rd, cam_h_rd, width, height):
-    """Where each pixel's first hit lands in the history camera: (fx, fy, D, in_front) float32 (h, w); None when the history
-    camera cannot be inverted."""
-    rinv = invert_rotation(cam_h_rd)
+def project(Z, cam_rd, cam_h_rd, width, height, A=None, dtype=F32):
+    """Where each pixel's first hit (depth Z (h, w) along its camera ray) lands in the history camera, after the per-pixel
+    map A (h, w, 3, 4) from the current world to the history's (None: none): (fx, fy, D, in_front) (h, w); None when the
+    history camera cannot be inverted. dtype float32 is the kernel's arithmetic; float64 the same formulas in double
+    (tests)."""
+    T = dtype
+    rinv = invert_rotation(cam_h_rd) if T is F32 else inv3(_rotation(cam_h_rd))
     if rinv is None:
         return None
-    c0, c1, c2, cam, aspect, fov = camera(cam_rd)
-    _, _, _, cam_h, aspect_h, fov_h = camera(cam_h_rd)
+    c0, c1, c2, cam, aspect, fov = (np.asarray(v, T) for v in camera(cam_rd))
+    _, _, _, cam_h, aspect_h, fov_h = (np.asarray(v, T) for v in camera(cam_h_rd))
+    rinv = np.asarray(rinv, T)
     ys, xs = np.mgrid[0:height, 0:width]
     with np.errstate(all="ignore"):
-        ndc_x = (xs.astype(F32) + F32(0.5)) / F32(width)
-        ndc_y = (ys.astype(F32) + F32(0.5)) / F32(height)
-        sx = ((F32(2) * ndc_x - F32(1)) * aspect) * fov
-        sy = (F32(1) - F32(2) * ndc_y) * fov
-        r = [((c0[k] * sx + c1[k] * sy) + c2[k] * F32(-1)) + cam[k] * F32(0) for k in range(3)]
-        rs = rsqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2])
-        Z = cur["Z"]
-        e = [(cam[k] + Z * (r[k] * rs)) - cam_h[k] for k in range(3)]
-        Dist = np.sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]).astype(F32)
+        ndc_x = (xs.astype(T) + T(0.5)) / T(width)
+        ndc_y = (ys.astype(T) + T(0.5)) / T(height)
+        sx = ((T(2) * ndc_x - T(1)) * aspect) * fov
+        sy = (T(1) - T(2) * ndc_y) * fov
+        r = [((c0[k] * sx + c1[k] * sy) + c2[k] * T(-1)) + cam[k] * T(0) for k in range(3)]
+        n2 = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]
+        rs = rsqrt(n2) if T is F32 else 1.0 / np.sqrt(n2)
+        Zt = np.asarray(Z, T)
+        X = [cam[k] + Zt * (r[k] * rs) for k in range(3)]
+        if A is not None:
+            At = np.asarray(A, T)
+            X = [((At[..., k, 0] * X[0] + At[..., k, 1] * X[1]) + At[..., k, 2] * X[2]) + At[..., k, 3] for k in range(3)]
+        e = [X[k] - cam_h[k] for k in range(3)]
+        Dist = np.sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]).astype(T)
         v = [(rinv[k, 0] * e[0] + rinv[k, 1] * e[1]) + rinv[k, 2] * e[2] for k in range(3)]
         qx, qy = v[0] / -v[2], v[1] / -v[2]
-        fx = ((qx / (aspect_h * fov_h) + F32(1)) / F32(2)) * F32(width) - F32(0.5)
-        fy = ((F32(1) - qy / fov_h) / F32(2)) * F32(height) - F32(0.5)
-    return fx.astype(F32), fy.astype(F32), Dist, v[2] < 0
+        fx = ((qx / (aspect_h * fov_h) + T(1)) / T(2)) * T(width) - T(0.5)
+        fy = ((T(1) - qy / fov_h) / T(2)) * T(height) - T(0.5)
+    return fx.astype(T), fy.astype(T), Dist, v[2] < 0
 
 
-def reproject(cur, hist, cam_rd, normal_threshold=0.9, depth_threshold=0.05):
+def reproject(cur, hist, cam_rd, normal_threshold=0.9, depth_threshold=0.05, ids=None, table=None):
     """-> dict h, c (h, w, 3), m1, m2 (the weight-normalised history; h = 0 where there is none), taps (h, w) = the number of
-    counted taps, borderline (h, w) bool. `hist` is Tracer.read_denoise_history()."""
+    counted taps, borderline (h, w) bool. `hist` is Tracer.read_denoise_history().
+
+    Without a table this is srt_temporal_setup_kernel; with one srt_temporal_motion_kernel (temporal_body.inc with
+    SRT_TEMPORAL_MOTION 1): ids (h, w) uint32 are the frame's shape indices, hist['ids'] the history frame's, table a dict
+    state (n,), A (n, 3, 4), B (n, 3, 3) float32 (motion_ref.scene_table); the result also holds 'state' (h, w), each
+    pixel's shape state (-1: no shape)."""
     height, width = cur["Z"].shape
     out = dict(h=np.zeros((height, width), F32), c=np.zeros((height, width, 3), F32), m1=np.zeros((height, width), F32),
                m2=np.zeros((height, width), F32), taps=np.zeros((height, width), np.int32), borderline=np.zeros((height, width), bool))
+    motion = table is not None
+    if motion:
+        n_shapes = len(table["state"])
+        ids = np.asarray(ids, np.uint32)
+        has_shape = ids < n_shapes
+        sid = np.where(has_shape, ids, 0).astype(np.int64)
+        state = np.where(has_shape, table["state"][sid] if n_shapes else 0, -1)
+        out["state"] = state
     if not hist["valid"]:
         return out
+    same = same_camera(cam_rd, hist["camera"])
+    # the motion kernel needs the inverse also for the same camera (a moved shape projects): TP_NONE without it
+    if (motion or not same) and invert_rotation(hist["camera"]) is None:
+        return out
     active = (cur["cov"] > 0) & np.all(np.isfinite(cur["c"]), axis=-1)
-    ys, xs = np.mgrid[0:height, 0:width]
-    if same_camera(cam_rd, hist["camera"]):
-        taps = [(xs, ys, np.ones((height, width), F32))]
-        Dist = cur["Z"]
-    else:
-        pr = project(cur, cam_rd, hist["camera"], width, height)
-        if pr is None:
-            return out
-        fx, fy, Dist, front = pr
-        with np.errstate(all="ignore"):
-            inside = front & (fx > F32(-1)) & (fx < F32(width)) & (fy > F32(-1)) & (fy < F32(height))
-        active &= inside
-        fxs, fys = np.where(inside, fx, F32(0)), np.where(inside, fy, F32(0))
-        flx, fly = np.floor(fxs), np.floor(fys)
-        ax, ay = (fxs - flx).astype(F32), (fys - fly).astype(F32)
-        x0, y0 = flx.astype(np.int64), fly.astype(np.int64)
-        for f in (fxs, fys):
-            out["borderline"] |= active & (np.abs(f - np.round(f)) < 1e-4)
-        taps = []
-        for k in range(4):
-            wx = ax if k & 1 else F32(1) - ax
-            wy = ay if k >> 1 else F32(1) - ay
-            taps.append((x0 + (k & 1), y0 + (k >> 1), (wx * wy).astype(F32)))
-    hc, hcount, hm1, hm2, hg = hist["colour"], hist["count"], hist["m1"], hist["m2"], hist["guide"]
     N = cur["N"]
+    moved = np.zeros((height, width), bool)
+    if motion:
+        moved = state == MOVED
+        B = table["B"][sid]
+        with np.errstate(all="ignore"):
+            t = [(B[..., k, 0] * N[..., 0] + B[..., k, 1] * N[..., 1]) + B[..., k, 2] * N[..., 2] for k in range(3)]
+            ln = np.sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]).astype(F32)
+            len_ok = (ln > 0) & np.isfinite(ln)
+            N = np.stack([np.where(moved, t[k] / ln, N[..., k]) for k in range(3)], -1).astype(F32)  # normalise(B_s N_p)
+        active &= has_shape & (state != NO_HISTORY) & (~moved | len_ok)
+    # the pixels that project: all under a moved camera (a static pixel by the camera alone), else the moved shapes' pixels;
+    # the others take the one tap p with weight 1 and D = Z_p
+    projected = moved if same else np.ones((height, width), bool)
+    ys, xs = np.mgrid[0:height, 0:width]
+    fx = fy = np.zeros((height, width), F32)
+    Dist, front = cur["Z"], np.zeros((height, width), bool)
+    if not same:
+        fx, fy, Dist, front = project(cur["Z"], cam_rd, hist["camera"], width, height)
+    if moved.any():
+        pm = project(cur["Z"], cam_rd, hist["camera"], width, height, A=table["A"][sid])
+        fx, fy, Dist, front = (np.where(moved, a, b) for a, b in zip(pm, (fx, fy, Dist, front)))
+    with np.errstate(all="ignore"):
+        inside = front & (fx > F32(-1)) & (fx < F32(width)) & (fy > F32(-1)) & (fy < F32(height))
+    active &= inside | ~projected
+    fxs, fys = np.where(inside & projected, fx, F32(0)).astype(F32), np.where(inside & projected, fy, F32(0)).astype(F32)
+    flx, fly = np.floor(fxs), np.floor(fys)
+    ax, ay = (fxs - flx).astype(F32), (fys - fly).astype(F32)
+    x0 = np.where(projected, flx.astype(np.int64), xs)
+    y0 = np.where(projected, fly.astype(np.int64), ys)
+    Dist = np.where(projected, Dist, cur["Z"]).astype(F32)
+    for f in (fxs, fys):
+        out["borderline"] |= active & projected & (np.abs(f - np.round(f)) < 1e-4)
+    taps = []
+    for k in range(4):
+        wx = ax if k & 1 else F32(1) - ax
+        wy = ay if k >> 1 else F32(1) - ay
+        wgt = np.where(projected, (wx * wy).astype(F32), F32(1) if k == 0 else F32(0)).astype(F32)
+        taps.append((x0 + (k & 1), y0 + (k >> 1), wgt, projected | (k == 0)))
+    hc, hcount, hm1, hm2, hg = hist["colour"], hist["count"], hist["m1"], hist["m2"], hist["guide"]
     nt, dt = F32(normal_threshold), F32(depth_threshold)
     sw = np.zeros((height, width), F32)
     sc = np.zeros((height, width, 3), F32)
     sh, s1, s2 = (np.zeros((height, width), F32) for _ in range(3))
-    for qx, qy, w in taps:
-        ok = active & (qx >= 0) & (qx < width) & (qy >= 0) & (qy < height)
+    for qx, qy, w, used in taps:
+        ok = active & used & (qx >= 0) & (qx < width) & (qy >= 0) & (qy < height)
         jx, jy = np.clip(qx, 0, width - 1), np.clip(qy, 0, height - 1)
         g0, g1 = hg[jy, jx, 0], hg[jy, jx, 1]
         c = hc[jy, jx]
         ok &= (g1[..., 3] > 0) & np.all(np.isfinite(c), axis=-1)
+        if motion:  # a moved shape's tap must show that shape; a static one's must not show a shape that has left
+            hs = np.asarray(hist["ids"], np.uint32)[jy, jx]
+            hs_state = np.where(hs < n_shapes, table["state"][np.where(hs < n_shapes, hs, 0).astype(np.int64)], STATIC)
+            ok &= np.where(moved, hs == ids, hs_state == STATIC)
         with np.errstate(all="ignore"):
             dot = (N[..., 0] * g0[..., 0] + N[..., 1] * g0[..., 1]) + N[..., 2] * g0[..., 2]
             dz = np.abs(g0[..., 3] - Dist)
@@ -157,10 +218,11 @@ def reproject(cur, hist, cam_rd, normal_threshold=0.9, depth_threshold=0.05):
     out["borderline"] |= (out["taps"] > 0) & (np.abs(sw - F32(0.01)) <= F32(1e-7))
     has = sw >= F32(0.01)
     with np.errstate(all="ignore"):
-        out["h"] = np.where(has, sh / np.where(has, sw, F32(1)), F32(0)).astype(F32)
-        out["c"] = np.where(has[..., None], sc / np.where(has, sw, F32(1))[..., None], F32(0)).astype(F32)
-        out["m1"] = np.where(has, s1 / np.where(has, sw, F32(1)), F32(0)).astype(F32)
-        out["m2"] = np.where(has, s2 / np.where(has, sw, F32(1)), F32(0)).astype(F32)
+        one = np.where(has, sw, F32(1))
+        out["h"] = np.where(has, sh / one, F32(0)).astype(F32)
+        out["c"] = np.where(has[..., None], sc / one[..., None], F32(0)).astype(F32)
+        out["m1"] = np.where(has, s1 / one, F32(0)).astype(F32)
+        out["m2"] = np.where(has, s2 / one, F32(0)).astype(F32)
     return out
 
 
@@ -187,10 +249,14 @@ def integrate(cur, rep, history_limit=32):
     return dict(c=c, V=V, h=h, commit=commit)
 
 
-def temporal_setup(canvas, inputs, F, hist, cam_rd, history_limit=32, normal_threshold=0.9, depth_threshold=0.05):
-    """The whole set-up: -> (integrate()'s dict with reproject()'s under 'rep', frame()'s under 'cur')."""
+def temporal_setup(canvas, inputs, F, hist, cam_rd, history_limit=32, normal_threshold=0.9, depth_threshold=0.05, ids=None, table=None):
+    """The whole set-up: -> (integrate()'s dict with reproject()'s under 'rep', frame()'s under 'cur'). With object motion
+    (ids, table: as reproject) the host's rule picks the kernel: the motion kernel when there is a history and a shape of
+    the table is not STATIC, else what the library launches without object motion."""
     cur = frame(canvas, inputs, F)
-    rep = reproject(cur, hist, cam_rd, normal_threshold, depth_threshold)
+    if not (table is not None and hist["valid"] and np.any(table["state"] != STATIC)):
+        ids = table = None
+    rep = reproject(cur, hist, cam_rd, normal_threshold, depth_threshold, ids=ids, table=table)
     out = integrate(cur, rep, history_limit)
     out["rep"], out["cur"] = rep, cur
     return out

@@ -8,19 +8,13 @@ import pytest
 
 import golden_io
 from conftest import bits_equal
+from gpu_harness import T  # noqa: F401 (the fixture)
 from simple_raytracer_amd import records as R, scenes as S
 from test_gpu_fuzz import random_scene
 
 pytestmark = pytest.mark.gpu
 CASES = golden_io.load_cases()
 MESH_CASES = sorted(n for n, g in CASES.items() if (g["shapes"]["type"] == 2).any())
-
-
-@pytest.fixture(scope="module")
-def T():
-    from simple_raytracer_amd import build, tracer
-    build.build_hip()
-    return tracer
 
 
 def bvh_tracer(T, g, sky, accel=1):

@@ -9,16 +9,10 @@ import pytest
 
 import golden_io
 from conftest import bits_equal
+from gpu_harness import T  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 CASES = golden_io.load_cases()
-
-
-@pytest.fixture(scope="module")
-def T():
-    from simple_raytracer_amd import build, tracer
-    build.build_hip()
-    return tracer
 
 
 def test_group_of_one_device_renders_the_golden_frames(T, sky):

@@ -9,44 +9,10 @@ import pytest
 
 import denoise_ref as D
 from conftest import bits_equal
+from gpu_harness import T, make, scene, tone  # noqa: F401 (T: the fixture)
 from simple_raytracer_amd import records as R, scenes as S
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def T():
-    from simple_raytracer_amd import build, tracer
-    build.build_hip()
-    return tracer
-
-
-def scene(name):
-    if name == "spheres":
-        return S.sphere_scene()
-    if name == "meshes":
-        return S.mesh_scene()
-    return S.mixed_test_scene()
-
-
-def make(T, sky, name, w, h, spp=4, accel=0, denoise=None, time=777, show_normals=False):
-    shapes, tris, mats = scene(name)
-    t = T.Tracer(w, h)
-    t.set_skybox(sky)
-    t.set_acceleration(accel)
-    t.options = R.render_data(w, h, spp, 10, camera_to_world=S.default_camera(), time=time, show_normals=show_normals)
-    t.scene_data = R.scene_data(len(shapes))
-    t.update_scene(shapes, tris, mats)
-    t.clear_canvas()
-    if denoise is not None:
-        t.set_denoise(**denoise)
-    return t
-
-
-def tone(x):
-    """the tonemapped value the resolve turns into a byte: sqrt(aces(x)), in [0, 1]"""
-    x = np.asarray(x, np.float32)
-    return np.sqrt(D._aces1(x)).astype(np.float64)
 
 
 # ---- 1. feature pass ----------------------------------------------------------------------------------------------------
@@ -200,7 +166,7 @@ def test_filter_matrix_matches_numpy(T, sky, w, h, sig):
     """The filter against numpy over frame shapes, K and sigma sets, with F counted from the dispatches."""
     k_render = FILTER_KS[(FILTER_FRAMES.index((w, h)) + sorted(FILTER_SIGMAS).index(sig)) % len(FILTER_KS)]
     sigmas = FILTER_SIGMAS[sig]
-    t = make(T, sky, "mixed", w, h, accel=1, denoise=dict(feature_samples=2, iterations=k_render, **sigmas))
+    t = make(T, sky, "mixed", w, h, spp=4, accel=1, denoise=dict(feature_samples=2, iterations=k_render, **sigmas))
     filter_against_numpy(t, sigmas, 2, k_render, f"{w}x{h} {sig}")
     t.close()
 

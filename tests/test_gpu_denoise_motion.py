@@ -1,8 +1,7 @@
 """GPU: object motion for the denoiser's temporal stage (srt_set_denoise_object_motion) -- the shape indices of the feature
-pass against the oracle, nothing moved = object motion off bit for bit, moved shapes against tests/motion_ref.py, the rules
+pass against the oracle, nothing moved = object motion off bit for bit, moved shapes against tests/temporal_ref.py, the rules
 that keep or drop the history, the error codes, and quality against the spatial filter while a shape is dragged."""
 import json
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -11,38 +10,10 @@ import denoise_ref as D
 import motion_ref as M
 import temporal_ref as TR
 from conftest import bits_equal
-from simple_raytracer_amd import records as R, scenes as S
-from test_gpu_denoise_inputs import SCENES, scene as inputs_scene
+from gpu_harness import SCENES, T, cam_at, guide_scene, make, scene, tone  # noqa: F401 (T: the fixture)
+from simple_raytracer_amd import scenes as S
 
 pytestmark = pytest.mark.gpu
-
-F32 = np.float32
-ROOT = Path(__file__).resolve().parent.parent
-
-
-@pytest.fixture(scope="module")
-def T():
-    from simple_raytracer_amd import build, tracer
-    build.build_hip()
-    return tracer
-
-
-def make(T, sky, scn, w, h, spp=2, accel=0, denoise=None, temporal=None, motion=False, time=777, cam=None):
-    shapes, tris, mats = scn
-    t = T.Tracer(w, h)
-    t.set_skybox(sky)
-    t.set_acceleration(accel)
-    t.options = R.render_data(w, h, spp, 10, camera_to_world=S.default_camera() if cam is None else cam, time=time)
-    t.scene_data = R.scene_data(len(shapes))
-    t.update_scene(shapes, tris, mats)
-    t.clear_canvas()
-    if denoise is not None:
-        t.set_denoise(**denoise)
-    if temporal is not None:
-        t.set_denoise_temporal(**temporal)
-    if motion:
-        t.set_denoise_object_motion(True)
-    return t
 
 
 def history(t):
@@ -62,7 +33,7 @@ def oracle_ids(oracle, t, shapes, tris, mats, w, h):
 
 
 def run_ids(T, sky, oracle, name, w, h, accel, dispatches=((3, 4096), (2, 31337))):
-    shapes, tris, mats, cam = inputs_scene(name)
+    shapes, tris, mats, cam = guide_scene(name)
     t = make(T, sky, (shapes, tris, mats), w, h, spp=1, accel=accel, denoise=dict(iterations=0), temporal={}, motion=True, cam=cam)
     got = []
     for i, (ns, tm) in enumerate(dispatches):
@@ -116,7 +87,7 @@ def test_nothing_moved_equals_motion_off(T, sky, kind):
         for t in (off, on):
             t.clear_canvas()
             t.update_scene(*scn)
-            t.options["camera_to_world"] = M.camera_of(kind, k)
+            t.options["camera_to_world"] = cam_at(k, kind)
             t.options["time"] = 300 + k
             outs.append(t.render(1).copy())
         assert np.array_equal(outs[0], outs[1]), k
@@ -140,9 +111,9 @@ def test_moved_shapes_match_numpy(T, sky, case):
     """tests/test_motion_reference.py asserts on the CPU that these moves flag at most 1 % of a frame's pixels"""
     name, scn_name, accel, cam_kind, steps = case
     w, h = M.SIZE
-    shapes, tris, mats = M.scene(scn_name)
+    shapes, tris, mats = scene(scn_name)
     tp = dict(history_limit=64, normal_threshold=0.9, depth_threshold=0.05)
-    t = make(T, sky, (shapes, tris, mats), w, h, accel=accel, denoise=dict(iterations=0), temporal=tp, motion=True, cam=M.camera_of(cam_kind, 0))
+    t = make(T, sky, (shapes, tris, mats), w, h, accel=accel, denoise=dict(iterations=0), temporal=tp, motion=True, cam=cam_at(0, cam_kind))
     t.render(1)
     moved_idx = [s[0] for s in steps]
     for k in range(1, M.FRAMES):
@@ -156,12 +127,12 @@ def test_moved_shapes_match_numpy(T, sky, case):
         want_table = M.scene_table((M.move_shapes(shapes, tris, steps, k - 1), tris, mats, t.scene_data), (now, tris, mats, t.scene_data))
         assert table["any_moved"] and table["state"].tolist() == want_table["state"].tolist()
         assert np.array_equal(table["A"], want_table["A"]) or np.abs(table["A"] - want_table["A"]).max() < 1e-6
-        t.options["camera_to_world"] = M.camera_of(cam_kind, k)
+        t.options["camera_to_world"] = cam_at(k, cam_kind)
         t.options["time"] = 2000 + k
         argb = t.render(1).copy().reshape(h, w, 4)
         inp = t.read_denoise_inputs()
         ids = t.read_denoise_shape_ids()[0]
-        want = M.setup(t.read_canvas(), inp, inp["T"], hist, t.options, ids, table, **tp)  # (the device's own table)
+        want = TR.temporal_setup(t.read_canvas(), inp, inp["T"], hist, t.options, ids=ids, table=table, **tp)  # (the device's own table)
         got = t.read_denoised()
         t.clear_canvas()
         got_h = t.read_denoise_history()
@@ -307,10 +278,6 @@ def test_error_codes(T, sky):
 
 
 # ---- 8. quality while a shape is dragged --------------------------------------------------------------------------------
-def tone(x):
-    return np.sqrt(D._aces1(np.asarray(x, F32))).astype(np.float64)
-
-
 def dilate(mask, r):
     out = mask.copy()
     for dy in range(-r, r + 1):
@@ -330,7 +297,7 @@ def test_quality_dragged_shape(T, sky, name):
     (profiles/r07_motion_quality.json): see DESIGN.md section 12."""
     scn_name, accel, steps = QUALITY[name]
     w, h, frames = 160, 90, 8
-    shapes, tris, mats = M.scene(scn_name)
+    shapes, tris, mats = scene(scn_name)
     idx = steps[0][0]
 
     def at(k):

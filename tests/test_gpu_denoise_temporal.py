@@ -10,52 +10,10 @@ import pytest
 import denoise_ref as D
 import temporal_ref as TR
 from conftest import bits_equal
-from simple_raytracer_amd import records as R, scenes as S
+from gpu_harness import T, cam_at, make, tone  # noqa: F401 (T: the fixture)
+from simple_raytracer_amd import records as R
 
 pytestmark = pytest.mark.gpu
-
-F32 = np.float32
-
-
-@pytest.fixture(scope="module")
-def T():
-    from simple_raytracer_amd import build, tracer
-    build.build_hip()
-    return tracer
-
-
-def scene(name):
-    if name == "spheres":
-        return S.sphere_scene()
-    if name == "meshes":
-        return S.mesh_scene()
-    return S.mixed_test_scene()
-
-
-def make(T, sky, name, w, h, spp=2, accel=0, denoise=None, temporal=None, time=777):
-    shapes, tris, mats = scene(name)
-    t = T.Tracer(w, h)
-    t.set_skybox(sky)
-    t.set_acceleration(accel)
-    t.options = R.render_data(w, h, spp, 10, camera_to_world=S.default_camera(), time=time)
-    t.scene_data = R.scene_data(len(shapes))
-    t.update_scene(shapes, tris, mats)
-    t.clear_canvas()
-    if denoise is not None:
-        t.set_denoise(**denoise)
-    if temporal is not None:
-        t.set_denoise_temporal(**temporal)
-    t.scene = (shapes, tris, mats)
-    return t
-
-
-def cam_at(k, kind="move"):
-    """camera of frame k of a path: small moves in x, y and z, or yaw / pitch steps, from the default camera"""
-    if kind == "move":
-        return R.camera_matrix((0.013 * k, 0.5 + 0.007 * k, 5.0 - 0.011 * k), 0.0, 0.0)
-    if kind == "yaw":
-        return R.camera_matrix((0.0, 0.5, 5.0), 0.011 * k, 0.0)
-    return R.camera_matrix((0.0, 0.5, 5.0), 0.004 * k, 0.009 * k)
 
 
 def next_frame(t, k, kind, time):
@@ -271,10 +229,6 @@ def test_set_denoise_off_turns_temporal_off(T, sky):
 
 
 # ---- 6. quality -------------------------------------------------------------------------------------------------------------
-def tone(x):
-    return np.sqrt(D._aces1(np.asarray(x, F32))).astype(np.float64)
-
-
 @pytest.mark.parametrize("name,accel", [("spheres", 0), ("meshes", 1)])
 def test_quality_moving_camera(T, sky, name, accel):
     w, h, frames = 160, 90, 8

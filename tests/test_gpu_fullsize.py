@@ -13,17 +13,11 @@ import numpy as np
 import pytest
 
 from conftest import bits_equal
+from gpu_harness import T  # noqa: F401 (the fixture)
 from simple_raytracer_amd import records as R, scenes as S
 
 pytestmark = pytest.mark.gpu
 THREADS = max(1, min(len(os.sched_getaffinity(0)), 64))
-
-
-@pytest.fixture(scope="module")
-def T():
-    from simple_raytracer_amd import build, tracer
-    build.build_hip()
-    return tracer
 
 
 def tracer_for(T, sky, shapes, tris, mats, rd, accel=None):

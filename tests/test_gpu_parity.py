@@ -8,17 +8,11 @@ import pytest
 import cases as C
 import golden_io
 from conftest import bits_equal
+from gpu_harness import T  # noqa: F401 (the fixture)
 from simple_raytracer_amd import records as R, scenes as S
 
 pytestmark = pytest.mark.gpu
 CASES = golden_io.load_cases()
-
-
-@pytest.fixture(scope="module")
-def T():
-    from simple_raytracer_amd import build, tracer
-    build.build_hip()
-    return tracer
 
 
 def make_tracer(T, g, sky, rd=None, lib=None):

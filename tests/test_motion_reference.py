@@ -1,11 +1,13 @@
 """CPU: the per-shape motion table of the temporal stage's object motion (srt_motion_table_host, host only) against its
-float64 formulas, the numpy restatement of the moved set-up kernel (tests/motion_ref.py) on analytic cases, its agreement
-with tests/temporal_ref.py, and the flagged share of the moves tests/test_gpu_denoise_motion.py runs."""
+float64 formulas (tests/motion_ref.py), the numpy restatement of the moved set-up kernel (tests/temporal_ref.py reproject
+with a table) on analytic cases, its agreement with the path without a table, and the flagged share of the moves
+tests/test_gpu_denoise_motion.py runs."""
 import numpy as np
 import pytest
 
 import motion_ref as M
 import temporal_ref as TR
+from gpu_harness import cam_at, scene
 from simple_raytracer_amd import records as R, scenes as S, tracer as T
 from test_temporal_reference import frame_of, history_of, rd
 
@@ -166,14 +168,14 @@ def test_translated_quad_finds_its_history_k_pixels_back():
         hist_f, hist_ids = quad_frame(w, h, L, cam, -1.0, 1.0)
         cur_f, ids = quad_frame(w, h, L, cam, -1.0 + k * pix, 1.0 + k * pix)
         A = np.hstack([np.eye(3), [[-k * pix], [0], [0]]])  # current -> history: back by k pixel widths
-        fx, fy, Dist, front = M.project(cur_f["Z"], cam, cam, w, h, A=np.broadcast_to(A.astype(F32), (h, w, 3, 4)))
+        fx, fy, Dist, front = TR.project(cur_f["Z"], cam, cam, w, h, A=np.broadcast_to(A.astype(F32), (h, w, 3, 4)))
         on = ids == 1
         xs = np.broadcast_to(np.arange(w)[None, :], (h, w))
         assert on.any() and np.abs(fx - (xs - k))[on].max() < 2e-3 and np.abs(fy - np.arange(h)[:, None])[on].max() < 2e-3
         hist = history_of(hist_f, hist_f["c"], 6.0, cam)
         hist["guide"][..., 1, 3] = hist_f["cov"]
         hist["ids"] = hist_ids
-        rep = M.reproject(cur_f, hist, cam, ids, table_for(A))
+        rep = TR.reproject(cur_f, hist, cam, ids=ids, table=table_for(A))
         inner = on & (hist_ids[:, np.clip(np.arange(w) - k, 0, w - 1)] == 1)
         assert np.all(rep["h"][inner & ~rep["borderline"]] > 0) and np.all(rep["h"][~on] == 0)
         src = hist["colour"][:, np.clip(np.arange(w) - k, 0, w - 1)]
@@ -181,7 +183,7 @@ def test_translated_quad_finds_its_history_k_pixels_back():
         assert sel.any() and np.allclose(rep["c"][sel], src[sel], rtol=2e-2, atol=2e-2)
         # the same pixels without the map look at where the quad was not: the shape index rejects what they find there
         wrong = dict(hist, ids=np.where(hist_ids == 1, 0, hist_ids).astype(np.uint32))
-        assert np.all(M.reproject(cur_f, wrong, cam, ids, table_for(A))["h"] == 0)
+        assert np.all(TR.reproject(cur_f, wrong, cam, ids=ids, table=table_for(A))["h"] == 0)
 
 
 def test_scaled_sphere_maps_a_hit_to_the_same_angle():
@@ -213,14 +215,14 @@ def test_nothing_moved_equals_temporal_ref_bit_for_bit():
         hist = history_of(cur, rng.uniform(0, 3, (h, w, 3)), 5.0, cam_h_rd)
         hist["ids"] = ids
         want = TR.reproject(cur, hist, cam_rd)
-        got = M.reproject(cur, hist, cam_rd, ids, M.static_table(3))  # the moved kernel's path with every shape static
+        got = TR.reproject(cur, hist, cam_rd, ids=ids, table=M.static_table(3))  # the moved kernel's path with every shape static
         for k in ("h", "c", "m1", "m2", "taps", "borderline"):
             assert np.array_equal(got[k], want[k]), k
         assert (want["h"] > 0).any()
         # a history pixel that showed a shape which has since moved does not count for a static pixel
         t = M.static_table(3)
         t["state"][2] = M.MOVED
-        got = M.reproject(cur, hist, cam_rd, np.zeros((h, w), np.uint32), t)
+        got = TR.reproject(cur, hist, cam_rd, ids=np.zeros((h, w), np.uint32), table=t)
         assert np.all(got["taps"] <= want["taps"]) and (got["taps"] < want["taps"]).any()
 
 
@@ -238,9 +240,9 @@ def test_rigid_move_of_every_shape_equals_moving_the_history_camera():
         Ainv = np.linalg.inv(Gm)[:3, :]  # current -> history
         cam_h_m = (np.float64(cam_m) @ G).astype(F32)  # column layout: (G C)^T = C^T G^T
         cam_h_rd = rd(w, h, cam_h_m)
-        a = M.project(Z, cam_rd, cam_rd, w, h, A=np.broadcast_to(Ainv.astype(F32), (h, w, 3, 4)))
-        b = TR.project(dict(Z=Z), cam_rd, cam_h_rd, w, h)
-        truth = M.project(Z, cam_rd, cam_h_rd, w, h, dtype=np.float64)
+        a = TR.project(Z, cam_rd, cam_rd, w, h, A=np.broadcast_to(Ainv.astype(F32), (h, w, 3, 4)))
+        b = TR.project(Z, cam_rd, cam_h_rd, w, h)
+        truth = TR.project(Z, cam_rd, cam_h_rd, w, h, dtype=np.float64)
         assert a[3].all() and b[3].all()
         # float32 rounding of either route: the point and both camera positions are at most `mag` from the origin, ~10
         # rounded operations lead to the view vector v (each within 2^-24 of a value <= ~3 mag: the 3-term sums), q = v.xy / -v.z
@@ -277,7 +279,7 @@ def geometry_frame(oracle, name, cam_m, shapes, tris, mats, w, h, time):
 def test_moves_stay_under_the_flagged_share(oracle, case):
     """at most 1 % of a frame's pixels flagged, for every move of the GPU test; the moved shape has pixels with history and
     disoccluded pixels without"""
-    FRAMES, SIZE, camera_of, scene = M.FRAMES, M.SIZE, M.camera_of, M.scene
+    FRAMES, SIZE = M.FRAMES, M.SIZE
     name, scn, accel, cam_kind, steps = case
     w, h = SIZE
     shapes, tris, mats = scene(scn)
@@ -285,14 +287,14 @@ def test_moves_stay_under_the_flagged_share(oracle, case):
     prev = None
     for k in range(FRAMES):
         now = M.move_shapes(shapes, tris, steps, k)
-        cur, ids, rdata = geometry_frame(oracle, scn, camera_of(cam_kind, k), now, tris, mats, w, h, 2000 + k)
+        cur, ids, rdata = geometry_frame(oracle, scn, cam_at(k, cam_kind), now, tris, mats, w, h, 2000 + k)
         if prev is not None:
             p_cur, p_ids, p_rd, p_shapes = prev
             table = M.scene_table((p_shapes, tris, mats, sd), (now, tris, mats, sd))
             assert table is not None and [i for i, s in enumerate(table["state"]) if s == M.MOVED] == sorted(s[0] for s in steps)
             hist = TR.history_from_commit(TR.integrate(p_cur, TR.reproject(p_cur, dict(valid=False), p_rd))["commit"], p_rd)
             hist["ids"] = p_ids
-            rep = M.reproject(cur, hist, rdata, ids, table)
+            rep = TR.reproject(cur, hist, rdata, ids=ids, table=table)
             share = rep["borderline"].mean()
             on_moved = np.isin(ids, [s[0] for s in steps])
             kept, lost = on_moved & (rep["h"] > 0), (cur["cov"] > 0) & (rep["taps"] == 0) & ~rep["borderline"]

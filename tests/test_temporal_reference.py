@@ -80,7 +80,7 @@ def test_translated_camera_taps_land_analytically():
     for k in (1, 3, -2):
         cam = rd(w, h, R.camera_matrix((k * pix, 0.0, 0.0)))
         cur = plane_frame(w, h, L, cam)
-        fx, fy, Dist, front = TR.project(cur, cam, cam_h, w, h)
+        fx, fy, Dist, front = TR.project(cur["Z"], cam, cam_h, w, h)
         xs = np.arange(w)[None, :] + k
         assert front.all()
         assert np.abs(fx - xs).max() < 2e-3 and np.abs(fy - np.arange(h)[:, None]).max() < 2e-3, k
@@ -104,7 +104,7 @@ def test_taps_behind_camera_and_outside_image_rejected():
     # the history camera stands beyond the plane, looking the same way: every point lies behind it
     behind = rd(w, h, R.camera_matrix((0.0, 0.0, -2 * L)))
     hist = history_of(cur, cur["c"], 4.0, behind)
-    fx, fy, Dist, front = TR.project(cur, cam, behind, w, h)
+    fx, fy, Dist, front = TR.project(cur["Z"], cam, behind, w, h)
     assert not front.any()
     assert np.all(TR.reproject(cur, hist, cam)["h"] == 0)
     # moved far sideways: every tap falls outside the history image
