@@ -254,6 +254,10 @@ const char *srt_group_last_error(const srt_group *g);
 int srt_group_size(const srt_group *g);
 srt_tracer *srt_group_tracer(srt_group *g, int i);
 int srt_group_set_skybox(srt_group *g, const float *rgba, int width, int height);
+/* albedo textures (below): the same call on every member */
+int srt_group_set_textures(srt_group *g, const srt_texture_desc *descs, size_t n);
+int srt_group_set_material_textures(srt_group *g, const srt_material_texture *bindings, size_t n_materials);
+int srt_group_set_triangle_uvs(srt_group *g, const float *uv, size_t n_triangles);
 int srt_group_set_acceleration(srt_group *g, int mode);
 int srt_group_update_scene(srt_group *g, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
                            const srt_material *materials, size_t n_materials, const srt_scene_data *scene);
@@ -376,6 +380,52 @@ int srt_motion_table_host(const srt_shape *h_shapes, size_t h_n_shapes, const sr
                           const srt_material *h_materials, size_t h_n_materials, const srt_scene_data *h_scene,
                           const srt_shape *c_shapes, size_t c_n_shapes, const srt_triangle *c_triangles, size_t c_n_triangles,
                           const srt_material *c_materials, size_t c_n_materials, const srt_scene_data *c_scene, uint32_t *table, int *keep);
+
+/* ---- albedo textures ----------------------------------------------------------
+ * Opt-in: where a material has a texture bound, the colour that multiplies the path's mask (and the denoiser's albedo
+ * guide) is the texel at the hit's UV instead of srt_material.color. Nothing else about a material changes and a lookup
+ * draws no random numbers. With no texture bound the library launches exactly the kernels it launches without this
+ * interface. show_normals ignores textures. Each of the three setters takes effect for later dispatches, does not clear
+ * the canvas (the caller clears, as after srt_update_scene) and drops the denoiser's temporal history.
+ *
+ * UV, all float32, unfused, in the order written; X = the hit position the kernel shades:
+ *   sphere  n = (X - centre) / radius;  u = dm_atan2pif(n.z, n.x) * 0.5 + 0.5;  v = n.y * 0.5 + 0.5
+ *   plane   u = dot(X - position, T), v = dot(X - position, B), dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; the frame
+ *           (srt_plane_frame_host) is made at srt_update_scene in double and rounded to float: a = the world axis on
+ *           which |normal| is smallest (ties: x, then y, then z), T = normalise(a x n), B = n x T. A plane whose normal
+ *           is zero or not finite has no frame and keeps the material colour.
+ *   model   uv = (uv0 * w2 + uv1 * w0) + uv2 * w1 with the shading's barycentric weights (w0, w1 of render.cl:223-241,
+ *           w2 = 1 - w0 - w1); without srt_set_triangle_uvs: uv = (w0, w1)
+ * then u = u * scale_u, v = v * scale_v and the sampler over the W x H image, addressing REPEAT, fW = (float)W:
+ *   NEAREST pu = u * fW, pv = v * fH; column floor(pu) mod W, row floor(pv) mod H (mod never negative); the texel as stored
+ *   LINEAR  fu = u * fW - 0.5, fv = v * fH - 0.5; x0 = floor(fu), y0 = floor(fv); a = fu - x0, b = fv - y0; columns
+ *           x0 mod W and (x0 + 1) mod W, rows likewise; w00 = (1-a)*(1-b), w10 = a*(1-b), w01 = (1-a)*b, w11 = a*b;
+ *           channel = dm_bilinear(w00, T00, w10, T10, w01, T01, w11, T11) (csrc/detmath.h; T10 = column x0+1, row y0)
+ *   A coordinate (pu, pv / fu, fv) that is NaN, infinite or not below 2^30 in magnitude: the texel (0, 0) as stored.
+ * Texels are expected finite and not negative; they are not checked (as the skybox's are not). */
+
+/* n images (n <= SRT_MAX_TEXTURES), copied; n == 0 (descs may be NULL) removes them all. SRT_ERR_INVALID: NULL texels,
+ * width or height < 1 or > 16384, too many images. */
+int srt_set_textures(srt_tracer *t, const srt_texture_desc *descs, size_t n);
+/* One entry per material, in the material array's order; fewer entries than materials: none for the rest; NULL / 0 unbinds
+ * everything. Checked at the next srt_update_scene and at every dispatch: a texture index at or beyond the image count (or
+ * below -1), an unknown filter or a scale that is not finite is SRT_ERR_INVALID (entries beyond the scene's materials too
+ * are checked). An srt_update_scene that fails one of these checks fails before anything is replaced: the handle keeps
+ * its previous scene. */
+int srt_set_material_textures(srt_tracer *t, const srt_material_texture *bindings, size_t n_materials);
+/* n_triangles x 3 x 2 floats (u, v per vertex), parallel to the triangle array of srt_update_scene; NULL: no UVs.
+ * A count that differs from the scene's triangle count is SRT_ERR_INVALID at the next srt_update_scene and at dispatches. */
+int srt_set_triangle_uvs(srt_tracer *t, const float *uv, size_t n_triangles);
+/* Which kernels the last srt_trace launched: *textured = 1 when the textured instantiations ran (some material of the
+ * scene has a texture bound), else 0. */
+int srt_last_trace_textured(const srt_tracer *t, int *textured);
+/* Host-only (no device). The frame of a plane with this normal: returns 1 and writes T, B (3 floats each), or 0 when the
+ * plane has none (T, B zeroed). */
+int srt_plane_frame_host(const float normal[3], float T[3], float B[3]);
+/* Host-only: the checks of the three setters and of their meeting a scene. SRT_OK or SRT_ERR_INVALID. descs may be NULL
+ * when only the count matters (n_textures images assumed good); uv_triangles < 0: no UVs set. */
+int srt_texture_check_host(const srt_texture_desc *descs, size_t n_textures, const srt_material_texture *bindings, size_t n_bindings,
+                           long long uv_triangles, size_t scene_triangles);
 
 /* Device self-test of the deterministic math (tests only). Walks r = 0, stride, ... over
  * all 2^32 RNG outputs: out[0..2] = mismatch counts of the kernel-local sqrt / log / cos

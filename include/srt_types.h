@@ -151,6 +151,19 @@ typedef struct srt_temporal_params {
 	int32_t reserved[4];    /* must be 0 */
 } srt_temporal_params;
 
+/* Albedo textures (srt_set_textures, srt_set_material_textures; include/srt_abi.h). */
+#define SRT_MAX_TEXTURES 64
+enum { SRT_FILTER_LINEAR = 0, SRT_FILTER_NEAREST = 1 };
+typedef struct srt_texture_desc {
+	const float *rgba; /* width * height * 4 floats, row 0 = bottom (as the skybox) */
+	int32_t width, height;
+} srt_texture_desc;
+typedef struct srt_material_texture {
+	int32_t texture; /* index into the images of srt_set_textures; -1: the material keeps its colour */
+	int32_t filter;  /* SRT_FILTER_* */
+	float scale_u, scale_v; /* finite; u *= scale_u, v *= scale_v before the sampler */
+} srt_material_texture;
+
 #ifdef __cplusplus
 }
 #endif
@@ -204,5 +217,7 @@ SRT_STATIC_ASSERT(offsetof(srt_temporal_params, history_limit) == 4, "TemporalPa
 SRT_STATIC_ASSERT(offsetof(srt_temporal_params, normal_threshold) == 8, "TemporalParams.normal_threshold@8");
 SRT_STATIC_ASSERT(offsetof(srt_temporal_params, depth_threshold) == 12, "TemporalParams.depth_threshold@12");
 SRT_STATIC_ASSERT(offsetof(srt_temporal_params, reserved) == 16, "TemporalParams.reserved@16");
+SRT_STATIC_ASSERT(sizeof(srt_material_texture) == 16, "MaterialTexture 16 B");
+SRT_STATIC_ASSERT(offsetof(srt_material_texture, scale_u) == 8, "MaterialTexture.scale_u@8");
 
 #endif /* SRT_TYPES_H */

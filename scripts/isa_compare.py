@@ -7,7 +7,7 @@ compiled device-only with the product flags of build.py, its gfx950 code object 
 llvm-objdump, and every function in it is compared instruction by instruction, branch offsets and the s_nop padding
 between functions left out. A function that only one side has counts as a difference; the plain ordered reduction is
 matched across its rename to srt_reduce_kernel<false> (a template since the denoiser's moments variant). Exit status 1 on
-any difference.
+any difference; with --allow-new, functions that only the new tree has do not count.
 """
 import re
 import subprocess
@@ -61,23 +61,27 @@ def functions(elf):
 
 
 def main():
-    old_tree, new_tree = sys.argv[1], sys.argv[2]
+    allow_new = "--allow-new" in sys.argv
+    old_tree, new_tree = [x for x in sys.argv[1:] if x != "--allow-new"][:2]
     B = build_module()
     a, b = {}, {}
     with tempfile.TemporaryDirectory() as d:
         a_dir, b_dir = Path(d) / "a", Path(d) / "b"
         a_dir.mkdir()
         b_dir.mkdir()
-        for src in B.SOURCES:
-            a.update({(src, RENAMED.get(k, k)): v for k, v in functions(build(B, old_tree, src, a_dir)).items()})
-            b.update({(src, k): v for k, v in functions(build(B, new_tree, src, b_dir)).items()})
+        for src in B.SOURCES:  # (a source only one tree has: its functions are reported as "only in")
+            if (Path(old_tree) / "simple-raytracer_amd/csrc" / src).exists():
+                a.update({(src, RENAMED.get(k, k)): v for k, v in functions(build(B, old_tree, src, a_dir)).items()})
+            if (Path(new_tree) / "simple-raytracer_amd/csrc" / src).exists():
+                b.update({(src, k): v for k, v in functions(build(B, new_tree, src, b_dir)).items()})
     names = sorted(a.keys() | b.keys())
     bad = 0
     for k in names:
         same = k in a and k in b and a[k] == b[k]
-        bad += not same
+        bad += not same and not (allow_new and k not in a)
         where = "" if k in a and k in b else f"  only in {'old' if k in a else 'new'}"
-        print(f"{'same' if same else 'DIFFERENT'}  {k[0]}  {k[1]}  ({len(a.get(k, b.get(k)))} instructions){where}")
+        word = "same" if same else "new" if allow_new and k not in a else "DIFFERENT"
+        print(f"{word}  {k[0]}  {k[1]}  ({len(a.get(k, b.get(k)))} instructions){where}")
     print(f"{len(names)} functions of {len(B.SOURCES)} sources compared, {bad} different")
     sys.exit(1 if bad or not names else 0)
 

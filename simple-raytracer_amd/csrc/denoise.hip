@@ -169,7 +169,14 @@ int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples
 	fp.albedo_hits = t->dn_ah.ptr;
 	fp.num_pixels = (uint32_t)full_pixels(t);
 	fp.feature_samples = fs;
-	if (t->om_on) srt_launch_features_ids(fp, t->om_ids[t->om_cur].ptr, t->stream); // temporal.hip: object motion
+	if (t->last_trace_textured) { // albedo textures: the texel at the first hit is the albedo (srt_texture.hip)
+		TexFeatureParams fx;
+		memset(&fx, 0, sizeof fx);
+		static_cast<FeatureParams &>(fx) = fp;
+		fx.tx = srt_texture_params(t);
+		if (t->om_on) srt_launch_features_ids_tex(fx, t->om_ids[t->om_cur].ptr, t->stream);
+		else srt_launch_features_tex(fx, t->stream);
+	} else if (t->om_on) srt_launch_features_ids(fp, t->om_ids[t->om_cur].ptr, t->stream); // temporal.hip: object motion
 	else srt_launch_features(fp, t->stream);
 	SRT_HIP(t, hipGetLastError());
 	t->dn_T += 1;

@@ -223,6 +223,41 @@ struct FeatureParams {
 	uint32_t feature_samples; /* min(feature_samples, num_samples), > 0 */
 };
 
+/* Albedo textures (include/srt_abi.h "albedo textures" states the UV rules and the sampler). The textured kernels are
+ * the text of kernels.hip compiled a second time with SRT_TEXTURED set (kernels_tex.hip), under names of their own and
+ * with these parameter blocks: the untextured ones' parameters, then the texture tables. The untextured kernels see
+ * none of this. */
+struct TexDesc { /* one image inside TexParams.texels */
+	uint32_t offset; /* first texel (float4 units) */
+	int32_t w, h;
+	float fw, fh; /* exact int -> float conversions */
+	uint32_t _pad[3];
+};
+static_assert(sizeof(TexDesc) == 32, "TexDesc 32 B");
+struct PlaneFrame { /* per shape; only textured plane lanes read it */
+	float px, py, pz, valid; /* the plane's position; valid = 1 when the plane has a frame, else 0 (the material colour) */
+	float tx, ty, tz, _pad0;
+	float bx, by, bz, _pad1;
+};
+static_assert(sizeof(PlaneFrame) == 48, "PlaneFrame 48 B");
+struct TexParams {
+	const float *texels;                  /* RGBA32F, all images back to back */
+	const TexDesc *descs;
+	const srt_material_texture *bindings; /* one per material of the scene (texture = -1: none) */
+	const PlaneFrame *frames;             /* one per shape */
+	const float *tri_uvs;                 /* 6 floats per triangle of the scene's triangle array, or NULL */
+};
+struct TexTraceParams : TraceParams {
+	TexParams tx;
+};
+struct TexFeatureParams : FeatureParams {
+	TexParams tx;
+};
+void srt_launch_trace_tex(TexTraceParams p, bool count_triangles, int num_waves, void *stream);
+int srt_trace_tex_resident_waves_per_cu(const TexTraceParams &p, bool count_triangles);
+void srt_launch_features_tex(const TexFeatureParams &p, void *stream);
+void srt_launch_features_ids_tex(const TexFeatureParams &p, uint32_t *shape_ids, void *stream);
+
 void srt_launch_trace(TraceParams p, bool count_triangles, int num_waves, void *stream);
 void srt_launch_reduce(const ReduceParams &p, void *stream);
 /* the same reduction that also adds (1/n) sum_k lum(radiance_k)^2 into moments[pixel] (denoiser; `running`.w carries the sum across batches) */

@@ -74,7 +74,11 @@
 			nsum = nsum + nrm;
 			tsum = tsum + tmin;
 			const srt_float3 &mc = p.materials[material].color;
+#if SRT_TEXTURED
+			asum = asum + texture_albedo<HAS_MODELS, USE_BVH>(p, fp.tx, best, best_tri, org + dir * tmin, material, mk(mc.x, mc.y, mc.z));
+#else
 			asum = asum + mk(mc.x, mc.y, mc.z);
+#endif
 			hits = hits + 1.0f;
 #if SRT_FEATURES_IDS
 			if (sample == 0) id0 = (uint32_t)best;

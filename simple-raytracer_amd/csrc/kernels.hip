@@ -37,6 +37,30 @@
 #include "device_types.h"
 #include "tonemap.h" // aces1, to_uchar (the resolve), lum (the moments)
 
+// Albedo textures: kernels_tex.hip compiles this text a second time with SRT_TEXTURED set. That build keeps
+// the trace and feature kernels and their launch wrappers only, under the names below and with the texture tables behind
+// their parameters; everything between `#if SRT_TEXTURED` and its `#endif` exists there alone. With the macro unset this
+// file preprocesses to what it was before textures: a template parameter or a shared __device__ function in their place
+// reschedules the untextured kernels.
+#ifndef SRT_TEXTURED
+#define SRT_TEXTURED 0
+#endif
+#if SRT_TEXTURED
+#define SRT_TRACE_PARAMS TexTraceParams
+#define SRT_FEATURE_PARAMS TexFeatureParams
+#define srt_trace_kernel srt_trace_tex_kernel
+#define srt_features_kernel srt_features_tex_kernel
+#define srt_features_ids_kernel srt_features_ids_tex_kernel
+#define srt_launch_trace srt_launch_trace_tex
+#define srt_trace_resident_waves_per_cu srt_trace_tex_resident_waves_per_cu
+#define srt_launch_features srt_launch_features_tex
+#define srt_launch_features_ids srt_launch_features_ids_tex
+int srt_trace_lds_floats(int has_models, int use_bvh);
+#else
+#define SRT_TRACE_PARAMS TraceParams
+#define SRT_FEATURE_PARAMS FeatureParams
+#endif
+
 // ---- regions: where the trace kernel's instructions are executed (development aid) ------------------------------
 // SRT_REGION(NAME) marks the start of a stretch of the trace kernel that runs as often as its first statement. In the
 // product build it expands to nothing; scripts/isa_phase_mix.py reads the markers' source lines and assigns every
@@ -850,6 +874,100 @@ __device__ __forceinline__ f3 sky_box(const TraceParams &p_live, f3 dir) {
 	return sample_sky((const float *)p.sky, p.sky_w, p.sky_h, p.f_sky_w, p.f_sky_h, u, v) + sun;
 }
 
+#if SRT_TEXTURED
+// ---- albedo textures: include/srt_abi.h states these rules; tests/texture_ref.py copies the expressions below ----
+__device__ __forceinline__ int tex_wrap(int x, int n) { // x mod n, never negative
+	const int m = x % n;
+	return m < 0 ? m + n : m;
+}
+// The sampler, addressing REPEAT. (u, v) already scaled.
+//   NEAREST: pu = u * fW, pv = v * fH; texel (floor(pu) mod W, floor(pv) mod H) as stored.
+//   LINEAR:  fu = u * fW - 0.5, fv = v * fH - 0.5; x0 = floor(fu), y0 = floor(fv); a = fu - x0, b = fv - y0; columns x0 mod W and
+//            (x0 + 1) mod W, rows likewise; sample_sky's weights and dm_bilinear.
+//   A coordinate (pu, pv / fu, fv) that is NaN, infinite or >= 2^30 in magnitude: texel (0, 0) as stored.
+__device__ __forceinline__ f3 sample_texture(const TexParams &tx, int texture, int filter, float u, float v) {
+	const TexDesc *__restrict__ d = tx.descs + texture;
+	const int W = d->w, H = d->h;
+	const float4 *__restrict__ img = reinterpret_cast<const float4 *>(tx.texels) + d->offset;
+	float fu = u * d->fw, fv = v * d->fh;
+	if (filter == SRT_FILTER_LINEAR) {
+		fu = fu - 0.5f;
+		fv = fv - 0.5f;
+	}
+	if (!(dm_fabs(fu) < 0x1p30f && dm_fabs(fv) < 0x1p30f)) {
+		const float4 T = img[0];
+		return mk(T.x, T.y, T.z);
+	}
+	const float x0f = __builtin_floorf(fu), y0f = __builtin_floorf(fv);
+	const int i0 = tex_wrap((int)x0f, W), j0 = tex_wrap((int)y0f, H);
+	if (filter != SRT_FILTER_LINEAR) {
+		const float4 T = img[(size_t)j0 * W + i0];
+		return mk(T.x, T.y, T.z);
+	}
+	const float a = fu - x0f, b = fv - y0f;
+	const int i1 = i0 + 1 == W ? 0 : i0 + 1, j1 = j0 + 1 == H ? 0 : j0 + 1;
+	const float4 T00 = img[(size_t)j0 * W + i0];
+	const float4 T10 = img[(size_t)j0 * W + i1];
+	const float4 T01 = img[(size_t)j1 * W + i0];
+	const float4 T11 = img[(size_t)j1 * W + i1];
+	const float w00 = (1.0f - a) * (1.0f - b), w10 = a * (1.0f - b), w01 = (1.0f - a) * b, w11 = a * b;
+	return mk(dm_bilinear(w00, T00.x, w10, T10.x, w01, T01.x, w11, T11.x), dm_bilinear(w00, T00.y, w10, T10.y, w01, T01.y, w11, T11.y),
+	          dm_bilinear(w00, T00.z, w10, T10.z, w01, T01.z, w11, T11.z));
+}
+
+// The albedo of the hit at `pos` on shape `best`: the texel at the hit's UV where the material has a texture bound, else
+// `mcolor`. Only lanes with a binding load anything beyond it. The UV per kind of shape (products and sums unfused, in this order):
+//   sphere  n = (pos - centre) / radius (SHADE_WINNER's normal before the front-face flip); u = dm_atan2pif(n.z, n.x) * 0.5 + 0.5,
+//           v = n.y * 0.5 + 0.5 (the sky's mapping, sky_box)
+//   plane   d = pos - position; u = (d.x * T.x + d.y * T.y) + d.z * T.z, v the same with B (PlaneFrame, made by the host);
+//           a plane without a frame keeps mcolor
+//   model   SHADE_MESH_NORMAL's barycentric weights; uv = (uv0 * w2 + uv1 * w0) + uv2 * w1, without UVs (w0, w1)
+template <bool HAS_MODELS, bool USE_BVH>
+__device__ __forceinline__ f3 texture_albedo(const TraceParams &p, const TexParams &tx, int best, uint32_t best_tri, f3 pos, int material, f3 mcolor) {
+	const srt_material_texture bind = tx.bindings[material];
+	if (bind.texture < 0) return mcolor;
+	const WinnerRec *__restrict__ wr = p.winners + best;
+	const int type = wr->type;
+	float u, v;
+	if (type == SRT_SHAPE_SPHERE) {
+		const f3 n = div3_by_rcp(pos - mk(wr->vx, wr->vy, wr->vz), wr->w, wr->inv_w);
+		u = dm_atan2pif(n.z, n.x) * 0.5f + 0.5f;
+		v = n.y * 0.5f + 0.5f;
+	} else if (type == SRT_SHAPE_PLANE) {
+		const float4 *__restrict__ fr = reinterpret_cast<const float4 *>(tx.frames + best);
+		const float4 P = fr[0], T = fr[1], B = fr[2];
+		if (P.w == 0.0f) return mcolor;
+		const f3 d = pos - mk(P.x, P.y, P.z);
+		u = (d.x * T.x + d.y * T.y) + d.z * T.z;
+		v = (d.x * B.x + d.y * B.y) + d.z * B.z;
+	} else if (HAS_MODELS) {
+		const srt_model *__restrict__ m = &p.shapes[best].shape.model;
+		const float *__restrict__ w = USE_BVH ? p.bvh_blocks + (size_t)(best_tri >> 2) * 32u + (best_tri & 3u) * SRT_BVH_TRI_FLOATS
+		                                      : p.wtris + (size_t)(wr->first_wtri + best_tri) * SRT_WTRI_FLOATS;
+		const uint32_t tri_in_model = USE_BVH ? bvh_tri_in_model(reinterpret_cast<const float4 *>(p.bvh_blocks), best_tri) : best_tri;
+		f3 v0 = mk(w[0], w[1], w[2]);
+		f3 e1 = mk(w[3], w[4], w[5]);
+		f3 e2 = mk(w[6], w[7], w[8]);
+		f3 v2 = pos - v0;
+		float d00 = dot3(e1, e1), d01 = dot3(e1, e2), d11 = dot3(e2, e2);
+		float d20 = dot3(v2, e1), d21 = dot3(v2, e2);
+		float den = d00 * d11 - d01 * d01;
+		float w0 = (d11 * d20 - d01 * d21) / den;
+		float w1 = (d00 * d21 - d01 * d20) / den;
+		float w2 = 1.0f - w0 - w1;
+		u = w0, v = w1;
+		if (tx.tri_uvs) {
+			const float *__restrict__ t = tx.tri_uvs + 6ull * (m->triangle_index + tri_in_model);
+			u = (t[0] * w2 + t[2] * w0) + t[4] * w1;
+			v = (t[1] * w2 + t[3] * w0) + t[5] * w1;
+		}
+	} else {
+		return mcolor;
+	}
+	return sample_texture(tx, bind.texture, bind.filter, u * bind.scale_u, v * bind.scale_v);
+}
+#endif
+
 
 } // namespace
 
@@ -1000,7 +1118,7 @@ constexpr uint32_t hq_fields(bool has_models) { return has_models ? 17u : 16u; }
 // spheres and planes (BASELINE configs 0, 1, 3) get a leaner kernel; the host picks the
 // instantiation from the scene.
 template <bool COUNT_TRIS, bool USE_LDS, bool HAS_MODELS, bool USE_BVH>
-__global__ __launch_bounds__(64, USE_BVH ? SRT_TRACE_WAVES_PER_SIMD_BVH : HAS_MODELS ? SRT_TRACE_WAVES_PER_SIMD_MODELS : SRT_TRACE_WAVES_PER_SIMD) void srt_trace_kernel(const TraceParams p) {
+__global__ __launch_bounds__(64, USE_BVH ? SRT_TRACE_WAVES_PER_SIMD_BVH : HAS_MODELS ? SRT_TRACE_WAVES_PER_SIMD_MODELS : SRT_TRACE_WAVES_PER_SIMD) void srt_trace_kernel(const SRT_TRACE_PARAMS p) {
 	extern __shared__ float4 lds[]; // [2*n_shapes] winner records, [4*n_materials] materials, (sphere / plane scenes: group headers, shape blocks,) sky ring, hit queue
 	constexpr uint32_t SUB = USE_BVH ? SRT_SUB_BVH : HAS_MODELS ? SRT_SUB_MODELS : SRT_SUB_PLAIN;
 	const int width = p.rd.width;
@@ -1470,7 +1588,11 @@ __global__ __launch_bounds__(64, USE_BVH ? SRT_TRACE_WAVES_PER_SIMD_BVH : HAS_MO
 					}
 					const float smoothness = m0.x, metallic = m0.y, specular = m0.z, emission_strength = m0.w;
 					const float transmittance = m1.x, ior = m1.y;
+#if SRT_TEXTURED
+					const f3 mcolor = texture_albedo<HAS_MODELS, USE_BVH>(p, p.tx, best, best_tri, pos, material_index, mk(mc.x, mc.y, mc.z));
+#else
 					const f3 mcolor = mk(mc.x, mc.y, mc.z);
+#endif
 					color = color + (mask * mk(me.x, me.y, me.z)) * emission_strength; // render.cl:413
 					if ((shm & ~lastm) != 0ull) { // (wave-uniform) somebody bounces on: see `lastm` above
 						SRT_REGION(SHADE_BOUNCE);
@@ -1899,6 +2021,7 @@ __global__ __launch_bounds__(64, USE_BVH ? SRT_TRACE_WAVES_PER_SIMD_BVH : HAS_MO
 #endif
 }
 
+#if !SRT_TEXTURED
 // ---------------------------------------------------------------------------------
 // Ordered reduction: lane = pixel, serial over the batch's samples in sample order, so
 // the float sums are the reference's `color += trace(...)` sequence bit for bit no matter
@@ -1994,6 +2117,8 @@ __global__ __launch_bounds__(256) void srt_reduce_kernel(const ReduceParams p) {
 	}
 }
 
+#endif // !SRT_TEXTURED
+
 // ---------------------------------------------------------------------------------
 // Denoiser guide buffers (device_types.h FeatureParams; the filter is csrc/denoise.hip). One lane = one pixel, its first
 // feature_samples camera rays one after the other: the trace kernel's seed, jitter and camera matrix (CAMERA above), its
@@ -2037,7 +2162,7 @@ __device__ __forceinline__ f3 winner_normal(const TraceParams &p, int best, uint
 } // namespace
 
 template <bool HAS_MODELS, bool USE_BVH>
-__global__ __launch_bounds__(64) void srt_features_kernel(const FeatureParams fp) {
+__global__ __launch_bounds__(64) void srt_features_kernel(const SRT_FEATURE_PARAMS fp) {
 #define SRT_FEATURES_IDS 0
 #include "features_body.inc"
 #undef SRT_FEATURES_IDS
@@ -2045,12 +2170,13 @@ __global__ __launch_bounds__(64) void srt_features_kernel(const FeatureParams fp
 
 // the same, and the shape index per pixel for the temporal stage's object motion (temporal.hip)
 template <bool HAS_MODELS, bool USE_BVH>
-__global__ __launch_bounds__(64) void srt_features_ids_kernel(const FeatureParams fp, uint32_t *__restrict__ shape_ids) {
+__global__ __launch_bounds__(64) void srt_features_ids_kernel(const SRT_FEATURE_PARAMS fp, uint32_t *__restrict__ shape_ids) {
 #define SRT_FEATURES_IDS 1
 #include "features_body.inc"
 #undef SRT_FEATURES_IDS
 }
 
+#if !SRT_TEXTURED
 // ---------------------------------------------------------------------------------
 // Pre-pass: world-space triangles per model instance. blockIdx.y = shape.
 // ---------------------------------------------------------------------------------
@@ -2238,9 +2364,10 @@ int srt_trace_lds_floats(int has_models, int use_bvh) {
 #endif
 	return n;
 }
+#endif // !SRT_TEXTURED
 
 namespace {
-typedef void (*TraceKernel)(const TraceParams);
+typedef void (*TraceKernel)(const SRT_TRACE_PARAMS);
 TraceKernel pick_trace_kernel(bool models, bool use_bvh, bool use_lds, bool count_triangles) {
 	if (!models) return use_lds ? srt_trace_kernel<false, true, false, false> : srt_trace_kernel<false, false, false, false>;
 	if (use_bvh) {
@@ -2261,7 +2388,7 @@ size_t scene_lds_bytes(const TraceParams &p) {
 // Persistent waves (= one-wave workgroups) of this launch configuration that one CU holds at once, as the runtime
 // computes it from the kernel's registers and its dynamic LDS; the grid must not exceed CUs x this, or the surplus
 // waves would only start -- each with a first chunk of its own -- when others have drained the queue.
-int srt_trace_resident_waves_per_cu(const TraceParams &p, bool count_triangles) {
+int srt_trace_resident_waves_per_cu(const SRT_TRACE_PARAMS &p, bool count_triangles) {
 	const size_t scene_lds = scene_lds_bytes(p);
 	const size_t need = scene_lds + (size_t)srt_trace_lds_floats(p.num_models > 0, p.use_bvh) * sizeof(float);
 	int blocks = 0;
@@ -2273,7 +2400,7 @@ int srt_trace_resident_waves_per_cu(const TraceParams &p, bool count_triangles) 
 	return blocks;
 }
 
-void srt_launch_trace(TraceParams p, bool count_triangles, int num_waves, void *stream) {
+void srt_launch_trace(SRT_TRACE_PARAMS p, bool count_triangles, int num_waves, void *stream) {
 	if (p.total_items == 0 || num_waves <= 0) return;
 	dim3 grid((unsigned)num_waves), block(64);
 	const size_t scene_lds = scene_lds_bytes(p);
@@ -2283,6 +2410,7 @@ void srt_launch_trace(TraceParams p, bool count_triangles, int num_waves, void *
 	hipLaunchKernelGGL(pick_trace_kernel(p.num_models > 0, p.use_bvh != 0, scene_lds != 0, count_triangles), grid, block, need, (hipStream_t)stream, p);
 }
 
+#if !SRT_TEXTURED
 void srt_launch_reduce(const ReduceParams &p, void *stream) {
 	if (p.num_pixels == 0) return;
 	hipLaunchKernelGGL(srt_reduce_kernel<false>, dim3((p.num_pixels + 255) / 256), dim3(256), 0, (hipStream_t)stream, p);
@@ -2308,17 +2436,19 @@ void srt_launch_reduce_moments(const ReduceParams &p, void *stream) {
 	hipLaunchKernelGGL(srt_reduce_kernel<true>, dim3((p.num_pixels + 255) / 256), dim3(256), 0, (hipStream_t)stream, p);
 }
 
-void srt_launch_features(const FeatureParams &p, void *stream) {
+#endif // !SRT_TEXTURED
+
+void srt_launch_features(const SRT_FEATURE_PARAMS &p, void *stream) {
 	if (p.num_pixels == 0 || p.feature_samples == 0) return;
-	typedef void (*FeatureKernel)(const FeatureParams);
+	typedef void (*FeatureKernel)(const SRT_FEATURE_PARAMS);
 	const bool models = p.tp.num_models > 0, bvh = p.tp.use_bvh != 0;
 	const FeatureKernel k = !models ? srt_features_kernel<false, false> : bvh ? srt_features_kernel<true, true> : srt_features_kernel<true, false>;
 	hipLaunchKernelGGL(k, dim3((p.num_pixels + 63u) / 64u), dim3(64), 0, (hipStream_t)stream, p);
 }
 
-void srt_launch_features_ids(const FeatureParams &p, uint32_t *shape_ids, void *stream) {
+void srt_launch_features_ids(const SRT_FEATURE_PARAMS &p, uint32_t *shape_ids, void *stream) {
 	if (p.num_pixels == 0 || p.feature_samples == 0) return;
-	typedef void (*FeatureKernel)(const FeatureParams, uint32_t *);
+	typedef void (*FeatureKernel)(const SRT_FEATURE_PARAMS, uint32_t *);
 	const bool models = p.tp.num_models > 0, bvh = p.tp.use_bvh != 0;
 	const FeatureKernel k = !models ? srt_features_ids_kernel<false, false> : bvh ? srt_features_ids_kernel<true, true> : srt_features_ids_kernel<true, false>;
 	hipLaunchKernelGGL(k, dim3((p.num_pixels + 63u) / 64u), dim3(64), 0, (hipStream_t)stream, p, shape_ids);

@@ -671,6 +671,7 @@ void srt_destroy(srt_tracer *t) {
 	t->om_ids[0].release();
 	t->om_ids[1].release();
 	t->om_table_dev.release();
+	srt_texture_release(t);
 	if (t->ev_t0) (void)hipEventDestroy(t->ev_t0);
 	if (t->ev_t1) (void)hipEventDestroy(t->ev_t1);
 	if (t->ev_r0) (void)hipEventDestroy(t->ev_r0);
@@ -1015,8 +1016,10 @@ static int upload_scene_begin(srt_tracer *t, const ScenePrep &sp, const srt_shap
 	const bool use_bvh = sp.use_bvh;
 	const uint64_t total_wtris = sp.total_wtris, max_tris = sp.max_tris;
 	const int num_models = sp.num_models;
+	if (const int trc = srt_texture_check_scene(t, n_triangles)) return trc; // (before anything of the current scene is replaced)
 	SRT_HIP(t, hipSetDevice(t->device));
 	SRT_HIP(t, hipStreamSynchronize(t->stream)); // previous launches may still read the old scene
+	srt_texture_scene(t, shapes, n_shapes, n_triangles);
 	SRT_HIP(t, t->shapes.reserve(n_shapes));
 	SRT_HIP(t, t->runs.reserve(groups.size()));
 	SRT_HIP(t, t->run_data.reserve(data.size()));
@@ -1087,7 +1090,7 @@ static int upload_scene_end(srt_tracer *t, const ScenePrep &sp, size_t n_shapes,
 	t->num_runs = (int)sp.groups.size();
 	t->num_materials = n_materials;
 	t->scene_set = true;
-	return SRT_OK;
+	return srt_texture_sync(t); // albedo textures: bindings and UVs are checked against the new scene
 }
 
 
@@ -1152,6 +1155,9 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 		return fail(t, SRT_ERR_INVALID, "srt_trace: options width/height differ from the handle's (no resize, tracer.hpp:61-66)");
 	if (t->sky_w <= 0) return fail(t, SRT_ERR_STATE, "srt_trace: no skybox set (srt_set_skybox)");
 	SRT_HIP(t, hipSetDevice(t->device));
+	if (const int trc = srt_texture_sync(t)) return trc;
+	const bool textured = t->tex_active && !options->show_normals; // (show_normals ignores textures: the untextured kernels)
+	t->last_trace_textured = textured;
 	TraceParams p;
 	memset(&p, 0, sizeof p);
 	p.rd = *options;
@@ -1251,7 +1257,14 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 	if (n_batches > 1) SRT_HIP(t, t->running.reserve(pixels * 4));
 	p.radiance = t->radiance.ptr;
 	p.queue = t->counters.ptr + SRT_CTR_QUEUE;
-	int per_cu = srt_trace_resident_waves_per_cu(p, t->count_tris);
+	auto with_textures = [&](const TraceParams &tp) { // the textured kernels' parameters: tp, then the texture tables
+		TexTraceParams x;
+		memset(&x, 0, sizeof x);
+		static_cast<TraceParams &>(x) = tp;
+		x.tx = srt_texture_params(t);
+		return x;
+	};
+	int per_cu = textured ? srt_trace_tex_resident_waves_per_cu(with_textures(p), t->count_tris) : srt_trace_resident_waves_per_cu(p, t->count_tris);
 	if (const char *env = dev_env("SRT_WAVES_PER_CU")) {
 		const int v = atoi(env);
 		if (v > 0 && v < per_cu) per_cu = v;
@@ -1431,7 +1444,8 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 		if (p.pool_blocks) SRT_HIP(t, hipMemsetAsync(p.scan_queue, 0, (size_t)SRT_POOL_CTL_WORDS * sizeof(uint32_t), ts));
 		if (timed) SRT_HIP(t, hipEventRecord(t->ev_k[2 * b], ts));
 		t->last_grid = num_waves;
-		srt_launch_trace(p, t->count_tris, num_waves, ts);
+		if (textured) srt_launch_trace_tex(with_textures(p), t->count_tris, num_waves, ts);
+		else srt_launch_trace(p, t->count_tris, num_waves, ts);
 		SRT_HIP(t, hipGetLastError());
 		if (timed) SRT_HIP(t, hipEventRecord(t->ev_k[2 * b + 1], ts));
 		if (overlap) {

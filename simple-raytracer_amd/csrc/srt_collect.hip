@@ -386,6 +386,24 @@ int srt_group_set_skybox(srt_group *g, const float *rgba, int width, int height)
 	return SRT_OK;
 }
 
+int srt_group_set_textures(srt_group *g, const srt_texture_desc *descs, size_t n) {
+	if (!g) return SRT_ERR_INVALID;
+	SRT_EACH(g, srt_set_textures(t_, descs, n));
+	return SRT_OK;
+}
+
+int srt_group_set_material_textures(srt_group *g, const srt_material_texture *bindings, size_t n_materials) {
+	if (!g) return SRT_ERR_INVALID;
+	SRT_EACH(g, srt_set_material_textures(t_, bindings, n_materials));
+	return SRT_OK;
+}
+
+int srt_group_set_triangle_uvs(srt_group *g, const float *uv, size_t n_triangles) {
+	if (!g) return SRT_ERR_INVALID;
+	SRT_EACH(g, srt_set_triangle_uvs(t_, uv, n_triangles));
+	return SRT_OK;
+}
+
 int srt_group_set_acceleration(srt_group *g, int mode) {
 	if (!g) return SRT_ERR_INVALID;
 	SRT_EACH(g, srt_set_acceleration(t_, mode));

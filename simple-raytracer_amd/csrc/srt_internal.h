@@ -120,6 +120,21 @@ struct srt_tracer {
 	std::vector<uint8_t> om_hist_scene; // scene_bytes of the history frame
 	std::vector<uint32_t> om_table;     // SRT_MOTION_WORDS per shape of the current scene: the next filter's current -> history maps
 	DevBuf<uint32_t> om_table_dev;
+	// albedo textures (srt_texture.hip; include/srt_abi.h). What the three setters were given lives on the host; the device
+	// tables are (re)made by srt_texture_sync when a setter or srt_update_scene has run since (tex_dirty)
+	std::vector<TexDesc> tex_images;                // srt_set_textures: the images inside tex_texels
+	std::vector<srt_material_texture> tex_bindings; // srt_set_material_textures, as given
+	std::vector<float> tex_uv_host;                 // srt_set_triangle_uvs
+	bool tex_has_uvs = false;
+	std::vector<PlaneFrame> tex_frames_host; // per shape of the current scene (srt_update_scene)
+	size_t tex_scene_triangles = 0;          // of the current scene
+	DevBuf<float> tex_texels, tex_uvs;
+	DevBuf<TexDesc> tex_descs;
+	DevBuf<srt_material_texture> tex_bind_dev; // one per material of the scene
+	DevBuf<PlaneFrame> tex_frames;
+	bool tex_dirty = false;
+	bool tex_active = false;         // a material of the current scene has a texture bound: dispatches launch the textured kernels
+	bool last_trace_textured = false; // srt_last_trace_textured
 	hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;
 	bool have_trace_ev = false, have_resolve_ev = false, have_kernel_ev = false;
 	std::string err;
@@ -140,6 +155,14 @@ static inline size_t full_pixels(const srt_tracer *t) { return (size_t)t->width 
 
 
 void srt_collect_release(srt_tracer *t);
+/* srt_texture.hip: the setters' data checked against a scene that is about to be uploaded; the plane frames and triangle count of the scene being uploaded (srt_update_scene, every group member);
+ * checking the setters' data against the current scene and bringing the device tables up to date (after srt_update_scene
+ * and before every dispatch; sets tex_active); the tables as the textured kernels take them; freeing them */
+int srt_texture_check_scene(srt_tracer *t, size_t n_triangles); /* before a scene with this many triangles replaces the current one */
+void srt_texture_scene(srt_tracer *t, const srt_shape *shapes, size_t n_shapes, size_t n_triangles);
+int srt_texture_sync(srt_tracer *t);
+TexParams srt_texture_params(const srt_tracer *t);
+void srt_texture_release(srt_tracer *t);
 /* denoise.hip: zero the denoiser's accumulations and counts (enqueued); after a dispatch's reductions, the feature pass of
  * that dispatch (p: its TraceParams) and the counts; the filter over the canvas into argb (device, width*height*4 bytes) */
 int srt_denoise_clear(srt_tracer *t);

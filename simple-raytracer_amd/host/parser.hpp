@@ -71,14 +71,19 @@ inline std::optional<ModelPair> load_stl_model(const fs::path &filename, std::ve
 	return ModelPair{first, loaded};
 }
 
-inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vector<Triangle> &triangles) {
+/// `uvs` (optional): receives 6 floats per loaded triangle (u, v of its three corners, from the corners' `vt`; a corner
+/// without one, or with an index that does not exist, gets (0, 0)), appended so that the vector stays parallel to
+/// `triangles` when it was before: what Tracer::set_triangle_uvs takes.
+inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vector<Triangle> &triangles, std::vector<float> *uvs = nullptr) {
 	std::ifstream file(filename, std::ios::in);
 	if (file.fail()) return std::nullopt;
 
 	struct Corner {
 		long v = 0, n = 0; // 1-based / negative as written; n == 0: no normal given
+		long t = 0;        // the same for the texture coordinate
 	};
 	std::vector<glm::vec3> positions, normals;
+	std::vector<float> texcoords; // u, v per `vt`
 	std::vector<Corner> corners; // 3 per face
 
 	std::string line;
@@ -94,6 +99,11 @@ inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vec
 			float x = 0, y = 0, z = 0;
 			in >> x >> y >> z;
 			normals.push_back(glm::normalize(glm::vec3(x, y, z)));
+		} else if (tag == "vt") {
+			float u = 0, v = 0;
+			in >> u >> v;
+			texcoords.push_back(u);
+			texcoords.push_back(v);
 		} else if (tag == "f") {
 			std::string tok;
 			int got = 0;
@@ -103,21 +113,24 @@ inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vec
 				long v = 0, vt = 0, vn = 0;
 				if (std::sscanf(tok.c_str(), "%ld/%ld/%ld", &v, &vt, &vn) == 3) {
 				} else if (std::sscanf(tok.c_str(), "%ld//%ld", &v, &vn) == 2) {
+					vt = 0;
 				} else if (std::sscanf(tok.c_str(), "%ld/%ld", &v, &vt) == 2) {
 					vn = 0;
 				} else if (std::sscanf(tok.c_str(), "%ld", &v) == 1) {
 					vn = 0;
+					vt = 0;
 				} else {
 					break;
 				}
 				c[got].v = v;
 				c[got].n = vn;
+				c[got].t = vt;
 				got++;
 			}
 			if (got == 3)
 				for (auto &k : c) corners.push_back(k);
 		}
-		// '#', 's', 'o', 'g', 'vt', 'usemtl', ... are ignored
+		// '#', 's', 'o', 'g', 'usemtl', ... are ignored
 	}
 
 	auto resolve = [](long index, size_t len) -> long { // -> 0-based, or -1 when invalid
@@ -127,6 +140,7 @@ inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vec
 	};
 
 	const unsigned first = (unsigned)triangles.size();
+	const size_t first_uv = uvs ? uvs->size() : 0;
 	for (size_t f = 0; f + 2 < corners.size(); f += 3) {
 		Triangle t;
 		bool have_normals = true;
@@ -134,6 +148,7 @@ inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vec
 			long vi = resolve(corners[f + i].v, positions.size());
 			if (vi < 0) {
 				triangles.resize(first);
+				if (uvs) uvs->resize(first_uv);
 				return std::nullopt;
 			}
 			t.vertices[i].pos = positions[(size_t)vi];
@@ -143,6 +158,7 @@ inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vec
 				long ni = resolve(corners[f + i].n, normals.size());
 				if (ni < 0) {
 					triangles.resize(first);
+					if (uvs) uvs->resize(first_uv);
 					return std::nullopt;
 				}
 				t.vertices[i].normal = normals[(size_t)ni];
@@ -155,6 +171,12 @@ inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vec
 			for (auto &v : t.vertices) v.normal = n;
 		}
 		triangles.push_back(t);
+		if (uvs)
+			for (int i = 0; i < 3; i++) {
+				const long ti = corners[f + i].t == 0 ? -1 : resolve(corners[f + i].t, texcoords.size() / 2);
+				uvs->push_back(ti < 0 ? 0.0f : texcoords[2 * (size_t)ti]);
+				uvs->push_back(ti < 0 ? 0.0f : texcoords[2 * (size_t)ti + 1]);
+			}
 	}
 	return ModelPair{first, (unsigned)(triangles.size() - first)};
 }

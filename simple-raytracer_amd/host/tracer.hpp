@@ -129,6 +129,29 @@ class Tracer {
 	}
 
 	// -- extras beyond the reference's interface --
+	/// Albedo textures (include/srt_abi.h "albedo textures"; the reference's "texture support" plan). A texture is
+	/// width * height RGBA32F texels, row 0 = bottom (host/skybox.hpp prepares 8-bit images); `bindings` holds one
+	/// MaterialTexture per material, in the order of MaterialHelper::materials; `uvs` 6 floats per triangle as
+	/// load_obj_model hands them out. None of the three clears the canvas.
+	struct Texture {
+		std::vector<float> rgba;
+		int width = 0, height = 0;
+	};
+	using MaterialTexture = srt_material_texture; // {texture (-1: none), filter (SRT_FILTER_*), scale_u, scale_v}
+	void set_textures(const std::vector<Texture> &textures) {
+		std::vector<srt_texture_desc> d(textures.size());
+		for (size_t i = 0; i < textures.size(); i++) d[i] = srt_texture_desc{textures[i].rgba.data(), textures[i].width, textures[i].height};
+		check(group ? srt_group_set_textures(group, d.data(), d.size()) : srt_set_textures(handle, d.data(), d.size()));
+	}
+	void set_material_textures(const std::vector<MaterialTexture> &bindings) {
+		check(group ? srt_group_set_material_textures(group, bindings.data(), bindings.size())
+		            : srt_set_material_textures(handle, bindings.data(), bindings.size()));
+	}
+	void set_triangle_uvs(const std::vector<float> &uvs) {
+		const float *p = uvs.empty() ? nullptr : uvs.data();
+		check(group ? srt_group_set_triangle_uvs(group, p, uvs.size() / 6) : srt_set_triangle_uvs(handle, p, uvs.size() / 6));
+	}
+
 	/// SRT_ACCEL_BVH: models get a bounding-volume hierarchy at the next update_scene (the
 	/// reference's README.md:41 "future plan"); SRT_ACCEL_NONE (default) keeps the array-order scan
 	void set_acceleration(int mode) { check(group ? srt_group_set_acceleration(group, mode) : srt_set_acceleration(handle, mode)); }

@@ -60,6 +60,10 @@ SCENE_DATA = np.dtype(
     }
 )
 
+# srt_material_texture (albedo textures): texture = -1 for none, filter 0 LINEAR / 1 NEAREST
+MATERIAL_TEXTURE = np.dtype({"names": ["texture", "filter", "scale_u", "scale_v"], "formats": [np.int32, np.int32, np.float32, np.float32],
+                             "offsets": [0, 4, 8, 12], "itemsize": 16})
+
 SHAPE_SPHERE, SHAPE_PLANE, SHAPE_MODEL = 0, 1, 2
 
 assert MATERIAL.itemsize == 64 and TRIANGLE.itemsize == 96 and SHAPE.itemsize == 128
@@ -114,6 +118,12 @@ def material(color=(1, 1, 1), smoothness=0.0, metallic=0.0, specular=0.0, transm
     m["refraction_index"] = refraction_index
     m["emission"] = emission
     m["emission_strength"] = emission_strength
+    return m
+
+
+def material_texture(texture=-1, filter=0, scale_u=1.0, scale_v=1.0):
+    m = np.zeros((), MATERIAL_TEXTURE)
+    m["texture"], m["filter"], m["scale_u"], m["scale_v"] = texture, filter, scale_u, scale_v
     return m
 
 

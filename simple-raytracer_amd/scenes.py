@@ -262,3 +262,57 @@ def write_obj(path, tris):
         for i in range(len(tris)):
             a = 3 * i + 1
             f.write("f %d//%d %d//%d %d//%d\n" % (a, a, a + 1, a + 1, a + 2, a + 2))
+
+
+# ---- albedo textures: procedural images (RGBA32F, row 0 = bottom) and textured scenes ----
+def checker_texture(w=8, h=8, a=(0.9, 0.9, 0.9), b=(0.1, 0.2, 0.6)):
+    img = np.ones((h, w, 4), np.float32)
+    yy, xx = np.mgrid[0:h, 0:w]
+    img[..., :3] = np.where(((xx + yy) & 1)[..., None] == 0, np.asarray(a, np.float32), np.asarray(b, np.float32))
+    return img
+
+
+def gradient_texture(w=16, h=8):
+    img = np.ones((h, w, 4), np.float32)
+    yy, xx = np.mgrid[0:h, 0:w]
+    img[..., 0] = (xx + 1) / np.float32(w + 1)
+    img[..., 1] = (yy + 1) / np.float32(h + 1)
+    img[..., 2] = np.float32(0.25)
+    return img
+
+
+def noise_texture(w=1024, h=1024, seed=1):
+    img = np.ones((h, w, 4), np.float32)
+    img[..., :3] = np.random.default_rng(seed).random((h, w, 3), np.float32)
+    return img
+
+
+def textured_sphere_scene():
+    """The sphere scene with a checker floor (two squares per world unit), a gradient back wall and a striped sphere.
+    Returns (shapes, triangles, materials, textures, bindings)."""
+    shapes, tris, mats = sphere_scene()
+    textures = [checker_texture(2, 2), gradient_texture(), checker_texture(16, 1, (0.9, 0.6, 0.2), (0.3, 0.1, 0.1))]
+    bindings = np.zeros(len(mats), R.MATERIAL_TEXTURE)
+    bindings[:] = R.material_texture()
+    bindings[0] = R.material_texture(0, 1, 1.0, 1.0)    # floor: NEAREST checker
+    bindings[2] = R.material_texture(1, 0, 0.125, 0.125)  # back wall: LINEAR gradient, one repeat per 8 units
+    bindings[3] = R.material_texture(2, 1, 1.0, 1.0)    # the big sphere: 16 stripes around
+    return shapes, tris, mats, textures, bindings
+
+
+def planar_triangle_uvs(tris, scale=1.0):
+    """(n, 3, 2) UVs from the model-space positions: (x + y, z + y) * scale per vertex."""
+    pos = np.asarray(tris["v"]["pos"], np.float32)
+    uv = np.stack([pos[..., 0] + pos[..., 1], pos[..., 2] + pos[..., 1]], axis=-1) * np.float32(scale)
+    return uv.astype(np.float32)
+
+
+def textured_mesh_scene(n_instances=2, lon=22, bands=23):
+    """mesh_scene with every material on a texture and UVs for every triangle.
+    Returns (shapes, triangles, materials, textures, bindings, uvs)."""
+    shapes, tris, mats = mesh_scene(n_instances, lon, bands)
+    textures = [checker_texture(4, 4), gradient_texture()]
+    bindings = np.zeros(len(mats), R.MATERIAL_TEXTURE)
+    for i in range(len(mats)):
+        bindings[i] = R.material_texture(i % 2, i % 2, 1.0, 1.0)
+    return shapes, tris, mats, textures, bindings, planar_triangle_uvs(tris, 2.0)

@@ -16,6 +16,8 @@
 // --skybox sky.ppm: an 8-bit binary PPM (P6) as the sky, prepared the way the reference prepares assets/skybox.png
 //                   (host/skybox.hpp: four channels, rows flipped, pow(byte / 255, 2.2)); default: the synthetic sky.
 //
+// --texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]: an 8-bit binary PPM as the albedo texture of
+//                   material N, its texels prepared like the sky's (host/skybox.hpp); OBJ models hand their `vt` out as UVs
 // --dump prefix writes prefix.{shapes,tris,mats,rd,sd,canvas,argb}.bin (raw records).
 // --parse-only skips everything that needs a GPU (loaders + scene construction only).
 #include <chrono>
@@ -100,7 +102,10 @@ static void dump(const std::string &path, const T *data, size_t count) {
 }
 
 int main(int argc, char **argv) {
-	std::string scene = "spheres", out, dump_prefix, skybox_path;
+	std::string scene = "spheres", out, dump_prefix, skybox_path, texture_path;
+	int texture_material = -1;
+	float texture_scale = 1.0f;
+	bool texture_nearest = false;
 	std::vector<std::string> objs, stls;
 	int width = 256, height = 256, spp = 16, bounces = 10, frames = 1;
 	unsigned time_seed = 12345;
@@ -135,6 +140,10 @@ int main(int argc, char **argv) {
 		else if (a == "--gpus") gpus = std::atoi(next());
 		else if (a == "--pipelined") pipelined = true;
 		else if (a == "--skybox") skybox_path = next();
+		else if (a == "--texture") texture_path = next();
+		else if (a == "--texture-material") texture_material = std::atoi(next());
+		else if (a == "--texture-scale") texture_scale = std::strtof(next(), nullptr);
+		else if (a == "--texture-nearest") texture_nearest = true;
 		else if (a == "--denoise") denoise = std::atoi(next());
 		else if (a == "--temporal") temporal = true;
 		else if (a == "--move") move = std::strtof(next(), nullptr), moving = true;
@@ -142,7 +151,7 @@ int main(int argc, char **argv) {
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--temporal] [--move DX] [--move-shape I DX]\n";
+			             "[--denoise K] [--temporal] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]]\n";
 			return 2;
 		}
 	}
@@ -198,8 +207,10 @@ int main(int argc, char **argv) {
 		slot++;
 		std::cout << path << ": " << pair->second << " triangles at " << pair->first << "\n";
 	};
-	for (auto &p : objs) add_model(load_obj_model(p, triangles), p);
+	std::vector<float> uvs(triangles.size() * 6, 0.0f); // parallel to `triangles`: the box's and STL triangles have none
+	for (auto &p : objs) add_model(load_obj_model(p, triangles, &uvs), p);
 	for (auto &p : stls) add_model(load_stl_model(p, triangles), p);
+	uvs.resize(triangles.size() * 6, 0.0f);
 
 	const glm::mat4 camera_to_world = eye_matrix(glm::vec3(0.0f, 0.5f, 5.0f), 0.0f, 0.0f);
 
@@ -246,6 +257,29 @@ int main(int argc, char **argv) {
 		sky = synthetic_sky(sky_w, sky_h);
 	}
 	tracer.set_skybox(sky.data(), sky_w, sky_h);
+	if (!texture_path.empty()) {
+		std::vector<uint8_t> rgb;
+		Tracer::Texture tex;
+		if (!load_ppm(texture_path, rgb, tex.width, tex.height)) {
+			std::cerr << "cannot read " << texture_path << " (binary PPM, P6, maxval 255)\n";
+			return 3;
+		}
+		if (texture_material < 0 || (size_t)texture_material >= materials.list.size()) {
+			std::cerr << "--texture needs --texture-material N with N below " << materials.list.size() << "\n";
+			return 2;
+		}
+		tex.rgba.resize((size_t)tex.width * tex.height * 4);
+		srt_skybox_from_rgb8(rgb.data(), tex.width, tex.height, 3, tex.rgba.data());
+		std::vector<Tracer::MaterialTexture> bindings(materials.list.size(), Tracer::MaterialTexture{-1, SRT_FILTER_LINEAR, 1.0f, 1.0f});
+		bindings[(size_t)texture_material] = Tracer::MaterialTexture{0, texture_nearest ? SRT_FILTER_NEAREST : SRT_FILTER_LINEAR, texture_scale, texture_scale};
+		tracer.set_textures({tex});
+		tracer.set_material_textures(bindings);
+		if (!objs.empty()) tracer.set_triangle_uvs(uvs);
+		if (!dump_prefix.empty()) {
+			dump(dump_prefix + ".texture.bin", tex.rgba.data(), tex.rgba.size());
+			dump(dump_prefix + ".uvs.bin", uvs.data(), uvs.size());
+		}
+	}
 	if (!dump_prefix.empty()) dump(dump_prefix + ".sky.bin", sky.data(), sky.size());
 
 	std::vector<uint8_t> pixels((size_t)width * height * 4);

@@ -36,12 +36,62 @@ ABI_SYMBOLS = [
     "srt_denoise_defaults", "srt_set_denoise", "srt_resolve_denoised", "srt_read_denoised", "srt_read_denoise_inputs",
     "srt_temporal_defaults", "srt_set_denoise_temporal", "srt_reset_denoise_history", "srt_read_denoise_history",
     "srt_set_denoise_object_motion", "srt_read_denoise_shape_ids", "srt_read_denoise_motion", "srt_motion_table_host",
+    "srt_set_textures", "srt_set_material_textures", "srt_set_triangle_uvs", "srt_last_trace_textured", "srt_plane_frame_host",
+    "srt_texture_check_host", "srt_group_set_textures", "srt_group_set_material_textures", "srt_group_set_triangle_uvs",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
 MOTION_STATIC, MOTION_MOVED, MOTION_NO_HISTORY = 0, 1, 2
 MOTION_WORDS = 22
 NO_SHAPE = 0xFFFFFFFF
+FILTER_LINEAR, FILTER_NEAREST = 0, 1
+MAX_TEXTURES = 64
+
+
+class TextureDesc(C.Structure):
+    """srt_texture_desc"""
+    _fields_ = [("rgba", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+def _texture_descs(images):
+    """images: (H, W, 4) float32 arrays, row 0 = bottom -> (the contiguous arrays to keep alive, a TextureDesc array)."""
+    keep = [np.ascontiguousarray(im, np.float32) for im in images]
+    for im in keep:
+        assert im.ndim == 3 and im.shape[2] == 4
+    descs = (TextureDesc * max(len(keep), 1))()
+    for k, im in enumerate(keep):
+        descs[k].rgba, descs[k].width, descs[k].height = im.ctypes.data, im.shape[1], im.shape[0]
+    return keep, descs
+
+
+def _uv_array(uv):
+    if uv is None:
+        return None, 0
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 3, 2)
+    return uv, len(uv)
+
+
+def plane_frame_host(normal):
+    """srt_plane_frame_host (host only): (T, B) float32 (3,) each, or None for a plane without a frame."""
+    lib = load_library()
+    n = np.ascontiguousarray(normal, np.float32).reshape(3)
+    T, B = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    return (T, B) if lib.srt_plane_frame_host(_ptr(n), _ptr(T), _ptr(B)) else None
+
+
+def texture_check_host(n_textures, bindings=None, uv_triangles=None, scene_triangles=0, images=None):
+    """srt_texture_check_host (host only): the setters' checks; returns the status (0 = SRT_OK, 1 = SRT_ERR_INVALID).
+    images: (rgba pointer or None, width, height) triples, checked as srt_set_textures checks its descriptors."""
+    lib = load_library()
+    descs, keep = None, None
+    if images is not None:
+        keep = np.zeros(4, np.float32)
+        descs = (TextureDesc * max(len(images), 1))()
+        for k, (has_texels, w, h) in enumerate(images):
+            descs[k].rgba, descs[k].width, descs[k].height = (keep.ctypes.data if has_texels else None), w, h
+    b = R.as_records(bindings if bindings is not None else [], R.MATERIAL_TEXTURE)
+    return lib.srt_texture_check_host(descs, n_textures, _ptr(b) if len(b) else None, len(b),
+                                      -1 if uv_triangles is None else int(uv_triangles), scene_triangles)
 
 
 def _motion_rows(table):
@@ -294,6 +344,16 @@ def _bind(lib):
         lib.srt_read_denoise_shape_ids.argtypes = [vp, vp, vp]
         lib.srt_read_denoise_motion.argtypes = [vp, vp, sz, C.POINTER(sz), C.POINTER(C.c_int)]
         lib.srt_motion_table_host.argtypes = [vp, sz, vp, sz, vp, sz, vp] * 2 + [vp, C.POINTER(C.c_int)]
+    if hasattr(lib, "srt_set_textures"):
+        lib.srt_set_textures.argtypes = [vp, vp, sz]
+        lib.srt_set_material_textures.argtypes = [vp, vp, sz]
+        lib.srt_set_triangle_uvs.argtypes = [vp, vp, sz]
+        lib.srt_last_trace_textured.argtypes = [vp, C.POINTER(C.c_int)]
+        lib.srt_plane_frame_host.argtypes = [vp, vp, vp]
+        lib.srt_texture_check_host.argtypes = [vp, sz, vp, sz, C.c_longlong, sz]
+        lib.srt_group_set_textures.argtypes = [vp, vp, sz]
+        lib.srt_group_set_material_textures.argtypes = [vp, vp, sz]
+        lib.srt_group_set_triangle_uvs.argtypes = [vp, vp, sz]
     return lib
 
 
@@ -338,6 +398,27 @@ class Tracer:
         rgba = np.ascontiguousarray(rgba, np.float32)
         assert rgba.ndim == 3 and rgba.shape[2] == 4
         self._check(self.lib.srt_set_skybox(self._h, _ptr(rgba), rgba.shape[1], rgba.shape[0]))
+
+    # -- albedo textures (include/srt_abi.h) --
+    def set_textures(self, images):
+        """images: list of (H, W, 4) float32, row 0 = bottom; [] removes them all."""
+        keep, descs = _texture_descs(images)
+        self._check(self.lib.srt_set_textures(self._h, descs if keep else None, len(keep)))
+
+    def set_material_textures(self, bindings):
+        """bindings: records.MATERIAL_TEXTURE records (records.material_texture), one per material; None / [] unbinds all."""
+        b = R.as_records(bindings if bindings is not None else [], R.MATERIAL_TEXTURE)
+        self._check(self.lib.srt_set_material_textures(self._h, _ptr(b) if len(b) else None, len(b)))
+
+    def set_triangle_uvs(self, uv):
+        """uv: (n_triangles, 3, 2) float32 parallel to the triangle array, or None."""
+        uv, n = _uv_array(uv)
+        self._check(self.lib.srt_set_triangle_uvs(self._h, _ptr(uv) if uv is not None else None, n))
+
+    def last_trace_textured(self):
+        out = C.c_int(0)
+        self._check(self.lib.srt_last_trace_textured(self._h, C.byref(out)))
+        return bool(out.value)
 
     def update_scene(self, shapes, triangles, materials):
         shapes = R.as_records(shapes, R.SHAPE)
@@ -644,6 +725,18 @@ class TracerGroup:
 
     def set_acceleration(self, mode):
         self._check(self.lib.srt_group_set_acceleration(self._g, int(mode)))
+
+    def set_textures(self, images):
+        keep, descs = _texture_descs(images)
+        self._check(self.lib.srt_group_set_textures(self._g, descs if keep else None, len(keep)))
+
+    def set_material_textures(self, bindings):
+        b = R.as_records(bindings if bindings is not None else [], R.MATERIAL_TEXTURE)
+        self._check(self.lib.srt_group_set_material_textures(self._g, _ptr(b) if len(b) else None, len(b)))
+
+    def set_triangle_uvs(self, uv):
+        uv, n = _uv_array(uv)
+        self._check(self.lib.srt_group_set_triangle_uvs(self._g, _ptr(uv) if uv is not None else None, n))
 
     def update_scene(self, shapes, triangles, materials):
         shapes = R.as_records(shapes, R.SHAPE)

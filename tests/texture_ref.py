@@ -1,0 +1,137 @@
+"""numpy restatement of the albedo-texture contract (include/srt_abi.h "albedo textures"; csrc/kernels.hip sample_texture,
+texture_albedo): the UV per kind of shape and both filters, in float32, unfused, in the kernel's order. dm_atan2pif and
+dm_bilinear come from a host build of csrc/detmath.h (tests/csrc/texture_math.c). A plain module, not a test module."""
+import ctypes as C
+import subprocess
+import tempfile
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+F = np.float32
+LINEAR, NEAREST = 0, 1
+_lib = None
+_tmp = None
+
+
+def lib():
+    global _lib, _tmp
+    if _lib is None:
+        _tmp = tempfile.TemporaryDirectory()
+        so = Path(_tmp.name) / "libtexture_math.so"
+        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", f"-I{ROOT}/simple-raytracer_amd/csrc",
+                        str(ROOT / "tests/csrc/texture_math.c"), "-o", str(so), "-lm"], check=True)
+        _lib = C.CDLL(str(so))
+        _lib.tex_atan2pif.restype = None
+        _lib.tex_bilinear.restype = None
+    return _lib
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def atan2pif(y, x):
+    y, x = np.ascontiguousarray(y, F).reshape(-1), np.ascontiguousarray(x, F).reshape(-1)
+    out = np.zeros(len(y), F)
+    lib().tex_atan2pif(_p(y), _p(x), _p(out), C.c_size_t(len(y)))
+    return out
+
+
+def bilinear(w, t):
+    """w, t: (n, 4) float32 -> (n,)"""
+    w, t = np.ascontiguousarray(w, F), np.ascontiguousarray(t, F)
+    out = np.zeros(len(w), F)
+    lib().tex_bilinear(_p(w), _p(t), _p(out), C.c_size_t(len(w)))
+    return out
+
+
+# ---- UV per kind of shape (float32, every product and sum rounded on its own) ----
+def sphere_uv(X, centre, radius):
+    """n = (X - centre) / radius; u = dm_atan2pif(n.z, n.x) * 0.5 + 0.5; v = n.y * 0.5 + 0.5"""
+    X = np.asarray(X, F).reshape(-1, 3)
+    n = (X - np.asarray(centre, F)) / F(radius)
+    u = atan2pif(n[:, 2], n[:, 0]) * F(0.5) + F(0.5)
+    v = n[:, 1] * F(0.5) + F(0.5)
+    return u.astype(F), v.astype(F)
+
+
+def plane_frame(normal):
+    """The host's frame in float64, rounded to float32 at the end: a = the axis of the smallest |n| (ties: x, y, z),
+    T = normalise(a x n), B = n x T. None for a zero or non-finite normal."""
+    n = np.asarray(normal, F).astype(np.float64)
+    if not np.all(np.isfinite(n)) or not n.any():
+        return None
+    a = np.zeros(3)
+    a[int(np.argmin(np.abs(n)))] = 1.0  # argmin: the first of equal minima
+    t = np.cross(a, n)
+    t = t / np.sqrt((t * t).sum())
+    return t.astype(F), np.cross(n, t).astype(F)
+
+
+def plane_uv(X, position, T, B):
+    """d = X - position; u = (d.x*T.x + d.y*T.y) + d.z*T.z; v the same with B"""
+    d = np.asarray(X, F).reshape(-1, 3) - np.asarray(position, F)
+    T, B = np.asarray(T, F), np.asarray(B, F)
+    u = (d[:, 0] * T[0] + d[:, 1] * T[1]) + d[:, 2] * T[2]
+    v = (d[:, 0] * B[0] + d[:, 1] * B[1]) + d[:, 2] * B[2]
+    return u.astype(F), v.astype(F)
+
+
+def model_uv(w0, w1, w2, uv=None):
+    """uv = (uv0 * w2 + uv1 * w0) + uv2 * w1; without UVs (w0, w1). uv: (n, 3, 2) per hit."""
+    w0, w1, w2 = (np.asarray(x, F).reshape(-1) for x in (w0, w1, w2))
+    if uv is None:
+        return w0, w1
+    uv = np.asarray(uv, F).reshape(-1, 3, 2)
+    u = (uv[:, 0, 0] * w2 + uv[:, 1, 0] * w0) + uv[:, 2, 0] * w1
+    v = (uv[:, 0, 1] * w2 + uv[:, 1, 1] * w0) + uv[:, 2, 1] * w1
+    return u.astype(F), v.astype(F)
+
+
+# ---- the sampler, addressing REPEAT ----
+def sample(image, filt, u, v, scale_u=1.0, scale_v=1.0):
+    """image (H, W, 4) float32, row 0 = bottom; u, v (n,) before the scale -> (n, 3) float32."""
+    image = np.asarray(image, F)
+    H, W = image.shape[:2]
+    with np.errstate(all="ignore"):
+        u = np.asarray(u, F).reshape(-1) * F(scale_u)
+        v = np.asarray(v, F).reshape(-1) * F(scale_v)
+        fu, fv = u * F(W), v * F(H)
+        if filt == LINEAR:
+            fu, fv = fu - F(0.5), fv - F(0.5)
+        ok = (np.abs(fu) < F(2.0 ** 30)) & (np.abs(fv) < F(2.0 ** 30))  # false for NaN and inf
+        fu, fv = np.where(ok, fu, F(0)), np.where(ok, fv, F(0))
+        x0f, y0f = np.floor(fu).astype(F), np.floor(fv).astype(F)
+        i0, j0 = np.mod(x0f.astype(np.int64), W), np.mod(y0f.astype(np.int64), H)  # numpy's mod of a positive modulus is never negative
+        if filt == NEAREST:
+            out = image[j0, i0, :3]
+        else:
+            a, b = (fu - x0f).astype(F), (fv - y0f).astype(F)
+            i1, j1 = np.mod(i0 + 1, W), np.mod(j0 + 1, H)
+            one = F(1)
+            w = np.stack([(one - a) * (one - b), a * (one - b), (one - a) * b, a * b], axis=1).astype(F)
+            out = np.zeros((len(u), 3), F)
+            for c in range(3):
+                t = np.stack([image[j0, i0, c], image[j0, i1, c], image[j1, i0, c], image[j1, i1, c]], axis=1)
+                out[:, c] = bilinear(w, t)
+        out = np.where(ok[:, None], out, image[0, 0, :3][None, :])
+    return out.astype(F)
+
+
+# ---- procedural textures (the tests' and scenes') ----
+def checker(w=8, h=8, a=(0.9, 0.9, 0.9), b=(0.1, 0.2, 0.6)):
+    img = np.ones((h, w, 4), F)
+    yy, xx = np.mgrid[0:h, 0:w]
+    img[..., :3] = np.where(((xx + yy) & 1)[..., None] == 0, np.asarray(a, F), np.asarray(b, F))
+    return img
+
+
+def gradient(w=16, h=8):
+    img = np.ones((h, w, 4), F)
+    yy, xx = np.mgrid[0:h, 0:w]
+    img[..., 0] = (xx + 1) / F(w + 1)
+    img[..., 1] = (yy + 1) / F(h + 1)
+    img[..., 2] = F(0.25)
+    return img.astype(F)
