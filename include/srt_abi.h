@@ -419,6 +419,10 @@ int srt_set_triangle_uvs(srt_tracer *t, const float *uv, size_t n_triangles);
 /* Which kernels the last srt_trace launched: *textured = 1 when the textured instantiations ran (some material of the
  * scene has a texture bound), else 0. */
 int srt_last_trace_textured(const srt_tracer *t, int *textured);
+/* Which instantiation of the trace kernel the last srt_trace launched: *scene_class = 0 for the general kernels, 1 and up
+ * for a kernel compiled for the scene's class (sphere / plane scenes of one block group). The class follows
+ * the scene and the options of the dispatch; results do not depend on it. */
+int srt_last_trace_class(const srt_tracer *t, int *scene_class);
 /* Host-only (no device). The frame of a plane with this normal: returns 1 and writes T, B (3 floats each), or 0 when the
  * plane has none (T, B zeroed). */
 int srt_plane_frame_host(const float normal[3], float T[3], float B[3]);

@@ -3,6 +3,7 @@
 #ifndef SRT_DEVICE_TYPES_H
 #define SRT_DEVICE_TYPES_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/srt_types.h"
@@ -115,6 +116,31 @@ enum { SRT_CTR_RAYS = 0, SRT_CTR_SKY, SRT_CTR_TRI, SRT_CTR_TRI_PASS_U, SRT_CTR_N
 #define SRT_MF_NO_SPECULAR 1 /* every material's specular threshold is 0: `specular > random_float` is false for every output of the generator */
 #define SRT_MF_PLAIN_COLORS 2 /* every material colour component is finite and not -0: mix(colour, 1, 0) = fma(1 - colour, 0, colour) is the colour itself, bit for bit */
 
+/* Scene classes of the sphere / plane trace kernel (kernels.hip "SCENE CLASSES"): X(number, header of the scene's one
+ * block group, NO_SPEC). A class is one more instantiation of the kernel, so the list is short: the layouts of the
+ * benchmark's sphere scene (two planes, one plane, four spheres; with and without a specular material) and the two
+ * largest scenes one group holds (twelve spheres; six planes). Every other scene is class 0, the general kernel. */
+#define SRT_BLK_CODE(type, count) ((uint32_t)((type) + 1) | ((uint32_t)(count) << 2)) /* one byte of BlockGroup.code */
+#define SRT_GROUP_CODE(b0, b1, b2) ((b0) | ((b1) << 8) | ((b2) << 16))
+#define SRT_GC_PPS SRT_GROUP_CODE(SRT_BLK_CODE(SRT_SHAPE_PLANE, 2), SRT_BLK_CODE(SRT_SHAPE_PLANE, 1), SRT_BLK_CODE(SRT_SHAPE_SPHERE, 4))
+#define SRT_GC_SSS SRT_GROUP_CODE(SRT_BLK_CODE(SRT_SHAPE_SPHERE, 4), SRT_BLK_CODE(SRT_SHAPE_SPHERE, 4), SRT_BLK_CODE(SRT_SHAPE_SPHERE, 4))
+#define SRT_GC_PPP SRT_GROUP_CODE(SRT_BLK_CODE(SRT_SHAPE_PLANE, 2), SRT_BLK_CODE(SRT_SHAPE_PLANE, 2), SRT_BLK_CODE(SRT_SHAPE_PLANE, 2))
+#define SRT_SCENE_CLASS_LIST(X) \
+	X(1, SRT_GC_PPS, true)      \
+	X(2, SRT_GC_PPS, false)     \
+	X(3, SRT_GC_SSS, true)      \
+	X(4, SRT_GC_PPP, true)
+#define SRT_SCENE_CLASS_GENERAL 0
+
+/* Winner records and materials (sphere / plane scenes: group headers and shape blocks too) are staged in LDS when they are
+ * small enough not to cost the trace kernel a resident wave; 0 = they stay in global memory. All record types are
+ * multiples of 16 B. */
+static inline size_t srt_scene_lds_bytes(size_t num_shapes, size_t num_materials, int num_models, size_t num_runs) {
+	size_t scene = num_shapes * sizeof(WinnerRec) + num_materials * sizeof(srt_material);
+	if (num_models == 0) scene += num_runs * (sizeof(BlockGroup) + 192);
+	return scene <= 4608 ? scene : 0;
+}
+
 struct TraceParams {
 	srt_render_data rd;
 	srt_scene_data sd;
@@ -124,7 +150,7 @@ struct TraceParams {
 	int32_t num_runs;
 	int32_t num_materials;
 	uint32_t lds_bytes; /* dynamic LDS given to the launch; 0 = winners/materials stay in global memory */
-	int32_t _pad0;
+	int32_t scene_class; /* SRT_SCENE_CLASS_LIST below: which trace kernel the launcher starts; 0 = the general one (never read on the device) */
 	const srt_shape *shapes;
 	const srt_triangle *triangles;
 	const srt_material *materials;
@@ -266,6 +292,7 @@ void srt_launch_features(const FeatureParams &p, void *stream);
 /* the same, also storing the shape index of feature sample 0 per pixel (0xffffffff: no hit or no material) into shape_ids */
 void srt_launch_features_ids(const FeatureParams &p, uint32_t *shape_ids, void *stream);
 int srt_trace_waves_per_simd(int has_models, int use_bvh);
+int srt_trace_has_scene_classes(); /* 1 when this build of kernels.hip holds the SRT_SCENE_CLASS_LIST instantiations */
 int srt_trace_resident_waves_per_cu(const TraceParams &p, bool count_triangles); /* from the runtime's occupancy calculator */
 int srt_scan_suspend_min(void); /* array scan: models of at least this many triangles sit alone in their block and are flagged big */
 int srt_sub_job_items(int has_models, int use_bvh); /* items per sub-job (the unit a wave's chunk is handed to its lanes in); chunks per atomic are multiples of it */

@@ -757,6 +757,7 @@ struct ScenePrep {
 	int num_models = 0;
 	bool use_bvh = false, unit_materials = false, all_materials_ok = true;
 	int material_flags = 0;
+	uint32_t one_group_code = 0; // srt_tracer::one_group_code
 	uint64_t bvh_info[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -939,6 +940,14 @@ static int prepare_scene(srt_tracer *t, ScenePrep &sp, const srt_shape *shapes, 
 		g.first[b % 3] = runs[b].first_shape;
 	}
 	data.resize(groups.size() * 48 + 16, 0.0f);
+	// a scene class (scene_class() below) is a scene of one group whose blocks hold shapes 0 .. n - 1 with none left out
+	sp.one_group_code = 0;
+	if (groups.size() == 1 && num_models == 0) {
+		uint32_t next = 0;
+		bool packed = true;
+		for (size_t b = 0; b < runs.size(); b++) packed = packed && runs[b].first_shape == next, next += runs[b].count;
+		if (packed && next == n_shapes) sp.one_group_code = groups[0].code;
+	}
 	const uint64_t build_us =
 	    (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - build_t0).count();
 
@@ -1087,6 +1096,7 @@ static int upload_scene_end(srt_tracer *t, const ScenePrep &sp, size_t n_shapes,
 	t->all_materials_ok = sp.all_materials_ok;
 	t->unit_materials = sp.unit_materials;
 	t->material_flags = sp.material_flags;
+	t->one_group_code = sp.one_group_code;
 	t->num_runs = (int)sp.groups.size();
 	t->num_materials = n_materials;
 	t->scene_set = true;
@@ -1144,6 +1154,31 @@ int srt_clear_canvas(srt_tracer *t) {
 	return clear_canvas_impl(t);
 }
 
+// THE scene-class predicate: which instantiation of the sphere / plane trace kernel a dispatch of `options` over the handle's
+// scene starts (device_types.h SRT_SCENE_CLASS_LIST; 0 = the general kernel). Host data only: what srt_update_scene found
+// of the scene, and the options of this dispatch. A class needs all of: no models, one block group over all shapes, the scene
+// records staged in LDS, every shape with a material, material probabilities as thresholds, bounces, no show_normals, no
+// textures, no triangle counting, and a build that holds the classes (kernels.hip SRT_SCENE_CLASSES: sky ring of 64, no instruments).
+static int scene_class(const srt_tracer *t, const srt_render_data *options, bool textured) {
+	if (!srt_trace_has_scene_classes()) return SRT_SCENE_CLASS_GENERAL;
+	if (!t->scene_set || t->num_models != 0 || t->num_runs != 1 || t->one_group_code == 0) return SRT_SCENE_CLASS_GENERAL;
+	if (srt_scene_lds_bytes((size_t)t->sd.num_shapes, t->num_materials, 0, 1) == 0) return SRT_SCENE_CLASS_GENERAL;
+	if (!t->all_materials_ok || !t->unit_materials) return SRT_SCENE_CLASS_GENERAL;
+	if (options->num_bounces <= 0 || options->show_normals || textured || t->count_tris) return SRT_SCENE_CLASS_GENERAL;
+	const bool no_spec = (t->material_flags & (SRT_MF_NO_SPECULAR | SRT_MF_PLAIN_COLORS)) == (SRT_MF_NO_SPECULAR | SRT_MF_PLAIN_COLORS);
+#define SRT_SCENE_CLASS_MATCH(number, code, class_no_spec) \
+	if (t->one_group_code == (code) && no_spec == class_no_spec) return number;
+	SRT_SCENE_CLASS_LIST(SRT_SCENE_CLASS_MATCH)
+#undef SRT_SCENE_CLASS_MATCH
+	return SRT_SCENE_CLASS_GENERAL;
+}
+
+int srt_last_trace_class(const srt_tracer *t, int *scene_class_out) {
+	if (!t || !scene_class_out) return SRT_ERR_INVALID;
+	*scene_class_out = t->last_trace_class;
+	return SRT_OK;
+}
+
 int srt_trace(srt_tracer *t, const srt_render_data *options) { return srt_trace_fused(t, options, nullptr, 0u); }
 
 // srt_trace; with fused_argb != NULL the last reduction also resolves every pixel it has just accumulated into fused_argb
@@ -1190,6 +1225,7 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 	p.all_materials_ok = t->scene_set && t->all_materials_ok ? 1 : 0;
 	p.unit_materials = t->scene_set && t->unit_materials ? 1 : 0;
 	p.material_flags = t->scene_set ? t->material_flags : 0;
+	p.scene_class = t->last_trace_class = scene_class(t, options, textured);
 	p.f_sky_w = (float)t->sky_w;
 	p.f_sky_h = (float)t->sky_h;
 	p.sun_focus_int = dm_pow_small_int(p.sd.sun_focus);

@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "srt_set_denoise_object_motion", "srt_read_denoise_shape_ids", "srt_read_denoise_motion", "srt_motion_table_host",
     "srt_set_textures", "srt_set_material_textures", "srt_set_triangle_uvs", "srt_last_trace_textured", "srt_plane_frame_host",
     "srt_texture_check_host", "srt_group_set_textures", "srt_group_set_material_textures", "srt_group_set_triangle_uvs",
+    "srt_last_trace_class",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -354,6 +355,8 @@ def _bind(lib):
         lib.srt_group_set_textures.argtypes = [vp, vp, sz]
         lib.srt_group_set_material_textures.argtypes = [vp, vp, sz]
         lib.srt_group_set_triangle_uvs.argtypes = [vp, vp, sz]
+    if hasattr(lib, "srt_last_trace_class"):  # (an older library, SRT_LIB, in an A/B run)
+        lib.srt_last_trace_class.argtypes = [vp, C.POINTER(C.c_int)]
     return lib
 
 
@@ -419,6 +422,12 @@ class Tracer:
         out = C.c_int(0)
         self._check(self.lib.srt_last_trace_textured(self._h, C.byref(out)))
         return bool(out.value)
+
+    def last_trace_class(self):
+        """0: the last trace ran a general kernel; 1..: the kernel of the scene's class (srt_last_trace_class)"""
+        out = C.c_int(0)
+        self._check(self.lib.srt_last_trace_class(self._h, C.byref(out)))
+        return out.value
 
     def update_scene(self, shapes, triangles, materials):
         shapes = R.as_records(shapes, R.SHAPE)
