@@ -423,6 +423,12 @@ int srt_last_trace_textured(const srt_tracer *t, int *textured);
  * for a kernel compiled for the scene's class (sphere / plane scenes of one block group). The class follows
  * the scene and the options of the dispatch; results do not depend on it. */
 int srt_last_trace_class(const srt_tracer *t, int *scene_class);
+/* Host-only (no device). The integer srt_update_scene puts in place of a material probability p (metallic, specular,
+ * transmittance): *threshold = the number of generator outputs r in [0, 2^32) with p > (float)r * 2^-32f, so that the kernel's
+ * draw is r < *threshold. 0 for p <= 0 and NaN; below 2^32 for every p <= 1 (p = 1: 2^32 - 128, the 128 largest r convert to
+ * 1.0); 2^32 for p > 1, which has no 32-bit threshold: a scene with such a probability keeps its float compares and runs the
+ * general kernel. SRT_ERR_INVALID on a NULL pointer. */
+int srt_bernoulli_threshold_host(float p, uint64_t *threshold);
 /* Host-only (no device). The frame of a plane with this normal: returns 1 and writes T, B (3 floats each), or 0 when the
  * plane has none (T, B zeroed). */
 int srt_plane_frame_host(const float normal[3], float T[3], float B[3]);

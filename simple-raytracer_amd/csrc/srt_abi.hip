@@ -496,6 +496,20 @@ uint64_t hash_triangles(const srt_triangle *tris, size_t count) {
 	return h;
 }
 
+// bernoulli() thresholds (kernels.hip): T(p) = how many of the generator's 2^32 outputs r give p > (float)r * 2^-32 -- a prefix,
+// the conversion is monotone. 0 for p <= 0 and NaN, 2^32 for p > 1; p = 1 gives 2^32 - 128 (the 128 largest r convert to 1.0).
+// THE one copy: srt_update_scene and srt_bernoulli_threshold_host both call it.
+uint64_t bernoulli_threshold(float pr) {
+	uint64_t lo = 0, hi = (uint64_t)1 << 32; // first r in [lo, hi] for which !(pr > u(r)); hi = 2^32: none
+	while (lo < hi) {
+		const uint64_t mid = (lo + hi) >> 1;
+		const float u = (float)(uint32_t)mid * 2.3283064365386963e-10f;
+		if (pr > u) lo = mid + 1;
+		else hi = mid;
+	}
+	return lo;
+}
+
 int clear_canvas_impl(srt_tracer *t) {
 	const int rc = srt_temporal_commit(t); // temporal.hip: the frame being cleared becomes the denoiser's history
 	if (rc) return rc;
@@ -963,28 +977,17 @@ static int prepare_scene(srt_tracer *t, ScenePrep &sp, const srt_shape *shapes, 
 		float r0 = (float)((1.0 - (double)mu) / (1.0 + (double)mu));
 		return r0 * r0;
 	};
-	// bernoulli() thresholds (kernels.hip): T(p) = how many of the generator's 2^32 outputs r give p > (float)r * 2^-32 -- a prefix,
-	// the conversion is monotone. When every probability of the scene has T < 2^32 (p <= 1 does) the device table carries the
-	// thresholds' bits in place of metallic / specular / transmittance.
-	auto threshold = [](float pr) -> uint64_t {
-		uint64_t lo = 0, hi = (uint64_t)1 << 32; // first r in [lo, hi] for which !(pr > u(r)); hi = 2^32: none
-		while (lo < hi) {
-			const uint64_t mid = (lo + hi) >> 1;
-			const float u = (float)(uint32_t)mid * 2.3283064365386963e-10f;
-			if (pr > u) lo = mid + 1;
-			else hi = mid;
-		}
-		return lo;
-	};
+	// When every probability of the scene has a threshold (bernoulli_threshold() above) below 2^32 (p <= 1 does) the device table
+	// carries the thresholds' bits in place of metallic / specular / transmittance.
 	bool unit_materials = true;
 	for (const auto &m : dev_mats)
-		if (threshold(m.metallic) >> 32 || threshold(m.specular) >> 32 || threshold(m.transmittance) >> 32) unit_materials = false;
+		if (bernoulli_threshold(m.metallic) >> 32 || bernoulli_threshold(m.specular) >> 32 || bernoulli_threshold(m.transmittance) >> 32) unit_materials = false;
 	sp.unit_materials = unit_materials;
 	{
 		// what holds for every material (SRT_MF_*): draws the scene decides are not made by the kernel
 		bool no_specular = unit_materials, plain = true;
 		for (const auto &m : dev_mats) {
-			if (threshold(m.specular) != 0) no_specular = false;
+			if (bernoulli_threshold(m.specular) != 0) no_specular = false;
 			for (float c : {m.color.x, m.color.y, m.color.z})
 				if (!std::isfinite(c) || (c == 0.0f && std::signbit(c))) plain = false;
 		}
@@ -992,7 +995,7 @@ static int prepare_scene(srt_tracer *t, ScenePrep &sp, const srt_shape *shapes, 
 	}
 	for (auto &m : dev_mats) {
 		if (unit_materials) {
-			const uint32_t tm = (uint32_t)threshold(m.metallic), ts = (uint32_t)threshold(m.specular), tt = (uint32_t)threshold(m.transmittance);
+			const uint32_t tm = (uint32_t)bernoulli_threshold(m.metallic), ts = (uint32_t)bernoulli_threshold(m.specular), tt = (uint32_t)bernoulli_threshold(m.transmittance);
 			memcpy(&m.metallic, &tm, 4), memcpy(&m.specular, &ts, 4), memcpy(&m.transmittance, &tt, 4);
 		}
 		const float inv_ior = 1.0f / m.refraction_index;
@@ -1176,6 +1179,12 @@ static int scene_class(const srt_tracer *t, const srt_render_data *options, bool
 int srt_last_trace_class(const srt_tracer *t, int *scene_class_out) {
 	if (!t || !scene_class_out) return SRT_ERR_INVALID;
 	*scene_class_out = t->last_trace_class;
+	return SRT_OK;
+}
+
+int srt_bernoulli_threshold_host(float p, uint64_t *threshold_out) {
+	if (!threshold_out) return SRT_ERR_INVALID;
+	*threshold_out = bernoulli_threshold(p);
 	return SRT_OK;
 }
 

@@ -38,7 +38,7 @@ ABI_SYMBOLS = [
     "srt_set_denoise_object_motion", "srt_read_denoise_shape_ids", "srt_read_denoise_motion", "srt_motion_table_host",
     "srt_set_textures", "srt_set_material_textures", "srt_set_triangle_uvs", "srt_last_trace_textured", "srt_plane_frame_host",
     "srt_texture_check_host", "srt_group_set_textures", "srt_group_set_material_textures", "srt_group_set_triangle_uvs",
-    "srt_last_trace_class",
+    "srt_last_trace_class", "srt_bernoulli_threshold_host",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -78,6 +78,15 @@ def plane_frame_host(normal):
     n = np.ascontiguousarray(normal, np.float32).reshape(3)
     T, B = np.zeros(3, np.float32), np.zeros(3, np.float32)
     return (T, B) if lib.srt_plane_frame_host(_ptr(n), _ptr(T), _ptr(B)) else None
+
+
+def bernoulli_threshold_host(p):
+    """srt_bernoulli_threshold_host (host only): the integer T in [0, 2^32] that srt_update_scene makes of a material
+    probability p (a float32): the kernel's draw `r < T` is `p > float32(r) * 2^-32` for every generator output r."""
+    out = C.c_uint64(0)
+    if load_library().srt_bernoulli_threshold_host(C.c_float(float(np.float32(p))), C.byref(out)):
+        raise SrtError("srt_bernoulli_threshold_host failed")
+    return int(out.value)
 
 
 def texture_check_host(n_textures, bindings=None, uv_triangles=None, scene_triangles=0, images=None):
@@ -357,6 +366,8 @@ def _bind(lib):
         lib.srt_group_set_triangle_uvs.argtypes = [vp, vp, sz]
     if hasattr(lib, "srt_last_trace_class"):  # (an older library, SRT_LIB, in an A/B run)
         lib.srt_last_trace_class.argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(lib, "srt_bernoulli_threshold_host"):
+        lib.srt_bernoulli_threshold_host.argtypes = [C.c_float, C.POINTER(C.c_uint64)]
     return lib
 
 

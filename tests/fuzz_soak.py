@@ -2,7 +2,9 @@
 Same generator and checks as tests/test_gpu_fuzz.py, with progress lines so that a long
 run is visibly alive. Prints every failing iteration and a final summary; exit code 1 on
 any mismatch. SRT_FUZZ_ACCEL=1 runs the GPU side through the BVH (triangle counters are then
-not compared: the walk tests fewer triangles by design)."""
+not compared: the walk tests fewer triangles by design). SRT_FUZZ_LANE=<name> (or "all") runs that lane of
+tests/fuzz_scenes.py instead -- class1..class4, near_miss, scan, bvh, ..., tex_class -- with the checks of
+tests/test_gpu_fuzz_dispatch.py (class and textured flag, canvas, counters), N scenes per flavour."""
 import os
 import sys
 import time
@@ -18,12 +20,31 @@ import srt_pkg  # noqa: E402
 srt_pkg.load()
 from simple_raytracer_amd import build, records as R, scenes as S, tracer as T  # noqa: E402
 from oracle import oracle_py  # noqa: E402
+import fuzz_scenes as FS  # noqa: E402
 from test_gpu_fuzz import random_scene  # noqa: E402
 
 
 def bits_equal(a, b):
     na, nb = np.isnan(a), np.isnan(b)
     return np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb])
+
+
+def soak_lanes(names, n_benign, n_hostile, seed, orc, sky):
+    fails, t0 = 0, time.time()
+    for name in names:
+        for hostile, n in ((False, n_benign), (True, n_hostile)):
+            def progress(it, failures):
+                if it % 100 == 99:
+                    print(f"{name} hostile={hostile} {it + 1}/{n} scenes, {len(failures)} mismatches, {time.time() - t0:.0f} s", flush=True)
+            if n <= 0:
+                continue
+            failures, classes, edits = FS.run_lane(T, orc, sky, name, hostile, n, seed=seed, nthreads=8, progress=progress)
+            for f in failures:
+                print(f"MISMATCH lane={f[0]} hostile={hostile} it={f[1]} {f[2]}: {f[3]} pixels differ, counters {f[4]}", flush=True)
+            fails += len(failures)
+            print(f"{name} hostile={hostile}: {n} scenes, classes {sorted(set(classes))}, {len(failures)} mismatches", flush=True)
+    print(f"DONE lanes {names}: {n_benign} benign + {n_hostile} hostile scenes each: {fails} mismatches", flush=True)
+    return 1 if fails else 0
 
 
 def main():
@@ -34,6 +55,13 @@ def main():
     oracle_py.build()
     orc = oracle_py.Oracle("oracle")
     sky = S.synthetic_sky()
+    lane = os.environ.get("SRT_FUZZ_LANE")
+    if lane:
+        names = list(FS.LANES) if lane == "all" else lane.split(",")
+        for name in names:
+            if name not in FS.LANES:
+                sys.exit(f"SRT_FUZZ_LANE: unknown lane {name}; one of {list(FS.LANES)} or all")
+        return soak_lanes(names, n_benign, n_hostile, seed, orc, sky)
     w, h = 24, 16
     t = T.Tracer(w, h)
     t.set_skybox(sky)

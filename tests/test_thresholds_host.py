@@ -1,0 +1,122 @@
+"""CPU: the integer thresholds srt_update_scene puts in place of the material probabilities (csrc/srt_abi.hip
+bernoulli_threshold, exported host-only as srt_bernoulli_threshold_host) against their definition in numpy float32:
+
+    u(r) = float32(uint32 r) * float32(2^-32)        what the kernel's random_float makes of the generator's output r
+    T(p) = #{ r in [0, 2^32) : p > u(r) }            so that the kernel's draw `r < T(p)` IS `p > u(r)`
+
+An off-by-one in T changes one draw in 2^32: no canvas test would see it, and the result would no longer be the reference's.
+u is non-decreasing, so T is pinned by p > u(T - 1) (T > 0) and not (p > u(T)) (T < 2^32)."""
+import numpy as np
+import pytest
+
+from fuzz_scenes import threshold_by_definition, u_of_r
+from simple_raytracer_amd import tracer as T
+
+F = np.float32
+TWO32 = 1 << 32
+DENORMAL = np.finfo(F).smallest_subnormal
+
+
+def named_inputs():
+    ps = [0.0, -0.0, DENORMAL, 2.0 ** -33, 2.0 ** -32, 1.0 - 2.0 ** -24, 1.0, np.nextafter(F(1), F(2)), 1.5, np.inf, -np.inf, np.nan,
+          -DENORMAL, -2.0 ** -32, -0.2, -1.0, -3e38, 2.0, 3e38, 0.5, 0.25 + 2.0 ** -20]
+    for e in range(-149, 1):  # every power of two up to 1, and both of its neighbours
+        p = F(2.0 ** e)
+        ps += [np.nextafter(p, F(0)), p, np.nextafter(p, F(2))]
+    return [F(p) for p in ps]
+
+
+def random_inputs():
+    return np.random.RandomState(4).uniform(0, 1, 10_000).astype(F)
+
+
+def lib_threshold(p):
+    return T.bernoulli_threshold_host(F(p))
+
+
+def draws(p, r):
+    with np.errstate(invalid="ignore"):
+        return F(p) > u_of_r(r)
+
+
+def sample_r(rng, thr, n_uniform, cluster):
+    """uniform values of r, and values within +-512 of the threshold and of the powers of two (where the rounding step of
+    the conversion to float changes)"""
+    centres = np.array([thr] + [1 << k for k in range(0, 33)], np.int64)
+    near = (centres[rng.randint(len(centres), size=cluster)] + rng.randint(-512, 513, size=cluster)).clip(0, TWO32 - 1)
+    every = (centres[:, None] + np.arange(-2, 3)[None, :]).reshape(-1).clip(0, TWO32 - 1)  # and the borders themselves, always
+    return np.concatenate([rng.randint(0, TWO32, size=n_uniform, dtype=np.int64), near, every]).astype(np.uint64)
+
+
+def test_u_is_the_kernels_conversion():
+    """the definition's own edges: u(0) = 0, u(1) = 2^-32, the largest 128 outputs convert to exactly 1.0, and u never decreases"""
+    assert u_of_r(0) == 0 and u_of_r(1) == F(2.0 ** -32)
+    top = u_of_r(np.arange(TWO32 - 300, TWO32, dtype=np.uint64))
+    assert (top == 1.0).sum() == 128 and top[-129] < 1.0 and (top[-128:] == 1.0).all() and top.max() == 1.0
+    rng = np.random.RandomState(1)
+    r = np.sort(sample_r(rng, 12345, 1 << 18, 1 << 18))
+    assert (np.diff(u_of_r(r).astype(np.float64)) >= 0).all()
+
+
+@pytest.mark.parametrize("p", named_inputs(), ids=lambda p: f"{float(p)!r}")
+def test_threshold_is_the_definition(p):
+    """pinned at its border, equal to the bisection over the definition, and draw for draw on 2^20 values of r"""
+    thr = lib_threshold(p)
+    assert 0 <= thr <= TWO32
+    if thr > 0:
+        assert draws(p, thr - 1), (p, thr)
+    if thr < TWO32:
+        assert not draws(p, thr), (p, thr)
+    assert thr == threshold_by_definition(p)
+    rng = np.random.RandomState(int(F(p).view(np.uint32)) & 0x7fffffff)
+    r = sample_r(rng, thr, 1 << 19, 1 << 19)
+    assert np.array_equal(r < np.uint64(thr), draws(p, r)), p
+
+
+def test_random_probabilities():
+    """10^4 random floats in [0, 1]: the border, and draw for draw on 2^10 values of r each (2^10 * 10^4 in all)"""
+    rng = np.random.RandomState(5)
+    for p in random_inputs():
+        thr = lib_threshold(p)
+        assert (thr == 0 or draws(p, thr - 1)) and (thr == TWO32 or not draws(p, thr)), (p, thr)
+        r = sample_r(rng, thr, 1 << 9, 1 << 9)
+        assert np.array_equal(r < np.uint64(thr), draws(p, r)), p
+
+
+def test_what_the_rest_of_the_code_assumes():
+    """T < 2^32 for every p <= 1 (such scenes carry thresholds: unit_materials); T = 2^32 for p > 1 (they do not); T = 0 exactly
+    for p <= 0 and NaN (the no-specular shortcut); p = 1.0 is NOT "always": 128 outputs convert to 1.0; T never decreases"""
+    ps = np.array(named_inputs() + list(random_inputs()), F)
+    thr = np.array([lib_threshold(p) for p in ps], np.uint64)
+    with np.errstate(invalid="ignore"):
+        le1, gt1, le0 = ps <= 1, ps > 1, ps <= 0
+    nan = np.isnan(ps)
+    assert (thr[le1] < TWO32).all()
+    assert (thr[gt1] == TWO32).all() and gt1.sum() >= 5
+    assert np.array_equal(thr == 0, le0 | nan)
+    assert lib_threshold(1.0) == TWO32 - 128
+    # by hand, from round-to-nearest-even of uint32 -> float32 (steps of 256 below 2^32, of 128 below 2^31):
+    # r = 2^32 - 128 is the first to round up to 2^32; 2^32 - 384 ties to the even 2^32 - 512 and still draws for p = 1 - 2^-24;
+    # r = 2^31 - 64 is the first to round up to 2^31
+    assert lib_threshold(np.nextafter(F(1), F(0))) == TWO32 - 383
+    assert lib_threshold(0.5) == (1 << 31) - 64
+    assert lib_threshold(DENORMAL) == 1 and lib_threshold(2.0 ** -32) == 1 and lib_threshold(np.nextafter(F(2.0 ** -32), F(1))) == 2
+    order = np.argsort(ps[~nan], kind="stable")
+    assert (np.diff(thr[~nan][order].astype(np.int64)) >= 0).all()
+
+
+def test_null_pointer_is_invalid():
+    assert T.load_library().srt_bernoulli_threshold_host(F(0.5), None) != 0
+
+
+def test_exhaustive_over_every_output():
+    """all 2^32 values of r, in chunks: for p = 1.0 and one random p the draws are exactly the prefix [0, T) (about 20 s)"""
+    ps = [F(1.0), np.random.RandomState(6).uniform(0, 1, 1).astype(F)[0]]
+    thr = [lib_threshold(p) for p in ps]
+    chunk = 1 << 24
+    for base in range(0, TWO32, chunk):
+        u = (np.arange(base, base + chunk, dtype=np.uint32).astype(F) * F(2.0 ** -32))
+        for p, t in zip(ps, thr):
+            d = p > u
+            k = min(max(t - base, 0), chunk)  # the chunk's share of the prefix
+            assert d[:k].all() and not d[k:].any(), (p, base)
