@@ -1,0 +1,453 @@
+// bvh_host.cpp -- the host BVH builder (bvh_host.h): SAH build, refit, four-wide fold with its byte quantiser, the per-model cache
+// entry, and the two host-only entry points of include/srt_abi.h that hand its results out. Standard library only.
+#include "bvh_host.h"
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <future>
+#include <system_error>
+
+// World-space vertices as the pre-pass kernel computes them (render.cl:114-120 order); boxes
+// are padded by 2^-12 of the model's diagonal: a hit the float Moller-Trumbore test accepts
+// lies within rounding error of its triangle, and must still be inside every box above it.
+void BvhBuilder::load(const srt_model &m, const srt_triangle *all) {
+	const uint32_t n = m.num_triangles;
+	tris.resize(n);
+	auto xf = [&](const srt_float3 &v, float out[3]) {
+		const srt_float4 *t = m.transform;
+		out[0] = ((t[0].x * v.x + t[1].x * v.y) + t[2].x * v.z) + t[3].x * 1.0f;
+		out[1] = ((t[0].y * v.x + t[1].y * v.y) + t[2].y * v.z) + t[3].y * 1.0f;
+		out[2] = ((t[0].z * v.x + t[1].z * v.y) + t[2].z * v.z) + t[3].z * 1.0f;
+	};
+	float mlo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mhi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+	for (uint32_t j = 0; j < n; j++) {
+		const srt_triangle &tr = all[m.triangle_index + j];
+		float p[3][3];
+		for (int k = 0; k < 3; k++) xf(tr.vertices[k].pos, p[k]);
+		Tri &t = tris[j];
+		t.j = j;
+		bool finite = true;
+		for (int a = 0; a < 3; a++) {
+			// the kernel's triangle is (p0, p0 + e1, p0 + e2) with e = p_k - p0 rounded: cover both
+			const float q1 = p[0][a] + (p[1][a] - p[0][a]), q2 = p[0][a] + (p[2][a] - p[0][a]);
+			t.lo[a] = std::min(std::min(std::min(p[0][a], p[1][a]), std::min(p[2][a], q1)), q2);
+			t.hi[a] = std::max(std::max(std::max(p[0][a], p[1][a]), std::max(p[2][a], q1)), q2);
+			finite = finite && std::isfinite(t.lo[a]) && std::isfinite(t.hi[a]);
+		}
+		if (!finite) { // hostile input: a box that every ray enters, so the triangle is always tested
+			for (int a = 0; a < 3; a++) t.lo[a] = -FLT_MAX, t.hi[a] = FLT_MAX, t.c[a] = 0.0f;
+			continue;
+		}
+		for (int a = 0; a < 3; a++) {
+			t.c[a] = 0.5f * t.lo[a] + 0.5f * t.hi[a];
+			mlo[a] = std::min(mlo[a], t.lo[a]);
+			mhi[a] = std::max(mhi[a], t.hi[a]);
+		}
+	}
+	double d2 = 0.0;
+	for (int a = 0; a < 3; a++)
+		if (mhi[a] >= mlo[a]) d2 += ((double)mhi[a] - mlo[a]) * ((double)mhi[a] - mlo[a]);
+	const float pad = (float)std::min(std::sqrt(d2) * (1.0 / 4096.0), (double)FLT_MAX);
+	for (Tri &t : tris)
+		for (int a = 0; a < 3; a++) {
+			if (t.lo[a] == -FLT_MAX) continue;
+			// widen by pad plus two ulps (the slab arithmetic rounds, too); stays finite
+			t.lo[a] = std::max(-FLT_MAX, std::nextafter(std::nextafter(t.lo[a] - pad, -INFINITY), -INFINITY));
+			t.hi[a] = std::min(FLT_MAX, std::nextafter(std::nextafter(t.hi[a] + pad, INFINITY), INFINITY));
+		}
+}
+
+// Subtree over tris[b, e) appended to `out` (indices inside `out`; a node's skip = the index behind its subtree, which
+// for the subtree's last nodes is out.size() at return). The two halves of a large range are built by two threads into
+// vectors of their own and appended in order -- same nodes in the same order as the one-thread build, the ranges of
+// `tris` the threads partition are disjoint -- down to `par` levels: 10^5 triangles 42 -> 13 ms on the GPU box's cores.
+BvhBuilder::Stats BvhBuilder::build_into(std::vector<BvhNode> &out, uint32_t b, uint32_t e, uint32_t depth, int par) {
+	Stats st;
+	const uint32_t self = (uint32_t)out.size();
+	out.emplace_back();
+	st.max_depth = depth;
+	float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+	float clo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, chi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+	for (uint32_t i = b; i < e; i++)
+		for (int a = 0; a < 3; a++) {
+			lo[a] = std::min(lo[a], tris[i].lo[a]), hi[a] = std::max(hi[a], tris[i].hi[a]);
+			clo[a] = std::min(clo[a], tris[i].c[a]), chi[a] = std::max(chi[a], tris[i].c[a]);
+		}
+	for (int a = 0; a < 3; a++) out[self].lo[a] = lo[a], out[self].hi[a] = hi[a];
+	const uint32_t n = e - b;
+	if (n <= SRT_BVH_LEAF_MAX) {
+		out[self].leaf = (n << 28) | (rec_base + b);
+		out[self].skip = (uint32_t)out.size();
+		st.leaves = 1;
+		return st;
+	}
+	// binned SAH over the three axes
+	constexpr int NB = 16;
+	int best_axis = -1, best_bin = 0;
+	float best_cost = INFINITY;
+	if (depth < sah_depth) {
+		for (int a = 0; a < 3; a++) {
+			const float ext = chi[a] - clo[a];
+			if (!(ext > 0.0f) || !std::isfinite(ext)) continue;
+			const float scale = (float)NB / ext;
+			uint32_t cnt[NB] = {0};
+			float blo[NB][3], bhi[NB][3];
+			for (int k = 0; k < NB; k++)
+				for (int c = 0; c < 3; c++) blo[k][c] = FLT_MAX, bhi[k][c] = -FLT_MAX;
+			for (uint32_t i = b; i < e; i++) {
+				int k = (int)((tris[i].c[a] - clo[a]) * scale);
+				k = k < 0 ? 0 : (k >= NB ? NB - 1 : k);
+				cnt[k]++;
+				for (int c = 0; c < 3; c++) blo[k][c] = std::min(blo[k][c], tris[i].lo[c]), bhi[k][c] = std::max(bhi[k][c], tris[i].hi[c]);
+			}
+			float rarea[NB];
+			uint32_t rcnt[NB];
+			float rl[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, rh[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+			uint32_t rc = 0;
+			for (int k = NB - 1; k > 0; k--) {
+				for (int c = 0; c < 3; c++) rl[c] = std::min(rl[c], blo[k][c]), rh[c] = std::max(rh[c], bhi[k][c]);
+				rc += cnt[k];
+				rarea[k] = rc ? half_area(rl, rh) : 0.0f;
+				rcnt[k] = rc;
+			}
+			float ll[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, lh[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+			uint32_t lc = 0;
+			for (int k = 0; k < NB - 1; k++) { // split after bin k
+				for (int c = 0; c < 3; c++) ll[c] = std::min(ll[c], blo[k][c]), lh[c] = std::max(lh[c], bhi[k][c]);
+				lc += cnt[k];
+				if (lc == 0 || rcnt[k + 1] == 0) continue;
+				const float cost = half_area(ll, lh) * (float)lc + rarea[k + 1] * (float)rcnt[k + 1];
+				if (cost < best_cost) best_cost = cost, best_axis = a, best_bin = k;
+			}
+		}
+	}
+	uint32_t mid;
+	if (best_axis >= 0) {
+		const int a = best_axis;
+		const float scale = (float)NB / (chi[a] - clo[a]);
+		const float c0 = clo[a];
+		auto it = std::partition(tris.begin() + b, tris.begin() + e, [&](const Tri &t) {
+			int k = (int)((t.c[a] - c0) * scale);
+			k = k < 0 ? 0 : (k >= NB ? NB - 1 : k);
+			return k <= best_bin;
+		});
+		mid = (uint32_t)(it - tris.begin());
+	} else {
+		mid = b; // no usable split (coincident centroids, overflow, depth cap): halve by index
+	}
+	if (mid == b || mid == e) {
+		int a = 0;
+		for (int c = 1; c < 3; c++)
+			if (chi[c] - clo[c] > chi[a] - clo[a]) a = c;
+		mid = b + n / 2;
+		std::nth_element(tris.begin() + b, tris.begin() + mid, tris.begin() + e, [a](const Tri &x, const Tri &y) { return x.c[a] < y.c[a]; });
+	}
+	out[self].leaf = 0;
+	Stats sl, sr;
+	if (par > 0 && n >= 8192) {
+		std::vector<BvhNode> left, right;
+		std::future<Stats> fut;
+		try {
+			fut = std::async(std::launch::async, [&] { return build_into(left, b, mid, depth + 1, par - 1); });
+		} catch (const std::system_error &) { // no thread to be had: this one does both halves
+		}
+		sr = build_into(right, mid, e, depth + 1, par - 1);
+		sl = fut.valid() ? fut.get() /* (rethrows what the other thread threw) */ : build_into(left, b, mid, depth + 1, 0);
+		for (std::vector<BvhNode> *sub : {&left, &right}) {
+			const uint32_t off = (uint32_t)out.size();
+			out.insert(out.end(), sub->begin(), sub->end());
+			for (size_t i = off; i < out.size(); i++) out[i].skip += off;
+		}
+	} else {
+		sl = build_into(out, b, mid, depth + 1, 0);
+		sr = build_into(out, mid, e, depth + 1, 0);
+	}
+	out[self].skip = (uint32_t)out.size();
+	st.leaves = sl.leaves + sr.leaves;
+	st.max_depth = std::max(sl.max_depth, sr.max_depth);
+	return st;
+}
+uint32_t BvhBuilder::build(uint32_t b, uint32_t e, uint32_t depth) {
+	const uint32_t self = (uint32_t)nodes.size();
+	const Stats st = build_into(nodes, b, e, depth, par);
+	leaves += st.leaves;
+	if (st.max_depth > max_depth) max_depth = st.max_depth;
+	return self;
+}
+
+// New boxes for an existing topology (nodes relative to the model, `order` = triangle of each
+// record): the model moved but its triangles did not. Children follow their parent in the
+// array, so one backward sweep has every child's box ready before its parent's. O(n).
+void BvhBuilder::refit(const srt_model &m, const srt_triangle *all) {
+	load(m, all);
+	const uint32_t n = (uint32_t)nodes.size();
+	for (uint32_t i = n; i-- > 0;) {
+		BvhNode &nd = nodes[i];
+		float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+		if (nd.leaf) {
+			const uint32_t first = nd.leaf & 0x0fffffffu, cnt = nd.leaf >> 28;
+			for (uint32_t r = first; r < first + cnt; r++) {
+				const Tri &t = tris[order[r]]; // load() leaves tris in triangle order
+				for (int a = 0; a < 3; a++) lo[a] = std::min(lo[a], t.lo[a]), hi[a] = std::max(hi[a], t.hi[a]);
+			}
+		} else {
+			const uint32_t left = i + 1, right = nodes[left].skip == SRT_BVH_END ? n : nodes[left].skip;
+			for (uint32_t c : {left, right})
+				for (int a = 0; a < 3; a++) lo[a] = std::min(lo[a], nodes[c].lo[a]), hi[a] = std::max(hi[a], nodes[c].hi[a]);
+		}
+		for (int a = 0; a < 3; a++) nd.lo[a] = lo[a], nd.hi[a] = hi[a];
+	}
+}
+
+// The boxes of an inner block as bytes (device_types.h): bound = fmaf(q, 2^e, origin) per axis, rounded outwards and CHECKED in
+// exactly that arithmetic, the grid coarsened until every upper bound fits a byte. Non-finite extents (hostile input in
+// all-embracing boxes) end on the coarsest grid, where upper bounds overflow to +inf: still a box that contains the child.
+template <class Fma>
+static inline __attribute__((always_inline)) void quantise_body(const std::vector<BvhNode> &c, const uint32_t *kids, uint32_t nk, uint32_t tags, uint32_t first, uint32_t *blk, Fma fmaf_any) {
+	float origin[3];
+	uint32_t expo[3];
+	uint8_t qlo[3][4], qhi[3][4];
+	auto pow2 = [](int e) { // 2^e as a float, -126 <= e <= 127
+		const uint32_t bits = (uint32_t)(e + 127) << 23;
+		float f;
+		memcpy(&f, &bits, 4);
+		return f;
+	};
+	for (int a = 0; a < 3; a++) {
+		origin[a] = FLT_MAX;
+		float top = -FLT_MAX;
+		for (uint32_t k = 0; k < nk; k++) origin[a] = std::min(origin[a], c[kids[k]].lo[a]), top = std::max(top, c[kids[k]].hi[a]);
+		if (!(origin[a] == origin[a])) origin[a] = -FLT_MAX; // (NaN boxes of hostile input)
+		int e = -126;
+		const float extent = top - origin[a];
+		if (extent > 0.0f) {
+			int ex = 0;
+			(void)std::frexp(extent / 255.0f, &ex); // extent / 255 = m * 2^ex, m in [0.5, 1): 2^ex is the first power of two above it
+			e = std::isfinite(extent) ? ex : 126;
+		}
+		for (;; e++) {
+			if (e < -126) e = -126;
+			if (e > 127) e = 127;
+			const float scale = pow2(e);
+			const double inv_scale = std::ldexp(1.0, -e); // (exact; in double so that 2^126 has a reciprocal)
+			bool fits = true;
+			for (uint32_t k = 0; k < nk && fits; k++) {
+				const float lo = c[kids[k]].lo[a], hi = c[kids[k]].hi[a];
+				const double fl = ((double)lo - (double)origin[a]) * inv_scale; // >= 0: origin is the smallest lo
+				int ql = fl >= 255.0 ? 255 : (fl > 0.0 ? (int)fl : 0);       // (NaN: 0)
+				while (ql > 0 && !(fmaf_any((float)ql, scale, origin[a]) <= lo)) ql--;
+				const double fh = ((double)hi - (double)origin[a]) * inv_scale;
+				int qh = fh > 255.0 ? 256 : (fh > 0.0 ? (int)fh + ((double)(int)fh < fh ? 1 : 0) : 0);
+				if (!(fh == fh)) qh = 256;
+				while (qh <= 255 && !(fmaf_any((float)qh, scale, origin[a]) >= hi)) qh++;
+				if (qh > 255) fits = false;
+				qlo[a][k] = (uint8_t)ql, qhi[a][k] = (uint8_t)(qh & 255);
+			}
+			if (fits || e == 127) { // (e == 127: 255 * 2^127 overflows every finite bound; keep what we have, q = 255 gives +inf)
+				if (!fits)
+					for (uint32_t k = 0; k < nk; k++) qhi[a][k] = 255;
+				expo[a] = (uint32_t)(e + 127);
+				break;
+			}
+		}
+	}
+	for (int a = 0; a < 3; a++) memcpy(&blk[a], &origin[a], 4);
+	blk[3] = expo[0] | (expo[1] << 8) | (expo[2] << 16) | (nk << 24);
+	for (int a = 0; a < 3; a++) {
+		blk[4 + a] = 0u, blk[7 + a] = 0u;
+		for (uint32_t k = 0; k < 4; k++) {
+			blk[4 + a] |= (uint32_t)(k < nk ? qlo[a][k] : 255u) << (8 * k); // (an empty slot: lo above hi; the walk counts the slots)
+			blk[7 + a] |= (uint32_t)(k < nk ? qhi[a][k] : 0u) << (8 * k);
+		}
+	}
+	blk[10] = tags;
+	blk[11] = first;
+}
+// The check wants fmaf as the device rounds it. glibc's fmaf is a call into a software path on some hosts (85 ns: 45 ms of a
+// 10^5-triangle hierarchy's 528,000 checks); a CPU with FMA does it in one instruction, inlined into a copy of the function.
+__attribute__((target("fma"))) static void quantise_hw(const std::vector<BvhNode> &c, const uint32_t *kids, uint32_t nk, uint32_t tags, uint32_t first, uint32_t *blk) {
+	quantise_body(c, kids, nk, tags, first, blk, [](float a, float b, float x) __attribute__((target("fma"))) { return __builtin_fmaf(a, b, x); });
+}
+static void quantise(const std::vector<BvhNode> &c, const uint32_t *kids, uint32_t nk, uint32_t tags, uint32_t first, uint32_t *blk) {
+	static const bool hw = __builtin_cpu_supports("fma");
+	if (hw) quantise_hw(c, kids, nk, tags, first, blk);
+	else quantise_body(c, kids, nk, tags, first, blk, [](float a, float b, float x) { return std::fmaf(a, b, x); });
+}
+// fills block `self` (already allocated) from node ci; returns the reference to it
+uint32_t BvhBuilder::fold_node(const std::vector<BvhNode> &c, uint32_t ci, uint32_t self, bool balanced, Wide &w, uint32_t &need) {
+	const BvhNode &nd = c[ci];
+	if (nd.leaf) {
+		const uint32_t first = nd.leaf & 0x0fffffffu, cnt = nd.leaf >> 28;
+		for (uint32_t k = 0; k < cnt; k++) w.dest[first + k] = (self << 2) | k;
+		need = 0;
+		return SRT_BVH_LEAF_BIT | (cnt << 28) | self;
+	}
+	w.inner.push_back(self);
+	uint32_t kids[4], nk = 0;
+	const uint32_t left = ci + 1u, right = c[left].skip;
+	kids[nk++] = left, kids[nk++] = right;
+	if (balanced) {
+		uint32_t g[4], ng = 0;
+		for (uint32_t k = 0; k < 2; k++)
+			if (c[kids[k]].leaf) g[ng++] = kids[k];
+			else g[ng++] = kids[k] + 1u, g[ng++] = c[kids[k] + 1u].skip;
+		nk = ng;
+		for (uint32_t k = 0; k < ng; k++) kids[k] = g[k];
+	} else {
+		while (nk < 4) {
+			int open = -1;
+			float area = -1.0f;
+			for (uint32_t k = 0; k < nk; k++) {
+				if (c[kids[k]].leaf) continue;
+				const float a = half_area(c[kids[k]].lo, c[kids[k]].hi);
+				if (open < 0 || a > area) open = (int)k, area = a; // NaN / inf areas (hostile input) still pick somebody
+			}
+			if (open < 0) break;
+			const uint32_t o = kids[open];
+			kids[open] = o + 1u;
+			kids[nk++] = c[o + 1u].skip;
+		}
+	}
+	// the children's blocks lie side by side: the walk finds child k at first + k
+	const uint32_t first = (uint32_t)(w.blocks.size() / 32);
+	w.blocks.resize(w.blocks.size() + 32 * (size_t)nk, 0u);
+	uint32_t deepest = 0;
+	uint32_t tags = 0;
+	for (uint32_t k = 0; k < 4; k++) {
+		if (k >= nk) {
+			tags |= k << (8 * k);
+			continue;
+		}
+		uint32_t sub = 0;
+		const uint32_t ref = fold_node(c, kids[k], first + k, balanced, w, sub); // may grow w.blocks: index, do not keep pointers
+		if (sub > deepest) deepest = sub;
+		tags |= SRT_BVH_TAG(ref, k) << (8 * k);
+	}
+	w.jobs.push_back({self, {kids[0], kids[1], nk > 2 ? kids[2] : 0u, nk > 3 ? kids[3] : 0u}, nk, tags, first});
+	need = deepest + (nk - 1u);
+	return self;
+}
+void BvhBuilder::fold_wide(const std::vector<BvhNode> &c, uint32_t records, bool balanced, Wide &w) {
+	w.blocks.clear(), w.inner.clear();
+	w.dest.assign(records, 0u);
+	w.root = SRT_BVH_NONE, w.need = 0;
+	if (c.empty()) return;
+	w.blocks.reserve(32 * c.size()); // (every node of the binary hierarchy becomes at most one block)
+	w.inner.reserve(c.size() / 2 + 1), w.jobs.reserve(c.size() / 2 + 1);
+	w.blocks.resize(32, 0u);
+	w.jobs.clear();
+	w.root = fold_node(c, 0u, 0u, balanced, w, w.need);
+	// the blocks' boxes: every inner block by itself (reads the binary nodes, writes its own 48 bytes), large hierarchies on up
+	// to eight threads (10^5 triangles: 22k blocks x 24 bounds rounded outwards and checked)
+	uint32_t *blocks = w.blocks.data();
+	const size_t nj = w.jobs.size();
+	auto run = [&](size_t lo, size_t hi) {
+		for (size_t i = lo; i < hi; i++) {
+			const Wide::Job &j = w.jobs[i];
+			quantise(c, j.kids, j.nk, j.tags, j.first, blocks + 32 * (size_t)j.self);
+		}
+	};
+	const size_t parts = nj >= 4096 ? 8 : 1;
+	std::vector<std::future<void>> futs;
+	try {
+		for (size_t t = 1; t < parts; t++) futs.push_back(std::async(std::launch::async, run, nj * t / parts, nj * (t + 1) / parts));
+	} catch (const std::system_error &) { // no more threads: the rest is done here
+	}
+	run(0, nj / parts);
+	for (size_t t = futs.size() + 1; t < parts; t++) run(nj * t / parts, nj * (t + 1) / parts);
+	for (auto &f : futs) f.get();
+	w.jobs.clear();
+	w.jobs.shrink_to_fit();
+}
+
+// Appends the model's nodes and triangle order; returns the root's index.
+uint32_t BvhBuilder::run(const srt_model &m, const srt_triangle *all, uint32_t first_record) {
+	rec_base = first_record;
+	load(m, all);
+	const uint32_t n0 = (uint32_t)nodes.size();
+	build(0, (uint32_t)tris.size(), 1);
+	const uint32_t n1 = (uint32_t)nodes.size();
+	for (uint32_t i = n0; i < n1; i++)
+		if (nodes[i].skip == n1) nodes[i].skip = SRT_BVH_END;
+	for (const Tri &t : tris) order.push_back(t.j);
+	return n0;
+}
+
+// (re)builds nodes/order from the model and folds them; the fallback keeps every walk inside SRT_BVH_STACK_CAP
+void BvhCacheEntry::build(const srt_model &m, const srt_triangle *all) {
+	for (int attempt = balanced ? 1 : 0; attempt < 2; attempt++) {
+		nodes.clear(), order.clear();
+		BvhBuilder bb(nodes, order);
+		if (attempt) bb.sah_depth = 0;
+		bb.run(m, all, 0u);
+		leaves = bb.leaves, depth = bb.max_depth;
+		balanced = attempt != 0;
+		BvhBuilder::fold_wide(nodes, m.num_triangles, balanced, wide);
+		if (wide.need <= SRT_BVH_STACK_CAP) break; // a balanced tree of < 2^28 triangles needs at most 3 * 15
+	}
+}
+void BvhCacheEntry::refit(const srt_model &m, const srt_triangle *all) {
+	BvhBuilder bb(nodes, order);
+	bb.refit(m, all);
+	BvhBuilder::fold_wide(nodes, m.num_triangles, balanced, wide);
+	if (wide.need > SRT_BVH_STACK_CAP) build(m, all); // the new boxes fold differently: start over
+}
+
+// 64-bit FNV-1a over 8-byte words (records are 96 B)
+uint64_t hash_triangles(const srt_triangle *tris, size_t count) {
+	uint64_t h = 0xcbf29ce484222325ull;
+	const size_t words = count * sizeof(srt_triangle) / 8;
+	for (size_t i = 0; i < words; i++) {
+		uint64_t w;
+		memcpy(&w, reinterpret_cast<const char *>(tris) + 8 * i, 8);
+		h = (h ^ w) * 0x100000001b3ull;
+	}
+	return h;
+}
+
+extern "C" {
+
+int srt_bvh_build_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, srt_bvh_node *nodes_out, size_t nodes_cap,
+                       uint32_t *order_out, size_t order_cap, size_t *n_nodes) {
+	if (!model || !n_nodes || model->type != SRT_SHAPE_MODEL || (n_triangles && !triangles)) return SRT_ERR_INVALID;
+	const srt_model &m = model->shape.model;
+	if ((uint64_t)m.triangle_index + m.num_triangles > n_triangles || m.num_triangles > 0x0fffffffu) return SRT_ERR_INVALID;
+	try {
+		std::vector<BvhNode> nodes;
+		std::vector<uint32_t> order;
+		if (m.num_triangles > 0) {
+			BvhBuilder bb(nodes, order);
+			bb.run(m, triangles, 0u);
+		}
+		*n_nodes = nodes.size();
+		if (nodes_out) memcpy(nodes_out, nodes.data(), std::min(nodes.size(), nodes_cap) * sizeof(BvhNode));
+		if (order_out) memcpy(order_out, order.data(), std::min(order.size(), order_cap) * sizeof(uint32_t));
+	} catch (...) { // std::bad_alloc: no C++ exception may cross the C ABI
+		return SRT_ERR_INVALID;
+	}
+	return SRT_OK;
+}
+
+int srt_bvh_wide_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, int force_balanced, uint32_t *blocks_out,
+                      size_t blocks_cap, uint32_t *dest_out, size_t dest_cap, size_t *n_blocks, uint32_t *root, uint32_t *stack_need, int *balanced) {
+	if (!model || !n_blocks || model->type != SRT_SHAPE_MODEL || (n_triangles && !triangles)) return SRT_ERR_INVALID;
+	const srt_model &m = model->shape.model;
+	if ((uint64_t)m.triangle_index + m.num_triangles > n_triangles || m.num_triangles > 0x0fffffffu) return SRT_ERR_INVALID;
+	try {
+		BvhCacheEntry ent;
+		ent.balanced = force_balanced != 0;
+		if (m.num_triangles > 0) ent.build(m, triangles);
+		*n_blocks = ent.wide.blocks.size() / 32;
+		if (root) *root = ent.wide.root;
+		if (stack_need) *stack_need = ent.wide.need;
+		if (balanced) *balanced = ent.balanced ? 1 : 0;
+		if (blocks_out) memcpy(blocks_out, ent.wide.blocks.data(), std::min(ent.wide.blocks.size(), blocks_cap * 32) * sizeof(uint32_t));
+		if (dest_out) memcpy(dest_out, ent.wide.dest.data(), std::min(ent.wide.dest.size(), dest_cap) * sizeof(uint32_t));
+	} catch (...) { // std::bad_alloc: no C++ exception may cross the C ABI
+		return SRT_ERR_INVALID;
+	}
+	return SRT_OK;
+}
+
+} // extern "C"

@@ -1,0 +1,100 @@
+// bvh_host.h — the host BVH builder of libsrt_hip.so: what srt_update_scene (scene_prep.cpp) builds, caches and refits per model
+// instance, and what srt_bvh_build_host / srt_bvh_wide_host hand out. No HIP: the standard library, the public record types and
+// device_types.h only, so it compiles with any C++17 compiler and runs without a device (tests/csrc/host_units_check.cpp).
+#ifndef SRT_BVH_HOST_H
+#define SRT_BVH_HOST_H
+
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "../../include/srt_abi.h"
+#include "device_types.h"
+
+// ---- BVH builder (host; layout in device_types.h) --------------------
+// Top-down, binned surface-area heuristic (16 bins, all three axes), leaves of at most
+// SRT_BVH_LEAF_MAX triangles, nodes emitted in depth-first order with skip links. Runs once
+// per srt_update_scene and model instance; ~35 ms for 10^5 triangles on one host core.
+struct BvhBuilder {
+	struct Tri {
+		float lo[3], hi[3], c[3];
+		uint32_t j;
+	};
+	std::vector<Tri> tris;
+	std::vector<BvhNode> &nodes;
+	std::vector<uint32_t> &order;
+	uint32_t rec_base = 0;
+	uint32_t leaves = 0, max_depth = 0;
+	uint32_t sah_depth = 48; // below this depth: median splits (0 = a balanced tree, see fold_wide's stack bound)
+	int par = 3;             // levels at which build_into gives one half to a thread of its own: up to 8 subtrees at a time (0 = one thread)
+
+	BvhBuilder(std::vector<BvhNode> &n, std::vector<uint32_t> &o) : nodes(n), order(o) {}
+
+	static float half_area(const float lo[3], const float hi[3]) {
+		const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+		return dx * dy + dy * dz + dz * dx;
+	}
+
+	void load(const srt_model &m, const srt_triangle *all);
+	struct Stats {
+		uint32_t leaves = 0, max_depth = 0;
+	};
+	Stats build_into(std::vector<BvhNode> &out, uint32_t b, uint32_t e, uint32_t depth, int par);
+	uint32_t build(uint32_t b, uint32_t e, uint32_t depth);
+	void refit(const srt_model &m, const srt_triangle *all);
+
+	// The wide form of a hierarchy (device_types.h): `c` is the canonical binary form build() leaves (depth-first, the left
+	// child directly behind its parent, the right one at the left one's skip link; indices and records relative to the
+	// model). An inner block takes the two children of a node and then, while it has room, replaces the child with the
+	// largest box by that child's own two (`balanced`: the node's grandchildren, level by level); leaves become leaf
+	// blocks. Blocks are appended to `out` (32 dwords each, block indices relative to `out`'s start = the model's first
+	// block), `inner` lists the inner ones (their references are shifted when the model is placed in the scene), dest[r]
+	// = (leaf block << 2) | slot of record r. Returns the root reference and in `need` the most entries a walk can have
+	// waiting at once: every block on the way down leaves at most (children - 1) behind.
+	struct Wide {
+		std::vector<uint32_t> blocks;
+		std::vector<uint32_t> inner;
+		std::vector<uint32_t> dest;
+		uint32_t root = SRT_BVH_NONE, need = 0;
+		struct Job { // an inner block whose boxes are still to be quantised (fold_wide does them on several threads)
+			uint32_t self, kids[4], nk, tags, first;
+		};
+		std::vector<Job> jobs;
+	};
+	static uint32_t fold_node(const std::vector<BvhNode> &c, uint32_t ci, uint32_t self, bool balanced, Wide &w, uint32_t &need);
+	static void fold_wide(const std::vector<BvhNode> &c, uint32_t records, bool balanced, Wide &w);
+
+	uint32_t run(const srt_model &m, const srt_triangle *all, uint32_t first_record);
+};
+
+// One model instance's hierarchy with indices relative to its own first node / first record, kept
+// between srt_update_scene calls together with what it was built from: an edit that leaves a model's
+// triangles and transform alone (camera, materials, sun, OTHER shapes) re-uses it instead of paying
+// the build again (10^5 triangles: 37 ms -> 1.5 ms for the comparison).
+struct BvhCacheEntry {
+	uint32_t count = 0;
+	uint64_t tri_hash = 0; // of the triangle bytes: looked at before any memcmp
+	bool claimed = false;  // taken by a model of the srt_update_scene in progress
+	srt_float4 transform[4];
+	std::vector<srt_triangle> tris;
+	std::vector<BvhNode> nodes;
+	std::vector<uint32_t> order;
+	BvhBuilder::Wide wide; // what the device walks, block indices relative to the model's first block
+	bool balanced = false; // built without the SAH because the SAH tree could overflow a lane's stack
+	uint32_t leaves = 0, depth = 0;
+	void build(const srt_model &m, const srt_triangle *all);
+	void refit(const srt_model &m, const srt_triangle *all);
+	bool same_triangles(const srt_model &m, const srt_triangle *all, uint64_t hash) const {
+		return m.num_triangles == count && hash == tri_hash && memcmp(tris.data(), all + m.triangle_index, (size_t)count * sizeof(srt_triangle)) == 0;
+	}
+	bool same_transform(const srt_model &m) const { return memcmp(transform, m.transform, sizeof transform) == 0; }
+};
+
+// the hierarchies of the previous srt_update_scene; a handle owns one (srt_tracer::bvh_cache), made when first needed
+struct BvhCache {
+	std::vector<BvhCacheEntry> entries;
+};
+
+uint64_t hash_triangles(const srt_triangle *tris, size_t count);
+
+#endif

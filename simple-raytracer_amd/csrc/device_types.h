@@ -1,5 +1,5 @@
-/* device_types.h — device-side scene representation shared by kernels.hip and
- * srt_abi.hip. Not part of the public ABI. */
+/* device_types.h — device-side scene representation shared by kernels.hip and the host side
+ * (srt_abi.hip, scene_prep.cpp, bvh_host.cpp). No HIP header. Not part of the public ABI. */
 #ifndef SRT_DEVICE_TYPES_H
 #define SRT_DEVICE_TYPES_H
 
@@ -16,7 +16,7 @@
  *   plane : 8 dwords  {px, py, pz, 0, nx, ny, nz, 0}       -> 2 planes per block
  *   model : 8 dwords  {min.x, min.y, min.z, first_wtri(bits), max.x, max.y, max.z, count(bits)} -> 2 per block
  *           (with a BVH: the root node's index in place of first_wtri)
- * A block that is not full ends in records that cannot be hit (srt_abi.hip). Block b lives at
+ * A block that is not full ends in records that cannot be hit (scene_prep.cpp). Block b lives at
  * dword 16 * b of the packed array. Three consecutive blocks form a GROUP with one 16-byte header
  * (BlockGroup): the kernel issues the header load and the three 64-byte block loads together and
  * waits once -- a 7-shape scene is one group, i.e. one scalar-memory round trip per path segment. */
@@ -79,7 +79,7 @@ static_assert(sizeof(WinnerRec) == 32, "WinnerRec 32 B");
  *                nothing to walk; else block index (absolute, <= SRT_BVH_INDEX_MAX so that byte
  *                offsets fit 32 bits), bit 31 = leaf, bits 28-29 = triangles in the leaf
  * A lane keeps the children it still has to enter on a stack of SRT_BVH_STACK_CAP entries; the host
- * checks every hierarchy against that bound (srt_abi.hip fold_wide) and falls back to a balanced one. */
+ * checks every hierarchy against that bound (bvh_host.cpp fold_wide) and falls back to a balanced one. */
 typedef srt_bvh_node BvhNode; /* include/srt_types.h */
 #define SRT_BVH_FIRST_DWORD 11 /* where an inner block keeps the index of its child 0 */
 #define SRT_BVH_TRI_FLOATS 9

@@ -995,7 +995,7 @@ __device__ __forceinline__ f3 texture_albedo(const TraceParams &p, const TexPara
 #define SRT_SUB_MODELS 64
 #endif
 #ifndef SRT_SUB_BVH
-#define SRT_SUB_BVH 64 // (round 2 measured 128 faster -- with chunks of 5 sub-jobs: it was the chunk, not the sub-job; srt_abi.hip)
+#define SRT_SUB_BVH 64 // (round 2 measured 128 faster -- with chunks of 5 sub-jobs: it was the chunk, not the sub-job; trace_plan.h)
 #endif
 // SHADE runs when hits + queued paths reach this many lanes (64 = always a full wave)
 #ifndef SRT_SHADE_MIN
@@ -1011,7 +1011,7 @@ __device__ __forceinline__ f3 texture_albedo(const TraceParams &p, const TexPara
 #ifndef SRT_HQ_CAP_MODELS
 #define SRT_HQ_CAP_MODELS 64 // (40 / 48 / 56 / 64 at full size: configs[2] array scan 103.3 / 103.1 / 103.2 / 103.2 ms -- the scan does not care)
 #endif
-// Array-scan kernels: a model of at least this many triangles ("big", srt_abi.hip packs it alone in its block) is not
+// Array-scan kernels: a model of at least this many triangles ("big", scene_prep.cpp packs it alone in its block) is not
 // scanned by the few lanes whose rays happen to enter its box in one EXTEND phase; those rays wait in one of the
 // wave's two scan stacks (the host deals the big models out to them) until SRT_SCAN_FULL of them have gathered.
 #ifndef SRT_SCAN_SUSPEND_MIN
@@ -1464,7 +1464,7 @@ __global__ __launch_bounds__(256) void srt_selftest_kernel(unsigned long long *o
 		float b = rand_float_exp(h, 127 - 44, 88);
 		if ((r & 0xffffu) == 11u) b = dm_u2f(0x7fc00000u | (mix32(h) & 0x3fffffu)); // a NaN denominator now and then
 		bad_div += same_f3(div3(a, b), a / b) ? 0 : 1;
-		{ // the sphere normal's form: the host's correctly rounded 1 / b for b in [2^-40, 2^40], else 0 (WinnerRec.inv_w, srt_abi.hip)
+		{ // the sphere normal's form: the host's correctly rounded 1 / b for b in [2^-40, 2^40], else 0 (WinnerRec.inv_w, scene_prep.cpp)
 			const float ab = dm_fabs(b);
 			const float y = (ab >= 0x1p-40f && ab <= 0x1p40f) ? 1.0f / b : 0.0f;
 			bad_div += same_f3(div3_by_rcp(a, b, y), a / b) ? 0 : 1;

@@ -1,0 +1,35 @@
+// scene_prep.h — the host pass of srt_update_scene / srt_group_update_scene: everything a device needs of a scene, as host arrays.
+// No HIP, and no handle: the caller (srt_abi.hip) passes what the pass reads of one and uploads the result.
+#ifndef SRT_SCENE_PREP_H
+#define SRT_SCENE_PREP_H
+
+#include <string>
+#include <vector>
+
+#include "bvh_host.h"
+
+// Everything a device needs of a scene, made on the host ONCE per srt_update_scene / srt_group_update_scene: shape blocks and group
+// headers, winner records, world-triangle offsets, the hierarchy in its device form, the device material table (bernoulli()
+// thresholds, Schlick constants). A group of N devices prepares one of these and uploads it N times (round 4; before, the whole
+// host pass -- 18 ms of BVH build for 10^5 triangles -- ran once per device, in turn).
+struct ScenePrep {
+	std::vector<BlockGroup> groups;
+	std::vector<float> data;
+	std::vector<WinnerRec> winners;
+	std::vector<uint32_t> offs, bvh_blocks, bvh_order, bvh_dest;
+	std::vector<srt_material> dev_mats;
+	uint64_t total_wtris = 0, max_tris = 0;
+	int num_models = 0;
+	bool use_bvh = false, unit_materials = false, all_materials_ok = true;
+	int material_flags = 0;
+	uint32_t one_group_code = 0; // srt_tracer::one_group_code
+	uint64_t bvh_info[7] = {0, 0, 0, 0, 0, 0, 0};
+};
+
+// accel_mode: SRT_ACCEL_*; cache: the caller's hierarchy cache (a group: its first member's); scan_suspend_min: srt_scan_suspend_min()
+int prepare_scene(int accel_mode, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
+                  const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene);
+
+uint64_t bernoulli_threshold(float pr);
+
+#endif

@@ -1,6 +1,7 @@
 // srt_internal.h — the handle behind `srt_tracer *` and the small helpers the translation units of
-// libsrt_hip.so share (srt_abi.hip: life cycle, scene, trace; srt_collect.hip: multi-GPU collection,
-// frame pipeline). Not part of the public ABI.
+// libsrt_hip.so share (srt_abi.hip: life cycle, scene upload, trace; srt_collect.hip: multi-GPU collection,
+// frame pipeline). What of the host side needs no handle and no HIP is not here: bvh_host.h, scene_prep.h, trace_plan.h.
+// Not part of the public ABI.
 #ifndef SRT_INTERNAL_H
 #define SRT_INTERNAL_H
 
@@ -60,7 +61,7 @@ struct srt_tracer {
 	int accel_mode = SRT_ACCEL_NONE; // what the next srt_update_scene builds
 	bool bvh_active = false;         // the current scene's models carry BVH roots
 	uint64_t bvh_info[7] = {0, 0, 0, 0, 0, 0, 0};
-	struct BvhCache *bvh_cache = nullptr; // hierarchies of the previous srt_update_scene (see BvhCacheEntry)
+	struct BvhCache *bvh_cache = nullptr; // hierarchies of the previous srt_update_scene (bvh_host.h BvhCacheEntry; made by scene_prep.cpp)
 	DevBuf<unsigned long long> counters;
 	DevBuf<unsigned long long> wave_counters; // per persistent wave, summed in srt_get_counters
 	DevBuf<float> scan_queue;                 // array scan: per persistent wave (two sets, as the counters), allocated when first needed

@@ -7,7 +7,7 @@ random_scene() is the generator of tests/test_gpu_fuzz.py, moved here unchanged:
 A LANE is a generator of (shapes, tris, mats, cam, rd, sd, expected, extra): expected = (scene class, textured) the library
 must report for the dispatch (Tracer.last_trace_class / last_trace_textured), BY CONSTRUCTION of the lane; extra = what the
 runner needs besides (acceleration mode, textures, the near-miss edit). expected_class() is the independent restatement of
-csrc/srt_abi.hip scene_class() from the rules (block building, one group, LDS fit, thresholds by their definition); the tests
+csrc/srt_abi.hip scene_class() from the rules (block building as csrc/scene_prep.cpp does it, one group, LDS fit, thresholds by their definition); the tests
 demand lane intention == restatement == library.
 
   class1..class4  one per entry of device_types.h SRT_SCENE_CLASS_LIST, everything else random; the hostile flavour draws only

@@ -1,4 +1,4 @@
-"""CPU: the integer thresholds srt_update_scene puts in place of the material probabilities (csrc/srt_abi.hip
+"""CPU: the integer thresholds srt_update_scene puts in place of the material probabilities (csrc/scene_prep.cpp
 bernoulli_threshold, exported host-only as srt_bernoulli_threshold_host) against their definition in numpy float32:
 
     u(r) = float32(uint32 r) * float32(2^-32)        what the kernel's random_float makes of the generator's output r
