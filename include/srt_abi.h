@@ -237,6 +237,15 @@ int srt_read_gathered(srt_tracer *t, float *canvas_out, uint8_t *argb_out);
  * float4, rank-major; image: height x width float4); synchronous. For callers that gather by other
  * means, and for tests. */
 int srt_unpermute_device(const void *gathered, void *image, int width, int height, int world, int rows_per_block);
+/* The same step for a frame gathered with the denoiser's inputs (srt_group_set_denoise below). Every rank's slot of
+ * `gathered` holds four planes of plane = padded_rows * width pixels back to back: its canvas rows, normal_depth and
+ * albedo_hits (float4 per pixel each) and moments (one float per pixel, the plane padded to a multiple of four floats, so
+ * that every slot starts on 16 bytes): srt_partition_planes_floats() = 12 * plane + round_up(plane, 4) floats per rank
+ * (host only; -1 on bad arguments). ONE kernel launch puts all four back in image order: canvas, normal_depth,
+ * albedo_hits = height x width float4, moments = height x width floats; synchronous. */
+long long srt_partition_planes_floats(int width, int height, int world, int rows_per_block);
+int srt_unpermute_planes_device(const void *gathered, void *canvas, void *normal_depth, void *albedo_hits, void *moments, int width, int height,
+                                int world, int rows_per_block);
 
 /* One process driving several GPUs -- what a front-end that keeps the reference's single `Tracer`
  * object needs (host/tracer.hpp: Tracer(width, height, n_devices)). The group owns one handle per
@@ -266,6 +275,29 @@ int srt_group_trace_and_gather(srt_group *g, const srt_render_data *options); /*
 int srt_group_render(srt_group *g, const srt_render_data *options, uint32_t ticks_stopped, uint8_t *argb_out);
 int srt_group_read_canvas(srt_group *g, float *rgba_out); /* the gathered canvas, height*width float4 */
 int srt_group_get_counters(srt_group *g, srt_counters *out); /* summed over the devices */
+/* The denoiser (below: srt_set_denoise, srt_set_denoise_temporal) on a group. Semantics, validation and error codes are
+ * those of the per-handle calls of the same names; the filtered frame equals the single-device one bit for bit. While it is
+ * on, every member accumulates the guide sums and moments of its OWN rows beside its canvas rows, in one allocation; the
+ * frame is still collected by one gather per member (52 B per pixel instead of 16) and ONE unpermute launch on the
+ * group's first device, where filter, history (two sets, there only) and counts live. srt_group_render resolves through
+ * the filter (K = 0: the plain resolve's bytes); srt_group_clear_canvas makes the frame being cleared the history when
+ * something was traced and zeroes every member's sums and the counts. Turning the denoiser on, or changing
+ * feature_samples, clears the canvas and the sums on every member. The history is dropped by
+ * srt_group_reset_denoise_history, srt_group_set_skybox, the three srt_group_set_*texture* calls, an
+ * srt_group_update_scene with other bytes than the previous one's, and by turning the denoiser or temporal off.
+ * srt_group_resolve_denoised: after srt_group_trace_and_gather, asynchronous on the first device. The read-backs block;
+ * srt_group_read_denoise_inputs returns what the last srt_group_trace_and_gather / srt_group_render collected.
+ * The per-handle rules stand: srt_set_denoise on a member (srt_group_tracer) of a group of more than one still returns
+ * SRT_ERR_STATE, and while the group's denoiser is on a member refuses srt_set_partition, srt_bind_canvas and
+ * srt_set_denoise (SRT_ERR_STATE). Not carried over: object motion (srt_set_denoise_object_motion), srt_render_pipelined on
+ * a member, and the one-process-per-GPU path (srt_gather / srt_resolve_gathered stay plain resolves). */
+int srt_group_set_denoise(srt_group *g, const srt_denoise_params *params);
+int srt_group_set_denoise_temporal(srt_group *g, const srt_temporal_params *params);
+int srt_group_reset_denoise_history(srt_group *g);
+int srt_group_resolve_denoised(srt_group *g, uint32_t ticks_stopped);
+int srt_group_read_denoised(srt_group *g, float *rgba_out);
+int srt_group_read_denoise_inputs(srt_group *g, float *normal_depth, float *albedo_hits, float *moments, uint32_t counts[2]);
+int srt_group_read_denoise_history(srt_group *g, float *colour_count, float *moments, float *guide, srt_render_data *camera, int *valid);
 
 /* ---- frame pipeline for the interactive loop (new; src/main.cpp:277-337) ----------- */
 
@@ -289,8 +321,8 @@ int srt_pipeline_flush(srt_tracer *t, uint8_t *argb_out, long long *frame_delive
  *     lum(c) = 0.2126 r + 0.7152 g + 0.0722 b;
  * and the render calls resolve through the filter instead of the plain resolve. The canvas itself is
  * bit-for-bit what it is with the denoiser off; the filter is outside the parity contract (fast exp / pow).
- * Not available on a partitioned handle (srt_set_partition world > 1) or through srt_group_* /
- * srt_resolve_gathered / srt_resolve_external. */
+ * Not available on a partitioned handle (srt_set_partition world > 1) or through srt_resolve_gathered /
+ * srt_resolve_external; a device group has calls of its own (srt_group_set_denoise above). */
 
 /* Host-only: K = 5, sigma_luminance = 4, sigma_normal = 128, sigma_depth = 1, sigma_albedo = 0.1,
  * feature_samples = 1, enable = 1. */
@@ -325,7 +357,7 @@ int srt_read_denoise_inputs(srt_tracer *t, float *normal_depth, float *albedo_hi
  * The history is dropped by srt_reset_denoise_history, turning temporal on or off, srt_set_denoise turning the denoiser
  * off (which also turns temporal off) or clearing its accumulations, srt_set_skybox, and an srt_update_scene whose
  * arrays or scene data differ in bytes from the previous call's. 112 B of device memory per pixel (two history sets),
- * allocated on the first enable. Full-frame handles only, like the denoiser. */
+ * allocated on the first enable. Full-frame handles only, like the denoiser (a device group: srt_group_set_denoise_temporal). */
 
 /* Host-only: enable = 1, history_limit = 32, normal_threshold = 0.9, depth_threshold = 0.05. */
 int srt_temporal_defaults(srt_temporal_params *out);

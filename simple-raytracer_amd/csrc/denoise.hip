@@ -162,12 +162,14 @@ int srt_denoise_clear(srt_tracer *t) {
 
 int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples) {
 	const uint32_t ns = num_samples > 0 ? (uint32_t)num_samples : 0u;
-	const uint32_t fs = (uint32_t)t->dn.feature_samples < ns ? (uint32_t)t->dn.feature_samples : ns;
+	const uint32_t want = (uint32_t)(t->gd_on ? t->gd_feature_samples : t->dn.feature_samples);
+	const uint32_t fs = want < ns ? want : ns;
 	FeatureParams fp;
 	fp.tp = p;
-	fp.normal_depth = t->dn_nd.ptr;
-	fp.albedo_hits = t->dn_ah.ptr;
-	fp.num_pixels = (uint32_t)full_pixels(t);
+	// a group member (gd_on): its own rows into the planes behind its canvas rows; the counts are the group's (srt_collect.hip)
+	fp.normal_depth = t->gd_on ? gd_normal_depth(t) : t->dn_nd.ptr;
+	fp.albedo_hits = t->gd_on ? gd_albedo_hits(t) : t->dn_ah.ptr;
+	fp.num_pixels = (uint32_t)(t->gd_on ? owned_pixels(t) : full_pixels(t));
 	fp.feature_samples = fs;
 	if (t->last_trace_textured) { // albedo textures: the texel at the first hit is the albedo (srt_texture.hip)
 		TexFeatureParams fx;
@@ -179,12 +181,46 @@ int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples
 	} else if (t->om_on) srt_launch_features_ids(fp, t->om_ids[t->om_cur].ptr, t->stream); // temporal.hip: object motion
 	else srt_launch_features(fp, t->stream);
 	SRT_HIP(t, hipGetLastError());
+	if (t->gd_on) return SRT_OK;
+	srt_denoise_count(t, p.rd, t->dn.feature_samples);
+	if (t->om_on && fs == 0) t->om_mixed = true; // a dispatch without feature rays wrote no shape indices
+	return SRT_OK;
+}
+
+void srt_denoise_count(srt_tracer *t, const srt_render_data &rd, int feature_samples) {
+	const uint32_t ns = rd.num_samples > 0 ? (uint32_t)rd.num_samples : 0u;
 	t->dn_T += 1;
 	t->dn_P += ns;
-	t->dn_F += fs;
-	t->dn_cam = p.rd;
-	if (t->om_on && fs == 0) t->om_mixed = true; // a dispatch without feature rays wrote no shape indices
+	t->dn_F += (uint32_t)feature_samples < ns ? (uint32_t)feature_samples : ns;
+	t->dn_cam = rd;
 	t->tp_fresh = false; // temporal.hip: the staging set no longer holds what is traced since the clear
+}
+
+int srt_denoise_member(srt_tracer *t, int feature_samples) {
+	SRT_HIP(t, hipSetDevice(t->device));
+	SRT_HIP(t, hipStreamSynchronize(t->stream)); // launches may still use the canvas that is about to be replaced
+	if (feature_samples <= 0) {
+		if (!t->gd_on) return SRT_OK;
+		// what is accumulated stays: the canvas rows go back where they were before (as srt_set_denoise(t, NULL) keeps the canvas)
+		const size_t rows_bytes = gd_plane_pixels(t->width, t->height, t->world, t->rows_per_block) * 16;
+		SRT_HIP(t, hipMemcpyAsync(t->gd_prev_canvas, t->gd_pack.ptr, rows_bytes < t->gd_prev_bytes ? rows_bytes : t->gd_prev_bytes, hipMemcpyDeviceToDevice, t->stream));
+		SRT_HIP(t, hipStreamSynchronize(t->stream));
+		t->canvas = t->gd_prev_canvas;
+		t->canvas_bytes = t->gd_prev_bytes;
+		t->gd_on = false;
+		return SRT_OK;
+	}
+	const size_t floats = gd_slot_floats(gd_plane_pixels(t->width, t->height, t->world, t->rows_per_block));
+	if (!t->gd_on) {
+		SRT_HIP(t, t->gd_pack.reserve(floats));
+		t->gd_prev_canvas = t->canvas;
+		t->gd_prev_bytes = t->canvas_bytes;
+		t->canvas = t->gd_pack.ptr;
+		t->canvas_bytes = floats * sizeof(float); // srt_clear_canvas zeroes the canvas rows and the three planes in one fill
+		t->gd_on = true;
+	}
+	t->gd_feature_samples = feature_samples;
+	SRT_HIP(t, hipMemsetAsync(t->canvas, 0, t->canvas_bytes, t->stream));
 	return SRT_OK;
 }
 
@@ -267,6 +303,7 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 	if (!params_ok(*params))
 		return fail(t, SRT_ERR_INVALID, "srt_set_denoise: iterations 0..8, feature_samples 1..64, sigmas finite and > 0, reserved 0");
 	if (t->world > 1) return fail(t, SRT_ERR_STATE, "srt_set_denoise: not available on a partitioned handle (srt_set_partition world > 1)");
+	if (t->gd_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise: the handle's group has its denoiser on (srt_group_set_denoise)");
 	SRT_HIP(t, hipSetDevice(t->device));
 	const size_t px = full_pixels(t);
 	SRT_HIP(t, t->dn_nd.reserve(px * 4));

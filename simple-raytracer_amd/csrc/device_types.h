@@ -240,12 +240,14 @@ struct ResolveParams {
 
 /* Denoiser guide buffers (kernels.hip srt_features_kernel): the primary hits of samples 0 .. feature_samples - 1 of the
  * dispatch `tp` describes, added per pixel into normal_depth {sum of front-facing normals, sum of t over hits} and
- * albedo_hits {sum of material colours, sky = (1,1,1); hits}. Full frame only (world == 1). */
+ * albedo_hits {sum of material colours, sky = (1,1,1); hits}. One lane per OWNED pixel of the handle's packed rows, as the
+ * canvas: the full frame (world == 1), or a device group member's rows (tp.rank / world / rows_per_block; srt_internal.h
+ * "group denoiser"), whose rays are those of the global pixel. */
 struct FeatureParams {
 	TraceParams tp; /* the scene buffers and camera set-up of the dispatch, as srt_trace fills them */
 	float *normal_depth;
 	float *albedo_hits;
-	uint32_t num_pixels;
+	uint32_t num_pixels;      /* owned pixels: normal_depth and albedo_hits hold that many float4 */
 	uint32_t feature_samples; /* min(feature_samples, num_samples), > 0 */
 };
 

@@ -9,8 +9,18 @@
 	__shared__ uint32_t region_ctr[2 * SRT_REGION_MAX]; // (development builds: the shared helpers count regions; nobody reads these)
 #endif
 	const int width = p.rd.width;
-	const uint32_t lrow = (__umulhi(q, p.width_magic) + q) >> p.width_shift; // q / width (full frame: the pixel id is q)
-	const int px = (int)(q - lrow * (uint32_t)width), py = (int)lrow;
+	// q is the lane's pixel in the handle's packed rows (fp.num_pixels = owned pixels). Full frame: that is the pixel id. A
+	// member of a device group (world != 1) finds the global y of its packed row as srt_trace_kernel's CAMERA does; seed,
+	// jitter and camera ray below come from the global pixel id, the sums go to the packed place q.
+	const uint32_t lrow = (__umulhi(q, p.width_magic) + q) >> p.width_shift; // q / width
+	const int px = (int)(q - lrow * (uint32_t)width);
+	int py = (int)lrow;
+	uint32_t id = q;
+	if (p.world != 1) {
+		const uint32_t lb = (__umulhi(lrow, p.rpb_magic) + lrow) >> p.rpb_shift;
+		py = (int)((lb * (uint32_t)p.world + (uint32_t)p.rank) * (uint32_t)p.rows_per_block + (lrow - lb * (uint32_t)p.rows_per_block));
+		id = (uint32_t)px + (uint32_t)py * (uint32_t)width;
+	}
 	const uint32_t ns = (uint32_t)p.rd.num_samples;
 	const f3 c0 = mk(p.rd.camera_to_world[0].x, p.rd.camera_to_world[0].y, p.rd.camera_to_world[0].z);
 	const f3 c1 = mk(p.rd.camera_to_world[1].x, p.rd.camera_to_world[1].y, p.rd.camera_to_world[1].z);
@@ -25,7 +35,7 @@
 #endif
 	for (uint32_t sample = 0; sample < fp.feature_samples; sample++) {
 		// ---- camera ray: srt_trace_kernel CAMERA ----
-		uint32_t seed = (sample + q * ns) * p.rd.time * 5304u;
+		uint32_t seed = (sample + id * ns) * p.rd.time * 5304u;
 		const float ndc_x = div_by_rcp((float)px + random_float(seed), p.f_width, p.inv_f_width);
 		const float ndc_y = div_by_rcp((float)py + random_float(seed), p.f_height, p.inv_f_height);
 		const float sx = ((2.f * ndc_x - 1.f) * p.rd.aspect_ratio) * p.rd.fov_scale;

@@ -42,6 +42,19 @@ int srt_fail(srt_tracer *t, int code, const std::string &msg) {
 }
 
 
+void srt_scene_bytes(std::vector<uint8_t> &bytes, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
+                     const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
+	const size_t nb[4] = {n_shapes * sizeof(srt_shape), n_triangles * sizeof(srt_triangle), n_materials * sizeof(srt_material), sizeof(srt_scene_data)};
+	const void *src[4] = {shapes, triangles, materials, scene};
+	bytes.resize(32 + nb[0] + nb[1] + nb[2] + nb[3]);
+	memcpy(bytes.data(), nb, 32);
+	size_t o = 32;
+	for (int k = 0; k < 4; k++) {
+		if (nb[k]) memcpy(bytes.data() + o, src[k], nb[k]);
+		o += nb[k];
+	}
+}
+
 extern "C" {
 
 const char *srt_version(void) {
@@ -171,6 +184,7 @@ void srt_destroy(srt_tracer *t) {
 	if (t->own_stream) (void)hipStreamSynchronize(t->own_stream);
 	srt_collect_release(t);
 	t->canvas_own.release();
+	t->gd_pack.release();
 	t->argb.release();
 	t->shapes.release();
 	t->runs.release();
@@ -242,17 +256,7 @@ int srt_update_scene(srt_tracer *t, const srt_shape *shapes, size_t n_shapes, co
 		// the denoiser's history (temporal.hip) survives only a call with the same bytes as the previous one: the front-end
 		// calls this after every clear, and without object motion vectors a moved or edited object starts from scratch
 		std::vector<uint8_t> bytes;
-		if (t && scene) {
-			const size_t nb[4] = {n_shapes * sizeof(srt_shape), n_triangles * sizeof(srt_triangle), n_materials * sizeof(srt_material), sizeof(srt_scene_data)};
-			const void *src[4] = {shapes, triangles, materials, scene};
-			bytes.resize(32 + nb[0] + nb[1] + nb[2] + nb[3]);
-			memcpy(bytes.data(), nb, 32);
-			size_t o = 32;
-			for (int k = 0; k < 4; k++) {
-				if (nb[k]) memcpy(bytes.data() + o, src[k], nb[k]);
-				o += nb[k];
-			}
-		}
+		if (t && scene) srt_scene_bytes(bytes, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
 		const int rc = update_scene_impl(t, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
 		if (t && t->om_on) { // temporal.hip: object motion compares with the history's scene and keeps what only moved
 			const int mrc = srt_motion_update_scene(t, bytes, rc);
@@ -586,10 +590,11 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 	rp.num_steps = ticks_stopped;
 	// With the denoiser on, the reductions also collect the per-pixel moments and the render calls resolve through the filter
 	// after the feature pass (below), so no reduction resolves.
-	const bool denoise = t->dn_on;
+	// A member of a group whose denoiser is on (gd_on) does the same for its own rows; the group's resolver handle filters.
+	const bool denoise = t->dn_on || t->gd_on;
 	auto launch_reduce = [&](uint8_t *argb) {
 		if (denoise) {
-			rp.moments = t->dn_mom.ptr;
+			rp.moments = t->gd_on ? gd_moments(t) : t->dn_mom.ptr;
 			srt_launch_reduce_moments(rp, t->stream);
 		} else {
 			rp.argb = argb;
@@ -688,8 +693,17 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 	}
 	if (denoise) {
 		int rc = srt_denoise_after_trace(t, p, ns);
-		if (rc == SRT_OK && fused_argb) rc = srt_denoise_filter(t, ticks_stopped, fused_argb);
+		if (rc == SRT_OK && fused_argb && t->dn_on) rc = srt_denoise_filter(t, ticks_stopped, fused_argb);
 		if (rc) return rc;
+		if (fused_argb && !t->dn_on) { // a group member rendered on its own: its rows unfiltered (the group's resolver filters whole frames)
+			ResolveParams rs;
+			rs.canvas = t->canvas;
+			rs.argb = fused_argb;
+			rs.num_steps = ticks_stopped;
+			rs.num_pixels = (uint32_t)pixels;
+			srt_launch_resolve(rs, t->stream);
+			SRT_HIP(t, hipGetLastError());
+		}
 	}
 	if (timed) SRT_HIP(t, hipEventRecord(t->ev_t1, t->stream));
 	t->have_trace_ev = timed;
@@ -880,6 +894,7 @@ int srt_device_buffers(srt_tracer *t, void **canvas, size_t *canvas_bytes, void 
 
 int srt_bind_canvas(srt_tracer *t, void *device_canvas, size_t bytes) {
 	if (!t) return SRT_ERR_INVALID;
+	if (t->gd_on) return fail(t, SRT_ERR_STATE, "srt_bind_canvas: the handle's group has its denoiser on: the canvas lives in the member's gather buffer (srt_group_set_denoise(g, NULL) first)");
 	SRT_HIP(t, hipSetDevice(t->device));
 	SRT_HIP(t, hipStreamSynchronize(t->stream));
 	if (!device_canvas) {
@@ -905,6 +920,7 @@ int srt_set_partition(srt_tracer *t, int rank, int world, int rows_per_block) {
 	if (!t) return SRT_ERR_INVALID;
 	if (world < 1 || rank < 0 || rank >= world || rows_per_block < 1)
 		return fail(t, SRT_ERR_INVALID, "srt_set_partition: need 0 <= rank < world and rows_per_block >= 1");
+	if (t->gd_on) return fail(t, SRT_ERR_STATE, "srt_set_partition: the handle's group has its denoiser on (srt_group_set_denoise(g, NULL) first)");
 	if (world > 1 && t->tp_on) return fail(t, SRT_ERR_STATE, "srt_set_partition: temporal reprojection works on the full frame only (srt_set_denoise_temporal(t, NULL) first)");
 	if (world > 1 && t->dn_on) return fail(t, SRT_ERR_STATE, "srt_set_partition: the denoiser works on the full frame only (srt_set_denoise(t, NULL) first)");
 	SRT_HIP(t, hipSetDevice(t->device));

@@ -118,6 +118,40 @@ __global__ __launch_bounds__(256) void srt_unpermute_kernel(const float4 *__rest
 	}
 }
 
+// The same for a frame gathered with the denoiser's inputs (srt_group_set_denoise): every rank's slot of `gathered` is
+// gd_slot_floats(plane) floats -- three float4 planes of `plane` = padded_rows * width pixels (canvas rows, normal_depth,
+// albedo_hits) and one float plane (moments) -- and ONE pass puts all four back in image order, a pixel's 52 bytes per lane.
+__global__ __launch_bounds__(256) void srt_unpermute_planes_kernel(const float *__restrict__ gathered, float4 *__restrict__ canvas,
+                                                                   float4 *__restrict__ normal_depth, float4 *__restrict__ albedo_hits,
+                                                                   float *__restrict__ moments, int width, int height, int world, int rpb,
+                                                                   int padded_rows, size_t slot_floats) {
+	const size_t n = (size_t)width * height, plane = (size_t)padded_rows * width;
+	for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+		const int y = (int)(i / width), x = (int)(i - (size_t)y * width);
+		const int blk = y / rpb, r = blk % world, lb = blk / world;
+		const int lr = lb * rpb + (y - blk * rpb);
+		const float *__restrict__ slot = gathered + (size_t)r * slot_floats;
+		const float4 *__restrict__ slot4 = reinterpret_cast<const float4 *>(slot);
+		const size_t j = (size_t)lr * width + x; // < plane: lr < padded_rows
+		canvas[i] = slot4[j];
+		normal_depth[i] = slot4[plane + j];
+		albedo_hits[i] = slot4[2 * plane + j];
+		moments[i] = slot[12 * plane + j];
+	}
+}
+
+int launch_unpermute_planes(const float *gathered, float *canvas, float *nd, float *ah, float *mom, int width, int height, int world, int rpb,
+                            hipStream_t stream) {
+	const int padded = srt_partition_padded_rows(height, world, rpb);
+	const size_t n = (size_t)width * height;
+	unsigned blocks = (unsigned)((n + 255) / 256);
+	if (blocks > 8192) blocks = 8192;
+	hipLaunchKernelGGL(srt_unpermute_planes_kernel, dim3(blocks), dim3(256), 0, stream, gathered, reinterpret_cast<float4 *>(canvas),
+	                   reinterpret_cast<float4 *>(nd), reinterpret_cast<float4 *>(ah), mom, width, height, world, rpb, padded,
+	                   gd_slot_floats((size_t)padded * width));
+	return hipGetLastError() == hipSuccess ? SRT_OK : SRT_ERR_HIP;
+}
+
 int unpermute_on_root(srt_tracer *t, SrtCollect *c) {
 	const int padded = srt_partition_padded_rows(t->height, t->world, t->rows_per_block);
 	const size_t n = (size_t)t->width * t->height;
@@ -216,6 +250,25 @@ int srt_unpermute_device(const void *gathered, void *image, int width, int heigh
 	return SRT_OK;
 }
 
+/* test hook: the multi-plane unpermute kernel alone on caller-owned device buffers (gathered: world slots of
+ * srt_partition_planes_floats() floats; canvas, normal_depth, albedo_hits: height x width float4; moments: height x width
+ * float), on the NULL stream, synchronous */
+int srt_unpermute_planes_device(const void *gathered, void *canvas, void *normal_depth, void *albedo_hits, void *moments, int width, int height,
+                                int world, int rows_per_block) {
+	if (!gathered || !canvas || !normal_depth || !albedo_hits || !moments || width <= 0 || height <= 0 || world < 1 || rows_per_block < 1)
+		return SRT_ERR_INVALID;
+	if (launch_unpermute_planes(static_cast<const float *>(gathered), static_cast<float *>(canvas), static_cast<float *>(normal_depth),
+	                            static_cast<float *>(albedo_hits), static_cast<float *>(moments), width, height, world, rows_per_block, nullptr) != SRT_OK ||
+	    hipDeviceSynchronize() != hipSuccess)
+		return SRT_ERR_HIP;
+	return SRT_OK;
+}
+
+long long srt_partition_planes_floats(int width, int height, int world, int rows_per_block) {
+	if (width <= 0 || height < 0 || world < 1 || rows_per_block < 1) return -1;
+	return (long long)gd_slot_floats(gd_plane_pixels(width, height, world, rows_per_block));
+}
+
 int srt_resolve_gathered(srt_tracer *t, uint32_t ticks_stopped) {
 	if (!t) return SRT_ERR_INVALID;
 	SrtCollect *c = t->collect;
@@ -264,6 +317,17 @@ struct srt_group {
 	// what a one-GPU box can run of the N > 1 path (tests/test_gpu_collect.py).
 	bool loopback = false;
 	std::vector<hipEvent_t> copied; // loopback: member i's canvas has arrived in the root's buffer
+	// The denoiser on a group (srt_group_set_denoise). The members accumulate the filter's inputs for their own rows
+	// (srt_internal.h "group denoiser"), one collective brings canvas rows and inputs to the root, one unpermute puts them into
+	// the full-frame state of `resolver`: a handle of the whole frame on the root device and the root's stream, made when the
+	// denoiser is first asked for. Its canvas is the root's SrtCollect::full, its dn_nd / dn_ah / dn_mom the other planes, its
+	// counts and camera the group's, its history buffers the group's only ones -- and filter, temporal set-up and commit,
+	// validation and the read-backs are the single handle's code run on it.
+	srt_tracer *resolver = nullptr;
+	bool dn_on = false;
+	int dn_feature_samples = 0;
+	hipEvent_t unpermuted = nullptr;  // loopback: the root has read the gather buffer (the next frame's copies wait for it)
+	std::vector<uint8_t> scene_bytes; // the last srt_group_update_scene's (the history survives an unchanged scene)
 	std::string err;
 };
 
@@ -271,6 +335,40 @@ namespace {
 int gfail(srt_group *g, int code, const std::string &msg) {
 	if (g) g->err = msg;
 	return code;
+}
+
+// the group's full-frame handle for the denoiser, made at first use; it works on the root's stream as that is bound now
+srt_tracer *resolver_of(srt_group *g) {
+	srt_tracer *root = g->t[0];
+	if (!g->resolver) {
+		srt_tracer *r = nullptr;
+		if (srt_create(g->width, g->height, root->device, &r) != SRT_OK) {
+			g->err = std::string("srt_group: the denoiser's handle on the root device: ") + srt_last_error(nullptr);
+			return nullptr;
+		}
+		// its canvas is the gathered, unpermuted one (bound the way srt_bind_canvas does); its own is not needed
+		SrtCollect *rc = root->collect;
+		const size_t n = (size_t)g->width * g->height;
+		if (hipSetDevice(root->device) != hipSuccess || rc->full.reserve(n * 4) != hipSuccess ||
+		    hipMemsetAsync(rc->full.ptr, 0, n * 16, root->stream) != hipSuccess ||
+		    (g->loopback && hipEventCreateWithFlags(&g->unpermuted, hipEventDisableTiming) != hipSuccess)) {
+			(void)hipGetLastError();
+			srt_destroy(r);
+			g->err = "srt_group: the denoiser's buffers on the root device";
+			return nullptr;
+		}
+		r->canvas_own.release();
+		r->canvas = rc->full.ptr;
+		r->canvas_bytes = n * 16;
+		g->resolver = r;
+	}
+	g->resolver->stream = root->stream;
+	return g->resolver;
+}
+
+// a history-dropping call reached the members: the group's history saw the old sky / textures / scene
+void drop_history(srt_group *g) {
+	if (g->resolver) srt_temporal_drop(g->resolver);
 }
 } // namespace
 
@@ -280,6 +378,13 @@ void srt_group_destroy(srt_group *g) {
 	if (!g) return;
 	for (hipEvent_t e : g->copied)
 		if (e) (void)hipEventDestroy(e);
+	if (g->resolver) { // (its canvas is the root's gathered image: gone with the root below)
+		(void)hipSetDevice(g->resolver->device);
+		if (!g->t.empty() && g->t[0]) (void)hipStreamSynchronize(g->t[0]->stream);
+		g->resolver->canvas = nullptr;
+		srt_destroy(g->resolver);
+	}
+	if (g->unpermuted) (void)hipEventDestroy(g->unpermuted);
 	for (srt_tracer *t : g->t) {
 		if (t && t->collect && t->collect->comm && rccl().lib) {
 			(void)hipSetDevice(t->device);
@@ -383,24 +488,28 @@ srt_tracer *srt_group_tracer(srt_group *g, int i) { return (g && i >= 0 && i < (
 int srt_group_set_skybox(srt_group *g, const float *rgba, int width, int height) {
 	if (!g) return SRT_ERR_INVALID;
 	SRT_EACH(g, srt_set_skybox(t_, rgba, width, height));
+	drop_history(g); // (as the per-handle call does for its own)
 	return SRT_OK;
 }
 
 int srt_group_set_textures(srt_group *g, const srt_texture_desc *descs, size_t n) {
 	if (!g) return SRT_ERR_INVALID;
 	SRT_EACH(g, srt_set_textures(t_, descs, n));
+	drop_history(g); // (as the per-handle call does for its own)
 	return SRT_OK;
 }
 
 int srt_group_set_material_textures(srt_group *g, const srt_material_texture *bindings, size_t n_materials) {
 	if (!g) return SRT_ERR_INVALID;
 	SRT_EACH(g, srt_set_material_textures(t_, bindings, n_materials));
+	drop_history(g); // (as the per-handle call does for its own)
 	return SRT_OK;
 }
 
 int srt_group_set_triangle_uvs(srt_group *g, const float *uv, size_t n_triangles) {
 	if (!g) return SRT_ERR_INVALID;
 	SRT_EACH(g, srt_set_triangle_uvs(t_, uv, n_triangles));
+	drop_history(g); // (as the per-handle call does for its own)
 	return SRT_OK;
 }
 
@@ -416,12 +525,34 @@ int srt_group_update_scene(srt_group *g, const srt_shape *shapes, size_t n_shape
 	// the scene is replicated: prepared on the host once (hierarchy build, shape blocks, thresholds), uploaded to every member
 	size_t who = 0;
 	const int rc = srt_update_scene_many(g->t.data(), g->t.size(), shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene, &who);
+	// the denoiser's history survives only a call with the same bytes as the previous one, as on a single handle (srt_update_scene)
+	try {
+		std::vector<uint8_t> bytes;
+		if (scene) srt_scene_bytes(bytes, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
+		if (rc != SRT_OK || bytes.empty() || bytes != g->scene_bytes) drop_history(g);
+		g->scene_bytes.swap(bytes);
+	} catch (...) {
+		drop_history(g);
+		g->scene_bytes.clear();
+		if (rc == SRT_OK) return gfail(g, SRT_ERR_INVALID, "out of host memory");
+	}
 	if (rc != SRT_OK) return gfail(g, rc, srt_last_error(g->t[who < g->t.size() ? who : 0]));
 	return SRT_OK;
 }
 
 int srt_group_clear_canvas(srt_group *g) {
 	if (!g) return SRT_ERR_INVALID;
+	if (g->dn_on) {
+		// what srt_clear_canvas does for a single handle: the frame being cleared becomes the history when something was traced
+		// (the commit reads the gathered planes on the root), then the sums -- each member's canvas rows and planes are one
+		// fill -- and the counts start again
+		srt_tracer *r = resolver_of(g);
+		if (!r) return SRT_ERR_HIP;
+		if (hipSetDevice(r->device) != hipSuccess) return gfail(g, SRT_ERR_HIP, "srt_group_clear_canvas: hipSetDevice");
+		const int rc = srt_temporal_commit(r);
+		if (rc != SRT_OK) return gfail(g, rc, srt_last_error(r));
+		r->dn_T = r->dn_P = r->dn_F = 0;
+	}
 	SRT_EACH(g, srt_clear_canvas(t_));
 	return SRT_OK;
 }
@@ -429,17 +560,33 @@ int srt_group_clear_canvas(srt_group *g) {
 // trace on every device, ONE gather to device 0 of the group, unpermute there; everything asynchronous
 int srt_group_trace_and_gather(srt_group *g, const srt_render_data *options) {
 	if (!g) return SRT_ERR_INVALID;
+	srt_tracer *res = g->dn_on ? resolver_of(g) : nullptr;
+	if (g->dn_on && !res) return SRT_ERR_HIP;
 	SRT_EACH(g, srt_trace(t_, options));
 	srt_tracer *root = g->t[0];
 	const int world = (int)g->t.size();
 	const int padded = srt_partition_padded_rows(g->height, world, g->rpb);
-	const size_t count = (size_t)padded * g->width * 4;
+	// floats every rank sends: its padded canvas rows; with the denoiser on its whole gd_pack, the canvas rows and the filter's
+	// inputs behind them (52 B per pixel instead of 16) -- still one collective
+	const size_t count = res ? gd_slot_floats((size_t)padded * g->width) : (size_t)padded * g->width * 4;
+	if (res) srt_denoise_count(res, *options, g->dn_feature_samples); // the counts of the dispatch every member has just run
 	SrtCollect *rc = root->collect;
+	// put the gathered frame back in image order on the root: the canvas alone, or all four planes into the resolver's state
+	auto unpermute = [&]() {
+		if (!res) return unpermute_on_root(root, rc);
+		if (launch_unpermute_planes(rc->gathered.ptr, rc->full.ptr, res->dn_nd.ptr, res->dn_ah.ptr, res->dn_mom.ptr, g->width, g->height, world, g->rpb,
+		                            root->stream) != SRT_OK)
+			return fail(root, SRT_ERR_HIP, "srt_group: unpermute of the gathered planes");
+		rc->have_full = true;
+		return (int)SRT_OK;
+	};
 	if (hipSetDevice(root->device) != hipSuccess || rc->gathered.reserve(count * (size_t)world) != hipSuccess)
 		return gfail(g, SRT_ERR_HIP, "srt_group: gather buffer on the root device");
 	if (g->loopback) {
 		for (int i = 0; i < world; i++) {
 			srt_tracer *t = g->t[i];
+			// (denoiser: a resolve may be enqueued behind the previous frame's unpermute, so the root can still be reading the buffer)
+			if (res && i > 0 && hipStreamWaitEvent(t->stream, g->unpermuted, 0) != hipSuccess) return gfail(g, SRT_ERR_HIP, "srt_group: loopback wait");
 			if (hipSetDevice(t->device) != hipSuccess ||
 			    hipMemcpyAsync(rc->gathered.ptr + (size_t)i * count, t->canvas, count * sizeof(float), hipMemcpyDeviceToDevice, t->stream) != hipSuccess ||
 			    hipEventRecord(g->copied[i], t->stream) != hipSuccess)
@@ -448,8 +595,9 @@ int srt_group_trace_and_gather(srt_group *g, const srt_render_data *options) {
 		(void)hipSetDevice(root->device);
 		for (int i = 1; i < world; i++)
 			if (hipStreamWaitEvent(root->stream, g->copied[i], 0) != hipSuccess) return gfail(g, SRT_ERR_HIP, "srt_group: loopback wait");
-		const int u = unpermute_on_root(root, rc);
+		const int u = unpermute();
 		if (u != SRT_OK) return gfail(g, u, srt_last_error(root));
+		if (res && hipEventRecord(g->unpermuted, root->stream) != hipSuccess) return gfail(g, SRT_ERR_HIP, "srt_group: loopback event");
 		return SRT_OK;
 	}
 	int r = rccl().GroupStart();
@@ -461,7 +609,7 @@ int srt_group_trace_and_gather(srt_group *g, const srt_render_data *options) {
 	const int r2 = rccl().GroupEnd();
 	if (r != kNcclSuccess || r2 != kNcclSuccess) return gfail(g, SRT_ERR_HIP, std::string("srt_group: ncclGather: ") + rccl().GetErrorString(r != kNcclSuccess ? r : r2));
 	(void)hipSetDevice(root->device);
-	const int u = unpermute_on_root(root, rc);
+	const int u = unpermute();
 	if (u != SRT_OK) return gfail(g, u, srt_last_error(root));
 	return SRT_OK;
 }
@@ -473,9 +621,15 @@ int srt_group_render(srt_group *g, const srt_render_data *options, uint32_t tick
 	int rc = srt_group_trace_and_gather(g, options);
 	if (rc != SRT_OK) return rc;
 	srt_tracer *root = g->t[0];
-	rc = srt_resolve_gathered(root, ticks_stopped);
-	if (rc == SRT_OK) rc = srt_read_gathered(root, nullptr, argb_out);
-	if (rc != SRT_OK) return gfail(g, rc, srt_last_error(root));
+	if (g->dn_on) { // through the filter on the root (K = 0: the plain resolve's bytes)
+		rc = srt_resolve_denoised(g->resolver, ticks_stopped);
+		if (rc == SRT_OK) rc = srt_read_argb(g->resolver, argb_out);
+		if (rc != SRT_OK) return gfail(g, rc, srt_last_error(g->resolver));
+	} else {
+		rc = srt_resolve_gathered(root, ticks_stopped);
+		if (rc == SRT_OK) rc = srt_read_gathered(root, nullptr, argb_out);
+		if (rc != SRT_OK) return gfail(g, rc, srt_last_error(root));
+	}
 	for (size_t i = 1; i < g->t.size(); i++) { // every device has finished its part before the call returns
 		rc = srt_synchronize(g->t[i]);
 		if (rc != SRT_OK) return gfail(g, rc, srt_last_error(g->t[i]));
@@ -487,6 +641,80 @@ int srt_group_read_canvas(srt_group *g, float *rgba_out) {
 	if (!g) return SRT_ERR_INVALID;
 	const int rc = srt_read_gathered(g->t[0], rgba_out, nullptr);
 	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+// ---- the denoiser on a group: the per-handle calls on the group's full-frame handle, the switch carried to the members ----
+#define SRT_ON_RESOLVER(g, r, expr)                                  \
+	do {                                                             \
+		const int rc_ = (expr);                                      \
+		if (rc_ != SRT_OK) return gfail((g), rc_, srt_last_error(r)); \
+	} while (0)
+
+int srt_group_set_denoise(srt_group *g, const srt_denoise_params *params) {
+	if (!g) return SRT_ERR_INVALID;
+	if (!params || !params->enable) {
+		if (g->resolver) SRT_ON_RESOLVER(g, g->resolver, srt_set_denoise(g->resolver, nullptr)); // (drops the history, temporal off)
+		if (g->dn_on) SRT_EACH(g, srt_denoise_member(t_, 0));
+		g->dn_on = false;
+		return SRT_OK;
+	}
+	srt_tracer *r = resolver_of(g);
+	if (!r) return SRT_ERR_HIP;
+	const bool clear = !g->dn_on || params->feature_samples != g->dn_feature_samples;
+	SRT_ON_RESOLVER(g, r, srt_set_denoise(r, params)); // validation, the full-frame buffers, and on `clear` the root's sums and history
+	if (clear) SRT_EACH(g, srt_denoise_member(t_, params->feature_samples)); // canvas rows and sums of every member: zero
+	g->dn_on = true;
+	g->dn_feature_samples = params->feature_samples;
+	return SRT_OK;
+}
+
+int srt_group_set_denoise_temporal(srt_group *g, const srt_temporal_params *params) {
+	if (!g) return SRT_ERR_INVALID;
+	if ((!params || !params->enable) && !g->resolver) return SRT_OK;
+	srt_tracer *r = resolver_of(g);
+	if (!r) return SRT_ERR_HIP;
+	SRT_ON_RESOLVER(g, r, srt_set_denoise_temporal(r, params));
+	return SRT_OK;
+}
+
+int srt_group_reset_denoise_history(srt_group *g) {
+	if (!g) return SRT_ERR_INVALID;
+	drop_history(g);
+	return SRT_OK;
+}
+
+int srt_group_resolve_denoised(srt_group *g, uint32_t ticks_stopped) {
+	if (!g) return SRT_ERR_INVALID;
+	if (!g->dn_on) return gfail(g, SRT_ERR_STATE, "srt_group_resolve_denoised: the denoiser is off (srt_group_set_denoise)");
+	srt_tracer *r = resolver_of(g);
+	if (!r) return SRT_ERR_HIP;
+	SRT_ON_RESOLVER(g, r, srt_resolve_denoised(r, ticks_stopped));
+	return SRT_OK;
+}
+
+int srt_group_read_denoised(srt_group *g, float *rgba_out) {
+	if (!g) return SRT_ERR_INVALID;
+	if (!rgba_out) return gfail(g, SRT_ERR_INVALID, "srt_group_read_denoised: rgba_out is NULL");
+	if (!g->resolver) return gfail(g, SRT_ERR_STATE, "srt_group_read_denoised: no filtered image (srt_group_set_denoise, then render)");
+	srt_tracer *r = resolver_of(g);
+	SRT_ON_RESOLVER(g, r, srt_read_denoised(r, rgba_out));
+	return SRT_OK;
+}
+
+int srt_group_read_denoise_inputs(srt_group *g, float *normal_depth, float *albedo_hits, float *moments, uint32_t counts[2]) {
+	if (!g) return SRT_ERR_INVALID;
+	if (!g->resolver) return gfail(g, SRT_ERR_STATE, "srt_group_read_denoise_inputs: the denoiser was never enabled");
+	srt_tracer *r = resolver_of(g);
+	SRT_ON_RESOLVER(g, r, srt_read_denoise_inputs(r, normal_depth, albedo_hits, moments, counts)); // as gathered with the last frame
+	return SRT_OK;
+}
+
+int srt_group_read_denoise_history(srt_group *g, float *colour_count, float *moments, float *guide, srt_render_data *camera, int *valid) {
+	if (!g) return SRT_ERR_INVALID;
+	if (!g->resolver) return gfail(g, SRT_ERR_STATE, "srt_group_read_denoise_history: temporal reprojection was never enabled (srt_group_set_denoise_temporal)");
+	srt_tracer *r = resolver_of(g);
+	SRT_ON_RESOLVER(g, r, srt_read_denoise_history(r, colour_count, moments, guide, camera, valid));
+	return SRT_OK;
 }
 
 int srt_group_get_counters(srt_group *g, srt_counters *out) {

@@ -122,6 +122,16 @@ struct srt_tracer {
 	std::vector<uint8_t> om_hist_scene; // scene_bytes of the history frame
 	std::vector<uint32_t> om_table;     // SRT_MOTION_WORDS per shape of the current scene: the next filter's current -> history maps
 	DevBuf<uint32_t> om_table_dev;
+	// group denoiser (srt_collect.hip srt_group_set_denoise): a member of a device group accumulates the denoiser's inputs for
+	// its OWN rows, packed as its canvas rows are. gd_pack is ONE allocation of srt_planes_slot_floats() floats that one collective
+	// sends: the canvas rows (bound as the canvas, the way srt_bind_canvas does), the normal_depth and albedo_hits planes
+	// (float4 per pixel of the padded rows each) and the moments plane. The filter runs on the group's full-frame resolver
+	// handle; dn_on stays false here, and the public per-handle rules (no denoiser on a partitioned handle) are unchanged.
+	bool gd_on = false;
+	int gd_feature_samples = 0;
+	DevBuf<float> gd_pack;
+	float *gd_prev_canvas = nullptr; // what was bound before, bound again when the group's denoiser goes off
+	size_t gd_prev_bytes = 0;
 	// albedo textures (srt_texture.hip; include/srt_abi.h). What the three setters were given lives on the host; the device
 	// tables are (re)made by srt_texture_sync when a setter or srt_update_scene has run since (tex_dirty)
 	std::vector<TexDesc> tex_images;                // srt_set_textures: the images inside tex_texels
@@ -149,6 +159,15 @@ static inline int fail(srt_tracer *t, int code, const std::string &msg) { return
 static inline size_t owned_pixels(const srt_tracer *t) { return (size_t)t->owned_rows * (size_t)t->width; }
 static inline size_t full_pixels(const srt_tracer *t) { return (size_t)t->width * (size_t)t->height; }
 
+// group denoiser: pixels of one plane of a member's gd_pack (the padded rows every rank sends), the float offsets of its four
+// planes and the floats of the whole (the moments plane is padded so that every rank's slot of the gathered buffer starts
+// on 16 bytes)
+static inline size_t gd_plane_pixels(int width, int height, int world, int rpb) { return (size_t)srt_partition_padded_rows(height, world, rpb) * (size_t)width; }
+static inline size_t gd_slot_floats(size_t plane_pixels) { return 12 * plane_pixels + ((plane_pixels + 3) & ~(size_t)3); }
+static inline float *gd_normal_depth(const srt_tracer *t) { return t->gd_pack.ptr + 4 * gd_plane_pixels(t->width, t->height, t->world, t->rows_per_block); }
+static inline float *gd_albedo_hits(const srt_tracer *t) { return t->gd_pack.ptr + 8 * gd_plane_pixels(t->width, t->height, t->world, t->rows_per_block); }
+static inline float *gd_moments(const srt_tracer *t) { return t->gd_pack.ptr + 12 * gd_plane_pixels(t->width, t->height, t->world, t->rows_per_block); }
+
 #define SRT_HIP(t, call)                                                                              \
 	do {                                                                                              \
 		hipError_t e_ = (call);                                                                       \
@@ -171,6 +190,16 @@ void srt_texture_release(srt_tracer *t);
 int srt_denoise_clear(srt_tracer *t);
 int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples);
 int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb);
+/* the counts of one dispatch of `rd` (T, P, F, the camera) added to t's: srt_denoise_after_trace's, and what a group keeps on
+ * its resolver handle for the dispatch all members have just run */
+void srt_denoise_count(srt_tracer *t, const srt_render_data &rd, int feature_samples);
+/* group denoiser, a group's way to its members (the public srt_set_denoise refuses a partitioned handle): feature_samples > 0
+ * turns the member's accumulation on (allocates gd_pack for the current partition, binds the canvas into it, zeroes all of it),
+ * 0 turns it off (the canvas rows go back to the buffer bound before) */
+int srt_denoise_member(srt_tracer *t, int feature_samples);
+/* the bytes srt_update_scene compares two scenes by (the denoiser's history survives an unchanged scene) */
+void srt_scene_bytes(std::vector<uint8_t> &bytes, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
+                     const srt_material *materials, size_t n_materials, const srt_scene_data *scene);
 /* temporal.hip: the temporal set-up over the canvas into `col` (and argb when not NULL), *guide = the guide it wrote;
  * the commit at srt_clear_canvas (before the canvas is zeroed); dropping the history */
 int srt_temporal_setup(srt_tracer *t, float4 *col, uint32_t *argb, const float4 **guide);

@@ -156,13 +156,12 @@ class Tracer {
 	/// reference's README.md:41 "future plan"); SRT_ACCEL_NONE (default) keeps the array-order scan
 	void set_acceleration(int mode) { check(group ? srt_group_set_acceleration(group, mode) : srt_set_acceleration(handle, mode)); }
 	/// The edge-aware denoiser (srt_set_denoise): iterations < 0 turns it off, else it is on with srt_denoise_defaults()
-	/// overridden by the arguments; render() / render_pipelined() then hand out the filtered image. Single-device tracers
-	/// only (throws on a Tracer over several devices: gathering the guide buffers is not built).
+	/// overridden by the arguments; render() / render_pipelined() then hand out the filtered image. On a Tracer over several
+	/// devices the members gather the filter's inputs with the frame and device 0 filters (srt_group_set_denoise): the same bytes.
 	void set_denoise(int iterations = 5, int feature_samples = 1, float sigma_luminance = 4.0f, float sigma_normal = 128.0f,
 	                 float sigma_depth = 1.0f, float sigma_albedo = 0.1f) {
-		if (group) throw std::runtime_error("Tracer::set_denoise: single-device tracers only");
 		if (iterations < 0) {
-			check(srt_set_denoise(handle, nullptr));
+			check(group ? srt_group_set_denoise(group, nullptr) : srt_set_denoise(handle, nullptr));
 			return;
 		}
 		srt_denoise_params d;
@@ -173,14 +172,13 @@ class Tracer {
 		d.sigma_normal = sigma_normal;
 		d.sigma_depth = sigma_depth;
 		d.sigma_albedo = sigma_albedo;
-		check(srt_set_denoise(handle, &d));
+		check(group ? srt_group_set_denoise(group, &d) : srt_set_denoise(handle, &d));
 	}
 	/// The denoiser's temporal reprojection (srt_set_denoise_temporal): the frame before each clear_canvas is reprojected
-	/// into the next camera and blended in. Needs set_denoise first; enable = false turns it off. Single-device tracers only.
+	/// into the next camera and blended in. Needs set_denoise first; enable = false turns it off. Several devices: the history lives on device 0.
 	void set_denoise_temporal(bool enable = true, int history_limit = 32, float normal_threshold = 0.9f, float depth_threshold = 0.05f) {
-		if (group) throw std::runtime_error("Tracer::set_denoise_temporal: single-device tracers only");
 		if (!enable) {
-			check(srt_set_denoise_temporal(handle, nullptr));
+			check(group ? srt_group_set_denoise_temporal(group, nullptr) : srt_set_denoise_temporal(handle, nullptr));
 			return;
 		}
 		srt_temporal_params p;
@@ -188,11 +186,11 @@ class Tracer {
 		p.history_limit = history_limit;
 		p.normal_threshold = normal_threshold;
 		p.depth_threshold = depth_threshold;
-		check(srt_set_denoise_temporal(handle, &p));
+		check(group ? srt_group_set_denoise_temporal(group, &p) : srt_set_denoise_temporal(handle, &p));
 	}
 	/// Object motion for the temporal stage (srt_set_denoise_object_motion): the history survives an update_scene that only
 	/// moves spheres, planes or model instances. Needs set_denoise_temporal first; the clear_canvas / update_scene / render
-	/// order of the frame loop stays as it is. Single-device tracers only.
+	/// order of the frame loop stays as it is. Single-device tracers only (a group gathers no shape indices).
 	void set_denoise_object_motion(bool enable = true) {
 		if (group) throw std::runtime_error("Tracer::set_denoise_object_motion: single-device tracers only");
 		check(srt_set_denoise_object_motion(handle, enable ? 1 : 0));

@@ -6,7 +6,8 @@
 //   srt_headless [--scene spheres|meshes|empty] [--obj f.obj]... [--stl f.stl]...
 //                [--width W --height H --spp S --bounces B --frames N --time T]
 //                [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--temporal] [--move DX]
-// --denoise K: the frames go through the edge-aware denoiser with K a-trous passes (Tracer::set_denoise; one device only)
+// --denoise K: the frames go through the edge-aware denoiser with K a-trous passes (Tracer::set_denoise; with --gpus N the
+//                members gather the filter's inputs with the frame and device 0 filters: the same bytes as on one device)
 // --temporal: with --denoise, the denoiser's temporal reprojection (Tracer::set_denoise_temporal)
 // --move DX: the camera moves by DX along x every frame and every frame clears the canvas, as the front-end does while moving
 // --move-shape I DX: with --temporal, shape I (a sphere, a plane or a model instance) moves by DX along x every frame and every

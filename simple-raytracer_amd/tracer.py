@@ -39,6 +39,9 @@ ABI_SYMBOLS = [
     "srt_set_textures", "srt_set_material_textures", "srt_set_triangle_uvs", "srt_last_trace_textured", "srt_plane_frame_host",
     "srt_texture_check_host", "srt_group_set_textures", "srt_group_set_material_textures", "srt_group_set_triangle_uvs",
     "srt_last_trace_class", "srt_bernoulli_threshold_host",
+    "srt_group_set_denoise", "srt_group_set_denoise_temporal", "srt_group_reset_denoise_history", "srt_group_resolve_denoised",
+    "srt_group_read_denoised", "srt_group_read_denoise_inputs", "srt_group_read_denoise_history", "srt_partition_planes_floats",
+    "srt_unpermute_planes_device",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -336,6 +339,17 @@ def _bind(lib):
         lib.srt_group_render.argtypes = [vp, vp, C.c_uint32, vp]
         lib.srt_group_read_canvas.argtypes = [vp, vp]
         lib.srt_group_get_counters.argtypes = [vp, C.POINTER(Counters)]
+        if hasattr(lib, "srt_group_set_denoise"):  # (an older library, SRT_LIB, in an A/B run)
+            lib.srt_group_set_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
+            lib.srt_group_set_denoise_temporal.argtypes = [vp, C.POINTER(TemporalParams)]
+            lib.srt_group_reset_denoise_history.argtypes = [vp]
+            lib.srt_group_resolve_denoised.argtypes = [vp, C.c_uint32]
+            lib.srt_group_read_denoised.argtypes = [vp, vp]
+            lib.srt_group_read_denoise_inputs.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_uint32)]
+            lib.srt_group_read_denoise_history.argtypes = [vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
+            lib.srt_partition_planes_floats.argtypes = [i, i, i, i]
+            lib.srt_partition_planes_floats.restype = C.c_longlong
+            lib.srt_unpermute_planes_device.argtypes = [vp, vp, vp, vp, vp, i, i, i, i]
         lib.srt_render_pipelined.argtypes = [vp, vp, C.c_uint32, vp, C.POINTER(C.c_longlong)]
         lib.srt_pipeline_flush.argtypes = [vp, vp, C.POINTER(C.c_longlong)]
     if hasattr(lib, "srt_set_denoise"):
@@ -375,7 +389,75 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-class Tracer:
+class _Denoise:
+    """The denoiser's calls, shared by Tracer (srt_*) and TracerGroup (srt_group_*: the same semantics on a device group).
+    self._dn(name, *args) calls the class's entry point of that name on its handle."""
+
+    def set_denoise(self, enable=True, **kw):
+        """Turn the denoiser on with srt_denoise_defaults() overridden by kw (iterations, feature_samples, sigma_luminance,
+        sigma_normal, sigma_depth, sigma_albedo), or off with enable=False."""
+        if not enable:
+            self._check(self._dn("set_denoise", None))
+            return
+        d = DenoiseParams()
+        self._check(self.lib.srt_denoise_defaults(C.byref(d)))
+        for k, v in kw.items():
+            if k not in d.as_dict() or k == "enable":
+                raise TypeError(f"set_denoise: unknown parameter {k}")
+            setattr(d, k, v)
+        self._check(self._dn("set_denoise", C.byref(d)))
+
+    def resolve_denoised(self, ticks_stopped):
+        """The filter over the current canvas into the handle's ARGB image (read_argb); asynchronous."""
+        self._check(self._dn("resolve_denoised", ticks_stopped))
+
+    def read_denoised(self):
+        """(height, width, 4) float32: the last filter result before tonemapping (r, g, b, variance)."""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._dn("read_denoised", _ptr(out)))
+        return out
+
+    def read_denoise_inputs(self):
+        """dict: normal_depth (h, w, 4), albedo_hits (h, w, 4), moments (h, w), T, P."""
+        nd = np.zeros((self.height, self.width, 4), np.float32)
+        ah = np.zeros((self.height, self.width, 4), np.float32)
+        m = np.zeros((self.height, self.width), np.float32)
+        counts = (C.c_uint32 * 2)()
+        self._check(self._dn("read_denoise_inputs", _ptr(nd), _ptr(ah), _ptr(m), counts))
+        return {"normal_depth": nd, "albedo_hits": ah, "moments": m, "T": int(counts[0]), "P": int(counts[1])}
+
+    def set_denoise_temporal(self, enable=True, **kw):
+        """Turn the denoiser's temporal reprojection on with srt_temporal_defaults() overridden by kw (history_limit,
+        normal_threshold, depth_threshold), or off with enable=False. Needs the denoiser on (set_denoise)."""
+        if not enable:
+            self._check(self._dn("set_denoise_temporal", None))
+            return
+        d = TemporalParams()
+        self._check(self.lib.srt_temporal_defaults(C.byref(d)))
+        for k, v in kw.items():
+            if k not in ("history_limit", "normal_threshold", "depth_threshold"):
+                raise TypeError(f"set_denoise_temporal: unknown parameter {k}")
+            setattr(d, k, v)
+        self._check(self._dn("set_denoise_temporal", C.byref(d)))
+
+    def reset_denoise_history(self):
+        """Drop the temporal history: the next frame is filtered as by the spatial denoiser alone."""
+        self._check(self._dn("reset_denoise_history"))
+
+    def read_denoise_history(self):
+        """dict: valid, colour (h, w, 3), count (h, w), m1, m2 (h, w), guide (h, w, 2, 4) {N, Z}, {A, cov}, camera (the history
+        frame's records.RENDER_DATA). Without a history every array is zero and valid is False."""
+        cc = np.zeros((self.height, self.width, 4), np.float32)
+        m = np.zeros((self.height, self.width, 2), np.float32)
+        g = np.zeros((self.height, self.width, 2, 4), np.float32)
+        cam = np.zeros((), R.RENDER_DATA)
+        valid = C.c_int(0)
+        self._check(self._dn("read_denoise_history", _ptr(cc), _ptr(m), _ptr(g), _ptr(cam), C.byref(valid)))
+        return {"valid": bool(valid.value), "colour": cc[..., :3], "count": cc[..., 3], "m1": m[..., 0], "m2": m[..., 1], "guide": g,
+                "camera": cam}
+
+
+class Tracer(_Denoise):
     """Mirror of the reference's `class Tracer`. Field and method names are the
     reference's; records are numpy scalars of records.RENDER_DATA / SCENE_DATA."""
 
@@ -617,69 +699,9 @@ class Tracer:
         self._check(self.lib.srt_pipeline_flush(self._h, _ptr(output), C.byref(n)))
         return n.value
 
-    # -- edge-aware denoiser (srt_set_denoise) --
-    def set_denoise(self, enable=True, **kw):
-        """Turn the denoiser on with srt_denoise_defaults() overridden by kw (iterations, feature_samples, sigma_luminance,
-        sigma_normal, sigma_depth, sigma_albedo), or off with enable=False."""
-        if not enable:
-            self._check(self.lib.srt_set_denoise(self._h, None))
-            return
-        d = DenoiseParams()
-        self._check(self.lib.srt_denoise_defaults(C.byref(d)))
-        for k, v in kw.items():
-            if k not in d.as_dict() or k == "enable":
-                raise TypeError(f"set_denoise: unknown parameter {k}")
-            setattr(d, k, v)
-        self._check(self.lib.srt_set_denoise(self._h, C.byref(d)))
-
-    def resolve_denoised(self, ticks_stopped):
-        """The filter over the current canvas into the handle's ARGB image (read_argb); asynchronous."""
-        self._check(self.lib.srt_resolve_denoised(self._h, ticks_stopped))
-
-    def read_denoised(self):
-        """(height, width, 4) float32: the last filter result before tonemapping (r, g, b, variance)."""
-        out = np.zeros((self.height, self.width, 4), np.float32)
-        self._check(self.lib.srt_read_denoised(self._h, _ptr(out)))
-        return out
-
-    def read_denoise_inputs(self):
-        """dict: normal_depth (h, w, 4), albedo_hits (h, w, 4), moments (h, w), T, P."""
-        nd = np.zeros((self.height, self.width, 4), np.float32)
-        ah = np.zeros((self.height, self.width, 4), np.float32)
-        m = np.zeros((self.height, self.width), np.float32)
-        counts = (C.c_uint32 * 2)()
-        self._check(self.lib.srt_read_denoise_inputs(self._h, _ptr(nd), _ptr(ah), _ptr(m), counts))
-        return {"normal_depth": nd, "albedo_hits": ah, "moments": m, "T": int(counts[0]), "P": int(counts[1])}
-
-    def set_denoise_temporal(self, enable=True, **kw):
-        """Turn the denoiser's temporal reprojection on with srt_temporal_defaults() overridden by kw (history_limit,
-        normal_threshold, depth_threshold), or off with enable=False. Needs the denoiser on (set_denoise)."""
-        if not enable:
-            self._check(self.lib.srt_set_denoise_temporal(self._h, None))
-            return
-        d = TemporalParams()
-        self._check(self.lib.srt_temporal_defaults(C.byref(d)))
-        for k, v in kw.items():
-            if k not in ("history_limit", "normal_threshold", "depth_threshold"):
-                raise TypeError(f"set_denoise_temporal: unknown parameter {k}")
-            setattr(d, k, v)
-        self._check(self.lib.srt_set_denoise_temporal(self._h, C.byref(d)))
-
-    def reset_denoise_history(self):
-        """Drop the temporal history: the next frame is filtered as by the spatial denoiser alone."""
-        self._check(self.lib.srt_reset_denoise_history(self._h))
-
-    def read_denoise_history(self):
-        """dict: valid, colour (h, w, 3), count (h, w), m1, m2 (h, w), guide (h, w, 2, 4) {N, Z}, {A, cov}, camera (the history
-        frame's records.RENDER_DATA). Without a history every array is zero and valid is False."""
-        cc = np.zeros((self.height, self.width, 4), np.float32)
-        m = np.zeros((self.height, self.width, 2), np.float32)
-        g = np.zeros((self.height, self.width, 2, 4), np.float32)
-        cam = np.zeros((), R.RENDER_DATA)
-        valid = C.c_int(0)
-        self._check(self.lib.srt_read_denoise_history(self._h, _ptr(cc), _ptr(m), _ptr(g), _ptr(cam), C.byref(valid)))
-        return {"valid": bool(valid.value), "colour": cc[..., :3], "count": cc[..., 3], "m1": m[..., 0], "m2": m[..., 1], "guide": g,
-                "camera": cam}
+    # -- edge-aware denoiser (srt_set_denoise): set_denoise ... read_denoise_history are _Denoise's --
+    def _dn(self, name, *args):
+        return getattr(self.lib, "srt_" + name)(self._h, *args)
 
     def set_denoise_object_motion(self, enable=True):
         """Keep the temporal history across an update_scene that only moves shapes (srt_set_denoise_object_motion). Needs
@@ -709,7 +731,7 @@ class Tracer:
         self.owned_rows = self.lib.srt_partition_owned_rows(self.height, rank, world, rows_per_block)
 
 
-class TracerGroup:
+class TracerGroup(_Denoise):
     """One process driving several GPUs (srt_group_*): the reference's Tracer interface over a row partition,
     collected with one ncclGather per frame."""
 
@@ -786,6 +808,20 @@ class TracerGroup:
         c = Counters()
         self._check(self.lib.srt_group_get_counters(self._g, C.byref(c)))
         return c.as_dict()
+
+    # -- the denoiser on the group (srt_group_set_denoise): set_denoise, set_denoise_temporal, reset_denoise_history,
+    # resolve_denoised, read_denoised, read_denoise_inputs, read_denoise_history are _Denoise's, on the whole frame --
+    def _dn(self, name, *args):
+        return getattr(self.lib, "srt_group_" + name)(self._g, *args)
+
+    def trace_and_gather(self):
+        """Trace on every member, collect and unpermute on the first device; asynchronous (then resolve_denoised)."""
+        rd = R.as_records(self.options, R.RENDER_DATA)
+        self._check(self.lib.srt_group_trace_and_gather(self._g, _ptr(rd)))
+
+    def member(self, i):
+        """The srt_tracer handle of member i (ctypes void pointer; owned by the group)."""
+        return C.c_void_p(self.lib.srt_group_tracer(self._g, i))
 
 
 # ---- pure-host partition helpers (no GPU) ------------------------------------------
