@@ -413,6 +413,35 @@ int srt_motion_table_host(const srt_shape *h_shapes, size_t h_n_shapes, const sr
                           const srt_shape *c_shapes, size_t c_n_shapes, const srt_triangle *c_triangles, size_t c_n_triangles,
                           const srt_material *c_materials, size_t c_n_materials, const srt_scene_data *c_scene, uint32_t *table, int *keep);
 
+/* ---- albedo demodulation for the filter (new; SVGF's own: filter illumination, not colour) ------------------------------ */
+
+/* Opt-in. With it on and iterations K >= 1 the a-trous passes run over the illumination I = colour / albedo instead of the
+ * colour, and the last pass multiplies the albedo back: a surface whose texels differ from pixel to pixel keeps its pattern
+ * and still gets its noise averaged across texels and across coplanar materials. The albedo is the mean first-hit albedo
+ * of the guide (the texel where a texture is bound), so no trace kernel, feature kernel or record changes.
+ *   demodulate  after whichever set-up ran (spatial, temporal, moved). A pixel with cov > 0 and a finite colour:
+ *               D = max(A, SRT_DEMOD_EPS) per channel (a NaN channel: SRT_DEMOD_EPS), I = c / D per channel (IEEE),
+ *               V_I = V / lum(D)^2. Any other pixel is left as it is: never a tap, passed through, as without the switch.
+ *   passes      the filter's formula (csrc/denoise.hip) over I and V_I WITHOUT the albedo factor: sigma_albedo is ignored in
+ *               this mode. The luminance term uses lum(I); prefilter, skip rules and pass-through rules are unchanged.
+ *   remodulate  in the last pass, for the pixels that were demodulated: o = I' D_p, V' = V_I' lum(D_p)^2; tonemap(o) is the
+ *               ARGB image and {o, V'} what srt_read_denoised returns. A demodulated pixel that got no weight returns
+ *               I_p D_p, within rounding of its colour but not bit-equal to it.
+ * K = 0: no effect, the plain resolve's bytes. SRT_DEMOD_EPS bounds the amplification at 100x; it is not a tunable.
+ * The temporal history keeps holding colour. For diffuse and metallic first hits the colour is exactly albedo x
+ * illumination; for specular > 0, glass and emitters the first-hit colour is not the exact factor (the transform is
+ * still inverted per pixel, only the smoothness of I is weaker there). With feature_samples < num_samples the guide's
+ * mean texel estimates the canvas's: use feature_samples = num_samples on textured scenes. */
+#define SRT_DEMOD_EPS 0.01f
+/* enable != 0: on. SRT_ERR_STATE unless the denoiser is on (the group call: the group's denoiser). Turning the denoiser off
+ * turns it off. Clears nothing and keeps the temporal history; takes effect at the next filter (srt_render*,
+ * srt_resolve_denoised, srt_group_render, srt_group_resolve_denoised). */
+int srt_set_denoise_demodulation(srt_tracer *t, int enable);
+int srt_group_set_denoise_demodulation(srt_group *g, int enable);
+/* Which passes the last filter ran: *demodulated = 1 for the demodulated ones (the switch on and K >= 1), else 0. */
+int srt_last_filter_demodulated(const srt_tracer *t, int *demodulated);
+int srt_group_last_filter_demodulated(const srt_group *g, int *demodulated);
+
 /* ---- albedo textures ----------------------------------------------------------
  * Opt-in: where a material has a texture bound, the colour that multiplies the path's mask (and the denoiser's albedo
  * guide) is the texel at the hit's UV instead of srt_material.color. Nothing else about a material changes and a lookup

@@ -17,6 +17,11 @@
 //           c' = sum w c / sum w, V' = sum w^2 V / (sum w)^2; a tap with cov = 0 or a non-finite colour has weight 0; a pixel
 //           with cov = 0 or a non-finite colour (or no weight at all) passes through unchanged
 //   last    srt_resolve_kernel's tonemap (ACES fit, sqrt, bytes A,R,G,B); K = 0 gives the plain resolve's bytes.
+// Albedo demodulation (srt_set_denoise_demodulation; tests/demod_ref.py), K >= 1 only: one launch after the set-up divides
+//   a pixel with cov > 0 and a finite colour by D = max(A, SRT_DEMOD_EPS) per channel, I = c / D, V_I = V / lum(D)^2 (other
+//   pixels stay as they are), the passes run the formula above over I and V_I without the albedo factor -- sigma_albedo is
+//   ignored in this mode -- with lum(I) in the luminance term, and the last pass writes o = I' D_p, V' = V_I' lum(D_p)^2
+//   for the pixels that were demodulated (one that got no weight: I_p D_p, within rounding of c, not bit-equal).
 // No atomics: every output is a fixed function of its inputs, so runs are bit-identical. The passes use the fast
 // exp / log instructions: this stage is outside the parity contract (DESIGN.md "Denoiser").
 #include <hip/hip_runtime.h>
@@ -140,6 +145,85 @@ __global__ __launch_bounds__(256) void srt_denoise_atrous_kernel(const FilterPar
 	if (p.argb) p.argb[i] = tonemap(o.x, o.y, o.z);
 }
 
+struct DemodParams {
+	uint32_t num_pixels;
+	const float4 *guide;
+	float4 *io; // the set-up's {colour, variance}, in place
+};
+
+// albedo demodulation: colour -> illumination, in place, between the set-up and the passes
+__global__ __launch_bounds__(256) void srt_denoise_demodulate_kernel(const DemodParams p) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= p.num_pixels) return;
+	const float4 g1 = p.guide[2 * i + 1];
+	const float4 c = p.io[i];
+	if (!(g1.w > 0.f) || !finite3(c)) return;
+	const float dr = fmaxf(g1.x, SRT_DEMOD_EPS), dg = fmaxf(g1.y, SRT_DEMOD_EPS), db = fmaxf(g1.z, SRT_DEMOD_EPS);
+	const float ld = lum(dr, dg, db);
+	p.io[i] = make_float4(c.x / dr, c.y / dg, c.z / db, c.w / (ld * ld));
+}
+
+// srt_denoise_atrous_kernel over the illumination: no albedo term, so a tap is its {I, V_I} and {N, Z} alone (32 B, not 48).
+// A tap without hits has N = 0 and fails d > 0, which is all its cov > 0 test would do; the centre keeps that test (a
+// centre without hits is no filtered pixel). LAST: the remodulation and the tonemap.
+template <bool LAST>
+__global__ __launch_bounds__(256) void srt_denoise_atrous_demod_kernel(const FilterParams p) {
+	const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+	if (x >= p.width || y >= p.height) return;
+	const uint32_t i = (uint32_t)y * (uint32_t)p.width + (uint32_t)x;
+	const float4 cp = p.in[i];
+	const float4 g1p = p.guide[2 * i + 1];
+	float4 o = cp;
+	if (g1p.w > 0.f && finite3(cp)) {
+		const float4 g0p = p.guide[2 * i];
+		float gv = 0.f, gw = 0.f;
+		for (int dy = -1; dy <= 1; dy++) {
+			const int qy = y + dy;
+			if (qy < 0 || qy >= p.height) continue;
+			for (int dx = -1; dx <= 1; dx++) {
+				const int qx = x + dx;
+				if (qx < 0 || qx >= p.width) continue;
+				const float k = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);
+				gv += k * p.in[(uint32_t)qy * (uint32_t)p.width + (uint32_t)qx].w;
+				gw += k;
+			}
+		}
+		gv = gv / gw;
+		const float lp = lum(cp.x, cp.y, cp.z);
+		const float inv_dl = 1.0f / (p.sigma_l * sqrtf(gv) + 1e-10f);
+		const float inv_dz = 1.0f / (p.sigma_z * g0p.w * (float)p.step + 1e-6f);
+		const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+		float sw = 0.f, sv = 0.f, sr = 0.f, sg = 0.f, sb = 0.f;
+		for (int dy = -2; dy <= 2; dy++) {
+			const int qy = y + dy * p.step;
+			if (qy < 0 || qy >= p.height) continue;
+			for (int dx = -2; dx <= 2; dx++) {
+				const int qx = x + dx * p.step;
+				if (qx < 0 || qx >= p.width) continue;
+				const uint32_t j = (uint32_t)qy * (uint32_t)p.width + (uint32_t)qx;
+				const float4 g0q = p.guide[2 * j];
+				const float4 cq = p.in[j];
+				const float d = g0p.x * g0q.x + g0p.y * g0q.y + g0p.z * g0q.z;
+				if (!(d > 0.f) || !finite3(cq)) continue; // max(0, d)^sigma_n = 0 (no hits: N = 0)
+				const float wn = __expf(p.sigma_n * __logf(d));
+				const float e = fabsf(g0p.w - g0q.w) * inv_dz + fabsf(lp - lum(cq.x, cq.y, cq.z)) * inv_dl;
+				const float w = h[dx + 2] * h[dy + 2] * wn * __expf(-e);
+				sw += w;
+				sv += w * w * cq.w;
+				sr += w * cq.x, sg += w * cq.y, sb += w * cq.z;
+			}
+		}
+		if (sw > 0.f) o = make_float4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
+		if (LAST) {
+			const float dr = fmaxf(g1p.x, SRT_DEMOD_EPS), dg = fmaxf(g1p.y, SRT_DEMOD_EPS), db = fmaxf(g1p.z, SRT_DEMOD_EPS);
+			const float ld = lum(dr, dg, db);
+			o = make_float4(o.x * dr, o.y * dg, o.z * db, o.w * (ld * ld));
+		}
+	}
+	p.out[i] = o;
+	if (LAST) p.argb[i] = tonemap(o.x, o.y, o.z);
+}
+
 bool params_ok(const srt_denoise_params &d) {
 	auto sigma_ok = [](float s) { return std::isfinite(s) && s > 0.0f; };
 	return d.iterations >= 0 && d.iterations <= 8 && d.feature_samples >= 1 && d.feature_samples <= 64 && sigma_ok(d.sigma_luminance) &&
@@ -251,6 +335,15 @@ int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
 		hipLaunchKernelGGL(srt_denoise_setup_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, t->stream, sp);
 		SRT_HIP(t, hipGetLastError());
 	}
+	const bool demod = t->dn_demod && K >= 1;
+	if (demod) { // colour -> illumination, in place on the set-up's image (whichever set-up ran)
+		DemodParams dp;
+		dp.num_pixels = (uint32_t)px;
+		dp.guide = fguide;
+		dp.io = col;
+		hipLaunchKernelGGL(srt_denoise_demodulate_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, t->stream, dp);
+		SRT_HIP(t, hipGetLastError());
+	}
 	FilterParams fp;
 	fp.width = t->width;
 	fp.height = t->height;
@@ -268,11 +361,14 @@ int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
 		fp.in = col + (size_t)(k & 1) * px;
 		fp.out = col + (size_t)((k + 1) & 1) * px;
 		fp.argb = k == K - 1 ? reinterpret_cast<uint32_t *>(argb) : nullptr;
-		hipLaunchKernelGGL(srt_denoise_atrous_kernel, grid, dim3(256), 0, t->stream, fp);
+		if (!demod) hipLaunchKernelGGL(srt_denoise_atrous_kernel, grid, dim3(256), 0, t->stream, fp);
+		else if (k == K - 1) hipLaunchKernelGGL(srt_denoise_atrous_demod_kernel<true>, grid, dim3(256), 0, t->stream, fp);
+		else hipLaunchKernelGGL(srt_denoise_atrous_demod_kernel<false>, grid, dim3(256), 0, t->stream, fp);
 		SRT_HIP(t, hipGetLastError());
 	}
 	t->dn_out = K & 1;
 	t->dn_filtered = true;
+	t->last_filter_demod = demod;
 	return SRT_OK;
 }
 
@@ -295,6 +391,7 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 	if (!t) return SRT_ERR_INVALID;
 	if (!params || !params->enable) {
 		t->dn_on = false;
+		t->dn_demod = false; // albedo demodulation is a mode of the filter
 		t->tp_on = false; // temporal reprojection is a stage of the denoiser
 		t->om_on = false; // and object motion a stage of that
 		srt_temporal_drop(t);
@@ -320,6 +417,23 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 		SRT_HIP(t, hipMemsetAsync(t->canvas, 0, t->canvas_bytes, t->stream)); // srt_clear_canvas
 		return srt_denoise_clear(t);
 	}
+	return SRT_OK;
+}
+
+int srt_set_denoise_demodulation(srt_tracer *t, int enable) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!enable) {
+		t->dn_demod = false;
+		return SRT_OK;
+	}
+	if (!t->dn_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_demodulation: the denoiser is off (srt_set_denoise)");
+	t->dn_demod = true;
+	return SRT_OK;
+}
+
+int srt_last_filter_demodulated(const srt_tracer *t, int *demodulated) {
+	if (!t || !demodulated) return SRT_ERR_INVALID;
+	*demodulated = t->last_filter_demod ? 1 : 0;
 	return SRT_OK;
 }
 

@@ -677,6 +677,25 @@ int srt_group_set_denoise_temporal(srt_group *g, const srt_temporal_params *para
 	return SRT_OK;
 }
 
+int srt_group_set_denoise_demodulation(srt_group *g, int enable) {
+	if (!g) return SRT_ERR_INVALID;
+	if (!enable) {
+		if (g->resolver) g->resolver->dn_demod = false;
+		return SRT_OK;
+	}
+	if (!g->dn_on) return gfail(g, SRT_ERR_STATE, "srt_group_set_denoise_demodulation: the denoiser is off (srt_group_set_denoise)");
+	srt_tracer *r = resolver_of(g);
+	if (!r) return SRT_ERR_HIP;
+	SRT_ON_RESOLVER(g, r, srt_set_denoise_demodulation(r, 1)); // the filter runs on that handle
+	return SRT_OK;
+}
+
+int srt_group_last_filter_demodulated(const srt_group *g, int *demodulated) {
+	if (!g || !demodulated) return SRT_ERR_INVALID;
+	*demodulated = (g->resolver && g->resolver->last_filter_demod) ? 1 : 0;
+	return SRT_OK;
+}
+
 int srt_group_reset_denoise_history(srt_group *g) {
 	if (!g) return SRT_ERR_INVALID;
 	drop_history(g);

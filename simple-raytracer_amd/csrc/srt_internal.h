@@ -101,6 +101,8 @@ struct srt_tracer {
 	DevBuf<float> dn_guide;                // filter set-up: 2 float4 per pixel {N, Z}, {A, cov}
 	DevBuf<float> dn_col;                  // two float4 images {colour, variance}, ping-pong between passes
 	int dn_out = 0;                        // the image of dn_col the last pass wrote
+	bool dn_demod = false;                 // srt_set_denoise_demodulation: the passes filter colour / albedo (K >= 1)
+	bool last_filter_demod = false;        // srt_last_filter_demodulated
 	srt_render_data dn_cam{};              // the last dispatch's render data since the clear (its camera: temporal reprojection)
 	// temporal reprojection (temporal.hip; srt_set_denoise_temporal). Two history sets, each px x 14 floats: float4
 	// {colour, count}, float2 {m1, m2}, 2 float4 guide; tp_set[tp_cur] is the history, the other the frame being integrated

@@ -188,6 +188,12 @@ class Tracer {
 		p.depth_threshold = depth_threshold;
 		check(group ? srt_group_set_denoise_temporal(group, &p) : srt_set_denoise_temporal(handle, &p));
 	}
+	/// Albedo demodulation (srt_set_denoise_demodulation): the a-trous passes filter colour / first-hit albedo and the last one
+	/// multiplies the albedo back, which keeps fine textures and still averages their noise. Needs set_denoise first; one
+	/// device or a device group (the group's filter runs on device 0).
+	void set_denoise_demodulation(bool enable = true) {
+		check(group ? srt_group_set_denoise_demodulation(group, enable ? 1 : 0) : srt_set_denoise_demodulation(handle, enable ? 1 : 0));
+	}
 	/// Object motion for the temporal stage (srt_set_denoise_object_motion): the history survives an update_scene that only
 	/// moves spheres, planes or model instances. Needs set_denoise_temporal first; the clear_canvas / update_scene / render
 	/// order of the frame loop stays as it is. Single-device tracers only (a group gathers no shape indices).

@@ -300,6 +300,24 @@ def textured_sphere_scene():
     return shapes, tris, mats, textures, bindings
 
 
+def textured_noise_scene():
+    """A ground plane and two spheres, all diffuse, all on ONE 64x64 NEAREST texture of independent uniform texels in
+    [0.05, 1] (a fixed seed): neighbouring pixels see unrelated albedos. The scales put a texel at about one pixel of a
+    160x90 frame at default_camera() (fov_scale 1: a pixel is 2 Z / 90 world units at distance Z). Plane: u, v are world units
+    along its frame, scale 0.1 makes a texel 1 / 6.4 unit, the pixel size at Z = 7, the mid-ground. Spheres: u runs once
+    around (2 pi r = 6.3 units, ~43 pixels at Z = 6.6: 0.7 x 64 texels), v once over the height (2 r, ~14 pixels: 0.25 x 64).
+    Returns (shapes, triangles, materials, textures, bindings)."""
+    mats = _stack([R.material((0.8, 0.8, 0.8)), R.material((0.9, 0.5, 0.4)), R.material((0.4, 0.6, 0.9))], R.MATERIAL)
+    shapes = _stack([R.plane(0, (0, -1, 0), (0, 1, 0)), R.sphere(1, (-1.4, 0.0, -1.5), 1.0), R.sphere(2, (1.3, -0.3, -0.5), 0.7)], R.SHAPE)
+    img = np.ones((64, 64, 4), np.float32)
+    img[..., :3] = np.float32(0.05) + np.float32(0.95) * np.random.default_rng(20).random((64, 64, 3), np.float32)
+    bindings = np.zeros(len(mats), R.MATERIAL_TEXTURE)
+    bindings[0] = R.material_texture(0, 1, 0.1, 0.1)
+    bindings[1] = R.material_texture(0, 1, 0.7, 0.25)
+    bindings[2] = R.material_texture(0, 1, 0.7, 0.25)
+    return shapes, R.box_triangles(), mats, [img], bindings
+
+
 def planar_triangle_uvs(tris, scale=1.0):
     """(n, 3, 2) UVs from the model-space positions: (x + y, z + y) * scale per vertex."""
     pos = np.asarray(tris["v"]["pos"], np.float32)

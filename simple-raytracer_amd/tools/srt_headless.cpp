@@ -5,9 +5,10 @@
 //
 //   srt_headless [--scene spheres|meshes|empty] [--obj f.obj]... [--stl f.stl]...
 //                [--width W --height H --spp S --bounces B --frames N --time T]
-//                [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--temporal] [--move DX]
+//                [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--demodulate] [--temporal] [--move DX]
 // --denoise K: the frames go through the edge-aware denoiser with K a-trous passes (Tracer::set_denoise; with --gpus N the
 //                members gather the filter's inputs with the frame and device 0 filters: the same bytes as on one device)
+// --demodulate: with --denoise, the passes filter colour / first-hit albedo (Tracer::set_denoise_demodulation); an error without it
 // --temporal: with --denoise, the denoiser's temporal reprojection (Tracer::set_denoise_temporal)
 // --move DX: the camera moves by DX along x every frame and every frame clears the canvas, as the front-end does while moving
 // --move-shape I DX: with --temporal, shape I (a sphere, a plane or a model instance) moves by DX along x every frame and every
@@ -112,7 +113,7 @@ int main(int argc, char **argv) {
 	unsigned time_seed = 12345;
 	bool parse_only = false, bvh = false, pipelined = false;
 	int gpus = 1, denoise = -1;
-	bool temporal = false;
+	bool temporal = false, demodulate = false;
 	float move = 0.0f, shape_move = 0.0f;
 	int move_shape = -1;
 	bool moving = false;
@@ -146,17 +147,22 @@ int main(int argc, char **argv) {
 		else if (a == "--texture-scale") texture_scale = std::strtof(next(), nullptr);
 		else if (a == "--texture-nearest") texture_nearest = true;
 		else if (a == "--denoise") denoise = std::atoi(next());
+		else if (a == "--demodulate") demodulate = true;
 		else if (a == "--temporal") temporal = true;
 		else if (a == "--move") move = std::strtof(next(), nullptr), moving = true;
 		else if (a == "--move-shape") move_shape = std::atoi(next()), shape_move = std::strtof(next(), nullptr);
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--temporal] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]]\n";
+			             "[--denoise K] [--demodulate] [--temporal] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]]\n";
 			return 2;
 		}
 	}
 
+	if (demodulate && denoise < 0) {
+		std::cerr << "--demodulate needs --denoise K\n";
+		return 2;
+	}
 	if (temporal && denoise < 0) {
 		std::cerr << "--temporal needs --denoise K\n";
 		return 2;
@@ -226,6 +232,7 @@ int main(int argc, char **argv) {
 	Tracer tracer(width, height, 0, gpus); // --gpus N: one Tracer over N devices (rows split, one RCCL gather per frame)
 	if (bvh) tracer.set_acceleration(SRT_ACCEL_BVH);
 	if (denoise >= 0) tracer.set_denoise(denoise);
+	if (demodulate) tracer.set_denoise_demodulation();
 	if (temporal) tracer.set_denoise_temporal();
 	if (move_shape >= 0) {
 		if (!temporal || (size_t)move_shape >= shapes.size()) {

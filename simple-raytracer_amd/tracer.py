@@ -42,6 +42,8 @@ ABI_SYMBOLS = [
     "srt_group_set_denoise", "srt_group_set_denoise_temporal", "srt_group_reset_denoise_history", "srt_group_resolve_denoised",
     "srt_group_read_denoised", "srt_group_read_denoise_inputs", "srt_group_read_denoise_history", "srt_partition_planes_floats",
     "srt_unpermute_planes_device",
+    "srt_set_denoise_demodulation", "srt_group_set_denoise_demodulation", "srt_last_filter_demodulated",
+    "srt_group_last_filter_demodulated",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -368,6 +370,11 @@ def _bind(lib):
         lib.srt_read_denoise_shape_ids.argtypes = [vp, vp, vp]
         lib.srt_read_denoise_motion.argtypes = [vp, vp, sz, C.POINTER(sz), C.POINTER(C.c_int)]
         lib.srt_motion_table_host.argtypes = [vp, sz, vp, sz, vp, sz, vp] * 2 + [vp, C.POINTER(C.c_int)]
+    if hasattr(lib, "srt_set_denoise_demodulation"):  # (an older library, SRT_LIB, in an A/B run)
+        lib.srt_set_denoise_demodulation.argtypes = [vp, C.c_int]
+        lib.srt_group_set_denoise_demodulation.argtypes = [vp, C.c_int]
+        lib.srt_last_filter_demodulated.argtypes = [vp, C.POINTER(C.c_int)]
+        lib.srt_group_last_filter_demodulated.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(lib, "srt_set_textures"):
         lib.srt_set_textures.argtypes = [vp, vp, sz]
         lib.srt_set_material_textures.argtypes = [vp, vp, sz]
@@ -439,6 +446,17 @@ class _Denoise:
                 raise TypeError(f"set_denoise_temporal: unknown parameter {k}")
             setattr(d, k, v)
         self._check(self._dn("set_denoise_temporal", C.byref(d)))
+
+    def set_denoise_demodulation(self, enable=True):
+        """Filter illumination (colour / first-hit albedo) and multiply the albedo back in the last pass
+        (srt_set_denoise_demodulation). Needs the denoiser on; clears nothing, keeps the temporal history."""
+        self._check(self._dn("set_denoise_demodulation", 1 if enable else 0))
+
+    def last_filter_demodulated(self):
+        """True when the last filter ran the demodulated passes (the switch on and iterations >= 1)."""
+        out = C.c_int(0)
+        self._check(self._dn("last_filter_demodulated", C.byref(out)))
+        return bool(out.value)
 
     def reset_denoise_history(self):
         """Drop the temporal history: the next frame is filtered as by the spatial denoiser alone."""
