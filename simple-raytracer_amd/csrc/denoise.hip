@@ -244,6 +244,17 @@ int srt_denoise_clear(srt_tracer *t) {
 	return SRT_OK;
 }
 
+// the feature pass's one fork: the kernels of the dispatch's kind (albedo textures: the texel at the first hit is the albedo,
+// srt_texture.hip), storing shape indices when object motion is on (temporal.hip)
+static void launch_features(srt_tracer *t, const FeatureParams &fp) {
+	if (t->last_trace_textured) {
+		const TexFeatureParams fx = srt_with_textures<TexFeatureParams>(t, fp);
+		if (t->om_on) srt_launch_features_ids_tex(fx, t->om_ids[t->om_cur].ptr, t->stream);
+		else srt_launch_features_tex(fx, t->stream);
+	} else if (t->om_on) srt_launch_features_ids(fp, t->om_ids[t->om_cur].ptr, t->stream);
+	else srt_launch_features(fp, t->stream);
+}
+
 int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples) {
 	const uint32_t ns = num_samples > 0 ? (uint32_t)num_samples : 0u;
 	const uint32_t want = (uint32_t)(t->gd_on ? t->gd_feature_samples : t->dn.feature_samples);
@@ -255,15 +266,7 @@ int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples
 	fp.albedo_hits = t->gd_on ? gd_albedo_hits(t) : t->dn_ah.ptr;
 	fp.num_pixels = (uint32_t)(t->gd_on ? owned_pixels(t) : full_pixels(t));
 	fp.feature_samples = fs;
-	if (t->last_trace_textured) { // albedo textures: the texel at the first hit is the albedo (srt_texture.hip)
-		TexFeatureParams fx;
-		memset(&fx, 0, sizeof fx);
-		static_cast<FeatureParams &>(fx) = fp;
-		fx.tx = srt_texture_params(t);
-		if (t->om_on) srt_launch_features_ids_tex(fx, t->om_ids[t->om_cur].ptr, t->stream);
-		else srt_launch_features_tex(fx, t->stream);
-	} else if (t->om_on) srt_launch_features_ids(fp, t->om_ids[t->om_cur].ptr, t->stream); // temporal.hip: object motion
-	else srt_launch_features(fp, t->stream);
+	launch_features(t, fp);
 	SRT_HIP(t, hipGetLastError());
 	if (t->gd_on) return SRT_OK;
 	srt_denoise_count(t, p.rd, t->dn.feature_samples);

@@ -449,18 +449,38 @@ int srt_last_trace_class(const srt_tracer *t, int *scene_class_out) {
 
 int srt_trace(srt_tracer *t, const srt_render_data *options) { return srt_trace_fused(t, options, nullptr, 0u); }
 
-// srt_trace; with fused_argb != NULL the last reduction also resolves every pixel it has just accumulated into fused_argb
-// (owned pixels x 4 bytes, device memory) with the divisor ticks_stopped: what srt_resolve would do in a launch of its own
-int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fused_argb, uint32_t ticks_stopped) {
-	if (!t) return SRT_ERR_INVALID;
-	if (!options) return fail(t, SRT_ERR_INVALID, "srt_trace: options is NULL");
-	if (options->width != t->width || options->height != t->height)
-		return fail(t, SRT_ERR_INVALID, "srt_trace: options width/height differ from the handle's (no resize, tracer.hpp:61-66)");
-	if (t->sky_w <= 0) return fail(t, SRT_ERR_STATE, "srt_trace: no skybox set (srt_set_skybox)");
-	SRT_HIP(t, hipSetDevice(t->device));
-	if (const int trc = srt_texture_sync(t)) return trc;
-	const bool textured = t->tex_active && !options->show_normals; // (show_normals ignores textures: the untextured kernels)
-	t->last_trace_textured = textured;
+// ---- the steps of a dispatch (srt_trace_fused below runs them in this order) ------------------------------------------------
+
+// What the steps hand to each other, on srt_trace_fused's stack (value-initialised there). The two parameter blocks travel beside
+// it: the TraceParams (trace_params_of; launch_batch fills the batch's fields in place) and the ReduceParams (reduce_params_of).
+struct Dispatch {
+	bool textured, timed, denoise;
+	size_t pixels; // owned
+	int ns;        // options->num_samples
+	uint8_t *fused_argb;
+	uint32_t batch, n_batches; // reserve_radiance, with radiance_stride
+	size_t radiance_stride;
+	int slots;              // resident waves of the device for this launch configuration (wave_slots)
+	bool scan_queue;        // reserve_scan_stacks: array scan, the launches get scan stacks, scan_set_floats per set
+	size_t scan_set_floats;
+	uint32_t pool_blocks;
+};
+
+// num_pixels of `canvas` through the tone map into `argb`, on the handle's stream
+static int launch_resolve(srt_tracer *t, const float *canvas, uint32_t num_pixels, uint32_t ticks_stopped, uint8_t *argb) {
+	ResolveParams rp;
+	rp.canvas = canvas;
+	rp.argb = argb;
+	rp.num_steps = ticks_stopped;
+	rp.num_pixels = num_pixels;
+	srt_launch_resolve(rp, t->stream);
+	SRT_HIP(t, hipGetLastError());
+	return SRT_OK;
+}
+
+// The TraceParams that the handle and the options decide: everything but the batch's buffers, cursor, samples and chunks
+// (launch_batch). No side effects.
+static TraceParams trace_params_of(const srt_tracer *t, const srt_render_data *options, bool textured) {
 	TraceParams p;
 	memset(&p, 0, sizeof p);
 	p.rd = *options;
@@ -493,7 +513,7 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 	p.all_materials_ok = t->scene_set && t->all_materials_ok ? 1 : 0;
 	p.unit_materials = t->scene_set && t->unit_materials ? 1 : 0;
 	p.material_flags = t->scene_set ? t->material_flags : 0;
-	p.scene_class = t->last_trace_class = scene_class(t, options, textured);
+	p.scene_class = scene_class(t, options, textured);
 	p.f_sky_w = (float)t->sky_w;
 	p.f_sky_h = (float)t->sky_h;
 	p.sun_focus_int = dm_pow_small_int(p.sd.sun_focus);
@@ -504,9 +524,44 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 	p.world = t->world;
 	p.rows_per_block = t->rows_per_block;
 	p.owned_rows = t->owned_rows;
-	// ---- batches of samples: radiance[pixel][sample] must fit the HBM budget ----------
-	const size_t pixels = owned_pixels(t);
-	const int ns = options->num_samples;
+	return p;
+}
+
+// the ReduceParams of a dispatch but for the batch's fields (launch_batch) and the moments / argb union (launch_reduce)
+static ReduceParams reduce_params_of(const srt_tracer *t, const Dispatch &d, uint32_t ticks_stopped) {
+	ReduceParams rp;
+	rp.radiance = t->radiance.ptr;
+	rp.running = t->running.ptr;
+	rp.canvas = t->canvas;
+	rp.counters = t->counters.ptr;
+	rp.num_pixels = (uint32_t)d.pixels;
+	rp.num_samples = d.ns;
+	rp.queue_reset = nullptr;
+	rp.argb = nullptr;
+	rp.num_steps = ticks_stopped;
+	return rp;
+}
+
+// With the denoiser on, the reductions also collect the per-pixel moments and the render calls resolve through the filter
+// after the feature pass (denoise_tail), so no reduction resolves.
+// A member of a group whose denoiser is on (gd_on) does the same for its own rows; the group's resolver handle filters.
+static void launch_reduce(srt_tracer *t, ReduceParams &rp, bool denoise, uint8_t *argb) {
+	if (denoise) {
+		rp.moments = t->gd_on ? gd_moments(t) : t->dn_mom.ptr;
+		srt_launch_reduce_moments(rp, t->stream);
+	} else {
+		rp.argb = argb;
+		srt_launch_reduce(rp, t->stream);
+	}
+}
+
+// ---- batches of samples: radiance[pixel][sample] must fit the HBM budget ----------
+// Chooses the budget (first use), plans the batch and allocates the radiance buffers -- two when there are several batches,
+// and `running` with them --, falling back to smaller batches if the device cannot give that much right now. Fills d.batch
+// (samples per batch), d.n_batches and d.radiance_stride.
+static int reserve_radiance(srt_tracer *t, Dispatch &d) {
+	const size_t pixels = d.pixels;
+	const int ns = d.ns;
 	if (t->radiance_budget == 0) {
 		size_t free_b = 0, total_b = 0;
 		SRT_HIP(t, hipMemGetInfo(&free_b, &total_b));
@@ -529,44 +584,44 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 		batch = plan_batch_halved(batch);
 		t->radiance_budget = pixels * 12 * (size_t)batch;
 	}
-	const uint32_t n_batches = plan_num_batches(ns, batch);
-	if (n_batches > 1) SRT_HIP(t, t->running.reserve(pixels * 4));
-	p.radiance = t->radiance.ptr;
-	p.queue = t->counters.ptr + SRT_CTR_QUEUE;
-	auto with_textures = [&](const TraceParams &tp) { // the textured kernels' parameters: tp, then the texture tables
-		TexTraceParams x;
-		memset(&x, 0, sizeof x);
-		static_cast<TraceParams &>(x) = tp;
-		x.tx = srt_texture_params(t);
-		return x;
-	};
-	int per_cu = textured ? srt_trace_tex_resident_waves_per_cu(with_textures(p), t->count_tris) : srt_trace_resident_waves_per_cu(p, t->count_tris);
+	d.batch = batch;
+	d.n_batches = plan_num_batches(ns, batch);
+	d.radiance_stride = plan_radiance_stride(pixels, batch);
+	if (d.n_batches > 1) SRT_HIP(t, t->running.reserve(pixels * 4));
+	return SRT_OK;
+}
+
+// resident waves of the device for this dispatch's kernel: one counter line per persistent wave
+static int wave_slots(srt_tracer *t, const TraceParams &p, bool textured) {
+	int per_cu = textured ? srt_trace_tex_resident_waves_per_cu(srt_with_textures<TexTraceParams>(t, p), t->count_tris) : srt_trace_resident_waves_per_cu(p, t->count_tris);
 	if (const char *env = dev_env("SRT_WAVES_PER_CU")) {
 		const int v = atoi(env);
 		if (v > 0 && v < per_cu) per_cu = v;
 	}
 	t->last_waves_per_cu = per_cu;
-	int slots = t->num_cus * per_cu;
-	if (slots > SRT_WAVE_CTR_SLOTS) slots = SRT_WAVE_CTR_SLOTS; // one counter line per persistent wave
+	const int slots = t->num_cus * per_cu;
+	return slots > SRT_WAVE_CTR_SLOTS ? SRT_WAVE_CTR_SLOTS : slots;
+}
 
-	// Array scan: one block of scan / park stacks per persistent wave the largest launch of this dispatch starts (46 KB each),
-	// the launch-end ray pool's records (84 MB), and a second set of both only when sample batches overlap: 320 MB for a
-	// one-launch frame on 256 CUs, 640 MB for an overlapped one. If the device cannot give that, the
-	// dispatch runs without the pool (every wave scans its own remainder: slower tails, same canvas) before it fails.
-	const bool wants_scan_queue = t->num_models > 0 && !t->bvh_active;
-	const bool overlap_batches = n_batches > 1;
-	const size_t scan_waves = plan_scan_waves(slots, pixels, batch);
-	uint32_t pool_blocks = wants_scan_queue && !dev_env("SRT_NO_SCAN_POOL") ? (uint32_t)SRT_POOL_BLOCKS : 0u;
+// Array scan: one block of scan / park stacks per persistent wave the largest launch of this dispatch starts (46 KB each),
+// the launch-end ray pool's records (84 MB), and a second set of both only when sample batches overlap: 320 MB for a
+// one-launch frame on 256 CUs, 640 MB for an overlapped one. If the device cannot give that, the
+// dispatch runs without the pool (every wave scans its own remainder: slower tails, same canvas) before it fails.
+// Fills d.scan_queue, d.scan_set_floats and d.pool_blocks.
+static int reserve_scan_stacks(srt_tracer *t, Dispatch &d) {
+	d.scan_queue = t->num_models > 0 && !t->bvh_active;
+	const size_t scan_waves = plan_scan_waves(d.slots, d.pixels, d.batch);
+	d.pool_blocks = d.scan_queue && !dev_env("SRT_NO_SCAN_POOL") ? (uint32_t)SRT_POOL_BLOCKS : 0u;
 	if (const char *env = dev_env("SRT_POOL_BLOCKS")) { // tests: a pool that overflows
 		const int v = atoi(env);
-		if (v >= 0 && (uint32_t)v < pool_blocks) pool_blocks = (uint32_t)v;
+		if (v >= 0 && (uint32_t)v < d.pool_blocks) d.pool_blocks = (uint32_t)v;
 	}
-	if (wants_scan_queue) {
-		const size_t sets = overlap_batches ? 2 : 1;
-		hipError_t e = t->scan_queue.reserve(sets * SRT_SCAN_SET_FLOATS(scan_waves, pool_blocks != 0u));
-		if (e == hipErrorOutOfMemory && pool_blocks != 0u) {
+	if (d.scan_queue) {
+		const size_t sets = d.n_batches > 1 ? 2 : 1;
+		hipError_t e = t->scan_queue.reserve(sets * SRT_SCAN_SET_FLOATS(scan_waves, d.pool_blocks != 0u));
+		if (e == hipErrorOutOfMemory && d.pool_blocks != 0u) {
 			(void)hipGetLastError();
-			pool_blocks = 0u;
+			d.pool_blocks = 0u;
 			e = t->scan_queue.reserve(sets * SRT_SCAN_SET_FLOATS(scan_waves, false));
 		}
 		if (e != hipSuccess) {
@@ -574,34 +629,12 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 			return fail(t, SRT_ERR_HIP, std::string("srt_trace: scan stacks: ") + hipGetErrorString(e));
 		}
 	}
+	d.scan_set_floats = SRT_SCAN_SET_FLOATS(scan_waves, d.pool_blocks != 0u);
+	return SRT_OK;
+}
 
-	ReduceParams rp;
-	rp.radiance = t->radiance.ptr;
-	rp.running = t->running.ptr;
-	rp.canvas = t->canvas;
-	rp.counters = t->counters.ptr;
-	// The kernel timers (srt_last_kernel_ms, srt_last_trace_kernel_ms) are four event records per dispatch: 10-17 us of a 150 us
-	// interactive frame. srt_trace always takes them; the render calls only when asked to (srt_set_kernel_timers).
-	const bool timed = !fused_argb || t->timers_in_render;
-	rp.num_pixels = (uint32_t)pixels;
-	rp.num_samples = ns;
-	rp.queue_reset = nullptr;
-	rp.argb = nullptr;
-	rp.num_steps = ticks_stopped;
-	// With the denoiser on, the reductions also collect the per-pixel moments and the render calls resolve through the filter
-	// after the feature pass (below), so no reduction resolves.
-	// A member of a group whose denoiser is on (gd_on) does the same for its own rows; the group's resolver handle filters.
-	const bool denoise = t->dn_on || t->gd_on;
-	auto launch_reduce = [&](uint8_t *argb) {
-		if (denoise) {
-			rp.moments = t->gd_on ? gd_moments(t) : t->dn_mom.ptr;
-			srt_launch_reduce_moments(rp, t->stream);
-		} else {
-			rp.argb = argb;
-			srt_launch_reduce(rp, t->stream);
-		}
-	};
-
+// one pair of timer events per sample batch (srt_last_trace_kernel_ms)
+static int reserve_timer_events(srt_tracer *t, uint32_t n_batches) {
 	while (t->ev_k.size() < 2 * (size_t)n_batches) { // std::vector growth is the only throwing step: srt_trace's callers catch nothing
 		hipEvent_t ev = nullptr;
 		SRT_HIP(t, hipEventCreate(&ev));
@@ -612,116 +645,145 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 			return fail(t, SRT_ERR_INVALID, "out of host memory");
 		}
 	}
-	t->ev_k_used = 0;
-	if (timed) SRT_HIP(t, hipEventRecord(t->ev_t0, t->stream));
-	if (n_batches == 0) {
-		// num_samples <= 0: no paths; the reduction still applies colour = 0 / num_samples (render.cl:520-522)
-		rp.batch_samples = 0;
-		rp.first_batch = rp.last_batch = 1;
-		launch_reduce(fused_argb);
-	}
-	// Several sample batches: even and odd batches trace on two streams of their own, each into its own radiance buffer,
-	// work cursor and set of per-wave counter lines, so that the tail of a batch (its last long paths, a few lanes per wave
-	// and most waves gone: half of a launch of the 10^5-triangle array scan) runs under the next batch instead of leaving
-	// the GPU idle. The ordered reductions stay on the caller's stream, in batch order; a batch's trace waits for the
-	// reduction that last read its buffer.
-	const bool overlap = n_batches > 1;
-	t->batches_overlapped = overlap;
-	const size_t radiance_stride = plan_radiance_stride(pixels, batch);
-	if (overlap) {
-		for (int k = 0; k < 2; k++) {
-			if (!t->batch_stream[k]) {
-				// The two streams must not share a hardware queue, or the batches they carry run one after the other: the runtime
-				// deals its few queues out to streams as they are created, and in a process that holds other streams (bench.py:
-				// torch's, the headline handle's) both of these landed on one -- configs[4] 5.5 s instead of 4.3 s. Streams of
-				// different priority never share a queue, so the odd batches' stream is created one level above the even ones'.
-				int pr_low = 0, pr_high = 0;
-				(void)hipDeviceGetStreamPriorityRange(&pr_low, &pr_high); // (numerically lower = higher priority)
-				const int pr = (k == 1 && pr_high < pr_low) ? pr_low - 1 : pr_low;
-				SRT_HIP(t, hipStreamCreateWithPriority(&t->batch_stream[k], hipStreamNonBlocking, pr));
-			}
-			if (!t->ev_batch_traced[k]) SRT_HIP(t, hipEventCreateWithFlags(&t->ev_batch_traced[k], hipEventDisableTiming));
-			if (!t->ev_batch_reduced[k]) SRT_HIP(t, hipEventCreateWithFlags(&t->ev_batch_reduced[k], hipEventDisableTiming));
-		}
-		if (!t->ev_batch_fork) SRT_HIP(t, hipEventCreateWithFlags(&t->ev_batch_fork, hipEventDisableTiming));
-		SRT_HIP(t, hipEventRecord(t->ev_batch_fork, t->stream)); // everything the caller's stream holds so far (scene upload, clear, ...)
-		for (int k = 0; k < 2; k++) SRT_HIP(t, hipStreamWaitEvent(t->batch_stream[k], t->ev_batch_fork, 0));
-	}
-	for (uint32_t b = 0; b < n_batches; b++) {
-		const int par = overlap ? (int)(b & 1u) : 0;
-		hipStream_t ts = overlap ? t->batch_stream[par] : t->stream;
-		p.radiance = t->radiance.ptr + (size_t)par * radiance_stride;
-		rp.radiance = p.radiance;
-		p.queue = t->counters.ptr + (par ? SRT_CTR_QUEUE2 : SRT_CTR_QUEUE);
-		p.wave_counters = t->wave_counters.ptr + (size_t)par * SRT_WAVE_CTR_SLOTS * SRT_WAVE_CTR_STRIDE;
-		p.scan_queue = wants_scan_queue ? t->scan_queue.ptr + (size_t)par * SRT_SCAN_SET_FLOATS(scan_waves, pool_blocks != 0u) : nullptr;
-		p.pool_blocks = pool_blocks;
-		if (overlap && b >= 2) SRT_HIP(t, hipStreamWaitEvent(ts, t->ev_batch_reduced[par], 0)); // batch b - 2 has been summed up
-		const uint32_t s0 = b * batch;
-		const uint32_t nbs = (uint32_t)ns - s0 < batch ? (uint32_t)ns - s0 : batch;
-		p.batch_samples = nbs;
-		p.first_sample = s0;
-		p.total_items = (unsigned long long)pixels * nbs;
-		const LaunchPlan lp = plan_launch(p.total_items, nbs, (unsigned long long)srt_sub_job_items(t->num_models > 0, t->bvh_active), t->num_cus, slots,
-		                                  t->num_models > 0, t->bvh_active, dev_int("SRT_ITEMS_PER_WAVE"), dev_int("SRT_JOB_CAP_SUBS"));
-		p.nbs_magic16 = lp.nbs_magic16;
-		p.job_items = lp.job_items;
-		// the work cursor is zero: the reduction behind the launch that used it last has reset it (srt_reduce_kernel). Only a launch
-		// whose reduction was never enqueued (an error in between) leaves it dirty.
-		if (t->queue_dirty[par]) SRT_HIP(t, hipMemsetAsync(p.queue, 0, sizeof(unsigned long long), ts));
-		t->queue_dirty[par] = true;
-		if (p.pool_blocks) SRT_HIP(t, hipMemsetAsync(p.scan_queue, 0, (size_t)SRT_POOL_CTL_WORDS * sizeof(uint32_t), ts));
-		if (timed) SRT_HIP(t, hipEventRecord(t->ev_k[2 * b], ts));
-		t->last_grid = lp.num_waves;
-		if (textured) srt_launch_trace_tex(with_textures(p), t->count_tris, lp.num_waves, ts);
-		else srt_launch_trace(p, t->count_tris, lp.num_waves, ts);
-		SRT_HIP(t, hipGetLastError());
-		if (timed) SRT_HIP(t, hipEventRecord(t->ev_k[2 * b + 1], ts));
-		if (overlap) {
-			SRT_HIP(t, hipEventRecord(t->ev_batch_traced[par], ts));
-			SRT_HIP(t, hipStreamWaitEvent(t->stream, t->ev_batch_traced[par], 0));
-		}
-		t->ev_k_used = 2 * (size_t)(b + 1);
-		rp.batch_samples = nbs;
-		rp.first_batch = (b == 0);
-		rp.last_batch = (b == n_batches - 1);
-		rp.queue_reset = p.queue;
-		launch_reduce(rp.last_batch ? fused_argb : nullptr);
-		SRT_HIP(t, hipGetLastError());
-		t->queue_dirty[par] = false; // (no pixels: neither launch ran, the cursor is untouched)
-		if (overlap) SRT_HIP(t, hipEventRecord(t->ev_batch_reduced[par], t->stream));
-	}
-	if (denoise) {
-		int rc = srt_denoise_after_trace(t, p, ns);
-		if (rc == SRT_OK && fused_argb && t->dn_on) rc = srt_denoise_filter(t, ticks_stopped, fused_argb);
-		if (rc) return rc;
-		if (fused_argb && !t->dn_on) { // a group member rendered on its own: its rows unfiltered (the group's resolver filters whole frames)
-			ResolveParams rs;
-			rs.canvas = t->canvas;
-			rs.argb = fused_argb;
-			rs.num_steps = ticks_stopped;
-			rs.num_pixels = (uint32_t)pixels;
-			srt_launch_resolve(rs, t->stream);
-			SRT_HIP(t, hipGetLastError());
-		}
-	}
-	if (timed) SRT_HIP(t, hipEventRecord(t->ev_t1, t->stream));
-	t->have_trace_ev = timed;
-	t->have_kernel_ev = timed && n_batches > 0;
 	return SRT_OK;
 }
 
-// srt_resolve / srt_resolve_external: num_pixels of `canvas` through the tone map into `argb`, between the resolve timer's events
+// Several sample batches: even and odd batches trace on two streams of their own, each into its own radiance buffer,
+// work cursor and set of per-wave counter lines, so that the tail of a batch (its last long paths, a few lanes per wave
+// and most waves gone: half of a launch of the 10^5-triangle array scan) runs under the next batch instead of leaving
+// the GPU idle. The ordered reductions stay on the caller's stream, in batch order; a batch's trace waits for the
+// reduction that last read its buffer (launch_batch). Here: the streams and events, made when first needed, and the fork.
+static int fork_batch_streams(srt_tracer *t) {
+	for (int k = 0; k < 2; k++) {
+		if (!t->batch_stream[k]) {
+			// The two streams must not share a hardware queue, or the batches they carry run one after the other: the runtime
+			// deals its few queues out to streams as they are created, and in a process that holds other streams (bench.py:
+			// torch's, the headline handle's) both of these landed on one -- configs[4] 5.5 s instead of 4.3 s. Streams of
+			// different priority never share a queue, so the odd batches' stream is created one level above the even ones'.
+			int pr_low = 0, pr_high = 0;
+			(void)hipDeviceGetStreamPriorityRange(&pr_low, &pr_high); // (numerically lower = higher priority)
+			const int pr = (k == 1 && pr_high < pr_low) ? pr_low - 1 : pr_low;
+			SRT_HIP(t, hipStreamCreateWithPriority(&t->batch_stream[k], hipStreamNonBlocking, pr));
+		}
+		if (!t->ev_batch_traced[k]) SRT_HIP(t, hipEventCreateWithFlags(&t->ev_batch_traced[k], hipEventDisableTiming));
+		if (!t->ev_batch_reduced[k]) SRT_HIP(t, hipEventCreateWithFlags(&t->ev_batch_reduced[k], hipEventDisableTiming));
+	}
+	if (!t->ev_batch_fork) SRT_HIP(t, hipEventCreateWithFlags(&t->ev_batch_fork, hipEventDisableTiming));
+	SRT_HIP(t, hipEventRecord(t->ev_batch_fork, t->stream)); // everything the caller's stream holds so far (scene upload, clear, ...)
+	for (int k = 0; k < 2; k++) SRT_HIP(t, hipStreamWaitEvent(t->batch_stream[k], t->ev_batch_fork, 0));
+	return SRT_OK;
+}
+
+// Batch b of the dispatch: its trace launch on the batch's stream, its ordered reduction on the handle's.
+static int launch_batch(srt_tracer *t, const Dispatch &d, uint32_t b, TraceParams &p, ReduceParams &rp) {
+	const bool overlap = d.n_batches > 1;
+	const BatchSlice bs = plan_batch_slice(b, d.n_batches, d.pixels, d.ns, d.batch);
+	const int par = bs.parity;
+	hipStream_t ts = overlap ? t->batch_stream[par] : t->stream;
+	p.radiance = t->radiance.ptr + (size_t)par * d.radiance_stride;
+	p.queue = t->counters.ptr + (par ? SRT_CTR_QUEUE2 : SRT_CTR_QUEUE);
+	p.wave_counters = t->wave_counters.ptr + (size_t)par * SRT_WAVE_CTR_SLOTS * SRT_WAVE_CTR_STRIDE;
+	p.scan_queue = d.scan_queue ? t->scan_queue.ptr + (size_t)par * d.scan_set_floats : nullptr;
+	p.pool_blocks = d.pool_blocks;
+	if (overlap && b >= 2) SRT_HIP(t, hipStreamWaitEvent(ts, t->ev_batch_reduced[par], 0)); // batch b - 2 has been summed up
+	p.batch_samples = bs.samples;
+	p.first_sample = bs.first_sample;
+	p.total_items = bs.total_items;
+	const LaunchPlan lp = plan_launch(p.total_items, bs.samples, (unsigned long long)srt_sub_job_items(t->num_models > 0, t->bvh_active), t->num_cus, d.slots,
+	                                  t->num_models > 0, t->bvh_active, dev_int("SRT_ITEMS_PER_WAVE"), dev_int("SRT_JOB_CAP_SUBS"));
+	p.nbs_magic16 = lp.nbs_magic16;
+	p.job_items = lp.job_items;
+	// the work cursor is zero: the reduction behind the launch that used it last has reset it (srt_reduce_kernel). Only a launch
+	// whose reduction was never enqueued (an error in between) leaves it dirty.
+	if (t->queue_dirty[par]) SRT_HIP(t, hipMemsetAsync(p.queue, 0, sizeof(unsigned long long), ts));
+	t->queue_dirty[par] = true;
+	if (p.pool_blocks) SRT_HIP(t, hipMemsetAsync(p.scan_queue, 0, (size_t)SRT_POOL_CTL_WORDS * sizeof(uint32_t), ts));
+	if (d.timed) SRT_HIP(t, hipEventRecord(t->ev_k[2 * b], ts));
+	t->last_grid = lp.num_waves;
+	if (d.textured) srt_launch_trace_tex(srt_with_textures<TexTraceParams>(t, p), t->count_tris, lp.num_waves, ts);
+	else srt_launch_trace(p, t->count_tris, lp.num_waves, ts);
+	SRT_HIP(t, hipGetLastError());
+	if (d.timed) SRT_HIP(t, hipEventRecord(t->ev_k[2 * b + 1], ts));
+	if (overlap) {
+		SRT_HIP(t, hipEventRecord(t->ev_batch_traced[par], ts));
+		SRT_HIP(t, hipStreamWaitEvent(t->stream, t->ev_batch_traced[par], 0));
+	}
+	t->ev_k_used = 2 * (size_t)(b + 1);
+	rp.radiance = p.radiance;
+	rp.batch_samples = bs.samples;
+	rp.first_batch = (b == 0);
+	rp.last_batch = (b == d.n_batches - 1);
+	rp.queue_reset = p.queue;
+	launch_reduce(t, rp, d.denoise, rp.last_batch ? d.fused_argb : nullptr);
+	SRT_HIP(t, hipGetLastError());
+	t->queue_dirty[par] = false; // (no pixels: neither launch ran, the cursor is untouched)
+	if (overlap) SRT_HIP(t, hipEventRecord(t->ev_batch_reduced[par], t->stream));
+	return SRT_OK;
+}
+
+// behind the reductions of a dispatch with a denoiser on: the feature pass, and for the render calls the filter
+static int denoise_tail(srt_tracer *t, const Dispatch &d, const TraceParams &p, uint32_t ticks_stopped) {
+	int rc = srt_denoise_after_trace(t, p, d.ns);
+	if (rc == SRT_OK && d.fused_argb && t->dn_on) rc = srt_denoise_filter(t, ticks_stopped, d.fused_argb);
+	if (rc) return rc;
+	// a group member rendered on its own: its rows unfiltered (the group's resolver filters whole frames)
+	if (d.fused_argb && !t->dn_on) return launch_resolve(t, t->canvas, (uint32_t)d.pixels, ticks_stopped, d.fused_argb);
+	return SRT_OK;
+}
+
+// srt_trace; with fused_argb != NULL the last reduction also resolves every pixel it has just accumulated into fused_argb
+// (owned pixels x 4 bytes, device memory) with the divisor ticks_stopped: what srt_resolve would do in a launch of its own
+int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fused_argb, uint32_t ticks_stopped) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!options) return fail(t, SRT_ERR_INVALID, "srt_trace: options is NULL");
+	if (options->width != t->width || options->height != t->height)
+		return fail(t, SRT_ERR_INVALID, "srt_trace: options width/height differ from the handle's (no resize, tracer.hpp:61-66)");
+	if (t->sky_w <= 0) return fail(t, SRT_ERR_STATE, "srt_trace: no skybox set (srt_set_skybox)");
+	SRT_HIP(t, hipSetDevice(t->device));
+	if (const int trc = srt_texture_sync(t)) return trc;
+	Dispatch d{};
+	d.textured = t->tex_active && !options->show_normals; // (show_normals ignores textures: the untextured kernels)
+	t->last_trace_textured = d.textured;
+	// The kernel timers (srt_last_kernel_ms, srt_last_trace_kernel_ms) are four event records per dispatch: 10-17 us of a 150 us
+	// interactive frame. srt_trace always takes them; the render calls only when asked to (srt_set_kernel_timers).
+	d.timed = !fused_argb || t->timers_in_render;
+	d.denoise = t->dn_on || t->gd_on;
+	d.pixels = owned_pixels(t);
+	d.ns = options->num_samples;
+	d.fused_argb = fused_argb;
+	TraceParams p = trace_params_of(t, options, d.textured);
+	t->last_trace_class = p.scene_class;
+	if (const int rc = reserve_radiance(t, d)) return rc;
+	d.slots = wave_slots(t, p, d.textured);
+	if (const int rc = reserve_scan_stacks(t, d)) return rc;
+	ReduceParams rp = reduce_params_of(t, d, ticks_stopped);
+	if (const int rc = reserve_timer_events(t, d.n_batches)) return rc;
+	t->ev_k_used = 0;
+	if (d.timed) SRT_HIP(t, hipEventRecord(t->ev_t0, t->stream));
+	if (d.n_batches == 0) {
+		// num_samples <= 0: no paths; the reduction still applies colour = 0 / num_samples (render.cl:520-522)
+		rp.batch_samples = 0;
+		rp.first_batch = rp.last_batch = 1;
+		launch_reduce(t, rp, d.denoise, fused_argb);
+	}
+	t->batches_overlapped = d.n_batches > 1;
+	if (t->batches_overlapped)
+		if (const int rc = fork_batch_streams(t)) return rc;
+	for (uint32_t b = 0; b < d.n_batches; b++)
+		if (const int rc = launch_batch(t, d, b, p, rp)) return rc;
+	if (d.denoise)
+		if (const int rc = denoise_tail(t, d, p, ticks_stopped)) return rc;
+	if (d.timed) SRT_HIP(t, hipEventRecord(t->ev_t1, t->stream));
+	t->have_trace_ev = d.timed;
+	t->have_kernel_ev = d.timed && d.n_batches > 0;
+	return SRT_OK;
+}
+
+// srt_resolve / srt_resolve_external: launch_resolve between the resolve timer's events
 static int resolve_impl(srt_tracer *t, const float *canvas, uint32_t num_pixels, uint32_t ticks_stopped, uint8_t *argb) {
 	SRT_HIP(t, hipSetDevice(t->device));
-	ResolveParams rp;
-	rp.canvas = canvas;
-	rp.argb = argb;
-	rp.num_steps = ticks_stopped;
-	rp.num_pixels = num_pixels;
 	SRT_HIP(t, hipEventRecord(t->ev_r0, t->stream));
-	srt_launch_resolve(rp, t->stream);
-	SRT_HIP(t, hipGetLastError());
+	if (const int rc = launch_resolve(t, canvas, num_pixels, ticks_stopped, argb)) return rc;
 	SRT_HIP(t, hipEventRecord(t->ev_r1, t->stream));
 	t->have_resolve_ev = true;
 	return SRT_OK;

@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -187,8 +188,21 @@ void srt_texture_scene(srt_tracer *t, const srt_shape *shapes, size_t n_shapes, 
 int srt_texture_sync(srt_tracer *t);
 TexParams srt_texture_params(const srt_tracer *t);
 void srt_texture_release(srt_tracer *t);
+/* THE place a textured kernel's parameter block is made (Tex = TexTraceParams / TexFeatureParams over Base = TraceParams /
+ * FeatureParams): zeroed, padding included (what a kernel is handed is compared byte for byte), then the untextured
+ * kernel's parameters, then the texture tables */
+template <class Tex, class Base>
+static inline Tex srt_with_textures(const srt_tracer *t, const Base &base) {
+	Tex x;
+	memset(&x, 0, sizeof x);
+	static_cast<Base &>(x) = base;
+	x.tx = srt_texture_params(t);
+	return x;
+}
 /* denoise.hip: zero the denoiser's accumulations and counts (enqueued); after a dispatch's reductions, the feature pass of
- * that dispatch (p: its TraceParams) and the counts; the filter over the canvas into argb (device, width*height*4 bytes) */
+ * that dispatch (p: its TraceParams as srt_trace_fused's last batch left them -- a dispatch without samples has no batch: the
+ * batch's fields, radiance and queue among them, are zero, and no feature kernel is launched; else one launch of the kernel
+ * last_trace_textured and om_on choose) and the counts; the filter over the canvas into argb (device, width*height*4 bytes) */
 int srt_denoise_clear(srt_tracer *t);
 int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples);
 int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb);
@@ -210,7 +224,9 @@ void srt_temporal_drop(srt_tracer *t);
 /* srt_update_scene with object motion on (`bytes`: the new scene, scene_bytes still the previous call's; rc: the update's
  * result): keeps or drops the history and rebuilds the motion table */
 int srt_motion_update_scene(srt_tracer *t, const std::vector<uint8_t> &bytes, int rc);
-/* srt_trace whose last reduction also resolves into fused_argb (device, owned pixels x 4 bytes; NULL: plain srt_trace) */
+/* srt_trace whose last reduction also resolves into fused_argb (device, owned pixels x 4 bytes; NULL: plain srt_trace); with a
+ * denoiser on, the feature pass and the filter (a group member on its own: the plain resolve) follow the reductions. A
+ * sequence of file-local steps in srt_abi.hip; the arithmetic they share with the host unit check is trace_plan.h's */
 extern "C" int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fused_argb, uint32_t ticks_stopped);
 /* one scene for several handles: the host pass once (members[0]'s acceleration mode and hierarchy cache), the uploads of all
  * members enqueued before the first is waited for (srt_abi.hip; srt_group_update_scene). *failed_member = the member an error came from */

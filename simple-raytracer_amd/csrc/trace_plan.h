@@ -1,7 +1,10 @@
 // trace_plan.h — the launch plan of srt_trace as arithmetic: how many samples a batch holds, how a failed allocation shrinks it,
-// how large the chunks of a launch are and how many waves it starts. Integers in, small structs out; no HIP and no handle.
-// srt_trace_fused (srt_abi.hip) asks the device for the budget and the resident waves, calls these, and does the allocating and
-// the launching. The development overrides (-DSRT_DEV_KNOBS builds, read by srt_abi.hip dev_env()) arrive as arguments: 0 = not set.
+// which samples, buffers and stream batch b of a dispatch takes, how large the chunks of a launch are and how many waves it
+// starts. Integers in, small structs out; no HIP and no handle. The steps of srt_trace_fused (srt_abi.hip) call these and do
+// what needs the device: reserve_radiance asks for the budget and allocates (plan_batch, plan_batch_halved), wave_slots asks
+// for the resident waves, reserve_scan_stacks sizes the scan stacks (plan_scan_waves), launch_batch enqueues one batch
+// (plan_batch_slice, plan_launch). The development overrides (-DSRT_DEV_KNOBS builds, read by srt_abi.hip dev_env()) arrive
+// as arguments: 0 = not set.
 #ifndef SRT_TRACE_PLAN_H
 #define SRT_TRACE_PLAN_H
 
@@ -61,6 +64,25 @@ static inline size_t plan_scan_waves(int slots, size_t pixels, uint32_t batch) {
 	const unsigned long long need = (most_items + 63ull) / 64ull;
 	if (need < (unsigned long long)scan_waves) scan_waves = (size_t)(need ? need : 1ull);
 	return scan_waves;
+}
+
+// Batch b of the n_batches = plan_num_batches(ns, batch) a dispatch of ns samples runs as: its samples (the last batch may be
+// ragged), its work-items, and which of the two sets of everything a launch writes (radiance buffer, work cursor, per-wave
+// counter lines, scan stacks) and of the two batch streams it uses -- set 0 always when the dispatch is one batch.
+struct BatchSlice {
+	int parity;                     // 0 / 1: even / odd batches of a dispatch of several
+	uint32_t first_sample;          // sample index of the batch's first sample
+	uint32_t samples;               // samples per pixel in this batch (nbs)
+	unsigned long long total_items; // pixels x samples
+};
+
+static inline BatchSlice plan_batch_slice(uint32_t b, uint32_t n_batches, size_t pixels, int ns, uint32_t batch) {
+	BatchSlice bs;
+	bs.parity = n_batches > 1 ? (int)(b & 1u) : 0;
+	bs.first_sample = b * batch;
+	bs.samples = (uint32_t)ns - bs.first_sample < batch ? (uint32_t)ns - bs.first_sample : batch;
+	bs.total_items = (unsigned long long)pixels * bs.samples;
+	return bs;
 }
 
 struct LaunchPlan {

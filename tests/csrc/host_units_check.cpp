@@ -1,6 +1,6 @@
 // host_units_check.cpp -- the three host units of csrc/ that need no device, without the library: the BVH builder
 // (bvh_host.cpp), the scene's host pass with its hierarchy cache (scene_prep.cpp) and the launch plan (trace_plan.h).
-// usage: host_units_check bvh | scene | plan   (tests/test_host_units.py; scripts/host_asan.sh runs the first two under sanitizers)
+// usage: host_units_check bvh | scene | plan | batches   (tests/test_host_units.py; scripts/host_asan.sh runs bvh, scene and batches under sanitizers)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -245,11 +245,59 @@ static int mode_plan() {
 	}
 }
 
+// ---- batches ------------------------------------------------------------------------------------------------------------------
+// plan_batch_slice over every batch of a dispatch: the slices tile [0, ns) once and in order, parities alternate only when there
+// is more than one batch, total_items = pixels x samples. Returns the number of batches; *first and *last = those slices.
+static uint32_t check_batches(size_t pixels, int ns, uint32_t batch, BatchSlice *first, BatchSlice *last) {
+	const uint32_t n_batches = plan_num_batches(ns, batch);
+	CHECK((n_batches == 0) == (ns <= 0 || batch == 0), "pixels %zu ns %d batch %u: %u batches", pixels, ns, batch, n_batches);
+	uint32_t next = 0;
+	int previous_parity = 1; // (the first batch takes set 0)
+	for (uint32_t b = 0; b < n_batches; b++) {
+		const BatchSlice bs = plan_batch_slice(b, n_batches, pixels, ns, batch);
+		CHECK(bs.first_sample == next, "batch %u of %u starts at sample %u, the one before ended at %u", b, n_batches, bs.first_sample, next);
+		CHECK(bs.samples >= 1 && bs.samples <= batch, "batch %u holds %u samples of at most %u", b, bs.samples, batch);
+		CHECK(b == n_batches - 1 || bs.samples == batch, "batch %u of %u is ragged (%u of %u) but not the last", b, n_batches, bs.samples, batch);
+		CHECK(bs.parity == 0 || bs.parity == 1, "batch %u of %u has parity %d", b, n_batches, bs.parity);
+		CHECK(b == 0 ? bs.parity == 0 : bs.parity != previous_parity, "batch %u of %u has parity %d after %d", b, n_batches, bs.parity, previous_parity);
+		previous_parity = bs.parity;
+		CHECK(bs.total_items == (unsigned long long)pixels * bs.samples, "batch %u: %llu items for %zu pixels x %u samples", b, bs.total_items, pixels, bs.samples);
+		next = bs.first_sample + bs.samples;
+		if (b == 0) *first = bs;
+		*last = bs;
+	}
+	CHECK(next == (ns > 0 ? (uint32_t)ns : 0u), "pixels %zu ns %d batch %u: the batches end at sample %u", pixels, ns, batch, next);
+	return n_batches;
+}
+
+// the cases every run checks, then stdin: rows of pixels ns batch; stdout per such row: n_batches, then parity first_sample
+// samples of the first and of the last batch (zeros when there is none); "ok" at the end
+static int mode_batches() {
+	BatchSlice first, last;
+	CHECK(check_batches(1200, 5, 2, &first, &last) == 3 && last.first_sample == 4 && last.samples == 1 && last.parity == 0, "5 samples in batches of 2: 2, 2, 1");
+	CHECK(check_batches(1200, 5, 5, &first, &last) == 1 && first.parity == 0 && first.samples == 5, "5 samples in one batch: set 0");
+	CHECK(check_batches(1200, 5, 1, &first, &last) == 5 && last.parity == 0, "5 samples one by one");
+	CHECK(check_batches(1200, 0, 0, &first, &last) == 0 && check_batches(1200, -3, 0, &first, &last) == 0, "no samples: no batch");
+	CHECK(check_batches(0, 4, 4, &first, &last) == 1 && first.total_items == 0, "a handle without rows: one launch of no items");
+	long long v[3];
+	for (;;) {
+		for (int k = 0; k < 3; k++)
+			if (scanf("%lld", &v[k]) != 1) {
+				if (k == 0) printf("ok\n");
+				return k == 0 ? 0 : 1;
+			}
+		memset(&first, 0, sizeof first), memset(&last, 0, sizeof last);
+		const uint32_t n_batches = check_batches((size_t)v[0], (int)v[1], (uint32_t)v[2], &first, &last);
+		printf("%u %d %u %u %d %u %u\n", n_batches, first.parity, first.first_sample, first.samples, last.parity, last.first_sample, last.samples);
+	}
+}
+
 int main(int argc, char **argv) {
 	const std::string mode = argc > 1 ? argv[1] : "";
 	if (mode == "bvh") return mode_bvh();
 	if (mode == "scene") return mode_scene();
 	if (mode == "plan") return mode_plan();
-	fprintf(stderr, "usage: %s bvh | scene | plan\n", argv[0]);
+	if (mode == "batches") return mode_batches();
+	fprintf(stderr, "usage: %s bvh | scene | plan | batches\n", argv[0]);
 	return 2;
 }

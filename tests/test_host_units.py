@@ -2,7 +2,7 @@
 (tests/csrc/host_units_check.cpp): the BVH builder (bvh_host.cpp: threaded against one-thread build, refit, stack bound), the
 scene's host pass with its hierarchy cache (scene_prep.cpp: reuse, refit, claim, eviction, an error that keeps the cache) and
 the launch plan of srt_trace (trace_plan.h) against the table the parent of the split printed (tests/golden/
-trace_plan_parent.json). And the g++ build of the builder against the library's, bit for bit."""
+trace_plan_parent.json), with the slices its batches cut a dispatch into. And the g++ build of the builder against the library's, bit for bit."""
 import ctypes as C
 import json
 import subprocess
@@ -44,6 +44,23 @@ def test_launch_plan_is_the_parents(exe):
     assert len(got) == len(rows)
     for r, g in zip(rows, got):
         assert g == r["out"], (r["case"], dict(zip(table["output_columns"], zip(g, r["out"]))))
+
+
+def test_batch_slices_tile_the_samples(exe):
+    """plan_batch_slice (what srt_abi.hip launch_batch takes its samples, items and buffer set from) over every batch of a
+    dispatch: the program checks that the slices tile [0, ns) once in order, that parities alternate only with several batches
+    and that total_items = pixels x samples -- for its own cases (5 samples in batches of 2: ragged; ns <= 0) and for
+    (pixels, ns, batch) of every golden row, whose batch count and first / last sample counts must be the table's."""
+    rows = json.loads((GOLDEN / "trace_plan_parent.json").read_text())["rows"]
+    cases = [(r["in"][0], r["in"][1], r["out"][0]) for r in rows] + [(40 * 30, 5, 2), (40 * 30, 0, 0), (40 * 30, -3, 0)]
+    out = subprocess.run([str(exe), "batches"], input="".join(f"{p} {ns} {b}\n" for p, ns, b in cases), capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout + out.stderr
+    got = [[int(x) for x in line.split()] for line in out.stdout.splitlines()[:-1]]
+    assert len(got) == len(cases)
+    for r, g in zip(rows, got):
+        assert (g[0], g[3], g[6]) == (r["out"][2], r["out"][5], r["out"][9]), (r["case"], g)
+        assert g[1] == 0 and g[2] == 0 and g[4] == ((g[0] - 1) & 1 if g[0] > 1 else 0), (r["case"], g)
+    assert got[len(rows):] == [[3, 0, 0, 2, 0, 4, 1], [0, 0, 0, 0, 0, 0, 0], [0, 0, 0, 0, 0, 0, 0]]
 
 
 def test_gxx_build_of_the_builder_equals_the_librarys(tmp_path, monkeypatch):
