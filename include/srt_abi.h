@@ -516,6 +516,14 @@ int srt_texture_check_host(const srt_texture_desc *descs, size_t n_textures, con
  * 1..32 over the RNG outputs, their negatives and all bit patterns (must be 0). */
 int srt_selftest_math(srt_tracer *t, uint32_t stride, uint64_t out[16]);
 
+/* Device self-test of the trace kernel's wave-level votes (tests only): the bounce's three Box-Muller normals (what = 0), its
+ * vector-times-sign (what = 1) as the kernel runs them -- one vote per wave, then
+ * the fast or the rare form on all its lanes -- against the per-lane forms. Lane i of wave i / 64 reads in[8 * i ..]:
+ * {seed} / {vx, vy, vz, d} (float bits), and writes four words of each result to out_new and
+ * out_ref ({x, y, z, seed afterwards} / {x, y, z, 0}); *mismatches = the number of words whose bits differ (must be 0 wherever
+ * a NaN component comes with a NaN d, as it does in the kernel). waves <= 65536. */
+int srt_selftest_rare_lanes(srt_tracer *t, int what, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, uint64_t *mismatches);
+
 /* Library / build identification, e.g. "srt-hip gfx950 parity fp-contract=off". */
 const char *srt_version(void);
 

@@ -115,9 +115,17 @@ __device__ __forceinline__ float cos_cur(float x, bool alt) {
 	return dm_u2f(dm_f2u(res) ^ ((((uint32_t)k << 30) + 0x40000000u) & 0x80000000u));
 }
 
-enum { SQ_S1, SQ_S2, SQ_S3, SQ_S4, SQ_S1_BM, SQ_S5_BM, SQ_S3_BM, LOG_D1, LOG_D2, LOG_D4, GEN_D2, GEN_FIX_BOX, GEN_FIX_WIDE, GEN_FIX1_WIDE, CAM_HOSTRCP, COS_ALT, SQ_S1_GLASS, N_OUT };
+enum { SQ_S1, SQ_S2, SQ_S3, SQ_S4, SQ_S1_BM, SQ_S5_BM, SQ_S3_BM, SQ_S1_BM_ADMIT, SIGN_XOR, SIGN_XOR_NAN, LOG_D1, LOG_D2, LOG_D4, GEN_D2, GEN_FIX_BOX, GEN_FIX_WIDE, GEN_FIX1_WIDE, CAM_HOSTRCP, COS_ALT, SQ_S1_GLASS, N_OUT };
 
-__global__ __launch_bounds__(256) void probe(unsigned long long *out) {
+// the built-in sign as the kernel's sign_fast computes it (kernels.hip)
+__device__ __forceinline__ float sign_fast(float x) {
+	const float one = dm_u2f((dm_f2u(x) & 0x80000000u) | 0x3f800000u);
+	const float zero_or_x = __builtin_amdgcn_class(x, 0x60) ? x : 0.0f;
+	return __builtin_islessgreater(x, 0.0f) ? one : zero_or_x;
+}
+
+// dots: a positive and a negative number, handed in at run time (a multiply by a constant 1 would be folded away)
+__global__ __launch_bounds__(256) void probe(unsigned long long *out, const float *dots) {
 	unsigned long long bad[N_OUT] = {0};
 	const float widths[8] = {1920.f, 1080.f, 256.f, 3840.f, 2160.f, 960.f, 37.f, 41.f};
 	for (unsigned long long i = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; i < 0x100000000ull; i += (unsigned long long)gridDim.x * blockDim.x) {
@@ -142,6 +150,16 @@ __global__ __launch_bounds__(256) void probe(unsigned long long *out) {
 		bad[SQ_S1_BM] += same(sqrt_s1(arg), rho) ? 0 : 1; // fails at u = 0 (inf) and u = 1 (-0) at least
 		bad[SQ_S5_BM] += (u == 0.0f || same(sqrt_s5(arg), rho)) ? 0 : 1; // u = 0 is selected away by the caller
 		bad[SQ_S3_BM] += same(sqrt_s3(arg), rho) ? 0 : 1;
+		// (2b) the same with no clamp and no select, on the outputs the trace kernel's wave vote admits: every r but 0 (u = 0) and
+		// the 128 largest (the conversion rounds them to 2^32: u = 1)
+		if (r != 0u && r < 0xffffff80u) bad[SQ_S1_BM_ADMIT] += same(sqrt_s1(arg), rho) ? 0 : 1;
+		// (2c) v * sign(d) for a dot d that is less or greater than 0: d's sign bit xor-ed into the component against the multiply,
+		// BIT FOR BIT (a NaN is not equal to another NaN here), every bit pattern of the component under both signs
+		for (int k = 0; k < 2; k++) {
+			const float d = dots[k];
+			const uint32_t by_xor = r ^ (dm_f2u(d) & 0x80000000u), by_mul = dm_f2u(x * sign_fast(d));
+			if (by_xor != by_mul) bad[x != x ? SIGN_XOR_NAN : SIGN_XOR]++;
+		}
 		// (3) the logarithm's division on every u (f from the mantissa normalisation of dm_logf)
 		{
 			uint32_t ix = dm_f2u(u) & 0x007fffffu;
@@ -191,10 +209,14 @@ int main() {
 	unsigned long long *d = nullptr, h[N_OUT];
 	hipMalloc(&d, sizeof h);
 	hipMemset(d, 0, sizeof h);
-	hipLaunchKernelGGL(probe, dim3(4096), dim3(256), 0, 0, d);
+	const float dots_h[2] = {0.37f, -0.37f};
+	float *dots = nullptr;
+	hipMalloc(&dots, sizeof dots_h);
+	hipMemcpy(dots, dots_h, sizeof dots_h, hipMemcpyHostToDevice);
+	hipLaunchKernelGGL(probe, dim3(4096), dim3(256), 0, 0, d, dots);
 	hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
 	const char *names[N_OUT] = {"sqrt S1 (rsq+1 Markstein) normal x>=2^-96", "sqrt S2 (rsq+Goldschmidt+Markstein)", "sqrt S3 (v_sqrt + rsq correction)", "sqrt S4 (rsq + 2 Markstein)",
-	                            "Box-Muller sqrt S1 (all u)", "Box-Muller sqrt S5 (clamped rsq, u != 0)", "Box-Muller sqrt S3 (all u)", "log div D1 (raw rcp, 1 corr)", "log div D2 (refined rcp, 1 corr)",
+	                            "Box-Muller sqrt S1 (all u)", "Box-Muller sqrt S5 (clamped rsq, u != 0)", "Box-Muller sqrt S3 (all u)", "Box-Muller sqrt S1 (admitted u)", "sign xor vs multiply (component not NaN)", "sign xor vs multiply (NaN component)", "log div D1 (raw rcp, 1 corr)", "log div D2 (refined rcp, 1 corr)",
 	                            "log div D4 (raw rcp, 2 corr)", "general div D2 in the box", "general div fixup (box, zeros)", "general div fixup (wide exponents)", "general div fixup 1 corr (wide)",
 	                            "camera div with host 1/W", "cos sign by integer ops", "glass sqrt S1 (1 - u^2, nonzero)"};
 	for (int k = 0; k < N_OUT; k++) printf("%-48s mismatches %llu\n", names[k], h[k]);

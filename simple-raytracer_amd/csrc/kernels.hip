@@ -284,6 +284,20 @@ __device__ __forceinline__ float sign_fast(float x) {
 	return __builtin_islessgreater(x, 0.0f) ? one : zero_or_x;
 }
 
+// v * sign(d) for the WAVE (the bounce's `rd * sign(dot(n, rd))` and `n * sign(dot(n, dir))`). Where d is less or greater than 0,
+// sign(d) is +-1 and the product is v or -v exactly: d's sign bit xor-ed into the three components (one v_and, three v_xor; the
+// five instructions of sign_fast and the three multiplies go). One v_cmp_class vote on d (zero | NaN) sends the whole wave
+// through today's form otherwise. A NaN component is the one value on which the xor and the multiply differ (the multiply
+// keeps a NaN's sign, the xor flips it: exact_math_probe.hip "sign xor", NaN rows) -- and is never seen here: d is a dot
+// product WITH v, so a NaN in v makes d NaN and the wave votes. EXHAUSTIVE for every other component, both signs, same probe.
+// (Denormal components included: this build keeps f32 denormals -- build.py never passes -fgpu-flush-denormals-to-zero -- so
+// v_mul_f32 by +-1 returns them unchanged, as the xor does. A build that flushed them would have to vote on them too.)
+__device__ __forceinline__ f3 mul_sign_wave(f3 v, float d) {
+	if (__builtin_expect(any64(__builtin_amdgcn_class(d, 0x63)), 0)) return v * sign_fast(d); // (wave-uniform) sNaN | qNaN | -0 | +0 @rare
+	const uint32_t sb = dm_f2u(d) & 0x80000000u;
+	return mk(dm_u2f(dm_f2u(v.x) ^ sb), dm_u2f(dm_f2u(v.y) ^ sb), dm_u2f(dm_f2u(v.z) ^ sb));
+}
+
 // column-major 4x4 times (v, w): ((m0*v.x + m1*v.y) + m2*v.z) + m3*w  (render.cl:114-120)
 __device__ __forceinline__ f3 mat_by_vec(const srt_float4 *m, f3 v, float w) {
 	return mk(((m[0].x * v.x + m[1].x * v.y) + m[2].x * v.z) + m[3].x * w,
@@ -385,24 +399,55 @@ __device__ __forceinline__ float cos_2pi(float x) {
 }
 
 // Three Box-Muller normals (render.cl:150-158: x, y, z in that order, theta drawn before rho each time), the three square
-// roots side by side. -2 log u is -0 (u = 1), +inf (u = 0) or in [1.19e-7, 44.4] for every u random_float can return: the root
-// by sqrt_rsq_zero_ok, and u = 0 (whose logarithm is left some finite number here) selected to sqrt(+inf) = +inf afterwards.
-// Equal to the IEEE sqrt(-2 log u) for all 2^32 u: srt_selftest_math out[10].
-__device__ __forceinline__ f3 random_normal3(uint32_t &seed) {
-	float th[3], cnt[3], arg[3], rho[3];
+// roots side by side. box_muller_draws makes the six draws (the rho draws' bits are kept for the wave form's vote) and the
+// three arguments -2 log u, which are -0 (u = 1), +inf (u = 0) or in [1.19e-7, 44.4] for every u random_float can return.
+__device__ __forceinline__ void box_muller_draws(uint32_t &seed, float (&th)[3], uint32_t (&rb)[3], float (&cnt)[3], float (&arg)[3]) {
 #pragma unroll
 	for (int k = 0; k < 3; k++) {
 		th[k] = (6.28318548f * 2.3283064365386963e-10f) * random_count(seed); // = 6.28318548f * random_float, bit for bit
-		cnt[k] = random_count(seed);
+		rb[k] = random_bits(seed);
+		cnt[k] = (float)rb[k];
 	}
 #pragma unroll
 	for (int k = 0; k < 3; k++) arg[k] = -2.0f * log_unit_biased<159, false>(cnt[k]);
+}
+// The roots for EVERY u: sqrt_rsq_zero_ok, and u = 0 (whose logarithm is left some finite number) selected to sqrt(+inf) = +inf
+// afterwards. Equal to the IEEE sqrt(-2 log u) for all 2^32 u: srt_selftest_math out[10]. Three v_med3 and three compare /
+// select pairs, for 129 of the generator's 2^32 outputs.
+__device__ __forceinline__ void box_muller_rho_any(const float (&arg)[3], const float (&cnt)[3], float (&rho)[3]) {
 	sqrt_rsq_n<3, true>(arg, rho);
 #pragma unroll
 	for (int k = 0; k < 3; k++) {
 		asm volatile("" : "+v"(rho[k])); // keep the zero test a select (see log_unit_biased)
 		rho[k] = cnt[k] == 0.0f ? DM_INF_F : rho[k];
 	}
+}
+// The per-lane form (the general kernels; the selftest's reference for the wave form below).
+__device__ __forceinline__ f3 random_normal3_lane(uint32_t &seed) {
+	float th[3], cnt[3], arg[3], rho[3];
+	uint32_t rb[3];
+	box_muller_draws(seed, th, rb, cnt, arg);
+	box_muller_rho_any(arg, cnt, rho);
+	return mk(rho[0] * cos_2pi(th[0]), rho[1] * cos_2pi(th[1]), rho[2] * cos_2pi(th[2]));
+}
+// The same for the WAVE. The two arguments sqrt_rsq gets wrong come from 129 generator outputs: r = 0 (u = 0, -2 log u = +inf)
+// and the 128 largest, r >= 2^32 - 128, which the conversion rounds to 2^32 (u = 1, -2 log u = -0). One vote on the three rho
+// draws' bits (v_min3_u32, v_max3_u32, two compares); a wave that holds one -- three draws x 64 lanes x 129 / 2^32: one bounce in
+// 170,000 -- runs the per-lane tail above on all its lanes. Every other count is an integer in [1, 2^32 - 256]:
+// u in [2^-32, 1 - 2^-24], log u in [-22.18, -5.96e-8], so -2 log u is a normal float in [1.19e-7, 44.4] -- far inside
+// [2^-96, inf), where sqrt_rsq IS the IEEE root (exhaustive: srt_selftest_math out[12]) -- and the clamp of the reciprocal root
+// and the select to +inf would be the identity. Checked draw by draw over all those counts: exact_math_probe.hip "Box-Muller
+// sqrt S1 (admitted u)" (its sqrt_s1 is sqrt_rsq_n<3, false>'s sequence -- rsq, x y, y / 2, two fmas -- for one value, on
+// -2 dm_logf(u), which log_unit_biased<159, false> equals on every count but 0: srt_selftest_math out[1], out[11]).
+__device__ __forceinline__ bool rho_draws_rare(uint32_t r0, uint32_t r1, uint32_t r2) {
+	return min(min(r0, r1), r2) == 0u || max(max(r0, r1), r2) >= 0xffffff80u;
+}
+__device__ __forceinline__ f3 random_normal3(uint32_t &seed) {
+	float th[3], cnt[3], arg[3], rho[3];
+	uint32_t rb[3];
+	box_muller_draws(seed, th, rb, cnt, arg);
+	if (__builtin_expect(any64(rho_draws_rare(rb[0], rb[1], rb[2])), 0)) box_muller_rho_any(arg, cnt, rho); // (wave-uniform) @rare
+	else sqrt_rsq_n<3, false>(arg, rho);
 	return mk(rho[0] * cos_2pi(th[0]), rho[1] * cos_2pi(th[1]), rho[2] * cos_2pi(th[2]));
 }
 
@@ -1496,6 +1541,42 @@ void srt_launch_selftest(unsigned long long *out, uint32_t stride, void *stream)
 	const float w[8] = {1920.f, 1080.f, 256.f, 3840.f, 2160.f, 960.f, 37.f, 16777216.f};
 	for (int i = 0; i < 8; i++) sz.w[i] = w[i], sz.inv_w[i] = 1.0f / w[i];
 	hipLaunchKernelGGL(srt_selftest_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, out, stride, sz);
+}
+
+// The bounce's wave-voted forms (random_normal3, mul_sign_wave) against the per-lane forms they replaced,
+// WAVE BY WAVE: one workgroup = one wave = 64 consecutive lanes of the input, so the caller decides which lanes of a wave hold
+// a rare case (none, one, lane 0, lane 63, all). 8 input words and 4 output words per lane:
+//   what 0  in {seed}                 out {x, y, z of the three normals, seed afterwards}
+//   what 1  in {vx, vy, vz, d}        out {v * sign(d), 0}
+// Both results go back to the host; *mismatches counts the words whose bits differ.
+__global__ __launch_bounds__(64) void srt_selftest_rare_kernel(int what, const uint32_t *__restrict__ in, uint32_t *__restrict__ out_new,
+                                                               uint32_t *__restrict__ out_ref, unsigned long long *mismatches) {
+	const size_t lane = (size_t)blockIdx.x * 64u + threadIdx.x;
+	const uint32_t *__restrict__ w = in + lane * 8u;
+	f3 a = mk(0.0f, 0.0f, 0.0f), b = a;
+	uint32_t ta = 0u, tb = 0u;
+	if (what == 0) { // (uniform)
+		uint32_t sa = w[0], sb = w[0];
+		a = random_normal3(sa), b = random_normal3_lane(sb);
+		ta = sa, tb = sb;
+	} else {
+		const f3 v = mk(dm_u2f(w[0]), dm_u2f(w[1]), dm_u2f(w[2]));
+		const float d = dm_u2f(w[3]);
+		a = mul_sign_wave(v, d), b = v * sign_fast(d);
+	}
+	const uint32_t ra[4] = {dm_f2u(a.x), dm_f2u(a.y), dm_f2u(a.z), ta}, rb[4] = {dm_f2u(b.x), dm_f2u(b.y), dm_f2u(b.z), tb};
+	unsigned long long bad = 0;
+#pragma unroll
+	for (int k = 0; k < 4; k++) {
+		out_new[lane * 4u + k] = ra[k], out_ref[lane * 4u + k] = rb[k];
+		bad += ra[k] != rb[k] ? 1u : 0u;
+	}
+	if (bad) atomicAdd(mismatches, bad);
+}
+
+void srt_launch_selftest_rare(int what, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, unsigned long long *mismatches, void *stream) {
+	if (waves == 0) return;
+	hipLaunchKernelGGL(srt_selftest_rare_kernel, dim3(waves), dim3(64), 0, (hipStream_t)stream, what, in, out_new, out_ref, mismatches);
 }
 
 // ---------------------------------------------------------------------------------

@@ -1025,6 +1025,32 @@ int srt_selftest_math(srt_tracer *t, uint32_t stride, uint64_t out[16]) {
 	return SRT_OK;
 }
 
+int srt_selftest_rare_lanes(srt_tracer *t, int what, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, uint64_t *mismatches) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!in || !out_new || !out_ref || !mismatches || what < 0 || what > 1 || waves == 0 || waves > 65536u)
+		return fail(t, SRT_ERR_INVALID, "srt_selftest_rare_lanes: bad arguments");
+	SRT_HIP(t, hipSetDevice(t->device));
+	const size_t lanes = (size_t)waves * 64u, in_bytes = lanes * 8u * sizeof(uint32_t), out_bytes = lanes * 4u * sizeof(uint32_t);
+	char *d = nullptr; // [in | out_new | out_ref | count]
+	SRT_HIP(t, hipMalloc(reinterpret_cast<void **>(&d), in_bytes + 2 * out_bytes + sizeof(unsigned long long)));
+	uint32_t *d_in = reinterpret_cast<uint32_t *>(d), *d_new = reinterpret_cast<uint32_t *>(d + in_bytes), *d_ref = reinterpret_cast<uint32_t *>(d + in_bytes + out_bytes);
+	unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(d + in_bytes + 2 * out_bytes), h_bad = 0;
+	hipError_t e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, t->stream);
+	if (e == hipSuccess) e = hipMemsetAsync(d_new, 0, 2 * out_bytes + sizeof(unsigned long long), t->stream);
+	if (e == hipSuccess) {
+		srt_launch_selftest_rare(what, d_in, waves, d_new, d_ref, d_bad, t->stream);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(out_new, d_new, out_bytes, hipMemcpyDeviceToHost, t->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(out_ref, d_ref, out_bytes, hipMemcpyDeviceToHost, t->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, d_bad, sizeof h_bad, hipMemcpyDeviceToHost, t->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+	(void)hipFree(d);
+	if (e != hipSuccess) return fail(t, SRT_ERR_HIP, std::string("srt_selftest_rare_lanes: ") + hipGetErrorString(e));
+	*mismatches = h_bad;
+	return SRT_OK;
+}
+
 int srt_set_acceleration(srt_tracer *t, int mode) {
 	if (!t) return SRT_ERR_INVALID;
 	if (mode != SRT_ACCEL_NONE && mode != SRT_ACCEL_BVH) return fail(t, SRT_ERR_INVALID, "srt_set_acceleration: unknown mode");

@@ -509,8 +509,13 @@
 					if ((shm & ~lastm) != 0ull) { // (wave-uniform) somebody bounces on: see `lastm` above
 						SRT_REGION(SHADE_BOUNCE);
 						// cosine weighted direction: 6 draws (render.cl:421, 156-163)
-						f3 rd_ = normalize3(random_normal3(seed));
-						f3 hemi = rd_ * sign_fast(dot3(nrm, rd_));
+						// The once-in-2^32 cases of a bounce (a count of 0 or 2^32, a dot product of +-0 or NaN) are decided by one vote per
+						// WAVE in the scene classes' kernels, and the lanes run without the selects and clamps for them. The general kernels
+						// keep the per-lane forms: the second copy of each stretch costs them 4 VGPRs, and the sphere / plane ones among them
+						// a wave per SIMD.
+						f3 rd_ = normalize3(FAST ? random_normal3(seed) : random_normal3_lane(seed));
+						const float rd_side = dot3(nrm, rd_);
+						f3 hemi = FAST ? mul_sign_wave(rd_, rd_side) : rd_ * sign_fast(rd_side);
 						f3 random_dir = normalize3(nrm + hemi);
 						f3 reflected_dir = reflect3(dir, nrm);
 						// the three material draws (render.cl:427-430; nothing else draws in between)
@@ -559,7 +564,8 @@
 						}
 						SRT_REGION(SHADE_TAIL);
 						dir = normalize3(dir);
-						org = pos + (nrm * sign_fast(dot3(nrm, dir))) * 0.001f; // render.cl:462
+						const float out_side = dot3(nrm, dir);
+						org = pos + (FAST ? mul_sign_wave(nrm, out_side) : nrm * sign_fast(out_side)) * 0.001f; // render.cl:462
 						bounce++;
 					}
 				}

@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "srt_get_counters", "srt_set_count_triangles", "srt_reset_counters", "srt_last_kernel_ms", "srt_set_kernel_timers", "srt_last_trace_kernel_ms", "srt_last_trace_launches",
     "srt_device_buffers", "srt_bind_canvas", "srt_bind_stream", "srt_set_partition",
     "srt_partition_owned_rows", "srt_partition_padded_rows", "srt_partition_global_row",
-    "srt_partition_unpermute", "srt_selftest_math", "srt_version", "srt_set_acceleration", "srt_acceleration_info", "srt_bvh_build_host", "srt_bvh_wide_host", "srt_debug_counters", "srt_debug_region_counters",
+    "srt_partition_unpermute", "srt_selftest_math", "srt_selftest_rare_lanes", "srt_version", "srt_set_acceleration", "srt_acceleration_info", "srt_bvh_build_host", "srt_bvh_wide_host", "srt_debug_counters", "srt_debug_region_counters",
     "srt_comm_unique_id", "srt_comm_init", "srt_gather", "srt_resolve_gathered", "srt_gathered_buffers", "srt_read_gathered",
     "srt_group_create", "srt_group_destroy", "srt_group_last_error", "srt_group_size", "srt_group_tracer", "srt_group_set_skybox",
     "srt_group_set_acceleration", "srt_group_update_scene", "srt_group_clear_canvas", "srt_group_trace_and_gather", "srt_group_render",
@@ -313,6 +313,8 @@ def _bind(lib):
     lib.srt_partition_unpermute.argtypes = [vp, vp, i, i, i, sz]
     if hasattr(lib, "srt_selftest_math"):  # absent only in older A/B builds selected through SRT_LIB
         lib.srt_selftest_math.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "srt_selftest_rare_lanes"):  # (the same)
+        lib.srt_selftest_rare_lanes.argtypes = [vp, i, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     lib.srt_version.restype = C.c_char_p
     if hasattr(lib, "srt_set_acceleration"):
         lib.srt_set_acceleration.argtypes = [vp, i]
@@ -640,6 +642,16 @@ class Tracer(_Denoise):
         out = (C.c_uint64 * 16)()
         self._check(self.lib.srt_selftest_math(self._h, stride, out))
         return [int(v) for v in out]
+
+    def selftest_rare_lanes(self, what, words):
+        """words: uint32 [lanes, 8], lanes a multiple of 64 (one wave each) -> (new [lanes, 4], per-lane reference [lanes, 4], mismatching words)"""
+        words = np.ascontiguousarray(words, np.uint32)
+        assert words.ndim == 2 and words.shape[1] == 8 and words.shape[0] % 64 == 0
+        new, ref, bad = np.zeros((words.shape[0], 4), np.uint32), np.zeros((words.shape[0], 4), np.uint32), C.c_uint64()
+        u32p = C.POINTER(C.c_uint32)
+        self._check(self.lib.srt_selftest_rare_lanes(self._h, int(what), words.ctypes.data_as(u32p), words.shape[0] // 64,
+                                                     new.ctypes.data_as(u32p), ref.ctypes.data_as(u32p), C.byref(bad)))
+        return new, ref, int(bad.value)
 
     def set_kernel_timers(self, enable=True):
         """the render calls record the kernel timers' events too (default: only trace() does)"""
