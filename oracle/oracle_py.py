@@ -56,6 +56,58 @@ def _scene_arrays(shapes, tris, mats, rd, sd):
             R.as_records(rd, R.RENDER_DATA), R.as_records(sd, R.SCENE_DATA))
 
 
+class _TexDesc(C.Structure):  # srt_texture_desc
+    _fields_ = [("rgba", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class _PlaneFrame(C.Structure):  # orc_plane_frame
+    _fields_ = [("has_frame", C.c_int32), ("T", C.c_float * 3), ("B", C.c_float * 3)]
+
+
+class _Textures(C.Structure):  # orc_textures
+    _fields_ = [("images", C.POINTER(_TexDesc)), ("num_images", C.c_int32), ("first_hit_only", C.c_int32), ("bindings", C.c_void_p),
+                ("tri_uvs", C.c_void_p), ("frames", C.POINTER(_PlaneFrame))]
+
+
+class TextureTable:
+    """The texture table of the orc_*_textured entry points (srt_oracle.c orc_textures), kept alive with its arrays.
+    images: list of (H, W, 4) float32, row 0 = bottom; bindings: one records.MATERIAL_TEXTURE per material (index -1: none);
+    uvs: (n_triangles, 3, 2) float32 or None; frames: one entry per shape, None or (T, B) -- the caller makes them
+    (tests/texture_ref.py plane_frame), this module and the C file never do. first_hit_only: hits after a path's first keep
+    the material colour (the tests' coverage probe)."""
+
+    def __init__(self, images, bindings, n_materials, n_shapes, n_triangles, frames, uvs=None, first_hit_only=False):
+        R = _rec()
+        self.images = [np.ascontiguousarray(im, np.float32) for im in images]
+        self.bindings = R.as_records(bindings, R.MATERIAL_TEXTURE).copy()
+        assert len(self.bindings) == n_materials and len(frames) == n_shapes
+        for b in self.bindings:
+            assert -1 <= int(b["texture"]) < len(self.images) and int(b["filter"]) in (0, 1)
+        self.descs = (_TexDesc * max(len(self.images), 1))()
+        for d, im in zip(self.descs, self.images):
+            assert im.ndim == 3 and im.shape[2] == 4 and im.shape[0] >= 1 and im.shape[1] >= 1
+            d.rgba, d.width, d.height = im.ctypes.data, im.shape[1], im.shape[0]
+        self.frames = (_PlaneFrame * max(n_shapes, 1))()
+        for f, tb in zip(self.frames, frames):
+            if tb is not None:
+                f.has_frame = 1
+                f.T[:] = [float(x) for x in np.asarray(tb[0], np.float32)]
+                f.B[:] = [float(x) for x in np.asarray(tb[1], np.float32)]
+        self.uvs = None
+        if uvs is not None:
+            self.uvs = np.ascontiguousarray(uvs, np.float32)
+            assert self.uvs.shape == (n_triangles, 3, 2)
+        self.c = _Textures(self.descs, len(self.images), int(bool(first_hit_only)), self.bindings.ctypes.data,
+                           self.uvs.ctypes.data if self.uvs is not None else None, self.frames)
+
+    def ref(self):
+        return C.byref(self.c)
+
+
+def _tex(textures):
+    return textures.ref() if textures is not None else None
+
+
 class Oracle:
     def __init__(self, kind="oracle"):
         self.kind = kind
@@ -109,6 +161,65 @@ class Oracle:
         if counters:
             return canvas, dict(zip(COUNTER_NAMES, (int(v) for v in ctr))) if ctr is not None else None
         return canvas
+
+    def render_textured(self, rd, sd, shapes, tris, mats, sky, textures, canvas=None, rows=None, nthreads=0, counters=False, row_stride=1):
+        """render() with albedo textures (include/srt_abi.h "albedo textures"; oracle only): `textures` is a TextureTable or
+        None (none: exactly render()). Same rows / stride / counters."""
+        shapes, tris, mats, rd, sd = _scene_arrays(shapes, tris, mats, rd, sd)
+        w, h = int(rd["width"]), int(rd["height"])
+        if canvas is None:
+            canvas = np.zeros((h, w, 4), np.float32)
+        y0, y1 = (0, h) if rows is None else rows
+        sky = np.ascontiguousarray(sky, np.float32)
+        ctr = np.zeros(len(COUNTER_NAMES), np.uint64)
+        self.lib.orc_render_textured.restype = None
+        self.lib.orc_render_textured(_p(rd), _p(sd), _p(canvas), _p(shapes), _p(tris), _p(mats), _p(sky), C.c_int(sky.shape[1]),
+                                     C.c_int(sky.shape[0]), _tex(textures), C.c_int(y0), C.c_int(y1), C.c_int(row_stride),
+                                     C.c_int(nthreads), _p(ctr))
+        if counters:
+            return canvas, dict(zip(COUNTER_NAMES, (int(v) for v in ctr)))
+        return canvas
+
+    def trace_paths_textured(self, rd, sd, shapes, tris, mats, sky, textures, pixel_ids, samples):
+        """trace_paths() with albedo textures (oracle only) -> radiance (n, 3) float32, lookups (n, 3) int32: per path the
+        texels read at its first hit and at its later hits (a hit reads one when its material has a texture bound, a plane
+        has a frame and the path bounces on), and the specular bounces among them whose mix(texel, 1, 1) is not 1.0f."""
+        pixel_ids = np.ascontiguousarray(pixel_ids, np.int32)
+        samples = np.ascontiguousarray(samples, np.int32)
+        out = np.zeros((len(pixel_ids), 3), np.float32)
+        looks = np.zeros((len(pixel_ids), 3), np.int32)
+        shapes, tris, mats, rd, sd = _scene_arrays(shapes, tris, mats, rd, sd)
+        sky = np.ascontiguousarray(sky, np.float32)
+        self.lib.orc_trace_paths_textured.restype = None
+        self.lib.orc_trace_paths_textured(_p(rd), _p(sd), _p(shapes), _p(tris), _p(mats), _p(sky), C.c_int(sky.shape[1]),
+                                          C.c_int(sky.shape[0]), _tex(textures), _p(pixel_ids), _p(samples),
+                                          C.c_int(len(pixel_ids)), _p(out), _p(looks))
+        return out, looks
+
+    def features_textured(self, rd, sd, shapes, tris, mats, textures, feature_samples, normal_depth=None, albedo_hits=None, nthreads=0):
+        """features() with albedo textures (oracle only): the albedo of a hit is the texel where its material has one."""
+        shapes, tris, mats, rd, sd = _scene_arrays(shapes, tris, mats, rd, sd)
+        w, h = int(rd["width"]), int(rd["height"])
+        if normal_depth is None:
+            normal_depth = np.zeros((h, w, 4), np.float32)
+        if albedo_hits is None:
+            albedo_hits = np.zeros((h, w, 4), np.float32)
+        for a in (normal_depth, albedo_hits):
+            assert a.dtype == np.float32 and a.shape == (h, w, 4) and a.flags.c_contiguous
+        self.lib.orc_features_textured.restype = None
+        self.lib.orc_features_textured(_p(rd), _p(sd), _p(shapes), _p(tris), _p(mats), _tex(textures), C.c_int(feature_samples),
+                                       _p(normal_depth), _p(albedo_hits), C.c_int(nthreads))
+        return normal_depth, albedo_hits
+
+    def sample_texture(self, image, filt, u, v, scale_u=1.0, scale_v=1.0):
+        """The C texture sampler alone (oracle only): image (H, W, 4) float32, u, v (n,) before the scale -> (n, 3)."""
+        image = np.ascontiguousarray(image, np.float32)
+        u, v = np.ascontiguousarray(u, np.float32).reshape(-1), np.ascontiguousarray(v, np.float32).reshape(-1)
+        out = np.zeros((len(u), 3), np.float32)
+        self.lib.orc_sample_texture.restype = None
+        self.lib.orc_sample_texture(_p(image), C.c_int(image.shape[1]), C.c_int(image.shape[0]), C.c_int(filt), C.c_float(scale_u),
+                                    C.c_float(scale_v), _p(u), _p(v), C.c_size_t(len(u)), _p(out))
+        return out
 
     def average(self, num_steps, canvas):
         canvas = np.ascontiguousarray(canvas, np.float32)

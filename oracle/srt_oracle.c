@@ -23,6 +23,13 @@
  * bounds against glibc (tests/test_detmath.py) and to statistical agreement with a glibc-backed
  * build of the same object (tests/test_oracle_statistics.py). See DESIGN.md "Oracle and parity".
  *
+ * The TEXTURED entry points (orc_render_textured, orc_trace_paths_textured, orc_features_textured, orc_sample_texture)
+ * restate this repository's own contract, include/srt_abi.h "albedo textures": they have no counterpart in the reference and
+ * no `_ref` build to check against. What earns them trust is tests/test_oracle_textures.py: with nothing bound they are the
+ * untextured functions bit for bit, at the first hit they equal the independent numpy restatement tests/texture_ref.py,
+ * and hand-computed paths pin how the texel meets the mask. The untextured entry points pass a NULL table and compile
+ * `trace` without a trace of it (trace_body's `textured` is a literal).
+ *
  * Build: gcc -O2 -ffp-contract=off [-mfma] -fopenmp -fPIC -shared (oracle/Makefile).
  */
 #include <stdint.h>
@@ -210,6 +217,22 @@ int orc_intersection_aabb(const float *bmin, const float *bmax, const float *o, 
 	return tmin < tmax;
 }
 
+/* ---- albedo textures (include/srt_abi.h "albedo textures"): this repository's own contract, no counterpart in the
+ * reference. The table a caller hands to the orc_*_textured entry points; NULL means no textures at all. ---- */
+typedef struct {
+	int32_t has_frame; /* 0: the plane's normal is zero or not finite -- it keeps the material colour */
+	float T[3], B[3];  /* tests/texture_ref.py plane_frame (float64, rounded to float32); never made here */
+} orc_plane_frame;
+
+typedef struct {
+	const srt_texture_desc *images; /* rgba, width, height; row 0 = bottom */
+	int32_t num_images;
+	int32_t first_hit_only; /* coverage probe of the tests: hits after a path's first keep the material colour */
+	const srt_material_texture *bindings; /* one per material */
+	const float *tri_uvs;                 /* num triangles x 3 x 2, or NULL */
+	const orc_plane_frame *frames;        /* one per shape (read for planes only) */
+} orc_textures;
+
 typedef struct {
 	const srt_scene_data *data;
 	const srt_shape *shapes;
@@ -217,12 +240,15 @@ typedef struct {
 	const srt_material *materials;
 	const float *sky; /* RGBA32F, row 0 first */
 	int sky_w, sky_h;
+	const orc_textures *tex; /* NULL: none (every reference-parity entry point) */
 } scene_t;
 
 typedef struct {
 	v3 position, normal;
 	int front;
 	float t; /* tmin: the distance along the (unit) ray to the closest hit, INFINITY when nothing was hit */
+	int shape;    /* index of the closest shape; written with tmin */
+	uint32_t tri; /* a model's winning triangle, counted from its triangle_index; written with tmin */
 } hit_t;
 
 /* render.cl:293-378 */
@@ -243,6 +269,7 @@ static int closest_intersection(const scene_t *scene, v3 org, v3 dir, hit_t *ray
 				if (t_i < tmin) {
 					tmin = t_i;
 					closest = shape->material;
+					rayhit->shape = i;
 					rayhit->position = vadd(org, vscale(dir, tmin));
 					rayhit->normal = vdivs(vsub(rayhit->position, f3(&sphere->position)), sphere->radius);
 				}
@@ -268,6 +295,8 @@ static int closest_intersection(const scene_t *scene, v3 org, v3 dir, hit_t *ray
 					if (t_i < tmin) {
 						tmin = t_i;
 						closest = shape->material;
+						rayhit->shape = i;
+						rayhit->tri = (uint32_t)j;
 						rayhit->position = vadd(org, vscale(dir, tmin));
 						/* render.cl:340-343 smooth shading; forward matrix, w = 0 */
 						v3 w = barycentric_weights(p0, p1, p2, rayhit->position);
@@ -287,6 +316,7 @@ static int closest_intersection(const scene_t *scene, v3 org, v3 dir, hit_t *ray
 				if (t_i < tmin) {
 					tmin = t_i;
 					closest = shape->material;
+					rayhit->shape = i;
 					rayhit->normal = f3(&plane->normal);
 					rayhit->position = vadd(org, vscale(dir, tmin));
 				}
@@ -339,8 +369,88 @@ static v3 sky_box(const scene_t *scene, v3 dir) {
 	return vadd(sample_sky(scene, u, v), sun);
 }
 
-/* render.cl:396-471 */
-static v3 trace(const srt_render_data *render, const scene_t *scene, v3 org, v3 dir, uint32_t seed, uint64_t *ctr) {
+/* ---- albedo textures: include/srt_abi.h "albedo textures", restated from the header's words ---------------------- */
+static inline int wrapi(int x, int n) { /* x mod n, never negative */
+	int m = x % n;
+	return m < 0 ? m + n : m;
+}
+
+/* The sampler, addressing REPEAT, over a W x H image (row 0 = bottom); u, v already scaled. */
+static v3 sample_texture(const float *rgba, int W, int H, int filter, float u, float v) {
+	float fu = u * (float)W, fv = v * (float)H;
+	if (filter == SRT_FILTER_LINEAR) {
+		fu = fu - 0.5f;
+		fv = fv - 0.5f;
+	}
+	/* NaN, infinite or not below 2^30 in magnitude: the texel (0, 0) as stored */
+	if (!(dm_fabs(fu) < 1073741824.0f) || !(dm_fabs(fv) < 1073741824.0f)) return V(rgba[0], rgba[1], rgba[2]);
+	float x0f = __builtin_floorf(fu), y0f = __builtin_floorf(fv);
+	int i0 = wrapi((int)x0f, W), j0 = wrapi((int)y0f, H);
+	const float *T00 = rgba + 4 * ((size_t)j0 * W + i0);
+	if (filter != SRT_FILTER_LINEAR) return V(T00[0], T00[1], T00[2]);
+	float a = fu - x0f, b = fv - y0f;
+	int i1 = wrapi(i0 + 1, W), j1 = wrapi(j0 + 1, H);
+	const float *T10 = rgba + 4 * ((size_t)j0 * W + i1);
+	const float *T01 = rgba + 4 * ((size_t)j1 * W + i0);
+	const float *T11 = rgba + 4 * ((size_t)j1 * W + i1);
+	float w00 = (1.0f - a) * (1.0f - b), w10 = a * (1.0f - b), w01 = (1.0f - a) * b, w11 = a * b;
+	return V(dm_bilinear(w00, T00[0], w10, T10[0], w01, T01[0], w11, T11[0]),
+	         dm_bilinear(w00, T00[1], w10, T10[1], w01, T01[1], w11, T11[1]),
+	         dm_bilinear(w00, T00[2], w10, T10[2], w01, T01[2], w11, T11[2]));
+}
+
+/* dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, unfused (the plane's UV) */
+static inline float dot_unfused(v3 a, const float *b) { return (a.x * b[0] + a.y * b[1]) + a.z * b[2]; }
+
+/* The colour a hit multiplies into the mask: the texel at the hit's UV where its material has a texture bound (a plane
+ * needs a frame besides), else the material colour. *looked = 1 when a texel was read. X = hit->position. */
+static v3 albedo(const scene_t *scene, const hit_t *hit, int material_index, int *looked) {
+	const orc_textures *tex = scene->tex;
+	const srt_material_texture *bind = &tex->bindings[material_index];
+	const v3 mcolor = f3(&scene->materials[material_index].color);
+	*looked = 0;
+	if (bind->texture < 0) return mcolor;
+	const srt_shape *shape = &scene->shapes[hit->shape];
+	const v3 X = hit->position;
+	float u, v;
+	if (shape->type == SRT_SHAPE_SPHERE) {
+		/* the normal as made from X, whichever side was hit */
+		v3 n = vdivs(vsub(X, f3(&shape->shape.sphere.position)), shape->shape.sphere.radius);
+		u = dm_atan2pif(n.z, n.x) * 0.5f + 0.5f;
+		v = n.y * 0.5f + 0.5f;
+	} else if (shape->type == SRT_SHAPE_PLANE) {
+		const orc_plane_frame *fr = &tex->frames[hit->shape];
+		if (!fr->has_frame) return mcolor;
+		v3 d = vsub(X, f3(&shape->shape.plane.position));
+		u = dot_unfused(d, fr->T);
+		v = dot_unfused(d, fr->B);
+	} else {
+		const srt_model *model = &shape->shape.model;
+		const size_t ti = (size_t)model->triangle_index + hit->tri;
+		const srt_triangle *tri = &scene->triangles[ti];
+		v3 p0 = mat_by_vec(model->transform, f3(&tri->vertices[0].pos), 1.0f);
+		v3 p1 = mat_by_vec(model->transform, f3(&tri->vertices[1].pos), 1.0f);
+		v3 p2 = mat_by_vec(model->transform, f3(&tri->vertices[2].pos), 1.0f);
+		v3 w = barycentric_weights(p0, p1, p2, X); /* (w2, w0, w1): the shading's weights */
+		const float w2 = w.x, w0 = w.y, w1 = w.z;
+		u = w0, v = w1;
+		if (tex->tri_uvs) {
+			const float *t = tex->tri_uvs + 6 * ti;
+			u = (t[0] * w2 + t[2] * w0) + t[4] * w1;
+			v = (t[1] * w2 + t[3] * w0) + t[5] * w1;
+		}
+	}
+	const srt_texture_desc *img = &tex->images[bind->texture];
+	*looked = 1;
+	return sample_texture(img->rgba, img->width, img->height, bind->filter, u * bind->scale_u, v * bind->scale_v);
+}
+
+/* render.cl:396-471. One body, compiled twice: `textured` is a literal at both call sites, so the untextured form is the
+ * reference's text and nothing else. lookups (textured only, may be NULL): [0] += texels read at the path's first hit,
+ * [1] += texels read at later hits, [2] += specular bounces whose mix(texel, 1, 1) is not 1.0f in every channel (the
+ * texel's bits reach the mask where a colour "is ignored"). */
+static inline __attribute__((always_inline)) v3 trace_body(const srt_render_data *render, const scene_t *scene, v3 org, v3 dir, uint32_t seed,
+                                                           uint64_t *ctr, const int textured, int32_t *lookups) {
 	v3 color = V(0.f, 0.f, 0.f);
 	v3 mask = V(1.f, 1.f, 1.f);
 	hit_t rayhit;
@@ -366,10 +476,18 @@ static v3 trace(const srt_render_data *render, const scene_t *scene, v3 org, v3 
 			int is_specular = material->specular > orc_random_float(&seed);
 			v3 rough_dir = vmix(random_dir, reflected_dir, material->smoothness);
 			int is_transparent = material->transmittance > orc_random_float(&seed);
+			v3 mcolor = f3(&material->color);
+			int looked = 0;
+			if (textured && !(scene->tex->first_hit_only && i > 0)) {
+				mcolor = albedo(scene, &rayhit, material_index, &looked);
+				if (lookups) lookups[i > 0] += looked;
+			}
 
 			if (!is_transparent) {
 				dir = vmix(random_dir, rough_dir, (is_metallic || is_specular) ? 1.0f : 0.0f);
-				mask = vmul(mask, vmix(f3(&material->color), V(1.0f, 1.0f, 1.0f), is_specular ? 1.0f : 0.0f));
+				v3 f = vmix(mcolor, V(1.0f, 1.0f, 1.0f), is_specular ? 1.0f : 0.0f);
+				mask = vmul(mask, f);
+				if (textured && lookups && looked && is_specular && (f.x != 1.0f || f.y != 1.0f || f.z != 1.0f)) lookups[2]++;
 			} else {
 				v3 in_dir = reflect3(rough_dir, rayhit.normal);
 				float mu = rayhit.front ? 1.0f / material->refraction_index : material->refraction_index;
@@ -384,7 +502,7 @@ static v3 trace(const srt_render_data *render, const scene_t *scene, v3 org, v3 
 					float lsq = out_perp.x * out_perp.x + out_perp.y * out_perp.y + out_perp.z * out_perp.z;
 					v3 out_parallel = vscale(rayhit.normal, -dm_sqrtf(dm_fabs(1.0f - lsq)));
 					dir = vadd(out_perp, out_parallel);
-					mask = vmul(mask, f3(&material->color));
+					mask = vmul(mask, mcolor);
 				}
 			}
 			dir = vnormalize(dir);
@@ -397,6 +515,14 @@ static v3 trace(const srt_render_data *render, const scene_t *scene, v3 org, v3 
 		}
 	}
 	return color;
+}
+
+static v3 trace(const srt_render_data *render, const scene_t *scene, v3 org, v3 dir, uint32_t seed, uint64_t *ctr) {
+	return trace_body(render, scene, org, dir, seed, ctr, 0, NULL);
+}
+static v3 trace_textured(const srt_render_data *render, const scene_t *scene, v3 org, v3 dir, uint32_t seed, uint64_t *ctr,
+                         int32_t *lookups) {
+	return trace_body(render, scene, org, dir, seed, ctr, 1, lookups);
 }
 
 /* render.cl:489-516: the camera ray of (pixel id, sample) -> org, unit dir; returns the seed after the two jitter draws */
@@ -413,16 +539,23 @@ static inline uint32_t camera_ray(const srt_render_data *data, uint32_t id, uint
 }
 
 /* render.cl:483-523 for one pixel; returns the per-dispatch colour (already /num_samples) */
-static v3 render_pixel(const srt_render_data *data, const scene_t *scene, int px, int py, uint64_t *ctr) {
+static inline __attribute__((always_inline)) v3 render_pixel_body(const srt_render_data *data, const scene_t *scene, int px, int py,
+                                                                  uint64_t *ctr, const int textured) {
 	uint32_t id = (uint32_t)px + (uint32_t)py * (uint32_t)data->width;
 	v3 color = V(0.f, 0.f, 0.f);
 	for (int sample = 0; sample < data->num_samples; sample++) {
 		v3 org, dir;
 		uint32_t seed = camera_ray(data, id, (uint32_t)sample, &org, &dir);
 		ctr[ORC_C_PATHS]++;
-		color = vadd(color, trace(data, scene, org, dir, seed, ctr));
+		color = vadd(color, textured ? trace_textured(data, scene, org, dir, seed, ctr, NULL) : trace(data, scene, org, dir, seed, ctr));
 	}
 	return vdivs(color, (float)data->num_samples);
+}
+static v3 render_pixel(const srt_render_data *data, const scene_t *scene, int px, int py, uint64_t *ctr) {
+	return render_pixel_body(data, scene, px, py, ctr, 0);
+}
+static v3 render_pixel_textured(const srt_render_data *data, const scene_t *scene, int px, int py, uint64_t *ctr) {
+	return render_pixel_body(data, scene, px, py, ctr, 1);
 }
 
 /* The `render` kernel over rows [y0, y1): canvas[id] += colour. canvas is the full
@@ -430,6 +563,9 @@ static v3 render_pixel(const srt_render_data *data, const scene_t *scene, int px
 void orc_render_strided(const srt_render_data *data, const srt_scene_data *scene_data, float *canvas,
                         const srt_shape *shapes, const srt_triangle *triangles, const srt_material *materials,
                         const float *sky_rgba, int sky_w, int sky_h, int y0, int y1, int ystride, int nthreads,
+                        uint64_t *counters);
+
+static void render_rows(const srt_render_data *data, const scene_t *scene, float *canvas, int y0, int y1, int ystride, int nthreads,
                         uint64_t *counters);
 
 void orc_render(const srt_render_data *data, const srt_scene_data *scene_data, float *canvas,
@@ -444,7 +580,21 @@ void orc_render_strided(const srt_render_data *data, const srt_scene_data *scene
                         const srt_shape *shapes, const srt_triangle *triangles, const srt_material *materials,
                         const float *sky_rgba, int sky_w, int sky_h, int y0, int y1, int ystride, int nthreads,
                         uint64_t *counters) {
-	scene_t scene = {scene_data, shapes, triangles, materials, sky_rgba, sky_w, sky_h};
+	scene_t scene = {scene_data, shapes, triangles, materials, sky_rgba, sky_w, sky_h, NULL};
+	render_rows(data, &scene, canvas, y0, y1, ystride, nthreads, counters);
+}
+
+/* The same with albedo textures (tex == NULL: none, and then this is orc_render_strided). */
+void orc_render_textured(const srt_render_data *data, const srt_scene_data *scene_data, float *canvas, const srt_shape *shapes,
+                         const srt_triangle *triangles, const srt_material *materials, const float *sky_rgba, int sky_w, int sky_h,
+                         const orc_textures *tex, int y0, int y1, int ystride, int nthreads, uint64_t *counters) {
+	scene_t scene = {scene_data, shapes, triangles, materials, sky_rgba, sky_w, sky_h, tex};
+	render_rows(data, &scene, canvas, y0, y1, ystride, nthreads, counters);
+}
+
+static void render_rows(const srt_render_data *data, const scene_t *scene, float *canvas, int y0, int y1, int ystride, int nthreads,
+                        uint64_t *counters) {
+	const int textured = scene->tex != NULL && !data->show_normals; /* chosen once per call */
 	uint64_t total[ORC_C_COUNT];
 	memset(total, 0, sizeof total);
 #ifdef _OPENMP
@@ -463,7 +613,7 @@ void orc_render_strided(const srt_render_data *data, const srt_scene_data *scene
 		for (int r = 0; r < nrows; r++) {
 			for (int x = 0; x < data->width; x++) {
 				const int y = y0 + r * ystride;
-				v3 c = render_pixel(data, &scene, x, y, ctr);
+				v3 c = textured ? render_pixel_textured(data, scene, x, y, ctr) : render_pixel(data, scene, x, y, ctr);
 				float *out = canvas + 4 * ((size_t)y * data->width + x);
 				out[0] += c.x;
 				out[1] += c.y;
@@ -482,7 +632,7 @@ void orc_render_strided(const srt_render_data *data, const srt_scene_data *scene
 void orc_trace_paths(const srt_render_data *data, const srt_scene_data *scene_data, const srt_shape *shapes,
                      const srt_triangle *triangles, const srt_material *materials, const float *sky_rgba, int sky_w,
                      int sky_h, const int32_t *pixel_ids, const int32_t *samples, int n, float *out_rgb) {
-	scene_t scene = {scene_data, shapes, triangles, materials, sky_rgba, sky_w, sky_h};
+	scene_t scene = {scene_data, shapes, triangles, materials, sky_rgba, sky_w, sky_h, NULL};
 	uint64_t ctr[ORC_C_COUNT];
 	memset(ctr, 0, sizeof ctr);
 	for (int k = 0; k < n; k++) {
@@ -495,13 +645,36 @@ void orc_trace_paths(const srt_render_data *data, const srt_scene_data *scene_da
 	}
 }
 
+/* The same with albedo textures (tex may be NULL). out_lookups (may be NULL): three counts per path, the texels read at its
+ * first hit and at its later hits -- only hits that bounce on read one (the last bounce adds emission alone) -- and the
+ * specular bounces among them whose mix(texel, 1, 1) is not 1.0f. */
+void orc_trace_paths_textured(const srt_render_data *data, const srt_scene_data *scene_data, const srt_shape *shapes,
+                              const srt_triangle *triangles, const srt_material *materials, const float *sky_rgba, int sky_w,
+                              int sky_h, const orc_textures *tex, const int32_t *pixel_ids, const int32_t *samples, int n,
+                              float *out_rgb, int32_t *out_lookups) {
+	scene_t scene = {scene_data, shapes, triangles, materials, sky_rgba, sky_w, sky_h, tex};
+	const int textured = tex != NULL && !data->show_normals;
+#pragma omp parallel for schedule(dynamic, 64)
+	for (int k = 0; k < n; k++) {
+		uint64_t ctr[ORC_C_COUNT] = {0};
+		int32_t looks[3] = {0, 0, 0};
+		v3 org, dir;
+		uint32_t seed = camera_ray(data, (uint32_t)pixel_ids[k], (uint32_t)samples[k], &org, &dir);
+		v3 c = textured ? trace_textured(data, &scene, org, dir, seed, ctr, looks) : trace(data, &scene, org, dir, seed, ctr);
+		out_rgb[3 * k + 0] = c.x;
+		out_rgb[3 * k + 1] = c.y;
+		out_rgb[3 * k + 2] = c.z;
+		if (out_lookups) out_lookups[3 * k + 0] = looks[0], out_lookups[3 * k + 1] = looks[1], out_lookups[3 * k + 2] = looks[2];
+	}
+}
+
 /* The primary hit of single (pixel, sample) camera rays, for the denoiser's guide buffers. out: 8 floats per ray:
  * the unit direction, tmin, the front-facing normal (0 without a hit) and the material index (-1: sky, or a shape
  * without a material -- render.cl:404 shades neither). */
 void orc_primary_hits(const srt_render_data *data, const srt_scene_data *scene_data, const srt_shape *shapes,
                       const srt_triangle *triangles, const srt_material *materials, const int32_t *pixel_ids,
                       const int32_t *samples, int n, float *out) {
-	scene_t scene = {scene_data, shapes, triangles, materials, NULL, 0, 0};
+	scene_t scene = {scene_data, shapes, triangles, materials, NULL, 0, 0, NULL};
 	uint64_t ctr[ORC_C_COUNT];
 	memset(ctr, 0, sizeof ctr);
 	for (int k = 0; k < n; k++) {
@@ -521,10 +694,23 @@ void orc_primary_hits(const srt_render_data *data, const srt_scene_data *scene_d
  * its samples 0 .. min(feature_samples, max(num_samples, 0)) - 1 in order, float32 partial sums of {front-facing normal,
  * tmin} and {material colour, 1} over the hits and {1, 1, 1, 0} over the misses, then added into normal_depth and
  * albedo_hits ((h, w, 4) float32 each). */
+void orc_features_textured(const srt_render_data *data, const srt_scene_data *scene_data, const srt_shape *shapes,
+                           const srt_triangle *triangles, const srt_material *materials, const orc_textures *tex,
+                           int feature_samples, float *normal_depth, float *albedo_hits, int nthreads);
+
 void orc_features(const srt_render_data *data, const srt_scene_data *scene_data, const srt_shape *shapes,
                   const srt_triangle *triangles, const srt_material *materials, int feature_samples, float *normal_depth,
                   float *albedo_hits, int nthreads) {
-	scene_t scene = {scene_data, shapes, triangles, materials, NULL, 0, 0};
+	orc_features_textured(data, scene_data, shapes, triangles, materials, NULL, feature_samples, normal_depth, albedo_hits, nthreads);
+}
+
+/* The same with albedo textures (tex may be NULL): the albedo of a hit is the texel where its material has one bound.
+ * show_normals ignores textures here as in the trace. */
+void orc_features_textured(const srt_render_data *data, const srt_scene_data *scene_data, const srt_shape *shapes,
+                           const srt_triangle *triangles, const srt_material *materials, const orc_textures *tex,
+                           int feature_samples, float *normal_depth, float *albedo_hits, int nthreads) {
+	scene_t scene = {scene_data, shapes, triangles, materials, NULL, 0, 0, tex};
+	const int textured = tex != NULL && !data->show_normals;
 	const int ns = data->num_samples > 0 ? data->num_samples : 0;
 	const int fs = feature_samples < ns ? feature_samples : ns;
 	const int npix = data->width * data->height;
@@ -550,7 +736,8 @@ void orc_features(const srt_render_data *data, const srt_scene_data *scene_data,
 				if (material >= 0) {
 					nsum = vadd(nsum, hit.normal);
 					tsum = tsum + hit.t;
-					asum = vadd(asum, f3(&scene.materials[material].color));
+					int looked;
+					asum = vadd(asum, textured ? albedo(&scene, &hit, material, &looked) : f3(&scene.materials[material].color));
 					hits = hits + 1.0f;
 				} else {
 					asum = vadd(asum, V(1.f, 1.f, 1.f));
@@ -605,11 +792,19 @@ void orc_barycentric_weights(const float *p0, const float *p1, const float *p2, 
 	out3[2] = w.z;
 }
 void orc_sky_box(const srt_scene_data *sd, const float *sky, int w, int h, const float *dir, float *out3) {
-	scene_t scene = {sd, NULL, NULL, NULL, sky, w, h};
+	scene_t scene = {sd, NULL, NULL, NULL, sky, w, h, NULL};
 	v3 c = sky_box(&scene, V(dir[0], dir[1], dir[2]));
 	out3[0] = c.x;
 	out3[1] = c.y;
 	out3[2] = c.z;
+}
+/* The texture sampler alone: n coordinates (u, v) before the scale -> n x 3 texels. */
+void orc_sample_texture(const float *rgba, int w, int h, int filter, float scale_u, float scale_v, const float *u, const float *v,
+                        size_t n, float *out_rgb) {
+	for (size_t k = 0; k < n; k++) {
+		v3 c = sample_texture(rgba, w, h, filter, u[k] * scale_u, v[k] * scale_v);
+		out_rgb[3 * k + 0] = c.x, out_rgb[3 * k + 1] = c.y, out_rgb[3 * k + 2] = c.z;
+	}
 }
 void orc_aces(const float *in3, float *out3) {
 	for (int k = 0; k < 3; k++) out3[k] = aces1(in3[k]);

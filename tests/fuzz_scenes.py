@@ -18,15 +18,19 @@ demand lane intention == restatement == library.
                   materials appended (the scene records no longer fit LDS), and a sphere / plane scene of several block groups
   tex_*           the same scenes with every material bound NEAREST to a texture whose texels all equal its colour: the
                   textured twins must give the UNTEXTURED oracle's canvas
+  texvar_*        the tex_* scenes with images of 1x1 to 5x4 random texels (finite, not negative) and random filters: the
+                  textured twins must give the TEXTURED oracle's canvas (oracle/srt_oracle.c orc_render_textured)
 """
 import numpy as np
 
+import texture_cases
 from simple_raytracer_amd import records as R, scenes as S
 
 F = np.float32
 GENERAL, PPS, PPS_SPECULAR, SSS, PPP = 0, 1, 2, 3, 4  # device_types.h SRT_SCENE_CLASS_LIST
 ACCEL_NONE, ACCEL_BVH = 0, 1
 NEAREST = 1
+LINEAR = 0
 MAX_TEXTURES = 64
 PAD_MATERIALS = 80  # 80 more 64-byte materials: no scene fits the 4608-byte LDS copy
 FRAME = (23, 17)  # ragged: 391 pixels, the last wave is partial
@@ -467,7 +471,22 @@ def constant_textures(rng, mats, tris, hostile):
     return {"images": images, "bindings": bindings, "rejected": rejected, "uvs": uvs}
 
 
-def textured_lane(kind):
+def varying_textures(rng, mats, tris, hostile):
+    """constant_textures' bindings, scales, UVs and refused NaN scale, but the images are 1x1 to 5x4 with random finite texels
+    that are not negative, and the filters are random: the expectation is the TEXTURED oracle's canvas."""
+    tex = constant_textures(rng, mats, tris, hostile)
+    images = []
+    for _ in tex["images"]:
+        img = np.ones((int(rng.randint(1, 5)), int(rng.randint(1, 6)), 4), F)
+        img[..., :3] = rng.uniform(0.0, 1.5, img.shape[:2] + (3,)).astype(F)
+        images.append(img)
+    for b in (tex["bindings"], tex["rejected"]):
+        if b is not None:
+            b["filter"] = np.where(rng.rand(len(mats)) < 0.5, LINEAR, NEAREST)
+    return dict(tex, images=images, varying=True)
+
+
+def textured_lane(kind, varying=False):
     def lane(rng, hostile, it):
         if kind == "class":
             base = class_lane((PPS, PPS_SPECULAR, SSS, PPP)[it % 4])
@@ -476,7 +495,7 @@ def textured_lane(kind):
         else:  # scan / bvh: plain and with the padding materials in turn
             base = general_lane(kind + ("_pad" if it % 2 else ""))
         shapes, tris, mats, cam, rd, sd, _, extra = base(rng, hostile, it)
-        extra = dict(extra, textures=constant_textures(rng, mats, tris, hostile))
+        extra = dict(extra, textures=(varying_textures if varying else constant_textures)(rng, mats, tris, hostile))
         return shapes, tris, mats, cam, rd, sd, (GENERAL, not rd["show_normals"]), extra
     return lane
 
@@ -486,11 +505,18 @@ LANES = {"class1": class_lane(PPS), "class2": class_lane(PPS_SPECULAR), "class3"
          "scan": general_lane("scan"), "bvh": general_lane("bvh"), "scan_pad": general_lane("scan_pad"), "bvh_pad": general_lane("bvh_pad"),
          "shapes_only": general_lane("shapes_only"),
          "tex_scan": textured_lane("scan"), "tex_bvh": textured_lane("bvh"), "tex_shapes_only": textured_lane("shapes_only"),
-         "tex_class": textured_lane("class")}
+         "tex_class": textured_lane("class"),
+         "texvar_scan": textured_lane("scan", True), "texvar_bvh": textured_lane("bvh", True),
+         "texvar_shapes_only": textured_lane("shapes_only", True), "texvar_class": textured_lane("class", True)}
 CLASS_LANES = {"class1": PPS, "class2": PPS_SPECULAR, "class3": SSS, "class4": PPP}
 # iterations per case = SRT_FUZZ_ITERS (default 300) * share: 50 per class lane, 60 near misses (6 of each edit), 40 per general and
-# per textured lane -- 1,240 scenes over both flavours (tests/test_gpu_fuzz_dispatch.py has the measured cost)
-LANE_SHARE = {name: (1, 5) if name == "near_miss" else (1, 6) if name in CLASS_LANES else (2, 15) for name in LANES}
+# per tex_* lane, 20 per texvar_* lane -- 1,400 scenes over both flavours (tests/test_gpu_fuzz_dispatch.py has the measured cost).
+# 20: a texvar lane's deterministic branches (plain / padded in turn, the four classes in turn, a budget every third scene) come
+# round in 12 scenes, and its random ones (both filters, a 1x1 and a 4x5 image, a refused NaN scale when hostile) have all been
+# drawn by scene 19 at the latest over the eight cases (texvar_shapes_only benign; the others by scene 12), which
+# tests/test_fuzz_lanes.py asserts at the count in use; 20 is the next share of the base count.
+LANE_SHARE = {name: (1, 5) if name == "near_miss" else (1, 6) if name in CLASS_LANES else (1, 15) if name.startswith("texvar_") else (2, 15)
+              for name in LANES}
 
 
 def lane_iterations(name, base=300):
@@ -559,7 +585,11 @@ def run_lane(T, oracle, sky, name, hostile, iterations, seed=20250, nthreads=4, 
             if not (reported == tuple(expected) == restated):
                 problems.append(f"class / textured: library {reported}, lane {tuple(expected)}, restatement {restated}")
             with np.errstate(all="ignore"):
-                want, oc = oracle.render(rd, sd, shapes, tris, mats, sky, counters=True, nthreads=nthreads)
+                if tex is not None and tex.get("varying"):
+                    table = texture_cases.oracle_table((shapes, tris, mats), tex["images"], tex["bindings"], tex["uvs"])
+                    want, oc = oracle.render_textured(rd, sd, shapes, tris, mats, sky, table, counters=True, nthreads=nthreads)
+                else:
+                    want, oc = oracle.render(rd, sd, shapes, tris, mats, sky, counters=True, nthreads=nthreads)
             bad = differing_pixels(got, want)
             ctr = {k: (c[k], oc[k]) for k in COUNTERS if c[k] != oc[k]}
             if c["watchdog"] != 0:

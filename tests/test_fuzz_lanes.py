@@ -55,11 +55,20 @@ def test_restatement_gives_the_intended_class(name, hostile):
             assert tuple(expected) == (FS.CLASS_LANES[name], False)
         elif name != "near_miss":
             assert expected[0] == FS.GENERAL
-        if name.startswith("tex_"):
+        if name.startswith(("tex_", "texvar_")):
             assert expected[1] == (not rd["show_normals"])
-            assert FS.expected_class(shapes, mats, rd) == (FS.CLASS_LANES[f"class{it % 4 + 1}"] if name == "tex_class" else FS.GENERAL)
+            assert FS.expected_class(shapes, mats, rd) == (FS.CLASS_LANES[f"class{it % 4 + 1}"] if name.endswith("_class") else FS.GENERAL)
+        if name.startswith("texvar_"):
+            tex = extra["textures"]
+            assert all(np.isfinite(im).all() and (im >= 0).all() and not np.signbit(im).any() for im in tex["images"])
+            assert np.isfinite(tex["bindings"]["scale_u"]).all() and np.isfinite(tex["bindings"]["scale_v"]).all()
     if name in ("scan_pad", "bvh_pad"):
         assert all(FS.scene_lds_bytes(len(s[0]), len(s[2])) == 0 for s in scenes)
+    if name.startswith("texvar_"):  # every branch of the image generator: both filters, 1x1 and larger, a refused NaN scale when hostile
+        assert {int(f) for s in scenes for f in s[7]["textures"]["bindings"]["filter"]} == {0, 1}
+        shapes_seen = {im.shape[:2] for s in scenes for im in s[7]["textures"]["images"]}
+        assert (1, 1) in shapes_seen and (4, 5) in shapes_seen
+        assert not hostile or any(s[7]["textures"]["rejected"] is not None for s in scenes)
     if name == "shapes_only":
         assert all(len(FS.shape_blocks(s[0])) > 3 for s in scenes if len(s[0]) > 12)  # several block groups
         assert sum(len(FS.shape_blocks(s[0])) > 3 for s in scenes) >= len(scenes) * 3 // 4
@@ -127,9 +136,10 @@ def test_hostile_scenes_still_show_something(name, sky, oracle):
     """40 hostile scenes per lane through the oracle: at most a quarter have more than half their pixels NaN or exactly the
     sky's value (the same dispatch over no shapes at all); in the class lanes paths bounce (rays > paths)"""
     scenes = lane_scenes(name, True)
-    assert len(scenes) >= HOSTILE_SAMPLE
+    sample = len(scenes) if name.startswith("texvar_") else HOSTILE_SAMPLE  # (the texvar lanes run 20 scenes: all of them, same share)
+    assert len(scenes) >= sample
     blank, rays, paths = 0, 0, 0
-    for shapes, tris, mats, cam, rd, sd, expected, extra in scenes[:HOSTILE_SAMPLE]:
+    for shapes, tris, mats, cam, rd, sd, expected, extra in scenes[:sample]:
         with np.errstate(all="ignore"):
             want, oc = oracle.render(rd, sd, shapes, tris, mats, sky, counters=True, nthreads=4)
             empty_sd = sd.copy()
@@ -140,7 +150,7 @@ def test_hostile_scenes_still_show_something(name, sky, oracle):
         if (nan | only_sky).mean() > 0.5:
             blank += 1
         rays, paths = rays + oc["rays"], paths + oc["paths"]
-    print(f"{name}: {blank} of {HOSTILE_SAMPLE} hostile scenes mostly NaN or sky; rays {rays}, paths {paths}")
-    assert blank <= HOSTILE_SAMPLE // 4, (name, blank)
+    print(f"{name}: {blank} of {sample} hostile scenes mostly NaN or sky; rays {rays}, paths {paths}")
+    assert blank <= sample // 4, (name, blank)
     if name in FS.CLASS_LANES:
         assert rays > paths, (name, rays, paths)

@@ -10,8 +10,9 @@ predicate (no lane can pass by falling back); the canvas is the oracle's bit for
 nan_pixels are the oracle's; the watchdog did not fire.
 
 Iterations per case: SRT_FUZZ_ITERS (default 300) times the lane's share (fuzz_scenes.LANE_SHARE): 50 per class lane, 60
-near misses, 40 per general and textured lane; 1,240 scenes over the 28 cases. Measured on one MI355X box (the oracle on 4
-threads is the cost): RUNTIME below."""
+near misses, 40 per general and tex_* lane, 20 per texvar_* lane (random texels and filters against the TEXTURED oracle; the
+smallest share that visits every branch of their generator: fuzz_scenes.LANE_SHARE); 1,400 scenes over the 36 cases.
+Measured on one MI355X box (the oracle on 4 threads is the cost): RUNTIME below."""
 import os
 
 import pytest
@@ -20,9 +21,11 @@ import fuzz_scenes as FS
 
 pytestmark = pytest.mark.gpu
 
-# Measured on an MI355X box in one session, pytest's call durations summed: tests/test_gpu_fuzz.py (600 scenes) plus the fuzz of
-# tests/test_gpu_bvh.py (150 scenes) 1.11 s (3.3 s with start-up); this module at its defaults (1,240 scenes) 1.79 s (4.0 s): 1.6x.
-RUNTIME = {"test_gpu_fuzz.py + test_gpu_bvh.py fuzz, s": 1.11, "this module, s": 1.79}
+# Measured on an MI355X box, pytest's call durations summed: tests/test_gpu_fuzz.py (600 scenes) plus the fuzz of
+# tests/test_gpu_bvh.py (150 scenes) 1.11 s (3.3 s with start-up); this module at its defaults, before the texvar_* lanes
+# (1,240 scenes), 1.79 s (4.0 s): 1.6x. With them (1,400 scenes, measured in a later session) 1.96 s (4.30 s with start-up), of which
+# the eight texvar_* cases (160 scenes) take 0.32 s; the slowest single case 0.15 s.
+RUNTIME = {"test_gpu_fuzz.py + test_gpu_bvh.py fuzz, s": 1.11, "this module, s": 1.96, "its texvar_* cases, s": 0.32}
 
 
 @pytest.mark.parametrize("hostile", [False, True], ids=["benign", "hostile"])

@@ -1,5 +1,8 @@
-"""GPU: albedo textures (include/srt_abi.h "albedo textures") by identities the frozen oracle can express, bit for bit.
-Off means off; a texture of equal texels sampled NEAREST is exactly a colour (which runs the textured kernels over every
+"""GPU: albedo textures (include/srt_abi.h "albedo textures"), bit for bit: the switch, the first hit and the interfaces.
+What a texel does at the SECOND and later hits of a path -- the whole canvas at full depth against the textured CPU oracle
+(oracle/srt_oracle.c orc_render_textured) -- is tests/test_gpu_texture_paths.py's; the scenes, textures and the numpy route
+to a first-hit texel that both share are tests/texture_cases.py. Here, by identities the untextured oracle expresses:
+off means off; a texture of equal texels sampled NEAREST is exactly a colour (which runs the textured kernels over every
 scene kind at full depth); the denoiser's albedo guide equals tests/texture_ref.py at the oracle's primary hits; a two-bounce
 white scene's canvas equals texel(first hit) * the oracle's white radiance; partitions and groups reproduce the single
 handle; each setter drops the temporal history."""
@@ -13,18 +16,12 @@ import texture_ref as TR
 from conftest import bits_equal
 from gpu_harness import SCENES, T, guide_scene, make, tone  # noqa: F401 (T: the fixture)
 from simple_raytracer_amd import records as R, scenes as S
+from texture_cases import FIRST_HIT_CASES, TEXTURES, bind_all, constant_textures, first_hit_case, first_hit_texels, white_bindings, white_scene
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 W, H = 37, 29
 GOLDEN = golden_io.load_cases()
-
-
-def bind_all(n_materials, texture_of, filt=TR.NEAREST, scale=(1.0, 1.0)):
-    b = np.zeros(n_materials, R.MATERIAL_TEXTURE)
-    for i in range(n_materials):
-        b[i] = R.material_texture(texture_of(i), filt, *scale)
-    return b
 
 
 def render_canvas(T, sky, scn, cam, accel, spp=4, bounces=10, textures=None, bindings=None, uvs=None, w=W, h=H, time=4242, budget=None):
@@ -67,15 +64,6 @@ def test_off_means_off(T, sky, oracle, name, accel):
 
 
 # ---- 5. constant texture = colour --------------------------------------------------------------------------------------
-def constant_textures(mats, side):
-    out = []
-    for m in mats:
-        img = np.ones((side, side, 4), F)
-        img[..., :3] = np.asarray(m["color"], F).reshape(-1)[:3]
-        out.append(img)
-    return out
-
-
 @pytest.mark.parametrize("pad_materials", [0, 80])  # 80 more 64-byte materials: the scene records no longer fit the LDS copy (USE_LDS false)
 @pytest.mark.parametrize("side", [1, 4])
 @pytest.mark.parametrize("name,accel", [s for s in SCENES if s[0] != "empty"])
@@ -137,106 +125,7 @@ def test_show_normals_ignores_textures(T, sky, oracle):
     t.close()
 
 
-# ---- 6 / 7. the texel at the first hit -----------------------------------------------------------------------------------
-def white_scene():
-    """three spheres and two planes (one tilted), every shape its own white diffuse material"""
-    mats = np.array([R.material(color=(1, 1, 1)) for _ in range(5)], R.MATERIAL)
-    shapes = np.array([R.sphere(0, (-1.6, 0.4, -1.0), 0.9), R.sphere(1, (0.3, 0.1, 0.5), 0.6), R.sphere(2, (1.7, 0.8, -2.0), 1.3),
-                       R.plane(3, (0.0, -0.5, 0.0), (0.0, 1.0, 0.0)), R.plane(4, (0.0, 0.0, -6.0), (0.3, 0.2, 1.0))], R.SHAPE)
-    return shapes, np.zeros(0, R.TRIANGLE), mats
-
-
-def white_mesh_scene():
-    """two rotated, non-uniformly scaled box instances over triangle ranges of their own and a floor plane, every shape its
-    own white diffuse material"""
-    mats = np.array([R.material(color=(1, 1, 1)) for _ in range(3)], R.MATERIAL)
-    tris = R.concat(R.TRIANGLE, R.box_triangles(), R.box_triangles())
-    m0 = R.mat_mul(R.mat_mul(R.translate((-1.5, 0.7, 0.8)), R.euler_yxz(0.6, 0.35, 0.2)), R.scale_matrix((1.4, 1.0, 0.8)))
-    m1 = R.mat_mul(R.mat_mul(R.translate((1.5, 0.5, 0.2)), R.euler_yxz(-0.4, 0.2, -0.3)), R.scale_matrix((0.9, 1.5, 1.2)))
-    shapes = np.array([R.model(0, tris, 0, 12, m0), R.plane(1, (0.0, -0.8, 0.0), (0.0, 1.0, 0.0)), R.model(2, tris, 12, 12, m1)], R.SHAPE)
-    return shapes, tris, mats
-
-
-def mesh_uvs():
-    return np.random.default_rng(17).uniform(-1.5, 2.5, (24, 3, 2)).astype(F)
-
-
-def mesh_bindings(filt):
-    b = np.zeros(3, R.MATERIAL_TEXTURE)
-    b[0] = R.material_texture(0, filt, 3.0, 2.0)
-    b[1] = R.material_texture(2, filt, 0.5, 0.25)
-    b[2] = R.material_texture(1, filt, -2.0, 1.5)
-    return b
-
-
-# (scene, bindings, accel, with UVs): spheres and planes; a mesh with UVs and without, array scan and BVH
-FIRST_HIT_CASES = [("shapes", 0, False), ("mesh", 0, True), ("mesh", 0, False), ("mesh", 1, True), ("mesh", 1, False)]
-
-
-def first_hit_case(kind, filt, with_uvs):
-    if kind == "shapes":
-        return white_scene(), white_bindings(filt), None
-    return white_mesh_scene(), mesh_bindings(filt), (mesh_uvs() if with_uvs else None)
-
-
-TEXTURES = [TR.checker(8, 8), TR.gradient(16, 8), TR.checker(5, 3, (0.8, 0.3, 0.2), (0.2, 0.7, 0.9))]
-
-
-def white_bindings(filt):
-    b = np.zeros(5, R.MATERIAL_TEXTURE)
-    b[0] = R.material_texture(0, filt, 4.0, 2.0)
-    b[1] = R.material_texture(1, filt, 1.0, 1.0)
-    b[2] = R.material_texture(2, filt, 1e30, 5.0)  # u * 1e30 * fW >= 2^30 (but at u = 0): texel (0, 0)
-    b[3] = R.material_texture(0, filt, 0.5, 0.5)
-    b[4] = R.material_texture(1, filt, 0.25, -3e38)  # v * -3e38 * fH overflows to an infinity where |v| > 0.15: texel (0, 0)
-    return b
-
-
-def model_hit_uv(oracle, shapes, tris, s, cam, d, t, X, uvs):
-    """UV of primary hits on model s: the triangle by the oracle's intersect_triangle in array order (first of equal t) on the
-    world-space vertices of its matrix_by_vector, the weights by its barycentric_weights at X (they come as w2, w0, w1)."""
-    ti, n = int(shapes["triangle_index"][s]), int(shapes["num_triangles"][s])
-    P = [[oracle.matrix_by_vector(shapes["transform"][s], np.append(tris["v"]["pos"][ti + j][k], F(1)))[:3] for k in range(3)] for j in range(n)]
-    u, v = np.zeros(len(d), F), np.zeros(len(d), F)
-    for i in range(len(d)):
-        best, bt = -1, F(np.inf)
-        for j in range(n):
-            hit, tt = oracle.intersect_triangle(*P[j], cam, d[i])
-            if hit and tt < bt:
-                best, bt = j, tt
-        assert best >= 0 and bt == t[i], (s, i, bt, t[i])
-        w = oracle.barycentric_weights(*P[best], X[i])
-        uu, vv = TR.model_uv(w[1], w[2], w[0], None if uvs is None else uvs[ti + best])
-        u[i], v[i] = uu[0], vv[0]
-    return u, v
-
-
-def first_hit_texels(oracle, rd, sd, scn, bindings, ids, smp, uvs=None):
-    """texture_ref at the oracle's primary hits -> (n, 3) texels ((1, 1, 1) where nothing is hit), hit mask"""
-    shapes, tris, mats = scn
-    ph = oracle.primary_hits(rd, sd, shapes, tris, mats, ids, smp)
-    cam = np.asarray(rd["camera_to_world"], F).reshape(4, 4)[3, :3]
-    d, t = ph["dir"].astype(F), ph["t"].astype(F)
-    with np.errstate(all="ignore"):
-        X = (cam[None, :] + d * t[:, None]).astype(F)  # org + dir * tmin
-    out = np.ones((len(ids), 3), F)
-    hit = ph["material"] >= 0
-    for s in range(len(shapes)):  # every shape has its own material
-        sel = hit & (ph["material"] == shapes["material"][s])
-        if not sel.any():
-            continue
-        b = bindings[shapes["material"][s]]
-        if shapes["type"][s] == R.SHAPE_SPHERE:
-            u, v = TR.sphere_uv(X[sel], shapes["sphere_position"][s], shapes["sphere_radius"][s])
-        elif shapes["type"][s] == R.SHAPE_MODEL:
-            u, v = model_hit_uv(oracle, shapes, tris, s, cam, d[sel], t[sel], X[sel], uvs)
-        else:
-            Tn, Bn = TR.plane_frame(shapes["plane_normal"][s])
-            u, v = TR.plane_uv(X[sel], shapes["plane_position"][s], Tn, Bn)
-        out[sel] = TR.sample(TEXTURES[b["texture"]], b["filter"], u, v, b["scale_u"], b["scale_v"])
-    return out, hit
-
-
+# ---- 6 / 7. the texel at the first hit (scenes, bindings and the numpy route: tests/texture_cases.py) ---------------------
 @pytest.mark.parametrize("fs", [1, 3])
 @pytest.mark.parametrize("filt", [TR.LINEAR, TR.NEAREST])
 @pytest.mark.parametrize("kind,accel,with_uvs", FIRST_HIT_CASES)
