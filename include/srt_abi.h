@@ -112,6 +112,45 @@ int srt_bvh_build_host(const srt_shape *model, const srt_triangle *triangles, si
 int srt_bvh_wide_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, int force_balanced, uint32_t *blocks_out,
                       size_t blocks_cap, uint32_t *dest_out, size_t dest_cap, size_t *n_blocks, uint32_t *root, uint32_t *stack_need, int *balanced);
 
+/* Host-only: order[r] = index inside the model of the triangle in record r of the hierarchy srt_bvh_wide_host hands out for
+ * the same arguments (srt_bvh_build_host's order is that of the SAH form only; the balanced form has its own). Writes at
+ * most order_cap indices; the hierarchy has num_triangles records. */
+int srt_bvh_wide_order_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, int force_balanced,
+                            uint32_t *order_out, size_t order_cap);
+
+/* Host-only: the wide hierarchy of `built` (exactly srt_bvh_wide_host's) refitted IN PLACE for `moved`: the topology it was
+ * folded with is kept -- root, stack need, dest, order, every block's tags, first and child count, the number of blocks --
+ * and every inner block's origin, exponents and byte boxes (dwords 0-9) are recomputed around the moved triangles. `moved`
+ * must have `built`'s triangle_index and num_triangles; only its transform may differ (SRT_ERR_INVALID otherwise). Blocks
+ * as srt_bvh_wide_host hands them out: relative to the model, leaf blocks zero. This is what SRT_REFIT_DEVICE (below)
+ * computes on the device, bit for bit. */
+int srt_bvh_refit_wide_host(const srt_shape *built, const srt_shape *moved, const srt_triangle *triangles, size_t n_triangles,
+                            int force_balanced, uint32_t *blocks_out, size_t blocks_cap, size_t *n_blocks, uint32_t *root);
+
+/* Who refits the hierarchy of a model that only MOVED between two srt_update_scene calls (same triangle bytes, another
+ * transform). SRT_REFIT_HOST, the default: the host recomputes the boxes, folds and quantises them again and uploads the
+ * result, as ever. SRT_REFIT_DEVICE: the host keeps the hierarchy's topology and uploads it as it is; kernels on the
+ * handle's stream, behind the pre-pass, recompute the triangles' boxes, the leaf blocks' boxes and, level by level from
+ * the leaves up, every inner block's byte boxes -- the bytes srt_bvh_refit_wide_host gives. Because the fold is kept where
+ * the host path re-folds, the two hierarchies can differ in shape after a rotation; the walk's result does not depend on
+ * the visiting order, so the canvas is the same. Takes effect at the next srt_update_scene; accepted and without effect
+ * under SRT_ACCEL_NONE. The group form sets every member. */
+#define SRT_REFIT_HOST 0
+#define SRT_REFIT_DEVICE 1
+int srt_set_acceleration_refit(srt_tracer *t, int mode);
+/* out = {models refitted on the device by the last srt_update_scene, inner blocks they requantised, refit launches
+ * enqueued, 0}. A model counts whenever its blocks were uploaded from a hierarchy whose boxes the host no longer keeps
+ * current, also in a call in which it did not move itself. srt_acceleration_info's out[6] counts the models that moved,
+ * whoever refitted them. */
+int srt_acceleration_refit_info(const srt_tracer *t, uint64_t out[4]);
+/* With srt_set_kernel_timers on: the device time of the last srt_update_scene's refit launches, first to last, in
+ * milliseconds (0 when it enqueued none or the timers were off). Blocking. */
+int srt_last_refit_kernel_ms(srt_tracer *t, float *ms);
+/* Tests / inspection: the device's block array as the kernel walks it -- every model's blocks, absolute indices, leaf
+ * blocks with their triangles. Blocking. Writes at most blocks_cap blocks of 32 dwords and always sets *n_blocks (0 without
+ * SRT_ACCEL_BVH or without models); blocks_out may be NULL to only query. */
+int srt_read_bvh_blocks(srt_tracer *t, uint32_t *blocks_out, size_t blocks_cap, size_t *n_blocks);
+
 /* Tracer::clear_canvas — src/tracer.cpp:98-101. With the denoiser on, also its sums and counts. */
 int srt_clear_canvas(srt_tracer *t);
 
@@ -268,6 +307,7 @@ int srt_group_set_textures(srt_group *g, const srt_texture_desc *descs, size_t n
 int srt_group_set_material_textures(srt_group *g, const srt_material_texture *bindings, size_t n_materials);
 int srt_group_set_triangle_uvs(srt_group *g, const float *uv, size_t n_triangles);
 int srt_group_set_acceleration(srt_group *g, int mode);
+int srt_group_set_acceleration_refit(srt_group *g, int mode); /* srt_set_acceleration_refit on every member */
 int srt_group_update_scene(srt_group *g, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
                            const srt_material *materials, size_t n_materials, const srt_scene_data *scene);
 int srt_group_clear_canvas(srt_group *g);

@@ -357,8 +357,28 @@ void BvhBuilder::fold_wide(const std::vector<BvhNode> &c, uint32_t records, bool
 	run(0, nj / parts);
 	for (size_t t = futs.size() + 1; t < parts; t++) run(nj * t / parts, nj * (t + 1) / parts);
 	for (auto &f : futs) f.get();
-	w.jobs.clear();
-	w.jobs.shrink_to_fit();
+	w.sched.clear(), w.level_off.clear();
+}
+
+void BvhBuilder::Wide::ensure_schedule() {
+	if (!level_off.empty() || jobs.empty()) return;
+	std::vector<uint32_t> height(blocks.size() / 32, 0u); // leaf blocks: 0
+	uint32_t top = 0;
+	for (const Job &j : jobs) { // children come before their parent
+		uint32_t h = 0;
+		for (uint32_t k = 0; k < j.nk; k++) h = std::max(h, height[j.first + k]);
+		height[j.self] = h + 1u;
+		top = std::max(top, h + 1u);
+	}
+	level_off.assign(top + 1u, 0u);
+	for (const Job &j : jobs) level_off[height[j.self]]++;
+	for (uint32_t h = 1, sum = 0; h <= top; h++) { // level_off[h] = end of level h, level_off[h - 1] = its start
+		sum += level_off[h];
+		level_off[h] = sum;
+	}
+	sched.resize(jobs.size());
+	std::vector<uint32_t> at(level_off.begin(), level_off.end() - 1);
+	for (const Job &j : jobs) sched[at[height[j.self] - 1u]++] = j.self;
 }
 
 // Appends the model's nodes and triangle order; returns the root's index.
@@ -376,6 +396,7 @@ uint32_t BvhBuilder::run(const srt_model &m, const srt_triangle *all, uint32_t f
 
 // (re)builds nodes/order from the model and folds them; the fallback keeps every walk inside SRT_BVH_STACK_CAP
 void BvhCacheEntry::build(const srt_model &m, const srt_triangle *all) {
+	stale = false;
 	for (int attempt = balanced ? 1 : 0; attempt < 2; attempt++) {
 		nodes.clear(), order.clear();
 		BvhBuilder bb(nodes, order);
@@ -388,10 +409,17 @@ void BvhCacheEntry::build(const srt_model &m, const srt_triangle *all) {
 	}
 }
 void BvhCacheEntry::refit(const srt_model &m, const srt_triangle *all) {
+	stale = false;
 	BvhBuilder bb(nodes, order);
 	bb.refit(m, all);
 	BvhBuilder::fold_wide(nodes, m.num_triangles, balanced, wide);
 	if (wide.need > SRT_BVH_STACK_CAP) build(m, all); // the new boxes fold differently: start over
+}
+void BvhCacheEntry::refit_in_place(const srt_model &m, const srt_triangle *all) {
+	stale = false;
+	BvhBuilder bb(nodes, order);
+	bb.refit(m, all);
+	for (const BvhBuilder::Wide::Job &j : wide.jobs) quantise(nodes, j.kids, j.nk, j.tags, j.first, wide.blocks.data() + 32 * (size_t)j.self);
 }
 
 // 64-bit FNV-1a over 8-byte words (records are 96 B)
@@ -444,6 +472,43 @@ int srt_bvh_wide_host(const srt_shape *model, const srt_triangle *triangles, siz
 		if (balanced) *balanced = ent.balanced ? 1 : 0;
 		if (blocks_out) memcpy(blocks_out, ent.wide.blocks.data(), std::min(ent.wide.blocks.size(), blocks_cap * 32) * sizeof(uint32_t));
 		if (dest_out) memcpy(dest_out, ent.wide.dest.data(), std::min(ent.wide.dest.size(), dest_cap) * sizeof(uint32_t));
+	} catch (...) { // std::bad_alloc: no C++ exception may cross the C ABI
+		return SRT_ERR_INVALID;
+	}
+	return SRT_OK;
+}
+
+int srt_bvh_wide_order_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, int force_balanced, uint32_t *order_out, size_t order_cap) {
+	if (!model || model->type != SRT_SHAPE_MODEL || (n_triangles && !triangles)) return SRT_ERR_INVALID;
+	const srt_model &m = model->shape.model;
+	if ((uint64_t)m.triangle_index + m.num_triangles > n_triangles || m.num_triangles > 0x0fffffffu) return SRT_ERR_INVALID;
+	try {
+		BvhCacheEntry ent;
+		ent.balanced = force_balanced != 0;
+		if (m.num_triangles > 0) ent.build(m, triangles);
+		if (order_out) memcpy(order_out, ent.order.data(), std::min(ent.order.size(), order_cap) * sizeof(uint32_t));
+	} catch (...) { // std::bad_alloc: no C++ exception may cross the C ABI
+		return SRT_ERR_INVALID;
+	}
+	return SRT_OK;
+}
+
+int srt_bvh_refit_wide_host(const srt_shape *built, const srt_shape *moved, const srt_triangle *triangles, size_t n_triangles, int force_balanced,
+                            uint32_t *blocks_out, size_t blocks_cap, size_t *n_blocks, uint32_t *root) {
+	if (!built || !moved || !n_blocks || built->type != SRT_SHAPE_MODEL || moved->type != SRT_SHAPE_MODEL || (n_triangles && !triangles)) return SRT_ERR_INVALID;
+	const srt_model &m = built->shape.model, &mv = moved->shape.model;
+	if ((uint64_t)m.triangle_index + m.num_triangles > n_triangles || m.num_triangles > 0x0fffffffu) return SRT_ERR_INVALID;
+	if (mv.triangle_index != m.triangle_index || mv.num_triangles != m.num_triangles) return SRT_ERR_INVALID; // only the transform may differ
+	try {
+		BvhCacheEntry ent;
+		ent.balanced = force_balanced != 0;
+		if (m.num_triangles > 0) {
+			ent.build(m, triangles);
+			ent.refit_in_place(mv, triangles);
+		}
+		*n_blocks = ent.wide.blocks.size() / 32;
+		if (root) *root = ent.wide.root;
+		if (blocks_out) memcpy(blocks_out, ent.wide.blocks.data(), std::min(ent.wide.blocks.size(), blocks_cap * 32) * sizeof(uint32_t));
 	} catch (...) { // std::bad_alloc: no C++ exception may cross the C ABI
 		return SRT_ERR_INVALID;
 	}

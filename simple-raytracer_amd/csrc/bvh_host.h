@@ -56,10 +56,18 @@ struct BvhBuilder {
 		std::vector<uint32_t> inner;
 		std::vector<uint32_t> dest;
 		uint32_t root = SRT_BVH_NONE, need = 0;
-		struct Job { // an inner block whose boxes are still to be quantised (fold_wide does them on several threads)
+		struct Job { // an inner block and the nodes of `c` its boxes are quantised from (fold_wide does them on several threads)
 			uint32_t self, kids[4], nk, tags, first;
 		};
+		// One per inner block, children before their parent (fold_node's post-order). Kept with the blocks: an in-place refit
+		// (BvhCacheEntry::refit_in_place, and on the device bvh_refit.hip) requantises every inner block from the children it
+		// already has. A block's children as BLOCKS are in the block itself: child k is block first + k, a leaf when its tag says so.
 		std::vector<Job> jobs;
+		// The refit schedule: the inner blocks by height (1 + the highest child's; leaf blocks have height 0), level h in
+		// sched[level_off[h - 1], level_off[h]): every block of a level reads only boxes of lower levels. Made when first asked
+		// for (ensure_schedule), dropped by fold_wide.
+		std::vector<uint32_t> sched, level_off;
+		void ensure_schedule();
 	};
 	static uint32_t fold_node(const std::vector<BvhNode> &c, uint32_t ci, uint32_t self, bool balanced, Wide &w, uint32_t &need);
 	static void fold_wide(const std::vector<BvhNode> &c, uint32_t records, bool balanced, Wide &w);
@@ -84,6 +92,15 @@ struct BvhCacheEntry {
 	uint32_t leaves = 0, depth = 0;
 	void build(const srt_model &m, const srt_triangle *all);
 	void refit(const srt_model &m, const srt_triangle *all);
+	// New boxes for the wide hierarchy AS IT IS FOLDED: the binary boxes as refit() makes them, then every inner block
+	// requantised with the children it has. No re-fold, so root, need, dest, order, tags, first and the block count stay
+	// (refit() re-folds, and the fold opens children by box area: a rotation can change its topology). The host statement
+	// of what bvh_refit.hip computes on the device.
+	void refit_in_place(const srt_model &m, const srt_triangle *all);
+	// The model moved under SRT_REFIT_DEVICE: `transform` is the new one, the boxes of `nodes` and `wide.blocks` are those of
+	// an earlier one. Whatever is uploaded from a stale entry is refitted on the device behind the upload; build() and
+	// refit() recompute everything from the triangles and clear the mark.
+	bool stale = false;
 	bool same_triangles(const srt_model &m, const srt_triangle *all, uint64_t hash) const {
 		return m.num_triangles == count && hash == tri_hash && memcmp(tris.data(), all + m.triangle_index, (size_t)count * sizeof(srt_triangle)) == 0;
 	}

@@ -308,6 +308,32 @@ int srt_sub_job_items(int has_models, int use_bvh); /* items per sub-job (the un
 #define SRT_POOL_REC_FLOATS ((size_t)2 * SRT_POOL_BLOCKS * 20 * 64)
 #define SRT_SCAN_SET_FLOATS(waves, pool) ((size_t)SRT_POOL_CTL_WORDS + ((pool) ? SRT_POOL_REC_FLOATS : (size_t)0) + (size_t)(waves) * SRT_SCAN_QUEUE_FLOATS) /* one set (pool: with the launch-end ray pool's records, 84 MB; TraceParams.pool_blocks != 0); a multiple of 4 */
 void srt_launch_prepass(const PrepassParams &p, uint64_t total_wtris, void *stream);
+
+/* In-place refit of moved models' hierarchies on the device (bvh_refit.hip; include/srt_abi.h SRT_REFIT_DEVICE). All indices
+ * are the scene's: absolute records and blocks. */
+struct RefitModel {
+	uint32_t shape;        /* index of the model's srt_shape: its transform and triangle range */
+	uint32_t first_record; /* = wtri_offset[shape] */
+	uint32_t num_records;
+	uint32_t _pad;
+};
+struct RefitParams {
+	const srt_shape *shapes;
+	const srt_triangle *triangles;
+	const uint32_t *order, *dest; /* as PrepassParams */
+	const RefitModel *models;
+	uint32_t *extents;     /* per refitted model: lo.xyz, hi.xyz over its finite triangles as order-preserving integers (bvh_refit.hip), uploaded as the empty box below */
+	float *boxes;          /* per block of the scene: lo.xyz, hi.xyz; only the refitted models' are written and read */
+	uint32_t *blocks;
+	const uint32_t *sched; /* the refitted models' inner blocks, level by level (height 1 first) */
+};
+#define SRT_REFIT_EXT_LO_INIT 0xff7fffffu /* FLT_MAX in that order */
+#define SRT_REFIT_EXT_HI_INIT 0x00800000u /* -FLT_MAX */
+/* passes A and B: one thread per record of models[0 .. num_models); return the launches enqueued */
+int srt_launch_refit_extents(const RefitParams &p, uint32_t num_models, uint32_t max_records, void *stream);
+int srt_launch_refit_leaves(const RefitParams &p, uint32_t num_models, uint32_t max_records, void *stream);
+/* pass C for one level: the inner blocks sched[first .. first + count), whose children are all of lower levels */
+int srt_launch_refit_level(const RefitParams &p, uint32_t first, uint32_t count, void *stream);
 void srt_launch_resolve(const ResolveParams &p, void *stream);
 void srt_launch_selftest(unsigned long long *out16, uint32_t stride, void *stream);
 void srt_launch_selftest_rare(int what, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, unsigned long long *mismatches, void *stream);

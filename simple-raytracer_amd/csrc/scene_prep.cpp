@@ -1,6 +1,7 @@
 // scene_prep.cpp -- the host pass of srt_update_scene (scene_prep.h) and the material thresholds. Standard library only.
 #include "scene_prep.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -24,7 +25,7 @@ uint64_t bernoulli_threshold(float pr) {
 
 // host pass; `cache` is made when a BVH scene first needs it and emptied by an array-scan scene; an error return leaves its text
 // in `err` and every cached hierarchy in place
-int prepare_scene(int accel_mode, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
+int prepare_scene(int accel_mode, int refit_mode, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
                   const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
 	auto fail = [&err](int code, const char *msg) {
 		err = msg;
@@ -53,6 +54,7 @@ int prepare_scene(int accel_mode, BvhCache *&cache, int scan_suspend_min, std::s
 	std::deque<BvhCacheEntry> fresh;                 // hierarchies built by this call (deque: growth keeps references valid)
 	std::vector<std::pair<bool, size_t>> plan;       // per model with triangles: {from the cache?, index there / in fresh}
 	std::vector<std::pair<uint64_t, uint64_t>> range_hashes; // {triangle_index << 32 | count, hash}
+	std::vector<std::pair<const BvhCacheEntry *, uint32_t>> stale_plan; // the models the device refits: {hierarchy, its first block}
 	if (use_bvh && !cache) cache = new BvhCache();
 	if (cache)
 		for (BvhCacheEntry &e : cache->entries) e.claimed = false;
@@ -148,9 +150,14 @@ int prepare_scene(int accel_mode, BvhCache *&cache, int scan_suspend_min, std::s
 				if (kept) {
 					ent = kept;
 					ent->claimed = true;
-					if (ent->same_transform(m)) {
-						bvh_reused++;
-					} else { // the model moved: keep the topology, recompute the boxes
+					const bool on_device = refit_mode == SRT_REFIT_DEVICE;
+					if (ent->same_transform(m) && (!ent->stale || on_device)) {
+						bvh_reused++; // (a stale one: refitted on the device again, below)
+					} else if (on_device) { // the model moved: the topology is uploaded as it is, the device recomputes the boxes
+						memcpy(ent->transform, m.transform, sizeof ent->transform);
+						ent->stale = true;
+						bvh_refitted++;
+					} else { // the model moved (or its boxes are a device refit behind): keep the tree, recompute the boxes
 						ent->refit(m, triangles);
 						memcpy(ent->transform, m.transform, sizeof ent->transform);
 						bvh_refitted++;
@@ -179,6 +186,12 @@ int prepare_scene(int accel_mode, BvhCache *&cache, int scan_suspend_min, std::s
 				bvh_canonical_nodes += ent->nodes.size();
 				bvh_order.insert(bvh_order.end(), ent->order.begin(), ent->order.end());
 				link = wd.root == SRT_BVH_NONE ? SRT_BVH_NONE : wd.root + b0; // the root reference (a leaf reference for a model of <= 3 triangles)
+				if (ent->stale) { // its host boxes are not this transform's: never walked as they are
+					ent->wide.ensure_schedule();
+					sp.refit_models.push_back({(uint32_t)i, r0, m.num_triangles, 0u});
+					stale_plan.emplace_back(ent, b0);
+					if (m.num_triangles > sp.refit_max_records) sp.refit_max_records = m.num_triangles;
+				}
 				bvh_leaves += ent->leaves;
 				if (ent->depth > bvh_depth) bvh_depth = ent->depth;
 			}
@@ -212,6 +225,21 @@ int prepare_scene(int accel_mode, BvhCache *&cache, int scan_suspend_min, std::s
 		bool packed = true;
 		for (size_t b = 0; b < runs.size(); b++) packed = packed && runs[b].first_shape == next, next += runs[b].count;
 		if (packed && next == n_shapes) sp.one_group_code = groups[0].code;
+	}
+	if (!stale_plan.empty()) { // the refit schedule of the scene: level h of every stale model, then level h + 1, ...
+		size_t top = 0;
+		for (const auto &st : stale_plan) top = std::max(top, st.first->wide.level_off.size());
+		sp.refit_levels.assign(1, 0u);
+		for (size_t h = 1; h < top; h++) {
+			for (const auto &st : stale_plan) {
+				const BvhBuilder::Wide &wd = st.first->wide;
+				if (h >= wd.level_off.size()) continue;
+				for (uint32_t k = wd.level_off[h - 1]; k < wd.level_off[h]; k++) sp.refit_sched.push_back(wd.sched[k] + st.second);
+			}
+			sp.refit_levels.push_back((uint32_t)sp.refit_sched.size());
+		}
+		for (size_t k = 0; k < stale_plan.size(); k++)
+			sp.refit_extents.insert(sp.refit_extents.end(), {SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_HI_INIT, SRT_REFIT_EXT_HI_INIT, SRT_REFIT_EXT_HI_INIT});
 	}
 	const uint64_t build_us =
 	    (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - build_t0).count();

@@ -24,11 +24,23 @@ struct ScenePrep {
 	int material_flags = 0;
 	uint32_t one_group_code = 0; // srt_tracer::one_group_code
 	uint64_t bvh_info[7] = {0, 0, 0, 0, 0, 0, 0};
+	// SRT_REFIT_DEVICE: the models whose blocks above come from a stale hierarchy (bvh_host.h) and are refitted on the device
+	// behind the upload (bvh_refit.hip), their empty extents, their inner blocks as absolute indices level by level -- level h
+	// of ALL of them in refit_sched[refit_levels[h - 1], refit_levels[h]): one launch per level, not per model and level
+	std::vector<RefitModel> refit_models;
+	std::vector<uint32_t> refit_extents, refit_sched, refit_levels;
+	uint32_t refit_max_records = 0;
 };
 
-// accel_mode: SRT_ACCEL_*; cache: the caller's hierarchy cache (a group: its first member's); scan_suspend_min: srt_scan_suspend_min()
-int prepare_scene(int accel_mode, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
+// accel_mode: SRT_ACCEL_*; refit_mode: SRT_REFIT_* (who refits a model that only moved; nothing without SRT_ACCEL_BVH); cache: the caller's hierarchy cache (a group: its first member's); scan_suspend_min: srt_scan_suspend_min()
+int prepare_scene(int accel_mode, int refit_mode, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
                   const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene);
+
+// the same with SRT_REFIT_HOST
+inline int prepare_scene(int accel_mode, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
+                         const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
+	return prepare_scene(accel_mode, SRT_REFIT_HOST, cache, scan_suspend_min, err, sp, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
+}
 
 uint64_t bernoulli_threshold(float pr);
 

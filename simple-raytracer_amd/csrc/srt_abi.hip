@@ -197,6 +197,12 @@ void srt_destroy(srt_tracer *t) {
 	t->bvh_blocks.release();
 	t->bvh_order.release();
 	t->bvh_dest.release();
+	t->refit_models.release();
+	t->refit_extents.release();
+	t->refit_sched.release();
+	t->refit_boxes.release();
+	for (hipEvent_t ev : t->ev_refit)
+		if (ev) (void)hipEventDestroy(ev);
 	t->sky.release();
 	t->counters.release();
 	t->wave_counters.release();
@@ -275,6 +281,49 @@ int srt_update_scene(srt_tracer *t, const srt_shape *shapes, size_t n_shapes, co
 	}
 }
 
+// SRT_REFIT_DEVICE: behind the pre-pass, new boxes for the models whose blocks were uploaded from a stale hierarchy
+// (bvh_refit.hip): passes A and B over their records, then one launch per height level of their inner blocks
+static int refit_on_device(srt_tracer *t, const ScenePrep &sp) {
+	for (uint64_t &v : t->refit_info) v = 0;
+	t->refit_timed = false;
+	if (sp.refit_models.empty()) return SRT_OK;
+	const uint32_t n_models = (uint32_t)sp.refit_models.size();
+	SRT_HIP(t, t->refit_models.reserve(n_models));
+	SRT_HIP(t, t->refit_extents.reserve(sp.refit_extents.size()));
+	SRT_HIP(t, t->refit_sched.reserve(sp.refit_sched.size()));
+	SRT_HIP(t, t->refit_boxes.reserve(sp.bvh_blocks.size() / 32 * 6));
+	SRT_HIP(t, hipMemcpyAsync(t->refit_models.ptr, sp.refit_models.data(), n_models * sizeof(RefitModel), hipMemcpyHostToDevice, t->stream));
+	SRT_HIP(t, hipMemcpyAsync(t->refit_extents.ptr, sp.refit_extents.data(), sp.refit_extents.size() * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream));
+	if (!sp.refit_sched.empty())
+		SRT_HIP(t, hipMemcpyAsync(t->refit_sched.ptr, sp.refit_sched.data(), sp.refit_sched.size() * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream));
+	RefitParams rp;
+	rp.shapes = t->shapes.ptr;
+	rp.triangles = t->triangles.ptr;
+	rp.order = t->bvh_order.ptr;
+	rp.dest = t->bvh_dest.ptr;
+	rp.models = t->refit_models.ptr;
+	rp.extents = t->refit_extents.ptr;
+	rp.boxes = t->refit_boxes.ptr;
+	rp.blocks = t->bvh_blocks.ptr;
+	rp.sched = t->refit_sched.ptr;
+	if (t->timers_in_render) {
+		for (hipEvent_t &ev : t->ev_refit)
+			if (!ev) SRT_HIP(t, hipEventCreate(&ev));
+		SRT_HIP(t, hipEventRecord(t->ev_refit[0], t->stream));
+	}
+	int launches = srt_launch_refit_extents(rp, n_models, sp.refit_max_records, t->stream);
+	launches += srt_launch_refit_leaves(rp, n_models, sp.refit_max_records, t->stream);
+	for (size_t h = 1; h < sp.refit_levels.size(); h++)
+		launches += srt_launch_refit_level(rp, sp.refit_levels[h - 1], sp.refit_levels[h] - sp.refit_levels[h - 1], t->stream);
+	SRT_HIP(t, hipGetLastError());
+	if (t->timers_in_render) {
+		SRT_HIP(t, hipEventRecord(t->ev_refit[1], t->stream));
+		t->refit_timed = true;
+	}
+	t->refit_info[0] = n_models, t->refit_info[1] = sp.refit_sched.size(), t->refit_info[2] = (uint64_t)launches;
+	return SRT_OK;
+}
+
 // device pass, first half: wait for the handle's previous launches, (re)allocate, enqueue every upload and the pre-pass on its stream
 static int upload_scene_begin(srt_tracer *t, const ScenePrep &sp, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles,
                               size_t n_triangles, size_t n_materials) {
@@ -341,7 +390,7 @@ static int upload_scene_begin(srt_tracer *t, const ScenePrep &sp, const srt_shap
 		}
 		SRT_HIP(t, hipGetLastError());
 	}
-	return SRT_OK;
+	return refit_on_device(t, sp);
 }
 
 // device pass, second half: the uploads have arrived (the host arrays are free again), the handle describes the new scene
@@ -353,6 +402,7 @@ static int upload_scene_end(srt_tracer *t, const ScenePrep &sp, size_t n_shapes,
 	t->num_models = sp.num_models;
 	t->scan_tris = sp.use_bvh ? 0 : sp.total_wtris;
 	t->bvh_active = sp.use_bvh && sp.num_models > 0;
+	t->bvh_num_blocks = sp.use_bvh ? sp.bvh_blocks.size() / 32 : 0;
 	for (int k = 0; k < 7; k++) t->bvh_info[k] = sp.bvh_info[k];
 	t->all_materials_ok = sp.all_materials_ok;
 	t->unit_materials = sp.unit_materials;
@@ -368,7 +418,7 @@ static int upload_scene_end(srt_tracer *t, const ScenePrep &sp, size_t n_shapes,
 static int prepare_scene_of(srt_tracer *t, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
                             const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
 	std::string err;
-	const int rc = prepare_scene(t->accel_mode, t->bvh_cache, srt_scan_suspend_min(), err, sp, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
+	const int rc = prepare_scene(t->accel_mode, t->refit_mode, t->bvh_cache, srt_scan_suspend_min(), err, sp, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
 	return rc == SRT_OK ? SRT_OK : fail(t, rc, err);
 }
 
@@ -397,6 +447,7 @@ int srt_update_scene_many(srt_tracer *const *members, size_t n_members, const sr
 		for (; begun < n_members && rc == SRT_OK; begun++) {
 			if (failed_member) *failed_member = begun;
 			members[begun]->accel_mode = members[0]->accel_mode; // (the prepared scene is in this form)
+			members[begun]->refit_mode = members[0]->refit_mode;
 			rc = upload_scene_begin(members[begun], sp, shapes, n_shapes, triangles, n_triangles, n_materials);
 		}
 		if (rc != SRT_OK) { // what was enqueued on the members before the failing one still reads the host arrays: let it finish
@@ -1055,6 +1106,40 @@ int srt_set_acceleration(srt_tracer *t, int mode) {
 	if (!t) return SRT_ERR_INVALID;
 	if (mode != SRT_ACCEL_NONE && mode != SRT_ACCEL_BVH) return fail(t, SRT_ERR_INVALID, "srt_set_acceleration: unknown mode");
 	t->accel_mode = mode;
+	return SRT_OK;
+}
+
+int srt_set_acceleration_refit(srt_tracer *t, int mode) {
+	if (!t) return SRT_ERR_INVALID;
+	if (mode != SRT_REFIT_HOST && mode != SRT_REFIT_DEVICE) return fail(t, SRT_ERR_INVALID, "srt_set_acceleration_refit: unknown mode");
+	t->refit_mode = mode;
+	return SRT_OK;
+}
+
+int srt_acceleration_refit_info(const srt_tracer *t, uint64_t out[4]) {
+	if (!t || !out) return SRT_ERR_INVALID;
+	for (int i = 0; i < 4; i++) out[i] = t->bvh_active ? t->refit_info[i] : 0;
+	return SRT_OK;
+}
+
+int srt_last_refit_kernel_ms(srt_tracer *t, float *ms) {
+	if (!t || !ms) return SRT_ERR_INVALID;
+	*ms = 0.f;
+	SRT_HIP(t, hipSetDevice(t->device));
+	SRT_HIP(t, hipStreamSynchronize(t->stream));
+	if (t->refit_timed) SRT_HIP(t, hipEventElapsedTime(ms, t->ev_refit[0], t->ev_refit[1]));
+	return SRT_OK;
+}
+
+int srt_read_bvh_blocks(srt_tracer *t, uint32_t *blocks_out, size_t blocks_cap, size_t *n_blocks) {
+	if (!t || !n_blocks) return SRT_ERR_INVALID;
+	const size_t n = t->bvh_active ? t->bvh_num_blocks : 0;
+	*n_blocks = n;
+	const size_t take = n < blocks_cap ? n : blocks_cap;
+	if (!blocks_out || take == 0) return SRT_OK;
+	SRT_HIP(t, hipSetDevice(t->device));
+	SRT_HIP(t, hipStreamSynchronize(t->stream));
+	SRT_HIP(t, hipMemcpy(blocks_out, t->bvh_blocks.ptr, take * 32 * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	return SRT_OK;
 }
 

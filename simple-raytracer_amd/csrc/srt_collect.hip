@@ -519,6 +519,12 @@ int srt_group_set_acceleration(srt_group *g, int mode) {
 	return SRT_OK;
 }
 
+int srt_group_set_acceleration_refit(srt_group *g, int mode) {
+	if (!g) return SRT_ERR_INVALID;
+	SRT_EACH(g, srt_set_acceleration_refit(t_, mode));
+	return SRT_OK;
+}
+
 int srt_group_update_scene(srt_group *g, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
                            const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
 	if (!g) return SRT_ERR_INVALID;

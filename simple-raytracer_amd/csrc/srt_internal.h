@@ -62,6 +62,15 @@ struct srt_tracer {
 	int accel_mode = SRT_ACCEL_NONE; // what the next srt_update_scene builds
 	bool bvh_active = false;         // the current scene's models carry BVH roots
 	uint64_t bvh_info[7] = {0, 0, 0, 0, 0, 0, 0};
+	// in-place refit on the device (bvh_refit.hip; srt_set_acceleration_refit)
+	int refit_mode = SRT_REFIT_HOST;  // who refits a moved model at the next srt_update_scene
+	size_t bvh_num_blocks = 0;        // blocks of the current scene in bvh_blocks (srt_read_bvh_blocks)
+	DevBuf<RefitModel> refit_models;  // the last upload's refitted models, their extents, inner blocks by level, and a box per block
+	DevBuf<uint32_t> refit_extents, refit_sched;
+	DevBuf<float> refit_boxes;
+	uint64_t refit_info[4] = {0, 0, 0, 0};
+	hipEvent_t ev_refit[2] = {nullptr, nullptr}; // around the refit launches, when the kernel timers are on
+	bool refit_timed = false;
 	struct BvhCache *bvh_cache = nullptr; // hierarchies of the previous srt_update_scene (bvh_host.h BvhCacheEntry; made by scene_prep.cpp)
 	DevBuf<unsigned long long> counters;
 	DevBuf<unsigned long long> wave_counters; // per persistent wave, summed in srt_get_counters

@@ -155,6 +155,8 @@ class Tracer {
 	/// SRT_ACCEL_BVH: models get a bounding-volume hierarchy at the next update_scene (the
 	/// reference's README.md:41 "future plan"); SRT_ACCEL_NONE (default) keeps the array-order scan
 	void set_acceleration(int mode) { check(group ? srt_group_set_acceleration(group, mode) : srt_set_acceleration(handle, mode)); }
+	// SRT_REFIT_HOST / SRT_REFIT_DEVICE: who refits the hierarchy of a model that only moved (the next update_scene on)
+	void set_acceleration_refit(int mode) { check(group ? srt_group_set_acceleration_refit(group, mode) : srt_set_acceleration_refit(handle, mode)); }
 	/// The edge-aware denoiser (srt_set_denoise): iterations < 0 turns it off, else it is on with srt_denoise_defaults()
 	/// overridden by the arguments; render() / render_pipelined() then hand out the filtered image. On a Tracer over several
 	/// devices the members gather the filter's inputs with the frame and device 0 filters (srt_group_set_denoise): the same bytes.

@@ -44,9 +44,12 @@ ABI_SYMBOLS = [
     "srt_unpermute_planes_device",
     "srt_set_denoise_demodulation", "srt_group_set_denoise_demodulation", "srt_last_filter_demodulated",
     "srt_group_last_filter_demodulated",
+    "srt_bvh_refit_wide_host", "srt_set_acceleration_refit", "srt_group_set_acceleration_refit", "srt_acceleration_refit_info",
+    "srt_last_refit_kernel_ms", "srt_read_bvh_blocks", "srt_bvh_wide_order_host",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
+REFIT_HOST, REFIT_DEVICE = 0, 1
 MOTION_STATIC, MOTION_MOVED, MOTION_NO_HISTORY = 0, 1, 2
 MOTION_WORDS = 22
 NO_SHAPE = 0xFFFFFFFF
@@ -192,6 +195,40 @@ def bvh_wide_host(model_shape, triangles, force_balanced=False):
     return {"blocks": blocks, "dest": dest, "root": root.value, "stack_need": need.value, "balanced": bool(bal.value)}
 
 
+def bvh_wide_order_host(model_shape, triangles, force_balanced=False):
+    """srt_bvh_wide_order_host (host only): order[record] = triangle inside the model, of the hierarchy bvh_wide_host gives
+    for the same arguments."""
+    shape = np.zeros(1, R.SHAPE)
+    shape[0] = model_shape
+    tris = R.as_records(triangles, R.TRIANGLE)
+    order = np.zeros(int(shape[0]["num_triangles"]), np.uint32)
+    rc = load_library().srt_bvh_wide_order_host(_ptr(shape), _ptr(tris), len(tris), int(bool(force_balanced)), _ptr(order), len(order))
+    if rc:
+        raise SrtError(f"srt_bvh_wide_order_host failed ({rc})")
+    return order
+
+
+def bvh_refit_wide_host(built_shape, moved_shape, triangles, force_balanced=False):
+    """srt_bvh_refit_wide_host (host only): the wide hierarchy of built_shape (bvh_wide_host's) refitted in place for
+    moved_shape, which may differ in its transform only: dict with blocks (n x 32 uint32, relative to the model, leaf
+    blocks zero) and root. What REFIT_DEVICE computes on the device."""
+    lib = load_library()
+    shapes = np.zeros(2, R.SHAPE)
+    shapes[0], shapes[1] = built_shape, moved_shape
+    tris = R.as_records(triangles, R.TRIANGLE)
+    n, root = C.c_size_t(0), C.c_uint32(0)
+    flags = int(bool(force_balanced))
+    args = (_ptr(shapes[0:1]), _ptr(shapes[1:2]), _ptr(tris), len(tris), flags)
+    rc = lib.srt_bvh_refit_wide_host(*args, None, 0, C.byref(n), None)
+    if rc:
+        raise SrtError(f"srt_bvh_refit_wide_host failed ({rc})")
+    blocks = np.zeros((n.value, 32), np.uint32)
+    rc = lib.srt_bvh_refit_wide_host(*args, _ptr(blocks), len(blocks), C.byref(n), C.byref(root))
+    if rc:
+        raise SrtError(f"srt_bvh_refit_wide_host failed ({rc})")
+    return {"blocks": blocks, "root": root.value}
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("paths", "rays", "sky", "tri_tests", "tri_pass_u", "nan_pixels", "watchdog")]
 
@@ -320,6 +357,14 @@ def _bind(lib):
         lib.srt_set_acceleration.argtypes = [vp, i]
         lib.srt_acceleration_info.argtypes = [vp, C.POINTER(C.c_uint64)]
         lib.srt_bvh_build_host.argtypes = [vp, vp, sz, vp, sz, vp, sz, C.POINTER(sz)]
+    if hasattr(lib, "srt_set_acceleration_refit"):  # (an older library, SRT_LIB, in an A/B run)
+        lib.srt_bvh_refit_wide_host.argtypes = [vp, vp, vp, sz, i, vp, sz, C.POINTER(sz), C.POINTER(C.c_uint32)]
+        lib.srt_bvh_wide_order_host.argtypes = [vp, vp, sz, i, vp, sz]
+        lib.srt_set_acceleration_refit.argtypes = [vp, i]
+        lib.srt_group_set_acceleration_refit.argtypes = [vp, i]
+        lib.srt_acceleration_refit_info.argtypes = [vp, C.POINTER(C.c_uint64)]
+        lib.srt_last_refit_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        lib.srt_read_bvh_blocks.argtypes = [vp, vp, sz, C.POINTER(sz)]
     if hasattr(lib, "srt_gather"):
         lib.srt_comm_unique_id.argtypes = [vp]
         lib.srt_comm_init.argtypes = [vp, vp, i, i]
@@ -638,6 +683,31 @@ class Tracer(_Denoise):
         self._check(self.lib.srt_acceleration_info(self._h, out))
         return dict(zip(("nodes", "leaves", "depth", "build_us", "models_built", "models_reused", "models_refitted"), (int(v) for v in out)))
 
+    def set_acceleration_refit(self, mode):
+        """REFIT_HOST (the default) or REFIT_DEVICE: who refits the hierarchy of a model that only moved; applies at the next
+        update_scene."""
+        self._check(self.lib.srt_set_acceleration_refit(self._h, int(mode)))
+
+    def acceleration_refit_info(self):
+        """Of the last update_scene: models refitted on the device, inner blocks they requantised, refit launches."""
+        out = (C.c_uint64 * 4)()
+        self._check(self.lib.srt_acceleration_refit_info(self._h, out))
+        return dict(zip(("models", "inner_blocks", "launches"), (int(v) for v in out)))
+
+    def last_refit_kernel_ms(self):
+        """Device time of the last update_scene's refit launches (needs set_kernel_timers); blocking."""
+        a = C.c_float()
+        self._check(self.lib.srt_last_refit_kernel_ms(self._h, C.byref(a)))
+        return a.value
+
+    def read_bvh_blocks(self):
+        """(n, 32) uint32: the device's block array as the kernel walks it (absolute indices); blocking."""
+        n = C.c_size_t(0)
+        self._check(self.lib.srt_read_bvh_blocks(self._h, None, 0, C.byref(n)))
+        blocks = np.zeros((n.value, 32), np.uint32)
+        self._check(self.lib.srt_read_bvh_blocks(self._h, _ptr(blocks), len(blocks), C.byref(n)))
+        return blocks
+
     def selftest_math(self, stride=1):
         out = (C.c_uint64 * 16)()
         self._check(self.lib.srt_selftest_math(self._h, stride, out))
@@ -797,6 +867,10 @@ class TracerGroup(_Denoise):
 
     def set_acceleration(self, mode):
         self._check(self.lib.srt_group_set_acceleration(self._g, int(mode)))
+
+    def set_acceleration_refit(self, mode):
+        """Tracer.set_acceleration_refit on every member."""
+        self._check(self.lib.srt_group_set_acceleration_refit(self._g, int(mode)))
 
     def set_textures(self, images):
         keep, descs = _texture_descs(images)

@@ -1,0 +1,142 @@
+"""What the in-place BVH refit's tests share (tests/test_bvh_refit_host.py, tests/test_gpu_bvh_refit.py): the models and
+transforms, a numpy statement of the padded triangle boxes (float32 operations in the builder's order, from the raw triangles
+and a transform alone), the decoding of an inner block's byte boxes, and the walk over a wide hierarchy that checks them.
+A plain module, not a test module."""
+import functools
+
+import numpy as np
+
+from simple_raytracer_amd import records as R, scenes as S, tracer as T
+
+FLT_MAX = np.finfo(np.float32).max
+F = np.float32
+
+
+@functools.lru_cache(maxsize=None)
+def model_triangles(name):
+    """n1, n3, n4, n13, n200: the first n triangles of a 240-triangle blob; n6k: blob_mesh(55, 56), 6,050 triangles (more
+    than 1,024 inner blocks); chain400: the geometric chain of tests/test_gpu_bvh.py, whose SAH tree is a chain (the
+    library's way into the balanced form); n200bad: n200 with a NaN vertex in one triangle and an inf vertex in another."""
+    if name == "n6k":
+        return S.blob_mesh(55, 56, seed=7, smooth=False)
+    if name == "chain400":
+        tris = np.zeros(400, R.TRIANGLE)
+        for i in range(400):
+            s, x = 1.02 ** i, 60.0 * (1.02 ** i)
+            z = 3.0 * np.sin(0.7 * i)
+            tris[i] = R.flat_triangle((0, 0, 1), (x, 0, z), (x + s, 0, z), (x, s, z + 0.5 * s))
+        return tris
+    base = R.as_records(S.blob_mesh(12, 11, seed=4, smooth=True), R.TRIANGLE)
+    if name == "n200bad":
+        tris = base[:200].copy()
+        tris["v"]["pos"][17, 1, 0] = np.nan
+        tris["v"]["pos"][101, 2, 1] = np.inf
+        return tris
+    return base[:int(name[1:])].copy()
+
+
+BUILT = {"chain400": R.scale_matrix((0.004, 0.004, 0.004))}  # every other model is built at the identity
+
+MOVES = {
+    "translate": R.translate((0.3, -0.2, 0.5)),
+    "rotate": R.mat_mul(R.translate((-0.4, 0.2, 0.1)), R.mat_mul(R.euler_yxz(0.8, -0.4, 0.3), R.scale_matrix((1.2, 0.7, 1.0)))),
+    "far": R.translate((2.0e4, -1.0e4, 3.0e4)),  # 10^4 model sizes from the origin
+    "tiny": R.scale_matrix((2.0 ** -60,) * 3),
+    "huge": R.scale_matrix((2.0 ** 60,) * 3),
+    "flat": R.scale_matrix((1.0, 0.0, 1.0)),     # extent 0 on one axis: the finest grid there
+}
+
+# (model, move): every shape and every transform at least once
+CASES = [("n1", "translate"), ("n3", "rotate"), ("n4", "rotate"), ("n13", "translate"), ("n200", "rotate"), ("n6k", "rotate"),
+         ("chain400", "rotate"), ("n200", "far"), ("n200", "tiny"), ("n200", "huge"), ("n200", "flat"), ("n200bad", "rotate")]
+
+
+def shapes_of(model, move):
+    """(built shape, moved shape, triangles): one model over the whole triangle array"""
+    tris = model_triangles(model)
+    built = BUILT.get(model, R.identity4())
+    with np.errstate(all="ignore"):
+        return R.model(0, tris, 0, len(tris), built), R.model(0, tris, 0, len(tris), R.mat_mul(MOVES[move], built)), tris
+
+
+def padded_boxes(shape, tris):
+    """(lo, hi) float32 (n, 3): every triangle's padded world box, from the raw triangles and the transform: vertices in the
+    kernel's left-associated order, the box over p0, p1, p2, p0 + (p1 - p0), p0 + (p2 - p0), one with an infinite bound
+    all-embracing, the rest widened by 2^-12 of the diagonal over the finite ones and two ulps. A triangle with a NaN
+    coordinate asks for nothing (the empty box): no ray hits it, whatever box the builder gives it (its comparisons drop a
+    NaN or keep it depending on where it stands)."""
+    first, n = int(shape["triangle_index"]), int(shape["num_triangles"])
+    m = np.asarray(shape["transform"], F)
+    v = np.asarray(tris["v"]["pos"][first:first + n], F)  # (n, 3 vertices, 3)
+    with np.errstate(all="ignore"):
+        p = ((m[0][None, None, :3] * v[..., 0:1] + m[1][None, None, :3] * v[..., 1:2]) + m[2][None, None, :3] * v[..., 2:3]) + m[3][None, None, :3]
+        q1, q2 = p[:, 0] + (p[:, 1] - p[:, 0]), p[:, 0] + (p[:, 2] - p[:, 0])
+        pts = np.stack([p[:, 0], p[:, 1], p[:, 2], q1, q2], axis=1)
+        nan = np.isnan(pts).any(axis=(1, 2))
+        finite = np.isfinite(pts).all(axis=(1, 2))
+        lo, hi = np.where(finite[:, None], pts.min(axis=1), -FLT_MAX).astype(F), np.where(finite[:, None], pts.max(axis=1), FLT_MAX).astype(F)
+        d2 = 0.0
+        if finite.any():
+            ext = hi[finite].max(axis=0).astype(np.float64) - lo[finite].min(axis=0).astype(np.float64)
+            d2 = float((ext * ext).sum())
+        pad = F(min(np.sqrt(d2) / 4096.0, float(FLT_MAX)))
+        plo = np.nextafter(np.nextafter(lo - pad, F(-np.inf)), F(-np.inf))
+        phi = np.nextafter(np.nextafter(hi + pad, F(np.inf)), F(np.inf))
+        keep = lo == -FLT_MAX  # (per axis, as the builder)
+        lo, hi = np.where(keep, lo, np.maximum(plo, -FLT_MAX)).astype(F), np.where(keep, hi, np.minimum(phi, FLT_MAX)).astype(F)
+        return np.where(nan[:, None], F(np.inf), lo), np.where(nan[:, None], F(-np.inf), hi)
+
+
+def fma32(q, scale, origin):
+    """float32(q * scale + origin) with ONE rounding, in float64: the product of a byte and a power of two is exact; the
+    sum's float64 rounding error (TwoSum) decides the cases in which the float64 sum sits exactly half way between two
+    float32 values."""
+    with np.errstate(all="ignore"):
+        p = np.asarray(q, np.float64) * np.asarray(scale, np.float64)
+        o = np.asarray(origin, np.float64)
+        s = p + o
+        bb = s - p
+        err = (p - (s - bb)) + (o - bb)
+        half = np.isfinite(s) & ((s.view(np.int64) & 0x1FFFFFFF) == 0x10000000) & (err != 0) & np.isfinite(err)
+        s = np.where(half, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+        return s.astype(F)
+
+
+def decode_inner(block):
+    """(nk, first, tags[4], lo (4, 3), hi (4, 3)) of an inner block (csrc/device_types.h): bound = fmaf(byte, 2^e, origin)"""
+    b = np.asarray(block, np.uint32)
+    origin = b[0:3].view(F)
+    nk, first = int(b[3]) >> 24, int(b[11])
+    scale = np.array([((int(b[3]) >> (8 * a)) & 255) << 23 for a in range(3)], np.uint32).view(F)
+    qlo = np.array([[(int(b[4 + a]) >> (8 * k)) & 255 for a in range(3)] for k in range(4)], np.float64)
+    qhi = np.array([[(int(b[7 + a]) >> (8 * k)) & 255 for a in range(3)] for k in range(4)], np.float64)
+    tags = [(int(b[10]) >> (8 * k)) & 255 for k in range(4)]
+    return nk, first, tags, fma32(qlo, scale[None, :], origin[None, :]), fma32(qhi, scale[None, :], origin[None, :])
+
+
+def check_contains(blocks, root, dest, order, lo, hi, first_block=0):
+    """Walks the wide hierarchy from `root`: every child's decoded box contains the padded box (lo, hi: per triangle of the
+    model) of every triangle beneath it. dest / order as srt_bvh_wide_host / srt_bvh_build_host give them (relative to the
+    model); first_block shifts them onto `blocks`. Returns the inner blocks' indices (in `blocks`)."""
+    recs_of_leaf = {}
+    for r, d in enumerate(dest.tolist()):
+        recs_of_leaf.setdefault((d >> 2) + first_block, []).append(r)
+    inner = []
+
+    def box_of(idx, leaf):
+        if leaf:
+            t = order[recs_of_leaf[idx]]
+            return lo[t].min(axis=0), hi[t].max(axis=0)
+        inner.append(idx)
+        nk, first, tags, clo, chi = decode_inner(blocks[idx])
+        assert 2 <= nk <= 4
+        ulo, uhi = [], []
+        for k in range(nk):
+            l, h = box_of(first + k, bool(tags[k] & 16))
+            assert (clo[k] <= l).all() and (chi[k] >= h).all(), (idx, k, clo[k], l, chi[k], h)
+            ulo.append(l), uhi.append(h)
+        return np.min(ulo, axis=0), np.max(uhi, axis=0)
+
+    if root != T.BVH_NONE:
+        box_of((root & T.BVH_INDEX_MASK), bool(root & T.BVH_LEAF_BIT))
+    return inner
