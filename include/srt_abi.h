@@ -306,6 +306,7 @@ int srt_group_set_skybox(srt_group *g, const float *rgba, int width, int height)
 int srt_group_set_textures(srt_group *g, const srt_texture_desc *descs, size_t n);
 int srt_group_set_material_textures(srt_group *g, const srt_material_texture *bindings, size_t n_materials);
 int srt_group_set_triangle_uvs(srt_group *g, const float *uv, size_t n_triangles);
+int srt_group_set_triangle_materials(srt_group *g, const int32_t *materials, size_t n_triangles); /* per-triangle materials (below) */
 int srt_group_set_acceleration(srt_group *g, int mode);
 int srt_group_set_acceleration_refit(srt_group *g, int mode); /* srt_set_acceleration_refit on every member */
 int srt_group_update_scene(srt_group *g, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
@@ -323,7 +324,8 @@ int srt_group_get_counters(srt_group *g, srt_counters *out); /* summed over the 
  * the filter (K = 0: the plain resolve's bytes); srt_group_clear_canvas makes the frame being cleared the history when
  * something was traced and zeroes every member's sums and the counts. Turning the denoiser on, or changing
  * feature_samples, clears the canvas and the sums on every member. The history is dropped by
- * srt_group_reset_denoise_history, srt_group_set_skybox, the three srt_group_set_*texture* calls, an
+ * srt_group_reset_denoise_history, srt_group_set_skybox, the three srt_group_set_*texture* calls,
+ * srt_group_set_triangle_materials, an
  * srt_group_update_scene with other bytes than the previous one's, and by turning the denoiser or temporal off.
  * srt_group_resolve_denoised: after srt_group_trace_and_gather, asynchronous on the first device. The read-backs block;
  * srt_group_read_denoise_inputs returns what the last srt_group_trace_and_gather / srt_group_render collected.
@@ -517,8 +519,35 @@ int srt_set_material_textures(srt_tracer *t, const srt_material_texture *binding
 /* n_triangles x 3 x 2 floats (u, v per vertex), parallel to the triangle array of srt_update_scene; NULL: no UVs.
  * A count that differs from the scene's triangle count is SRT_ERR_INVALID at the next srt_update_scene and at dispatches. */
 int srt_set_triangle_uvs(srt_tracer *t, const float *uv, size_t n_triangles);
+/* ---- per-triangle materials ----------------------------------------------------
+ * Opt-in: one material index per triangle of the scene's triangle array, so that one model shape can carry several
+ * materials (an OBJ's `usemtl` groups; host/parser.hpp hands them out). n_triangles int32 values parallel to
+ * srt_update_scene's triangle array (as srt_set_triangle_uvs). -1: the triangle keeps its shape's material; m >= 0:
+ * materials[m]. NULL / 0 removes them.
+ *   which material  a hit on triangle k (index in the scene's triangle array: model.triangle_index + index in the model) of
+ *                   a model whose shape material is >= 0 is shaded with materials[tm[k]] when tm[k] >= 0: the reference's
+ *                   `closest = shape->material` (render.cl:334) made per triangle. Emission, the three probabilities,
+ *                   smoothness, the refraction index, the colour and the texture binding all come from that material, in
+ *                   the trace kernel and in the denoiser's albedo guide. show_normals ignores the table.
+ *   hit / miss      stays the shape's: a model with material < 0 is a miss whatever its triangles say, and the table has no
+ *                   "no material" value. The denoiser's shape ids stay the shape's.
+ *   instances       two instances over one triangle range share the table's entries, as they share UVs.
+ * The canvas equals that of the same scene with every model split into one model shape per maximal run of consecutive
+ * triangles of one effective material (same transform and bounds, the run's triangle range and material, in the model's
+ * place in the shape array). The setter behaves as the three texture setters: it takes effect for later dispatches, does
+ * not clear the canvas and drops the denoiser's temporal history. A count that differs from the scene's triangle count, or
+ * an entry below -1 or not below the scene's material count, is SRT_ERR_INVALID at the next srt_update_scene (which then
+ * fails before anything is replaced: the handle keeps its previous scene) and at every dispatch. A table with an entry
+ * >= 0 over a scene that has triangles makes the library launch the textured instantiations (srt_last_trace_textured
+ * reports 1), with or without a texture bound; a NULL table, a table of only -1 or a scene without triangles launches
+ * exactly what is launched without this interface. */
+int srt_set_triangle_materials(srt_tracer *t, const int32_t *materials, size_t n_triangles);
+/* Host-only: SRT_OK / SRT_ERR_INVALID for a table meeting a scene (count == scene_triangles, every entry in
+ * [-1, n_materials)); NULL with n == 0: no table, SRT_OK. */
+int srt_triangle_materials_check_host(const int32_t *materials, size_t n, size_t scene_triangles, size_t n_materials);
 /* Which kernels the last srt_trace launched: *textured = 1 when the textured instantiations ran (some material of the
- * scene has a texture bound), else 0. */
+ * scene has a texture bound, or a per-triangle material table with an entry >= 0 is set over a scene with triangles --
+ * the table is read by those instantiations alone), else 0. */
 int srt_last_trace_textured(const srt_tracer *t, int *textured);
 /* Which instantiation of the trace kernel the last srt_trace launched: *scene_class = 0 for the general kernels, 1 and up
  * for a kernel compiled for the scene's class (sphere / plane scenes of one block group). The class follows

@@ -274,6 +274,7 @@ struct TexParams {
 	const srt_material_texture *bindings; /* one per material of the scene (texture = -1: none) */
 	const PlaneFrame *frames;             /* one per shape */
 	const float *tri_uvs;                 /* 6 floats per triangle of the scene's triangle array, or NULL */
+	const int32_t *tri_materials;         /* per-triangle materials (srt_set_triangle_materials): one index per triangle of that array (-1: the shape's), or NULL: none */
 };
 struct TexTraceParams : TraceParams {
 	TexParams tx;

@@ -85,7 +85,11 @@
 			tsum = tsum + tmin;
 			const srt_float3 &mc = p.materials[material].color;
 #if SRT_TEXTURED
-			asum = asum + texture_albedo<HAS_MODELS, USE_BVH>(p, fp.tx, best, best_tri, org + dir * tmin, material, mk(mc.x, mc.y, mc.z));
+			// per-triangle materials: the albedo is that of the material the trace kernel shades the hit with (the shape id stays the shape's)
+			const int shaded = hit_material<HAS_MODELS, USE_BVH>(p, fp.tx, best, best_tri, material);
+			const srt_float3 &tc = p.materials[shaded].color;
+			(void)mc;
+			asum = asum + texture_albedo<HAS_MODELS, USE_BVH>(p, fp.tx, best, best_tri, org + dir * tmin, shaded, mk(tc.x, tc.y, tc.z));
 #else
 			asum = asum + mk(mc.x, mc.y, mc.z);
 #endif

@@ -1011,6 +1011,27 @@ __device__ __forceinline__ f3 texture_albedo(const TraceParams &p, const TexPara
 	}
 	return sample_texture(tx, bind.texture, bind.filter, u * bind.scale_u, v * bind.scale_v);
 }
+
+// ---- per-triangle materials (include/srt_abi.h) ----
+// The material that shades a hit on triangle `tri` (index in the scene's triangle array) of a model whose shape material is
+// `material` (>= 0: the hit was decided by the shape): the table's entry where there is a table and the entry is >= 0. The
+// host has checked every entry against the scene's material count, unit_materials and SRT_MF_* are computed over the whole
+// material array (scene_prep.cpp) and the LDS copy holds all materials, so any index the table holds is consistent with what
+// the kernel assumes of `material`. One dword per shaded mesh hit, beside the triangle's normals and UVs.
+__device__ __forceinline__ int triangle_material(const TexParams &tx, uint32_t tri, int material) {
+	if (!tx.tri_materials) return material; // (uniform over the launch)
+	const int tm = tx.tri_materials[tri];
+	return tm >= 0 ? tm : material;
+}
+// the same for the feature pass, which has the hit as (shape, triangle reference): SHADE_MESH_NORMAL's triangle index
+template <bool HAS_MODELS, bool USE_BVH>
+__device__ __forceinline__ int hit_material(const TraceParams &p, const TexParams &tx, int best, uint32_t best_tri, int material) {
+	if (!HAS_MODELS || !tx.tri_materials) return material;
+	const int type = p.winners[best].type;
+	if (type == SRT_SHAPE_SPHERE || type == SRT_SHAPE_PLANE) return material;
+	const uint32_t tri_in_model = USE_BVH ? bvh_tri_in_model(reinterpret_cast<const float4 *>(p.bvh_blocks), best_tri) : best_tri;
+	return triangle_material(tx, p.shapes[best].shape.model.triangle_index + tri_in_model, material);
+}
 #endif
 
 

@@ -335,7 +335,7 @@ static int upload_scene_begin(srt_tracer *t, const ScenePrep &sp, const srt_shap
 	const bool use_bvh = sp.use_bvh;
 	const uint64_t total_wtris = sp.total_wtris, max_tris = sp.max_tris;
 	const int num_models = sp.num_models;
-	if (const int trc = srt_texture_check_scene(t, n_triangles)) return trc; // (before anything of the current scene is replaced)
+	if (const int trc = srt_texture_check_scene(t, n_triangles, n_materials)) return trc; // (before anything of the current scene is replaced)
 	SRT_HIP(t, hipSetDevice(t->device));
 	SRT_HIP(t, hipStreamSynchronize(t->stream)); // previous launches may still read the old scene
 	srt_texture_scene(t, shapes, n_shapes, n_triangles);

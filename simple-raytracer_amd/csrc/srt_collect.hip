@@ -513,6 +513,13 @@ int srt_group_set_triangle_uvs(srt_group *g, const float *uv, size_t n_triangles
 	return SRT_OK;
 }
 
+int srt_group_set_triangle_materials(srt_group *g, const int32_t *materials, size_t n_triangles) {
+	if (!g) return SRT_ERR_INVALID;
+	SRT_EACH(g, srt_set_triangle_materials(t_, materials, n_triangles));
+	drop_history(g); // (as the per-handle call does for its own)
+	return SRT_OK;
+}
+
 int srt_group_set_acceleration(srt_group *g, int mode) {
 	if (!g) return SRT_ERR_INVALID;
 	SRT_EACH(g, srt_set_acceleration(t_, mode));

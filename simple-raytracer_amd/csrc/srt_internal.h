@@ -150,14 +150,18 @@ struct srt_tracer {
 	std::vector<srt_material_texture> tex_bindings; // srt_set_material_textures, as given
 	std::vector<float> tex_uv_host;                 // srt_set_triangle_uvs
 	bool tex_has_uvs = false;
+	std::vector<int32_t> tex_tm_host;               // srt_set_triangle_materials
+	bool tex_has_tm = false;
 	std::vector<PlaneFrame> tex_frames_host; // per shape of the current scene (srt_update_scene)
 	size_t tex_scene_triangles = 0;          // of the current scene
 	DevBuf<float> tex_texels, tex_uvs;
 	DevBuf<TexDesc> tex_descs;
 	DevBuf<srt_material_texture> tex_bind_dev; // one per material of the scene
 	DevBuf<PlaneFrame> tex_frames;
+	DevBuf<int32_t> tex_tm;
 	bool tex_dirty = false;
-	bool tex_active = false;         // a material of the current scene has a texture bound: dispatches launch the textured kernels
+	bool tex_tm_active = false;      // the table has an entry >= 0 and the current scene has triangles
+	bool tex_active = false;         // a material of the current scene has a texture bound, or tex_tm_active: dispatches launch the textured kernels
 	bool last_trace_textured = false; // srt_last_trace_textured
 	int last_trace_class = 0;         // srt_last_trace_class
 	hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;
@@ -192,7 +196,7 @@ void srt_collect_release(srt_tracer *t);
 /* srt_texture.hip: the setters' data checked against a scene that is about to be uploaded; the plane frames and triangle count of the scene being uploaded (srt_update_scene, every group member);
  * checking the setters' data against the current scene and bringing the device tables up to date (after srt_update_scene
  * and before every dispatch; sets tex_active); the tables as the textured kernels take them; freeing them */
-int srt_texture_check_scene(srt_tracer *t, size_t n_triangles); /* before a scene with this many triangles replaces the current one */
+int srt_texture_check_scene(srt_tracer *t, size_t n_triangles, size_t n_materials); /* before a scene with this many triangles and materials replaces the current one */
 void srt_texture_scene(srt_tracer *t, const srt_shape *shapes, size_t n_shapes, size_t n_triangles);
 int srt_texture_sync(srt_tracer *t);
 TexParams srt_texture_params(const srt_tracer *t);

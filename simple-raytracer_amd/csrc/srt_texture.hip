@@ -1,6 +1,7 @@
-// srt_texture.hip -- albedo textures, host side: what srt_set_textures / srt_set_material_textures / srt_set_triangle_uvs
-// store, the checks, the plane frames, the device tables of the textured kernels (kernels_tex.hip) and the choice between
-// those and the untextured ones (tex_active). include/srt_abi.h "albedo textures" states the contract; DESIGN.md §13.
+// srt_texture.hip -- albedo textures and per-triangle materials, host side: what srt_set_textures / srt_set_material_textures /
+// srt_set_triangle_uvs / srt_set_triangle_materials store, the checks, the plane frames, the device tables of the textured
+// kernels (kernels_tex.hip) and the choice between those and the untextured ones (tex_active). include/srt_abi.h "albedo
+// textures" and "per-triangle materials" state the contracts; DESIGN.md §13 and §16.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -65,6 +66,19 @@ std::string check_uvs(bool has_uvs, size_t uv_triangles, size_t scene_triangles)
 	return "";
 }
 
+// per-triangle materials meeting a scene: one entry per triangle, each -1 or a material of the scene
+std::string check_tri_materials(bool has, const int32_t *tm, size_t n, size_t scene_triangles, size_t n_materials) {
+	if (!has) return "";
+	if (n != scene_triangles) return "materials for " + std::to_string(n) + " triangles, the scene has " + std::to_string(scene_triangles);
+	for (size_t k = 0; k < n; k++)
+		if (tm[k] < -1 || (tm[k] >= 0 && (size_t)tm[k] >= n_materials))
+			return "triangle " + std::to_string(k) + " has material " + std::to_string(tm[k]) + " but " + std::to_string(n_materials) + " exist";
+	return "";
+}
+
+// nothing was given to any setter: nothing to check, nothing to upload
+bool nothing_set(const srt_tracer *t) { return t->tex_bindings.empty() && !t->tex_has_uvs && !t->tex_has_tm; }
+
 // after a setter: later dispatches see the new data, the denoiser's history saw the old
 void changed(srt_tracer *t) {
 	t->tex_dirty = true;
@@ -90,25 +104,33 @@ void srt_texture_scene(srt_tracer *t, const srt_shape *shapes, size_t n_shapes, 
 	t->tex_dirty = true;
 }
 
-int srt_texture_check_scene(srt_tracer *t, size_t n_triangles) {
-	if (t->tex_bindings.empty() && !t->tex_has_uvs) return SRT_OK;
+int srt_texture_check_scene(srt_tracer *t, size_t n_triangles, size_t n_materials) {
+	if (nothing_set(t)) return SRT_OK;
 	std::string bad = check_bindings(t->tex_bindings.data(), t->tex_bindings.size(), t->tex_images.size());
 	if (bad.empty()) bad = check_uvs(t->tex_has_uvs, t->tex_uv_host.size() / 6, n_triangles);
+	if (bad.empty()) bad = check_tri_materials(t->tex_has_tm, t->tex_tm_host.data(), t->tex_tm_host.size(), n_triangles, n_materials);
 	if (!bad.empty()) return fail(t, SRT_ERR_INVALID, "srt_update_scene: textures: " + bad);
 	return SRT_OK;
 }
 
 int srt_texture_sync(srt_tracer *t) {
-	t->tex_active = false;
-	if (t->tex_bindings.empty() && !t->tex_has_uvs) return SRT_OK; // nothing bound: nothing to check, nothing to upload
+	t->tex_active = t->tex_tm_active = false;
+	if (nothing_set(t)) return SRT_OK;
 	std::string bad = check_bindings(t->tex_bindings.data(), t->tex_bindings.size(), t->tex_images.size());
 	if (bad.empty() && t->scene_set) bad = check_uvs(t->tex_has_uvs, t->tex_uv_host.size() / 6, t->tex_scene_triangles);
+	if (bad.empty() && t->scene_set)
+		bad = check_tri_materials(t->tex_has_tm, t->tex_tm_host.data(), t->tex_tm_host.size(), t->tex_scene_triangles, t->num_materials);
 	if (!bad.empty()) return fail(t, SRT_ERR_INVALID, "textures: " + bad);
 	if (!t->scene_set) return SRT_OK;
 	const size_t n_mat = t->num_materials;
 	bool any = false;
 	for (size_t i = 0; i < n_mat && i < t->tex_bindings.size(); i++) any = any || t->tex_bindings[i].texture >= 0;
-	if (!any) return SRT_OK;
+	// per-triangle materials are read by the textured kernels alone: a table that replaces something (an entry >= 0; a checked
+	// table is as long as the scene's triangle array, so a scene without triangles has none) launches them with no texture
+	// bound too -- every binding of the table below is then -1 and texture_albedo returns the material's colour
+	bool any_tm = false;
+	for (size_t k = 0; k < t->tex_tm_host.size() && !any_tm; k++) any_tm = t->tex_tm_host[k] >= 0;
+	if (!any && !any_tm) return SRT_OK;
 	if (t->tex_dirty) {
 		std::vector<srt_material_texture> table(n_mat ? n_mat : 1, srt_material_texture{-1, SRT_FILTER_LINEAR, 1.0f, 1.0f});
 		for (size_t i = 0; i < n_mat && i < t->tex_bindings.size(); i++) table[i] = t->tex_bindings[i];
@@ -123,8 +145,13 @@ int srt_texture_sync(srt_tracer *t) {
 			SRT_HIP(t, t->tex_uvs.reserve(t->tex_uv_host.size()));
 			SRT_HIP(t, hipMemcpy(t->tex_uvs.ptr, t->tex_uv_host.data(), t->tex_uv_host.size() * sizeof(float), hipMemcpyHostToDevice));
 		}
+		if (any_tm) {
+			SRT_HIP(t, t->tex_tm.reserve(t->tex_tm_host.size()));
+			SRT_HIP(t, hipMemcpy(t->tex_tm.ptr, t->tex_tm_host.data(), t->tex_tm_host.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+		}
 		t->tex_dirty = false;
 	}
+	t->tex_tm_active = any_tm;
 	t->tex_active = true;
 	return SRT_OK;
 }
@@ -136,12 +163,14 @@ TexParams srt_texture_params(const srt_tracer *t) {
 	x.bindings = t->tex_bind_dev.ptr;
 	x.frames = t->tex_frames.ptr;
 	x.tri_uvs = (t->tex_has_uvs && !t->tex_uv_host.empty()) ? t->tex_uvs.ptr : nullptr;
+	x.tri_materials = t->tex_tm_active ? t->tex_tm.ptr : nullptr;
 	return x;
 }
 
 void srt_texture_release(srt_tracer *t) {
 	t->tex_texels.release();
 	t->tex_uvs.release();
+	t->tex_tm.release();
 	t->tex_descs.release();
 	t->tex_bind_dev.release();
 	t->tex_frames.release();
@@ -218,6 +247,28 @@ int srt_set_triangle_uvs(srt_tracer *t, const float *uv, size_t n_triangles) {
 		return SRT_OK;
 	} catch (...) {
 		return fail(t, SRT_ERR_INVALID, "out of host memory");
+	}
+}
+
+int srt_set_triangle_materials(srt_tracer *t, const int32_t *materials, size_t n_triangles) {
+	if (!t) return SRT_ERR_INVALID;
+	try {
+		if (!materials) n_triangles = 0;
+		t->tex_has_tm = materials != nullptr && n_triangles != 0;
+		t->tex_tm_host.assign(materials, materials + n_triangles);
+		changed(t);
+		return SRT_OK;
+	} catch (...) {
+		return fail(t, SRT_ERR_INVALID, "out of host memory");
+	}
+}
+
+int srt_triangle_materials_check_host(const int32_t *materials, size_t n, size_t scene_triangles, size_t n_materials) {
+	try {
+		if (!materials && n) return SRT_ERR_INVALID;
+		return check_tri_materials(materials != nullptr && n != 0, materials, n, scene_triangles, n_materials).empty() ? SRT_OK : SRT_ERR_INVALID;
+	} catch (...) {
+		return SRT_ERR_INVALID;
 	}
 }
 

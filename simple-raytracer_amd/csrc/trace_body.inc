@@ -482,6 +482,11 @@
 					f3 n = (ld3(tr->vertices[0].normal) * w2 + ld3(tr->vertices[1].normal) * w0) + ld3(tr->vertices[2].normal) * w1;
 					n = mat_by_vec(m->transform, n, 0.0f); // forward matrix, as the reference
 					nrm = normalize3(n);
+#if SRT_TEXTURED
+					// per-triangle materials: everything below that reads a material (emission, thresholds, smoothness, ior, colour,
+					// texture binding) reads the triangle's. Any valid index is consistent with the scene's flags: see triangle_material.
+					material_index = triangle_material(p.tx, m->triangle_index + tri_in_model, material_index);
+#endif
 				}
 				const bool front = dot3(nrm, dir) < 0.0f;
 				nrm = nrm * (front ? 1.0f : -1.0f);

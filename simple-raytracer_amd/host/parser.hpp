@@ -3,7 +3,8 @@
 //
 //   save_ppm        ARGB8 frame -> binary PPM ("P6 W H 255\n", alpha dropped)
 //   load_stl_model  binary STL  -> flat-shaded Triangles (facet normal on all 3 corners)
-//   load_obj_model  Wavefront OBJ (v / vn / f, triangulated) -> smooth-shaded Triangles
+//   load_obj_model  Wavefront OBJ (v / vn / vt / f, triangulated; optionally usemtl / mtllib) -> smooth-shaded Triangles
+//   load_mtl        Wavefront MTL -> named Materials (the mapping is at the function)
 //
 // Both loaders APPEND to `triangles` and return {first index, count}, or nullopt when
 // the file cannot be opened — as the reference does. Deliberate differences (the
@@ -16,6 +17,7 @@
 //   * Index values outside the vertex / normal lists make the loader return nullopt.
 #pragma once
 
+#include <algorithm>
 #include <cinttypes>
 #include <cstdio>
 #include <cstring>
@@ -27,6 +29,7 @@
 #include <utility>
 #include <vector>
 
+#include "material.hpp"
 #include "shape.hpp"
 
 namespace fs = std::filesystem;
@@ -74,7 +77,13 @@ inline std::optional<ModelPair> load_stl_model(const fs::path &filename, std::ve
 /// `uvs` (optional): receives 6 floats per loaded triangle (u, v of its three corners, from the corners' `vt`; a corner
 /// without one, or with an index that does not exist, gets (0, 0)), appended so that the vector stays parallel to
 /// `triangles` when it was before: what Tracer::set_triangle_uvs takes.
-inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vector<Triangle> &triangles, std::vector<float> *uvs = nullptr) {
+/// `face_materials` and `material_names` (optional, given together): `usemtl NAME` sets the current name; every loaded triangle
+/// appends the index of its name in `material_names` (a name is appended there on first use, so several files can share one
+/// list), -1 for a face before any `usemtl`. The caller maps names to indices of its material array (load_mtl) to make what
+/// Tracer::set_triangle_materials takes. `mtllibs` (optional): the file names of the `mtllib` lines, as written.
+inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vector<Triangle> &triangles, std::vector<float> *uvs = nullptr,
+                                               std::vector<int32_t> *face_materials = nullptr, std::vector<std::string> *material_names = nullptr,
+                                               std::vector<std::string> *mtllibs = nullptr) {
 	std::ifstream file(filename, std::ios::in);
 	if (file.fail()) return std::nullopt;
 
@@ -85,6 +94,9 @@ inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vec
 	std::vector<glm::vec3> positions, normals;
 	std::vector<float> texcoords; // u, v per `vt`
 	std::vector<Corner> corners; // 3 per face
+	const bool want_materials = face_materials && material_names;
+	std::vector<int32_t> corner_face_material; // one per face, parallel to corners / 3
+	int32_t current_material = -1;
 
 	std::string line;
 	while (std::getline(file, line)) {
@@ -127,10 +139,21 @@ inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vec
 				c[got].t = vt;
 				got++;
 			}
-			if (got == 3)
+			if (got == 3) {
 				for (auto &k : c) corners.push_back(k);
+				if (want_materials) corner_face_material.push_back(current_material);
+			}
+		} else if (tag == "usemtl" && want_materials) {
+			std::string name;
+			in >> name;
+			const auto at = std::find(material_names->begin(), material_names->end(), name);
+			current_material = (int32_t)(at - material_names->begin());
+			if (at == material_names->end()) material_names->push_back(name);
+		} else if (tag == "mtllib" && mtllibs) {
+			std::string name;
+			while (in >> name) mtllibs->push_back(name);
 		}
-		// '#', 's', 'o', 'g', 'usemtl', ... are ignored
+		// '#', 's', 'o', 'g', ... are ignored
 	}
 
 	auto resolve = [](long index, size_t len) -> long { // -> 0-based, or -1 when invalid
@@ -141,6 +164,7 @@ inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vec
 
 	const unsigned first = (unsigned)triangles.size();
 	const size_t first_uv = uvs ? uvs->size() : 0;
+	const size_t first_fm = want_materials ? face_materials->size() : 0;
 	for (size_t f = 0; f + 2 < corners.size(); f += 3) {
 		Triangle t;
 		bool have_normals = true;
@@ -149,6 +173,7 @@ inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vec
 			if (vi < 0) {
 				triangles.resize(first);
 				if (uvs) uvs->resize(first_uv);
+				if (want_materials) face_materials->resize(first_fm);
 				return std::nullopt;
 			}
 			t.vertices[i].pos = positions[(size_t)vi];
@@ -159,6 +184,7 @@ inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vec
 				if (ni < 0) {
 					triangles.resize(first);
 					if (uvs) uvs->resize(first_uv);
+					if (want_materials) face_materials->resize(first_fm);
 					return std::nullopt;
 				}
 				t.vertices[i].normal = normals[(size_t)ni];
@@ -171,6 +197,7 @@ inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vec
 			for (auto &v : t.vertices) v.normal = n;
 		}
 		triangles.push_back(t);
+		if (want_materials) face_materials->push_back(corner_face_material[f / 3]);
 		if (uvs)
 			for (int i = 0; i < 3; i++) {
 				const long ti = corners[f + i].t == 0 ? -1 : resolve(corners[f + i].t, texcoords.size() / 2);
@@ -179,4 +206,72 @@ inline std::optional<ModelPair> load_obj_model(const fs::path filename, std::vec
 			}
 	}
 	return ModelPair{first, (unsigned)(triangles.size() - first)};
+}
+
+/// Wavefront MTL -> the file's materials in file order, as (name, Material) pairs; `maps` (optional) receives one `map_Kd` file
+/// name per material (empty: none). The mapping is fixed:
+///   Kd r g b   color
+///   Ke r g b   emission; emission_strength = 1 when any component > 0
+///   Ni x       refraction_index
+///   d x        transmittance = 1 - x
+///   Tr x       transmittance = x
+///   Pm x       metallic
+///   Pr x       smoothness = 1 - x
+///   Ns x       smoothness = clamp(x / 1000, 0, 1), only in a material without Pr
+///   map_Kd f   reported through `maps`
+/// Everything else starts from Material()'s defaults; unknown keys are ignored; a file that cannot be opened gives an empty list.
+inline std::vector<std::pair<std::string, Material>> load_mtl(const fs::path &filename, std::vector<std::string> *maps = nullptr) {
+	std::vector<std::pair<std::string, Material>> out;
+	std::ifstream file(filename, std::ios::in);
+	if (file.fail()) return out;
+	bool have_pr = false;
+	std::string line;
+	while (std::getline(file, line)) {
+		std::istringstream in(line);
+		std::string tag;
+		in >> tag;
+		if (tag == "newmtl") {
+			std::string name;
+			in >> name;
+			out.emplace_back(name, Material());
+			if (maps) maps->push_back("");
+			have_pr = false;
+			continue;
+		}
+		if (out.empty()) continue; // a key before the first newmtl belongs to nothing
+		Material &m = out.back().second;
+		float x = 0, y = 0, z = 0;
+		if (tag == "Kd") {
+			in >> x >> y >> z;
+			m.color = Color(x, y, z);
+		} else if (tag == "Ke") {
+			in >> x >> y >> z;
+			m.emission = Color(x, y, z);
+			m.emission_strength = (x > 0.0f || y > 0.0f || z > 0.0f) ? 1.0f : 0.0f;
+		} else if (tag == "Ni") {
+			in >> x;
+			m.refraction_index = x;
+		} else if (tag == "d") {
+			in >> x;
+			m.transmittance = 1.0f - x;
+		} else if (tag == "Tr") {
+			in >> x;
+			m.transmittance = x;
+		} else if (tag == "Pm") {
+			in >> x;
+			m.metallic = x;
+		} else if (tag == "Pr") {
+			in >> x;
+			m.smoothness = 1.0f - x;
+			have_pr = true;
+		} else if (tag == "Ns") {
+			in >> x;
+			if (!have_pr) m.smoothness = std::min(std::max(x / 1000.0f, 0.0f), 1.0f);
+		} else if (tag == "map_Kd" && maps) {
+			std::string name, last;
+			while (in >> name) last = name; // options (-s, -o, ...) come before the file name
+			maps->back() = last;
+		}
+	}
+	return out;
 }

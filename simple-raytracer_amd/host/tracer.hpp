@@ -152,6 +152,14 @@ class Tracer {
 		check(group ? srt_group_set_triangle_uvs(group, p, uvs.size() / 6) : srt_set_triangle_uvs(handle, p, uvs.size() / 6));
 	}
 
+	/// Per-triangle materials (include/srt_abi.h "per-triangle materials"): one index into the material array per triangle,
+	/// parallel to `triangles` as load_obj_model hands them out for an OBJ's `usemtl` groups; -1 keeps the shape's material.
+	/// An empty vector removes the table. Does not clear the canvas.
+	void set_triangle_materials(const std::vector<int32_t> &materials) {
+		const int32_t *p = materials.empty() ? nullptr : materials.data();
+		check(group ? srt_group_set_triangle_materials(group, p, materials.size()) : srt_set_triangle_materials(handle, p, materials.size()));
+	}
+
 	/// SRT_ACCEL_BVH: models get a bounding-volume hierarchy at the next update_scene (the
 	/// reference's README.md:41 "future plan"); SRT_ACCEL_NONE (default) keeps the array-order scan
 	void set_acceleration(int mode) { check(group ? srt_group_set_acceleration(group, mode) : srt_set_acceleration(handle, mode)); }

@@ -5,7 +5,7 @@
 //
 //   srt_headless [--scene spheres|meshes|empty] [--obj f.obj]... [--stl f.stl]...
 //                [--width W --height H --spp S --bounces B --frames N --time T]
-//                [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--demodulate] [--temporal] [--move DX]
+//                [--obj-materials] [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--demodulate] [--temporal] [--move DX]
 // --denoise K: the frames go through the edge-aware denoiser with K a-trous passes (Tracer::set_denoise; with --gpus N the
 //                members gather the filter's inputs with the frame and device 0 filters: the same bytes as on one device)
 // --demodulate: with --denoise, the passes filter colour / first-hit albedo (Tracer::set_denoise_demodulation); an error without it
@@ -20,6 +20,11 @@
 //
 // --texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]: an 8-bit binary PPM as the albedo texture of
 //                   material N, its texels prepared like the sky's (host/skybox.hpp); OBJ models hand their `vt` out as UVs
+// --obj-materials: OBJ models keep their `usemtl` groups: the `mtllib` files are read relative to the OBJ (host/parser.hpp
+//                   load_mtl), their materials appended to the scene's, and every triangle gets the material of its group
+//                   (Tracer::set_triangle_materials); a group whose name no MTL file defines, and everything that is not an
+//                   OBJ, keeps the shape's material. A `map_Kd` that names a binary PPM becomes that material's texture
+//                   (as --texture); any other kind of file is reported and skipped. --parse-only prints the table's summary.
 // --dump prefix writes prefix.{shapes,tris,mats,rd,sd,canvas,argb}.bin (raw records).
 // --parse-only skips everything that needs a GPU (loaders + scene construction only).
 #include <chrono>
@@ -111,7 +116,7 @@ int main(int argc, char **argv) {
 	std::vector<std::string> objs, stls;
 	int width = 256, height = 256, spp = 16, bounces = 10, frames = 1;
 	unsigned time_seed = 12345;
-	bool parse_only = false, bvh = false, pipelined = false;
+	bool parse_only = false, bvh = false, pipelined = false, obj_materials = false;
 	int gpus = 1, denoise = -1;
 	bool temporal = false, demodulate = false;
 	float move = 0.0f, shape_move = 0.0f;
@@ -139,6 +144,7 @@ int main(int argc, char **argv) {
 		else if (a == "--dump") dump_prefix = next();
 		else if (a == "--parse-only") parse_only = true;
 		else if (a == "--bvh") bvh = true;
+		else if (a == "--obj-materials") obj_materials = true;
 		else if (a == "--gpus") gpus = std::atoi(next());
 		else if (a == "--pipelined") pipelined = true;
 		else if (a == "--skybox") skybox_path = next();
@@ -154,7 +160,7 @@ int main(int argc, char **argv) {
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--temporal] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]]\n";
+			             "[--denoise K] [--demodulate] [--temporal] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
@@ -199,6 +205,7 @@ int main(int argc, char **argv) {
 		materials.add(Material()); // the app's start-up state (main.cpp:100)
 	}
 
+	std::vector<std::pair<std::string, int>> mtl_index; // --obj-materials: (MTL material name, its index in `materials`)
 	int slot = 0;
 	auto add_model = [&](const std::optional<ModelPair> &pair, const std::string &path) {
 		if (!pair) {
@@ -215,9 +222,51 @@ int main(int argc, char **argv) {
 		std::cout << path << ": " << pair->second << " triangles at " << pair->first << "\n";
 	};
 	std::vector<float> uvs(triangles.size() * 6, 0.0f); // parallel to `triangles`: the box's and STL triangles have none
-	for (auto &p : objs) add_model(load_obj_model(p, triangles, &uvs), p);
+	// --obj-materials: the `usemtl` name of every triangle (an index into usemtl_names, -1: none), the OBJs' MTL materials
+	// appended to the scene's, and the table Tracer::set_triangle_materials takes
+	std::vector<int32_t> face_names(triangles.size(), -1), triangle_materials;
+	std::vector<std::string> usemtl_names;
+	std::vector<std::pair<int, std::string>> material_maps; // (material, its map_Kd file)
+	for (auto &p : objs) {
+		if (!obj_materials) {
+			add_model(load_obj_model(p, triangles, &uvs), p);
+			continue;
+		}
+		std::vector<std::string> mtllibs;
+		add_model(load_obj_model(p, triangles, &uvs, &face_names, &usemtl_names, &mtllibs), p);
+		for (auto &lib : mtllibs) {
+			std::vector<std::string> maps;
+			const fs::path lib_path = fs::path(p).parent_path() / lib;
+			const auto loaded = load_mtl(lib_path, &maps);
+			if (loaded.empty()) std::cerr << lib_path.string() << ": no materials read\n";
+			for (size_t i = 0; i < loaded.size(); i++) {
+				const int index = materials.add(loaded[i].second);
+				mtl_index.emplace_back(loaded[i].first, index);
+				if (!maps[i].empty()) material_maps.emplace_back(index, (lib_path.parent_path() / maps[i]).string());
+			}
+		}
+	}
 	for (auto &p : stls) add_model(load_stl_model(p, triangles), p);
 	uvs.resize(triangles.size() * 6, 0.0f);
+	if (obj_materials) {
+		face_names.resize(triangles.size(), -1);
+		std::vector<int32_t> of_name(usemtl_names.size(), -1); // a name no MTL file defines keeps the shape's material
+		for (size_t n = 0; n < usemtl_names.size(); n++)
+			for (auto &entry : mtl_index)
+				if (entry.first == usemtl_names[n]) {
+					of_name[n] = entry.second; // (the first definition of a name counts)
+					break;
+				}
+		size_t with = 0;
+		for (int32_t f : face_names) {
+			triangle_materials.push_back(f < 0 ? -1 : of_name[(size_t)f]);
+			with += triangle_materials.back() >= 0;
+		}
+		std::cout << "per-triangle materials: " << triangle_materials.size() << " triangles, " << with << " with a material of their own, " << usemtl_names.size()
+		          << " usemtl names:";
+		for (size_t n = 0; n < usemtl_names.size(); n++) std::cout << ' ' << usemtl_names[n] << '=' << of_name[n];
+		std::cout << "\n";
+	}
 
 	const glm::mat4 camera_to_world = eye_matrix(glm::vec3(0.0f, 0.5f, 5.0f), 0.0f, 0.0f);
 
@@ -225,6 +274,7 @@ int main(int argc, char **argv) {
 		dump(dump_prefix + ".shapes.bin", shapes.data(), shapes.size());
 		dump(dump_prefix + ".tris.bin", triangles.data(), triangles.size());
 		dump(dump_prefix + ".mats.bin", materials.list.data(), materials.list.size());
+		if (obj_materials) dump(dump_prefix + ".tm.bin", triangle_materials.data(), triangle_materials.size());
 	}
 	if (parse_only) return 0;
 
@@ -265,10 +315,18 @@ int main(int argc, char **argv) {
 		sky = synthetic_sky(sky_w, sky_h);
 	}
 	tracer.set_skybox(sky.data(), sky_w, sky_h);
-	if (!texture_path.empty()) {
+	std::vector<Tracer::Texture> textures;
+	std::vector<Tracer::MaterialTexture> bindings(materials.list.size(), Tracer::MaterialTexture{-1, SRT_FILTER_LINEAR, 1.0f, 1.0f});
+	auto load_texture = [&](const std::string &path, Tracer::Texture &tex) {
 		std::vector<uint8_t> rgb;
+		if (!load_ppm(path, rgb, tex.width, tex.height)) return false;
+		tex.rgba.resize((size_t)tex.width * tex.height * 4);
+		srt_skybox_from_rgb8(rgb.data(), tex.width, tex.height, 3, tex.rgba.data());
+		return true;
+	};
+	if (!texture_path.empty()) {
 		Tracer::Texture tex;
-		if (!load_ppm(texture_path, rgb, tex.width, tex.height)) {
+		if (!load_texture(texture_path, tex)) {
 			std::cerr << "cannot read " << texture_path << " (binary PPM, P6, maxval 255)\n";
 			return 3;
 		}
@@ -276,18 +334,28 @@ int main(int argc, char **argv) {
 			std::cerr << "--texture needs --texture-material N with N below " << materials.list.size() << "\n";
 			return 2;
 		}
-		tex.rgba.resize((size_t)tex.width * tex.height * 4);
-		srt_skybox_from_rgb8(rgb.data(), tex.width, tex.height, 3, tex.rgba.data());
-		std::vector<Tracer::MaterialTexture> bindings(materials.list.size(), Tracer::MaterialTexture{-1, SRT_FILTER_LINEAR, 1.0f, 1.0f});
 		bindings[(size_t)texture_material] = Tracer::MaterialTexture{0, texture_nearest ? SRT_FILTER_NEAREST : SRT_FILTER_LINEAR, texture_scale, texture_scale};
-		tracer.set_textures({tex});
+		textures.push_back(tex);
+	}
+	for (auto &map : material_maps) { // --obj-materials: the MTL files' map_Kd, where the tool reads that kind of file
+		Tracer::Texture tex;
+		if (textures.size() >= SRT_MAX_TEXTURES || !load_texture(map.second, tex)) {
+			std::cerr << "map_Kd " << map.second << " of material " << map.first << ": not a binary PPM the tool reads (or too many images), skipped\n";
+			continue;
+		}
+		bindings[(size_t)map.first] = Tracer::MaterialTexture{(int32_t)textures.size(), SRT_FILTER_LINEAR, 1.0f, 1.0f};
+		textures.push_back(tex);
+	}
+	if (!textures.empty()) {
+		tracer.set_textures(textures);
 		tracer.set_material_textures(bindings);
 		if (!objs.empty()) tracer.set_triangle_uvs(uvs);
 		if (!dump_prefix.empty()) {
-			dump(dump_prefix + ".texture.bin", tex.rgba.data(), tex.rgba.size());
+			dump(dump_prefix + ".texture.bin", textures[0].rgba.data(), textures[0].rgba.size());
 			dump(dump_prefix + ".uvs.bin", uvs.data(), uvs.size());
 		}
 	}
+	if (obj_materials) tracer.set_triangle_materials(triangle_materials);
 	if (!dump_prefix.empty()) dump(dump_prefix + ".sky.bin", sky.data(), sky.size());
 
 	std::vector<uint8_t> pixels((size_t)width * height * 4);

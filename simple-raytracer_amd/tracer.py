@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "srt_set_textures", "srt_set_material_textures", "srt_set_triangle_uvs", "srt_last_trace_textured", "srt_plane_frame_host",
     "srt_texture_check_host", "srt_group_set_textures", "srt_group_set_material_textures", "srt_group_set_triangle_uvs",
     "srt_last_trace_class", "srt_bernoulli_threshold_host",
+    "srt_set_triangle_materials", "srt_group_set_triangle_materials", "srt_triangle_materials_check_host",
     "srt_group_set_denoise", "srt_group_set_denoise_temporal", "srt_group_reset_denoise_history", "srt_group_resolve_denoised",
     "srt_group_read_denoised", "srt_group_read_denoise_inputs", "srt_group_read_denoise_history", "srt_partition_planes_floats",
     "srt_unpermute_planes_device",
@@ -78,6 +79,20 @@ def _uv_array(uv):
         return None, 0
     uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 3, 2)
     return uv, len(uv)
+
+
+def _tm_array(tm):
+    if tm is None:
+        return None
+    tm = np.ascontiguousarray(tm, np.int32).reshape(-1)
+    return tm if len(tm) else None
+
+
+def triangle_materials_check_host(materials, scene_triangles, n_materials):
+    """srt_triangle_materials_check_host (host only): the return code for a table (None: no table) meeting a scene."""
+    lib = load_library()
+    tm = None if materials is None else np.ascontiguousarray(materials, np.int32).reshape(-1)
+    return lib.srt_triangle_materials_check_host(_ptr(tm) if tm is not None else None, 0 if tm is None else len(tm), int(scene_triangles), int(n_materials))
 
 
 def plane_frame_host(normal):
@@ -432,6 +447,10 @@ def _bind(lib):
         lib.srt_group_set_textures.argtypes = [vp, vp, sz]
         lib.srt_group_set_material_textures.argtypes = [vp, vp, sz]
         lib.srt_group_set_triangle_uvs.argtypes = [vp, vp, sz]
+    if hasattr(lib, "srt_set_triangle_materials"):  # (an older library, SRT_LIB, in an A/B run)
+        lib.srt_set_triangle_materials.argtypes = [vp, vp, sz]
+        lib.srt_group_set_triangle_materials.argtypes = [vp, vp, sz]
+        lib.srt_triangle_materials_check_host.argtypes = [vp, sz, sz, sz]
     if hasattr(lib, "srt_last_trace_class"):  # (an older library, SRT_LIB, in an A/B run)
         lib.srt_last_trace_class.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(lib, "srt_bernoulli_threshold_host"):
@@ -541,7 +560,9 @@ class Tracer(_Denoise):
     # -- plumbing --
     def _check(self, rc):
         if rc:
-            raise SrtError(self.lib.srt_last_error(self._h).decode())
+            e = SrtError(self.lib.srt_last_error(self._h).decode())
+            e.code = rc  # SRT_ERR_*
+            raise e
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -575,6 +596,12 @@ class Tracer(_Denoise):
         """uv: (n_triangles, 3, 2) float32 parallel to the triangle array, or None."""
         uv, n = _uv_array(uv)
         self._check(self.lib.srt_set_triangle_uvs(self._h, _ptr(uv) if uv is not None else None, n))
+
+    def set_triangle_materials(self, materials):
+        """materials: n_triangles int32 parallel to the triangle array (-1: the shape's material, m >= 0: materials[m]), or None
+        (include/srt_abi.h "per-triangle materials")."""
+        tm = _tm_array(materials)
+        self._check(self.lib.srt_set_triangle_materials(self._h, _ptr(tm) if tm is not None else None, 0 if tm is None else len(tm)))
 
     def last_trace_textured(self):
         out = C.c_int(0)
@@ -848,7 +875,9 @@ class TracerGroup(_Denoise):
 
     def _check(self, rc):
         if rc:
-            raise SrtError(self.lib.srt_group_last_error(self._g).decode())
+            e = SrtError(self.lib.srt_group_last_error(self._g).decode())
+            e.code = rc
+            raise e
 
     def close(self):
         if getattr(self, "_g", None) is not None and self._g.value:
@@ -883,6 +912,10 @@ class TracerGroup(_Denoise):
     def set_triangle_uvs(self, uv):
         uv, n = _uv_array(uv)
         self._check(self.lib.srt_group_set_triangle_uvs(self._g, _ptr(uv) if uv is not None else None, n))
+
+    def set_triangle_materials(self, materials):
+        tm = _tm_array(materials)
+        self._check(self.lib.srt_group_set_triangle_materials(self._g, _ptr(tm) if tm is not None else None, 0 if tm is None else len(tm)))
 
     def update_scene(self, shapes, triangles, materials):
         shapes = R.as_records(shapes, R.SHAPE)
