@@ -199,8 +199,8 @@ int srt_get_counters(srt_tracer *t, srt_counters *out);
 int srt_set_count_triangles(srt_tracer *t, int enable);
 int srt_reset_counters(srt_tracer *t);
 /* Diagnostics of the trace kernel's scheduling (not part of any result): out[0..4] = rays, sky, paths,
- * tri_tests, tri_pass_u as above; out[5] = 0 (rounds 1-3: paths that outlived their LDS staging buffer; since round 4
- * every path stores its radiance itself); out[6] = iterations of the
+ * tri_tests, tri_pass_u as above; out[5] = the scene-class kernels' EXTEND phases that held fresh camera rays only (they run
+ * the camera forms of the tests) << 36 | the rays in those phases, 0 for every other kernel; out[6] = iterations of the
  * waves' main loop; out[7] = SHADE phases executed (sums since the last srt_reset_counters); out[8] = persistent
  * waves per CU and out[9] = workgroups of the most recent trace launch; out[10..17] = per-phase wave cycles
  * (extend, sky ring, shade, park, deliver, refill, loop head, whole kernel) of a -DSRT_PHASE_CLOCK build; in the product

@@ -131,6 +131,15 @@ enum { SRT_CTR_RAYS = 0, SRT_CTR_SKY, SRT_CTR_TRI, SRT_CTR_TRI_PASS_U, SRT_CTR_N
 	X(3, SRT_GC_SSS, true)      \
 	X(4, SRT_GC_PPP, true)
 #define SRT_SCENE_CLASS_GENERAL 0
+/* A class kernel keeps, per sphere of its group, what a camera ray's test makes from the sphere and the camera's origin alone
+ * (kernels.hip "CAMERA PHASES"): one float4 {L, c} per sphere slot of every sphere block of the header `code`, behind the hit
+ * queue in the wave's dynamic LDS. The launcher adds the bytes; 64 for the benchmark's layout, which stays inside the LDS
+ * allocation 21 resident waves per CU leave each of them (7,536 -> 7,600 of 7,801 bytes). */
+static constexpr inline uint32_t srt_class_cam_records(uint32_t code) {
+	return ((code & 3u) == SRT_SHAPE_SPHERE + 1u ? 4u : 0u) + (((code >> 8) & 3u) == SRT_SHAPE_SPHERE + 1u ? 4u : 0u) +
+	       (((code >> 16) & 3u) == SRT_SHAPE_SPHERE + 1u ? 4u : 0u);
+}
+static constexpr inline size_t srt_class_cam_lds_bytes(uint32_t code) { return 16u * (size_t)srt_class_cam_records(code); }
 
 /* Winner records and materials (sphere / plane scenes: group headers and shape blocks too) are staged in LDS when they are
  * small enough not to cost the trace kernel a resident wave; 0 = they stay in global memory. All record types are

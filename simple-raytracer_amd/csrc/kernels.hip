@@ -574,6 +574,102 @@ __device__ __forceinline__ void test_planes2(const Blk16 &b, uint32_t count, f3 
 	}
 }
 
+// ---- CAMERA PHASES of the scene classes (trace_body.inc EXTEND) ------------------------------------------------
+// Every camera ray of a launch starts at camera_to_world[3], so what the two tests above make from a shape and the origin
+// alone is the same number for all of them: a sphere's L = centre - org and c = dot3(L, L) - r*r, a plane's
+// num = dot3(n, p - org). A class kernel makes them once per wave in its prologue (cam_records_of_block: the expressions of
+// test_spheres / test_planes2, on the device, so the bits are theirs) and keeps them in LDS: a sphere's {L, c} as a record of
+// its own behind the hit queue, a plane's num in the unused fourth dword of its point in the staged block. An EXTEND phase in
+// which every ray is a fresh camera ray (one wave-uniform flag, set by REFILL) runs the forms below, which start from those
+// numbers and are otherwise the sequences above. The 64 rays of such a phase are (nearly) one pixel's, so they mostly agree on
+// which spheres they cannot hit, and one vote per sphere takes out work that would change no lane's tmin / best: a sphere whose
+// discriminant is negative or NaN on every lane that holds a ray has a NaN root there, both keys are above +inf's bits, and
+// take_if_closer takes nothing. (+inf votes "may hit" and is rooted as before; tiny and zero discriminants have gone to the
+// slow path before the vote.) The same vote for a plane -- skip the division where every lane's quotient is certainly negative
+// and not -0 -- was built and measured nothing beyond the hoisting (profiles/r13_camera_phase_ab.txt, `hoist_pln`): not kept.
+// The development switches exist for the A/B of each cut alone (profiles/README.md).
+#ifndef SRT_CAM_FORM
+#define SRT_CAM_FORM 1
+#endif
+#ifndef SRT_CAM_SPHERE_VOTE
+#define SRT_CAM_SPHERE_VOTE 1
+#endif
+// cam: the block's records {L, c}; actm: the lanes that hold a ray (the others compute on whatever they hold and must not vote)
+template <int N>
+__device__ __forceinline__ void test_spheres_cam(const float4 *__restrict__ cam, f3 dir, unsigned long long actm, int idx0, float &tmin, int &best) {
+	float bq[4], disc[4];
+	bool slow = is_neg_zero(tmin);
+#pragma unroll
+	for (int i = 0; i < N; i++) {
+		const float4 lc = cam[i];
+		bq[i] = dot3(mk(lc.x, lc.y, lc.z), dir);
+		disc[i] = bq[i] * bq[i] - lc.w;
+		slow = slow || dm_fabs(disc[i]) < 0x1p-96f;
+	}
+	if (__builtin_expect(any64(slow), 0)) { // (wave-uniform) the reference's sequence, as in test_spheres
+#pragma unroll
+		for (int i = 0; i < N; i++) { // @rare
+			const float sq = __builtin_sqrtf(disc[i]); // @rare
+			float t = bq[i] - sq; // @rare
+			if (t < 0.0f) t = bq[i] + sq; // @rare
+			if (!(disc[i] < 0.0f) && !(t < 0.0f) && t < tmin) tmin = t, best = idx0 + i; // @rare
+		}
+	} else {
+#if SRT_CAM_SPHERE_VOTE
+#pragma unroll
+		for (int i = 0; i < N; i++) {
+			if ((ballot64(disc[i] >= 0.0f) & actm) != 0ull) { // (wave-uniform) somebody's ray may hit sphere i
+				const float sq = sqrt_rsq(disc[i]);
+				const uint32_t k = min(dm_f2u(bq[i] - sq), dm_f2u(bq[i] + sq));
+				take_if_closer(dm_u2f(k), idx0 + i, tmin, best);
+			}
+		}
+#else
+		float dd[N], sq[N];
+#pragma unroll
+		for (int i = 0; i < N; i++) dd[i] = disc[i];
+		sqrt_rsq_n<N, false>(dd, sq);
+#pragma unroll
+		for (int i = 0; i < N; i++) {
+			const uint32_t k = min(dm_f2u(bq[i] - sq[i]), dm_f2u(bq[i] + sq[i]));
+			take_if_closer(dm_u2f(k), idx0 + i, tmin, best);
+		}
+#endif
+	}
+}
+// blk: the staged block {p, num, n, 0} x 2
+__device__ __forceinline__ void test_planes2_cam(const float4 *__restrict__ blk, uint32_t count, f3 dir, int idx0, float &tmin, int &best) {
+#pragma unroll
+	for (int i = 0; i < 2; i++) {
+		if (i == 1 && count < 2u) break;
+		const float4 nq = blk[2 * i + 1];
+		const float num = reinterpret_cast<const float *>(blk + 2 * i)[3];
+		const float denom = dot3(mk(nq.x, nq.y, nq.z), dir);
+		const float t = num / denom;
+		const bool hit = !(t < 0.0f);
+		if (hit && t < tmin) {
+			tmin = t;
+			best = idx0 + i;
+		}
+	}
+}
+// The prologue's part: block K of the class, staged at blk, seen from the camera's origin. Lane i makes shape i's numbers.
+template <uint32_t K>
+__device__ __forceinline__ void cam_records_of_block(float4 *__restrict__ blk, float4 *__restrict__ cam, f3 org, int lane) {
+	if constexpr ((K & 3u) == SRT_SHAPE_SPHERE + 1u) {
+		if (lane < 4) {
+			const float4 s = blk[lane];
+			const f3 L = mk(s.x - org.x, s.y - org.y, s.z - org.z);
+			const float c = dot3(L, L) - s.w;
+			cam[lane] = make_float4(L.x, L.y, L.z, c);
+		}
+	} else if constexpr ((K & 3u) == SRT_SHAPE_PLANE + 1u) {
+		if (lane < 2) {
+			const float4 pq = blk[2 * lane], nq = blk[2 * lane + 1];
+			reinterpret_cast<float *>(blk + 2 * lane)[3] = dot3(mk(nq.x, nq.y, nq.z), mk(pq.x - org.x, pq.y - org.y, pq.z - org.z));
+		}
+	}
+}
 // render.cl:279-290 with tmax = the lane's current closest t
 __device__ __forceinline__ bool test_aabb(float lx, float ly, float lz, float hx, float hy, float hz, f3 org, f3 inv, float tmax) {
 	float t0 = 0.0f, t1 = tmax;
@@ -1214,6 +1310,16 @@ __device__ __forceinline__ void test_block_of_class(const Blk16 &b, int base, f3
 		test_planes2(b, (K >> 2) & 7u, org, dir, base, tmin, best);
 	}
 }
+// the same block in a phase of fresh camera rays only ("CAMERA PHASES" above): blk = the staged block, cam = its spheres' records
+template <uint32_t K>
+__device__ __forceinline__ void test_block_of_class_cam(const float4 *__restrict__ blk, const float4 *__restrict__ cam, int base, f3 dir, unsigned long long actm, float &tmin, int &best) {
+	if constexpr ((K & 3u) == SRT_SHAPE_SPHERE + 1u) {
+		if constexpr (((K >> 2) & 7u) <= 2u) test_spheres_cam<2>(cam, dir, actm, base, tmin, best);
+		else test_spheres_cam<4>(cam, dir, actm, base, tmin, best);
+	} else if constexpr ((K & 3u) == SRT_SHAPE_PLANE + 1u) {
+		test_planes2_cam(blk, (K >> 2) & 7u, dir, base, tmin, best);
+	}
+}
 
 template <bool COUNT_TRIS, bool USE_LDS, bool HAS_MODELS, bool USE_BVH>
 __global__ __launch_bounds__(64, USE_BVH ? SRT_TRACE_WAVES_PER_SIMD_BVH : HAS_MODELS ? SRT_TRACE_WAVES_PER_SIMD_MODELS : SRT_TRACE_WAVES_PER_SIMD) void srt_trace_kernel(const SRT_TRACE_PARAMS p) {
@@ -1647,6 +1753,20 @@ TraceKernel pick_trace_kernel(const SRT_TRACE_PARAMS &p, bool use_lds, bool coun
 #endif
 	return pick_trace_kernel(p.num_models > 0, p.use_bvh != 0, use_lds, count_triangles);
 }
+// dynamic LDS of a launch: the scene records, the per-wave queues and, for a scene class, its camera records ("CAMERA PHASES")
+size_t trace_lds_bytes(const SRT_TRACE_PARAMS &p, size_t scene_lds) {
+	size_t need = scene_lds + (size_t)srt_trace_lds_floats(p.num_models > 0, p.use_bvh) * sizeof(float);
+#if SRT_SCENE_CLASSES
+	switch (p.scene_class) {
+#define SRT_SCENE_CLASS_CASE(number, code, no_spec) \
+	case number: need += srt_class_cam_lds_bytes(code); break;
+		SRT_SCENE_CLASS_LIST(SRT_SCENE_CLASS_CASE)
+#undef SRT_SCENE_CLASS_CASE
+	default: break;
+	}
+#endif
+	return need;
+}
 } // namespace
 
 // whether this build has the scene classes at all (the textured, instrumented and development builds do not)
@@ -1659,7 +1779,7 @@ int srt_trace_has_scene_classes() { return SRT_SCENE_CLASSES; }
 // waves would only start -- each with a first chunk of its own -- when others have drained the queue.
 int srt_trace_resident_waves_per_cu(const SRT_TRACE_PARAMS &p, bool count_triangles) {
 	const size_t scene_lds = scene_lds_bytes(p);
-	const size_t need = scene_lds + (size_t)srt_trace_lds_floats(p.num_models > 0, p.use_bvh) * sizeof(float);
+	const size_t need = trace_lds_bytes(p, scene_lds);
 	int blocks = 0;
 	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, pick_trace_kernel(p, scene_lds != 0, count_triangles), 64, need) != hipSuccess ||
 	    blocks <= 0) {
@@ -1675,7 +1795,7 @@ void srt_launch_trace(SRT_TRACE_PARAMS p, bool count_triangles, int num_waves, v
 	const size_t scene_lds = scene_lds_bytes(p);
 	p.lds_bytes = (uint32_t)scene_lds;
 	p.stage_off = (uint32_t)(scene_lds / sizeof(float4));
-	const size_t need = scene_lds + (size_t)srt_trace_lds_floats(p.num_models > 0, p.use_bvh) * sizeof(float);
+	const size_t need = trace_lds_bytes(p, scene_lds);
 	hipLaunchKernelGGL(pick_trace_kernel(p, scene_lds != 0, count_triangles), grid, block, need, (hipStream_t)stream, p);
 }
 

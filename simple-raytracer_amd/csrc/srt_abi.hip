@@ -1149,8 +1149,8 @@ int srt_acceleration_info(const srt_tracer *t, uint64_t out[7]) {
 	return SRT_OK;
 }
 
-/* diagnostics: sums of the eight per-wave counter slots since the last reset (slot 5 = unused since round 4, 6 = wave
- * iterations, 7 = SHADE phases) */
+/* diagnostics: sums of the eight per-wave counter slots since the last reset (slot 5 = the scene-class kernels' EXTEND phases of
+ * fresh camera rays only << 36 | the rays in those phases, 6 = wave iterations, 7 = SHADE phases) */
 int srt_debug_counters(srt_tracer *t, uint64_t out[18]) {
 	if (!t || !out) return SRT_ERR_INVALID;
 	SRT_HIP(t, hipSetDevice(t->device));

@@ -77,6 +77,21 @@
 	float *__restrict__ ring = reinterpret_cast<float *>(lds + p.stage_off); // [10][64] escaped paths awaiting their sky lookup
 	float *__restrict__ hq = ring + 10u * (uint32_t)SRT_RING_CAP; // [hq_fields][HQ] paths that hit, awaiting their bounce (FIFO)
 	constexpr uint32_t HQ = USE_BVH ? SRT_HQ_CAP_BVH : HAS_MODELS ? SRT_HQ_CAP_MODELS : SRT_HQ_CAP;
+	// Scene classes: what a camera ray's tests make from a shape and the camera's origin alone, once per wave (kernels.hip
+	// "CAMERA PHASES"): the spheres' records {L, c} behind the hit queue, a plane's num in the staged block itself.
+	constexpr bool CAM = FAST && SRT_CAM_FORM != 0;
+	constexpr uint32_t CS1 = srt_class_cam_records(FK0), CS2 = srt_class_cam_records(FK0 | (FK1 << 8)); // first record of block 1 / 2
+	float4 *__restrict__ cam_rec = reinterpret_cast<float4 *>(hq + hq_fields(HAS_MODELS) * HQ);
+	if (CAM) {
+		const auto &c = SRT_COLD(p);
+		const f3 cam_org = mk(c.rd.camera_to_world[3].x, c.rd.camera_to_world[3].y, c.rd.camera_to_world[3].z); // as CAMERA loads it
+		cam_records_of_block<FK0>(lds + 2 * FN, cam_rec, cam_org, lane);
+		cam_records_of_block<FK1>(lds + 2 * FN + 4, cam_rec + CS1, cam_org, lane);
+		cam_records_of_block<FK2>(lds + 2 * FN + 8, cam_rec + CS2, cam_org, lane);
+		__syncthreads();
+	}
+	bool cam_phase = false;  // (wave-uniform) every lane of actm took its ray in the REFILL just before: EXTEND runs the camera forms
+	unsigned long long w_cam = 0; // diagnostics: such phases << 36 | the rays in them (srt_debug_counters; good for some 8 full-size frames between resets)
 #ifdef SRT_REGION_COUNT
 	uint32_t *region_ctr = reinterpret_cast<uint32_t *>(hq + hq_fields(HAS_MODELS) * HQ);
 	for (int i = lane; i < 2 * SRT_REGION_MAX; i += 64) region_ctr[i] = 0u;
@@ -272,9 +287,17 @@
 							b.v[8] = q2.x, b.v[9] = q2.y, b.v[10] = q2.z, b.v[11] = q2.w, b.v[12] = q3.x, b.v[13] = q3.y, b.v[14] = q3.z, b.v[15] = q3.w;
 							return b;
 						};
-						test_block_of_class<FK0>(ld_lds(0), 0, org, dir, tmin, best);
-						if (FK1 != 0u) test_block_of_class<FK1>(ld_lds(1), FN0, org, dir, tmin, best);
-						if (FK2 != 0u) test_block_of_class<FK2>(ld_lds(2), FN0 + FN1, org, dir, tmin, best);
+						if (CAM && cam_phase) {
+							// (wave-uniform) fresh camera rays only: the same tests in the same order from the prologue's numbers
+							w_cam += (1ull << 36) + popc64(actm);
+							test_block_of_class_cam<FK0>(lb, cam_rec, 0, dir, actm, tmin, best);
+							if (FK1 != 0u) test_block_of_class_cam<FK1>(lb + 4, cam_rec + CS1, FN0, dir, actm, tmin, best);
+							if (FK2 != 0u) test_block_of_class_cam<FK2>(lb + 8, cam_rec + CS2, FN0 + FN1, dir, actm, tmin, best);
+						} else {
+							test_block_of_class<FK0>(ld_lds(0), 0, org, dir, tmin, best);
+							if (FK1 != 0u) test_block_of_class<FK1>(ld_lds(1), FN0, org, dir, tmin, best);
+							if (FK2 != 0u) test_block_of_class<FK2>(ld_lds(2), FN0 + FN1, org, dir, tmin, best);
+						}
 					}
 					for (int g = 0; g < n_groups; g++) {
 						SRT_REGION(EXTEND_GROUP);
@@ -797,6 +820,7 @@
 			}
 		}
 		const uint32_t n_free = 64u - n_act;
+		if (CAM) cam_phase = false;
 		if (!queue_dry && n_free >= (uint32_t)SRT_REFILL_MIN && (!SUSPEND || pk_count == 0u)) {
 			const unsigned long long freem = ~actm;
 			const uint32_t rank = lane_rank(freem);
@@ -850,6 +874,7 @@
 			}
 			const unsigned long long gotm = ballot64(rank < given) & freem; // every lane served holds a camera ray from here on
 			actm |= gotm;
+			if (CAM) cam_phase = n_act == 0u; // gotm covers actm: no lane holds an older ray
 			if (in_mask(gotm)) {
 				SRT_REGION(CAMERA);
 				// ---- camera ray (render.cl:488,496-516) ----
@@ -928,6 +953,7 @@
 			w[10] += w_pool_taken, w[11] += w_pool_given, w[12] += (unsigned long long)w_pool_taken * w_pool_taken, w[13] += w_pool_last_taken;
 #endif
 		}
+		if (CAM) w[5] += w_cam;
 		w[6] += w_iter;
 		w[7] += w_shade;
 #ifdef SRT_PHASE_CLOCK

@@ -679,7 +679,9 @@ class Tracer(_Denoise):
         self.lib.srt_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         self._check(self.lib.srt_debug_counters(self._h, out))
         v = [int(x) for x in out]
-        return {"rays": v[0], "sky": v[1], "paths": v[2], "orphans": v[5] & ((1 << 40) - 1), "evictions": v[5] >> 40,
+        return {"rays": v[0], "sky": v[1], "paths": v[2], "orphans": 0, "evictions": 0,  # (rounds 1-3; the scripts still print them)
+                # scene-class kernels: EXTEND phases of fresh camera rays only (they run the camera forms), and the rays in them
+                "camera_phases": v[5] >> 36, "camera_phase_rays": v[5] & ((1 << 36) - 1),
                 "iterations": v[6], "shade_phases": v[7], "waves_per_cu": v[8], "grid": v[9],
                 "phase_cycles": dict(zip(("extend", "ring", "shade", "park", "deliver", "refill", "head", "kernel"), v[10:18])),
                 # array-scan kernels without -DSRT_PHASE_CLOCK reuse the first two clock slots: big-model scans and the lanes in them
