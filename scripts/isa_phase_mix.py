@@ -2,13 +2,15 @@
 """Executed instruction mix of a trace-kernel instantiation, per region of the kernel.
 
   static mix   : the PRODUCT build's assembly (hipcc -S -gline-tables-only with build.py's flags; line tables do not
-                 change code generation), every instruction assigned to the SRT_REGION(...) stretch of csrc/kernels.hip
-                 it was written in (its .loc line; inlined helpers inherit the region of the code around them) and to a
-                 class (arith / int / cmp+cndmask / mov / lane / trans / fp64 / cvt / s_nop / salu / smem / lds / vmem / branch / wait).
+                 change code generation), every instruction assigned to the SRT_REGION(...) stretch it was written in
+                 (its .loc line: the kernel's body is csrc/trace_body.inc, the helpers are in csrc/kernels.hip and
+                 device_*.h; inlined helpers inherit the region of the code around them) and to a class
+                 (arith / int / cmp+cndmask / mov / lane / trans / fp64 / cvt / s_nop / salu / smem / lds / vmem / branch / wait).
   frequencies  : how often a wave ran each region, from a -DSRT_REGION_COUNT build on the GPU (scripts/region_probe.py).
   executed mix : static x frequency, summed per phase; checked against rocprofv3 PMC totals of the product build when given.
 
 usage:  isa_phase_mix.py static  [--kernel 'srt_trace_kernel<false, true, false, false>'] [--flags ...]        (CPU box)
+                 [--csrc OTHER/simple-raytracer_amd/csrc]   the same analysis of another checkout's sources, to compare two trees
         isa_phase_mix.py merge --freq gpurun_out/region_freq.json [--pmc profiles/xyz.json] --out profiles/r03_phase_mix.json
 """
 import argparse
@@ -21,7 +23,9 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "simple-raytracer_amd" / "csrc"
-SRC = CSRC / "kernels.hip"
+SRC = CSRC / "kernels.hip"  # the unit that is compiled
+BODY = "trace_body.inc"     # the trace kernel's body: its lines carry the regions
+HELPER_FILES = ["kernels.hip", "device_math.h", "device_intersect.h", "device_shading.h"]  # where the body's helpers are written
 BASE_FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fno-gpu-rdc", "--offload-arch=gfx950"]
 
 PHASE_OF = {  # region -> phase of DESIGN.md's split
@@ -145,37 +149,33 @@ def compile_code_object(flags, out):
         raise SystemExit("clang-offload-bundler failed:\n" + r.stderr)
 
 
-slot_calls = {}  # source line of a test_block(..., slot) call -> slot
+slot_calls = {}  # line of the body with a test_block(..., slot) call -> slot
 
 
 def source_tables():
-    """(markers [(line, region)], body (lo, hi) of the trace kernel, helper ranges [(lo, hi, name)], rare lines) of kernels.hip"""
-    lines = SRC.read_text().split("\n")
-    markers, rare = [], set()
+    """(markers [(file, line, region)], helper ranges [(file, lo, hi, name)], rare lines {(file, line)}) of the body and the helpers' files"""
+    markers, rare, helpers = [], set(), []
     slot_calls.clear()
-    for i, l in enumerate(lines, 1):
-        m = re.search(r"\bSRT_REGION\((\w+)\)", l) or re.search(r"\bSRT_REGION_SLOT\((\w+), slot\)", l)
-        if m and not l.lstrip().startswith(("#define", "//", "X(")) and "R_##" not in l:
-            markers.append((i, m.group(1) + ("_@" if "SRT_REGION_SLOT" in l else "")))
-        m = re.search(r"\btest_block\(.*, (\d)\);", l)
-        if m:
-            slot_calls[i] = int(m.group(1))
-        if "@rare" in l:
-            rare.add(i)
-    body_lo = next(i for i, l in enumerate(lines, 1) if "void srt_trace_kernel(const TraceParams p)" in l)
-    body_hi = next(i for i, l in enumerate(lines, 1) if i > body_lo and l.startswith("}"))
-    helpers = []
     fn = re.compile(r"^(?:template.*>\s*)?__device__ __forceinline__ [\w:<> ]+?[ &*](\w+)\(")
-    cur = None
-    for i, l in enumerate(lines, 1):
-        m = fn.match(l)
-        if m and i < body_lo:
-            if cur:
-                helpers.append((cur[0], i - 1, cur[1]))
-            cur = (i, m.group(1))
-    if cur:
-        helpers.append((cur[0], body_lo - 1, cur[1]))
-    return markers, (body_lo, body_hi), helpers, rare
+    for name in [BODY] + HELPER_FILES:
+        lines = (CSRC / name).read_text().split("\n")
+        cur = None
+        for i, l in enumerate(lines, 1):
+            m = re.search(r"\bSRT_REGION\((\w+)\)", l) or re.search(r"\bSRT_REGION_SLOT\((\w+), slot\)", l)
+            if m and not l.lstrip().startswith(("#define", "//", "X(")) and "R_##" not in l:
+                markers.append((name, i, m.group(1) + ("_@" if "SRT_REGION_SLOT" in l else "")))
+            m = re.search(r"\btest_block\(.*, (\d)\);", l)
+            if m and name == BODY:
+                slot_calls[i] = int(m.group(1))
+            if "@rare" in l:
+                rare.add((name, i))
+            m = fn.match(l) if name != BODY else None
+            if m:
+                cur = (i, m.group(1))
+            if cur and (l.startswith("}") or (m and l.split("//")[0].rstrip().endswith("}"))):  # the helper's closing brace (a one-liner's: on its first line, before any comment)
+                helpers.append((name, cur[0], i, cur[1]))
+                cur = None
+    return markers, helpers, rare
 
 
 def disassemble(code_object, kernel_demangled):
@@ -228,13 +228,13 @@ def inline_stacks(code_object, addrs):
 
 def static_mix(kernel, flags, cache="/tmp/srt_phase_mix.hsaco"):
     compile_code_object(flags, cache)
-    markers, (body_lo, body_hi), helpers, rare = source_tables()
+    markers, helpers, rare = source_tables()
     insts = disassemble(cache, kernel)
     stacks = inline_stacks(cache, [a[0] for a in insts])
 
-    def helper_of(line):
-        for lo, hi, name in helpers:
-            if lo <= line <= hi:
+    def helper_of(file, line):
+        for f, lo, hi, name in helpers:
+            if f == file and lo <= line <= hi:
                 return lo, hi, name
         return None
 
@@ -248,27 +248,27 @@ def static_mix(kernel, flags, cache="/tmp/srt_phase_mix.hsaco"):
             if base in FIXED_HELPERS and FIXED_HELPERS[base]:
                 region, depth = FIXED_HELPERS[base], d
                 continue
-            if file != "kernels.hip" or line == 0:
+            if (file != BODY and file not in HELPER_FILES) or line == 0:
                 continue
-            if line in slot_calls:
+            if file == BODY and line in slot_calls:
                 slot = slot_calls[line]
-            if line in rare:
+            if (file, line) in rare:
                 return "RARE", ()
-            if body_lo <= line <= body_hi:
+            if file == BODY:
                 if region is None:
                     region, depth = "PROLOGUE", d  # the kernel's lines before its first marker
-                for ml, name in markers:
-                    if body_lo <= ml <= line:
+                for mf, ml, name in markers:
+                    if mf == BODY and ml <= line:
                         region, depth = name, d
             else:
-                h = helper_of(line)
+                h = helper_of(file, line)
                 if h:
-                    for ml, name in markers:
-                        if h[0] <= ml <= line:
+                    for mf, ml, name in markers:
+                        if mf == file and h[0] <= ml <= line:
                             region, depth = name, d
         if not region:
             return None, ()
-        copy = tuple(line for fn, file, line in frames[:depth] if file == "kernels.hip" and body_lo <= line <= body_hi)
+        copy = tuple(line for fn, file, line in frames[:depth] if file == BODY)
         return region.replace("_@", f"_{slot}"), copy
 
     # ---- basic blocks: an instruction the compiler merged from several places carries no line; it takes the region of its
@@ -358,10 +358,15 @@ def main():
     ap.add_argument("--region", default="", help="dump: regions to list (prefix match), comma separated")
     ap.add_argument("--kernel", default="srt_trace_kernel<false, true, false, false>")
     ap.add_argument("--flags", default="")
+    ap.add_argument("--csrc", help="analyse this csrc directory instead of the checkout's own (helper files it does not have are skipped)")
     ap.add_argument("--freq")
     ap.add_argument("--pmc")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.csrc:
+        global CSRC, SRC
+        CSRC, SRC = Path(a.csrc).resolve(), Path(a.csrc).resolve() / "kernels.hip"
+    HELPER_FILES[:] = [f for f in HELPER_FILES if (CSRC / f).exists()]
     if a.freq:
         static_mix.freq = {k: v[0] for k, v in json.loads(Path(a.freq).read_text())["regions"].items()}
     st = static_mix(a.kernel, a.flags.split())

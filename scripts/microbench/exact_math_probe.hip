@@ -1,7 +1,7 @@
 // exact_math_probe.hip — which cheaper instruction sequences still give the IEEE result on gfx950?
 // Exhaustive (2^32 inputs) mismatch counts of candidate sqrt / division / cosine-sign sequences against the
 // compiler's correctly rounded ones, on exactly the domains the trace kernel feeds them. A candidate is used in
-// csrc/kernels.hip only when its count here is 0 (and srt_selftest_math then re-checks it inside the library).
+// csrc/device_math.h only when its count here is 0 (and srt_selftest_math then re-checks it inside the library).
 // Build + run on the GPU box:
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -I simple-raytracer_amd/csrc scripts/microbench/exact_math_probe.hip -o scripts/microbench/bin/exact_math_probe && scripts/microbench/bin/exact_math_probe
 #include <hip/hip_runtime.h>
@@ -117,7 +117,7 @@ __device__ __forceinline__ float cos_cur(float x, bool alt) {
 
 enum { SQ_S1, SQ_S2, SQ_S3, SQ_S4, SQ_S1_BM, SQ_S5_BM, SQ_S3_BM, SQ_S1_BM_ADMIT, SIGN_XOR, SIGN_XOR_NAN, LOG_D1, LOG_D2, LOG_D4, GEN_D2, GEN_FIX_BOX, GEN_FIX_WIDE, GEN_FIX1_WIDE, CAM_HOSTRCP, COS_ALT, SQ_S1_GLASS, N_OUT };
 
-// the built-in sign as the kernel's sign_fast computes it (kernels.hip)
+// the built-in sign as the kernel's sign_fast computes it (device_math.h)
 __device__ __forceinline__ float sign_fast(float x) {
 	const float one = dm_u2f((dm_f2u(x) & 0x80000000u) | 0x3f800000u);
 	const float zero_or_x = __builtin_amdgcn_class(x, 0x60) ? x : 0.0f;

@@ -1,5 +1,5 @@
 """Region frequencies of the trace kernel from a -DSRT_REGION_COUNT build (SRT_LIB=lib/variants/regions/libsrt_hip.so):
-per region of kernels.hip's SRT_REGION_LIST how often a wave ran it and with how many lanes, next to the launch's exact
+per region of trace_regions.h's SRT_REGION_LIST how often a wave ran it and with how many lanes, next to the launch's exact
 work counters. Input of scripts/isa_phase_mix.py merge. usage: region_probe.py <workload of sched_probe.py> [spp] > freq.json"""
 import json, re, sys
 from pathlib import Path
@@ -11,7 +11,7 @@ srt_pkg.load()
 from simple_raytracer_amd import records as R, scenes as S
 from simple_raytracer_amd.tracer import Tracer
 
-src = (ROOT / "simple-raytracer_amd/csrc/kernels.hip").read_text()
+src = (ROOT / "simple-raytracer_amd/csrc/trace_regions.h").read_text()
 lst = src[src.index("#define SRT_REGION_LIST(X)"):src.index("enum SrtRegion")]
 NAMES = re.findall(r"X\((\w+)\)", lst)
 WORK = {

@@ -4,7 +4,7 @@
 // Inputs, per pixel, accumulated since the last clear while the denoiser is on:
 //   normal_depth  {sum of front-facing first-hit normals, sum of hit distances} over the hits of the feature rays
 //   albedo_hits   {sum of hit material colours (sky: 1,1,1) over all feature rays, hits}   (kernels.hip srt_features_kernel)
-//   moments       sum over dispatches of (1/n) sum_k lum(radiance_k)^2                    (kernels.hip srt_reduce_kernel<true>)
+//   moments       sum over dispatches of (1/n) sum_k lum(radiance_k)^2                    (frame.hip srt_reduce_kernel<true>)
 // and the handle's counts T (dispatches), P (sum of num_samples), F (feature rays per pixel).
 //
 // Filter (tests/denoise_ref.py restates it in numpy):

@@ -1,4 +1,4 @@
-/* device_types.h — device-side scene representation shared by kernels.hip and the host side
+/* device_types.h — device-side scene representation shared by the kernel units (kernels.hip, frame.hip, selftest.hip) and the host side
  * (srt_abi.hip, scene_prep.cpp, bvh_host.cpp). No HIP header. Not part of the public ABI. */
 #ifndef SRT_DEVICE_TYPES_H
 #define SRT_DEVICE_TYPES_H
@@ -40,7 +40,7 @@ struct WinnerRec {
 	int32_t material;
 	float vx, vy, vz, w;
 	uint32_t first_wtri;
-	float inv_w; /* spheres: 1.0f / radius as the host rounds it (an IEEE quotient) when 2^-40 <= |radius| <= 2^40, else 0 (kernels.hip div3_by_rcp) */
+	float inv_w; /* spheres: 1.0f / radius as the host rounds it (an IEEE quotient) when 2^-40 <= |radius| <= 2^40, else 0 (device_math.h div3_by_rcp) */
 };
 static_assert(sizeof(WinnerRec) == 32, "WinnerRec 32 B");
 
@@ -101,7 +101,7 @@ typedef srt_bvh_node BvhNode; /* include/srt_types.h */
  * summed on the host when asked for: thousands of waves ending together on three shared atomics
  * cost a small dispatch 100 us (profiles/README.md). Launches of a handle are stream-ordered and a
  * launch has one wave per index, so a plain read-modify-write is enough. */
-#define SRT_REGION_MAX 56 /* kernels.hip SRT_REGION_LIST: regions of the trace kernel a -DSRT_REGION_COUNT build counts (waves, lanes) for */
+#define SRT_REGION_MAX 56 /* trace_regions.h SRT_REGION_LIST: regions of the trace kernel a -DSRT_REGION_COUNT build counts (waves, lanes) for */
 #ifdef SRT_REGION_COUNT
 #define SRT_WAVE_CTR_STRIDE (16 + 2 * SRT_REGION_MAX)
 #else
@@ -132,7 +132,7 @@ enum { SRT_CTR_RAYS = 0, SRT_CTR_SKY, SRT_CTR_TRI, SRT_CTR_TRI_PASS_U, SRT_CTR_N
 	X(4, SRT_GC_PPP, true)
 #define SRT_SCENE_CLASS_GENERAL 0
 /* A class kernel keeps, per sphere of its group, what a camera ray's test makes from the sphere and the camera's origin alone
- * (kernels.hip "CAMERA PHASES"): one float4 {L, c} per sphere slot of every sphere block of the header `code`, behind the hit
+ * (device_intersect.h "CAMERA PHASES"): one float4 {L, c} per sphere slot of every sphere block of the header `code`, behind the hit
  * queue in the wave's dynamic LDS. The launcher adds the bytes; 64 for the benchmark's layout, which stays inside the LDS
  * allocation 21 resident waves per CU leave each of them (7,536 -> 7,600 of 7,801 bytes). */
 static constexpr inline uint32_t srt_class_cam_records(uint32_t code) {
@@ -180,20 +180,20 @@ struct TraceParams {
 	 * recomputed (and kept in VGPRs / spilled masks) by every persistent wave */
 	float f_width, f_height, f_sky_w, f_sky_h; /* exact int -> float conversions */
 	int32_t sun_focus_int;                     /* dm_pow_small_int(sd.sun_focus): 1..32, or 0 = general pow */
-	int32_t material_flags;                    /* SRT_MF_*: what srt_update_scene found true of EVERY material of the scene (kernels.hip SHADE) */
+	int32_t material_flags;                    /* SRT_MF_*: what srt_update_scene found true of EVERY material of the scene (trace_body.inc SHADE) */
 	int32_t num_models;
 	int32_t rank, world, rows_per_block, owned_rows;
 	int32_t use_bvh;          /* model records carry a BVH root instead of a first world triangle */
 	const float *bvh_blocks;  /* all models' 128-byte blocks (wide hierarchy above) */
 	float *scan_queue;        /* array scan: SRT_POOL_CTL_WORDS words of pool control (zeroed before the launch), SRT_POOL_REC_FLOATS of pool records (only when pool_blocks != 0), then
 	                             SRT_SCAN_QUEUE_FLOATS per persistent wave (rays that wait for a big model's triangle scan, parked rays) */
-	/* camera-ray set-up without per-lane integer or IEEE divisions (kernels.hip CAMERA; srt_abi.hip fills them per launch) */
-	float inv_f_width, inv_f_height;  /* 1.0f / f_width, 1.0f / f_height, correctly rounded on the host (srt_div_by_rcp in kernels.hip) */
+	/* camera-ray set-up without per-lane integer or IEEE divisions (trace_body.inc CAMERA; srt_abi.hip fills them per launch) */
+	float inv_f_width, inv_f_height;  /* 1.0f / f_width, 1.0f / f_height, correctly rounded on the host (device_math.h div_by_rcp) */
 	uint32_t width_magic, width_shift; /* n / width = (mulhi(n, magic) + n) >> shift for n < 2^31 (srt_magic_u31) */
 	uint32_t rpb_magic, rpb_shift;     /* the same for rows_per_block */
 	uint32_t nbs_magic16;              /* n / batch_samples = (n * magic16) >> 16 for n < 256, when batch_samples < 128 (else unused) */
 	uint32_t pool_blocks;              /* array scan, end of a launch: the waves' leftover rays are pooled, in at most this many blocks of 64 per stack
-	                                      (kernels.hip; <= SRT_POOL_BLOCKS; 0 = no pool, every wave scans its own remainder) */
+	                                      (trace_body.inc REFILL_POOL; <= SRT_POOL_BLOCKS; 0 = no pool, every wave scans its own remainder) */
 	int32_t unit_materials;            /* the device materials hold bernoulli() thresholds in place of metallic / specular / transmittance */
 	int32_t all_materials_ok;          /* no shape with a negative material index: the closest shape is a hit without looking its material up (render.cl:404) */
 };

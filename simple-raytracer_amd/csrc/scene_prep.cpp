@@ -9,7 +9,7 @@
 #include <deque>
 #include <utility>
 
-// bernoulli() thresholds (kernels.hip): T(p) = how many of the generator's 2^32 outputs r give p > (float)r * 2^-32 -- a prefix,
+// bernoulli() thresholds (device_math.h): T(p) = how many of the generator's 2^32 outputs r give p > (float)r * 2^-32 -- a prefix,
 // the conversion is monotone. 0 for p <= 0 and NaN, 2^32 for p > 1; p = 1 gives 2^32 - 128 (the 128 largest r convert to 1.0).
 // THE one copy: srt_update_scene and srt_bernoulli_threshold_host both call it.
 uint64_t bernoulli_threshold(float pr) {
@@ -209,7 +209,7 @@ int prepare_scene(int accel_mode, int refit_mode, BvhCache *&cache, int scan_sus
 	// group headers: three blocks each (device_types.h BlockGroup); the data of a last, partial group is zero-filled
 	std::vector<BlockGroup> &groups = sp.groups;
 	groups.assign((runs.size() + 2) / 3, BlockGroup());
-	uint32_t n_big = 0; // big model number k waits in scan stack k & 1 (kernels.hip)
+	uint32_t n_big = 0; // big model number k waits in scan stack k & 1 (trace_body.inc)
 	for (size_t b = 0; b < runs.size(); b++) {
 		BlockGroup &g = groups[b / 3];
 		if (b % 3 == 0) memset(&g, 0, sizeof g);

@@ -557,7 +557,7 @@ static TraceParams trace_params_of(const srt_tracer *t, const srt_render_data *o
 	p.sky_h = t->sky_h;
 	p.f_width = (float)options->width;
 	p.f_height = (float)options->height;
-	p.inv_f_width = 1.0f / p.f_width; // IEEE quotients: the kernel's camera rays divide by multiplying with them (kernels.hip div_by_rcp)
+	p.inv_f_width = 1.0f / p.f_width; // IEEE quotients: the kernel's camera rays divide by multiplying with them (device_math.h div_by_rcp)
 	p.inv_f_height = 1.0f / p.f_height;
 	srt_magic_u31(options->width > 0 ? (uint32_t)options->width : 1u, &p.width_magic, &p.width_shift);
 	srt_magic_u31(t->rows_per_block > 0 ? (uint32_t)t->rows_per_block : 1u, &p.rpb_magic, &p.rpb_shift);
@@ -1166,7 +1166,7 @@ int srt_debug_counters(srt_tracer *t, uint64_t out[18]) {
 	return SRT_OK;
 }
 
-/* -DSRT_REGION_COUNT builds: per region of the trace kernel (kernels.hip SRT_REGION_LIST, in that order) how often a wave
+/* -DSRT_REGION_COUNT builds: per region of the trace kernel (trace_regions.h SRT_REGION_LIST, in that order) how often a wave
  * ran it and with how many lanes, summed over the waves since the last reset. *written = 0 in the product build. */
 int srt_debug_region_counters(srt_tracer *t, uint64_t *out, int capacity, int *written) {
 	if (!t || !out || !written || capacity < 0) return SRT_ERR_INVALID;

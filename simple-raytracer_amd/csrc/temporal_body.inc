@@ -65,7 +65,7 @@
 #else
 		if (p.mode == TP_PROJECT) {
 #endif
-			// the camera ray through the pixel's centre (kernels.hip CAMERA with 0.5 for the jitter; its division through the
+			// the camera ray through the pixel's centre (trace_body.inc CAMERA with 0.5 for the jitter; its division through the
 			// host's reciprocal is the IEEE quotient)
 			const float ndc_x = ((float)x + 0.5f) / p.f_width, ndc_y = ((float)y + 0.5f) / p.f_height;
 			const float sx = ((2.f * ndc_x - 1.f) * p.aspect) * p.fov;

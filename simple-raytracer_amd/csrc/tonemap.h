@@ -1,4 +1,4 @@
-// tonemap.h — the per-pixel device helpers the resolve and the denoiser share (kernels.hip, denoise.hip, temporal.hip):
+// tonemap.h — the per-pixel device helpers the resolve and the denoiser share (frame.hip, denoise.hip, temporal.hip):
 // srt_resolve_kernel's ACES fit and byte conversion, the tonemap as srt_denoise_setup_kernel and the passes write it,
 // luminance and the finite-colour test. One copy, so the denoiser's K = 0 bytes are the plain resolve's by construction.
 // Not part of the public ABI.

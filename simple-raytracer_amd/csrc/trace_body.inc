@@ -1,7 +1,8 @@
-// The body of the trace kernel: kernels.hip includes this text inside srt_trace_kernel (SC = GeneralScene) and inside
-// srt_trace_scene_kernel (SC = OneGroupScene<CODE, NO_SPEC>; COUNT_TRIS, HAS_MODELS, USE_BVH false and USE_LDS true there).
-// It is included, not called: the general kernels must compile to what they were before scene classes existed, and a body
-// that is inlined from a function does not (the inliner's alias scopes reorder the code). kernels.hip "SCENE CLASSES".
+// trace_body.inc -- the body of the trace kernel: kernels.hip includes this text inside srt_trace_kernel (SC = GeneralScene)
+// and inside srt_trace_scene_kernel (SC = OneGroupScene<CODE, NO_SPEC>; COUNT_TRIS, HAS_MODELS, USE_BVH false and USE_LDS true
+// there), after the tunables and helpers it uses (kernels.hip; device_math.h, device_intersect.h, device_shading.h). It is
+// included, not called: the general kernels must compile to what they were before scene classes existed, and a body that is
+// inlined from a function does not (the inliner's alias scopes reorder the code). kernels.hip "SCENE CLASSES".
 	extern __shared__ float4 lds[]; // [2*n_shapes] winner records, [4*n_materials] materials, (sphere / plane scenes: group headers, shape blocks,) sky ring, hit queue
 	constexpr bool FAST = SC::FAST;
 	static_assert(!FAST || (USE_LDS && !HAS_MODELS && !USE_BVH && !COUNT_TRIS), "scene classes exist for sphere / plane scenes staged in LDS");
@@ -77,12 +78,11 @@
 	float *__restrict__ ring = reinterpret_cast<float *>(lds + p.stage_off); // [10][64] escaped paths awaiting their sky lookup
 	float *__restrict__ hq = ring + 10u * (uint32_t)SRT_RING_CAP; // [hq_fields][HQ] paths that hit, awaiting their bounce (FIFO)
 	constexpr uint32_t HQ = USE_BVH ? SRT_HQ_CAP_BVH : HAS_MODELS ? SRT_HQ_CAP_MODELS : SRT_HQ_CAP;
-	// Scene classes: what a camera ray's tests make from a shape and the camera's origin alone, once per wave (kernels.hip
+	// Scene classes: what a camera ray's tests make from a shape and the camera's origin alone, once per wave (device_intersect.h
 	// "CAMERA PHASES"): the spheres' records {L, c} behind the hit queue, a plane's num in the staged block itself.
-	constexpr bool CAM = FAST && SRT_CAM_FORM != 0;
 	constexpr uint32_t CS1 = srt_class_cam_records(FK0), CS2 = srt_class_cam_records(FK0 | (FK1 << 8)); // first record of block 1 / 2
 	float4 *__restrict__ cam_rec = reinterpret_cast<float4 *>(hq + hq_fields(HAS_MODELS) * HQ);
-	if (CAM) {
+	if (FAST) {
 		const auto &c = SRT_COLD(p);
 		const f3 cam_org = mk(c.rd.camera_to_world[3].x, c.rd.camera_to_world[3].y, c.rd.camera_to_world[3].z); // as CAMERA loads it
 		cam_records_of_block<FK0>(lds + 2 * FN, cam_rec, cam_org, lane);
@@ -188,9 +188,6 @@
 						f3 inv = mk(0.f, 0.f, 0.f);
 						if (HAS_MODELS) inv = mk(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
 
-					// Blocks of same-type shapes in array order; header and data of the NEXT block are fetched (scalar
-					// loads, one allocated past the end) before this one is tested, so only the first block's load
-					// latency is exposed per segment.
 					// Groups of three 64-byte blocks of same-type shapes, in array order (device_types.h). The header and
 					// the three blocks of a group are fetched with four scalar loads issued together: one scalar-memory
 					// round trip per group (a 7-shape scene is one group). The mesh kernels, whose triangle loops need
@@ -287,7 +284,7 @@
 							b.v[8] = q2.x, b.v[9] = q2.y, b.v[10] = q2.z, b.v[11] = q2.w, b.v[12] = q3.x, b.v[13] = q3.y, b.v[14] = q3.z, b.v[15] = q3.w;
 							return b;
 						};
-						if (CAM && cam_phase) {
+						if (cam_phase) {
 							// (wave-uniform) fresh camera rays only: the same tests in the same order from the prologue's numbers
 							w_cam += (1ull << 36) + popc64(actm);
 							test_block_of_class_cam<FK0>(lb, cam_rec, 0, dir, actm, tmin, best);
@@ -820,7 +817,7 @@
 			}
 		}
 		const uint32_t n_free = 64u - n_act;
-		if (CAM) cam_phase = false;
+		if (FAST) cam_phase = false;
 		if (!queue_dry && n_free >= (uint32_t)SRT_REFILL_MIN && (!SUSPEND || pk_count == 0u)) {
 			const unsigned long long freem = ~actm;
 			const uint32_t rank = lane_rank(freem);
@@ -874,7 +871,7 @@
 			}
 			const unsigned long long gotm = ballot64(rank < given) & freem; // every lane served holds a camera ray from here on
 			actm |= gotm;
-			if (CAM) cam_phase = n_act == 0u; // gotm covers actm: no lane holds an older ray
+			if (FAST) cam_phase = n_act == 0u; // gotm covers actm: no lane holds an older ray
 			if (in_mask(gotm)) {
 				SRT_REGION(CAMERA);
 				// ---- camera ray (render.cl:488,496-516) ----
@@ -953,7 +950,7 @@
 			w[10] += w_pool_taken, w[11] += w_pool_given, w[12] += (unsigned long long)w_pool_taken * w_pool_taken, w[13] += w_pool_last_taken;
 #endif
 		}
-		if (CAM) w[5] += w_cam;
+		if (FAST) w[5] += w_cam;
 		w[6] += w_iter;
 		w[7] += w_shade;
 #ifdef SRT_PHASE_CLOCK

@@ -129,7 +129,7 @@ def stats_render(o, case, sky, time_seed):
 
 
 def big_models_between_shapes(seed):
-    """Big models (>= 128 triangles: the array scan suspends the rays that enter their boxes, csrc/kernels.hip) with
+    """Big models (>= 128 triangles: the array scan suspends the rays that enter their boxes, csrc/trace_body.inc) with
     spheres, planes, boxes and a second instance of the same mesh BEHIND them in the shape array, overlapping boxes,
     glass and mirror materials: a suspended ray has to come back with its closest hit so far and see every later shape."""
     rng = np.random.RandomState(seed)

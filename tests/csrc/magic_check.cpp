@@ -48,7 +48,7 @@ int main() {
 				return 1;
 			}
 	}
-	// n / nbs = (n * ceil(2^16 / nbs)) >> 16 for n < 256 and nbs < 128 (kernels.hip CAMERA)
+	// n / nbs = (n * ceil(2^16 / nbs)) >> 16 for n < 256 and nbs < 128 (trace_body.inc CAMERA)
 	for (uint32_t nbs = 1; nbs < 128; nbs++) {
 		const uint32_t m16 = (65536u + nbs - 1u) / nbs;
 		for (uint32_t n = 0; n < 256; n++)

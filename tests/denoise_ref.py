@@ -24,7 +24,7 @@ def lum(c):
 
 
 def moments(radiance, acc=None):
-    """One dispatch of the moments reduction (kernels.hip srt_reduce_kernel<true>) in float32: radiance (pixels, n, 3) of the
+    """One dispatch of the moments reduction (frame.hip srt_reduce_kernel<true>) in float32: radiance (pixels, n, 3) of the
     dispatch's n samples, s2 = s2 + lum(r_k)^2 in sample order, then acc + s2 / n -> (pixels,)."""
     r = np.asarray(radiance, F32)
     s2 = np.zeros(r.shape[0], F32)

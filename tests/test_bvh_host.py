@@ -130,7 +130,7 @@ def check_wide(wide, nodes, order, n_tris):
 
 
 def walk(wide, rec_of_slot, org, d):
-    """The device's walk (csrc/kernels.hip walk_bvh) with tmin = inf, in float32; returns the tested records, the
+    """The device's walk (csrc/device_intersect.h walk_bvh) with tmin = inf, in float32; returns the tested records, the
     blocks fetched and the deepest the stack got (waiting children, as the host's bound counts them)."""
     f = np.float32
     org, d = org.astype(f), d.astype(f)

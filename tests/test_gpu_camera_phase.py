@@ -1,4 +1,4 @@
-"""GPU (MI355X): the camera phases of the scene-class trace kernels (kernels.hip "CAMERA PHASES"). An EXTEND phase whose rays
+"""GPU (MI355X): the camera phases of the scene-class trace kernels (device_intersect.h "CAMERA PHASES"). An EXTEND phase whose rays
 are all fresh camera rays starts from numbers the wave made once from the shapes and the camera's origin, and skips, by wave
 vote, spheres and planes that no ray of the phase can hit. None of it may change a bit: every case compares the canvas and the
 path / ray / sky / NaN counters with the CPU oracle, asserts WHICH kernel ran (Tracer.last_trace_class) and asserts that camera

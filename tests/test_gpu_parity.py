@@ -79,7 +79,7 @@ def test_mesh_scene_968_triangles_vs_oracle(T, sky, oracle):
 
 
 def test_scan_pool_sizes_are_invisible(T, sky, oracle, monkeypatch):
-    """Array scan: at the end of a launch the waves pool the rays left in their scan stacks (kernels.hip). Whatever the pool
+    """Array scan: at the end of a launch the waves pool the rays left in their scan stacks (trace_body.inc REFILL_POOL). Whatever the pool
     holds -- nothing at all, one block of 64 rays (it overflows at once: the waves keep what does not fit), seven blocks, the
     full size -- and however many launches (sample batches) there are, the canvas is the oracle's bit for bit."""
     shapes, tris, mats = S.mesh_scene(2)

@@ -1,4 +1,4 @@
-"""numpy restatement of the albedo-texture contract (include/srt_abi.h "albedo textures"; csrc/kernels.hip sample_texture,
+"""numpy restatement of the albedo-texture contract (include/srt_abi.h "albedo textures"; csrc/device_shading.h sample_texture,
 texture_albedo): the UV per kind of shape and both filters, in float32, unfused, in the kernel's order. dm_atan2pif and
 dm_bilinear come from a host build of csrc/detmath.h (tests/csrc/texture_math.c). A plain module, not a test module."""
 import ctypes as C
