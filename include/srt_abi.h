@@ -144,8 +144,44 @@ int srt_set_acceleration_refit(srt_tracer *t, int mode);
  * whoever refitted them. */
 int srt_acceleration_refit_info(const srt_tracer *t, uint64_t out[4]);
 /* With srt_set_kernel_timers on: the device time of the last srt_update_scene's refit launches, first to last, in
- * milliseconds (0 when it enqueued none or the timers were off). Blocking. */
+ * milliseconds (0 when it enqueued none or the timers were off); under SRT_DEFORM_REFIT (below) the cost launch with its
+ * small copies is inside the span. Blocking. */
 int srt_last_refit_kernel_ms(srt_tracer *t, float *ms);
+/* What becomes of a model whose VERTICES changed between two srt_update_scene calls (a skinned character, a cloth step, a morph
+ * target, a sculpt stroke). SRT_DEFORM_REBUILD, the default: its hierarchy is built anew, as ever. SRT_DEFORM_REFIT: a model
+ * that finds no hierarchy of byte-identical triangles takes an unclaimed one of the previous call with its triangle_index and
+ * num_triangles -- after every model of the call has claimed its byte-identical one -- and keeps that tree: the topology and
+ * the records' order stay, every box is recomputed around the new triangles, by SRT_REFIT_HOST or SRT_REFIT_DEVICE exactly as
+ * for a model that moved (the transform may change in the same call). Another count or another range still builds. Nothing
+ * checks that the mesh's connectivity is what it was: the canvas does not depend on the tree's shape (closest hit, first in
+ * array order among equals), only the trace time does. To bound that, every refit under this mode measures the tree:
+ *   cost = (sum over inner blocks H(box) * children + sum over leaf blocks H(box) * triangles) / H(root box),
+ *   H(b) = dx * dy + dy * dz + dz * dx in double, extents as (double)hi - (double)lo of the padded float boxes
+ * -- on the device one more launch behind the refit, summed per wave and read back asynchronously; on the host under
+ * SRT_REFIT_HOST. ratio = cost now / cost of the tree as built; unknown (reported as 0, never a reason to rebuild) when a root
+ * has H == 0 or a term is not finite. rebuild_ratio: 0 = never rebuild on cost; a finite value > 1 = a model whose vertices
+ * changed and whose last known ratio is above it is built anew instead (its ratio is 1 again). SRT_ERR_INVALID for another
+ * mode or ratio. Takes effect at the next srt_update_scene; accepted and without effect under SRT_ACCEL_NONE. */
+#define SRT_DEFORM_REBUILD 0
+#define SRT_DEFORM_REFIT 1
+int srt_set_acceleration_deform(srt_tracer *t, int mode, float rebuild_ratio);
+/* Of the last srt_update_scene: out = {models whose hierarchy was kept across a change of triangle bytes (they count in
+ * srt_acceleration_info's out[6], refitted, not in out[4], built), models built anew because their ratio was above
+ * rebuild_ratio (they count in out[4]), cost launches enqueued, 0}; *worst_ratio = the largest known cost ratio among the
+ * scene's models, 0 when none is known (always under SRT_DEFORM_REBUILD). Waits for the last update's cost read-back, not for
+ * the stream. */
+int srt_acceleration_deform_info(srt_tracer *t, uint64_t out[4], double *worst_ratio);
+/* Host-only: srt_bvh_refit_wide_host for a model whose triangles changed too. The wide hierarchy of `built` over
+ * built_triangles, refitted in place around `now` over now_triangles (both arrays of n_triangles entries; `now` must have
+ * `built`'s triangle_index and num_triangles, its transform may differ). With now_triangles == built_triangles these are
+ * srt_bvh_refit_wide_host's bytes. What SRT_DEFORM_REFIT with SRT_REFIT_DEVICE leaves on the device, bit for bit. */
+int srt_bvh_refit_deformed_wide_host(const srt_shape *built, const srt_triangle *built_triangles, const srt_shape *now,
+                                     const srt_triangle *now_triangles, size_t n_triangles, int force_balanced, uint32_t *blocks_out,
+                                     size_t blocks_cap, size_t *n_blocks, uint32_t *root);
+/* Host-only: the cost (above) of that hierarchy as built and as refitted in place; 0 = unknown (also: a model without
+ * triangles). The device's sum takes its terms in another order: it agrees within n_blocks * 2^-53 relative. */
+int srt_bvh_wide_cost_host(const srt_shape *built, const srt_triangle *built_triangles, const srt_shape *now,
+                           const srt_triangle *now_triangles, size_t n_triangles, int force_balanced, double *cost_built, double *cost_now);
 /* Tests / inspection: the device's block array as the kernel walks it -- every model's blocks, absolute indices, leaf
  * blocks with their triangles. Blocking. Writes at most blocks_cap blocks of 32 dwords and always sets *n_blocks (0 without
  * SRT_ACCEL_BVH or without models); blocks_out may be NULL to only query. */
@@ -309,6 +345,7 @@ int srt_group_set_triangle_uvs(srt_group *g, const float *uv, size_t n_triangles
 int srt_group_set_triangle_materials(srt_group *g, const int32_t *materials, size_t n_triangles); /* per-triangle materials (below) */
 int srt_group_set_acceleration(srt_group *g, int mode);
 int srt_group_set_acceleration_refit(srt_group *g, int mode); /* srt_set_acceleration_refit on every member */
+int srt_group_set_acceleration_deform(srt_group *g, int mode, float rebuild_ratio); /* srt_set_acceleration_deform on every member */
 int srt_group_update_scene(srt_group *g, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
                            const srt_material *materials, size_t n_materials, const srt_scene_data *scene);
 int srt_group_clear_canvas(srt_group *g);

@@ -360,6 +360,23 @@ void BvhBuilder::fold_wide(const std::vector<BvhNode> &c, uint32_t records, bool
 	w.sched.clear(), w.level_off.clear();
 }
 
+double BvhBuilder::wide_cost(const std::vector<BvhNode> &c, const Wide &w) {
+	if (c.empty() || w.root == SRT_BVH_NONE) return 0.0;
+	const double root_h = half_area_d(c[0].lo, c[0].hi);
+	double sum = 0.0;
+	if (c[0].leaf) sum = root_h * (double)(c[0].leaf >> 28);
+	for (const Wide::Job &j : w.jobs) {
+		float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+		for (uint32_t k = 0; k < j.nk; k++) {
+			const BvhNode &kid = c[j.kids[k]];
+			for (int a = 0; a < 3; a++) lo[a] = std::min(lo[a], kid.lo[a]), hi[a] = std::max(hi[a], kid.hi[a]);
+			if (kid.leaf) sum += half_area_d(kid.lo, kid.hi) * (double)(kid.leaf >> 28);
+		}
+		sum += half_area_d(lo, hi) * (double)j.nk;
+	}
+	return cost_of(sum, root_h);
+}
+
 void BvhBuilder::Wide::ensure_schedule() {
 	if (!level_off.empty() || jobs.empty()) return;
 	std::vector<uint32_t> height(blocks.size() / 32, 0u); // leaf blocks: 0
@@ -407,6 +424,7 @@ void BvhCacheEntry::build(const srt_model &m, const srt_triangle *all) {
 		BvhBuilder::fold_wide(nodes, m.num_triangles, balanced, wide);
 		if (wide.need <= SRT_BVH_STACK_CAP) break; // a balanced tree of < 2^28 triangles needs at most 3 * 15
 	}
+	cost_built = cost_now = BvhBuilder::wide_cost(nodes, wide);
 }
 void BvhCacheEntry::refit(const srt_model &m, const srt_triangle *all) {
 	stale = false;
@@ -414,12 +432,14 @@ void BvhCacheEntry::refit(const srt_model &m, const srt_triangle *all) {
 	bb.refit(m, all);
 	BvhBuilder::fold_wide(nodes, m.num_triangles, balanced, wide);
 	if (wide.need > SRT_BVH_STACK_CAP) build(m, all); // the new boxes fold differently: start over
+	else cost_now = 0.0;                               // (unknown until somebody asks: scene_prep.cpp under SRT_DEFORM_REFIT)
 }
 void BvhCacheEntry::refit_in_place(const srt_model &m, const srt_triangle *all) {
 	stale = false;
 	BvhBuilder bb(nodes, order);
 	bb.refit(m, all);
 	for (const BvhBuilder::Wide::Job &j : wide.jobs) quantise(nodes, j.kids, j.nk, j.tags, j.first, wide.blocks.data() + 32 * (size_t)j.self);
+	cost_now = BvhBuilder::wide_cost(nodes, wide);
 }
 
 // 64-bit FNV-1a over 8-byte words (records are 96 B)
@@ -509,6 +529,52 @@ int srt_bvh_refit_wide_host(const srt_shape *built, const srt_shape *moved, cons
 		*n_blocks = ent.wide.blocks.size() / 32;
 		if (root) *root = ent.wide.root;
 		if (blocks_out) memcpy(blocks_out, ent.wide.blocks.data(), std::min(ent.wide.blocks.size(), blocks_cap * 32) * sizeof(uint32_t));
+	} catch (...) { // std::bad_alloc: no C++ exception may cross the C ABI
+		return SRT_ERR_INVALID;
+	}
+	return SRT_OK;
+}
+
+// the checks the two calls below share; `m`, `mv`: the two models
+static bool deformed_args_ok(const srt_shape *built, const srt_triangle *built_triangles, const srt_shape *now, const srt_triangle *now_triangles, size_t n_triangles) {
+	if (!built || !now || built->type != SRT_SHAPE_MODEL || now->type != SRT_SHAPE_MODEL || (n_triangles && (!built_triangles || !now_triangles))) return false;
+	const srt_model &m = built->shape.model, &mv = now->shape.model;
+	if ((uint64_t)m.triangle_index + m.num_triangles > n_triangles || m.num_triangles > 0x0fffffffu) return false;
+	return mv.triangle_index == m.triangle_index && mv.num_triangles == m.num_triangles; // the transform and the triangles' bytes may differ
+}
+
+int srt_bvh_refit_deformed_wide_host(const srt_shape *built, const srt_triangle *built_triangles, const srt_shape *now, const srt_triangle *now_triangles,
+                                     size_t n_triangles, int force_balanced, uint32_t *blocks_out, size_t blocks_cap, size_t *n_blocks, uint32_t *root) {
+	if (!n_blocks || !deformed_args_ok(built, built_triangles, now, now_triangles, n_triangles)) return SRT_ERR_INVALID;
+	const srt_model &m = built->shape.model;
+	try {
+		BvhCacheEntry ent;
+		ent.balanced = force_balanced != 0;
+		if (m.num_triangles > 0) {
+			ent.build(m, built_triangles);
+			ent.refit_in_place(now->shape.model, now_triangles);
+		}
+		*n_blocks = ent.wide.blocks.size() / 32;
+		if (root) *root = ent.wide.root;
+		if (blocks_out) memcpy(blocks_out, ent.wide.blocks.data(), std::min(ent.wide.blocks.size(), blocks_cap * 32) * sizeof(uint32_t));
+	} catch (...) { // std::bad_alloc: no C++ exception may cross the C ABI
+		return SRT_ERR_INVALID;
+	}
+	return SRT_OK;
+}
+
+int srt_bvh_wide_cost_host(const srt_shape *built, const srt_triangle *built_triangles, const srt_shape *now, const srt_triangle *now_triangles,
+                           size_t n_triangles, int force_balanced, double *cost_built, double *cost_now) {
+	if (!cost_built || !cost_now || !deformed_args_ok(built, built_triangles, now, now_triangles, n_triangles)) return SRT_ERR_INVALID;
+	const srt_model &m = built->shape.model;
+	try {
+		BvhCacheEntry ent;
+		ent.balanced = force_balanced != 0;
+		if (m.num_triangles > 0) {
+			ent.build(m, built_triangles);
+			ent.refit_in_place(now->shape.model, now_triangles);
+		}
+		*cost_built = ent.cost_built, *cost_now = ent.cost_now;
 	} catch (...) { // std::bad_alloc: no C++ exception may cross the C ABI
 		return SRT_ERR_INVALID;
 	}

@@ -34,6 +34,12 @@ struct BvhBuilder {
 		const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
 		return dx * dy + dy * dz + dz * dx;
 	}
+	// the same in double, the extents taken as (double)hi - (double)lo: the measure of the hierarchy's cost (wide_cost below, and
+	// srt_refit_cost_kernel in bvh_refit.hip, which evaluates these operations in this order)
+	static double half_area_d(const float lo[3], const float hi[3]) {
+		const double dx = (double)hi[0] - (double)lo[0], dy = (double)hi[1] - (double)lo[1], dz = (double)hi[2] - (double)lo[2];
+		return dx * dy + dy * dz + dz * dx;
+	}
 
 	void load(const srt_model &m, const srt_triangle *all);
 	struct Stats {
@@ -71,6 +77,17 @@ struct BvhBuilder {
 	};
 	static uint32_t fold_node(const std::vector<BvhNode> &c, uint32_t ci, uint32_t self, bool balanced, Wide &w, uint32_t &need);
 	static void fold_wide(const std::vector<BvhNode> &c, uint32_t records, bool balanced, Wide &w);
+	// The surface-area cost of the wide hierarchy `w` folded over `c`, with c's boxes as they are now:
+	//   (sum over inner blocks H(box) * children + sum over leaf blocks H(box) * triangles) / H(root box)
+	// A block's box is the union of its children's (an inner block) or its binary leaf node's (a leaf block). 0 = unknown: no
+	// hierarchy, a root with H == 0, or a term that is not finite (cost_of).
+	static double wide_cost(const std::vector<BvhNode> &c, const Wide &w);
+	static double cost_of(double sum, double root_h) { // the quotient, or 0 where it says nothing
+		const double q = sum / root_h;
+		return root_h > 0.0 && q > 0.0 && q <= 1.7976931348623157e308 ? q : 0.0;
+	}
+	// cost_now / cost_built; 0 = unknown (either cost is)
+	static double cost_ratio(double cost_now, double cost_built) { return cost_now > 0.0 && cost_built > 0.0 ? cost_of(cost_now, cost_built) : 0.0; }
 
 	uint32_t run(const srt_model &m, const srt_triangle *all, uint32_t first_record);
 };
@@ -81,6 +98,7 @@ struct BvhBuilder {
 // the build again (10^5 triangles: 37 ms -> 1.5 ms for the comparison).
 struct BvhCacheEntry {
 	uint32_t count = 0;
+	uint32_t triangle_index = 0; // of the model it was last used for (SRT_DEFORM_REFIT: the same range with other bytes keeps the entry)
 	uint64_t tri_hash = 0; // of the triangle bytes: looked at before any memcmp
 	bool claimed = false;  // taken by a model of the srt_update_scene in progress
 	srt_float4 transform[4];
@@ -90,6 +108,9 @@ struct BvhCacheEntry {
 	BvhBuilder::Wide wide; // what the device walks, block indices relative to the model's first block
 	bool balanced = false; // built without the SAH because the SAH tree could overflow a lane's stack
 	uint32_t leaves = 0, depth = 0;
+	// BvhBuilder::wide_cost of the hierarchy as build() left it, and of its boxes as they were last known (the host's refits
+	// store it; for a stale entry the device's cost kernel reports it, srt_abi.hip); 0 = unknown
+	double cost_built = 0.0, cost_now = 0.0;
 	void build(const srt_model &m, const srt_triangle *all);
 	void refit(const srt_model &m, const srt_triangle *all);
 	// New boxes for the wide hierarchy AS IT IS FOLDED: the binary boxes as refit() makes them, then every inner block

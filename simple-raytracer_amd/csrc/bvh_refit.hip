@@ -12,6 +12,7 @@
 // written in the host's operation order and compiled, like the host's, with -ffp-contract=off; float division and the double
 // square root are the correctly rounded ones. The kernels are launch- and latency-bound (10^5 triangles: 22k inner blocks,
 // a dozen levels); nothing here waits for another workgroup: the order is the stream's.
+// Behind pass C, under SRT_DEFORM_REFIT only, one more launch measures the refitted hierarchy: srt_refit_cost_kernel, below.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -225,6 +226,43 @@ __global__ __launch_bounds__(256) void srt_refit_level_kernel(const RefitParams 
 		b[a] = f2u(origin), b[4 + a] = wlo, b[7 + a] = whi;
 	}
 	b[3] = expo[0] | (expo[1] << 8) | (expo[2] << 16) | (nk << 24);
+}
+
+// ---- the cost of the refitted hierarchy (include/srt_abi.h SRT_DEFORM_REFIT) ----------------------------------------------------
+// BvhBuilder::half_area_d (bvh_host.h), operation for operation: -ffp-contract=off keeps the products and sums apart
+static __device__ __forceinline__ double half_area_d(const float *box) {
+	const double dx = (double)box[3] - (double)box[0], dy = (double)box[4] - (double)box[1], dz = (double)box[5] - (double)box[2];
+	return dx * dy + dy * dz + dz * dx;
+}
+
+// blockIdx.y = refitted model, a grid-stride loop over its blocks: after pass C `boxes` holds every one's padded box, `weights`
+// what the box counts for (an inner block's children, a leaf block's triangles). Every term is what BvhBuilder::wide_cost forms
+// on the host; the order of the sum is not (lanes, waves, atomics), which a sum of non-negative doubles forgives to one
+// rounding per term. One wave: a butterfly over its 64 lanes, one atomic add. The root is the model's first block; whoever
+// meets it stores its H beside the sum. Nothing is read outside [first_block, first_block + num_blocks).
+__global__ __launch_bounds__(256) void srt_refit_cost_kernel(const float *__restrict__ boxes, const uint8_t *__restrict__ weights, const RefitCostRange *__restrict__ ranges, double *sums) {
+	const RefitCostRange r = ranges[blockIdx.y];
+	double sum = 0.0;
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < r.num_blocks; i += gridDim.x * blockDim.x) {
+		const size_t b = (size_t)r.first_block + i;
+		const double h = half_area_d(boxes + 6u * b);
+		sum += h * (double)weights[b];
+		if (i == 0u) sums[2u * blockIdx.y + 1u] = h;
+	}
+	for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+	if ((threadIdx.x & 63u) == 0u && sum != 0.0) atomicAdd(sums + 2u * blockIdx.y, sum); // (NaN != 0: a non-finite term arrives)
+}
+
+int srt_launch_refit_cost(const float *boxes, const uint8_t *weights, const RefitCostRange *ranges, double *sums, uint32_t num_models, uint32_t max_blocks, void *stream) {
+	int launches = 0;
+	const uint32_t want = max_blocks ? (max_blocks + 255u) / 256u : 1u;
+	const uint32_t gx = want > 64u ? 64u : want; // (64 workgroups of 256 stride over the largest models: 256 atomics per model at the most)
+	for (uint32_t base = 0; base < num_models; base += 65535u) {
+		const uint32_t cnt = num_models - base > 65535u ? 65535u : num_models - base;
+		hipLaunchKernelGGL(srt_refit_cost_kernel, dim3(gx, cnt), dim3(256), 0, (hipStream_t)stream, boxes, weights, ranges + base, sums + 2u * (size_t)base);
+		launches++;
+	}
+	return launches;
 }
 
 // blockIdx.y = model: slabs of 65535

@@ -327,6 +327,9 @@ struct RefitModel {
 	uint32_t num_records;
 	uint32_t _pad;
 };
+struct RefitCostRange { /* a refitted model's blocks, for srt_refit_cost_kernel */
+	uint32_t first_block, num_blocks;
+};
 struct RefitParams {
 	const srt_shape *shapes;
 	const srt_triangle *triangles;
@@ -344,6 +347,10 @@ int srt_launch_refit_extents(const RefitParams &p, uint32_t num_models, uint32_t
 int srt_launch_refit_leaves(const RefitParams &p, uint32_t num_models, uint32_t max_records, void *stream);
 /* pass C for one level: the inner blocks sched[first .. first + count), whose children are all of lower levels */
 int srt_launch_refit_level(const RefitParams &p, uint32_t first, uint32_t count, void *stream);
+/* Behind pass C (include/srt_abi.h SRT_DEFORM_REFIT): sums[2 * k] += the sum over the blocks b of ranges[k] of H(boxes[b]) * weights[b]
+ * in double (H: the box's half area), sums[2 * k + 1] = H of the model's root box (its first block's). `sums` starts zeroed; the
+ * host divides. Returns the launches enqueued. */
+int srt_launch_refit_cost(const float *boxes, const uint8_t *weights, const RefitCostRange *ranges, double *sums, uint32_t num_models, uint32_t max_blocks, void *stream);
 void srt_launch_resolve(const ResolveParams &p, void *stream);
 void srt_launch_selftest(unsigned long long *out16, uint32_t stride, void *stream);
 void srt_launch_selftest_rare(int what, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, unsigned long long *mismatches, void *stream);

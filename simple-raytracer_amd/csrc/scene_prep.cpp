@@ -25,7 +25,7 @@ uint64_t bernoulli_threshold(float pr) {
 
 // host pass; `cache` is made when a BVH scene first needs it and emptied by an array-scan scene; an error return leaves its text
 // in `err` and every cached hierarchy in place
-int prepare_scene(int accel_mode, int refit_mode, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
+int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
                   const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
 	auto fail = [&err](int code, const char *msg) {
 		err = msg;
@@ -60,6 +60,62 @@ int prepare_scene(int accel_mode, int refit_mode, BvhCache *&cache, int scan_sus
 		for (BvhCacheEntry &e : cache->entries) e.claimed = false;
 	if (!use_bvh && cache) cache->entries.clear();
 	const auto build_t0 = std::chrono::steady_clock::now();
+	// hash of a model's triangle range, once per distinct range per call (instances share ranges)
+	auto range_hash = [&](const srt_model &m) {
+		for (const auto &rh : range_hashes)
+			if (rh.first == (((uint64_t)m.triangle_index << 32) | m.num_triangles)) return rh.second;
+		const uint64_t th = hash_triangles(triangles + m.triangle_index, m.num_triangles);
+		range_hashes.emplace_back(((uint64_t)m.triangle_index << 32) | m.num_triangles, th);
+		return th;
+	};
+	// An unclaimed entry of the previous call with the same triangles: one with the model's transform if there is one. Hash and
+	// transform are compared before any memcmp.
+	auto find_same_triangles = [&](const srt_model &m, uint64_t th) {
+		BvhCacheEntry *kept = nullptr;
+		for (BvhCacheEntry &e : cache->entries) {
+			if (e.claimed || e.count != m.num_triangles || e.tri_hash != th) continue;
+			const bool exact = e.same_transform(m);
+			if (!exact && kept) continue; // already holding a refit candidate: only an exact match improves on it
+			if (!e.same_triangles(m, triangles, th)) continue;
+			kept = &e;
+			if (exact) break;
+		}
+		return kept;
+	};
+	// SRT_DEFORM_REFIT: every model's entry is chosen before the shape loop. First the models that find their own triangle bytes,
+	// in array order, exactly as the loop would choose; then, among the entries nobody claimed, the models whose bytes changed
+	// take one of the same triangle range (index and count) -- so a deformed model never takes what a later one matches byte
+	// for byte. (Models the loop is going to refuse are left out here.)
+	const bool deform_on = use_bvh && deform.mode == SRT_DEFORM_REFIT;
+	struct Match {
+		BvhCacheEntry *ent = nullptr;
+		bool deformed = false;
+	};
+	std::vector<Match> matched;
+	uint64_t deform_kept = 0, deform_rebuilt = 0;
+	if (deform_on) {
+		matched.assign(n_shapes, Match());
+		auto wants_entry = [&](size_t i) {
+			const srt_model &m = shapes[i].shape.model;
+			return shapes[i].type == SRT_SHAPE_MODEL && m.num_triangles > 0 && (uint64_t)m.triangle_index + m.num_triangles <= n_triangles;
+		};
+		for (size_t i = 0; i < n_shapes; i++) {
+			if (!wants_entry(i)) continue;
+			const srt_model &m = shapes[i].shape.model;
+			if ((matched[i].ent = find_same_triangles(m, range_hash(m)))) matched[i].ent->claimed = true;
+		}
+		for (size_t i = 0; i < n_shapes; i++) {
+			if (!wants_entry(i) || matched[i].ent) continue;
+			const srt_model &m = shapes[i].shape.model;
+			BvhCacheEntry *kept = nullptr;
+			for (BvhCacheEntry &e : cache->entries) {
+				if (e.claimed || e.count != m.num_triangles || e.triangle_index != m.triangle_index) continue;
+				if (!kept || e.same_transform(m)) kept = &e;
+				if (e.same_transform(m)) break;
+			}
+			if (kept) kept->claimed = true, matched[i].ent = kept, matched[i].deformed = true;
+		}
+	}
 	auto u2f = [](uint32_t u) {
 		float f;
 		memcpy(&f, &u, 4);
@@ -124,34 +180,30 @@ int prepare_scene(int accel_mode, int refit_mode, BvhCache *&cache, int scan_sus
 				return fail(SRT_ERR_INVALID, "srt_update_scene: too many world triangles");
 			uint32_t link = use_bvh ? SRT_BVH_NONE : (uint32_t)total_wtris; // first world triangle of the model; BVH: root reference (NONE = nothing to walk)
 			if (use_bvh && m.num_triangles > 0) {
-				// hash of this triangle range, once per distinct range per call (instances share ranges)
-				uint64_t th = 0;
-				bool have_hash = false;
-				for (const auto &rh : range_hashes)
-					if (rh.first == (((uint64_t)m.triangle_index << 32) | m.num_triangles)) th = rh.second, have_hash = true;
-				if (!have_hash) {
-					th = hash_triangles(triangles + m.triangle_index, m.num_triangles);
-					range_hashes.emplace_back(((uint64_t)m.triangle_index << 32) | m.num_triangles, th);
-				}
-				// An entry of the previous call with the same triangles: as it is when the transform did not
-				// change either, otherwise refitted. Hash and transform are compared before any memcmp, and
-				// entries only LEAVE the cache once the whole shape loop has validated (an early error return
-				// keeps every hierarchy).
-				BvhCacheEntry *kept = nullptr;
-				for (BvhCacheEntry &e : cache->entries) {
-					if (e.claimed || e.count != m.num_triangles || e.tri_hash != th) continue;
-					const bool exact = e.same_transform(m);
-					if (!exact && kept) continue; // already holding a refit candidate: only an exact match improves on it
-					if (!e.same_triangles(m, triangles, th)) continue;
-					kept = &e;
-					if (exact) break;
+				const uint64_t th = range_hash(m);
+				// An entry of the previous call with the same triangles: as it is when the transform did not change either,
+				// otherwise refitted. Entries only LEAVE the cache once the whole shape loop has validated (an early error
+				// return keeps every hierarchy).
+				BvhCacheEntry *kept = deform_on ? matched[i].ent : find_same_triangles(m, th);
+				bool deformed = deform_on && matched[i].deformed;
+				if (deformed && deform.rebuild_ratio > 0.0f && BvhBuilder::cost_ratio(kept->cost_now, kept->cost_built) > (double)deform.rebuild_ratio) {
+					kept = nullptr, deformed = false; // refitted too often: the tree has degraded past the caller's bound, build a new one
+					deform_rebuilt++;
 				}
 				BvhCacheEntry *ent;
 				if (kept) {
 					ent = kept;
 					ent->claimed = true;
+					ent->triangle_index = m.triangle_index;
 					const bool on_device = refit_mode == SRT_REFIT_DEVICE;
-					if (ent->same_transform(m) && (!ent->stale || on_device)) {
+					if (deformed) { // other bytes in the same triangle range: the tree and its records' order stay, every box is recomputed
+						ent->tris.assign(triangles + m.triangle_index, triangles + m.triangle_index + m.num_triangles);
+						ent->tri_hash = th;
+						memcpy(ent->transform, m.transform, sizeof ent->transform);
+						if (on_device) ent->stale = true;
+						else ent->refit(m, triangles), ent->cost_now = BvhBuilder::wide_cost(ent->nodes, ent->wide);
+						bvh_refitted++, deform_kept++;
+					} else if (ent->same_transform(m) && (!ent->stale || on_device)) {
 						bvh_reused++; // (a stale one: refitted on the device again, below)
 					} else if (on_device) { // the model moved: the topology is uploaded as it is, the device recomputes the boxes
 						memcpy(ent->transform, m.transform, sizeof ent->transform);
@@ -159,6 +211,7 @@ int prepare_scene(int accel_mode, int refit_mode, BvhCache *&cache, int scan_sus
 						bvh_refitted++;
 					} else { // the model moved (or its boxes are a device refit behind): keep the tree, recompute the boxes
 						ent->refit(m, triangles);
+						if (deform_on) ent->cost_now = BvhBuilder::wide_cost(ent->nodes, ent->wide);
 						memcpy(ent->transform, m.transform, sizeof ent->transform);
 						bvh_refitted++;
 					}
@@ -168,6 +221,7 @@ int prepare_scene(int accel_mode, int refit_mode, BvhCache *&cache, int scan_sus
 					ent = &fresh.back();
 					ent->build(m, triangles);
 					ent->count = m.num_triangles;
+					ent->triangle_index = m.triangle_index;
 					ent->tri_hash = th;
 					memcpy(ent->transform, m.transform, sizeof ent->transform);
 					ent->tris.assign(triangles + m.triangle_index, triangles + m.triangle_index + m.num_triangles);
@@ -191,6 +245,17 @@ int prepare_scene(int accel_mode, int refit_mode, BvhCache *&cache, int scan_sus
 					sp.refit_models.push_back({(uint32_t)i, r0, m.num_triangles, 0u});
 					stale_plan.emplace_back(ent, b0);
 					if (m.num_triangles > sp.refit_max_records) sp.refit_max_records = m.num_triangles;
+					if (deform_on) { // the cost launch's view of the model
+						const uint32_t nb = (uint32_t)(wd.blocks.size() / 32);
+						sp.refit_cost_ranges.push_back({b0, nb});
+						sp.refit_cost_entry.push_back(plan.size() - 1);
+						sp.refit_cost_built.push_back(ent->cost_built);
+						sp.refit_weights.resize((size_t)b0 + nb, 0);
+						for (const BvhBuilder::Wide::Job &j : wd.jobs) sp.refit_weights[b0 + j.self] = (uint8_t)j.nk;
+						for (uint32_t d : wd.dest) sp.refit_weights[b0 + (d >> 2)]++;
+					}
+				} else if (deform_on) {
+					sp.deform_worst_ratio = std::max(sp.deform_worst_ratio, BvhBuilder::cost_ratio(ent->cost_now, ent->cost_built));
 				}
 				bvh_leaves += ent->leaves;
 				if (ent->depth > bvh_depth) bvh_depth = ent->depth;
@@ -284,6 +349,8 @@ int prepare_scene(int accel_mode, int refit_mode, BvhCache *&cache, int scan_sus
 	}
 	sp.bvh_info[0] = bvh_canonical_nodes, sp.bvh_info[1] = bvh_leaves, sp.bvh_info[2] = bvh_depth, sp.bvh_info[3] = use_bvh ? build_us : 0;
 	sp.bvh_info[4] = use_bvh ? plan.size() - bvh_reused - bvh_refitted : 0, sp.bvh_info[5] = bvh_reused, sp.bvh_info[6] = bvh_refitted;
+	sp.deform_info[0] = deform_kept, sp.deform_info[1] = deform_rebuilt;
+	if (deform_on) sp.refit_weights.resize(bvh_blocks.size() / 32, 0);
 	if (use_bvh) {
 		std::vector<BvhCacheEntry> next_cache;
 		next_cache.reserve(plan.size());

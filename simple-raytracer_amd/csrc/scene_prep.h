@@ -30,11 +30,34 @@ struct ScenePrep {
 	std::vector<RefitModel> refit_models;
 	std::vector<uint32_t> refit_extents, refit_sched, refit_levels;
 	uint32_t refit_max_records = 0;
+	// SRT_DEFORM_REFIT (empty / zero without it): {models kept across a change of triangle bytes, models rebuilt on their cost
+	// ratio}; and what the cost launch behind the device's refit needs of every refitted model (bvh_refit.hip
+	// srt_refit_cost_kernel): its blocks' range, per block of the scene the weight of its box in the cost (an inner block's
+	// children, a leaf block's triangles; other models' stay 0), its entry in the cache as this call leaves it and that
+	// entry's cost as built. deform_worst_ratio: the largest cost ratio the host knows among the models NOT refitted on the device.
+	uint64_t deform_info[2] = {0, 0};
+	std::vector<RefitCostRange> refit_cost_ranges;
+	std::vector<uint8_t> refit_weights;
+	std::vector<size_t> refit_cost_entry;
+	std::vector<double> refit_cost_built;
+	double deform_worst_ratio = 0.0;
 };
 
-// accel_mode: SRT_ACCEL_*; refit_mode: SRT_REFIT_* (who refits a model that only moved; nothing without SRT_ACCEL_BVH); cache: the caller's hierarchy cache (a group: its first member's); scan_suspend_min: srt_scan_suspend_min()
-int prepare_scene(int accel_mode, int refit_mode, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
+// srt_set_acceleration_deform: what becomes of a model whose triangle bytes changed (nothing without SRT_ACCEL_BVH)
+struct DeformPolicy {
+	int mode = SRT_DEFORM_REBUILD;
+	float rebuild_ratio = 0.0f; // SRT_DEFORM_REFIT: a kept model whose last known cost ratio is above this is rebuilt; 0 = never
+};
+
+// accel_mode: SRT_ACCEL_*; refit_mode: SRT_REFIT_* (who refits a model that only moved; nothing without SRT_ACCEL_BVH); deform: above; cache: the caller's hierarchy cache (a group: its first member's); scan_suspend_min: srt_scan_suspend_min()
+int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
                   const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene);
+
+// the same with SRT_DEFORM_REBUILD
+inline int prepare_scene(int accel_mode, int refit_mode, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
+                         const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
+	return prepare_scene(accel_mode, refit_mode, DeformPolicy(), cache, scan_suspend_min, err, sp, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
+}
 
 // the same with SRT_REFIT_HOST
 inline int prepare_scene(int accel_mode, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,

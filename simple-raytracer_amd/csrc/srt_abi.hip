@@ -4,6 +4,7 @@
 // beside it: the BVH builder (bvh_host.cpp), the scene's host pass (scene_prep.cpp), the launch plan (trace_plan.h).
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -203,6 +204,11 @@ void srt_destroy(srt_tracer *t) {
 	t->refit_boxes.release();
 	for (hipEvent_t ev : t->ev_refit)
 		if (ev) (void)hipEventDestroy(ev);
+	t->deform_ranges.release();
+	t->deform_weights.release();
+	t->deform_sums.release();
+	if (t->deform_sums_host) (void)hipHostFree(t->deform_sums_host);
+	if (t->ev_deform) (void)hipEventDestroy(t->ev_deform);
 	t->sky.release();
 	t->counters.release();
 	t->wave_counters.release();
@@ -281,11 +287,61 @@ int srt_update_scene(srt_tracer *t, const srt_shape *shapes, size_t n_shapes, co
 	}
 }
 
+// SRT_DEFORM_REFIT: waits for the last upload's cost sums (behind their event only, not for the stream) and turns them into
+// ratios: on the handle for srt_acceleration_deform_info, and on the hierarchies `cache` keeps (the handle's own; a group's first
+// member's) for the next srt_update_scene's rebuild rule. Once per upload.
+static int deform_consume(srt_tracer *t, BvhCache *cache) {
+	if (!t->deform_pending) return SRT_OK;
+	SRT_HIP(t, hipSetDevice(t->device));
+	SRT_HIP(t, hipEventSynchronize(t->ev_deform));
+	t->deform_pending = false;
+	for (size_t k = 0; k < t->deform_entry.size(); k++) {
+		const double cost_now = BvhBuilder::cost_of(t->deform_sums_host[2 * k], t->deform_sums_host[2 * k + 1]);
+		t->deform_ratio[k] = BvhBuilder::cost_ratio(cost_now, t->deform_built[k]);
+		if (cache && t->deform_entry[k] < cache->entries.size()) cache->entries[t->deform_entry[k]].cost_now = cost_now;
+	}
+	return SRT_OK;
+}
+
+// behind pass C: the cost of every refitted hierarchy, summed on the device and copied to pinned host memory
+static int deform_cost_on_device(srt_tracer *t, const ScenePrep &sp) {
+	const size_t n = sp.refit_cost_ranges.size();
+	t->deform_entry = sp.refit_cost_entry;
+	t->deform_built = sp.refit_cost_built;
+	t->deform_ratio.assign(n, 0.0);
+	if (n == 0) return SRT_OK;
+	SRT_HIP(t, t->deform_ranges.reserve(n));
+	SRT_HIP(t, t->deform_weights.reserve(sp.refit_weights.size()));
+	SRT_HIP(t, t->deform_sums.reserve(2 * n));
+	if (t->deform_sums_cap < 2 * n) {
+		if (t->deform_sums_host) (void)hipHostFree(t->deform_sums_host);
+		t->deform_sums_host = nullptr, t->deform_sums_cap = 0;
+		SRT_HIP(t, hipHostMalloc(reinterpret_cast<void **>(&t->deform_sums_host), 2 * n * sizeof(double), hipHostMallocDefault));
+		t->deform_sums_cap = 2 * n;
+	}
+	if (!t->ev_deform) SRT_HIP(t, hipEventCreateWithFlags(&t->ev_deform, hipEventDisableTiming));
+	SRT_HIP(t, hipMemcpyAsync(t->deform_ranges.ptr, sp.refit_cost_ranges.data(), n * sizeof(RefitCostRange), hipMemcpyHostToDevice, t->stream));
+	SRT_HIP(t, hipMemcpyAsync(t->deform_weights.ptr, sp.refit_weights.data(), sp.refit_weights.size(), hipMemcpyHostToDevice, t->stream));
+	SRT_HIP(t, hipMemsetAsync(t->deform_sums.ptr, 0, 2 * n * sizeof(double), t->stream));
+	uint32_t max_blocks = 0;
+	for (const RefitCostRange &r : sp.refit_cost_ranges) max_blocks = r.num_blocks > max_blocks ? r.num_blocks : max_blocks;
+	t->deform_info[2] = (uint64_t)srt_launch_refit_cost(t->refit_boxes.ptr, t->deform_weights.ptr, t->deform_ranges.ptr, t->deform_sums.ptr, (uint32_t)n, max_blocks, t->stream);
+	SRT_HIP(t, hipGetLastError());
+	SRT_HIP(t, hipMemcpyAsync(t->deform_sums_host, t->deform_sums.ptr, 2 * n * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+	SRT_HIP(t, hipEventRecord(t->ev_deform, t->stream));
+	t->deform_pending = true;
+	return SRT_OK;
+}
+
 // SRT_REFIT_DEVICE: behind the pre-pass, new boxes for the models whose blocks were uploaded from a stale hierarchy
 // (bvh_refit.hip): passes A and B over their records, then one launch per height level of their inner blocks
 static int refit_on_device(srt_tracer *t, const ScenePrep &sp) {
 	for (uint64_t &v : t->refit_info) v = 0;
 	t->refit_timed = false;
+	t->deform_pending = false; // (upload_scene_begin has waited for the stream: an earlier copy has landed, nobody asked for it)
+	t->deform_info[0] = sp.deform_info[0], t->deform_info[1] = sp.deform_info[1], t->deform_info[2] = 0, t->deform_info[3] = 0;
+	t->deform_worst_host = sp.deform_worst_ratio;
+	t->deform_entry.clear(), t->deform_built.clear(), t->deform_ratio.clear();
 	if (sp.refit_models.empty()) return SRT_OK;
 	const uint32_t n_models = (uint32_t)sp.refit_models.size();
 	SRT_HIP(t, t->refit_models.reserve(n_models));
@@ -316,6 +372,7 @@ static int refit_on_device(srt_tracer *t, const ScenePrep &sp) {
 	for (size_t h = 1; h < sp.refit_levels.size(); h++)
 		launches += srt_launch_refit_level(rp, sp.refit_levels[h - 1], sp.refit_levels[h] - sp.refit_levels[h - 1], t->stream);
 	SRT_HIP(t, hipGetLastError());
+	if (const int rc = deform_cost_on_device(t, sp)) return rc; // (nothing to do, and no launch, without SRT_DEFORM_REFIT)
 	if (t->timers_in_render) {
 		SRT_HIP(t, hipEventRecord(t->ev_refit[1], t->stream));
 		t->refit_timed = true;
@@ -418,7 +475,10 @@ static int upload_scene_end(srt_tracer *t, const ScenePrep &sp, size_t n_shapes,
 static int prepare_scene_of(srt_tracer *t, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
                             const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
 	std::string err;
-	const int rc = prepare_scene(t->accel_mode, t->refit_mode, t->bvh_cache, srt_scan_suspend_min(), err, sp, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
+	if (const int crc = deform_consume(t, t->bvh_cache)) return crc; // the rebuild rule looks at the last known cost ratios
+	DeformPolicy deform;
+	deform.mode = t->deform_mode, deform.rebuild_ratio = t->deform_rebuild_ratio;
+	const int rc = prepare_scene(t->accel_mode, t->refit_mode, deform, t->bvh_cache, srt_scan_suspend_min(), err, sp, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
 	return rc == SRT_OK ? SRT_OK : fail(t, rc, err);
 }
 
@@ -448,6 +508,7 @@ int srt_update_scene_many(srt_tracer *const *members, size_t n_members, const sr
 			if (failed_member) *failed_member = begun;
 			members[begun]->accel_mode = members[0]->accel_mode; // (the prepared scene is in this form)
 			members[begun]->refit_mode = members[0]->refit_mode;
+			members[begun]->deform_mode = members[0]->deform_mode, members[begun]->deform_rebuild_ratio = members[0]->deform_rebuild_ratio;
 			rc = upload_scene_begin(members[begun], sp, shapes, n_shapes, triangles, n_triangles, n_materials);
 		}
 		if (rc != SRT_OK) { // what was enqueued on the members before the failing one still reads the host arrays: let it finish
@@ -1113,6 +1174,29 @@ int srt_set_acceleration_refit(srt_tracer *t, int mode) {
 	if (!t) return SRT_ERR_INVALID;
 	if (mode != SRT_REFIT_HOST && mode != SRT_REFIT_DEVICE) return fail(t, SRT_ERR_INVALID, "srt_set_acceleration_refit: unknown mode");
 	t->refit_mode = mode;
+	return SRT_OK;
+}
+
+int srt_set_acceleration_deform(srt_tracer *t, int mode, float rebuild_ratio) {
+	if (!t) return SRT_ERR_INVALID;
+	if (mode != SRT_DEFORM_REBUILD && mode != SRT_DEFORM_REFIT) return fail(t, SRT_ERR_INVALID, "srt_set_acceleration_deform: unknown mode");
+	if (!(rebuild_ratio == 0.0f || (rebuild_ratio > 1.0f && rebuild_ratio <= FLT_MAX))) // (a NaN fails every comparison)
+		return fail(t, SRT_ERR_INVALID, "srt_set_acceleration_deform: rebuild_ratio must be 0 or a finite value above 1");
+	t->deform_mode = mode;
+	t->deform_rebuild_ratio = rebuild_ratio;
+	return SRT_OK;
+}
+
+int srt_acceleration_deform_info(srt_tracer *t, uint64_t out[4], double *worst_ratio) {
+	if (!t || !out || !worst_ratio) return SRT_ERR_INVALID;
+	for (int i = 0; i < 4; i++) out[i] = 0;
+	*worst_ratio = 0.0;
+	if (const int rc = deform_consume(t, t->bvh_cache)) return rc;
+	if (!t->bvh_active) return SRT_OK;
+	for (int i = 0; i < 4; i++) out[i] = t->deform_info[i];
+	double worst = t->deform_worst_host;
+	for (double r : t->deform_ratio) worst = r > worst ? r : worst;
+	*worst_ratio = worst;
 	return SRT_OK;
 }
 

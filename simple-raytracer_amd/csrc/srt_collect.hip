@@ -532,6 +532,12 @@ int srt_group_set_acceleration_refit(srt_group *g, int mode) {
 	return SRT_OK;
 }
 
+int srt_group_set_acceleration_deform(srt_group *g, int mode, float rebuild_ratio) {
+	if (!g) return SRT_ERR_INVALID;
+	SRT_EACH(g, srt_set_acceleration_deform(t_, mode, rebuild_ratio));
+	return SRT_OK;
+}
+
 int srt_group_update_scene(srt_group *g, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
                            const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
 	if (!g) return SRT_ERR_INVALID;

@@ -71,6 +71,22 @@ struct srt_tracer {
 	uint64_t refit_info[4] = {0, 0, 0, 0};
 	hipEvent_t ev_refit[2] = {nullptr, nullptr}; // around the refit launches, when the kernel timers are on
 	bool refit_timed = false;
+	// a deformed model keeps its hierarchy (srt_set_acceleration_deform): the policy of the next srt_update_scene, and of the last
+	// one its counts, the cost launch's inputs on the device and its sums on their way back -- device sums, a pinned host copy,
+	// the event behind the copy; deform_pending until somebody has waited for it (srt_deform_consume)
+	int deform_mode = SRT_DEFORM_REBUILD;
+	float deform_rebuild_ratio = 0.0f;
+	uint64_t deform_info[4] = {0, 0, 0, 0};
+	DevBuf<RefitCostRange> deform_ranges;
+	DevBuf<uint8_t> deform_weights;
+	DevBuf<double> deform_sums;
+	double *deform_sums_host = nullptr; // pinned, deform_sums_cap doubles
+	size_t deform_sums_cap = 0;
+	hipEvent_t ev_deform = nullptr;
+	bool deform_pending = false;
+	std::vector<size_t> deform_entry;  // per refitted model of the last upload: its entry in the cache, its cost as built
+	std::vector<double> deform_built, deform_ratio; // deform_ratio: cost now / as built once the sums are in; 0 = unknown
+	double deform_worst_host = 0.0;    // the largest ratio among the models the device did not refit
 	struct BvhCache *bvh_cache = nullptr; // hierarchies of the previous srt_update_scene (bvh_host.h BvhCacheEntry; made by scene_prep.cpp)
 	DevBuf<unsigned long long> counters;
 	DevBuf<unsigned long long> wave_counters; // per persistent wave, summed in srt_get_counters

@@ -165,6 +165,11 @@ class Tracer {
 	void set_acceleration(int mode) { check(group ? srt_group_set_acceleration(group, mode) : srt_set_acceleration(handle, mode)); }
 	// SRT_REFIT_HOST / SRT_REFIT_DEVICE: who refits the hierarchy of a model that only moved (the next update_scene on)
 	void set_acceleration_refit(int mode) { check(group ? srt_group_set_acceleration_refit(group, mode) : srt_set_acceleration_refit(handle, mode)); }
+	// SRT_DEFORM_REBUILD / SRT_DEFORM_REFIT: a model whose vertices changed is built anew / keeps its tree with new boxes, until
+	// its cost ratio passes rebuild_ratio (0 = never; the next update_scene on)
+	void set_acceleration_deform(int mode, float rebuild_ratio = 0.0f) {
+		check(group ? srt_group_set_acceleration_deform(group, mode, rebuild_ratio) : srt_set_acceleration_deform(handle, mode, rebuild_ratio));
+	}
 	/// The edge-aware denoiser (srt_set_denoise): iterations < 0 turns it off, else it is on with srt_denoise_defaults()
 	/// overridden by the arguments; render() / render_pipelined() then hand out the filtered image. On a Tracer over several
 	/// devices the members gather the filter's inputs with the frame and device 0 filters (srt_group_set_denoise): the same bytes.

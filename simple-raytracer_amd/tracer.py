@@ -47,10 +47,13 @@ ABI_SYMBOLS = [
     "srt_group_last_filter_demodulated",
     "srt_bvh_refit_wide_host", "srt_set_acceleration_refit", "srt_group_set_acceleration_refit", "srt_acceleration_refit_info",
     "srt_last_refit_kernel_ms", "srt_read_bvh_blocks", "srt_bvh_wide_order_host",
+    "srt_set_acceleration_deform", "srt_group_set_acceleration_deform", "srt_acceleration_deform_info",
+    "srt_bvh_refit_deformed_wide_host", "srt_bvh_wide_cost_host",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
 REFIT_HOST, REFIT_DEVICE = 0, 1
+DEFORM_REBUILD, DEFORM_REFIT = 0, 1
 MOTION_STATIC, MOTION_MOVED, MOTION_NO_HISTORY = 0, 1, 2
 MOTION_WORDS = 22
 NO_SHAPE = 0xFFFFFFFF
@@ -244,6 +247,44 @@ def bvh_refit_wide_host(built_shape, moved_shape, triangles, force_balanced=Fals
     return {"blocks": blocks, "root": root.value}
 
 
+def _deformed_args(built_shape, built_triangles, now_shape, now_triangles, force_balanced):
+    shapes = np.zeros(2, R.SHAPE)
+    shapes[0], shapes[1] = built_shape, now_shape
+    bt, nt = R.as_records(built_triangles, R.TRIANGLE), R.as_records(now_triangles, R.TRIANGLE)
+    if len(bt) != len(nt):
+        raise SrtError("the two triangle arrays differ in length")
+    return (shapes, bt, nt), (_ptr(shapes[0:1]), _ptr(bt), _ptr(shapes[1:2]), _ptr(nt), len(bt), int(bool(force_balanced)))
+
+
+def bvh_refit_deformed_wide_host(built_shape, built_triangles, now_shape, now_triangles, force_balanced=False):
+    """srt_bvh_refit_deformed_wide_host (host only): bvh_refit_wide_host for a model whose triangles changed too -- the
+    hierarchy of built_shape over built_triangles refitted in place around now_shape over now_triangles: dict with blocks
+    and root. What DEFORM_REFIT with REFIT_DEVICE leaves on the device."""
+    lib = load_library()
+    keep, args = _deformed_args(built_shape, built_triangles, now_shape, now_triangles, force_balanced)
+    n, root = C.c_size_t(0), C.c_uint32(0)
+    rc = lib.srt_bvh_refit_deformed_wide_host(*args, None, 0, C.byref(n), None)
+    if rc:
+        raise SrtError(f"srt_bvh_refit_deformed_wide_host failed ({rc})")
+    blocks = np.zeros((n.value, 32), np.uint32)
+    rc = lib.srt_bvh_refit_deformed_wide_host(*args, _ptr(blocks), len(blocks), C.byref(n), C.byref(root))
+    if rc:
+        raise SrtError(f"srt_bvh_refit_deformed_wide_host failed ({rc})")
+    return {"blocks": blocks, "root": root.value}
+
+
+def bvh_wide_cost_host(built_shape, built_triangles, now_shape, now_triangles, force_balanced=False):
+    """srt_bvh_wide_cost_host (host only): (cost_built, cost_now), the surface-area cost of that hierarchy as built and as
+    refitted in place; 0.0 = unknown."""
+    lib = load_library()
+    keep, args = _deformed_args(built_shape, built_triangles, now_shape, now_triangles, force_balanced)
+    built, now = C.c_double(0), C.c_double(0)
+    rc = lib.srt_bvh_wide_cost_host(*args, C.byref(built), C.byref(now))
+    if rc:
+        raise SrtError(f"srt_bvh_wide_cost_host failed ({rc})")
+    return built.value, now.value
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("paths", "rays", "sky", "tri_tests", "tri_pass_u", "nan_pixels", "watchdog")]
 
@@ -379,6 +420,12 @@ def _bind(lib):
         lib.srt_group_set_acceleration_refit.argtypes = [vp, i]
         lib.srt_acceleration_refit_info.argtypes = [vp, C.POINTER(C.c_uint64)]
         lib.srt_last_refit_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    if hasattr(lib, "srt_set_acceleration_deform"):  # (likewise)
+        lib.srt_set_acceleration_deform.argtypes = [vp, i, C.c_float]
+        lib.srt_group_set_acceleration_deform.argtypes = [vp, i, C.c_float]
+        lib.srt_acceleration_deform_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        lib.srt_bvh_refit_deformed_wide_host.argtypes = [vp, vp, vp, vp, sz, i, vp, sz, C.POINTER(sz), C.POINTER(C.c_uint32)]
+        lib.srt_bvh_wide_cost_host.argtypes = [vp, vp, vp, vp, sz, i, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         lib.srt_read_bvh_blocks.argtypes = [vp, vp, sz, C.POINTER(sz)]
     if hasattr(lib, "srt_gather"):
         lib.srt_comm_unique_id.argtypes = [vp]
@@ -717,6 +764,18 @@ class Tracer(_Denoise):
         update_scene."""
         self._check(self.lib.srt_set_acceleration_refit(self._h, int(mode)))
 
+    def set_acceleration_deform(self, mode, rebuild_ratio=0.0):
+        """DEFORM_REBUILD (the default) or DEFORM_REFIT: a model whose vertices changed is built anew / keeps its tree with
+        new boxes until its cost ratio passes rebuild_ratio (0: never); applies at the next update_scene."""
+        self._check(self.lib.srt_set_acceleration_deform(self._h, int(mode), float(rebuild_ratio)))
+
+    def acceleration_deform_info(self):
+        """Of the last update_scene: models kept across a change of triangle bytes, models rebuilt on their cost ratio, cost
+        launches, and the largest known cost ratio (0.0: none known). Waits for the cost read-back only."""
+        out, worst = (C.c_uint64 * 4)(), C.c_double(0)
+        self._check(self.lib.srt_acceleration_deform_info(self._h, out, C.byref(worst)))
+        return {"models_kept": int(out[0]), "models_rebuilt": int(out[1]), "cost_launches": int(out[2]), "worst_ratio": worst.value}
+
     def acceleration_refit_info(self):
         """Of the last update_scene: models refitted on the device, inner blocks they requantised, refit launches."""
         out = (C.c_uint64 * 4)()
@@ -902,6 +961,16 @@ class TracerGroup(_Denoise):
     def set_acceleration_refit(self, mode):
         """Tracer.set_acceleration_refit on every member."""
         self._check(self.lib.srt_group_set_acceleration_refit(self._g, int(mode)))
+
+    def set_acceleration_deform(self, mode, rebuild_ratio=0.0):
+        """Tracer.set_acceleration_deform on every member."""
+        self._check(self.lib.srt_group_set_acceleration_deform(self._g, int(mode), float(rebuild_ratio)))
+
+    def member_deform_info(self, i):
+        """Tracer.acceleration_deform_info of member i."""
+        out, worst = (C.c_uint64 * 4)(), C.c_double(0)
+        self._check(self.lib.srt_acceleration_deform_info(self.member(i), out, C.byref(worst)))
+        return {"models_kept": int(out[0]), "models_rebuilt": int(out[1]), "cost_launches": int(out[2]), "worst_ratio": worst.value}
 
     def set_textures(self, images):
         keep, descs = _texture_descs(images)

@@ -1,0 +1,269 @@
+// bvh_deform_check.cpp -- a deformed model keeps its hierarchy (include/srt_abi.h SRT_DEFORM_REFIT): the host side as a stand-alone
+// program for the sanitizers:
+//   g++ -std=c++17 -fsanitize=address,undefined -ffp-contract=off -pthread -I simple-raytracer_amd/csrc
+//       tests/csrc/bvh_deform_check.cpp simple-raytracer_amd/csrc/bvh_host.cpp simple-raytracer_amd/csrc/scene_prep.cpp
+// The chain build -> deformed refit in place -> cost at 6,050 triangles (through the cache entry and through the two host-only
+// calls), the quotient's "unknown" conventions, and the cache rule of prepare_scene: two instances of a deformed range both keep
+// their trees, under either refit mode; byte-identical matches are claimed before deformed ones; another count builds; the
+// default mode builds; an error return leaves the cache usable; a tree whose ratio passed rebuild_ratio is built anew. Exit
+// status 0 and "ok" when all of it holds.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "scene_prep.h"
+
+static int failures = 0;
+#define CHECK(c)                                                   \
+	do {                                                           \
+		if (!(c)) {                                                \
+			printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c);  \
+			failures++;                                            \
+		}                                                          \
+	} while (0)
+
+static uint32_t rng_state = 2024u;
+static float rnd() { // [0, 1)
+	rng_state = rng_state * 1664525u + 1013904223u;
+	return (float)(rng_state >> 8) * (1.0f / 16777216.0f);
+}
+
+// a bumpy sheet of n triangles over [0, 4)^2: neighbours in the array are neighbours in space
+static std::vector<srt_triangle> sheet(size_t n) {
+	std::vector<srt_triangle> t(n);
+	const size_t side = (size_t)std::ceil(std::sqrt((double)n));
+	for (size_t i = 0; i < n; i++) {
+		const float cx = 4.0f * (float)(i % side) / (float)side, cz = 4.0f * (float)(i / side) / (float)side;
+		for (int k = 0; k < 3; k++) {
+			memset(&t[i].vertices[k], 0, sizeof t[i].vertices[k]);
+			t[i].vertices[k].pos.x = cx + (k == 1 ? 4.0f / (float)side : 0.0f);
+			t[i].vertices[k].pos.z = cz + (k == 2 ? 4.0f / (float)side : 0.0f);
+			t[i].vertices[k].pos.y = 0.3f * std::sin(1.7f * cx) * std::cos(1.3f * cz) + 0.01f * rnd();
+			t[i].vertices[k].normal.y = 1.0f;
+		}
+	}
+	return t;
+}
+// the smooth wave: a few percent of the sheet's size
+static void wave(srt_triangle *t, size_t n, float phase) {
+	for (size_t i = 0; i < n; i++)
+		for (int k = 0; k < 3; k++) {
+			srt_float3 &p = t[i].vertices[k].pos;
+			p.y += 0.2f * std::sin(1.1f * p.x - 0.7f * p.z + phase);
+			p.x += 0.2f * std::sin(0.9f * p.z + phase);
+		}
+}
+// every vertex somewhere in the box
+static void scramble(srt_triangle *t, size_t n) {
+	for (size_t i = 0; i < n; i++)
+		for (int k = 0; k < 3; k++) t[i].vertices[k].pos.x = 4.0f * rnd(), t[i].vertices[k].pos.y = rnd() - 0.5f, t[i].vertices[k].pos.z = 4.0f * rnd();
+}
+
+static srt_shape model(uint32_t first, uint32_t n, float tx) {
+	srt_shape s;
+	memset(&s, 0, sizeof s);
+	s.type = SRT_SHAPE_MODEL;
+	s.shape.model.triangle_index = first, s.shape.model.num_triangles = n;
+	const float m[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, tx, 0, 0, 1};
+	memcpy(s.shape.model.transform, m, sizeof m);
+	return s;
+}
+
+struct Scene {
+	std::vector<srt_shape> shapes;
+	std::vector<srt_triangle> tris;
+	std::vector<srt_material> mats;
+};
+
+static int prepare(int refit, int deform_mode, float ratio, BvhCache *&cache, const Scene &s, ScenePrep &sp) {
+	srt_scene_data sd;
+	memset(&sd, 0, sizeof sd);
+	DeformPolicy dp;
+	dp.mode = deform_mode, dp.rebuild_ratio = ratio;
+	std::string err;
+	return prepare_scene(SRT_ACCEL_BVH, refit, dp, cache, 4096, err, sp, s.shapes.data(), s.shapes.size(), s.tris.data(), s.tris.size(), s.mats.data(), s.mats.size(), &sd);
+}
+// {built, reused, refitted, kept across a deformation, rebuilt on cost}
+static bool counts(const ScenePrep &sp, uint64_t built, uint64_t reused, uint64_t refitted, uint64_t kept, uint64_t rebuilt) {
+	const bool ok = sp.bvh_info[4] == built && sp.bvh_info[5] == reused && sp.bvh_info[6] == refitted && sp.deform_info[0] == kept && sp.deform_info[1] == rebuilt;
+	if (!ok)
+		printf("  built %llu reused %llu refitted %llu kept %llu rebuilt %llu\n", (unsigned long long)sp.bvh_info[4], (unsigned long long)sp.bvh_info[5],
+		       (unsigned long long)sp.bvh_info[6], (unsigned long long)sp.deform_info[0], (unsigned long long)sp.deform_info[1]);
+	return ok;
+}
+
+static void chain() {
+	const size_t n = 6050;
+	const std::vector<srt_triangle> t0 = sheet(n);
+	std::vector<srt_triangle> t1 = t0;
+	wave(t1.data(), n, 0.4f);
+	t1[n / 2].vertices[1].pos.x = NAN;
+	t1[n / 3].vertices[2].pos.y = INFINITY;
+	const srt_shape built = model(0, (uint32_t)n, 0.0f), now = model(0, (uint32_t)n, 0.5f);
+	for (int balanced = 0; balanced < 2; balanced++) {
+		BvhCacheEntry ent;
+		ent.balanced = balanced != 0;
+		ent.build(built.shape.model, t0.data());
+		CHECK(ent.cost_built > 0.0 && ent.cost_now == ent.cost_built);
+		const BvhBuilder::Wide as_built = ent.wide;
+		const double cost_built = ent.cost_built;
+		ent.refit_in_place(now.shape.model, t1.data());
+		CHECK(ent.cost_built == cost_built && ent.cost_now > 0.0 && std::isfinite(ent.cost_now));
+		CHECK(ent.wide.root == as_built.root && ent.wide.dest == as_built.dest && ent.wide.blocks.size() == as_built.blocks.size());
+		std::vector<uint32_t> out(as_built.blocks.size());
+		size_t nb = 0;
+		uint32_t root = 0;
+		CHECK(srt_bvh_refit_deformed_wide_host(&built, t0.data(), &now, t1.data(), n, balanced, out.data(), out.size() / 32, &nb, &root) == SRT_OK);
+		CHECK(nb == out.size() / 32 && root == ent.wide.root && out == ent.wide.blocks);
+		double cb = -1.0, cn = -1.0;
+		CHECK(srt_bvh_wide_cost_host(&built, t0.data(), &now, t1.data(), n, balanced, &cb, &cn) == SRT_OK);
+		CHECK(cb == cost_built && cn == ent.cost_now);
+		CHECK(srt_bvh_refit_wide_host(&built, &now, t0.data(), n, balanced, out.data(), out.size() / 32, &nb, &root) == SRT_OK);
+		std::vector<uint32_t> same(out.size());
+		CHECK(srt_bvh_refit_deformed_wide_host(&built, t0.data(), &now, t0.data(), n, balanced, same.data(), same.size() / 32, &nb, &root) == SRT_OK);
+		CHECK(same == out);
+		std::vector<srt_triangle> t2 = t0;
+		scramble(t2.data(), n);
+		double cs = 0.0;
+		CHECK(srt_bvh_wide_cost_host(&built, t0.data(), &built, t2.data(), n, balanced, &cb, &cs) == SRT_OK);
+		CHECK(cs > 2.0 * cb);
+		srt_shape wrong = now;
+		wrong.shape.model.num_triangles = (uint32_t)n - 1u;
+		CHECK(srt_bvh_wide_cost_host(&built, t0.data(), &wrong, t1.data(), n, balanced, &cb, &cn) == SRT_ERR_INVALID);
+		CHECK(srt_bvh_refit_deformed_wide_host(&built, t0.data(), &wrong, t1.data(), n, balanced, nullptr, 0, &nb, nullptr) == SRT_ERR_INVALID);
+	}
+	// the quotient: unknown is 0
+	const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+	CHECK(BvhBuilder::cost_of(6.0, 2.0) == 3.0);
+	CHECK(BvhBuilder::cost_of(6.0, 0.0) == 0.0 && BvhBuilder::cost_of(0.0, 0.0) == 0.0 && BvhBuilder::cost_of(inf, 2.0) == 0.0);
+	CHECK(BvhBuilder::cost_of(nan, 2.0) == 0.0 && BvhBuilder::cost_of(2.0, nan) == 0.0 && BvhBuilder::cost_of(2.0, inf) == 0.0 && BvhBuilder::cost_of(inf, inf) == 0.0);
+	CHECK(BvhBuilder::cost_ratio(3.0, 2.0) == 1.5 && BvhBuilder::cost_ratio(0.0, 2.0) == 0.0 && BvhBuilder::cost_ratio(3.0, 0.0) == 0.0);
+}
+
+static void cache_rule(int refit) {
+	const uint32_t n = 6050, nb = 40;
+	Scene s;
+	s.tris = sheet(n);
+	const std::vector<srt_triangle> small = sheet(nb);
+	s.tris.insert(s.tris.end(), small.begin(), small.end());
+	s.mats.resize(1);
+	memset(s.mats.data(), 0, sizeof(srt_material));
+	s.mats[0].refraction_index = 1.0f;
+	s.shapes = {model(0, n, 0.0f), model(n, nb, 9.0f), model(0, n, 5.0f)}; // two instances of one range around another model
+	BvhCache *cache = nullptr;
+	{
+		ScenePrep sp;
+		CHECK(prepare(refit, SRT_DEFORM_REFIT, 0.0f, cache, s, sp) == SRT_OK && counts(sp, 3, 0, 0, 0, 0));
+		CHECK(sp.refit_cost_ranges.empty() && sp.deform_worst_ratio == 1.0);
+	}
+	Scene d = s;
+	wave(d.tris.data(), n, 0.3f); // only the shared range's bytes change
+	{
+		ScenePrep sp;
+		CHECK(prepare(refit, SRT_DEFORM_REFIT, 0.0f, cache, d, sp) == SRT_OK && counts(sp, 0, 1, 2, 2, 0));
+		CHECK(cache->entries.size() == 3 && cache->entries[0].tri_hash == cache->entries[2].tri_hash);
+		CHECK(memcmp(cache->entries[0].tris.data(), d.tris.data(), n * sizeof(srt_triangle)) == 0);
+		if (refit == SRT_REFIT_DEVICE) { // both are handed to the device, with what the cost launch needs
+			CHECK(sp.refit_models.size() == 2 && sp.refit_cost_ranges.size() == 2 && sp.refit_cost_entry.size() == 2 && sp.refit_cost_built.size() == 2);
+			CHECK(sp.refit_weights.size() == sp.bvh_blocks.size() / 32);
+			CHECK(sp.refit_cost_entry[0] == 0 && sp.refit_cost_entry[1] == 2 && sp.refit_cost_built[0] == cache->entries[0].cost_built);
+			for (size_t k = 0; k < sp.refit_cost_ranges.size(); k++) {
+				const RefitCostRange r = sp.refit_cost_ranges[k];
+				CHECK((size_t)r.first_block + r.num_blocks <= sp.refit_weights.size());
+				uint64_t leaf_weight = 0, empty = 0;
+				for (uint32_t b = r.first_block; b < r.first_block + r.num_blocks; b++) {
+					const uint32_t nk = sp.bvh_blocks[32 * (size_t)b + 3] >> 24; // (0: a leaf block, which the host leaves empty)
+					if (nk) CHECK(sp.refit_weights[b] == nk);
+					else leaf_weight += sp.refit_weights[b];
+					empty += sp.refit_weights[b] == 0;
+				}
+				CHECK(leaf_weight == n && empty == 0);
+			}
+			CHECK(cache->entries[0].stale && cache->entries[2].stale && !cache->entries[1].stale);
+		} else {
+			CHECK(sp.refit_models.empty() && sp.refit_cost_ranges.empty() && sp.deform_worst_ratio > 0.0);
+			CHECK(cache->entries[0].cost_now > 0.0 && cache->entries[0].cost_now != cache->entries[0].cost_built);
+		}
+	}
+	{ // an error return (the last shape's material does not exist) after another deformation: the cache stays usable
+		Scene bad = d;
+		wave(bad.tris.data(), n, 0.9f);
+		bad.shapes[2].material = 7;
+		ScenePrep sp, again;
+		CHECK(prepare(refit, SRT_DEFORM_REFIT, 0.0f, cache, bad, sp) == SRT_ERR_INVALID);
+		CHECK(cache->entries.size() == 3);
+		bad.shapes[2].material = 0;
+		CHECK(prepare(refit, SRT_DEFORM_REFIT, 0.0f, cache, bad, again) == SRT_OK);
+		CHECK(again.bvh_info[4] == 0 && again.bvh_info[5] + again.bvh_info[6] == 3);
+		d = bad;
+	}
+	{ // Byte-identical matches first. The array gets new triangles IN FRONT: the first model's range [0, n) now holds other
+	  // bytes, the second model's range [n, 2n) the bytes the cached hierarchy of range [0, n) was made of.
+		Scene one;
+		one.mats = s.mats;
+		one.tris = sheet(n);
+		one.shapes = {model(0, n, 0.0f)};
+		BvhCache *c2 = nullptr;
+		ScenePrep sp0, sp1;
+		CHECK(prepare(refit, SRT_DEFORM_REFIT, 0.0f, c2, one, sp0) == SRT_OK && counts(sp0, 1, 0, 0, 0, 0));
+		Scene two = one;
+		std::vector<srt_triangle> front = one.tris;
+		wave(front.data(), n, 1.9f);
+		two.tris.insert(two.tris.begin(), front.begin(), front.end());
+		two.shapes = {model(0, n, 0.0f), model(n, n, 0.0f)};
+		CHECK(prepare(refit, SRT_DEFORM_REFIT, 0.0f, c2, two, sp1) == SRT_OK && counts(sp1, 1, 1, 0, 0, 0));
+		CHECK(c2->entries.size() == 2 && c2->entries[1].triangle_index == n && c2->entries[0].triangle_index == 0);
+		delete c2;
+	}
+	{ // another count builds; so does the default mode
+		Scene fewer = d;
+		wave(fewer.tris.data(), n, 1.3f);
+		fewer.shapes = {model(0, n - 1, 0.0f), model(n, nb, 9.0f)};
+		ScenePrep sp;
+		CHECK(prepare(refit, SRT_DEFORM_REFIT, 0.0f, cache, fewer, sp) == SRT_OK && counts(sp, 1, 1, 0, 0, 0));
+		Scene next = fewer;
+		wave(next.tris.data(), n, 1.5f);
+		ScenePrep sp2;
+		CHECK(prepare(refit, SRT_DEFORM_REBUILD, 0.0f, cache, next, sp2) == SRT_OK && counts(sp2, 1, 1, 0, 0, 0));
+		CHECK(sp2.refit_cost_ranges.empty() && sp2.refit_weights.empty() && sp2.deform_worst_ratio == 0.0);
+	}
+	delete cache;
+}
+
+// the rebuild rule, where the host knows the cost at once (SRT_REFIT_HOST)
+static void rebuild_rule() {
+	const uint32_t n = 600;
+	Scene s;
+	s.tris = sheet(n);
+	s.mats.resize(1);
+	memset(s.mats.data(), 0, sizeof(srt_material));
+	s.shapes = {model(0, n, 0.0f)};
+	BvhCache *cache = nullptr;
+	ScenePrep a, b, c, d, e;
+	const float bound = 1.5f;
+	CHECK(prepare(SRT_REFIT_HOST, SRT_DEFORM_REFIT, bound, cache, s, a) == SRT_OK && counts(a, 1, 0, 0, 0, 0));
+	wave(s.tris.data(), n, 0.2f);
+	CHECK(prepare(SRT_REFIT_HOST, SRT_DEFORM_REFIT, bound, cache, s, b) == SRT_OK && counts(b, 0, 0, 1, 1, 0));
+	CHECK(b.deform_worst_ratio > 0.0 && b.deform_worst_ratio < bound);
+	scramble(s.tris.data(), n);
+	CHECK(prepare(SRT_REFIT_HOST, SRT_DEFORM_REFIT, bound, cache, s, c) == SRT_OK && counts(c, 0, 0, 1, 1, 0)); // (the last KNOWN ratio was the wave's)
+	CHECK(c.deform_worst_ratio > bound);
+	wave(s.tris.data(), n, 0.5f);
+	CHECK(prepare(SRT_REFIT_HOST, SRT_DEFORM_REFIT, bound, cache, s, d) == SRT_OK && counts(d, 1, 0, 0, 0, 1));
+	CHECK(d.deform_worst_ratio == 1.0);
+	wave(s.tris.data(), n, 0.7f);
+	CHECK(prepare(SRT_REFIT_HOST, SRT_DEFORM_REFIT, 0.0f, cache, s, e) == SRT_OK && counts(e, 0, 0, 1, 1, 0));
+	delete cache;
+}
+
+int main() {
+	chain();
+	cache_rule(SRT_REFIT_HOST);
+	cache_rule(SRT_REFIT_DEVICE);
+	rebuild_rule();
+	printf(failures ? "%d checks failed\n" : "ok\n", failures);
+	return failures ? 1 : 0;
+}
