@@ -182,6 +182,41 @@ int srt_bvh_refit_deformed_wide_host(const srt_shape *built, const srt_triangle 
  * triangles). The device's sum takes its terms in another order: it agrees within n_blocks * 2^-53 relative. */
 int srt_bvh_wide_cost_host(const srt_shape *built, const srt_triangle *built_triangles, const srt_shape *now,
                            const srt_triangle *now_triangles, size_t n_triangles, int force_balanced, double *cost_built, double *cost_now);
+/* Who BUILDS the hierarchy of a model that has none to keep (a new model, another triangle count, other triangle bytes without
+ * SRT_DEFORM_REFIT, a rebuild that rebuild_ratio asked for). SRT_BUILD_HOST, the default: the binned-SAH build on the host, as
+ * ever. SRT_BUILD_DEVICE: a model of at least min_triangles triangles (0: every model) gets the BALANCED topology of its count
+ * -- halves by record index down to leaves of three, a function of the count alone that the host keeps per count -- over the
+ * MORTON order of its triangles, which kernels on the handle's stream compute before the pre-pass: the model's extents, a
+ * 30-bit code per triangle, a stable radix sort by (code, index); the refit passes of SRT_REFIT_DEVICE then make every box.
+ *   per triangle j: world vertices, unpadded box lo / hi and finiteness as the builder's; c[a] = 0.5f * lo[a] + 0.5f * hi[a]
+ *   mlo / mhi: the model's extents over its finite triangles; per axis ext = mhi[a] - mlo[a];
+ *   q[a] = ext > 0 and finite ? clamp((int)((c[a] - mlo[a]) * (1024.0f / ext)), 0, 1023) : 0   (float32, unfused, IEEE division)
+ *   code: bit 3i+2 = bit i of q[x], 3i+1 of q[y], 3i of q[z]; a non-finite triangle: 0x40000000, behind every finite one
+ *   order = the triangles by ascending (code, j)
+ * Smaller models keep the host's build. The canvas does not depend on the tree's shape; the trace time does (a median split of a
+ * 10-bit Morton order is a worse tree than the SAH's: DESIGN.md has the cost and time ratios). Afterwards such a model is
+ * re-used, moved and deformed like any other; the sorted order comes back to the host asynchronously and is waited for at the
+ * next srt_update_scene and in srt_acceleration_build_info. A device-built model counts in srt_acceleration_info's out[4]
+ * (built); out[3] is the host's time alone. Under SRT_DEFORM_REFIT the cost launch runs behind the build and its value becomes
+ * the tree's cost as built. SRT_ERR_INVALID for another mode. Takes effect at the next srt_update_scene; accepted and without
+ * effect under SRT_ACCEL_NONE. */
+#define SRT_BUILD_HOST 0
+#define SRT_BUILD_DEVICE 1
+int srt_set_acceleration_build(srt_tracer *t, int mode, uint32_t min_triangles);
+/* Of the last srt_update_scene: out = {models built on the device, records sorted, build launches enqueued (extents, codes and
+ * the sort's; the refit's are srt_acceleration_refit_info's), 0}. Waits for the sorted order's read-back, not for the stream. */
+int srt_acceleration_build_info(srt_tracer *t, uint64_t out[4]);
+/* With srt_set_kernel_timers on: the device time from the first build launch of the last srt_update_scene to the last launch of
+ * the refit behind it (the pre-pass lies in between), in milliseconds; 0 when nothing was built on the device. Blocking. */
+int srt_last_build_kernel_ms(srt_tracer *t, float *ms);
+/* Host-only: the Morton order defined above for one model (order[r] = index inside the model of the triangle in record r).
+ * Writes at most order_cap indices. */
+int srt_bvh_morton_order_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, uint32_t *order_out, size_t order_cap);
+/* Host-only: the wide hierarchy SRT_BUILD_DEVICE leaves on the device, bit for bit: the balanced topology over the Morton order
+ * with the boxes of the in-place refit. Blocks, dest, root and stack_need as srt_bvh_wide_host hands them out (relative to the
+ * model, leaf blocks zero; stack_need is at most 45); *cost = the hierarchy's cost (above; may be NULL). */
+int srt_bvh_morton_wide_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, uint32_t *blocks_out, size_t blocks_cap,
+                             uint32_t *dest_out, size_t dest_cap, size_t *n_blocks, uint32_t *root, uint32_t *stack_need, double *cost);
 /* Tests / inspection: the device's block array as the kernel walks it -- every model's blocks, absolute indices, leaf
  * blocks with their triangles. Blocking. Writes at most blocks_cap blocks of 32 dwords and always sets *n_blocks (0 without
  * SRT_ACCEL_BVH or without models); blocks_out may be NULL to only query. */
@@ -346,6 +381,7 @@ int srt_group_set_triangle_materials(srt_group *g, const int32_t *materials, siz
 int srt_group_set_acceleration(srt_group *g, int mode);
 int srt_group_set_acceleration_refit(srt_group *g, int mode); /* srt_set_acceleration_refit on every member */
 int srt_group_set_acceleration_deform(srt_group *g, int mode, float rebuild_ratio); /* srt_set_acceleration_deform on every member */
+int srt_group_set_acceleration_build(srt_group *g, int mode, uint32_t min_triangles); /* srt_set_acceleration_build on every member (the scene is prepared once; every member sorts on its own device) */
 int srt_group_update_scene(srt_group *g, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
                            const srt_material *materials, size_t n_materials, const srt_scene_data *scene);
 int srt_group_clear_canvas(srt_group *g);

@@ -14,6 +14,7 @@
 void BvhBuilder::load(const srt_model &m, const srt_triangle *all) {
 	const uint32_t n = m.num_triangles;
 	tris.resize(n);
+	is_finite.assign(n, 1);
 	auto xf = [&](const srt_float3 &v, float out[3]) {
 		const srt_float4 *t = m.transform;
 		out[0] = ((t[0].x * v.x + t[1].x * v.y) + t[2].x * v.z) + t[3].x * 1.0f;
@@ -37,6 +38,7 @@ void BvhBuilder::load(const srt_model &m, const srt_triangle *all) {
 		}
 		if (!finite) { // hostile input: a box that every ray enters, so the triangle is always tested
 			for (int a = 0; a < 3; a++) t.lo[a] = -FLT_MAX, t.hi[a] = FLT_MAX, t.c[a] = 0.0f;
+			is_finite[j] = 0;
 			continue;
 		}
 		for (int a = 0; a < 3; a++) {
@@ -45,6 +47,7 @@ void BvhBuilder::load(const srt_model &m, const srt_triangle *all) {
 			mhi[a] = std::max(mhi[a], t.hi[a]);
 		}
 	}
+	for (int a = 0; a < 3; a++) ext_lo[a] = mlo[a], ext_hi[a] = mhi[a];
 	double d2 = 0.0;
 	for (int a = 0; a < 3; a++)
 		if (mhi[a] >= mlo[a]) d2 += ((double)mhi[a] - mlo[a]) * ((double)mhi[a] - mlo[a]);
@@ -411,6 +414,92 @@ uint32_t BvhBuilder::run(const srt_model &m, const srt_triangle *all, uint32_t f
 	return n0;
 }
 
+uint32_t BvhBuilder::morton_code(const float c[3], const float mlo[3], const float mhi[3]) {
+	uint32_t q[3];
+	for (int a = 0; a < 3; a++) {
+		q[a] = 0u;
+		const float ext = mhi[a] - mlo[a];
+		if (!(ext > 0.0f) || !std::isfinite(ext)) continue;
+		const float f = (c[a] - mlo[a]) * (1024.0f / ext);
+		q[a] = f >= 1023.0f ? 1023u : (f > 0.0f ? (uint32_t)(int)f : 0u); // = clamp((int)f, 0, 1023); a NaN (0 * inf) gives 0
+	}
+	uint32_t code = 0u;
+	for (int i = 0; i < 10; i++) code |= (((q[0] >> i) & 1u) << (3 * i + 2)) | (((q[1] >> i) & 1u) << (3 * i + 1)) | (((q[2] >> i) & 1u) << (3 * i));
+	return code;
+}
+void BvhBuilder::morton_order(std::vector<uint32_t> &out) const {
+	std::vector<uint64_t> keys(tris.size());
+	for (size_t j = 0; j < tris.size(); j++) // (load() leaves tris in triangle order)
+		keys[j] = ((uint64_t)(is_finite[j] ? morton_code(tris[j].c, ext_lo, ext_hi) : MORTON_NONFINITE) << 32) | (uint64_t)j;
+	std::sort(keys.begin(), keys.end());
+	out.resize(keys.size());
+	for (size_t r = 0; r < keys.size(); r++) out[r] = (uint32_t)keys[r];
+}
+static BvhBuilder::Stats balanced_into(std::vector<BvhNode> &out, uint32_t b, uint32_t e, uint32_t depth) {
+	BvhBuilder::Stats st;
+	const uint32_t self = (uint32_t)out.size(), n = e - b;
+	out.emplace_back();
+	memset(&out[self], 0, sizeof(BvhNode));
+	st.max_depth = depth;
+	if (n <= SRT_BVH_LEAF_MAX) {
+		out[self].leaf = (n << 28) | b;
+		st.leaves = 1;
+	} else {
+		const BvhBuilder::Stats sl = balanced_into(out, b, b + n / 2, depth + 1), sr = balanced_into(out, b + n / 2, e, depth + 1);
+		st.leaves = sl.leaves + sr.leaves;
+		st.max_depth = std::max(sl.max_depth, sr.max_depth);
+	}
+	out[self].skip = (uint32_t)out.size();
+	return st;
+}
+BvhBuilder::Stats BvhBuilder::balanced_topology(uint32_t count, std::vector<BvhNode> &out) {
+	out.clear();
+	if (count == 0) return Stats();
+	out.reserve(count); // (at most 2 * ceil(count / 2) - 1 nodes)
+	const Stats st = balanced_into(out, 0u, count, 1u);
+	const uint32_t end = (uint32_t)out.size();
+	for (BvhNode &nd : out)
+		if (nd.skip == end) nd.skip = SRT_BVH_END;
+	return st;
+}
+
+void BvhCacheEntry::set_balanced_topology(uint32_t n) {
+	const BvhBuilder::Stats st = BvhBuilder::balanced_topology(n, nodes);
+	leaves = st.leaves, depth = st.max_depth;
+	balanced = true;
+	BvhBuilder::fold_wide(nodes, n, true, wide); // (quantises the zero boxes: every inner block is requantised by the refit)
+	order.resize(n);
+	for (uint32_t r = 0; r < n; r++) order[r] = r;
+	stale = true, order_pending = true;
+	cost_built = cost_now = 0.0;
+}
+void BvhCacheEntry::build_morton(const srt_model &m, const srt_triangle *all) {
+	set_balanced_topology(m.num_triangles);
+	{
+		std::vector<BvhNode> none;
+		std::vector<uint32_t> unused;
+		BvhBuilder bb(none, unused);
+		bb.load(m, all);
+		bb.morton_order(order);
+	}
+	order_pending = false;
+	refit_in_place(m, all); // (clears `stale`)
+	cost_built = cost_now;
+}
+const BvhCacheEntry &BvhCache::balanced_topology(uint32_t count) {
+	for (size_t k = 0; k < topologies.size(); k++)
+		if (topologies[k].count == count) {
+			std::rotate(topologies.begin(), topologies.begin() + k, topologies.begin() + k + 1);
+			return topologies.front();
+		}
+	if (topologies.size() >= 4) topologies.pop_back();
+	topologies.emplace(topologies.begin());
+	topologies.front().count = count;
+	topologies.front().set_balanced_topology(count);
+	topologies.front().wide.ensure_schedule();
+	return topologies.front();
+}
+
 // (re)builds nodes/order from the model and folds them; the fallback keeps every walk inside SRT_BVH_STACK_CAP
 void BvhCacheEntry::build(const srt_model &m, const srt_triangle *all) {
 	stale = false;
@@ -529,6 +618,43 @@ int srt_bvh_refit_wide_host(const srt_shape *built, const srt_shape *moved, cons
 		*n_blocks = ent.wide.blocks.size() / 32;
 		if (root) *root = ent.wide.root;
 		if (blocks_out) memcpy(blocks_out, ent.wide.blocks.data(), std::min(ent.wide.blocks.size(), blocks_cap * 32) * sizeof(uint32_t));
+	} catch (...) { // std::bad_alloc: no C++ exception may cross the C ABI
+		return SRT_ERR_INVALID;
+	}
+	return SRT_OK;
+}
+
+int srt_bvh_morton_order_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, uint32_t *order_out, size_t order_cap) {
+	if (!model || model->type != SRT_SHAPE_MODEL || (n_triangles && !triangles)) return SRT_ERR_INVALID;
+	const srt_model &m = model->shape.model;
+	if ((uint64_t)m.triangle_index + m.num_triangles > n_triangles || m.num_triangles > 0x0fffffffu) return SRT_ERR_INVALID;
+	try {
+		std::vector<BvhNode> none;
+		std::vector<uint32_t> order;
+		BvhBuilder bb(none, order);
+		bb.load(m, triangles);
+		bb.morton_order(order);
+		if (order_out && !order.empty()) memcpy(order_out, order.data(), std::min(order.size(), order_cap) * sizeof(uint32_t));
+	} catch (...) { // std::bad_alloc: no C++ exception may cross the C ABI
+		return SRT_ERR_INVALID;
+	}
+	return SRT_OK;
+}
+
+int srt_bvh_morton_wide_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, uint32_t *blocks_out, size_t blocks_cap,
+                             uint32_t *dest_out, size_t dest_cap, size_t *n_blocks, uint32_t *root, uint32_t *stack_need, double *cost) {
+	if (!model || !n_blocks || model->type != SRT_SHAPE_MODEL || (n_triangles && !triangles)) return SRT_ERR_INVALID;
+	const srt_model &m = model->shape.model;
+	if ((uint64_t)m.triangle_index + m.num_triangles > n_triangles || m.num_triangles > 0x0fffffffu) return SRT_ERR_INVALID;
+	try {
+		BvhCacheEntry ent;
+		if (m.num_triangles > 0) ent.build_morton(m, triangles);
+		*n_blocks = ent.wide.blocks.size() / 32;
+		if (root) *root = ent.wide.root;
+		if (stack_need) *stack_need = ent.wide.need;
+		if (cost) *cost = ent.cost_built;
+		if (blocks_out && !ent.wide.blocks.empty()) memcpy(blocks_out, ent.wide.blocks.data(), std::min(ent.wide.blocks.size(), blocks_cap * 32) * sizeof(uint32_t));
+		if (dest_out && !ent.wide.dest.empty()) memcpy(dest_out, ent.wide.dest.data(), std::min(ent.wide.dest.size(), dest_cap) * sizeof(uint32_t));
 	} catch (...) { // std::bad_alloc: no C++ exception may cross the C ABI
 		return SRT_ERR_INVALID;
 	}

@@ -21,6 +21,10 @@ struct BvhBuilder {
 		uint32_t j;
 	};
 	std::vector<Tri> tris;
+	// of the last load(): per triangle whether its unpadded box was finite, and the model's extents over the finite ones
+	// (FLT_MAX / -FLT_MAX on an axis without any): what the Morton order below is defined over
+	std::vector<uint8_t> is_finite;
+	float ext_lo[3] = {0, 0, 0}, ext_hi[3] = {0, 0, 0};
 	std::vector<BvhNode> &nodes;
 	std::vector<uint32_t> &order;
 	uint32_t rec_base = 0;
@@ -90,6 +94,18 @@ struct BvhBuilder {
 	static double cost_ratio(double cost_now, double cost_built) { return cost_now > 0.0 && cost_built > 0.0 ? cost_of(cost_now, cost_built) : 0.0; }
 
 	uint32_t run(const srt_model &m, const srt_triangle *all, uint32_t first_record);
+
+	// ---- the Morton order and the balanced topology (include/srt_abi.h SRT_BUILD_DEVICE; bvh_build.hip sorts by the same codes) ----
+	// 30 bits: per axis the centroid's cell of 1024 between the model's extents, x above y above z in every bit triple; an axis
+	// whose extent is not a positive finite number gives cell 0. float32, unfused, in this order.
+	static uint32_t morton_code(const float c[3], const float mlo[3], const float mhi[3]);
+	static constexpr uint32_t MORTON_NONFINITE = 0x40000000u; // a triangle with a non-finite box: behind every finite one
+	// after load(): the model's triangles by ascending (code, index)
+	void morton_order(std::vector<uint32_t> &out) const;
+	// The canonical binary form over `count` records that depends on nothing else: what build_into gives with sah_depth = 0 and
+	// without its nth_element -- halves at b + n / 2 down to leaves of at most SRT_BVH_LEAF_MAX records, skip links as run()
+	// leaves them. The boxes are zero: a refit fills them in.
+	static Stats balanced_topology(uint32_t count, std::vector<BvhNode> &out);
 };
 
 // One model instance's hierarchy with indices relative to its own first node / first record, kept
@@ -112,6 +128,12 @@ struct BvhCacheEntry {
 	// store it; for a stale entry the device's cost kernel reports it, srt_abi.hip); 0 = unknown
 	double cost_built = 0.0, cost_now = 0.0;
 	void build(const srt_model &m, const srt_triangle *all);
+	// The hierarchy SRT_BUILD_DEVICE makes, on the host: `order` = the Morton order, the balanced topology of the model's count
+	// folded with balanced = true, the boxes of refit_in_place over that order.
+	void build_morton(const srt_model &m, const srt_triangle *all);
+	// The part of it that depends on the count alone: nodes and `wide` of the balanced topology (boxes zero, inner blocks not
+	// yet quantised), `order` the identity, stale, order_pending. The device sorts and refits (scene_prep.cpp, srt_abi.hip).
+	void set_balanced_topology(uint32_t n);
 	void refit(const srt_model &m, const srt_triangle *all);
 	// New boxes for the wide hierarchy AS IT IS FOLDED: the binary boxes as refit() makes them, then every inner block
 	// requantised with the children it has. No re-fold, so root, need, dest, order, tags, first and the block count stay
@@ -122,6 +144,9 @@ struct BvhCacheEntry {
 	// an earlier one. Whatever is uploaded from a stale entry is refitted on the device behind the upload; build() and
 	// refit() recompute everything from the triangles and clear the mark.
 	bool stale = false;
+	// Built on the device by the srt_update_scene before: `order` is still the identity, the sorted one is on its way back
+	// (srt_abi.hip waits for the copy before the next host pass looks at any entry).
+	bool order_pending = false;
 	bool same_triangles(const srt_model &m, const srt_triangle *all, uint64_t hash) const {
 		return m.num_triangles == count && hash == tri_hash && memcmp(tris.data(), all + m.triangle_index, (size_t)count * sizeof(srt_triangle)) == 0;
 	}
@@ -131,6 +156,10 @@ struct BvhCacheEntry {
 // the hierarchies of the previous srt_update_scene; a handle owns one (srt_tracer::bvh_cache), made when first needed
 struct BvhCache {
 	std::vector<BvhCacheEntry> entries;
+	// SRT_BUILD_DEVICE: the balanced topologies of the last few triangle counts, the most recent first (entries without
+	// triangles or order: set_balanced_topology's result, copied into the model's entry)
+	std::vector<BvhCacheEntry> topologies;
+	const BvhCacheEntry &balanced_topology(uint32_t count);
 };
 
 uint64_t hash_triangles(const srt_triangle *tris, size_t count);

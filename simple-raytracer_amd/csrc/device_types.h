@@ -325,7 +325,7 @@ struct RefitModel {
 	uint32_t shape;        /* index of the model's srt_shape: its transform and triangle range */
 	uint32_t first_record; /* = wtri_offset[shape] */
 	uint32_t num_records;
-	uint32_t _pad;
+	uint32_t first_tile;   /* a model built on the device (bvh_build.hip): its first tile in the sort's histogram table; else 0 */
 };
 struct RefitCostRange { /* a refitted model's blocks, for srt_refit_cost_kernel */
 	uint32_t first_block, num_blocks;
@@ -351,6 +351,26 @@ int srt_launch_refit_level(const RefitParams &p, uint32_t first, uint32_t count,
  * in double (H: the box's half area), sums[2 * k + 1] = H of the model's root box (its first block's). `sums` starts zeroed; the
  * host divides. Returns the launches enqueued. */
 int srt_launch_refit_cost(const float *boxes, const uint8_t *weights, const RefitCostRange *ranges, double *sums, uint32_t num_models, uint32_t max_blocks, void *stream);
+/* Building a model's hierarchy on the device (bvh_build.hip; include/srt_abi.h SRT_BUILD_DEVICE): the Morton code of every record
+ * of models[0 .. num_models) and a stable radix sort of the records by it, 8 bits a pass. Records and tiles are the scene's
+ * (absolute); a model's tiles are SRT_BUILD_TILE records each, its histogram table 256 x tiles counters, digit-major, at
+ * table[256 * first_tile]. */
+#define SRT_BUILD_TILE 1024u /* records per workgroup of the sort: 256 threads, four rounds */
+#define SRT_BUILD_SORT_PASSES 4 /* the codes' 31 significant bits */
+struct BuildParams {
+	const srt_shape *shapes;
+	const srt_triangle *triangles;
+	const RefitModel *models;
+	const uint32_t *extents; /* per model, as RefitParams::extents: srt_launch_refit_extents over the identity order has run */
+	uint32_t *keys[2];       /* per record of the scene: the codes, and the other side of the sort's ping-pong */
+	uint32_t *vals[2];       /* likewise the triangle indices */
+	uint32_t *table;
+	uint32_t *order;         /* the scene's order array: the last pass writes the models' record ranges */
+};
+#define SRT_BUILD_TILES(records) (((uint32_t)(records) + SRT_BUILD_TILE - 1u) / SRT_BUILD_TILE)
+/* the codes into keys[0]; then the sort: per pass a histogram, a scan and a scatter launch. Return the launches enqueued. */
+int srt_launch_build_keys(const BuildParams &p, uint32_t num_models, uint32_t max_records, void *stream);
+int srt_launch_build_sort(const BuildParams &p, uint32_t num_models, uint32_t max_records, void *stream);
 void srt_launch_resolve(const ResolveParams &p, void *stream);
 void srt_launch_selftest(unsigned long long *out16, uint32_t stride, void *stream);
 void srt_launch_selftest_rare(int what, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, unsigned long long *mismatches, void *stream);

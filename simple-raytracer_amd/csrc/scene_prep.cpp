@@ -25,7 +25,7 @@ uint64_t bernoulli_threshold(float pr) {
 
 // host pass; `cache` is made when a BVH scene first needs it and emptied by an array-scan scene; an error return leaves its text
 // in `err` and every cached hierarchy in place
-int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
+int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, const BuildPolicy &build, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
                   const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
 	auto fail = [&err](int code, const char *msg) {
 		err = msg;
@@ -191,6 +191,7 @@ int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, Bv
 					deform_rebuilt++;
 				}
 				BvhCacheEntry *ent;
+				bool device_built = false;
 				if (kept) {
 					ent = kept;
 					ent->claimed = true;
@@ -219,7 +220,11 @@ int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, Bv
 				} else {
 					fresh.emplace_back();
 					ent = &fresh.back();
-					ent->build(m, triangles);
+					device_built = build.mode == SRT_BUILD_DEVICE && m.num_triangles >= build.min_triangles;
+					// on the device: the topology of the count, stale with the identity order -- the device sorts the records
+					// before the pre-pass reads them and refits every box behind it
+					if (device_built) *ent = cache->balanced_topology(m.num_triangles);
+					else ent->build(m, triangles);
 					ent->count = m.num_triangles;
 					ent->triangle_index = m.triangle_index;
 					ent->tri_hash = th;
@@ -245,11 +250,18 @@ int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, Bv
 					sp.refit_models.push_back({(uint32_t)i, r0, m.num_triangles, 0u});
 					stale_plan.emplace_back(ent, b0);
 					if (m.num_triangles > sp.refit_max_records) sp.refit_max_records = m.num_triangles;
+					if (device_built) {
+						sp.build_models.push_back({(uint32_t)i, r0, m.num_triangles, sp.build_tiles});
+						sp.build_tiles += SRT_BUILD_TILES(m.num_triangles);
+						sp.build_entry.push_back(plan.size() - 1);
+						if (m.num_triangles > sp.build_max_records) sp.build_max_records = m.num_triangles;
+					}
 					if (deform_on) { // the cost launch's view of the model
 						const uint32_t nb = (uint32_t)(wd.blocks.size() / 32);
 						sp.refit_cost_ranges.push_back({b0, nb});
 						sp.refit_cost_entry.push_back(plan.size() - 1);
 						sp.refit_cost_built.push_back(ent->cost_built);
+						sp.refit_cost_fresh.push_back(device_built ? 1 : 0);
 						sp.refit_weights.resize((size_t)b0 + nb, 0);
 						for (const BvhBuilder::Wide::Job &j : wd.jobs) sp.refit_weights[b0 + j.self] = (uint8_t)j.nk;
 						for (uint32_t d : wd.dest) sp.refit_weights[b0 + (d >> 2)]++;
@@ -303,6 +315,8 @@ int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, Bv
 			}
 			sp.refit_levels.push_back((uint32_t)sp.refit_sched.size());
 		}
+		for (size_t k = 0; k < sp.build_models.size(); k++)
+			sp.build_extents.insert(sp.build_extents.end(), {SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_HI_INIT, SRT_REFIT_EXT_HI_INIT, SRT_REFIT_EXT_HI_INIT});
 		for (size_t k = 0; k < stale_plan.size(); k++)
 			sp.refit_extents.insert(sp.refit_extents.end(), {SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_HI_INIT, SRT_REFIT_EXT_HI_INIT, SRT_REFIT_EXT_HI_INIT});
 	}

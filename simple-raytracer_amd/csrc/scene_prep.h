@@ -41,6 +41,21 @@ struct ScenePrep {
 	std::vector<size_t> refit_cost_entry;
 	std::vector<double> refit_cost_built;
 	double deform_worst_ratio = 0.0;
+	std::vector<uint8_t> refit_cost_fresh; // per cost range: the model was built by this call (below): the sum becomes its cost as built
+	// SRT_BUILD_DEVICE (empty / zero without it): the models whose order the device sorts before the pre-pass (bvh_build.hip) --
+	// bvh_order holds the identity for their records, their blocks come from the balanced topology and they are among
+	// refit_models, too --, their first tiles in the sort's table (RefitModel::first_tile) adding up to build_tiles, their empty
+	// extents, and per model its entry in the cache as this call leaves it: where the sorted order goes once it is back.
+	std::vector<RefitModel> build_models;
+	std::vector<uint32_t> build_extents;
+	std::vector<size_t> build_entry;
+	uint32_t build_max_records = 0, build_tiles = 0;
+};
+
+// srt_set_acceleration_build: who builds a model that has no hierarchy to keep (nothing without SRT_ACCEL_BVH)
+struct BuildPolicy {
+	int mode = SRT_BUILD_HOST;
+	uint32_t min_triangles = 0; // SRT_BUILD_DEVICE: smaller models keep the host's build
 };
 
 // srt_set_acceleration_deform: what becomes of a model whose triangle bytes changed (nothing without SRT_ACCEL_BVH)
@@ -49,9 +64,15 @@ struct DeformPolicy {
 	float rebuild_ratio = 0.0f; // SRT_DEFORM_REFIT: a kept model whose last known cost ratio is above this is rebuilt; 0 = never
 };
 
-// accel_mode: SRT_ACCEL_*; refit_mode: SRT_REFIT_* (who refits a model that only moved; nothing without SRT_ACCEL_BVH); deform: above; cache: the caller's hierarchy cache (a group: its first member's); scan_suspend_min: srt_scan_suspend_min()
-int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
+// accel_mode: SRT_ACCEL_*; refit_mode: SRT_REFIT_* (who refits a model that only moved; nothing without SRT_ACCEL_BVH); deform, build: above; cache: the caller's hierarchy cache (a group: its first member's); scan_suspend_min: srt_scan_suspend_min()
+int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, const BuildPolicy &build, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
                   const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene);
+
+// the same with SRT_BUILD_HOST
+inline int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
+                         const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
+	return prepare_scene(accel_mode, refit_mode, deform, BuildPolicy(), cache, scan_suspend_min, err, sp, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
+}
 
 // the same with SRT_DEFORM_REBUILD
 inline int prepare_scene(int accel_mode, int refit_mode, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,

@@ -204,6 +204,14 @@ void srt_destroy(srt_tracer *t) {
 	t->refit_boxes.release();
 	for (hipEvent_t ev : t->ev_refit)
 		if (ev) (void)hipEventDestroy(ev);
+	t->build_models.release();
+	t->build_extents.release();
+	t->build_table.release();
+	for (int k = 0; k < 2; k++) t->build_keys[k].release(), t->build_vals[k].release();
+	if (t->build_order_host) (void)hipHostFree(t->build_order_host);
+	if (t->ev_build_done) (void)hipEventDestroy(t->ev_build_done);
+	for (hipEvent_t ev : t->ev_build)
+		if (ev) (void)hipEventDestroy(ev);
 	t->deform_ranges.release();
 	t->deform_weights.release();
 	t->deform_sums.release();
@@ -297,8 +305,12 @@ static int deform_consume(srt_tracer *t, BvhCache *cache) {
 	t->deform_pending = false;
 	for (size_t k = 0; k < t->deform_entry.size(); k++) {
 		const double cost_now = BvhBuilder::cost_of(t->deform_sums_host[2 * k], t->deform_sums_host[2 * k + 1]);
-		t->deform_ratio[k] = BvhBuilder::cost_ratio(cost_now, t->deform_built[k]);
-		if (cache && t->deform_entry[k] < cache->entries.size()) cache->entries[t->deform_entry[k]].cost_now = cost_now;
+		const bool fresh = k < t->deform_fresh.size() && t->deform_fresh[k]; // built on the device by that upload: this IS its cost as built
+		t->deform_ratio[k] = BvhBuilder::cost_ratio(cost_now, fresh ? cost_now : t->deform_built[k]);
+		if (cache && t->deform_entry[k] < cache->entries.size()) {
+			cache->entries[t->deform_entry[k]].cost_now = cost_now;
+			if (fresh) cache->entries[t->deform_entry[k]].cost_built = cost_now;
+		}
 	}
 	return SRT_OK;
 }
@@ -308,6 +320,7 @@ static int deform_cost_on_device(srt_tracer *t, const ScenePrep &sp) {
 	const size_t n = sp.refit_cost_ranges.size();
 	t->deform_entry = sp.refit_cost_entry;
 	t->deform_built = sp.refit_cost_built;
+	t->deform_fresh = sp.refit_cost_fresh;
 	t->deform_ratio.assign(n, 0.0);
 	if (n == 0) return SRT_OK;
 	SRT_HIP(t, t->deform_ranges.reserve(n));
@@ -333,6 +346,102 @@ static int deform_cost_on_device(srt_tracer *t, const ScenePrep &sp) {
 	return SRT_OK;
 }
 
+// SRT_BUILD_DEVICE: waits for the last upload's sorted order (behind its event only, not for the stream) and hands every built
+// model's records to its hierarchy in `cache` (the handle's own; a group's first member's), so that every host path that reads
+// an entry's order finds it. An entry whose order never came back (an upload that failed half way) leaves the cache: its
+// model is built again. Once per upload.
+static int build_consume(srt_tracer *t, BvhCache *cache) {
+	if (t->build_pending) {
+		SRT_HIP(t, hipSetDevice(t->device));
+		SRT_HIP(t, hipEventSynchronize(t->ev_build_done));
+		t->build_pending = false;
+		for (size_t k = 0; cache && k < t->build_entry.size(); k++) {
+			if (t->build_entry[k] >= cache->entries.size()) continue;
+			BvhCacheEntry &e = cache->entries[t->build_entry[k]];
+			const RefitModel &rm = t->build_ranges[k];
+			if (!e.order_pending || e.count != rm.num_records) continue;
+			e.order.assign(t->build_order_host + rm.first_record, t->build_order_host + rm.first_record + rm.num_records);
+			e.order_pending = false;
+		}
+	}
+	if (cache)
+		for (size_t k = cache->entries.size(); k-- > 0;)
+			if (cache->entries[k].order_pending) cache->entries.erase(cache->entries.begin() + (ptrdiff_t)k);
+	return SRT_OK;
+}
+
+// SRT_BUILD_DEVICE, before the pre-pass: the order of the models this call builds (bvh_build.hip) -- their extents over the
+// identity order the upload carries, a Morton code per record, the sort, whose last pass writes the scene's order array
+static int build_on_device(srt_tracer *t, const ScenePrep &sp) {
+	for (uint64_t &v : t->build_info) v = 0;
+	t->build_timed = false;
+	t->build_pending = false; // (upload_scene_begin has waited for the stream: an earlier copy has landed, nobody asked for it)
+	t->build_entry.clear(), t->build_ranges.clear();
+	if (sp.build_models.empty()) return SRT_OK;
+	const uint32_t n_models = (uint32_t)sp.build_models.size();
+	const size_t records = sp.bvh_order.size();
+	SRT_HIP(t, t->build_models.reserve(n_models));
+	SRT_HIP(t, t->build_extents.reserve(sp.build_extents.size()));
+	SRT_HIP(t, t->build_table.reserve(256 * (size_t)sp.build_tiles));
+	for (int k = 0; k < 2; k++) {
+		SRT_HIP(t, t->build_keys[k].reserve(records));
+		SRT_HIP(t, t->build_vals[k].reserve(records));
+	}
+	SRT_HIP(t, hipMemcpyAsync(t->build_models.ptr, sp.build_models.data(), n_models * sizeof(RefitModel), hipMemcpyHostToDevice, t->stream));
+	SRT_HIP(t, hipMemcpyAsync(t->build_extents.ptr, sp.build_extents.data(), sp.build_extents.size() * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream));
+	if (t->timers_in_render) {
+		for (hipEvent_t &ev : t->ev_build)
+			if (!ev) SRT_HIP(t, hipEventCreate(&ev));
+		SRT_HIP(t, hipEventRecord(t->ev_build[0], t->stream));
+	}
+	RefitParams rp;
+	memset(&rp, 0, sizeof rp);
+	rp.shapes = t->shapes.ptr;
+	rp.triangles = t->triangles.ptr;
+	rp.order = t->bvh_order.ptr;
+	rp.models = t->build_models.ptr;
+	rp.extents = t->build_extents.ptr;
+	BuildParams bp;
+	bp.shapes = t->shapes.ptr;
+	bp.triangles = t->triangles.ptr;
+	bp.models = t->build_models.ptr;
+	bp.extents = t->build_extents.ptr;
+	for (int k = 0; k < 2; k++) bp.keys[k] = t->build_keys[k].ptr, bp.vals[k] = t->build_vals[k].ptr;
+	bp.table = t->build_table.ptr;
+	bp.order = t->bvh_order.ptr;
+	int launches = srt_launch_refit_extents(rp, n_models, sp.build_max_records, t->stream);
+	launches += srt_launch_build_keys(bp, n_models, sp.build_max_records, t->stream);
+	launches += srt_launch_build_sort(bp, n_models, sp.build_max_records, t->stream);
+	SRT_HIP(t, hipGetLastError());
+	uint64_t sorted = 0;
+	for (const RefitModel &rm : sp.build_models) sorted += rm.num_records;
+	t->build_info[0] = n_models, t->build_info[1] = sorted, t->build_info[2] = (uint64_t)launches;
+	return SRT_OK;
+}
+
+// ... and behind the refit of the same upload: the end of the timed span, and the sorted order on its way to pinned host memory
+static int build_read_back(srt_tracer *t, const ScenePrep &sp) {
+	if (sp.build_models.empty()) return SRT_OK;
+	if (t->timers_in_render) {
+		SRT_HIP(t, hipEventRecord(t->ev_build[1], t->stream));
+		t->build_timed = true;
+	}
+	const size_t records = sp.bvh_order.size();
+	if (t->build_order_cap < records) {
+		if (t->build_order_host) (void)hipHostFree(t->build_order_host);
+		t->build_order_host = nullptr, t->build_order_cap = 0;
+		SRT_HIP(t, hipHostMalloc(reinterpret_cast<void **>(&t->build_order_host), records * sizeof(uint32_t), hipHostMallocDefault));
+		t->build_order_cap = records;
+	}
+	if (!t->ev_build_done) SRT_HIP(t, hipEventCreateWithFlags(&t->ev_build_done, hipEventDisableTiming));
+	SRT_HIP(t, hipMemcpyAsync(t->build_order_host, t->bvh_order.ptr, records * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream));
+	SRT_HIP(t, hipEventRecord(t->ev_build_done, t->stream));
+	t->build_entry = sp.build_entry;
+	t->build_ranges = sp.build_models;
+	t->build_pending = true;
+	return SRT_OK;
+}
+
 // SRT_REFIT_DEVICE: behind the pre-pass, new boxes for the models whose blocks were uploaded from a stale hierarchy
 // (bvh_refit.hip): passes A and B over their records, then one launch per height level of their inner blocks
 static int refit_on_device(srt_tracer *t, const ScenePrep &sp) {
@@ -341,7 +450,7 @@ static int refit_on_device(srt_tracer *t, const ScenePrep &sp) {
 	t->deform_pending = false; // (upload_scene_begin has waited for the stream: an earlier copy has landed, nobody asked for it)
 	t->deform_info[0] = sp.deform_info[0], t->deform_info[1] = sp.deform_info[1], t->deform_info[2] = 0, t->deform_info[3] = 0;
 	t->deform_worst_host = sp.deform_worst_ratio;
-	t->deform_entry.clear(), t->deform_built.clear(), t->deform_ratio.clear();
+	t->deform_entry.clear(), t->deform_built.clear(), t->deform_ratio.clear(), t->deform_fresh.clear();
 	if (sp.refit_models.empty()) return SRT_OK;
 	const uint32_t n_models = (uint32_t)sp.refit_models.size();
 	SRT_HIP(t, t->refit_models.reserve(n_models));
@@ -429,6 +538,7 @@ static int upload_scene_begin(srt_tracer *t, const ScenePrep &sp, const srt_shap
 	if (n_materials)
 		SRT_HIP(t, hipMemcpyAsync(t->materials.ptr, dev_mats.data(), n_materials * sizeof(srt_material), hipMemcpyHostToDevice, t->stream));
 
+	if (const int brc = build_on_device(t, sp)) return brc; // (nothing to do, and no launch, without SRT_BUILD_DEVICE)
 	if (num_models > 0 && total_wtris > 0) {
 		if (!use_bvh) SRT_HIP(t, hipMemsetAsync(t->wtris.ptr, 0, ((size_t)total_wtris * SRT_WTRI_FLOATS + 64) * sizeof(float), t->stream));
 		// blockIdx.y = shape index; launch in slabs of 65535 shapes
@@ -447,7 +557,8 @@ static int upload_scene_begin(srt_tracer *t, const ScenePrep &sp, const srt_shap
 		}
 		SRT_HIP(t, hipGetLastError());
 	}
-	return refit_on_device(t, sp);
+	if (const int rrc = refit_on_device(t, sp)) return rrc;
+	return build_read_back(t, sp);
 }
 
 // device pass, second half: the uploads have arrived (the host arrays are free again), the handle describes the new scene
@@ -476,9 +587,12 @@ static int prepare_scene_of(srt_tracer *t, ScenePrep &sp, const srt_shape *shape
                             const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
 	std::string err;
 	if (const int crc = deform_consume(t, t->bvh_cache)) return crc; // the rebuild rule looks at the last known cost ratios
+	if (const int brc = build_consume(t, t->bvh_cache)) return brc;  // every entry's order is the sorted one
 	DeformPolicy deform;
 	deform.mode = t->deform_mode, deform.rebuild_ratio = t->deform_rebuild_ratio;
-	const int rc = prepare_scene(t->accel_mode, t->refit_mode, deform, t->bvh_cache, srt_scan_suspend_min(), err, sp, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
+	BuildPolicy build;
+	build.mode = t->build_mode, build.min_triangles = t->build_min_triangles;
+	const int rc = prepare_scene(t->accel_mode, t->refit_mode, deform, build, t->bvh_cache, srt_scan_suspend_min(), err, sp, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
 	return rc == SRT_OK ? SRT_OK : fail(t, rc, err);
 }
 
@@ -509,6 +623,7 @@ int srt_update_scene_many(srt_tracer *const *members, size_t n_members, const sr
 			members[begun]->accel_mode = members[0]->accel_mode; // (the prepared scene is in this form)
 			members[begun]->refit_mode = members[0]->refit_mode;
 			members[begun]->deform_mode = members[0]->deform_mode, members[begun]->deform_rebuild_ratio = members[0]->deform_rebuild_ratio;
+			members[begun]->build_mode = members[0]->build_mode, members[begun]->build_min_triangles = members[0]->build_min_triangles;
 			rc = upload_scene_begin(members[begun], sp, shapes, n_shapes, triangles, n_triangles, n_materials);
 		}
 		if (rc != SRT_OK) { // what was enqueued on the members before the failing one still reads the host arrays: let it finish
@@ -1197,6 +1312,32 @@ int srt_acceleration_deform_info(srt_tracer *t, uint64_t out[4], double *worst_r
 	double worst = t->deform_worst_host;
 	for (double r : t->deform_ratio) worst = r > worst ? r : worst;
 	*worst_ratio = worst;
+	return SRT_OK;
+}
+
+int srt_set_acceleration_build(srt_tracer *t, int mode, uint32_t min_triangles) {
+	if (!t) return SRT_ERR_INVALID;
+	if (mode != SRT_BUILD_HOST && mode != SRT_BUILD_DEVICE) return fail(t, SRT_ERR_INVALID, "srt_set_acceleration_build: unknown mode");
+	t->build_mode = mode;
+	t->build_min_triangles = min_triangles;
+	return SRT_OK;
+}
+
+int srt_acceleration_build_info(srt_tracer *t, uint64_t out[4]) {
+	if (!t || !out) return SRT_ERR_INVALID;
+	for (int i = 0; i < 4; i++) out[i] = 0;
+	if (const int rc = deform_consume(t, t->bvh_cache)) return rc; // (a built model's cost as built comes with the same upload)
+	if (const int rc = build_consume(t, t->bvh_cache)) return rc;
+	for (int i = 0; i < 4; i++) out[i] = t->bvh_active ? t->build_info[i] : 0;
+	return SRT_OK;
+}
+
+int srt_last_build_kernel_ms(srt_tracer *t, float *ms) {
+	if (!t || !ms) return SRT_ERR_INVALID;
+	*ms = 0.f;
+	SRT_HIP(t, hipSetDevice(t->device));
+	SRT_HIP(t, hipStreamSynchronize(t->stream));
+	if (t->build_timed) SRT_HIP(t, hipEventElapsedTime(ms, t->ev_build[0], t->ev_build[1]));
 	return SRT_OK;
 }
 

@@ -87,6 +87,24 @@ struct srt_tracer {
 	std::vector<size_t> deform_entry;  // per refitted model of the last upload: its entry in the cache, its cost as built
 	std::vector<double> deform_built, deform_ratio; // deform_ratio: cost now / as built once the sums are in; 0 = unknown
 	double deform_worst_host = 0.0;    // the largest ratio among the models the device did not refit
+	// a model's hierarchy built on the device (bvh_build.hip; srt_set_acceleration_build): the policy of the next srt_update_scene;
+	// of the last one the built models, their extents, the sort's two key / index buffers (a slot per record of the scene) and
+	// its histogram table, the counts, and the sorted order on its way back to the host -- a pinned copy of the scene's order
+	// array and the event behind the copy; build_pending until somebody has waited for it (build_consume in srt_abi.hip)
+	int build_mode = SRT_BUILD_HOST;
+	uint32_t build_min_triangles = 0;
+	DevBuf<RefitModel> build_models;
+	DevBuf<uint32_t> build_extents, build_keys[2], build_vals[2], build_table;
+	uint64_t build_info[4] = {0, 0, 0, 0};
+	uint32_t *build_order_host = nullptr; // pinned, build_order_cap indices
+	size_t build_order_cap = 0;
+	hipEvent_t ev_build_done = nullptr;
+	bool build_pending = false;
+	std::vector<size_t> build_entry;             // per built model of the last upload: its entry in the cache ...
+	std::vector<RefitModel> build_ranges;        // ... and its records
+	std::vector<uint8_t> deform_fresh;           // per cost range of the last upload: a model built by it (its sum is its cost as built)
+	hipEvent_t ev_build[2] = {nullptr, nullptr}; // around the build launches and the refit behind them, when the kernel timers are on
+	bool build_timed = false;
 	struct BvhCache *bvh_cache = nullptr; // hierarchies of the previous srt_update_scene (bvh_host.h BvhCacheEntry; made by scene_prep.cpp)
 	DevBuf<unsigned long long> counters;
 	DevBuf<unsigned long long> wave_counters; // per persistent wave, summed in srt_get_counters

@@ -170,6 +170,13 @@ class Tracer {
 	void set_acceleration_deform(int mode, float rebuild_ratio = 0.0f) {
 		check(group ? srt_group_set_acceleration_deform(group, mode, rebuild_ratio) : srt_set_acceleration_deform(handle, mode, rebuild_ratio));
 	}
+	// SRT_BUILD_HOST / SRT_BUILD_DEVICE: a model of at least min_triangles triangles without a hierarchy to keep is built by the
+	// host's SAH / gets the balanced topology over its Morton order, sorted on the device
+	void set_acceleration_build(int mode, uint32_t min_triangles = 0) {
+		check(group ? srt_group_set_acceleration_build(group, mode, min_triangles) : srt_set_acceleration_build(handle, mode, min_triangles));
+	}
+	// {models built on the device by the last update, records sorted, build launches, 0} (a group: its first member's)
+	void acceleration_build_info(uint64_t out[4]) { check(srt_acceleration_build_info(group ? srt_group_tracer(group, 0) : handle, out)); }
 	/// The edge-aware denoiser (srt_set_denoise): iterations < 0 turns it off, else it is on with srt_denoise_defaults()
 	/// overridden by the arguments; render() / render_pipelined() then hand out the filtered image. On a Tracer over several
 	/// devices the members gather the filter's inputs with the frame and device 0 filters (srt_group_set_denoise): the same bytes.

@@ -5,7 +5,7 @@
 //
 //   srt_headless [--scene spheres|meshes|empty] [--obj f.obj]... [--stl f.stl]...
 //                [--width W --height H --spp S --bounces B --frames N --time T]
-//                [--obj-materials] [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--demodulate] [--temporal] [--move DX]
+//                [--obj-materials] [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--demodulate] [--temporal] [--move DX]
 // --denoise K: the frames go through the edge-aware denoiser with K a-trous passes (Tracer::set_denoise; with --gpus N the
 //                members gather the filter's inputs with the frame and device 0 filters: the same bytes as on one device)
 // --demodulate: with --denoise, the passes filter colour / first-hit albedo (Tracer::set_denoise_demodulation); an error without it
@@ -122,6 +122,8 @@ int main(int argc, char **argv) {
 	float move = 0.0f, shape_move = 0.0f;
 	int move_shape = -1;
 	bool moving = false;
+	bool bvh_build_device = false;
+	uint32_t bvh_build_min = 0;
 	for (int i = 1; i < argc; i++) {
 		std::string a = argv[i];
 		auto next = [&]() -> const char * {
@@ -144,6 +146,17 @@ int main(int argc, char **argv) {
 		else if (a == "--dump") dump_prefix = next();
 		else if (a == "--parse-only") parse_only = true;
 		else if (a == "--bvh") bvh = true;
+		else if (a == "--bvh-build") { // device[:MIN] | host
+			const std::string v = next();
+			if (v == "host") bvh_build_device = false;
+			else if (v.rfind("device", 0) == 0 && (v.size() == 6 || v[6] == ':')) {
+				bvh_build_device = true;
+				bvh_build_min = v.size() > 7 ? (uint32_t)std::strtoul(v.c_str() + 7, nullptr, 10) : 0u;
+			} else {
+				std::cerr << "--bvh-build takes host or device[:MIN]\n";
+				return 2;
+			}
+		}
 		else if (a == "--obj-materials") obj_materials = true;
 		else if (a == "--gpus") gpus = std::atoi(next());
 		else if (a == "--pipelined") pipelined = true;
@@ -159,7 +172,7 @@ int main(int argc, char **argv) {
 		else if (a == "--move-shape") move_shape = std::atoi(next()), shape_move = std::strtof(next(), nullptr);
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
-			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--gpus N] [--pipelined] [--skybox sky.ppm] "
+			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--gpus N] [--pipelined] [--skybox sky.ppm] "
 			             "[--denoise K] [--demodulate] [--temporal] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
@@ -281,6 +294,7 @@ int main(int argc, char **argv) {
 	// ---- tracer set-up, as src/main.cpp:114-126 ----
 	Tracer tracer(width, height, 0, gpus); // --gpus N: one Tracer over N devices (rows split, one RCCL gather per frame)
 	if (bvh) tracer.set_acceleration(SRT_ACCEL_BVH);
+	if (bvh_build_device) tracer.set_acceleration_build(SRT_BUILD_DEVICE, bvh_build_min); // (models of at least MIN triangles; without --bvh: no effect)
 	if (denoise >= 0) tracer.set_denoise(denoise);
 	if (demodulate) tracer.set_denoise_demodulation();
 	if (temporal) tracer.set_denoise_temporal();

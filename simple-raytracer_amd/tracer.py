@@ -49,11 +49,14 @@ ABI_SYMBOLS = [
     "srt_last_refit_kernel_ms", "srt_read_bvh_blocks", "srt_bvh_wide_order_host",
     "srt_set_acceleration_deform", "srt_group_set_acceleration_deform", "srt_acceleration_deform_info",
     "srt_bvh_refit_deformed_wide_host", "srt_bvh_wide_cost_host",
+    "srt_set_acceleration_build", "srt_group_set_acceleration_build", "srt_acceleration_build_info", "srt_last_build_kernel_ms",
+    "srt_bvh_morton_order_host", "srt_bvh_morton_wide_host",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
 REFIT_HOST, REFIT_DEVICE = 0, 1
 DEFORM_REBUILD, DEFORM_REFIT = 0, 1
+BUILD_HOST, BUILD_DEVICE = 0, 1
 MOTION_STATIC, MOTION_MOVED, MOTION_NO_HISTORY = 0, 1, 2
 MOTION_WORDS = 22
 NO_SHAPE = 0xFFFFFFFF
@@ -285,6 +288,41 @@ def bvh_wide_cost_host(built_shape, built_triangles, now_shape, now_triangles, f
     return built.value, now.value
 
 
+def bvh_morton_order_host(model_shape, triangles):
+    """srt_bvh_morton_order_host (host only): order[record] = triangle inside the model, by ascending (Morton code, index):
+    what BUILD_DEVICE sorts on the device."""
+    lib = load_library()
+    shape = np.zeros(1, R.SHAPE)
+    shape[0] = model_shape
+    tris = R.as_records(triangles, R.TRIANGLE)
+    order = np.zeros(int(shape[0]["num_triangles"]), np.uint32)
+    rc = lib.srt_bvh_morton_order_host(_ptr(shape), _ptr(tris), len(tris), _ptr(order), len(order))
+    if rc:
+        raise SrtError(f"srt_bvh_morton_order_host failed ({rc})")
+    return order
+
+
+def bvh_morton_wide_host(model_shape, triangles):
+    """srt_bvh_morton_wide_host (host only): the hierarchy BUILD_DEVICE leaves on the device -- the balanced topology of the
+    model's count over the Morton order, boxes of the in-place refit: dict with blocks (relative to the model, leaf blocks
+    zero), dest, root, stack_need and cost (0.0: unknown)."""
+    lib = load_library()
+    shape = np.zeros(1, R.SHAPE)
+    shape[0] = model_shape
+    tris = R.as_records(triangles, R.TRIANGLE)
+    n, root, need, cost = C.c_size_t(0), C.c_uint32(0), C.c_uint32(0), C.c_double(0)
+    rc = lib.srt_bvh_morton_wide_host(_ptr(shape), _ptr(tris), len(tris), None, 0, None, 0, C.byref(n), None, None, None)
+    if rc:
+        raise SrtError(f"srt_bvh_morton_wide_host failed ({rc})")
+    blocks = np.zeros((n.value, 32), np.uint32)
+    dest = np.zeros(int(shape[0]["num_triangles"]), np.uint32)
+    rc = lib.srt_bvh_morton_wide_host(_ptr(shape), _ptr(tris), len(tris), _ptr(blocks), len(blocks), _ptr(dest), len(dest), C.byref(n),
+                                      C.byref(root), C.byref(need), C.byref(cost))
+    if rc:
+        raise SrtError(f"srt_bvh_morton_wide_host failed ({rc})")
+    return {"blocks": blocks, "dest": dest, "root": root.value, "stack_need": need.value, "cost": cost.value}
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("paths", "rays", "sky", "tri_tests", "tri_pass_u", "nan_pixels", "watchdog")]
 
@@ -426,6 +464,13 @@ def _bind(lib):
         lib.srt_acceleration_deform_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         lib.srt_bvh_refit_deformed_wide_host.argtypes = [vp, vp, vp, vp, sz, i, vp, sz, C.POINTER(sz), C.POINTER(C.c_uint32)]
         lib.srt_bvh_wide_cost_host.argtypes = [vp, vp, vp, vp, sz, i, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(lib, "srt_set_acceleration_build"):  # (likewise)
+        lib.srt_set_acceleration_build.argtypes = [vp, i, C.c_uint32]
+        lib.srt_group_set_acceleration_build.argtypes = [vp, i, C.c_uint32]
+        lib.srt_acceleration_build_info.argtypes = [vp, C.POINTER(C.c_uint64)]
+        lib.srt_last_build_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        lib.srt_bvh_morton_order_host.argtypes = [vp, vp, sz, vp, sz]
+        lib.srt_bvh_morton_wide_host.argtypes = [vp, vp, sz, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
         lib.srt_read_bvh_blocks.argtypes = [vp, vp, sz, C.POINTER(sz)]
     if hasattr(lib, "srt_gather"):
         lib.srt_comm_unique_id.argtypes = [vp]
@@ -776,6 +821,25 @@ class Tracer(_Denoise):
         self._check(self.lib.srt_acceleration_deform_info(self._h, out, C.byref(worst)))
         return {"models_kept": int(out[0]), "models_rebuilt": int(out[1]), "cost_launches": int(out[2]), "worst_ratio": worst.value}
 
+    def set_acceleration_build(self, mode, min_triangles=0):
+        """BUILD_HOST (the default) or BUILD_DEVICE: a model of at least min_triangles triangles that has no hierarchy to keep
+        gets the balanced topology over its Morton order, sorted on the device; applies at the next update_scene."""
+        self._check(self.lib.srt_set_acceleration_build(self._h, int(mode), int(min_triangles)))
+
+    def acceleration_build_info(self):
+        """Of the last update_scene: models built on the device, records sorted, build launches. Waits for the sorted order's
+        read-back only."""
+        out = (C.c_uint64 * 4)()
+        self._check(self.lib.srt_acceleration_build_info(self._h, out))
+        return dict(zip(("models", "records", "launches"), (int(v) for v in out)))
+
+    def last_build_kernel_ms(self):
+        """Device time from the first build launch of the last update_scene to the end of the refit behind it (needs
+        set_kernel_timers); blocking."""
+        a = C.c_float()
+        self._check(self.lib.srt_last_build_kernel_ms(self._h, C.byref(a)))
+        return a.value
+
     def acceleration_refit_info(self):
         """Of the last update_scene: models refitted on the device, inner blocks they requantised, refit launches."""
         out = (C.c_uint64 * 4)()
@@ -965,6 +1029,16 @@ class TracerGroup(_Denoise):
     def set_acceleration_deform(self, mode, rebuild_ratio=0.0):
         """Tracer.set_acceleration_deform on every member."""
         self._check(self.lib.srt_group_set_acceleration_deform(self._g, int(mode), float(rebuild_ratio)))
+
+    def set_acceleration_build(self, mode, min_triangles=0):
+        """Tracer.set_acceleration_build on every member."""
+        self._check(self.lib.srt_group_set_acceleration_build(self._g, int(mode), int(min_triangles)))
+
+    def member_build_info(self, i):
+        """Tracer.acceleration_build_info of member i."""
+        out = (C.c_uint64 * 4)()
+        self._check(self.lib.srt_acceleration_build_info(self.member(i), out))
+        return dict(zip(("models", "records", "launches"), (int(v) for v in out)))
 
     def member_deform_info(self, i):
         """Tracer.acceleration_deform_info of member i."""
