@@ -217,6 +217,31 @@ int srt_bvh_morton_order_host(const srt_shape *model, const srt_triangle *triang
  * model, leaf blocks zero; stack_need is at most 45); *cost = the hierarchy's cost (above; may be NULL). */
 int srt_bvh_morton_wide_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, uint32_t *blocks_out, size_t blocks_cap,
                              uint32_t *dest_out, size_t dest_cap, size_t *n_blocks, uint32_t *root, uint32_t *stack_need, double *cost);
+/* The ORDER SRT_BUILD_DEVICE lays the balanced topology over. SRT_BUILD_ORDER_MORTON, the default: the Morton order above, launch
+ * for launch what SRT_BUILD_DEVICE has always done. SRT_BUILD_ORDER_MEDIAN: the order the host's balanced tree is after, a
+ * median split on the widest centroid axis in every range, computed top-down on the device -- more launches (about 80 for 10^5
+ * triangles against 14) for a tree close to the host's balanced one instead of 2-3 times the SAH tree's cost (DESIGN.md has the
+ * figures). Everything behind the order is the same: the topology cached per count, the refit passes, the cost launch, the
+ * read-back. The definition, float32, unfused, in this order, with c = 0.5f * lo + 0.5f * hi of the unpadded box as above:
+ *   start from the identity order; for every range [b, e) of the balanced topology with n = e - b > 3, top-down (its halves
+ *   are [b, b + n / 2) and [b + n / 2, e)), before its halves are visited:
+ *     clo[a], chi[a] = min, max of c[a] over the range's finite triangles (FLT_MAX, -FLT_MAX without any); ext[a] = chi[a] - clo[a]
+ *     a = 0; for k = 1, 2: if (ext[k] > ext[a]) a = k
+ *     key = 0 where ext[a] is not a positive finite number, else with f = (c[a] - clo[a]) * (65536.0f / ext[a]):
+ *           f >= 65535 ? 65535 : (f > 0 ? (uint32_t)(int)f : 0); a non-finite triangle: 0x10000
+ *     the range is sorted STABLY by key
+ * A model of more than 1,024 << 15 = 33,554,432 triangles keeps the Morton order (the device's composite key has 32 bits).
+ * SRT_ERR_INVALID for another value. Takes effect at the next srt_update_scene; accepted and without effect under
+ * SRT_BUILD_HOST and SRT_ACCEL_NONE. srt_acceleration_build_info counts the launches actually enqueued, and
+ * srt_last_build_kernel_ms spans them. */
+#define SRT_BUILD_ORDER_MORTON 0
+#define SRT_BUILD_ORDER_MEDIAN 1
+int srt_set_acceleration_build_order(srt_tracer *t, int order);
+/* Host-only: srt_bvh_morton_order_host and srt_bvh_morton_wide_host for SRT_BUILD_ORDER_MEDIAN -- the order defined above, and
+ * the hierarchy the device leaves under it, bit for bit. */
+int srt_bvh_median_order_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, uint32_t *order_out, size_t order_cap);
+int srt_bvh_median_wide_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, uint32_t *blocks_out, size_t blocks_cap,
+                             uint32_t *dest_out, size_t dest_cap, size_t *n_blocks, uint32_t *root, uint32_t *stack_need, double *cost);
 /* Tests / inspection: the device's block array as the kernel walks it -- every model's blocks, absolute indices, leaf
  * blocks with their triangles. Blocking. Writes at most blocks_cap blocks of 32 dwords and always sets *n_blocks (0 without
  * SRT_ACCEL_BVH or without models); blocks_out may be NULL to only query. */
@@ -382,6 +407,7 @@ int srt_group_set_acceleration(srt_group *g, int mode);
 int srt_group_set_acceleration_refit(srt_group *g, int mode); /* srt_set_acceleration_refit on every member */
 int srt_group_set_acceleration_deform(srt_group *g, int mode, float rebuild_ratio); /* srt_set_acceleration_deform on every member */
 int srt_group_set_acceleration_build(srt_group *g, int mode, uint32_t min_triangles); /* srt_set_acceleration_build on every member (the scene is prepared once; every member sorts on its own device) */
+int srt_group_set_acceleration_build_order(srt_group *g, int order); /* srt_set_acceleration_build_order on every member */
 int srt_group_update_scene(srt_group *g, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
                            const srt_material *materials, size_t n_materials, const srt_scene_data *scene);
 int srt_group_clear_canvas(srt_group *g);

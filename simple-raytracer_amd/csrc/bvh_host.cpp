@@ -435,6 +435,38 @@ void BvhBuilder::morton_order(std::vector<uint32_t> &out) const {
 	out.resize(keys.size());
 	for (size_t r = 0; r < keys.size(); r++) out[r] = (uint32_t)keys[r];
 }
+uint32_t BvhBuilder::median_key(float c, float clo, float ext) {
+	if (!(ext > 0.0f) || !std::isfinite(ext)) return 0u;
+	const float f = (c - clo) * (65536.0f / ext);
+	return f >= 65535.0f ? 65535u : (f > 0.0f ? (uint32_t)(int)f : 0u);
+}
+void BvhBuilder::median_order(std::vector<uint32_t> &out) const {
+	const uint32_t n = (uint32_t)tris.size();
+	if (srt_build_median_levels(n) > SRT_BUILD_MEDIAN_MAX_LEVELS) return morton_order(out);
+	out.resize(n);
+	for (uint32_t r = 0; r < n; r++) out[r] = r; // (load() leaves tris in triangle order)
+	std::vector<uint32_t> keys(n);                // per triangle, of the range it is in
+	std::vector<std::pair<uint32_t, uint32_t>> todo;
+	todo.emplace_back(0u, n);
+	while (!todo.empty()) { // (a range reads what its ancestors left: the order among the ranges of a depth does not matter)
+		const uint32_t b = todo.back().first, e = todo.back().second, cnt = e - b;
+		todo.pop_back();
+		if (cnt <= SRT_BVH_LEAF_MAX) continue;
+		float clo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, chi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+		for (uint32_t r = b; r < e; r++) {
+			if (!is_finite[out[r]]) continue;
+			for (int a = 0; a < 3; a++) clo[a] = std::min(clo[a], tris[out[r]].c[a]), chi[a] = std::max(chi[a], tris[out[r]].c[a]);
+		}
+		float ext[3];
+		for (int a = 0; a < 3; a++) ext[a] = chi[a] - clo[a];
+		int a = 0;
+		for (int k = 1; k < 3; k++)
+			if (ext[k] > ext[a]) a = k;
+		for (uint32_t r = b; r < e; r++) keys[out[r]] = is_finite[out[r]] ? median_key(tris[out[r]].c[a], clo[a], ext[a]) : MEDIAN_NONFINITE;
+		std::stable_sort(out.begin() + b, out.begin() + e, [&keys](uint32_t x, uint32_t y) { return keys[x] < keys[y]; });
+		todo.emplace_back(b, b + cnt / 2), todo.emplace_back(b + cnt / 2, e);
+	}
+}
 static BvhBuilder::Stats balanced_into(std::vector<BvhNode> &out, uint32_t b, uint32_t e, uint32_t depth) {
 	BvhBuilder::Stats st;
 	const uint32_t self = (uint32_t)out.size(), n = e - b;
@@ -481,6 +513,19 @@ void BvhCacheEntry::build_morton(const srt_model &m, const srt_triangle *all) {
 		BvhBuilder bb(none, unused);
 		bb.load(m, all);
 		bb.morton_order(order);
+	}
+	order_pending = false;
+	refit_in_place(m, all); // (clears `stale`)
+	cost_built = cost_now;
+}
+void BvhCacheEntry::build_median(const srt_model &m, const srt_triangle *all) {
+	set_balanced_topology(m.num_triangles);
+	{
+		std::vector<BvhNode> none;
+		std::vector<uint32_t> unused;
+		BvhBuilder bb(none, unused);
+		bb.load(m, all);
+		bb.median_order(order);
 	}
 	order_pending = false;
 	refit_in_place(m, all); // (clears `stale`)
@@ -649,6 +694,43 @@ int srt_bvh_morton_wide_host(const srt_shape *model, const srt_triangle *triangl
 	try {
 		BvhCacheEntry ent;
 		if (m.num_triangles > 0) ent.build_morton(m, triangles);
+		*n_blocks = ent.wide.blocks.size() / 32;
+		if (root) *root = ent.wide.root;
+		if (stack_need) *stack_need = ent.wide.need;
+		if (cost) *cost = ent.cost_built;
+		if (blocks_out && !ent.wide.blocks.empty()) memcpy(blocks_out, ent.wide.blocks.data(), std::min(ent.wide.blocks.size(), blocks_cap * 32) * sizeof(uint32_t));
+		if (dest_out && !ent.wide.dest.empty()) memcpy(dest_out, ent.wide.dest.data(), std::min(ent.wide.dest.size(), dest_cap) * sizeof(uint32_t));
+	} catch (...) { // std::bad_alloc: no C++ exception may cross the C ABI
+		return SRT_ERR_INVALID;
+	}
+	return SRT_OK;
+}
+
+int srt_bvh_median_order_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, uint32_t *order_out, size_t order_cap) {
+	if (!model || model->type != SRT_SHAPE_MODEL || (n_triangles && !triangles)) return SRT_ERR_INVALID;
+	const srt_model &m = model->shape.model;
+	if ((uint64_t)m.triangle_index + m.num_triangles > n_triangles || m.num_triangles > 0x0fffffffu) return SRT_ERR_INVALID;
+	try {
+		std::vector<BvhNode> none;
+		std::vector<uint32_t> order;
+		BvhBuilder bb(none, order);
+		bb.load(m, triangles);
+		bb.median_order(order);
+		if (order_out && !order.empty()) memcpy(order_out, order.data(), std::min(order.size(), order_cap) * sizeof(uint32_t));
+	} catch (...) { // std::bad_alloc: no C++ exception may cross the C ABI
+		return SRT_ERR_INVALID;
+	}
+	return SRT_OK;
+}
+
+int srt_bvh_median_wide_host(const srt_shape *model, const srt_triangle *triangles, size_t n_triangles, uint32_t *blocks_out, size_t blocks_cap,
+                             uint32_t *dest_out, size_t dest_cap, size_t *n_blocks, uint32_t *root, uint32_t *stack_need, double *cost) {
+	if (!model || !n_blocks || model->type != SRT_SHAPE_MODEL || (n_triangles && !triangles)) return SRT_ERR_INVALID;
+	const srt_model &m = model->shape.model;
+	if ((uint64_t)m.triangle_index + m.num_triangles > n_triangles || m.num_triangles > 0x0fffffffu) return SRT_ERR_INVALID;
+	try {
+		BvhCacheEntry ent;
+		if (m.num_triangles > 0) ent.build_median(m, triangles);
 		*n_blocks = ent.wide.blocks.size() / 32;
 		if (root) *root = ent.wide.root;
 		if (stack_need) *stack_need = ent.wide.need;

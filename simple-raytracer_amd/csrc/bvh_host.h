@@ -106,6 +106,15 @@ struct BvhBuilder {
 	// without its nth_element -- halves at b + n / 2 down to leaves of at most SRT_BVH_LEAF_MAX records, skip links as run()
 	// leaves them. The boxes are zero: a refit fills them in.
 	static Stats balanced_topology(uint32_t count, std::vector<BvhNode> &out);
+	// ---- the median-split order (include/srt_abi.h SRT_BUILD_ORDER_MEDIAN; bvh_build.hip computes the same, bit for bit) ----
+	// 17 bits: the centroid's cell of 65536 between a range's centroid extents `clo` and clo + ext on the range's widest axis; an
+	// extent that is not a positive finite number gives cell 0. float32, unfused, in this order.
+	static uint32_t median_key(float c, float clo, float ext);
+	static constexpr uint32_t MEDIAN_NONFINITE = 0x10000u; // a triangle with a non-finite box: behind every finite one of its range
+	// after load(): from the identity, every range of the balanced topology with more than SRT_BVH_LEAF_MAX records sorted stably
+	// by key before its halves are visited. A model with too many triangles for the device's composite key
+	// (device_types.h srt_build_median_levels) gets the Morton order.
+	void median_order(std::vector<uint32_t> &out) const;
 };
 
 // One model instance's hierarchy with indices relative to its own first node / first record, kept
@@ -131,6 +140,8 @@ struct BvhCacheEntry {
 	// The hierarchy SRT_BUILD_DEVICE makes, on the host: `order` = the Morton order, the balanced topology of the model's count
 	// folded with balanced = true, the boxes of refit_in_place over that order.
 	void build_morton(const srt_model &m, const srt_triangle *all);
+	// the same over the median-split order (SRT_BUILD_ORDER_MEDIAN)
+	void build_median(const srt_model &m, const srt_triangle *all);
 	// The part of it that depends on the count alone: nodes and `wide` of the balanced topology (boxes zero, inner blocks not
 	// yet quantised), `order` the identity, stale, order_pending. The device sorts and refits (scene_prep.cpp, srt_abi.hip).
 	void set_balanced_topology(uint32_t n);

@@ -366,11 +366,38 @@ struct BuildParams {
 	uint32_t *vals[2];       /* likewise the triangle indices */
 	uint32_t *table;
 	uint32_t *order;         /* the scene's order array: the last pass writes the models' record ranges */
+	/* SRT_BUILD_ORDER_MEDIAN only (else NULL): per model the first of its slots in `ranges`, and per slot lo.xyz, hi.xyz of a range's
+	 * centroids as order-preserving integers, uploaded as the empty box; the slot of range i of depth L is (1 << L) - 1 + i */
+	const uint32_t *range_first;
+	uint32_t *ranges;
 };
 #define SRT_BUILD_TILES(records) (((uint32_t)(records) + SRT_BUILD_TILE - 1u) / SRT_BUILD_TILE)
 /* the codes into keys[0]; then the sort: per pass a histogram, a scan and a scatter launch. Return the launches enqueued. */
 int srt_launch_build_keys(const BuildParams &p, uint32_t num_models, uint32_t max_records, void *stream);
 int srt_launch_build_sort(const BuildParams &p, uint32_t num_models, uint32_t max_records, void *stream);
+/* The median-split order (include/srt_abi.h SRT_BUILD_ORDER_MEDIAN): the balanced topology's ranges sorted by a 17-bit key along
+ * their widest centroid axis, top-down. While a depth's largest range, ceil(n / 2^L), exceeds SRT_BUILD_LOCAL the depth is a
+ * GLOBAL level: an extents launch, a key launch and the sort's passes over the composite (range << 17 | key); the remaining
+ * depths run in one launch, one workgroup per range, in LDS. A model of more than SRT_BUILD_LOCAL << 15 triangles would need a
+ * sixteenth global level (the composite has 32 bits): it keeps the Morton order. */
+#define SRT_BUILD_LOCAL 1024u /* the largest range the local launch takes (= SRT_BUILD_TILE: 256 threads, four records each) */
+#define SRT_BUILD_MEDIAN_MAX_LEVELS 15u
+#define SRT_BUILD_MEDIAN_KEY_BITS 17u /* cells 0 .. 65535, and 0x10000 for a non-finite triangle */
+#ifdef __HIPCC__
+#define SRT_BUILD_HD __host__ __device__
+#else
+#define SRT_BUILD_HD
+#endif
+/* the global levels of a model of n triangles; SRT_BUILD_MEDIAN_MAX_LEVELS + 1 = too many */
+static inline SRT_BUILD_HD uint32_t srt_build_median_levels(uint32_t n) {
+	uint32_t levels = 0;
+	while (levels <= SRT_BUILD_MEDIAN_MAX_LEVELS && n > (SRT_BUILD_LOCAL << levels)) levels++;
+	return levels;
+}
+/* the radix passes of global level L */
+static inline SRT_BUILD_HD uint32_t srt_build_median_passes(uint32_t level) { return (SRT_BUILD_MEDIAN_KEY_BITS + level + 7u) / 8u; }
+/* All of it for models[0 .. num_models): the order into p.order. Returns the launches enqueued. */
+int srt_launch_build_median(const BuildParams &p, uint32_t num_models, uint32_t max_records, void *stream);
 void srt_launch_resolve(const ResolveParams &p, void *stream);
 void srt_launch_selftest(unsigned long long *out16, uint32_t stride, void *stream);
 void srt_launch_selftest_rare(int what, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, unsigned long long *mismatches, void *stream);

@@ -207,6 +207,7 @@ void srt_destroy(srt_tracer *t) {
 	t->build_models.release();
 	t->build_extents.release();
 	t->build_table.release();
+	t->build_ranges_dev.release();
 	for (int k = 0; k < 2; k++) t->build_keys[k].release(), t->build_vals[k].release();
 	if (t->build_order_host) (void)hipHostFree(t->build_order_host);
 	if (t->ev_build_done) (void)hipEventDestroy(t->ev_build_done);
@@ -371,7 +372,10 @@ static int build_consume(srt_tracer *t, BvhCache *cache) {
 }
 
 // SRT_BUILD_DEVICE, before the pre-pass: the order of the models this call builds (bvh_build.hip) -- their extents over the
-// identity order the upload carries, a Morton code per record, the sort, whose last pass writes the scene's order array
+// identity order the upload carries, a Morton code per record, the sort, whose last pass writes the scene's order array. Under
+// SRT_BUILD_ORDER_MEDIAN the median-split launches instead (they take their extents per range, of the centroids); a model too
+// large for them keeps the Morton order: then the Morton launches run first, over every model, and the median ones overwrite
+// the order of the models they take.
 static int build_on_device(srt_tracer *t, const ScenePrep &sp) {
 	for (uint64_t &v : t->build_info) v = 0;
 	t->build_timed = false;
@@ -389,6 +393,28 @@ static int build_on_device(srt_tracer *t, const ScenePrep &sp) {
 	}
 	SRT_HIP(t, hipMemcpyAsync(t->build_models.ptr, sp.build_models.data(), n_models * sizeof(RefitModel), hipMemcpyHostToDevice, t->stream));
 	SRT_HIP(t, hipMemcpyAsync(t->build_extents.ptr, sp.build_extents.data(), sp.build_extents.size() * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream));
+	const bool median = t->build_order == SRT_BUILD_ORDER_MEDIAN;
+	bool morton = !median;
+	uint32_t median_max_records = 0;
+	if (median) { // per model its first range slot, then the slots: (2^levels - 1) empty boxes per model
+		std::vector<uint32_t> &up = t->build_ranges_host;
+		up.assign(n_models, 0u);
+		uint32_t slots = 0;
+		for (uint32_t k = 0; k < n_models; k++) {
+			const uint32_t n = sp.build_models[k].num_records, levels = srt_build_median_levels(n);
+			up[k] = slots;
+			if (levels > SRT_BUILD_MEDIAN_MAX_LEVELS) {
+				morton = true;
+				continue;
+			}
+			slots += (1u << levels) - 1u;
+			if (n > median_max_records) median_max_records = n;
+		}
+		for (uint32_t k = 0; k < slots; k++)
+			up.insert(up.end(), {SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_HI_INIT, SRT_REFIT_EXT_HI_INIT, SRT_REFIT_EXT_HI_INIT});
+		SRT_HIP(t, t->build_ranges_dev.reserve(up.size()));
+		SRT_HIP(t, hipMemcpyAsync(t->build_ranges_dev.ptr, up.data(), up.size() * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream));
+	}
 	if (t->timers_in_render) {
 		for (hipEvent_t &ev : t->ev_build)
 			if (!ev) SRT_HIP(t, hipEventCreate(&ev));
@@ -409,9 +435,15 @@ static int build_on_device(srt_tracer *t, const ScenePrep &sp) {
 	for (int k = 0; k < 2; k++) bp.keys[k] = t->build_keys[k].ptr, bp.vals[k] = t->build_vals[k].ptr;
 	bp.table = t->build_table.ptr;
 	bp.order = t->bvh_order.ptr;
-	int launches = srt_launch_refit_extents(rp, n_models, sp.build_max_records, t->stream);
-	launches += srt_launch_build_keys(bp, n_models, sp.build_max_records, t->stream);
-	launches += srt_launch_build_sort(bp, n_models, sp.build_max_records, t->stream);
+	bp.range_first = median ? t->build_ranges_dev.ptr : nullptr;
+	bp.ranges = median ? t->build_ranges_dev.ptr + n_models : nullptr;
+	int launches = 0;
+	if (morton) {
+		launches += srt_launch_refit_extents(rp, n_models, sp.build_max_records, t->stream);
+		launches += srt_launch_build_keys(bp, n_models, sp.build_max_records, t->stream);
+		launches += srt_launch_build_sort(bp, n_models, sp.build_max_records, t->stream);
+	}
+	if (median) launches += srt_launch_build_median(bp, n_models, median_max_records, t->stream);
 	SRT_HIP(t, hipGetLastError());
 	uint64_t sorted = 0;
 	for (const RefitModel &rm : sp.build_models) sorted += rm.num_records;
@@ -624,6 +656,7 @@ int srt_update_scene_many(srt_tracer *const *members, size_t n_members, const sr
 			members[begun]->refit_mode = members[0]->refit_mode;
 			members[begun]->deform_mode = members[0]->deform_mode, members[begun]->deform_rebuild_ratio = members[0]->deform_rebuild_ratio;
 			members[begun]->build_mode = members[0]->build_mode, members[begun]->build_min_triangles = members[0]->build_min_triangles;
+			members[begun]->build_order = members[0]->build_order;
 			rc = upload_scene_begin(members[begun], sp, shapes, n_shapes, triangles, n_triangles, n_materials);
 		}
 		if (rc != SRT_OK) { // what was enqueued on the members before the failing one still reads the host arrays: let it finish
@@ -1320,6 +1353,13 @@ int srt_set_acceleration_build(srt_tracer *t, int mode, uint32_t min_triangles) 
 	if (mode != SRT_BUILD_HOST && mode != SRT_BUILD_DEVICE) return fail(t, SRT_ERR_INVALID, "srt_set_acceleration_build: unknown mode");
 	t->build_mode = mode;
 	t->build_min_triangles = min_triangles;
+	return SRT_OK;
+}
+
+int srt_set_acceleration_build_order(srt_tracer *t, int order) {
+	if (!t) return SRT_ERR_INVALID;
+	if (order != SRT_BUILD_ORDER_MORTON && order != SRT_BUILD_ORDER_MEDIAN) return fail(t, SRT_ERR_INVALID, "srt_set_acceleration_build_order: unknown order");
+	t->build_order = order;
 	return SRT_OK;
 }
 

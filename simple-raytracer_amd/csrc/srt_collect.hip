@@ -544,6 +544,12 @@ int srt_group_set_acceleration_build(srt_group *g, int mode, uint32_t min_triang
 	return SRT_OK;
 }
 
+int srt_group_set_acceleration_build_order(srt_group *g, int order) {
+	if (!g) return SRT_ERR_INVALID;
+	SRT_EACH(g, srt_set_acceleration_build_order(t_, order));
+	return SRT_OK;
+}
+
 int srt_group_update_scene(srt_group *g, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
                            const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
 	if (!g) return SRT_ERR_INVALID;

@@ -93,6 +93,11 @@ struct srt_tracer {
 	// array and the event behind the copy; build_pending until somebody has waited for it (build_consume in srt_abi.hip)
 	int build_mode = SRT_BUILD_HOST;
 	uint32_t build_min_triangles = 0;
+	int build_order = SRT_BUILD_ORDER_MORTON; // srt_set_acceleration_build_order
+	// SRT_BUILD_ORDER_MEDIAN only: per built model its first range slot, then six dwords per range (device_types.h BuildParams), and
+	// the host vector it is uploaded from
+	DevBuf<uint32_t> build_ranges_dev;
+	std::vector<uint32_t> build_ranges_host;
 	DevBuf<RefitModel> build_models;
 	DevBuf<uint32_t> build_extents, build_keys[2], build_vals[2], build_table;
 	uint64_t build_info[4] = {0, 0, 0, 0};

@@ -175,6 +175,11 @@ class Tracer {
 	void set_acceleration_build(int mode, uint32_t min_triangles = 0) {
 		check(group ? srt_group_set_acceleration_build(group, mode, min_triangles) : srt_set_acceleration_build(handle, mode, min_triangles));
 	}
+	// SRT_BUILD_ORDER_MORTON / SRT_BUILD_ORDER_MEDIAN: the order SRT_BUILD_DEVICE lays the balanced topology over (the next
+	// update_scene on; without effect under SRT_BUILD_HOST)
+	void set_acceleration_build_order(int order) {
+		check(group ? srt_group_set_acceleration_build_order(group, order) : srt_set_acceleration_build_order(handle, order));
+	}
 	// {models built on the device by the last update, records sorted, build launches, 0} (a group: its first member's)
 	void acceleration_build_info(uint64_t out[4]) { check(srt_acceleration_build_info(group ? srt_group_tracer(group, 0) : handle, out)); }
 	/// The edge-aware denoiser (srt_set_denoise): iterations < 0 turns it off, else it is on with srt_denoise_defaults()

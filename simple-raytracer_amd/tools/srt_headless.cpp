@@ -5,7 +5,7 @@
 //
 //   srt_headless [--scene spheres|meshes|empty] [--obj f.obj]... [--stl f.stl]...
 //                [--width W --height H --spp S --bounces B --frames N --time T]
-//                [--obj-materials] [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--demodulate] [--temporal] [--move DX]
+//                [--obj-materials] [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--demodulate] [--temporal] [--move DX]
 // --denoise K: the frames go through the edge-aware denoiser with K a-trous passes (Tracer::set_denoise; with --gpus N the
 //                members gather the filter's inputs with the frame and device 0 filters: the same bytes as on one device)
 // --demodulate: with --denoise, the passes filter colour / first-hit albedo (Tracer::set_denoise_demodulation); an error without it
@@ -124,6 +124,7 @@ int main(int argc, char **argv) {
 	bool moving = false;
 	bool bvh_build_device = false;
 	uint32_t bvh_build_min = 0;
+	int bvh_order = SRT_BUILD_ORDER_MORTON;
 	for (int i = 1; i < argc; i++) {
 		std::string a = argv[i];
 		auto next = [&]() -> const char * {
@@ -157,6 +158,15 @@ int main(int argc, char **argv) {
 				return 2;
 			}
 		}
+		else if (a == "--bvh-order") { // morton | median
+			const std::string v = next();
+			if (v == "morton") bvh_order = SRT_BUILD_ORDER_MORTON;
+			else if (v == "median") bvh_order = SRT_BUILD_ORDER_MEDIAN;
+			else {
+				std::cerr << "--bvh-order takes morton or median\n";
+				return 2;
+			}
+		}
 		else if (a == "--obj-materials") obj_materials = true;
 		else if (a == "--gpus") gpus = std::atoi(next());
 		else if (a == "--pipelined") pipelined = true;
@@ -172,7 +182,7 @@ int main(int argc, char **argv) {
 		else if (a == "--move-shape") move_shape = std::atoi(next()), shape_move = std::strtof(next(), nullptr);
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
-			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--gpus N] [--pipelined] [--skybox sky.ppm] "
+			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
 			             "[--denoise K] [--demodulate] [--temporal] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
@@ -294,6 +304,7 @@ int main(int argc, char **argv) {
 	// ---- tracer set-up, as src/main.cpp:114-126 ----
 	Tracer tracer(width, height, 0, gpus); // --gpus N: one Tracer over N devices (rows split, one RCCL gather per frame)
 	if (bvh) tracer.set_acceleration(SRT_ACCEL_BVH);
+	tracer.set_acceleration_build_order(bvh_order); // (of --bvh-build device; else no effect)
 	if (bvh_build_device) tracer.set_acceleration_build(SRT_BUILD_DEVICE, bvh_build_min); // (models of at least MIN triangles; without --bvh: no effect)
 	if (denoise >= 0) tracer.set_denoise(denoise);
 	if (demodulate) tracer.set_denoise_demodulation();

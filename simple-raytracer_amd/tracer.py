@@ -51,12 +51,15 @@ ABI_SYMBOLS = [
     "srt_bvh_refit_deformed_wide_host", "srt_bvh_wide_cost_host",
     "srt_set_acceleration_build", "srt_group_set_acceleration_build", "srt_acceleration_build_info", "srt_last_build_kernel_ms",
     "srt_bvh_morton_order_host", "srt_bvh_morton_wide_host",
+    "srt_set_acceleration_build_order", "srt_group_set_acceleration_build_order", "srt_bvh_median_order_host", "srt_bvh_median_wide_host",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
 REFIT_HOST, REFIT_DEVICE = 0, 1
 DEFORM_REBUILD, DEFORM_REFIT = 0, 1
 BUILD_HOST, BUILD_DEVICE = 0, 1
+BUILD_ORDER_MORTON, BUILD_ORDER_MEDIAN = 0, 1
+BUILD_LOCAL = 1024  # csrc/device_types.h SRT_BUILD_LOCAL: the largest range the median order's local launch takes
 MOTION_STATIC, MOTION_MOVED, MOTION_NO_HISTORY = 0, 1, 2
 MOTION_WORDS = 22
 NO_SHAPE = 0xFFFFFFFF
@@ -288,7 +291,7 @@ def bvh_wide_cost_host(built_shape, built_triangles, now_shape, now_triangles, f
     return built.value, now.value
 
 
-def bvh_morton_order_host(model_shape, triangles):
+def bvh_morton_order_host(model_shape, triangles, _call="srt_bvh_morton_order_host"):
     """srt_bvh_morton_order_host (host only): order[record] = triangle inside the model, by ascending (Morton code, index):
     what BUILD_DEVICE sorts on the device."""
     lib = load_library()
@@ -296,13 +299,19 @@ def bvh_morton_order_host(model_shape, triangles):
     shape[0] = model_shape
     tris = R.as_records(triangles, R.TRIANGLE)
     order = np.zeros(int(shape[0]["num_triangles"]), np.uint32)
-    rc = lib.srt_bvh_morton_order_host(_ptr(shape), _ptr(tris), len(tris), _ptr(order), len(order))
+    rc = getattr(lib, _call)(_ptr(shape), _ptr(tris), len(tris), _ptr(order), len(order))
     if rc:
-        raise SrtError(f"srt_bvh_morton_order_host failed ({rc})")
+        raise SrtError(f"{_call} failed ({rc})")
     return order
 
 
-def bvh_morton_wide_host(model_shape, triangles):
+def bvh_median_order_host(model_shape, triangles):
+    """srt_bvh_median_order_host (host only): order[record] = triangle inside the model in the median-split order: what
+    BUILD_DEVICE computes on the device under BUILD_ORDER_MEDIAN."""
+    return bvh_morton_order_host(model_shape, triangles, _call="srt_bvh_median_order_host")
+
+
+def bvh_morton_wide_host(model_shape, triangles, _call="srt_bvh_morton_wide_host"):
     """srt_bvh_morton_wide_host (host only): the hierarchy BUILD_DEVICE leaves on the device -- the balanced topology of the
     model's count over the Morton order, boxes of the in-place refit: dict with blocks (relative to the model, leaf blocks
     zero), dest, root, stack_need and cost (0.0: unknown)."""
@@ -311,16 +320,22 @@ def bvh_morton_wide_host(model_shape, triangles):
     shape[0] = model_shape
     tris = R.as_records(triangles, R.TRIANGLE)
     n, root, need, cost = C.c_size_t(0), C.c_uint32(0), C.c_uint32(0), C.c_double(0)
-    rc = lib.srt_bvh_morton_wide_host(_ptr(shape), _ptr(tris), len(tris), None, 0, None, 0, C.byref(n), None, None, None)
+    call = getattr(lib, _call)
+    rc = call(_ptr(shape), _ptr(tris), len(tris), None, 0, None, 0, C.byref(n), None, None, None)
     if rc:
-        raise SrtError(f"srt_bvh_morton_wide_host failed ({rc})")
+        raise SrtError(f"{_call} failed ({rc})")
     blocks = np.zeros((n.value, 32), np.uint32)
     dest = np.zeros(int(shape[0]["num_triangles"]), np.uint32)
-    rc = lib.srt_bvh_morton_wide_host(_ptr(shape), _ptr(tris), len(tris), _ptr(blocks), len(blocks), _ptr(dest), len(dest), C.byref(n),
-                                      C.byref(root), C.byref(need), C.byref(cost))
+    rc = call(_ptr(shape), _ptr(tris), len(tris), _ptr(blocks), len(blocks), _ptr(dest), len(dest), C.byref(n), C.byref(root), C.byref(need), C.byref(cost))
     if rc:
-        raise SrtError(f"srt_bvh_morton_wide_host failed ({rc})")
+        raise SrtError(f"{_call} failed ({rc})")
     return {"blocks": blocks, "dest": dest, "root": root.value, "stack_need": need.value, "cost": cost.value}
+
+
+def bvh_median_wide_host(model_shape, triangles):
+    """srt_bvh_median_wide_host (host only): bvh_morton_wide_host for BUILD_ORDER_MEDIAN -- the same topology over the
+    median-split order."""
+    return bvh_morton_wide_host(model_shape, triangles, _call="srt_bvh_median_wide_host")
 
 
 class Counters(C.Structure):
@@ -472,6 +487,11 @@ def _bind(lib):
         lib.srt_bvh_morton_order_host.argtypes = [vp, vp, sz, vp, sz]
         lib.srt_bvh_morton_wide_host.argtypes = [vp, vp, sz, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
         lib.srt_read_bvh_blocks.argtypes = [vp, vp, sz, C.POINTER(sz)]
+    if hasattr(lib, "srt_set_acceleration_build_order"):  # (likewise)
+        lib.srt_set_acceleration_build_order.argtypes = [vp, i]
+        lib.srt_group_set_acceleration_build_order.argtypes = [vp, i]
+        lib.srt_bvh_median_order_host.argtypes = lib.srt_bvh_morton_order_host.argtypes
+        lib.srt_bvh_median_wide_host.argtypes = lib.srt_bvh_morton_wide_host.argtypes
     if hasattr(lib, "srt_gather"):
         lib.srt_comm_unique_id.argtypes = [vp]
         lib.srt_comm_init.argtypes = [vp, vp, i, i]
@@ -826,6 +846,12 @@ class Tracer(_Denoise):
         gets the balanced topology over its Morton order, sorted on the device; applies at the next update_scene."""
         self._check(self.lib.srt_set_acceleration_build(self._h, int(mode), int(min_triangles)))
 
+    def set_acceleration_build_order(self, order):
+        """BUILD_ORDER_MORTON (the default) or BUILD_ORDER_MEDIAN: the order BUILD_DEVICE lays the balanced topology over -- the
+        30-bit Morton order, or every range of the topology sorted along its widest centroid axis, top-down (more launches, a
+        tree close to the host's balanced one); applies at the next update_scene, without effect under BUILD_HOST."""
+        self._check(self.lib.srt_set_acceleration_build_order(self._h, int(order)))
+
     def acceleration_build_info(self):
         """Of the last update_scene: models built on the device, records sorted, build launches. Waits for the sorted order's
         read-back only."""
@@ -1033,6 +1059,10 @@ class TracerGroup(_Denoise):
     def set_acceleration_build(self, mode, min_triangles=0):
         """Tracer.set_acceleration_build on every member."""
         self._check(self.lib.srt_group_set_acceleration_build(self._g, int(mode), int(min_triangles)))
+
+    def set_acceleration_build_order(self, order):
+        """Tracer.set_acceleration_build_order on every member."""
+        self._check(self.lib.srt_group_set_acceleration_build_order(self._g, int(order)))
 
     def member_build_info(self, i):
         """Tracer.acceleration_build_info of member i."""
