@@ -1,6 +1,6 @@
 """What the device-build tests share (tests/test_bvh_morton_host.py, tests/test_gpu_bvh_build.py): the meshes -- the models of
 tests/bvh_refit_cases.py, their with_nan and flattened variants of tests/bvh_deform_cases.py, prefixes of n6k at the sort's
-sizes, a mesh whose centroids coincide -- and a numpy statement of the Morton code of include/srt_abi.h (SRT_BUILD_DEVICE):
+sizes, prefixes of the 262,812-triangle n262k around 1,024 << 8, a mesh whose centroids coincide -- and a numpy statement of the Morton code of include/srt_abi.h (SRT_BUILD_DEVICE):
 float32 operations in the builder's order, from the raw triangles and a transform alone. A plain module, not a test module."""
 import functools
 
@@ -14,17 +14,20 @@ NONFINITE = 0x40000000
 TILE = 1024  # csrc/device_types.h SRT_BUILD_TILE: records per workgroup of the sort, four rounds of 256
 # a wave (64, 65), a round of the scatter (256, 257), one tile (1024, 1025), two tiles (2048, 2049)
 SORT_SIZES = [64, 65, 256, 257, TILE, TILE + 1, 2 * TILE, 2 * TILE + 1]
+BIG = "n262k"  # blob_mesh(363, 363): 262,812 triangles, the q<count> prefixes' mesh
 VARIANTS = {"base": lambda t: t, "with_nan": D.with_nan, "flattened": D.flattened}
 
 
 @functools.lru_cache(maxsize=None)
 def mesh(name, variant="base"):
-    """name: a model of tests/bvh_refit_cases.py, p<count> = the first <count> triangles of n6k, or same<count> = <count>
-    copies of one triangle (every centroid the same)"""
+    """name: a model of tests/bvh_refit_cases.py, p<count> = the first <count> triangles of n6k, q<count> = the first <count> of
+    n262k, or same<count> = <count> copies of one triangle (every centroid the same)"""
     if name.startswith("same"):
         tris = np.repeat(D.base("n1"), int(name[4:]))
     elif name.startswith("p"):
         tris = D.base("n6k")[:int(name[1:])].copy()
+    elif name.startswith("q"):
+        tris = D.base(BIG)[:int(name[1:])].copy()
     else:
         tris = D.base(name)
     return VARIANTS[variant](tris)

@@ -1,7 +1,8 @@
-"""What the median-order tests share (tests/test_bvh_median_host.py, tests/test_gpu_bvh_build_median.py): the case meshes, a numpy
-statement of the order of include/srt_abi.h (SRT_BUILD_ORDER_MEDIAN) -- float32, level by level, np.argsort(kind="stable") --
-and the number of launches the device needs, stated from SRT_BUILD_LOCAL and the count alone. A plain module, not a test
-module."""
+"""What the median-order tests share (tests/test_bvh_median_host.py, tests/test_gpu_bvh_build_median.py,
+tests/test_gpu_bvh_build_scale.py): the case meshes, a numpy statement of the order of include/srt_abi.h (SRT_BUILD_ORDER_MEDIAN) --
+float32, level by level, np.argsort(kind="stable") --, the same statement with a depth's ranges taken at once for the counts at
+which the loop takes too long, and the number of launches the device needs, stated from SRT_BUILD_LOCAL and the count alone. A
+plain module, not a test module."""
 import numpy as np
 
 import bvh_build_cases as B
@@ -19,6 +20,10 @@ assert LOCAL == 1024
 PREFIXES = [1, 3, 4, 5, 7, 8, 64, 65, 257, LOCAL - 1, LOCAL, LOCAL + 1, 2 * LOCAL, 2 * LOCAL + 1, 4 * LOCAL + 3]
 SAME = ["same257", f"same{LOCAL + 1}"]
 # (model, variant): the prefixes, n6k itself (three global levels, ragged everywhere), hostile variants, coinciding centroids
+# the prefixes of n262k (tests/bvh_build_cases.py BIG): eight global levels with every range exactly LOCAL and three passes at each --
+# the last count before the change; nine levels, the ninth of four passes over ranges of LOCAL and LOCAL + 1, ragged local ranges
+BIG_PREFIXES = [LOCAL << 8, (LOCAL << 8) + 3]
+BIG_CASES = [f"q{n}" for n in BIG_PREFIXES]
 CASES = ([(f"p{n}", "base") for n in PREFIXES] + [(m, v) for v in B.VARIANTS for m in D.SIZES if (v, m) != ("base", "n1")]
          + [(m, "base") for m in SAME])
 
@@ -72,6 +77,47 @@ def median_order(shape, tris):
             halves += [(b, b + cnt // 2), (b + cnt // 2, e)]
         ranges = halves
     return order
+
+
+def median_order_by_depth(shape, tris):
+    """median_order with every depth's ranges at once: the segments' minima and maxima (np.minimum.reduceat), every record's
+    key, and one np.lexsort by (range, key, position) -- the stable sort of every range. For the counts at which the loop over
+    ranges takes too long; tests/test_bvh_median_host.py holds it equal to median_order on every entry of CASES."""
+    lo, hi, finite = B.boxes(shape, tris)
+    n = len(lo)
+    with np.errstate(all="ignore"):
+        c = F(0.5) * lo + F(0.5) * hi
+    order = np.arange(n, dtype=np.uint32)
+    b, e = np.array([0], np.int64), np.array([n], np.int64)
+    while True:
+        keep = e - b > LEAF_MAX
+        b, e = b[keep], e[keep]
+        if not len(b):
+            return order
+        cnt = e - b
+        start = np.cumsum(cnt) - cnt  # of every range among the records of the ranges that are split
+        seg = np.repeat(np.arange(len(b)), cnt)
+        pos = np.arange(int(cnt.sum())) - start[seg] + b[seg]
+        idx = order[pos]
+        fin, cc = finite[idx], c[idx]
+        # (FLT_MAX and -FLT_MAX in place of a non-finite centroid: the loop's values for a range without a finite one, and
+        # no finite centroid lies beyond them)
+        clo = np.minimum.reduceat(np.where(fin[:, None], cc, FLT_MAX).astype(F), start, axis=0)
+        chi = np.maximum.reduceat(np.where(fin[:, None], cc, -FLT_MAX).astype(F), start, axis=0)
+        with np.errstate(all="ignore"):
+            ext = chi - clo
+            a = np.where(ext[:, 1] > ext[:, 0], 1, 0)
+            a = np.where(ext[:, 2] > ext[np.arange(len(b)), a], 2, a)
+            ea, la = ext[np.arange(len(b)), a], clo[np.arange(len(b)), a]
+            f = (cc[np.arange(len(pos)), a[seg]] - la[seg]) * (F(65536.0) / ea)[seg]
+            assert f.dtype == F
+            f = np.where(fin, f, F(0.0))
+            key = np.where(f >= F(65535.0), 65535, np.where(f > F(0.0), np.trunc(f), 0)).astype(np.uint32)
+            key = np.where(((ea > 0) & np.isfinite(ea))[seg], key, 0)
+        key = np.where(fin, key, NONFINITE).astype(np.uint32)
+        order[pos] = idx[np.lexsort((pos, key, seg))]
+        mid = b + cnt // 2
+        b, e = np.stack([b, mid], axis=1).ravel(), np.stack([mid, e], axis=1).ravel()
 
 
 def cost_meshes():

@@ -15,10 +15,13 @@ F = np.float32
 @functools.lru_cache(maxsize=None)
 def model_triangles(name):
     """n1, n3, n4, n13, n200: the first n triangles of a 240-triangle blob; n6k: blob_mesh(55, 56), 6,050 triangles (more
-    than 1,024 inner blocks); chain400: the geometric chain of tests/test_gpu_bvh.py, whose SAH tree is a chain (the
+    than 1,024 inner blocks); n262k: blob_mesh(363, 363), 262,812 triangles (its face loop is host Python: once per process);
+    chain400: the geometric chain of tests/test_gpu_bvh.py, whose SAH tree is a chain (the
     library's way into the balanced form); n200bad: n200 with a NaN vertex in one triangle and an inf vertex in another."""
     if name == "n6k":
         return S.blob_mesh(55, 56, seed=7, smooth=False)
+    if name == "n262k":  # 262,812 triangles: past 1,024 << 8, where a ninth global level of the median order begins
+        return S.blob_mesh(363, 363, seed=7, smooth=False)
     if name == "chain400":
         tris = np.zeros(400, R.TRIANGLE)
         for i in range(400):

@@ -5,9 +5,10 @@
 // The two host-only calls on small and hostile meshes (0, 1, 3, 4, 7, 200 and SRT_BUILD_LOCAL + 1 triangles; NaN and inf
 // vertices; one axis flat; every centroid the same; no finite triangle at all): the order is a permutation; in every range of
 // the balanced topology that is split, no key of the left half is above a key of the right half (the halves' own sorts permute
-// inside them: the range's extents, axis and keys are what they were when it was sorted); equal centroids give the identity; the hierarchy has the balanced
-// topology's counts and a stack need of at most 45; and its cost on a shuffled sheet is below the Morton hierarchy's. Exit
-// status 0 and "ok" when all of it holds.
+// inside them: the range's extents, axis and keys are what they were when it was sorted); equal centroids give the identity;
+// the hierarchy has the balanced topology's counts and a stack need of at most 45; the same on a sheet of 262,147 =
+// (SRT_BUILD_LOCAL << 8) + 3 triangles, the first count with a ninth global level on the device, with NaN and inf vertices
+// among them; and its cost on a shuffled sheet is below the Morton hierarchy's. Exit status 0 and "ok" when all of it holds.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -85,7 +86,8 @@ static void ranges_ascend(const BvhBuilder &bb, const std::vector<uint32_t> &ord
 	ranges_ascend(bb, order, b + n / 2, e);
 }
 
-static void both_calls(const char *name, const std::vector<srt_triangle> &t) {
+// sizing_call = false: the hierarchy's buffers are sized from the topology of the count, without the call that only counts
+static void both_calls(const char *name, const std::vector<srt_triangle> &t, bool sizing_call = true) {
 	const uint32_t n = (uint32_t)t.size();
 	const srt_shape s = model(0, n);
 	std::vector<uint32_t> order(n + 1, 0xdeadbeefu);
@@ -106,17 +108,17 @@ static void both_calls(const char *name, const std::vector<srt_triangle> &t) {
 		bb.load(s.shape.model, t.data());
 		ranges_ascend(bb, order, 0, n);
 	}
-	size_t n_blocks = 0;
+	BvhCacheEntry topo;
+	topo.set_balanced_topology(n);
+	size_t n_blocks = topo.wide.blocks.size() / 32;
 	uint32_t root = 0, need = 99;
 	double cost = -1.0;
-	CHECK(srt_bvh_median_wide_host(&s, t.data(), n, nullptr, 0, nullptr, 0, &n_blocks, &root, &need, &cost) == SRT_OK);
+	if (sizing_call) CHECK(srt_bvh_median_wide_host(&s, t.data(), n, nullptr, 0, nullptr, 0, &n_blocks, &root, &need, &cost) == SRT_OK);
 	std::vector<uint32_t> blocks(32 * n_blocks + 1, 0xdeadbeefu), dest(n + 1, 0xdeadbeefu);
-	CHECK(srt_bvh_median_wide_host(&s, t.data(), n, blocks.data(), n_blocks, dest.data(), n, &n_blocks, &root, &need, nullptr) == SRT_OK);
+	CHECK(srt_bvh_median_wide_host(&s, t.data(), n, blocks.data(), n_blocks, dest.data(), n, &n_blocks, &root, &need, sizing_call ? nullptr : &cost) == SRT_OK);
 	CHECK(blocks[32 * n_blocks] == 0xdeadbeefu && dest[n] == 0xdeadbeefu);
 	CHECK(need <= 45u && cost >= 0.0);
 	CHECK((root == SRT_BVH_NONE) == (n == 0));
-	BvhCacheEntry topo;
-	topo.set_balanced_topology(n);
 	CHECK(topo.wide.blocks.size() / 32 == n_blocks && topo.wide.root == root && topo.wide.need == need);
 	CHECK(std::equal(topo.wide.dest.begin(), topo.wide.dest.end(), dest.begin()));
 	printf("%s: %u triangles, %zu blocks, stack %u, cost %.6g\n", name, n, n_blocks, need, cost);
@@ -140,6 +142,14 @@ static void calls() {
 			both_calls("no finite triangle", none);
 		}
 	}
+	{ // nine global levels on the device: the sheet with three hostile triangles, its hierarchy built once (under the sanitizers
+		// each build takes seconds)
+		std::vector<srt_triangle> t = sheet(((size_t)SRT_BUILD_LOCAL << 8) + 3);
+		shuffle(t);
+		const size_t n = t.size();
+		t[n / 2].vertices[1].pos.x = NAN, t[n / 3].vertices[2].pos.y = INFINITY, t[0].vertices[0].pos.z = NAN;
+		both_calls("deep hostile", t, false);
+	}
 	std::vector<srt_triangle> same(37, sheet(1)[0]);
 	both_calls("same", same);
 	const srt_shape s = model(0, 37);
@@ -151,6 +161,7 @@ static void calls() {
 	size_t nb = 0;
 	CHECK(srt_bvh_median_wide_host(&beyond, same.data(), 37, nullptr, 0, nullptr, 0, &nb, nullptr, nullptr, nullptr) == SRT_ERR_INVALID);
 	CHECK(srt_build_median_levels(SRT_BUILD_LOCAL) == 0 && srt_build_median_levels(SRT_BUILD_LOCAL + 1) == 1 && srt_build_median_levels(99904) == 7);
+	CHECK(srt_build_median_levels(SRT_BUILD_LOCAL << 8) == 8 && srt_build_median_levels((SRT_BUILD_LOCAL << 8) + 3) == 9);
 	CHECK(srt_build_median_levels(SRT_BUILD_LOCAL << 15) == 15 && srt_build_median_levels((SRT_BUILD_LOCAL << 15) + 1) == 16 && srt_build_median_levels(0x0fffffffu) == 16);
 }
 

@@ -1,5 +1,6 @@
 """CPU: the host statement of the median-split order (include/srt_abi.h SRT_BUILD_ORDER_MEDIAN; no GPU involved). The order
-(srt_bvh_median_order_host) against a numpy restatement of the definition (tests/bvh_median_cases.py); the hierarchy
+(srt_bvh_median_order_host) against a numpy restatement of the definition (tests/bvh_median_cases.py), up to 262,147 triangles
+(nine global levels on the device) against the restatement by depth, itself held to the definition; the hierarchy
 (srt_bvh_median_wide_host): the Morton statement's topology with other leaves; its cost against the Morton tree's and the host's
 balanced tree's; the setter's validation without a handle; and the two calls on small and hostile meshes under AddressSanitizer
 and UndefinedBehaviorSanitizer as a stand-alone program (tests/csrc/bvh_median_check.cpp)."""
@@ -46,6 +47,26 @@ def test_order_is_the_definitions(model, variant):
     if variant == "with_nan" and n > M.LEAF_MAX:
         finite = B.boxes(shape, tris)[2]
         assert not finite.all() and not finite[got[-1]]  # (behind every finite triangle of every range that is sorted)
+
+
+@pytest.mark.parametrize("model,variant", CASES)
+def test_statement_by_depth_is_the_looped_one(model, variant):
+    """M.median_order_by_depth, which the counts past 2^18 are compared with, against the definition's loop over ranges"""
+    shape, tris = mesh_of(model, variant)
+    assert np.array_equal(M.median_order_by_depth(shape, tris), M.median_order(shape, tris))
+
+
+@pytest.mark.parametrize("model", M.BIG_CASES)
+def test_order_is_the_definitions_at_eight_and_nine_global_levels(model):
+    """262,144 triangles: 256 ranges of exactly SRT_BUILD_LOCAL; 262,147: a ninth level. The statement is the one by depth (the
+    loop over ranges takes tens of seconds here), held equal to the loop above."""
+    shape, tris = mesh_of(model, "base")
+    n = int(shape["num_triangles"])
+    assert n == int(model[1:]) and M.global_levels(n) == {M.LOCAL << 8: 8, (M.LOCAL << 8) + 3: 9}[n]
+    got = T.bvh_median_order_host(shape, tris)
+    assert np.array_equal(np.sort(got), np.arange(n))
+    assert np.array_equal(got, M.median_order_by_depth(shape, tris))
+    assert not np.array_equal(got, np.arange(n))
 
 
 @pytest.mark.parametrize("model,variant", CASES)
@@ -104,6 +125,9 @@ def test_launch_formula():
     """what tests/test_gpu_bvh_build_median.py expects of the counters, at the counts DESIGN.md names"""
     assert [M.global_levels(n) for n in (1, M.LOCAL, M.LOCAL + 1, 2 * M.LOCAL, 2 * M.LOCAL + 1, 4 * M.LOCAL + 3, 6050, 99904)] == [0, 0, 1, 1, 2, 3, 3, 7]
     assert M.launches(M.LOCAL) == 1 and M.launches(M.LOCAL + 1) == 12 and M.launches(6050) == 34 and M.launches(99904) == 78
+    # 1,024 << 8: the last count of eight levels, three passes each; three more: a ninth level, of four passes
+    assert [M.global_levels(n) for n in M.BIG_PREFIXES] == [8, 9] and M.BIG_PREFIXES == [262144, 262147]
+    assert M.launches(262144) == 8 * (2 + 9) + 1 and M.launches(262147) == 8 * (2 + 9) + (2 + 12) + 1
 
 
 def test_setters_refuse_without_a_handle():

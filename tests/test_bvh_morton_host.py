@@ -39,6 +39,15 @@ def test_order_is_the_definitions(model, variant):
         assert len(np.unique(codes)) > len(codes) // 2 and not np.array_equal(got, np.arange(len(tris)))
 
 
+def test_order_is_the_definitions_at_257_tiles():
+    """q262147 (tests/bvh_build_cases.py): 257 tiles of the device's sort, 65 steps of its scan"""
+    tris = B.mesh("q262147")
+    shape = D.shape_over(tris)
+    got = T.bvh_morton_order_host(shape, tris)
+    assert len(got) == 262147 and np.array_equal(got, B.morton_order(shape, tris))
+    assert not np.array_equal(got, np.arange(len(tris)))
+
+
 @pytest.mark.parametrize("count", [1, 5, 37])
 def test_coinciding_centroids_give_the_identity(count):
     tris = B.mesh(f"same{count}")
