@@ -1,0 +1,185 @@
+"""The moved-camera cases of the temporal set-up (TP_PROJECT in simple-raytracer_amd/csrc/temporal_body.inc) that
+tests/test_temporal_cases.py checks on the CPU and tests/test_gpu_denoise_temporal_cases.py runs on the device, and the
+oracle's feature pass as a frame of tests/temporal_ref.py. A plain module.
+
+A case is a history camera and a current camera, each (camera_to_world, fov_scale, aspect_ratio or None: width / height).
+The history stands at the default camera; every current pose starts from GENERIC, a pose a little off it in all six degrees
+of freedom. Without that offset a pure zoom, a pure aspect change, a pure scale or a mirror that shares an axis with the
+history puts 30-100 % of the pixels on whole-pixel tap coordinates, which temporal_ref flags `borderline`; with it every
+case flags at most 0.07 % of a 128x72 frame of the `mixed` scene and at most one pixel of a 37x29 one.
+"""
+import numpy as np
+
+import motion_ref as M
+import temporal_ref as TR
+from simple_raytracer_amd import records as R, scenes as S
+
+F32 = np.float32
+
+
+def pose(position, yaw=0.0, pitch=0.0, roll=0.0):
+    """records.camera_matrix with a roll about the viewing axis"""
+    return R.mat_mul(R.translate(position), R.euler_yxz(yaw, pitch, roll))
+
+
+def with_rotation(m, m3):
+    """the camera m with the upper 3x3 (columns m[0..2][:3]) replaced by m3 (3, 3) [column][row]"""
+    out = np.array(m, F32)
+    out[:3, :3] = np.asarray(m3, F32)
+    return out
+
+
+POSITION, YAW, PITCH, ROLL = (0.037, 0.53, 4.9), 0.021, -0.013, 0.017
+GENERIC = pose(POSITION, YAW, PITCH, ROLL)
+HISTORY = S.default_camera()
+
+
+def _mirror_shear(m):
+    c = np.array(m[:3, :3], F32)
+    c[0] = c[0] + F32(0.2) * c[1]
+    c[1] = -c[1]
+    return with_rotation(m, c)
+
+
+# name -> ((history matrix, fov_scale, aspect_ratio), (current matrix, fov_scale, aspect_ratio))
+CASES = {
+    "zoom_in": ((HISTORY, 1.0, None), (GENERIC, 0.8, None)),
+    "zoom_out": ((HISTORY, 1.0, None), (GENERIC, 1.3, None)),
+    "aspect": ((HISTORY, 1.0, None), (GENERIC, 1.0, 1.5)),
+    "roll": ((HISTORY, 1.0, None), (pose(POSITION, YAW, PITCH, ROLL + 0.35), 1.0, None)),
+    "big_yaw": ((HISTORY, 1.0, None), (pose(POSITION, YAW + 0.6, PITCH, ROLL), 1.0, None)),
+    "about_face": ((HISTORY, 1.0, None), (pose(POSITION, YAW + np.pi, PITCH, ROLL), 1.0, None)),
+    "dolly": ((HISTORY, 1.0, None), (pose((0.3, 0.7, 3.0), YAW + 0.05, PITCH - 0.03, ROLL), 1.0, None)),
+    "hist_scaled": ((with_rotation(HISTORY, HISTORY[:3, :3] * F32(3)), 1.0, None), (GENERIC, 1.0, None)),
+    "hist_mirror_shear": ((_mirror_shear(HISTORY), 1.0, None), (GENERIC, 1.0, None)),
+    "cur_scaled": ((HISTORY, 1.0, None), (with_rotation(GENERIC, GENERIC[:3, :3] * F32(0.5)), 1.0, None)),
+    "hist_singular": ((with_rotation(HISTORY, np.zeros((3, 3), F32)), 1.0, None), (GENERIC, 1.0, None)),
+}
+NAMES = list(CASES)
+NO_HISTORY = ("about_face", "hist_singular")  # no pixel gets history: everything behind the camera / TP_NONE on the host
+# The current frame sees past the history's image, so the 2x2 of some pixel with history hangs over its border (x0 or y0 is
+# -1 or the last column or row). GENERIC's own turn does that for the cases that change nothing else about the view (a scale
+# of either 3x3 cancels in v.xy / -v.z); zoom_in and dolly look at the history's middle only, and `aspect` looks past the
+# border where 1.5 is wider than the frame (sees_past_the_border).
+OVER_THE_BORDER = ("zoom_out", "roll", "big_yaw", "hist_scaled", "hist_mirror_shear", "cur_scaled")
+MOSTLY_OUTSIDE = ("big_yaw", "zoom_out")  # more than a quarter of the covered pixels outside the window
+SIZES = [(128, 72), (37, 29)]  # the CPU test's; the GPU test adds 1x33 and 33x1
+
+
+def sees_past_the_border(name, w, h):
+    return name in OVER_THE_BORDER or (name == "aspect" and CASES[name][1][2] > w / h)
+
+
+def render_record(w, h, cam, spp=2, time=12345):
+    """the render record of one camera of a case"""
+    m, fov, aspect = cam
+    return R.render_data(w, h, spp, 10, fov_scale=fov, camera_to_world=m, time=time, aspect_ratio=aspect)
+
+
+def interpolate(name, k, n):
+    """frame k of n + 1 along a case (k = 0: the history camera, k = n: the current one): matrices and fov linear in k / n"""
+    (mh, fh, ah), (mc, fc, ac) = CASES[name]
+    assert ah is None and ac is None
+    s = F32(k) / F32(n)
+    return ((F32(1) - s) * np.asarray(mh, F32) + s * np.asarray(mc, F32)).astype(F32), float((1 - s) * fh + s * fc), None
+
+
+def features_frame(oracle, rdata, shapes, tris, mats):
+    """a frame's guide and shape indices from the oracle's feature pass (one feature ray per pixel) under the render record
+    rdata, flat colour"""
+    w, h = int(rdata["width"]), int(rdata["height"])
+    own = shapes.copy()
+    own["material"] = np.arange(len(shapes))  # a material per shape: orc_primary_hits' material is the shape
+    mats_own = np.resize(mats, len(shapes))
+    sd = R.scene_data(len(shapes))
+    nd, ah = oracle.features(rdata, sd, shapes, tris, mats, 1)
+    hit = oracle.primary_hits(rdata, sd, own, tris, mats_own, np.arange(w * h), np.zeros(w * h, np.int32))
+    ids = np.where(hit["material"] >= 0, hit["material"], M.NO_SHAPE).astype(np.uint32).reshape(h, w)
+    inputs = dict(normal_depth=nd, albedo_hits=ah, moments=np.ones((h, w), F32), T=1, P=2)
+    return TR.frame(np.ones((h, w, 4), F32), inputs, 1), ids, rdata
+
+
+def geometry_frame(oracle, name, cam_m, shapes, tris, mats, w, h, time):
+    """a frame's guide and shape indices from the oracle's feature pass (one feature ray per pixel), flat colour"""
+    return features_frame(oracle, R.render_data(w, h, 2, 10, camera_to_world=cam_m, time=time), shapes, tris, mats)
+
+
+def first_history(frame, rdata):
+    """the history a first frame (no history of its own) commits"""
+    return TR.history_from_commit(TR.integrate(frame, TR.reproject(frame, dict(valid=False), rdata))["commit"], rdata)
+
+
+def window(cur, hist_rd, cur_rd):
+    """Where the covered pixels of `cur` land in the history camera -> dict covered, in_front, inside (the kernel's
+    window: in front, -1 < fx < w, -1 < fy < h), x0, y0 (the 2x2's corner; 0 outside the window), or None when the history
+    camera cannot be inverted."""
+    h, w = cur["Z"].shape
+    pr = TR.project(cur["Z"], cur_rd, hist_rd, w, h)
+    if pr is None:
+        return None
+    fx, fy, _, front = pr
+    with np.errstate(all="ignore"):
+        inside = front & (fx > F32(-1)) & (fx < F32(w)) & (fy > F32(-1)) & (fy < F32(h))
+        x0 = np.floor(np.where(inside, fx, F32(0))).astype(np.int64)
+        y0 = np.floor(np.where(inside, fy, F32(0))).astype(np.int64)
+    return dict(covered=cur["cov"] > 0, in_front=front, inside=inside, x0=x0, y0=y0)
+
+
+NAN_MATERIAL = 3  # of scenes.sphere_scene(): the large sphere on the left
+
+
+def nan_scene():
+    """the sphere scene with one material's colour (NaN, 0.5, 0.5): every path through it is not finite"""
+    shapes, tris, mats = S.sphere_scene()
+    mats = mats.copy()
+    mats[NAN_MATERIAL]["color"][:3] = (np.nan, 0.5, 0.5)
+    return shapes, tris, mats
+
+
+def taps_lost_to_colour(cur, hist, cur_rd, **thresholds):
+    """(taps counted, taps a finite history colour would have added) per pixel, by temporal_ref.reproject"""
+    clean = dict(hist, colour=np.where(np.isfinite(hist["colour"]), hist["colour"], F32(0)).astype(F32))
+    got, all_finite = TR.reproject(cur, hist, cur_rd, **thresholds)["taps"], TR.reproject(cur, clean, cur_rd, **thresholds)["taps"]
+    return got, all_finite - got
+
+
+# ---- a device frame against temporal_ref.temporal_setup ----------------------------------------------------------------
+def same_bits(a, b):
+    """per pixel (h, w): every float of a and b has the same bits, any NaN equal to any NaN (conftest.bits_equal's rule)"""
+    a, b = np.ascontiguousarray(a, F32), np.ascontiguousarray(b, F32)
+    eq = (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+    return eq.reshape(eq.shape[:2] + (-1,)).all(-1)
+
+
+def ulps(a, b):
+    """the largest distance of a from b in units of b's last place, over the floats finite in both (0 without any)"""
+    a, b = np.asarray(a, F32).ravel(), np.asarray(b, F32).ravel()
+    both = np.isfinite(a) & np.isfinite(b)
+    if not both.any():
+        return 0.0
+    a, b = a[both].astype(np.float64), b[both]
+    return float((np.abs(a - b.astype(np.float64)) / np.spacing(np.maximum(np.abs(b), np.finfo(F32).tiny)).astype(np.float64)).max())
+
+
+def compare_setup(want, got, argb, history):
+    """The device's set-up of one frame -- got = read_denoised(), argb (h, w, 4) the bytes, history = what the next clear
+    committed -- against want = temporal_ref.temporal_setup(). -> per pixel (h, w): `exact`, colour, variance, bytes and the
+    committed colour, count, m1, m2 agree bit for bit; `close`, they agree within rtol 1e-4 and one byte step; and
+    the largest distance in
+    float32 ulps over the pixels not flagged borderline. The committed guide does not depend on the history: asserted equal everywhere."""
+    import denoise_ref as D
+    commit = want["commit"]
+    assert same_bits(history["guide"], commit["guide"]).all(), "guide"
+    tone = D.tonemap(want["c"])
+    floats = [(got[..., :3], want["c"], 1e-6), (got[..., 3], want["V"], 1e-7), (history["colour"], commit["colour"], 1e-6),
+              (history["count"], commit["count"], 0.0), (history["m1"], commit["m1"], 1e-6), (history["m2"], commit["m2"], 1e-6)]
+    exact = np.all(argb == tone, axis=-1)
+    close = (np.abs(argb.astype(int) - tone.astype(int)) <= 1).all(-1)
+    worst, keep = 0.0, ~want["rep"]["borderline"]
+    with np.errstate(all="ignore"):
+        for a, b, atol in floats:
+            exact &= same_bits(a, b)
+            ok = np.isclose(a, b, rtol=1e-4, atol=atol, equal_nan=True)
+            close &= ok.reshape(ok.shape[:2] + (-1,)).all(-1)
+            worst = max(worst, ulps(a[keep], b[keep]))
+    return exact, close, worst

@@ -1,5 +1,5 @@
 """GPU: the denoiser's temporal reprojection (srt_set_denoise_temporal) -- off and no-history mean the spatial denoiser bit
-for bit, a still camera against tests/temporal_ref.py bit for bit, a moving camera against it within float32 noise, the
+for bit, a still camera against tests/temporal_ref.py bit for bit, a moving camera against it bit for bit on the pixels it does not flag, the
 rules that drop the history, quality on a moving camera, the render paths, determinism, srt_headless and the error codes."""
 import ctypes as C
 import subprocess
@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import denoise_ref as D
+import temporal_cases as TC
 import temporal_ref as TR
 from conftest import bits_equal
 from gpu_harness import T, cam_at, make, tone  # noqa: F401 (T: the fixture)
@@ -142,7 +143,8 @@ def test_moving_camera_matches_numpy(T, sky, name, accel, kind):
         want = frame_ref(t, hist, **tp)
         got = t.read_denoised()
         t.clear_canvas()
-        got_count = t.read_denoise_history()["count"]
+        got_h = t.read_denoise_history()
+        got_count = got_h["count"]
         border = want["rep"]["borderline"]
         with np.errstate(all="ignore"):
             ok = np.isclose(got[..., :3], want["c"], rtol=1e-4, atol=1e-6, equal_nan=True).all(-1)
@@ -151,6 +153,9 @@ def test_moving_camera_matches_numpy(T, sky, name, accel, kind):
             ok &= (np.abs(argb.astype(int) - D.tonemap(want["c"]).astype(int)) <= 1).all(-1)
         bad = ~ok & ~border
         assert not bad.any(), (k, np.argwhere(bad)[:5])
+        # and bit for bit where the restatement does not flag the pixel (tests/test_gpu_denoise_temporal_cases.py's rule)
+        exact, _, _ = TC.compare_setup(want, got, argb, got_h)
+        assert not (~exact & ~border).any(), (k, np.argwhere(~exact & ~border)[:5])
         # flagged pixels are exempt only where they differ: a translation leaves the far field (parallax -> 0) within 1e-4 of
         # whole-pixel coordinates, which flags up to ~0.5 % of the pixels, nearly all of them computed alike
         exempt = int((~ok & border).sum())

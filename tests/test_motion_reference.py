@@ -9,6 +9,7 @@ import motion_ref as M
 import temporal_ref as TR
 from gpu_harness import cam_at, scene
 from simple_raytracer_amd import records as R, scenes as S, tracer as T
+from temporal_cases import geometry_frame
 from test_temporal_reference import frame_of, history_of, rd
 
 F32 = np.float32
@@ -261,20 +262,6 @@ def test_rigid_move_of_every_shape_equals_moving_the_history_camera():
 
 
 # ---- 6 (CPU part). the flagged share of the GPU test's moves ---------------------------------------------------------
-def geometry_frame(oracle, name, cam_m, shapes, tris, mats, w, h, time):
-    """a frame's guide and shape indices from the oracle's feature pass (one feature ray per pixel), flat colour"""
-    own = shapes.copy()
-    own["material"] = np.arange(len(shapes))  # a material per shape: orc_primary_hits' material is the shape
-    mats_own = np.resize(mats, len(shapes))
-    rdata = R.render_data(w, h, 2, 10, camera_to_world=cam_m, time=time)
-    sd = R.scene_data(len(shapes))
-    nd, ah = oracle.features(rdata, sd, shapes, tris, mats, 1)
-    hit = oracle.primary_hits(rdata, sd, own, tris, mats_own, np.arange(w * h), np.zeros(w * h, np.int32))
-    ids = np.where(hit["material"] >= 0, hit["material"], M.NO_SHAPE).astype(np.uint32).reshape(h, w)
-    inputs = dict(normal_depth=nd, albedo_hits=ah, moments=np.ones((h, w), F32), T=1, P=2)
-    return TR.frame(np.ones((h, w, 4), F32), inputs, 1), ids, rdata
-
-
 @pytest.mark.parametrize("case", M.MOVES, ids=[m[0] for m in M.MOVES])
 def test_moves_stay_under_the_flagged_share(oracle, case):
     """at most 1 % of a frame's pixels flagged, for every move of the GPU test; the moved shape has pixels with history and
