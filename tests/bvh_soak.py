@@ -4,7 +4,8 @@ translations (up to 10^4 model sizes from the world's origin), a plane, glass / 
 model sizes away that looks at the mesh; rendered 48x32 at 2 spp and 6 bounces through the array-order scan (the reference's
 result, checked against the oracle elsewhere) and through the BVH: canvases must agree bit for bit, rays / sky / paths counters
 too. What this adds to tests/fuzz_soak.py (whose meshes have a handful of triangles): hierarchies several levels deep, far
-from the origin, seen from far away -- where the boxes' padding is what keeps an accepted hit inside them."""
+from the origin, seen from far away -- where the boxes' padding is what keeps an accepted hit inside them.
+Cameras here are drawn from continuous distributions; origins exactly on decoded planes and +-0 direction components are the directed cases of tests/bvh_walk_cases.py."""
 import sys
 import time
 from pathlib import Path

@@ -3,21 +3,17 @@ points srt_bvh_build_host (the binary hierarchy that is built, cached and refitt
 srt_bvh_wide_host (its four-wide folding, which the kernel walks); no GPU involved. Structure
 invariants, box containment, the bound on a walk's stack, and a float32 re-enactment of the walk
 against a brute-force double-precision Moller-Trumbore: every triangle a ray really hits must be
-among the triangles the walk tests."""
+among the triangles the walk tests. The re-enactment is tests/bvh_walk_cases.py walk: it decodes a child's planes relative to the
+ray as the kernel does, fmaf(byte, 2^e, origin - o), and orders zeros as v_max_f32 / v_min_f32 do."""
 import numpy as np
 import pytest
 
+from bvh_walk_cases import blob968, inner_children, true_hits, walk, world_vertices  # noqa: F401 (the walk's restatement lives with its directed cases)
 from simple_raytracer_amd import records as R, scenes as S, tracer as T
 
 END = T.BVH_END
 FLT_MAX = np.finfo(np.float32).max
 LEAF_MAX = 3  # SRT_BVH_LEAF_MAX (csrc/device_types.h)
-
-
-def world_vertices(shape, tris):
-    first, n = int(shape["triangle_index"]), int(shape["num_triangles"])
-    pos = tris["v"]["pos"][first:first + n].reshape(-1, 3)
-    return R.transform_points(np.asarray(shape["transform"], np.float32), pos, 1.0).reshape(n, 3, 3).astype(np.float64)
 
 
 def check_structure(nodes, order, n_tris):
@@ -57,22 +53,6 @@ def check_boxes(nodes, order, wv):
         v = wv[order[first:first + cnt]].reshape(-1, 3)
         assert (v >= nodes["lo"][i] - 0).all() and (v <= nodes["hi"][i] + 0).all(), f"leaf {i} does not contain its triangles"
         assert (v.min(axis=0) > nodes["lo"][i]).all() and (v.max(axis=0) < nodes["hi"][i]).all(), "boxes are padded"
-
-
-def inner_children(blocks, idx):
-    """(first, nk, tags[4], lo[4][3], hi[4][3]) of inner block idx (csrc/device_types.h): boxes as bytes on the block's power-of-two
-    grid -- origin in dwords 0-2, exponents and count in 3, lo bytes 4-6, hi bytes 7-9, tags 10, first 11; bound = fmaf(byte, 2^e,
-    origin) (the product is exact, the float64 sum rounds to float32 once: the kernel's fmaf up to double rounding)."""
-    b = blocks[idx]
-    assert not b[12:].any()
-    origin = b.view(np.float32)[0:3].astype(np.float64)
-    ex, nk = int(b[3]), int(b[3]) >> 24
-    scale = np.array([((ex >> (8 * a)) & 255) << 23 for a in range(3)], np.uint32).view(np.float32).astype(np.float64)
-    byte = lambda w, k: float((int(w) >> (8 * k)) & 255)
-    with np.errstate(all="ignore"):
-        lo = [np.array([byte(b[4 + a], k) * scale[a] + origin[a] for a in range(3)]).astype(np.float32) for k in range(4)]
-        hi = [np.array([byte(b[7 + a], k) * scale[a] + origin[a] for a in range(3)]).astype(np.float32) for k in range(4)]
-    return int(b[11]), nk, [(int(b[10]) >> (8 * k)) & 255 for k in range(4)], lo, hi
 
 
 def check_wide(wide, nodes, order, n_tris):
@@ -129,67 +109,8 @@ def check_wide(wide, nodes, order, n_tris):
     return inner, leaves
 
 
-def walk(wide, rec_of_slot, org, d):
-    """The device's walk (csrc/device_intersect.h walk_bvh) with tmin = inf, in float32; returns the tested records, the
-    blocks fetched and the deepest the stack got (waiting children, as the host's bound counts them)."""
-    f = np.float32
-    org, d = org.astype(f), d.astype(f)
-    with np.errstate(all="ignore"):
-        inv = np.where(np.abs(d) >= f(2.0 ** -100), f(1) / d, np.copysign(f(2.0 ** 100), d)).astype(f)
-    neg = inv < 0
-    blocks = wide["blocks"]
-    fl = blocks.view(np.float32)
-    tested, steps, deepest = [], 0, 0
-    root = wide["root"]
-    stack = []  # (key, first)
-    cur = None if root == T.BVH_NONE else (root & T.BVH_INDEX_MASK, ((root >> 31) << 4) | (((root >> 28) & 3) << 2))
-    while cur is not None:
-        steps += 1
-        idx, tag = cur
-        cur = None
-        if tag & 16:
-            tested.extend(rec_of_slot[(idx << 2) | k] for k in range((tag >> 2) & 3))
-        else:
-            first, nk, tags, los, his = inner_children(blocks, idx)
-            keys = []
-            for k in range(4):
-                lo, hi = los[k], his[k]
-                near, far = np.where(neg, hi, lo), np.where(neg, lo, hi)  # what the lane's selects pick
-                with np.errstate(all="ignore"):
-                    tn = max(((near - org) * inv).max(), f(0))
-                    tf = ((far - org) * inv).min()
-                    hit = tn <= tf * f(1.000001) and k < nk
-                bits = int(np.array([tn], f).view(np.uint32)[0]) if hit else 0x7F800000
-                keys.append((bits & ~31) | tags[k])
-            keys.sort()
-            enter = [k for k in keys if k < 0x7F800000]
-            assert all(k & 3 < nk for k in enter), "an empty slot was entered"
-            if enter:
-                cur = (first + (enter[0] & 3), enter[0])
-                stack.extend((k, first) for k in reversed(enter[1:]))
-                deepest = max(deepest, len(stack))
-        if cur is None and stack:
-            key, first = stack.pop()
-            cur = (first + (key & 3), key)
-    return tested, steps, deepest
-
-
-def true_hits(wv, org, d):
-    v0, e1, e2 = wv[:, 0], wv[:, 1] - wv[:, 0], wv[:, 2] - wv[:, 0]
-    h = np.cross(d, e2)
-    a = (e1 * h).sum(-1)
-    with np.errstate(all="ignore"):
-        f = 1.0 / a
-        s = org - v0
-        u = f * (s * h).sum(-1)
-        q = np.cross(s, e1)
-        v = f * (q * d).sum(-1)
-        t = f * (e2 * q).sum(-1)
-        return np.nonzero((a != 0) & (u >= 0) & (u <= 1) & (v >= 0) & (u + v <= 1) & (t > 0))[0]
-
-
 MESHES = {
-    "blob968": lambda: (S.blob_mesh(22, 23, seed=1), R.mat_mul(R.translate((0.4, -0.1, 0.2)), R.mat_mul(R.euler_yxz(0.6, -0.3, 0.2), R.scale_matrix((1.0, 0.7, 1.3))))),
+    "blob968": blob968,
     "box12": lambda: (R.box_triangles(), R.mat_mul(R.translate((1, 2, 3)), R.euler_yxz(0.3, 0.9, 0.0))),
     "flat48": lambda: (S.blob_mesh(6, 5, seed=9, smooth=False), R.identity4()),
     "single": lambda: (R.box_triangles()[:1], R.identity4()),
