@@ -134,7 +134,7 @@ struct BvhCacheEntry {
 	bool balanced = false; // built without the SAH because the SAH tree could overflow a lane's stack
 	uint32_t leaves = 0, depth = 0;
 	// BvhBuilder::wide_cost of the hierarchy as build() left it, and of its boxes as they were last known (the host's refits
-	// store it; for a stale entry the device's cost kernel reports it, srt_abi.hip); 0 = unknown
+	// store it; for a stale entry the device's cost kernel reports it, accel_device.hip); 0 = unknown
 	double cost_built = 0.0, cost_now = 0.0;
 	void build(const srt_model &m, const srt_triangle *all);
 	// The hierarchy SRT_BUILD_DEVICE makes, on the host: `order` = the Morton order, the balanced topology of the model's count
@@ -143,7 +143,7 @@ struct BvhCacheEntry {
 	// the same over the median-split order (SRT_BUILD_ORDER_MEDIAN)
 	void build_median(const srt_model &m, const srt_triangle *all);
 	// The part of it that depends on the count alone: nodes and `wide` of the balanced topology (boxes zero, inner blocks not
-	// yet quantised), `order` the identity, stale, order_pending. The device sorts and refits (scene_prep.cpp, srt_abi.hip).
+	// yet quantised), `order` the identity, stale, order_pending. The device sorts and refits (scene_prep.cpp, accel_device.hip).
 	void set_balanced_topology(uint32_t n);
 	void refit(const srt_model &m, const srt_triangle *all);
 	// New boxes for the wide hierarchy AS IT IS FOLDED: the binary boxes as refit() makes them, then every inner block
@@ -156,7 +156,7 @@ struct BvhCacheEntry {
 	// refit() recompute everything from the triangles and clear the mark.
 	bool stale = false;
 	// Built on the device by the srt_update_scene before: `order` is still the identity, the sorted one is on its way back
-	// (srt_abi.hip waits for the copy before the next host pass looks at any entry).
+	// (accel_device.hip srt_accel_build_consume waits for the copy before the next host pass looks at any entry).
 	bool order_pending = false;
 	bool same_triangles(const srt_model &m, const srt_triangle *all, uint64_t hash) const {
 		return m.num_triangles == count && hash == tri_hash && memcmp(tris.data(), all + m.triangle_index, (size_t)count * sizeof(srt_triangle)) == 0;

@@ -25,7 +25,7 @@ uint64_t bernoulli_threshold(float pr) {
 
 // host pass; `cache` is made when a BVH scene first needs it and emptied by an array-scan scene; an error return leaves its text
 // in `err` and every cached hierarchy in place
-int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, const BuildPolicy &build, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
+int prepare_scene(const AccelPolicy &policy, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
                   const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
 	auto fail = [&err](int code, const char *msg) {
 		err = msg;
@@ -47,7 +47,7 @@ int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, co
 	offs.assign(n_shapes ? n_shapes : 1, 0u);
 	uint64_t &total_wtris = sp.total_wtris, &max_tris = sp.max_tris;
 	int &num_models = sp.num_models;
-	const bool use_bvh = sp.use_bvh = accel_mode == SRT_ACCEL_BVH;
+	const bool use_bvh = sp.use_bvh = policy.accel == SRT_ACCEL_BVH;
 	std::vector<uint32_t> &bvh_blocks = sp.bvh_blocks; // 32 dwords each (device_types.h)
 	std::vector<uint32_t> &bvh_order = sp.bvh_order, &bvh_dest = sp.bvh_dest;
 	uint64_t bvh_leaves = 0, bvh_depth = 0, bvh_reused = 0, bvh_refitted = 0, bvh_canonical_nodes = 0;
@@ -86,7 +86,7 @@ int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, co
 	// in array order, exactly as the loop would choose; then, among the entries nobody claimed, the models whose bytes changed
 	// take one of the same triangle range (index and count) -- so a deformed model never takes what a later one matches byte
 	// for byte. (Models the loop is going to refuse are left out here.)
-	const bool deform_on = use_bvh && deform.mode == SRT_DEFORM_REFIT;
+	const bool deform_on = use_bvh && policy.deform.mode == SRT_DEFORM_REFIT;
 	struct Match {
 		BvhCacheEntry *ent = nullptr;
 		bool deformed = false;
@@ -186,7 +186,7 @@ int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, co
 				// return keeps every hierarchy).
 				BvhCacheEntry *kept = deform_on ? matched[i].ent : find_same_triangles(m, th);
 				bool deformed = deform_on && matched[i].deformed;
-				if (deformed && deform.rebuild_ratio > 0.0f && BvhBuilder::cost_ratio(kept->cost_now, kept->cost_built) > (double)deform.rebuild_ratio) {
+				if (deformed && policy.deform.rebuild_ratio > 0.0f && BvhBuilder::cost_ratio(kept->cost_now, kept->cost_built) > (double)policy.deform.rebuild_ratio) {
 					kept = nullptr, deformed = false; // refitted too often: the tree has degraded past the caller's bound, build a new one
 					deform_rebuilt++;
 				}
@@ -196,7 +196,7 @@ int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, co
 					ent = kept;
 					ent->claimed = true;
 					ent->triangle_index = m.triangle_index;
-					const bool on_device = refit_mode == SRT_REFIT_DEVICE;
+					const bool on_device = policy.refit == SRT_REFIT_DEVICE;
 					if (deformed) { // other bytes in the same triangle range: the tree and its records' order stay, every box is recomputed
 						ent->tris.assign(triangles + m.triangle_index, triangles + m.triangle_index + m.num_triangles);
 						ent->tri_hash = th;
@@ -220,7 +220,7 @@ int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, co
 				} else {
 					fresh.emplace_back();
 					ent = &fresh.back();
-					device_built = build.mode == SRT_BUILD_DEVICE && m.num_triangles >= build.min_triangles;
+					device_built = policy.build.mode == SRT_BUILD_DEVICE && m.num_triangles >= policy.build.min_triangles;
 					// on the device: the topology of the count, stale with the identity order -- the device sorts the records
 					// before the pre-pass reads them and refits every box behind it
 					if (device_built) *ent = cache->balanced_topology(m.num_triangles);

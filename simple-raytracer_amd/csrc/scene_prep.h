@@ -1,5 +1,5 @@
 // scene_prep.h — the host pass of srt_update_scene / srt_group_update_scene: everything a device needs of a scene, as host arrays.
-// No HIP, and no handle: the caller (srt_abi.hip) passes what the pass reads of one and uploads the result.
+// No HIP, and no handle: the caller (srt_abi.hip) passes what the pass reads of one -- its AccelPolicy and hierarchy cache -- and uploads the result.
 #ifndef SRT_SCENE_PREP_H
 #define SRT_SCENE_PREP_H
 
@@ -52,10 +52,11 @@ struct ScenePrep {
 	uint32_t build_max_records = 0, build_tiles = 0;
 };
 
-// srt_set_acceleration_build: who builds a model that has no hierarchy to keep (nothing without SRT_ACCEL_BVH)
+// srt_set_acceleration_build / _build_order: who builds a model that has no hierarchy to keep (nothing without SRT_ACCEL_BVH)
 struct BuildPolicy {
 	int mode = SRT_BUILD_HOST;
-	uint32_t min_triangles = 0; // SRT_BUILD_DEVICE: smaller models keep the host's build
+	uint32_t min_triangles = 0;         // SRT_BUILD_DEVICE: smaller models keep the host's build
+	int order = SRT_BUILD_ORDER_MORTON; // SRT_BUILD_DEVICE: the order the device sorts into (accel_device.hip; the host pass does not read it)
 };
 
 // srt_set_acceleration_deform: what becomes of a model whose triangle bytes changed (nothing without SRT_ACCEL_BVH)
@@ -64,27 +65,18 @@ struct DeformPolicy {
 	float rebuild_ratio = 0.0f; // SRT_DEFORM_REFIT: a kept model whose last known cost ratio is above this is rebuilt; 0 = never
 };
 
-// accel_mode: SRT_ACCEL_*; refit_mode: SRT_REFIT_* (who refits a model that only moved; nothing without SRT_ACCEL_BVH); deform, build: above; cache: the caller's hierarchy cache (a group: its first member's); scan_suspend_min: srt_scan_suspend_min()
-int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, const BuildPolicy &build, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
+// THE acceleration policy of a handle: what the five srt_set_acceleration* setters write and the next srt_update_scene reads. A
+// group copies its first member's to every member whole; a new policy is a member here and nothing else.
+struct AccelPolicy {
+	int accel = SRT_ACCEL_NONE; // SRT_ACCEL_*
+	int refit = SRT_REFIT_HOST; // SRT_REFIT_*: who refits a model that only moved (nothing without SRT_ACCEL_BVH)
+	DeformPolicy deform;
+	BuildPolicy build;
+};
+
+// cache: the caller's hierarchy cache (a group: its first member's); scan_suspend_min: srt_scan_suspend_min()
+int prepare_scene(const AccelPolicy &policy, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
                   const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene);
-
-// the same with SRT_BUILD_HOST
-inline int prepare_scene(int accel_mode, int refit_mode, const DeformPolicy &deform, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
-                         const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
-	return prepare_scene(accel_mode, refit_mode, deform, BuildPolicy(), cache, scan_suspend_min, err, sp, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
-}
-
-// the same with SRT_DEFORM_REBUILD
-inline int prepare_scene(int accel_mode, int refit_mode, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
-                         const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
-	return prepare_scene(accel_mode, refit_mode, DeformPolicy(), cache, scan_suspend_min, err, sp, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
-}
-
-// the same with SRT_REFIT_HOST
-inline int prepare_scene(int accel_mode, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
-                         const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
-	return prepare_scene(accel_mode, SRT_REFIT_HOST, cache, scan_suspend_min, err, sp, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
-}
 
 uint64_t bernoulli_threshold(float pr);
 

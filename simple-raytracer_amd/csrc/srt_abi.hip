@@ -1,10 +1,9 @@
-// srt_abi.hip — host side of libsrt_hip.so: the C ABI of include/srt_abi.h over the
-// kernels in kernels.hip. This is what replaces the boost.compute/OpenCL dispatch of
-// the reference's Tracer (src/tracer.cpp:11-116). HIP runtime only. What needs no device lives
-// beside it: the BVH builder (bvh_host.cpp), the scene's host pass (scene_prep.cpp), the launch plan (trace_plan.h).
+// srt_abi.hip — host side of libsrt_hip.so: the C ABI of include/srt_abi.h over the kernels in kernels.hip. This is what replaces
+// the boost.compute/OpenCL dispatch of the reference's Tracer (src/tracer.cpp:11-116). HIP runtime only: life cycle, scene upload,
+// trace; the BVH's upkeep on the device around an upload's pre-pass and the srt_*acceleration* entry points are accel_device.hip's.
+// What needs no device lives beside it: the BVH builder (bvh_host.cpp), the scene's host pass (scene_prep.cpp), the launch plan (trace_plan.h).
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -198,26 +197,7 @@ void srt_destroy(srt_tracer *t) {
 	t->bvh_blocks.release();
 	t->bvh_order.release();
 	t->bvh_dest.release();
-	t->refit_models.release();
-	t->refit_extents.release();
-	t->refit_sched.release();
-	t->refit_boxes.release();
-	for (hipEvent_t ev : t->ev_refit)
-		if (ev) (void)hipEventDestroy(ev);
-	t->build_models.release();
-	t->build_extents.release();
-	t->build_table.release();
-	t->build_ranges_dev.release();
-	for (int k = 0; k < 2; k++) t->build_keys[k].release(), t->build_vals[k].release();
-	if (t->build_order_host) (void)hipHostFree(t->build_order_host);
-	if (t->ev_build_done) (void)hipEventDestroy(t->ev_build_done);
-	for (hipEvent_t ev : t->ev_build)
-		if (ev) (void)hipEventDestroy(ev);
-	t->deform_ranges.release();
-	t->deform_weights.release();
-	t->deform_sums.release();
-	if (t->deform_sums_host) (void)hipHostFree(t->deform_sums_host);
-	if (t->ev_deform) (void)hipEventDestroy(t->ev_deform);
+	t->upkeep.release();
 	t->sky.release();
 	t->counters.release();
 	t->wave_counters.release();
@@ -296,232 +276,6 @@ int srt_update_scene(srt_tracer *t, const srt_shape *shapes, size_t n_shapes, co
 	}
 }
 
-// SRT_DEFORM_REFIT: waits for the last upload's cost sums (behind their event only, not for the stream) and turns them into
-// ratios: on the handle for srt_acceleration_deform_info, and on the hierarchies `cache` keeps (the handle's own; a group's first
-// member's) for the next srt_update_scene's rebuild rule. Once per upload.
-static int deform_consume(srt_tracer *t, BvhCache *cache) {
-	if (!t->deform_pending) return SRT_OK;
-	SRT_HIP(t, hipSetDevice(t->device));
-	SRT_HIP(t, hipEventSynchronize(t->ev_deform));
-	t->deform_pending = false;
-	for (size_t k = 0; k < t->deform_entry.size(); k++) {
-		const double cost_now = BvhBuilder::cost_of(t->deform_sums_host[2 * k], t->deform_sums_host[2 * k + 1]);
-		const bool fresh = k < t->deform_fresh.size() && t->deform_fresh[k]; // built on the device by that upload: this IS its cost as built
-		t->deform_ratio[k] = BvhBuilder::cost_ratio(cost_now, fresh ? cost_now : t->deform_built[k]);
-		if (cache && t->deform_entry[k] < cache->entries.size()) {
-			cache->entries[t->deform_entry[k]].cost_now = cost_now;
-			if (fresh) cache->entries[t->deform_entry[k]].cost_built = cost_now;
-		}
-	}
-	return SRT_OK;
-}
-
-// behind pass C: the cost of every refitted hierarchy, summed on the device and copied to pinned host memory
-static int deform_cost_on_device(srt_tracer *t, const ScenePrep &sp) {
-	const size_t n = sp.refit_cost_ranges.size();
-	t->deform_entry = sp.refit_cost_entry;
-	t->deform_built = sp.refit_cost_built;
-	t->deform_fresh = sp.refit_cost_fresh;
-	t->deform_ratio.assign(n, 0.0);
-	if (n == 0) return SRT_OK;
-	SRT_HIP(t, t->deform_ranges.reserve(n));
-	SRT_HIP(t, t->deform_weights.reserve(sp.refit_weights.size()));
-	SRT_HIP(t, t->deform_sums.reserve(2 * n));
-	if (t->deform_sums_cap < 2 * n) {
-		if (t->deform_sums_host) (void)hipHostFree(t->deform_sums_host);
-		t->deform_sums_host = nullptr, t->deform_sums_cap = 0;
-		SRT_HIP(t, hipHostMalloc(reinterpret_cast<void **>(&t->deform_sums_host), 2 * n * sizeof(double), hipHostMallocDefault));
-		t->deform_sums_cap = 2 * n;
-	}
-	if (!t->ev_deform) SRT_HIP(t, hipEventCreateWithFlags(&t->ev_deform, hipEventDisableTiming));
-	SRT_HIP(t, hipMemcpyAsync(t->deform_ranges.ptr, sp.refit_cost_ranges.data(), n * sizeof(RefitCostRange), hipMemcpyHostToDevice, t->stream));
-	SRT_HIP(t, hipMemcpyAsync(t->deform_weights.ptr, sp.refit_weights.data(), sp.refit_weights.size(), hipMemcpyHostToDevice, t->stream));
-	SRT_HIP(t, hipMemsetAsync(t->deform_sums.ptr, 0, 2 * n * sizeof(double), t->stream));
-	uint32_t max_blocks = 0;
-	for (const RefitCostRange &r : sp.refit_cost_ranges) max_blocks = r.num_blocks > max_blocks ? r.num_blocks : max_blocks;
-	t->deform_info[2] = (uint64_t)srt_launch_refit_cost(t->refit_boxes.ptr, t->deform_weights.ptr, t->deform_ranges.ptr, t->deform_sums.ptr, (uint32_t)n, max_blocks, t->stream);
-	SRT_HIP(t, hipGetLastError());
-	SRT_HIP(t, hipMemcpyAsync(t->deform_sums_host, t->deform_sums.ptr, 2 * n * sizeof(double), hipMemcpyDeviceToHost, t->stream));
-	SRT_HIP(t, hipEventRecord(t->ev_deform, t->stream));
-	t->deform_pending = true;
-	return SRT_OK;
-}
-
-// SRT_BUILD_DEVICE: waits for the last upload's sorted order (behind its event only, not for the stream) and hands every built
-// model's records to its hierarchy in `cache` (the handle's own; a group's first member's), so that every host path that reads
-// an entry's order finds it. An entry whose order never came back (an upload that failed half way) leaves the cache: its
-// model is built again. Once per upload.
-static int build_consume(srt_tracer *t, BvhCache *cache) {
-	if (t->build_pending) {
-		SRT_HIP(t, hipSetDevice(t->device));
-		SRT_HIP(t, hipEventSynchronize(t->ev_build_done));
-		t->build_pending = false;
-		for (size_t k = 0; cache && k < t->build_entry.size(); k++) {
-			if (t->build_entry[k] >= cache->entries.size()) continue;
-			BvhCacheEntry &e = cache->entries[t->build_entry[k]];
-			const RefitModel &rm = t->build_ranges[k];
-			if (!e.order_pending || e.count != rm.num_records) continue;
-			e.order.assign(t->build_order_host + rm.first_record, t->build_order_host + rm.first_record + rm.num_records);
-			e.order_pending = false;
-		}
-	}
-	if (cache)
-		for (size_t k = cache->entries.size(); k-- > 0;)
-			if (cache->entries[k].order_pending) cache->entries.erase(cache->entries.begin() + (ptrdiff_t)k);
-	return SRT_OK;
-}
-
-// SRT_BUILD_DEVICE, before the pre-pass: the order of the models this call builds (bvh_build.hip) -- their extents over the
-// identity order the upload carries, a Morton code per record, the sort, whose last pass writes the scene's order array. Under
-// SRT_BUILD_ORDER_MEDIAN the median-split launches instead (they take their extents per range, of the centroids); a model too
-// large for them keeps the Morton order: then the Morton launches run first, over every model, and the median ones overwrite
-// the order of the models they take.
-static int build_on_device(srt_tracer *t, const ScenePrep &sp) {
-	for (uint64_t &v : t->build_info) v = 0;
-	t->build_timed = false;
-	t->build_pending = false; // (upload_scene_begin has waited for the stream: an earlier copy has landed, nobody asked for it)
-	t->build_entry.clear(), t->build_ranges.clear();
-	if (sp.build_models.empty()) return SRT_OK;
-	const uint32_t n_models = (uint32_t)sp.build_models.size();
-	const size_t records = sp.bvh_order.size();
-	SRT_HIP(t, t->build_models.reserve(n_models));
-	SRT_HIP(t, t->build_extents.reserve(sp.build_extents.size()));
-	SRT_HIP(t, t->build_table.reserve(256 * (size_t)sp.build_tiles));
-	for (int k = 0; k < 2; k++) {
-		SRT_HIP(t, t->build_keys[k].reserve(records));
-		SRT_HIP(t, t->build_vals[k].reserve(records));
-	}
-	SRT_HIP(t, hipMemcpyAsync(t->build_models.ptr, sp.build_models.data(), n_models * sizeof(RefitModel), hipMemcpyHostToDevice, t->stream));
-	SRT_HIP(t, hipMemcpyAsync(t->build_extents.ptr, sp.build_extents.data(), sp.build_extents.size() * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream));
-	const bool median = t->build_order == SRT_BUILD_ORDER_MEDIAN;
-	bool morton = !median;
-	uint32_t median_max_records = 0;
-	if (median) { // per model its first range slot, then the slots: (2^levels - 1) empty boxes per model
-		std::vector<uint32_t> &up = t->build_ranges_host;
-		up.assign(n_models, 0u);
-		uint32_t slots = 0;
-		for (uint32_t k = 0; k < n_models; k++) {
-			const uint32_t n = sp.build_models[k].num_records, levels = srt_build_median_levels(n);
-			up[k] = slots;
-			if (levels > SRT_BUILD_MEDIAN_MAX_LEVELS) {
-				morton = true;
-				continue;
-			}
-			slots += (1u << levels) - 1u;
-			if (n > median_max_records) median_max_records = n;
-		}
-		for (uint32_t k = 0; k < slots; k++)
-			up.insert(up.end(), {SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_LO_INIT, SRT_REFIT_EXT_HI_INIT, SRT_REFIT_EXT_HI_INIT, SRT_REFIT_EXT_HI_INIT});
-		SRT_HIP(t, t->build_ranges_dev.reserve(up.size()));
-		SRT_HIP(t, hipMemcpyAsync(t->build_ranges_dev.ptr, up.data(), up.size() * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream));
-	}
-	if (t->timers_in_render) {
-		for (hipEvent_t &ev : t->ev_build)
-			if (!ev) SRT_HIP(t, hipEventCreate(&ev));
-		SRT_HIP(t, hipEventRecord(t->ev_build[0], t->stream));
-	}
-	RefitParams rp;
-	memset(&rp, 0, sizeof rp);
-	rp.shapes = t->shapes.ptr;
-	rp.triangles = t->triangles.ptr;
-	rp.order = t->bvh_order.ptr;
-	rp.models = t->build_models.ptr;
-	rp.extents = t->build_extents.ptr;
-	BuildParams bp;
-	bp.shapes = t->shapes.ptr;
-	bp.triangles = t->triangles.ptr;
-	bp.models = t->build_models.ptr;
-	bp.extents = t->build_extents.ptr;
-	for (int k = 0; k < 2; k++) bp.keys[k] = t->build_keys[k].ptr, bp.vals[k] = t->build_vals[k].ptr;
-	bp.table = t->build_table.ptr;
-	bp.order = t->bvh_order.ptr;
-	bp.range_first = median ? t->build_ranges_dev.ptr : nullptr;
-	bp.ranges = median ? t->build_ranges_dev.ptr + n_models : nullptr;
-	int launches = 0;
-	if (morton) {
-		launches += srt_launch_refit_extents(rp, n_models, sp.build_max_records, t->stream);
-		launches += srt_launch_build_keys(bp, n_models, sp.build_max_records, t->stream);
-		launches += srt_launch_build_sort(bp, n_models, sp.build_max_records, t->stream);
-	}
-	if (median) launches += srt_launch_build_median(bp, n_models, median_max_records, t->stream);
-	SRT_HIP(t, hipGetLastError());
-	uint64_t sorted = 0;
-	for (const RefitModel &rm : sp.build_models) sorted += rm.num_records;
-	t->build_info[0] = n_models, t->build_info[1] = sorted, t->build_info[2] = (uint64_t)launches;
-	return SRT_OK;
-}
-
-// ... and behind the refit of the same upload: the end of the timed span, and the sorted order on its way to pinned host memory
-static int build_read_back(srt_tracer *t, const ScenePrep &sp) {
-	if (sp.build_models.empty()) return SRT_OK;
-	if (t->timers_in_render) {
-		SRT_HIP(t, hipEventRecord(t->ev_build[1], t->stream));
-		t->build_timed = true;
-	}
-	const size_t records = sp.bvh_order.size();
-	if (t->build_order_cap < records) {
-		if (t->build_order_host) (void)hipHostFree(t->build_order_host);
-		t->build_order_host = nullptr, t->build_order_cap = 0;
-		SRT_HIP(t, hipHostMalloc(reinterpret_cast<void **>(&t->build_order_host), records * sizeof(uint32_t), hipHostMallocDefault));
-		t->build_order_cap = records;
-	}
-	if (!t->ev_build_done) SRT_HIP(t, hipEventCreateWithFlags(&t->ev_build_done, hipEventDisableTiming));
-	SRT_HIP(t, hipMemcpyAsync(t->build_order_host, t->bvh_order.ptr, records * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream));
-	SRT_HIP(t, hipEventRecord(t->ev_build_done, t->stream));
-	t->build_entry = sp.build_entry;
-	t->build_ranges = sp.build_models;
-	t->build_pending = true;
-	return SRT_OK;
-}
-
-// SRT_REFIT_DEVICE: behind the pre-pass, new boxes for the models whose blocks were uploaded from a stale hierarchy
-// (bvh_refit.hip): passes A and B over their records, then one launch per height level of their inner blocks
-static int refit_on_device(srt_tracer *t, const ScenePrep &sp) {
-	for (uint64_t &v : t->refit_info) v = 0;
-	t->refit_timed = false;
-	t->deform_pending = false; // (upload_scene_begin has waited for the stream: an earlier copy has landed, nobody asked for it)
-	t->deform_info[0] = sp.deform_info[0], t->deform_info[1] = sp.deform_info[1], t->deform_info[2] = 0, t->deform_info[3] = 0;
-	t->deform_worst_host = sp.deform_worst_ratio;
-	t->deform_entry.clear(), t->deform_built.clear(), t->deform_ratio.clear(), t->deform_fresh.clear();
-	if (sp.refit_models.empty()) return SRT_OK;
-	const uint32_t n_models = (uint32_t)sp.refit_models.size();
-	SRT_HIP(t, t->refit_models.reserve(n_models));
-	SRT_HIP(t, t->refit_extents.reserve(sp.refit_extents.size()));
-	SRT_HIP(t, t->refit_sched.reserve(sp.refit_sched.size()));
-	SRT_HIP(t, t->refit_boxes.reserve(sp.bvh_blocks.size() / 32 * 6));
-	SRT_HIP(t, hipMemcpyAsync(t->refit_models.ptr, sp.refit_models.data(), n_models * sizeof(RefitModel), hipMemcpyHostToDevice, t->stream));
-	SRT_HIP(t, hipMemcpyAsync(t->refit_extents.ptr, sp.refit_extents.data(), sp.refit_extents.size() * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream));
-	if (!sp.refit_sched.empty())
-		SRT_HIP(t, hipMemcpyAsync(t->refit_sched.ptr, sp.refit_sched.data(), sp.refit_sched.size() * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream));
-	RefitParams rp;
-	rp.shapes = t->shapes.ptr;
-	rp.triangles = t->triangles.ptr;
-	rp.order = t->bvh_order.ptr;
-	rp.dest = t->bvh_dest.ptr;
-	rp.models = t->refit_models.ptr;
-	rp.extents = t->refit_extents.ptr;
-	rp.boxes = t->refit_boxes.ptr;
-	rp.blocks = t->bvh_blocks.ptr;
-	rp.sched = t->refit_sched.ptr;
-	if (t->timers_in_render) {
-		for (hipEvent_t &ev : t->ev_refit)
-			if (!ev) SRT_HIP(t, hipEventCreate(&ev));
-		SRT_HIP(t, hipEventRecord(t->ev_refit[0], t->stream));
-	}
-	int launches = srt_launch_refit_extents(rp, n_models, sp.refit_max_records, t->stream);
-	launches += srt_launch_refit_leaves(rp, n_models, sp.refit_max_records, t->stream);
-	for (size_t h = 1; h < sp.refit_levels.size(); h++)
-		launches += srt_launch_refit_level(rp, sp.refit_levels[h - 1], sp.refit_levels[h] - sp.refit_levels[h - 1], t->stream);
-	SRT_HIP(t, hipGetLastError());
-	if (const int rc = deform_cost_on_device(t, sp)) return rc; // (nothing to do, and no launch, without SRT_DEFORM_REFIT)
-	if (t->timers_in_render) {
-		SRT_HIP(t, hipEventRecord(t->ev_refit[1], t->stream));
-		t->refit_timed = true;
-	}
-	t->refit_info[0] = n_models, t->refit_info[1] = sp.refit_sched.size(), t->refit_info[2] = (uint64_t)launches;
-	return SRT_OK;
-}
-
 // device pass, first half: wait for the handle's previous launches, (re)allocate, enqueue every upload and the pre-pass on its stream
 static int upload_scene_begin(srt_tracer *t, const ScenePrep &sp, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles,
                               size_t n_triangles, size_t n_materials) {
@@ -570,7 +324,7 @@ static int upload_scene_begin(srt_tracer *t, const ScenePrep &sp, const srt_shap
 	if (n_materials)
 		SRT_HIP(t, hipMemcpyAsync(t->materials.ptr, dev_mats.data(), n_materials * sizeof(srt_material), hipMemcpyHostToDevice, t->stream));
 
-	if (const int brc = build_on_device(t, sp)) return brc; // (nothing to do, and no launch, without SRT_BUILD_DEVICE)
+	if (const int brc = srt_accel_before_prepass(t, sp)) return brc; // accel_device.hip: SRT_BUILD_DEVICE sorts the order the pre-pass reads
 	if (num_models > 0 && total_wtris > 0) {
 		if (!use_bvh) SRT_HIP(t, hipMemsetAsync(t->wtris.ptr, 0, ((size_t)total_wtris * SRT_WTRI_FLOATS + 64) * sizeof(float), t->stream));
 		// blockIdx.y = shape index; launch in slabs of 65535 shapes
@@ -589,8 +343,7 @@ static int upload_scene_begin(srt_tracer *t, const ScenePrep &sp, const srt_shap
 		}
 		SRT_HIP(t, hipGetLastError());
 	}
-	if (const int rrc = refit_on_device(t, sp)) return rrc;
-	return build_read_back(t, sp);
+	return srt_accel_behind_prepass(t, sp); // SRT_REFIT_DEVICE refits what the pre-pass wrote; the built order starts its way back
 }
 
 // device pass, second half: the uploads have arrived (the host arrays are free again), the handle describes the new scene
@@ -618,13 +371,9 @@ static int upload_scene_end(srt_tracer *t, const ScenePrep &sp, size_t n_shapes,
 static int prepare_scene_of(srt_tracer *t, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
                             const srt_material *materials, size_t n_materials, const srt_scene_data *scene) {
 	std::string err;
-	if (const int crc = deform_consume(t, t->bvh_cache)) return crc; // the rebuild rule looks at the last known cost ratios
-	if (const int brc = build_consume(t, t->bvh_cache)) return brc;  // every entry's order is the sorted one
-	DeformPolicy deform;
-	deform.mode = t->deform_mode, deform.rebuild_ratio = t->deform_rebuild_ratio;
-	BuildPolicy build;
-	build.mode = t->build_mode, build.min_triangles = t->build_min_triangles;
-	const int rc = prepare_scene(t->accel_mode, t->refit_mode, deform, build, t->bvh_cache, srt_scan_suspend_min(), err, sp, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
+	if (const int crc = srt_accel_deform_consume(t, t->bvh_cache)) return crc; // the rebuild rule looks at the last known cost ratios
+	if (const int brc = srt_accel_build_consume(t, t->bvh_cache)) return brc;  // every entry's order is the sorted one
+	const int rc = prepare_scene(t->policy, t->bvh_cache, srt_scan_suspend_min(), err, sp, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
 	return rc == SRT_OK ? SRT_OK : fail(t, rc, err);
 }
 
@@ -652,11 +401,7 @@ int srt_update_scene_many(srt_tracer *const *members, size_t n_members, const sr
 		size_t begun = 0;
 		for (; begun < n_members && rc == SRT_OK; begun++) {
 			if (failed_member) *failed_member = begun;
-			members[begun]->accel_mode = members[0]->accel_mode; // (the prepared scene is in this form)
-			members[begun]->refit_mode = members[0]->refit_mode;
-			members[begun]->deform_mode = members[0]->deform_mode, members[begun]->deform_rebuild_ratio = members[0]->deform_rebuild_ratio;
-			members[begun]->build_mode = members[0]->build_mode, members[begun]->build_min_triangles = members[0]->build_min_triangles;
-			members[begun]->build_order = members[0]->build_order;
+			members[begun]->policy = members[0]->policy; // (the prepared scene is in this form)
 			rc = upload_scene_begin(members[begun], sp, shapes, n_shapes, triangles, n_triangles, n_materials);
 		}
 		if (rc != SRT_OK) { // what was enqueued on the members before the failing one still reads the host arrays: let it finish
@@ -1308,109 +1053,6 @@ int srt_selftest_rare_lanes(srt_tracer *t, int what, const uint32_t *in, uint32_
 	(void)hipFree(d);
 	if (e != hipSuccess) return fail(t, SRT_ERR_HIP, std::string("srt_selftest_rare_lanes: ") + hipGetErrorString(e));
 	*mismatches = h_bad;
-	return SRT_OK;
-}
-
-int srt_set_acceleration(srt_tracer *t, int mode) {
-	if (!t) return SRT_ERR_INVALID;
-	if (mode != SRT_ACCEL_NONE && mode != SRT_ACCEL_BVH) return fail(t, SRT_ERR_INVALID, "srt_set_acceleration: unknown mode");
-	t->accel_mode = mode;
-	return SRT_OK;
-}
-
-int srt_set_acceleration_refit(srt_tracer *t, int mode) {
-	if (!t) return SRT_ERR_INVALID;
-	if (mode != SRT_REFIT_HOST && mode != SRT_REFIT_DEVICE) return fail(t, SRT_ERR_INVALID, "srt_set_acceleration_refit: unknown mode");
-	t->refit_mode = mode;
-	return SRT_OK;
-}
-
-int srt_set_acceleration_deform(srt_tracer *t, int mode, float rebuild_ratio) {
-	if (!t) return SRT_ERR_INVALID;
-	if (mode != SRT_DEFORM_REBUILD && mode != SRT_DEFORM_REFIT) return fail(t, SRT_ERR_INVALID, "srt_set_acceleration_deform: unknown mode");
-	if (!(rebuild_ratio == 0.0f || (rebuild_ratio > 1.0f && rebuild_ratio <= FLT_MAX))) // (a NaN fails every comparison)
-		return fail(t, SRT_ERR_INVALID, "srt_set_acceleration_deform: rebuild_ratio must be 0 or a finite value above 1");
-	t->deform_mode = mode;
-	t->deform_rebuild_ratio = rebuild_ratio;
-	return SRT_OK;
-}
-
-int srt_acceleration_deform_info(srt_tracer *t, uint64_t out[4], double *worst_ratio) {
-	if (!t || !out || !worst_ratio) return SRT_ERR_INVALID;
-	for (int i = 0; i < 4; i++) out[i] = 0;
-	*worst_ratio = 0.0;
-	if (const int rc = deform_consume(t, t->bvh_cache)) return rc;
-	if (!t->bvh_active) return SRT_OK;
-	for (int i = 0; i < 4; i++) out[i] = t->deform_info[i];
-	double worst = t->deform_worst_host;
-	for (double r : t->deform_ratio) worst = r > worst ? r : worst;
-	*worst_ratio = worst;
-	return SRT_OK;
-}
-
-int srt_set_acceleration_build(srt_tracer *t, int mode, uint32_t min_triangles) {
-	if (!t) return SRT_ERR_INVALID;
-	if (mode != SRT_BUILD_HOST && mode != SRT_BUILD_DEVICE) return fail(t, SRT_ERR_INVALID, "srt_set_acceleration_build: unknown mode");
-	t->build_mode = mode;
-	t->build_min_triangles = min_triangles;
-	return SRT_OK;
-}
-
-int srt_set_acceleration_build_order(srt_tracer *t, int order) {
-	if (!t) return SRT_ERR_INVALID;
-	if (order != SRT_BUILD_ORDER_MORTON && order != SRT_BUILD_ORDER_MEDIAN) return fail(t, SRT_ERR_INVALID, "srt_set_acceleration_build_order: unknown order");
-	t->build_order = order;
-	return SRT_OK;
-}
-
-int srt_acceleration_build_info(srt_tracer *t, uint64_t out[4]) {
-	if (!t || !out) return SRT_ERR_INVALID;
-	for (int i = 0; i < 4; i++) out[i] = 0;
-	if (const int rc = deform_consume(t, t->bvh_cache)) return rc; // (a built model's cost as built comes with the same upload)
-	if (const int rc = build_consume(t, t->bvh_cache)) return rc;
-	for (int i = 0; i < 4; i++) out[i] = t->bvh_active ? t->build_info[i] : 0;
-	return SRT_OK;
-}
-
-int srt_last_build_kernel_ms(srt_tracer *t, float *ms) {
-	if (!t || !ms) return SRT_ERR_INVALID;
-	*ms = 0.f;
-	SRT_HIP(t, hipSetDevice(t->device));
-	SRT_HIP(t, hipStreamSynchronize(t->stream));
-	if (t->build_timed) SRT_HIP(t, hipEventElapsedTime(ms, t->ev_build[0], t->ev_build[1]));
-	return SRT_OK;
-}
-
-int srt_acceleration_refit_info(const srt_tracer *t, uint64_t out[4]) {
-	if (!t || !out) return SRT_ERR_INVALID;
-	for (int i = 0; i < 4; i++) out[i] = t->bvh_active ? t->refit_info[i] : 0;
-	return SRT_OK;
-}
-
-int srt_last_refit_kernel_ms(srt_tracer *t, float *ms) {
-	if (!t || !ms) return SRT_ERR_INVALID;
-	*ms = 0.f;
-	SRT_HIP(t, hipSetDevice(t->device));
-	SRT_HIP(t, hipStreamSynchronize(t->stream));
-	if (t->refit_timed) SRT_HIP(t, hipEventElapsedTime(ms, t->ev_refit[0], t->ev_refit[1]));
-	return SRT_OK;
-}
-
-int srt_read_bvh_blocks(srt_tracer *t, uint32_t *blocks_out, size_t blocks_cap, size_t *n_blocks) {
-	if (!t || !n_blocks) return SRT_ERR_INVALID;
-	const size_t n = t->bvh_active ? t->bvh_num_blocks : 0;
-	*n_blocks = n;
-	const size_t take = n < blocks_cap ? n : blocks_cap;
-	if (!blocks_out || take == 0) return SRT_OK;
-	SRT_HIP(t, hipSetDevice(t->device));
-	SRT_HIP(t, hipStreamSynchronize(t->stream));
-	SRT_HIP(t, hipMemcpy(blocks_out, t->bvh_blocks.ptr, take * 32 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-	return SRT_OK;
-}
-
-int srt_acceleration_info(const srt_tracer *t, uint64_t out[7]) {
-	if (!t || !out) return SRT_ERR_INVALID;
-	for (int i = 0; i < 7; i++) out[i] = t->bvh_active ? t->bvh_info[i] : 0;
 	return SRT_OK;
 }
 

@@ -1,6 +1,6 @@
 // srt_internal.h — the handle behind `srt_tracer *` and the small helpers the translation units of
-// libsrt_hip.so share (srt_abi.hip: life cycle, scene upload, trace; srt_collect.hip: multi-GPU collection,
-// frame pipeline). What of the host side needs no handle and no HIP is not here: bvh_host.h, scene_prep.h, trace_plan.h.
+// libsrt_hip.so share (srt_abi.hip: life cycle, scene upload, trace; accel_device.hip: BVH upkeep on the device;
+// srt_collect.hip: multi-GPU collection, frame pipeline). What of the host side needs no handle and no HIP is not here: bvh_host.h, scene_prep.h, trace_plan.h.
 // Not part of the public ABI.
 #ifndef SRT_INTERNAL_H
 #define SRT_INTERNAL_H
@@ -13,6 +13,7 @@
 
 #include "../../include/srt_abi.h"
 #include "device_types.h"
+#include "scene_prep.h"
 
 template <class T>
 struct DevBuf {
@@ -33,6 +34,103 @@ struct DevBuf {
 		if (ptr) (void)hipFree(ptr);
 		ptr = nullptr;
 		cap = 0;
+	}
+};
+
+// A device result on its way to the host: a pinned host copy that only ever grows, the event behind the copy (made with the
+// first buffer), `pending` until somebody has waited for it
+template <class T>
+struct PinnedReadback {
+	T *host = nullptr; // pinned, cap elements
+	size_t cap = 0;
+	hipEvent_t done = nullptr;
+	bool pending = false;
+	hipError_t reserve(size_t n) {
+		if (cap < n) {
+			if (host) (void)hipHostFree(host);
+			host = nullptr, cap = 0;
+			if (hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&host), n * sizeof(T), hipHostMallocDefault)) return e;
+			cap = n;
+		}
+		return done ? hipSuccess : hipEventCreateWithFlags(&done, hipEventDisableTiming);
+	}
+	hipError_t copy(const T *dev, size_t n, hipStream_t stream) { // n <= cap elements, behind what the stream holds
+		hipError_t e = hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, stream);
+		if (e == hipSuccess) e = hipEventRecord(done, stream);
+		pending = e == hipSuccess;
+		return e;
+	}
+	hipError_t wait() { // for the copy alone, not for the stream
+		const hipError_t e = pending ? hipEventSynchronize(done) : hipSuccess;
+		if (e == hipSuccess) pending = false;
+		return e;
+	}
+	void release() {
+		if (host) (void)hipHostFree(host);
+		if (done) (void)hipEventDestroy(done);
+		*this = PinnedReadback();
+	}
+};
+
+// Two events around a stretch of a stream, made on first use; `timed` once the second is recorded (the owner clears it)
+struct TimedSpan {
+	hipEvent_t ev[2] = {nullptr, nullptr};
+	bool timed = false;
+	hipError_t begin(hipStream_t stream) {
+		for (hipEvent_t &e : ev)
+			if (hipError_t rc = e ? hipSuccess : hipEventCreate(&e)) return rc;
+		return hipEventRecord(ev[0], stream);
+	}
+	hipError_t end(hipStream_t stream) {
+		const hipError_t e = hipEventRecord(ev[1], stream);
+		timed = e == hipSuccess;
+		return e;
+	}
+	hipError_t elapsed(float *ms) const { return timed ? hipEventElapsedTime(ms, ev[0], ev[1]) : hipSuccess; } // (the stream has passed it)
+	void release() {
+		for (hipEvent_t e : ev)
+			if (e) (void)hipEventDestroy(e);
+		*this = TimedSpan();
+	}
+};
+
+// Upkeep of the BVH on the device (accel_device.hip, which alone reads it): the state of the last upload, by owner
+struct AccelDevice {
+	// in-place refit (bvh_refit.hip; SRT_REFIT_DEVICE): the refitted models, their extents, inner blocks by level, a box per block
+	DevBuf<RefitModel> refit_models;
+	DevBuf<uint32_t> refit_extents, refit_sched;
+	DevBuf<float> refit_boxes;
+	uint64_t refit_info[4] = {0, 0, 0, 0};
+	TimedSpan refit_span; // around the refit launches, when the kernel timers are on
+	// a deformed model keeps its hierarchy (SRT_DEFORM_REFIT): the counts, the cost launch's inputs on the device and its sums
+	// on their way back (pending until srt_accel_deform_consume)
+	uint64_t deform_info[4] = {0, 0, 0, 0};
+	DevBuf<RefitCostRange> deform_ranges;
+	DevBuf<uint8_t> deform_weights;
+	DevBuf<double> deform_sums;
+	PinnedReadback<double> deform_sums_back;
+	std::vector<size_t> deform_entry;  // per refitted model: its entry in the cache, its cost as built
+	std::vector<double> deform_built, deform_ratio; // deform_ratio: cost now / as built once the sums are in; 0 = unknown
+	std::vector<uint8_t> deform_fresh; // per cost range: a model built by that upload (its sum is its cost as built)
+	double deform_worst_host = 0.0;    // the largest ratio among the models the device did not refit
+	// a model's hierarchy built on the device (bvh_build.hip; SRT_BUILD_DEVICE): the built models, their extents, the sort's two
+	// key / index buffers (a slot per record of the scene) and its histogram table, the counts, and the scene's sorted order
+	// array on its way back (pending until srt_accel_build_consume)
+	DevBuf<RefitModel> build_models;
+	DevBuf<uint32_t> build_extents, build_keys[2], build_vals[2], build_table;
+	DevBuf<uint32_t> build_ranges_dev; // SRT_BUILD_ORDER_MEDIAN only: per built model its first range slot, then six dwords per range (device_types.h BuildParams)
+	std::vector<uint32_t> build_ranges_host; // ... and what it is uploaded from
+	uint64_t build_info[4] = {0, 0, 0, 0};
+	PinnedReadback<uint32_t> build_order_back;
+	std::vector<size_t> build_entry;      // per built model: its entry in the cache ...
+	std::vector<RefitModel> build_ranges; // ... and its records
+	TimedSpan build_span; // around the build launches and the refit behind them, when the kernel timers are on
+	void release() {
+		refit_models.release(), refit_extents.release(), refit_sched.release(), refit_boxes.release(), refit_span.release();
+		deform_ranges.release(), deform_weights.release(), deform_sums.release(), deform_sums_back.release();
+		build_models.release(), build_extents.release(), build_table.release(), build_ranges_dev.release();
+		for (int k = 0; k < 2; k++) build_keys[k].release(), build_vals[k].release();
+		build_order_back.release(), build_span.release();
 	}
 };
 
@@ -59,57 +157,11 @@ struct srt_tracer {
 	DevBuf<float> sky;
 	DevBuf<uint32_t> bvh_blocks; // wide hierarchy, 32 dwords per block (device_types.h)
 	DevBuf<uint32_t> bvh_order, bvh_dest;
-	int accel_mode = SRT_ACCEL_NONE; // what the next srt_update_scene builds
+	AccelPolicy policy;              // what the next srt_update_scene builds and who keeps it up (scene_prep.h; the srt_set_acceleration* setters)
 	bool bvh_active = false;         // the current scene's models carry BVH roots
 	uint64_t bvh_info[7] = {0, 0, 0, 0, 0, 0, 0};
-	// in-place refit on the device (bvh_refit.hip; srt_set_acceleration_refit)
-	int refit_mode = SRT_REFIT_HOST;  // who refits a moved model at the next srt_update_scene
-	size_t bvh_num_blocks = 0;        // blocks of the current scene in bvh_blocks (srt_read_bvh_blocks)
-	DevBuf<RefitModel> refit_models;  // the last upload's refitted models, their extents, inner blocks by level, and a box per block
-	DevBuf<uint32_t> refit_extents, refit_sched;
-	DevBuf<float> refit_boxes;
-	uint64_t refit_info[4] = {0, 0, 0, 0};
-	hipEvent_t ev_refit[2] = {nullptr, nullptr}; // around the refit launches, when the kernel timers are on
-	bool refit_timed = false;
-	// a deformed model keeps its hierarchy (srt_set_acceleration_deform): the policy of the next srt_update_scene, and of the last
-	// one its counts, the cost launch's inputs on the device and its sums on their way back -- device sums, a pinned host copy,
-	// the event behind the copy; deform_pending until somebody has waited for it (srt_deform_consume)
-	int deform_mode = SRT_DEFORM_REBUILD;
-	float deform_rebuild_ratio = 0.0f;
-	uint64_t deform_info[4] = {0, 0, 0, 0};
-	DevBuf<RefitCostRange> deform_ranges;
-	DevBuf<uint8_t> deform_weights;
-	DevBuf<double> deform_sums;
-	double *deform_sums_host = nullptr; // pinned, deform_sums_cap doubles
-	size_t deform_sums_cap = 0;
-	hipEvent_t ev_deform = nullptr;
-	bool deform_pending = false;
-	std::vector<size_t> deform_entry;  // per refitted model of the last upload: its entry in the cache, its cost as built
-	std::vector<double> deform_built, deform_ratio; // deform_ratio: cost now / as built once the sums are in; 0 = unknown
-	double deform_worst_host = 0.0;    // the largest ratio among the models the device did not refit
-	// a model's hierarchy built on the device (bvh_build.hip; srt_set_acceleration_build): the policy of the next srt_update_scene;
-	// of the last one the built models, their extents, the sort's two key / index buffers (a slot per record of the scene) and
-	// its histogram table, the counts, and the sorted order on its way back to the host -- a pinned copy of the scene's order
-	// array and the event behind the copy; build_pending until somebody has waited for it (build_consume in srt_abi.hip)
-	int build_mode = SRT_BUILD_HOST;
-	uint32_t build_min_triangles = 0;
-	int build_order = SRT_BUILD_ORDER_MORTON; // srt_set_acceleration_build_order
-	// SRT_BUILD_ORDER_MEDIAN only: per built model its first range slot, then six dwords per range (device_types.h BuildParams), and
-	// the host vector it is uploaded from
-	DevBuf<uint32_t> build_ranges_dev;
-	std::vector<uint32_t> build_ranges_host;
-	DevBuf<RefitModel> build_models;
-	DevBuf<uint32_t> build_extents, build_keys[2], build_vals[2], build_table;
-	uint64_t build_info[4] = {0, 0, 0, 0};
-	uint32_t *build_order_host = nullptr; // pinned, build_order_cap indices
-	size_t build_order_cap = 0;
-	hipEvent_t ev_build_done = nullptr;
-	bool build_pending = false;
-	std::vector<size_t> build_entry;             // per built model of the last upload: its entry in the cache ...
-	std::vector<RefitModel> build_ranges;        // ... and its records
-	std::vector<uint8_t> deform_fresh;           // per cost range of the last upload: a model built by it (its sum is its cost as built)
-	hipEvent_t ev_build[2] = {nullptr, nullptr}; // around the build launches and the refit behind them, when the kernel timers are on
-	bool build_timed = false;
+	size_t bvh_num_blocks = 0;       // blocks of the current scene in bvh_blocks (srt_read_bvh_blocks)
+	AccelDevice upkeep;              // refit, deform cost and build on the device (accel_device.hip)
 	struct BvhCache *bvh_cache = nullptr; // hierarchies of the previous srt_update_scene (bvh_host.h BvhCacheEntry; made by scene_prep.cpp)
 	DevBuf<unsigned long long> counters;
 	DevBuf<unsigned long long> wave_counters; // per persistent wave, summed in srt_get_counters
@@ -232,6 +284,10 @@ static inline float *gd_moments(const srt_tracer *t) { return t->gd_pack.ptr + 1
 
 
 void srt_collect_release(srt_tracer *t);
+int srt_accel_deform_consume(srt_tracer *t, BvhCache *cache); /* accel_device.hip, before the host pass: the last upload's cost sums become ratios, here and in `cache` (the handle's own, a group's first member's) */
+int srt_accel_build_consume(srt_tracer *t, BvhCache *cache);  /* before the host pass: the last upload's sorted order goes to its entries of `cache` */
+int srt_accel_before_prepass(srt_tracer *t, const ScenePrep &sp); /* SRT_BUILD_DEVICE: the order of the models this upload builds */
+int srt_accel_behind_prepass(srt_tracer *t, const ScenePrep &sp); /* SRT_REFIT_DEVICE: new boxes, the deform cost, then the built order starts its way back */
 /* srt_texture.hip: the setters' data checked against a scene that is about to be uploaded; the plane frames and triangle count of the scene being uploaded (srt_update_scene, every group member);
  * checking the setters' data against the current scene and bringing the device tables up to date (after srt_update_scene
  * and before every dispatch; sets tex_active); the tables as the textured kernels take them; freeing them */

@@ -81,10 +81,11 @@ struct Scene {
 static int prepare(int refit, int deform_mode, float ratio, BvhCache *&cache, const Scene &s, ScenePrep &sp) {
 	srt_scene_data sd;
 	memset(&sd, 0, sizeof sd);
-	DeformPolicy dp;
-	dp.mode = deform_mode, dp.rebuild_ratio = ratio;
+	AccelPolicy ap;
+	ap.accel = SRT_ACCEL_BVH, ap.refit = refit;
+	ap.deform.mode = deform_mode, ap.deform.rebuild_ratio = ratio;
 	std::string err;
-	return prepare_scene(SRT_ACCEL_BVH, refit, dp, cache, 4096, err, sp, s.shapes.data(), s.shapes.size(), s.tris.data(), s.tris.size(), s.mats.data(), s.mats.size(), &sd);
+	return prepare_scene(ap, cache, 4096, err, sp, s.shapes.data(), s.shapes.size(), s.tris.data(), s.tris.size(), s.mats.data(), s.mats.size(), &sd);
 }
 // {built, reused, refitted, kept across a deformation, rebuilt on cost}
 static bool counts(const ScenePrep &sp, uint64_t built, uint64_t reused, uint64_t refitted, uint64_t kept, uint64_t rebuilt) {

@@ -158,10 +158,11 @@ static void scene_rule() {
 	srt_scene_data sd;
 	memset(&sd, 0, sizeof sd);
 	auto prepare = [&](int mode, uint32_t min_tris, BvhCache *&cache, ScenePrep &sp) {
-		BuildPolicy bp;
-		bp.mode = mode, bp.min_triangles = min_tris;
+		AccelPolicy ap;
+		ap.accel = SRT_ACCEL_BVH;
+		ap.build.mode = mode, ap.build.min_triangles = min_tris;
 		std::string err;
-		return prepare_scene(SRT_ACCEL_BVH, SRT_REFIT_HOST, DeformPolicy(), bp, cache, 4096, err, sp, shapes.data(), shapes.size(), tris.data(), tris.size(), mats.data(), mats.size(), &sd);
+		return prepare_scene(ap, cache, 4096, err, sp, shapes.data(), shapes.size(), tris.data(), tris.size(), mats.data(), mats.size(), &sd);
 	};
 	{
 		BvhCache *cache = nullptr;

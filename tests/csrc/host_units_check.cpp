@@ -134,7 +134,9 @@ struct Scene {
 static int prepare(int accel, BvhCache *&cache, const Scene &s, ScenePrep &sp, std::string &err) {
 	srt_scene_data sd;
 	memset(&sd, 0, sizeof sd);
-	return prepare_scene(accel, cache, 4096, err, sp, s.shapes.data(), s.shapes.size(), s.tris.data(), s.tris.size(), s.mats.data(), s.mats.size(), &sd);
+	AccelPolicy ap;
+	ap.accel = accel;
+	return prepare_scene(ap, cache, 4096, err, sp, s.shapes.data(), s.shapes.size(), s.tris.data(), s.tris.size(), s.mats.data(), s.mats.size(), &sd);
 }
 
 // prepares `s` with the persistent cache, expects (built, reused, refitted), and the arrays of a preparation that starts from nothing
