@@ -554,6 +554,60 @@ int srt_motion_table_host(const srt_shape *h_shapes, size_t h_n_shapes, const sr
                           const srt_shape *c_shapes, size_t c_n_shapes, const srt_triangle *c_triangles, size_t c_n_triangles,
                           const srt_material *c_materials, size_t c_n_materials, const srt_scene_data *c_scene, uint32_t *table, int *keep);
 
+/* ---- per-triangle motion for the temporal stage (new) ---------------------------------------------------------------- */
+
+/* Opt-in, on top of srt_set_denoise_object_motion: the history also survives an srt_update_scene that changes the vertices
+ * of a model (skinning, cloth, morph targets) as long as the topology stays. While it is on:
+ *   keep rule   object motion's, except that the triangle arrays need only have the same count: each model keeps its
+ *               triangle_index and num_triangles, the bytes inside a model's range may differ, bytes no model's range
+ *               covers are not compared. A model with a differing byte in its range is DEFORMED (whether or not its
+ *               transform changed too), and so is every instance over that range; a model whose range is the same bytes is
+ *               STATIC, MOVED or NO_HISTORY as without the switch.
+ *   table       a DEFORMED row holds the state in word 0, the shape's first row in the vertex tables in word 1, zeros else.
+ *   triangles   the feature pass also stores, per pixel, the index inside its model of the triangle feature sample 0 of the
+ *               latest dispatch hit (0xffffffff: a miss, a shape without a material, not a model): 4 B per pixel, twice.
+ *   vertices    two tables (the frame's, the history's) of 9 floats per instance triangle: P0, P1, P2 = transform * vertex
+ *               in the tracer's own expressions, so they are the traced world vertices bit for bit. Model shapes in shape
+ *               order, triangle j of a model in row first_row + j. The frame's table is written by one launch before the
+ *               first feature pass after an srt_update_scene with other bytes (not at the update: the history keeps the
+ *               scene its frame was traced with); srt_clear_canvas's commit swaps the two. 72 B per instance triangle and
+ *               table, allocated with the first enable over a scene with triangles.
+ *   a pixel     of a DEFORMED shape with triangle t (none, or t >= num_triangles: no history), rows P (frame) and Q
+ *               (history) at first_row + t, all float32, unfused, dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z:
+ *                 e1 = P1 - P0, e2 = P2 - P0, f1 = Q1 - Q0, f2 = Q2 - Q0, X = the first hit, d = X - P0
+ *                 a11 = dot(e1, e1), a12 = dot(e1, e2), a22 = dot(e2, e2), det = a11 a22 - a12 a12 (not > 0 or not
+ *                 finite: no history)
+ *                 u = (a22 dot(d, e1) - a12 dot(d, e2)) / det, v = (a11 dot(d, e2) - a12 dot(d, e1)) / det (not clamped)
+ *                 X_h = (Q0 + u f1) + v f2 (not finite: no history)
+ *                 gc = cross(e1, e2) / |cross(e1, e2)|, gh likewise of f1, f2 (a zero or non-finite length: no history)
+ *                 nu, nv = the same solve with the pixel's normal N_p for d, c = dot(N_p, gc)
+ *                 N_h = normalise((nu f1 + nv f2) + c gh) (a zero or non-finite length: no history)
+ *               X_h is projected into the history camera (also for the same camera); a tap counts only when its history
+ *               shape index is the pixel's, its normal is compared with N_h and its depth with |X_h - cam_h|, as for a
+ *               MOVED shape. Exact for rigid motion and for flat normals under any deformation; under stretch a smooth
+ *               normal's tilt is distorted and the test errs towards no history.
+ *   a STATIC pixel rejects a tap whose history shape is MOVED or DEFORMED; MOVED and NO_HISTORY pixels are unchanged.
+ * With the switch off the library enqueues what it enqueues without it and keeps every drop rule. Another triangle count or
+ * another topology drops the history as before; lighting is not tracked (see above). */
+enum { SRT_MOTION_DEFORMED = 3 };
+
+/* enable != 0: on. SRT_ERR_STATE unless object motion is on (so never on a partitioned handle). Turning object motion,
+ * temporal reprojection or the denoiser off turns it off. Every change of the switch drops the history. */
+int srt_set_denoise_vertex_motion(srt_tracer *t, int enable);
+/* The triangle indices (blocking; NULL skips an output; width*height words each), as srt_read_denoise_shape_ids.
+ * SRT_ERR_STATE when per-triangle motion was never enabled on this handle. */
+int srt_read_denoise_triangle_ids(srt_tracer *t, uint32_t *current, uint32_t *history);
+/* The world-vertex tables (blocking; NULL skips an output): *n_rows = rows of the current scene, 9 floats each; current = the
+ * table as last written (before the first dispatch after an update: the previous contents), history = the history frame's
+ * (zeros without a history). SRT_ERR_INVALID when an output is given and cap_rows < *n_rows (still set). SRT_ERR_STATE when
+ * per-triangle motion was never enabled on this handle. */
+int srt_read_denoise_vertex_tables(srt_tracer *t, float *current, float *history, size_t cap_rows, size_t *n_rows);
+/* Host-only: srt_motion_table_host with the keep rule above (what srt_update_scene applies while the switch is on). */
+int srt_motion_table_deform_host(const srt_shape *h_shapes, size_t h_n_shapes, const srt_triangle *h_triangles, size_t h_n_triangles,
+                                 const srt_material *h_materials, size_t h_n_materials, const srt_scene_data *h_scene,
+                                 const srt_shape *c_shapes, size_t c_n_shapes, const srt_triangle *c_triangles, size_t c_n_triangles,
+                                 const srt_material *c_materials, size_t c_n_materials, const srt_scene_data *c_scene, uint32_t *table, int *keep);
+
 /* ---- albedo demodulation for the filter (new; SVGF's own: filter illumination, not colour) ------------------------------ */
 
 /* Opt-in. With it on and iterations K >= 1 the a-trous passes run over the illumination I = colour / albedo instead of the

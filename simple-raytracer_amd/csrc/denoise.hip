@@ -247,11 +247,14 @@ int srt_denoise_clear(srt_tracer *t) {
 // the feature pass's one fork: the kernels of the dispatch's kind (albedo textures: the texel at the first hit is the albedo,
 // srt_texture.hip), storing shape indices when object motion is on (temporal.hip)
 static void launch_features(srt_tracer *t, const FeatureParams &fp) {
+	const bool tris = t->om_on && t->vm_on; // per-triangle motion: the hit triangle's index beside the shape's
 	if (t->last_trace_textured) {
 		const TexFeatureParams fx = srt_with_textures<TexFeatureParams>(t, fp);
-		if (t->om_on) srt_launch_features_ids_tex(fx, t->om_ids[t->om_cur].ptr, t->stream);
+		if (tris) srt_launch_features_tris_tex(fx, t->om_ids[t->om_cur].ptr, t->vm_tri[t->om_cur].ptr, t->stream);
+		else if (t->om_on) srt_launch_features_ids_tex(fx, t->om_ids[t->om_cur].ptr, t->stream);
 		else srt_launch_features_tex(fx, t->stream);
-	} else if (t->om_on) srt_launch_features_ids(fp, t->om_ids[t->om_cur].ptr, t->stream);
+	} else if (tris) srt_launch_features_tris(fp, t->om_ids[t->om_cur].ptr, t->vm_tri[t->om_cur].ptr, t->stream);
+	else if (t->om_on) srt_launch_features_ids(fp, t->om_ids[t->om_cur].ptr, t->stream);
 	else srt_launch_features(fp, t->stream);
 }
 
@@ -266,6 +269,10 @@ int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples
 	fp.albedo_hits = t->gd_on ? gd_albedo_hits(t) : t->dn_ah.ptr;
 	fp.num_pixels = (uint32_t)(t->gd_on ? owned_pixels(t) : full_pixels(t));
 	fp.feature_samples = fs;
+	if (t->om_on && t->vm_on && fs > 0) { // the world vertices this frame is traced with, once per scene
+		const int vrc = srt_vertex_table_sync(t);
+		if (vrc) return vrc;
+	}
 	launch_features(t, fp);
 	SRT_HIP(t, hipGetLastError());
 	if (t->gd_on) return SRT_OK;
@@ -397,6 +404,7 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 		t->dn_demod = false; // albedo demodulation is a mode of the filter
 		t->tp_on = false; // temporal reprojection is a stage of the denoiser
 		t->om_on = false; // and object motion a stage of that
+		t->vm_on = false; // (with its per-triangle part)
 		srt_temporal_drop(t);
 		return SRT_OK;
 	}

@@ -295,6 +295,7 @@ void srt_launch_trace_tex(TexTraceParams p, bool count_triangles, int num_waves,
 int srt_trace_tex_resident_waves_per_cu(const TexTraceParams &p, bool count_triangles);
 void srt_launch_features_tex(const TexFeatureParams &p, void *stream);
 void srt_launch_features_ids_tex(const TexFeatureParams &p, uint32_t *shape_ids, void *stream);
+void srt_launch_features_tris_tex(const TexFeatureParams &p, uint32_t *shape_ids, uint32_t *tri_ids, void *stream);
 
 void srt_launch_trace(TraceParams p, bool count_triangles, int num_waves, void *stream);
 void srt_launch_reduce(const ReduceParams &p, void *stream);
@@ -303,6 +304,8 @@ void srt_launch_reduce_moments(const ReduceParams &p, void *stream);
 void srt_launch_features(const FeatureParams &p, void *stream);
 /* the same, also storing the shape index of feature sample 0 per pixel (0xffffffff: no hit or no material) into shape_ids */
 void srt_launch_features_ids(const FeatureParams &p, uint32_t *shape_ids, void *stream);
+/* the same, also storing the index inside its model of the triangle that sample hit (0xffffffff: no hit, no material, not a model) into tri_ids */
+void srt_launch_features_tris(const FeatureParams &p, uint32_t *shape_ids, uint32_t *tri_ids, void *stream);
 int srt_trace_waves_per_simd(int has_models, int use_bvh);
 int srt_trace_has_scene_classes(); /* 1 when this build of kernels.hip holds the SRT_SCENE_CLASS_LIST instantiations */
 int srt_trace_resident_waves_per_cu(const TraceParams &p, bool count_triangles); /* from the runtime's occupancy calculator */

@@ -1,7 +1,9 @@
 // features_body.inc -- the body of srt_features_kernel and srt_features_ids_kernel (kernels.hip includes it once for each, so
 // that the two are the same statements in the same place: a shared __device__ function schedules the first differently).
 // In scope: fp (FeatureParams), HAS_MODELS, USE_BVH; SRT_FEATURES_IDS 0 / 1; with 1 also shape_ids (uint32_t *): the shape
-// index of feature sample 0 per pixel, 0xffffffff for a miss or a shape without a material, a plain store.
+// index of feature sample 0 per pixel, 0xffffffff for a miss or a shape without a material, a plain store. SRT_FEATURES_IDS 2
+// (srt_features_tris_kernel) is 1 and tri_ids (uint32_t *): the index inside its model of the triangle that sample hit (what
+// winner_normal takes), 0xffffffff also for a sphere or a plane.
 	const TraceParams &p = fp.tp;
 	const uint32_t q = blockIdx.x * 64u + threadIdx.x;
 	if (q >= fp.num_pixels) return;
@@ -32,6 +34,9 @@
 	float tsum = 0.f, hits = 0.f;
 #if SRT_FEATURES_IDS
 	uint32_t id0 = 0xffffffffu;
+#endif
+#if SRT_FEATURES_IDS == 2
+	uint32_t tri0 = 0xffffffffu;
 #endif
 	for (uint32_t sample = 0; sample < fp.feature_samples; sample++) {
 		// ---- camera ray: srt_trace_kernel CAMERA ----
@@ -97,12 +102,19 @@
 #if SRT_FEATURES_IDS
 			if (sample == 0) id0 = (uint32_t)best;
 #endif
+#if SRT_FEATURES_IDS == 2
+			if (HAS_MODELS && sample == 0 && p.winners[best].type == SRT_SHAPE_MODEL)
+				tri0 = USE_BVH ? bvh_tri_in_model(reinterpret_cast<const float4 *>(p.bvh_blocks), best_tri) : best_tri;
+#endif
 		} else {
 			asum = asum + mk(1.f, 1.f, 1.f);
 		}
 	}
 #if SRT_FEATURES_IDS
 	shape_ids[q] = id0;
+#endif
+#if SRT_FEATURES_IDS == 2
+	tri_ids[q] = tri0;
 #endif
 	float4 *nd = reinterpret_cast<float4 *>(fp.normal_depth) + q;
 	float4 *ah = reinterpret_cast<float4 *>(fp.albedo_hits) + q;

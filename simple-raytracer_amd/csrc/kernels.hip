@@ -54,10 +54,12 @@
 #define srt_trace_kernel srt_trace_tex_kernel
 #define srt_features_kernel srt_features_tex_kernel
 #define srt_features_ids_kernel srt_features_ids_tex_kernel
+#define srt_features_tris_kernel srt_features_tris_tex_kernel
 #define srt_launch_trace srt_launch_trace_tex
 #define srt_trace_resident_waves_per_cu srt_trace_tex_resident_waves_per_cu
 #define srt_launch_features srt_launch_features_tex
 #define srt_launch_features_ids srt_launch_features_ids_tex
+#define srt_launch_features_tris srt_launch_features_tris_tex
 int srt_trace_lds_floats(int has_models, int use_bvh);
 #else
 #define SRT_TRACE_PARAMS TraceParams
@@ -298,6 +300,14 @@ __global__ __launch_bounds__(64) void srt_features_ids_kernel(const SRT_FEATURE_
 #undef SRT_FEATURES_IDS
 }
 
+// the same, and the hit triangle's index inside its model for the temporal stage's per-triangle motion (temporal.hip)
+template <bool HAS_MODELS, bool USE_BVH>
+__global__ __launch_bounds__(64) void srt_features_tris_kernel(const SRT_FEATURE_PARAMS fp, uint32_t *__restrict__ shape_ids, uint32_t *__restrict__ tri_ids) {
+#define SRT_FEATURES_IDS 2
+#include "features_body.inc"
+#undef SRT_FEATURES_IDS
+}
+
 // ---------------------------------------------------------------------------------
 // launch wrappers (host)
 // ---------------------------------------------------------------------------------
@@ -403,4 +413,12 @@ void srt_launch_features_ids(const SRT_FEATURE_PARAMS &p, uint32_t *shape_ids, v
 	const bool models = p.tp.num_models > 0, bvh = p.tp.use_bvh != 0;
 	const FeatureKernel k = !models ? srt_features_ids_kernel<false, false> : bvh ? srt_features_ids_kernel<true, true> : srt_features_ids_kernel<true, false>;
 	hipLaunchKernelGGL(k, dim3((p.num_pixels + 63u) / 64u), dim3(64), 0, (hipStream_t)stream, p, shape_ids);
+}
+
+void srt_launch_features_tris(const SRT_FEATURE_PARAMS &p, uint32_t *shape_ids, uint32_t *tri_ids, void *stream) {
+	if (p.num_pixels == 0 || p.feature_samples == 0) return;
+	typedef void (*FeatureKernel)(const SRT_FEATURE_PARAMS, uint32_t *, uint32_t *);
+	const bool models = p.tp.num_models > 0, bvh = p.tp.use_bvh != 0;
+	const FeatureKernel k = !models ? srt_features_tris_kernel<false, false> : bvh ? srt_features_tris_kernel<true, true> : srt_features_tris_kernel<true, false>;
+	hipLaunchKernelGGL(k, dim3((p.num_pixels + 63u) / 64u), dim3(64), 0, (hipStream_t)stream, p, shape_ids, tri_ids);
 }

@@ -214,6 +214,8 @@ void srt_destroy(srt_tracer *t) {
 	t->om_ids[0].release();
 	t->om_ids[1].release();
 	t->om_table_dev.release();
+	for (int k = 0; k < 2; k++) t->vm_tri[k].release(), t->vm_rows[k].release();
+	t->vm_first_dev.release();
 	srt_texture_release(t);
 	if (t->ev_t0) (void)hipEventDestroy(t->ev_t0);
 	if (t->ev_t1) (void)hipEventDestroy(t->ev_t1);

@@ -225,6 +225,17 @@ struct srt_tracer {
 	std::vector<uint8_t> om_hist_scene; // scene_bytes of the history frame
 	std::vector<uint32_t> om_table;     // SRT_MOTION_WORDS per shape of the current scene: the next filter's current -> history maps
 	DevBuf<uint32_t> om_table_dev;
+	// per-triangle motion (temporal.hip; srt_set_denoise_vertex_motion): beside the shape index the feature pass stores the
+	// hit triangle's index inside its model into vm_tri[om_cur], and vm_rows[om_cur] holds the frame's world vertices (9
+	// floats per instance triangle, shape vm_first[s]'s first row; vm_first[n_shapes] = all rows). The commit swaps both
+	// with om_cur. vm_ver[k] names the scene vm_rows[k] was written from (0: none), vm_scene_ver the current scene
+	bool vm_on = false;
+	bool om_any_deformed = false; // a shape of om_table is SRT_MOTION_DEFORMED (the deform set-up kernel runs)
+	DevBuf<uint32_t> vm_tri[2];
+	DevBuf<float> vm_rows[2];
+	std::vector<uint32_t> vm_first;
+	DevBuf<uint32_t> vm_first_dev;
+	uint64_t vm_scene_ver = 1, vm_ver[2] = {0, 0};
 	// group denoiser (srt_collect.hip srt_group_set_denoise): a member of a device group accumulates the denoiser's inputs for
 	// its OWN rows, packed as its canvas rows are. gd_pack is ONE allocation of srt_planes_slot_floats() floats that one collective
 	// sends: the canvas rows (bound as the canvas, the way srt_bind_canvas does), the normal_depth and albedo_hits planes
@@ -332,6 +343,8 @@ void srt_temporal_drop(srt_tracer *t);
 /* srt_update_scene with object motion on (`bytes`: the new scene, scene_bytes still the previous call's; rc: the update's
  * result): keeps or drops the history and rebuilds the motion table */
 int srt_motion_update_scene(srt_tracer *t, const std::vector<uint8_t> &bytes, int rc);
+/* per-triangle motion, before a feature pass: the frame's world-vertex table, written when the scene has changed since */
+int srt_vertex_table_sync(srt_tracer *t);
 /* srt_trace whose last reduction also resolves into fused_argb (device, owned pixels x 4 bytes; NULL: plain srt_trace); with a
  * denoiser on, the feature pass and the filter (a group member on its own: the plain resolve) follow the reductions. A
  * sequence of file-local steps in srt_abi.hip; the arithmetic they share with the host unit check is trace_plan.h's */

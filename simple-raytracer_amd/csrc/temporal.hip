@@ -18,6 +18,7 @@
 // bit-identical.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -87,6 +88,55 @@ __global__ __launch_bounds__(256) void srt_temporal_motion_kernel(const Temporal
 #define SRT_TEMPORAL_MOTION 1
 #include "temporal_body.inc"
 #undef SRT_TEMPORAL_MOTION
+}
+
+// per-triangle motion (srt_set_denoise_vertex_motion): the frame's triangle index per pixel, the world-vertex tables of the
+// frame and of the history (9 floats per instance triangle: P0, P1, P2) and each shape's first row (n_shapes + 1 entries)
+struct VertexParams {
+	const uint32_t *tris;
+	const float *rows, *h_rows;
+	const uint32_t *first;
+};
+
+// The set-up when a shape of the table is DEFORMED: the moved kernel, and per pixel of a DEFORMED shape the map of
+// include/srt_abi.h ("per-triangle motion"): the point at the same barycentric place of the same triangle as it stood in the
+// history frame. tests/vertex_motion_ref.py restates it.
+__global__ __launch_bounds__(256) void srt_temporal_deform_kernel(const TemporalParams p, const MotionParams mp, const VertexParams vp) {
+#define SRT_TEMPORAL_MOTION 2
+#include "temporal_body.inc"
+#undef SRT_TEMPORAL_MOTION
+}
+
+// The world-vertex table of a scene: blockIdx.y = shape (models only), row first[shape] + j = triangle j's P0, P1, P2 in the
+// pre-pass's expressions (frame.hip srt_prepass_kernel: mat_by_vec(transform, pos, 1.0f)), so the rows are the tracer's world
+// vertices bit for bit, in array order whatever the acceleration stores.
+struct VertexTableParams {
+	const srt_shape *shapes;
+	const srt_triangle *triangles;
+	const uint32_t *first; // per shape of this slab: its first row (one entry more: the end of the last)
+	float *rows;
+	int32_t num_shapes;
+};
+
+__global__ __launch_bounds__(256) void srt_vertex_table_kernel(const VertexTableParams p) {
+	const int si = blockIdx.y;
+	if (si >= p.num_shapes) return;
+	const srt_shape *sh = p.shapes + si;
+	if (sh->type != SRT_SHAPE_MODEL) return;
+	const srt_model *m = &sh->shape.model;
+	const srt_float4 *tm = m->transform;
+	const uint32_t room = p.first[si + 1] - p.first[si]; // the model's rows (= num_triangles; never past them)
+	const uint32_t n = m->num_triangles < room ? m->num_triangles : room;
+	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
+		const srt_triangle *t = p.triangles + (m->triangle_index + j);
+		float *w = p.rows + (size_t)(p.first[si] + j) * 9;
+		for (int k = 0; k < 3; k++) {
+			const srt_float3 &v = t->vertices[k].pos;
+			w[3 * k + 0] = ((tm[0].x * v.x + tm[1].x * v.y) + tm[2].x * v.z) + tm[3].x * 1.0f;
+			w[3 * k + 1] = ((tm[0].y * v.x + tm[1].y * v.y) + tm[2].y * v.z) + tm[3].y * 1.0f;
+			w[3 * k + 2] = ((tm[0].z * v.x + tm[1].z * v.y) + tm[2].z * v.z) + tm[3].z * 1.0f;
+		}
+	}
 }
 
 // set offsets, in floats: {colour, count} float4, {m1, m2} float2, guide 2 float4
@@ -230,12 +280,15 @@ bool model_row(const srt_model &h, const srt_model &c, uint32_t *row) {
 }
 
 // the rules of include/srt_abi.h: false = drop the history; else `table` gets SRT_MOTION_WORDS words per shape
-bool motion_table(const SceneView &h, const SceneView &c, uint32_t *table, bool *any_moved) {
+// `deform` (per-triangle motion): the triangle arrays need only have the same count; a model whose range differs in a byte
+// is DEFORMED {state, its first row in the vertex tables, zeros}, bytes outside every range are not compared
+bool motion_table(const SceneView &h, const SceneView &c, uint32_t *table, bool *any_moved, bool deform = false, bool *any_deformed = nullptr) {
 	*any_moved = false;
+	if (any_deformed) *any_deformed = false;
 	if (h.n_shapes != c.n_shapes || h.tri_bytes != c.tri_bytes || h.mat_bytes != c.mat_bytes) return false;
 	if (memcmp(h.scene, c.scene, sizeof(srt_scene_data)) != 0) return false;
 	if (h.mat_bytes && memcmp(h.mats, c.mats, h.mat_bytes) != 0) return false;
-	if (h.tri_bytes && memcmp(h.tris, c.tris, h.tri_bytes) != 0) return false;
+	if (!deform && h.tri_bytes && memcmp(h.tris, c.tris, h.tri_bytes) != 0) return false;
 	for (size_t k = 0; k < c.n_shapes; k++) {
 		const srt_shape &a = h.shapes[k], &b = c.shapes[k];
 		if (a.type != b.type || a.material != b.material) return false;
@@ -243,11 +296,29 @@ bool motion_table(const SceneView &h, const SceneView &c, uint32_t *table, bool 
 			const srt_model &ma = a.shape.model, &mb = b.shape.model;
 			// (bounding_min / bounding_max are the world box of the transformed vertices: they move with the transform)
 			if (ma.triangle_index != mb.triangle_index || ma.num_triangles != mb.num_triangles) return false;
+			// (a range outside the array: srt_update_scene refuses such a scene)
+			if (deform && ((uint64_t)mb.triangle_index + mb.num_triangles) * sizeof(srt_triangle) > c.tri_bytes) return false;
 		}
 	}
+	uint64_t first_row = 0;
 	for (size_t k = 0; k < c.n_shapes; k++) {
 		const srt_shape &a = h.shapes[k], &b = c.shapes[k];
 		uint32_t *row = table + k * SRT_MOTION_WORDS;
+		if (deform && a.type == SRT_SHAPE_MODEL) {
+			const srt_model &mb = b.shape.model;
+			const size_t off = (size_t)mb.triangle_index * sizeof(srt_triangle), len = (size_t)mb.num_triangles * sizeof(srt_triangle);
+			const uint64_t row0 = first_row;
+			first_row += mb.num_triangles;
+			if (first_row > 0xffffffffull) return false;
+			if (len && memcmp(static_cast<const uint8_t *>(h.tris) + off, static_cast<const uint8_t *>(c.tris) + off, len) != 0) {
+				memset(row, 0, SRT_MOTION_WORDS * sizeof(uint32_t));
+				row[0] = SRT_MOTION_DEFORMED;
+				row[1] = (uint32_t)row0;
+				*any_moved = true;
+				if (any_deformed) *any_deformed = true;
+				continue;
+			}
+		}
 		if (memcmp(&a, &b, sizeof a) == 0) {
 			identity_rows(row, 1, SRT_MOTION_STATIC);
 			continue;
@@ -269,6 +340,35 @@ void static_table(srt_tracer *t) {
 	t->om_table.resize(n * SRT_MOTION_WORDS);
 	identity_rows(t->om_table.data(), n, SRT_MOTION_STATIC);
 	t->om_any_moved = false;
+	t->om_any_deformed = false;
+}
+
+// per-triangle motion: the rows of scene `bytes` (vm_first, on the host and on the device) and room for both tables. A
+// table that had to grow holds nothing (the history it belonged to is dropped with the triangle count)
+int vertex_layout(srt_tracer *t, const std::vector<uint8_t> &bytes) {
+	SceneView v;
+	const size_t n = view_of(bytes, v) ? v.n_shapes : 0;
+	std::vector<uint32_t> first(n + 1, 0u);
+	uint64_t rows = 0;
+	for (size_t k = 0; k < n; k++) {
+		first[k] = (uint32_t)rows;
+		if (v.shapes[k].type == SRT_SHAPE_MODEL) rows += v.shapes[k].shape.model.num_triangles;
+		if (rows > 0xffffffffull) return fail(t, SRT_ERR_INVALID, "per-triangle motion: more than 2^32 - 1 instance triangles");
+	}
+	first[n] = (uint32_t)rows;
+	if (first == t->vm_first && t->vm_first_dev.ptr && t->vm_rows[0].cap >= rows * 9 && t->vm_rows[1].cap >= rows * 9) return SRT_OK; // the layout stands
+	t->vm_first.swap(first);
+	SRT_HIP(t, hipSetDevice(t->device));
+	SRT_HIP(t, hipStreamSynchronize(t->stream)); // a set-up still on the stream reads the old rows
+	SRT_HIP(t, t->vm_first_dev.reserve(n + 1));
+	for (int k = 0; k < 2; k++) {
+		const float *before = t->vm_rows[k].ptr;
+		SRT_HIP(t, t->vm_rows[k].reserve((size_t)rows * 9));
+		if (t->vm_rows[k].ptr != before) t->vm_ver[k] = 0;
+	}
+	SRT_HIP(t, hipMemcpyAsync(t->vm_first_dev.ptr, t->vm_first.data(), (n + 1) * 4, hipMemcpyHostToDevice, t->stream));
+	SRT_HIP(t, hipStreamSynchronize(t->stream));
+	return SRT_OK;
 }
 
 // the temporal set-up into the staging set (and `col` / argb when given)
@@ -323,7 +423,15 @@ int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 		mp.h_ids = t->om_ids[1 - t->om_cur].ptr;
 		mp.table = t->om_table_dev.ptr;
 		mp.n_shapes = (uint32_t)(t->om_table.size() / SRT_MOTION_WORDS);
-		hipLaunchKernelGGL(srt_temporal_motion_kernel, grid, dim3(256), 0, t->stream, p, mp);
+		if (t->vm_on && t->om_any_deformed) { // a deformed model: its pixels look their triangles up in the two vertex tables
+			VertexParams vp;
+			vp.tris = t->vm_tri[t->om_cur].ptr;
+			vp.rows = t->vm_rows[t->om_cur].ptr;
+			vp.h_rows = t->vm_rows[1 - t->om_cur].ptr;
+			vp.first = t->vm_first_dev.ptr;
+			hipLaunchKernelGGL(srt_temporal_deform_kernel, grid, dim3(256), 0, t->stream, p, mp, vp);
+		} else
+			hipLaunchKernelGGL(srt_temporal_motion_kernel, grid, dim3(256), 0, t->stream, p, mp);
 	} else {
 		hipLaunchKernelGGL(srt_temporal_setup_kernel, grid, dim3(256), 0, t->stream, p);
 	}
@@ -370,7 +478,7 @@ int srt_temporal_commit(srt_tracer *t) {
 		if (t->om_mixed) { // traced with more than one scene: no single set of maps leads back to this frame
 			srt_temporal_drop(t);
 		} else {
-			t->om_cur = 1 - t->om_cur; // the frame's shape indices become the history's
+			t->om_cur = 1 - t->om_cur; // the frame's shape indices become the history's (with them its triangle indices and vertex table)
 			t->om_hist_scene = t->scene_bytes;
 		}
 		static_table(t);
@@ -384,14 +492,21 @@ int srt_motion_update_scene(srt_tracer *t, const std::vector<uint8_t> &bytes, in
 		return SRT_OK;
 	}
 	if (t->dn_T > 0 && bytes != t->scene_bytes) t->om_mixed = true; // samples of the old scene are on the canvas
+	if (t->vm_on && bytes != t->scene_bytes) t->vm_scene_ver++;      // the next feature pass writes this scene's vertex table
 	SceneView h, c;
 	view_of(bytes, c);
 	t->om_table.assign(c.n_shapes * SRT_MOTION_WORDS, 0u);
 	t->om_any_moved = false;
-	if (t->tp_valid && !(view_of(t->om_hist_scene, h) && motion_table(h, c, t->om_table.data(), &t->om_any_moved))) srt_temporal_drop(t);
+	t->om_any_deformed = false;
+	if (t->tp_valid && !(view_of(t->om_hist_scene, h) && motion_table(h, c, t->om_table.data(), &t->om_any_moved, t->vm_on, &t->om_any_deformed))) srt_temporal_drop(t);
 	if (!t->tp_valid) {
 		identity_rows(t->om_table.data(), c.n_shapes, SRT_MOTION_STATIC);
 		t->om_any_moved = false;
+		t->om_any_deformed = false;
+	}
+	if (t->vm_on) {
+		const int vrc = vertex_layout(t, bytes);
+		if (vrc) return vrc;
 	}
 	if (t->om_any_moved) { // with the scene upload; a set-up still running on the stream reads the old table first
 		SRT_HIP(t, hipSetDevice(t->device));
@@ -399,6 +514,33 @@ int srt_motion_update_scene(srt_tracer *t, const std::vector<uint8_t> &bytes, in
 		SRT_HIP(t, hipMemcpyAsync(t->om_table_dev.ptr, t->om_table.data(), t->om_table.size() * 4, hipMemcpyHostToDevice, t->stream));
 		SRT_HIP(t, hipStreamSynchronize(t->stream));
 	}
+	return SRT_OK;
+}
+
+int srt_vertex_table_sync(srt_tracer *t) {
+	const int cur = t->om_cur;
+	if (t->vm_ver[cur] == t->vm_scene_ver) return SRT_OK; // this table already holds the scene being traced
+	const size_t n_shapes = t->vm_first.empty() ? 0 : t->vm_first.size() - 1;
+	const uint32_t rows = n_shapes ? t->vm_first[n_shapes] : 0u;
+	// (the layout is that of the last srt_update_scene's arrays; when that call failed the device holds another scene: no table)
+	if (rows && t->scene_set && (size_t)t->sd.num_shapes == n_shapes && t->vm_rows[cur].cap >= (size_t)rows * 9) {
+		uint32_t max_tris = 0;
+		for (size_t k = 0; k < n_shapes; k++) max_tris = std::max(max_tris, t->vm_first[k + 1] - t->vm_first[k]);
+		unsigned gx = (max_tris + 255u) / 256u;
+		if (gx > 4096u) gx = 4096u;
+		for (size_t base = 0; base < n_shapes; base += 65535) { // blockIdx.y = shape index, in slabs as the pre-pass
+			VertexTableParams vt;
+			vt.shapes = t->shapes.ptr + base;
+			vt.triangles = t->triangles.ptr;
+			vt.first = t->vm_first_dev.ptr + base;
+			vt.rows = t->vm_rows[cur].ptr;
+			const size_t cnt = n_shapes - base;
+			vt.num_shapes = (int32_t)(cnt > 65535 ? 65535 : cnt);
+			hipLaunchKernelGGL(srt_vertex_table_kernel, dim3(gx, (unsigned)vt.num_shapes), dim3(256), 0, t->stream, vt);
+		}
+		SRT_HIP(t, hipGetLastError());
+	}
+	t->vm_ver[cur] = t->vm_scene_ver;
 	return SRT_OK;
 }
 
@@ -420,6 +562,7 @@ int srt_set_denoise_temporal(srt_tracer *t, const srt_temporal_params *params) {
 		if (t->tp_on) srt_temporal_drop(t);
 		t->tp_on = false;
 		t->om_on = false;
+		t->vm_on = false;
 		return SRT_OK;
 	}
 	if (!params_ok(*params))
@@ -441,6 +584,7 @@ int srt_set_denoise_object_motion(srt_tracer *t, int enable) {
 	if (!enable) {
 		if (t->om_on) srt_temporal_drop(t);
 		t->om_on = false;
+		t->vm_on = false; // per-triangle motion is a part of it
 		return SRT_OK;
 	}
 	if (!t->tp_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_object_motion: temporal reprojection is off (srt_set_denoise_temporal)");
@@ -504,6 +648,84 @@ int srt_motion_table_host(const srt_shape *h_shapes, size_t h_n_shapes, const sr
 	} catch (...) {
 		return SRT_ERR_INVALID;
 	}
+	return SRT_OK;
+}
+
+int srt_motion_table_deform_host(const srt_shape *h_shapes, size_t h_n_shapes, const srt_triangle *h_triangles, size_t h_n_triangles,
+                                 const srt_material *h_materials, size_t h_n_materials, const srt_scene_data *h_scene,
+                                 const srt_shape *c_shapes, size_t c_n_shapes, const srt_triangle *c_triangles, size_t c_n_triangles,
+                                 const srt_material *c_materials, size_t c_n_materials, const srt_scene_data *c_scene, uint32_t *table, int *keep) {
+	if (!h_scene || !c_scene || !keep || (c_n_shapes && !table)) return SRT_ERR_INVALID;
+	if ((h_n_shapes && !h_shapes) || (c_n_shapes && !c_shapes) || (h_n_triangles && !h_triangles) || (c_n_triangles && !c_triangles) ||
+	    (h_n_materials && !h_materials) || (c_n_materials && !c_materials))
+		return SRT_ERR_INVALID;
+	const SceneView h = {h_shapes, h_n_shapes, h_triangles, h_materials, h_scene, h_n_triangles * sizeof(srt_triangle), h_n_materials * sizeof(srt_material)};
+	const SceneView c = {c_shapes, c_n_shapes, c_triangles, c_materials, c_scene, c_n_triangles * sizeof(srt_triangle), c_n_materials * sizeof(srt_material)};
+	bool any = false, any_deformed = false;
+	try {
+		std::vector<uint32_t> rows(c_n_shapes * SRT_MOTION_WORDS);
+		*keep = motion_table(h, c, rows.data(), &any, true, &any_deformed) ? 1 : 0;
+		if (*keep && !rows.empty()) memcpy(table, rows.data(), rows.size() * 4);
+	} catch (...) {
+		return SRT_ERR_INVALID;
+	}
+	return SRT_OK;
+}
+
+int srt_set_denoise_vertex_motion(srt_tracer *t, int enable) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!enable) {
+		if (t->vm_on) srt_temporal_drop(t);
+		t->vm_on = false;
+		return SRT_OK;
+	}
+	if (!t->om_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_vertex_motion: object motion is off (srt_set_denoise_object_motion)");
+	if (t->vm_on) return SRT_OK;
+	SRT_HIP(t, hipSetDevice(t->device));
+	const size_t px = full_pixels(t);
+	for (int k = 0; k < 2; k++) {
+		SRT_HIP(t, t->vm_tri[k].reserve(px));
+		SRT_HIP(t, hipMemsetAsync(t->vm_tri[k].ptr, 0xff, px * 4, t->stream));
+	}
+	const int rc = vertex_layout(t, t->scene_bytes);
+	if (rc) return rc;
+	t->vm_scene_ver++; // whatever the tables hold, the next feature pass writes the current scene's
+	srt_temporal_drop(t);
+	t->vm_on = true;
+	t->om_mixed = t->dn_T > 0; // what is on the canvas was traced without triangle indices
+	static_table(t);
+	return SRT_OK;
+}
+
+int srt_read_denoise_triangle_ids(srt_tracer *t, uint32_t *current, uint32_t *history) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!t->vm_tri[0].ptr) return fail(t, SRT_ERR_STATE, "srt_read_denoise_triangle_ids: per-triangle motion was never enabled (srt_set_denoise_vertex_motion)");
+	const size_t px = full_pixels(t);
+	SRT_HIP(t, hipSetDevice(t->device));
+	if (current) SRT_HIP(t, hipMemcpyAsync(current, t->vm_tri[t->om_cur].ptr, px * 4, hipMemcpyDeviceToHost, t->stream));
+	if (history) {
+		if (t->tp_valid) SRT_HIP(t, hipMemcpyAsync(history, t->vm_tri[1 - t->om_cur].ptr, px * 4, hipMemcpyDeviceToHost, t->stream));
+		else memset(history, 0xff, px * 4);
+	}
+	SRT_HIP(t, hipStreamSynchronize(t->stream));
+	return SRT_OK;
+}
+
+int srt_read_denoise_vertex_tables(srt_tracer *t, float *current, float *history, size_t cap_rows, size_t *n_rows) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!t->vm_tri[0].ptr) return fail(t, SRT_ERR_STATE, "srt_read_denoise_vertex_tables: per-triangle motion was never enabled (srt_set_denoise_vertex_motion)");
+	const size_t n = t->vm_first.empty() ? 0 : t->vm_first.back();
+	if (n_rows) *n_rows = n;
+	if (!current && !history) return SRT_OK;
+	if (cap_rows < n) return fail(t, SRT_ERR_INVALID, "srt_read_denoise_vertex_tables: the tables have more rows than cap_rows");
+	if (n == 0) return SRT_OK;
+	SRT_HIP(t, hipSetDevice(t->device));
+	if (current) SRT_HIP(t, hipMemcpyAsync(current, t->vm_rows[t->om_cur].ptr, n * 36, hipMemcpyDeviceToHost, t->stream));
+	if (history) {
+		if (t->tp_valid) SRT_HIP(t, hipMemcpyAsync(history, t->vm_rows[1 - t->om_cur].ptr, n * 36, hipMemcpyDeviceToHost, t->stream));
+		else memset(history, 0, n * 36);
+	}
+	SRT_HIP(t, hipStreamSynchronize(t->stream));
 	return SRT_OK;
 }
 

@@ -1,6 +1,8 @@
 // temporal_body.inc -- the body of srt_temporal_setup_kernel (SRT_TEMPORAL_MOTION 0) and srt_temporal_motion_kernel (1);
 // temporal.hip includes it once for each. With 0 the preprocessed text is the set-up kernel as it was before object motion,
-// so its instructions are too. In scope: p (TemporalParams); with 1 also mp (MotionParams).
+// so its instructions are too. In scope: p (TemporalParams); with 1 also mp (MotionParams). SRT_TEMPORAL_MOTION 2
+// (srt_temporal_deform_kernel) is 1 and the DEFORMED state, with vp (VertexParams) in scope; what only it has sits between
+// `#if SRT_TEMPORAL_MOTION == 2` and its `#endif`, so the moved kernel's preprocessed text is what it was.
 	const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
 	if (x >= p.width || y >= p.height) return;
 	const uint32_t i = (uint32_t)y * (uint32_t)p.width + (uint32_t)x;
@@ -33,6 +35,11 @@
 	const float *mrow = nullptr;
 	float bnx = nx, bny = ny, bnz = nz;
 	bool live = p.mode != TP_NONE && g1.w > 0.f && finite3(cc), moved = false;
+#if SRT_TEMPORAL_MOTION == 2
+	bool deformed = false;
+	float p0x = 0.f, p0y = 0.f, p0z = 0.f, q0x = 0.f, q0y = 0.f, q0z = 0.f, e1x = 0.f, e1y = 0.f, e1z = 0.f, e2x = 0.f, e2y = 0.f, e2z = 0.f;
+	float f1x = 0.f, f1y = 0.f, f1z = 0.f, f2x = 0.f, f2y = 0.f, f2z = 0.f, a11 = 0.f, a12 = 0.f, a22 = 0.f, det = 1.f;
+#endif
 	if (live) {
 		sid = mp.ids[i];
 		live = sid < mp.n_shapes;
@@ -49,6 +56,40 @@
 				live = len > 0.f && __builtin_isfinite(len);
 				bnx = tx / len, bny = ty / len, bnz = tz / len;
 			}
+#if SRT_TEMPORAL_MOTION == 2
+			// a deformed model: the pixel's triangle as it stands now (P) and as it stood in the history frame (Q). It projects
+			// and takes only its own shape's taps, as a moved shape does; N_h = normalise((nu f1 + nv f2) + c gh)
+			deformed = state == SRT_MOTION_DEFORMED;
+			if (deformed) {
+				moved = true;
+				const uint32_t tri = vp.tris[i];
+				live = tri < vp.first[sid + 1] - vp.first[sid]; // (0xffffffff: no triangle)
+				if (live) {
+					const float *P = vp.rows + (size_t)(row[1] + tri) * 9, *Q = vp.h_rows + (size_t)(row[1] + tri) * 9;
+					p0x = P[0], p0y = P[1], p0z = P[2];
+					q0x = Q[0], q0y = Q[1], q0z = Q[2];
+					e1x = P[3] - p0x, e1y = P[4] - p0y, e1z = P[5] - p0z;
+					e2x = P[6] - p0x, e2y = P[7] - p0y, e2z = P[8] - p0z;
+					f1x = Q[3] - q0x, f1y = Q[4] - q0y, f1z = Q[5] - q0z;
+					f2x = Q[6] - q0x, f2y = Q[7] - q0y, f2z = Q[8] - q0z;
+					a11 = (e1x * e1x + e1y * e1y) + e1z * e1z;
+					a12 = (e1x * e2x + e1y * e2y) + e1z * e2z;
+					a22 = (e2x * e2x + e2y * e2y) + e2z * e2z;
+					det = a11 * a22 - a12 * a12;
+					const float cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
+					const float hx = f1y * f2z - f1z * f2y, hy = f1z * f2x - f1x * f2z, hz = f1x * f2y - f1y * f2x;
+					const float lc = sqrtf((cx * cx + cy * cy) + cz * cz), lh = sqrtf((hx * hx + hy * hy) + hz * hz);
+					live = det > 0.f && __builtin_isfinite(det) && lc > 0.f && __builtin_isfinite(lc) && lh > 0.f && __builtin_isfinite(lh);
+					const float ne1 = (nx * e1x + ny * e1y) + nz * e1z, ne2 = (nx * e2x + ny * e2y) + nz * e2z;
+					const float nu = (a22 * ne1 - a12 * ne2) / det, nv = (a11 * ne2 - a12 * ne1) / det;
+					const float cn = (nx * (cx / lc) + ny * (cy / lc)) + nz * (cz / lc);
+					const float tx = (nu * f1x + nv * f2x) + cn * (hx / lh), ty = (nu * f1y + nv * f2y) + cn * (hy / lh), tz = (nu * f1z + nv * f2z) + cn * (hz / lh);
+					const float len = sqrtf((tx * tx + ty * ty) + tz * tz);
+					live = live && len > 0.f && __builtin_isfinite(len);
+					bnx = tx / len, bny = ty / len, bnz = tz / len;
+				}
+			}
+#endif
 		}
 	}
 	const bool identity = p.mode == TP_IDENTITY && !moved;
@@ -77,6 +118,16 @@
 			const float dx = rx * rs, dy = ry * rs, dz = rz * rs;
 #if SRT_TEMPORAL_MOTION
 			float wx = p.cam[0] + z * dx, wy = p.cam[1] + z * dy, wz = p.cam[2] + z * dz;
+#if SRT_TEMPORAL_MOTION == 2
+			bool xh_ok = true;
+			if (deformed) { // the same barycentric place on the history's triangle (the affine map of the triangle's plane)
+				const float ddx = wx - p0x, ddy = wy - p0y, ddz = wz - p0z;
+				const float de1 = (ddx * e1x + ddy * e1y) + ddz * e1z, de2 = (ddx * e2x + ddy * e2y) + ddz * e2z;
+				const float u = (a22 * de1 - a12 * de2) / det, v2 = (a11 * de2 - a12 * de1) / det;
+				wx = (q0x + u * f1x) + v2 * f2x, wy = (q0y + u * f1y) + v2 * f2y, wz = (q0z + u * f1z) + v2 * f2z;
+				xh_ok = __builtin_isfinite(wx) && __builtin_isfinite(wy) && __builtin_isfinite(wz);
+			} else
+#endif
 			if (moved) {
 				const float hx = ((mrow[0] * wx + mrow[1] * wy) + mrow[2] * wz) + mrow[3];
 				const float hy = ((mrow[4] * wx + mrow[5] * wy) + mrow[6] * wz) + mrow[7];
@@ -96,6 +147,9 @@
 			const float fy = ((1.f - qy / p.fov_h) / 2.f) * p.f_height - 0.5f;
 			// in front of the history camera, and a 2x2 that touches the image (this also keeps the conversions in range)
 			any = vz < 0.f && fx > -1.f && fx < p.f_width && fy > -1.f && fy < p.f_height;
+#if SRT_TEMPORAL_MOTION == 2
+			any = any && xh_ok;
+#endif
 			if (any) {
 				const float flx = floorf(fx), fly = floorf(fy);
 				x0 = (int)flx, y0 = (int)fly;

@@ -228,6 +228,13 @@ class Tracer {
 		if (group) throw std::runtime_error("Tracer::set_denoise_object_motion: single-device tracers only");
 		check(srt_set_denoise_object_motion(handle, enable ? 1 : 0));
 	}
+	/// Per-triangle motion (srt_set_denoise_vertex_motion): the history also survives an update_scene that changes a model's
+	/// vertices and keeps its topology (skinning, cloth, morph targets). Needs set_denoise_object_motion first.
+	/// Single-device tracers only.
+	void set_denoise_vertex_motion(bool enable = true) {
+		if (group) throw std::runtime_error("Tracer::set_denoise_vertex_motion: single-device tracers only");
+		check(srt_set_denoise_vertex_motion(handle, enable ? 1 : 0));
+	}
 	/// render() / render_pipelined() record the kernel timers' events too (off by default: they cost 10-17 us of a 150 us
 	/// frame); single-device tracers only
 	void set_kernel_timers(bool enable) {

@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "srt_denoise_defaults", "srt_set_denoise", "srt_resolve_denoised", "srt_read_denoised", "srt_read_denoise_inputs",
     "srt_temporal_defaults", "srt_set_denoise_temporal", "srt_reset_denoise_history", "srt_read_denoise_history",
     "srt_set_denoise_object_motion", "srt_read_denoise_shape_ids", "srt_read_denoise_motion", "srt_motion_table_host",
+    "srt_set_denoise_vertex_motion", "srt_read_denoise_triangle_ids", "srt_read_denoise_vertex_tables", "srt_motion_table_deform_host",
     "srt_set_textures", "srt_set_material_textures", "srt_set_triangle_uvs", "srt_last_trace_textured", "srt_plane_frame_host",
     "srt_texture_check_host", "srt_group_set_textures", "srt_group_set_material_textures", "srt_group_set_triangle_uvs",
     "srt_last_trace_class", "srt_bernoulli_threshold_host",
@@ -60,7 +61,7 @@ DEFORM_REBUILD, DEFORM_REFIT = 0, 1
 BUILD_HOST, BUILD_DEVICE = 0, 1
 BUILD_ORDER_MORTON, BUILD_ORDER_MEDIAN = 0, 1
 BUILD_LOCAL = 1024  # csrc/device_types.h SRT_BUILD_LOCAL: the largest range the median order's local launch takes
-MOTION_STATIC, MOTION_MOVED, MOTION_NO_HISTORY = 0, 1, 2
+MOTION_STATIC, MOTION_MOVED, MOTION_NO_HISTORY, MOTION_DEFORMED = 0, 1, 2, 3
 MOTION_WORDS = 22
 NO_SHAPE = 0xFFFFFFFF
 FILTER_LINEAR, FILTER_NEAREST = 0, 1
@@ -143,10 +144,12 @@ def _motion_rows(table):
     return {"state": table[:, 0].astype(np.int64), "A": f[:, :12].reshape(-1, 3, 4), "B": f[:, 12:].reshape(-1, 3, 3)}
 
 
-def motion_table_host(history, current):
+def motion_table_host(history, current, deform=False):
     """srt_motion_table_host (host only, no GPU needed). history / current: (shapes, triangles, materials, scene_data) of
     the two scenes. None when the history would be dropped, else dict state (n,), A (n, 3, 4) current world -> history
-    world, B (n, 3, 3) current normal -> history normal."""
+    world, B (n, 3, 3) current normal -> history normal. deform: srt_motion_table_deform_host, the keep rule of per-triangle
+    motion; the dict then also holds first_row (n,) = word 1 of each row (a DEFORMED shape's first row in the vertex
+    tables)."""
     lib = load_library()
     args, keep = [], []
     for shapes, triangles, materials, sd in (history, current):
@@ -159,10 +162,16 @@ def motion_table_host(history, current):
     n = len(keep[4])
     table = np.zeros((max(n, 1), MOTION_WORDS), np.uint32)
     kept = C.c_int(0)
-    rc = lib.srt_motion_table_host(*args, _ptr(table), C.byref(kept))
+    fn = lib.srt_motion_table_deform_host if deform else lib.srt_motion_table_host
+    rc = fn(*args, _ptr(table), C.byref(kept))
     if rc:
         raise SrtError(f"srt_motion_table_host failed ({rc})")
-    return _motion_rows(table[:n]) if kept.value else None
+    if not kept.value:
+        return None
+    out = _motion_rows(table[:n])
+    if deform:
+        out["first_row"] = table[:n, 1].astype(np.int64)
+    return out
 
 
 BVH_NODE = np.dtype({"names": ["lo", "skip", "hi", "leaf"], "formats": [(np.float32, (3,)), np.uint32, (np.float32, (3,)), np.uint32],
@@ -544,6 +553,11 @@ def _bind(lib):
         lib.srt_read_denoise_shape_ids.argtypes = [vp, vp, vp]
         lib.srt_read_denoise_motion.argtypes = [vp, vp, sz, C.POINTER(sz), C.POINTER(C.c_int)]
         lib.srt_motion_table_host.argtypes = [vp, sz, vp, sz, vp, sz, vp] * 2 + [vp, C.POINTER(C.c_int)]
+    if hasattr(lib, "srt_set_denoise_vertex_motion"):
+        lib.srt_set_denoise_vertex_motion.argtypes = [vp, C.c_int]
+        lib.srt_read_denoise_triangle_ids.argtypes = [vp, vp, vp]
+        lib.srt_read_denoise_vertex_tables.argtypes = [vp, vp, vp, sz, C.POINTER(sz)]
+        lib.srt_motion_table_deform_host.argtypes = [vp, sz, vp, sz, vp, sz, vp] * 2 + [vp, C.POINTER(C.c_int)]
     if hasattr(lib, "srt_set_denoise_demodulation"):  # (an older library, SRT_LIB, in an A/B run)
         lib.srt_set_denoise_demodulation.argtypes = [vp, C.c_int]
         lib.srt_group_set_denoise_demodulation.argtypes = [vp, C.c_int]
@@ -1002,7 +1016,30 @@ class Tracer(_Denoise):
         self._check(self.lib.srt_read_denoise_motion(self._h, _ptr(table), n.value, C.byref(n), C.byref(any_moved)))
         out = _motion_rows(table[:n.value])
         out["any_moved"] = bool(any_moved.value)
+        out["first_row"] = table[:n.value, 1].astype(np.int64)  # (a DEFORMED row's word 1; the bits of A[0][0] otherwise)
         return out
+
+    def set_denoise_vertex_motion(self, enable=True):
+        """Keep the temporal history across an update_scene that changes a model's vertices and keeps its topology
+        (srt_set_denoise_vertex_motion). Needs object motion on; every change of the switch drops the history."""
+        self._check(self.lib.srt_set_denoise_vertex_motion(self._h, 1 if enable else 0))
+
+    def read_denoise_triangle_ids(self):
+        """(current, history): (h, w) uint32 index inside its model of the triangle each pixel's first hit lies on (feature
+        sample 0 of the latest dispatch; NO_SHAPE: no hit, no material, or not a model), as read_denoise_shape_ids."""
+        cur = np.zeros((self.height, self.width), np.uint32)
+        hist = np.zeros((self.height, self.width), np.uint32)
+        self._check(self.lib.srt_read_denoise_triangle_ids(self._h, _ptr(cur), _ptr(hist)))
+        return cur, hist
+
+    def read_denoise_vertex_tables(self):
+        """(current, history): (rows, 3, 3) float32 world vertices P0, P1, P2 per instance triangle (model shapes in shape
+        order), of the frame since the clear and of the history frame (zeros without a history)."""
+        n = C.c_size_t(0)
+        self._check(self.lib.srt_read_denoise_vertex_tables(self._h, None, None, 0, C.byref(n)))
+        cur, hist = np.zeros((max(n.value, 1), 3, 3), np.float32), np.zeros((max(n.value, 1), 3, 3), np.float32)
+        self._check(self.lib.srt_read_denoise_vertex_tables(self._h, _ptr(cur), _ptr(hist), n.value, C.byref(n)))
+        return cur[:n.value], hist[:n.value]
 
     def set_partition(self, rank, world, rows_per_block=8):
         self._check(self.lib.srt_set_partition(self._h, rank, world, rows_per_block))
