@@ -637,6 +637,42 @@ int srt_group_set_denoise_demodulation(srt_group *g, int enable);
 int srt_last_filter_demodulated(const srt_tracer *t, int *demodulated);
 int srt_group_last_filter_demodulated(const srt_group *g, int *demodulated);
 
+/* ---- spatial variance estimate for pixels with few samples (new; SVGF §4.2) -------------------------------------------- */
+
+/* Opt-in. The set-ups take a pixel's variance from that pixel's own moments: from two samples it is often exactly 0 and
+ * otherwise wrong by large factors, and every a-trous pass takes its luminance weight from it. With min_samples > 0 and
+ * iterations K >= 1, one more launch between the set-up (whichever ran: spatial, temporal, moved, deformed; under
+ * demodulation after the demodulate launch) and the passes replaces the variance of every pixel that has fewer than
+ * min_samples samples by an estimate from the moments of its 7x7 neighbourhood, weighted by the filter's geometric weights.
+ * All float32, unfused, in the order written; tests/spatial_variance_ref.py restates it.
+ *   inputs     per pixel p: the spatial set-up: s_p = P (as a float), m1_p = lum(canvas / T), m2_p = M / T (the expressions of
+ *              the set-up kernel, from the same buffers); any temporal set-up: s_p = the staged count min(n, history_limit),
+ *              m1_p, m2_p = the staged moments.
+ *   qualifies  cov_p > 0, a finite colour and s_p < (float)min_samples. Every other pixel keeps its {colour, variance} bit
+ *              for bit.
+ *   taps       q = p + (dx, dy), dx, dy in -3..3, dy in the outer loop and dx in the inner one; taps outside the image are
+ *              skipped; a tap counts when cov_q > 0, its colour is finite and m1_q, m2_q are finite.
+ *   weight     w = exp(-|Zp - Zq| / (sigma_depth Zp r + 1e-6)) max(0, Np.Nq)^sigma_normal exp(-|Ap - Aq|^2 / sigma_albedo^2),
+ *              r = max(|dx|, |dy|), with the a-trous kernel's expressions and fast exp / log. No spatial kernel h and no
+ *              luminance term; a tap with Np.Nq <= 0 is skipped; the centre tap (when it counts) has weight 1.
+ *   result     m1' = sum(w m1_q) / sum(w), m2' = sum(w m2_q) / sum(w), V = max(0, m2' - m1' m1') / s_p (non-finite: 0). Only
+ *              the variance is written; the colour is untouched.
+ *   demodulation (srt_set_denoise_demodulation on): the estimate is made in illumination space and the albedo factor is
+ *              dropped, as the passes drop it: a_q = 1 / lum(D_q), D the demodulate launch's divisor, a tap contributes
+ *              m1_q a_q and (m2_q a_q) a_q, and the result is V_I itself (the launch runs after the demodulate launch).
+ * K = 0: nothing is launched, the plain resolve's bytes, srt_read_denoised's variance is the set-up's. With the switch off
+ * the library enqueues exactly what it enqueues without this interface. The history holds colour and moments, never
+ * variance: the switch changes nothing that is staged or committed. When history_limit < min_samples, s_p never reaches
+ * min_samples and every pixel is estimated spatially, with divisor s_p: not an error.
+ * min_samples = 0: off (the default); 1..2^20: on. SRT_ERR_INVALID above 2^20. SRT_ERR_STATE unless the denoiser is on (the
+ * group call: the group's denoiser). Turning the denoiser off turns it off. Clears nothing and keeps the temporal history;
+ * takes effect at the next filter, as srt_set_denoise_demodulation does. */
+int srt_set_denoise_spatial_variance(srt_tracer *t, uint32_t min_samples);
+int srt_group_set_denoise_spatial_variance(srt_group *g, uint32_t min_samples);
+/* *ran = 1 when the last filter enqueued the estimate (the switch on and K >= 1), else 0. */
+int srt_last_filter_spatial_variance(const srt_tracer *t, int *ran);
+int srt_group_last_filter_spatial_variance(const srt_group *g, int *ran);
+
 /* ---- albedo textures ----------------------------------------------------------
  * Opt-in: where a material has a texture bound, the colour that multiplies the path's mask (and the denoiser's albedo
  * guide) is the texel at the hit's UV instead of srt_material.color. Nothing else about a material changes and a lookup

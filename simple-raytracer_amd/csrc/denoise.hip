@@ -22,6 +22,9 @@
 //   pixels stay as they are), the passes run the formula above over I and V_I without the albedo factor -- sigma_albedo is
 //   ignored in this mode -- with lum(I) in the luminance term, and the last pass writes o = I' D_p, V' = V_I' lum(D_p)^2
 //   for the pixels that were demodulated (one that got no weight: I_p D_p, within rounding of c, not bit-equal).
+// Spatial variance estimate (srt_set_denoise_spatial_variance; tests/spatial_variance_ref.py), K >= 1 only: one launch before
+//   the passes (after the demodulate launch) gives a pixel with fewer than min_samples samples the variance of the
+//   edge-weighted moments of its 7x7 neighbourhood instead of its own (srt_denoise_spatial_variance_kernel below).
 // No atomics: every output is a fixed function of its inputs, so runs are bit-identical. The passes use the fast
 // exp / log instructions: this stage is outside the parity contract (DESIGN.md "Denoiser").
 #include <hip/hip_runtime.h>
@@ -224,6 +227,192 @@ __global__ __launch_bounds__(256) void srt_denoise_atrous_demod_kernel(const Fil
 	if (LAST) p.argb[i] = tonemap(o.x, o.y, o.z);
 }
 
+// ---- spatial variance estimate (srt_set_denoise_spatial_variance; include/srt_abi.h has the definition, tests/spatial_variance_ref.py
+// restates it): one launch between the set-up (and the demodulate launch) and the passes. A pixel with cov > 0, a finite
+// colour and fewer than min_samples samples gets V = max(0, m2' - m1'^2) / s_p from the edge-weighted means m1', m2' of the
+// moments of its 7x7 neighbourhood; only that pixel's variance slot is written, in place. (A neighbouring tile reads the
+// float4 for its colour's finiteness while this one writes .w: no value that is read changes.)
+struct SpatialVarParams {
+	int32_t width, height;
+	float min_samples;                    // (float)min_samples
+	float T, P;                           // the spatial set-up's divisors (STAGED: unused)
+	float sigma_n, sigma_z, inv_sigma_a2; // as FilterParams
+	const float4 *guide;
+	const float4 *canvas; // the spatial set-up's sources: s = P, m1 = lum(canvas / T), m2 = M / T
+	const float *moments;
+	const float4 *s_cc;   // STAGED, the temporal set-up's staging set: s = {c, count}.w, {m1, m2}
+	const float2 *s_m;
+	float4 *io;           // {colour, variance}
+};
+
+// what a tap contributes: its guide, its moments (DEMOD: scaled into illumination space, A unused) and whether it counts
+struct SvTap {
+	float4 g0;        // {N, Z}
+	float ar, ag, ab; // A
+	float m1, m2;
+	bool ok;          // cov > 0, a finite colour, finite moments
+};
+
+enum { SV_R = 3, SV_HALO = 16 + 2 * SV_R, SV_ROW4 = 32, SV_ROW1 = 48 }; // LDS row strides: float4 arrays 32, the float array 48
+
+// pixel j as a tap; *live = cov > 0 and a finite colour, *s = its sample count
+template <bool STAGED, bool DEMOD>
+__device__ inline SvTap sv_load(const SpatialVarParams &p, uint32_t j, bool *live, float *s) {
+	SvTap t;
+	t.g0 = p.guide[2 * j];
+	const float4 g1 = p.guide[2 * j + 1];
+	const float4 c = p.io[j];
+	float m1, m2;
+	if (STAGED) {
+		*s = p.s_cc[j].w;
+		const float2 m = p.s_m[j];
+		m1 = m.x, m2 = m.y;
+	} else {
+		const float4 cv = p.canvas[j];
+		*s = p.P;
+		m1 = lum(cv.x / p.T, cv.y / p.T, cv.z / p.T);
+		m2 = p.moments[j] / p.T;
+	}
+	*live = g1.w > 0.f && finite3(c);
+	t.ok = *live && __builtin_isfinite(m1) && __builtin_isfinite(m2);
+	if (DEMOD) {
+		const float a = 1.0f / lum(fmaxf(g1.x, SRT_DEMOD_EPS), fmaxf(g1.y, SRT_DEMOD_EPS), fmaxf(g1.z, SRT_DEMOD_EPS));
+		m1 = m1 * a;
+		m2 = (m2 * a) * a;
+		t.ar = t.ag = t.ab = 0.f;
+	} else {
+		t.ar = g1.x, t.ag = g1.y, t.ab = g1.z;
+	}
+	t.m1 = m1, t.m2 = m2;
+	return t;
+}
+
+// one tap other than the centre into the sums; inv_dz = 1 / (sigma_z Zp r + 1e-6), r = max(|dx|, |dy|)
+template <bool DEMOD>
+__device__ inline void sv_tap(const SpatialVarParams &p, const SvTap &c, const SvTap &q, float inv_dz, float &sw, float &s1, float &s2) {
+	if (!q.ok) return;
+	const float d = c.g0.x * q.g0.x + c.g0.y * q.g0.y + c.g0.z * q.g0.z;
+	if (!(d > 0.f)) return; // max(0, d)^sigma_n = 0
+	const float wn = __expf(p.sigma_n * __logf(d));
+	float e = fabsf(c.g0.w - q.g0.w) * inv_dz;
+	if (!DEMOD) {
+		const float ar = c.ar - q.ar, ag = c.ag - q.ag, ab = c.ab - q.ab;
+		e = e + (ar * ar + ag * ag + ab * ab) * p.inv_sigma_a2;
+	}
+	const float w = wn * __expf(-e);
+	sw += w;
+	s1 += w * q.m1;
+	s2 += w * q.m2;
+}
+
+// STAGED: the moments' source; DEMOD: illumination space; LDS: the 22x22 halo tile staged in LDS (else a tap is loaded where
+// it is used, as in the a-trous passes). All instantiations run the same arithmetic in the same order.
+template <bool STAGED, bool DEMOD, bool LDS>
+__global__ __launch_bounds__(256) void srt_denoise_spatial_variance_kernel(const SpatialVarParams p) {
+	const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+	const int x0 = blockIdx.x * 16, y0 = blockIdx.y * 16;
+	const int x = x0 + tx, y = y0 + ty;
+	const uint32_t i = (uint32_t)y * (uint32_t)p.width + (uint32_t)x;
+	SvTap c;
+	float s = 0.f;
+	bool qualifies = false;
+	if (x < p.width && y < p.height) {
+		bool live;
+		c = sv_load<STAGED, DEMOD>(p, i, &live, &s);
+		qualifies = live && s < p.min_samples;
+	}
+	float sw = 0.f, s1 = 0.f, s2 = 0.f;
+	if (LDS) {
+		// the halo tile: float4 rows of 32 and float rows of 48 entries, so that the two image rows a 32-lane group reads
+		// fall on disjoint banks (16-B reads: 64 banks, 4-B reads: 32). A tap that does not count has m2 = NaN.
+		__shared__ float4 t_g0[SV_HALO * SV_ROW4];
+		__shared__ float4 t_am[SV_HALO * SV_ROW4];
+		__shared__ float t_m2[SV_HALO * SV_ROW1];
+		if (!__syncthreads_or(qualifies ? 1 : 0)) return; // no lane of the tile qualifies: nothing is staged
+		for (int e = threadIdx.x; e < SV_HALO * SV_HALO; e += 256) {
+			const int hy = e / SV_HALO, hx = e - hy * SV_HALO;
+			const int qx = x0 - SV_R + hx, qy = y0 - SV_R + hy;
+			SvTap q;
+			q.ok = false;
+			if (qx >= 0 && qx < p.width && qy >= 0 && qy < p.height) {
+				bool live;
+				float sq;
+				q = sv_load<STAGED, DEMOD>(p, (uint32_t)qy * (uint32_t)p.width + (uint32_t)qx, &live, &sq);
+			}
+			if (q.ok) {
+				t_g0[hy * SV_ROW4 + hx] = q.g0;
+				t_am[hy * SV_ROW4 + hx] = make_float4(q.ar, q.ag, q.ab, q.m1);
+			}
+			t_m2[hy * SV_ROW1 + hx] = q.ok ? q.m2 : __builtin_nanf("");
+		}
+		__syncthreads();
+		if (!qualifies) return;
+		const float zs = p.sigma_z * c.g0.w;
+		const float inv_dz1 = 1.0f / (zs * 1.0f + 1e-6f), inv_dz2 = 1.0f / (zs * 2.0f + 1e-6f), inv_dz3 = 1.0f / (zs * 3.0f + 1e-6f);
+		for (int dy = -SV_R; dy <= SV_R; dy++) {
+			for (int dx = -SV_R; dx <= SV_R; dx++) {
+				if (dx == 0 && dy == 0) {
+					if (c.ok) sw += 1.0f, s1 += c.m1, s2 += c.m2; // the centre: weight 1
+					continue;
+				}
+				const int hy = ty + SV_R + dy, hx = tx + SV_R + dx;
+				SvTap q;
+				q.m2 = t_m2[hy * SV_ROW1 + hx];
+				q.ok = q.m2 == q.m2;
+				if (!q.ok) continue;
+				q.g0 = t_g0[hy * SV_ROW4 + hx];
+				const float4 am = t_am[hy * SV_ROW4 + hx];
+				q.ar = am.x, q.ag = am.y, q.ab = am.z, q.m1 = am.w;
+				const int r = max(abs(dx), abs(dy));
+				sv_tap<DEMOD>(p, c, q, r == 1 ? inv_dz1 : r == 2 ? inv_dz2 : inv_dz3, sw, s1, s2);
+			}
+		}
+	} else {
+		if (!qualifies) return;
+		const float zs = p.sigma_z * c.g0.w;
+		const float inv_dz1 = 1.0f / (zs * 1.0f + 1e-6f), inv_dz2 = 1.0f / (zs * 2.0f + 1e-6f), inv_dz3 = 1.0f / (zs * 3.0f + 1e-6f);
+		for (int dy = -SV_R; dy <= SV_R; dy++) {
+			const int qy = y + dy;
+			if (qy < 0 || qy >= p.height) continue;
+			for (int dx = -SV_R; dx <= SV_R; dx++) {
+				const int qx = x + dx;
+				if (qx < 0 || qx >= p.width) continue;
+				if (dx == 0 && dy == 0) {
+					if (c.ok) sw += 1.0f, s1 += c.m1, s2 += c.m2; // the centre: weight 1
+					continue;
+				}
+				bool live;
+				float sq;
+				const SvTap q = sv_load<STAGED, DEMOD>(p, (uint32_t)qy * (uint32_t)p.width + (uint32_t)qx, &live, &sq);
+				const int r = max(abs(dx), abs(dy));
+				sv_tap<DEMOD>(p, c, q, r == 1 ? inv_dz1 : r == 2 ? inv_dz2 : inv_dz3, sw, s1, s2);
+			}
+		}
+	}
+	const float m1 = s1 / sw, m2 = s2 / sw;
+	float v = m2 - m1 * m1;
+	v = v > 0.f ? v : 0.f;
+	v = v / s;
+	if (!__builtin_isfinite(v)) v = 0.f;
+	reinterpret_cast<float *>(p.io)[4 * (size_t)i + 3] = v;
+}
+
+// the form the library launches: the halo tile in LDS, or (-DSRT_SV_GLOBAL, scripts/spatial_variance_probe.py's other
+// build) the plain global loads; DESIGN.md "Spatial variance estimate" has both forms' times
+#ifdef SRT_SV_GLOBAL
+constexpr bool kSvLds = false;
+#else
+constexpr bool kSvLds = true;
+#endif
+
+void launch_spatial_variance(const SpatialVarParams &p, bool staged, bool demod, hipStream_t stream) {
+	const dim3 grid((unsigned)((p.width + 15) / 16), (unsigned)((p.height + 15) / 16));
+	if (staged && demod) hipLaunchKernelGGL((srt_denoise_spatial_variance_kernel<true, true, kSvLds>), grid, dim3(256), 0, stream, p);
+	else if (staged) hipLaunchKernelGGL((srt_denoise_spatial_variance_kernel<true, false, kSvLds>), grid, dim3(256), 0, stream, p);
+	else if (demod) hipLaunchKernelGGL((srt_denoise_spatial_variance_kernel<false, true, kSvLds>), grid, dim3(256), 0, stream, p);
+	else hipLaunchKernelGGL((srt_denoise_spatial_variance_kernel<false, false, kSvLds>), grid, dim3(256), 0, stream, p);
+}
+
 bool params_ok(const srt_denoise_params &d) {
 	auto sigma_ok = [](float s) { return std::isfinite(s) && s > 0.0f; };
 	return d.iterations >= 0 && d.iterations <= 8 && d.feature_samples >= 1 && d.feature_samples <= 64 && sigma_ok(d.sigma_luminance) &&
@@ -338,9 +527,11 @@ int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
 	sp.out = col;
 	sp.argb = K == 0 ? reinterpret_cast<uint32_t *>(argb) : nullptr;
 	const float4 *fguide = guide;
+	TemporalStaged staged = {nullptr, nullptr, nullptr};
 	if (t->tp_on) { // temporal.hip: the set-up with the reprojected history blended in; it writes the guide into the staging set
-		const int rc = srt_temporal_setup(t, col, sp.argb, &fguide);
+		const int rc = srt_temporal_setup(t, col, sp.argb, &staged);
 		if (rc) return rc;
+		fguide = staged.guide;
 	} else {
 		hipLaunchKernelGGL(srt_denoise_setup_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, t->stream, sp);
 		SRT_HIP(t, hipGetLastError());
@@ -365,6 +556,26 @@ int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
 	// inf, which turns every tap's 0 * inf albedo term into NaN (no pixel filtered); clamped, equal albedos still cost 0
 	fp.inv_sigma_a2 = (float)std::min(1.0 / ((double)t->dn.sigma_albedo * (double)t->dn.sigma_albedo), (double)FLT_MAX);
 	fp.guide = fguide;
+	const bool spatial_var = t->dn_sv_min > 0 && K >= 1;
+	if (spatial_var) { // pixels with few samples: the variance of their 7x7 neighbourhood's moments (whichever set-up ran)
+		SpatialVarParams vp;
+		vp.width = t->width;
+		vp.height = t->height;
+		vp.min_samples = (float)t->dn_sv_min;
+		vp.T = sp.T;
+		vp.P = sp.P;
+		vp.sigma_n = fp.sigma_n;
+		vp.sigma_z = fp.sigma_z;
+		vp.inv_sigma_a2 = fp.inv_sigma_a2;
+		vp.guide = fguide;
+		vp.canvas = sp.canvas;
+		vp.moments = sp.moments;
+		vp.s_cc = staged.cc;
+		vp.s_m = staged.m;
+		vp.io = col;
+		launch_spatial_variance(vp, t->tp_on, demod, t->stream);
+		SRT_HIP(t, hipGetLastError());
+	}
 	const dim3 grid((unsigned)((t->width + 15) / 16), (unsigned)((t->height + 15) / 16));
 	for (int k = 0; k < K; k++) {
 		fp.step = 1 << k;
@@ -379,6 +590,7 @@ int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
 	t->dn_out = K & 1;
 	t->dn_filtered = true;
 	t->last_filter_demod = demod;
+	t->last_filter_sv = spatial_var;
 	return SRT_OK;
 }
 
@@ -402,6 +614,7 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 	if (!params || !params->enable) {
 		t->dn_on = false;
 		t->dn_demod = false; // albedo demodulation is a mode of the filter
+		t->dn_sv_min = 0;    // and so is the spatial variance estimate
 		t->tp_on = false; // temporal reprojection is a stage of the denoiser
 		t->om_on = false; // and object motion a stage of that
 		t->vm_on = false; // (with its per-triangle part)
@@ -445,6 +658,24 @@ int srt_set_denoise_demodulation(srt_tracer *t, int enable) {
 int srt_last_filter_demodulated(const srt_tracer *t, int *demodulated) {
 	if (!t || !demodulated) return SRT_ERR_INVALID;
 	*demodulated = t->last_filter_demod ? 1 : 0;
+	return SRT_OK;
+}
+
+int srt_set_denoise_spatial_variance(srt_tracer *t, uint32_t min_samples) {
+	if (!t) return SRT_ERR_INVALID;
+	if (min_samples == 0) {
+		t->dn_sv_min = 0;
+		return SRT_OK;
+	}
+	if (min_samples > (1u << 20)) return fail(t, SRT_ERR_INVALID, "srt_set_denoise_spatial_variance: min_samples 0..2^20");
+	if (!t->dn_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_spatial_variance: the denoiser is off (srt_set_denoise)");
+	t->dn_sv_min = min_samples;
+	return SRT_OK;
+}
+
+int srt_last_filter_spatial_variance(const srt_tracer *t, int *ran) {
+	if (!t || !ran) return SRT_ERR_INVALID;
+	*ran = t->last_filter_sv ? 1 : 0;
 	return SRT_OK;
 }
 

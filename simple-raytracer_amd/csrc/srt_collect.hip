@@ -727,6 +727,26 @@ int srt_group_last_filter_demodulated(const srt_group *g, int *demodulated) {
 	return SRT_OK;
 }
 
+int srt_group_set_denoise_spatial_variance(srt_group *g, uint32_t min_samples) {
+	if (!g) return SRT_ERR_INVALID;
+	if (min_samples == 0) {
+		if (g->resolver) g->resolver->dn_sv_min = 0;
+		return SRT_OK;
+	}
+	if (min_samples > (1u << 20)) return gfail(g, SRT_ERR_INVALID, "srt_group_set_denoise_spatial_variance: min_samples 0..2^20");
+	if (!g->dn_on) return gfail(g, SRT_ERR_STATE, "srt_group_set_denoise_spatial_variance: the denoiser is off (srt_group_set_denoise)");
+	srt_tracer *r = resolver_of(g);
+	if (!r) return SRT_ERR_HIP;
+	SRT_ON_RESOLVER(g, r, srt_set_denoise_spatial_variance(r, min_samples)); // the filter runs on that handle
+	return SRT_OK;
+}
+
+int srt_group_last_filter_spatial_variance(const srt_group *g, int *ran) {
+	if (!g || !ran) return SRT_ERR_INVALID;
+	*ran = (g->resolver && g->resolver->last_filter_sv) ? 1 : 0;
+	return SRT_OK;
+}
+
 int srt_group_reset_denoise_history(srt_group *g) {
 	if (!g) return SRT_ERR_INVALID;
 	drop_history(g);

@@ -204,6 +204,8 @@ struct srt_tracer {
 	int dn_out = 0;                        // the image of dn_col the last pass wrote
 	bool dn_demod = false;                 // srt_set_denoise_demodulation: the passes filter colour / albedo (K >= 1)
 	bool last_filter_demod = false;        // srt_last_filter_demodulated
+	uint32_t dn_sv_min = 0;                // srt_set_denoise_spatial_variance: pixels with fewer samples get their variance from their 7x7 neighbourhood (0: off)
+	bool last_filter_sv = false;           // srt_last_filter_spatial_variance
 	srt_render_data dn_cam{};              // the last dispatch's render data since the clear (its camera: temporal reprojection)
 	// temporal reprojection (temporal.hip; srt_set_denoise_temporal). Two history sets, each px x 14 floats: float4
 	// {colour, count}, float2 {m1, m2}, 2 float4 guide; tp_set[tp_cur] is the history, the other the frame being integrated
@@ -335,9 +337,15 @@ int srt_denoise_member(srt_tracer *t, int feature_samples);
 /* the bytes srt_update_scene compares two scenes by (the denoiser's history survives an unchanged scene) */
 void srt_scene_bytes(std::vector<uint8_t> &bytes, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles, size_t n_triangles,
                      const srt_material *materials, size_t n_materials, const srt_scene_data *scene);
-/* temporal.hip: the temporal set-up over the canvas into `col` (and argb when not NULL), *guide = the guide it wrote;
+/* temporal.hip: the temporal set-up over the canvas into `col` (and argb when not NULL), *staged = what it wrote into the
+ * staging set (the guide the passes filter with; {c, count} and {m1, m2} for the spatial variance estimate);
  * the commit at srt_clear_canvas (before the canvas is zeroed); dropping the history */
-int srt_temporal_setup(srt_tracer *t, float4 *col, uint32_t *argb, const float4 **guide);
+struct TemporalStaged {
+	const float4 *guide; // 2 float4 per pixel
+	const float4 *cc;    // {colour, min(n, history_limit)}
+	const float2 *m;     // {m1, m2}
+};
+int srt_temporal_setup(srt_tracer *t, float4 *col, uint32_t *argb, TemporalStaged *staged);
 int srt_temporal_commit(srt_tracer *t);
 void srt_temporal_drop(srt_tracer *t);
 /* srt_update_scene with object motion on (`bytes`: the new scene, scene_bytes still the previous call's; rc: the update's

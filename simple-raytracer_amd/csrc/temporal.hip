@@ -455,11 +455,14 @@ void srt_temporal_drop(srt_tracer *t) {
 	t->tp_fresh = false;
 }
 
-int srt_temporal_setup(srt_tracer *t, float4 *col, uint32_t *argb, const float4 **guide) {
+int srt_temporal_setup(srt_tracer *t, float4 *col, uint32_t *argb, TemporalStaged *staged) {
 	const int rc = launch_setup(t, col, argb);
 	if (rc) return rc;
 	const size_t px = full_pixels(t);
-	*guide = reinterpret_cast<const float4 *>(t->tp_set[1 - t->tp_cur].ptr + off_guide(px));
+	const float *stage = t->tp_set[1 - t->tp_cur].ptr;
+	staged->guide = reinterpret_cast<const float4 *>(stage + off_guide(px));
+	staged->cc = reinterpret_cast<const float4 *>(stage);
+	staged->m = reinterpret_cast<const float2 *>(stage + off_m(px));
 	t->tp_fresh = true;
 	return SRT_OK;
 }

@@ -221,6 +221,18 @@ class Tracer {
 	void set_denoise_demodulation(bool enable = true) {
 		check(group ? srt_group_set_denoise_demodulation(group, enable ? 1 : 0) : srt_set_denoise_demodulation(handle, enable ? 1 : 0));
 	}
+	/// Spatial variance estimate (srt_set_denoise_spatial_variance): a pixel with fewer than min_samples samples (the first
+	/// frames after a clear, disocclusions under temporal reprojection) takes its variance from the moments of its 7x7
+	/// neighbourhood instead of its own two or three samples. 0 turns it off. Needs set_denoise first; one device or a group.
+	void set_denoise_spatial_variance(uint32_t min_samples = 8) {
+		check(group ? srt_group_set_denoise_spatial_variance(group, min_samples) : srt_set_denoise_spatial_variance(handle, min_samples));
+	}
+	/// Whether the last filter enqueued that estimate (the switch on and iterations >= 1)
+	bool last_filter_spatial_variance() {
+		int ran = 0;
+		check(group ? srt_group_last_filter_spatial_variance(group, &ran) : srt_last_filter_spatial_variance(handle, &ran));
+		return ran != 0;
+	}
 	/// Object motion for the temporal stage (srt_set_denoise_object_motion): the history survives an update_scene that only
 	/// moves spheres, planes or model instances. Needs set_denoise_temporal first; the clear_canvas / update_scene / render
 	/// order of the frame loop stays as it is. Single-device tracers only (a group gathers no shape indices).

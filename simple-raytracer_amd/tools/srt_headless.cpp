@@ -5,10 +5,12 @@
 //
 //   srt_headless [--scene spheres|meshes|empty] [--obj f.obj]... [--stl f.stl]...
 //                [--width W --height H --spp S --bounces B --frames N --time T]
-//                [--obj-materials] [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--demodulate] [--temporal] [--move DX]
+//                [--obj-materials] [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--move DX]
 // --denoise K: the frames go through the edge-aware denoiser with K a-trous passes (Tracer::set_denoise; with --gpus N the
 //                members gather the filter's inputs with the frame and device 0 filters: the same bytes as on one device)
 // --demodulate: with --denoise, the passes filter colour / first-hit albedo (Tracer::set_denoise_demodulation); an error without it
+// --spatial-variance N: with --denoise, pixels with fewer than N samples take their variance from their 7x7 neighbourhood
+//                (Tracer::set_denoise_spatial_variance); an error without it
 // --temporal: with --denoise, the denoiser's temporal reprojection (Tracer::set_denoise_temporal)
 // --move DX: the camera moves by DX along x every frame and every frame clears the canvas, as the front-end does while moving
 // --move-shape I DX: with --temporal, shape I (a sphere, a plane or a model instance) moves by DX along x every frame and every
@@ -117,7 +119,7 @@ int main(int argc, char **argv) {
 	int width = 256, height = 256, spp = 16, bounces = 10, frames = 1;
 	unsigned time_seed = 12345;
 	bool parse_only = false, bvh = false, pipelined = false, obj_materials = false;
-	int gpus = 1, denoise = -1;
+	int gpus = 1, denoise = -1, spatial_variance = 0;
 	bool temporal = false, demodulate = false;
 	float move = 0.0f, shape_move = 0.0f;
 	int move_shape = -1;
@@ -177,19 +179,24 @@ int main(int argc, char **argv) {
 		else if (a == "--texture-nearest") texture_nearest = true;
 		else if (a == "--denoise") denoise = std::atoi(next());
 		else if (a == "--demodulate") demodulate = true;
+		else if (a == "--spatial-variance") spatial_variance = std::atoi(next());
 		else if (a == "--temporal") temporal = true;
 		else if (a == "--move") move = std::strtof(next(), nullptr), moving = true;
 		else if (a == "--move-shape") move_shape = std::atoi(next()), shape_move = std::strtof(next(), nullptr);
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--temporal] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
+			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
 
 	if (demodulate && denoise < 0) {
 		std::cerr << "--demodulate needs --denoise K\n";
+		return 2;
+	}
+	if (spatial_variance != 0 && (denoise < 0 || spatial_variance < 0)) {
+		std::cerr << "--spatial-variance N needs --denoise K and N >= 0\n";
 		return 2;
 	}
 	if (temporal && denoise < 0) {
@@ -308,6 +315,7 @@ int main(int argc, char **argv) {
 	if (bvh_build_device) tracer.set_acceleration_build(SRT_BUILD_DEVICE, bvh_build_min); // (models of at least MIN triangles; without --bvh: no effect)
 	if (denoise >= 0) tracer.set_denoise(denoise);
 	if (demodulate) tracer.set_denoise_demodulation();
+	if (spatial_variance > 0) tracer.set_denoise_spatial_variance((uint32_t)spatial_variance);
 	if (temporal) tracer.set_denoise_temporal();
 	if (move_shape >= 0) {
 		if (!temporal || (size_t)move_shape >= shapes.size()) {

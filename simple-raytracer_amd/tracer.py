@@ -46,6 +46,8 @@ ABI_SYMBOLS = [
     "srt_unpermute_planes_device",
     "srt_set_denoise_demodulation", "srt_group_set_denoise_demodulation", "srt_last_filter_demodulated",
     "srt_group_last_filter_demodulated",
+    "srt_set_denoise_spatial_variance", "srt_group_set_denoise_spatial_variance", "srt_last_filter_spatial_variance",
+    "srt_group_last_filter_spatial_variance",
     "srt_bvh_refit_wide_host", "srt_set_acceleration_refit", "srt_group_set_acceleration_refit", "srt_acceleration_refit_info",
     "srt_last_refit_kernel_ms", "srt_read_bvh_blocks", "srt_bvh_wide_order_host",
     "srt_set_acceleration_deform", "srt_group_set_acceleration_deform", "srt_acceleration_deform_info",
@@ -563,6 +565,11 @@ def _bind(lib):
         lib.srt_group_set_denoise_demodulation.argtypes = [vp, C.c_int]
         lib.srt_last_filter_demodulated.argtypes = [vp, C.POINTER(C.c_int)]
         lib.srt_group_last_filter_demodulated.argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(lib, "srt_set_denoise_spatial_variance"):  # (an older library, SRT_LIB, in an A/B run)
+        lib.srt_set_denoise_spatial_variance.argtypes = [vp, C.c_uint32]
+        lib.srt_group_set_denoise_spatial_variance.argtypes = [vp, C.c_uint32]
+        lib.srt_last_filter_spatial_variance.argtypes = [vp, C.POINTER(C.c_int)]
+        lib.srt_group_last_filter_spatial_variance.argtypes = [vp, C.POINTER(C.c_int)]
     if hasattr(lib, "srt_set_textures"):
         lib.srt_set_textures.argtypes = [vp, vp, sz]
         lib.srt_set_material_textures.argtypes = [vp, vp, sz]
@@ -648,6 +655,17 @@ class _Denoise:
         """True when the last filter ran the demodulated passes (the switch on and iterations >= 1)."""
         out = C.c_int(0)
         self._check(self._dn("last_filter_demodulated", C.byref(out)))
+        return bool(out.value)
+
+    def set_denoise_spatial_variance(self, min_samples=8):
+        """Pixels with fewer than min_samples samples get their variance from the moments of their 7x7 neighbourhood
+        (srt_set_denoise_spatial_variance); 0: off. Needs the denoiser on; clears nothing, keeps the temporal history."""
+        self._check(self._dn("set_denoise_spatial_variance", int(min_samples)))
+
+    def last_filter_spatial_variance(self):
+        """True when the last filter enqueued the spatial variance estimate (the switch on and iterations >= 1)."""
+        out = C.c_int(0)
+        self._check(self._dn("last_filter_spatial_variance", C.byref(out)))
         return bool(out.value)
 
     def reset_denoise_history(self):
