@@ -673,6 +673,38 @@ int srt_group_set_denoise_spatial_variance(srt_group *g, uint32_t min_samples);
 int srt_last_filter_spatial_variance(const srt_tracer *t, int *ran);
 int srt_group_last_filter_spatial_variance(const srt_group *g, int *ran);
 
+/* ---- the history reprojected as illumination (new; SVGF reprojects demodulated illumination) ---------------------------- */
+
+/* Opt-in, on top of srt_set_denoise_temporal. The temporal set-up gathers the history's *colour* through a bilinear 2x2:
+ * on a textured surface that is a bilinear blur of the texture, once more every frame the camera or an object moves. With
+ * the switch on a tap is rescaled from its own first-hit albedo to this pixel's at the moment it is gathered, which is
+ * reprojection of illumination. The history's contents do not change (it keeps holding colour; every history pixel
+ * already carries its albedo and coverage in its guide), so there is no new device memory and a clear commits what it
+ * commits without the switch. All float32, unfused, in the order written; tests/history_illumination_ref.py restates it.
+ *   pixel p     D_p = max(A_p, SRT_DEMOD_EPS) per channel (fmaxf: a NaN channel gives SRT_DEMOD_EPS), L_p = lum(D_p),
+ *               full_p = (cov_p == 1.0f): every feature sample hit.
+ *   tap h       a counted tap (every rejection rule of the set-up unchanged) of a pixel that projects: D_h, L_h likewise
+ *               from the history guide. full_p and cov_h == 1.0f: r = D_p / D_h per channel (IEEE), rl = L_p / L_h;
+ *               otherwise r = (1, 1, 1), rl = 1 (a partly covered pixel's colour holds sky light that no albedo scaled).
+ *   sums        colour += w (c_h r) per channel, m1 += w (m1_h rl), m2 += w ((m2_h rl) rl); the weight and count sums, the
+ *               integration, the staged and committed sets, the guide and the tonemap are unchanged.
+ *   identity    the one tap of a pixel that does not project (the same camera bit for bit, the shape not moved) is the pixel
+ *               itself and is not rescaled: a still camera gives the same bits with the switch on or off.
+ * Where D_p and D_h are bit-equal, r is exactly 1: an untextured, fully covered surface of one material gives the colour
+ * path's bits. The limits of albedo demodulation carry over: specular > 0, glass and emissive first hits are not exactly
+ * albedo x illumination, so a tap from a dark texel of an emitter can be amplified up to 1 / SRT_DEMOD_EPS; and with
+ * feature_samples < num_samples the guide's mean texel is an estimate (use feature_samples = num_samples on textured scenes).
+ * enable != 0: on. SRT_ERR_STATE unless temporal reprojection is on (so never on a partitioned handle; the group call: the
+ * group's temporal reprojection). Turning temporal reprojection or the denoiser off turns it off. Clears nothing and keeps
+ * the history; takes effect at the next set-up, a filter's or the one a clear runs before its commit when no filter ran
+ * after the last trace (a change of the switch makes the clear run its own set-up, so the history never depends on whether
+ * a filter ran). Independent of demodulation, object motion, per-triangle motion and the spatial variance estimate. */
+int srt_set_denoise_history_illumination(srt_tracer *t, int enable);
+int srt_group_set_denoise_history_illumination(srt_group *g, int enable);
+/* 1 when the last temporal set-up (a filter's or a clear's) launched one of the three illumination kernels, else 0 (also for NULL). */
+int srt_last_setup_history_illumination(srt_tracer *t);
+int srt_group_last_setup_history_illumination(srt_group *g);
+
 /* ---- albedo textures ----------------------------------------------------------
  * Opt-in: where a material has a texture bound, the colour that multiplies the path's mask (and the denoiser's albedo
  * guide) is the texel at the hit's UV instead of srt_material.color. Nothing else about a material changes and a lookup

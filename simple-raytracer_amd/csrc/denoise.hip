@@ -616,6 +616,7 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 		t->dn_demod = false; // albedo demodulation is a mode of the filter
 		t->dn_sv_min = 0;    // and so is the spatial variance estimate
 		t->tp_on = false; // temporal reprojection is a stage of the denoiser
+		t->tp_illum = false; // (with its illumination mode)
 		t->om_on = false; // and object motion a stage of that
 		t->vm_on = false; // (with its per-triangle part)
 		srt_temporal_drop(t);

@@ -727,6 +727,20 @@ int srt_group_last_filter_demodulated(const srt_group *g, int *demodulated) {
 	return SRT_OK;
 }
 
+int srt_group_set_denoise_history_illumination(srt_group *g, int enable) {
+	if (!g) return SRT_ERR_INVALID;
+	if (!enable) {
+		if (g->resolver) SRT_ON_RESOLVER(g, g->resolver, srt_set_denoise_history_illumination(g->resolver, 0));
+		return SRT_OK;
+	}
+	if (!g->dn_on || !g->resolver)
+		return gfail(g, SRT_ERR_STATE, "srt_group_set_denoise_history_illumination: temporal reprojection is off (srt_group_set_denoise_temporal)");
+	SRT_ON_RESOLVER(g, g->resolver, srt_set_denoise_history_illumination(g->resolver, 1)); // the set-up runs on that handle
+	return SRT_OK;
+}
+
+int srt_group_last_setup_history_illumination(srt_group *g) { return g && g->resolver && g->resolver->last_setup_illum ? 1 : 0; }
+
 int srt_group_set_denoise_spatial_variance(srt_group *g, uint32_t min_samples) {
 	if (!g) return SRT_ERR_INVALID;
 	if (min_samples == 0) {

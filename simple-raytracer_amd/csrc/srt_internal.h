@@ -216,6 +216,8 @@ struct srt_tracer {
 	bool tp_valid = false;   // tp_set[tp_cur] holds a history
 	bool tp_fresh = false;   // tp_set[1 - tp_cur] holds the integration of what is traced since the clear (a filter ran after the last trace)
 	srt_render_data tp_cam{}; // the history frame's render data
+	bool tp_illum = false;         // srt_set_denoise_history_illumination: the set-ups rescale a history tap by D_p / D_h
+	bool last_setup_illum = false; // srt_last_setup_history_illumination: the last set-up launched an *_illum_kernel
 	std::vector<uint8_t> scene_bytes; // the last srt_update_scene's arrays and scene data (the history survives an unchanged scene)
 	// object motion (temporal.hip; srt_set_denoise_object_motion): the feature pass stores a shape index per pixel into
 	// om_ids[om_cur]; the commit swaps, so om_ids[1 - om_cur] belongs to the history, traced with the scene om_hist_scene

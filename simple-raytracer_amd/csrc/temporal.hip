@@ -14,6 +14,10 @@
 //   integrate  h' = min(h, history_limit), n = P + h'. h' = 0: the spatial set-up's values (for ticks = T, bit for bit).
 //              Else c = (P c_cur + h' c_h) / n, m1, m2 likewise, V = max(0, m2 - m1^2) / n (non-finite: 0)
 //   staging    {c, min(n, history_limit)}, {m1, m2} and the guide go to the set that becomes the history at the next clear
+//   illumination (srt_set_denoise_history_illumination; the *_illum_kernel variants; tests/history_illumination_ref.py): a counted
+//              tap of the projected 2x2 whose pixel and whose history pixel are both fully covered (cov == 1) enters the sums
+//              as c_h (D_p / D_h) per channel, m1_h rl and (m2_h rl) rl with D = max(A, SRT_DEMOD_EPS), rl = lum(D_p) / lum(D_h);
+//              the identity tap and every other tap stay in colour. The history's contents are the same either way
 // One lane per pixel in 16x16 tiles, like srt_denoise_atrous_kernel; float4 loads, no atomics and no LDS, so runs are
 // bit-identical.
 #include <hip/hip_runtime.h>
@@ -106,6 +110,28 @@ __global__ __launch_bounds__(256) void srt_temporal_deform_kernel(const Temporal
 #include "temporal_body.inc"
 #undef SRT_TEMPORAL_MOTION
 }
+
+// The three set-ups with the history reprojected as illumination (srt_set_denoise_history_illumination): the same bodies with
+// SRT_TEMPORAL_ILLUM 1. The host launches one of these in place of its twin above while the switch is on.
+#define SRT_TEMPORAL_ILLUM 1
+__global__ __launch_bounds__(256) void srt_temporal_setup_illum_kernel(const TemporalParams p) {
+#define SRT_TEMPORAL_MOTION 0
+#include "temporal_body.inc"
+#undef SRT_TEMPORAL_MOTION
+}
+
+__global__ __launch_bounds__(256) void srt_temporal_motion_illum_kernel(const TemporalParams p, const MotionParams mp) {
+#define SRT_TEMPORAL_MOTION 1
+#include "temporal_body.inc"
+#undef SRT_TEMPORAL_MOTION
+}
+
+__global__ __launch_bounds__(256) void srt_temporal_deform_illum_kernel(const TemporalParams p, const MotionParams mp, const VertexParams vp) {
+#define SRT_TEMPORAL_MOTION 2
+#include "temporal_body.inc"
+#undef SRT_TEMPORAL_MOTION
+}
+#undef SRT_TEMPORAL_ILLUM
 
 // The world-vertex table of a scene: blockIdx.y = shape (models only), row first[shape] + j = triangle j's P0, P1, P2 in the
 // pre-pass's expressions (frame.hip srt_prepass_kernel: mat_by_vec(transform, pos, 1.0f)), so the rows are the tracer's world
@@ -417,6 +443,7 @@ int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 	p.out = col;
 	p.argb = argb;
 	const dim3 grid((unsigned)((t->width + 15) / 16), (unsigned)((t->height + 15) / 16));
+	const bool illum = t->tp_illum; // the same variant for a filter's set-up and for a clear's commit
 	if (motion) {
 		MotionParams mp;
 		mp.ids = t->om_ids[t->om_cur].ptr;
@@ -429,13 +456,19 @@ int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 			vp.rows = t->vm_rows[t->om_cur].ptr;
 			vp.h_rows = t->vm_rows[1 - t->om_cur].ptr;
 			vp.first = t->vm_first_dev.ptr;
-			hipLaunchKernelGGL(srt_temporal_deform_kernel, grid, dim3(256), 0, t->stream, p, mp, vp);
-		} else
+			if (illum) hipLaunchKernelGGL(srt_temporal_deform_illum_kernel, grid, dim3(256), 0, t->stream, p, mp, vp);
+			else hipLaunchKernelGGL(srt_temporal_deform_kernel, grid, dim3(256), 0, t->stream, p, mp, vp);
+		} else if (illum)
+			hipLaunchKernelGGL(srt_temporal_motion_illum_kernel, grid, dim3(256), 0, t->stream, p, mp);
+		else
 			hipLaunchKernelGGL(srt_temporal_motion_kernel, grid, dim3(256), 0, t->stream, p, mp);
+	} else if (illum) {
+		hipLaunchKernelGGL(srt_temporal_setup_illum_kernel, grid, dim3(256), 0, t->stream, p);
 	} else {
 		hipLaunchKernelGGL(srt_temporal_setup_kernel, grid, dim3(256), 0, t->stream, p);
 	}
 	SRT_HIP(t, hipGetLastError());
+	t->last_setup_illum = illum;
 	return SRT_OK;
 }
 
@@ -566,6 +599,7 @@ int srt_set_denoise_temporal(srt_tracer *t, const srt_temporal_params *params) {
 		t->tp_on = false;
 		t->om_on = false;
 		t->vm_on = false;
+		t->tp_illum = false; // a mode of the temporal set-up
 		return SRT_OK;
 	}
 	if (!params_ok(*params))
@@ -581,6 +615,18 @@ int srt_set_denoise_temporal(srt_tracer *t, const srt_temporal_params *params) {
 	t->tp_fresh = false; // the staging set was integrated with the old settings
 	return SRT_OK;
 }
+
+int srt_set_denoise_history_illumination(srt_tracer *t, int enable) {
+	if (!t) return SRT_ERR_INVALID;
+	if (enable && !t->tp_on)
+		return fail(t, SRT_ERR_STATE, "srt_set_denoise_history_illumination: temporal reprojection is off (srt_set_denoise_temporal)");
+	const bool on = enable != 0;
+	if (on != t->tp_illum) t->tp_fresh = false; // the staging set was integrated by the other variant: the commit runs its own set-up
+	t->tp_illum = on;
+	return SRT_OK;
+}
+
+int srt_last_setup_history_illumination(srt_tracer *t) { return t && t->last_setup_illum ? 1 : 0; }
 
 int srt_set_denoise_object_motion(srt_tracer *t, int enable) {
 	if (!t) return SRT_ERR_INVALID;

@@ -3,6 +3,9 @@
 // so its instructions are too. In scope: p (TemporalParams); with 1 also mp (MotionParams). SRT_TEMPORAL_MOTION 2
 // (srt_temporal_deform_kernel) is 1 and the DEFORMED state, with vp (VertexParams) in scope; what only it has sits between
 // `#if SRT_TEMPORAL_MOTION == 2` and its `#endif`, so the moved kernel's preprocessed text is what it was.
+// SRT_TEMPORAL_ILLUM 1 (srt_set_denoise_history_illumination; the three *_illum_kernel): a counted tap of the projected 2x2 is
+// rescaled from its own first-hit albedo to this pixel's before it is summed, so the history is reprojected as illumination.
+// What only they have sits between `#if SRT_TEMPORAL_ILLUM` and its `#else` / `#endif`: with 0 the text is what it was.
 	const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
 	if (x >= p.width || y >= p.height) return;
 	const uint32_t i = (uint32_t)y * (uint32_t)p.width + (uint32_t)x;
@@ -25,6 +28,13 @@
 	}
 	const float4 g0 = make_float4(nx, ny, nz, z);
 	const float4 g1 = make_float4(ah.x / p.F, ah.y / p.F, ah.z / p.F, hits / p.F);
+#if SRT_TEMPORAL_ILLUM
+	// the pixel's divisor as srt_denoise_demodulate_kernel forms it (a NaN channel: eps); only a fully covered pixel's colour
+	// is albedo x illumination (hits / F is exactly 1 when every feature sample hit)
+	const float dpr = fmaxf(g1.x, SRT_DEMOD_EPS), dpg = fmaxf(g1.y, SRT_DEMOD_EPS), dpb = fmaxf(g1.z, SRT_DEMOD_EPS);
+	const float lp = lum(dpr, dpg, dpb);
+	const bool full_p = g1.w == 1.0f;
+#endif
 
 	// ---- reprojection ----
 	float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sh = 0.f, s1 = 0.f, s2 = 0.f;
@@ -183,9 +193,27 @@
 				if (!(fabsf(hg0.w - D) <= p.depth_threshold * D)) continue;
 				const float2 hm = p.h_m[j];
 				sw += w;
+#if SRT_TEMPORAL_ILLUM
+				// r = D_p / D_h per channel, rl = lum(D_p) / lum(D_h); a partly covered pixel or tap stays in colour (it holds sky
+				// light no albedo scaled), and so does the identity tap: the pixel itself
+				float rr = 1.f, rg = 1.f, rb = 1.f, rl = 1.f;
+#if SRT_TEMPORAL_MOTION
+				if (full_p && hg1.w == 1.0f && !identity) {
+#else
+				if (full_p && hg1.w == 1.0f && p.mode != TP_IDENTITY) {
+#endif
+					const float dhr = fmaxf(hg1.x, SRT_DEMOD_EPS), dhg = fmaxf(hg1.y, SRT_DEMOD_EPS), dhb = fmaxf(hg1.z, SRT_DEMOD_EPS);
+					rr = dpr / dhr, rg = dpg / dhg, rb = dpb / dhb;
+					rl = lp / lum(dhr, dhg, dhb);
+				}
+				sr += w * (hc.x * rr), sg += w * (hc.y * rg), sb += w * (hc.z * rb);
+				sh += w * hc.w;
+				s1 += w * (hm.x * rl), s2 += w * ((hm.y * rl) * rl);
+#else
 				sr += w * hc.x, sg += w * hc.y, sb += w * hc.z;
 				sh += w * hc.w;
 				s1 += w * hm.x, s2 += w * hm.y;
+#endif
 			}
 		}
 	}

@@ -221,6 +221,16 @@ class Tracer {
 	void set_denoise_demodulation(bool enable = true) {
 		check(group ? srt_group_set_denoise_demodulation(group, enable ? 1 : 0) : srt_set_denoise_demodulation(handle, enable ? 1 : 0));
 	}
+	/// The history reprojected as illumination (srt_set_denoise_history_illumination): a history tap is rescaled from its own
+	/// first-hit albedo to the pixel's, so a moving camera no longer blurs a texture through the history. Needs
+	/// set_denoise_temporal first; one device or a device group (the group's set-up runs on device 0).
+	void set_denoise_history_illumination(bool enable = true) {
+		check(group ? srt_group_set_denoise_history_illumination(group, enable ? 1 : 0) : srt_set_denoise_history_illumination(handle, enable ? 1 : 0));
+	}
+	/// Whether the last temporal set-up (a filter's or a clear's) launched an illumination kernel
+	bool last_setup_history_illumination() {
+		return (group ? srt_group_last_setup_history_illumination(group) : srt_last_setup_history_illumination(handle)) != 0;
+	}
 	/// Spatial variance estimate (srt_set_denoise_spatial_variance): a pixel with fewer than min_samples samples (the first
 	/// frames after a clear, disocclusions under temporal reprojection) takes its variance from the moments of its 7x7
 	/// neighbourhood instead of its own two or three samples. 0 turns it off. Needs set_denoise first; one device or a group.

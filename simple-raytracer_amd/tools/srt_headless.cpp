@@ -5,13 +5,14 @@
 //
 //   srt_headless [--scene spheres|meshes|empty] [--obj f.obj]... [--stl f.stl]...
 //                [--width W --height H --spp S --bounces B --frames N --time T]
-//                [--obj-materials] [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--move DX]
+//                [--obj-materials] [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--move DX]
 // --denoise K: the frames go through the edge-aware denoiser with K a-trous passes (Tracer::set_denoise; with --gpus N the
 //                members gather the filter's inputs with the frame and device 0 filters: the same bytes as on one device)
 // --demodulate: with --denoise, the passes filter colour / first-hit albedo (Tracer::set_denoise_demodulation); an error without it
 // --spatial-variance N: with --denoise, pixels with fewer than N samples take their variance from their 7x7 neighbourhood
 //                (Tracer::set_denoise_spatial_variance); an error without it
 // --temporal: with --denoise, the denoiser's temporal reprojection (Tracer::set_denoise_temporal)
+// --history-illumination: with --temporal, the history is reprojected as illumination (Tracer::set_denoise_history_illumination); an error without it
 // --move DX: the camera moves by DX along x every frame and every frame clears the canvas, as the front-end does while moving
 // --move-shape I DX: with --temporal, shape I (a sphere, a plane or a model instance) moves by DX along x every frame and every
 //                frame clears the canvas, as the front-end does while a gizmo is dragged; turns object motion on
@@ -120,7 +121,7 @@ int main(int argc, char **argv) {
 	unsigned time_seed = 12345;
 	bool parse_only = false, bvh = false, pipelined = false, obj_materials = false;
 	int gpus = 1, denoise = -1, spatial_variance = 0;
-	bool temporal = false, demodulate = false;
+	bool temporal = false, demodulate = false, history_illumination = false;
 	float move = 0.0f, shape_move = 0.0f;
 	int move_shape = -1;
 	bool moving = false;
@@ -181,12 +182,13 @@ int main(int argc, char **argv) {
 		else if (a == "--demodulate") demodulate = true;
 		else if (a == "--spatial-variance") spatial_variance = std::atoi(next());
 		else if (a == "--temporal") temporal = true;
+		else if (a == "--history-illumination") history_illumination = true;
 		else if (a == "--move") move = std::strtof(next(), nullptr), moving = true;
 		else if (a == "--move-shape") move_shape = std::atoi(next()), shape_move = std::strtof(next(), nullptr);
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
+			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
@@ -197,6 +199,10 @@ int main(int argc, char **argv) {
 	}
 	if (spatial_variance != 0 && (denoise < 0 || spatial_variance < 0)) {
 		std::cerr << "--spatial-variance N needs --denoise K and N >= 0\n";
+		return 2;
+	}
+	if (history_illumination && (!temporal || denoise < 0)) {
+		std::cerr << "--history-illumination needs --denoise K --temporal\n";
 		return 2;
 	}
 	if (temporal && denoise < 0) {
@@ -317,6 +323,7 @@ int main(int argc, char **argv) {
 	if (demodulate) tracer.set_denoise_demodulation();
 	if (spatial_variance > 0) tracer.set_denoise_spatial_variance((uint32_t)spatial_variance);
 	if (temporal) tracer.set_denoise_temporal();
+	if (history_illumination) tracer.set_denoise_history_illumination();
 	if (move_shape >= 0) {
 		if (!temporal || (size_t)move_shape >= shapes.size()) {
 			std::cerr << "--move-shape needs --temporal and a shape index below " << shapes.size() << "\n";

@@ -48,6 +48,8 @@ ABI_SYMBOLS = [
     "srt_group_last_filter_demodulated",
     "srt_set_denoise_spatial_variance", "srt_group_set_denoise_spatial_variance", "srt_last_filter_spatial_variance",
     "srt_group_last_filter_spatial_variance",
+    "srt_set_denoise_history_illumination", "srt_group_set_denoise_history_illumination", "srt_last_setup_history_illumination",
+    "srt_group_last_setup_history_illumination",
     "srt_bvh_refit_wide_host", "srt_set_acceleration_refit", "srt_group_set_acceleration_refit", "srt_acceleration_refit_info",
     "srt_last_refit_kernel_ms", "srt_read_bvh_blocks", "srt_bvh_wide_order_host",
     "srt_set_acceleration_deform", "srt_group_set_acceleration_deform", "srt_acceleration_deform_info",
@@ -570,6 +572,11 @@ def _bind(lib):
         lib.srt_group_set_denoise_spatial_variance.argtypes = [vp, C.c_uint32]
         lib.srt_last_filter_spatial_variance.argtypes = [vp, C.POINTER(C.c_int)]
         lib.srt_group_last_filter_spatial_variance.argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(lib, "srt_set_denoise_history_illumination"):  # (an older library, SRT_LIB, in an A/B run)
+        lib.srt_set_denoise_history_illumination.argtypes = [vp, C.c_int]
+        lib.srt_group_set_denoise_history_illumination.argtypes = [vp, C.c_int]
+        lib.srt_last_setup_history_illumination.argtypes = [vp]
+        lib.srt_group_last_setup_history_illumination.argtypes = [vp]
     if hasattr(lib, "srt_set_textures"):
         lib.srt_set_textures.argtypes = [vp, vp, sz]
         lib.srt_set_material_textures.argtypes = [vp, vp, sz]
@@ -667,6 +674,15 @@ class _Denoise:
         out = C.c_int(0)
         self._check(self._dn("last_filter_spatial_variance", C.byref(out)))
         return bool(out.value)
+
+    def set_denoise_history_illumination(self, enable=True):
+        """Reproject the temporal history as illumination: a history tap is rescaled from its own first-hit albedo to the
+        pixel's (srt_set_denoise_history_illumination). Needs temporal reprojection on; clears nothing, keeps the history."""
+        self._check(self._dn("set_denoise_history_illumination", 1 if enable else 0))
+
+    def last_setup_history_illumination(self):
+        """True when the last temporal set-up (a filter's or a clear's) launched an illumination kernel."""
+        return bool(self._dn("last_setup_history_illumination"))
 
     def reset_denoise_history(self):
         """Drop the temporal history: the next frame is filtered as by the spatial denoiser alone."""
