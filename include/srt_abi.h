@@ -705,6 +705,51 @@ int srt_group_set_denoise_history_illumination(srt_group *g, int enable);
 int srt_last_setup_history_illumination(srt_tracer *t);
 int srt_group_last_setup_history_illumination(srt_group *g);
 
+/* ---- the history clamped to the frame's local colour range (new; neighbourhood clamping of the reprojected history) ------ */
+
+/* Opt-in, on top of srt_set_denoise_temporal. The temporal set-up accepts a history tap on geometry alone (shape, normal,
+ * depth), so what a moved shape lights or shades -- its shadow, its reflection, an emitter's glow -- stays in the history of
+ * pixels that did not move and fades over history_limit / P frames. With the clamp on, the history colour of a pixel is pulled
+ * into the range the current frame's own samples around that pixel make plausible before it is blended in. All float32,
+ * unfused, in the order written; tests/history_clamp_ref.py restates it.
+ *   bounds      one launch before the set-up, only when the clamp is on and a valid history exists (without one nothing new
+ *               is launched). Pixel p qualifies with cov_p > 0 and a finite colour c_p = canvas_p / T (the set-up's
+ *               expressions). Its 49 taps q = p + (dx, dy), |dx|, |dy| <= 3, dy outer, dx inner; a tap counts unless it is
+ *               outside the image, has cov 0 or a non-finite colour. The centre has weight 1, another counting tap the spatial
+ *               variance estimate's geometric weight from the handle's filter sigmas,
+ *               w = exp(-|Zp - Zq| / (sz Zp r + 1e-6)) max(0, Np.Nq)^sn exp(-|Ap - Aq|^2 / sa^2), r = max(|dx|, |dy|)
+ *               (Np.Nq <= 0: it counts with weight 0). Per channel mu = sum w c / sum w, s = sum w (c c) / sum w,
+ *               sigma = sqrt(max(0, s - mu mu)), evaluated on the differences from the centre (which is the same
+ *               quantity, without subtracting two large squares where the colour is bright and the spread small):
+ *               e_q = c_q - c_p, d = sum w e / sum w, q = sum w (e e) / sum w, mu = c_p + d, sigma = sqrt(max(0, q - d d)).
+ *   planes      0: {mu.rgb, sum w}, 1: {sigma.rgb, number of counting taps}. sum w is stored as 0, "do not clamp", when
+ *               fewer than 5 taps count (the centre included: a thin feature's 4 neighbours say nothing about a range) or a
+ *               mu or q is not finite; a pixel that does not qualify has both planes 0.
+ *   clamp       in the set-up, where a pixel's history colour x_h is complete: after the bilinear gather or the same-camera
+ *               tap, and after srt_set_denoise_history_illumination's rescale. With sum w > 0 each channel:
+ *               x < mu - gamma sigma: x = mu - gamma sigma; else x > mu + gamma sigma: x = mu + gamma sigma (gamma sigma
+ *               rounded first; comparisons, so a NaN moves nothing). No channel moved: nothing else changes and the pixel's
+ *               outputs are the switch-off outputs bit for bit. Else the history moments follow and keep their variance:
+ *               m1' = lum(x_h'), m2' = max(0, m2_h - m1_h m1_h) + m1' m1'.
+ *   unchanged   counts, weights, history_limit, the blend, the staged and committed sets' layout. The clamped value goes
+ *               through the blend into what the next clear commits, so a stale value decays on its own; no count is reduced.
+ * gamma == 0: off (the default). Finite 0 < gamma <= 64: on; anything else SRT_ERR_INVALID. SRT_ERR_STATE unless temporal
+ * reprojection is on (so never on a partitioned handle; the group call: the group's temporal reprojection). Turning temporal
+ * reprojection or the denoiser off turns it off. Clears nothing and keeps the history; the two planes (32 B per pixel) are
+ * allocated at the first enable and are no part of the history or of a group's gather. Takes effect at the next set-up, a
+ * filter's or the one a clear runs before its commit when no filter ran after the last trace (a change of gamma makes the
+ * clear run its own set-up: both run the bounds launch and the same clamping kernel, so the history never depends on
+ * whether a filter ran). Works under demodulation (the set-up still outputs colour), the spatial variance estimate, history
+ * illumination, object and per-triangle motion, K = 0 and frames of several dispatches. */
+int srt_set_denoise_history_clamp(srt_tracer *t, float gamma);
+int srt_group_set_denoise_history_clamp(srt_group *g, float gamma);
+/* 1 when the last temporal set-up (a filter's or a clear's) ran the bounds launch and a clamping set-up, else 0 (also for NULL). */
+int srt_last_setup_history_clamp(srt_tracer *t);
+int srt_group_last_setup_history_clamp(srt_group *g);
+/* For tests: the two planes of the last bounds launch, height*width float4 each (either may be NULL). SRT_ERR_STATE when the
+ * clamp has never run on this handle. */
+int srt_read_denoise_history_bounds(srt_tracer *t, float *mean_weight, float *sigma_taps);
+
 /* ---- albedo textures ----------------------------------------------------------
  * Opt-in: where a material has a texture bound, the colour that multiplies the path's mask (and the denoiser's albedo
  * guide) is the texel at the hit's UV instead of srt_material.color. Nothing else about a material changes and a lookup

@@ -617,6 +617,7 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 		t->dn_sv_min = 0;    // and so is the spatial variance estimate
 		t->tp_on = false; // temporal reprojection is a stage of the denoiser
 		t->tp_illum = false; // (with its illumination mode)
+		t->tp_clamp = 0.f;   // (and its history clamp)
 		t->om_on = false; // and object motion a stage of that
 		t->vm_on = false; // (with its per-triangle part)
 		srt_temporal_drop(t);
@@ -634,6 +635,7 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 	SRT_HIP(t, t->dn_guide.reserve(px * 8));
 	SRT_HIP(t, t->dn_col.reserve(px * 8));
 	const bool clear = !t->dn_on || params->feature_samples != t->dn.feature_samples;
+	if (t->tp_clamp > 0.f) t->tp_fresh = false; // the history clamp's bounds take their weights from the filter's sigmas
 	t->dn = *params;
 	t->dn_on = true;
 	if (clear) {

@@ -211,6 +211,7 @@ void srt_destroy(srt_tracer *t) {
 	t->dn_col.release();
 	t->tp_set[0].release();
 	t->tp_set[1].release();
+	t->tp_bounds.release();
 	t->om_ids[0].release();
 	t->om_ids[1].release();
 	t->om_table_dev.release();

@@ -12,6 +12,7 @@
 // single-GPU user never touches it.
 #include <dlfcn.h>
 
+#include <cmath>
 #include <cstring>
 #include <new>
 
@@ -740,6 +741,22 @@ int srt_group_set_denoise_history_illumination(srt_group *g, int enable) {
 }
 
 int srt_group_last_setup_history_illumination(srt_group *g) { return g && g->resolver && g->resolver->last_setup_illum ? 1 : 0; }
+
+int srt_group_set_denoise_history_clamp(srt_group *g, float gamma) {
+	if (!g) return SRT_ERR_INVALID;
+	if (gamma == 0.0f) {
+		if (g->resolver) SRT_ON_RESOLVER(g, g->resolver, srt_set_denoise_history_clamp(g->resolver, 0.0f));
+		return SRT_OK;
+	}
+	if (!(std::isfinite(gamma) && gamma > 0.0f && gamma <= 64.0f))
+		return gfail(g, SRT_ERR_INVALID, "srt_group_set_denoise_history_clamp: gamma 0 (off) or finite in (0, 64]");
+	if (!g->dn_on || !g->resolver)
+		return gfail(g, SRT_ERR_STATE, "srt_group_set_denoise_history_clamp: temporal reprojection is off (srt_group_set_denoise_temporal)");
+	SRT_ON_RESOLVER(g, g->resolver, srt_set_denoise_history_clamp(g->resolver, gamma)); // the set-up runs on that handle
+	return SRT_OK;
+}
+
+int srt_group_last_setup_history_clamp(srt_group *g) { return g && g->resolver && g->resolver->last_setup_clamp ? 1 : 0; }
 
 int srt_group_set_denoise_spatial_variance(srt_group *g, uint32_t min_samples) {
 	if (!g) return SRT_ERR_INVALID;

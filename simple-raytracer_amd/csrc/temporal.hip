@@ -133,6 +133,162 @@ __global__ __launch_bounds__(256) void srt_temporal_deform_illum_kernel(const Te
 }
 #undef SRT_TEMPORAL_ILLUM
 
+// ---- the history clamp (srt_set_denoise_history_clamp; include/srt_abi.h has the definition, tests/history_clamp_ref.py restates
+// it): one launch before the set-up makes per-pixel colour bounds of the frame, and the set-up's clamping form pulls the
+// history colour of a pixel into them before it is blended in.
+struct BoundsParams {
+	int32_t width, height;
+	uint32_t num_pixels;
+	float T, F;                           // the set-up's divisors
+	float sigma_n, sigma_z, inv_sigma_a2; // as the filter's FilterParams
+	const float4 *canvas;
+	const float4 *normal_depth;
+	const float4 *albedo_hits;
+	float4 *bounds; // plane 0 {mu.rgb, sum of weights (0: do not clamp)}, plane 1 {sigma.rgb, counting taps}
+};
+
+struct ClampParams { // the last argument of the *_clamp_kernel set-ups
+	const float4 *bounds;
+	uint32_t num_pixels;
+	float gamma;
+};
+
+enum { TB_R = 3, TB_HALO = 16 + 2 * TB_R, TB_ROW = 32 }; // the 22x22 halo tile, rows of 32 float4
+
+// Per pixel p with cov > 0 and a finite colour c_p = canvas_p / T: over the 49 taps q = p + (dx, dy), |dx|, |dy| <= 3 (dy outer,
+// dx inner) that are inside the image, have cov > 0 and a finite colour, with the spatial variance estimate's geometric weight
+// w = exp(-|Zp - Zq| / (sz Zp r + 1e-6)) max(0, Np.Nq)^sn exp(-|Ap - Aq|^2 / sa^2), r = max(|dx|, |dy|) (the centre: 1),
+// mu = sum w c / sum w, s = sum w c^2 / sum w, sigma = sqrt(max(0, s - mu^2)) per channel, evaluated on e = c_q - c_p (mu =
+// c_p + sum w e / sum w, sigma^2 = sum w e^2 / sum w - (sum w e / sum w)^2: the same numbers without the cancellation of two
+// large squares where the colour is bright and the spread small). No atomics, a fixed tap order.
+// The tile is three float4 arrays ({c, counts ? 1 : 0}, {N, Z}, {A, -}) with rows of 32 entries = 128 dwords: a 16-B LDS read
+// is served in groups of 16 lanes that take 8 pixels of one image row and 4 + 4 of the next (64 banks), and with that stride
+// the next row starts on bank 0 again, so pixels 0-3 and 12-15 of one row (banks 0-15, 48-63) and 4-11 of the other (16-47)
+// never meet. A tap that does not count costs one read (its marker), the two other arrays hold nothing for it.
+__global__ __launch_bounds__(256) void srt_temporal_bounds_kernel(const BoundsParams p) {
+	__shared__ float4 t_c[TB_HALO * TB_ROW];
+	__shared__ float4 t_g0[TB_HALO * TB_ROW];
+	__shared__ float4 t_a[TB_HALO * TB_ROW];
+	const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+	const int x0 = blockIdx.x * 16, y0 = blockIdx.y * 16;
+	for (int e = threadIdx.x; e < TB_HALO * TB_HALO; e += 256) {
+		const int hy = e / TB_HALO, hx = e - hy * TB_HALO;
+		const int qx = x0 - TB_R + hx, qy = y0 - TB_R + hy;
+		float4 cc = make_float4(0.f, 0.f, 0.f, 0.f);
+		if (qx >= 0 && qx < p.width && qy >= 0 && qy < p.height) {
+			// the set-up's expressions (temporal_body.inc): colour, cov = hits / F, N, Z, A
+			const uint32_t j = (uint32_t)qy * (uint32_t)p.width + (uint32_t)qx;
+			const float4 c = p.canvas[j], ah = p.albedo_hits[j];
+			cc = make_float4(c.x / p.T, c.y / p.T, c.z / p.T, 0.f);
+			const float hits = ah.w;
+			if (hits / p.F > 0.f && finite3(cc)) {
+				const float4 nd = p.normal_depth[j];
+				float nx = 0.f, ny = 0.f, nz = 0.f;
+				const float len = sqrtf(nd.x * nd.x + nd.y * nd.y + nd.z * nd.z);
+				if (len > 0.f) nx = nd.x / len, ny = nd.y / len, nz = nd.z / len;
+				cc.w = 1.f;
+				t_g0[hy * TB_ROW + hx] = make_float4(nx, ny, nz, nd.w / hits);
+				t_a[hy * TB_ROW + hx] = make_float4(ah.x / p.F, ah.y / p.F, ah.z / p.F, 0.f);
+			}
+		}
+		t_c[hy * TB_ROW + hx] = cc;
+	}
+	__syncthreads();
+	const int x = x0 + tx, y = y0 + ty;
+	if (x >= p.width || y >= p.height) return;
+	const uint32_t i = (uint32_t)y * (uint32_t)p.width + (uint32_t)x;
+	const int ce = (ty + TB_R) * TB_ROW + tx + TB_R;
+	const float4 cp = t_c[ce];
+	float4 o0 = make_float4(0.f, 0.f, 0.f, 0.f), o1 = o0;
+	if (cp.w > 0.f) {
+		const float4 g0p = t_g0[ce], ap = t_a[ce];
+		const float zs = p.sigma_z * g0p.w;
+		const float inv_dz1 = 1.0f / (zs * 1.0f + 1e-6f), inv_dz2 = 1.0f / (zs * 2.0f + 1e-6f), inv_dz3 = 1.0f / (zs * 3.0f + 1e-6f);
+		float sw = 0.f, s1r = 0.f, s1g = 0.f, s1b = 0.f, s2r = 0.f, s2g = 0.f, s2b = 0.f;
+		int taps = 0;
+		for (int dy = -TB_R; dy <= TB_R; dy++) {
+			for (int dx = -TB_R; dx <= TB_R; dx++) {
+				if (dx == 0 && dy == 0) { // the centre: weight 1
+					taps++;
+					sw += 1.0f;
+					continue; // (its difference from itself adds 0 to every sum)
+				}
+				const int qe = (ty + TB_R + dy) * TB_ROW + tx + TB_R + dx;
+				const float4 cq = t_c[qe];
+				if (!(cq.w > 0.f)) continue;
+				taps++;
+				const float4 g0q = t_g0[qe];
+				const float d = g0p.x * g0q.x + g0p.y * g0q.y + g0p.z * g0q.z;
+				if (!(d > 0.f)) continue; // max(0, d)^sigma_n = 0: it counts and weighs nothing
+				const float4 aq = t_a[qe];
+				const float wn = __expf(p.sigma_n * __logf(d));
+				const int r = max(abs(dx), abs(dy));
+				const float ar = ap.x - aq.x, ag = ap.y - aq.y, ab = ap.z - aq.z;
+				const float e = fabsf(g0p.w - g0q.w) * (r == 1 ? inv_dz1 : r == 2 ? inv_dz2 : inv_dz3) + (ar * ar + ag * ag + ab * ab) * p.inv_sigma_a2;
+				const float w = wn * __expf(-e);
+				sw += w;
+				const float er = cq.x - cp.x, eg = cq.y - cp.y, eb = cq.z - cp.z;
+				s1r += w * er, s1g += w * eg, s1b += w * eb;
+				s2r += w * (er * er), s2g += w * (eg * eg), s2b += w * (eb * eb);
+			}
+		}
+		const float dr = s1r / sw, dg = s1g / sw, db = s1b / sw; // mu - c_p
+		const float qr = s2r / sw, qg = s2g / sw, qb = s2b / sw;
+		const float mr = cp.x + dr, mg = cp.y + dg, mb = cp.z + db;
+		float vr = qr - dr * dr, vg = qg - dg * dg, vb = qb - db * db;
+		vr = vr > 0.f ? vr : 0.f, vg = vg > 0.f ? vg : 0.f, vb = vb > 0.f ? vb : 0.f;
+		// fewer than 5 counting taps say nothing about a range; a sum that overflowed gives no range either
+		const bool use = taps >= 5 && finite3(make_float4(mr, mg, mb, 0.f)) && finite3(make_float4(qr, qg, qb, 0.f));
+		o0 = make_float4(mr, mg, mb, use ? sw : 0.f);
+		o1 = make_float4(sqrtf(vr), sqrtf(vg), sqrtf(vb), (float)taps);
+	}
+	p.bounds[i] = o0;
+	p.bounds[p.num_pixels + i] = o1;
+}
+
+// The six set-ups that clamp: the same bodies with SRT_TEMPORAL_CLAMP 1 and the bounds as their last argument. The host launches
+// one of these in place of its twin above when the clamp is on and a history exists. Instantiations, not a flag in fewer
+// kernels: the twins above keep their instructions, and a clamping set-up pays no branch for the other variants.
+#define SRT_TEMPORAL_CLAMP 1
+__global__ __launch_bounds__(256) void srt_temporal_setup_clamp_kernel(const TemporalParams p, const ClampParams cp) {
+#define SRT_TEMPORAL_MOTION 0
+#include "temporal_body.inc"
+#undef SRT_TEMPORAL_MOTION
+}
+
+__global__ __launch_bounds__(256) void srt_temporal_motion_clamp_kernel(const TemporalParams p, const MotionParams mp, const ClampParams cp) {
+#define SRT_TEMPORAL_MOTION 1
+#include "temporal_body.inc"
+#undef SRT_TEMPORAL_MOTION
+}
+
+__global__ __launch_bounds__(256) void srt_temporal_deform_clamp_kernel(const TemporalParams p, const MotionParams mp, const VertexParams vp, const ClampParams cp) {
+#define SRT_TEMPORAL_MOTION 2
+#include "temporal_body.inc"
+#undef SRT_TEMPORAL_MOTION
+}
+
+#define SRT_TEMPORAL_ILLUM 1
+__global__ __launch_bounds__(256) void srt_temporal_setup_illum_clamp_kernel(const TemporalParams p, const ClampParams cp) {
+#define SRT_TEMPORAL_MOTION 0
+#include "temporal_body.inc"
+#undef SRT_TEMPORAL_MOTION
+}
+
+__global__ __launch_bounds__(256) void srt_temporal_motion_illum_clamp_kernel(const TemporalParams p, const MotionParams mp, const ClampParams cp) {
+#define SRT_TEMPORAL_MOTION 1
+#include "temporal_body.inc"
+#undef SRT_TEMPORAL_MOTION
+}
+
+__global__ __launch_bounds__(256) void srt_temporal_deform_illum_clamp_kernel(const TemporalParams p, const MotionParams mp, const VertexParams vp, const ClampParams cp) {
+#define SRT_TEMPORAL_MOTION 2
+#include "temporal_body.inc"
+#undef SRT_TEMPORAL_MOTION
+}
+#undef SRT_TEMPORAL_ILLUM
+#undef SRT_TEMPORAL_CLAMP
+
 // The world-vertex table of a scene: blockIdx.y = shape (models only), row first[shape] + j = triangle j's P0, P1, P2 in the
 // pre-pass's expressions (frame.hip srt_prepass_kernel: mat_by_vec(transform, pos, 1.0f)), so the rows are the tracer's world
 // vertices bit for bit, in array order whatever the acceleration stores.
@@ -444,7 +600,52 @@ int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 	p.argb = argb;
 	const dim3 grid((unsigned)((t->width + 15) / 16), (unsigned)((t->height + 15) / 16));
 	const bool illum = t->tp_illum; // the same variant for a filter's set-up and for a clear's commit
-	if (motion) {
+	const bool clamp = t->tp_clamp > 0.f && t->tp_valid; // the history clamp: without a history nothing new is launched
+	if (clamp) {
+		BoundsParams bp;
+		bp.width = t->width;
+		bp.height = t->height;
+		bp.num_pixels = (uint32_t)px;
+		bp.T = p.T;
+		bp.F = p.F;
+		bp.sigma_n = t->dn.sigma_normal;
+		bp.sigma_z = t->dn.sigma_depth;
+		bp.inv_sigma_a2 = (float)std::min(1.0 / ((double)t->dn.sigma_albedo * (double)t->dn.sigma_albedo), (double)FLT_MAX); // as srt_denoise_filter
+		bp.canvas = p.canvas;
+		bp.normal_depth = p.normal_depth;
+		bp.albedo_hits = p.albedo_hits;
+		bp.bounds = reinterpret_cast<float4 *>(t->tp_bounds.ptr);
+		hipLaunchKernelGGL(srt_temporal_bounds_kernel, grid, dim3(256), 0, t->stream, bp);
+		SRT_HIP(t, hipGetLastError());
+		t->tp_bounds_ran = true;
+		ClampParams cp;
+		cp.bounds = bp.bounds;
+		cp.num_pixels = bp.num_pixels;
+		cp.gamma = t->tp_clamp;
+		if (motion) {
+			MotionParams mp;
+			mp.ids = t->om_ids[t->om_cur].ptr;
+			mp.h_ids = t->om_ids[1 - t->om_cur].ptr;
+			mp.table = t->om_table_dev.ptr;
+			mp.n_shapes = (uint32_t)(t->om_table.size() / SRT_MOTION_WORDS);
+			if (t->vm_on && t->om_any_deformed) {
+				VertexParams vp;
+				vp.tris = t->vm_tri[t->om_cur].ptr;
+				vp.rows = t->vm_rows[t->om_cur].ptr;
+				vp.h_rows = t->vm_rows[1 - t->om_cur].ptr;
+				vp.first = t->vm_first_dev.ptr;
+				if (illum) hipLaunchKernelGGL(srt_temporal_deform_illum_clamp_kernel, grid, dim3(256), 0, t->stream, p, mp, vp, cp);
+				else hipLaunchKernelGGL(srt_temporal_deform_clamp_kernel, grid, dim3(256), 0, t->stream, p, mp, vp, cp);
+			} else if (illum)
+				hipLaunchKernelGGL(srt_temporal_motion_illum_clamp_kernel, grid, dim3(256), 0, t->stream, p, mp, cp);
+			else
+				hipLaunchKernelGGL(srt_temporal_motion_clamp_kernel, grid, dim3(256), 0, t->stream, p, mp, cp);
+		} else if (illum) {
+			hipLaunchKernelGGL(srt_temporal_setup_illum_clamp_kernel, grid, dim3(256), 0, t->stream, p, cp);
+		} else {
+			hipLaunchKernelGGL(srt_temporal_setup_clamp_kernel, grid, dim3(256), 0, t->stream, p, cp);
+		}
+	} else if (motion) {
 		MotionParams mp;
 		mp.ids = t->om_ids[t->om_cur].ptr;
 		mp.h_ids = t->om_ids[1 - t->om_cur].ptr;
@@ -469,6 +670,7 @@ int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 	}
 	SRT_HIP(t, hipGetLastError());
 	t->last_setup_illum = illum;
+	t->last_setup_clamp = clamp;
 	return SRT_OK;
 }
 
@@ -600,6 +802,7 @@ int srt_set_denoise_temporal(srt_tracer *t, const srt_temporal_params *params) {
 		t->om_on = false;
 		t->vm_on = false;
 		t->tp_illum = false; // a mode of the temporal set-up
+		t->tp_clamp = 0.f;   // and so is the history clamp
 		return SRT_OK;
 	}
 	if (!params_ok(*params))
@@ -627,6 +830,34 @@ int srt_set_denoise_history_illumination(srt_tracer *t, int enable) {
 }
 
 int srt_last_setup_history_illumination(srt_tracer *t) { return t && t->last_setup_illum ? 1 : 0; }
+
+int srt_set_denoise_history_clamp(srt_tracer *t, float gamma) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!(gamma == 0.0f) && !(std::isfinite(gamma) && gamma > 0.0f && gamma <= 64.0f))
+		return fail(t, SRT_ERR_INVALID, "srt_set_denoise_history_clamp: gamma 0 (off) or finite in (0, 64]");
+	if (gamma == 0.0f) gamma = 0.0f; // (-0: off)
+	if (gamma > 0.0f) {
+		if (!t->tp_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_history_clamp: temporal reprojection is off (srt_set_denoise_temporal)");
+		SRT_HIP(t, hipSetDevice(t->device));
+		SRT_HIP(t, t->tp_bounds.reserve(full_pixels(t) * 8)); // the two planes, on the first enable
+	}
+	if (gamma != t->tp_clamp) t->tp_fresh = false; // the staging set was integrated with the other setting: the commit runs its own set-up
+	t->tp_clamp = gamma;
+	return SRT_OK;
+}
+
+int srt_last_setup_history_clamp(srt_tracer *t) { return t && t->last_setup_clamp ? 1 : 0; }
+
+int srt_read_denoise_history_bounds(srt_tracer *t, float *mean_weight, float *sigma_taps) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!t->tp_bounds.ptr || !t->tp_bounds_ran) return fail(t, SRT_ERR_STATE, "srt_read_denoise_history_bounds: the history clamp has never run on this handle (srt_set_denoise_history_clamp)");
+	const size_t px = full_pixels(t);
+	SRT_HIP(t, hipSetDevice(t->device));
+	if (mean_weight) SRT_HIP(t, hipMemcpyAsync(mean_weight, t->tp_bounds.ptr, px * 16, hipMemcpyDeviceToHost, t->stream));
+	if (sigma_taps) SRT_HIP(t, hipMemcpyAsync(sigma_taps, t->tp_bounds.ptr + px * 4, px * 16, hipMemcpyDeviceToHost, t->stream));
+	SRT_HIP(t, hipStreamSynchronize(t->stream));
+	return SRT_OK;
+}
 
 int srt_set_denoise_object_motion(srt_tracer *t, int enable) {
 	if (!t) return SRT_ERR_INVALID;

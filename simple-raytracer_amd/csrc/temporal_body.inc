@@ -6,6 +6,8 @@
 // SRT_TEMPORAL_ILLUM 1 (srt_set_denoise_history_illumination; the three *_illum_kernel): a counted tap of the projected 2x2 is
 // rescaled from its own first-hit albedo to this pixel's before it is summed, so the history is reprojected as illumination.
 // What only they have sits between `#if SRT_TEMPORAL_ILLUM` and its `#else` / `#endif`: with 0 the text is what it was.
+// SRT_TEMPORAL_CLAMP 1 (srt_set_denoise_history_clamp; the six *_clamp_kernel, cp (ClampParams) in scope): the history colour is
+// clamped into the bounds srt_temporal_bounds_kernel made of the frame, between `#if SRT_TEMPORAL_CLAMP` and its `#else`.
 	const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
 	if (x >= p.width || y >= p.height) return;
 	const uint32_t i = (uint32_t)y * (uint32_t)p.width + (uint32_t)x;
@@ -225,7 +227,33 @@
 	float m1 = l, m2 = m2c, n = p.P;
 	if (h > 0.f) {
 		n = p.P + h;
+#if SRT_TEMPORAL_CLAMP
+		// the history colour x_h is complete here (gathered, and rescaled under SRT_TEMPORAL_ILLUM): each channel into
+		// [mu - gamma sigma, mu + gamma sigma] of this pixel's bounds (sum of weights 0: no clamp). By comparisons, so a NaN on
+		// either side moves nothing; when no channel moved every value below is what it is without the clamp
+		float hr = sr / sw, hgc = sg / sw, hb = sb / sw, h1 = s1 / sw, h2 = s2 / sw;
+		const float4 b0 = cp.bounds[i];
+		if (b0.w > 0.f) {
+			const float4 b1 = cp.bounds[cp.num_pixels + i];
+			const float er = cp.gamma * b1.x, eg = cp.gamma * b1.y, eb = cp.gamma * b1.z;
+			const float lor = b0.x - er, hir = b0.x + er, log_ = b0.y - eg, hig = b0.y + eg, lob = b0.z - eb, hib = b0.z + eb;
+			bool mv = false;
+			if (hr < lor) hr = lor, mv = true;
+			else if (hr > hir) hr = hir, mv = true;
+			if (hgc < log_) hgc = log_, mv = true;
+			else if (hgc > hig) hgc = hig, mv = true;
+			if (hb < lob) hb = lob, mv = true;
+			else if (hb > hib) hb = hib, mv = true;
+			if (mv) { // the moments follow the colour and keep their variance
+				float hv = h2 - h1 * h1;
+				hv = hv > 0.f ? hv : 0.f;
+				h1 = lum(hr, hgc, hb);
+				h2 = hv + h1 * h1;
+			}
+		}
+#else
 		const float hr = sr / sw, hgc = sg / sw, hb = sb / sw, h1 = s1 / sw, h2 = s2 / sw;
+#endif
 		o.x = (p.P * cc.x + h * hr) / n;
 		o.y = (p.P * cc.y + h * hgc) / n;
 		o.z = (p.P * cc.z + h * hb) / n;

@@ -231,6 +231,17 @@ class Tracer {
 	bool last_setup_history_illumination() {
 		return (group ? srt_group_last_setup_history_illumination(group) : srt_last_setup_history_illumination(handle)) != 0;
 	}
+	/// The history clamp (srt_set_denoise_history_clamp): the reprojected history colour of a pixel is pulled into mean +- gamma
+	/// sigma of the current frame's 7x7 neighbourhood before it is blended in, so lighting a moved shape left behind (its shadow,
+	/// its reflection) is corrected within a frame or two. 0 turns it off. Needs set_denoise_temporal first; one device or a
+	/// device group (the group's set-up runs on device 0).
+	void set_denoise_history_clamp(float gamma = 1.0f) {
+		check(group ? srt_group_set_denoise_history_clamp(group, gamma) : srt_set_denoise_history_clamp(handle, gamma));
+	}
+	/// Whether the last temporal set-up (a filter's or a clear's) ran the bounds launch and a clamping set-up
+	bool last_setup_history_clamp() {
+		return (group ? srt_group_last_setup_history_clamp(group) : srt_last_setup_history_clamp(handle)) != 0;
+	}
 	/// Spatial variance estimate (srt_set_denoise_spatial_variance): a pixel with fewer than min_samples samples (the first
 	/// frames after a clear, disocclusions under temporal reprojection) takes its variance from the moments of its 7x7
 	/// neighbourhood instead of its own two or three samples. 0 turns it off. Needs set_denoise first; one device or a group.

@@ -50,6 +50,8 @@ ABI_SYMBOLS = [
     "srt_group_last_filter_spatial_variance",
     "srt_set_denoise_history_illumination", "srt_group_set_denoise_history_illumination", "srt_last_setup_history_illumination",
     "srt_group_last_setup_history_illumination",
+    "srt_set_denoise_history_clamp", "srt_group_set_denoise_history_clamp", "srt_last_setup_history_clamp",
+    "srt_group_last_setup_history_clamp", "srt_read_denoise_history_bounds",
     "srt_bvh_refit_wide_host", "srt_set_acceleration_refit", "srt_group_set_acceleration_refit", "srt_acceleration_refit_info",
     "srt_last_refit_kernel_ms", "srt_read_bvh_blocks", "srt_bvh_wide_order_host",
     "srt_set_acceleration_deform", "srt_group_set_acceleration_deform", "srt_acceleration_deform_info",
@@ -577,6 +579,12 @@ def _bind(lib):
         lib.srt_group_set_denoise_history_illumination.argtypes = [vp, C.c_int]
         lib.srt_last_setup_history_illumination.argtypes = [vp]
         lib.srt_group_last_setup_history_illumination.argtypes = [vp]
+    if hasattr(lib, "srt_set_denoise_history_clamp"):  # (an older library, SRT_LIB, in an A/B run)
+        lib.srt_set_denoise_history_clamp.argtypes = [vp, C.c_float]
+        lib.srt_group_set_denoise_history_clamp.argtypes = [vp, C.c_float]
+        lib.srt_last_setup_history_clamp.argtypes = [vp]
+        lib.srt_group_last_setup_history_clamp.argtypes = [vp]
+        lib.srt_read_denoise_history_bounds.argtypes = [vp, vp, vp]
     if hasattr(lib, "srt_set_textures"):
         lib.srt_set_textures.argtypes = [vp, vp, sz]
         lib.srt_set_material_textures.argtypes = [vp, vp, sz]
@@ -683,6 +691,17 @@ class _Denoise:
     def last_setup_history_illumination(self):
         """True when the last temporal set-up (a filter's or a clear's) launched an illumination kernel."""
         return bool(self._dn("last_setup_history_illumination"))
+
+    def set_denoise_history_clamp(self, gamma=1.0):
+        """Clamp the reprojected history colour of a pixel into mean +- gamma sigma of the current frame's 7x7 neighbourhood
+        before it is blended in (srt_set_denoise_history_clamp), so that lighting a moved shape left behind (its shadow, its
+        reflection) is corrected within a frame or two. 0 turns it off; 0 < gamma <= 64. Needs temporal reprojection on; clears
+        nothing, keeps the history."""
+        self._check(self._dn("set_denoise_history_clamp", float(gamma)))
+
+    def last_setup_history_clamp(self):
+        """True when the last temporal set-up (a filter's or a clear's) ran the bounds launch and a clamping set-up."""
+        return bool(self._dn("last_setup_history_clamp"))
 
     def reset_denoise_history(self):
         """Drop the temporal history: the next frame is filtered as by the spatial denoiser alone."""
@@ -1033,6 +1052,14 @@ class Tracer(_Denoise):
         """Keep the temporal history across an update_scene that only moves shapes (srt_set_denoise_object_motion). Needs
         temporal reprojection on; every change of the switch drops the history."""
         self._check(self.lib.srt_set_denoise_object_motion(self._h, 1 if enable else 0))
+
+    def read_denoise_history_bounds(self):
+        """The history clamp's two planes of the last bounds launch (srt_read_denoise_history_bounds): dict mu (h, w, 3),
+        weight (h, w) (0: do not clamp), sigma (h, w, 3), taps (h, w) (the counting taps, as floats)."""
+        b0 = np.zeros((self.height, self.width, 4), np.float32)
+        b1 = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self.lib.srt_read_denoise_history_bounds(self._h, _ptr(b0), _ptr(b1)))
+        return {"mu": b0[..., :3], "weight": b0[..., 3], "sigma": b1[..., :3], "taps": b1[..., 3]}
 
     def read_denoise_shape_ids(self):
         """(current, history): (h, w) uint32 shape index of each pixel's first hit (feature sample 0 of the latest dispatch;
