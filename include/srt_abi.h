@@ -819,6 +819,15 @@ int srt_last_trace_textured(const srt_tracer *t, int *textured);
  * for a kernel compiled for the scene's class (sphere / plane scenes of one block group). The class follows
  * the scene and the options of the dispatch; results do not depend on it. */
 int srt_last_trace_class(const srt_tracer *t, int *scene_class);
+/* Which twin of that class the last srt_trace launched: *plane_form = 0 for the class's own kernel (and for the general
+ * kernels), else the scene's plane form, for which the class has an axis twin (DESIGN.md 5 "Axis planes"): 2 bits per plane
+ * slot of the scene's block group in block order (block b, slot i: bits 4b + 2i), 1 / 2 / 3 = the plane's normal is +-e_x /
+ * +-e_y / +-e_z. Results do not depend on it. */
+int srt_last_trace_plane_form(const srt_tracer *t, int *plane_form);
+/* Host-only (no device). The axis code srt_update_scene gives a plane: 1, 2, 3 when the normal has exactly one component
+ * equal to +1 or -1 (x, y, z) and two zeros of either sign and every component of the position is at most 2^100 in
+ * magnitude, else 0. SRT_ERR_INVALID on a NULL pointer. */
+int srt_plane_axis_code_host(const float normal[3], const float position[3], int *code);
 /* Host-only (no device). The integer srt_update_scene puts in place of a material probability p (metallic, specular,
  * transmittance): *threshold = the number of generator outputs r in [0, 2^32) with p > (float)r * 2^-32f, so that the kernel's
  * draw is r < *threshold. 0 for p <= 0 and NaN; below 2^32 for every p <= 1 (p = 1: 2^32 - 128, the 128 largest r convert to
@@ -858,6 +867,16 @@ int srt_selftest_math(srt_tracer *t, uint32_t stride, uint64_t out[16]);
  * out_ref ({x, y, z, seed afterwards} / {x, y, z, 0}); *mismatches = the number of words whose bits differ (must be 0 wherever
  * a NaN component comes with a NaN d, as it does in the kernel). waves <= 65536. */
 int srt_selftest_rare_lanes(srt_tracer *t, int what, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, uint64_t *mismatches);
+
+/* Device self-test of the axis twins' plane tests (tests only; DESIGN.md 5 "Axis planes"), for the benchmark's plane form
+ * (planes y, x | plane z): planes[32] = the two staged plane blocks, {p, 0, n, 0} x 2 each (the fourth slot a filler). Each wave
+ * runs what an EXTEND phase of the twin runs for its planes -- the guard, its vote, then the folded tests or the reference's
+ * on all lanes -- and, beside it, test_planes2 alone. what = 0: lane i reads in[8 * i ..] = {org, dir, tmin} (float bits);
+ * what = 1, as in a camera phase: every lane's origin is cam_org[3] (so the numerators are the same for the whole
+ * wave), the lane reads {-, -, -, dir, tmin}. out_new / out_ref: {tmin, best} per lane (best counts from 0; -1: none); fast[w] = 1 when wave w passed the
+ * guard; *mismatches = the words of out_new that differ from out_ref (must be 0). waves <= 65536. */
+int srt_selftest_plane_forms(srt_tracer *t, int what, const float planes[32], const float cam_org[3], const uint32_t *in, uint32_t waves,
+                             uint32_t *out_new, uint32_t *out_ref, uint32_t *fast, uint64_t *mismatches);
 
 /* Library / build identification, e.g. "srt-hip gfx950 parity fp-contract=off". */
 const char *srt_version(void);

@@ -19,6 +19,13 @@ ROCM = Path("/opt/rocm")
 RENAMED = {"_Z17srt_reduce_kernel12ReduceParams": "_Z17srt_reduce_kernelILb0EEv12ReduceParams"}  # old name -> new name
 
 
+def renamed(name):
+    """an old tree's function under the name the new tree gives it: the table above, and a scene-class kernel from before the
+    plane form was a template parameter is the class's own kernel, plane form 0"""
+    name = RENAMED.get(name, name)
+    return re.sub(r"^(_Z22srt_trace_scene_kernelILj\d+ELb[01])(EEv11TraceParams)$", r"\1ELj0\2", name)
+
+
 def build_module():
     sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
     import srt_pkg
@@ -71,7 +78,7 @@ def main():
         b_dir.mkdir()
         for src in B.SOURCES:  # (a source only one tree has: its functions are reported as "only in")
             if (Path(old_tree) / "simple-raytracer_amd/csrc" / src).exists():
-                a.update({(src, RENAMED.get(k, k)): v for k, v in functions(build(B, old_tree, src, a_dir)).items()})
+                a.update({(src, renamed(k)): v for k, v in functions(build(B, old_tree, src, a_dir)).items()})
             if (Path(new_tree) / "simple-raytracer_amd/csrc" / src).exists():
                 b.update({(src, k): v for k, v in functions(build(B, new_tree, src, b_dir)).items()})
     names = sorted(a.keys() | b.keys())

@@ -200,6 +200,82 @@ __device__ __forceinline__ void cam_records_of_block(float4 *__restrict__ blk, f
 		}
 	}
 }
+// ---- AXIS PLANES of a scene class's axis twin (device_types.h SRT_SCENE_AXIS_LIST; DESIGN.md 5 "Axis planes") ------------------------
+// A plane whose normal is s e_k (s = +-1, the other two components +-0) and whose position is tame (scene_prep.cpp
+// srt_plane_axis_code). With dm_dot3 = fma(az, bz, fma(ay, by, ax * bx)), a product with a zero component is a zero whenever the
+// other factor is finite, and adding a zero to a number that is not one returns that number, so
+//   dot3(n, dir) = s dir[k]              when the other two components of dir are finite and dir[k] != 0,
+//   dot3(n, p - org) = s (p[k] - org[k]) when the other two differences are finite and p[k] - org[k] != 0,
+// and (s a) / (s b) = a / b bit for bit: t = (p[k] - org[k]) / dir[k]. Where a side is +-0 the two forms may differ in the zero's
+// sign (which reaches org + dir * tmin through t = +-0, a hit), and where an unused component is not finite the reference has a NaN
+// the folded form does not. ONE test per EXTEND phase (axis_operands_ok, voted over the lanes that hold a ray) excludes all of it
+// and puts the quotients inside div_core's box, where rcp_refined + div_core IS the division (device_math.h; srt_selftest_math
+// out[8], out[9]):
+//   the planes' numerators a = p[k] - org[k]:  2^-60 <= |a|, sum |a| <= 2^50   (not zero, finite; a NaN fails the sum's compare)
+//   the direction's three components b:        2^-40 <= |b|, sum |b| <= 2^40
+// The numerators between them hold every component of org (srt_axes_buildable: the planes use all three axes), and a plane's
+// position is at most 2^100 in every component (the host's predicate), so every p[j] - org[j] of the reference is finite too. A
+// wave with a lane outside runs today's test_planes2 / test_planes2_cam for that phase. min3 skips a NaN; the sums do not.
+#ifndef SRT_AXIS_SHORT_DIV
+#define SRT_AXIS_SHORT_DIV 1 // (0: the compiler's division behind the same guard -- the "folding alone" build of profiles/r21_axis_planes_ab.txt)
+#endif
+template <int C>
+__device__ __forceinline__ float f3_at(f3 v) { return C == 0 ? v.x : C == 1 ? v.y : v.z; }
+// the numerators of block K's planes (blk: its 16 floats) as seen from org, a[i] for slot i
+template <uint32_t K, uint32_t AX>
+__device__ __forceinline__ void axis_numerators(const float *__restrict__ blk, f3 org, float *__restrict__ a) {
+	if constexpr ((K & 3u) == SRT_SHAPE_PLANE + 1u) {
+		constexpr int C0 = (int)(AX & 3u) - 1, C1 = (int)((AX >> 2) & 3u) - 1;
+		a[0] = blk[C0 < 0 ? 0 : C0] - f3_at<C0>(org);
+		if constexpr (((K >> 2) & 7u) > 1u) a[1] = blk[8 + (C1 < 0 ? 0 : C1)] - f3_at<C1>(org);
+	}
+}
+template <int N>
+__device__ __forceinline__ bool axis_operands_ok(const float *__restrict__ a, f3 dir) {
+	float mn = dm_fabs(a[0]), sm = dm_fabs(a[0]);
+#pragma unroll
+	for (int i = 1; i < N; i++) mn = __builtin_fminf(mn, dm_fabs(a[i])), sm = sm + dm_fabs(a[i]);
+	const float bx = dm_fabs(dir.x), by = dm_fabs(dir.y), bz = dm_fabs(dir.z);
+	const float mnb = __builtin_fminf(__builtin_fminf(bx, by), bz), smb = (bx + by) + bz;
+	return mn >= 0x1p-60f && sm <= 0x1p50f && mnb >= 0x1p-40f && smb <= 0x1p40f;
+}
+// a / b for operands that passed axis_operands_ok
+__device__ __forceinline__ float axis_div(float a, float b) {
+#if SRT_AXIS_SHORT_DIV
+	return div_core(a, b, rcp_refined(b));
+#else
+	return a / b;
+#endif
+}
+// test_planes2 / test_planes2_cam for a wave that passed: a[i] = slot i's numerator (axis_numerators; in a camera phase the
+// prologue's, from the staged block)
+template <uint32_t AX>
+__device__ __forceinline__ void test_planes2_axis(const float *__restrict__ a, uint32_t count, f3 dir, int idx0, float &tmin, int &best) {
+#pragma unroll
+	for (int i = 0; i < 2; i++) {
+		if (i == 1 && count < 2u) break;
+		const float b = i == 0 ? f3_at<(int)(AX & 3u) - 1>(dir) : f3_at<(int)((AX >> 2) & 3u) - 1>(dir);
+		const float t = axis_div(a[i], b);
+		const bool hit = !(t < 0.0f);
+		if (hit && t < tmin) {
+			tmin = t;
+			best = idx0 + i;
+		}
+	}
+}
+// The prologue's part for the camera phases: the folded numerator of block K's planes seen from the camera's origin, in the
+// unused fourth dword of the plane's normal in the staged block (num itself stays where the reference form reads it).
+template <uint32_t K, uint32_t AX>
+__device__ __forceinline__ void cam_axis_numerators(float4 *__restrict__ blk, f3 org, int lane) {
+	if constexpr ((K & 3u) == SRT_SHAPE_PLANE + 1u) {
+		if (lane < 2) {
+			const float4 pq = blk[2 * lane];
+			const int c = (int)((AX >> (2 * lane)) & 3u) - 1;
+			const float pk = c == 0 ? pq.x : c == 1 ? pq.y : pq.z, ok = c == 0 ? org.x : c == 1 ? org.y : org.z;
+			reinterpret_cast<float *>(blk + 2 * lane + 1)[3] = pk - ok;
+		}
+	}
+}
 // render.cl:279-290 with tmax = the lane's current closest t
 __device__ __forceinline__ bool test_aabb(float lx, float ly, float lz, float hx, float hy, float hz, f3 org, f3 inv, float tmax) {
 	float t0 = 0.0f, t1 = tmax;

@@ -131,6 +131,37 @@ enum { SRT_CTR_RAYS = 0, SRT_CTR_SKY, SRT_CTR_TRI, SRT_CTR_TRI_PASS_U, SRT_CTR_N
 	X(3, SRT_GC_SSS, true)      \
 	X(4, SRT_GC_PPP, true)
 #define SRT_SCENE_CLASS_GENERAL 0
+/* Axis planes (DESIGN.md 5 "Axis planes"). A scene's PLANE FORM is a pattern of 2 bits per plane slot of its one block group, in
+ * block order (block b, slot i: bits 4b + 2i): 0 = a general plane, a filler or no plane at all; 1, 2, 3 = the normal is +-e_x,
+ * +-e_y, +-e_z exactly and the position is tame (scene_prep.cpp srt_plane_axis_code). A class has one more kernel -- its axis
+ * twin -- per pattern listed here: X(class number, header, NO_SPEC, pattern). The class numbers are those of
+ * SRT_SCENE_CLASS_LIST; the launcher starts the twin when the scene's pattern is the listed one, else the class's own kernel.
+ * Listed: the benchmark's layout, planes y, x | plane z | four spheres. */
+#define SRT_AXES_PPS_YXZ (2u | (1u << 2) | (3u << 4))
+#define SRT_SCENE_AXIS_LIST(X)               \
+	X(1, SRT_GC_PPS, true, SRT_AXES_PPS_YXZ) \
+	X(2, SRT_GC_PPS, false, SRT_AXES_PPS_YXZ)
+/* A pattern an axis twin can be built for: every plane of the header `code` has an axis, and between them the planes use all
+ * three axes -- the twin's guard looks at the planes' numerators and at the ray direction's three components, and that covers
+ * every component of the origin only then (device_intersect.h "AXIS PLANES"). */
+static constexpr inline bool srt_axes_buildable(uint32_t code, uint32_t axes) {
+	uint32_t used = 0, planes = 0;
+	for (uint32_t b = 0; b < 3; b++) {
+		const uint32_t k = (code >> (8 * b)) & 255u, n = (k >> 2) & 7u;
+		for (uint32_t i = 0; i < 2; i++) {
+			const uint32_t a = (axes >> (4 * b + 2 * i)) & 3u;
+			const bool plane = (k & 3u) == SRT_SHAPE_PLANE + 1u && i < n;
+			if (plane != (a != 0u)) return false;
+			if (plane) used |= 1u << a, planes++;
+		}
+	}
+	return planes != 0u && used == 14u && (axes >> 12) == 0u;
+}
+/* TraceParams.scene_class carries both to the launcher: the class in its low byte, the plane form the launch runs above it
+ * (0 = the class's own kernel). Host side only. */
+static constexpr inline int32_t srt_kernel_key(int scene_class, uint32_t plane_form) { return (int32_t)((uint32_t)scene_class | (plane_form << 8)); }
+static constexpr inline int srt_key_class(int32_t key) { return (int)((uint32_t)key & 255u); }
+static constexpr inline uint32_t srt_key_plane_form(int32_t key) { return (uint32_t)key >> 8; }
 /* A class kernel keeps, per sphere of its group, what a camera ray's test makes from the sphere and the camera's origin alone
  * (device_intersect.h "CAMERA PHASES"): one float4 {L, c} per sphere slot of every sphere block of the header `code`, behind the hit
  * queue in the wave's dynamic LDS. The launcher adds the bytes; 64 for the benchmark's layout, which stays inside the LDS
@@ -159,7 +190,7 @@ struct TraceParams {
 	int32_t num_runs;
 	int32_t num_materials;
 	uint32_t lds_bytes; /* dynamic LDS given to the launch; 0 = winners/materials stay in global memory */
-	int32_t scene_class; /* SRT_SCENE_CLASS_LIST below: which trace kernel the launcher starts; 0 = the general one (never read on the device) */
+	int32_t scene_class; /* srt_kernel_key(class of SRT_SCENE_CLASS_LIST, plane form): which trace kernel the launcher starts; 0 = the general one (never read on the device) */
 	const srt_shape *shapes;
 	const srt_triangle *triangles;
 	const srt_material *materials;
@@ -404,5 +435,7 @@ int srt_launch_build_median(const BuildParams &p, uint32_t num_models, uint32_t 
 void srt_launch_resolve(const ResolveParams &p, void *stream);
 void srt_launch_selftest(unsigned long long *out16, uint32_t stride, void *stream);
 void srt_launch_selftest_rare(int what, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, unsigned long long *mismatches, void *stream);
+void srt_launch_selftest_plane_forms(int what, const float *planes32, const float *cam_org3, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref,
+                                     uint32_t *fast, unsigned long long *mismatches, void *stream);
 
 #endif

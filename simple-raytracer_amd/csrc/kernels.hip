@@ -222,16 +222,18 @@ constexpr uint32_t hq_fields(bool has_models) { return has_models ? 17u : 16u; }
 // a scene outside every listed class runs the general kernel.
 struct GeneralScene {
 	static constexpr bool FAST = false, NO_SPEC = false;
-	static constexpr uint32_t CODE = 0;
+	static constexpr uint32_t CODE = 0, AXES = 0;
 };
 // A sphere / plane scene of ONE group whose header is CODE (device_types.h BlockGroup: per block, type and shape count), staged
 // in LDS, shapes 0 .. N - 1 in the blocks in array order, every shape with a material, the materials' probabilities as
 // thresholds (unit_materials), num_bounces > 0, show_normals off. NO_SPEC: no material is specular and every colour is plain
-// (SRT_MF_NO_SPECULAR | SRT_MF_PLAIN_COLORS).
-template <uint32_t CODE_, bool NO_SPEC_>
+// (SRT_MF_NO_SPECULAR | SRT_MF_PLAIN_COLORS). AXES: the scene's plane form (device_types.h "Axis planes"); 0 = the class's own
+// kernel, whose planes are general ones.
+template <uint32_t CODE_, bool NO_SPEC_, uint32_t AXES_ = 0>
 struct OneGroupScene {
 	static constexpr bool FAST = true, NO_SPEC = NO_SPEC_;
-	static constexpr uint32_t CODE = CODE_;
+	static constexpr uint32_t CODE = CODE_, AXES = AXES_;
+	static_assert(AXES_ == 0 || srt_axes_buildable(CODE_, AXES_), "an axis twin needs an axis for every plane, and all three axes in use");
 };
 // one block of a OneGroupScene: test_block of the general kernel with the block's byte of the header a constant
 template <uint32_t K>
@@ -254,6 +256,39 @@ __device__ __forceinline__ void test_block_of_class_cam(const float4 *__restrict
 	}
 }
 
+// A block of an axis twin (device_intersect.h "AXIS PLANES"): blk = the staged block, a = its planes' numerators, pass = the
+// phase's guard held for every ray of the wave (wave-uniform). A plane block then runs the folded tests, else today's; a sphere
+// block is what it is in the class's own kernel.
+__device__ __forceinline__ Blk16 ld_blk16_lds(const float4 *__restrict__ blk) {
+	Blk16 b;
+	const float4 q0 = blk[0], q1 = blk[1], q2 = blk[2], q3 = blk[3];
+	b.v[0] = q0.x, b.v[1] = q0.y, b.v[2] = q0.z, b.v[3] = q0.w, b.v[4] = q1.x, b.v[5] = q1.y, b.v[6] = q1.z, b.v[7] = q1.w;
+	b.v[8] = q2.x, b.v[9] = q2.y, b.v[10] = q2.z, b.v[11] = q2.w, b.v[12] = q3.x, b.v[13] = q3.y, b.v[14] = q3.z, b.v[15] = q3.w;
+	return b;
+}
+template <uint32_t K, uint32_t AX>
+__device__ __forceinline__ void test_block_of_class_axis(const float4 *__restrict__ blk, bool pass, const float *__restrict__ a, int base, f3 org, f3 dir, float &tmin, int &best) {
+	if constexpr ((K & 3u) == SRT_SHAPE_PLANE + 1u) {
+		if (__builtin_expect(pass, 1)) test_planes2_axis<AX>(a, (K >> 2) & 7u, dir, base, tmin, best);
+		else test_planes2(ld_blk16_lds(blk), (K >> 2) & 7u, org, dir, base, tmin, best); // @rare
+	} else {
+		test_block_of_class<K>(ld_blk16_lds(blk), base, org, dir, tmin, best);
+	}
+}
+template <uint32_t K, uint32_t AX>
+__device__ __forceinline__ void test_block_of_class_axis_cam(const float4 *__restrict__ blk, const float4 *__restrict__ cam, bool pass, int base, f3 dir, unsigned long long actm, float &tmin, int &best) {
+	if constexpr ((K & 3u) == SRT_SHAPE_PLANE + 1u) {
+		if (__builtin_expect(pass, 1)) {
+			const float a[2] = {reinterpret_cast<const float *>(blk + 1)[3], reinterpret_cast<const float *>(blk + 3)[3]}; // the prologue's (cam_axis_numerators)
+			test_planes2_axis<AX>(a, (K >> 2) & 7u, dir, base, tmin, best);
+		} else {
+			test_planes2_cam(blk, (K >> 2) & 7u, dir, base, tmin, best); // @rare
+		}
+	} else {
+		test_block_of_class_cam<K>(blk, cam, base, dir, actm, tmin, best);
+	}
+}
+
 template <bool COUNT_TRIS, bool USE_LDS, bool HAS_MODELS, bool USE_BVH>
 __global__ __launch_bounds__(64, USE_BVH ? SRT_TRACE_WAVES_PER_SIMD_BVH : HAS_MODELS ? SRT_TRACE_WAVES_PER_SIMD_MODELS : SRT_TRACE_WAVES_PER_SIMD) void srt_trace_kernel(const SRT_TRACE_PARAMS p) {
 	using SC = GeneralScene;
@@ -267,10 +302,10 @@ __global__ __launch_bounds__(64, USE_BVH ? SRT_TRACE_WAVES_PER_SIMD_BVH : HAS_MO
 #define SRT_SCENE_CLASSES 1
 // (six waves per SIMD asked of the register allocator: at most 80 VGPRs, the general sphere kernel's allocation, so that the
 // 21 waves per CU the LDS allows stay resident -- with five, the specular class took 81)
-template <uint32_t CODE, bool NO_SPEC>
+template <uint32_t CODE, bool NO_SPEC, uint32_t PLANE_FORM>
 __global__ __launch_bounds__(64, 6) void srt_trace_scene_kernel(const TraceParams p) {
 	constexpr bool COUNT_TRIS = false, USE_LDS = true, HAS_MODELS = false, USE_BVH = false;
-	using SC = OneGroupScene<CODE, NO_SPEC>;
+	using SC = OneGroupScene<CODE, NO_SPEC, PLANE_FORM>;
 #include "trace_body.inc"
 }
 #else
@@ -348,11 +383,15 @@ size_t scene_lds_bytes(const TraceParams &p) {
 // the kernel of a launch: its scene class's, or the general instantiation for the scene's kind
 TraceKernel pick_trace_kernel(const SRT_TRACE_PARAMS &p, bool use_lds, bool count_triangles) {
 #if SRT_SCENE_CLASSES
-	switch (p.scene_class) {
+	switch (p.scene_class) { // (srt_kernel_key: a class's own kernel has plane form 0)
 #define SRT_SCENE_CLASS_CASE(number, code, no_spec) \
-	case number: return srt_trace_scene_kernel<code, no_spec>;
+	case number: return srt_trace_scene_kernel<code, no_spec, 0u>;
 		SRT_SCENE_CLASS_LIST(SRT_SCENE_CLASS_CASE)
 #undef SRT_SCENE_CLASS_CASE
+#define SRT_SCENE_AXIS_CASE(number, code, no_spec, axes) \
+	case srt_kernel_key(number, axes): return srt_trace_scene_kernel<code, no_spec, axes>;
+		SRT_SCENE_AXIS_LIST(SRT_SCENE_AXIS_CASE)
+#undef SRT_SCENE_AXIS_CASE
 	default: break;
 	}
 #endif
@@ -362,7 +401,7 @@ TraceKernel pick_trace_kernel(const SRT_TRACE_PARAMS &p, bool use_lds, bool coun
 size_t trace_lds_bytes(const SRT_TRACE_PARAMS &p, size_t scene_lds) {
 	size_t need = scene_lds + (size_t)srt_trace_lds_floats(p.num_models > 0, p.use_bvh) * sizeof(float);
 #if SRT_SCENE_CLASSES
-	switch (p.scene_class) {
+	switch (srt_key_class(p.scene_class)) {
 #define SRT_SCENE_CLASS_CASE(number, code, no_spec) \
 	case number: need += srt_class_cam_lds_bytes(code); break;
 		SRT_SCENE_CLASS_LIST(SRT_SCENE_CLASS_CASE)

@@ -23,6 +23,24 @@ uint64_t bernoulli_threshold(float pr) {
 	return lo;
 }
 
+// Axis planes (device_types.h "Axis planes"): 1, 2, 3 for a plane whose normal is +-e_x, +-e_y, +-e_z -- exactly one component
+// equal to +1 or -1, the other two zeros of either sign -- and whose position is at most 2^100 in every component; 0 for every
+// other plane (any other length, a denormal or a NaN anywhere). The position's clause is the twin's, not the identity's: its
+// guard sees, of a plane's position, only the component on the axis; a position that is not finite in another component puts
+// 0 * NaN into the reference's numerator, and one near FLT_MAX can overflow the difference to the origin. With |p| <= 2^100 and
+// the origin within 2^50 of every axis's plane (the guard; the planes of a buildable pattern use all three axes) no difference
+// does. THE one copy: srt_update_scene and srt_plane_axis_code_host both call it.
+int srt_plane_axis_code(const float n[3], const float p[3]) {
+	int axis = 0;
+	for (int k = 0; k < 3; k++) {
+		if (!(fabsf(p[k]) <= 0x1p100f)) return 0; // (a NaN fails)
+		if (n[k] == 0.0f) continue;               // +0 or -0
+		if (fabsf(n[k]) != 1.0f || axis != 0) return 0;
+		axis = k + 1;
+	}
+	return axis;
+}
+
 // host pass; `cache` is made when a BVH scene first needs it and emptied by an array-scan scene; an error return leaves its text
 // in `err` and every cached hierarchy in place
 int prepare_scene(const AccelPolicy &policy, BvhCache *&cache, int scan_suspend_min, std::string &err, ScenePrep &sp, const srt_shape *shapes, size_t n_shapes,
@@ -303,6 +321,15 @@ int prepare_scene(const AccelPolicy &policy, BvhCache *&cache, int scan_suspend_
 		for (size_t b = 0; b < runs.size(); b++) packed = packed && runs[b].first_shape == next, next += runs[b].count;
 		if (packed && next == n_shapes) sp.one_group_code = groups[0].code;
 	}
+	// its plane form: 2 bits per plane slot, in block order (fillers and other shapes' slots stay 0)
+	sp.plane_axes = 0;
+	if (sp.one_group_code != 0)
+		for (size_t b = 0; b < runs.size(); b++)
+			for (uint32_t i = 0; runs[b].type == SRT_SHAPE_PLANE && i < runs[b].count; i++) {
+				const srt_plane &pl = shapes[runs[b].first_shape + i].shape.plane;
+				const float n[3] = {pl.normal.x, pl.normal.y, pl.normal.z}, q[3] = {pl.position.x, pl.position.y, pl.position.z};
+				sp.plane_axes |= (uint32_t)srt_plane_axis_code(n, q) << (4 * b + 2 * i);
+			}
 	if (!stale_plan.empty()) { // the refit schedule of the scene: level h of every stale model, then level h + 1, ...
 		size_t top = 0;
 		for (const auto &st : stale_plan) top = std::max(top, st.first->wide.level_off.size());
@@ -374,6 +401,12 @@ int prepare_scene(const AccelPolicy &policy, BvhCache *&cache, int scan_suspend_
 	sp.all_materials_ok = true;
 	for (size_t i = 0; i < n_shapes; i++)
 		if (shapes[i].material < 0) sp.all_materials_ok = false;
+	return SRT_OK;
+}
+
+extern "C" int srt_plane_axis_code_host(const float normal[3], const float position[3], int *code_out) {
+	if (!normal || !position || !code_out) return SRT_ERR_INVALID;
+	*code_out = srt_plane_axis_code(normal, position);
 	return SRT_OK;
 }
 

@@ -23,6 +23,7 @@ struct ScenePrep {
 	bool use_bvh = false, unit_materials = false, all_materials_ok = true;
 	int material_flags = 0;
 	uint32_t one_group_code = 0; // srt_tracer::one_group_code
+	uint32_t plane_axes = 0;     // srt_tracer::plane_axes: the one group's plane form (device_types.h "Axis planes")
 	uint64_t bvh_info[7] = {0, 0, 0, 0, 0, 0, 0};
 	// SRT_REFIT_DEVICE: the models whose blocks above come from a stale hierarchy (bvh_host.h) and are refitted on the device
 	// behind the upload (bvh_refit.hip), their empty extents, their inner blocks as absolute indices level by level -- level h
@@ -79,5 +80,6 @@ int prepare_scene(const AccelPolicy &policy, BvhCache *&cache, int scan_suspend_
                   const srt_triangle *triangles, size_t n_triangles, const srt_material *materials, size_t n_materials, const srt_scene_data *scene);
 
 uint64_t bernoulli_threshold(float pr);
+int srt_plane_axis_code(const float normal[3], const float position[3]);
 
 #endif

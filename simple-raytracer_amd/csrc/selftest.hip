@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_math.h"
+#include "device_intersect.h" // test_planes2 and the axis forms
 #include "device_shading.h" // powi_uniform
 
 // ---------------------------------------------------------------------------------
@@ -161,4 +162,54 @@ __global__ __launch_bounds__(64) void srt_selftest_rare_kernel(int what, const u
 void srt_launch_selftest_rare(int what, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, unsigned long long *mismatches, void *stream) {
 	if (waves == 0) return;
 	hipLaunchKernelGGL(srt_selftest_rare_kernel, dim3(waves), dim3(64), 0, (hipStream_t)stream, what, in, out_new, out_ref, mismatches);
+}
+
+// The axis twins' plane tests (device_intersect.h "AXIS PLANES") as an EXTEND phase of the benchmark layout's twin runs them
+// (trace_body.inc: planes y, x | plane z), WAVE BY WAVE beside test_planes2 alone: numerators, guard, one vote over all 64
+// lanes, then the folded tests or the reference's. what 0: in {org, dir, tmin}; what 1 (as in a camera phase): the origin is
+// pl.cam_org for every lane, so the numerators are the wave's own; in {-, -, -, dir, tmin}. out {tmin, best}.
+struct PlaneFormsArgs {
+	float blk[32];    // the two staged plane blocks {p, 0, n, 0} x 2
+	float cam_org[3];
+};
+__global__ __launch_bounds__(64) void srt_selftest_plane_forms_kernel(int what, const PlaneFormsArgs pl, const uint32_t *__restrict__ in, uint32_t *__restrict__ out_new,
+                                                                      uint32_t *__restrict__ out_ref, uint32_t *__restrict__ fast, unsigned long long *mismatches) {
+	constexpr uint32_t K0 = SRT_BLK_CODE(SRT_SHAPE_PLANE, 2), K1 = SRT_BLK_CODE(SRT_SHAPE_PLANE, 1);
+	constexpr uint32_t A0 = SRT_AXES_PPS_YXZ & 15u, A1 = (SRT_AXES_PPS_YXZ >> 4) & 15u;
+	const size_t lane = (size_t)blockIdx.x * 64u + threadIdx.x;
+	const uint32_t *__restrict__ w = in + lane * 8u;
+	const f3 org = what == 1 ? mk(pl.cam_org[0], pl.cam_org[1], pl.cam_org[2]) : mk(dm_u2f(w[0]), dm_u2f(w[1]), dm_u2f(w[2]));
+	const f3 dir = mk(dm_u2f(w[3]), dm_u2f(w[4]), dm_u2f(w[5]));
+	Blk16 b0, b1;
+#pragma unroll
+	for (int i = 0; i < 16; i++) b0.v[i] = pl.blk[i], b1.v[i] = pl.blk[16 + i];
+	float tmin_r = dm_u2f(w[6]), tmin_n = tmin_r;
+	int best_r = -1, best_n = -1;
+	test_planes2(b0, 2u, org, dir, 0, tmin_r, best_r);
+	test_planes2(b1, 1u, org, dir, 2, tmin_r, best_r);
+	float an[3];
+	axis_numerators<K0, A0>(b0.v, org, an);
+	axis_numerators<K1, A1>(b1.v, org, an + 2);
+	const bool pass = !any64(!axis_operands_ok<3>(an, dir));
+	if (pass) {
+		test_planes2_axis<A0>(an, 2u, dir, 0, tmin_n, best_n);
+		test_planes2_axis<A1>(an + 2, 1u, dir, 2, tmin_n, best_n);
+	} else {
+		test_planes2(b0, 2u, org, dir, 0, tmin_n, best_n);
+		test_planes2(b1, 1u, org, dir, 2, tmin_n, best_n);
+	}
+	out_new[lane * 2u] = dm_f2u(tmin_n), out_new[lane * 2u + 1u] = (uint32_t)best_n;
+	out_ref[lane * 2u] = dm_f2u(tmin_r), out_ref[lane * 2u + 1u] = (uint32_t)best_r;
+	if (threadIdx.x == 0) fast[blockIdx.x] = pass ? 1u : 0u;
+	const unsigned long long bad = (dm_f2u(tmin_n) != dm_f2u(tmin_r) ? 1u : 0u) + (best_n != best_r ? 1u : 0u);
+	if (bad) atomicAdd(mismatches, bad);
+}
+
+void srt_launch_selftest_plane_forms(int what, const float *planes32, const float *cam_org3, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref,
+                                     uint32_t *fast, unsigned long long *mismatches, void *stream) {
+	if (waves == 0) return;
+	PlaneFormsArgs pl;
+	for (int i = 0; i < 32; i++) pl.blk[i] = planes32[i];
+	for (int i = 0; i < 3; i++) pl.cam_org[i] = cam_org3[i];
+	hipLaunchKernelGGL(srt_selftest_plane_forms_kernel, dim3(waves), dim3(64), 0, (hipStream_t)stream, what, pl, in, out_new, out_ref, fast, mismatches);
 }

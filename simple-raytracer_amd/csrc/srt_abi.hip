@@ -364,6 +364,7 @@ static int upload_scene_end(srt_tracer *t, const ScenePrep &sp, size_t n_shapes,
 	t->unit_materials = sp.unit_materials;
 	t->material_flags = sp.material_flags;
 	t->one_group_code = sp.one_group_code;
+	t->plane_axes = sp.plane_axes;
 	t->num_runs = (int)sp.groups.size();
 	t->num_materials = n_materials;
 	t->scene_set = true;
@@ -449,9 +450,25 @@ static int scene_class(const srt_tracer *t, const srt_render_data *options, bool
 	return SRT_SCENE_CLASS_GENERAL;
 }
 
+// Which twin of a class a launch runs: the scene's plane form when the class has an axis twin for exactly that pattern
+// (device_types.h SRT_SCENE_AXIS_LIST), else 0, the class's own kernel. The class is decided first and by scene_class() alone.
+static uint32_t plane_form_of(const srt_tracer *t, int scene_class) {
+#define SRT_SCENE_AXIS_MATCH(number, code, class_no_spec, axes) \
+	if (scene_class == number && t->plane_axes == (axes)) return axes;
+	SRT_SCENE_AXIS_LIST(SRT_SCENE_AXIS_MATCH)
+#undef SRT_SCENE_AXIS_MATCH
+	return 0u;
+}
+
 int srt_last_trace_class(const srt_tracer *t, int *scene_class_out) {
 	if (!t || !scene_class_out) return SRT_ERR_INVALID;
 	*scene_class_out = t->last_trace_class;
+	return SRT_OK;
+}
+
+int srt_last_trace_plane_form(const srt_tracer *t, int *plane_form_out) {
+	if (!t || !plane_form_out) return SRT_ERR_INVALID;
+	*plane_form_out = (int)t->last_trace_plane_form;
 	return SRT_OK;
 }
 
@@ -521,7 +538,10 @@ static TraceParams trace_params_of(const srt_tracer *t, const srt_render_data *o
 	p.all_materials_ok = t->scene_set && t->all_materials_ok ? 1 : 0;
 	p.unit_materials = t->scene_set && t->unit_materials ? 1 : 0;
 	p.material_flags = t->scene_set ? t->material_flags : 0;
-	p.scene_class = scene_class(t, options, textured);
+	{
+		const int sc = scene_class(t, options, textured);
+		p.scene_class = srt_kernel_key(sc, plane_form_of(t, sc));
+	}
 	p.f_sky_w = (float)t->sky_w;
 	p.f_sky_h = (float)t->sky_h;
 	p.sun_focus_int = dm_pow_small_int(p.sd.sun_focus);
@@ -760,7 +780,8 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 	d.ns = options->num_samples;
 	d.fused_argb = fused_argb;
 	TraceParams p = trace_params_of(t, options, d.textured);
-	t->last_trace_class = p.scene_class;
+	t->last_trace_class = srt_key_class(p.scene_class);
+	t->last_trace_plane_form = srt_key_plane_form(p.scene_class);
 	if (const int rc = reserve_radiance(t, d)) return rc;
 	d.slots = wave_slots(t, p, d.textured);
 	if (const int rc = reserve_scan_stacks(t, d)) return rc;
@@ -1059,8 +1080,38 @@ int srt_selftest_rare_lanes(srt_tracer *t, int what, const uint32_t *in, uint32_
 	return SRT_OK;
 }
 
+int srt_selftest_plane_forms(srt_tracer *t, int what, const float planes[32], const float cam_org[3], const uint32_t *in, uint32_t waves, uint32_t *out_new,
+                             uint32_t *out_ref, uint32_t *fast, uint64_t *mismatches) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!planes || !cam_org || !in || !out_new || !out_ref || !fast || !mismatches || what < 0 || what > 1 || waves == 0 || waves > 65536u)
+		return fail(t, SRT_ERR_INVALID, "srt_selftest_plane_forms: bad arguments");
+	SRT_HIP(t, hipSetDevice(t->device));
+	const size_t lanes = (size_t)waves * 64u, in_bytes = lanes * 8u * sizeof(uint32_t), out_bytes = lanes * 2u * sizeof(uint32_t), fast_bytes = (size_t)waves * sizeof(uint32_t);
+	char *d = nullptr; // [in | out_new | out_ref | count | fast]
+	SRT_HIP(t, hipMalloc(reinterpret_cast<void **>(&d), in_bytes + 2 * out_bytes + sizeof(unsigned long long) + fast_bytes));
+	uint32_t *d_in = reinterpret_cast<uint32_t *>(d), *d_new = reinterpret_cast<uint32_t *>(d + in_bytes), *d_ref = reinterpret_cast<uint32_t *>(d + in_bytes + out_bytes);
+	unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(d + in_bytes + 2 * out_bytes), h_bad = 0;
+	uint32_t *d_fast = reinterpret_cast<uint32_t *>(d + in_bytes + 2 * out_bytes + sizeof(unsigned long long));
+	hipError_t e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, t->stream);
+	if (e == hipSuccess) e = hipMemsetAsync(d_new, 0, 2 * out_bytes + sizeof(unsigned long long) + fast_bytes, t->stream);
+	if (e == hipSuccess) {
+		srt_launch_selftest_plane_forms(what, planes, cam_org, d_in, waves, d_new, d_ref, d_fast, d_bad, t->stream);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(out_new, d_new, out_bytes, hipMemcpyDeviceToHost, t->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(out_ref, d_ref, out_bytes, hipMemcpyDeviceToHost, t->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(fast, d_fast, fast_bytes, hipMemcpyDeviceToHost, t->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, d_bad, sizeof h_bad, hipMemcpyDeviceToHost, t->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+	(void)hipFree(d);
+	if (e != hipSuccess) return fail(t, SRT_ERR_HIP, std::string("srt_selftest_plane_forms: ") + hipGetErrorString(e));
+	*mismatches = h_bad;
+	return SRT_OK;
+}
+
 /* diagnostics: sums of the eight per-wave counter slots since the last reset (slot 5 = the scene-class kernels' EXTEND phases of
- * fresh camera rays only << 36 | the rays in those phases, 6 = wave iterations, 7 = SHADE phases) */
+ * fresh camera rays only << 36 | the rays in those phases, 6 = wave iterations, 7 = SHADE phases; out[10], out[11] = an axis
+ * twin's EXTEND phases and those among them that failed its guard, in the slots the -DSRT_PHASE_CLOCK builds keep clocks in) */
 int srt_debug_counters(srt_tracer *t, uint64_t out[18]) {
 	if (!t || !out) return SRT_ERR_INVALID;
 	SRT_HIP(t, hipSetDevice(t->device));

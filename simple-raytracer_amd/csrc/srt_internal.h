@@ -189,6 +189,7 @@ struct srt_tracer {
 	bool unit_materials = false;   // the device material table holds bernoulli() thresholds (srt_update_scene)
 	int material_flags = 0;        // SRT_MF_* (device_types.h)
 	uint32_t one_group_code = 0;   // the header of a sphere / plane scene that is ONE block group over shapes 0 .. n - 1, else 0 (scene classes)
+	uint32_t plane_axes = 0;       // that group's plane form: 2 bits per plane slot (device_types.h "Axis planes")
 	uint64_t scan_tris = 0; // array scan: triangles of the models a ray can be made to scan (all of them), for the launch-length bound
 	bool scene_set = false;
 	bool count_tris = false;
@@ -274,6 +275,7 @@ struct srt_tracer {
 	bool tex_active = false;         // a material of the current scene has a texture bound, or tex_tm_active: dispatches launch the textured kernels
 	bool last_trace_textured = false; // srt_last_trace_textured
 	int last_trace_class = 0;         // srt_last_trace_class
+	uint32_t last_trace_plane_form = 0; // srt_last_trace_plane_form
 	hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;
 	bool have_trace_ev = false, have_resolve_ev = false, have_kernel_ev = false;
 	std::string err;

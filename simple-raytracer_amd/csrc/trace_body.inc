@@ -10,6 +10,8 @@
 	// materials, [2*N] winner records, [12] shape blocks, [4*n_materials] materials: every address but a material's is a constant
 	constexpr uint32_t FK0 = SC::CODE & 255u, FK1 = (SC::CODE >> 8) & 255u, FK2 = (SC::CODE >> 16) & 255u;
 	constexpr int FN0 = (int)((FK0 >> 2) & 7u), FN1 = (int)((FK1 >> 2) & 7u), FN2 = (int)((FK2 >> 2) & 7u), FN = FN0 + FN1 + FN2;
+	// an axis twin: the plane form, and each block's two slots of it (device_types.h "Axis planes"; 0 everywhere else)
+	constexpr uint32_t AXES = SC::AXES, FA0 = AXES & 15u, FA1 = (AXES >> 4) & 15u, FA2 = (AXES >> 8) & 15u;
 	constexpr uint32_t SUB = USE_BVH ? SRT_SUB_BVH : HAS_MODELS ? SRT_SUB_MODELS : SRT_SUB_PLAIN;
 	const int width = p.rd.width;
 	const int lane = threadIdx.x;
@@ -88,7 +90,29 @@
 		cam_records_of_block<FK0>(lds + 2 * FN, cam_rec, cam_org, lane);
 		cam_records_of_block<FK1>(lds + 2 * FN + 4, cam_rec + CS1, cam_org, lane);
 		cam_records_of_block<FK2>(lds + 2 * FN + 8, cam_rec + CS2, cam_org, lane);
+		if constexpr (AXES != 0u) {
+			cam_axis_numerators<FK0, FA0>(lds + 2 * FN, cam_org, lane);
+			cam_axis_numerators<FK1, FA1>(lds + 2 * FN + 4, cam_org, lane);
+			cam_axis_numerators<FK2, FA2>(lds + 2 * FN + 8, cam_org, lane);
+		}
 		__syncthreads();
+	}
+	// Axis twins (device_intersect.h "AXIS PLANES"): whether the camera's own numerators are inside the guard's box is the same for
+	// every camera phase of the launch; its EXTEND phases and those that failed the guard are counted (srt_debug_counters [10], [11])
+	bool cam_nums_ok = false; // (wave-uniform)
+	uint32_t w_axis_phases = 0, w_axis_failed = 0;
+	if constexpr (AXES != 0u) {
+		const float4 *__restrict__ lb = lds + 2 * FN;
+		float mn = DM_INF_F, sm = 0.0f;
+#pragma unroll
+		for (int b = 0; b < 3; b++)
+#pragma unroll
+			for (int i = 0; i < 2; i++)
+				if (((AXES >> (4 * b + 2 * i)) & 3u) != 0u) {
+					const float a = dm_fabs(reinterpret_cast<const float *>(lb + 4 * b + 2 * i + 1)[3]);
+					mn = __builtin_fminf(mn, a), sm = sm + a;
+				}
+		cam_nums_ok = !any64(!(mn >= 0x1p-60f && sm <= 0x1p50f));
 	}
 	bool cam_phase = false;  // (wave-uniform) every lane of actm took its ray in the REFILL just before: EXTEND runs the camera forms
 	unsigned long long w_cam = 0; // diagnostics: such phases << 36 | the rays in them (srt_debug_counters; good for some 8 full-size frames between resets)
@@ -284,7 +308,33 @@
 							b.v[8] = q2.x, b.v[9] = q2.y, b.v[10] = q2.z, b.v[11] = q2.w, b.v[12] = q3.x, b.v[13] = q3.y, b.v[14] = q3.z, b.v[15] = q3.w;
 							return b;
 						};
-						if (cam_phase) {
+						if constexpr (AXES != 0u) {
+							// An axis twin: one guard for the phase's planes, voted over the lanes that hold a ray; a wave that passes runs the
+							// folded plane tests, any other today's forms below (device_intersect.h "AXIS PLANES").
+							constexpr int NP0 = (FK0 & 3u) == SRT_SHAPE_PLANE + 1u ? FN0 : 0, NP1 = (FK1 & 3u) == SRT_SHAPE_PLANE + 1u ? FN1 : 0;
+							constexpr int NP2 = (FK2 & 3u) == SRT_SHAPE_PLANE + 1u ? FN2 : 0, NP = NP0 + NP1 + NP2;
+							w_axis_phases++;
+							if (cam_phase) {
+								w_cam += (1ull << 36) + popc64(actm);
+								const float one[1] = {1.0f}; // (the numerators were looked at once, in the prologue: cam_nums_ok)
+								const bool pass = cam_nums_ok && (ballot64(!axis_operands_ok<1>(one, dir)) & actm) == 0ull;
+								w_axis_failed += pass ? 0u : 1u;
+								test_block_of_class_axis_cam<FK0, FA0>(lb, cam_rec, pass, 0, dir, actm, tmin, best);
+								if (FK1 != 0u) test_block_of_class_axis_cam<FK1, FA1>(lb + 4, cam_rec + CS1, pass, FN0, dir, actm, tmin, best);
+								if (FK2 != 0u) test_block_of_class_axis_cam<FK2, FA2>(lb + 8, cam_rec + CS2, pass, FN0 + FN1, dir, actm, tmin, best);
+							} else {
+								const float *__restrict__ lbf = reinterpret_cast<const float *>(lb);
+								float an[NP > 0 ? NP : 1];
+								axis_numerators<FK0, FA0>(lbf, org, an);
+								axis_numerators<FK1, FA1>(lbf + 16, org, an + NP0);
+								axis_numerators<FK2, FA2>(lbf + 32, org, an + NP0 + NP1);
+								const bool pass = (ballot64(!axis_operands_ok<NP>(an, dir)) & actm) == 0ull;
+								w_axis_failed += pass ? 0u : 1u;
+								test_block_of_class_axis<FK0, FA0>(lb, pass, an, 0, org, dir, tmin, best);
+								if (FK1 != 0u) test_block_of_class_axis<FK1, FA1>(lb + 4, pass, an + NP0, FN0, org, dir, tmin, best);
+								if (FK2 != 0u) test_block_of_class_axis<FK2, FA2>(lb + 8, pass, an + NP0 + NP1, FN0 + FN1, org, dir, tmin, best);
+							}
+						} else if (cam_phase) {
 							// (wave-uniform) fresh camera rays only: the same tests in the same order from the prologue's numbers
 							w_cam += (1ull << 36) + popc64(actm);
 							test_block_of_class_cam<FK0>(lb, cam_rec, 0, dir, actm, tmin, best);
@@ -951,6 +1001,7 @@
 #endif
 		}
 		if (FAST) w[5] += w_cam;
+		if constexpr (AXES != 0u) w[8] += w_axis_phases, w[9] += w_axis_failed; // (the phase clocks' slots: no class kernel is built with them)
 		w[6] += w_iter;
 		w[7] += w_shade;
 #ifdef SRT_PHASE_CLOCK

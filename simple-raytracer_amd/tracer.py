@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "srt_set_textures", "srt_set_material_textures", "srt_set_triangle_uvs", "srt_last_trace_textured", "srt_plane_frame_host",
     "srt_texture_check_host", "srt_group_set_textures", "srt_group_set_material_textures", "srt_group_set_triangle_uvs",
     "srt_last_trace_class", "srt_bernoulli_threshold_host",
+    "srt_last_trace_plane_form", "srt_plane_axis_code_host", "srt_selftest_plane_forms",
     "srt_set_triangle_materials", "srt_group_set_triangle_materials", "srt_triangle_materials_check_host",
     "srt_group_set_denoise", "srt_group_set_denoise_temporal", "srt_group_reset_denoise_history", "srt_group_resolve_denoised",
     "srt_group_read_denoised", "srt_group_read_denoise_inputs", "srt_group_read_denoise_history", "srt_partition_planes_floats",
@@ -117,6 +118,17 @@ def plane_frame_host(normal):
     n = np.ascontiguousarray(normal, np.float32).reshape(3)
     T, B = np.zeros(3, np.float32), np.zeros(3, np.float32)
     return (T, B) if lib.srt_plane_frame_host(_ptr(n), _ptr(T), _ptr(B)) else None
+
+
+def plane_axis_code_host(normal, position=(0.0, 0.0, 0.0)):
+    """srt_plane_axis_code_host (host only): 1, 2, 3 for a plane srt_update_scene takes for an axis plane (normal +-e_x, +-e_y,
+    +-e_z exactly, position at most 2^100 in every component), else 0."""
+    n = np.ascontiguousarray(normal, np.float32).reshape(3)
+    q = np.ascontiguousarray(position, np.float32).reshape(3)
+    out = C.c_int(-1)
+    if load_library().srt_plane_axis_code_host(_ptr(n), _ptr(q), C.byref(out)):
+        raise SrtError("srt_plane_axis_code_host failed")
+    return int(out.value)
 
 
 def bernoulli_threshold_host(p):
@@ -601,6 +613,11 @@ def _bind(lib):
         lib.srt_triangle_materials_check_host.argtypes = [vp, sz, sz, sz]
     if hasattr(lib, "srt_last_trace_class"):  # (an older library, SRT_LIB, in an A/B run)
         lib.srt_last_trace_class.argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(lib, "srt_last_trace_plane_form"):  # (the same)
+        lib.srt_last_trace_plane_form.argtypes = [vp, C.POINTER(C.c_int)]
+        lib.srt_plane_axis_code_host.argtypes = [vp, vp, C.POINTER(C.c_int)]
+        u32p = C.POINTER(C.c_uint32)
+        lib.srt_selftest_plane_forms.argtypes = [vp, i, vp, vp, u32p, C.c_uint32, u32p, u32p, u32p, C.POINTER(C.c_uint64)]
     if hasattr(lib, "srt_bernoulli_threshold_host"):
         lib.srt_bernoulli_threshold_host.argtypes = [C.c_float, C.POINTER(C.c_uint64)]
     return lib
@@ -787,6 +804,13 @@ class Tracer(_Denoise):
         self._check(self.lib.srt_last_trace_textured(self._h, C.byref(out)))
         return bool(out.value)
 
+    def last_trace_plane_form(self):
+        """0: the last trace ran its class's own kernel (or a general one); else the scene's plane form, whose axis twin ran
+        (srt_last_trace_plane_form)"""
+        out = C.c_int(-1)
+        self._check(self.lib.srt_last_trace_plane_form(self._h, C.byref(out)))
+        return int(out.value)
+
     def last_trace_class(self):
         """0: the last trace ran a general kernel; 1..: the kernel of the scene's class (srt_last_trace_class)"""
         out = C.c_int(0)
@@ -865,6 +889,8 @@ class Tracer(_Denoise):
                 "phase_cycles": dict(zip(("extend", "ring", "shade", "park", "deliver", "refill", "head", "kernel"), v[10:18])),
                 # array-scan kernels without -DSRT_PHASE_CLOCK reuse the first two clock slots: big-model scans and the lanes in them
                 "scans": v[10], "scan_lanes": v[11],
+                # ... as do the scene classes' axis twins: their EXTEND phases, and those among them that failed the twin's guard
+                "axis_phases": v[10], "axis_failed": v[11],
                 # ... and the next four: the launch-end ray pool (blocks taken, records handed in, sum of squares of the blocks a wave took, blocks the last wave took)
                 "pool_taken": v[12], "pool_given": v[13], "pool_taken_sq": v[14], "pool_last_taken": v[15]}
 
@@ -967,6 +993,21 @@ class Tracer(_Denoise):
         self._check(self.lib.srt_selftest_rare_lanes(self._h, int(what), words.ctypes.data_as(u32p), words.shape[0] // 64,
                                                      new.ctypes.data_as(u32p), ref.ctypes.data_as(u32p), C.byref(bad)))
         return new, ref, int(bad.value)
+
+    def selftest_plane_forms(self, what, planes, cam_org, words):
+        """planes: float32 [32] (the two staged plane blocks of the layout planes y, x | plane z); words: uint32 [lanes, 8], lanes a
+        multiple of 64 -> (new [lanes, 2] = {tmin bits, best}, test_planes2's [lanes, 2], fast [waves], mismatching words)"""
+        words = np.ascontiguousarray(words, np.uint32)
+        planes = np.ascontiguousarray(planes, np.float32).reshape(32)
+        cam_org = np.ascontiguousarray(cam_org, np.float32).reshape(3)
+        assert words.ndim == 2 and words.shape[1] == 8 and words.shape[0] % 64 == 0
+        waves = words.shape[0] // 64
+        new, ref = np.zeros((words.shape[0], 2), np.uint32), np.zeros((words.shape[0], 2), np.uint32)
+        fast, bad = np.zeros(waves, np.uint32), C.c_uint64()
+        u32p = C.POINTER(C.c_uint32)
+        self._check(self.lib.srt_selftest_plane_forms(self._h, int(what), _ptr(planes), _ptr(cam_org), words.ctypes.data_as(u32p), waves,
+                                                      new.ctypes.data_as(u32p), ref.ctypes.data_as(u32p), fast.ctypes.data_as(u32p), C.byref(bad)))
+        return new, ref, fast, int(bad.value)
 
     def set_kernel_timers(self, enable=True):
         """the render calls record the kernel timers' events too (default: only trace() does)"""
