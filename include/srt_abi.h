@@ -301,7 +301,11 @@ int srt_reset_counters(srt_tracer *t);
  * waves per CU and out[9] = workgroups of the most recent trace launch; out[10..17] = per-phase wave cycles
  * (extend, sky ring, shade, park, deliver, refill, loop head, whole kernel) of a -DSRT_PHASE_CLOCK build; in the product
  * build of the array-scan kernels out[10..15] = triangle scans of big models, lanes in them, blocks of 64 rays taken out
- * of the launch-end ray pool, records handed in to it, sum over waves of (blocks taken)^2, blocks the last wave took; else 0. */
+ * of the launch-end ray pool, records handed in to it, sum over waves of (blocks taken)^2, blocks the last wave took; in the
+ * product build of a scene class's axis twin out[10], out[11] = its EXTEND phases and those that failed the twin's guard; in the
+ * product build of the NO_SPEC scene classes (DESIGN.md 5 "Diffuse waves") out[7] is counted too, out[12] = the SHADE phases in
+ * which no lane ran the per-lane bounce (every shading lane's material plain diffuse, and the operand guard passed or no lane
+ * bounced on at all) and out[13] = the SHADE phases whose lanes were all plain diffuse but failed the operand guard; else 0. */
 int srt_debug_counters(srt_tracer *t, uint64_t out[18]);
 /* Development builds with -DSRT_REGION_COUNT only (the product build writes nothing and sets *written = 0): for each
  * region of the trace kernel, in the order of SRT_REGION_LIST (csrc/trace_regions.h), {times a wave ran it, lanes that ran it}
@@ -877,6 +881,16 @@ int srt_selftest_rare_lanes(srt_tracer *t, int what, const uint32_t *in, uint32_
  * guard; *mismatches = the words of out_new that differ from out_ref (must be 0). waves <= 65536. */
 int srt_selftest_plane_forms(srt_tracer *t, int what, const float planes[32], const float cam_org[3], const uint32_t *in, uint32_t waves,
                              uint32_t *out_new, uint32_t *out_ref, uint32_t *fast, uint64_t *mismatches);
+
+/* Device self-test of the NO_SPEC scene classes' diffuse-wave bounce (tests only; DESIGN.md 5 "Diffuse waves"). Each wave runs
+ * what a SHADE phase runs between random_dir and SHADE_TAIL -- the vote on the materials, the vote on the operands, then the
+ * short form (dir = random_dir, mask * colour, the generator three steps on) or the per-lane form on all 64 lanes -- and, beside
+ * it, the per-lane form alone. Lane i reads in[20 * i ..] = {random_dir, dir, nrm, metallic threshold, transmittance threshold,
+ * smoothness, mask, colour (float bits; the thresholds are the 32-bit draw thresholds), seed, unused} and writes eight words of
+ * each result: {dir, mask, seed afterwards, 1 where the lane drew transparent (its dir is then the rough direction the glass
+ * branch goes on from)}. fast[w] = 1 when wave w took the short form; *mismatches = the words of out_new that differ from
+ * out_ref (must be 0). waves <= 65536. */
+int srt_selftest_diffuse_bounce(srt_tracer *t, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, uint32_t *fast, uint64_t *mismatches);
 
 /* Library / build identification, e.g. "srt-hip gfx950 parity fp-contract=off". */
 const char *srt_version(void);

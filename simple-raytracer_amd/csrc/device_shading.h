@@ -118,6 +118,68 @@ __device__ __forceinline__ f3 winner_normal(const TraceParams &p, int best, uint
 	return nrm;
 }
 
+// ---- DIFFUSE WAVES (DESIGN.md §5 "Diffuse waves") ----
+// The NO_SPEC scene classes' bounce (trace_body.inc SHADE_BOUNCE .. SHADE_OPAQUE) on a lane whose material is PLAIN DIFFUSE --
+// metallic threshold 0 and transmittance threshold 0, so `random_bits < 0` makes both draws false for every output of the
+// generator -- comes to
+//     rough_dir = fma(reflect3(dir, nrm) - random_dir, smoothness, random_dir)
+//     dir       = fma(rough_dir - random_dir, +0, random_dir)        mask = mask * mcolor        seed three steps on
+// and fma(d, +0, x) is x, bit for bit, when d is finite (d * 0 is then an exact +-0) and x is neither a zero (+0 + -0 is +0: the
+// sign of a zero component reaches the plane tests' quotients) nor a NaN (kept out for a plain proof; the sum below refuses it).
+// A wave whose shading lanes are ALL plain diffuse and whose operands ALL pass diffuse_operands_ok takes random_dir as it is:
+// no draws, no reflect3, no mix3. Any other wave runs the per-lane form as it stands.
+__device__ __forceinline__ bool plain_diffuse(float metallic_threshold, float transmittance_threshold) {
+	return (dm_f2u(metallic_threshold) | dm_f2u(transmittance_threshold)) == 0u;
+}
+// The guard, per lane. S = the sum of the ten magnitudes (random_dir, dir, nrm, smoothness) <= 2^20, mn = the smallest
+// |random_dir component| > 0.
+//   * A NaN or an infinity among the ten makes S NaN or +inf and the compare false. A sum of non-negative floats is at least
+//     each term (rounding is monotone), so every magnitude is <= 2^20.
+//   * v_min3 skips NaNs, but S has refused them already; mn > 0 so refuses exactly a component of +-0 (a denormal passes: f32
+//     denormals are on, and fma(d, 0, x) returns a denormal x unchanged).
+//   * d is finite: |dot3(dir, nrm)| <= 3 * 2^40 * (1 + 2^-23)^3 < 2^42; doubled < 2^43; times a component of nrm < 2^63;
+//     |reflected_dir| < 2^64; |reflected_dir - random_dir| < 2^65; |rough_dir| < 2^85 + 2^20 < 2^86; |d| < 2^87 < 2^128.
+// So the identity holds for every lane the guard admits. (tests/test_diffuse_bounce_host.py restates it in numpy.)
+__device__ __forceinline__ bool diffuse_operands_ok(f3 random_dir, f3 dir, f3 nrm, float smoothness) {
+	const float rx = dm_fabs(random_dir.x), ry = dm_fabs(random_dir.y), rz = dm_fabs(random_dir.z);
+	const float mn = __builtin_fminf(__builtin_fminf(rx, ry), rz);
+	const float sm = ((((((((rx + ry) + rz) + dm_fabs(dir.x)) + dm_fabs(dir.y)) + dm_fabs(dir.z)) + dm_fabs(nrm.x)) + dm_fabs(nrm.y)) + dm_fabs(nrm.z)) + dm_fabs(smoothness);
+	return mn > 0.0f && sm <= 0x1p20f;
+}
+// (wave-uniform) the two votes over the lanes that are executing
+__device__ __forceinline__ bool diffuse_wave_materials(float metallic_threshold, float transmittance_threshold) {
+	return !any64(!plain_diffuse(metallic_threshold, transmittance_threshold));
+}
+__device__ __forceinline__ bool diffuse_wave_operands(f3 random_dir, f3 dir, f3 nrm, float smoothness) {
+	return !any64(!diffuse_operands_ok(random_dir, dir, nrm, smoothness));
+}
+// The short form: the generator steps over the three material draws (the compiler folds the steps into one multiply-add).
+__device__ __forceinline__ void bounce_diffuse_wave(f3 random_dir, f3 mcolor, f3 &dir, f3 &mask, uint32_t &seed) {
+	seed = seed * 747796405u + 2891336453u;
+	seed = seed * 747796405u + 2891336453u;
+	seed = seed * 747796405u + 2891336453u;
+	dir = random_dir;
+	mask = mask * mcolor;
+}
+// The per-lane form up to the branch on is_transparent, restated for srt_selftest_diffuse_bounce from the NO_SPEC text of
+// trace_body.inc (which the kernels keep as it stands; the oracle tests pin that text, the self-test pins the identity). An
+// opaque lane gets its new dir and mask; a transparent one is left with rough_dir, which SHADE_GLASS goes on from.
+__device__ __forceinline__ bool bounce_nospec_lane(f3 random_dir, f3 nrm, float smoothness, float metallic, float transmittance, f3 mcolor, f3 &dir, f3 &mask, uint32_t &seed) {
+	f3 reflected_dir = reflect3(dir, nrm);
+	bool is_metallic, is_transparent;
+	is_metallic = bernoulli(metallic, true, seed);
+	seed = seed * 747796405u + 2891336453u; // random_bits' state step, its output unused
+	is_transparent = bernoulli(transmittance, true, seed);
+	f3 rough_dir = mix3(random_dir, reflected_dir, smoothness);
+	if (!is_transparent) {
+		dir = mix3(random_dir, rough_dir, is_metallic ? 1.0f : 0.0f);
+		mask = mask * mcolor;
+	} else {
+		dir = rough_dir;
+	}
+	return is_transparent;
+}
+
 #if SRT_TEXTURED
 // ---- albedo textures: include/srt_abi.h states these rules; tests/texture_ref.py copies the expressions below ----
 __device__ __forceinline__ int tex_wrap(int x, int n) { // x mod n, never negative

@@ -437,5 +437,6 @@ void srt_launch_selftest(unsigned long long *out16, uint32_t stride, void *strea
 void srt_launch_selftest_rare(int what, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, unsigned long long *mismatches, void *stream);
 void srt_launch_selftest_plane_forms(int what, const float *planes32, const float *cam_org3, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref,
                                      uint32_t *fast, unsigned long long *mismatches, void *stream);
+void srt_launch_selftest_diffuse_bounce(const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, uint32_t *fast, unsigned long long *mismatches, void *stream);
 
 #endif

@@ -213,3 +213,41 @@ void srt_launch_selftest_plane_forms(int what, const float *planes32, const floa
 	for (int i = 0; i < 3; i++) pl.cam_org[i] = cam_org3[i];
 	hipLaunchKernelGGL(srt_selftest_plane_forms_kernel, dim3(waves), dim3(64), 0, (hipStream_t)stream, what, pl, in, out_new, out_ref, fast, mismatches);
 }
+
+// The NO_SPEC classes' bounce (device_shading.h "DIFFUSE WAVES") as a SHADE phase runs it, WAVE BY WAVE beside the per-lane form
+// alone: the vote on the materials, the vote on the operands, then the short form or the per-lane form on all 64 lanes. 20
+// input words per lane: {random_dir, dir, nrm, metallic threshold, transmittance threshold, smoothness, mask, mcolor, seed, -};
+// 8 output words: {dir, mask, seed, 1 where the lane drew `transparent` (its dir is rough_dir then)}.
+__global__ __launch_bounds__(64) void srt_selftest_diffuse_bounce_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out_new, uint32_t *__restrict__ out_ref,
+                                                                         uint32_t *__restrict__ fast, unsigned long long *mismatches) {
+	const size_t lane = (size_t)blockIdx.x * 64u + threadIdx.x;
+	const uint32_t *__restrict__ w = in + lane * 20u;
+	const f3 random_dir = mk(dm_u2f(w[0]), dm_u2f(w[1]), dm_u2f(w[2]));
+	const f3 dir = mk(dm_u2f(w[3]), dm_u2f(w[4]), dm_u2f(w[5]));
+	const f3 nrm = mk(dm_u2f(w[6]), dm_u2f(w[7]), dm_u2f(w[8]));
+	const float metallic = dm_u2f(w[9]), transmittance = dm_u2f(w[10]), smoothness = dm_u2f(w[11]);
+	const f3 mask = mk(dm_u2f(w[12]), dm_u2f(w[13]), dm_u2f(w[14]));
+	const f3 mcolor = mk(dm_u2f(w[15]), dm_u2f(w[16]), dm_u2f(w[17]));
+	f3 dir_r = dir, mask_r = mask, dir_n = dir, mask_n = mask;
+	uint32_t seed_r = w[18], seed_n = w[18];
+	const bool glass_r = bounce_nospec_lane(random_dir, nrm, smoothness, metallic, transmittance, mcolor, dir_r, mask_r, seed_r);
+	bool glass_n = false;
+	const bool pass = diffuse_wave_materials(metallic, transmittance) && diffuse_wave_operands(random_dir, dir, nrm, smoothness);
+	if (pass) bounce_diffuse_wave(random_dir, mcolor, dir_n, mask_n, seed_n);
+	else glass_n = bounce_nospec_lane(random_dir, nrm, smoothness, metallic, transmittance, mcolor, dir_n, mask_n, seed_n);
+	const uint32_t rn[8] = {dm_f2u(dir_n.x), dm_f2u(dir_n.y), dm_f2u(dir_n.z), dm_f2u(mask_n.x), dm_f2u(mask_n.y), dm_f2u(mask_n.z), seed_n, glass_n ? 1u : 0u};
+	const uint32_t rr[8] = {dm_f2u(dir_r.x), dm_f2u(dir_r.y), dm_f2u(dir_r.z), dm_f2u(mask_r.x), dm_f2u(mask_r.y), dm_f2u(mask_r.z), seed_r, glass_r ? 1u : 0u};
+	unsigned long long bad = 0;
+#pragma unroll
+	for (int k = 0; k < 8; k++) {
+		out_new[lane * 8u + k] = rn[k], out_ref[lane * 8u + k] = rr[k];
+		bad += rn[k] != rr[k] ? 1u : 0u;
+	}
+	if (threadIdx.x == 0) fast[blockIdx.x] = pass ? 1u : 0u;
+	if (bad) atomicAdd(mismatches, bad);
+}
+
+void srt_launch_selftest_diffuse_bounce(const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, uint32_t *fast, unsigned long long *mismatches, void *stream) {
+	if (waves == 0) return;
+	hipLaunchKernelGGL(srt_selftest_diffuse_bounce_kernel, dim3(waves), dim3(64), 0, (hipStream_t)stream, in, out_new, out_ref, fast, mismatches);
+}

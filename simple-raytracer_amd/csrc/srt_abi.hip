@@ -1109,9 +1109,37 @@ int srt_selftest_plane_forms(srt_tracer *t, int what, const float planes[32], co
 	return SRT_OK;
 }
 
+int srt_selftest_diffuse_bounce(srt_tracer *t, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, uint32_t *fast, uint64_t *mismatches) {
+	if (!t) return SRT_ERR_INVALID;
+	if (!in || !out_new || !out_ref || !fast || !mismatches || waves == 0 || waves > 65536u) return fail(t, SRT_ERR_INVALID, "srt_selftest_diffuse_bounce: bad arguments");
+	SRT_HIP(t, hipSetDevice(t->device));
+	const size_t lanes = (size_t)waves * 64u, in_bytes = lanes * 20u * sizeof(uint32_t), out_bytes = lanes * 8u * sizeof(uint32_t), fast_bytes = (size_t)waves * sizeof(uint32_t);
+	char *d = nullptr; // [in | out_new | out_ref | count | fast]
+	SRT_HIP(t, hipMalloc(reinterpret_cast<void **>(&d), in_bytes + 2 * out_bytes + sizeof(unsigned long long) + fast_bytes));
+	uint32_t *d_in = reinterpret_cast<uint32_t *>(d), *d_new = reinterpret_cast<uint32_t *>(d + in_bytes), *d_ref = reinterpret_cast<uint32_t *>(d + in_bytes + out_bytes);
+	unsigned long long *d_bad = reinterpret_cast<unsigned long long *>(d + in_bytes + 2 * out_bytes), h_bad = 0;
+	uint32_t *d_fast = reinterpret_cast<uint32_t *>(d + in_bytes + 2 * out_bytes + sizeof(unsigned long long));
+	hipError_t e = hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, t->stream);
+	if (e == hipSuccess) e = hipMemsetAsync(d_new, 0, 2 * out_bytes + sizeof(unsigned long long) + fast_bytes, t->stream);
+	if (e == hipSuccess) {
+		srt_launch_selftest_diffuse_bounce(d_in, waves, d_new, d_ref, d_fast, d_bad, t->stream);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(out_new, d_new, out_bytes, hipMemcpyDeviceToHost, t->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(out_ref, d_ref, out_bytes, hipMemcpyDeviceToHost, t->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(fast, d_fast, fast_bytes, hipMemcpyDeviceToHost, t->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(&h_bad, d_bad, sizeof h_bad, hipMemcpyDeviceToHost, t->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+	(void)hipFree(d);
+	if (e != hipSuccess) return fail(t, SRT_ERR_HIP, std::string("srt_selftest_diffuse_bounce: ") + hipGetErrorString(e));
+	*mismatches = h_bad;
+	return SRT_OK;
+}
+
 /* diagnostics: sums of the eight per-wave counter slots since the last reset (slot 5 = the scene-class kernels' EXTEND phases of
  * fresh camera rays only << 36 | the rays in those phases, 6 = wave iterations, 7 = SHADE phases; out[10], out[11] = an axis
- * twin's EXTEND phases and those among them that failed its guard, in the slots the -DSRT_PHASE_CLOCK builds keep clocks in) */
+ * twin's EXTEND phases and those among them that failed its guard, out[12], out[13] = a NO_SPEC class's SHADE phases that ran no
+ * per-lane bounce and those that failed the diffuse-wave guard, in the slots the -DSRT_PHASE_CLOCK builds keep clocks in) */
 int srt_debug_counters(srt_tracer *t, uint64_t out[18]) {
 	if (!t || !out) return SRT_ERR_INVALID;
 	SRT_HIP(t, hipSetDevice(t->device));

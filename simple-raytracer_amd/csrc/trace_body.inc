@@ -114,6 +114,11 @@
 				}
 		cam_nums_ok = !any64(!(mn >= 0x1p-60f && sm <= 0x1p50f));
 	}
+	// NO_SPEC classes (device_shading.h "DIFFUSE WAVES"): SHADE phases are counted, those that ran no per-lane bounce (the short form; or
+	// all lanes plain diffuse and on their last bounce, which run no bounce at all) and those whose lanes were all plain diffuse but
+	// failed the operand guard (srt_debug_counters [7], [12], [13])
+	constexpr bool DIFFUSE_WAVE = FAST && SC::NO_SPEC;
+	uint32_t w_diffuse_short = 0, w_diffuse_failed = 0;
 	bool cam_phase = false;  // (wave-uniform) every lane of actm took its ray in the REFILL just before: EXTEND runs the camera forms
 	unsigned long long w_cam = 0; // diagnostics: such phases << 36 | the rays in them (srt_debug_counters; good for some 8 full-size frames between resets)
 #ifdef SRT_REGION_COUNT
@@ -502,7 +507,8 @@
 			// the whole wave is on its last bounce.
 			const unsigned long long lastm = ballot64(bounce == nb - 1) & shm;
 			const bool show_normals = !FAST && p.rd.show_normals != 0;
-			if (SRT_DIAG_ON) w_shade++;
+			if (SRT_DIAG_ON || DIFFUSE_WAVE) w_shade++;
+			bool diffuse_all = false, diffuse_short = false; // (the same in every lane of shm) NO_SPEC classes: every shading lane is plain diffuse / and no lane runs the per-lane bounce
 			if (in_mask(shm)) {
 				SRT_REGION(SHADE_WINNER);
 				// ---- winner: normal, material (render.cl:311-312,337-343,361-362,372-375); org = hit position ----
@@ -580,6 +586,7 @@
 #else
 					const f3 mcolor = mk(mc.x, mc.y, mc.z);
 #endif
+					if constexpr (DIFFUSE_WAVE) diffuse_all = diffuse_short = diffuse_wave_materials(metallic, transmittance); // (a phase that bounces votes on its operands below)
 					color = color + (mask * mk(me.x, me.y, me.z)) * emission_strength; // render.cl:413
 					if ((shm & ~lastm) != 0ull) { // (wave-uniform) somebody bounces on: see `lastm` above
 						SRT_REGION(SHADE_BOUNCE);
@@ -592,6 +599,12 @@
 						const float rd_side = dot3(nrm, rd_);
 						f3 hemi = FAST ? mul_sign_wave(rd_, rd_side) : rd_ * sign_fast(rd_side);
 						f3 random_dir = normalize3(nrm + hemi);
+						// Diffuse waves (device_shading.h "DIFFUSE WAVES"): every shading lane's material is plain diffuse and the operands pass
+						// the guard, voted once per phase: the new direction is random_dir as it is. Any other wave: the per-lane form. @rare
+						if constexpr (DIFFUSE_WAVE) diffuse_short = diffuse_all && diffuse_wave_operands(random_dir, dir, nrm, smoothness);
+						if (DIFFUSE_WAVE && diffuse_short) {
+							bounce_diffuse_wave(random_dir, mcolor, dir, mask, seed);
+						} else {
 						f3 reflected_dir = reflect3(dir, nrm);
 						// the three material draws (render.cl:427-430; nothing else draws in between)
 						bool is_metallic, is_specular, is_transparent;
@@ -637,6 +650,7 @@
 								mask = mask * mcolor;
 							}
 						}
+						}
 						SRT_REGION(SHADE_TAIL);
 						dir = normalize3(dir);
 						const float out_side = dot3(nrm, dir);
@@ -645,6 +659,8 @@
 					}
 				}
 			}
+			// (the two flags were set under the exec mask shm and are false in the other lanes: a vote makes them the wave's again)
+			if constexpr (DIFFUSE_WAVE) w_diffuse_short += any64(diffuse_short) ? 1u : 0u, w_diffuse_failed += any64(diffuse_all && !diffuse_short) ? 1u : 0u;
 			// what became of the shaded paths: ended (show_normals, or the last bounce: only its emission counts) or on their way again
 			if (show_normals) {
 				finm |= shm;
@@ -1002,6 +1018,7 @@
 		}
 		if (FAST) w[5] += w_cam;
 		if constexpr (AXES != 0u) w[8] += w_axis_phases, w[9] += w_axis_failed; // (the phase clocks' slots: no class kernel is built with them)
+		if constexpr (DIFFUSE_WAVE) w[10] += w_diffuse_short, w[11] += w_diffuse_failed; // (likewise)
 		w[6] += w_iter;
 		w[7] += w_shade;
 #ifdef SRT_PHASE_CLOCK

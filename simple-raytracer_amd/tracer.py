@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "srt_set_textures", "srt_set_material_textures", "srt_set_triangle_uvs", "srt_last_trace_textured", "srt_plane_frame_host",
     "srt_texture_check_host", "srt_group_set_textures", "srt_group_set_material_textures", "srt_group_set_triangle_uvs",
     "srt_last_trace_class", "srt_bernoulli_threshold_host",
-    "srt_last_trace_plane_form", "srt_plane_axis_code_host", "srt_selftest_plane_forms",
+    "srt_last_trace_plane_form", "srt_plane_axis_code_host", "srt_selftest_plane_forms", "srt_selftest_diffuse_bounce",
     "srt_set_triangle_materials", "srt_group_set_triangle_materials", "srt_triangle_materials_check_host",
     "srt_group_set_denoise", "srt_group_set_denoise_temporal", "srt_group_reset_denoise_history", "srt_group_resolve_denoised",
     "srt_group_read_denoised", "srt_group_read_denoise_inputs", "srt_group_read_denoise_history", "srt_partition_planes_floats",
@@ -618,6 +618,9 @@ def _bind(lib):
         lib.srt_plane_axis_code_host.argtypes = [vp, vp, C.POINTER(C.c_int)]
         u32p = C.POINTER(C.c_uint32)
         lib.srt_selftest_plane_forms.argtypes = [vp, i, vp, vp, u32p, C.c_uint32, u32p, u32p, u32p, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "srt_selftest_diffuse_bounce"):  # (the same)
+        u32p = C.POINTER(C.c_uint32)
+        lib.srt_selftest_diffuse_bounce.argtypes = [vp, u32p, C.c_uint32, u32p, u32p, u32p, C.POINTER(C.c_uint64)]
     if hasattr(lib, "srt_bernoulli_threshold_host"):
         lib.srt_bernoulli_threshold_host.argtypes = [C.c_float, C.POINTER(C.c_uint64)]
     return lib
@@ -891,6 +894,9 @@ class Tracer(_Denoise):
                 "scans": v[10], "scan_lanes": v[11],
                 # ... as do the scene classes' axis twins: their EXTEND phases, and those among them that failed the twin's guard
                 "axis_phases": v[10], "axis_failed": v[11],
+                # ... and the NO_SPEC classes (which count shade_phases in the product build, too): SHADE phases in which no lane ran the
+                # per-lane bounce, and those whose lanes were all plain diffuse but failed the operand guard
+                "diffuse_short": v[12], "diffuse_failed": v[13],
                 # ... and the next four: the launch-end ray pool (blocks taken, records handed in, sum of squares of the blocks a wave took, blocks the last wave took)
                 "pool_taken": v[12], "pool_given": v[13], "pool_taken_sq": v[14], "pool_last_taken": v[15]}
 
@@ -1007,6 +1013,20 @@ class Tracer(_Denoise):
         u32p = C.POINTER(C.c_uint32)
         self._check(self.lib.srt_selftest_plane_forms(self._h, int(what), _ptr(planes), _ptr(cam_org), words.ctypes.data_as(u32p), waves,
                                                       new.ctypes.data_as(u32p), ref.ctypes.data_as(u32p), fast.ctypes.data_as(u32p), C.byref(bad)))
+        return new, ref, fast, int(bad.value)
+
+    def selftest_diffuse_bounce(self, words):
+        """words: uint32 [lanes, 20] = {random_dir, dir, nrm, metallic threshold, transmittance threshold, smoothness, mask, colour,
+        seed, -}, lanes a multiple of 64 -> (wave form [lanes, 8] = {dir, mask, seed, drew transparent}, the per-lane form's
+        [lanes, 8], fast [waves], mismatching words)"""
+        words = np.ascontiguousarray(words, np.uint32)
+        assert words.ndim == 2 and words.shape[1] == 20 and words.shape[0] % 64 == 0
+        waves = words.shape[0] // 64
+        new, ref = np.zeros((words.shape[0], 8), np.uint32), np.zeros((words.shape[0], 8), np.uint32)
+        fast, bad = np.zeros(waves, np.uint32), C.c_uint64()
+        u32p = C.POINTER(C.c_uint32)
+        self._check(self.lib.srt_selftest_diffuse_bounce(self._h, words.ctypes.data_as(u32p), waves, new.ctypes.data_as(u32p),
+                                                         ref.ctypes.data_as(u32p), fast.ctypes.data_as(u32p), C.byref(bad)))
         return new, ref, fast, int(bad.value)
 
     def set_kernel_timers(self, enable=True):
