@@ -1,6 +1,10 @@
 // tonemap.h — the per-pixel device helpers the resolve and the denoiser share (frame.hip, denoise.hip, temporal.hip):
 // srt_resolve_kernel's ACES fit and byte conversion, the tonemap as srt_denoise_setup_kernel and the passes write it,
-// luminance and the finite-colour test. One copy, so the denoiser's K = 0 bytes are the plain resolve's by construction.
+// luminance and the finite-colour test. aces1 and to_uchar exist once; the expression around them (divide, fit, sqrt, * 255,
+// pack) is written out three times: srt_resolve_kernel and srt_reduce_kernel<false>'s fused resolve in frame.hip divide by
+// (float)num_steps and call sqrt_ieee, tonemap() below takes a divided colour and calls __builtin_sqrtf. The three are held
+// equal byte for byte, the denoiser's K = 0 bytes being the plain resolve's, by tests/test_gpu_tonemap_edges.py on canvas
+// values at every byte boundary and at the non-finite ends (tests/tonemap_cases.py), not by construction.
 // Not part of the public ABI.
 #ifndef SRT_TONEMAP_H
 #define SRT_TONEMAP_H
