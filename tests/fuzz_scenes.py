@@ -541,11 +541,12 @@ def differing_pixels(got, want):
     return int((~((got.view(np.uint32) == want.view(np.uint32)) | (np.isnan(got) & np.isnan(want)))).any(axis=-1).sum())
 
 
-def run_lane(T, oracle, sky, name, hostile, iterations, seed=20250, nthreads=4, progress=None):
+def run_lane(T, oracle, sky, name, hostile, iterations, seed=20250, nthreads=4, progress=None, report=None):
     """`iterations` scenes of lane `name` on one Tracer (T: the simple_raytracer_amd.tracer module). For every scene: the class
     and the textured flag the library reports equal the lane's intention AND the restatement; the canvas is the oracle's bit
     for bit; paths, rays, sky, nan_pixels are the oracle's; the watchdog did not fire. On a third of the scenes a radiance
-    budget forces two or three sample batches. -> (failures [(lane, iteration, what, differing pixels, differing counters)],
+    budget forces two or three sample batches. report: a list that receives (class, plane form, textured) of every dispatch as the
+    library reports them. -> (failures [(lane, iteration, what, differing pixels, differing counters)],
     classes reported [int], edits {kind: count})"""
     lane = LANES[name]
     rng = np.random.RandomState(lane_seed(name, hostile, seed))
@@ -581,6 +582,8 @@ def run_lane(T, oracle, sky, name, hostile, iterations, seed=20250, nthreads=4, 
             got, c = t.read_canvas(), t.counters()
             reported = (t.last_trace_class(), t.last_trace_textured())
             classes.append(reported[0])
+            if report is not None:
+                report.append((reported[0], t.last_trace_plane_form(), reported[1]))
             restated = (expected_class(shapes, mats, rd, textured=expected[1]), expected[1])
             if not (reported == tuple(expected) == restated):
                 problems.append(f"class / textured: library {reported}, lane {tuple(expected)}, restatement {restated}")

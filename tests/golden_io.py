@@ -36,7 +36,8 @@ def load_kats():
 
 def load_ref_checks():
     """The reference build's outputs for tests/test_oracle_vs_ref.py ("frame/<name>", "average/<steps>") and for
-    tests/test_tonemap_cases.py ("tonemap/<ticks>", "tonemap/disagree"), and the glibc-libm build's renders for
+    tests/test_tonemap_cases.py ("tonemap/<ticks>", "tonemap/disagree"), its sky_box for tests/test_sky_cases.py ("sky/dirs",
+    "sky/<sky>"), and the glibc-libm build's renders for
     tests/test_oracle_statistics.py ("libm/<case>")."""
     z = np.load(GOLDEN / "ref_checks.npz")
     return {k: z[k] for k in z.files if k != "detmath_revision"}

@@ -1,6 +1,7 @@
 """numpy restatement of the albedo-texture contract (include/srt_abi.h "albedo textures"; csrc/device_shading.h sample_texture,
 texture_albedo): the UV per kind of shape and both filters, in float32, unfused, in the kernel's order. dm_atan2pif and
-dm_bilinear come from a host build of csrc/detmath.h (tests/csrc/texture_math.c). A plain module, not a test module."""
+dm_bilinear come from a host build of csrc/detmath.h (tests/csrc/texture_math.c). A plain module, not a test module. Its
+CLAMP_TO_EDGE sibling, the sky's sampler, is tests/sky_ref.py, which loads the same host build through lib()."""
 import ctypes as C
 import subprocess
 import tempfile
