@@ -7,8 +7,8 @@ for a moved shape.
                  launches together (the library's events surround the filter, not each launch)
   added_ms       setup_on_ms - setup_off_ms: what the switch costs a frame
 
-camera: the camera moved since the history (srt_temporal_setup_kernel / _clamp_kernel); shape: the camera still, object motion on
-and one sphere moved (srt_temporal_motion_kernel / _clamp_kernel). Switch off and on alternate in one process on one handle and
+camera: the camera moved since the history (srt_temporal_kernel<0, false, false> / <0, false, true>); shape: the camera still, object motion on
+and one sphere moved (srt_temporal_kernel<1, false, false> / <1, false, true>). Switch off and on alternate in one process on one handle and
 one canvas; medians of --reps rounds (default 7) after one round that is thrown away. Scene: scenes.sphere_scene, 2 spp. Writes
 profiles/r20_history_clamp_<w>x<h>.json to --out-dir. With a library that lacks the switch (SRT_LIB: a parent checkout's build)
 only the off figures are reported: the parent's set-up time by the same probe.

@@ -2,8 +2,8 @@
 (srt_set_denoise_history_illumination), and the quality of a moving camera over a textured scene with the switch off and on.
 
   setup_colour_ms        srt_resolve_denoised with K = 0, temporal on, the camera moved since the history, the switch off:
-                         srt_temporal_setup_kernel, the launch of a library without the switch (library HIP events)
-  setup_illumination_ms  the same frame with the switch on: srt_temporal_setup_illum_kernel
+                         srt_temporal_kernel<0, false, false>, the launch of a library without the switch (library HIP events)
+  setup_illumination_ms  the same frame with the switch on: srt_temporal_kernel<0, true, false>
   ratio                  setup_illumination_ms / setup_colour_ms
 
 Switch off and on alternate in one process on one handle and one canvas; medians of --reps rounds (default 7) after one round

@@ -6,7 +6,8 @@ Each tree is a checkout's root (holding simple-raytracer_amd/csrc and include/).
 compiled device-only with the product flags of build.py, its gfx950 code object is unbundled and disassembled with
 llvm-objdump, and every function in it is compared instruction by instruction, branch offsets and the s_nop padding
 between functions left out. A function that only one side has counts as a difference; the plain ordered reduction is
-matched across its rename to srt_reduce_kernel<false> (a template since the denoiser's moments variant). Exit status 1 on
+matched across its rename to srt_reduce_kernel<false> (a template since the denoiser's moments variant), and the twelve temporal
+set-ups across theirs to srt_temporal_kernel<MOTION, ILLUM, CLAMP>. A function that differs prints both counts. Exit status 1 on
 any difference; with --allow-new, functions that only the new tree has do not count.
 """
 import re
@@ -17,12 +18,17 @@ from pathlib import Path
 
 ROCM = Path("/opt/rocm")
 RENAMED = {"_Z17srt_reduce_kernel12ReduceParams": "_Z17srt_reduce_kernelILb0EEv12ReduceParams"}  # old name -> new name
+TEMPORAL_SETUP = re.compile(r"^_ZN12_GLOBAL__N_1\d+srt_temporal_(setup|motion|deform)(_illum)?(_clamp)?_kernelENS_14TemporalParamsE")
 
 
 def renamed(name):
     """an old tree's function under the name the new tree gives it: the table above, and a scene-class kernel from before the
     plane form was a template parameter is the class's own kernel, plane form 0"""
     name = RENAMED.get(name, name)
+    m = TEMPORAL_SETUP.match(name)
+    if m:  # the twelve temporal set-ups from before they were srt_temporal_kernel<MOTION, ILLUM, CLAMP> (DESIGN.md section 11)
+        motion = {"setup": 0, "motion": 1, "deform": 2}[m.group(1)]
+        return f"_ZN12_GLOBAL__N_119srt_temporal_kernelILi{motion}ELb{int(bool(m.group(2)))}ELb{int(bool(m.group(3)))}EEEvNS_9SetupArgsIXT_EXT1_EEE"
     return re.sub(r"^(_Z22srt_trace_scene_kernelILj\d+ELb[01])(EEv11TraceParams)$", r"\1ELj0\2", name)
 
 
@@ -88,7 +94,8 @@ def main():
         bad += not same and not (allow_new and k not in a)
         where = "" if k in a and k in b else f"  only in {'old' if k in a else 'new'}"
         word = "same" if same else "new" if allow_new and k not in a else "DIFFERENT"
-        print(f"{word}  {k[0]}  {k[1]}  ({len(a.get(k, b.get(k)))} instructions){where}")
+        count = f"{len(a[k])} -> {len(b[k])}" if k in a and k in b and not same else len(a.get(k, b.get(k)))
+        print(f"{word}  {k[0]}  {k[1]}  ({count} instructions){where}")
     print(f"{len(names)} functions of {len(B.SOURCES)} sources compared, {bad} different")
     sys.exit(1 if bad or not names else 0)
 

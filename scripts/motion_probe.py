@@ -6,10 +6,10 @@ dragged.
 
 Each round starts one child process per build (a fresh process per library) that measures, with the library's HIP events:
 
-  setup_camera_moved_ms   the temporal set-up after a camera move (the bilinear 2x2): srt_temporal_setup_kernel on both builds
-  setup_object_moved_ms   this build, object motion on, one sphere moved since the history, camera still: srt_temporal_motion_kernel
+  setup_camera_moved_ms   the temporal set-up after a camera move (the bilinear 2x2): srt_temporal_kernel<0, false, false> on both builds
+  setup_object_moved_ms   this build, object motion on, one sphere moved since the history, camera still: srt_temporal_kernel<1, false, false>
   setup_both_moved_ms     the same with the camera moved too
-  setup_nothing_moved_ms  object motion on, nothing moved, camera moved: the host launches srt_temporal_setup_kernel
+  setup_nothing_moved_ms  object motion on, nothing moved, camera moved: the host launches srt_temporal_kernel<0, false, false>
   dispatch_ms             one 1-spp, 1-bounce dispatch with the denoiser on (trace + reduction + feature pass; the feature pass is
                           not timed alone); dispatch_ids_ms the same with object motion on (the feature pass stores the index)
 

@@ -5,11 +5,11 @@ library (the parent commit's libsrt_hip.so), alternating the two builds in one s
 
 Each round starts one child process per build (a fresh process per library) that measures, with the library's HIP events:
 
-  setup_camera_moved_ms   the temporal set-up after a camera move, every switch off: srt_temporal_setup_kernel on both builds
+  setup_camera_moved_ms   the temporal set-up after a camera move, every switch off: srt_temporal_kernel<0, false, false> on both builds
   setup_model_moved_ms    this build, mesh scene (two 968-triangle instances, BVH), object motion on, one instance translated,
-                          camera still: srt_temporal_motion_kernel
+                          camera still: srt_temporal_kernel<1, false, false>
   setup_deformed_ms       the same scene, per-triangle motion on, the mesh waved since the history, camera still:
-                          srt_temporal_deform_kernel (both instances' pixels project)
+                          srt_temporal_kernel<2, false, false> (both instances' pixels project)
   setup_deformed_cam_ms   the same with the camera moved too (every pixel projects)
   dispatch_ms             one 1-spp, 1-bounce dispatch of the mesh scene with the denoiser on (trace + reduction + feature pass);
                           dispatch_ids_ms with object motion on, dispatch_tris_ms with per-triangle motion on (the triangle-index store)

@@ -218,11 +218,11 @@ struct srt_tracer {
 	bool tp_fresh = false;   // tp_set[1 - tp_cur] holds the integration of what is traced since the clear (a filter ran after the last trace)
 	srt_render_data tp_cam{}; // the history frame's render data
 	bool tp_illum = false;         // srt_set_denoise_history_illumination: the set-ups rescale a history tap by D_p / D_h
-	bool last_setup_illum = false; // srt_last_setup_history_illumination: the last set-up launched an *_illum_kernel
+	bool last_setup_illum = false; // srt_last_setup_history_illumination: the last set-up launched an ILLUM variant
 	float tp_clamp = 0.f;          // srt_set_denoise_history_clamp: gamma (0: off); the set-ups clamp the history colour into mu +- gamma sigma
 	DevBuf<float> tp_bounds;       // two float4 planes {mu, sum of weights}, {sigma, taps} (allocated on the first enable; no part of the history)
 	bool tp_bounds_ran = false;    // srt_temporal_bounds_kernel has written tp_bounds at least once (srt_read_denoise_history_bounds)
-	bool last_setup_clamp = false; // srt_last_setup_history_clamp: the last set-up ran the bounds launch and a *_clamp_kernel
+	bool last_setup_clamp = false; // srt_last_setup_history_clamp: the last set-up ran the bounds launch and a CLAMP variant
 	std::vector<uint8_t> scene_bytes; // the last srt_update_scene's arrays and scene data (the history survives an unchanged scene)
 	// object motion (temporal.hip; srt_set_denoise_object_motion): the feature pass stores a shape index per pixel into
 	// om_ids[om_cur]; the commit swaps, so om_ids[1 - om_cur] belongs to the history, traced with the scene om_hist_scene

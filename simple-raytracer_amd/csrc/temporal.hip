@@ -14,7 +14,7 @@
 //   integrate  h' = min(h, history_limit), n = P + h'. h' = 0: the spatial set-up's values (for ticks = T, bit for bit).
 //              Else c = (P c_cur + h' c_h) / n, m1, m2 likewise, V = max(0, m2 - m1^2) / n (non-finite: 0)
 //   staging    {c, min(n, history_limit)}, {m1, m2} and the guide go to the set that becomes the history at the next clear
-//   illumination (srt_set_denoise_history_illumination; the *_illum_kernel variants; tests/history_illumination_ref.py): a counted
+//   illumination (srt_set_denoise_history_illumination; the ILLUM set-ups; tests/history_illumination_ref.py): a counted
 //              tap of the projected 2x2 whose pixel and whose history pixel are both fully covered (cov == 1) enters the sums
 //              as c_h (D_p / D_h) per channel, m1_h rl and (m2_h rl) rl with D = max(A, SRT_DEMOD_EPS), rl = lum(D_p) / lum(D_h);
 //              the identity tap and every other tap stay in colour. The history's contents are the same either way
@@ -27,6 +27,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/srt_abi.h"
@@ -74,26 +75,6 @@ struct MotionParams {
 	uint32_t n_shapes;
 };
 
-__global__ __launch_bounds__(256) void srt_temporal_setup_kernel(const TemporalParams p) {
-#define SRT_TEMPORAL_MOTION 0
-#include "temporal_body.inc"
-#undef SRT_TEMPORAL_MOTION
-}
-
-// The set-up when object motion is on and a shape of the table is not STATIC. Per pixel p with shape index s = ids[p]:
-//   s invalid or NO_HISTORY   no history
-//   s STATIC                  the arithmetic above (the identity tap for the same camera, else the projection of X), and a
-//                             tap whose history shape index is a MOVED / NO_HISTORY shape does not count
-//   s MOVED                   X_h = A_s X (rows: ((a0 X.x + a1 X.y) + a2 X.z) + a3), projected into the history camera also
-//                             when the cameras are the same, D = |X_h - cam_h|; a tap must carry history shape index s, and
-//                             its normal is compared with normalise(B_s N_p) (zero length or not finite: no history)
-// tests/temporal_ref.py reproject with a table restates it.
-__global__ __launch_bounds__(256) void srt_temporal_motion_kernel(const TemporalParams p, const MotionParams mp) {
-#define SRT_TEMPORAL_MOTION 1
-#include "temporal_body.inc"
-#undef SRT_TEMPORAL_MOTION
-}
-
 // per-triangle motion (srt_set_denoise_vertex_motion): the frame's triangle index per pixel, the world-vertex tables of the
 // frame and of the history (9 floats per instance triangle: P0, P1, P2) and each shape's first row (n_shapes + 1 entries)
 struct VertexParams {
@@ -102,36 +83,283 @@ struct VertexParams {
 	const uint32_t *first;
 };
 
-// The set-up when a shape of the table is DEFORMED: the moved kernel, and per pixel of a DEFORMED shape the map of
-// include/srt_abi.h ("per-triangle motion"): the point at the same barycentric place of the same triangle as it stood in the
-// history frame. tests/vertex_motion_ref.py restates it.
-__global__ __launch_bounds__(256) void srt_temporal_deform_kernel(const TemporalParams p, const MotionParams mp, const VertexParams vp) {
-#define SRT_TEMPORAL_MOTION 2
-#include "temporal_body.inc"
-#undef SRT_TEMPORAL_MOTION
-}
+// the history clamp (below): the two planes srt_temporal_bounds_kernel made of the frame, and gamma
+struct ClampParams {
+	const float4 *bounds;
+	uint32_t num_pixels;
+	float gamma;
+};
 
-// The three set-ups with the history reprojected as illumination (srt_set_denoise_history_illumination): the same bodies with
-// SRT_TEMPORAL_ILLUM 1. The host launches one of these in place of its twin above while the switch is on.
-#define SRT_TEMPORAL_ILLUM 1
-__global__ __launch_bounds__(256) void srt_temporal_setup_illum_kernel(const TemporalParams p) {
-#define SRT_TEMPORAL_MOTION 0
-#include "temporal_body.inc"
-#undef SRT_TEMPORAL_MOTION
-}
+// A set-up's kernel arguments: p, then mp, vp and cp for the variants that read them. A member the variant lacks is empty and
+// takes no room, so the kernel-argument segment holds what the variant reads and nothing else.
+template <class T> struct Absent {
+	Absent() = default;
+	__host__ __device__ Absent(const T &) {}
+};
+template <int MOTION, bool CLAMP> struct SetupArgs {
+	TemporalParams p;
+	[[no_unique_address]] std::conditional_t<MOTION >= 1, MotionParams, Absent<MotionParams>> mp;
+	[[no_unique_address]] std::conditional_t<MOTION == 2, VertexParams, Absent<VertexParams>> vp;
+	[[no_unique_address]] std::conditional_t<CLAMP, ClampParams, Absent<ClampParams>> cp;
+};
+static_assert(sizeof(SetupArgs<0, false>) == sizeof(TemporalParams) && sizeof(SetupArgs<1, true>) == sizeof(TemporalParams) + sizeof(MotionParams) + sizeof(ClampParams) &&
+              sizeof(SetupArgs<2, true>) == sizeof(TemporalParams) + sizeof(MotionParams) + sizeof(VertexParams) + sizeof(ClampParams), "SetupArgs: no room for an absent member");
 
-__global__ __launch_bounds__(256) void srt_temporal_motion_illum_kernel(const TemporalParams p, const MotionParams mp) {
-#define SRT_TEMPORAL_MOTION 1
-#include "temporal_body.inc"
-#undef SRT_TEMPORAL_MOTION
-}
+// The set-up, one instantiation per variant the host launches (launch_setup):
+//   MOTION 0 the camera alone; 1 per-shape motion (mp), when object motion is on and a shape of the table is not STATIC; 2 also
+//          per-triangle motion (vp), when a shape is DEFORMED
+//   ILLUM  a counted tap of the projected 2x2 is rescaled from its own first-hit albedo to this pixel's before it is summed
+//   CLAMP  the history colour is clamped into the bounds srt_temporal_bounds_kernel made of the frame (cp)
+// With MOTION >= 1, per pixel p with shape index s = ids[p] (tests/temporal_ref.py reproject with a table restates it):
+//   s invalid or NO_HISTORY   no history
+//   s STATIC                  the camera-only arithmetic (the identity tap for the same camera, else the projection of X), and a
+//                             tap whose history shape index is a MOVED / NO_HISTORY shape does not count
+//   s MOVED                   X_h = A_s X (rows: ((a0 X.x + a1 X.y) + a2 X.z) + a3), projected into the history camera also
+//                             when the cameras are the same, D = |X_h - cam_h|; a tap must carry history shape index s, and
+//                             its normal is compared with normalise(B_s N_p) (zero length or not finite: no history)
+//   s DEFORMED (MOTION 2)     as MOVED, with the map of include/srt_abi.h ("per-triangle motion"): the point at the same barycentric
+//                             place of the same triangle as it stood in the history frame. tests/vertex_motion_ref.py restates it
+template <int MOTION, bool ILLUM, bool CLAMP>
+__global__ __launch_bounds__(256) void srt_temporal_kernel(const SetupArgs<MOTION, CLAMP> a) {
+	const TemporalParams &p = a.p;
+	[[maybe_unused]] const auto &mp = a.mp;
+	[[maybe_unused]] const auto &vp = a.vp;
+	[[maybe_unused]] const auto &cp = a.cp;
+	const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+	if (x >= p.width || y >= p.height) return;
+	const uint32_t i = (uint32_t)y * (uint32_t)p.width + (uint32_t)x;
+	// ---- the spatial set-up (srt_denoise_setup_kernel's expressions, divisor T) ----
+	const float4 c = p.canvas[i], nd = p.normal_depth[i], ah = p.albedo_hits[i];
+	const float m = p.moments[i];
+	const float4 cc = make_float4(c.x / p.T, c.y / p.T, c.z / p.T, 0.f);
+	const float l = lum(cc.x, cc.y, cc.z);
+	const float m2c = m / p.T;
+	float v = m2c - l * l;
+	v = v > 0.f ? v : 0.f;
+	v = v / p.P;
+	if (!__builtin_isfinite(v)) v = 0.f;
+	const float hits = ah.w;
+	float nx = 0.f, ny = 0.f, nz = 0.f, z = 0.f;
+	if (hits > 0.f) {
+		const float len = sqrtf(nd.x * nd.x + nd.y * nd.y + nd.z * nd.z);
+		if (len > 0.f) nx = nd.x / len, ny = nd.y / len, nz = nd.z / len;
+		z = nd.w / hits;
+	}
+	const float4 g0 = make_float4(nx, ny, nz, z);
+	const float4 g1 = make_float4(ah.x / p.F, ah.y / p.F, ah.z / p.F, hits / p.F);
+	float dpr = 0.f, dpg = 0.f, dpb = 0.f, lp = 0.f;
+	bool full_p = false;
+	if constexpr (ILLUM) {
+		// the pixel's divisor as srt_denoise_demodulate_kernel forms it (a NaN channel: eps); only a fully covered pixel's colour
+		// is albedo x illumination (hits / F is exactly 1 when every feature sample hit)
+		dpr = fmaxf(g1.x, SRT_DEMOD_EPS), dpg = fmaxf(g1.y, SRT_DEMOD_EPS), dpb = fmaxf(g1.z, SRT_DEMOD_EPS);
+		lp = lum(dpr, dpg, dpb);
+		full_p = g1.w == 1.0f;
+	}
 
-__global__ __launch_bounds__(256) void srt_temporal_deform_illum_kernel(const TemporalParams p, const MotionParams mp, const VertexParams vp) {
-#define SRT_TEMPORAL_MOTION 2
-#include "temporal_body.inc"
-#undef SRT_TEMPORAL_MOTION
+	// ---- reprojection ----
+	float sw = 0.f, sr = 0.f, sg = 0.f, sb = 0.f, sh = 0.f, s1 = 0.f, s2 = 0.f;
+	// the pixel's shape s and its state: a static shape keeps the camera-only arithmetic, a moved one maps X through A_s and
+	// compares the taps' normals with normalise(B_s N_p). MOTION 0 leaves all of it as it is set here
+	uint32_t sid = 0xffffffffu;
+	const float *mrow = nullptr;
+	float bnx = nx, bny = ny, bnz = nz;
+	bool live = p.mode != TP_NONE && g1.w > 0.f && finite3(cc), moved = false, deformed = false;
+	float p0x = 0.f, p0y = 0.f, p0z = 0.f, q0x = 0.f, q0y = 0.f, q0z = 0.f, e1x = 0.f, e1y = 0.f, e1z = 0.f, e2x = 0.f, e2y = 0.f, e2z = 0.f;
+	float f1x = 0.f, f1y = 0.f, f1z = 0.f, f2x = 0.f, f2y = 0.f, f2z = 0.f, a11 = 0.f, a12 = 0.f, a22 = 0.f, det = 1.f;
+	if constexpr (MOTION >= 1) {
+		if (live) {
+			sid = mp.ids[i];
+			live = sid < mp.n_shapes;
+			if (live) {
+				const uint32_t *row = mp.table + (size_t)sid * SRT_MOTION_WORDS;
+				const uint32_t state = row[0];
+				mrow = reinterpret_cast<const float *>(row + 1);
+				live = state != SRT_MOTION_NO_HISTORY;
+				moved = state == SRT_MOTION_MOVED;
+				if (moved) {
+					const float *b = mrow + 12;
+					const float tx = (b[0] * nx + b[1] * ny) + b[2] * nz, ty = (b[3] * nx + b[4] * ny) + b[5] * nz, tz = (b[6] * nx + b[7] * ny) + b[8] * nz;
+					const float len = sqrtf((tx * tx + ty * ty) + tz * tz);
+					live = len > 0.f && __builtin_isfinite(len);
+					bnx = tx / len, bny = ty / len, bnz = tz / len;
+				}
+				if constexpr (MOTION == 2) {
+					// a deformed model: the pixel's triangle as it stands now (P) and as it stood in the history frame (Q). It projects
+					// and takes only its own shape's taps, as a moved shape does; N_h = normalise((nu f1 + nv f2) + c gh)
+					deformed = state == SRT_MOTION_DEFORMED;
+					if (deformed) {
+						moved = true;
+						const uint32_t tri = vp.tris[i];
+						live = tri < vp.first[sid + 1] - vp.first[sid]; // (0xffffffff: no triangle)
+						if (live) {
+							const float *P = vp.rows + (size_t)(row[1] + tri) * 9, *Q = vp.h_rows + (size_t)(row[1] + tri) * 9;
+							p0x = P[0], p0y = P[1], p0z = P[2];
+							q0x = Q[0], q0y = Q[1], q0z = Q[2];
+							e1x = P[3] - p0x, e1y = P[4] - p0y, e1z = P[5] - p0z;
+							e2x = P[6] - p0x, e2y = P[7] - p0y, e2z = P[8] - p0z;
+							f1x = Q[3] - q0x, f1y = Q[4] - q0y, f1z = Q[5] - q0z;
+							f2x = Q[6] - q0x, f2y = Q[7] - q0y, f2z = Q[8] - q0z;
+							a11 = (e1x * e1x + e1y * e1y) + e1z * e1z;
+							a12 = (e1x * e2x + e1y * e2y) + e1z * e2z;
+							a22 = (e2x * e2x + e2y * e2y) + e2z * e2z;
+							det = a11 * a22 - a12 * a12;
+							const float cx = e1y * e2z - e1z * e2y, cy = e1z * e2x - e1x * e2z, cz = e1x * e2y - e1y * e2x;
+							const float hx = f1y * f2z - f1z * f2y, hy = f1z * f2x - f1x * f2z, hz = f1x * f2y - f1y * f2x;
+							const float lc = sqrtf((cx * cx + cy * cy) + cz * cz), lh = sqrtf((hx * hx + hy * hy) + hz * hz);
+							live = det > 0.f && __builtin_isfinite(det) && lc > 0.f && __builtin_isfinite(lc) && lh > 0.f && __builtin_isfinite(lh);
+							const float ne1 = (nx * e1x + ny * e1y) + nz * e1z, ne2 = (nx * e2x + ny * e2y) + nz * e2z;
+							const float nu = (a22 * ne1 - a12 * ne2) / det, nv = (a11 * ne2 - a12 * ne1) / det;
+							const float cn = (nx * (cx / lc) + ny * (cy / lc)) + nz * (cz / lc);
+							const float tx = (nu * f1x + nv * f2x) + cn * (hx / lh), ty = (nu * f1y + nv * f2y) + cn * (hy / lh), tz = (nu * f1z + nv * f2z) + cn * (hz / lh);
+							const float len = sqrtf((tx * tx + ty * ty) + tz * tz);
+							live = live && len > 0.f && __builtin_isfinite(len);
+							bnx = tx / len, bny = ty / len, bnz = tz / len;
+						}
+					}
+				}
+			}
+		}
+	}
+	const bool identity = p.mode == TP_IDENTITY && !moved;
+	if (live) {
+		float D = z;
+		int x0 = x, y0 = y;
+		float ax = 0.f, ay = 0.f;
+		bool any = true;
+		if (p.mode == TP_PROJECT || moved) {
+			// the camera ray through the pixel's centre (trace_body.inc CAMERA with 0.5 for the jitter; its division through the
+			// host's reciprocal is the IEEE quotient)
+			const float ndc_x = ((float)x + 0.5f) / p.f_width, ndc_y = ((float)y + 0.5f) / p.f_height;
+			const float sx = ((2.f * ndc_x - 1.f) * p.aspect) * p.fov;
+			const float sy = (1.f - 2.f * ndc_y) * p.fov;
+			const float rx = ((p.c0[0] * sx + p.c1[0] * sy) + p.c2[0] * -1.0f) + p.cam[0] * 0.0f;
+			const float ry = ((p.c0[1] * sx + p.c1[1] * sy) + p.c2[1] * -1.0f) + p.cam[1] * 0.0f;
+			const float rz = ((p.c0[2] * sx + p.c1[2] * sy) + p.c2[2] * -1.0f) + p.cam[2] * 0.0f;
+			const float rs = dm_rsqrtf(rx * rx + ry * ry + rz * rz);
+			const float dx = rx * rs, dy = ry * rs, dz = rz * rs;
+			float wx = p.cam[0] + z * dx, wy = p.cam[1] + z * dy, wz = p.cam[2] + z * dz;
+			bool xh_ok = true;
+			if (deformed) { // the same barycentric place on the history's triangle (the affine map of the triangle's plane)
+				const float ddx = wx - p0x, ddy = wy - p0y, ddz = wz - p0z;
+				const float de1 = (ddx * e1x + ddy * e1y) + ddz * e1z, de2 = (ddx * e2x + ddy * e2y) + ddz * e2z;
+				const float u = (a22 * de1 - a12 * de2) / det, v2 = (a11 * de2 - a12 * de1) / det;
+				wx = (q0x + u * f1x) + v2 * f2x, wy = (q0y + u * f1y) + v2 * f2y, wz = (q0z + u * f1z) + v2 * f2z;
+				xh_ok = __builtin_isfinite(wx) && __builtin_isfinite(wy) && __builtin_isfinite(wz);
+			} else if (moved) {
+				const float hx = ((mrow[0] * wx + mrow[1] * wy) + mrow[2] * wz) + mrow[3];
+				const float hy = ((mrow[4] * wx + mrow[5] * wy) + mrow[6] * wz) + mrow[7];
+				const float hz = ((mrow[8] * wx + mrow[9] * wy) + mrow[10] * wz) + mrow[11];
+				wx = hx, wy = hy, wz = hz;
+			}
+			const float ex = wx - p.cam_h[0], ey = wy - p.cam_h[1], ez = wz - p.cam_h[2];
+			D = sqrtf(ex * ex + ey * ey + ez * ez);
+			const float vx = (p.rinv[0] * ex + p.rinv[1] * ey) + p.rinv[2] * ez;
+			const float vy = (p.rinv[3] * ex + p.rinv[4] * ey) + p.rinv[5] * ez;
+			const float vz = (p.rinv[6] * ex + p.rinv[7] * ey) + p.rinv[8] * ez;
+			const float qx = vx / -vz, qy = vy / -vz;
+			const float fx = ((qx / (p.aspect_h * p.fov_h) + 1.f) / 2.f) * p.f_width - 0.5f;
+			const float fy = ((1.f - qy / p.fov_h) / 2.f) * p.f_height - 0.5f;
+			// in front of the history camera, and a 2x2 that touches the image (this also keeps the conversions in range)
+			any = vz < 0.f && fx > -1.f && fx < p.f_width && fy > -1.f && fy < p.f_height;
+			any = any && xh_ok;
+			if (any) {
+				const float flx = floorf(fx), fly = floorf(fy);
+				x0 = (int)flx, y0 = (int)fly;
+				ax = fx - flx, ay = fy - fly;
+			}
+		}
+		if (any) {
+			for (int k = 0; k < 4; k++) {
+				const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
+				const float w = (k & 1 ? ax : 1.f - ax) * (k >> 1 ? ay : 1.f - ay);
+				if (identity && k) break;
+				if (qx < 0 || qx >= p.width || qy < 0 || qy >= p.height) continue;
+				const uint32_t j = (uint32_t)qy * (uint32_t)p.width + (uint32_t)qx;
+				const float4 hg1 = p.h_guide[2 * j + 1];
+				const float4 hc = p.h_cc[j];
+				if (!(hg1.w > 0.f) || !finite3(hc)) continue;
+				// a moved shape's tap must show that shape; a static one's must not show a shape that has left. (hs at this level and the
+				// test on a bare `if constexpr`: a `continue` out of a braced block costs these kernels 18 to 61 instructions)
+				[[maybe_unused]] uint32_t hs = 0xffffffffu;
+				if constexpr (MOTION >= 1) hs = mp.h_ids[j];
+				if constexpr (MOTION >= 1)
+					if (moved ? hs != sid : (hs < mp.n_shapes && mp.table[(size_t)hs * SRT_MOTION_WORDS] != SRT_MOTION_STATIC)) continue;
+				const float4 hg0 = p.h_guide[2 * j];
+				if (!(bnx * hg0.x + bny * hg0.y + bnz * hg0.z >= p.normal_threshold)) continue;
+				if (!(fabsf(hg0.w - D) <= p.depth_threshold * D)) continue;
+				const float2 hm = p.h_m[j];
+				sw += w;
+				if constexpr (ILLUM) {
+					// r = D_p / D_h per channel, rl = lum(D_p) / lum(D_h); a partly covered pixel or tap stays in colour (it holds sky
+					// light no albedo scaled), and so does the identity tap: the pixel itself
+					float rr = 1.f, rg = 1.f, rb = 1.f, rl = 1.f;
+					if (full_p && hg1.w == 1.0f && !identity) {
+						const float dhr = fmaxf(hg1.x, SRT_DEMOD_EPS), dhg = fmaxf(hg1.y, SRT_DEMOD_EPS), dhb = fmaxf(hg1.z, SRT_DEMOD_EPS);
+						rr = dpr / dhr, rg = dpg / dhg, rb = dpb / dhb;
+						rl = lp / lum(dhr, dhg, dhb);
+					}
+					sr += w * (hc.x * rr), sg += w * (hc.y * rg), sb += w * (hc.z * rb);
+					sh += w * hc.w;
+					s1 += w * (hm.x * rl), s2 += w * ((hm.y * rl) * rl);
+				} else {
+					sr += w * hc.x, sg += w * hc.y, sb += w * hc.z;
+					sh += w * hc.w;
+					s1 += w * hm.x, s2 += w * hm.y;
+				}
+			}
+		}
+	}
+
+	// ---- integration ----
+	float h = 0.f;
+	if (sw >= 0.01f) h = fminf(sh / sw, p.limit);
+	float4 o = make_float4(cc.x, cc.y, cc.z, v);
+	float m1 = l, m2 = m2c, n = p.P;
+	if (h > 0.f) {
+		n = p.P + h;
+		float hr = sr / sw, hgc = sg / sw, hb = sb / sw, h1 = s1 / sw, h2 = s2 / sw;
+		if constexpr (CLAMP) {
+			// the history colour x_h is complete here (gathered, and rescaled under ILLUM): each channel into
+			// [mu - gamma sigma, mu + gamma sigma] of this pixel's bounds (sum of weights 0: no clamp). By comparisons, so a NaN on
+			// either side moves nothing; when no channel moved every value below is what it is without the clamp
+			const float4 b0 = cp.bounds[i];
+			if (b0.w > 0.f) {
+				const float4 b1 = cp.bounds[cp.num_pixels + i];
+				const float er = cp.gamma * b1.x, eg = cp.gamma * b1.y, eb = cp.gamma * b1.z;
+				const float lor = b0.x - er, hir = b0.x + er, log_ = b0.y - eg, hig = b0.y + eg, lob = b0.z - eb, hib = b0.z + eb;
+				bool mv = false;
+				if (hr < lor) hr = lor, mv = true;
+				else if (hr > hir) hr = hir, mv = true;
+				if (hgc < log_) hgc = log_, mv = true;
+				else if (hgc > hig) hgc = hig, mv = true;
+				if (hb < lob) hb = lob, mv = true;
+				else if (hb > hib) hb = hib, mv = true;
+				if (mv) { // the moments follow the colour and keep their variance
+					float hv = h2 - h1 * h1;
+					hv = hv > 0.f ? hv : 0.f;
+					h1 = lum(hr, hgc, hb);
+					h2 = hv + h1 * h1;
+				}
+			}
+		}
+		o.x = (p.P * cc.x + h * hr) / n;
+		o.y = (p.P * cc.y + h * hgc) / n;
+		o.z = (p.P * cc.z + h * hb) / n;
+		m1 = (p.P * l + h * h1) / n;
+		m2 = (p.P * m2c + h * h2) / n;
+		float V = m2 - m1 * m1;
+		V = V > 0.f ? V : 0.f;
+		V = V / n;
+		o.w = __builtin_isfinite(V) ? V : 0.f;
+	}
+	p.o_cc[i] = make_float4(o.x, o.y, o.z, fminf(n, p.limit));
+	p.o_m[i] = make_float2(m1, m2);
+	p.o_guide[2 * i] = g0;
+	p.o_guide[2 * i + 1] = g1;
+	if (p.out) p.out[i] = o;
+	if (p.argb) p.argb[i] = tonemap(o.x, o.y, o.z);
 }
-#undef SRT_TEMPORAL_ILLUM
 
 // ---- the history clamp (srt_set_denoise_history_clamp; include/srt_abi.h has the definition, tests/history_clamp_ref.py restates
 // it): one launch before the set-up makes per-pixel colour bounds of the frame, and the set-up's clamping form pulls the
@@ -145,12 +373,6 @@ struct BoundsParams {
 	const float4 *normal_depth;
 	const float4 *albedo_hits;
 	float4 *bounds; // plane 0 {mu.rgb, sum of weights (0: do not clamp)}, plane 1 {sigma.rgb, counting taps}
-};
-
-struct ClampParams { // the last argument of the *_clamp_kernel set-ups
-	const float4 *bounds;
-	uint32_t num_pixels;
-	float gamma;
 };
 
 enum { TB_R = 3, TB_HALO = 16 + 2 * TB_R, TB_ROW = 32 }; // the 22x22 halo tile, rows of 32 float4
@@ -176,7 +398,7 @@ __global__ __launch_bounds__(256) void srt_temporal_bounds_kernel(const BoundsPa
 		const int qx = x0 - TB_R + hx, qy = y0 - TB_R + hy;
 		float4 cc = make_float4(0.f, 0.f, 0.f, 0.f);
 		if (qx >= 0 && qx < p.width && qy >= 0 && qy < p.height) {
-			// the set-up's expressions (temporal_body.inc): colour, cov = hits / F, N, Z, A
+			// the set-up's expressions (srt_temporal_kernel): colour, cov = hits / F, N, Z, A
 			const uint32_t j = (uint32_t)qy * (uint32_t)p.width + (uint32_t)qx;
 			const float4 c = p.canvas[j], ah = p.albedo_hits[j];
 			cc = make_float4(c.x / p.T, c.y / p.T, c.z / p.T, 0.f);
@@ -245,49 +467,6 @@ __global__ __launch_bounds__(256) void srt_temporal_bounds_kernel(const BoundsPa
 	p.bounds[i] = o0;
 	p.bounds[p.num_pixels + i] = o1;
 }
-
-// The six set-ups that clamp: the same bodies with SRT_TEMPORAL_CLAMP 1 and the bounds as their last argument. The host launches
-// one of these in place of its twin above when the clamp is on and a history exists. Instantiations, not a flag in fewer
-// kernels: the twins above keep their instructions, and a clamping set-up pays no branch for the other variants.
-#define SRT_TEMPORAL_CLAMP 1
-__global__ __launch_bounds__(256) void srt_temporal_setup_clamp_kernel(const TemporalParams p, const ClampParams cp) {
-#define SRT_TEMPORAL_MOTION 0
-#include "temporal_body.inc"
-#undef SRT_TEMPORAL_MOTION
-}
-
-__global__ __launch_bounds__(256) void srt_temporal_motion_clamp_kernel(const TemporalParams p, const MotionParams mp, const ClampParams cp) {
-#define SRT_TEMPORAL_MOTION 1
-#include "temporal_body.inc"
-#undef SRT_TEMPORAL_MOTION
-}
-
-__global__ __launch_bounds__(256) void srt_temporal_deform_clamp_kernel(const TemporalParams p, const MotionParams mp, const VertexParams vp, const ClampParams cp) {
-#define SRT_TEMPORAL_MOTION 2
-#include "temporal_body.inc"
-#undef SRT_TEMPORAL_MOTION
-}
-
-#define SRT_TEMPORAL_ILLUM 1
-__global__ __launch_bounds__(256) void srt_temporal_setup_illum_clamp_kernel(const TemporalParams p, const ClampParams cp) {
-#define SRT_TEMPORAL_MOTION 0
-#include "temporal_body.inc"
-#undef SRT_TEMPORAL_MOTION
-}
-
-__global__ __launch_bounds__(256) void srt_temporal_motion_illum_clamp_kernel(const TemporalParams p, const MotionParams mp, const ClampParams cp) {
-#define SRT_TEMPORAL_MOTION 1
-#include "temporal_body.inc"
-#undef SRT_TEMPORAL_MOTION
-}
-
-__global__ __launch_bounds__(256) void srt_temporal_deform_illum_clamp_kernel(const TemporalParams p, const MotionParams mp, const VertexParams vp, const ClampParams cp) {
-#define SRT_TEMPORAL_MOTION 2
-#include "temporal_body.inc"
-#undef SRT_TEMPORAL_MOTION
-}
-#undef SRT_TEMPORAL_ILLUM
-#undef SRT_TEMPORAL_CLAMP
 
 // The world-vertex table of a scene: blockIdx.y = shape (models only), row first[shape] + j = triangle j's P0, P1, P2 in the
 // pre-pass's expressions (frame.hip srt_prepass_kernel: mat_by_vec(transform, pos, 1.0f)), so the rows are the tracer's world
@@ -464,9 +643,9 @@ bool model_row(const srt_model &h, const srt_model &c, uint32_t *row) {
 // the rules of include/srt_abi.h: false = drop the history; else `table` gets SRT_MOTION_WORDS words per shape
 // `deform` (per-triangle motion): the triangle arrays need only have the same count; a model whose range differs in a byte
 // is DEFORMED {state, its first row in the vertex tables, zeros}, bytes outside every range are not compared
-bool motion_table(const SceneView &h, const SceneView &c, uint32_t *table, bool *any_moved, bool deform = false, bool *any_deformed = nullptr) {
+bool motion_table(const SceneView &h, const SceneView &c, uint32_t *table, bool *any_moved, bool deform, bool *any_deformed) {
 	*any_moved = false;
-	if (any_deformed) *any_deformed = false;
+	*any_deformed = false;
 	if (h.n_shapes != c.n_shapes || h.tri_bytes != c.tri_bytes || h.mat_bytes != c.mat_bytes) return false;
 	if (memcmp(h.scene, c.scene, sizeof(srt_scene_data)) != 0) return false;
 	if (h.mat_bytes && memcmp(h.mats, c.mats, h.mat_bytes) != 0) return false;
@@ -497,7 +676,7 @@ bool motion_table(const SceneView &h, const SceneView &c, uint32_t *table, bool 
 				row[0] = SRT_MOTION_DEFORMED;
 				row[1] = (uint32_t)row0;
 				*any_moved = true;
-				if (any_deformed) *any_deformed = true;
+				*any_deformed = true;
 				continue;
 			}
 		}
@@ -553,6 +732,20 @@ int vertex_layout(srt_tracer *t, const std::vector<uint8_t> &bytes) {
 	return SRT_OK;
 }
 
+// one instantiation's launch: of the four structs it passes on those its kernel takes
+template <int MOTION, bool ILLUM, bool CLAMP>
+void launch_variant(hipStream_t stream, dim3 grid, const TemporalParams &p, const MotionParams &mp, const VertexParams &vp, const ClampParams &cp) {
+	const SetupArgs<MOTION, CLAMP> a = {p, mp, vp, cp};
+	hipLaunchKernelGGL((srt_temporal_kernel<MOTION, ILLUM, CLAMP>), grid, dim3(256), 0, stream, a);
+}
+
+using SetupLaunch = decltype(&launch_variant<0, false, false>);
+const SetupLaunch setup_launch[3][2][2] = { // [motion_level][illum][clamp]
+	{{launch_variant<0, false, false>, launch_variant<0, false, true>}, {launch_variant<0, true, false>, launch_variant<0, true, true>}},
+	{{launch_variant<1, false, false>, launch_variant<1, false, true>}, {launch_variant<1, true, false>, launch_variant<1, true, true>}},
+	{{launch_variant<2, false, false>, launch_variant<2, false, true>}, {launch_variant<2, true, false>, launch_variant<2, true, true>}},
+};
+
 // the temporal set-up into the staging set (and `col` / argb when given)
 int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 	const size_t px = full_pixels(t);
@@ -599,8 +792,25 @@ int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 	p.out = col;
 	p.argb = argb;
 	const dim3 grid((unsigned)((t->width + 15) / 16), (unsigned)((t->height + 15) / 16));
+	// a deformed model: its pixels look their triangles up in the two vertex tables
+	const int motion_level = !motion ? 0 : (t->vm_on && t->om_any_deformed) ? 2 : 1;
 	const bool illum = t->tp_illum; // the same variant for a filter's set-up and for a clear's commit
 	const bool clamp = t->tp_clamp > 0.f && t->tp_valid; // the history clamp: without a history nothing new is launched
+	MotionParams mp = {};
+	VertexParams vp = {};
+	ClampParams cp = {};
+	if (motion_level >= 1) {
+		mp.ids = t->om_ids[t->om_cur].ptr;
+		mp.h_ids = t->om_ids[1 - t->om_cur].ptr;
+		mp.table = t->om_table_dev.ptr;
+		mp.n_shapes = (uint32_t)(t->om_table.size() / SRT_MOTION_WORDS);
+	}
+	if (motion_level == 2) {
+		vp.tris = t->vm_tri[t->om_cur].ptr;
+		vp.rows = t->vm_rows[t->om_cur].ptr;
+		vp.h_rows = t->vm_rows[1 - t->om_cur].ptr;
+		vp.first = t->vm_first_dev.ptr;
+	}
 	if (clamp) {
 		BoundsParams bp;
 		bp.width = t->width;
@@ -618,56 +828,11 @@ int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 		hipLaunchKernelGGL(srt_temporal_bounds_kernel, grid, dim3(256), 0, t->stream, bp);
 		SRT_HIP(t, hipGetLastError());
 		t->tp_bounds_ran = true;
-		ClampParams cp;
 		cp.bounds = bp.bounds;
 		cp.num_pixels = bp.num_pixels;
 		cp.gamma = t->tp_clamp;
-		if (motion) {
-			MotionParams mp;
-			mp.ids = t->om_ids[t->om_cur].ptr;
-			mp.h_ids = t->om_ids[1 - t->om_cur].ptr;
-			mp.table = t->om_table_dev.ptr;
-			mp.n_shapes = (uint32_t)(t->om_table.size() / SRT_MOTION_WORDS);
-			if (t->vm_on && t->om_any_deformed) {
-				VertexParams vp;
-				vp.tris = t->vm_tri[t->om_cur].ptr;
-				vp.rows = t->vm_rows[t->om_cur].ptr;
-				vp.h_rows = t->vm_rows[1 - t->om_cur].ptr;
-				vp.first = t->vm_first_dev.ptr;
-				if (illum) hipLaunchKernelGGL(srt_temporal_deform_illum_clamp_kernel, grid, dim3(256), 0, t->stream, p, mp, vp, cp);
-				else hipLaunchKernelGGL(srt_temporal_deform_clamp_kernel, grid, dim3(256), 0, t->stream, p, mp, vp, cp);
-			} else if (illum)
-				hipLaunchKernelGGL(srt_temporal_motion_illum_clamp_kernel, grid, dim3(256), 0, t->stream, p, mp, cp);
-			else
-				hipLaunchKernelGGL(srt_temporal_motion_clamp_kernel, grid, dim3(256), 0, t->stream, p, mp, cp);
-		} else if (illum) {
-			hipLaunchKernelGGL(srt_temporal_setup_illum_clamp_kernel, grid, dim3(256), 0, t->stream, p, cp);
-		} else {
-			hipLaunchKernelGGL(srt_temporal_setup_clamp_kernel, grid, dim3(256), 0, t->stream, p, cp);
-		}
-	} else if (motion) {
-		MotionParams mp;
-		mp.ids = t->om_ids[t->om_cur].ptr;
-		mp.h_ids = t->om_ids[1 - t->om_cur].ptr;
-		mp.table = t->om_table_dev.ptr;
-		mp.n_shapes = (uint32_t)(t->om_table.size() / SRT_MOTION_WORDS);
-		if (t->vm_on && t->om_any_deformed) { // a deformed model: its pixels look their triangles up in the two vertex tables
-			VertexParams vp;
-			vp.tris = t->vm_tri[t->om_cur].ptr;
-			vp.rows = t->vm_rows[t->om_cur].ptr;
-			vp.h_rows = t->vm_rows[1 - t->om_cur].ptr;
-			vp.first = t->vm_first_dev.ptr;
-			if (illum) hipLaunchKernelGGL(srt_temporal_deform_illum_kernel, grid, dim3(256), 0, t->stream, p, mp, vp);
-			else hipLaunchKernelGGL(srt_temporal_deform_kernel, grid, dim3(256), 0, t->stream, p, mp, vp);
-		} else if (illum)
-			hipLaunchKernelGGL(srt_temporal_motion_illum_kernel, grid, dim3(256), 0, t->stream, p, mp);
-		else
-			hipLaunchKernelGGL(srt_temporal_motion_kernel, grid, dim3(256), 0, t->stream, p, mp);
-	} else if (illum) {
-		hipLaunchKernelGGL(srt_temporal_setup_illum_kernel, grid, dim3(256), 0, t->stream, p);
-	} else {
-		hipLaunchKernelGGL(srt_temporal_setup_kernel, grid, dim3(256), 0, t->stream, p);
 	}
+	setup_launch[motion_level][illum][clamp](t->stream, grid, p, mp, vp, cp);
 	SRT_HIP(t, hipGetLastError());
 	t->last_setup_illum = illum;
 	t->last_setup_clamp = clamp;
@@ -910,31 +1075,11 @@ int srt_read_denoise_motion(srt_tracer *t, uint32_t *table, size_t capacity_shap
 	return SRT_OK;
 }
 
-int srt_motion_table_host(const srt_shape *h_shapes, size_t h_n_shapes, const srt_triangle *h_triangles, size_t h_n_triangles,
-                          const srt_material *h_materials, size_t h_n_materials, const srt_scene_data *h_scene,
-                          const srt_shape *c_shapes, size_t c_n_shapes, const srt_triangle *c_triangles, size_t c_n_triangles,
-                          const srt_material *c_materials, size_t c_n_materials, const srt_scene_data *c_scene, uint32_t *table, int *keep) {
-	if (!h_scene || !c_scene || !keep || (c_n_shapes && !table)) return SRT_ERR_INVALID;
-	if ((h_n_shapes && !h_shapes) || (c_n_shapes && !c_shapes) || (h_n_triangles && !h_triangles) || (c_n_triangles && !c_triangles) ||
-	    (h_n_materials && !h_materials) || (c_n_materials && !c_materials))
-		return SRT_ERR_INVALID;
-	const SceneView h = {h_shapes, h_n_shapes, h_triangles, h_materials, h_scene, h_n_triangles * sizeof(srt_triangle), h_n_materials * sizeof(srt_material)};
-	const SceneView c = {c_shapes, c_n_shapes, c_triangles, c_materials, c_scene, c_n_triangles * sizeof(srt_triangle), c_n_materials * sizeof(srt_material)};
-	bool any = false;
-	try {
-		std::vector<uint32_t> rows(c_n_shapes * SRT_MOTION_WORDS);
-		*keep = motion_table(h, c, rows.data(), &any) ? 1 : 0;
-		if (*keep && !rows.empty()) memcpy(table, rows.data(), rows.size() * 4);
-	} catch (...) {
-		return SRT_ERR_INVALID;
-	}
-	return SRT_OK;
-}
-
-int srt_motion_table_deform_host(const srt_shape *h_shapes, size_t h_n_shapes, const srt_triangle *h_triangles, size_t h_n_triangles,
-                                 const srt_material *h_materials, size_t h_n_materials, const srt_scene_data *h_scene,
-                                 const srt_shape *c_shapes, size_t c_n_shapes, const srt_triangle *c_triangles, size_t c_n_triangles,
-                                 const srt_material *c_materials, size_t c_n_materials, const srt_scene_data *c_scene, uint32_t *table, int *keep) {
+// srt_motion_table_host (deform false) and srt_motion_table_deform_host (true)
+static int motion_table_host(bool deform, const srt_shape *h_shapes, size_t h_n_shapes, const srt_triangle *h_triangles, size_t h_n_triangles,
+                             const srt_material *h_materials, size_t h_n_materials, const srt_scene_data *h_scene,
+                             const srt_shape *c_shapes, size_t c_n_shapes, const srt_triangle *c_triangles, size_t c_n_triangles,
+                             const srt_material *c_materials, size_t c_n_materials, const srt_scene_data *c_scene, uint32_t *table, int *keep) {
 	if (!h_scene || !c_scene || !keep || (c_n_shapes && !table)) return SRT_ERR_INVALID;
 	if ((h_n_shapes && !h_shapes) || (c_n_shapes && !c_shapes) || (h_n_triangles && !h_triangles) || (c_n_triangles && !c_triangles) ||
 	    (h_n_materials && !h_materials) || (c_n_materials && !c_materials))
@@ -944,13 +1089,30 @@ int srt_motion_table_deform_host(const srt_shape *h_shapes, size_t h_n_shapes, c
 	bool any = false, any_deformed = false;
 	try {
 		std::vector<uint32_t> rows(c_n_shapes * SRT_MOTION_WORDS);
-		*keep = motion_table(h, c, rows.data(), &any, true, &any_deformed) ? 1 : 0;
+		*keep = motion_table(h, c, rows.data(), &any, deform, &any_deformed) ? 1 : 0;
 		if (*keep && !rows.empty()) memcpy(table, rows.data(), rows.size() * 4);
 	} catch (...) {
 		return SRT_ERR_INVALID;
 	}
 	return SRT_OK;
 }
+
+int srt_motion_table_host(const srt_shape *h_shapes, size_t h_n_shapes, const srt_triangle *h_triangles, size_t h_n_triangles,
+                          const srt_material *h_materials, size_t h_n_materials, const srt_scene_data *h_scene,
+                          const srt_shape *c_shapes, size_t c_n_shapes, const srt_triangle *c_triangles, size_t c_n_triangles,
+                          const srt_material *c_materials, size_t c_n_materials, const srt_scene_data *c_scene, uint32_t *table, int *keep) {
+	return motion_table_host(false, h_shapes, h_n_shapes, h_triangles, h_n_triangles, h_materials, h_n_materials, h_scene,
+	                         c_shapes, c_n_shapes, c_triangles, c_n_triangles, c_materials, c_n_materials, c_scene, table, keep);
+}
+
+int srt_motion_table_deform_host(const srt_shape *h_shapes, size_t h_n_shapes, const srt_triangle *h_triangles, size_t h_n_triangles,
+                                 const srt_material *h_materials, size_t h_n_materials, const srt_scene_data *h_scene,
+                                 const srt_shape *c_shapes, size_t c_n_shapes, const srt_triangle *c_triangles, size_t c_n_triangles,
+                                 const srt_material *c_materials, size_t c_n_materials, const srt_scene_data *c_scene, uint32_t *table, int *keep) {
+	return motion_table_host(true, h_shapes, h_n_shapes, h_triangles, h_n_triangles, h_materials, h_n_materials, h_scene,
+	                         c_shapes, c_n_shapes, c_triangles, c_n_triangles, c_materials, c_n_materials, c_scene, table, keep);
+}
+
 
 int srt_set_denoise_vertex_motion(srt_tracer *t, int enable) {
 	if (!t) return SRT_ERR_INVALID;

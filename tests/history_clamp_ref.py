@@ -1,5 +1,5 @@
 """The history clamp (include/srt_abi.h srt_set_denoise_history_clamp; simple-raytracer_amd/csrc/temporal.hip
-srt_temporal_bounds_kernel and temporal_body.inc with SRT_TEMPORAL_CLAMP 1) in numpy, on top of
+srt_temporal_bounds_kernel and srt_temporal_kernel with CLAMP true) in numpy, on top of
 tests/history_illumination_ref.py's reprojection (the superset of the set-up kernels) and tests/temporal_ref.py's integration.
 
     bounds   per pixel p with cov > 0 and a finite colour, over its 7x7 taps q (dy outer, dx inner) that are inside the image,

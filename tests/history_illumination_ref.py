@@ -1,5 +1,5 @@
 """The temporal set-up with the history reprojected as illumination (include/srt_abi.h srt_set_denoise_history_illumination;
-simple-raytracer_amd/csrc/temporal_body.inc with SRT_TEMPORAL_ILLUM 1) in numpy: the tap loop of vertex_motion_ref.reproject --
+srt_temporal_kernel of simple-raytracer_amd/csrc/temporal.hip with ILLUM true) in numpy: the tap loop of vertex_motion_ref.reproject --
 the superset of the three kernels; without a table it is temporal_ref.reproject's -- with the rule
 
     D = max(A, SRT_DEMOD_EPS) per channel (fmaxf: a NaN channel gives eps), L = lum(D)
@@ -38,8 +38,8 @@ def ratios(Ap, cov_p, Ah, cov_h):
 def reproject(cur, hist, cam_rd, normal_threshold=0.9, depth_threshold=0.05, ids=None, table=None, tri_ids=None, rows=None, h_rows=None,
               rescale=True):
     """-> temporal_ref.reproject's dict (h, c, m1, m2, taps, borderline; with a table also state) and 'scaled'. table None:
-    srt_temporal_setup_illum_kernel; a table: srt_temporal_motion_illum_kernel; a table with DEFORMED rows and tri_ids, rows,
-    h_rows: srt_temporal_deform_illum_kernel (arguments as vertex_motion_ref.reproject)."""
+    srt_temporal_kernel<0, true, ...>; a table: srt_temporal_kernel<1, true, ...>; a table with DEFORMED rows and tri_ids, rows,
+    h_rows: srt_temporal_kernel<2, true, ...> (arguments as vertex_motion_ref.reproject)."""
     height, width = cur["Z"].shape
     out = dict(h=np.zeros((height, width), F32), c=np.zeros((height, width, 3), F32), m1=np.zeros((height, width), F32),
                m2=np.zeros((height, width), F32), taps=np.zeros((height, width), np.int32), borderline=np.zeros((height, width), bool),

@@ -1,4 +1,4 @@
-"""The moved-camera cases of the temporal set-up (TP_PROJECT in simple-raytracer_amd/csrc/temporal_body.inc) that
+"""The moved-camera cases of the temporal set-up (TP_PROJECT in srt_temporal_kernel of simple-raytracer_amd/csrc/temporal.hip) that
 tests/test_temporal_cases.py checks on the CPU and tests/test_gpu_denoise_temporal_cases.py runs on the device, and the
 oracle's feature pass as a frame of tests/temporal_ref.py. A plain module.
 

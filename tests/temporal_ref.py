@@ -124,7 +124,7 @@ def reproject(cur, hist, cam_rd, normal_threshold=0.9, depth_threshold=0.05, ids
     """-> dict h, c (h, w, 3), m1, m2 (the weight-normalised history; h = 0 where there is none), taps (h, w) = the number of
     counted taps, borderline (h, w) bool. `hist` is Tracer.read_denoise_history().
 
-    Without a table this is srt_temporal_setup_kernel; with one srt_temporal_motion_kernel (temporal_body.inc with
+    Without a table this is srt_temporal_kernel<0, ...>; with one srt_temporal_kernel<1, ...> (csrc/temporal.hip with
     SRT_TEMPORAL_MOTION 1): ids (h, w) uint32 are the frame's shape indices, hist['ids'] the history frame's, table a dict
     state (n,), A (n, 3, 4), B (n, 3, 3) float32 (motion_ref.scene_table); the result also holds 'state' (h, w), each
     pixel's shape state (-1: no shape)."""

@@ -1,4 +1,4 @@
-"""GPU: the temporal set-up under a moved camera (TP_PROJECT of csrc/temporal_body.inc) at its edges -- the cases of
+"""GPU: the temporal set-up under a moved camera (TP_PROJECT of srt_temporal_kernel, csrc/temporal.hip) at its edges -- the cases of
 tests/temporal_cases.py (zoom, aspect, roll, large turns, an about-face, scaled, mirrored, sheared and singular cameras) on
 whole and ragged frames, two thresholds pairs and three scenes, the cap at history_limit under projection, frames of two
 dispatches and of another sample count than their history, a history with non-finite colours, and the moved kernel.
@@ -100,7 +100,7 @@ def two_frames(t, hist_cam, cur_cam, tp, label, dispatches=1, spp=2, steps=None)
     if motion:
         t.update_scene(M.move_shapes(shapes, tris, steps, 1), tris, mats)
         table = t.read_denoise_motion()
-        assert table["any_moved"]  # srt_temporal_motion_kernel runs
+        assert table["any_moved"]  # srt_temporal_kernel<1, ...> runs
     else:
         t.update_scene(*t.scene)
     assert t.read_denoise_history()["valid"]

@@ -16,7 +16,7 @@ The expression is written out three times in the device code; which test reaches
                                                          denoise_ref.tonemap(canvas / ticks) and the plain resolve's bytes
     srt_denoise_atrous_kernel's last pass                test_filtered_bytes_are_the_tonemap_of_the_filtered_floats[plain-*]
     srt_denoise_atrous_demod_kernel<true>                ...[demod-*]
-    srt_temporal_setup_kernel (csrc/temporal_body.inc)   ...[temporal-0]: iterations = 0 with a valid history
+    srt_temporal_kernel<0, false, false> (csrc/temporal.hip)   ...[temporal-0]: iterations = 0 with a valid history
 
 Sites that share one of these and are covered through it (read in csrc/srt_collect.hip and csrc/srt_abi.hip):
 srt_resolve_gathered calls srt_resolve_external; srt_group_render calls srt_resolve_gathered, or with the group's denoiser on

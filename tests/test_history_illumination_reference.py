@@ -102,7 +102,7 @@ def test_anchor_rescale_off_is_the_colour_path(oracle, name, w, h):
     arrays = scene("mixed")
     hist_f, hist_rd, hist_ids, cur, cur_rd, ids = case_frames(oracle, arrays, "mixed", name, w, h)
     hist = coloured_history(hist_f, hist_rd)
-    # without a table: srt_temporal_setup_kernel's restatement
+    # without a table: srt_temporal_kernel<0, false, false>'s restatement
     off = HI.reproject(cur, hist, cur_rd, rescale=False)
     same(off, TR.reproject(cur, hist, cur_rd))
     assert not off["scaled"].any()

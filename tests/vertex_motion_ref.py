@@ -1,6 +1,6 @@
 """Per-triangle motion of the denoiser's temporal stage (include/srt_abi.h srt_set_denoise_vertex_motion,
 simple-raytracer_amd/csrc/temporal.hip) in numpy: the keep rule and the table with the DEFORMED state, the world-vertex
-rows, the per-pixel map of a deformed triangle, and srt_temporal_deform_kernel's reprojection -- temporal_ref.reproject with
+rows, the per-pixel map of a deformed triangle, and srt_temporal_kernel<2, ...>'s reprojection -- temporal_ref.reproject with
 the deformed branch, branching only where SRT_TEMPORAL_MOTION == 2 does. Everything float32 in the kernel's order, unfused.
 """
 import numpy as np
@@ -135,9 +135,9 @@ def project_point(X, cam_h_rd, width, height):
     return fx.astype(F32), fy.astype(F32), Dist, v[2] < 0
 
 
-# ---- srt_temporal_deform_kernel ------------------------------------------------------------------------------------------
+# ---- srt_temporal_kernel<2, ...> ------------------------------------------------------------------------------------------
 def reproject(cur, hist, cam_rd, normal_threshold=0.9, depth_threshold=0.05, ids=None, table=None, tri_ids=None, rows=None, h_rows=None):
-    """temporal_ref.reproject with a table (srt_temporal_motion_kernel) and the DEFORMED state: tri_ids (h, w) uint32 the
+    """temporal_ref.reproject with a table (srt_temporal_kernel<1, ...>) and the DEFORMED state: tri_ids (h, w) uint32 the
     frame's triangle indices, rows / h_rows (n, 3, 3) the world-vertex tables of the frame and of the history,
     table['first_row'] each shape's first row. A DEFORMED pixel is a moved one whose map is deform_map of its triangle."""
     height, width = cur["Z"].shape
