@@ -754,6 +754,52 @@ int srt_group_last_setup_history_clamp(srt_group *g);
  * clamp has never run on this handle. */
 int srt_read_denoise_history_bounds(srt_tracer *t, float *mean_weight, float *sigma_taps);
 
+/* ---- the first a-trous pass fed back into the history (new; SVGF's feedback of the first wavelet iteration) --------------- */
+
+/* Opt-in, on top of srt_set_denoise_temporal. The temporal history holds the integrated colour as the set-up blends it: raw
+ * samples, as noisy as the frame. With the switch on the colour that enters the history is the output of the first a-trous
+ * pass, so every frame's history has already been averaged over an edge-aware 5x5. All float32, unfused, in the order written;
+ * tests/feedback_ref.py restates it.
+ *   when        the switch on and iterations K >= 1. K = 0: there is no pass and nothing changes, the plain resolve's bytes and
+ *               the switch-off history.
+ *   what        pass 1 (k = 0, step 1; after the set-up, and after the demodulate launch and the spatial-variance launch where
+ *               those are on) also stores its colour result into the rgb of the staging set's {colour, count} plane: x, y, z
+ *               alone, one three-dword store; the count .w is not touched. A pixel's colour is written only when the pixel
+ *               entered the filter branch (cov > 0 and a finite input), received weight (sum w > 0) and the three values to
+ *               be stored are finite. Every other pixel -- sky, a non-finite colour, no weight, a non-finite result -- keeps
+ *               the set-up's integrated colour bit for bit.
+ *   demodulation the value stored is colour, as the history always holds: I' D_p per channel with D_p = max(A_p,
+ *               SRT_DEMOD_EPS), the expression the last pass remodulates with; for K = 1 the pass is the last one and its
+ *               remodulated output is the value.
+ *   unchanged   the staged count, {m1, m2} (the moments stay unfiltered, as in SVGF: the next frame's variance comes from
+ *               them) and the guide; the set-up kernels, the bounds launch, the blend, history_limit, the commit's swap; the
+ *               filter's output image and ARGB bytes of the same frame. With the history clamp off the committed count,
+ *               moments and guide of every frame are therefore bit-equal to the switch-off ones; only the colour differs.
+ *   the clear   a clear with no filter since the last trace (or with a setter below since the filter) makes the staging set
+ *               itself. With the switch on and K >= 1 it runs the filter's front before the commit: the set-up into the
+ *               filter image, the demodulate launch if on, the spatial-variance launch if on, pass 1 in its feedback form --
+ *               the code a filter runs, so the history never depends on whether a filter ran (the temporal set-up divides by
+ *               T: the clear needs no divisor). That run does not write the ARGB image. It uses the filter's two images:
+ *               afterwards srt_read_denoised returns SRT_ERR_STATE until the next filter. With the switch off
+ *               srt_read_denoised behaves as without this interface.
+ *   stale       while the switch is on, every setter that changes what pass 1 computes makes the next clear run that front:
+ *               this switch, srt_set_denoise when it changes a sigma or K, srt_set_denoise_demodulation and
+ *               srt_set_denoise_spatial_variance (as the illumination and clamp setters already do for the set-up).
+ *   repeats     two filters of one frame without a trace between them commit what one commits: the set-up rewrites the
+ *               staging set from the history and the canvas before pass 1 overwrites its colour.
+ * With the switch off the library enqueues exactly what it enqueues without this interface, and the kernels it launches then
+ * keep their instructions. No new device memory. Independent of object motion, per-triangle motion, history illumination
+ * and the history clamp (which acts on whatever colour the history holds).
+ * enable != 0: on. SRT_ERR_STATE unless temporal reprojection is on (so never on a partitioned handle; the group call: the
+ * group's temporal reprojection). Turning temporal reprojection or the denoiser off turns it off. Clears nothing and keeps
+ * the history. */
+int srt_set_denoise_history_feedback(srt_tracer *t, int enable);
+int srt_group_set_denoise_history_feedback(srt_group *g, int enable);
+/* 1 when the last pass 1 (a filter's or a clear's) was a feedback instantiation, else 0 (also for NULL, and after a filter
+ * with K = 0). */
+int srt_last_filter_history_feedback(srt_tracer *t);
+int srt_group_last_filter_history_feedback(srt_group *g);
+
 /* ---- albedo textures ----------------------------------------------------------
  * Opt-in: where a material has a texture bound, the colour that multiplies the path's mask (and the denoiser's albedo
  * guide) is the texel at the hit's UV instead of srt_material.color. Nothing else about a material changes and a lookup

@@ -4,8 +4,9 @@
 
 Each tree is a checkout's root (holding simple-raytracer_amd/csrc and include/). Every source of build.py SOURCES is
 compiled device-only with the product flags of build.py, its gfx950 code object is unbundled and disassembled with
-llvm-objdump, and every function in it is compared instruction by instruction, branch offsets and the s_nop padding
-between functions left out. A function that only one side has counts as a difference; the plain ordered reduction is
+llvm-objdump, and every function in it is compared instruction by instruction, branch offsets, the s_nop padding
+between functions and the pc-relative literal that follows an s_getpc_b64 (the distance to a constant table of the same object,
+which moves when another function is added to the source) left out. A function that only one side has counts as a difference; the plain ordered reduction is
 matched across its rename to srt_reduce_kernel<false> (a template since the denoiser's moments variant), and the twelve temporal
 set-ups across theirs to srt_temporal_kernel<MOTION, ILLUM, CLAMP>. A function that differs prints both counts. Exit status 1 on
 any difference; with --allow-new, functions that only the new tree has do not count.
@@ -66,6 +67,8 @@ def functions(elf):
             continue
         if text.startswith(("s_branch", "s_cbranch")):
             text = text.split()[0]
+        if text.startswith("s_add_u32") and fs[cur] and fs[cur][-1].startswith("s_getpc_b64"):
+            text = text.rsplit(",", 1)[0]  # pc + literal: where the object's constants lie from here
         fs[cur].append(text)
     for body in fs.values():
         while body and body[-1] == "s_nop 0":

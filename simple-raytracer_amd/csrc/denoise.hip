@@ -25,6 +25,9 @@
 // Spatial variance estimate (srt_set_denoise_spatial_variance; tests/spatial_variance_ref.py), K >= 1 only: one launch before
 //   the passes (after the demodulate launch) gives a pixel with fewer than min_samples samples the variance of the
 //   edge-weighted moments of its 7x7 neighbourhood instead of its own (srt_denoise_spatial_variance_kernel below).
+// History feedback (srt_set_denoise_history_feedback; tests/feedback_ref.py), K >= 1 and temporal reprojection only: pass 1 also
+//   writes its colour result into the staging set of temporal.hip (srt_denoise_atrous_feedback_kernel below); the frame's own
+//   output does not change.
 // No atomics: every output is a fixed function of its inputs, so runs are bit-identical. The passes use the fast
 // exp / log instructions: this stage is outside the parity contract (DESIGN.md "Denoiser").
 #include <hip/hip_runtime.h>
@@ -53,6 +56,7 @@ struct FilterParams {
 	const float4 *in;                              // {colour, variance}
 	float4 *out;
 	uint32_t *argb; // last pass only (else NULL): the tonemapped bytes
+	float4 *staged; // the feedback form of pass 1 only (else NULL): the staging set's {colour, count} plane
 };
 
 struct SetupParams {
@@ -91,6 +95,9 @@ __global__ __launch_bounds__(256) void srt_denoise_setup_kernel(const SetupParam
 	if (p.argb) p.argb[i] = tonemap(c0.x, c0.y, c0.z);
 }
 
+// (The pass formula stands three times in this unit: here, in srt_denoise_atrous_demod_kernel and in atrous_feedback_pass, which
+// restates both for pass 1 of the history feedback. An edit of the formula goes into all three; the feedback test's
+// same-frame check holds the copies together bit for bit.)
 __global__ __launch_bounds__(256) void srt_denoise_atrous_kernel(const FilterParams p) {
 	const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
 	if (x >= p.width || y >= p.height) return;
@@ -168,7 +175,8 @@ __global__ __launch_bounds__(256) void srt_denoise_demodulate_kernel(const Demod
 
 // srt_denoise_atrous_kernel over the illumination: no albedo term, so a tap is its {I, V_I} and {N, Z} alone (32 B, not 48).
 // A tap without hits has N = 0 and fails d > 0, which is all its cov > 0 test would do; the centre keeps that test (a
-// centre without hits is no filtered pixel). LAST: the remodulation and the tonemap.
+// centre without hits is no filtered pixel). LAST: the remodulation and the tonemap. (atrous_feedback_pass<true, LAST> below is a
+// copy of this body: edit both.)
 template <bool LAST>
 __global__ __launch_bounds__(256) void srt_denoise_atrous_demod_kernel(const FilterParams p) {
 	const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
@@ -226,6 +234,99 @@ __global__ __launch_bounds__(256) void srt_denoise_atrous_demod_kernel(const Fil
 	p.out[i] = o;
 	if (LAST) p.argb[i] = tonemap(o.x, o.y, o.z);
 }
+
+// Pass 1 in its feedback form (srt_set_denoise_history_feedback): the pass of srt_denoise_atrous_kernel (DEMOD false) or of
+// srt_denoise_atrous_demod_kernel<LAST> (DEMOD true) -- the same statements in the same order -- which also stores the pixel's
+// colour result into the rgb of the staging set's {colour, count} plane (p.staged): as colour, I' D_p under DEMOD (the expression
+// LAST remodulates with), when the pixel entered the filter branch, received weight and all three values are finite; x, y, z
+// alone in one 12-byte store, the count untouched. No lane reads that plane during the pass. argb may be NULL also for LAST (K = 1
+// in the run a clear makes). One body for the three feedback kernels. The two kernels above keep bodies of their own: as
+// wrappers of a body shared with these (tried: one template with a FEEDBACK parameter) they compiled to 6 to 8 % more
+// instructions than before (2850 -> 3020, 752 -> 809, 914 -> 970), and with the switch off the library must launch what it launched.
+template <bool DEMOD, bool LAST>
+__device__ __forceinline__ void atrous_feedback_pass(const FilterParams &p) {
+	const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+	if (x >= p.width || y >= p.height) return;
+	const uint32_t i = (uint32_t)y * (uint32_t)p.width + (uint32_t)x;
+	const float4 cp = p.in[i];
+	const float4 g1p = p.guide[2 * i + 1];
+	float4 o = cp;
+	if (g1p.w > 0.f && finite3(cp)) {
+		const float4 g0p = p.guide[2 * i];
+		// g(V): 3x3 binomial prefilter of the input variance over in-image taps
+		float gv = 0.f, gw = 0.f;
+		for (int dy = -1; dy <= 1; dy++) {
+			const int qy = y + dy;
+			if (qy < 0 || qy >= p.height) continue;
+			for (int dx = -1; dx <= 1; dx++) {
+				const int qx = x + dx;
+				if (qx < 0 || qx >= p.width) continue;
+				const float k = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);
+				gv += k * p.in[(uint32_t)qy * (uint32_t)p.width + (uint32_t)qx].w;
+				gw += k;
+			}
+		}
+		gv = gv / gw;
+		const float lp = lum(cp.x, cp.y, cp.z);
+		const float inv_dl = 1.0f / (p.sigma_l * sqrtf(gv) + 1e-10f);
+		const float inv_dz = 1.0f / (p.sigma_z * g0p.w * (float)p.step + 1e-6f);
+		const float h[5] = {1.0f / 16.0f, 1.0f / 4.0f, 3.0f / 8.0f, 1.0f / 4.0f, 1.0f / 16.0f};
+		float sw = 0.f, sv = 0.f, sr = 0.f, sg = 0.f, sb = 0.f;
+		for (int dy = -2; dy <= 2; dy++) {
+			const int qy = y + dy * p.step;
+			if (qy < 0 || qy >= p.height) continue;
+			for (int dx = -2; dx <= 2; dx++) {
+				const int qx = x + dx * p.step;
+				if (qx < 0 || qx >= p.width) continue;
+				const uint32_t j = (uint32_t)qy * (uint32_t)p.width + (uint32_t)qx;
+				float e;
+				float4 cq;
+				float wn;
+				if constexpr (DEMOD) {
+					const float4 g0q = p.guide[2 * j];
+					cq = p.in[j];
+					const float d = g0p.x * g0q.x + g0p.y * g0q.y + g0p.z * g0q.z;
+					if (!(d > 0.f) || !finite3(cq)) continue; // max(0, d)^sigma_n = 0 (no hits: N = 0)
+					wn = __expf(p.sigma_n * __logf(d));
+					e = fabsf(g0p.w - g0q.w) * inv_dz + fabsf(lp - lum(cq.x, cq.y, cq.z)) * inv_dl;
+				} else {
+					const float4 g1q = p.guide[2 * j + 1];
+					cq = p.in[j];
+					if (!(g1q.w > 0.f) || !finite3(cq)) continue;
+					const float4 g0q = p.guide[2 * j];
+					const float d = g0p.x * g0q.x + g0p.y * g0q.y + g0p.z * g0q.z;
+					if (!(d > 0.f)) continue; // max(0, d)^sigma_n = 0
+					wn = __expf(p.sigma_n * __logf(d));
+					const float ar = g1p.x - g1q.x, ag = g1p.y - g1q.y, ab = g1p.z - g1q.z;
+					e = fabsf(g0p.w - g0q.w) * inv_dz + (ar * ar + ag * ag + ab * ab) * p.inv_sigma_a2 +
+					    fabsf(lp - lum(cq.x, cq.y, cq.z)) * inv_dl;
+				}
+				const float w = h[dx + 2] * h[dy + 2] * wn * __expf(-e);
+				sw += w;
+				sv += w * w * cq.w;
+				sr += w * cq.x, sg += w * cq.y, sb += w * cq.z;
+			}
+		}
+		if (sw > 0.f) o = make_float4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
+		[[maybe_unused]] float dr = 1.f, dg = 1.f, db = 1.f;
+		if constexpr (DEMOD) dr = fmaxf(g1p.x, SRT_DEMOD_EPS), dg = fmaxf(g1p.y, SRT_DEMOD_EPS), db = fmaxf(g1p.z, SRT_DEMOD_EPS);
+		float fr = o.x, fg = o.y, fb = o.z; // the colour that goes back
+		if constexpr (DEMOD) fr = o.x * dr, fg = o.y * dg, fb = o.z * db;
+		if constexpr (DEMOD && LAST) {
+			const float ld = lum(dr, dg, db);
+			o = make_float4(o.x * dr, o.y * dg, o.z * db, o.w * (ld * ld));
+		}
+		if (sw > 0.f && __builtin_isfinite(fr) && __builtin_isfinite(fg) && __builtin_isfinite(fb))
+			*reinterpret_cast<float3 *>(p.staged + i) = make_float3(fr, fg, fb);
+	}
+	p.out[i] = o;
+	if constexpr (!DEMOD || LAST) {
+		if (p.argb) p.argb[i] = tonemap(o.x, o.y, o.z); // (NULL: a middle pass, or the clear's run)
+	}
+}
+
+template <bool DEMOD, bool LAST>
+__global__ __launch_bounds__(256) void srt_denoise_atrous_feedback_kernel(const FilterParams p) { atrous_feedback_pass<DEMOD, LAST>(p); }
 
 // ---- spatial variance estimate (srt_set_denoise_spatial_variance; include/srt_abi.h has the definition, tests/spatial_variance_ref.py
 // restates it): one launch between the set-up (and the demodulate launch) and the passes. A pixel with cov > 0, a finite
@@ -507,9 +608,39 @@ int srt_denoise_member(srt_tracer *t, int feature_samples) {
 	return SRT_OK;
 }
 
-int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
+// one pass: k = 0 .. K - 1, step 2^k, ping-pong between the two images of `col`; the last one writes argb (NULL: none)
+static void launch_pass(srt_tracer *t, FilterParams fp, int k, int K, bool demod, bool feedback, float4 *col, uint8_t *argb) {
 	const size_t px = full_pixels(t);
-	if (px == 0) return SRT_OK;
+	const dim3 grid((unsigned)((t->width + 15) / 16), (unsigned)((t->height + 15) / 16));
+	const bool last = k == K - 1;
+	fp.step = 1 << k;
+	fp.in = col + (size_t)(k & 1) * px;
+	fp.out = col + (size_t)((k + 1) & 1) * px;
+	fp.argb = last ? reinterpret_cast<uint32_t *>(argb) : nullptr;
+	if (!feedback) {
+		fp.staged = nullptr;
+		if (!demod) hipLaunchKernelGGL(srt_denoise_atrous_kernel, grid, dim3(256), 0, t->stream, fp);
+		else if (last) hipLaunchKernelGGL(srt_denoise_atrous_demod_kernel<true>, grid, dim3(256), 0, t->stream, fp);
+		else hipLaunchKernelGGL(srt_denoise_atrous_demod_kernel<false>, grid, dim3(256), 0, t->stream, fp);
+	} else if (!demod) hipLaunchKernelGGL((srt_denoise_atrous_feedback_kernel<false, false>), grid, dim3(256), 0, t->stream, fp);
+	else if (last) hipLaunchKernelGGL((srt_denoise_atrous_feedback_kernel<true, true>), grid, dim3(256), 0, t->stream, fp);
+	else hipLaunchKernelGGL((srt_denoise_atrous_feedback_kernel<true, false>), grid, dim3(256), 0, t->stream, fp);
+}
+
+// What the front leaves for the passes after the first
+struct FilterFront {
+	FilterParams fp; // everything but the per-pass members
+	float4 *col;
+	int K;
+	bool demod, spatial_var, feedback;
+};
+
+// The filter's front: the set-up (spatial or temporal) into the filter image, the demodulate launch and the spatial-variance
+// launch where those are on, and pass 1 (k = 0) -- in its feedback form when srt_set_denoise_history_feedback is on, which
+// writes the pass's colour into the staging set the set-up has just written. A filter and a clear that has to make the staging
+// set itself (srt_denoise_feedback_front) run this same code, so the history never depends on which of them ran.
+static int filter_front(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb, FilterFront *f) {
+	const size_t px = full_pixels(t);
 	const int K = t->dn.iterations;
 	float4 *col = reinterpret_cast<float4 *>(t->dn_col.ptr);
 	float4 *guide = reinterpret_cast<float4 *>(t->dn_guide.ptr);
@@ -546,6 +677,7 @@ int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
 		SRT_HIP(t, hipGetLastError());
 	}
 	FilterParams fp;
+	memset(&fp, 0, sizeof fp);
 	fp.width = t->width;
 	fp.height = t->height;
 	fp.num_pixels = (uint32_t)px;
@@ -576,21 +708,48 @@ int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
 		launch_spatial_variance(vp, t->tp_on, demod, t->stream);
 		SRT_HIP(t, hipGetLastError());
 	}
-	const dim3 grid((unsigned)((t->width + 15) / 16), (unsigned)((t->height + 15) / 16));
-	for (int k = 0; k < K; k++) {
-		fp.step = 1 << k;
-		fp.in = col + (size_t)(k & 1) * px;
-		fp.out = col + (size_t)((k + 1) & 1) * px;
-		fp.argb = k == K - 1 ? reinterpret_cast<uint32_t *>(argb) : nullptr;
-		if (!demod) hipLaunchKernelGGL(srt_denoise_atrous_kernel, grid, dim3(256), 0, t->stream, fp);
-		else if (k == K - 1) hipLaunchKernelGGL(srt_denoise_atrous_demod_kernel<true>, grid, dim3(256), 0, t->stream, fp);
-		else hipLaunchKernelGGL(srt_denoise_atrous_demod_kernel<false>, grid, dim3(256), 0, t->stream, fp);
+	// the history feedback: pass 1's colour goes into the set the set-up staged (the switch needs temporal reprojection)
+	const bool feedback = t->tp_feedback && t->tp_on && K >= 1;
+	if (K >= 1) {
+		fp.staged = feedback ? const_cast<float4 *>(staged.cc) : nullptr;
+		launch_pass(t, fp, 0, K, demod, feedback, col, argb);
 		SRT_HIP(t, hipGetLastError());
 	}
-	t->dn_out = K & 1;
+	f->fp = fp;
+	f->col = col;
+	f->K = K;
+	f->demod = demod;
+	f->spatial_var = spatial_var;
+	f->feedback = feedback;
+	t->last_filter_feedback = feedback;
+	return SRT_OK;
+}
+
+int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
+	if (full_pixels(t) == 0) return SRT_OK;
+	FilterFront f;
+	const int rc = filter_front(t, ticks_stopped, argb, &f);
+	if (rc) return rc;
+	for (int k = 1; k < f.K; k++) {
+		launch_pass(t, f.fp, k, f.K, f.demod, false, f.col, argb);
+		SRT_HIP(t, hipGetLastError());
+	}
+	t->dn_out = f.K & 1;
 	t->dn_filtered = true;
-	t->last_filter_demod = demod;
-	t->last_filter_sv = spatial_var;
+	t->last_filter_demod = f.demod;
+	t->last_filter_sv = f.spatial_var;
+	return SRT_OK;
+}
+
+int srt_denoise_feedback_front(srt_tracer *t, bool *ran) {
+	*ran = false;
+	if (!(t->tp_feedback && t->tp_on && t->dn.iterations >= 1) || full_pixels(t) == 0) return SRT_OK;
+	FilterFront f;
+	// no divisor: the temporal set-up divides by T. No ARGB: pass 1 gets none, whether or not it is the last pass (K = 1)
+	const int rc = filter_front(t, 1u, nullptr, &f);
+	if (rc) return rc;
+	t->dn_filtered = false; // the filter's two images hold this run's set-up and pass 1, no filter result
+	*ran = true;
 	return SRT_OK;
 }
 
@@ -618,6 +777,7 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 		t->tp_on = false; // temporal reprojection is a stage of the denoiser
 		t->tp_illum = false; // (with its illumination mode)
 		t->tp_clamp = 0.f;   // (and its history clamp)
+		t->tp_feedback = false; // (and its history feedback)
 		t->om_on = false; // and object motion a stage of that
 		t->vm_on = false; // (with its per-triangle part)
 		srt_temporal_drop(t);
@@ -636,6 +796,10 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 	SRT_HIP(t, t->dn_col.reserve(px * 8));
 	const bool clear = !t->dn_on || params->feature_samples != t->dn.feature_samples;
 	if (t->tp_clamp > 0.f) t->tp_fresh = false; // the history clamp's bounds take their weights from the filter's sigmas
+	// the history feedback stages pass 1's result: other sigmas or another K (0 against >= 1, the last pass against a middle one) stage another
+	if (t->tp_feedback && (params->iterations != t->dn.iterations || params->sigma_luminance != t->dn.sigma_luminance || params->sigma_normal != t->dn.sigma_normal ||
+	                       params->sigma_depth != t->dn.sigma_depth || params->sigma_albedo != t->dn.sigma_albedo))
+		t->tp_fresh = false;
 	t->dn = *params;
 	t->dn_on = true;
 	if (clear) {
@@ -650,10 +814,12 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 int srt_set_denoise_demodulation(srt_tracer *t, int enable) {
 	if (!t) return SRT_ERR_INVALID;
 	if (!enable) {
+		if (t->dn_demod && t->tp_feedback) t->tp_fresh = false; // the history feedback staged the demodulated pass 1's result
 		t->dn_demod = false;
 		return SRT_OK;
 	}
 	if (!t->dn_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_demodulation: the denoiser is off (srt_set_denoise)");
+	if (!t->dn_demod && t->tp_feedback) t->tp_fresh = false;
 	t->dn_demod = true;
 	return SRT_OK;
 }
@@ -667,11 +833,13 @@ int srt_last_filter_demodulated(const srt_tracer *t, int *demodulated) {
 int srt_set_denoise_spatial_variance(srt_tracer *t, uint32_t min_samples) {
 	if (!t) return SRT_ERR_INVALID;
 	if (min_samples == 0) {
+		if (t->dn_sv_min && t->tp_feedback) t->tp_fresh = false; // the history feedback staged pass 1 over the estimated variance
 		t->dn_sv_min = 0;
 		return SRT_OK;
 	}
 	if (min_samples > (1u << 20)) return fail(t, SRT_ERR_INVALID, "srt_set_denoise_spatial_variance: min_samples 0..2^20");
 	if (!t->dn_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_spatial_variance: the denoiser is off (srt_set_denoise)");
+	if (min_samples != t->dn_sv_min && t->tp_feedback) t->tp_fresh = false;
 	t->dn_sv_min = min_samples;
 	return SRT_OK;
 }

@@ -712,7 +712,7 @@ int srt_group_set_denoise_temporal(srt_group *g, const srt_temporal_params *para
 int srt_group_set_denoise_demodulation(srt_group *g, int enable) {
 	if (!g) return SRT_ERR_INVALID;
 	if (!enable) {
-		if (g->resolver) g->resolver->dn_demod = false;
+		if (g->resolver) SRT_ON_RESOLVER(g, g->resolver, srt_set_denoise_demodulation(g->resolver, 0));
 		return SRT_OK;
 	}
 	if (!g->dn_on) return gfail(g, SRT_ERR_STATE, "srt_group_set_denoise_demodulation: the denoiser is off (srt_group_set_denoise)");
@@ -758,10 +758,24 @@ int srt_group_set_denoise_history_clamp(srt_group *g, float gamma) {
 
 int srt_group_last_setup_history_clamp(srt_group *g) { return g && g->resolver && g->resolver->last_setup_clamp ? 1 : 0; }
 
+int srt_group_set_denoise_history_feedback(srt_group *g, int enable) {
+	if (!g) return SRT_ERR_INVALID;
+	if (!enable) {
+		if (g->resolver) SRT_ON_RESOLVER(g, g->resolver, srt_set_denoise_history_feedback(g->resolver, 0));
+		return SRT_OK;
+	}
+	if (!g->dn_on || !g->resolver)
+		return gfail(g, SRT_ERR_STATE, "srt_group_set_denoise_history_feedback: temporal reprojection is off (srt_group_set_denoise_temporal)");
+	SRT_ON_RESOLVER(g, g->resolver, srt_set_denoise_history_feedback(g->resolver, 1)); // the filter and the commit run on that handle
+	return SRT_OK;
+}
+
+int srt_group_last_filter_history_feedback(srt_group *g) { return g && g->resolver && g->resolver->last_filter_feedback ? 1 : 0; }
+
 int srt_group_set_denoise_spatial_variance(srt_group *g, uint32_t min_samples) {
 	if (!g) return SRT_ERR_INVALID;
 	if (min_samples == 0) {
-		if (g->resolver) g->resolver->dn_sv_min = 0;
+		if (g->resolver) SRT_ON_RESOLVER(g, g->resolver, srt_set_denoise_spatial_variance(g->resolver, 0));
 		return SRT_OK;
 	}
 	if (min_samples > (1u << 20)) return gfail(g, SRT_ERR_INVALID, "srt_group_set_denoise_spatial_variance: min_samples 0..2^20");

@@ -223,6 +223,8 @@ struct srt_tracer {
 	DevBuf<float> tp_bounds;       // two float4 planes {mu, sum of weights}, {sigma, taps} (allocated on the first enable; no part of the history)
 	bool tp_bounds_ran = false;    // srt_temporal_bounds_kernel has written tp_bounds at least once (srt_read_denoise_history_bounds)
 	bool last_setup_clamp = false; // srt_last_setup_history_clamp: the last set-up ran the bounds launch and a CLAMP variant
+	bool tp_feedback = false;          // srt_set_denoise_history_feedback: pass 1 (K >= 1) writes its colour into the staging set
+	bool last_filter_feedback = false; // srt_last_filter_history_feedback: the last pass 1 (a filter's or a clear's) was a feedback instantiation
 	std::vector<uint8_t> scene_bytes; // the last srt_update_scene's arrays and scene data (the history survives an unchanged scene)
 	// object motion (temporal.hip; srt_set_denoise_object_motion): the feature pass stores a shape index per pixel into
 	// om_ids[om_cur]; the commit swaps, so om_ids[1 - om_cur] belongs to the history, traced with the scene om_hist_scene
@@ -335,6 +337,10 @@ static inline Tex srt_with_textures(const srt_tracer *t, const Base &base) {
 int srt_denoise_clear(srt_tracer *t);
 int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples);
 int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb);
+/* the history feedback's part of a clear that has to make the staging set itself (temporal.hip srt_temporal_commit): with the
+ * switch on and K >= 1 the filter's front -- set-up, demodulate and spatial-variance launches, pass 1 in its feedback form --
+ * without an ARGB image, *ran = true, and the filter's images hold no filter result afterwards; else nothing, *ran = false */
+int srt_denoise_feedback_front(srt_tracer *t, bool *ran);
 /* the counts of one dispatch of `rd` (T, P, F, the camera) added to t's: srt_denoise_after_trace's, and what a group keeps on
  * its resolver handle for the dispatch all members have just run */
 void srt_denoise_count(srt_tracer *t, const srt_render_data &rd, int feature_samples);

@@ -870,7 +870,12 @@ int srt_temporal_setup(srt_tracer *t, float4 *col, uint32_t *argb, TemporalStage
 int srt_temporal_commit(srt_tracer *t) {
 	if (!t->dn_on || !t->tp_on || t->dn_T == 0 || full_pixels(t) == 0) return SRT_OK; // nothing traced: the history stays
 	if (!t->tp_fresh) {
-		const int rc = launch_setup(t, nullptr, nullptr);
+		// no filter since the last trace (or a setter since): the staging set is made here. With the history feedback on that is
+		// the filter's own front, pass 1 included (denoise.hip), so that the history never depends on whether a filter ran
+		bool front = false;
+		int rc = srt_denoise_feedback_front(t, &front);
+		if (rc) return rc;
+		if (!front) rc = launch_setup(t, nullptr, nullptr);
 		if (rc) return rc;
 	}
 	t->tp_cur = 1 - t->tp_cur;
@@ -968,6 +973,7 @@ int srt_set_denoise_temporal(srt_tracer *t, const srt_temporal_params *params) {
 		t->vm_on = false;
 		t->tp_illum = false; // a mode of the temporal set-up
 		t->tp_clamp = 0.f;   // and so is the history clamp
+		t->tp_feedback = false; // and the history feedback
 		return SRT_OK;
 	}
 	if (!params_ok(*params))
@@ -1012,6 +1018,18 @@ int srt_set_denoise_history_clamp(srt_tracer *t, float gamma) {
 }
 
 int srt_last_setup_history_clamp(srt_tracer *t) { return t && t->last_setup_clamp ? 1 : 0; }
+
+int srt_set_denoise_history_feedback(srt_tracer *t, int enable) {
+	if (!t) return SRT_ERR_INVALID;
+	if (enable && !t->tp_on)
+		return fail(t, SRT_ERR_STATE, "srt_set_denoise_history_feedback: temporal reprojection is off (srt_set_denoise_temporal)");
+	const bool on = enable != 0;
+	if (on != t->tp_feedback) t->tp_fresh = false; // the staging set holds the other setting's colour: the commit makes its own
+	t->tp_feedback = on;
+	return SRT_OK;
+}
+
+int srt_last_filter_history_feedback(srt_tracer *t) { return t && t->last_filter_feedback ? 1 : 0; }
 
 int srt_read_denoise_history_bounds(srt_tracer *t, float *mean_weight, float *sigma_taps) {
 	if (!t) return SRT_ERR_INVALID;

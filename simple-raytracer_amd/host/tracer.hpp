@@ -242,6 +242,16 @@ class Tracer {
 	bool last_setup_history_clamp() {
 		return (group ? srt_group_last_setup_history_clamp(group) : srt_last_setup_history_clamp(handle)) != 0;
 	}
+	/// The history feedback (srt_set_denoise_history_feedback): with iterations >= 1 the colour that enters the temporal history
+	/// is the first a-trous pass's output instead of the integrated samples, SVGF's feedback. Needs set_denoise_temporal first;
+	/// one device or a device group (the group's filter and commit run on device 0).
+	void set_denoise_history_feedback(bool enable = true) {
+		check(group ? srt_group_set_denoise_history_feedback(group, enable ? 1 : 0) : srt_set_denoise_history_feedback(handle, enable ? 1 : 0));
+	}
+	/// Whether the last pass 1 (a filter's or a clear's) was a feedback instantiation
+	bool last_filter_history_feedback() {
+		return (group ? srt_group_last_filter_history_feedback(group) : srt_last_filter_history_feedback(handle)) != 0;
+	}
 	/// Spatial variance estimate (srt_set_denoise_spatial_variance): a pixel with fewer than min_samples samples (the first
 	/// frames after a clear, disocclusions under temporal reprojection) takes its variance from the moments of its 7x7
 	/// neighbourhood instead of its own two or three samples. 0 turns it off. Needs set_denoise first; one device or a group.

@@ -5,7 +5,7 @@
 //
 //   srt_headless [--scene spheres|meshes|empty] [--obj f.obj]... [--stl f.stl]...
 //                [--width W --height H --spp S --bounces B --frames N --time T]
-//                [--obj-materials] [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--move DX]
+//                [--obj-materials] [--out frame.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] [--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--move DX]
 // --denoise K: the frames go through the edge-aware denoiser with K a-trous passes (Tracer::set_denoise; with --gpus N the
 //                members gather the filter's inputs with the frame and device 0 filters: the same bytes as on one device)
 // --demodulate: with --denoise, the passes filter colour / first-hit albedo (Tracer::set_denoise_demodulation); an error without it
@@ -15,6 +15,8 @@
 // --history-illumination: with --temporal, the history is reprojected as illumination (Tracer::set_denoise_history_illumination); an error without it
 // --history-clamp G: with --temporal, the reprojected history colour is clamped into mean +- G sigma of the frame's 7x7 neighbourhood
 //                (Tracer::set_denoise_history_clamp; 0 < G <= 64, 1 is the library's advice); an error without --temporal
+// --history-feedback: with --temporal, the first a-trous pass's output is what enters the history (Tracer::set_denoise_history_feedback);
+//                an error without --temporal
 // --move DX: the camera moves by DX along x every frame and every frame clears the canvas, as the front-end does while moving
 // --move-shape I DX: with --temporal, shape I (a sphere, a plane or a model instance) moves by DX along x every frame and every
 //                frame clears the canvas, as the front-end does while a gizmo is dragged; turns object motion on
@@ -123,7 +125,7 @@ int main(int argc, char **argv) {
 	unsigned time_seed = 12345;
 	bool parse_only = false, bvh = false, pipelined = false, obj_materials = false;
 	int gpus = 1, denoise = -1, spatial_variance = 0;
-	bool temporal = false, demodulate = false, history_illumination = false;
+	bool temporal = false, demodulate = false, history_illumination = false, history_feedback = false;
 	float history_clamp = 0.0f;
 	bool clamp_given = false;
 	float move = 0.0f, shape_move = 0.0f;
@@ -188,12 +190,13 @@ int main(int argc, char **argv) {
 		else if (a == "--temporal") temporal = true;
 		else if (a == "--history-illumination") history_illumination = true;
 		else if (a == "--history-clamp") history_clamp = std::strtof(next(), nullptr), clamp_given = true;
+		else if (a == "--history-feedback") history_feedback = true;
 		else if (a == "--move") move = std::strtof(next(), nullptr), moving = true;
 		else if (a == "--move-shape") move_shape = std::atoi(next()), shape_move = std::strtof(next(), nullptr);
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
+			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
@@ -212,6 +215,10 @@ int main(int argc, char **argv) {
 	}
 	if (clamp_given && (!temporal || denoise < 0 || !(history_clamp > 0.0f && history_clamp <= 64.0f))) {
 		std::cerr << "--history-clamp G needs --denoise K --temporal and 0 < G <= 64\n";
+		return 2;
+	}
+	if (history_feedback && (!temporal || denoise < 0)) {
+		std::cerr << "--history-feedback needs --denoise K --temporal\n";
 		return 2;
 	}
 	if (temporal && denoise < 0) {
@@ -334,6 +341,7 @@ int main(int argc, char **argv) {
 	if (temporal) tracer.set_denoise_temporal();
 	if (history_illumination) tracer.set_denoise_history_illumination();
 	if (clamp_given) tracer.set_denoise_history_clamp(history_clamp);
+	if (history_feedback) tracer.set_denoise_history_feedback();
 	if (move_shape >= 0) {
 		if (!temporal || (size_t)move_shape >= shapes.size()) {
 			std::cerr << "--move-shape needs --temporal and a shape index below " << shapes.size() << "\n";

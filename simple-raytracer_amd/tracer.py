@@ -53,6 +53,8 @@ ABI_SYMBOLS = [
     "srt_group_last_setup_history_illumination",
     "srt_set_denoise_history_clamp", "srt_group_set_denoise_history_clamp", "srt_last_setup_history_clamp",
     "srt_group_last_setup_history_clamp", "srt_read_denoise_history_bounds",
+    "srt_set_denoise_history_feedback", "srt_group_set_denoise_history_feedback", "srt_last_filter_history_feedback",
+    "srt_group_last_filter_history_feedback",
     "srt_bvh_refit_wide_host", "srt_set_acceleration_refit", "srt_group_set_acceleration_refit", "srt_acceleration_refit_info",
     "srt_last_refit_kernel_ms", "srt_read_bvh_blocks", "srt_bvh_wide_order_host",
     "srt_set_acceleration_deform", "srt_group_set_acceleration_deform", "srt_acceleration_deform_info",
@@ -597,6 +599,11 @@ def _bind(lib):
         lib.srt_last_setup_history_clamp.argtypes = [vp]
         lib.srt_group_last_setup_history_clamp.argtypes = [vp]
         lib.srt_read_denoise_history_bounds.argtypes = [vp, vp, vp]
+    if hasattr(lib, "srt_set_denoise_history_feedback"):  # (an older library, SRT_LIB, in an A/B run)
+        lib.srt_set_denoise_history_feedback.argtypes = [vp, C.c_int]
+        lib.srt_group_set_denoise_history_feedback.argtypes = [vp, C.c_int]
+        lib.srt_last_filter_history_feedback.argtypes = [vp]
+        lib.srt_group_last_filter_history_feedback.argtypes = [vp]
     if hasattr(lib, "srt_set_textures"):
         lib.srt_set_textures.argtypes = [vp, vp, sz]
         lib.srt_set_material_textures.argtypes = [vp, vp, sz]
@@ -722,6 +729,16 @@ class _Denoise:
     def last_setup_history_clamp(self):
         """True when the last temporal set-up (a filter's or a clear's) ran the bounds launch and a clamping set-up."""
         return bool(self._dn("last_setup_history_clamp"))
+
+    def set_denoise_history_feedback(self, enable=True):
+        """Feed the first a-trous pass back into the temporal history: with iterations >= 1 the colour a clear commits is pass 1's
+        output instead of the integrated samples (srt_set_denoise_history_feedback). Needs temporal reprojection on; clears
+        nothing, keeps the history. After a clear that had to run the pass itself read_denoised() fails until the next filter."""
+        self._check(self._dn("set_denoise_history_feedback", 1 if enable else 0))
+
+    def last_filter_history_feedback(self):
+        """True when the last pass 1 (a filter's or a clear's) was a feedback instantiation."""
+        return bool(self._dn("last_filter_history_feedback"))
 
     def reset_denoise_history(self):
         """Drop the temporal history: the next frame is filtered as by the spatial denoiser alone."""
