@@ -272,7 +272,8 @@ int srt_trace(srt_tracer *t, const srt_render_data *options);      /* `render` k
 int srt_resolve(srt_tracer *t, uint32_t ticks_stopped);             /* `average` kernel, render.cl:525 */
 int srt_synchronize(srt_tracer *t);
 /* The `average` kernel over caller-owned device buffers (num_pixels float4 in,
- * num_pixels*4 bytes out), e.g. the gathered full canvas on the root GPU. Async. */
+ * num_pixels*4 bytes out), e.g. the gathered full canvas on the root GPU. Async. Always the plain bytes: the handle's
+ * exposure (srt_set_exposure) is not applied here, and srt_last_resolve_exposed keeps its value. */
 int srt_resolve_external(srt_tracer *t, const void *device_canvas, uint32_t num_pixels, uint32_t ticks_stopped,
                          void *device_argb);
 
@@ -891,6 +892,49 @@ int srt_plane_frame_host(const float normal[3], float T[3], float B[3]);
  * when only the count matters (n_textures images assumed good); uv_triangles < 0: no UVs set. */
 int srt_texture_check_host(const srt_texture_desc *descs, size_t n_textures, const srt_material_texture *bindings, size_t n_bindings,
                            long long uv_triangles, size_t scene_triangles);
+
+/* ---- exposure for the resolve (new; no counterpart in the reference) ----------------------------------------------------
+ * The plain resolve is canvas / ticks_stopped -> ACES fit -> sqrt -> bytes, one fixed curve. With exposure enabled every site
+ * that resolves -- srt_resolve, srt_render, srt_render_async, srt_render_pipelined / srt_pipeline_flush, srt_resolve_denoised,
+ * srt_resolve_gathered, srt_group_render, srt_group_resolve_denoised -- resolves as before and then overwrites its ARGB image
+ * with tonemap(c * e) per channel, c the divided colour (with the handle's denoiser on: the image srt_read_denoised hands out)
+ * and e the exposure, a float in device memory that the kernel reads there: no call waits for the host, a pipelined frame
+ * included. At e == 1 the bytes are the plain resolve's. srt_resolve_external keeps the plain bytes. Off (the default): the
+ * library launches what it launches without the feature.
+ *
+ * MANUAL: e = (float)2^ev, written into the device slot by srt_set_exposure. One more launch per frame.
+ * AUTO, once per produced frame, on the handle's stream:
+ *   histogram  L = 0.2126 r + 0.7152 g + 0.0722 b of the divided colour (float, unfused). A finite L > 0 goes into
+ *              bin = clamp((bits(L) >> 21) - ((127 - 32) << 2), 0, 255): four bins per octave over 2^-32 .. 2^32, denormals in
+ *              bin 0. Any other pixel (L zero, negative, inf, NaN) is left out and counted as such. Integer sums: exact.
+ *   meter      N = the metered pixels in ascending bin order; kept are those numbered from N * low_permille / 1000 up to, not
+ *              including, max(N * high_permille / 1000, that + 1) (integer divisions; a boundary bin contributes its part).
+ *              mean = the kept pixels' mean of their bin's centre (bin + 0.5) / 4 - 32, accumulated in double in ascending bin
+ *              order; target = clamp(log2(key) - mean, min_ev, max_ev); state = state + (target - state) * adapt when a state
+ *              exists, else target; in double, stored as float. N == 0 leaves the state (0 on a fresh handle) and whether
+ *              one exists as they are. Then log2_exposure = (float)(state + ev) and e = (float)2^log2_exposure.
+ *   resolve    as above.
+ * A partitioned handle meters the rows it owns; the gathered frame is metered by srt_resolve_gathered on the root. A group
+ * keeps ONE state, on its first device, whichever of its two resolves (gathered, or denoised) a frame goes through.
+ * srt_clear_canvas keeps the adaptation state; srt_reset_exposure and disabling forget it (the next metered frame adopts its
+ * target). Changing the parameters while enabled keeps it. */
+int srt_exposure_defaults(srt_exposure_params *out); /* AUTO, ev 0, key 0.18, 100..950 permille, adapt 1, min_ev -16, max_ev 16 */
+/* Host-only: the validation srt_set_exposure applies to an enabled block (ranges as in srt_types.h, every float finite, adapt
+ * in (0, 1], reserved 0). SRT_OK or SRT_ERR_INVALID. */
+int srt_exposure_check_host(const srt_exposure_params *p);
+/* p NULL or enable == 0: off, and the adaptation state is forgotten. SRT_ERR_INVALID as srt_exposure_check_host. Asynchronous. */
+int srt_set_exposure(srt_tracer *t, const srt_exposure_params *p);
+int srt_group_set_exposure(srt_group *g, const srt_exposure_params *p);
+int srt_reset_exposure(srt_tracer *t);
+int srt_group_reset_exposure(srt_group *g);
+/* Waits for the handle's stream. log2_exposure, exposure: what the last exposed resolve multiplied with (0 and 1 before the
+ * feature was ever enabled); hist, counts = {metered pixels, pixels left out}: the last metered frame's (zeros before one; MANUAL
+ * meters nothing). Any pointer may be NULL. */
+int srt_read_exposure(srt_tracer *t, float *log2_exposure, float *exposure, uint32_t hist[256], uint32_t counts[2]);
+int srt_group_read_exposure(srt_group *g, float *log2_exposure, float *exposure, uint32_t hist[256], uint32_t counts[2]);
+/* For tests: *exposed = 1 when the last resolving call on the handle (the group: on its first device) ran the exposed resolve. */
+int srt_last_resolve_exposed(const srt_tracer *t, int *exposed);
+int srt_group_last_resolve_exposed(const srt_group *g, int *exposed);
 
 /* Device self-test of the deterministic math (tests only). Walks r = 0, stride, ... over
  * all 2^32 RNG outputs: out[0..2] = mismatch counts of the kernel-local sqrt / log / cos

@@ -151,6 +151,22 @@ typedef struct srt_temporal_params {
 	int32_t reserved[4];    /* must be 0 */
 } srt_temporal_params;
 
+/* Exposure for the resolve (srt_set_exposure in srt_abi.h; new, no counterpart in the reference): the divided colour is
+ * multiplied by an exposure before the tone map, a fixed one (MANUAL) or one metered from the frame's luminance histogram
+ * on the device (AUTO). */
+enum { SRT_EXPOSURE_MANUAL = 0, SRT_EXPOSURE_AUTO = 1 };
+typedef struct srt_exposure_params {
+	int32_t enable;        /* 0: off (the library launches what it launches without the feature) */
+	int32_t mode;          /* SRT_EXPOSURE_MANUAL / SRT_EXPOSURE_AUTO */
+	float ev;              /* finite, |ev| <= 32. MANUAL: exposure = 2^ev. AUTO: a bias added to the metered log2 exposure */
+	float key;             /* finite, > 0: the luminance the metered average is mapped to (default 0.18) */
+	int32_t low_permille;  /* 0..999: histogram mass ignored at the dark end (default 100) */
+	int32_t high_permille; /* low_permille + 1..1000: ... and kept up to here (default 950) */
+	float adapt;           /* 0 < adapt <= 1: share of the way from the previous exposure to the target per metered frame, in log2 (default 1: immediate) */
+	float min_ev, max_ev;  /* finite, min_ev <= max_ev, |.| <= 32: clamp of the metered log2 exposure before the bias (defaults -16, 16) */
+	int32_t reserved[3];   /* must be 0 */
+} srt_exposure_params;
+
 /* Albedo textures (srt_set_textures, srt_set_material_textures; include/srt_abi.h). */
 #define SRT_MAX_TEXTURES 64
 enum { SRT_FILTER_LINEAR = 0, SRT_FILTER_NEAREST = 1 };
@@ -217,6 +233,12 @@ SRT_STATIC_ASSERT(offsetof(srt_temporal_params, history_limit) == 4, "TemporalPa
 SRT_STATIC_ASSERT(offsetof(srt_temporal_params, normal_threshold) == 8, "TemporalParams.normal_threshold@8");
 SRT_STATIC_ASSERT(offsetof(srt_temporal_params, depth_threshold) == 12, "TemporalParams.depth_threshold@12");
 SRT_STATIC_ASSERT(offsetof(srt_temporal_params, reserved) == 16, "TemporalParams.reserved@16");
+SRT_STATIC_ASSERT(sizeof(srt_exposure_params) == 48, "ExposureParams 48 B");
+SRT_STATIC_ASSERT(offsetof(srt_exposure_params, ev) == 8, "ExposureParams.ev@8");
+SRT_STATIC_ASSERT(offsetof(srt_exposure_params, low_permille) == 16, "ExposureParams.low_permille@16");
+SRT_STATIC_ASSERT(offsetof(srt_exposure_params, adapt) == 24, "ExposureParams.adapt@24");
+SRT_STATIC_ASSERT(offsetof(srt_exposure_params, min_ev) == 28, "ExposureParams.min_ev@28");
+SRT_STATIC_ASSERT(offsetof(srt_exposure_params, reserved) == 36, "ExposureParams.reserved@36");
 SRT_STATIC_ASSERT(sizeof(srt_material_texture) == 16, "MaterialTexture 16 B");
 SRT_STATIC_ASSERT(offsetof(srt_material_texture, scale_u) == 8, "MaterialTexture.scale_u@8");
 

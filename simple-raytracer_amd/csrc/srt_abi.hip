@@ -217,6 +217,7 @@ void srt_destroy(srt_tracer *t) {
 	t->om_table_dev.release();
 	for (int k = 0; k < 2; k++) t->vm_tri[k].release(), t->vm_rows[k].release();
 	t->vm_first_dev.release();
+	t->ex_own.record.release();
 	srt_texture_release(t);
 	if (t->ev_t0) (void)hipEventDestroy(t->ev_t0);
 	if (t->ev_t1) (void)hipEventDestroy(t->ev_t1);
@@ -808,11 +809,14 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 	return SRT_OK;
 }
 
-// srt_resolve / srt_resolve_external: launch_resolve between the resolve timer's events
-static int resolve_impl(srt_tracer *t, const float *canvas, uint32_t num_pixels, uint32_t ticks_stopped, uint8_t *argb) {
+// srt_resolve / srt_resolve_external: launch_resolve between the resolve timer's events; `expose`: with the handle's exposure
+// on, its launches (exposure.hip) behind it, inside the same span
+static int resolve_impl(srt_tracer *t, const float *canvas, uint32_t num_pixels, uint32_t ticks_stopped, uint8_t *argb, bool expose) {
 	SRT_HIP(t, hipSetDevice(t->device));
 	SRT_HIP(t, hipEventRecord(t->ev_r0, t->stream));
 	if (const int rc = launch_resolve(t, canvas, num_pixels, ticks_stopped, argb)) return rc;
+	if (expose)
+		if (const int rc = srt_exposure_apply(t, canvas, (float)ticks_stopped, num_pixels, argb)) return rc;
 	SRT_HIP(t, hipEventRecord(t->ev_r1, t->stream));
 	t->have_resolve_ev = true;
 	return SRT_OK;
@@ -820,14 +824,14 @@ static int resolve_impl(srt_tracer *t, const float *canvas, uint32_t num_pixels,
 
 int srt_resolve(srt_tracer *t, uint32_t ticks_stopped) {
 	if (!t) return SRT_ERR_INVALID;
-	return resolve_impl(t, t->canvas, (uint32_t)owned_pixels(t), ticks_stopped, t->argb.ptr);
+	return resolve_impl(t, t->canvas, (uint32_t)owned_pixels(t), ticks_stopped, t->argb.ptr, true);
 }
 
 int srt_resolve_external(srt_tracer *t, const void *device_canvas, uint32_t num_pixels, uint32_t ticks_stopped,
                          void *device_argb) {
 	if (!t) return SRT_ERR_INVALID;
 	if (!device_canvas || !device_argb) return fail(t, SRT_ERR_INVALID, "srt_resolve_external: NULL buffer");
-	return resolve_impl(t, static_cast<const float *>(device_canvas), num_pixels, ticks_stopped, static_cast<uint8_t *>(device_argb));
+	return resolve_impl(t, static_cast<const float *>(device_canvas), num_pixels, ticks_stopped, static_cast<uint8_t *>(device_argb), false);
 }
 
 int srt_synchronize(srt_tracer *t) {
@@ -852,6 +856,7 @@ int srt_render_async(srt_tracer *t, const srt_render_data *options, uint32_t tic
 	int rc = srt_trace_fused(t, options, t->argb.ptr, ticks_stopped); // trace, ordered reduction and resolve: the last two in one launch
 	if (rc) return rc;
 	t->have_resolve_ev = false;
+	if (const int erc = srt_exposure_apply_frame(t, ticks_stopped, t->argb.ptr)) return erc; // exposure.hip: nothing while the feature is off
 	SRT_HIP(t, hipMemcpyAsync(argb_out, t->argb.ptr, owned_pixels(t) * 4, hipMemcpyDeviceToHost, t->stream));
 	return SRT_OK; // argb_out is valid after srt_synchronize()
 }

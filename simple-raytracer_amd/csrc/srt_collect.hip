@@ -276,7 +276,8 @@ int srt_resolve_gathered(srt_tracer *t, uint32_t ticks_stopped) {
 	if (!c || !c->have_full) return fail(t, SRT_ERR_STATE, "srt_resolve_gathered: nothing gathered on this handle (srt_gather as root)");
 	const size_t n = (size_t)t->width * t->height;
 	SRT_HIP(t, c->full_argb.reserve(n * 4));
-	return srt_resolve_external(t, c->full.ptr, (uint32_t)n, ticks_stopped, c->full_argb.ptr);
+	if (const int rc = srt_resolve_external(t, c->full.ptr, (uint32_t)n, ticks_stopped, c->full_argb.ptr)) return rc;
+	return srt_exposure_apply(t, c->full.ptr, (float)ticks_stopped, n, c->full_argb.ptr); // exposure.hip: nothing while the feature is off
 }
 
 int srt_gathered_buffers(srt_tracer *t, void **canvas, void **argb) {
@@ -364,6 +365,7 @@ srt_tracer *resolver_of(srt_group *g) {
 		g->resolver = r;
 	}
 	g->resolver->stream = root->stream;
+	g->resolver->ex = root->ex; // one exposure state per group, the first member's (srt_group_set_exposure)
 	return g->resolver;
 }
 
@@ -832,6 +834,30 @@ int srt_group_read_denoise_history(srt_group *g, float *colour_count, float *mom
 	return SRT_OK;
 }
 
+// ---- exposure on a group: the first member's state, which the group's resolves on the first device go through ----
+int srt_group_set_exposure(srt_group *g, const srt_exposure_params *p) {
+	if (!g) return SRT_ERR_INVALID;
+	const int rc = srt_set_exposure(g->t[0], p);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+int srt_group_reset_exposure(srt_group *g) {
+	if (!g) return SRT_ERR_INVALID;
+	const int rc = srt_reset_exposure(g->t[0]);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+int srt_group_read_exposure(srt_group *g, float *log2_exposure, float *exposure, uint32_t hist[256], uint32_t counts[2]) {
+	if (!g) return SRT_ERR_INVALID;
+	const int rc = srt_read_exposure(g->t[0], log2_exposure, exposure, hist, counts);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+int srt_group_last_resolve_exposed(const srt_group *g, int *exposed) {
+	if (!g) return SRT_ERR_INVALID;
+	return srt_last_resolve_exposed(g->t[0], exposed);
+}
+
 int srt_group_get_counters(srt_group *g, srt_counters *out) {
 	if (!g || !out) return SRT_ERR_INVALID;
 	memset(out, 0, sizeof *out);
@@ -873,6 +899,7 @@ int srt_render_pipelined(srt_tracer *t, const srt_render_data *options, uint32_t
 	const int slot = (int)(c->frames_enqueued & 1);
 	int rc = srt_trace_fused(t, options, c->dev_argb[slot], ticks_stopped); // the last reduction resolves into this frame's own image
 	if (rc != SRT_OK) return rc;
+	if ((rc = srt_exposure_apply_frame(t, ticks_stopped, c->dev_argb[slot])) != SRT_OK) return rc; // exposure.hip: nothing while the feature is off
 	SRT_HIP(t, hipEventRecord(c->resolved[slot], t->stream));
 	SRT_HIP(t, hipStreamWaitEvent(c->copy_stream, c->resolved[slot], 0));
 	SRT_HIP(t, hipMemcpyAsync(c->pinned[slot], c->dev_argb[slot], bytes, hipMemcpyDeviceToHost, c->copy_stream));

@@ -134,6 +134,15 @@ struct AccelDevice {
 	}
 };
 
+// Exposure for the resolve (exposure.hip; srt_set_exposure): the switch and its parameters, and the device record that holds
+// the histogram, the adaptation state and the scalar the exposed resolve reads (made when the feature is first enabled)
+struct ExposureState {
+	bool on = false;
+	bool last_exposed = false; // srt_last_resolve_exposed: the last resolve of a site went through the exposed kernel
+	srt_exposure_params p{};
+	DevBuf<uint32_t> record;
+};
+
 struct SrtCollect; // srt_collect.hip: RCCL communicator, gathered canvases, frame pipeline
 
 struct srt_tracer {
@@ -277,6 +286,8 @@ struct srt_tracer {
 	bool tex_active = false;         // a material of the current scene has a texture bound, or tex_tm_active: dispatches launch the textured kernels
 	bool last_trace_textured = false; // srt_last_trace_textured
 	int last_trace_class = 0;         // srt_last_trace_class
+	ExposureState ex_own;             // exposure.hip ...
+	ExposureState *ex = &ex_own;      // ... through this: a group's full-frame resolver handle shares the first member's (srt_collect.hip resolver_of)
 	uint32_t last_trace_plane_form = 0; // srt_last_trace_plane_form
 	hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;
 	bool have_trace_ev = false, have_resolve_ev = false, have_kernel_ev = false;
@@ -367,6 +378,14 @@ void srt_temporal_drop(srt_tracer *t);
 int srt_motion_update_scene(srt_tracer *t, const std::vector<uint8_t> &bytes, int rc);
 /* per-triangle motion, before a feature pass: the frame's world-vertex table, written when the scene has changed since */
 int srt_vertex_table_sync(srt_tracer *t);
+/* exposure.hip, behind a site's own resolve into `argb`: with the feature on, the metering (AUTO) and the exposed resolve of
+ * num_pixels float4 of `source` / divisor over the same image, on the handle's stream; off: nothing. Sets last_exposed. */
+int srt_exposure_apply(srt_tracer *t, const float *source, float divisor, size_t num_pixels, uint8_t *argb);
+/* ... for the render calls, whose frame is the canvas or, with the handle's denoiser on, the filter's image (divided already) */
+static inline int srt_exposure_apply_frame(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
+	if (t->dn_on && t->dn_filtered) return srt_exposure_apply(t, t->dn_col.ptr + (size_t)t->dn_out * full_pixels(t) * 4, 1.0f, full_pixels(t), argb);
+	return srt_exposure_apply(t, t->canvas, (float)ticks_stopped, owned_pixels(t), argb);
+}
 /* srt_trace whose last reduction also resolves into fused_argb (device, owned pixels x 4 bytes; NULL: plain srt_trace); with a
  * denoiser on, the feature pass and the filter (a group member on its own: the plain resolve) follow the reductions. A
  * sequence of file-local steps in srt_abi.hip; the arithmetic they share with the host unit check is trace_plan.h's */

@@ -264,6 +264,34 @@ class Tracer {
 		check(group ? srt_group_last_filter_spatial_variance(group, &ran) : srt_last_filter_spatial_variance(handle, &ran));
 		return ran != 0;
 	}
+	/// Exposure for the resolve (srt_set_exposure): every frame's bytes are tonemap(colour * exposure). automatic: the exposure is
+	/// metered on the device from the frame's luminance histogram and ev is a bias on it; else it is 2^ev. adapt in (0, 1]: how
+	/// much of the way to a new metered value one frame goes, in log2 (1: at once). One device or a group (the group's state
+	/// lives on device 0). Never waits for the device.
+	void set_exposure(bool automatic = true, float ev = 0.0f, float adapt = 1.0f) {
+		srt_exposure_params p;
+		check(srt_exposure_defaults(&p));
+		p.mode = automatic ? SRT_EXPOSURE_AUTO : SRT_EXPOSURE_MANUAL;
+		p.ev = ev;
+		p.adapt = adapt;
+		check(group ? srt_group_set_exposure(group, &p) : srt_set_exposure(handle, &p));
+	}
+	/// ... off: the plain resolve alone, and the adaptation starts anew when it is turned on again
+	void clear_exposure() { check(group ? srt_group_set_exposure(group, nullptr) : srt_set_exposure(handle, nullptr)); }
+	/// Forget the adaptation state: the next metered frame adopts its target (a cut to another scene)
+	void reset_exposure() { check(group ? srt_group_reset_exposure(group) : srt_reset_exposure(handle)); }
+	/// The exposure of the last exposed frame and its log2 (waits for the device; for a readout, not for the frame loop)
+	float read_exposure(float *log2_exposure = nullptr) {
+		float e = 1.0f;
+		check(group ? srt_group_read_exposure(group, log2_exposure, &e, nullptr, nullptr) : srt_read_exposure(handle, log2_exposure, &e, nullptr, nullptr));
+		return e;
+	}
+	/// Whether the last frame's bytes went through the exposed resolve
+	bool last_resolve_exposed() {
+		int exposed = 0;
+		check(group ? srt_group_last_resolve_exposed(group, &exposed) : srt_last_resolve_exposed(handle, &exposed));
+		return exposed != 0;
+	}
 	/// Object motion for the temporal stage (srt_set_denoise_object_motion): the history survives an update_scene that only
 	/// moves spheres, planes or model instances. Needs set_denoise_temporal first; the clear_canvas / update_scene / render
 	/// order of the frame loop stays as it is. Single-device tracers only (a group gathers no shape indices).

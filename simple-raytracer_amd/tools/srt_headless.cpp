@@ -17,6 +17,8 @@
 //                (Tracer::set_denoise_history_clamp; 0 < G <= 64, 1 is the library's advice); an error without --temporal
 // --history-feedback: with --temporal, the first a-trous pass's output is what enters the history (Tracer::set_denoise_history_feedback);
 //                an error without --temporal
+// --exposure auto[:EVBIAS] | EV: the bytes go through the exposed resolve (Tracer::set_exposure): metered on the device from every
+//                frame's luminance histogram, with an optional bias in stops, or a fixed 2^EV; the exposure is printed at the end
 // --move DX: the camera moves by DX along x every frame and every frame clears the canvas, as the front-end does while moving
 // --move-shape I DX: with --temporal, shape I (a sphere, a plane or a model instance) moves by DX along x every frame and every
 //                frame clears the canvas, as the front-end does while a gizmo is dragged; turns object motion on
@@ -128,6 +130,8 @@ int main(int argc, char **argv) {
 	bool temporal = false, demodulate = false, history_illumination = false, history_feedback = false;
 	float history_clamp = 0.0f;
 	bool clamp_given = false;
+	bool exposure = false, exposure_auto = false;
+	float exposure_ev = 0.0f;
 	float move = 0.0f, shape_move = 0.0f;
 	int move_shape = -1;
 	bool moving = false;
@@ -191,12 +195,24 @@ int main(int argc, char **argv) {
 		else if (a == "--history-illumination") history_illumination = true;
 		else if (a == "--history-clamp") history_clamp = std::strtof(next(), nullptr), clamp_given = true;
 		else if (a == "--history-feedback") history_feedback = true;
+		else if (a == "--exposure") { // auto[:EVBIAS] | EV
+			const std::string v = next();
+			char *end = nullptr;
+			exposure = true;
+			exposure_auto = v.rfind("auto", 0) == 0;
+			const char *num = exposure_auto ? (v.size() > 4 && v[4] == ':' ? v.c_str() + 5 : "") : v.c_str();
+			exposure_ev = *num ? std::strtof(num, &end) : 0.0f;
+			if ((exposure_auto && v.size() > 4 && v[4] != ':') || (!exposure_auto && !*num) || (*num && (!end || *end)) || !(exposure_ev >= -32.0f && exposure_ev <= 32.0f)) {
+				std::cerr << "--exposure takes auto, auto:EVBIAS or EV, |EV| <= 32\n";
+				return 2;
+			}
+		}
 		else if (a == "--move") move = std::strtof(next(), nullptr), moving = true;
 		else if (a == "--move-shape") move_shape = std::atoi(next()), shape_move = std::strtof(next(), nullptr);
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
+			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
@@ -335,6 +351,7 @@ int main(int argc, char **argv) {
 	if (bvh) tracer.set_acceleration(SRT_ACCEL_BVH);
 	tracer.set_acceleration_build_order(bvh_order); // (of --bvh-build device; else no effect)
 	if (bvh_build_device) tracer.set_acceleration_build(SRT_BUILD_DEVICE, bvh_build_min); // (models of at least MIN triangles; without --bvh: no effect)
+	if (exposure) tracer.set_exposure(exposure_auto, exposure_ev);
 	if (denoise >= 0) tracer.set_denoise(denoise);
 	if (demodulate) tracer.set_denoise_demodulation();
 	if (spatial_variance > 0) tracer.set_denoise_spatial_variance((uint32_t)spatial_variance);
@@ -450,6 +467,11 @@ int main(int argc, char **argv) {
 	srt_counters c = tracer.counters();
 	std::printf("%d frame(s) %dx%d x %d spp: %.3f s, %.1f Mray/s, %llu NaN pixels\n", frames, width, height, spp, secs,
 	            (double)c.rays / secs / 1e6, (unsigned long long)c.nan_pixels);
+	if (exposure) {
+		float log2_exposure = 0.0f;
+		const float e = tracer.read_exposure(&log2_exposure);
+		std::printf("exposure %s: %.6g (2^%.4f)%s\n", exposure_auto ? "auto" : "manual", e, log2_exposure, tracer.last_resolve_exposed() ? "" : " -- NOT applied");
+	}
 
 	if (!out.empty()) save_ppm(out, pixels, width, height);
 	if (!dump_prefix.empty()) {

@@ -62,6 +62,9 @@ ABI_SYMBOLS = [
     "srt_set_acceleration_build", "srt_group_set_acceleration_build", "srt_acceleration_build_info", "srt_last_build_kernel_ms",
     "srt_bvh_morton_order_host", "srt_bvh_morton_wide_host",
     "srt_set_acceleration_build_order", "srt_group_set_acceleration_build_order", "srt_bvh_median_order_host", "srt_bvh_median_wide_host",
+    "srt_exposure_defaults", "srt_exposure_check_host", "srt_set_exposure", "srt_group_set_exposure", "srt_reset_exposure",
+    "srt_group_reset_exposure", "srt_read_exposure", "srt_group_read_exposure", "srt_last_resolve_exposed",
+    "srt_group_last_resolve_exposed",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -398,6 +401,47 @@ class TemporalParams(C.Structure):
 assert C.sizeof(TemporalParams) == 32
 
 
+EXPOSURE_MANUAL, EXPOSURE_AUTO = 0, 1
+
+
+class ExposureParams(C.Structure):
+    """include/srt_types.h srt_exposure_params"""
+    _fields_ = [("enable", C.c_int32), ("mode", C.c_int32), ("ev", C.c_float), ("key", C.c_float), ("low_permille", C.c_int32),
+                ("high_permille", C.c_int32), ("adapt", C.c_float), ("min_ev", C.c_float), ("max_ev", C.c_float), ("reserved", C.c_int32 * 3)]
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n == "reserved" else getattr(self, n)) for n, _ in self._fields_}
+
+
+assert C.sizeof(ExposureParams) == 48
+
+
+def _exposure_params(kw, who):
+    """srt_exposure_defaults() overridden by kw; mode may be "manual" / "auto"."""
+    d = ExposureParams()
+    if load_library().srt_exposure_defaults(C.byref(d)):
+        raise SrtError("srt_exposure_defaults failed")
+    for k, v in kw.items():
+        if k not in d.as_dict():
+            raise TypeError(f"{who}: unknown parameter {k}")
+        if k == "mode" and isinstance(v, str):
+            v = {"manual": EXPOSURE_MANUAL, "auto": EXPOSURE_AUTO}[v]
+        if k == "reserved":
+            v = (C.c_int32 * 3)(*v)
+        setattr(d, k, v)
+    return d
+
+
+def exposure_defaults():
+    """srt_exposure_defaults (host only, no GPU needed) as a dict."""
+    return _exposure_params({}, "exposure_defaults").as_dict()
+
+
+def exposure_check_host(**kw):
+    """srt_exposure_check_host of the defaults overridden by kw (host only): True when srt_set_exposure would accept them."""
+    return load_library().srt_exposure_check_host(C.byref(_exposure_params(kw, "exposure_check_host"))) == 0
+
+
 def temporal_defaults():
     """srt_temporal_defaults (host only, no GPU needed) as a dict."""
     d = TemporalParams()
@@ -630,6 +674,15 @@ def _bind(lib):
         lib.srt_selftest_diffuse_bounce.argtypes = [vp, u32p, C.c_uint32, u32p, u32p, u32p, C.POINTER(C.c_uint64)]
     if hasattr(lib, "srt_bernoulli_threshold_host"):
         lib.srt_bernoulli_threshold_host.argtypes = [C.c_float, C.POINTER(C.c_uint64)]
+    if hasattr(lib, "srt_set_exposure"):  # (an older library, SRT_LIB, in an A/B run)
+        fp, u32p = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+        lib.srt_exposure_defaults.argtypes = [C.POINTER(ExposureParams)]
+        lib.srt_exposure_check_host.argtypes = [C.POINTER(ExposureParams)]
+        for pre in ("srt_", "srt_group_"):
+            getattr(lib, pre + "set_exposure").argtypes = [vp, C.POINTER(ExposureParams)]
+            getattr(lib, pre + "reset_exposure").argtypes = [vp]
+            getattr(lib, pre + "read_exposure").argtypes = [vp, fp, fp, u32p, u32p]
+            getattr(lib, pre + "last_resolve_exposed").argtypes = [vp, C.POINTER(C.c_int)]
     return lib
 
 
@@ -757,7 +810,37 @@ class _Denoise:
                 "camera": cam}
 
 
-class Tracer(_Denoise):
+class _Exposure:
+    """Exposure for the resolve (srt_set_exposure), shared by Tracer and TracerGroup the way _Denoise is."""
+
+    def set_exposure(self, enable=True, **kw):
+        """Turn exposure on with srt_exposure_defaults() overridden by kw (mode "manual" / "auto" or EXPOSURE_*, ev, key,
+        low_permille, high_permille, adapt, min_ev, max_ev), or off with enable=False (forgets the adaptation state)."""
+        if not enable:
+            self._check(self._dn("set_exposure", None))
+            return
+        self._check(self._dn("set_exposure", C.byref(_exposure_params(kw, "set_exposure"))))
+
+    def reset_exposure(self):
+        """Forget the adaptation state: the next metered frame adopts its target."""
+        self._check(self._dn("reset_exposure"))
+
+    def read_exposure(self):
+        """dict: log2_exposure, exposure (numpy float32), hist (256 uint32), metered, left_out. Waits for the stream."""
+        l2, e = C.c_float(0), C.c_float(0)
+        hist, counts = np.zeros(256, np.uint32), (C.c_uint32 * 2)()
+        self._check(self._dn("read_exposure", C.byref(l2), C.byref(e), hist.ctypes.data_as(C.POINTER(C.c_uint32)), counts))
+        return {"log2_exposure": np.float32(l2.value), "exposure": np.float32(e.value), "hist": hist, "metered": int(counts[0]),
+                "left_out": int(counts[1])}
+
+    def last_resolve_exposed(self):
+        """True when the last resolving call ran the exposed resolve."""
+        out = C.c_int(0)
+        self._check(self._dn("last_resolve_exposed", C.byref(out)))
+        return bool(out.value)
+
+
+class Tracer(_Denoise, _Exposure):
     """Mirror of the reference's `class Tracer`. Field and method names are the
     reference's; records are numpy scalars of records.RENDER_DATA / SCENE_DATA."""
 
@@ -1185,7 +1268,7 @@ class Tracer(_Denoise):
         self.owned_rows = self.lib.srt_partition_owned_rows(self.height, rank, world, rows_per_block)
 
 
-class TracerGroup(_Denoise):
+class TracerGroup(_Denoise, _Exposure):
     """One process driving several GPUs (srt_group_*): the reference's Tracer interface over a row partition,
     collected with one ncclGather per frame."""
 
