@@ -936,6 +936,47 @@ int srt_group_read_exposure(srt_group *g, float *log2_exposure, float *exposure,
 int srt_last_resolve_exposed(const srt_tracer *t, int *exposed);
 int srt_group_last_resolve_exposed(const srt_group *g, int *exposed);
 
+/* ---- bloom for the resolve (new; no counterpart in the reference) -------------------------------------------------------
+ * With bloom enabled every site that resolves a picture (the list above) resolves as before and then overwrites its ARGB image
+ * with tonemap(x + intensity * glow), on the handle's stream, without a wait for the host. With exposure on as well the
+ * composite takes the place of the exposed resolve; exposure metering keeps reading the un-bloomed colour. Off (the default):
+ * the library launches what it launches without the feature. srt_resolve_external keeps the plain bytes. A handle that holds
+ * interleaved rows (srt_set_partition with world > 1, a group member) is not a picture: its own resolve is not bloomed and
+ * srt_last_resolve_bloomed reports 0; the gathered frame (srt_resolve_gathered, srt_group_render, srt_group_resolve_denoised)
+ * is bloomed on the root. A group keeps ONE state, on its first device.
+ *
+ * The arithmetic is float, unfused, in the order written here; / is correctly rounded. x = (c / divisor) * e per channel is
+ * the colour the site exposes: c the canvas and divisor (float)ticks_stopped, or the denoiser's image and 1; e the exposure
+ * scalar in device memory with exposure on, else 1.0f. Alpha is never used; a pyramid texel's alpha is 0.
+ *   1 prefilter, per pixel: L = 0.2126 x.r + 0.7152 x.g + 0.0722 x.b (left to right). If any of x.r, x.g, x.b, L is not
+ *     finite, or !(L > 0), the pixel contributes (0, 0, 0). Otherwise g = L - threshold; if knee > 0: s = clamp((L - threshold)
+ *     + knee, 0, 2 * knee), q = (s * s) / (4 * knee), g = max(g, q); if clamp > 0: g = min(g, clamp); if !(g > 0) the pixel
+ *     contributes 0, otherwise bright = x * (g / L): one division, three products.
+ *   2 reduce, level k - 1 (level 0: the prefiltered frame) to level k: w_k = (w_{k-1} + 1) / 2, h_k = (h_{k-1} + 1) / 2.
+ *     Separable, horizontal first into a w_k x h_{k-1} intermediate, then vertical. Destination index i takes source indices
+ *     2i-1, 2i, 2i+1, 2i+2, clamped to the edge, as a, b, c, d: ((a + d) + 3.0f * (b + c)) * 0.125f. The effective level
+ *     count is `levels`, cut off after the first level that is 1 x 1.
+ *   3 expand-and-add, from the top level down: up_last = down_last; up_k = down_k + scatter * expand(up_{k+1}). expand is
+ *     separable, horizontal first: destination 2i is 0.75f * s[i] + 0.25f * s[i-1], destination 2i+1 is 0.75f * s[i] +
+ *     0.25f * s[i+1], source indices clamped to the edge. In place: one pyramid per handle.
+ *   4 composite, at full resolution: out = x + intensity * expand(up_0) per channel; argb = tonemap(out). */
+int srt_bloom_defaults(srt_bloom_params *out); /* enable 1, threshold 1, knee 0.5, intensity 0.1, scatter 0.7, clamp 64, levels 6 */
+/* Host-only: the validation srt_set_bloom applies to an enabled block (ranges as in srt_types.h, every float finite, reserved 0).
+ * SRT_OK or SRT_ERR_INVALID. */
+int srt_bloom_check_host(const srt_bloom_params *p);
+/* p NULL or enable == 0: off. SRT_ERR_INVALID as srt_bloom_check_host. The first enabling call allocates the handle's pyramid
+ * (about a third of a frame's float4). */
+int srt_set_bloom(srt_tracer *t, const srt_bloom_params *p);
+int srt_group_set_bloom(srt_group *g, const srt_bloom_params *p);
+/* Waits for the handle's stream. up_level of the last bloomed frame: *w x *h texels of 4 floats (r, g, b, 0) into rgba_out, of
+ * cap_pixels texels; rgba_out NULL: the size only. SRT_ERR_INVALID: level outside 0 .. the frame's effective level count - 1,
+ * or cap_pixels too small; SRT_ERR_STATE: no bloomed frame yet. w, h may be NULL. */
+int srt_read_bloom(srt_tracer *t, int level, float *rgba_out, size_t cap_pixels, int *w, int *h);
+int srt_group_read_bloom(srt_group *g, int level, float *rgba_out, size_t cap_pixels, int *w, int *h);
+/* For tests: *bloomed = 1 when the last resolving call on the handle (the group: on its first device) ran the bloom composite. */
+int srt_last_resolve_bloomed(const srt_tracer *t, int *bloomed);
+int srt_group_last_resolve_bloomed(const srt_group *g, int *bloomed);
+
 /* Device self-test of the deterministic math (tests only). Walks r = 0, stride, ... over
  * all 2^32 RNG outputs: out[0..2] = mismatch counts of the kernel-local sqrt / log / cos
  * specialisations against their generic definitions (must be 0); out[3..7] = sums of the

@@ -167,6 +167,20 @@ typedef struct srt_exposure_params {
 	int32_t reserved[3];   /* must be 0 */
 } srt_exposure_params;
 
+/* Bloom for the resolve (srt_set_bloom in srt_abi.h, where the arithmetic is written down; new, no counterpart in the
+ * reference): the part of the exposed colour above a threshold is blurred over an image pyramid and added before the tone map. */
+#define SRT_BLOOM_MAX_LEVELS 8
+typedef struct srt_bloom_params {
+	int32_t enable;   /* 0: off (the library launches what it launches without the feature) */
+	float threshold;  /* finite, >= 0: luminance of the exposed colour above which a pixel glows (default 1) */
+	float knee;       /* finite, 0 <= knee <= threshold: half width of the soft onset around the threshold; 0: a hard one (default 0.5) */
+	float intensity;  /* finite, 0 <= intensity <= 16: weight of the glow in the composite (default 0.1) */
+	float scatter;    /* finite, 0 <= scatter <= 1: weight of a coarser level when it is added to the next finer one (default 0.7) */
+	float clamp;      /* finite; 0: none; > 0: the largest luminance a pixel may contribute, the firefly limit (default 64) */
+	int32_t levels;   /* 1..SRT_BLOOM_MAX_LEVELS pyramid levels; cut off after the first that is 1 x 1 (default 6) */
+	int32_t reserved; /* must be 0 */
+} srt_bloom_params;
+
 /* Albedo textures (srt_set_textures, srt_set_material_textures; include/srt_abi.h). */
 #define SRT_MAX_TEXTURES 64
 enum { SRT_FILTER_LINEAR = 0, SRT_FILTER_NEAREST = 1 };
@@ -239,6 +253,9 @@ SRT_STATIC_ASSERT(offsetof(srt_exposure_params, low_permille) == 16, "ExposurePa
 SRT_STATIC_ASSERT(offsetof(srt_exposure_params, adapt) == 24, "ExposureParams.adapt@24");
 SRT_STATIC_ASSERT(offsetof(srt_exposure_params, min_ev) == 28, "ExposureParams.min_ev@28");
 SRT_STATIC_ASSERT(offsetof(srt_exposure_params, reserved) == 36, "ExposureParams.reserved@36");
+SRT_STATIC_ASSERT(sizeof(srt_bloom_params) == 32, "BloomParams 32 B");
+SRT_STATIC_ASSERT(offsetof(srt_bloom_params, clamp) == 20, "BloomParams.clamp@20");
+SRT_STATIC_ASSERT(offsetof(srt_bloom_params, levels) == 24, "BloomParams.levels@24");
 SRT_STATIC_ASSERT(sizeof(srt_material_texture) == 16, "MaterialTexture 16 B");
 SRT_STATIC_ASSERT(offsetof(srt_material_texture, scale_u) == 8, "MaterialTexture.scale_u@8");
 

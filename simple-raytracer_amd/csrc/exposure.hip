@@ -183,9 +183,12 @@ int forget_state(srt_tracer *t) {
 
 } // namespace
 
-int srt_exposure_apply(srt_tracer *t, const float *source, float divisor, size_t num_pixels, uint8_t *argb) {
+int srt_exposure_apply(srt_tracer *t, const float *source, float divisor, uint32_t w, uint32_t h, bool picture, uint8_t *argb) {
 	ExposureState *ex = t->ex;
+	const size_t num_pixels = (size_t)w * h;
 	ex->last_exposed = ex->on;
+	const bool bloom = srt_bloom_begin(t, picture, num_pixels);
+	if (bloom && !ex->on) return srt_bloom_resolve(t, source, divisor, nullptr, w, h, argb); // (x * 1.0f is x)
 	if (!ex->on || num_pixels == 0) return SRT_OK;
 	uint32_t *rec = ex->record.ptr;
 	if (ex->p.mode == SRT_EXPOSURE_AUTO) {
@@ -204,6 +207,8 @@ int srt_exposure_apply(srt_tracer *t, const float *source, float divisor, size_t
 		mp.low_permille = (uint32_t)ex->p.low_permille, mp.high_permille = (uint32_t)ex->p.high_permille;
 		hipLaunchKernelGGL(srt_exposure_meter_kernel, dim3(1), dim3(256), 0, t->stream, mp);
 	}
+	// bloom.hip's composite is the exposed resolve plus the glow: the frame is not written a third time
+	if (bloom) return srt_bloom_resolve(t, source, divisor, reinterpret_cast<const float *>(rec + SRT_EX_EXPOSURE), w, h, argb);
 	ExposureResolveParams rp;
 	rp.source = reinterpret_cast<const float4 *>(source);
 	rp.argb = reinterpret_cast<uint32_t *>(argb);

@@ -218,6 +218,7 @@ void srt_destroy(srt_tracer *t) {
 	for (int k = 0; k < 2; k++) t->vm_tri[k].release(), t->vm_rows[k].release();
 	t->vm_first_dev.release();
 	t->ex_own.record.release();
+	t->bl_own.pyramid.release();
 	srt_texture_release(t);
 	if (t->ev_t0) (void)hipEventDestroy(t->ev_t0);
 	if (t->ev_t1) (void)hipEventDestroy(t->ev_t1);
@@ -810,13 +811,13 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 }
 
 // srt_resolve / srt_resolve_external: launch_resolve between the resolve timer's events; `expose`: with the handle's exposure
-// on, its launches (exposure.hip) behind it, inside the same span
+// or bloom on, their launches (exposure.hip, bloom.hip) behind it, inside the same span: the image is the handle's own rows
 static int resolve_impl(srt_tracer *t, const float *canvas, uint32_t num_pixels, uint32_t ticks_stopped, uint8_t *argb, bool expose) {
 	SRT_HIP(t, hipSetDevice(t->device));
 	SRT_HIP(t, hipEventRecord(t->ev_r0, t->stream));
 	if (const int rc = launch_resolve(t, canvas, num_pixels, ticks_stopped, argb)) return rc;
 	if (expose)
-		if (const int rc = srt_exposure_apply(t, canvas, (float)ticks_stopped, num_pixels, argb)) return rc;
+		if (const int rc = srt_exposure_apply(t, canvas, (float)ticks_stopped, (uint32_t)t->width, (uint32_t)t->owned_rows, t->world == 1, argb)) return rc;
 	SRT_HIP(t, hipEventRecord(t->ev_r1, t->stream));
 	t->have_resolve_ev = true;
 	return SRT_OK;

@@ -277,7 +277,8 @@ int srt_resolve_gathered(srt_tracer *t, uint32_t ticks_stopped) {
 	const size_t n = (size_t)t->width * t->height;
 	SRT_HIP(t, c->full_argb.reserve(n * 4));
 	if (const int rc = srt_resolve_external(t, c->full.ptr, (uint32_t)n, ticks_stopped, c->full_argb.ptr)) return rc;
-	return srt_exposure_apply(t, c->full.ptr, (float)ticks_stopped, n, c->full_argb.ptr); // exposure.hip: nothing while the feature is off
+	// exposure.hip, bloom.hip: nothing while the features are off; the gathered frame is a picture
+	return srt_exposure_apply(t, c->full.ptr, (float)ticks_stopped, (uint32_t)t->width, (uint32_t)t->height, true, c->full_argb.ptr);
 }
 
 int srt_gathered_buffers(srt_tracer *t, void **canvas, void **argb) {
@@ -366,6 +367,7 @@ srt_tracer *resolver_of(srt_group *g) {
 	}
 	g->resolver->stream = root->stream;
 	g->resolver->ex = root->ex; // one exposure state per group, the first member's (srt_group_set_exposure)
+	g->resolver->bl = root->bl; // ... and one bloom state (srt_group_set_bloom)
 	return g->resolver;
 }
 
@@ -856,6 +858,24 @@ int srt_group_read_exposure(srt_group *g, float *log2_exposure, float *exposure,
 int srt_group_last_resolve_exposed(const srt_group *g, int *exposed) {
 	if (!g) return SRT_ERR_INVALID;
 	return srt_last_resolve_exposed(g->t[0], exposed);
+}
+
+// ---- bloom on a group: the first member's state, as exposure ----
+int srt_group_set_bloom(srt_group *g, const srt_bloom_params *p) {
+	if (!g) return SRT_ERR_INVALID;
+	const int rc = srt_set_bloom(g->t[0], p);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+int srt_group_read_bloom(srt_group *g, int level, float *rgba_out, size_t cap_pixels, int *w, int *h) {
+	if (!g) return SRT_ERR_INVALID;
+	const int rc = srt_read_bloom(g->t[0], level, rgba_out, cap_pixels, w, h);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+int srt_group_last_resolve_bloomed(const srt_group *g, int *bloomed) {
+	if (!g) return SRT_ERR_INVALID;
+	return srt_last_resolve_bloomed(g->t[0], bloomed);
 }
 
 int srt_group_get_counters(srt_group *g, srt_counters *out) {

@@ -143,6 +143,16 @@ struct ExposureState {
 	DevBuf<uint32_t> record;
 };
 
+// Bloom for the resolve (bloom.hip; srt_set_bloom): the switch and its parameters, the pyramid (every level's float4 texels one
+// after the other, made when the feature is first enabled) and the shape of the last bloomed frame's (srt_read_bloom)
+struct BloomState {
+	bool on = false;
+	bool last_bloomed = false; // srt_last_resolve_bloomed: the last resolve of a site went through the bloom composite
+	srt_bloom_params p{};
+	DevBuf<float> pyramid;
+	int last_w = 0, last_h = 0, last_levels = 0;
+};
+
 struct SrtCollect; // srt_collect.hip: RCCL communicator, gathered canvases, frame pipeline
 
 struct srt_tracer {
@@ -288,6 +298,8 @@ struct srt_tracer {
 	int last_trace_class = 0;         // srt_last_trace_class
 	ExposureState ex_own;             // exposure.hip ...
 	ExposureState *ex = &ex_own;      // ... through this: a group's full-frame resolver handle shares the first member's (srt_collect.hip resolver_of)
+	BloomState bl_own;                // bloom.hip ...
+	BloomState *bl = &bl_own;         // ... shared the same way
 	uint32_t last_trace_plane_form = 0; // srt_last_trace_plane_form
 	hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;
 	bool have_trace_ev = false, have_resolve_ev = false, have_kernel_ev = false;
@@ -378,14 +390,22 @@ void srt_temporal_drop(srt_tracer *t);
 int srt_motion_update_scene(srt_tracer *t, const std::vector<uint8_t> &bytes, int rc);
 /* per-triangle motion, before a feature pass: the frame's world-vertex table, written when the scene has changed since */
 int srt_vertex_table_sync(srt_tracer *t);
-/* exposure.hip, behind a site's own resolve into `argb`: with the feature on, the metering (AUTO) and the exposed resolve of
- * num_pixels float4 of `source` / divisor over the same image, on the handle's stream; off: nothing. Sets last_exposed. */
-int srt_exposure_apply(srt_tracer *t, const float *source, float divisor, size_t num_pixels, uint8_t *argb);
+/* exposure.hip, behind a site's own resolve into `argb`: with exposure on, the metering (AUTO) and the exposed resolve of the
+ * w x h float4 of `source` / divisor over the same image, on the handle's stream; with bloom on and `picture` (the rows are a
+ * picture's, not the interleaved blocks a partitioned handle owns), bloom.hip's launches, whose composite takes the exposed
+ * resolve's place; both off: nothing. Sets last_exposed and last_bloomed. */
+int srt_exposure_apply(srt_tracer *t, const float *source, float divisor, uint32_t w, uint32_t h, bool picture, uint8_t *argb);
 /* ... for the render calls, whose frame is the canvas or, with the handle's denoiser on, the filter's image (divided already) */
 static inline int srt_exposure_apply_frame(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
-	if (t->dn_on && t->dn_filtered) return srt_exposure_apply(t, t->dn_col.ptr + (size_t)t->dn_out * full_pixels(t) * 4, 1.0f, full_pixels(t), argb);
-	return srt_exposure_apply(t, t->canvas, (float)ticks_stopped, owned_pixels(t), argb);
+	if (t->dn_on && t->dn_filtered)
+		return srt_exposure_apply(t, t->dn_col.ptr + (size_t)t->dn_out * full_pixels(t) * 4, 1.0f, (uint32_t)t->width, (uint32_t)t->height, true, argb);
+	return srt_exposure_apply(t, t->canvas, (float)ticks_stopped, (uint32_t)t->width, (uint32_t)t->owned_rows, t->world == 1, argb);
 }
+/* bloom.hip: whether a site's resolve of num_pixels is bloomed (the feature on, a picture, not empty); sets last_bloomed */
+bool srt_bloom_begin(srt_tracer *t, bool picture, size_t num_pixels);
+/* ... and its launches on the handle's stream: the pyramid of (source / divisor) * *exposure (NULL: 1.0f) and the composite
+ * over `argb` */
+int srt_bloom_resolve(srt_tracer *t, const float *source, float divisor, const float *exposure, uint32_t w, uint32_t h, uint8_t *argb);
 /* srt_trace whose last reduction also resolves into fused_argb (device, owned pixels x 4 bytes; NULL: plain srt_trace); with a
  * denoiser on, the feature pass and the filter (a group member on its own: the plain resolve) follow the reductions. A
  * sequence of file-local steps in srt_abi.hip; the arithmetic they share with the host unit check is trace_plan.h's */

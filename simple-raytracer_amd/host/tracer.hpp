@@ -292,6 +292,42 @@ class Tracer {
 		check(group ? srt_group_last_resolve_exposed(group, &exposed) : srt_last_resolve_exposed(handle, &exposed));
 		return exposed != 0;
 	}
+	/// Bloom for the resolve (srt_set_bloom): what of the exposed colour lies above `threshold` is blurred over `levels` pyramid
+	/// levels on the device and added with weight `intensity` before the tone map. A negative threshold or intensity, or
+	/// levels 0, keeps the library's default (1, 0.1, 6). With or without set_exposure; one device or a group (the group's
+	/// state lives on device 0). Never waits for the device.
+	void set_bloom(float threshold = -1.0f, float intensity = -1.0f, int levels = 0) {
+		srt_bloom_params p;
+		check(srt_bloom_defaults(&p));
+		if (threshold >= 0.0f) {
+			p.threshold = threshold;
+			if (p.knee > threshold) p.knee = threshold; // (0 <= knee <= threshold)
+		}
+		if (intensity >= 0.0f) p.intensity = intensity;
+		if (levels > 0) p.levels = levels;
+		check(group ? srt_group_set_bloom(group, &p) : srt_set_bloom(handle, &p));
+	}
+	/// ... off: the sites resolve as they do without it
+	void clear_bloom() { check(group ? srt_group_set_bloom(group, nullptr) : srt_set_bloom(handle, nullptr)); }
+	/// Level `level` of the last bloomed frame's pyramid, 4 floats per texel, into `rgba` (resized; nullptr: the size only).
+	/// Waits for the device; for a readout, not for the frame loop
+	void read_bloom(int level, std::vector<float> *rgba, int *w, int *h) {
+		int lw = 0, lh = 0;
+		check(group ? srt_group_read_bloom(group, level, nullptr, 0, &lw, &lh) : srt_read_bloom(handle, level, nullptr, 0, &lw, &lh));
+		if (rgba) {
+			rgba->resize((size_t)lw * (size_t)lh * 4);
+			const size_t n = (size_t)lw * (size_t)lh;
+			check(group ? srt_group_read_bloom(group, level, rgba->data(), n, &lw, &lh) : srt_read_bloom(handle, level, rgba->data(), n, &lw, &lh));
+		}
+		if (w) *w = lw;
+		if (h) *h = lh;
+	}
+	/// Whether the last frame's bytes went through the bloom composite
+	bool last_resolve_bloomed() {
+		int bloomed = 0;
+		check(group ? srt_group_last_resolve_bloomed(group, &bloomed) : srt_last_resolve_bloomed(handle, &bloomed));
+		return bloomed != 0;
+	}
 	/// Object motion for the temporal stage (srt_set_denoise_object_motion): the history survives an update_scene that only
 	/// moves spheres, planes or model instances. Needs set_denoise_temporal first; the clear_canvas / update_scene / render
 	/// order of the frame loop stays as it is. Single-device tracers only (a group gathers no shape indices).

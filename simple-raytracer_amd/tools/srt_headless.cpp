@@ -19,6 +19,9 @@
 //                an error without --temporal
 // --exposure auto[:EVBIAS] | EV: the bytes go through the exposed resolve (Tracer::set_exposure): metered on the device from every
 //                frame's luminance histogram, with an optional bias in stops, or a fixed 2^EV; the exposure is printed at the end
+// --bloom [THRESHOLD[:INTENSITY[:LEVELS]]]: the bright part of every frame glows (Tracer::set_bloom): what of the exposed colour
+//                lies above THRESHOLD is blurred over LEVELS pyramid levels and added with weight INTENSITY before the tone map;
+//                what is left out is the library's default. Works with and without --exposure
 // --move DX: the camera moves by DX along x every frame and every frame clears the canvas, as the front-end does while moving
 // --move-shape I DX: with --temporal, shape I (a sphere, a plane or a model instance) moves by DX along x every frame and every
 //                frame clears the canvas, as the front-end does while a gizmo is dragged; turns object motion on
@@ -132,6 +135,9 @@ int main(int argc, char **argv) {
 	bool clamp_given = false;
 	bool exposure = false, exposure_auto = false;
 	float exposure_ev = 0.0f;
+	bool bloom = false;
+	float bloom_threshold = -1.0f, bloom_intensity = -1.0f; // (negative: the library's default)
+	int bloom_levels = 0;
 	float move = 0.0f, shape_move = 0.0f;
 	int move_shape = -1;
 	bool moving = false;
@@ -207,12 +213,26 @@ int main(int argc, char **argv) {
 				return 2;
 			}
 		}
+		else if (a == "--bloom") { // [THRESHOLD[:INTENSITY[:LEVELS]]]: the value is optional, the library's defaults fill the rest
+			bloom = true;
+			if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {
+				const std::string v = argv[++i];
+				char *end = nullptr;
+				bloom_threshold = std::strtof(v.c_str(), &end);
+				if (end && *end == ':') bloom_intensity = std::strtof(end + 1, &end);
+				if (end && *end == ':') bloom_levels = (int)std::strtol(end + 1, &end, 10);
+				if (!end || *end || end == v.c_str()) {
+					std::cerr << "--bloom takes nothing, THRESHOLD, THRESHOLD:INTENSITY or THRESHOLD:INTENSITY:LEVELS\n";
+					return 2;
+				}
+			}
+		}
 		else if (a == "--move") move = std::strtof(next(), nullptr), moving = true;
 		else if (a == "--move-shape") move_shape = std::atoi(next()), shape_move = std::strtof(next(), nullptr);
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
+			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
@@ -352,6 +372,7 @@ int main(int argc, char **argv) {
 	tracer.set_acceleration_build_order(bvh_order); // (of --bvh-build device; else no effect)
 	if (bvh_build_device) tracer.set_acceleration_build(SRT_BUILD_DEVICE, bvh_build_min); // (models of at least MIN triangles; without --bvh: no effect)
 	if (exposure) tracer.set_exposure(exposure_auto, exposure_ev);
+	if (bloom) tracer.set_bloom(bloom_threshold, bloom_intensity, bloom_levels);
 	if (denoise >= 0) tracer.set_denoise(denoise);
 	if (demodulate) tracer.set_denoise_demodulation();
 	if (spatial_variance > 0) tracer.set_denoise_spatial_variance((uint32_t)spatial_variance);
@@ -471,6 +492,12 @@ int main(int argc, char **argv) {
 		float log2_exposure = 0.0f;
 		const float e = tracer.read_exposure(&log2_exposure);
 		std::printf("exposure %s: %.6g (2^%.4f)%s\n", exposure_auto ? "auto" : "manual", e, log2_exposure, tracer.last_resolve_exposed() ? "" : " -- NOT applied");
+	}
+	if (bloom) {
+		int w0 = 0, h0 = 0;
+		const bool ran = tracer.last_resolve_bloomed();
+		if (ran) tracer.read_bloom(0, nullptr, &w0, &h0);
+		std::printf("bloom: level 0 is %dx%d%s\n", w0, h0, ran ? "" : " -- NOT applied");
 	}
 
 	if (!out.empty()) save_ppm(out, pixels, width, height);

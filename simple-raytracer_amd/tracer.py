@@ -65,6 +65,8 @@ ABI_SYMBOLS = [
     "srt_exposure_defaults", "srt_exposure_check_host", "srt_set_exposure", "srt_group_set_exposure", "srt_reset_exposure",
     "srt_group_reset_exposure", "srt_read_exposure", "srt_group_read_exposure", "srt_last_resolve_exposed",
     "srt_group_last_resolve_exposed",
+    "srt_bloom_defaults", "srt_bloom_check_host", "srt_set_bloom", "srt_group_set_bloom", "srt_read_bloom", "srt_group_read_bloom",
+    "srt_last_resolve_bloomed", "srt_group_last_resolve_bloomed",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -442,6 +444,43 @@ def exposure_check_host(**kw):
     return load_library().srt_exposure_check_host(C.byref(_exposure_params(kw, "exposure_check_host"))) == 0
 
 
+BLOOM_MAX_LEVELS = 8
+
+
+class BloomParams(C.Structure):
+    """include/srt_types.h srt_bloom_params"""
+    _fields_ = [("enable", C.c_int32), ("threshold", C.c_float), ("knee", C.c_float), ("intensity", C.c_float), ("scatter", C.c_float),
+                ("clamp", C.c_float), ("levels", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+assert C.sizeof(BloomParams) == 32
+
+
+def _bloom_params(kw, who):
+    """srt_bloom_defaults() overridden by kw."""
+    d = BloomParams()
+    if load_library().srt_bloom_defaults(C.byref(d)):
+        raise SrtError("srt_bloom_defaults failed")
+    for k, v in kw.items():
+        if k not in d.as_dict():
+            raise TypeError(f"{who}: unknown parameter {k}")
+        setattr(d, k, v)
+    return d
+
+
+def bloom_defaults():
+    """srt_bloom_defaults (host only, no GPU needed) as a dict."""
+    return _bloom_params({}, "bloom_defaults").as_dict()
+
+
+def bloom_check_host(**kw):
+    """srt_bloom_check_host of the defaults overridden by kw (host only): True when srt_set_bloom would accept them."""
+    return load_library().srt_bloom_check_host(C.byref(_bloom_params(kw, "bloom_check_host"))) == 0
+
+
 def temporal_defaults():
     """srt_temporal_defaults (host only, no GPU needed) as a dict."""
     d = TemporalParams()
@@ -683,6 +722,14 @@ def _bind(lib):
             getattr(lib, pre + "reset_exposure").argtypes = [vp]
             getattr(lib, pre + "read_exposure").argtypes = [vp, fp, fp, u32p, u32p]
             getattr(lib, pre + "last_resolve_exposed").argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(lib, "srt_set_bloom"):  # (likewise)
+        ip = C.POINTER(C.c_int)
+        lib.srt_bloom_defaults.argtypes = [C.POINTER(BloomParams)]
+        lib.srt_bloom_check_host.argtypes = [C.POINTER(BloomParams)]
+        for pre in ("srt_", "srt_group_"):
+            getattr(lib, pre + "set_bloom").argtypes = [vp, C.POINTER(BloomParams)]
+            getattr(lib, pre + "read_bloom").argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_size_t, ip, ip]
+            getattr(lib, pre + "last_resolve_bloomed").argtypes = [vp, ip]
     return lib
 
 
@@ -840,7 +887,33 @@ class _Exposure:
         return bool(out.value)
 
 
-class Tracer(_Denoise, _Exposure):
+class _Bloom:
+    """Bloom for the resolve (srt_set_bloom), shared by Tracer and TracerGroup the way _Denoise is."""
+
+    def set_bloom(self, enable=True, **kw):
+        """Turn bloom on with srt_bloom_defaults() overridden by kw (threshold, knee, intensity, scatter, clamp, levels), or off
+        with enable=False."""
+        if not enable:
+            self._check(self._dn("set_bloom", None))
+            return
+        self._check(self._dn("set_bloom", C.byref(_bloom_params(kw, "set_bloom"))))
+
+    def read_bloom(self, level):
+        """up_level of the last bloomed frame: (h_level, w_level, 4) float32 (r, g, b, 0). Waits for the stream."""
+        w, h = C.c_int(0), C.c_int(0)
+        self._check(self._dn("read_bloom", int(level), None, 0, C.byref(w), C.byref(h)))
+        out = np.zeros((h.value, w.value, 4), np.float32)
+        self._check(self._dn("read_bloom", int(level), out.ctypes.data_as(C.POINTER(C.c_float)), out.size // 4, C.byref(w), C.byref(h)))
+        return out
+
+    def last_resolve_bloomed(self):
+        """True when the last resolving call ran the bloom composite."""
+        out = C.c_int(0)
+        self._check(self._dn("last_resolve_bloomed", C.byref(out)))
+        return bool(out.value)
+
+
+class Tracer(_Denoise, _Exposure, _Bloom):
     """Mirror of the reference's `class Tracer`. Field and method names are the
     reference's; records are numpy scalars of records.RENDER_DATA / SCENE_DATA."""
 
@@ -1268,7 +1341,7 @@ class Tracer(_Denoise, _Exposure):
         self.owned_rows = self.lib.srt_partition_owned_rows(self.height, rank, world, rows_per_block)
 
 
-class TracerGroup(_Denoise, _Exposure):
+class TracerGroup(_Denoise, _Exposure, _Bloom):
     """One process driving several GPUs (srt_group_*): the reference's Tracer interface over a row partition,
     collected with one ncclGather per frame."""
 
