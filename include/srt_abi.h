@@ -977,6 +977,87 @@ int srt_group_read_bloom(srt_group *g, int level, float *rgba_out, size_t cap_pi
 int srt_last_resolve_bloomed(const srt_tracer *t, int *bloomed);
 int srt_group_last_resolve_bloomed(const srt_group *g, int *bloomed);
 
+/* ---- noise metering and render-until-converged (new; no counterpart in the reference) ----------------------------------
+ * With the denoiser on (srt_set_denoise; iterations = 0 is enough) every dispatch adds (1/n) sum lum(radiance)^2 per pixel to
+ * the moments plane beside the canvas, and the handle counts the dispatches T and the samples P since the clear. One pass
+ * over both gives every pixel a relative standard error of its mean, a 256-bin histogram of it and the number of pixels
+ * below a threshold; the host turns the histogram into a noise level and a stopping rule. Off (the default): every call
+ * enqueues exactly what it enqueues without the feature. Needs the handle's denoiser on (else SRT_ERR_STATE); not available
+ * on a partitioned handle. A group keeps ONE state, on its first device, and meters the gathered planes there.
+ *
+ * THE DEFINITION (float32, every operation rounded on its own -- no fused multiply-add --, in the order written). For pixel q,
+ * with Tf = (float)T, Pf = (float)P:
+ *   L  = lum(canvas.r / Tf, canvas.g / Tf, canvas.b / Tf)      lum(r, g, b) = (0.2126f * r + 0.7152f * g) + 0.0722f * b
+ *   m2 = moments[q] / Tf
+ *   the pixel is left out (and counted as such) unless L and m2 are both finite
+ *   v  = m2 - L * L;  v = (v > 0) ? v : 0
+ *   se = sqrt(v / Pf)                                           the correctly rounded square root
+ *   d  = (L > luminance_floor) ? L : luminance_floor
+ *   r  = se / d                                                 IEEE division; the pixel is left out if r is not finite
+ *   bin = clamp((int)(bits(r) >> 20) - ((127 - 24) << 3), 0, 255)    eight bins per octave over 2^-24 .. 2^8; r == 0 and denormals in bin 0
+ *   below += (r <= threshold)
+ * hist[256], metered, left_out and below are exact integer sums. The noise level is the upper edge of the bin in which the
+ * ascending cumulative count first reaches (metered * permille + 999) / 1000, computed on the host as
+ *   level = ldexpf(SRT_NOISE_EIGHTHS[(bin + 1) & 7], ((bin + 1) >> 3) - 24)
+ * with the table below (2^(k/8) rounded to float; no exp2 enters the result). The bins cut an octave by mantissa bits, at
+ * 1 + k/8, and the level quotes 2^(k/8): the two agree at the octave's ends, and inside the level lies within the bin, up to
+ * 6 % below its upper edge. And
+ *   converged = metered > 0 && P >= min_samples && (uint64)below * 1000 >= (uint64)permille * metered.
+ * Two weaknesses of the estimator: dispatches with different num_samples are weighted equally in m2, so the estimate is exact
+ * only when every dispatch since the clear had the same sample count. And a pixel whose rare bright paths have not been
+ * sampled yet has a small sample variance and reads as converged: the rule cannot see light it has not found. */
+#define SRT_NOISE_EIGHTHS {0x1.000000p+0f, 0x1.172b84p+0f, 0x1.306fe0p+0f, 0x1.4bfdaep+0f, 0x1.6a09e6p+0f, 0x1.8ace54p+0f, 0x1.ae89fap+0f, 0x1.d5818ep+0f}
+int srt_noise_defaults(srt_noise_params *out); /* enable 1, threshold 0.05, luminance_floor 0.01, permille 950, min_samples 16, check_every 4 */
+/* Host-only: the validation srt_set_noise_meter applies to an enabled block (ranges as in srt_types.h, floats finite, reserved 0).
+ * SRT_OK or SRT_ERR_INVALID. */
+int srt_noise_check_host(const srt_noise_params *p);
+/* Host-only: the percentile, the level and the stopping rule as the read calls apply them to a record: hist[256],
+ * counts = {metered, left_out, below}, the T and P of the metering, params' permille and min_samples. */
+int srt_noise_evaluate_host(const uint32_t hist[256], const uint32_t counts[3], uint32_t T, uint32_t P, const srt_noise_params *params, srt_noise_result *result);
+/* p NULL or enable == 0: off (a metering in flight stays readable). SRT_ERR_INVALID as srt_noise_check_host; SRT_ERR_STATE: the
+ * denoiser is off, or the handle is partitioned. The first enabling call allocates the device record and its pinned copies. */
+int srt_set_noise_meter(srt_tracer *t, const srt_noise_params *p);
+int srt_group_set_noise_meter(srt_group *g, const srt_noise_params *p); /* the group's denoiser must be on (srt_group_set_denoise) */
+/* Asynchronous: on the handle's stream, behind what it holds, zeroes the record, launches the meter kernel over the canvas and
+ * the moments and copies the record (1,060 bytes) into pinned memory behind an event. SRT_ERR_STATE: the meter or the
+ * denoiser is off, or nothing is traced since the clear. */
+int srt_meter_noise(srt_tracer *t);
+int srt_group_meter_noise(srt_group *g); /* over the planes the last srt_group_trace_and_gather / srt_group_render gathered */
+/* The newest metering's result (the calls above, srt_resolve_noise_view, an automatic one). srt_poll_noise never blocks:
+ * *ready = 0 while the copy is in flight (result and hist are not written then). srt_read_noise waits for that copy's event
+ * only, not for the stream. hist may be NULL. Where nothing was ever metered on the handle srt_poll_noise reports *ready = 0
+ * and srt_read_noise returns SRT_ERR_STATE. */
+int srt_poll_noise(srt_tracer *t, srt_noise_result *result, uint32_t hist[256], int *ready);
+int srt_read_noise(srt_tracer *t, srt_noise_result *result, uint32_t hist[256]);
+int srt_group_poll_noise(srt_group *g, srt_noise_result *result, uint32_t hist[256], int *ready);
+int srt_group_read_noise(srt_group *g, srt_noise_result *result, uint32_t hist[256]);
+/* Asynchronous: meters as srt_meter_noise and, in the same pass, overwrites the handle's ARGB image (srt_read_argb) with a heat
+ * map. With bin(x) the bin formula above, bt = bin(threshold) and dd = clamp(bin(r) - bt + 32, 0, 64) a pixel is
+ * R = dd * 255 / 64 (integer), G = 255 - R, B = 0; a left-out pixel is R = 255, G = 0, B = 255. Bytes as the resolve packs
+ * them: 255 | R << 8 | G << 16 | B << 24. Green is four octaves below the threshold, red four above. */
+int srt_resolve_noise_view(srt_tracer *t);
+int srt_group_resolve_noise_view(srt_group *g);
+int srt_group_read_noise_view(srt_group *g, uint8_t *argb_out); /* blocking: the group's width * height * 4 heat map bytes (one entry point beyond the handle's: a group has no srt_read_argb) */
+/* Blocking, like srt_render: traces until a check converges. Dispatch i (from 0) is srt_trace with options->time + i *
+ * time_stride (uint32 arithmetic). After every dispatch that makes T % check_every == 0 with P >= min_samples a metering is
+ * enqueued (check k); the call then waits for the copy event of check k - 1, and only for that, and stops if that check
+ * converged -- so the device always has one interval queued while the host waits, and the stop does not depend on timing:
+ * counted from a clear, *dispatches_done = min(T* + check_every, max_dispatches), T* the T of the first converged check. At
+ * max_dispatches the outstanding check is waited for and reported; converged = 0 unless it converged. The frame is then
+ * resolved as srt_resolve_denoised(t, T) resolves it (the filter when iterations >= 1, exposure and bloom as configured) and
+ * read into argb_out. *result is the deciding check's (result->dispatches = T*); all zero, level_bin -1, when no check ran.
+ * T and P count from the last clear: dispatches traced before the call count. SRT_ERR_STATE: the meter or the denoiser is off. */
+int srt_render_until(srt_tracer *t, const srt_render_data *options, uint32_t time_stride, uint32_t max_dispatches, uint8_t *argb_out,
+                     srt_noise_result *result, uint32_t *dispatches_done);
+/* Automatic metering: srt_render, srt_render_async and srt_render_pipelined meter the frame behind their resolve when the meter
+ * is on and T % check_every == 0, so a front-end only polls. For tests: *ran = 1 when the last of these calls metered. */
+int srt_last_meter_ran(const srt_tracer *t, int *ran);
+/* For tests: uploads num_pixels float4 of a canvas and num_pixels floats of moments and runs the meter kernel on them as a
+ * metering of a frame with these T, P and params would (view_out NULL: the metering instantiation; else the view one, and
+ * num_pixels * 4 heat map bytes into view_out). counts_out = {metered, left_out, below}. Blocking. num_pixels 1..2^24. */
+int srt_selftest_noise_meter(srt_tracer *t, const float *canvas_host, const float *moments_host, uint32_t num_pixels, uint32_t T, uint32_t P,
+                             const srt_noise_params *params, uint32_t hist_out[256], uint32_t counts_out[3], uint8_t *view_out);
+
 /* Device self-test of the deterministic math (tests only). Walks r = 0, stride, ... over
  * all 2^32 RNG outputs: out[0..2] = mismatch counts of the kernel-local sqrt / log / cos
  * specialisations against their generic definitions (must be 0); out[3..7] = sums of the

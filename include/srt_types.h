@@ -181,6 +181,30 @@ typedef struct srt_bloom_params {
 	int32_t reserved; /* must be 0 */
 } srt_bloom_params;
 
+/* Noise metering (srt_set_noise_meter in srt_abi.h, where the arithmetic is written down; new, no counterpart in the
+ * reference): a per-pixel relative standard error of the mean from the denoiser's moments, its histogram, and a stopping rule. */
+typedef struct srt_noise_params {
+	int32_t enable;         /* 0: off (the library launches what it launches without the feature) */
+	float threshold;        /* finite, 2^-24 <= threshold <= 2^8: a pixel with r <= threshold counts as converged (default 0.05) */
+	float luminance_floor;  /* finite, 2^-20 <= floor <= 2^20: the error is relative to max(L, floor) (default 0.01) */
+	int32_t permille;       /* 1..1000: the share of the metered pixels that has to be below the threshold, and the percentile the level is taken at (default 950) */
+	uint32_t min_samples;   /* >= 1: no frame with fewer samples per pixel is converged (default 16) */
+	int32_t check_every;    /* 1..65536: the resolving calls and srt_render_until meter when the dispatch count is a multiple of this (default 4) */
+	int32_t reserved[2];    /* must be 0 */
+} srt_noise_params;
+
+/* One metering as srt_poll_noise / srt_read_noise / srt_render_until report it */
+typedef struct srt_noise_result {
+	uint32_t metered;    /* pixels in the histogram */
+	uint32_t left_out;   /* pixels with a non-finite L, m2 or r */
+	uint32_t below;      /* metered pixels with r <= threshold */
+	int32_t converged;   /* the stopping rule (srt_abi.h) */
+	uint32_t dispatches; /* T at the metering */
+	uint32_t samples;    /* P at the metering */
+	int32_t level_bin;   /* the bin the permille percentile falls in; -1: nothing metered */
+	float level;         /* that bin's upper edge; 0: nothing metered */
+} srt_noise_result;
+
 /* Albedo textures (srt_set_textures, srt_set_material_textures; include/srt_abi.h). */
 #define SRT_MAX_TEXTURES 64
 enum { SRT_FILTER_LINEAR = 0, SRT_FILTER_NEAREST = 1 };
@@ -256,6 +280,12 @@ SRT_STATIC_ASSERT(offsetof(srt_exposure_params, reserved) == 36, "ExposureParams
 SRT_STATIC_ASSERT(sizeof(srt_bloom_params) == 32, "BloomParams 32 B");
 SRT_STATIC_ASSERT(offsetof(srt_bloom_params, clamp) == 20, "BloomParams.clamp@20");
 SRT_STATIC_ASSERT(offsetof(srt_bloom_params, levels) == 24, "BloomParams.levels@24");
+SRT_STATIC_ASSERT(sizeof(srt_noise_params) == 32, "NoiseParams 32 B");
+SRT_STATIC_ASSERT(offsetof(srt_noise_params, permille) == 12, "NoiseParams.permille@12");
+SRT_STATIC_ASSERT(offsetof(srt_noise_params, check_every) == 20, "NoiseParams.check_every@20");
+SRT_STATIC_ASSERT(offsetof(srt_noise_params, reserved) == 24, "NoiseParams.reserved@24");
+SRT_STATIC_ASSERT(sizeof(srt_noise_result) == 32, "NoiseResult 32 B");
+SRT_STATIC_ASSERT(offsetof(srt_noise_result, level) == 28, "NoiseResult.level@28");
 SRT_STATIC_ASSERT(sizeof(srt_material_texture) == 16, "MaterialTexture 16 B");
 SRT_STATIC_ASSERT(offsetof(srt_material_texture, scale_u) == 8, "MaterialTexture.scale_u@8");
 

@@ -219,6 +219,7 @@ void srt_destroy(srt_tracer *t) {
 	t->vm_first_dev.release();
 	t->ex_own.record.release();
 	t->bl_own.pyramid.release();
+	t->nz_own.release();
 	srt_texture_release(t);
 	if (t->ev_t0) (void)hipEventDestroy(t->ev_t0);
 	if (t->ev_t1) (void)hipEventDestroy(t->ev_t1);
@@ -859,6 +860,7 @@ int srt_render_async(srt_tracer *t, const srt_render_data *options, uint32_t tic
 	t->have_resolve_ev = false;
 	if (const int erc = srt_exposure_apply_frame(t, ticks_stopped, t->argb.ptr)) return erc; // exposure.hip: nothing while the feature is off
 	SRT_HIP(t, hipMemcpyAsync(argb_out, t->argb.ptr, owned_pixels(t) * 4, hipMemcpyDeviceToHost, t->stream));
+	if (const int nrc = srt_noise_after_resolve(t)) return nrc; // noise_meter.hip: nothing while the feature is off
 	return SRT_OK; // argb_out is valid after srt_synchronize()
 }
 

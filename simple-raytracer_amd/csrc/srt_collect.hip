@@ -368,6 +368,7 @@ srt_tracer *resolver_of(srt_group *g) {
 	g->resolver->stream = root->stream;
 	g->resolver->ex = root->ex; // one exposure state per group, the first member's (srt_group_set_exposure)
 	g->resolver->bl = root->bl; // ... and one bloom state (srt_group_set_bloom)
+	g->resolver->nz = root->nz; // ... and one noise meter (srt_group_set_noise_meter)
 	return g->resolver;
 }
 
@@ -878,6 +879,72 @@ int srt_group_last_resolve_bloomed(const srt_group *g, int *bloomed) {
 	return srt_last_resolve_bloomed(g->t[0], bloomed);
 }
 
+// ---- noise metering on a group: the single handle's calls on the group's full-frame handle, whose canvas and moments are the
+// gathered planes on the first device; the state is the first member's, shared by pointer as the exposure state is ----
+namespace {
+srt_tracer *noise_resolver(srt_group *g, const char *who) {
+	if (!g->dn_on) {
+		g->err = std::string(who) + ": the group's denoiser is off: nothing accumulates the moments (srt_group_set_denoise; iterations = 0 is enough)";
+		return nullptr;
+	}
+	return resolver_of(g);
+}
+} // namespace
+
+int srt_group_set_noise_meter(srt_group *g, const srt_noise_params *p) {
+	if (!g) return SRT_ERR_INVALID;
+	if (!p || !p->enable) {
+		const int rc = srt_set_noise_meter(g->t[0], nullptr);
+		return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+	}
+	if (srt_noise_check_host(p)) return gfail(g, SRT_ERR_INVALID, "srt_group_set_noise_meter: parameters out of range (srt_noise_check_host)");
+	srt_tracer *r = noise_resolver(g, "srt_group_set_noise_meter");
+	if (!r) return SRT_ERR_STATE;
+	SRT_ON_RESOLVER(g, r, srt_set_noise_meter(r, p));
+	return SRT_OK;
+}
+
+int srt_group_meter_noise(srt_group *g) {
+	if (!g) return SRT_ERR_INVALID;
+	srt_tracer *r = noise_resolver(g, "srt_group_meter_noise");
+	if (!r) return SRT_ERR_STATE;
+	SRT_ON_RESOLVER(g, r, srt_meter_noise(r));
+	return SRT_OK;
+}
+
+int srt_group_resolve_noise_view(srt_group *g) {
+	if (!g) return SRT_ERR_INVALID;
+	srt_tracer *r = noise_resolver(g, "srt_group_resolve_noise_view");
+	if (!r) return SRT_ERR_STATE;
+	SRT_ON_RESOLVER(g, r, srt_resolve_noise_view(r));
+	return SRT_OK;
+}
+
+int srt_group_poll_noise(srt_group *g, srt_noise_result *result, uint32_t hist[256], int *ready) {
+	if (!g) return SRT_ERR_INVALID;
+	srt_tracer *r = noise_resolver(g, "srt_group_poll_noise");
+	if (!r) return SRT_ERR_STATE;
+	SRT_ON_RESOLVER(g, r, srt_poll_noise(r, result, hist, ready));
+	return SRT_OK;
+}
+
+int srt_group_read_noise(srt_group *g, srt_noise_result *result, uint32_t hist[256]) {
+	if (!g) return SRT_ERR_INVALID;
+	srt_tracer *r = noise_resolver(g, "srt_group_read_noise");
+	if (!r) return SRT_ERR_STATE;
+	SRT_ON_RESOLVER(g, r, srt_read_noise(r, result, hist));
+	return SRT_OK;
+}
+
+int srt_group_read_noise_view(srt_group *g, uint8_t *argb_out) {
+	if (!g) return SRT_ERR_INVALID;
+	if (!argb_out) return gfail(g, SRT_ERR_INVALID, "srt_group_read_noise_view: argb_out is NULL");
+	srt_tracer *r = noise_resolver(g, "srt_group_read_noise_view");
+	if (!r) return SRT_ERR_STATE;
+	SRT_ON_RESOLVER(g, r, srt_read_argb(r, argb_out));
+	return SRT_OK;
+}
+
 int srt_group_get_counters(srt_group *g, srt_counters *out) {
 	if (!g || !out) return SRT_ERR_INVALID;
 	memset(out, 0, sizeof *out);
@@ -921,6 +988,7 @@ int srt_render_pipelined(srt_tracer *t, const srt_render_data *options, uint32_t
 	if (rc != SRT_OK) return rc;
 	if ((rc = srt_exposure_apply_frame(t, ticks_stopped, c->dev_argb[slot])) != SRT_OK) return rc; // exposure.hip: nothing while the feature is off
 	SRT_HIP(t, hipEventRecord(c->resolved[slot], t->stream));
+	if ((rc = srt_noise_after_resolve(t)) != SRT_OK) return rc; // noise_meter.hip: nothing while the feature is off; the frame's copy does not wait for it
 	SRT_HIP(t, hipStreamWaitEvent(c->copy_stream, c->resolved[slot], 0));
 	SRT_HIP(t, hipMemcpyAsync(c->pinned[slot], c->dev_argb[slot], bytes, hipMemcpyDeviceToHost, c->copy_stream));
 	SRT_HIP(t, hipEventRecord(c->copied[slot], c->copy_stream));

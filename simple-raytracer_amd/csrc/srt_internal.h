@@ -153,6 +153,22 @@ struct BloomState {
 	int last_w = 0, last_h = 0, last_levels = 0;
 };
 
+// Noise metering (noise_meter.hip; srt_set_noise_meter): the switch and its parameters, the device record one metering adds into
+// and its pinned copies (made when the feature is first enabled). Two copies, taken in turn: srt_render_until reads check k - 1
+// while check k is in flight. `enqueued` counts the meterings; the newest one's copy is back[(enqueued - 1) & 1]
+struct NoiseState {
+	bool on = false;
+	bool last_ran = false; // srt_last_meter_ran: the last resolving call of a site metered its frame
+	srt_noise_params p{};
+	DevBuf<uint32_t> record;
+	PinnedReadback<uint32_t> back[2];
+	uint64_t enqueued = 0;
+	void release() {
+		record.release();
+		for (PinnedReadback<uint32_t> &b : back) b.release();
+	}
+};
+
 struct SrtCollect; // srt_collect.hip: RCCL communicator, gathered canvases, frame pipeline
 
 struct srt_tracer {
@@ -300,6 +316,8 @@ struct srt_tracer {
 	ExposureState *ex = &ex_own;      // ... through this: a group's full-frame resolver handle shares the first member's (srt_collect.hip resolver_of)
 	BloomState bl_own;                // bloom.hip ...
 	BloomState *bl = &bl_own;         // ... shared the same way
+	NoiseState nz_own;                // noise_meter.hip ...
+	NoiseState *nz = &nz_own;         // ... shared the same way
 	uint32_t last_trace_plane_form = 0; // srt_last_trace_plane_form
 	hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;
 	bool have_trace_ev = false, have_resolve_ev = false, have_kernel_ev = false;
@@ -401,6 +419,12 @@ static inline int srt_exposure_apply_frame(srt_tracer *t, uint32_t ticks_stopped
 		return srt_exposure_apply(t, t->dn_col.ptr + (size_t)t->dn_out * full_pixels(t) * 4, 1.0f, (uint32_t)t->width, (uint32_t)t->height, true, argb);
 	return srt_exposure_apply(t, t->canvas, (float)ticks_stopped, (uint32_t)t->width, (uint32_t)t->owned_rows, t->world == 1, argb);
 }
+/* noise_meter.hip, behind a picture-producing site's resolve (srt_render, srt_render_async, srt_render_pipelined): with the meter
+ * on, the handle meterable and dn_T a multiple of check_every, one metering on the handle's stream; else nothing. Sets last_ran. */
+int srt_noise_after_resolve(srt_tracer *t);
+/* ... and the metering itself: zero the record, the kernel over the canvas and the moments (view_argb not NULL: the heat map
+ * into it as well), the record's copy into the next pinned slot behind its event. The caller has checked the state. */
+int srt_noise_meter_enqueue(srt_tracer *t, uint8_t *view_argb);
 /* bloom.hip: whether a site's resolve of num_pixels is bloomed (the feature on, a picture, not empty); sets last_bloomed */
 bool srt_bloom_begin(srt_tracer *t, bool picture, size_t num_pixels);
 /* ... and its launches on the handle's stream: the pyramid of (source / divisor) * *exposure (NULL: 1.0f) and the composite

@@ -328,6 +328,52 @@ class Tracer {
 		check(group ? srt_group_last_resolve_bloomed(group, &bloomed) : srt_last_resolve_bloomed(handle, &bloomed));
 		return bloomed != 0;
 	}
+	/// Noise metering (srt_set_noise_meter): a per-pixel relative standard error from the denoiser's moments, its histogram and
+	/// the stopping rule "permille of the pixels below threshold". A non-positive threshold, permille or check_every keeps the
+	/// library's default (0.05, 950, 4). Needs set_denoise first (iterations 0 is enough); one device or a group. With it on,
+	/// render() and render_pipelined() meter every check_every-th frame on their own and a front-end only polls.
+	void set_noise_meter(float threshold = 0.0f, int permille = 0, int check_every = 0) {
+		srt_noise_params p;
+		check(srt_noise_defaults(&p));
+		if (threshold > 0.0f) p.threshold = threshold;
+		if (permille > 0) p.permille = permille;
+		if (check_every > 0) p.check_every = check_every;
+		check(group ? srt_group_set_noise_meter(group, &p) : srt_set_noise_meter(handle, &p));
+	}
+	/// ... off: every call enqueues what it does without it
+	void clear_noise_meter() { check(group ? srt_group_set_noise_meter(group, nullptr) : srt_set_noise_meter(handle, nullptr)); }
+	/// Enqueue one metering of the current accumulation. Never waits for the device.
+	void meter_noise() { check(group ? srt_group_meter_noise(group) : srt_meter_noise(handle)); }
+	/// The newest metering's result; false while its copy is in flight (`result` untouched). Never waits for the device.
+	bool poll_noise(srt_noise_result &result) {
+		int ready = 0;
+		check(group ? srt_group_poll_noise(group, &result, nullptr, &ready) : srt_poll_noise(handle, &result, nullptr, &ready));
+		return ready != 0;
+	}
+	/// ... waiting for that copy only, not for the device's queue
+	srt_noise_result read_noise() {
+		srt_noise_result r;
+		check(group ? srt_group_read_noise(group, &r, nullptr) : srt_read_noise(handle, &r, nullptr));
+		return r;
+	}
+	/// Meter and read back the heat map (green: four octaves below the threshold, red: four above, magenta: left out) into
+	/// `output`, width*height*4 bytes. Waits for the device.
+	void resolve_noise_view(std::vector<uint8_t> &output) {
+		output.resize(size_t(options.width) * size_t(options.height) * 4);
+		check(group ? srt_group_resolve_noise_view(group) : srt_resolve_noise_view(handle));
+		check(group ? srt_group_read_noise_view(group, output.data()) : srt_read_argb(handle, output.data()));
+	}
+	/// Render until converged (srt_render_until): dispatches `options` with time + i * time_stride until a check converges or
+	/// max_dispatches are done, then resolves into `output`. Returns the dispatches done; `result` is the deciding check's.
+	/// Single-device tracers only.
+	uint32_t render_until(uint32_t max_dispatches, std::vector<uint8_t> &output, srt_noise_result &result, uint32_t time_stride = 7919) {
+		if (group) throw std::runtime_error("Tracer::render_until: single-device tracers only");
+		if (output.size() < size_t(options.width) * size_t(options.height) * 4)
+			throw std::runtime_error("Tracer::render_until: output must hold width*height*4 bytes");
+		uint32_t done = 0;
+		check(srt_render_until(handle, reinterpret_cast<const srt_render_data *>(&options), time_stride, max_dispatches, output.data(), &result, &done));
+		return done;
+	}
 	/// Object motion for the temporal stage (srt_set_denoise_object_motion): the history survives an update_scene that only
 	/// moves spheres, planes or model instances. Needs set_denoise_temporal first; the clear_canvas / update_scene / render
 	/// order of the frame loop stays as it is. Single-device tracers only (a group gathers no shape indices).

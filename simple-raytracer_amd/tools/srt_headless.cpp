@@ -22,6 +22,13 @@
 // --bloom [THRESHOLD[:INTENSITY[:LEVELS]]]: the bright part of every frame glows (Tracer::set_bloom): what of the exposed colour
 //                lies above THRESHOLD is blurred over LEVELS pyramid levels and added with weight INTENSITY before the tone map;
 //                what is left out is the library's default. Works with and without --exposure
+// --until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]: instead of --frames N, dispatches of --spp samples accumulate until PERMILLE
+//                (default 950) of the pixels have a relative standard error of at most THRESHOLD, or MAXDISPATCHES (default 1024)
+//                are done (Tracer::render_until; the time advances by 7919 per dispatch, as in the frame loop). Turns the denoiser on
+//                with K = 0 when --denoise is not given: the moments it accumulates are what is metered. Prints T, P and the level.
+//                One device only.
+// --noise-view f.ppm: the heat map of the final accumulation's noise (Tracer::resolve_noise_view): green four octaves below the
+//                threshold, red four above, magenta where the estimate is not finite. Turns the denoiser on like --until-noise.
 // --move DX: the camera moves by DX along x every frame and every frame clears the canvas, as the front-end does while moving
 // --move-shape I DX: with --temporal, shape I (a sphere, a plane or a model instance) moves by DX along x every frame and every
 //                frame clears the canvas, as the front-end does while a gizmo is dragged; turns object motion on
@@ -138,6 +145,11 @@ int main(int argc, char **argv) {
 	bool bloom = false;
 	float bloom_threshold = -1.0f, bloom_intensity = -1.0f; // (negative: the library's default)
 	int bloom_levels = 0;
+	bool until_noise = false;
+	float noise_threshold = 0.0f; // (0: the library's default)
+	long noise_max = 1024;
+	int noise_permille = 0;
+	std::string noise_view;
 	float move = 0.0f, shape_move = 0.0f;
 	int move_shape = -1;
 	bool moving = false;
@@ -227,12 +239,25 @@ int main(int argc, char **argv) {
 				}
 			}
 		}
+		else if (a == "--until-noise") { // THRESHOLD[:MAXDISPATCHES[:PERMILLE]]
+			const std::string v = next();
+			char *end = nullptr;
+			until_noise = true;
+			noise_threshold = std::strtof(v.c_str(), &end);
+			if (end && *end == ':') noise_max = std::strtol(end + 1, &end, 10);
+			if (end && *end == ':') noise_permille = (int)std::strtol(end + 1, &end, 10);
+			if (!end || *end || end == v.c_str() || !(noise_threshold > 0.0f) || noise_max < 1 || noise_permille < 0) {
+				std::cerr << "--until-noise takes THRESHOLD, THRESHOLD:MAXDISPATCHES or THRESHOLD:MAXDISPATCHES:PERMILLE\n";
+				return 2;
+			}
+		}
+		else if (a == "--noise-view") noise_view = next();
 		else if (a == "--move") move = std::strtof(next(), nullptr), moving = true;
 		else if (a == "--move-shape") move_shape = std::atoi(next()), shape_move = std::strtof(next(), nullptr);
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
+			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
@@ -261,6 +286,15 @@ int main(int argc, char **argv) {
 		std::cerr << "--temporal needs --denoise K\n";
 		return 2;
 	}
+	if ((until_noise || !noise_view.empty()) && gpus > 1) {
+		std::cerr << "--until-noise and --noise-view run on one device (--gpus 1): a group has no render-until call\n";
+		return 2;
+	}
+	if (until_noise && (pipelined || moving || move_shape >= 0)) {
+		std::cerr << "--until-noise accumulates one still frame: not with --pipelined, --move or --move-shape\n";
+		return 2;
+	}
+	if ((until_noise || !noise_view.empty()) && denoise < 0) denoise = 0; // the moments are the denoiser's; K = 0 keeps the plain resolve's bytes
 
 	// ---- scene construction, as src/main.cpp:95-126 does it ----
 	std::vector<Shape> shapes;
@@ -380,6 +414,7 @@ int main(int argc, char **argv) {
 	if (history_illumination) tracer.set_denoise_history_illumination();
 	if (clamp_given) tracer.set_denoise_history_clamp(history_clamp);
 	if (history_feedback) tracer.set_denoise_history_feedback();
+	if (until_noise || !noise_view.empty()) tracer.set_noise_meter(noise_threshold, noise_permille);
 	if (move_shape >= 0) {
 		if (!temporal || (size_t)move_shape >= shapes.size()) {
 			std::cerr << "--move-shape needs --temporal and a shape index below " << shapes.size() << "\n";
@@ -459,6 +494,20 @@ int main(int argc, char **argv) {
 	// ---- frame loop, as src/main.cpp:277-290,337 ----
 	unsigned time_not_moved = 1;
 	auto t0 = std::chrono::steady_clock::now();
+	srt_noise_result noise{};
+	uint32_t noise_dispatches = 0;
+	if (until_noise) { // one still frame, accumulated until the meter says so
+		frames = 0;
+		tracer.clear_canvas();
+		tracer.update_scene(shapes, triangles, materials.list);
+		auto &options = tracer.options;
+		options.aspect_ratio = (float)width / (float)height;
+		options.fov_scale = 1.0f;
+		options.camera_to_world = camera_to_world;
+		options.time = time_seed;
+		options.tick = 0;
+		noise_dispatches = tracer.render_until((uint32_t)noise_max, pixels, noise, 7919u);
+	}
 	for (int frame = 0; frame < frames; frame++) {
 		if (time_not_moved == 1) {
 			tracer.clear_canvas();
@@ -500,7 +549,20 @@ int main(int argc, char **argv) {
 		std::printf("bloom: level 0 is %dx%d%s\n", w0, h0, ran ? "" : " -- NOT applied");
 	}
 
+	if (until_noise)
+		std::printf("until-noise: %s after %u dispatches; deciding check at T = %u, P = %u: level %.6g (bin %d), %u of %u pixels below, %u left out\n",
+		            noise.converged ? "converged" : "NOT converged", noise_dispatches, noise.dispatches, noise.samples, (double)noise.level, noise.level_bin, noise.below,
+		            noise.metered, noise.left_out);
+
 	if (!out.empty()) save_ppm(out, pixels, width, height);
+	if (!noise_view.empty()) { // (after the picture: the heat map overwrites the handle's image)
+		std::vector<uint8_t> heat;
+		tracer.resolve_noise_view(heat);
+		save_ppm(noise_view, heat, width, height);
+		const srt_noise_result r = tracer.read_noise();
+		std::printf("noise-view: T = %u, P = %u: level %.6g (bin %d), %u of %u pixels below, %u left out\n", r.dispatches, r.samples, (double)r.level, r.level_bin, r.below,
+		            r.metered, r.left_out);
+	}
 	if (!dump_prefix.empty()) {
 		std::vector<float> canvas;
 		tracer.read_canvas(canvas);

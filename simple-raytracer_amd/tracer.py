@@ -67,6 +67,10 @@ ABI_SYMBOLS = [
     "srt_group_last_resolve_exposed",
     "srt_bloom_defaults", "srt_bloom_check_host", "srt_set_bloom", "srt_group_set_bloom", "srt_read_bloom", "srt_group_read_bloom",
     "srt_last_resolve_bloomed", "srt_group_last_resolve_bloomed",
+    "srt_noise_defaults", "srt_noise_check_host", "srt_noise_evaluate_host", "srt_set_noise_meter", "srt_group_set_noise_meter",
+    "srt_meter_noise", "srt_group_meter_noise", "srt_poll_noise", "srt_group_poll_noise", "srt_read_noise", "srt_group_read_noise",
+    "srt_resolve_noise_view", "srt_group_resolve_noise_view", "srt_group_read_noise_view", "srt_render_until", "srt_last_meter_ran",
+    "srt_selftest_noise_meter",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -481,6 +485,65 @@ def bloom_check_host(**kw):
     return load_library().srt_bloom_check_host(C.byref(_bloom_params(kw, "bloom_check_host"))) == 0
 
 
+class NoiseParams(C.Structure):
+    """include/srt_types.h srt_noise_params"""
+    _fields_ = [("enable", C.c_int32), ("threshold", C.c_float), ("luminance_floor", C.c_float), ("permille", C.c_int32),
+                ("min_samples", C.c_uint32), ("check_every", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+    def as_dict(self):
+        return {n: (list(getattr(self, n)) if n == "reserved" else getattr(self, n)) for n, _ in self._fields_}
+
+
+class NoiseResult(C.Structure):
+    """include/srt_types.h srt_noise_result"""
+    _fields_ = [("metered", C.c_uint32), ("left_out", C.c_uint32), ("below", C.c_uint32), ("converged", C.c_int32),
+                ("dispatches", C.c_uint32), ("samples", C.c_uint32), ("level_bin", C.c_int32), ("level", C.c_float)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["level"] = np.float32(d["level"])
+        return d
+
+
+assert C.sizeof(NoiseParams) == 32 and C.sizeof(NoiseResult) == 32
+
+
+def _noise_params(kw, who):
+    """srt_noise_defaults() overridden by kw."""
+    d = NoiseParams()
+    if load_library().srt_noise_defaults(C.byref(d)):
+        raise SrtError("srt_noise_defaults failed")
+    for k, v in kw.items():
+        if k not in d.as_dict():
+            raise TypeError(f"{who}: unknown parameter {k}")
+        if k == "reserved":
+            v = (C.c_int32 * 2)(*v)
+        setattr(d, k, v)
+    return d
+
+
+def noise_defaults():
+    """srt_noise_defaults (host only, no GPU needed) as a dict."""
+    return _noise_params({}, "noise_defaults").as_dict()
+
+
+def noise_check_host(**kw):
+    """srt_noise_check_host of the defaults overridden by kw (host only): True when srt_set_noise_meter would accept them."""
+    return load_library().srt_noise_check_host(C.byref(_noise_params(kw, "noise_check_host"))) == 0
+
+
+def noise_evaluate_host(hist, counts, T, P, **kw):
+    """srt_noise_evaluate_host (host only): the result dict of a record hist (256), counts (metered, left_out, below) metered
+    at T dispatches and P samples under the defaults overridden by kw."""
+    hist = np.ascontiguousarray(hist, np.uint32).reshape(256)
+    c = (C.c_uint32 * 3)(*[int(v) for v in counts])
+    out = NoiseResult()
+    if load_library().srt_noise_evaluate_host(hist.ctypes.data_as(C.POINTER(C.c_uint32)), c, int(T), int(P),
+                                              C.byref(_noise_params(kw, "noise_evaluate_host")), C.byref(out)):
+        raise SrtError("srt_noise_evaluate_host: bad arguments")
+    return out.as_dict()
+
+
 def temporal_defaults():
     """srt_temporal_defaults (host only, no GPU needed) as a dict."""
     d = TemporalParams()
@@ -730,6 +793,22 @@ def _bind(lib):
             getattr(lib, pre + "set_bloom").argtypes = [vp, C.POINTER(BloomParams)]
             getattr(lib, pre + "read_bloom").argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_size_t, ip, ip]
             getattr(lib, pre + "last_resolve_bloomed").argtypes = [vp, ip]
+    if hasattr(lib, "srt_set_noise_meter"):  # (likewise)
+        ip, u32p, fp = C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_float)
+        npp, nrp = C.POINTER(NoiseParams), C.POINTER(NoiseResult)
+        lib.srt_noise_defaults.argtypes = [npp]
+        lib.srt_noise_check_host.argtypes = [npp]
+        lib.srt_noise_evaluate_host.argtypes = [u32p, u32p, C.c_uint32, C.c_uint32, npp, nrp]
+        for pre in ("srt_", "srt_group_"):
+            getattr(lib, pre + "set_noise_meter").argtypes = [vp, npp]
+            getattr(lib, pre + "meter_noise").argtypes = [vp]
+            getattr(lib, pre + "poll_noise").argtypes = [vp, nrp, u32p, ip]
+            getattr(lib, pre + "read_noise").argtypes = [vp, nrp, u32p]
+            getattr(lib, pre + "resolve_noise_view").argtypes = [vp]
+        lib.srt_group_read_noise_view.argtypes = [vp, vp]
+        lib.srt_render_until.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, nrp, u32p]
+        lib.srt_last_meter_ran.argtypes = [vp, ip]
+        lib.srt_selftest_noise_meter.argtypes = [vp, fp, fp, C.c_uint32, C.c_uint32, C.c_uint32, npp, u32p, u32p, vp]
     return lib
 
 
@@ -913,7 +992,46 @@ class _Bloom:
         return bool(out.value)
 
 
-class Tracer(_Denoise, _Exposure, _Bloom):
+class _Noise:
+    """Noise metering (srt_set_noise_meter), shared by Tracer and TracerGroup the way _Denoise is. A result is a dict: metered,
+    left_out, below, converged, dispatches, samples, level_bin, level (numpy float32) and hist (256 uint32)."""
+
+    def set_noise_meter(self, enable=True, **kw):
+        """Turn the meter on with srt_noise_defaults() overridden by kw (threshold, luminance_floor, permille, min_samples,
+        check_every), or off with enable=False. Needs the denoiser on (set_denoise; iterations=0 is enough)."""
+        if not enable:
+            self._check(self._dn("set_noise_meter", None))
+            return
+        self._check(self._dn("set_noise_meter", C.byref(_noise_params(kw, "set_noise_meter"))))
+
+    def meter_noise(self):
+        """Enqueue one metering of the current accumulation; asynchronous (then poll_noise / read_noise)."""
+        self._check(self._dn("meter_noise"))
+
+    @staticmethod
+    def _noise_dict(res, hist):
+        d = res.as_dict()
+        d["hist"] = hist
+        return d
+
+    def poll_noise(self):
+        """The newest metering's result, or None while its copy is in flight. Never blocks."""
+        res, hist, ready = NoiseResult(), np.zeros(256, np.uint32), C.c_int(0)
+        self._check(self._dn("poll_noise", C.byref(res), hist.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(ready)))
+        return self._noise_dict(res, hist) if ready.value else None
+
+    def read_noise(self):
+        """The newest metering's result; waits for its copy only."""
+        res, hist = NoiseResult(), np.zeros(256, np.uint32)
+        self._check(self._dn("read_noise", C.byref(res), hist.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return self._noise_dict(res, hist)
+
+    def resolve_noise_view(self):
+        """Meter and overwrite the ARGB image with the heat map; asynchronous (Tracer: read_argb; a group: read_noise_view)."""
+        self._check(self._dn("resolve_noise_view"))
+
+
+class Tracer(_Denoise, _Exposure, _Bloom, _Noise):
     """Mirror of the reference's `class Tracer`. Field and method names are the
     reference's; records are numpy scalars of records.RENDER_DATA / SCENE_DATA."""
 
@@ -1278,6 +1396,38 @@ class Tracer(_Denoise, _Exposure, _Bloom):
         self._check(self.lib.srt_pipeline_flush(self._h, _ptr(output), C.byref(n)))
         return n.value
 
+    # -- noise metering (srt_set_noise_meter): set_noise_meter ... resolve_noise_view are _Noise's --
+    def render_until(self, max_dispatches, time_stride=7919, output=None):
+        """srt_render_until: trace self.options (time + i * time_stride) until a check converges or max_dispatches are done,
+        resolve, blocking read-back -> (output, the deciding check's result dict without hist, dispatches done)."""
+        if output is None:
+            output = np.zeros(self.owned_rows * self.width * 4, np.uint8)
+        assert output.dtype == np.uint8 and output.size >= self.owned_rows * self.width * 4
+        rd = R.as_records(self.options, R.RENDER_DATA)
+        res, done = NoiseResult(), C.c_uint32(0)
+        self._check(self.lib.srt_render_until(self._h, _ptr(rd), int(time_stride), int(max_dispatches), _ptr(output), C.byref(res), C.byref(done)))
+        return output, res.as_dict(), int(done.value)
+
+    def last_meter_ran(self):
+        """True when the last render / render_async / render_pipelined metered its frame."""
+        out = C.c_int(0)
+        self._check(self.lib.srt_last_meter_ran(self._h, C.byref(out)))
+        return bool(out.value)
+
+    def selftest_noise_meter(self, canvas, moments, T, P, view=False, **kw):
+        """srt_selftest_noise_meter: the meter kernel over canvas (n, 4) and moments (n) float32 as a metering at T, P under the
+        defaults overridden by kw -> hist (256 uint32), (metered, left_out, below), view bytes (n, 4) uint8 or None."""
+        canvas = np.ascontiguousarray(canvas, np.float32).reshape(-1, 4)
+        moments = np.ascontiguousarray(moments, np.float32).reshape(-1)
+        assert len(canvas) == len(moments)
+        hist, counts = np.zeros(256, np.uint32), (C.c_uint32 * 3)()
+        out = np.zeros((len(canvas), 4), np.uint8) if view else None
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.srt_selftest_noise_meter(self._h, canvas.ctypes.data_as(fp), moments.ctypes.data_as(fp), len(canvas), int(T), int(P),
+                                                      C.byref(_noise_params(kw, "selftest_noise_meter")), hist.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                      counts, _ptr(out) if view else None))
+        return hist, tuple(int(v) for v in counts), out
+
     # -- edge-aware denoiser (srt_set_denoise): set_denoise ... read_denoise_history are _Denoise's --
     def _dn(self, name, *args):
         return getattr(self.lib, "srt_" + name)(self._h, *args)
@@ -1341,7 +1491,7 @@ class Tracer(_Denoise, _Exposure, _Bloom):
         self.owned_rows = self.lib.srt_partition_owned_rows(self.height, rank, world, rows_per_block)
 
 
-class TracerGroup(_Denoise, _Exposure, _Bloom):
+class TracerGroup(_Denoise, _Exposure, _Bloom, _Noise):
     """One process driving several GPUs (srt_group_*): the reference's Tracer interface over a row partition,
     collected with one ncclGather per frame."""
 
@@ -1462,6 +1612,12 @@ class TracerGroup(_Denoise, _Exposure, _Bloom):
         """Trace on every member, collect and unpermute on the first device; asynchronous (then resolve_denoised)."""
         rd = R.as_records(self.options, R.RENDER_DATA)
         self._check(self.lib.srt_group_trace_and_gather(self._g, _ptr(rd)))
+
+    def read_noise_view(self):
+        """(height, width, 4) uint8: the heat map resolve_noise_view wrote on the first device. Waits for its stream."""
+        out = np.zeros((self.height, self.width, 4), np.uint8)
+        self._check(self.lib.srt_group_read_noise_view(self._g, _ptr(out)))
+        return out
 
     def member(self, i):
         """The srt_tracer handle of member i (ctypes void pointer; owned by the group)."""
