@@ -1058,6 +1058,70 @@ int srt_last_meter_ran(const srt_tracer *t, int *ran);
 int srt_selftest_noise_meter(srt_tracer *t, const float *canvas_host, const float *moments_host, uint32_t num_pixels, uint32_t T, uint32_t P,
                              const srt_noise_params *params, uint32_t hist_out[256], uint32_t counts_out[3], uint8_t *view_out);
 
+/* ---- ray queries (new): closest hits for caller rays, picking ------------------------------------------------------------- */
+
+/* The closest hit of each of n rays in the handle's scene -- its run/block layout, world triangles, hierarchy (built, refitted
+ * or device-built, whatever the last srt_update_scene left) and materials -- without rendering: what is under the mouse, where
+ * an object dropped along a ray lands, a line of sight (hit.t < tmax). Records: srt_ray, srt_ray_hit (srt_types.h).
+ *
+ * SAME RAY, SAME HIT. A ray is what the trace kernels' EXTEND gets:
+ *   - it starts at its origin, with the intersectors' own self-intersection rule and no tmin of its own;
+ *   - the direction is normalised with the kernels' normalize3 (a * rsqrt(dot(a, a)), detmath's rsqrt), unless
+ *     SRT_RAYS_UNIT_DIRECTIONS says it is already unit length: the caller's bits are then used as given, because normalising
+ *     an already normalised vector can change bits;
+ *   - tmax is the value the closest distance starts from (+inf is allowed); a hit is closer than tmax, strictly, by the
+ *     kernels' take_if_closer (so tmax <= 0, -0 and -inf included, is a miss that is not traversed);
+ *   - ties between shapes go to the first in array order, as in the trace; within a model to the lower triangle index;
+ *   - t is a world distance along the unit direction.
+ * THE RECORD.
+ *   - shape: the index in the array srt_update_scene was given, SRT_HIT_NONE (0xffffffff) for a miss;
+ *   - triangle: the index inside its model (under a hierarchy, the leaf record's index), SRT_HIT_NONE for spheres, planes, misses;
+ *   - normal: the trace's hit normal (winner_normal) turned to face the ray. SRT_HIT_FRONT is set when the ray met the front
+ *     face -- dot(normal as stored, direction) < 0, nothing had to be turned -- and clear when the normal was negated (a back
+ *     face: the inside of a sphere, the underside of a plane);
+ *   - material: the one the trace would shade with: the per-triangle index where srt_set_triangle_materials gave one that is
+ *     not -1, else the shape's;
+ *   - a shape WITHOUT a material (index < 0) IS REPORTED, with material = -1 (whatever the per-triangle table says) and
+ *     SRT_HIT_HIT set, unlike the trace, which treats it as sky (render.cl:404): a picker must be able to select such a shape;
+ *   - a miss: t = +inf, shape = triangle = SRT_HIT_NONE, material = -1, a zero normal, flags 0.
+ * HOSTILE RAYS. A ray is invalid if any origin or direction component is not finite, if tmax is NaN, or if the direction is
+ * zero or does not normalise to a finite vector of unit length (squared length outside (0.25, 4) after normalize3 -- 1e-30: the
+ * squared length underflows; 1e30: it overflows). It is
+ * not traversed and gets the miss record with SRT_HIT_INVALID_RAY. The DEVICE decides this: device-resident rays never pass
+ * the host. No ray makes the walk run on or read outside the scene's buffers, and the call still returns SRT_OK.
+ * STATE. A query reads the scene as the last srt_update_scene left it, ordered on the handle's stream behind the pre-pass,
+ * refit and build that update enqueued: a cast after a device refit sees the refitted boxes. It writes nothing but its outputs
+ * and a staging buffer of its own (bringing the per-triangle material table up to date, as the next dispatch would, aside):
+ * canvas, counters, denoiser planes, exposure and noise state stay as they were, and so does every srt_last_trace_* answer.
+ * Before any scene is set every valid ray misses.
+ * COUNTS AND ERRORS. n == 0: SRT_OK, no launch. A null pointer with n > 0, unknown flag bits, n >= 2^31, a device pointer not
+ * aligned to 16 bytes: SRT_ERR_INVALID. The host forms keep ONE growing staging allocation per handle (72 B per ray of the
+ * largest call), freed in srt_destroy.
+ *
+ * srt_cast_rays: host arrays, blocking. srt_cast_rays_device: n srt_ray / n srt_ray_hit in device memory of the handle's
+ * device, each 16-byte aligned, asynchronous on the handle's stream (srt_synchronize, or work on the bound stream, follows). */
+int srt_cast_rays(srt_tracer *t, const srt_ray *rays, size_t n, uint32_t flags, srt_ray_hit *hits);
+int srt_cast_rays_device(srt_tracer *t, const void *rays_dev, size_t n, uint32_t flags, void *hits_dev);
+/* Picking: the hits under n points of the image, xy = {x0, y0, x1, y1, ...} in CONTINUOUS pixel coordinates (x to the right, y
+ * down, the pixel (px, py) covers [px, px + 1) x [py, py + 1)), blocking. A small second kernel makes the rays on the device
+ * with the statements of the trace's CAMERA phase -- ndc = (x / width, y / height) through the host's reciprocals, the aspect
+ * and fov lines, the camera matrix's columns, normalize3, origin camera_to_world[3] -- with the caller's x, y in place of
+ * (float)px + random_float(seed); it writes into the staging buffer and the cast follows with unit directions. So
+ * xy = (px + 0.5, py + 0.5) is the pixel's centre ray, and xy = ((float)px + r0, (float)py + r1) with the two random floats of a
+ * sample is that sample's primary ray bit for bit. `options` supplies only the camera (camera_to_world, aspect_ratio,
+ * fov_scale) and the frame size (width, height, both > 0), which need not be the handle's. A partitioned handle or a group
+ * member answers for GLOBAL pixel coordinates: every member holds the whole scene. Coordinates outside the frame give the rays
+ * the same formulas give (NaN: an invalid ray). */
+int srt_pick(srt_tracer *t, const srt_render_data *options, const float *xy, size_t n, srt_ray_hit *hits);
+/* On the group's first member: every member holds the scene. */
+int srt_group_cast_rays(srt_group *g, const srt_ray *rays, size_t n, uint32_t flags, srt_ray_hit *hits);
+int srt_group_pick(srt_group *g, const srt_render_data *options, const float *xy, size_t n, srt_ray_hit *hits);
+/* With srt_set_kernel_timers on: the device time of the last query's launches (the cast; for srt_pick the ray set-up too), in
+ * milliseconds; 0 when the timers were off or nothing was launched. Blocking, as srt_last_kernel_ms. */
+int srt_last_ray_query_ms(srt_tracer *t, float *ms);
+/* Host-only: out = {sizeof(srt_ray), sizeof(srt_ray_hit)} as the library was built. */
+int srt_ray_query_sizes(size_t out[2]);
+
 /* Device self-test of the deterministic math (tests only). Walks r = 0, stride, ... over
  * all 2^32 RNG outputs: out[0..2] = mismatch counts of the kernel-local sqrt / log / cos
  * specialisations against their generic definitions (must be 0); out[3..7] = sums of the

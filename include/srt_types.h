@@ -218,6 +218,28 @@ typedef struct srt_material_texture {
 	float scale_u, scale_v; /* finite; u *= scale_u, v *= scale_v before the sampler */
 } srt_material_texture;
 
+/* Ray queries (srt_cast_rays, srt_pick; include/srt_abi.h "ray queries"). Both records are 32 bytes, read and written by the
+ * device as two 128-bit words each. */
+typedef struct srt_ray {
+	float origin[3];
+	float tmax; /* hits must be closer than this, strictly; +inf allowed */
+	float direction[3];
+	uint32_t reserved; /* not read */
+} srt_ray;
+typedef struct srt_ray_hit {
+	float t;           /* world distance along the unit direction; +inf: a miss */
+	uint32_t shape;    /* index into srt_update_scene's shapes; SRT_HIT_NONE: a miss */
+	uint32_t triangle; /* index inside its model; SRT_HIT_NONE: a sphere, a plane, a miss */
+	int32_t material;  /* the material the trace would shade with; -1: a miss, or a shape without one */
+	float normal[3];   /* unit, facing the ray; 0 for a miss */
+	uint32_t flags;    /* SRT_HIT_* */
+} srt_ray_hit;
+#define SRT_HIT_NONE 0xffffffffu
+#define SRT_RAYS_UNIT_DIRECTIONS 1u /* per call: directions are used as given (already unit length) */
+#define SRT_HIT_HIT 1u
+#define SRT_HIT_FRONT 2u
+#define SRT_HIT_INVALID_RAY 4u
+
 #ifdef __cplusplus
 }
 #endif
@@ -288,5 +310,9 @@ SRT_STATIC_ASSERT(sizeof(srt_noise_result) == 32, "NoiseResult 32 B");
 SRT_STATIC_ASSERT(offsetof(srt_noise_result, level) == 28, "NoiseResult.level@28");
 SRT_STATIC_ASSERT(sizeof(srt_material_texture) == 16, "MaterialTexture 16 B");
 SRT_STATIC_ASSERT(offsetof(srt_material_texture, scale_u) == 8, "MaterialTexture.scale_u@8");
+SRT_STATIC_ASSERT(sizeof(srt_ray) == 32, "Ray 32 B");
+SRT_STATIC_ASSERT(offsetof(srt_ray, direction) == 16, "Ray.direction@16");
+SRT_STATIC_ASSERT(sizeof(srt_ray_hit) == 32, "RayHit 32 B");
+SRT_STATIC_ASSERT(offsetof(srt_ray_hit, normal) == 16, "RayHit.normal@16");
 
 #endif /* SRT_TYPES_H */

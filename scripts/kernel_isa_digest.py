@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A digest of every kernel's gfx950 assembly, to show that a change left the device code alone (no GPU needed).
 
-    python scripts/kernel_isa_digest.py [--tree ROOT] [--flags="-DSRT_DEV_KNOBS"] [--sources kernels.hip ...] [--out FILE] [--compare FILE]
+    python scripts/kernel_isa_digest.py [--tree ROOT] [--flags="-DSRT_DEV_KNOBS"] [--sources kernels.hip ...] [--out FILE] [--list FILE] [--compare FILE]
 
 Every device translation unit (*.hip) of build.py SOURCES in ROOT (default: this checkout) is compiled with build.py's
 FLAGS, the --flags given and `--cuda-device-only -S`. Per kernel (a symbol with a kernel descriptor) the text from its label to
@@ -14,7 +14,9 @@ kernels here have none. Printed as JSON:
                           "amdhsa": the descriptor's lines}}
 
 keyed by the kernel alone, so a kernel that moved to another unit keeps its entry. With --compare, exit status 1 and a
-list of the kernels whose entries differ from FILE's (or that only one side has).
+list of the kernels whose entries differ from FILE's (or that only one side has). --list FILE writes the short form, one line
+per kernel: the sha256 of its whole entry (instruction count, text digest and descriptor lines), the instruction count, the
+name; --compare takes either form.
 """
 import argparse
 import concurrent.futures
@@ -93,22 +95,38 @@ def digest(tree, flags, sources=None):
     return dict(sorted(res.items()))
 
 
+def listing(res):
+    """kernel -> 'entry digest  instructions': the short form of a digest, one line per kernel"""
+    return {k: f"{hashlib.sha256(json.dumps(v, sort_keys=True).encode()).hexdigest()} {v['instructions']}" for k, v in res.items()}
+
+
+def read_digest(path):
+    """a digest written with --out (JSON) or with --list, as the short form"""
+    txt = Path(path).read_text()
+    if txt.lstrip().startswith("{"):
+        return listing(json.loads(txt))
+    return {l.split(None, 2)[2]: " ".join(l.split(None, 2)[:2]) for l in txt.splitlines() if l.strip()}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--tree", default=str(ROOT), help="checkout to digest (default: this one)")
     ap.add_argument("--flags", default="", help="extra compiler flags, e.g. a variant build's -D switches")
     ap.add_argument("--sources", nargs="*", help="units to compile (default: every *.hip of build.py SOURCES)")
     ap.add_argument("--out", help="write the JSON here instead of printing it")
+    ap.add_argument("--list", help="write the short form here: entry digest, instruction count and name per kernel")
     ap.add_argument("--compare", help="a digest written earlier: list the kernels that differ and exit 1 if any does")
     a = ap.parse_args()
     res = digest(a.tree, a.flags.split(), a.sources)
     txt = json.dumps(res, indent=1)
     if a.out:
         Path(a.out).write_text(txt + "\n")
-    elif not a.compare:
+    elif not a.compare and not a.list:
         print(txt)
+    if a.list:
+        Path(a.list).write_text("".join(f"{v}  {k}\n" for k, v in listing(res).items()))
     if a.compare:
-        ref = json.loads(Path(a.compare).read_text())
+        ref, res = read_digest(a.compare), listing(res)
         bad = [k for k in sorted(ref.keys() | res.keys()) if ref.get(k) != res.get(k)]
         for k in bad:
             print(f"DIFFERENT  {k}" + ("" if k in ref and k in res else f"  only in {'the reference' if k in ref else 'this build'}"))

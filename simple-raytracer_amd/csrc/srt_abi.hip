@@ -220,6 +220,8 @@ void srt_destroy(srt_tracer *t) {
 	t->ex_own.record.release();
 	t->bl_own.pyramid.release();
 	t->nz_own.release();
+	t->rq_stage.release();
+	t->rq_span.release();
 	srt_texture_release(t);
 	if (t->ev_t0) (void)hipEventDestroy(t->ev_t0);
 	if (t->ev_t1) (void)hipEventDestroy(t->ev_t1);
@@ -1189,3 +1191,7 @@ int srt_set_count_triangles(srt_tracer *t, int enable) {
 }
 
 } // extern "C"
+
+// ray_query.hip's way to trace_params_of: a query is handed the scene exactly as a dispatch is (never a textured one: a query
+// samples no texture)
+TraceParams srt_trace_params_for_query(const srt_tracer *t, const srt_render_data *options) { return trace_params_of(t, options, false); }

@@ -945,6 +945,19 @@ int srt_group_read_noise_view(srt_group *g, uint8_t *argb_out) {
 	return SRT_OK;
 }
 
+// ray queries (ray_query.hip) on the first member: every member holds the whole scene, and a query ignores the partition
+int srt_group_cast_rays(srt_group *g, const srt_ray *rays, size_t n, uint32_t flags, srt_ray_hit *hits) {
+	if (!g || g->t.empty()) return SRT_ERR_INVALID;
+	const int rc = srt_cast_rays(g->t[0], rays, n, flags, hits);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+int srt_group_pick(srt_group *g, const srt_render_data *options, const float *xy, size_t n, srt_ray_hit *hits) {
+	if (!g || g->t.empty()) return SRT_ERR_INVALID;
+	const int rc = srt_pick(g->t[0], options, xy, n, hits);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
 int srt_group_get_counters(srt_group *g, srt_counters *out) {
 	if (!g || !out) return SRT_ERR_INVALID;
 	memset(out, 0, sizeof *out);

@@ -319,6 +319,10 @@ struct srt_tracer {
 	NoiseState nz_own;                // noise_meter.hip ...
 	NoiseState *nz = &nz_own;         // ... shared the same way
 	uint32_t last_trace_plane_form = 0; // srt_last_trace_plane_form
+	// ray queries (ray_query.hip; srt_cast_rays, srt_pick): the host forms' one staging allocation -- n rays, n hits, n picked
+	// points (32 + 32 + 8 bytes each) of the largest call so far -- and the timers' span around the last query's launches
+	DevBuf<uint8_t> rq_stage;
+	TimedSpan rq_span;
 	hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;
 	bool have_trace_ev = false, have_resolve_ev = false, have_kernel_ev = false;
 	std::string err;
@@ -434,6 +438,9 @@ int srt_bloom_resolve(srt_tracer *t, const float *source, float divisor, const f
  * denoiser on, the feature pass and the filter (a group member on its own: the plain resolve) follow the reductions. A
  * sequence of file-local steps in srt_abi.hip; the arithmetic they share with the host unit check is trace_plan.h's */
 extern "C" int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fused_argb, uint32_t ticks_stopped);
+/* srt_abi.hip: trace_params_of for a caller outside it (ray_query.hip) -- the scene buffers and camera set-up a dispatch of
+ * `options` over the handle's current scene would be handed; the batch's fields stay zero */
+TraceParams srt_trace_params_for_query(const srt_tracer *t, const srt_render_data *options);
 /* one scene for several handles: the host pass once (members[0]'s acceleration mode and hierarchy cache), the uploads of all
  * members enqueued before the first is waited for (srt_abi.hip; srt_group_update_scene). *failed_member = the member an error came from */
 extern "C" int srt_update_scene_many(srt_tracer *const *members, size_t n_members, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles,

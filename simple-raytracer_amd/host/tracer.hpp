@@ -402,6 +402,23 @@ class Tracer {
 		check(group ? srt_group_get_counters(group, &c) : srt_get_counters(handle, &c));
 		return c;
 	}
+	/// Ray queries (srt_cast_rays): the closest hit of each ray in the scene of the last update_scene, without rendering.
+	/// unit_directions: the directions are unit length already and are used bit for bit. Blocking.
+	std::vector<srt_ray_hit> cast_rays(const std::vector<srt_ray> &rays, bool unit_directions = false) {
+		std::vector<srt_ray_hit> hits(rays.size());
+		const uint32_t flags = unit_directions ? SRT_RAYS_UNIT_DIRECTIONS : 0u;
+		check(group ? srt_group_cast_rays(group, rays.data(), rays.size(), flags, hits.data()) : srt_cast_rays(handle, rays.data(), rays.size(), flags, hits.data()));
+		return hits;
+	}
+	/// Picking (srt_pick): the hits under image points, xy = {x0, y0, x1, y1, ...} in continuous pixel coordinates of the
+	/// frame `options` describes (a pixel's centre is (px + 0.5, py + 0.5)) -- what a mouse handler asks. Blocking.
+	std::vector<srt_ray_hit> pick(const std::vector<float> &xy) {
+		std::vector<srt_ray_hit> hits(xy.size() / 2);
+		const srt_render_data *rd = reinterpret_cast<const srt_render_data *>(&options);
+		check(group ? srt_group_pick(group, rd, xy.data(), hits.size(), hits.data()) : srt_pick(handle, rd, xy.data(), hits.size(), hits.data()));
+		return hits;
+	}
+	srt_ray_hit pick(float x, float y) { return pick(std::vector<float>{x, y})[0]; }
 	srt_tracer *native_handle() { return group ? srt_group_tracer(group, 0) : handle; }
 };
 

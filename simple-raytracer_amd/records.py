@@ -64,10 +64,31 @@ SCENE_DATA = np.dtype(
 MATERIAL_TEXTURE = np.dtype({"names": ["texture", "filter", "scale_u", "scale_v"], "formats": [np.int32, np.int32, np.float32, np.float32],
                              "offsets": [0, 4, 8, 12], "itemsize": 16})
 
+# srt_ray / srt_ray_hit (ray queries: Tracer.cast_rays, Tracer.pick), 32 bytes each
+RAY = np.dtype({"names": ["origin", "tmax", "direction", "reserved"], "formats": [F3, np.float32, F3, np.uint32],
+                "offsets": [0, 12, 16, 28], "itemsize": 32})
+RAY_HIT = np.dtype({"names": ["t", "shape", "triangle", "material", "normal", "flags"],
+                    "formats": [np.float32, np.uint32, np.uint32, np.int32, F3, np.uint32], "offsets": [0, 4, 8, 12, 16, 28], "itemsize": 32})
+HIT_NONE = 0xFFFFFFFF  # RAY_HIT shape / triangle of a miss (triangle: also of a sphere or a plane)
+RAYS_UNIT_DIRECTIONS = 1
+HIT_HIT, HIT_FRONT, HIT_INVALID_RAY = 1, 2, 4
+
 SHAPE_SPHERE, SHAPE_PLANE, SHAPE_MODEL = 0, 1, 2
 
 assert MATERIAL.itemsize == 64 and TRIANGLE.itemsize == 96 and SHAPE.itemsize == 128
 assert RENDER_DATA.itemsize == 112 and SCENE_DATA.itemsize == 96
+assert RAY.itemsize == 32 and RAY_HIT.itemsize == 32
+
+
+def rays(origins, directions, tmax=np.inf):
+    """RAY records from (n, 3) or (3,) origins and directions (broadcast against each other) and a scalar or (n,) tmax."""
+    o = np.atleast_2d(np.asarray(origins, np.float32))
+    d = np.atleast_2d(np.asarray(directions, np.float32))
+    n = max(len(o), len(d))
+    r = np.zeros(n, RAY)
+    r["origin"], r["direction"] = o, d
+    r["tmax"] = np.asarray(tmax, np.float32)
+    return r
 
 
 def f32(x):

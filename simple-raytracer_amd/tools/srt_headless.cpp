@@ -29,6 +29,9 @@
 //                One device only.
 // --noise-view f.ppm: the heat map of the final accumulation's noise (Tracer::resolve_noise_view): green four octaves below the
 //                threshold, red four above, magenta where the estimate is not finite. Turns the denoiser on like --until-noise.
+// --pick X,Y (may be given several times): after the scene is loaded, the hit under the image point (X, Y) -- continuous pixel
+//                coordinates, a pixel's centre is (px + 0.5, py + 0.5) -- through the first frame's camera (Tracer::pick); one line
+//                per pick: shape, triangle, material (-1: none), t, position, normal. Then the frames render as before.
 // --move DX: the camera moves by DX along x every frame and every frame clears the canvas, as the front-end does while moving
 // --move-shape I DX: with --temporal, shape I (a sphere, a plane or a model instance) moves by DX along x every frame and every
 //                frame clears the canvas, as the front-end does while a gizmo is dragged; turns object motion on
@@ -156,6 +159,7 @@ int main(int argc, char **argv) {
 	bool bvh_build_device = false;
 	uint32_t bvh_build_min = 0;
 	int bvh_order = SRT_BUILD_ORDER_MORTON;
+	std::vector<float> picks; // --pick X,Y: x0, y0, x1, y1, ...
 	for (int i = 1; i < argc; i++) {
 		std::string a = argv[i];
 		auto next = [&]() -> const char * {
@@ -252,12 +256,20 @@ int main(int argc, char **argv) {
 			}
 		}
 		else if (a == "--noise-view") noise_view = next();
+		else if (a == "--pick") { // X,Y
+			float x = 0.f, y = 0.f;
+			if (std::sscanf(next(), "%f,%f", &x, &y) != 2) {
+				std::cerr << "--pick takes X,Y\n";
+				return 2;
+			}
+			picks.push_back(x), picks.push_back(y);
+		}
 		else if (a == "--move") move = std::strtof(next(), nullptr), moving = true;
 		else if (a == "--move-shape") move_shape = std::atoi(next()), shape_move = std::strtof(next(), nullptr);
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
+			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--pick X,Y]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
@@ -490,6 +502,36 @@ int main(int argc, char **argv) {
 	if (!dump_prefix.empty()) dump(dump_prefix + ".sky.bin", sky.data(), sky.size());
 
 	std::vector<uint8_t> pixels((size_t)width * height * 4);
+
+	if (!picks.empty()) { // --pick: what is under these image points, through the first frame's camera
+		tracer.update_scene(shapes, triangles, materials.list);
+		auto &options = tracer.options;
+		options.aspect_ratio = (float)width / (float)height;
+		options.fov_scale = 1.0f;
+		options.camera_to_world = moving ? eye_matrix(glm::vec3(0.0f, 0.5f, 5.0f), 0.0f, 0.0f) : camera_to_world;
+		// the picked point's ray once more on the host, for the printed position (the library's own is made on the device)
+		auto ray_of = [&](float x, float y) {
+			const float sx = (2.0f * (x / (float)width) - 1.0f) * options.aspect_ratio * options.fov_scale;
+			const float sy = (1.0f - 2.0f * (y / (float)height)) * options.fov_scale;
+			const glm::vec4 v = options.camera_to_world * glm::vec4(sx, sy, -1.0f, 0.0f);
+			const glm::vec3 d = glm::normalize(glm::vec3(v.x, v.y, v.z));
+			const glm::vec4 o = options.camera_to_world[3];
+			srt_ray r{{o.x, o.y, o.z}, INFINITY, {d.x, d.y, d.z}, 0u};
+			return r;
+		};
+		const std::vector<srt_ray_hit> hits = tracer.pick(picks);
+		for (size_t k = 0; k < hits.size(); k++) {
+			const srt_ray_hit &h = hits[k];
+			if (!(h.flags & SRT_HIT_HIT)) {
+				std::printf("pick %g,%g: miss\n", picks[2 * k], picks[2 * k + 1]);
+				continue;
+			}
+			const srt_ray r = ray_of(picks[2 * k], picks[2 * k + 1]);
+			std::printf("pick %g,%g: shape %u triangle %d material %d t %.9g position %.9g %.9g %.9g normal %.9g %.9g %.9g\n", picks[2 * k], picks[2 * k + 1],
+			            h.shape, h.triangle == SRT_HIT_NONE ? -1 : (int)h.triangle, h.material, h.t, r.origin[0] + r.direction[0] * h.t,
+			            r.origin[1] + r.direction[1] * h.t, r.origin[2] + r.direction[2] * h.t, h.normal[0], h.normal[1], h.normal[2]);
+		}
+	}
 
 	// ---- frame loop, as src/main.cpp:277-290,337 ----
 	unsigned time_not_moved = 1;

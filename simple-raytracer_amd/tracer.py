@@ -71,6 +71,8 @@ ABI_SYMBOLS = [
     "srt_meter_noise", "srt_group_meter_noise", "srt_poll_noise", "srt_group_poll_noise", "srt_read_noise", "srt_group_read_noise",
     "srt_resolve_noise_view", "srt_group_resolve_noise_view", "srt_group_read_noise_view", "srt_render_until", "srt_last_meter_ran",
     "srt_selftest_noise_meter",
+    "srt_cast_rays", "srt_cast_rays_device", "srt_pick", "srt_group_cast_rays", "srt_group_pick", "srt_last_ray_query_ms",
+    "srt_ray_query_sizes",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -809,6 +811,15 @@ def _bind(lib):
         lib.srt_render_until.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, nrp, u32p]
         lib.srt_last_meter_ran.argtypes = [vp, ip]
         lib.srt_selftest_noise_meter.argtypes = [vp, fp, fp, C.c_uint32, C.c_uint32, C.c_uint32, npp, u32p, u32p, vp]
+    if hasattr(lib, "srt_cast_rays"):  # (likewise)
+        for pre in ("srt_", "srt_group_"):
+            getattr(lib, pre + "cast_rays").argtypes = [vp, vp, sz, C.c_uint32, vp]
+            getattr(lib, pre + "pick").argtypes = [vp, vp, vp, sz, vp]
+        lib.srt_cast_rays_device.argtypes = [vp, vp, sz, C.c_uint32, vp]
+        lib.srt_last_ray_query_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        lib.srt_ray_query_sizes.argtypes = [C.POINTER(sz)]
+        sizes = (sz * 2)()
+        assert lib.srt_ray_query_sizes(sizes) == 0 and (sizes[0], sizes[1]) == (R.RAY.itemsize, R.RAY_HIT.itemsize), tuple(sizes)
     return lib
 
 
@@ -1031,7 +1042,32 @@ class _Noise:
         self._check(self._dn("resolve_noise_view"))
 
 
-class Tracer(_Denoise, _Exposure, _Bloom, _Noise):
+class _RayQuery:
+    """Ray queries (include/srt_abi.h "ray queries"), shared by Tracer (srt_*) and TracerGroup (srt_group_*: answered by the
+    first member). self._dn(name, *args) calls the class's entry point of that name on its handle."""
+
+    def cast_rays(self, origins, directions=None, tmax=np.inf, unit=False):
+        """The closest hit of each ray -> records.RAY_HIT array. origins / directions: (n, 3) or (3,), broadcast against each
+        other; tmax a scalar or (n,); or pass a records.RAY array as `origins` alone. unit=True: the directions are unit
+        length already and are used bit for bit (SRT_RAYS_UNIT_DIRECTIONS). Blocking."""
+        rays = R.as_records(origins, R.RAY) if directions is None else R.rays(origins, directions, tmax)
+        hits = np.zeros(len(rays), R.RAY_HIT)
+        self._check(self._dn("cast_rays", _ptr(rays) if len(rays) else None, len(rays), R.RAYS_UNIT_DIRECTIONS if unit else 0,
+                             _ptr(hits) if len(rays) else None))
+        return hits
+
+    def pick(self, xy, options=None):
+        """The hits under image points -> records.RAY_HIT array. xy: (n, 2) or (2,) continuous pixel coordinates (a pixel's
+        centre is (px + 0.5, py + 0.5)); options: the camera and frame size (default: self.options). Blocking."""
+        xy = np.ascontiguousarray(np.atleast_2d(np.asarray(xy, np.float32)))
+        assert xy.ndim == 2 and xy.shape[1] == 2, xy.shape
+        rd = R.as_records(self.options if options is None else options, R.RENDER_DATA)
+        hits = np.zeros(len(xy), R.RAY_HIT)
+        self._check(self._dn("pick", _ptr(rd), _ptr(xy) if len(xy) else None, len(xy), _ptr(hits) if len(xy) else None))
+        return hits
+
+
+class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery):
     """Mirror of the reference's `class Tracer`. Field and method names are the
     reference's; records are numpy scalars of records.RENDER_DATA / SCENE_DATA."""
 
@@ -1486,12 +1522,23 @@ class Tracer(_Denoise, _Exposure, _Bloom, _Noise):
         self._check(self.lib.srt_read_denoise_vertex_tables(self._h, _ptr(cur), _ptr(hist), n.value, C.byref(n)))
         return cur[:n.value], hist[:n.value]
 
+    def cast_rays_device(self, rays_ptr, n, hits_ptr, unit=False):
+        """cast_rays over device arrays (n records.RAY at rays_ptr, n records.RAY_HIT at hits_ptr, 16-byte aligned), enqueued
+        on the handle's stream: synchronize() before the hits are read."""
+        self._check(self.lib.srt_cast_rays_device(self._h, C.c_void_p(rays_ptr), n, R.RAYS_UNIT_DIRECTIONS if unit else 0, C.c_void_p(hits_ptr)))
+
+    def last_ray_query_ms(self):
+        """Device time of the last query's launches under set_kernel_timers (0 without)."""
+        ms = C.c_float(0)
+        self._check(self.lib.srt_last_ray_query_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def set_partition(self, rank, world, rows_per_block=8):
         self._check(self.lib.srt_set_partition(self._h, rank, world, rows_per_block))
         self.owned_rows = self.lib.srt_partition_owned_rows(self.height, rank, world, rows_per_block)
 
 
-class TracerGroup(_Denoise, _Exposure, _Bloom, _Noise):
+class TracerGroup(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery):
     """One process driving several GPUs (srt_group_*): the reference's Tracer interface over a row partition,
     collected with one ncclGather per frame."""
 
