@@ -537,20 +537,20 @@ int srt_denoise_clear(srt_tracer *t) {
 // the feature pass's one fork: the kernels of the dispatch's kind (albedo textures: the texel at the first hit is the albedo,
 // srt_texture.hip), storing shape indices when object motion is on (temporal.hip)
 static void launch_features(srt_tracer *t, const FeatureParams &fp) {
-	const bool tris = t->om_on && t->vm_on; // per-triangle motion: the hit triangle's index beside the shape's
+	const bool tris = t->dn.object_motion && t->dn.vertex_motion; // per-triangle motion: the hit triangle's index beside the shape's
 	if (t->last_trace_textured) {
 		const TexFeatureParams fx = srt_with_textures<TexFeatureParams>(t, fp);
 		if (tris) srt_launch_features_tris_tex(fx, t->om_ids[t->om_cur].ptr, t->vm_tri[t->om_cur].ptr, t->stream);
-		else if (t->om_on) srt_launch_features_ids_tex(fx, t->om_ids[t->om_cur].ptr, t->stream);
+		else if (t->dn.object_motion) srt_launch_features_ids_tex(fx, t->om_ids[t->om_cur].ptr, t->stream);
 		else srt_launch_features_tex(fx, t->stream);
 	} else if (tris) srt_launch_features_tris(fp, t->om_ids[t->om_cur].ptr, t->vm_tri[t->om_cur].ptr, t->stream);
-	else if (t->om_on) srt_launch_features_ids(fp, t->om_ids[t->om_cur].ptr, t->stream);
+	else if (t->dn.object_motion) srt_launch_features_ids(fp, t->om_ids[t->om_cur].ptr, t->stream);
 	else srt_launch_features(fp, t->stream);
 }
 
 int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples) {
 	const uint32_t ns = num_samples > 0 ? (uint32_t)num_samples : 0u;
-	const uint32_t want = (uint32_t)(t->gd_on ? t->gd_feature_samples : t->dn.feature_samples);
+	const uint32_t want = (uint32_t)(t->gd_on ? t->gd_feature_samples : t->dn.p.feature_samples);
 	const uint32_t fs = want < ns ? want : ns;
 	FeatureParams fp;
 	fp.tp = p;
@@ -559,15 +559,15 @@ int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples
 	fp.albedo_hits = t->gd_on ? gd_albedo_hits(t) : t->dn_ah.ptr;
 	fp.num_pixels = (uint32_t)(t->gd_on ? owned_pixels(t) : full_pixels(t));
 	fp.feature_samples = fs;
-	if (t->om_on && t->vm_on && fs > 0) { // the world vertices this frame is traced with, once per scene
+	if (t->dn.object_motion && t->dn.vertex_motion && fs > 0) { // the world vertices this frame is traced with, once per scene
 		const int vrc = srt_vertex_table_sync(t);
 		if (vrc) return vrc;
 	}
 	launch_features(t, fp);
 	SRT_HIP(t, hipGetLastError());
 	if (t->gd_on) return SRT_OK;
-	srt_denoise_count(t, p.rd, t->dn.feature_samples);
-	if (t->om_on && fs == 0) t->om_mixed = true; // a dispatch without feature rays wrote no shape indices
+	srt_denoise_count(t, p.rd, t->dn.p.feature_samples);
+	if (t->dn.object_motion && fs == 0) t->om_mixed = true; // a dispatch without feature rays wrote no shape indices
 	return SRT_OK;
 }
 
@@ -577,7 +577,7 @@ void srt_denoise_count(srt_tracer *t, const srt_render_data &rd, int feature_sam
 	t->dn_P += ns;
 	t->dn_F += (uint32_t)feature_samples < ns ? (uint32_t)feature_samples : ns;
 	t->dn_cam = rd;
-	t->tp_fresh = false; // temporal.hip: the staging set no longer holds what is traced since the clear
+	t->dn_serial++; // temporal.hip: a staging set made before this no longer holds what is traced since the clear
 }
 
 int srt_denoise_member(srt_tracer *t, int feature_samples) {
@@ -609,10 +609,11 @@ int srt_denoise_member(srt_tracer *t, int feature_samples) {
 }
 
 // one pass: k = 0 .. K - 1, step 2^k, ping-pong between the two images of `col`; the last one writes argb (NULL: none)
-static void launch_pass(srt_tracer *t, FilterParams fp, int k, int K, bool demod, bool feedback, float4 *col, uint8_t *argb) {
+static void launch_pass(srt_tracer *t, FilterParams fp, int k, const FilterPlan &plan, uint8_t *argb) {
 	const size_t px = full_pixels(t);
+	float4 *col = reinterpret_cast<float4 *>(t->dn_col.ptr);
 	const dim3 grid((unsigned)((t->width + 15) / 16), (unsigned)((t->height + 15) / 16));
-	const bool last = k == K - 1;
+	const bool last = k == plan.K - 1, demod = plan.demod, feedback = plan.feedback && k == 0;
 	fp.step = 1 << k;
 	fp.in = col + (size_t)(k & 1) * px;
 	fp.out = col + (size_t)((k + 1) & 1) * px;
@@ -630,9 +631,7 @@ static void launch_pass(srt_tracer *t, FilterParams fp, int k, int K, bool demod
 // What the front leaves for the passes after the first
 struct FilterFront {
 	FilterParams fp; // everything but the per-pass members
-	float4 *col;
-	int K;
-	bool demod, spatial_var, feedback;
+	FilterPlan plan;
 };
 
 // The filter's front: the set-up (spatial or temporal) into the filter image, the demodulate launch and the spatial-variance
@@ -641,7 +640,8 @@ struct FilterFront {
 // set itself (srt_denoise_feedback_front) run this same code, so the history never depends on which of them ran.
 static int filter_front(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb, FilterFront *f) {
 	const size_t px = full_pixels(t);
-	const int K = t->dn.iterations;
+	const FilterPlan plan = plan_filter(t->dn);
+	const int K = plan.K;
 	float4 *col = reinterpret_cast<float4 *>(t->dn_col.ptr);
 	float4 *guide = reinterpret_cast<float4 *>(t->dn_guide.ptr);
 	SetupParams sp;
@@ -659,7 +659,7 @@ static int filter_front(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb, Fi
 	sp.argb = K == 0 ? reinterpret_cast<uint32_t *>(argb) : nullptr;
 	const float4 *fguide = guide;
 	TemporalStaged staged = {nullptr, nullptr, nullptr};
-	if (t->tp_on) { // temporal.hip: the set-up with the reprojected history blended in; it writes the guide into the staging set
+	if (t->dn.temporal) { // temporal.hip: the set-up with the reprojected history blended in; it writes the guide into the staging set
 		const int rc = srt_temporal_setup(t, col, sp.argb, &staged);
 		if (rc) return rc;
 		fguide = staged.guide;
@@ -667,8 +667,7 @@ static int filter_front(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb, Fi
 		hipLaunchKernelGGL(srt_denoise_setup_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, t->stream, sp);
 		SRT_HIP(t, hipGetLastError());
 	}
-	const bool demod = t->dn_demod && K >= 1;
-	if (demod) { // colour -> illumination, in place on the set-up's image (whichever set-up ran)
+	if (plan.demod) { // colour -> illumination, in place on the set-up's image (whichever set-up ran)
 		DemodParams dp;
 		dp.num_pixels = (uint32_t)px;
 		dp.guide = fguide;
@@ -681,19 +680,16 @@ static int filter_front(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb, Fi
 	fp.width = t->width;
 	fp.height = t->height;
 	fp.num_pixels = (uint32_t)px;
-	fp.sigma_l = t->dn.sigma_luminance;
-	fp.sigma_n = t->dn.sigma_normal;
-	fp.sigma_z = t->dn.sigma_depth;
-	// in double, clamped to FLT_MAX: in float the square underflows for sigma_albedo below ~5.4e-20 and the inverse is
-	// inf, which turns every tap's 0 * inf albedo term into NaN (no pixel filtered); clamped, equal albedos still cost 0
-	fp.inv_sigma_a2 = (float)std::min(1.0 / ((double)t->dn.sigma_albedo * (double)t->dn.sigma_albedo), (double)FLT_MAX);
+	fp.sigma_l = t->dn.p.sigma_luminance;
+	fp.sigma_n = t->dn.p.sigma_normal;
+	fp.sigma_z = t->dn.p.sigma_depth;
+	fp.inv_sigma_a2 = plan.inv_sigma_a2;
 	fp.guide = fguide;
-	const bool spatial_var = t->dn_sv_min > 0 && K >= 1;
-	if (spatial_var) { // pixels with few samples: the variance of their 7x7 neighbourhood's moments (whichever set-up ran)
+	if (plan.spatial_var) { // pixels with few samples: the variance of their 7x7 neighbourhood's moments (whichever set-up ran)
 		SpatialVarParams vp;
 		vp.width = t->width;
 		vp.height = t->height;
-		vp.min_samples = (float)t->dn_sv_min;
+		vp.min_samples = (float)t->dn.sv_min;
 		vp.T = sp.T;
 		vp.P = sp.P;
 		vp.sigma_n = fp.sigma_n;
@@ -705,23 +701,16 @@ static int filter_front(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb, Fi
 		vp.s_cc = staged.cc;
 		vp.s_m = staged.m;
 		vp.io = col;
-		launch_spatial_variance(vp, t->tp_on, demod, t->stream);
+		launch_spatial_variance(vp, t->dn.temporal, plan.demod, t->stream);
 		SRT_HIP(t, hipGetLastError());
 	}
-	// the history feedback: pass 1's colour goes into the set the set-up staged (the switch needs temporal reprojection)
-	const bool feedback = t->tp_feedback && t->tp_on && K >= 1;
-	if (K >= 1) {
-		fp.staged = feedback ? const_cast<float4 *>(staged.cc) : nullptr;
-		launch_pass(t, fp, 0, K, demod, feedback, col, argb);
+	if (K >= 1) { // the history feedback: pass 1's colour goes into the set the set-up staged
+		fp.staged = plan.feedback ? const_cast<float4 *>(staged.cc) : nullptr;
+		launch_pass(t, fp, 0, plan, argb);
 		SRT_HIP(t, hipGetLastError());
 	}
 	f->fp = fp;
-	f->col = col;
-	f->K = K;
-	f->demod = demod;
-	f->spatial_var = spatial_var;
-	f->feedback = feedback;
-	t->last_filter_feedback = feedback;
+	f->plan = plan;
 	return SRT_OK;
 }
 
@@ -730,26 +719,23 @@ int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
 	FilterFront f;
 	const int rc = filter_front(t, ticks_stopped, argb, &f);
 	if (rc) return rc;
-	for (int k = 1; k < f.K; k++) {
-		launch_pass(t, f.fp, k, f.K, f.demod, false, f.col, argb);
+	for (int k = 1; k < f.plan.K; k++) {
+		launch_pass(t, f.fp, k, f.plan, argb);
 		SRT_HIP(t, hipGetLastError());
 	}
-	t->dn_out = f.K & 1;
+	t->dn_out = f.plan.K & 1;
 	t->dn_filtered = true;
-	t->last_filter_demod = f.demod;
-	t->last_filter_sv = f.spatial_var;
+	t->last_filter = f.plan;
 	return SRT_OK;
 }
 
-int srt_denoise_feedback_front(srt_tracer *t, bool *ran) {
-	*ran = false;
-	if (!(t->tp_feedback && t->tp_on && t->dn.iterations >= 1) || full_pixels(t) == 0) return SRT_OK;
+int srt_denoise_feedback_front(srt_tracer *t) {
 	FilterFront f;
 	// no divisor: the temporal set-up divides by T. No ARGB: pass 1 gets none, whether or not it is the last pass (K = 1)
 	const int rc = filter_front(t, 1u, nullptr, &f);
 	if (rc) return rc;
 	t->dn_filtered = false; // the filter's two images hold this run's set-up and pass 1, no filter result
-	*ran = true;
+	t->last_filter.feedback = f.plan.feedback; // the last pass 1 is this one; the rest still tells of the last filter
 	return SRT_OK;
 }
 
@@ -771,15 +757,7 @@ int srt_denoise_defaults(srt_denoise_params *out) {
 int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 	if (!t) return SRT_ERR_INVALID;
 	if (!params || !params->enable) {
-		t->dn_on = false;
-		t->dn_demod = false; // albedo demodulation is a mode of the filter
-		t->dn_sv_min = 0;    // and so is the spatial variance estimate
-		t->tp_on = false; // temporal reprojection is a stage of the denoiser
-		t->tp_illum = false; // (with its illumination mode)
-		t->tp_clamp = 0.f;   // (and its history clamp)
-		t->tp_feedback = false; // (and its history feedback)
-		t->om_on = false; // and object motion a stage of that
-		t->vm_on = false; // (with its per-triangle part)
+		t->dn.off(); // with every mode of the filter and the temporal stage
 		srt_temporal_drop(t);
 		return SRT_OK;
 	}
@@ -794,14 +772,9 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 	SRT_HIP(t, t->dn_mom.reserve(px));
 	SRT_HIP(t, t->dn_guide.reserve(px * 8));
 	SRT_HIP(t, t->dn_col.reserve(px * 8));
-	const bool clear = !t->dn_on || params->feature_samples != t->dn.feature_samples;
-	if (t->tp_clamp > 0.f) t->tp_fresh = false; // the history clamp's bounds take their weights from the filter's sigmas
-	// the history feedback stages pass 1's result: other sigmas or another K (0 against >= 1, the last pass against a middle one) stage another
-	if (t->tp_feedback && (params->iterations != t->dn.iterations || params->sigma_luminance != t->dn.sigma_luminance || params->sigma_normal != t->dn.sigma_normal ||
-	                       params->sigma_depth != t->dn.sigma_depth || params->sigma_albedo != t->dn.sigma_albedo))
-		t->tp_fresh = false;
-	t->dn = *params;
-	t->dn_on = true;
+	const bool clear = !t->dn.on || params->feature_samples != t->dn.p.feature_samples;
+	t->dn.p = *params;
+	t->dn.on = true;
 	if (clear) {
 		t->dn_filtered = false;
 		srt_temporal_drop(t);
@@ -813,46 +786,34 @@ int srt_set_denoise(srt_tracer *t, const srt_denoise_params *params) {
 
 int srt_set_denoise_demodulation(srt_tracer *t, int enable) {
 	if (!t) return SRT_ERR_INVALID;
-	if (!enable) {
-		if (t->dn_demod && t->tp_feedback) t->tp_fresh = false; // the history feedback staged the demodulated pass 1's result
-		t->dn_demod = false;
-		return SRT_OK;
-	}
-	if (!t->dn_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_demodulation: the denoiser is off (srt_set_denoise)");
-	if (!t->dn_demod && t->tp_feedback) t->tp_fresh = false;
-	t->dn_demod = true;
+	if (enable && !t->dn.on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_demodulation: the denoiser is off (srt_set_denoise)");
+	t->dn.demod = enable != 0;
 	return SRT_OK;
 }
 
 int srt_last_filter_demodulated(const srt_tracer *t, int *demodulated) {
 	if (!t || !demodulated) return SRT_ERR_INVALID;
-	*demodulated = t->last_filter_demod ? 1 : 0;
+	*demodulated = t->last_filter.demod ? 1 : 0;
 	return SRT_OK;
 }
 
 int srt_set_denoise_spatial_variance(srt_tracer *t, uint32_t min_samples) {
 	if (!t) return SRT_ERR_INVALID;
-	if (min_samples == 0) {
-		if (t->dn_sv_min && t->tp_feedback) t->tp_fresh = false; // the history feedback staged pass 1 over the estimated variance
-		t->dn_sv_min = 0;
-		return SRT_OK;
-	}
 	if (min_samples > (1u << 20)) return fail(t, SRT_ERR_INVALID, "srt_set_denoise_spatial_variance: min_samples 0..2^20");
-	if (!t->dn_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_spatial_variance: the denoiser is off (srt_set_denoise)");
-	if (min_samples != t->dn_sv_min && t->tp_feedback) t->tp_fresh = false;
-	t->dn_sv_min = min_samples;
+	if (min_samples && !t->dn.on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_spatial_variance: the denoiser is off (srt_set_denoise)");
+	t->dn.sv_min = min_samples;
 	return SRT_OK;
 }
 
 int srt_last_filter_spatial_variance(const srt_tracer *t, int *ran) {
 	if (!t || !ran) return SRT_ERR_INVALID;
-	*ran = t->last_filter_sv ? 1 : 0;
+	*ran = t->last_filter.spatial_var ? 1 : 0;
 	return SRT_OK;
 }
 
 int srt_resolve_denoised(srt_tracer *t, uint32_t ticks_stopped) {
 	if (!t) return SRT_ERR_INVALID;
-	if (!t->dn_on) return fail(t, SRT_ERR_STATE, "srt_resolve_denoised: the denoiser is off (srt_set_denoise)");
+	if (!t->dn.on) return fail(t, SRT_ERR_STATE, "srt_resolve_denoised: the denoiser is off (srt_set_denoise)");
 	if (t->dn_T == 0) return fail(t, SRT_ERR_STATE, "srt_resolve_denoised: nothing traced since the last clear");
 	SRT_HIP(t, hipSetDevice(t->device));
 	SRT_HIP(t, hipEventRecord(t->ev_r0, t->stream));

@@ -178,7 +178,7 @@ void evaluate(const uint32_t *rec, srt_noise_result *out) {
 const char *refusal(const srt_tracer *t) {
 	if (!t->nz->on) return "the noise meter is off (srt_set_noise_meter)";
 	if (t->world > 1) return "not available on a partitioned handle";
-	if (!t->dn_on) return "the denoiser is off: nothing accumulates the moments (srt_set_denoise; iterations = 0 is enough)";
+	if (!t->dn.on) return "the denoiser is off: nothing accumulates the moments (srt_set_denoise; iterations = 0 is enough)";
 	if (t->dn_T == 0 || t->dn_P == 0) return "nothing traced since the last clear";
 	return nullptr;
 }
@@ -250,7 +250,7 @@ int srt_set_noise_meter(srt_tracer *t, const srt_noise_params *p) {
 		return fail(t, SRT_ERR_INVALID, "srt_set_noise_meter: threshold in [2^-24, 2^8], luminance_floor in [2^-20, 2^20], both finite, permille 1..1000, "
 		                                "min_samples >= 1, check_every 1..65536, reserved 0");
 	if (t->world > 1) return fail(t, SRT_ERR_STATE, "srt_set_noise_meter: not available on a partitioned handle (srt_set_partition world > 1)");
-	if (!t->dn_on) return fail(t, SRT_ERR_STATE, "srt_set_noise_meter: the denoiser is off: nothing accumulates the moments (srt_set_denoise; iterations = 0 is enough)");
+	if (!t->dn.on) return fail(t, SRT_ERR_STATE, "srt_set_noise_meter: the denoiser is off: nothing accumulates the moments (srt_set_denoise; iterations = 0 is enough)");
 	SRT_HIP(t, hipSetDevice(t->device));
 	SRT_HIP(t, nz->record.reserve(SRT_NOISE_RECORD_WORDS));
 	for (int k = 0; k < 2; k++) SRT_HIP(t, nz->back[k].reserve(SRT_NOISE_RECORD_WORDS));
@@ -316,7 +316,7 @@ int srt_render_until(srt_tracer *t, const srt_render_data *options, uint32_t tim
 	NoiseState *nz = t->nz;
 	if (!nz->on) return fail(t, SRT_ERR_STATE, "srt_render_until: the noise meter is off (srt_set_noise_meter)");
 	if (t->world > 1) return fail(t, SRT_ERR_STATE, "srt_render_until: not available on a partitioned handle");
-	if (!t->dn_on) return fail(t, SRT_ERR_STATE, "srt_render_until: the denoiser is off: nothing accumulates the moments (srt_set_denoise)");
+	if (!t->dn.on) return fail(t, SRT_ERR_STATE, "srt_render_until: the denoiser is off: nothing accumulates the moments (srt_set_denoise)");
 	SRT_HIP(t, hipSetDevice(t->device));
 	memset(result, 0, sizeof *result);
 	result->level_bin = -1;

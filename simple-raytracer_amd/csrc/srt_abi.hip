@@ -29,7 +29,7 @@ int clear_canvas_impl(srt_tracer *t) {
 	if (rc) return rc;
 	// enqueue_fill_buffer with 0.0f over the whole canvas (src/tracer.cpp:98-101)
 	SRT_HIP(t, hipMemsetAsync(t->canvas, 0, t->canvas_bytes, t->stream));
-	if (t->dn_on) return srt_denoise_clear(t); // the denoiser's accumulations start again with the canvas
+	if (t->dn.on) return srt_denoise_clear(t); // the denoiser's accumulations start again with the canvas
 	return SRT_OK;
 }
 
@@ -267,7 +267,7 @@ int srt_update_scene(srt_tracer *t, const srt_shape *shapes, size_t n_shapes, co
 		std::vector<uint8_t> bytes;
 		if (t && scene) srt_scene_bytes(bytes, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
 		const int rc = update_scene_impl(t, shapes, n_shapes, triangles, n_triangles, materials, n_materials, scene);
-		if (t && t->om_on) { // temporal.hip: object motion compares with the history's scene and keeps what only moved
+		if (t && t->dn.object_motion) { // temporal.hip: object motion compares with the history's scene and keeps what only moved
 			const int mrc = srt_motion_update_scene(t, bytes, rc);
 			if (rc == SRT_OK && mrc != SRT_OK) {
 				t->scene_bytes.swap(bytes);
@@ -757,10 +757,10 @@ static int launch_batch(srt_tracer *t, const Dispatch &d, uint32_t b, TraceParam
 // behind the reductions of a dispatch with a denoiser on: the feature pass, and for the render calls the filter
 static int denoise_tail(srt_tracer *t, const Dispatch &d, const TraceParams &p, uint32_t ticks_stopped) {
 	int rc = srt_denoise_after_trace(t, p, d.ns);
-	if (rc == SRT_OK && d.fused_argb && t->dn_on) rc = srt_denoise_filter(t, ticks_stopped, d.fused_argb);
+	if (rc == SRT_OK && d.fused_argb && t->dn.on) rc = srt_denoise_filter(t, ticks_stopped, d.fused_argb);
 	if (rc) return rc;
 	// a group member rendered on its own: its rows unfiltered (the group's resolver filters whole frames)
-	if (d.fused_argb && !t->dn_on) return launch_resolve(t, t->canvas, (uint32_t)d.pixels, ticks_stopped, d.fused_argb);
+	if (d.fused_argb && !t->dn.on) return launch_resolve(t, t->canvas, (uint32_t)d.pixels, ticks_stopped, d.fused_argb);
 	return SRT_OK;
 }
 
@@ -780,7 +780,7 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 	// The kernel timers (srt_last_kernel_ms, srt_last_trace_kernel_ms) are four event records per dispatch: 10-17 us of a 150 us
 	// interactive frame. srt_trace always takes them; the render calls only when asked to (srt_set_kernel_timers).
 	d.timed = !fused_argb || t->timers_in_render;
-	d.denoise = t->dn_on || t->gd_on;
+	d.denoise = t->dn.on || t->gd_on;
 	d.pixels = owned_pixels(t);
 	d.ns = options->num_samples;
 	d.fused_argb = fused_argb;
@@ -1022,8 +1022,8 @@ int srt_set_partition(srt_tracer *t, int rank, int world, int rows_per_block) {
 	if (world < 1 || rank < 0 || rank >= world || rows_per_block < 1)
 		return fail(t, SRT_ERR_INVALID, "srt_set_partition: need 0 <= rank < world and rows_per_block >= 1");
 	if (t->gd_on) return fail(t, SRT_ERR_STATE, "srt_set_partition: the handle's group has its denoiser on (srt_group_set_denoise(g, NULL) first)");
-	if (world > 1 && t->tp_on) return fail(t, SRT_ERR_STATE, "srt_set_partition: temporal reprojection works on the full frame only (srt_set_denoise_temporal(t, NULL) first)");
-	if (world > 1 && t->dn_on) return fail(t, SRT_ERR_STATE, "srt_set_partition: the denoiser works on the full frame only (srt_set_denoise(t, NULL) first)");
+	if (world > 1 && t->dn.temporal) return fail(t, SRT_ERR_STATE, "srt_set_partition: temporal reprojection works on the full frame only (srt_set_denoise_temporal(t, NULL) first)");
+	if (world > 1 && t->dn.on) return fail(t, SRT_ERR_STATE, "srt_set_partition: the denoiser works on the full frame only (srt_set_denoise(t, NULL) first)");
 	SRT_HIP(t, hipSetDevice(t->device));
 	SRT_HIP(t, hipStreamSynchronize(t->stream));
 	const int padded = srt_partition_padded_rows(t->height, world, rows_per_block);

@@ -729,7 +729,7 @@ int srt_group_set_denoise_demodulation(srt_group *g, int enable) {
 
 int srt_group_last_filter_demodulated(const srt_group *g, int *demodulated) {
 	if (!g || !demodulated) return SRT_ERR_INVALID;
-	*demodulated = (g->resolver && g->resolver->last_filter_demod) ? 1 : 0;
+	*demodulated = (g->resolver && g->resolver->last_filter.demod) ? 1 : 0;
 	return SRT_OK;
 }
 
@@ -745,7 +745,7 @@ int srt_group_set_denoise_history_illumination(srt_group *g, int enable) {
 	return SRT_OK;
 }
 
-int srt_group_last_setup_history_illumination(srt_group *g) { return g && g->resolver && g->resolver->last_setup_illum ? 1 : 0; }
+int srt_group_last_setup_history_illumination(srt_group *g) { return g && g->resolver && g->resolver->last_setup.illum ? 1 : 0; }
 
 int srt_group_set_denoise_history_clamp(srt_group *g, float gamma) {
 	if (!g) return SRT_ERR_INVALID;
@@ -761,7 +761,7 @@ int srt_group_set_denoise_history_clamp(srt_group *g, float gamma) {
 	return SRT_OK;
 }
 
-int srt_group_last_setup_history_clamp(srt_group *g) { return g && g->resolver && g->resolver->last_setup_clamp ? 1 : 0; }
+int srt_group_last_setup_history_clamp(srt_group *g) { return g && g->resolver && g->resolver->last_setup.clamp ? 1 : 0; }
 
 int srt_group_set_denoise_history_feedback(srt_group *g, int enable) {
 	if (!g) return SRT_ERR_INVALID;
@@ -775,7 +775,7 @@ int srt_group_set_denoise_history_feedback(srt_group *g, int enable) {
 	return SRT_OK;
 }
 
-int srt_group_last_filter_history_feedback(srt_group *g) { return g && g->resolver && g->resolver->last_filter_feedback ? 1 : 0; }
+int srt_group_last_filter_history_feedback(srt_group *g) { return g && g->resolver && g->resolver->last_filter.feedback ? 1 : 0; }
 
 int srt_group_set_denoise_spatial_variance(srt_group *g, uint32_t min_samples) {
 	if (!g) return SRT_ERR_INVALID;
@@ -793,7 +793,7 @@ int srt_group_set_denoise_spatial_variance(srt_group *g, uint32_t min_samples) {
 
 int srt_group_last_filter_spatial_variance(const srt_group *g, int *ran) {
 	if (!g || !ran) return SRT_ERR_INVALID;
-	*ran = (g->resolver && g->resolver->last_filter_sv) ? 1 : 0;
+	*ran = (g->resolver && g->resolver->last_filter.spatial_var) ? 1 : 0;
 	return SRT_OK;
 }
 

@@ -1,6 +1,6 @@
 // srt_internal.h — the handle behind `srt_tracer *` and the small helpers the translation units of
 // libsrt_hip.so share (srt_abi.hip: life cycle, scene upload, trace; accel_device.hip: BVH upkeep on the device;
-// srt_collect.hip: multi-GPU collection, frame pipeline). What of the host side needs no handle and no HIP is not here: bvh_host.h, scene_prep.h, trace_plan.h.
+// srt_collect.hip: multi-GPU collection, frame pipeline). What of the host side needs no handle and no HIP is not here: bvh_host.h, scene_prep.h, trace_plan.h, denoise_plan.h.
 // Not part of the public ABI.
 #ifndef SRT_INTERNAL_H
 #define SRT_INTERNAL_H
@@ -8,10 +8,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <optional>
 #include <string>
 #include <vector>
 
 #include "../../include/srt_abi.h"
+#include "denoise_plan.h"
 #include "device_types.h"
 #include "scene_prep.h"
 
@@ -230,40 +232,29 @@ struct srt_tracer {
 	bool count_tris = false;
 	int rank = 0, world = 1, rows_per_block = 8, owned_rows = 0;
 	// edge-aware denoiser (denoise.hip; srt_set_denoise). Full frame only: never on together with world > 1.
-	bool dn_on = false;
+	DenoiseSettings dn;       // what the setters of denoise.hip and temporal.hip set (denoise_plan.h)
+	FilterPlan last_filter;   // the plan of the last filter (srt_last_filter_demodulated, _spatial_variance), its feedback of the last pass 1 (srt_last_filter_history_feedback)
+	SetupPlan last_setup;     // the plan of the last temporal set-up (srt_last_setup_history_illumination, srt_last_setup_history_clamp)
 	bool dn_filtered = false; // dn_col[dn_out] holds a filter result (srt_read_denoised)
-	srt_denoise_params dn{};
 	uint32_t dn_T = 0, dn_P = 0, dn_F = 0; // since the last clear: dispatches, sum of num_samples, feature rays per pixel
+	uint64_t dn_serial = 0;                // srt_denoise_count: names what is traced (a StagingKey's serial)
 	DevBuf<float> dn_nd, dn_ah, dn_mom;    // guide sums (float4 {normals, t}, float4 {albedos, hits}) and moments per pixel
 	DevBuf<float> dn_guide;                // filter set-up: 2 float4 per pixel {N, Z}, {A, cov}
 	DevBuf<float> dn_col;                  // two float4 images {colour, variance}, ping-pong between passes
 	int dn_out = 0;                        // the image of dn_col the last pass wrote
-	bool dn_demod = false;                 // srt_set_denoise_demodulation: the passes filter colour / albedo (K >= 1)
-	bool last_filter_demod = false;        // srt_last_filter_demodulated
-	uint32_t dn_sv_min = 0;                // srt_set_denoise_spatial_variance: pixels with fewer samples get their variance from their 7x7 neighbourhood (0: off)
-	bool last_filter_sv = false;           // srt_last_filter_spatial_variance
 	srt_render_data dn_cam{};              // the last dispatch's render data since the clear (its camera: temporal reprojection)
 	// temporal reprojection (temporal.hip; srt_set_denoise_temporal). Two history sets, each px x 14 floats: float4
 	// {colour, count}, float2 {m1, m2}, 2 float4 guide; tp_set[tp_cur] is the history, the other the frame being integrated
-	bool tp_on = false;
-	srt_temporal_params tp{};
 	DevBuf<float> tp_set[2];
 	int tp_cur = 0;
 	bool tp_valid = false;   // tp_set[tp_cur] holds a history
-	bool tp_fresh = false;   // tp_set[1 - tp_cur] holds the integration of what is traced since the clear (a filter ran after the last trace)
+	std::optional<StagingKey> tp_staged; // srt_temporal_setup: what it made tp_set[1 - tp_cur] under; the commit swaps that set in when the key then is equal, else makes the set itself
 	srt_render_data tp_cam{}; // the history frame's render data
-	bool tp_illum = false;         // srt_set_denoise_history_illumination: the set-ups rescale a history tap by D_p / D_h
-	bool last_setup_illum = false; // srt_last_setup_history_illumination: the last set-up launched an ILLUM variant
-	float tp_clamp = 0.f;          // srt_set_denoise_history_clamp: gamma (0: off); the set-ups clamp the history colour into mu +- gamma sigma
-	DevBuf<float> tp_bounds;       // two float4 planes {mu, sum of weights}, {sigma, taps} (allocated on the first enable; no part of the history)
+	DevBuf<float> tp_bounds;       // the history clamp: two float4 planes {mu, sum of weights}, {sigma, taps} (allocated on the first enable; no part of the history)
 	bool tp_bounds_ran = false;    // srt_temporal_bounds_kernel has written tp_bounds at least once (srt_read_denoise_history_bounds)
-	bool last_setup_clamp = false; // srt_last_setup_history_clamp: the last set-up ran the bounds launch and a CLAMP variant
-	bool tp_feedback = false;          // srt_set_denoise_history_feedback: pass 1 (K >= 1) writes its colour into the staging set
-	bool last_filter_feedback = false; // srt_last_filter_history_feedback: the last pass 1 (a filter's or a clear's) was a feedback instantiation
 	std::vector<uint8_t> scene_bytes; // the last srt_update_scene's arrays and scene data (the history survives an unchanged scene)
 	// object motion (temporal.hip; srt_set_denoise_object_motion): the feature pass stores a shape index per pixel into
 	// om_ids[om_cur]; the commit swaps, so om_ids[1 - om_cur] belongs to the history, traced with the scene om_hist_scene
-	bool om_on = false;
 	DevBuf<uint32_t> om_ids[2];
 	int om_cur = 0;
 	bool om_mixed = false;     // the frame on the canvas was traced with more than one scene (or without indices): it cannot become a history
@@ -275,7 +266,6 @@ struct srt_tracer {
 	// hit triangle's index inside its model into vm_tri[om_cur], and vm_rows[om_cur] holds the frame's world vertices (9
 	// floats per instance triangle, shape vm_first[s]'s first row; vm_first[n_shapes] = all rows). The commit swaps both
 	// with om_cur. vm_ver[k] names the scene vm_rows[k] was written from (0: none), vm_scene_ver the current scene
-	bool vm_on = false;
 	bool om_any_deformed = false; // a shape of om_table is SRT_MOTION_DEFORMED (the deform set-up kernel runs)
 	DevBuf<uint32_t> vm_tri[2];
 	DevBuf<float> vm_rows[2];
@@ -286,7 +276,7 @@ struct srt_tracer {
 	// its OWN rows, packed as its canvas rows are. gd_pack is ONE allocation of srt_planes_slot_floats() floats that one collective
 	// sends: the canvas rows (bound as the canvas, the way srt_bind_canvas does), the normal_depth and albedo_hits planes
 	// (float4 per pixel of the padded rows each) and the moments plane. The filter runs on the group's full-frame resolver
-	// handle; dn_on stays false here, and the public per-handle rules (no denoiser on a partitioned handle) are unchanged.
+	// handle; dn.on stays false here, and the public per-handle rules (no denoiser on a partitioned handle) are unchanged.
 	bool gd_on = false;
 	int gd_feature_samples = 0;
 	DevBuf<float> gd_pack;
@@ -378,14 +368,14 @@ static inline Tex srt_with_textures(const srt_tracer *t, const Base &base) {
 /* denoise.hip: zero the denoiser's accumulations and counts (enqueued); after a dispatch's reductions, the feature pass of
  * that dispatch (p: its TraceParams as srt_trace_fused's last batch left them -- a dispatch without samples has no batch: the
  * batch's fields, radiance and queue among them, are zero, and no feature kernel is launched; else one launch of the kernel
- * last_trace_textured and om_on choose) and the counts; the filter over the canvas into argb (device, width*height*4 bytes) */
+ * last_trace_textured and dn.object_motion choose) and the counts; the filter over the canvas into argb (device, width*height*4 bytes) */
 int srt_denoise_clear(srt_tracer *t);
 int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples);
 int srt_denoise_filter(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb);
-/* the history feedback's part of a clear that has to make the staging set itself (temporal.hip srt_temporal_commit): with the
- * switch on and K >= 1 the filter's front -- set-up, demodulate and spatial-variance launches, pass 1 in its feedback form --
- * without an ARGB image, *ran = true, and the filter's images hold no filter result afterwards; else nothing, *ran = false */
-int srt_denoise_feedback_front(srt_tracer *t, bool *ran);
+/* a clear that has to make the staging set itself under the history feedback (temporal.hip srt_temporal_commit, plan_filter's feedback):
+ * the filter's front -- set-up, demodulate and spatial-variance launches, pass 1 in its feedback form -- without an ARGB image;
+ * the filter's images hold no filter result afterwards */
+int srt_denoise_feedback_front(srt_tracer *t);
 /* the counts of one dispatch of `rd` (T, P, F, the camera) added to t's: srt_denoise_after_trace's, and what a group keeps on
  * its resolver handle for the dispatch all members have just run */
 void srt_denoise_count(srt_tracer *t, const srt_render_data &rd, int feature_samples);
@@ -419,7 +409,7 @@ int srt_vertex_table_sync(srt_tracer *t);
 int srt_exposure_apply(srt_tracer *t, const float *source, float divisor, uint32_t w, uint32_t h, bool picture, uint8_t *argb);
 /* ... for the render calls, whose frame is the canvas or, with the handle's denoiser on, the filter's image (divided already) */
 static inline int srt_exposure_apply_frame(srt_tracer *t, uint32_t ticks_stopped, uint8_t *argb) {
-	if (t->dn_on && t->dn_filtered)
+	if (t->dn.on && t->dn_filtered)
 		return srt_exposure_apply(t, t->dn_col.ptr + (size_t)t->dn_out * full_pixels(t) * 4, 1.0f, (uint32_t)t->width, (uint32_t)t->height, true, argb);
 	return srt_exposure_apply(t, t->canvas, (float)ticks_stopped, (uint32_t)t->width, (uint32_t)t->owned_rows, t->world == 1, argb);
 }

@@ -757,9 +757,9 @@ int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 	p.T = (float)t->dn_T;
 	p.P = (float)t->dn_P;
 	p.F = (float)t->dn_F;
-	p.limit = (float)t->tp.history_limit;
-	p.normal_threshold = t->tp.normal_threshold;
-	p.depth_threshold = t->tp.depth_threshold;
+	p.limit = (float)t->dn.tp.history_limit;
+	p.normal_threshold = t->dn.tp.normal_threshold;
+	p.depth_threshold = t->dn.tp.depth_threshold;
 	p.f_width = (float)t->width;
 	p.f_height = (float)t->height;
 	const srt_render_data &rd = t->dn_cam, &rh = t->tp_cam;
@@ -773,10 +773,10 @@ int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 	p.cam_h[0] = rh.camera_to_world[3].x, p.cam_h[1] = rh.camera_to_world[3].y, p.cam_h[2] = rh.camera_to_world[3].z;
 	p.aspect_h = rh.aspect_ratio;
 	p.fov_h = rh.fov_scale;
-	const bool motion = t->om_on && t->tp_valid && t->om_any_moved; // else: what the library launches without object motion
+	const SetupPlan plan = plan_setup(t->dn, t->tp_valid, t->om_any_moved, t->om_any_deformed);
 	p.mode = TP_NONE;
 	if (t->tp_valid) {
-		if (same_camera(rd, rh)) p.mode = (!motion || invert_rotation(rh, p.rinv)) ? TP_IDENTITY : TP_NONE; // a moved shape projects
+		if (same_camera(rd, rh)) p.mode = (plan.motion_level == 0 || invert_rotation(rh, p.rinv)) ? TP_IDENTITY : TP_NONE; // a moved shape projects
 		else if (invert_rotation(rh, p.rinv)) p.mode = TP_PROJECT;
 	}
 	p.canvas = reinterpret_cast<const float4 *>(t->canvas);
@@ -792,35 +792,31 @@ int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 	p.out = col;
 	p.argb = argb;
 	const dim3 grid((unsigned)((t->width + 15) / 16), (unsigned)((t->height + 15) / 16));
-	// a deformed model: its pixels look their triangles up in the two vertex tables
-	const int motion_level = !motion ? 0 : (t->vm_on && t->om_any_deformed) ? 2 : 1;
-	const bool illum = t->tp_illum; // the same variant for a filter's set-up and for a clear's commit
-	const bool clamp = t->tp_clamp > 0.f && t->tp_valid; // the history clamp: without a history nothing new is launched
 	MotionParams mp = {};
 	VertexParams vp = {};
 	ClampParams cp = {};
-	if (motion_level >= 1) {
+	if (plan.motion_level >= 1) {
 		mp.ids = t->om_ids[t->om_cur].ptr;
 		mp.h_ids = t->om_ids[1 - t->om_cur].ptr;
 		mp.table = t->om_table_dev.ptr;
 		mp.n_shapes = (uint32_t)(t->om_table.size() / SRT_MOTION_WORDS);
 	}
-	if (motion_level == 2) {
+	if (plan.motion_level == 2) { // a deformed model: its pixels look their triangles up in the two vertex tables
 		vp.tris = t->vm_tri[t->om_cur].ptr;
 		vp.rows = t->vm_rows[t->om_cur].ptr;
 		vp.h_rows = t->vm_rows[1 - t->om_cur].ptr;
 		vp.first = t->vm_first_dev.ptr;
 	}
-	if (clamp) {
+	if (plan.clamp) {
 		BoundsParams bp;
 		bp.width = t->width;
 		bp.height = t->height;
 		bp.num_pixels = (uint32_t)px;
 		bp.T = p.T;
 		bp.F = p.F;
-		bp.sigma_n = t->dn.sigma_normal;
-		bp.sigma_z = t->dn.sigma_depth;
-		bp.inv_sigma_a2 = (float)std::min(1.0 / ((double)t->dn.sigma_albedo * (double)t->dn.sigma_albedo), (double)FLT_MAX); // as srt_denoise_filter
+		bp.sigma_n = t->dn.p.sigma_normal;
+		bp.sigma_z = t->dn.p.sigma_depth;
+		bp.inv_sigma_a2 = plan_filter(t->dn).inv_sigma_a2;
 		bp.canvas = p.canvas;
 		bp.normal_depth = p.normal_depth;
 		bp.albedo_hits = p.albedo_hits;
@@ -830,14 +826,16 @@ int launch_setup(srt_tracer *t, float4 *col, uint32_t *argb) {
 		t->tp_bounds_ran = true;
 		cp.bounds = bp.bounds;
 		cp.num_pixels = bp.num_pixels;
-		cp.gamma = t->tp_clamp;
+		cp.gamma = t->dn.clamp_gamma;
 	}
-	setup_launch[motion_level][illum][clamp](t->stream, grid, p, mp, vp, cp);
+	setup_launch[plan.motion_level][plan.illum][plan.clamp](t->stream, grid, p, mp, vp, cp);
 	SRT_HIP(t, hipGetLastError());
-	t->last_setup_illum = illum;
-	t->last_setup_clamp = clamp;
+	t->last_setup = plan;
 	return SRT_OK;
 }
+
+// the key of a staging set made now
+StagingKey key_now(const srt_tracer *t) { return staging_key(t->dn, t->tp_valid, t->om_any_moved, t->om_any_deformed, t->dn_serial); }
 
 bool params_ok(const srt_temporal_params &p) {
 	for (int k = 0; k < 4; k++)
@@ -852,7 +850,7 @@ bool params_ok(const srt_temporal_params &p) {
 
 void srt_temporal_drop(srt_tracer *t) {
 	t->tp_valid = false;
-	t->tp_fresh = false;
+	t->tp_staged.reset();
 }
 
 int srt_temporal_setup(srt_tracer *t, float4 *col, uint32_t *argb, TemporalStaged *staged) {
@@ -863,26 +861,23 @@ int srt_temporal_setup(srt_tracer *t, float4 *col, uint32_t *argb, TemporalStage
 	staged->guide = reinterpret_cast<const float4 *>(stage + off_guide(px));
 	staged->cc = reinterpret_cast<const float4 *>(stage);
 	staged->m = reinterpret_cast<const float2 *>(stage + off_m(px));
-	t->tp_fresh = true;
+	t->tp_staged = key_now(t);
 	return SRT_OK;
 }
 
 int srt_temporal_commit(srt_tracer *t) {
-	if (!t->dn_on || !t->tp_on || t->dn_T == 0 || full_pixels(t) == 0) return SRT_OK; // nothing traced: the history stays
-	if (!t->tp_fresh) {
-		// no filter since the last trace (or a setter since): the staging set is made here. With the history feedback on that is
-		// the filter's own front, pass 1 included (denoise.hip), so that the history never depends on whether a filter ran
-		bool front = false;
-		int rc = srt_denoise_feedback_front(t, &front);
-		if (rc) return rc;
-		if (!front) rc = launch_setup(t, nullptr, nullptr);
+	if (!t->dn.on || !t->dn.temporal || t->dn_T == 0 || full_pixels(t) == 0) return SRT_OK; // nothing traced: the history stays
+	if (!(t->tp_staged == key_now(t))) {
+		// no filter since the last trace, or one whose staging launches were not those of the settings now: the set is made here. With the
+		// history feedback on that is the filter's own front, pass 1 included (denoise.hip), so that the history never depends on whether a filter ran
+		const int rc = plan_filter(t->dn).feedback ? srt_denoise_feedback_front(t) : launch_setup(t, nullptr, nullptr);
 		if (rc) return rc;
 	}
 	t->tp_cur = 1 - t->tp_cur;
 	t->tp_cam = t->dn_cam;
 	t->tp_valid = true;
-	t->tp_fresh = false;
-	if (t->om_on) {
+	t->tp_staged.reset();
+	if (t->dn.object_motion) {
 		if (t->om_mixed) { // traced with more than one scene: no single set of maps leads back to this frame
 			srt_temporal_drop(t);
 		} else {
@@ -900,19 +895,19 @@ int srt_motion_update_scene(srt_tracer *t, const std::vector<uint8_t> &bytes, in
 		return SRT_OK;
 	}
 	if (t->dn_T > 0 && bytes != t->scene_bytes) t->om_mixed = true; // samples of the old scene are on the canvas
-	if (t->vm_on && bytes != t->scene_bytes) t->vm_scene_ver++;      // the next feature pass writes this scene's vertex table
+	if (t->dn.vertex_motion && bytes != t->scene_bytes) t->vm_scene_ver++;      // the next feature pass writes this scene's vertex table
 	SceneView h, c;
 	view_of(bytes, c);
 	t->om_table.assign(c.n_shapes * SRT_MOTION_WORDS, 0u);
 	t->om_any_moved = false;
 	t->om_any_deformed = false;
-	if (t->tp_valid && !(view_of(t->om_hist_scene, h) && motion_table(h, c, t->om_table.data(), &t->om_any_moved, t->vm_on, &t->om_any_deformed))) srt_temporal_drop(t);
+	if (t->tp_valid && !(view_of(t->om_hist_scene, h) && motion_table(h, c, t->om_table.data(), &t->om_any_moved, t->dn.vertex_motion, &t->om_any_deformed))) srt_temporal_drop(t);
 	if (!t->tp_valid) {
 		identity_rows(t->om_table.data(), c.n_shapes, SRT_MOTION_STATIC);
 		t->om_any_moved = false;
 		t->om_any_deformed = false;
 	}
-	if (t->vm_on) {
+	if (t->dn.vertex_motion) {
 		const int vrc = vertex_layout(t, bytes);
 		if (vrc) return vrc;
 	}
@@ -967,40 +962,32 @@ int srt_temporal_defaults(srt_temporal_params *out) {
 int srt_set_denoise_temporal(srt_tracer *t, const srt_temporal_params *params) {
 	if (!t) return SRT_ERR_INVALID;
 	if (!params || !params->enable) {
-		if (t->tp_on) srt_temporal_drop(t);
-		t->tp_on = false;
-		t->om_on = false;
-		t->vm_on = false;
-		t->tp_illum = false; // a mode of the temporal set-up
-		t->tp_clamp = 0.f;   // and so is the history clamp
-		t->tp_feedback = false; // and the history feedback
+		if (t->dn.temporal) srt_temporal_drop(t);
+		t->dn.temporal_off(); // with the modes of the set-up and object motion
 		return SRT_OK;
 	}
 	if (!params_ok(*params))
 		return fail(t, SRT_ERR_INVALID, "srt_set_denoise_temporal: history_limit 1..2^20, normal_threshold -1..1, depth_threshold finite and > 0, reserved 0");
-	if (!t->dn_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_temporal: the denoiser is off (srt_set_denoise)");
+	if (!t->dn.on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_temporal: the denoiser is off (srt_set_denoise)");
 	if (t->world > 1) return fail(t, SRT_ERR_STATE, "srt_set_denoise_temporal: not available on a partitioned handle (srt_set_partition world > 1)");
 	SRT_HIP(t, hipSetDevice(t->device));
 	const size_t px = full_pixels(t);
 	for (int k = 0; k < 2; k++) SRT_HIP(t, t->tp_set[k].reserve(set_floats(px)));
-	if (!t->tp_on) srt_temporal_drop(t);
-	t->tp = *params;
-	t->tp_on = true;
-	t->tp_fresh = false; // the staging set was integrated with the old settings
+	if (!t->dn.temporal) srt_temporal_drop(t);
+	t->dn.tp = *params;
+	t->dn.temporal = true;
 	return SRT_OK;
 }
 
 int srt_set_denoise_history_illumination(srt_tracer *t, int enable) {
 	if (!t) return SRT_ERR_INVALID;
-	if (enable && !t->tp_on)
+	if (enable && !t->dn.temporal)
 		return fail(t, SRT_ERR_STATE, "srt_set_denoise_history_illumination: temporal reprojection is off (srt_set_denoise_temporal)");
-	const bool on = enable != 0;
-	if (on != t->tp_illum) t->tp_fresh = false; // the staging set was integrated by the other variant: the commit runs its own set-up
-	t->tp_illum = on;
+	t->dn.illum = enable != 0;
 	return SRT_OK;
 }
 
-int srt_last_setup_history_illumination(srt_tracer *t) { return t && t->last_setup_illum ? 1 : 0; }
+int srt_last_setup_history_illumination(srt_tracer *t) { return t && t->last_setup.illum ? 1 : 0; }
 
 int srt_set_denoise_history_clamp(srt_tracer *t, float gamma) {
 	if (!t) return SRT_ERR_INVALID;
@@ -1008,28 +995,25 @@ int srt_set_denoise_history_clamp(srt_tracer *t, float gamma) {
 		return fail(t, SRT_ERR_INVALID, "srt_set_denoise_history_clamp: gamma 0 (off) or finite in (0, 64]");
 	if (gamma == 0.0f) gamma = 0.0f; // (-0: off)
 	if (gamma > 0.0f) {
-		if (!t->tp_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_history_clamp: temporal reprojection is off (srt_set_denoise_temporal)");
+		if (!t->dn.temporal) return fail(t, SRT_ERR_STATE, "srt_set_denoise_history_clamp: temporal reprojection is off (srt_set_denoise_temporal)");
 		SRT_HIP(t, hipSetDevice(t->device));
 		SRT_HIP(t, t->tp_bounds.reserve(full_pixels(t) * 8)); // the two planes, on the first enable
 	}
-	if (gamma != t->tp_clamp) t->tp_fresh = false; // the staging set was integrated with the other setting: the commit runs its own set-up
-	t->tp_clamp = gamma;
+	t->dn.clamp_gamma = gamma;
 	return SRT_OK;
 }
 
-int srt_last_setup_history_clamp(srt_tracer *t) { return t && t->last_setup_clamp ? 1 : 0; }
+int srt_last_setup_history_clamp(srt_tracer *t) { return t && t->last_setup.clamp ? 1 : 0; }
 
 int srt_set_denoise_history_feedback(srt_tracer *t, int enable) {
 	if (!t) return SRT_ERR_INVALID;
-	if (enable && !t->tp_on)
+	if (enable && !t->dn.temporal)
 		return fail(t, SRT_ERR_STATE, "srt_set_denoise_history_feedback: temporal reprojection is off (srt_set_denoise_temporal)");
-	const bool on = enable != 0;
-	if (on != t->tp_feedback) t->tp_fresh = false; // the staging set holds the other setting's colour: the commit makes its own
-	t->tp_feedback = on;
+	t->dn.feedback = enable != 0;
 	return SRT_OK;
 }
 
-int srt_last_filter_history_feedback(srt_tracer *t) { return t && t->last_filter_feedback ? 1 : 0; }
+int srt_last_filter_history_feedback(srt_tracer *t) { return t && t->last_filter.feedback ? 1 : 0; }
 
 int srt_read_denoise_history_bounds(srt_tracer *t, float *mean_weight, float *sigma_taps) {
 	if (!t) return SRT_ERR_INVALID;
@@ -1045,13 +1029,12 @@ int srt_read_denoise_history_bounds(srt_tracer *t, float *mean_weight, float *si
 int srt_set_denoise_object_motion(srt_tracer *t, int enable) {
 	if (!t) return SRT_ERR_INVALID;
 	if (!enable) {
-		if (t->om_on) srt_temporal_drop(t);
-		t->om_on = false;
-		t->vm_on = false; // per-triangle motion is a part of it
+		if (t->dn.object_motion) srt_temporal_drop(t);
+		t->dn.object_motion = t->dn.vertex_motion = false; // per-triangle motion is a part of it
 		return SRT_OK;
 	}
-	if (!t->tp_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_object_motion: temporal reprojection is off (srt_set_denoise_temporal)");
-	if (t->om_on) return SRT_OK;
+	if (!t->dn.temporal) return fail(t, SRT_ERR_STATE, "srt_set_denoise_object_motion: temporal reprojection is off (srt_set_denoise_temporal)");
+	if (t->dn.object_motion) return SRT_OK;
 	SRT_HIP(t, hipSetDevice(t->device));
 	const size_t px = full_pixels(t);
 	for (int k = 0; k < 2; k++) {
@@ -1059,7 +1042,7 @@ int srt_set_denoise_object_motion(srt_tracer *t, int enable) {
 		SRT_HIP(t, hipMemsetAsync(t->om_ids[k].ptr, 0xff, px * 4, t->stream));
 	}
 	srt_temporal_drop(t);
-	t->om_on = true;
+	t->dn.object_motion = true;
 	t->om_mixed = t->dn_T > 0; // what is on the canvas was traced without shape indices
 	static_table(t);
 	return SRT_OK;
@@ -1081,7 +1064,7 @@ int srt_read_denoise_shape_ids(srt_tracer *t, uint32_t *current, uint32_t *histo
 
 int srt_read_denoise_motion(srt_tracer *t, uint32_t *table, size_t capacity_shapes, size_t *n_shapes, int *any_moved) {
 	if (!t) return SRT_ERR_INVALID;
-	if (!t->om_on) return fail(t, SRT_ERR_STATE, "srt_read_denoise_motion: object motion is off (srt_set_denoise_object_motion)");
+	if (!t->dn.object_motion) return fail(t, SRT_ERR_STATE, "srt_read_denoise_motion: object motion is off (srt_set_denoise_object_motion)");
 	const size_t n = t->om_table.size() / SRT_MOTION_WORDS;
 	if (n_shapes) *n_shapes = n;
 	if (any_moved) *any_moved = (t->tp_valid && t->om_any_moved) ? 1 : 0;
@@ -1135,12 +1118,12 @@ int srt_motion_table_deform_host(const srt_shape *h_shapes, size_t h_n_shapes, c
 int srt_set_denoise_vertex_motion(srt_tracer *t, int enable) {
 	if (!t) return SRT_ERR_INVALID;
 	if (!enable) {
-		if (t->vm_on) srt_temporal_drop(t);
-		t->vm_on = false;
+		if (t->dn.vertex_motion) srt_temporal_drop(t);
+		t->dn.vertex_motion = false;
 		return SRT_OK;
 	}
-	if (!t->om_on) return fail(t, SRT_ERR_STATE, "srt_set_denoise_vertex_motion: object motion is off (srt_set_denoise_object_motion)");
-	if (t->vm_on) return SRT_OK;
+	if (!t->dn.object_motion) return fail(t, SRT_ERR_STATE, "srt_set_denoise_vertex_motion: object motion is off (srt_set_denoise_object_motion)");
+	if (t->dn.vertex_motion) return SRT_OK;
 	SRT_HIP(t, hipSetDevice(t->device));
 	const size_t px = full_pixels(t);
 	for (int k = 0; k < 2; k++) {
@@ -1151,7 +1134,7 @@ int srt_set_denoise_vertex_motion(srt_tracer *t, int enable) {
 	if (rc) return rc;
 	t->vm_scene_ver++; // whatever the tables hold, the next feature pass writes the current scene's
 	srt_temporal_drop(t);
-	t->vm_on = true;
+	t->dn.vertex_motion = true;
 	t->om_mixed = t->dn_T > 0; // what is on the canvas was traced without triangle indices
 	static_table(t);
 	return SRT_OK;

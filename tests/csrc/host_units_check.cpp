@@ -1,6 +1,7 @@
 // host_units_check.cpp -- the three host units of csrc/ that need no device, without the library: the BVH builder
-// (bvh_host.cpp), the scene's host pass with its hierarchy cache (scene_prep.cpp) and the launch plan (trace_plan.h).
-// usage: host_units_check bvh | scene | plan | batches   (tests/test_host_units.py; scripts/host_asan.sh runs bvh, scene and batches under sanitizers)
+// (bvh_host.cpp), the scene's host pass with its hierarchy cache (scene_prep.cpp), the launch plan (trace_plan.h) and the
+// denoiser's settings, plans and staging key (denoise_plan.h).
+// usage: host_units_check bvh | scene | plan | batches | denoise   (tests/test_host_units.py; scripts/host_asan.sh runs bvh, scene and batches under sanitizers)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -9,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "denoise_plan.h"
 #include "scene_prep.h"
 #include "trace_plan.h"
 
@@ -294,12 +296,80 @@ static int mode_batches() {
 	}
 }
 
+// ---- denoise ------------------------------------------------------------------------------------------------------------------
+// One row per point of the lattice K x demod x sv_min x temporal x illum x gamma x feedback x history_valid x any_moved x
+// any_deformed x vertex_motion (object motion on throughout; the sigmas and thresholds fixed): the point, then plan_filter (K
+// demod spatial_var feedback inv_sigma_a2), plan_setup (motion_level illum clamp) and the staging key's fields as one word.
+// Then operator== over every ordered pair against equality of those words, the cascades, and "ok".
+static std::string key_word(const StagingKey &k) {
+	char b[256];
+	snprintf(b, sizeof b, "%llu/%d%d%d%d%d/%d/%d/%u/%a/%a/%a/%a/%a/%a/%a", (unsigned long long)k.serial, k.history_valid, k.illum, k.feedback, k.demod, k.pass1_last,
+	         k.history_limit, k.motion_level, k.sv_min, k.normal_threshold, k.depth_threshold, k.clamp_gamma, k.sigma_l, k.sigma_n, k.sigma_z, k.inv_sigma_a2);
+	return b;
+}
+
+static DenoiseSettings all_on() {
+	DenoiseSettings s;
+	s.on = s.demod = s.temporal = s.illum = s.feedback = s.object_motion = s.vertex_motion = true;
+	s.p.iterations = 3, s.p.feature_samples = 2, s.p.sigma_luminance = 4.0f, s.p.sigma_normal = 128.0f, s.p.sigma_depth = 1.0f, s.p.sigma_albedo = 0.1f;
+	s.sv_min = 8;
+	s.tp.history_limit = 32, s.tp.normal_threshold = 0.9f, s.tp.depth_threshold = 0.05f;
+	s.clamp_gamma = 1.0f;
+	return s;
+}
+
+static int mode_denoise() {
+	std::vector<StagingKey> keys;
+	std::vector<std::string> words;
+	for (int K : {0, 1, 3})
+		for (int bits = 0; bits < 512; bits++)
+			for (float gamma : {0.0f, 1.0f, 2.0f}) {
+				DenoiseSettings s = all_on();
+				s.p.iterations = K;
+				s.demod = bits & 1, s.sv_min = bits & 2 ? 8 : 0, s.temporal = bits & 4, s.illum = bits & 8, s.feedback = bits & 16;
+				s.clamp_gamma = gamma;
+				const bool valid = bits & 32, moved = bits & 64, deformed = bits & 128;
+				s.vertex_motion = bits & 256;
+				const FilterPlan f = plan_filter(s);
+				const SetupPlan u = plan_setup(s, valid, moved, deformed);
+				keys.push_back(staging_key(s, valid, moved, deformed, 7));
+				words.push_back(key_word(keys.back()));
+				printf("%d %d %u %d %d %g %d %d %d %d %d  %d %d %d %d %a  %d %d %d  %s\n", K, s.demod, s.sv_min, s.temporal, s.illum, gamma, s.feedback, valid, moved, deformed,
+				       s.vertex_motion, f.K, f.demod, f.spatial_var, f.feedback, f.inv_sigma_a2, u.motion_level, u.illum, u.clamp, words.back().c_str());
+			}
+	for (size_t a = 0; a < keys.size(); a++)
+		for (size_t b = 0; b < keys.size(); b++)
+			CHECK((keys[a] == keys[b]) == (words[a] == words[b]), "operator== and the printed fields disagree for rows %zu and %zu", a, b);
+	StagingKey other = keys[0];
+	other.serial++;
+	CHECK(!(other == keys[0]), "another serial is another key");
+	// a tiny sigma_albedo: the square underflows in float; the inverse is clamped, not inf
+	DenoiseSettings tiny = all_on();
+	tiny.p.sigma_albedo = 1e-30f;
+	CHECK(plan_filter(tiny).inv_sigma_a2 == FLT_MAX, "inv_sigma_a2 %a", plan_filter(tiny).inv_sigma_a2);
+	// the cascades: what is a mode of a stage goes off with it; the parameters and what is not stay
+	const DenoiseSettings fresh;
+	DenoiseSettings s = all_on();
+	s.temporal_off();
+	CHECK(s.temporal == fresh.temporal && s.illum == fresh.illum && s.clamp_gamma == fresh.clamp_gamma && s.feedback == fresh.feedback &&
+	      s.object_motion == fresh.object_motion && s.vertex_motion == fresh.vertex_motion, "temporal_off leaves a mode of the temporal stage on");
+	CHECK(s.on && s.demod && s.sv_min == 8 && s.p.iterations == 3 && s.tp.history_limit == 32, "temporal_off touches the filter's settings or the parameters");
+	s = all_on();
+	s.off();
+	CHECK(s.on == fresh.on && s.demod == fresh.demod && s.sv_min == fresh.sv_min && s.temporal == fresh.temporal && s.illum == fresh.illum &&
+	      s.clamp_gamma == fresh.clamp_gamma && s.feedback == fresh.feedback && s.object_motion == fresh.object_motion && s.vertex_motion == fresh.vertex_motion,
+	      "off leaves a switch on");
+	printf("ok\n");
+	return 0;
+}
+
 int main(int argc, char **argv) {
 	const std::string mode = argc > 1 ? argv[1] : "";
 	if (mode == "bvh") return mode_bvh();
 	if (mode == "scene") return mode_scene();
 	if (mode == "plan") return mode_plan();
 	if (mode == "batches") return mode_batches();
-	fprintf(stderr, "usage: %s bvh | scene | plan | batches\n", argv[0]);
+	if (mode == "denoise") return mode_denoise();
+	fprintf(stderr, "usage: %s bvh | scene | plan | batches | denoise\n", argv[0]);
 	return 2;
 }

@@ -1,8 +1,9 @@
-"""CPU: the three host units of csrc/ that need no device, compiled with g++ and run WITHOUT the library
+"""CPU: the host units of csrc/ that need no device, compiled with g++ and run WITHOUT the library
 (tests/csrc/host_units_check.cpp): the BVH builder (bvh_host.cpp: threaded against one-thread build, refit, stack bound), the
 scene's host pass with its hierarchy cache (scene_prep.cpp: reuse, refit, claim, eviction, an error that keeps the cache) and
 the launch plan of srt_trace (trace_plan.h) against the table the parent of the split printed (tests/golden/
-trace_plan_parent.json), with the slices its batches cut a dispatch into. And the g++ build of the builder against the library's, bit for bit."""
+trace_plan_parent.json), with the slices its batches cut a dispatch into; the denoiser's settings, plans and staging key
+(denoise_plan.h) against the rules of include/srt_abi.h restated here. And the g++ build of the builder against the library's, bit for bit."""
 import ctypes as C
 import json
 import subprocess
@@ -83,3 +84,53 @@ def test_gxx_build_of_the_builder_equals_the_librarys(tmp_path, monkeypatch):
         for g, w in zip(got[1:], want[1:]):
             assert g["blocks"].tobytes() == w["blocks"].tobytes() and np.array_equal(g["dest"], w["dest"]), name
             assert (g["root"], g["stack_need"], g["balanced"]) == (w["root"], w["stack_need"], w["balanced"]), name
+
+
+def _restated_plans(K, demod, sv_min, temporal, illum, gamma, feedback, valid, moved, deformed, vertex_motion):
+    """The rules as include/srt_abi.h states them (object motion is on at every lattice point). Filter: the demodulated passes
+    and the spatial variance estimate run with "the switch on and K >= 1"; pass 1 is a feedback instantiation with the switch
+    on, temporal reprojection on and K >= 1. Set-up: the per-shape maps are used when a shape has moved against a valid
+    history, the vertex tables when per-triangle motion is on and a mesh has deformed; the illumination kernels with the switch
+    on; the bounds launch and a clamping set-up with gamma > 0 and a history to clamp."""
+    f = (K, int(demod and K >= 1), int(sv_min > 0 and K >= 1), int(feedback and temporal and K >= 1))
+    motion = valid and moved
+    u = (0 if not motion else 2 if vertex_motion and deformed else 1, int(illum), int(gamma > 0 and valid))
+    return f, u
+
+
+def _restated_consumed(point):
+    """What the launches that make the staging set depend on, of a lattice point (the sigmas and thresholds are the same at
+    every point): nothing without temporal reprojection; else the validity of the history (the set-up's mode), the set-up's
+    instantiation, gamma where the clamp runs, and under the feedback what the filter's front up to pass 1 takes: the
+    demodulate launch, the estimate's threshold where it runs, and whether pass 1 is also the last pass (K = 1), which is
+    another instantiation of the demodulated kernel and the only thing of K that pass 1 sees."""
+    K, demod, sv_min, temporal, illum, gamma, feedback, valid, moved, deformed, vertex_motion = point
+    if not temporal:
+        return ()
+    f, u = _restated_plans(*point)
+    front = (f[1], sv_min if f[2] else 0, K == 1) if f[3] else None
+    return (valid, u[0], u[1], gamma if u[2] else 0.0, front)
+
+
+def test_denoise_plans_and_staging_key(exe):
+    """denoise_plan.h over the whole lattice: plan_filter and plan_setup equal the restated rules; two staging keys are equal
+    exactly when the restated plans and every field they consume are equal (every ordered pair: the map between the keys'
+    printed fields and the restated dependencies is one to one, and the program has checked operator== against the printed
+    fields pair by pair); the cascades of temporal_off() and off() (checked by the program)."""
+    out = subprocess.run([str(exe), "denoise"], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-2000:] + out.stderr
+    rows = [line.split() for line in out.stdout.splitlines()[:-1]]
+    assert len(rows) == 3 * 2**9 * 3
+    want_inv = float(np.float32(min(1.0 / (float(np.float32(0.1)) ** 2), float(np.finfo(np.float32).max))))
+    by_key, by_consumed, points = {}, {}, set()
+    for r in rows:
+        point = (int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), float(r[5]), *map(int, r[6:11]))
+        points.add(point)
+        f, u = _restated_plans(*point)
+        assert tuple(map(int, r[11:15])) == f and float.fromhex(r[15]) == want_inv, (point, r[11:16])
+        assert tuple(map(int, r[16:19])) == u, (point, r[16:19])
+        consumed = _restated_consumed(point)
+        assert by_key.setdefault(r[19], consumed) == consumed, ("equal keys, other dependencies", point, r[19])
+        assert by_consumed.setdefault(consumed, r[19]) == r[19], ("equal dependencies, other keys", point, r[19])
+    assert len(points) == len(rows)
+    assert len(by_key) == len(by_consumed) > 100
