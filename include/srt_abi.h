@@ -1096,7 +1096,7 @@ int srt_selftest_noise_meter(srt_tracer *t, const float *canvas_host, const floa
  * Before any scene is set every valid ray misses.
  * COUNTS AND ERRORS. n == 0: SRT_OK, no launch. A null pointer with n > 0, unknown flag bits, n >= 2^31, a device pointer not
  * aligned to 16 bytes: SRT_ERR_INVALID. The host forms keep ONE growing staging allocation per handle (72 B per ray of the
- * largest call), freed in srt_destroy.
+ * largest call; the occlusion queries below share it), freed in srt_destroy.
  *
  * srt_cast_rays: host arrays, blocking. srt_cast_rays_device: n srt_ray / n srt_ray_hit in device memory of the handle's
  * device, each 16-byte aligned, asynchronous on the handle's stream (srt_synchronize, or work on the bound stream, follows). */
@@ -1121,6 +1121,58 @@ int srt_group_pick(srt_group *g, const srt_render_data *options, const float *xy
 int srt_last_ray_query_ms(srt_tracer *t, float *ms);
 /* Host-only: out = {sizeof(srt_ray), sizeof(srt_ray_hit)} as the library was built. */
 int srt_ray_query_sizes(size_t out[2]);
+
+/* ---- occlusion queries (new): any-hit rays and segments with early exit ---------------------------------------------------- */
+
+/* Is anything in the handle's scene closer than tmax along each of n rays -- is B visible from A, does a place have a clear
+ * line to the light, which of these sample points see the sun -- answered as one bit per ray. What a cast answers with
+ * hit.t < tmax, without the rest of the cast: the walk stops at a ray's first hit instead of looking for the closest, nothing
+ * is fetched for a normal or a material, and 32 bytes go in and 2 bits come out per ray. Records: srt_ray, srt_segment.
+ *
+ * THE ANSWER is a bit mask: ray q is bit q & 63 of 64-bit word q >> 6, ceil(n / 64) words. The bits of the last word past n are
+ * written as 0; words past the last are not touched. `invalid` (may be NULL: then it is not written) has the same layout.
+ * SAME RAY, SAME ANSWER. Bit q of `occluded` is set exactly when srt_cast_rays of the same ray with the same flags would set
+ * SRT_HIT_HIT; the ray contract of "ray queries" above holds unchanged:
+ *   - the ray starts at its origin, with the intersectors' own self-intersection rule and no tmin of its own;
+ *   - the direction is normalised with the kernels' normalize3 unless SRT_RAYS_UNIT_DIRECTIONS is given;
+ *   - tmax is the strict bound: a surface at exactly tmax does not occlude, and tmax <= 0 (-0 and -inf included) is not
+ *     traversed: visible;
+ *   - a shape WITHOUT a material (index < 0) OCCLUDES, as the cast reports it, unlike the trace, which shows the sky through it;
+ *     so does glass: the answer is about geometry, not about light;
+ *   - the tests are the cast's own (spheres, planes, the model boxes, Moller-Trumbore, the hierarchy's padded boxes and
+ *     slack), against a limit that stays at tmax; which of several occluders is met first is not defined and not reported.
+ * HOSTILE RAYS. The cast's validity rules, decided on the DEVICE: an invalid ray is not traversed, is NOT occluded, and has its
+ * bit set in `invalid` when that mask is given. No ray makes the walk run on or read outside the scene's buffers, and the call
+ * still returns SRT_OK.
+ * SEGMENTS. srt_segment {from, end_gap, to, reserved = 0}: a small kernel turns each into an srt_ray in the handle's staging
+ * buffer with functions the kernels already have -- d = to - from, direction = normalize3(d), tmax = dot3(d, direction) -
+ * end_gap, origin = from -- and the occlusion launch follows with unit directions. end_gap > 0 keeps the end's own surface
+ * from occluding a point that lies on it (tmax is then the distance to a point end_gap in front of `to`). from == to (a zero
+ * direction), a non-finite component, a negative or non-finite end_gap and a non-zero `reserved` (tmax = NaN) give an invalid
+ * ray by the rules above. srt_segment_rays returns exactly those records (blocking), so
+ * srt_occluded_rays(srt_segment_rays(segs), SRT_RAYS_UNIT_DIRECTIONS) equals srt_occluded_segments(segs) bit for bit.
+ * STATE. As a cast: the scene as the last srt_update_scene left it, ordered on the handle's stream behind that update's
+ * pre-pass, refit and build. Outputs are written only to the caller's arrays and to the handle's ONE staging allocation, the
+ * ray queries' own (now the largest of 72 B per ray of a cast or pick and 64 B per ray + 16 B per 64 rays of a call here);
+ * canvas, counters, denoiser planes, exposure and noise state stay as they were, and so does every srt_last_trace_* answer.
+ * Before any scene is set every valid ray is visible. srt_last_ray_query_ms covers these launches too (for the segment form,
+ * the ray set-up and the occlusion launch).
+ * COUNTS AND ERRORS. n == 0: SRT_OK, no launch. A NULL required pointer with n > 0 (`invalid` alone is optional in the ray
+ * forms), unknown flag bits, n >= 2^31, device rays not aligned to 16 bytes or a device mask not aligned to 8: SRT_ERR_INVALID.
+ *
+ * srt_occluded_rays / srt_occluded_segments: host arrays, blocking. srt_occluded_rays_device: n srt_ray and the mask words in
+ * device memory of the handle's device, asynchronous on the handle's stream. */
+int srt_occluded_rays(srt_tracer *t, const srt_ray *rays, size_t n, uint32_t flags, uint64_t *occluded, uint64_t *invalid /* may be NULL */);
+int srt_occluded_rays_device(srt_tracer *t, const void *rays_dev, size_t n, uint32_t flags, void *occluded_dev, void *invalid_dev /* may be NULL */);
+int srt_occluded_segments(srt_tracer *t, const srt_segment *segs, size_t n, uint64_t *occluded, uint64_t *invalid /* may be NULL */);
+/* The rays the segment form casts, n srt_ray; blocking. */
+int srt_segment_rays(srt_tracer *t, const srt_segment *segs, size_t n, srt_ray *rays_out);
+/* On the group's first member, as srt_group_cast_rays. */
+int srt_group_occluded_rays(srt_group *g, const srt_ray *rays, size_t n, uint32_t flags, uint64_t *occluded, uint64_t *invalid);
+int srt_group_occluded_segments(srt_group *g, const srt_segment *segs, size_t n, uint64_t *occluded, uint64_t *invalid);
+int srt_group_segment_rays(srt_group *g, const srt_segment *segs, size_t n, srt_ray *rays_out);
+/* Host-only: out = {sizeof(srt_segment), the bytes of one mask word (8)} as the library was built. */
+int srt_occlusion_sizes(size_t out[2]);
 
 /* Device self-test of the deterministic math (tests only). Walks r = 0, stride, ... over
  * all 2^32 RNG outputs: out[0..2] = mismatch counts of the kernel-local sqrt / log / cos

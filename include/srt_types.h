@@ -240,6 +240,15 @@ typedef struct srt_ray_hit {
 #define SRT_HIT_FRONT 2u
 #define SRT_HIT_INVALID_RAY 4u
 
+/* Occlusion queries (srt_occluded_segments, srt_segment_rays; include/srt_abi.h "occlusion queries"): is anything between
+ * `from` and the point end_gap short of `to`. 32 bytes, read by the device as two 128-bit words. */
+typedef struct srt_segment {
+	float from[3];
+	float end_gap; /* >= 0, finite: the stretch in front of `to` that does not count (0: up to `to` itself, exclusive) */
+	float to[3];
+	float reserved; /* must be 0 */
+} srt_segment;
+
 #ifdef __cplusplus
 }
 #endif
@@ -314,5 +323,8 @@ SRT_STATIC_ASSERT(sizeof(srt_ray) == 32, "Ray 32 B");
 SRT_STATIC_ASSERT(offsetof(srt_ray, direction) == 16, "Ray.direction@16");
 SRT_STATIC_ASSERT(sizeof(srt_ray_hit) == 32, "RayHit 32 B");
 SRT_STATIC_ASSERT(offsetof(srt_ray_hit, normal) == 16, "RayHit.normal@16");
+SRT_STATIC_ASSERT(sizeof(srt_segment) == 32, "Segment 32 B");
+SRT_STATIC_ASSERT(offsetof(srt_segment, end_gap) == 12, "Segment.end_gap@12");
+SRT_STATIC_ASSERT(offsetof(srt_segment, to) == 16, "Segment.to@16");
 
 #endif /* SRT_TYPES_H */

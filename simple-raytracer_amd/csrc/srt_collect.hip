@@ -958,6 +958,25 @@ int srt_group_pick(srt_group *g, const srt_render_data *options, const float *xy
 	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
 }
 
+// occlusion queries (occlusion.hip), likewise
+int srt_group_occluded_rays(srt_group *g, const srt_ray *rays, size_t n, uint32_t flags, uint64_t *occluded, uint64_t *invalid) {
+	if (!g || g->t.empty()) return SRT_ERR_INVALID;
+	const int rc = srt_occluded_rays(g->t[0], rays, n, flags, occluded, invalid);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+int srt_group_occluded_segments(srt_group *g, const srt_segment *segs, size_t n, uint64_t *occluded, uint64_t *invalid) {
+	if (!g || g->t.empty()) return SRT_ERR_INVALID;
+	const int rc = srt_occluded_segments(g->t[0], segs, n, occluded, invalid);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+int srt_group_segment_rays(srt_group *g, const srt_segment *segs, size_t n, srt_ray *rays_out) {
+	if (!g || g->t.empty()) return SRT_ERR_INVALID;
+	const int rc = srt_segment_rays(g->t[0], segs, n, rays_out);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
 int srt_group_get_counters(srt_group *g, srt_counters *out) {
 	if (!g || !out) return SRT_ERR_INVALID;
 	memset(out, 0, sizeof *out);

@@ -310,7 +310,8 @@ struct srt_tracer {
 	NoiseState *nz = &nz_own;         // ... shared the same way
 	uint32_t last_trace_plane_form = 0; // srt_last_trace_plane_form
 	// ray queries (ray_query.hip; srt_cast_rays, srt_pick): the host forms' one staging allocation -- n rays, n hits, n picked
-	// points (32 + 32 + 8 bytes each) of the largest call so far -- and the timers' span around the last query's launches
+	// points (32 + 32 + 8 bytes each) of the largest call so far -- and the timers' span around the last query's launches;
+	// occlusion queries (occlusion.hip) use both: n rays, n segments and two bit masks in the same allocation
 	DevBuf<uint8_t> rq_stage;
 	TimedSpan rq_span;
 	hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;

@@ -419,6 +419,30 @@ class Tracer {
 		return hits;
 	}
 	srt_ray_hit pick(float x, float y) { return pick(std::vector<float>{x, y})[0]; }
+	/// Occlusion queries (srt_occluded_rays): is anything closer than tmax along each ray -- true exactly where cast_rays would
+	/// report a hit, without looking for the closest one. invalid (optional): the rays the device refused. Blocking.
+	std::vector<bool> occluded(const std::vector<srt_ray> &rays, bool unit_directions = false, std::vector<bool> *invalid = nullptr) {
+		std::vector<uint64_t> occ((rays.size() + 63) / 64), inv(invalid ? occ.size() : 0);
+		const uint32_t flags = unit_directions ? SRT_RAYS_UNIT_DIRECTIONS : 0u;
+		check(group ? srt_group_occluded_rays(group, rays.data(), rays.size(), flags, occ.data(), invalid ? inv.data() : nullptr)
+		            : srt_occluded_rays(handle, rays.data(), rays.size(), flags, occ.data(), invalid ? inv.data() : nullptr));
+		if (invalid) *invalid = mask_bits(inv, rays.size());
+		return mask_bits(occ, rays.size());
+	}
+	/// ... between `from` and the point end_gap short of `to` of each segment (srt_occluded_segments): a line of sight.
+	std::vector<bool> occluded(const std::vector<srt_segment> &segments, std::vector<bool> *invalid = nullptr) {
+		std::vector<uint64_t> occ((segments.size() + 63) / 64), inv(invalid ? occ.size() : 0);
+		check(group ? srt_group_occluded_segments(group, segments.data(), segments.size(), occ.data(), invalid ? inv.data() : nullptr)
+		            : srt_occluded_segments(handle, segments.data(), segments.size(), occ.data(), invalid ? inv.data() : nullptr));
+		if (invalid) *invalid = mask_bits(inv, segments.size());
+		return mask_bits(occ, segments.size());
+	}
+	/// the first n bits of a mask: ray q is bit q & 63 of word q >> 6
+	static std::vector<bool> mask_bits(const std::vector<uint64_t> &words, size_t n) {
+		std::vector<bool> bits(n);
+		for (size_t q = 0; q < n; q++) bits[q] = (words[q >> 6] >> (q & 63)) & 1u;
+		return bits;
+	}
 	srt_tracer *native_handle() { return group ? srt_group_tracer(group, 0) : handle; }
 };
 

@@ -72,12 +72,15 @@ RAY_HIT = np.dtype({"names": ["t", "shape", "triangle", "material", "normal", "f
 HIT_NONE = 0xFFFFFFFF  # RAY_HIT shape / triangle of a miss (triangle: also of a sphere or a plane)
 RAYS_UNIT_DIRECTIONS = 1
 HIT_HIT, HIT_FRONT, HIT_INVALID_RAY = 1, 2, 4
+# srt_segment (occlusion queries: Tracer.occluded_segments, Tracer.segment_rays), 32 bytes; "from" is the start point
+SEGMENT = np.dtype({"names": ["from", "end_gap", "to", "reserved"], "formats": [F3, np.float32, F3, np.float32],
+                    "offsets": [0, 12, 16, 28], "itemsize": 32})
 
 SHAPE_SPHERE, SHAPE_PLANE, SHAPE_MODEL = 0, 1, 2
 
 assert MATERIAL.itemsize == 64 and TRIANGLE.itemsize == 96 and SHAPE.itemsize == 128
 assert RENDER_DATA.itemsize == 112 and SCENE_DATA.itemsize == 96
-assert RAY.itemsize == 32 and RAY_HIT.itemsize == 32
+assert RAY.itemsize == 32 and RAY_HIT.itemsize == 32 and SEGMENT.itemsize == 32
 
 
 def rays(origins, directions, tmax=np.inf):
@@ -89,6 +92,22 @@ def rays(origins, directions, tmax=np.inf):
     r["origin"], r["direction"] = o, d
     r["tmax"] = np.asarray(tmax, np.float32)
     return r
+
+
+def segments(start, to, end_gap=0.0):
+    """SEGMENT records from (n, 3) or (3,) start and end points (broadcast against each other) and a scalar or (n,) end_gap."""
+    a = np.atleast_2d(np.asarray(start, np.float32))
+    b = np.atleast_2d(np.asarray(to, np.float32))
+    s = np.zeros(max(len(a), len(b)), SEGMENT)
+    s["from"], s["to"] = a, b
+    s["end_gap"] = np.asarray(end_gap, np.float32)
+    return s
+
+
+def mask_bits(words, n):
+    """The first n bits of an occlusion mask (uint64 words; ray q is bit q & 63 of word q >> 6) as a bool array."""
+    w = np.ascontiguousarray(words, np.uint64)
+    return np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool)
 
 
 def f32(x):

@@ -32,6 +32,9 @@
 // --pick X,Y (may be given several times): after the scene is loaded, the hit under the image point (X, Y) -- continuous pixel
 //                coordinates, a pixel's centre is (px + 0.5, py + 0.5) -- through the first frame's camera (Tracer::pick); one line
 //                per pick: shape, triangle, material (-1: none), t, position, normal. Then the frames render as before.
+// --line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP] (may be given several times): after the scene is loaded, is the point GAP (default 0)
+//                short of (X1, Y1, Z1) visible from (X0, Y0, Z0) (Tracer::occluded); one line per question: `visible`, `occluded`
+//                or `invalid`. Then the frames render as before.
 // --move DX: the camera moves by DX along x every frame and every frame clears the canvas, as the front-end does while moving
 // --move-shape I DX: with --temporal, shape I (a sphere, a plane or a model instance) moves by DX along x every frame and every
 //                frame clears the canvas, as the front-end does while a gizmo is dragged; turns object motion on
@@ -160,6 +163,7 @@ int main(int argc, char **argv) {
 	uint32_t bvh_build_min = 0;
 	int bvh_order = SRT_BUILD_ORDER_MORTON;
 	std::vector<float> picks; // --pick X,Y: x0, y0, x1, y1, ...
+	std::vector<srt_segment> sights; // --line-of-sight
 	for (int i = 1; i < argc; i++) {
 		std::string a = argv[i];
 		auto next = [&]() -> const char * {
@@ -264,12 +268,20 @@ int main(int argc, char **argv) {
 			}
 			picks.push_back(x), picks.push_back(y);
 		}
+		else if (a == "--line-of-sight") { // X0,Y0,Z0:X1,Y1,Z1[:GAP]
+			srt_segment sg{};
+			if (std::sscanf(next(), "%f,%f,%f:%f,%f,%f:%f", &sg.from[0], &sg.from[1], &sg.from[2], &sg.to[0], &sg.to[1], &sg.to[2], &sg.end_gap) < 6) {
+				std::cerr << "--line-of-sight takes X0,Y0,Z0:X1,Y1,Z1[:GAP]\n";
+				return 2;
+			}
+			sights.push_back(sg);
+		}
 		else if (a == "--move") move = std::strtof(next(), nullptr), moving = true;
 		else if (a == "--move-shape") move_shape = std::atoi(next()), shape_move = std::strtof(next(), nullptr);
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--pick X,Y]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
+			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--pick X,Y]... [--line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP]]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
@@ -530,6 +542,17 @@ int main(int argc, char **argv) {
 			std::printf("pick %g,%g: shape %u triangle %d material %d t %.9g position %.9g %.9g %.9g normal %.9g %.9g %.9g\n", picks[2 * k], picks[2 * k + 1],
 			            h.shape, h.triangle == SRT_HIT_NONE ? -1 : (int)h.triangle, h.material, h.t, r.origin[0] + r.direction[0] * h.t,
 			            r.origin[1] + r.direction[1] * h.t, r.origin[2] + r.direction[2] * h.t, h.normal[0], h.normal[1], h.normal[2]);
+		}
+	}
+
+	if (!sights.empty()) { // --line-of-sight: a yes/no question each, answered without rendering
+		tracer.update_scene(shapes, triangles, materials.list);
+		std::vector<bool> invalid;
+		const std::vector<bool> occluded = tracer.occluded(sights, &invalid);
+		for (size_t k = 0; k < sights.size(); k++) {
+			const srt_segment &sg = sights[k];
+			std::printf("line of sight %g,%g,%g:%g,%g,%g:%g: %s\n", sg.from[0], sg.from[1], sg.from[2], sg.to[0], sg.to[1], sg.to[2], sg.end_gap,
+			            invalid[k] ? "invalid" : occluded[k] ? "occluded" : "visible");
 		}
 	}
 

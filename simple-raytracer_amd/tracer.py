@@ -73,6 +73,8 @@ ABI_SYMBOLS = [
     "srt_selftest_noise_meter",
     "srt_cast_rays", "srt_cast_rays_device", "srt_pick", "srt_group_cast_rays", "srt_group_pick", "srt_last_ray_query_ms",
     "srt_ray_query_sizes",
+    "srt_occluded_rays", "srt_occluded_rays_device", "srt_occluded_segments", "srt_segment_rays", "srt_group_occluded_rays",
+    "srt_group_occluded_segments", "srt_group_segment_rays", "srt_occlusion_sizes",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -820,6 +822,15 @@ def _bind(lib):
         lib.srt_ray_query_sizes.argtypes = [C.POINTER(sz)]
         sizes = (sz * 2)()
         assert lib.srt_ray_query_sizes(sizes) == 0 and (sizes[0], sizes[1]) == (R.RAY.itemsize, R.RAY_HIT.itemsize), tuple(sizes)
+    if hasattr(lib, "srt_occluded_rays"):  # (likewise)
+        for pre in ("srt_", "srt_group_"):
+            getattr(lib, pre + "occluded_rays").argtypes = [vp, vp, sz, C.c_uint32, vp, vp]
+            getattr(lib, pre + "occluded_segments").argtypes = [vp, vp, sz, vp, vp]
+            getattr(lib, pre + "segment_rays").argtypes = [vp, vp, sz, vp]
+        lib.srt_occluded_rays_device.argtypes = [vp, vp, sz, C.c_uint32, vp, vp]
+        lib.srt_occlusion_sizes.argtypes = [C.POINTER(sz)]
+        sizes = (sz * 2)()
+        assert lib.srt_occlusion_sizes(sizes) == 0 and (sizes[0], sizes[1]) == (R.SEGMENT.itemsize, 8), tuple(sizes)
     return lib
 
 
@@ -1065,6 +1076,33 @@ class _RayQuery:
         hits = np.zeros(len(xy), R.RAY_HIT)
         self._check(self._dn("pick", _ptr(rd), _ptr(xy) if len(xy) else None, len(xy), _ptr(hits) if len(xy) else None))
         return hits
+
+    # ---- occlusion queries (include/srt_abi.h "occlusion queries") ----
+    def occluded_rays(self, origins, directions=None, tmax=np.inf, unit=False, with_invalid=False):
+        """Is anything closer than tmax along each ray -> bool array of length n: True exactly where cast_rays of the same
+        ray would set HIT_HIT. Arguments as cast_rays. with_invalid=True: (occluded, invalid), the second True for the rays
+        the device refused (they are not occluded). Blocking."""
+        rays = R.as_records(origins, R.RAY) if directions is None else R.rays(origins, directions, tmax)
+        return self._masks("occluded_rays", rays, (R.RAYS_UNIT_DIRECTIONS if unit else 0,), with_invalid)
+
+    def occluded_segments(self, segments, to=None, end_gap=0.0, with_invalid=False):
+        """Is anything between `from` and the point end_gap short of `to` -> bool array. segments: a records.SEGMENT array,
+        or (n, 3) / (3,) start points with `to` and `end_gap` (records.segments). Blocking."""
+        segs = R.as_records(segments, R.SEGMENT) if to is None else R.segments(segments, to, end_gap)
+        return self._masks("occluded_segments", segs, (), with_invalid)
+
+    def segment_rays(self, segments, to=None, end_gap=0.0):
+        """The rays occluded_segments casts -> records.RAY array (unit directions: pass unit=True with them). Blocking."""
+        segs = R.as_records(segments, R.SEGMENT) if to is None else R.segments(segments, to, end_gap)
+        rays = np.zeros(len(segs), R.RAY)
+        self._check(self._dn("segment_rays", _ptr(segs) if len(segs) else None, len(segs), _ptr(rays) if len(segs) else None))
+        return rays
+
+    def _masks(self, name, recs, flags, with_invalid):
+        n = len(recs)
+        occ, inv = np.zeros((n + 63) // 64, np.uint64), np.zeros((n + 63) // 64, np.uint64)
+        self._check(self._dn(name, _ptr(recs) if n else None, n, *flags, _ptr(occ) if n else None, _ptr(inv) if n and with_invalid else None))
+        return (R.mask_bits(occ, n), R.mask_bits(inv, n)) if with_invalid else R.mask_bits(occ, n)
 
 
 class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery):
@@ -1526,6 +1564,13 @@ class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery):
         """cast_rays over device arrays (n records.RAY at rays_ptr, n records.RAY_HIT at hits_ptr, 16-byte aligned), enqueued
         on the handle's stream: synchronize() before the hits are read."""
         self._check(self.lib.srt_cast_rays_device(self._h, C.c_void_p(rays_ptr), n, R.RAYS_UNIT_DIRECTIONS if unit else 0, C.c_void_p(hits_ptr)))
+
+    def occluded_rays_device(self, rays_ptr, n, occluded_ptr, invalid_ptr=None, unit=False):
+        """occluded_rays over device arrays (n records.RAY at rays_ptr, 16-byte aligned; ceil(n / 64) 64-bit words at
+        occluded_ptr and, if given, at invalid_ptr, 8-byte aligned: ray q is bit q & 63 of word q >> 6, see records.mask_bits),
+        enqueued on the handle's stream: synchronize() before the words are read."""
+        self._check(self.lib.srt_occluded_rays_device(self._h, C.c_void_p(rays_ptr), n, R.RAYS_UNIT_DIRECTIONS if unit else 0, C.c_void_p(occluded_ptr),
+                                                      C.c_void_p(invalid_ptr) if invalid_ptr else None))
 
     def last_ray_query_ms(self):
         """Device time of the last query's launches under set_kernel_timers (0 without)."""
