@@ -1220,6 +1220,62 @@ int srt_selftest_plane_forms(srt_tracer *t, int what, const float planes[32], co
  * out_ref (must be 0). waves <= 65536. */
 int srt_selftest_diffuse_bounce(srt_tracer *t, const uint32_t *in, uint32_t waves, uint32_t *out_new, uint32_t *out_ref, uint32_t *fast, uint64_t *mismatches);
 
+/* ---- selection overlay and the ID pass (new; no counterpart in the reference) ----------------------------------------------
+ * The ID pass: per pixel of a frame the closest hit of the ray through the pixel's centre, xy = (px + 0.5, py + 0.5), as three
+ * planes of width * height words -- shape, triangle inside its model, material. Pixel (px, py) holds what srt_pick reports for
+ * that point under the same options, bit for bit and under every acceleration mode; a miss is SRT_HIT_NONE, SRT_HIT_NONE, -1; a
+ * shape without a material is reported. The pass is one kernel over the frame (csrc/selection.hip): no staging, 12 bytes written
+ * per pixel. It touches neither canvas nor counters nor any denoiser, exposure, bloom or noise state. The material plane sees
+ * srt_set_triangle_materials as of the pass.
+ *
+ * The overlay: with a selection set, every site that produces a picture's bytes -- srt_render, srt_render_async,
+ * srt_render_pipelined, srt_resolve, srt_resolve_denoised, srt_resolve_gathered, srt_group_render, srt_group_resolve_denoised --
+ * composites a tint over the selected shapes' visible pixels and an outline around them, as the last step on the bytes (behind
+ * the denoiser, exposure and bloom). Unchanged: srt_resolve_external, srt_resolve_noise_view, srt_read_canvas, the denoiser's
+ * history, and the interleaved rows of a partitioned handle (world > 1), which are no picture. Off (the default): not one launch
+ * more, every byte and every srt_last_* answer as without the feature.
+ *   m(p) = 1 when the ID pass's shape at p is in the set. R = ceil(width + 0.5) - 1 (1..8).
+ *   d2(p) = the smallest dx^2 + dy^2 over the pixels q = p + (dx, dy), |dx|, |dy| <= R, q inside the frame, m(q) = 1 (integers).
+ *   table[d2] = floor(clamp(width + 0.5 - sqrt((double)d2), 0, 1) * outline alpha + 0.5), d2 = 0 .. 2 R^2, made on the host in
+ *   double from the float width (srt_selection_alpha_table_host); the device computes no square root.
+ *   alpha(p) = fill alpha (colour: fill) where m(p) = 1; table[d2] (colour: outline) where m(p) = 0 and d2 exists; else 0.
+ *   Per colour byte: out = (byte * (255 - a) + colour * a + 127) / 255 in integers; the picture's alpha byte stays; pixels with
+ *   a == 0 are not written.
+ * The overlay's camera is that of the handle's most recent dispatch (srt_trace, srt_render*); before any dispatch there is no
+ * overlay. Its ID pass runs behind a resolve only when its key -- the scene's revision (every successful srt_update_scene), the
+ * bytes of camera_to_world, aspect_ratio and fov_scale, width and height -- differs from the planes the handle holds: under an
+ * unchanged camera and scene it costs nothing per frame. The key is compared on the host; nothing waits for the device.
+ * Everything is enqueued on the handle's stream. A group keeps ONE state, on its first device, whose member holds the whole scene. */
+int srt_selection_defaults(srt_selection_params *out); /* enabled 1, width 2, outline 255 / 255, 160, 0, fill 0 / 255, 160, 0 */
+/* Host-only: the validation srt_set_selection applies. SRT_ERR_INVALID: a width outside [1, 8] or not finite, a non-zero
+ * reserved field, enabled neither 0 nor 1. */
+int srt_selection_check_host(const srt_selection_params *p);
+/* Host-only: out = {sizeof(srt_selection_params)} as the library was built. */
+int srt_selection_sizes(size_t out[1]);
+/* Host-only: table[0 .. 2 R^2] as defined above into table (cap entries, >= 2 R^2 + 1; SRT_SELECTION_TABLE_MAX always fits),
+ * *radius = R (may be NULL). SRT_ERR_INVALID as srt_selection_check_host, or cap too small. */
+int srt_selection_alpha_table_host(const srt_selection_params *p, uint8_t *table, size_t cap, int *radius);
+/* shapes: n indices into the array srt_update_scene was given; kept across scene updates, stored on the device as a bit table
+ * sized to the current scene's shape count -- an index beyond the scene never matches. p NULL, p->enabled == 0 or n == 0: off.
+ * Waits for the handle's stream. SRT_ERR_INVALID as srt_selection_check_host, or shapes NULL with n > 0. */
+int srt_set_selection(srt_tracer *t, const srt_selection_params *p, const uint32_t *shapes, size_t n);
+int srt_group_set_selection(srt_group *g, const srt_selection_params *p, const uint32_t *shapes, size_t n);
+/* The ID pass alone, for the camera and frame size of `options` (any positive size), asynchronous on the handle's stream: the
+ * AOV for callers who want no overlay. The planes it makes are the handle's: an overlay behind it reuses them when its key agrees. */
+int srt_render_ids(srt_tracer *t, const srt_render_data *options);
+/* Waits for the handle's stream. The planes of the last ID pass (srt_render_ids, or the overlay's), *w x *h words each, into the
+ * pointers that are not NULL, of cap_pixels words each. All three NULL: the size alone. SRT_ERR_STATE: no ID pass yet;
+ * SRT_ERR_INVALID: cap_pixels too small. */
+int srt_read_id_pass(srt_tracer *t, uint32_t *shape, uint32_t *triangle, int32_t *material, size_t cap_pixels, int *w, int *h);
+int srt_group_read_id_pass(srt_group *g, uint32_t *shape, uint32_t *triangle, int32_t *material, size_t cap_pixels, int *w, int *h);
+/* Waits for the handle's stream. alpha(p) of the last overlaid frame, one byte per pixel of the frame. SRT_ERR_STATE: no overlaid
+ * frame yet. */
+int srt_read_selection_alpha(srt_tracer *t, uint8_t *alpha, size_t cap_pixels);
+/* For tests: *applied = 1 when the last picture-producing resolve on the handle (the group: on its first device) ran the overlay,
+ * *id_pass_ran = 1 when it had to make the ID planes first. Either may be NULL. */
+int srt_last_resolve_selected(const srt_tracer *t, int *applied, int *id_pass_ran);
+int srt_group_last_resolve_selected(const srt_group *g, int *applied, int *id_pass_ran);
+
 /* Library / build identification, e.g. "srt-hip gfx950 parity fp-contract=off". */
 const char *srt_version(void);
 

@@ -249,6 +249,19 @@ typedef struct srt_segment {
 	float reserved; /* must be 0 */
 } srt_segment;
 
+/* Selection overlay (srt_set_selection in srt_abi.h, where the arithmetic is written down; new, no counterpart in the
+ * reference): the selected shapes' visible pixels are tinted and outlined over the resolved bytes. Colours are 8-bit A, R, G, B,
+ * the order of the picture's bytes. */
+#define SRT_SELECTION_MAX_WIDTH 8
+#define SRT_SELECTION_TABLE_MAX 129 /* entries of the alpha table at the largest radius: d2 = 0 .. 2 * 8 * 8 */
+typedef struct srt_selection_params {
+	int32_t enabled;         /* 0: off (the library launches what it launches without the feature); 1: on; anything else is refused */
+	float outline_width;     /* finite, 1 <= width <= SRT_SELECTION_MAX_WIDTH: pixels (default 2) */
+	uint8_t outline_argb[4]; /* A: the outline's opacity; R, G, B: its colour (default 255, 255, 160, 0) */
+	uint8_t fill_argb[4];    /* A: the tint's strength over the selected pixels, 0: no fill; R, G, B: its colour (default 0, 255, 160, 0) */
+	int32_t reserved[4];     /* must be 0 */
+} srt_selection_params;
+
 #ifdef __cplusplus
 }
 #endif
@@ -326,5 +339,8 @@ SRT_STATIC_ASSERT(offsetof(srt_ray_hit, normal) == 16, "RayHit.normal@16");
 SRT_STATIC_ASSERT(sizeof(srt_segment) == 32, "Segment 32 B");
 SRT_STATIC_ASSERT(offsetof(srt_segment, end_gap) == 12, "Segment.end_gap@12");
 SRT_STATIC_ASSERT(offsetof(srt_segment, to) == 16, "Segment.to@16");
+SRT_STATIC_ASSERT(sizeof(srt_selection_params) == 32, "SelectionParams 32 B");
+SRT_STATIC_ASSERT(offsetof(srt_selection_params, outline_argb) == 8, "SelectionParams.outline_argb@8");
+SRT_STATIC_ASSERT(offsetof(srt_selection_params, reserved) == 16, "SelectionParams.reserved@16");
 
 #endif /* SRT_TYPES_H */

@@ -820,6 +820,7 @@ int srt_resolve_denoised(srt_tracer *t, uint32_t ticks_stopped) {
 	int rc = srt_denoise_filter(t, ticks_stopped, t->argb.ptr);
 	if (rc) return rc;
 	if ((rc = srt_exposure_apply_frame(t, ticks_stopped, t->argb.ptr))) return rc; // exposure.hip: nothing while the feature is off
+	if ((rc = srt_selection_apply_frame(t, t->argb.ptr))) return rc;               // selection.hip: likewise
 	SRT_HIP(t, hipEventRecord(t->ev_r1, t->stream));
 	t->have_resolve_ev = true;
 	return SRT_OK;

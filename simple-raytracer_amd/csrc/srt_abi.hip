@@ -220,6 +220,7 @@ void srt_destroy(srt_tracer *t) {
 	t->ex_own.record.release();
 	t->bl_own.pyramid.release();
 	t->nz_own.release();
+	t->sel_own.release();
 	t->rq_stage.release();
 	t->rq_span.release();
 	srt_texture_release(t);
@@ -373,6 +374,7 @@ static int upload_scene_end(srt_tracer *t, const ScenePrep &sp, size_t n_shapes,
 	t->num_runs = (int)sp.groups.size();
 	t->num_materials = n_materials;
 	t->scene_set = true;
+	t->scene_rev++; // selection.hip: ID planes of the previous scene are stale
 	return srt_texture_sync(t); // albedo textures: bindings and UVs are checked against the new scene
 }
 
@@ -774,6 +776,7 @@ int srt_trace_fused(srt_tracer *t, const srt_render_data *options, uint8_t *fuse
 	if (t->sky_w <= 0) return fail(t, SRT_ERR_STATE, "srt_trace: no skybox set (srt_set_skybox)");
 	SRT_HIP(t, hipSetDevice(t->device));
 	if (const int trc = srt_texture_sync(t)) return trc;
+	t->last_rd = *options, t->have_last_rd = true; // selection.hip: the overlay's camera
 	Dispatch d{};
 	d.textured = t->tex_active && !options->show_normals; // (show_normals ignores textures: the untextured kernels)
 	t->last_trace_textured = d.textured;
@@ -821,6 +824,8 @@ static int resolve_impl(srt_tracer *t, const float *canvas, uint32_t num_pixels,
 	if (const int rc = launch_resolve(t, canvas, num_pixels, ticks_stopped, argb)) return rc;
 	if (expose)
 		if (const int rc = srt_exposure_apply(t, canvas, (float)ticks_stopped, (uint32_t)t->width, (uint32_t)t->owned_rows, t->world == 1, argb)) return rc;
+	if (expose)
+		if (const int rc = srt_selection_apply(t, (uint32_t)t->width, (uint32_t)t->owned_rows, t->world == 1, argb)) return rc; // selection.hip: likewise
 	SRT_HIP(t, hipEventRecord(t->ev_r1, t->stream));
 	t->have_resolve_ev = true;
 	return SRT_OK;
@@ -861,6 +866,7 @@ int srt_render_async(srt_tracer *t, const srt_render_data *options, uint32_t tic
 	if (rc) return rc;
 	t->have_resolve_ev = false;
 	if (const int erc = srt_exposure_apply_frame(t, ticks_stopped, t->argb.ptr)) return erc; // exposure.hip: nothing while the feature is off
+	if (const int src = srt_selection_apply_frame(t, t->argb.ptr)) return src;               // selection.hip: likewise
 	SRT_HIP(t, hipMemcpyAsync(argb_out, t->argb.ptr, owned_pixels(t) * 4, hipMemcpyDeviceToHost, t->stream));
 	if (const int nrc = srt_noise_after_resolve(t)) return nrc; // noise_meter.hip: nothing while the feature is off
 	return SRT_OK; // argb_out is valid after srt_synchronize()

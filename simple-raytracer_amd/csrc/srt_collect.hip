@@ -278,7 +278,8 @@ int srt_resolve_gathered(srt_tracer *t, uint32_t ticks_stopped) {
 	SRT_HIP(t, c->full_argb.reserve(n * 4));
 	if (const int rc = srt_resolve_external(t, c->full.ptr, (uint32_t)n, ticks_stopped, c->full_argb.ptr)) return rc;
 	// exposure.hip, bloom.hip: nothing while the features are off; the gathered frame is a picture
-	return srt_exposure_apply(t, c->full.ptr, (float)ticks_stopped, (uint32_t)t->width, (uint32_t)t->height, true, c->full_argb.ptr);
+	if (const int rc = srt_exposure_apply(t, c->full.ptr, (float)ticks_stopped, (uint32_t)t->width, (uint32_t)t->height, true, c->full_argb.ptr)) return rc;
+	return srt_selection_apply(t, (uint32_t)t->width, (uint32_t)t->height, true, c->full_argb.ptr); // selection.hip: likewise, the last step on the bytes
 }
 
 int srt_gathered_buffers(srt_tracer *t, void **canvas, void **argb) {
@@ -369,6 +370,7 @@ srt_tracer *resolver_of(srt_group *g) {
 	g->resolver->ex = root->ex; // one exposure state per group, the first member's (srt_group_set_exposure)
 	g->resolver->bl = root->bl; // ... and one bloom state (srt_group_set_bloom)
 	g->resolver->nz = root->nz; // ... and one noise meter (srt_group_set_noise_meter)
+	g->resolver->sel = root->sel; // ... and one selection, which names the root's scene (srt_group_set_selection)
 	return g->resolver;
 }
 
@@ -879,6 +881,24 @@ int srt_group_last_resolve_bloomed(const srt_group *g, int *bloomed) {
 	return srt_last_resolve_bloomed(g->t[0], bloomed);
 }
 
+// ---- the selection overlay on a group: the first member's state and scene; the group's resolves on the first device go through it ----
+int srt_group_set_selection(srt_group *g, const srt_selection_params *p, const uint32_t *shapes, size_t n) {
+	if (!g || g->t.empty()) return SRT_ERR_INVALID;
+	const int rc = srt_set_selection(g->t[0], p, shapes, n);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+int srt_group_read_id_pass(srt_group *g, uint32_t *shape, uint32_t *triangle, int32_t *material, size_t cap_pixels, int *w, int *h) {
+	if (!g || g->t.empty()) return SRT_ERR_INVALID;
+	const int rc = srt_read_id_pass(g->t[0], shape, triangle, material, cap_pixels, w, h);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+int srt_group_last_resolve_selected(const srt_group *g, int *applied, int *id_pass_ran) {
+	if (!g || g->t.empty()) return SRT_ERR_INVALID;
+	return srt_last_resolve_selected(g->t[0], applied, id_pass_ran);
+}
+
 // ---- noise metering on a group: the single handle's calls on the group's full-frame handle, whose canvas and moments are the
 // gathered planes on the first device; the state is the first member's, shared by pointer as the exposure state is ----
 namespace {
@@ -1019,6 +1039,7 @@ int srt_render_pipelined(srt_tracer *t, const srt_render_data *options, uint32_t
 	int rc = srt_trace_fused(t, options, c->dev_argb[slot], ticks_stopped); // the last reduction resolves into this frame's own image
 	if (rc != SRT_OK) return rc;
 	if ((rc = srt_exposure_apply_frame(t, ticks_stopped, c->dev_argb[slot])) != SRT_OK) return rc; // exposure.hip: nothing while the feature is off
+	if ((rc = srt_selection_apply_frame(t, c->dev_argb[slot])) != SRT_OK) return rc;               // selection.hip: likewise
 	SRT_HIP(t, hipEventRecord(c->resolved[slot], t->stream));
 	if ((rc = srt_noise_after_resolve(t)) != SRT_OK) return rc; // noise_meter.hip: nothing while the feature is off; the frame's copy does not wait for it
 	SRT_HIP(t, hipStreamWaitEvent(c->copy_stream, c->resolved[slot], 0));

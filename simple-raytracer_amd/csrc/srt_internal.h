@@ -171,6 +171,41 @@ struct NoiseState {
 	}
 };
 
+// Selection overlay and ID pass (selection.hip; srt_set_selection, srt_render_ids): the switch, its parameters and the set as
+// given; the set as a bit table sized to the scene it was made for and the outline's alpha table, both uploaded when they
+// change (their host copies stay put between two srt_set_selection, which wait for the stream); the ID planes (shape,
+// triangle, material: three planes of ids_w x ids_h words) with the key they were made under; the alpha plane of the last
+// overlaid frame
+struct SelectionKey {
+	uint64_t scene_rev;
+	const void *scene, *tri_materials; // the handle whose scene was walked, its per-triangle material table
+	float camera_to_world[16], aspect_ratio, fov_scale;
+	int32_t width, height;
+};
+struct SelectionState {
+	bool on = false;
+	bool last_applied = false, last_id_ran = false; // srt_last_resolve_selected
+	srt_selection_params p{};
+	std::vector<uint32_t> shapes;
+	srt_tracer *scene = nullptr; // the handle srt_set_selection was called on: its scene and its last dispatch's camera
+	std::vector<uint32_t> bits_host;
+	DevBuf<uint32_t> bits;
+	uint32_t bits_shapes = 0;    // shapes the table covers
+	uint64_t bits_rev = 0;       // the scene revision it was made for
+	bool bits_dirty = true;
+	uint8_t table_host[SRT_SELECTION_TABLE_MAX + 3] = {};
+	DevBuf<uint8_t> table;
+	int radius = 0;
+	bool table_dirty = true;
+	DevBuf<uint32_t> ids;
+	int ids_w = 0, ids_h = 0;
+	bool ids_valid = false;
+	SelectionKey ids_key{};
+	DevBuf<uint8_t> alpha;
+	int alpha_w = 0, alpha_h = 0;
+	void release() { bits.release(), table.release(), ids.release(), alpha.release(); }
+};
+
 struct SrtCollect; // srt_collect.hip: RCCL communicator, gathered canvases, frame pipeline
 
 struct srt_tracer {
@@ -309,6 +344,11 @@ struct srt_tracer {
 	NoiseState nz_own;                // noise_meter.hip ...
 	NoiseState *nz = &nz_own;         // ... shared the same way
 	uint32_t last_trace_plane_form = 0; // srt_last_trace_plane_form
+	SelectionState sel_own;           // selection.hip ...
+	SelectionState *sel = &sel_own;   // ... shared the same way
+	uint64_t scene_rev = 0;           // bumped by every successful srt_update_scene (the ID planes' key)
+	srt_render_data last_rd{};        // the most recent dispatch's options (the overlay's camera) ...
+	bool have_last_rd = false;        // ... once there was one
 	// ray queries (ray_query.hip; srt_cast_rays, srt_pick): the host forms' one staging allocation -- n rays, n hits, n picked
 	// points (32 + 32 + 8 bytes each) of the largest call so far -- and the timers' span around the last query's launches;
 	// occlusion queries (occlusion.hip) use both: n rays, n segments and two bit masks in the same allocation
@@ -420,6 +460,15 @@ int srt_noise_after_resolve(srt_tracer *t);
 /* ... and the metering itself: zero the record, the kernel over the canvas and the moments (view_argb not NULL: the heat map
  * into it as well), the record's copy into the next pinned slot behind its event. The caller has checked the state. */
 int srt_noise_meter_enqueue(srt_tracer *t, uint8_t *view_argb);
+/* selection.hip, the last step on a site's bytes (behind srt_exposure_apply): with a selection set, `picture` and a dispatch
+ * behind the handle whose scene the selection names, the ID pass when the planes' key differs, then the outline kernel over the
+ * w x h words of `argb`, on the handle's stream; else nothing. Sets last_applied and last_id_ran. */
+int srt_selection_apply(srt_tracer *t, uint32_t w, uint32_t h, bool picture, uint8_t *argb);
+/* ... for the render calls, whose frame is the handle's rows or, with its denoiser on, the filter's full image */
+static inline int srt_selection_apply_frame(srt_tracer *t, uint8_t *argb) {
+	if (t->dn.on && t->dn_filtered) return srt_selection_apply(t, (uint32_t)t->width, (uint32_t)t->height, true, argb);
+	return srt_selection_apply(t, (uint32_t)t->width, (uint32_t)t->owned_rows, t->world == 1, argb);
+}
 /* bloom.hip: whether a site's resolve of num_pixels is bloomed (the feature on, a picture, not empty); sets last_bloomed */
 bool srt_bloom_begin(srt_tracer *t, bool picture, size_t num_pixels);
 /* ... and its launches on the handle's stream: the pyramid of (source / divisor) * *exposure (NULL: 1.0f) and the composite

@@ -328,6 +328,47 @@ class Tracer {
 		check(group ? srt_group_last_resolve_bloomed(group, &bloomed) : srt_last_resolve_bloomed(handle, &bloomed));
 		return bloomed != 0;
 	}
+	/// Selection overlay (srt_set_selection): the visible pixels of `shapes` (indices into update_scene's array) are tinted and
+	/// outlined in every picture render() / render_pipelined() deliver, as the last step on the bytes. width: pixels, 1..8, a
+	/// non-positive one keeps the library's default (2); outline_rrggbbaa / fill_rrggbbaa: 0xRRGGBBAA, fill alpha 0 = no tint. No
+	/// shapes: off. The ID pass behind it runs only when the camera or the scene has changed. One device or a group.
+	void set_selection(const std::vector<uint32_t> &shapes, float width = 0.0f, uint32_t outline_rrggbbaa = 0xffa000ffu, uint32_t fill_rrggbbaa = 0xffa00000u) {
+		srt_selection_params p;
+		check(srt_selection_defaults(&p));
+		if (width > 0.0f) p.outline_width = width;
+		auto argb = [](uint32_t c, uint8_t out[4]) { out[0] = uint8_t(c), out[1] = uint8_t(c >> 24), out[2] = uint8_t(c >> 16), out[3] = uint8_t(c >> 8); };
+		argb(outline_rrggbbaa, p.outline_argb), argb(fill_rrggbbaa, p.fill_argb);
+		check(group ? srt_group_set_selection(group, &p, shapes.data(), shapes.size()) : srt_set_selection(handle, &p, shapes.data(), shapes.size()));
+	}
+	/// ... off: the sites resolve as they do without it
+	void clear_selection() { check(group ? srt_group_set_selection(group, nullptr, nullptr, 0) : srt_set_selection(handle, nullptr, nullptr, 0)); }
+	/// The ID pass alone for the camera of `options` (srt_render_ids): shape, triangle and material per pixel, for read_id_pass.
+	/// Asynchronous; single-device tracers only.
+	void render_ids() {
+		if (group) throw std::runtime_error("Tracer::render_ids: single-device tracers only");
+		check(srt_render_ids(handle, reinterpret_cast<const srt_render_data *>(&options)));
+	}
+	/// The planes of the last ID pass (render_ids, or the overlay's) into the vectors that are not nullptr (resized). Waits for
+	/// the device.
+	void read_id_pass(std::vector<uint32_t> *shape, std::vector<uint32_t> *triangle, std::vector<int32_t> *material, int *w = nullptr, int *h = nullptr) {
+		int pw = 0, ph = 0;
+		check(group ? srt_group_read_id_pass(group, nullptr, nullptr, nullptr, 0, &pw, &ph) : srt_read_id_pass(handle, nullptr, nullptr, nullptr, 0, &pw, &ph));
+		const size_t n = (size_t)pw * (size_t)ph;
+		if (shape) shape->resize(n);
+		if (triangle) triangle->resize(n);
+		if (material) material->resize(n);
+		uint32_t *s = shape ? shape->data() : nullptr, *t = triangle ? triangle->data() : nullptr;
+		int32_t *m = material ? material->data() : nullptr;
+		check(group ? srt_group_read_id_pass(group, s, t, m, n, &pw, &ph) : srt_read_id_pass(handle, s, t, m, n, &pw, &ph));
+		if (w) *w = pw;
+		if (h) *h = ph;
+	}
+	/// Whether the last frame's bytes went through the overlay
+	bool last_resolve_selected() {
+		int applied = 0;
+		check(group ? srt_group_last_resolve_selected(group, &applied, nullptr) : srt_last_resolve_selected(handle, &applied, nullptr));
+		return applied != 0;
+	}
 	/// Noise metering (srt_set_noise_meter): a per-pixel relative standard error from the denoiser's moments, its histogram and
 	/// the stopping rule "permille of the pixels below threshold". A non-positive threshold, permille or check_every keeps the
 	/// library's default (0.05, 950, 4). Needs set_denoise first (iterations 0 is enough); one device or a group. With it on,

@@ -75,12 +75,16 @@ HIT_HIT, HIT_FRONT, HIT_INVALID_RAY = 1, 2, 4
 # srt_segment (occlusion queries: Tracer.occluded_segments, Tracer.segment_rays), 32 bytes; "from" is the start point
 SEGMENT = np.dtype({"names": ["from", "end_gap", "to", "reserved"], "formats": [F3, np.float32, F3, np.float32],
                     "offsets": [0, 12, 16, 28], "itemsize": 32})
+# srt_selection_params (selection overlay: Tracer.set_selection), 32 bytes; the colours are bytes A, R, G, B
+SELECTION_PARAMS = np.dtype({"names": ["enabled", "outline_width", "outline_argb", "fill_argb", "reserved"],
+                             "formats": [np.int32, np.float32, (np.uint8, 4), (np.uint8, 4), (np.int32, 4)], "offsets": [0, 4, 8, 12, 16], "itemsize": 32})
+SELECTION_MAX_WIDTH, SELECTION_TABLE_MAX = 8, 129
 
 SHAPE_SPHERE, SHAPE_PLANE, SHAPE_MODEL = 0, 1, 2
 
 assert MATERIAL.itemsize == 64 and TRIANGLE.itemsize == 96 and SHAPE.itemsize == 128
 assert RENDER_DATA.itemsize == 112 and SCENE_DATA.itemsize == 96
-assert RAY.itemsize == 32 and RAY_HIT.itemsize == 32 and SEGMENT.itemsize == 32
+assert RAY.itemsize == 32 and RAY_HIT.itemsize == 32 and SEGMENT.itemsize == 32 and SELECTION_PARAMS.itemsize == 32
 
 
 def rays(origins, directions, tmax=np.inf):

@@ -35,6 +35,9 @@
 // --line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP] (may be given several times): after the scene is loaded, is the point GAP (default 0)
 //                short of (X1, Y1, Z1) visible from (X0, Y0, Z0) (Tracer::occluded); one line per question: `visible`, `occluded`
 //                or `invalid`. Then the frames render as before.
+// --select I[,J...][:WIDTH[:RRGGBBAA]]: shapes I, J, ... are outlined in every frame (Tracer::set_selection): WIDTH pixels (1..8,
+//                default: the library's 2) in the colour RRGGBBAA (hex; default ffa000ff), over the finished bytes; whether the
+//                overlay ran is printed at the end
 // --move DX: the camera moves by DX along x every frame and every frame clears the canvas, as the front-end does while moving
 // --move-shape I DX: with --temporal, shape I (a sphere, a plane or a model instance) moves by DX along x every frame and every
 //                frame clears the canvas, as the front-end does while a gizmo is dragged; turns object motion on
@@ -149,6 +152,9 @@ int main(int argc, char **argv) {
 	bool exposure = false, exposure_auto = false;
 	float exposure_ev = 0.0f;
 	bool bloom = false;
+	std::vector<uint32_t> selected; // --select
+	float select_width = 0.0f;      // (0: the library's default)
+	uint32_t select_colour = 0xffa000ffu;
 	float bloom_threshold = -1.0f, bloom_intensity = -1.0f; // (negative: the library's default)
 	int bloom_levels = 0;
 	bool until_noise = false;
@@ -260,6 +266,34 @@ int main(int argc, char **argv) {
 			}
 		}
 		else if (a == "--noise-view") noise_view = next();
+		else if (a == "--select") { // I[,J...][:WIDTH[:RRGGBBAA]]
+			const std::string v = next();
+			const char *c = v.c_str();
+			char *end = nullptr;
+			bool ok = true;
+			for (;;) {
+				const unsigned long i = std::strtoul(c, &end, 10);
+				ok = ok && end != c && i <= 0xfffffffeul;
+				if (!ok) break;
+				selected.push_back((uint32_t)i);
+				if (*end != ',') break;
+				c = end + 1;
+			}
+			if (ok && *end == ':') {
+				c = end + 1;
+				select_width = std::strtof(c, &end);
+				ok = end != c && select_width >= 1.0f && select_width <= 8.0f;
+				if (ok && *end == ':') {
+					c = end + 1;
+					select_colour = (uint32_t)std::strtoul(c, &end, 16);
+					ok = end - c == 8;
+				}
+			}
+			if (!ok || *end) {
+				std::cerr << "--select takes I[,J...], I[,J...]:WIDTH or I[,J...]:WIDTH:RRGGBBAA, 1 <= WIDTH <= 8\n";
+				return 2;
+			}
+		}
 		else if (a == "--pick") { // X,Y
 			float x = 0.f, y = 0.f;
 			if (std::sscanf(next(), "%f,%f", &x, &y) != 2) {
@@ -281,7 +315,7 @@ int main(int argc, char **argv) {
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--pick X,Y]... [--line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP]]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
+			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--select I[,J...][:WIDTH[:RRGGBBAA]]] [--pick X,Y]... [--line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP]]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
@@ -431,6 +465,7 @@ int main(int argc, char **argv) {
 	if (bvh_build_device) tracer.set_acceleration_build(SRT_BUILD_DEVICE, bvh_build_min); // (models of at least MIN triangles; without --bvh: no effect)
 	if (exposure) tracer.set_exposure(exposure_auto, exposure_ev);
 	if (bloom) tracer.set_bloom(bloom_threshold, bloom_intensity, bloom_levels);
+	if (!selected.empty()) tracer.set_selection(selected, select_width, select_colour);
 	if (denoise >= 0) tracer.set_denoise(denoise);
 	if (demodulate) tracer.set_denoise_demodulation();
 	if (spatial_variance > 0) tracer.set_denoise_spatial_variance((uint32_t)spatial_variance);
@@ -613,6 +648,7 @@ int main(int argc, char **argv) {
 		if (ran) tracer.read_bloom(0, nullptr, &w0, &h0);
 		std::printf("bloom: level 0 is %dx%d%s\n", w0, h0, ran ? "" : " -- NOT applied");
 	}
+	if (!selected.empty()) std::printf("selection: %zu shape(s)%s\n", selected.size(), tracer.last_resolve_selected() ? "" : " -- NOT applied");
 
 	if (until_noise)
 		std::printf("until-noise: %s after %u dispatches; deciding check at T = %u, P = %u: level %.6g (bin %d), %u of %u pixels below, %u left out\n",

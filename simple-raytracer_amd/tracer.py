@@ -75,6 +75,9 @@ ABI_SYMBOLS = [
     "srt_ray_query_sizes",
     "srt_occluded_rays", "srt_occluded_rays_device", "srt_occluded_segments", "srt_segment_rays", "srt_group_occluded_rays",
     "srt_group_occluded_segments", "srt_group_segment_rays", "srt_occlusion_sizes",
+    "srt_selection_defaults", "srt_selection_check_host", "srt_selection_sizes", "srt_selection_alpha_table_host", "srt_set_selection",
+    "srt_group_set_selection", "srt_render_ids", "srt_read_id_pass", "srt_group_read_id_pass", "srt_read_selection_alpha",
+    "srt_last_resolve_selected", "srt_group_last_resolve_selected",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -489,6 +492,37 @@ def bloom_check_host(**kw):
     return load_library().srt_bloom_check_host(C.byref(_bloom_params(kw, "bloom_check_host"))) == 0
 
 
+def _selection_params(kw, who):
+    """srt_selection_defaults() overridden by kw -> a records.SELECTION_PARAMS record. width: outline_width; outline / fill: (A, R, G, B)."""
+    d = np.zeros((), R.SELECTION_PARAMS)
+    if load_library().srt_selection_defaults(_ptr(d)):
+        raise SrtError("srt_selection_defaults failed")
+    for k, v in kw.items():
+        k = {"width": "outline_width", "outline": "outline_argb", "fill": "fill_argb"}.get(k, k)
+        if k not in R.SELECTION_PARAMS.names:
+            raise TypeError(f"{who}: unknown parameter {k}")
+        d[k] = v
+    return d
+
+
+def selection_defaults():
+    """srt_selection_defaults (host only, no GPU needed) as a records.SELECTION_PARAMS record."""
+    return _selection_params({}, "selection_defaults")
+
+
+def selection_check_host(**kw):
+    """srt_selection_check_host of the defaults overridden by kw (host only): True when srt_set_selection would accept them."""
+    return load_library().srt_selection_check_host(_ptr(_selection_params(kw, "selection_check_host"))) == 0
+
+
+def selection_alpha_table_host(**kw):
+    """srt_selection_alpha_table_host of the defaults overridden by kw (host only) -> (table of 2 R^2 + 1 uint8, R)."""
+    table, radius = np.zeros(R.SELECTION_TABLE_MAX, np.uint8), C.c_int(0)
+    if load_library().srt_selection_alpha_table_host(_ptr(_selection_params(kw, "selection_alpha_table_host")), _ptr(table), table.size, C.byref(radius)):
+        raise SrtError("srt_selection_alpha_table_host refused the parameters")
+    return table[:2 * radius.value ** 2 + 1].copy(), radius.value
+
+
 class NoiseParams(C.Structure):
     """include/srt_types.h srt_noise_params"""
     _fields_ = [("enable", C.c_int32), ("threshold", C.c_float), ("luminance_floor", C.c_float), ("permille", C.c_int32),
@@ -831,6 +865,20 @@ def _bind(lib):
         lib.srt_occlusion_sizes.argtypes = [C.POINTER(sz)]
         sizes = (sz * 2)()
         assert lib.srt_occlusion_sizes(sizes) == 0 and (sizes[0], sizes[1]) == (R.SEGMENT.itemsize, 8), tuple(sizes)
+    if hasattr(lib, "srt_set_selection"):  # (likewise)
+        ip = C.POINTER(C.c_int)
+        lib.srt_selection_defaults.argtypes = [vp]
+        lib.srt_selection_check_host.argtypes = [vp]
+        lib.srt_selection_alpha_table_host.argtypes = [vp, vp, sz, ip]
+        lib.srt_selection_sizes.argtypes = [C.POINTER(sz)]
+        for pre in ("srt_", "srt_group_"):
+            getattr(lib, pre + "set_selection").argtypes = [vp, vp, vp, sz]
+            getattr(lib, pre + "read_id_pass").argtypes = [vp, vp, vp, vp, sz, ip, ip]
+            getattr(lib, pre + "last_resolve_selected").argtypes = [vp, ip, ip]
+        lib.srt_render_ids.argtypes = [vp, vp]
+        lib.srt_read_selection_alpha.argtypes = [vp, vp, sz]
+        sizes = (sz * 1)()
+        assert lib.srt_selection_sizes(sizes) == 0 and sizes[0] == R.SELECTION_PARAMS.itemsize, tuple(sizes)
     return lib
 
 
@@ -1105,7 +1153,35 @@ class _RayQuery:
         return (R.mask_bits(occ, n), R.mask_bits(inv, n)) if with_invalid else R.mask_bits(occ, n)
 
 
-class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery):
+class _Selection:
+    """Selection overlay and ID pass (include/srt_abi.h "selection overlay and the ID pass"), shared by Tracer and TracerGroup
+    (the group: its first member's state and scene)."""
+
+    def set_selection(self, shapes=(), **kw):
+        """Outline and tint the shapes (indices into update_scene's array) in every picture the handle resolves, with
+        srt_selection_defaults() overridden by kw (width, outline=(A, R, G, B), fill=(A, R, G, B)); no shapes, None or
+        enabled=0: off."""
+        idx = np.ascontiguousarray(np.atleast_1d(np.asarray([] if shapes is None else shapes, np.int64)).astype(np.uint32))
+        self._check(self._dn("set_selection", _ptr(_selection_params(kw, "set_selection")), _ptr(idx) if len(idx) else None, len(idx)))
+
+    def read_id_pass(self):
+        """The planes of the last ID pass (render_ids, or the overlay's) -> dict shape, triangle (h, w) uint32 and material
+        (h, w) int32. Waits for the stream."""
+        w, h = C.c_int(0), C.c_int(0)
+        self._check(self._dn("read_id_pass", None, None, None, 0, C.byref(w), C.byref(h)))
+        out = dict(shape=np.zeros((h.value, w.value), np.uint32), triangle=np.zeros((h.value, w.value), np.uint32),
+                   material=np.zeros((h.value, w.value), np.int32))
+        self._check(self._dn("read_id_pass", _ptr(out["shape"]), _ptr(out["triangle"]), _ptr(out["material"]), w.value * h.value, C.byref(w), C.byref(h)))
+        return out
+
+    def last_resolve_selected(self):
+        """(applied, id_pass_ran) of the last picture-producing resolve."""
+        a, r = C.c_int(0), C.c_int(0)
+        self._check(self._dn("last_resolve_selected", C.byref(a), C.byref(r)))
+        return bool(a.value), bool(r.value)
+
+
+class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection):
     """Mirror of the reference's `class Tracer`. Field and method names are the
     reference's; records are numpy scalars of records.RENDER_DATA / SCENE_DATA."""
 
@@ -1572,6 +1648,17 @@ class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery):
         self._check(self.lib.srt_occluded_rays_device(self._h, C.c_void_p(rays_ptr), n, R.RAYS_UNIT_DIRECTIONS if unit else 0, C.c_void_p(occluded_ptr),
                                                       C.c_void_p(invalid_ptr) if invalid_ptr else None))
 
+    def render_ids(self, options=None):
+        """The ID pass alone for the camera and frame size of options (default: self.options), asynchronous; then read_id_pass()."""
+        rd = R.as_records(self.options if options is None else options, R.RENDER_DATA)
+        self._check(self.lib.srt_render_ids(self._h, _ptr(rd)))
+
+    def read_selection_alpha(self):
+        """alpha(p) of the last overlaid frame -> (h, w) uint8. Waits for the stream."""
+        out = np.zeros((self.owned_rows, self.width), np.uint8)
+        self._check(self.lib.srt_read_selection_alpha(self._h, _ptr(out), out.size))
+        return out
+
     def last_ray_query_ms(self):
         """Device time of the last query's launches under set_kernel_timers (0 without)."""
         ms = C.c_float(0)
@@ -1583,7 +1670,7 @@ class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery):
         self.owned_rows = self.lib.srt_partition_owned_rows(self.height, rank, world, rows_per_block)
 
 
-class TracerGroup(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery):
+class TracerGroup(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection):
     """One process driving several GPUs (srt_group_*): the reference's Tracer interface over a row partition,
     collected with one ncclGather per frame."""
 
