@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."
 # Stage 1, no library and nothing preloaded: the HIP-free host units (csrc/bvh_host.cpp, csrc/scene_prep.cpp) behind
 # tests/csrc/host_units_check.cpp, built by g++ once with AddressSanitizer + UndefinedBehaviorSanitizer and once with
 # ThreadSanitizer (the builder's std::async subtrees and quantiser threads), the runtime linked statically where the
-# toolchain has it; the `bvh`, `scene` and `batches` (csrc/trace_plan.h's batch slices) modes of each must run without a report.
+# toolchain has it; the `bvh`, `scene`, `batches` (csrc/trace_plan.h's batch slices) and `stage` (csrc/query_stage.h) modes of each must run without a report.
 CSRC=simple-raytracer_amd/csrc
 UNITS=$(mktemp -d)
 trap 'rm -rf "$UNITS"' EXIT
@@ -17,7 +17,7 @@ host_units() { # name, static-runtime flags, sanitizer flags...
 	shift 2
 	local cmd=(g++ -std=c++17 -O1 -g -ffp-contract=off -pthread "$@" "-I$CSRC" tests/csrc/host_units_check.cpp "$CSRC/bvh_host.cpp" "$CSRC/scene_prep.cpp" -o "$UNITS/$name")
 	"${cmd[@]}" $static 2>/dev/null || "${cmd[@]}"
-	for mode in bvh scene batches; do
+	for mode in bvh scene batches stage; do
 		if ! "$UNITS/$name" $mode </dev/null >"$UNITS/$name.$mode.log" 2>&1 || grep -q "runtime error\|Sanitizer" "$UNITS/$name.$mode.log"; then
 			cat "$UNITS/$name.$mode.log"
 			echo "SANITIZER REPORTS ABOVE (host units, $name, $mode)"

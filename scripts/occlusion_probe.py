@@ -4,13 +4,14 @@
                   hierarchy) and the 99,904-triangle scene (hierarchy) -- scripts/ray_query_probe.py's rows -- in two sets:
                   `camera` (tmax = inf: most rays are occluded, the early exit applies) and `half` (tmax = half the distance of
                   the ray's closest hit: most rays are visible, nothing ends early). Per row, under the kernel timers
-                  (srt_last_ray_query_ms) and taking turns REPS times: srt_occluded_rays_device of this library, the same of the
-                  walk's other stack form (the -DSRT_ANYHIT_REFS=0 variant this script builds; the hierarchy rows only),
+                  (srt_last_ray_query_ms) and taking turns REPS times: srt_occluded_rays_device of this library,
                   srt_cast_rays_device of this library, and -- with --parent-lib PATH, a build of the parent commit --
                   srt_cast_rays_device of that library: the baseline. Medians, the baseline's own spread (min, max), and the
-                  ratio occlusion / baseline. The masks of both stack forms are compared with the cast's SRT_HIT_HIT on the way.
+                  ratio occlusion / baseline. The mask is compared with the cast's SRT_HIT_HIT on the way.
+                  (profiles/r30_occlusion.json also holds `occlusion_keys_ms`, the walk's other stack form, measured by this
+                  script when that form was still in the tree: profiles/r32_anyhit_key_stack_experiment.patch.)
 
-    python scripts/occlusion_probe.py [--parent-lib PATH] [--out FILE] [--quick] [--no-variant]
+    python scripts/occlusion_probe.py [--parent-lib PATH] [--out FILE] [--quick]
 """
 import argparse
 import ctypes as C
@@ -38,18 +39,12 @@ def main():
     ap.add_argument("--parent-lib", help="libsrt_hip.so built from the parent commit: the baseline cast")
     ap.add_argument("--out", help="write the JSON document here as well")
     ap.add_argument("--quick", action="store_true", help="960x540 only")
-    ap.add_argument("--no-variant", action="store_true", help="do not build and time the walk's other stack form")
     a = ap.parse_args()
     import torch
     import srt_pkg
     srt_pkg.load()
-    from simple_raytracer_amd import build as B, records as R, scenes as S, tracer as T
+    from simple_raytracer_amd import records as R, scenes as S, tracer as T
     libs = {"this": T.load_library()}
-    if not a.no_variant:
-        keys = B.LIBDIR / "variants" / "anyhit_keys" / "libsrt_hip.so"
-        if not keys.exists() or keys.stat().st_mtime < B.LIB.stat().st_mtime:  # (built once, from the sources of the library beside it)
-            B.build_variant("anyhit_keys", ["-DSRT_ANYHIT_REFS=0"])
-        libs["keys"] = T._bind(C.CDLL(str(keys)))
     if a.parent_lib:
         libs["parent"] = T._bind(C.CDLL(str(a.parent_lib)))
         assert not hasattr(libs["parent"], "srt_occluded_rays"), "--parent-lib is not the parent commit's library"
@@ -89,8 +84,6 @@ def main():
                     return tr[key].last_ray_query_ms()
 
                 modes = [("occlusion", occlusion, "this"), ("cast", cast, "this")]
-                if "keys" in libs and accel:
-                    modes.append(("occlusion_keys", occlusion, "keys"))
                 if "parent" in libs:
                     modes.append(("parent_cast", cast, "parent"))
                 want = (tr["this"].cast_rays(rs, unit=True)["flags"] & R.HIT_HIT) != 0
@@ -107,8 +100,6 @@ def main():
                 row["baseline"] = base
                 row["baseline_min_max_ms"] = [round(min(ms[base][1:]), 4), round(max(ms[base][1:]), 4)]
                 row["occlusion_over_baseline"] = round(med(ms["occlusion"][1:]) / med(ms[base][1:]), 3)
-                if "occlusion_keys" in ms:
-                    row["refs_over_keys"] = round(med(ms["occlusion"][1:]) / med(ms["occlusion_keys"][1:]), 3)
                 rows.append(row)
                 print(json.dumps(row), flush=True)
             for t in tr.values():

@@ -8,20 +8,13 @@
 
 #include "device_intersect.h"
 
-// The walk's stack: 1 = 4-byte block references, children entered in slot order (what the early exit allows: a
-// popped entry needs no distance test against a limit that never shrinks, so neither the distance nor the order is kept);
-// 0 = walk_bvh's own {key, first} entries, children sorted nearest first. Both were measured (profiles/r30_occlusion.json).
-#ifndef SRT_ANYHIT_REFS
-#define SRT_ANYHIT_REFS 1
-#endif
-
 namespace {
 
-#if SRT_ANYHIT_REFS
+// The walk's stack: 4-byte block references, children entered in slot order (what the early exit allows: a
+// popped entry needs no distance test against a limit that never shrinks, so neither the distance nor the order is kept).
+// walk_bvh's own {key, first} entries with the children sorted nearest first were measured against it and lost
+// (profiles/r30_occlusion.json); that form is kept as profiles/r32_anyhit_key_stack_experiment.patch.
 typedef uint32_t AnyStackEntry; // (block << 5) | tag
-#else
-typedef BvhStackEntry AnyStackEntry;
-#endif
 
 // test_triangles for occlusion: the pairs arrive through the same wave-uniform scalar loads, so the exit is the wave's -- one
 // ballot per iteration (two pairs) over the lanes that came in. Within an iteration every lane that came in runs the tests, as
@@ -68,13 +61,8 @@ __device__ __forceinline__ bool walk_bvh_any(const float4 *__restrict__ blocks, 
 	// The youngest waiting entry lives in registers, stack[0 .. sp) holds the older ones, under them a sentinel that leads to
 	// block NONE: popping it ends the walk (as walk_bvh).
 	uint32_t sp = 0u;
-#if SRT_ANYHIT_REFS
 	uint32_t top = SRT_BVH_NONE;
 	stack[0] = SRT_BVH_NONE;
-#else
-	uint32_t top_key = 0u, top_first = SRT_BVH_NONE;
-	stack[0].key = 0u, stack[0].first = SRT_BVH_NONE;
-#endif
 	while (cur != SRT_BVH_NONE) {
 		uint32_t next = SRT_BVH_NONE;
 		const uint32_t at = (cur >> 5) << 7;
@@ -113,7 +101,6 @@ __device__ __forceinline__ bool walk_bvh_any(const float4 *__restrict__ blocks, 
 				const float tf = __builtin_fminf(__builtin_fminf(__builtin_fminf(tfx, tfy), tfz), tmax);
 				return tn <= tf * 1.000001f && there;
 			};
-#if SRT_ANYHIT_REFS
 			// the first child the ray enters is next, the others wait in no particular order: one store each
 			auto child = [&](int k, bool there) {
 				float tn;
@@ -124,38 +111,11 @@ __device__ __forceinline__ bool walk_bvh_any(const float4 *__restrict__ blocks, 
 				}
 			};
 			child(0, true), child(1, true), child(2, nk > 2u), child(3, nk > 3u);
-#else
-			auto child = [&](int k, bool there) -> uint32_t {
-				float tn;
-				const bool hit = entry(k, there, tn);
-				return ((hit ? f2u(tn) : SRT_BVH_KEY_INF) & ~SRT_BVH_TAG_MASK) | ((tags >> (8 * k)) & 255u);
-			};
-			uint32_t k0 = child(0, true), k1 = child(1, true), k2 = child(2, nk > 2u), k3 = child(3, nk > 3u);
-			bvh_order2(k0, k1);
-			bvh_order2(k2, k3);
-			bvh_order2(k0, k2);
-			bvh_order2(k1, k3);
-			bvh_order2(k1, k2); // nearest first; the children that are not entered (keys >= KEY_INF) last
-			const uint32_t w1 = k1 < SRT_BVH_KEY_INF ? 1u : 0u, w2 = k2 < SRT_BVH_KEY_INF ? 1u : 0u, w3 = k3 < SRT_BVH_KEY_INF ? 1u : 0u;
-			const uint32_t n = w1 + w2 + w3;
-			if (w1) stack[sp].key = top_key, stack[sp].first = top_first;
-			if (w3) stack[sp + 1u].key = k3, stack[sp + 1u].first = first;
-			if (w2) stack[sp + n - 1u].key = k2, stack[sp + n - 1u].first = first;
-			top_key = w1 ? k1 : top_key, top_first = w1 ? first : top_first;
-			sp += n;
-			if (k0 < SRT_BVH_KEY_INF) next = ((first + (k0 & 3u)) << 5) | (k0 & SRT_BVH_TAG_MASK);
-#endif
 		}
 		if (next == SRT_BVH_NONE) { // nothing to enter from here: the youngest waiting child, or the sentinel
-#if SRT_ANYHIT_REFS
 			next = top;
 			sp = sp > 0u ? sp - 1u : 0u;
 			top = stack[sp];
-#else
-			next = top_first == SRT_BVH_NONE ? SRT_BVH_NONE : (((top_first + (top_key & 3u)) << 5) | (top_key & SRT_BVH_TAG_MASK));
-			sp = sp > 0u ? sp - 1u : 0u;
-			top_key = stack[sp].key, top_first = stack[sp].first;
-#endif
 		}
 		cur = next;
 	}

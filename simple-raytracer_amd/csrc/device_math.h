@@ -28,6 +28,9 @@ __device__ __forceinline__ f3 operator*(f3 a, f3 b) { return mk(a.x * b.x, a.y *
 __device__ __forceinline__ f3 operator*(f3 a, float s) { return mk(a.x * s, a.y * s, a.z * s); }
 __device__ __forceinline__ f3 operator/(f3 a, float s) { return mk(a.x / s, a.y / s, a.z / s); }
 __device__ __forceinline__ f3 neg(f3 a) { return mk(-a.x, -a.y, -a.z); }
+// neither an infinity nor a NaN: the exponent's bits are not all ones
+__device__ __forceinline__ bool finite_bits(float x) { return (dm_f2u(x) & 0x7f800000u) != 0x7f800000u; }
+__device__ __forceinline__ bool finite3(f3 a) { return finite_bits(a.x) && finite_bits(a.y) && finite_bits(a.z); }
 // the OpenCL built-ins dot and cross as detmath.h pins them (FMA forms: 3 and 6 instructions)
 __device__ __forceinline__ float dot3(f3 a, f3 b) { return dm_dot3(a.x, a.y, a.z, b.x, b.y, b.z); }
 __device__ __forceinline__ f3 cross3(f3 a, f3 b) {
@@ -210,6 +213,23 @@ __device__ __forceinline__ f3 mat_by_vec(const srt_float4 *m, f3 v, float w) {
 __device__ __forceinline__ f3 mat_cols_by_vec(f3 c0, f3 c1, f3 c2, f3 c3, f3 v, float w) {
 	return mk(((c0.x * v.x + c1.x * v.y) + c2.x * v.z) + c3.x * w, ((c0.y * v.x + c1.y * v.y) + c2.y * v.z) + c3.y * w,
 	          ((c0.z * v.x + c1.z * v.y) + c2.z * v.z) + c3.z * w);
+}
+
+// The camera ray through the image point (x, y), in pixels: srt_trace_kernel's CAMERA with the point in place of pixel + jitter,
+// for srt_pick_rays_kernel (ray_query.hip) and srt_id_pass_kernel (selection.hip). features_body.inc keeps its own form: it
+// hoists the camera's columns out of its sample loop. p.rd: the camera and the frame; p.f_width .. p.inv_f_height as a dispatch
+// of p.rd has them.
+__device__ __forceinline__ void camera_ray(const TraceParams &p, float2 xy, f3 &org, f3 &dir) {
+	const f3 c0 = mk(p.rd.camera_to_world[0].x, p.rd.camera_to_world[0].y, p.rd.camera_to_world[0].z);
+	const f3 c1 = mk(p.rd.camera_to_world[1].x, p.rd.camera_to_world[1].y, p.rd.camera_to_world[1].z);
+	const f3 c2 = mk(p.rd.camera_to_world[2].x, p.rd.camera_to_world[2].y, p.rd.camera_to_world[2].z);
+	const f3 cam = mk(p.rd.camera_to_world[3].x, p.rd.camera_to_world[3].y, p.rd.camera_to_world[3].z);
+	const float ndc_x = div_by_rcp(xy.x, p.f_width, p.inv_f_width);
+	const float ndc_y = div_by_rcp(xy.y, p.f_height, p.inv_f_height);
+	const float sx = ((2.f * ndc_x - 1.f) * p.rd.aspect_ratio) * p.rd.fov_scale;
+	const float sy = (1.f - 2.f * ndc_y) * p.rd.fov_scale;
+	org = cam;
+	dir = normalize3(mat_cols_by_vec(c0, c1, c2, cam, mk(sx, sy, -1.0f), 0.0f));
 }
 
 // v - 2 (v.n) n  (render.cl:139-141)

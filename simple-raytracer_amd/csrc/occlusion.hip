@@ -4,12 +4,14 @@
 // are new, every kernel the library launched before keeps its instruction stream (scripts/kernel_isa_digest.py).
 //
 //  * srt_occlusion_kernel<HAS_MODELS, USE_BVH>: the cast's launch shape (one lane per ray, one wave per workgroup, the lane's
-//    BVH stack in scratch), its ray loads and its validity test, then the same runs and blocks through the same sphere and
-//    plane tests with tmin = tmax -- a lane is occluded as soon as `best >= 0` -- and the any-hit triangle scan and walk of
-//    device_anyhit.h. What differs from the cast: lanes past n stay to the end (inactive) because the answer is a ballot; one
+//    BVH stack in scratch), its ray loads and its validity test (ray_valid.inc, one text for both), then the same runs and
+//    blocks through the same sphere and plane tests with tmin = tmax -- a lane is occluded as soon as `best >= 0` -- and the
+//    any-hit triangle scan and walk of device_anyhit.h. The block test is this kernel's own, not closest_hit.inc: a model is
+//    tested against the constant limit by the lanes that still ask. What differs from the cast: lanes past n stay to the end (inactive) because the answer is a ballot; one
 //    ballot after each run leaves the run loop when no active lane is still unoccluded; no normal, no material, no record:
 //    lane 0 stores the wave's 64 answers as one 64-bit word (and a second one for "invalid" when the caller wants it).
 //  * srt_segment_rays_kernel: the srt_ray of a segment, from -> to less end_gap, with the functions the kernels already have.
+// The host side's scaffold is query_host.h, shared with ray_query.hip: one staging allocation, one layout (query_stage.h).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -20,7 +22,7 @@
 #include "device_math.h"
 #include "device_intersect.h"
 #include "device_anyhit.h"
-#include "srt_internal.h"
+#include "query_host.h"
 
 struct OcclusionParams {
 	TraceParams tp;     /* the scene buffers, as a dispatch's (rd: unused) */
@@ -36,11 +38,6 @@ struct SegmentParams {
 	uint32_t n;
 };
 
-namespace {
-__device__ __forceinline__ bool finite_bits(float x) { return (f2u(x) & 0x7f800000u) != 0x7f800000u; }
-__device__ __forceinline__ bool finite3(f3 a) { return finite_bits(a.x) && finite_bits(a.y) && finite_bits(a.z); }
-} // namespace
-
 template <bool HAS_MODELS, bool USE_BVH>
 __global__ __launch_bounds__(64) void srt_occlusion_kernel(const OcclusionParams op) {
 	const TraceParams &p = op.tp;
@@ -54,14 +51,8 @@ __global__ __launch_bounds__(64) void srt_occlusion_kernel(const OcclusionParams
 	const f3 org = mk(r0.x, r0.y, r0.z);
 	f3 dir = mk(r1.x, r1.y, r1.z);
 	const float tmax = r0.w;
-	// ---- hostile rays: ray_query.hip's test, statement for statement ----
-	bool valid = finite3(org) && finite3(dir) && tmax == tmax;
-	if (!(op.flags & SRT_RAYS_UNIT_DIRECTIONS)) {
-		dir = normalize3(dir);
-		const float len2 = dot3(dir, dir);
-		valid = valid && len2 > 0.25f && len2 < 4.0f;
-	}
-	valid = valid && finite3(dir) && !(dir.x == 0.0f && dir.y == 0.0f && dir.z == 0.0f);
+	const uint32_t flags = op.flags;
+#include "ray_valid.inc"
 	const bool active = in && valid && tmax > 0.0f; // (tmax <= 0: nothing is closer than it)
 	float tmin = tmax;
 	int best = -1;
@@ -131,36 +122,17 @@ __global__ __launch_bounds__(64) void srt_segment_rays_kernel(const SegmentParam
 // ---------------------------------------------------------------------------------
 namespace {
 
-size_t mask_words(size_t n) { return (n + 63u) / 64u; }
-
-// the kernel, picked as ray_query.hip's launch_ray_query picks the cast's
-void launch_occlusion(const OcclusionParams &op, hipStream_t stream) {
-	typedef void (*OcclusionKernel)(const OcclusionParams);
-	const bool models = op.tp.num_models > 0, bvh = op.tp.use_bvh != 0;
-	const OcclusionKernel k = !models ? srt_occlusion_kernel<false, false> : bvh ? srt_occlusion_kernel<true, true> : srt_occlusion_kernel<true, false>;
-	hipLaunchKernelGGL(k, dim3((op.n + 63u) / 64u), dim3(64), 0, stream, op);
-}
-
-int check_count(srt_tracer *t, const char *who, size_t n, uint32_t flags) {
-	if (flags & ~SRT_RAYS_UNIT_DIRECTIONS) return fail(t, SRT_ERR_INVALID, std::string(who) + ": unknown flag bits");
-	if (n >= ((size_t)1 << 31)) return fail(t, SRT_ERR_INVALID, std::string(who) + ": n must stay below 2^31 rays");
-	return SRT_OK;
-}
-
 // the occlusion launch over device arrays, enqueued on the handle's stream (the caller has checked the arguments and set the device)
 int enqueue_occlusion(srt_tracer *t, const void *rays_dev, size_t n, uint32_t flags, void *occluded_dev, void *invalid_dev) {
-	srt_render_data rd; // only sizes trace_params_of's camera fields: the kernel reads none of them
-	memset(&rd, 0, sizeof rd);
-	rd.width = rd.height = 1;
 	OcclusionParams op;
 	memset(&op, 0, sizeof op);
-	op.tp = srt_trace_params_for_query(t, &rd);
+	op.tp = query_scene_params(t);
 	op.rays = static_cast<const float4 *>(rays_dev);
 	op.occluded = static_cast<uint64_t *>(occluded_dev);
 	op.invalid = static_cast<uint64_t *>(invalid_dev);
 	op.n = (uint32_t)n;
 	op.flags = flags;
-	launch_occlusion(op, t->stream);
+	query_launch(SRT_QUERY_KERNEL(srt_occlusion_kernel, op.tp), op, op.n, t->stream);
 	SRT_HIP(t, hipGetLastError());
 	return SRT_OK;
 }
@@ -170,36 +142,16 @@ int enqueue_segment_rays(srt_tracer *t, const void *segs_dev, size_t n, void *ra
 	sp.segs = static_cast<const float4 *>(segs_dev);
 	sp.rays = static_cast<float4 *>(rays_dev);
 	sp.n = (uint32_t)n;
-	hipLaunchKernelGGL(srt_segment_rays_kernel, dim3((sp.n + 63u) / 64u), dim3(64), 0, t->stream, sp);
+	query_launch(srt_segment_rays_kernel, sp, sp.n, t->stream);
 	SRT_HIP(t, hipGetLastError());
 	return SRT_OK;
 }
 
-// the ray queries' one staging allocation (srt_internal.h rq_stage), laid out for these calls: n rays, n segments, two masks
-int reserve_stage(srt_tracer *t, size_t n) {
-	SRT_HIP(t, hipStreamSynchronize(t->stream)); // (a grown buffer replaces one a queued launch may still use)
-	SRT_HIP(t, t->rq_stage.reserve(n * 64 + 2 * 8 * mask_words(n)));
-	return SRT_OK;
-}
-uint8_t *stage_rays(const srt_tracer *t) { return t->rq_stage.ptr; }
-uint8_t *stage_segs(const srt_tracer *t, size_t n) { return t->rq_stage.ptr + 32 * n; }
-uint8_t *stage_occluded(const srt_tracer *t, size_t n) { return t->rq_stage.ptr + 64 * n; }
-uint8_t *stage_invalid(const srt_tracer *t, size_t n) { return t->rq_stage.ptr + 64 * n + 8 * mask_words(n); }
-
-int span_begin(srt_tracer *t) {
-	t->rq_span.timed = false;
-	if (t->timers_in_render) SRT_HIP(t, t->rq_span.begin(t->stream));
-	return SRT_OK;
-}
-int span_end(srt_tracer *t) {
-	if (t->timers_in_render) SRT_HIP(t, t->rq_span.end(t->stream));
-	return SRT_OK;
-}
-
 // the masks of the staged rays back to the host, blocking
-int fetch_masks(srt_tracer *t, size_t n, uint64_t *occluded, uint64_t *invalid) {
-	SRT_HIP(t, hipMemcpyAsync(occluded, stage_occluded(t, n), 8 * mask_words(n), hipMemcpyDeviceToHost, t->stream));
-	if (invalid) SRT_HIP(t, hipMemcpyAsync(invalid, stage_invalid(t, n), 8 * mask_words(n), hipMemcpyDeviceToHost, t->stream));
+int fetch_masks(srt_tracer *t, size_t n, const QueryStage &st, uint64_t *occluded, uint64_t *invalid) {
+	const uint8_t *const stage = t->rq_stage.ptr;
+	SRT_HIP(t, hipMemcpyAsync(occluded, stage + st.occluded, 8 * query_mask_words(n), hipMemcpyDeviceToHost, t->stream));
+	if (invalid) SRT_HIP(t, hipMemcpyAsync(invalid, stage + st.invalid, 8 * query_mask_words(n), hipMemcpyDeviceToHost, t->stream));
 	SRT_HIP(t, hipStreamSynchronize(t->stream));
 	return SRT_OK;
 }
@@ -217,58 +169,64 @@ int srt_occlusion_sizes(size_t out[2]) {
 
 int srt_occluded_rays_device(srt_tracer *t, const void *rays_dev, size_t n, uint32_t flags, void *occluded_dev, void *invalid_dev) {
 	if (!t) return SRT_ERR_INVALID;
-	if (const int rc = check_count(t, "srt_occluded_rays_device", n, flags)) return rc;
+	if (const int rc = query_check_count(t, "srt_occluded_rays_device", n, flags)) return rc;
 	if (n == 0) return SRT_OK;
 	if (!rays_dev || !occluded_dev) return fail(t, SRT_ERR_INVALID, "srt_occluded_rays_device: NULL array");
 	if (((uintptr_t)rays_dev & 15u) || (((uintptr_t)occluded_dev | (uintptr_t)invalid_dev) & 7u))
 		return fail(t, SRT_ERR_INVALID, "srt_occluded_rays_device: rays must be aligned to 16 bytes, masks to 8");
 	SRT_HIP(t, hipSetDevice(t->device));
-	if (const int rc = span_begin(t)) return rc;
+	if (const int rc = query_span_begin(t)) return rc;
 	if (const int rc = enqueue_occlusion(t, rays_dev, n, flags, occluded_dev, invalid_dev)) return rc;
-	return span_end(t);
+	return query_span_end(t);
 }
 
 int srt_occluded_rays(srt_tracer *t, const srt_ray *rays, size_t n, uint32_t flags, uint64_t *occluded, uint64_t *invalid) {
 	if (!t) return SRT_ERR_INVALID;
-	if (const int rc = check_count(t, "srt_occluded_rays", n, flags)) return rc;
+	if (const int rc = query_check_count(t, "srt_occluded_rays", n, flags)) return rc;
 	if (n == 0) return SRT_OK;
 	if (!rays || !occluded) return fail(t, SRT_ERR_INVALID, "srt_occluded_rays: NULL array");
 	SRT_HIP(t, hipSetDevice(t->device));
-	if (const int rc = reserve_stage(t, n)) return rc;
-	SRT_HIP(t, hipMemcpyAsync(stage_rays(t), rays, n * sizeof(srt_ray), hipMemcpyHostToDevice, t->stream));
-	if (const int rc = span_begin(t)) return rc;
-	if (const int rc = enqueue_occlusion(t, stage_rays(t), n, flags, stage_occluded(t, n), invalid ? stage_invalid(t, n) : nullptr)) return rc;
-	if (const int rc = span_end(t)) return rc;
-	return fetch_masks(t, n, occluded, invalid);
+	QueryStage st;
+	if (const int rc = query_reserve_stage(t, n, &st)) return rc;
+	uint8_t *const stage = t->rq_stage.ptr;
+	SRT_HIP(t, hipMemcpyAsync(stage + st.rays, rays, n * sizeof(srt_ray), hipMemcpyHostToDevice, t->stream));
+	if (const int rc = query_span_begin(t)) return rc;
+	if (const int rc = enqueue_occlusion(t, stage + st.rays, n, flags, stage + st.occluded, invalid ? stage + st.invalid : nullptr)) return rc;
+	if (const int rc = query_span_end(t)) return rc;
+	return fetch_masks(t, n, st, occluded, invalid);
 }
 
 int srt_occluded_segments(srt_tracer *t, const srt_segment *segs, size_t n, uint64_t *occluded, uint64_t *invalid) {
 	if (!t) return SRT_ERR_INVALID;
-	if (const int rc = check_count(t, "srt_occluded_segments", n, 0u)) return rc;
+	if (const int rc = query_check_count(t, "srt_occluded_segments", n, 0u)) return rc;
 	if (n == 0) return SRT_OK;
 	if (!segs || !occluded) return fail(t, SRT_ERR_INVALID, "srt_occluded_segments: NULL array");
 	SRT_HIP(t, hipSetDevice(t->device));
-	if (const int rc = reserve_stage(t, n)) return rc;
-	SRT_HIP(t, hipMemcpyAsync(stage_segs(t, n), segs, n * sizeof(srt_segment), hipMemcpyHostToDevice, t->stream));
-	if (const int rc = span_begin(t)) return rc;
-	if (const int rc = enqueue_segment_rays(t, stage_segs(t, n), n, stage_rays(t))) return rc;
-	if (const int rc = enqueue_occlusion(t, stage_rays(t), n, SRT_RAYS_UNIT_DIRECTIONS, stage_occluded(t, n), invalid ? stage_invalid(t, n) : nullptr)) return rc;
-	if (const int rc = span_end(t)) return rc;
-	return fetch_masks(t, n, occluded, invalid);
+	QueryStage st;
+	if (const int rc = query_reserve_stage(t, n, &st)) return rc;
+	uint8_t *const stage = t->rq_stage.ptr;
+	SRT_HIP(t, hipMemcpyAsync(stage + st.segs, segs, n * sizeof(srt_segment), hipMemcpyHostToDevice, t->stream));
+	if (const int rc = query_span_begin(t)) return rc;
+	if (const int rc = enqueue_segment_rays(t, stage + st.segs, n, stage + st.rays)) return rc;
+	if (const int rc = enqueue_occlusion(t, stage + st.rays, n, SRT_RAYS_UNIT_DIRECTIONS, stage + st.occluded, invalid ? stage + st.invalid : nullptr)) return rc;
+	if (const int rc = query_span_end(t)) return rc;
+	return fetch_masks(t, n, st, occluded, invalid);
 }
 
 int srt_segment_rays(srt_tracer *t, const srt_segment *segs, size_t n, srt_ray *rays_out) {
 	if (!t) return SRT_ERR_INVALID;
-	if (const int rc = check_count(t, "srt_segment_rays", n, 0u)) return rc;
+	if (const int rc = query_check_count(t, "srt_segment_rays", n, 0u)) return rc;
 	if (n == 0) return SRT_OK;
 	if (!segs || !rays_out) return fail(t, SRT_ERR_INVALID, "srt_segment_rays: NULL array");
 	SRT_HIP(t, hipSetDevice(t->device));
-	if (const int rc = reserve_stage(t, n)) return rc;
-	SRT_HIP(t, hipMemcpyAsync(stage_segs(t, n), segs, n * sizeof(srt_segment), hipMemcpyHostToDevice, t->stream));
-	if (const int rc = span_begin(t)) return rc;
-	if (const int rc = enqueue_segment_rays(t, stage_segs(t, n), n, stage_rays(t))) return rc;
-	if (const int rc = span_end(t)) return rc;
-	SRT_HIP(t, hipMemcpyAsync(rays_out, stage_rays(t), n * sizeof(srt_ray), hipMemcpyDeviceToHost, t->stream));
+	QueryStage st;
+	if (const int rc = query_reserve_stage(t, n, &st)) return rc;
+	uint8_t *const stage = t->rq_stage.ptr;
+	SRT_HIP(t, hipMemcpyAsync(stage + st.segs, segs, n * sizeof(srt_segment), hipMemcpyHostToDevice, t->stream));
+	if (const int rc = query_span_begin(t)) return rc;
+	if (const int rc = enqueue_segment_rays(t, stage + st.segs, n, stage + st.rays)) return rc;
+	if (const int rc = query_span_end(t)) return rc;
+	SRT_HIP(t, hipMemcpyAsync(rays_out, stage + st.rays, n * sizeof(srt_ray), hipMemcpyDeviceToHost, t->stream));
 	SRT_HIP(t, hipStreamSynchronize(t->stream));
 	return SRT_OK;
 }

@@ -1,0 +1,33 @@
+// query_stage.h -- the layout of the queries' one staging allocation (srt_internal.h rq_stage), for the host forms of
+// ray_query.hip and occlusion.hip: byte offsets of every region any of those calls uses, and the total to reserve, from the
+// call's n alone. No HIP and no handle: tests/csrc/host_units_check.cpp includes it by itself.
+//
+//   [0, 32 n)       rays      n srt_ray: every call
+//   [32 n, 64 n)    hits      n srt_ray_hit (srt_cast_rays, srt_pick)   | the same bytes:
+//                   segs      n srt_segment (srt_occluded_segments, srt_segment_rays) | no call has hits and segments
+//   [64 n, ...)     xy        n points of 8 bytes (srt_pick)            | the same bytes:
+//                   occluded, invalid   ceil(n / 64) words of 8 bytes each (srt_occluded_rays, srt_occluded_segments) | no call has points and masks
+#ifndef SRT_QUERY_STAGE_H
+#define SRT_QUERY_STAGE_H
+
+#include <stddef.h>
+
+struct QueryStage {
+	size_t rays, hits, segs, xy, occluded, invalid; // byte offsets
+	size_t total;                                    // bytes
+};
+
+static inline size_t query_mask_words(size_t n) { return (n + 63u) / 64u; }
+
+static inline QueryStage query_stage(size_t n) { // n < 2^31 (the calls' own check): nothing here overflows 64 bits
+	const size_t mask = 8 * query_mask_words(n);
+	QueryStage s;
+	s.rays = 0;
+	s.hits = s.segs = 32 * n;
+	s.xy = s.occluded = 64 * n;
+	s.invalid = s.occluded + mask;
+	s.total = 64 * n + (8 * n > 2 * mask ? 8 * n : 2 * mask);
+	return s;
+}
+
+#endif

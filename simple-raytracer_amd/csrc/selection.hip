@@ -2,11 +2,11 @@
 // unit of its own: the kernels here are new, every kernel the library launched before keeps its instruction stream
 // (scripts/kernel_isa_digest.py).
 //
-//  * srt_id_pass_kernel<HAS_MODELS, USE_BVH>: one lane per pixel. The ray through the pixel's centre with the statements of
-//    srt_pick_rays_kernel (ray_query.hip), walked with the body of srt_ray_query_kernel -- restated here, not shared: moving
-//    that body into a __device__ function changed the cast kernels' instruction streams -- and three words
-//    stored per pixel: shape, triangle inside its model, material. Nothing is staged: the 64 B ray and the 32 B record of the
-//    pick path never exist.
+//  * srt_id_pass_kernel<HAS_MODELS, USE_BVH>: one lane per pixel. The ray through the pixel's centre is srt_pick_rays_kernel's
+//    (device_math.h camera_ray), refused and walked as srt_ray_query_kernel refuses and walks it: ray_valid.inc and
+//    closest_hit.inc, the text both kernels include -- text, because moving those statements into __device__ functions changed
+//    the cast kernels' instruction streams -- and three words stored per pixel: shape, triangle inside its
+//    model, material. Nothing is staged: the 64 B ray and the 32 B record of the pick path never exist.
 //  * srt_selection_outline_kernel: one workgroup of 256 lanes per 32 x 8 pixel tile. The selection mask of the tile and its
 //    halo of R pixels sits in LDS as one 64-bit word per row (32 + 2 R <= 48 columns), each made by one ballot; a workgroup
 //    whose words are all zero leaves after one vote having read the ID plane's shape words and nothing else. The distance to
@@ -24,7 +24,7 @@
 #include "device_intersect.h"
 #include "device_shading.h"
 #include "selection_host.h"
-#include "srt_internal.h"
+#include "query_host.h"
 
 #define SRT_SEL_TILE_W 32
 #define SRT_SEL_TILE_H 8
@@ -49,11 +49,6 @@ struct OutlineParams {
 	uint32_t fill_alpha, fill_word, outline_word; /* the colours as picture words (R, G, B in bytes 1..3) */
 };
 
-namespace {
-__device__ __forceinline__ bool finite_bits(float x) { return (f2u(x) & 0x7f800000u) != 0x7f800000u; }
-__device__ __forceinline__ bool finite3(f3 a) { return finite_bits(a.x) && finite_bits(a.y) && finite_bits(a.z); }
-} // namespace
-
 template <bool HAS_MODELS, bool USE_BVH>
 __global__ __launch_bounds__(64) void srt_id_pass_kernel(const IdPassParams ip) {
 	const TraceParams &p = ip.tp;
@@ -62,23 +57,16 @@ __global__ __launch_bounds__(64) void srt_id_pass_kernel(const IdPassParams ip) 
 #ifdef SRT_REGION_COUNT
 	__shared__ uint32_t region_ctr[2 * SRT_REGION_MAX]; // (development builds: the shared helpers count regions; nobody reads these)
 #endif
-	// ---- the pixel centre's ray: srt_pick_rays_kernel with xy = (px + 0.5, py + 0.5) ----
+	// ---- the pixel centre's ray: srt_pick_rays_kernel's, of xy = (px + 0.5, py + 0.5) ----
 	const uint32_t width = (uint32_t)p.rd.width;
 	const uint32_t py = q / width, px = q - py * width;
 	const float2 xy = make_float2((float)px + 0.5f, (float)py + 0.5f);
-	const f3 c0 = mk(p.rd.camera_to_world[0].x, p.rd.camera_to_world[0].y, p.rd.camera_to_world[0].z);
-	const f3 c1 = mk(p.rd.camera_to_world[1].x, p.rd.camera_to_world[1].y, p.rd.camera_to_world[1].z);
-	const f3 c2 = mk(p.rd.camera_to_world[2].x, p.rd.camera_to_world[2].y, p.rd.camera_to_world[2].z);
-	const f3 cam = mk(p.rd.camera_to_world[3].x, p.rd.camera_to_world[3].y, p.rd.camera_to_world[3].z);
-	const float ndc_x = div_by_rcp(xy.x, p.f_width, p.inv_f_width);
-	const float ndc_y = div_by_rcp(xy.y, p.f_height, p.inv_f_height);
-	const float sx = ((2.f * ndc_x - 1.f) * p.rd.aspect_ratio) * p.rd.fov_scale;
-	const float sy = (1.f - 2.f * ndc_y) * p.rd.fov_scale;
-	const f3 dir = normalize3(mat_cols_by_vec(c0, c1, c2, cam, mk(sx, sy, -1.0f), 0.0f));
-	const f3 org = cam;
+	f3 org, dir;
+	camera_ray(p, xy, org, dir);
 	// ---- srt_ray_query_kernel under SRT_RAYS_UNIT_DIRECTIONS with tmax = +inf, as srt_pick casts it ----
-	bool valid = finite3(org) && finite3(dir);
-	valid = valid && finite3(dir) && !(dir.x == 0.0f && dir.y == 0.0f && dir.z == 0.0f);
+	const float tmax = DM_INF_F;
+	const uint32_t flags = SRT_RAYS_UNIT_DIRECTIONS;
+#include "ray_valid.inc"
 	float tmin = DM_INF_F;
 	int best = -1;
 	uint32_t best_tri = 0;
@@ -87,33 +75,7 @@ __global__ __launch_bounds__(64) void srt_id_pass_kernel(const IdPassParams ip) 
 		uint32_t n_tri = 0, n_tri_u = 0;
 		f3 inv = mk(0.f, 0.f, 0.f);
 		if (HAS_MODELS) inv = mk(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
-		auto test_block = [&](const Blk16 &b, uint32_t code, int base) {
-			const uint32_t type1 = code & 3u;
-			if (type1 == SRT_SHAPE_SPHERE + 1u) {
-				if (((code >> 2) & 7u) <= 2u) test_spheres<2>(b, org, dir, base, tmin, best);
-				else test_spheres<4>(b, org, dir, base, tmin, best);
-			} else if (type1 == SRT_SHAPE_PLANE + 1u) {
-				test_planes2(b, (code >> 2) & 7u, org, dir, base, tmin, best);
-			} else if (HAS_MODELS && type1 == SRT_SHAPE_MODEL + 1u) {
-				if (test_aabb(b.v[0], b.v[1], b.v[2], b.v[4], b.v[5], b.v[6], org, inv, tmin)) {
-					if (USE_BVH) walk_bvh<false>(reinterpret_cast<const float4 *>(p.bvh_blocks), bvh_stack, f2u(b.v[3]), org, dir, base, tmin, best, best_tri, n_tri, n_tri_u SRT_RC_ARG);
-					else test_triangles<false>(p.wtris, f2u(b.v[3]), f2u(b.v[7]), org, dir, base, tmin, best, best_tri, n_tri_u SRT_RC_ARG);
-				}
-				if (((code >> 2) & 7u) > 1u && test_aabb(b.v[8], b.v[9], b.v[10], b.v[12], b.v[13], b.v[14], org, inv, tmin)) {
-					if (USE_BVH) walk_bvh<false>(reinterpret_cast<const float4 *>(p.bvh_blocks), bvh_stack, f2u(b.v[11]), org, dir, base + 1, tmin, best, best_tri, n_tri, n_tri_u SRT_RC_ARG);
-					else test_triangles<false>(p.wtris, f2u(b.v[11]), f2u(b.v[15]), org, dir, base + 1, tmin, best, best_tri, n_tri_u SRT_RC_ARG);
-				}
-			}
-		};
-		for (int g = 0; g < p.num_runs; g++) {
-			float gh[4];
-			ld_uniform<4, 16>(reinterpret_cast<const float *>(p.runs + g), gh);
-			const uint32_t code = f2u(gh[0]);
-			const float *__restrict__ gd = p.run_data + 48 * g;
-			test_block(ld_blk16(gd), code & 255u, (int)f2u(gh[1]));
-			if ((code >> 8) & 255u) test_block(ld_blk16(gd + 16), (code >> 8) & 255u, (int)f2u(gh[2]));
-			if ((code >> 16) & 255u) test_block(ld_blk16(gd + 32), (code >> 16) & 255u, (int)f2u(gh[3]));
-		}
+#include "closest_hit.inc"
 	}
 	// ---- the three words ----
 	uint32_t shape = SRT_HIT_NONE, tri = SRT_HIT_NONE;
@@ -248,10 +210,7 @@ int enqueue_id_pass(srt_tracer *t, const srt_tracer *scene, const srt_render_dat
 	ip.material = reinterpret_cast<int32_t *>(s->ids.ptr + 2 * px);
 	ip.tri_materials = srt_texture_params(scene).tri_materials;
 	ip.n = (uint32_t)px;
-	typedef void (*IdKernel)(const IdPassParams);
-	const bool models = ip.tp.num_models > 0, bvh = ip.tp.use_bvh != 0;
-	const IdKernel k = !models ? srt_id_pass_kernel<false, false> : bvh ? srt_id_pass_kernel<true, true> : srt_id_pass_kernel<true, false>;
-	hipLaunchKernelGGL(k, dim3((ip.n + 63u) / 64u), dim3(64), 0, t->stream, ip);
+	query_launch(SRT_QUERY_KERNEL(srt_id_pass_kernel, ip.tp), ip, ip.n, t->stream);
 	SRT_HIP(t, hipGetLastError());
 	s->ids_w = rd.width, s->ids_h = rd.height;
 	s->ids_key = key_of(scene, rd);

@@ -349,9 +349,8 @@ struct srt_tracer {
 	uint64_t scene_rev = 0;           // bumped by every successful srt_update_scene (the ID planes' key)
 	srt_render_data last_rd{};        // the most recent dispatch's options (the overlay's camera) ...
 	bool have_last_rd = false;        // ... once there was one
-	// ray queries (ray_query.hip; srt_cast_rays, srt_pick): the host forms' one staging allocation -- n rays, n hits, n picked
-	// points (32 + 32 + 8 bytes each) of the largest call so far -- and the timers' span around the last query's launches;
-	// occlusion queries (occlusion.hip) use both: n rays, n segments and two bit masks in the same allocation
+	// ray and occlusion queries (ray_query.hip, occlusion.hip): the host forms' one staging allocation, sized for the largest
+	// call so far and laid out per call by query_stage.h, and the timers' span around the last query's launches
 	DevBuf<uint8_t> rq_stage;
 	TimedSpan rq_span;
 	hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;

@@ -1,16 +1,18 @@
 // host_units_check.cpp -- the three host units of csrc/ that need no device, without the library: the BVH builder
 // (bvh_host.cpp), the scene's host pass with its hierarchy cache (scene_prep.cpp), the launch plan (trace_plan.h) and the
-// denoiser's settings, plans and staging key (denoise_plan.h).
-// usage: host_units_check bvh | scene | plan | batches | denoise   (tests/test_host_units.py; scripts/host_asan.sh runs bvh, scene and batches under sanitizers)
+// denoiser's settings, plans and staging key (denoise_plan.h), the layout of the queries' staging allocation (query_stage.h).
+// usage: host_units_check bvh | scene | plan | batches | denoise | stage   (tests/test_host_units.py; scripts/host_asan.sh runs bvh, scene, batches and stage under sanitizers)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "denoise_plan.h"
+#include "query_stage.h"
 #include "scene_prep.h"
 #include "trace_plan.h"
 
@@ -363,6 +365,47 @@ static int mode_denoise() {
 	return 0;
 }
 
+// ---- stage --------------------------------------------------------------------------------------------------------------------
+// query_stage.h for the counts at which something changes (one item, around one and two mask words) and the largest a call
+// accepts: per call of include/srt_abi.h the regions it uses together and the bytes it moves through each (srt_ray,
+// srt_ray_hit and srt_segment are 32 bytes, a picked point 8, a mask ceil(n / 64) words of 8), alignment as the kernels' 128-bit
+// and 64-bit accesses need it, and a total within what the two formulas before the shared layout reserved.
+struct StageRegion {
+	const char *name;
+	size_t at, bytes, align;
+};
+
+static int mode_stage() {
+	for (const size_t n : {(size_t)1, (size_t)63, (size_t)64, (size_t)65, (size_t)129, ((size_t)1 << 31) - 1}) {
+		const QueryStage s = query_stage(n);
+		const size_t words = (n + 63) / 64;
+		CHECK(query_mask_words(n) == words, "n %zu: %zu mask words", n, query_mask_words(n));
+		const StageRegion rays = {"rays", s.rays, 32 * n, 16}, hits = {"hits", s.hits, 32 * n, 16}, segs = {"segs", s.segs, 32 * n, 16};
+		const StageRegion xy = {"xy", s.xy, 8 * n, 8}, occluded = {"occluded", s.occluded, 8 * words, 8}, invalid = {"invalid", s.invalid, 8 * words, 8};
+		const std::vector<std::pair<const char *, std::vector<StageRegion>>> calls = {
+		    {"srt_cast_rays", {rays, hits}},
+		    {"srt_pick", {xy, rays, hits}},
+		    {"srt_occluded_rays", {rays, occluded, invalid}},
+		    {"srt_occluded_segments", {segs, rays, occluded, invalid}},
+		    {"srt_segment_rays", {segs, rays}},
+		};
+		for (const auto &call : calls) {
+			const std::vector<StageRegion> &rs = call.second;
+			for (size_t a = 0; a < rs.size(); a++) {
+				CHECK(rs[a].at % rs[a].align == 0, "n %zu, %s: %s at %zu is not aligned to %zu", n, call.first, rs[a].name, rs[a].at, rs[a].align);
+				CHECK(rs[a].at + rs[a].bytes <= s.total, "n %zu, %s: %s ends at %zu of %zu", n, call.first, rs[a].name, rs[a].at + rs[a].bytes, s.total);
+				for (size_t b = a + 1; b < rs.size(); b++)
+					CHECK(rs[a].at + rs[a].bytes <= rs[b].at || rs[b].at + rs[b].bytes <= rs[a].at, "n %zu, %s: %s and %s overlap", n, call.first, rs[a].name, rs[b].name);
+			}
+		}
+		const size_t cast = n * 72, occlusion = n * 64 + 16 * words;
+		CHECK(s.total <= (cast > occlusion ? cast : occlusion), "n %zu: %zu bytes, more than the %zu / %zu of the separate layouts", n, s.total, cast, occlusion);
+		printf("stage n %10zu  total %12zu\n", n, s.total);
+	}
+	printf("ok\n");
+	return 0;
+}
+
 int main(int argc, char **argv) {
 	const std::string mode = argc > 1 ? argv[1] : "";
 	if (mode == "bvh") return mode_bvh();
@@ -370,6 +413,7 @@ int main(int argc, char **argv) {
 	if (mode == "plan") return mode_plan();
 	if (mode == "batches") return mode_batches();
 	if (mode == "denoise") return mode_denoise();
-	fprintf(stderr, "usage: %s bvh | scene | plan | batches | denoise\n", argv[0]);
+	if (mode == "stage") return mode_stage();
+	fprintf(stderr, "usage: %s bvh | scene | plan | batches | denoise | stage\n", argv[0]);
 	return 2;
 }

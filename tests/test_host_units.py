@@ -3,7 +3,9 @@
 scene's host pass with its hierarchy cache (scene_prep.cpp: reuse, refit, claim, eviction, an error that keeps the cache) and
 the launch plan of srt_trace (trace_plan.h) against the table the parent of the split printed (tests/golden/
 trace_plan_parent.json), with the slices its batches cut a dispatch into; the denoiser's settings, plans and staging key
-(denoise_plan.h) against the rules of include/srt_abi.h restated here. And the g++ build of the builder against the library's, bit for bit."""
+(denoise_plan.h) against the rules of include/srt_abi.h restated here; the layout of the queries' staging allocation
+(query_stage.h: per call its regions aligned, disjoint, large enough, the total within what the calls reserved before they
+shared it). And the g++ build of the builder against the library's, bit for bit."""
 import ctypes as C
 import json
 import subprocess
@@ -29,7 +31,7 @@ def exe(tmp_path_factory):
     return out
 
 
-@pytest.mark.parametrize("mode", ["bvh", "scene"])
+@pytest.mark.parametrize("mode", ["bvh", "scene", "stage"])
 def test_host_unit(exe, mode):
     out = subprocess.run([str(exe), mode], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout + out.stderr
