@@ -1276,6 +1276,73 @@ int srt_read_selection_alpha(srt_tracer *t, uint8_t *alpha, size_t cap_pixels);
 int srt_last_resolve_selected(const srt_tracer *t, int *applied, int *id_pass_ran);
 int srt_group_last_resolve_selected(const srt_group *g, int *applied, int *id_pass_ran);
 
+/* ---- ambient-occlusion pass (new; no counterpart in the reference) ----------------------------------------------------------
+ * Per pixel of a frame: how many of S cosine-weighted hemisphere rays from the visible surface meet anything within a radius.
+ * A "clay" picture of the geometry with a bounded, fixed noise, for the viewport while the camera or a gizmo moves, and the one
+ * AOV neither the denoiser's guides nor the ID pass cover. `options` supplies only the camera (camera_to_world, aspect_ratio,
+ * fov_scale) and the frame size (width, height: any positive size, not necessarily the handle's); S = params->samples.
+ *
+ * THE DEFINITION, per pixel q = py * width + px. The library is built with fp-contract=off: every line below is a plain float
+ * statement per component, nothing is fused.
+ *   SURFACE. The ray is the ID pass's: xy = (px + 0.5, py + 0.5), unit direction `dir`, origin `org`, tmax = +inf, refused and
+ *     walked exactly as srt_pick refuses and walks it. t = the pick's t, N = the pick's normal (the winner's, turned to face the
+ *     ray). A shape without a material is a surface, as it is for the pick. A miss or an invalid ray: no surface.
+ *   ORIGIN. P = org + dir * t;  O = P + N * bias.
+ *   SAMPLE s of S:  uint32_t seed = params->seed + (q * S + s) * 0x9E3779B9u;  then the per-lane random unit vector of the
+ *     trace's diffuse bounce, added to the normal:  rd = normalize3(random_normal3_lane(seed));  D = normalize3(N + rd).
+ *     The ray is {O, tmax = radius, D}, its direction of unit length. That is the cosine law about N (a point of the unit
+ *     sphere that touches the surface at P, seen from P): E[dot(D, N)] = 2/3. The trace's bounce first turns rd into N's
+ *     hemisphere (rd * sign(dot(N, rd))); the pass does NOT: normalize3(N + a direction of the hemisphere) keeps every ray
+ *     within 45 degrees of N (mean cosine 0.862) and is no cosine law. rd = -N, for which D would be 0, gives an invalid ray,
+ *     which is not occluded.
+ *   ANSWER. occluded[q] = the number of the pixel's S rays for which srt_occluded_rays(ray, SRT_RAYS_UNIT_DIRECTIONS) would set
+ *     its bit -- the occlusion contract unchanged: tmax strict, glass and shapes without a material occlude, an invalid ray is
+ *     not occluded. A pixel without a surface holds SRT_HIT_NONE.
+ * The plane is width * height uint32_t; a caller who wants a float derives 1 - occluded / S. The integer is what can be pinned:
+ * it does not depend on how the kernels map rays to lanes, nor on the acceleration mode.
+ *
+ * THE RAYS. srt_ao_rays returns the n_pixels * S rays defined above for pixels first_pixel .. of the frame, ray (q, s) at
+ * (q - first_pixel) * S + s, made by the same device function the pass makes a ray with (blocking; through the queries' staging
+ * allocation). A pixel without a surface gets S records with tmax = NaN (origin and direction 0): invalid rays by the cast's
+ * rule. So the per-pixel sum of srt_occluded_rays(srt_ao_rays(...), SRT_RAYS_UNIT_DIRECTIONS) equals srt_read_ao's plane,
+ * integer for integer.
+ * THE VIEW. srt_resolve_ao_view writes the grey picture into the handle's ARGB bytes (srt_read_argb reads it), asynchronous:
+ * A = 255, R = G = B = table[occluded], table[c] = floor(255 * (1 - c / S) + 0.5) made on the host in double
+ * (srt_ao_table_host); a pixel without a surface gets the bytes A, R, G, B of params->background = 0xAARRGGBB. Like
+ * srt_resolve_noise_view it is no picture site: selection overlay, exposure and bloom do not apply. The pass's frame must be
+ * the handle's size, else SRT_ERR_STATE.
+ * STATE. As a cast: the scene as the last srt_update_scene left it, ordered on the handle's stream behind that update's
+ * pre-pass, refit and build. The pass writes planes of its own on the handle (36 B per pixel, freed in srt_destroy),
+ * srt_ao_rays the queries' staging allocation (32 B per ray + 32 B per pixel), the view the ARGB bytes, and nothing else:
+ * canvas, counters, ID planes, denoiser, exposure, bloom, noise and selection state stay as they were, and so does every
+ * srt_last_* answer but srt_last_ray_query_ms, which covers the launches of the last of these calls when the kernel timers
+ * are on. A handle that never calls these launches exactly what it launched before. Before any scene is set every pixel is
+ * SRT_HIT_NONE.
+ * ERRORS. SRT_ERR_INVALID: a NULL argument; what srt_ao_check_host refuses; first_pixel + n_pixels beyond the frame; a
+ * capacity too small. SRT_ERR_STATE: srt_read_ao or srt_resolve_ao_view before any pass. n_pixels == 0: SRT_OK, no launch. */
+int srt_ao_defaults(srt_ao_params *out); /* samples 16, radius +inf, bias 0.001f (the reference's acne offset), seed 0, background 0xff000000 */
+/* Host-only: the validation srt_render_ao applies. SRT_ERR_INVALID unless samples is one of 1, 2, 4, 8, 16, 32, 64; radius > 0
+ * and not NaN (+inf allowed); bias >= 0 and finite; reserved zero; width, height > 0 and width * height * samples < 2^31. */
+int srt_ao_check_host(const srt_ao_params *p, int width, int height);
+/* Host-only: out = {sizeof(srt_ao_params)} as the library was built. */
+int srt_ao_sizes(size_t out[1]);
+/* Host-only: table[c] for c = 0 .. samples as defined above (the entries past samples: 0). SRT_ERR_INVALID: samples refused. */
+int srt_ao_table_host(const srt_ao_params *p, uint8_t table[65]);
+/* The pass, asynchronous on the handle's stream. */
+int srt_render_ao(srt_tracer *t, const srt_render_data *options, const srt_ao_params *params);
+/* Waits for the handle's stream. The last pass's plane, *w x *h words, into `occluded` of cap_pixels words; *samples = its S.
+ * `occluded` NULL: the sizes alone. Any of w, h, samples may be NULL. */
+int srt_read_ao(srt_tracer *t, uint32_t *occluded, size_t cap_pixels, int *w, int *h, int *samples);
+int srt_ao_rays(srt_tracer *t, const srt_render_data *options, const srt_ao_params *params, size_t first_pixel, size_t n_pixels, srt_ray *rays_out);
+int srt_resolve_ao_view(srt_tracer *t);
+/* On the group's first member, which holds the whole scene, as the group casts. srt_group_read_ao_view: blocking, the group's
+ * width * height * 4 bytes of the view (a group has no srt_read_argb). */
+int srt_group_render_ao(srt_group *g, const srt_render_data *options, const srt_ao_params *params);
+int srt_group_read_ao(srt_group *g, uint32_t *occluded, size_t cap_pixels, int *w, int *h, int *samples);
+int srt_group_ao_rays(srt_group *g, const srt_render_data *options, const srt_ao_params *params, size_t first_pixel, size_t n_pixels, srt_ray *rays_out);
+int srt_group_resolve_ao_view(srt_group *g);
+int srt_group_read_ao_view(srt_group *g, uint8_t *argb_out);
+
 /* Library / build identification, e.g. "srt-hip gfx950 parity fp-contract=off". */
 const char *srt_version(void);
 

@@ -262,6 +262,18 @@ typedef struct srt_selection_params {
 	int32_t reserved[4];     /* must be 0 */
 } srt_selection_params;
 
+/* Ambient-occlusion pass (srt_render_ao in srt_abi.h, where the rays are written down; new, no counterpart in the reference):
+ * per pixel, how many of `samples` cosine-weighted hemisphere rays from the visible surface meet anything within `radius`. */
+#define SRT_AO_MAX_SAMPLES 64
+typedef struct srt_ao_params {
+	uint32_t samples;     /* rays per pixel: 1, 2, 4, 8, 16, 32 or 64 (default 16) */
+	float radius;         /* > 0, +inf allowed: a ray's tmax, strict (default +inf) */
+	float bias;           /* >= 0, finite: the origin's offset along the facing normal (default 0.001f) */
+	uint32_t seed;        /* the rays' generator starts from seed + (pixel * samples + sample) * 0x9E3779B9 (default 0) */
+	uint32_t background;  /* srt_resolve_ao_view: 0xAARRGGBB of the pixels without a surface (default 0xff000000) */
+	uint32_t reserved[3]; /* must be 0 */
+} srt_ao_params;
+
 #ifdef __cplusplus
 }
 #endif
@@ -342,5 +354,7 @@ SRT_STATIC_ASSERT(offsetof(srt_segment, to) == 16, "Segment.to@16");
 SRT_STATIC_ASSERT(sizeof(srt_selection_params) == 32, "SelectionParams 32 B");
 SRT_STATIC_ASSERT(offsetof(srt_selection_params, outline_argb) == 8, "SelectionParams.outline_argb@8");
 SRT_STATIC_ASSERT(offsetof(srt_selection_params, reserved) == 16, "SelectionParams.reserved@16");
+SRT_STATIC_ASSERT(sizeof(srt_ao_params) == 32, "AoParams 32 B");
+SRT_STATIC_ASSERT(offsetof(srt_ao_params, background) == 16, "AoParams.background@16");
 
 #endif /* SRT_TYPES_H */

@@ -17,6 +17,21 @@ struct QueryStage {
 	size_t total;                                    // bytes
 };
 
+// srt_ao_rays (ao.hip) lays the same allocation out for n_pixels pixels of `samples` rays each:
+//   [0, 32 n_pixels samples)   rays       the call's answer
+//   [.., + 32 n_pixels)        surfaces   two float4 per pixel, what the ray kernel reads
+struct AoStage {
+	size_t rays, surfaces; // byte offsets
+	size_t total;          // bytes
+};
+static inline AoStage ao_stage(size_t n_pixels, size_t samples) { // n_pixels * samples < 2^31 (the call's own check)
+	AoStage s;
+	s.rays = 0;
+	s.surfaces = 32 * n_pixels * samples;
+	s.total = s.surfaces + 32 * n_pixels;
+	return s;
+}
+
 static inline size_t query_mask_words(size_t n) { return (n + 63u) / 64u; }
 
 static inline QueryStage query_stage(size_t n) { // n < 2^31 (the calls' own check): nothing here overflows 64 bits

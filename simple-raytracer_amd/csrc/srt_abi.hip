@@ -223,6 +223,7 @@ void srt_destroy(srt_tracer *t) {
 	t->sel_own.release();
 	t->rq_stage.release();
 	t->rq_span.release();
+	t->ao.release();
 	srt_texture_release(t);
 	if (t->ev_t0) (void)hipEventDestroy(t->ev_t0);
 	if (t->ev_t1) (void)hipEventDestroy(t->ev_t1);

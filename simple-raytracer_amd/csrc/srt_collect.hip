@@ -997,6 +997,41 @@ int srt_group_segment_rays(srt_group *g, const srt_segment *segs, size_t n, srt_
 	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
 }
 
+// the ambient-occlusion pass (ao.hip), likewise: planes, rays and view are the first member's
+int srt_group_render_ao(srt_group *g, const srt_render_data *options, const srt_ao_params *params) {
+	if (!g || g->t.empty()) return SRT_ERR_INVALID;
+	const int rc = srt_render_ao(g->t[0], options, params);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+int srt_group_read_ao(srt_group *g, uint32_t *occluded, size_t cap_pixels, int *w, int *h, int *samples) {
+	if (!g || g->t.empty()) return SRT_ERR_INVALID;
+	const int rc = srt_read_ao(g->t[0], occluded, cap_pixels, w, h, samples);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+int srt_group_ao_rays(srt_group *g, const srt_render_data *options, const srt_ao_params *params, size_t first_pixel, size_t n_pixels, srt_ray *rays_out) {
+	if (!g || g->t.empty()) return SRT_ERR_INVALID;
+	const int rc = srt_ao_rays(g->t[0], options, params, first_pixel, n_pixels, rays_out);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+int srt_group_resolve_ao_view(srt_group *g) {
+	if (!g || g->t.empty()) return SRT_ERR_INVALID;
+	const int rc = srt_resolve_ao_view(g->t[0]);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
+int srt_group_read_ao_view(srt_group *g, uint8_t *argb_out) {
+	if (!g || g->t.empty()) return SRT_ERR_INVALID;
+	if (!argb_out) return gfail(g, SRT_ERR_INVALID, "srt_group_read_ao_view: argb_out is NULL");
+	srt_tracer *t = g->t[0]; // (srt_read_argb would stop at the member's own rows: the view is the whole frame)
+	hipError_t e = hipSetDevice(t->device);
+	if (e == hipSuccess) e = hipMemcpyAsync(argb_out, t->argb.ptr, full_pixels(t) * 4, hipMemcpyDeviceToHost, t->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+	return e == hipSuccess ? SRT_OK : gfail(g, SRT_ERR_HIP, std::string("srt_group_read_ao_view: ") + hipGetErrorString(e));
+}
+
 int srt_group_get_counters(srt_group *g, srt_counters *out) {
 	if (!g || !out) return SRT_ERR_INVALID;
 	memset(out, 0, sizeof *out);

@@ -206,6 +206,20 @@ struct SelectionState {
 	void release() { bits.release(), table.release(), ids.release(), alpha.release(); }
 };
 
+// Ambient-occlusion pass (ao.hip; srt_render_ao): the surface records (two float4 per pixel) and the count plane of the last
+// pass with its frame and parameters, and the view's grey table on the device (uploaded when the sample count changes; its
+// host copy stays put between two such changes, which wait for the stream)
+struct AoState {
+	DevBuf<float> surfaces;
+	DevBuf<uint32_t> occluded;
+	int w = 0, h = 0; // of the last pass; 0: none yet
+	srt_ao_params p{};
+	uint8_t table_host[SRT_AO_MAX_SAMPLES + 1 + 3] = {};
+	DevBuf<uint8_t> table;
+	uint32_t table_samples = 0; // the sample count the device table was made for; 0: none
+	void release() { surfaces.release(), occluded.release(), table.release(); }
+};
+
 struct SrtCollect; // srt_collect.hip: RCCL communicator, gathered canvases, frame pipeline
 
 struct srt_tracer {
@@ -353,6 +367,7 @@ struct srt_tracer {
 	// call so far and laid out per call by query_stage.h, and the timers' span around the last query's launches
 	DevBuf<uint8_t> rq_stage;
 	TimedSpan rq_span;
+	AoState ao; // ao.hip
 	hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;
 	bool have_trace_ev = false, have_resolve_ev = false, have_kernel_ev = false;
 	std::string err;

@@ -404,6 +404,36 @@ class Tracer {
 		check(group ? srt_group_resolve_noise_view(group) : srt_resolve_noise_view(handle));
 		check(group ? srt_group_read_noise_view(group, output.data()) : srt_read_argb(handle, output.data()));
 	}
+	/// The ambient-occlusion pass for the camera and frame of `options` (srt_render_ao): per pixel, how many of `samples` hemisphere
+	/// rays from the visible surface meet anything within `radius`. A non-positive samples, radius or a negative bias keeps the
+	/// library's default (16, +inf, 0.001). Asynchronous; then read_ao() or resolve_ao_view().
+	void render_ao(int samples = 0, float radius = 0.0f, float bias = -1.0f, uint32_t seed = 0) {
+		srt_ao_params p;
+		check(srt_ao_defaults(&p));
+		if (samples > 0) p.samples = (uint32_t)samples;
+		if (radius > 0.0f) p.radius = radius;
+		if (bias >= 0.0f) p.bias = bias;
+		p.seed = seed;
+		const srt_render_data *rd = reinterpret_cast<const srt_render_data *>(&options);
+		check(group ? srt_group_render_ao(group, rd, &p) : srt_render_ao(handle, rd, &p));
+	}
+	/// The last pass's plane (resized): occluded rays per pixel, SRT_HIT_NONE where the pixel has no surface. Returns the pass's
+	/// sample count. Waits for the device.
+	int read_ao(std::vector<uint32_t> &occluded, int *w = nullptr, int *h = nullptr) {
+		int pw = 0, ph = 0, s = 0;
+		check(group ? srt_group_read_ao(group, nullptr, 0, &pw, &ph, &s) : srt_read_ao(handle, nullptr, 0, &pw, &ph, &s));
+		occluded.resize((size_t)pw * (size_t)ph);
+		check(group ? srt_group_read_ao(group, occluded.data(), occluded.size(), &pw, &ph, &s) : srt_read_ao(handle, occluded.data(), occluded.size(), &pw, &ph, &s));
+		if (w) *w = pw;
+		if (h) *h = ph;
+		return s;
+	}
+	/// The last pass as a grey picture into `output`, width*height*4 bytes (overwrites the handle's image). Waits for the device.
+	void resolve_ao_view(std::vector<uint8_t> &output) {
+		output.resize(size_t(options.width) * size_t(options.height) * 4);
+		check(group ? srt_group_resolve_ao_view(group) : srt_resolve_ao_view(handle));
+		check(group ? srt_group_read_ao_view(group, output.data()) : srt_read_argb(handle, output.data()));
+	}
 	/// Render until converged (srt_render_until): dispatches `options` with time + i * time_stride until a check converges or
 	/// max_dispatches are done, then resolves into `output`. Returns the dispatches done; `result` is the deciding check's.
 	/// Single-device tracers only.

@@ -79,12 +79,17 @@ SEGMENT = np.dtype({"names": ["from", "end_gap", "to", "reserved"], "formats": [
 SELECTION_PARAMS = np.dtype({"names": ["enabled", "outline_width", "outline_argb", "fill_argb", "reserved"],
                              "formats": [np.int32, np.float32, (np.uint8, 4), (np.uint8, 4), (np.int32, 4)], "offsets": [0, 4, 8, 12, 16], "itemsize": 32})
 SELECTION_MAX_WIDTH, SELECTION_TABLE_MAX = 8, 129
+# srt_ao_params (ambient-occlusion pass: Tracer.render_ao), 32 bytes; background is 0xAARRGGBB
+AO_PARAMS = np.dtype({"names": ["samples", "radius", "bias", "seed", "background", "reserved"],
+                      "formats": [np.uint32, np.float32, np.float32, np.uint32, np.uint32, (np.uint32, 3)], "offsets": [0, 4, 8, 12, 16, 20], "itemsize": 32})
+AO_MAX_SAMPLES = 64
 
 SHAPE_SPHERE, SHAPE_PLANE, SHAPE_MODEL = 0, 1, 2
 
 assert MATERIAL.itemsize == 64 and TRIANGLE.itemsize == 96 and SHAPE.itemsize == 128
 assert RENDER_DATA.itemsize == 112 and SCENE_DATA.itemsize == 96
 assert RAY.itemsize == 32 and RAY_HIT.itemsize == 32 and SEGMENT.itemsize == 32 and SELECTION_PARAMS.itemsize == 32
+assert AO_PARAMS.itemsize == 32
 
 
 def rays(origins, directions, tmax=np.inf):

@@ -38,6 +38,10 @@
 // --select I[,J...][:WIDTH[:RRGGBBAA]]: shapes I, J, ... are outlined in every frame (Tracer::set_selection): WIDTH pixels (1..8,
 //                default: the library's 2) in the colour RRGGBBAA (hex; default ffa000ff), over the finished bytes; whether the
 //                overlay ran is printed at the end
+// --ao S[:RADIUS[:BIAS]]: after the frames, the ambient-occlusion pass through the last frame's camera (Tracer::render_ao): S rays per
+//                pixel (1, 2, 4, ... 64) within RADIUS (default: no limit) from BIAS (default: the library's 0.001) above the
+//                surface; prints `ao: pixels P surfaces H mean M`, M the mean of occluded / S over the pixels with a surface
+// --ao-view f.ppm: the pass as a grey picture (Tracer::resolve_ao_view); needs --ao
 // --move DX: the camera moves by DX along x every frame and every frame clears the canvas, as the front-end does while moving
 // --move-shape I DX: with --temporal, shape I (a sphere, a plane or a model instance) moves by DX along x every frame and every
 //                frame clears the canvas, as the front-end does while a gizmo is dragged; turns object motion on
@@ -162,6 +166,9 @@ int main(int argc, char **argv) {
 	long noise_max = 1024;
 	int noise_permille = 0;
 	std::string noise_view;
+	int ao_samples = 0; // --ao
+	float ao_radius = 0.0f, ao_bias = -1.0f;
+	std::string ao_view;
 	float move = 0.0f, shape_move = 0.0f;
 	int move_shape = -1;
 	bool moving = false;
@@ -266,6 +273,25 @@ int main(int argc, char **argv) {
 			}
 		}
 		else if (a == "--noise-view") noise_view = next();
+		else if (a == "--ao") { // S[:RADIUS[:BIAS]]
+			const std::string v = next();
+			char *end = nullptr;
+			ao_samples = (int)std::strtol(v.c_str(), &end, 10);
+			bool ok = end != v.c_str() && ao_samples >= 1 && ao_samples <= 64 && (ao_samples & (ao_samples - 1)) == 0;
+			if (ok && *end == ':') {
+				ao_radius = std::strtof(end + 1, &end);
+				ok = ao_radius > 0.0f;
+				if (ok && *end == ':') {
+					ao_bias = std::strtof(end + 1, &end);
+					ok = ao_bias >= 0.0f && std::isfinite(ao_bias);
+				}
+			}
+			if (!ok || *end) {
+				std::cerr << "--ao takes S, S:RADIUS or S:RADIUS:BIAS; S one of 1, 2, 4, 8, 16, 32, 64, RADIUS > 0, BIAS >= 0\n";
+				return 2;
+			}
+		}
+		else if (a == "--ao-view") ao_view = next();
 		else if (a == "--select") { // I[,J...][:WIDTH[:RRGGBBAA]]
 			const std::string v = next();
 			const char *c = v.c_str();
@@ -315,7 +341,7 @@ int main(int argc, char **argv) {
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--select I[,J...][:WIDTH[:RRGGBBAA]]] [--pick X,Y]... [--line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP]]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
+			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--ao S[:RADIUS[:BIAS]]] [--ao-view f.ppm] [--select I[,J...][:WIDTH[:RRGGBBAA]]] [--pick X,Y]... [--line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP]]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
@@ -342,6 +368,10 @@ int main(int argc, char **argv) {
 	}
 	if (temporal && denoise < 0) {
 		std::cerr << "--temporal needs --denoise K\n";
+		return 2;
+	}
+	if (!ao_view.empty() && ao_samples == 0) {
+		std::cerr << "--ao-view needs --ao S\n";
 		return 2;
 	}
 	if ((until_noise || !noise_view.empty()) && gpus > 1) {
@@ -663,6 +693,21 @@ int main(int argc, char **argv) {
 		const srt_noise_result r = tracer.read_noise();
 		std::printf("noise-view: T = %u, P = %u: level %.6g (bin %d), %u of %u pixels below, %u left out\n", r.dispatches, r.samples, (double)r.level, r.level_bin, r.below,
 		            r.metered, r.left_out);
+	}
+	if (ao_samples > 0) { // (after the picture, as the noise view: the grey picture overwrites the handle's image)
+		tracer.render_ao(ao_samples, ao_radius, ao_bias);
+		std::vector<uint32_t> occluded;
+		const int s = tracer.read_ao(occluded);
+		size_t surfaces = 0;
+		double sum = 0.0;
+		for (uint32_t c : occluded)
+			if (c != SRT_HIT_NONE) surfaces++, sum += (double)c / (double)s;
+		std::printf("ao: pixels %zu surfaces %zu mean %.6f\n", occluded.size(), surfaces, surfaces ? sum / (double)surfaces : 0.0);
+		if (!ao_view.empty()) {
+			std::vector<uint8_t> grey;
+			tracer.resolve_ao_view(grey);
+			save_ppm(ao_view, grey, width, height);
+		}
 	}
 	if (!dump_prefix.empty()) {
 		std::vector<float> canvas;

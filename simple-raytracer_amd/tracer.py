@@ -78,6 +78,9 @@ ABI_SYMBOLS = [
     "srt_selection_defaults", "srt_selection_check_host", "srt_selection_sizes", "srt_selection_alpha_table_host", "srt_set_selection",
     "srt_group_set_selection", "srt_render_ids", "srt_read_id_pass", "srt_group_read_id_pass", "srt_read_selection_alpha",
     "srt_last_resolve_selected", "srt_group_last_resolve_selected",
+    "srt_ao_defaults", "srt_ao_check_host", "srt_ao_sizes", "srt_ao_table_host", "srt_render_ao", "srt_read_ao", "srt_ao_rays",
+    "srt_resolve_ao_view", "srt_group_render_ao", "srt_group_read_ao", "srt_group_ao_rays", "srt_group_resolve_ao_view",
+    "srt_group_read_ao_view",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -523,6 +526,37 @@ def selection_alpha_table_host(**kw):
     return table[:2 * radius.value ** 2 + 1].copy(), radius.value
 
 
+def _ao_params(kw, who):
+    """srt_ao_defaults() overridden by kw (samples, radius, bias, seed, background = 0xAARRGGBB) -> a records.AO_PARAMS record."""
+    d = np.zeros((), R.AO_PARAMS)
+    if load_library().srt_ao_defaults(_ptr(d)):
+        raise SrtError("srt_ao_defaults failed")
+    for k, v in kw.items():
+        if k not in R.AO_PARAMS.names:
+            raise TypeError(f"{who}: unknown parameter {k}")
+        d[k] = v
+    return d
+
+
+def ao_defaults():
+    """srt_ao_defaults (host only, no GPU needed) as a records.AO_PARAMS record."""
+    return _ao_params({}, "ao_defaults")
+
+
+def ao_check_host(width, height, **kw):
+    """srt_ao_check_host of the defaults overridden by kw for a frame of width x height (host only): True when srt_render_ao
+    would accept them."""
+    return load_library().srt_ao_check_host(_ptr(_ao_params(kw, "ao_check_host")), int(width), int(height)) == 0
+
+
+def ao_table(**kw):
+    """srt_ao_table_host of the defaults overridden by kw (host only) -> the samples + 1 grey levels of the view, uint8."""
+    p, table = _ao_params(kw, "ao_table"), np.zeros(R.AO_MAX_SAMPLES + 1, np.uint8)
+    if load_library().srt_ao_table_host(_ptr(p), _ptr(table)):
+        raise SrtError("srt_ao_table_host refused the parameters")
+    return table[:int(p["samples"]) + 1].copy()
+
+
 class NoiseParams(C.Structure):
     """include/srt_types.h srt_noise_params"""
     _fields_ = [("enable", C.c_int32), ("threshold", C.c_float), ("luminance_floor", C.c_float), ("permille", C.c_int32),
@@ -879,6 +913,20 @@ def _bind(lib):
         lib.srt_read_selection_alpha.argtypes = [vp, vp, sz]
         sizes = (sz * 1)()
         assert lib.srt_selection_sizes(sizes) == 0 and sizes[0] == R.SELECTION_PARAMS.itemsize, tuple(sizes)
+    if hasattr(lib, "srt_render_ao"):  # (likewise)
+        ip = C.POINTER(C.c_int)
+        lib.srt_ao_defaults.argtypes = [vp]
+        lib.srt_ao_check_host.argtypes = [vp, C.c_int, C.c_int]
+        lib.srt_ao_table_host.argtypes = [vp, vp]
+        lib.srt_ao_sizes.argtypes = [C.POINTER(sz)]
+        for pre in ("srt_", "srt_group_"):
+            getattr(lib, pre + "render_ao").argtypes = [vp, vp, vp]
+            getattr(lib, pre + "read_ao").argtypes = [vp, vp, sz, ip, ip, ip]
+            getattr(lib, pre + "ao_rays").argtypes = [vp, vp, vp, sz, sz, vp]
+            getattr(lib, pre + "resolve_ao_view").argtypes = [vp]
+        lib.srt_group_read_ao_view.argtypes = [vp, vp]
+        sizes = (sz * 1)()
+        assert lib.srt_ao_sizes(sizes) == 0 and sizes[0] == R.AO_PARAMS.itemsize, tuple(sizes)
     return lib
 
 
@@ -1181,7 +1229,42 @@ class _Selection:
         return bool(a.value), bool(r.value)
 
 
-class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection):
+class _AmbientOcclusion:
+    """The ambient-occlusion pass (include/srt_abi.h "ambient-occlusion pass"), shared by Tracer and TracerGroup (the group: on
+    its first member, which holds the whole scene). kw: srt_ao_defaults() overridden (samples, radius, bias, seed, background)."""
+
+    def render_ao(self, options=None, **kw):
+        """The pass for the camera and frame size of options (default: self.options), asynchronous; then read_ao()."""
+        rd = R.as_records(self.options if options is None else options, R.RENDER_DATA)
+        self._check(self._dn("render_ao", _ptr(rd), _ptr(_ao_params(kw, "render_ao"))))
+
+    def read_ao(self):
+        """The last pass's plane -> ((h, w) uint32: occluded rays per pixel, records.HIT_NONE without a surface; samples).
+        Waits for the stream."""
+        w, h, s = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self._dn("read_ao", None, 0, C.byref(w), C.byref(h), C.byref(s)))
+        out = np.zeros((h.value, w.value), np.uint32)
+        self._check(self._dn("read_ao", _ptr(out), out.size, C.byref(w), C.byref(h), C.byref(s)))
+        return out, s.value
+
+    def ao_rays(self, options=None, first=0, n=None, **kw):
+        """The rays the pass casts for pixels first .. first + n of the frame (default: all of it) -> records.RAY array of
+        n * samples, ray (q, s) at (q - first) * samples + s; tmax = NaN where the pixel has no surface. Blocking."""
+        rd = R.as_records(self.options if options is None else options, R.RENDER_DATA)
+        p = _ao_params(kw, "ao_rays")
+        n = int(rd["width"]) * int(rd["height"]) - first if n is None else n
+        rays = np.zeros(max(n, 0) * int(p["samples"]), R.RAY)
+        self._check(self._dn("ao_rays", _ptr(rd), _ptr(p), first, n, _ptr(rays) if len(rays) else None))
+        return rays
+
+    def resolve_ao_view(self):
+        """Overwrite the ARGB image with the last pass's grey picture; asynchronous (Tracer: read_argb; a group: read_ao_view)."""
+        self._check(self._dn("resolve_ao_view"))
+
+    ao_table = staticmethod(ao_table)
+
+
+class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection, _AmbientOcclusion):
     """Mirror of the reference's `class Tracer`. Field and method names are the
     reference's; records are numpy scalars of records.RENDER_DATA / SCENE_DATA."""
 
@@ -1670,7 +1753,7 @@ class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection):
         self.owned_rows = self.lib.srt_partition_owned_rows(self.height, rank, world, rows_per_block)
 
 
-class TracerGroup(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection):
+class TracerGroup(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection, _AmbientOcclusion):
     """One process driving several GPUs (srt_group_*): the reference's Tracer interface over a row partition,
     collected with one ncclGather per frame."""
 
@@ -1791,6 +1874,12 @@ class TracerGroup(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection):
         """Trace on every member, collect and unpermute on the first device; asynchronous (then resolve_denoised)."""
         rd = R.as_records(self.options, R.RENDER_DATA)
         self._check(self.lib.srt_group_trace_and_gather(self._g, _ptr(rd)))
+
+    def read_ao_view(self):
+        """(height, width, 4) uint8: the grey picture resolve_ao_view wrote on the first device. Waits for its stream."""
+        out = np.zeros((self.height, self.width, 4), np.uint8)
+        self._check(self.lib.srt_group_read_ao_view(self._g, _ptr(out)))
+        return out
 
     def read_noise_view(self):
         """(height, width, 4) uint8: the heat map resolve_noise_view wrote on the first device. Waits for its stream."""

@@ -1,0 +1,92 @@
+"""What the ambient-occlusion tests share (tests/test_ao_host.py, tests/test_gpu_ao.py): the two frames, the scenes' cameras,
+the definitions of include/srt_abi.h "ambient-occlusion pass" restated in numpy (the grey table, the view's bytes, the pixel
+centres' directions in float64) and the bound on a ray's origin. A plain module, not a test module."""
+import numpy as np
+
+from ray_query_cases import ACCELS, CAMERAS, frame_rd, o_hits, scene  # noqa: F401 (re-exported)
+from simple_raytracer_amd import records as R
+
+F = np.float32
+U = 2.0 ** -24  # half an ulp of a float in [1, 2): the relative error of one rounding
+# 24 x 16: six full waves of pixels. 13 x 7: 91 pixels, so that 91 S is no multiple of 64 for any S of the pass and the last wave
+# is partial for every sample count
+FRAMES = ((24, 16), (13, 7))
+SAMPLES = (1, 2, 4, 8, 16, 32, 64)
+HIT_NONE = 0xFFFFFFFF
+# scene -> (camera, fov): the sphere scene from the ray-query tests' second camera, which sees the sky beside the spheres, and
+# the smooth meshes from close by (ray_query_cases.close_mesh's camera). Chosen with the oracle on the CPU so that at least
+# half of each frame's pixels have a surface and at least one has none: tests/test_ao_host.py asserts it, the GPU tests assert
+# it again for the pixel centres
+VIEWS = {"spheres": (CAMERAS["spheres"][1], 1.0), "mesh_smooth": (R.camera_matrix((0.0, 0.3, 2.0), 0.0, 0.0), 0.5)}
+CASES = [(n, a) for n in VIEWS for a in ACCELS[n]]
+
+
+def rd(name, w, h):
+    cam, fov = VIEWS[name]
+    return frame_rd(cam, w, h, 1, fov=fov)
+
+
+def centres(w, h):
+    """xy of every pixel's centre, in pixel order"""
+    q = np.arange(w * h)
+    return np.stack([(q % w) + 0.5, (q // w) + 0.5], axis=1).astype(F)
+
+
+def table(samples):
+    """table[c] = floor(255 (1 - c / S) + 0.5), c = 0 .. S, in double"""
+    c = np.arange(samples + 1, dtype=np.float64)
+    return np.floor(255.0 * (1.0 - c / float(samples)) + 0.5).astype(np.uint8)
+
+
+def view_bytes(occluded, samples, background=0xFF000000):
+    """(h, w, 4) uint8, bytes A, R, G, B: 255 and the grey of the count; the bytes of background = 0xAARRGGBB without a surface"""
+    occ = np.asarray(occluded)
+    out = np.zeros(occ.shape + (4,), np.uint8)
+    none = occ == HIT_NONE
+    grey = table(samples)[np.where(none, 0, occ)]
+    out[..., 0] = 255
+    out[..., 1] = out[..., 2] = out[..., 3] = grey
+    out[none] = [(background >> 24) & 255, (background >> 16) & 255, (background >> 8) & 255, background & 255]
+    return out
+
+
+def centre_dirs64(rdata):
+    """the unit directions of the pixel centres' rays with every step of the camera set-up in float64, from the float32 inputs"""
+    w, h = int(rdata["width"]), int(rdata["height"])
+    xy = centres(w, h).astype(np.float64)
+    cam = np.asarray(rdata["camera_to_world"], np.float64).reshape(4, 4)
+    aspect, fov = float(rdata["aspect_ratio"]), float(rdata["fov_scale"])
+    sx = (2.0 * xy[:, 0] / w - 1.0) * aspect * fov
+    sy = (1.0 - 2.0 * xy[:, 1] / h) * fov
+    v = sx[:, None] * cam[0, :3] + sy[:, None] * cam[1, :3] - cam[2, :3]
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+# The bound on a ray's origin, per component, against  cam + dir64 t + N bias  in float64 (t, N: the pick's float32 values, the
+# same on both sides). With u = 2^-24, every float32 operation rounds its exact result by at most u times its magnitude.
+#   The float32 direction. ndc = xy / size is correctly rounded (u); 2 ndc - 1 adds one rounding of a value <= 1 (2 ndc is
+#   exact): <= 3 u absolute. Times aspect and fov, one rounding each: sx, sy are off by <= 3 u A + 2 u |s| <= 5 u A with
+#   A = max(1, aspect fov) >= |sx|, |sy|. A component of v = c0 sx + c1 sy - c2 (the columns' entries are <= 1 in magnitude, the
+#   products with the exact column entries carry the errors of sx, sy over: <= 10 u A) takes three products (u each, <= A) and
+#   two sums (u each, of partial sums <= 2 A + 1): <= 3 u A + 2 u (2 A + 1). Together <= (17 A + 2) u absolute, on a vector of
+#   length >= 1; dividing by that length does not enlarge it. normalize3 itself: the squared length by one product and two fmas
+#   (3 u), the reciprocal root (detmath's, within 2 u), one product per component (u): <= 3 u / 2 + 2 u + u <= 5 u relative, on
+#   a component <= 1. So  |dir32 - dir64| <= E_DIR u  per component with  E_DIR = 17 A + 7.
+#   The three adds and multiplies. dir t: u |dir t| <= u t. cam + (dir t): u (|cam| + t). N bias: u bias. The last sum:
+#   u (|cam| + t + bias). Together with t |dir32 - dir64|:
+#       |O32 - O64| <= u ((E_DIR + 1) t + 2 (|cam| + t) + 2 bias) <= (E_DIR + 3) u (|cam| + t) + 2 u bias
+#   with |cam| the largest camera coordinate in magnitude.
+def origin_bound(rdata, t, bias):
+    aspect_fov = max(1.0, float(rdata["aspect_ratio"]) * float(rdata["fov_scale"]))
+    e_dir = 17.0 * aspect_fov + 7.0
+    cam = float(np.abs(np.asarray(rdata["camera_to_world"], np.float64).reshape(4, 4)[3, :3]).max())
+    return (e_dir + 3.0) * U * (cam + np.asarray(t, np.float64)) + 2.0 * U * float(bias)
+
+
+def tangents(normals):
+    """two unit vectors across each normal, in float64"""
+    n = np.asarray(normals, np.float64)
+    axis = np.where((np.abs(n[:, 0]) < 0.9)[:, None], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0])
+    t1 = np.cross(n, axis)
+    t1 /= np.linalg.norm(t1, axis=1, keepdims=True)
+    return t1, np.cross(n, t1)
