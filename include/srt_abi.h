@@ -1122,6 +1122,80 @@ int srt_last_ray_query_ms(srt_tracer *t, float *ms);
 /* Host-only: out = {sizeof(srt_ray), sizeof(srt_ray_hit)} as the library was built. */
 int srt_ray_query_sizes(size_t out[2]);
 
+/* ---- nearest-surface queries (new): the closest scene point to caller points ------------------------------------------------ */
+
+/* For each of n points, the closest point of the handle's scene and how far away it is: snapping a dragged object or a gizmo
+ * handle to the nearest face, edge or vertex, clearance checks ("is anything within 0.2 of here"), dropping an object onto
+ * whatever is nearest, baking a distance field. Records: srt_point_query, srt_nearest (srt_types.h).
+ *
+ * THE ANSWER IS A MINIMUM OVER PRIMITIVES, so it does not depend on how the scene is traversed. A primitive is every sphere,
+ * every plane and every triangle of every model of the scene the last srt_update_scene left (a model's triangles are searched
+ * where its record's bounding box, which the caller supplies, says they are: as the cast trusts it). Each has ONE distance
+ * function, below; the record reports the primitive with the smallest `distance`, compared as a float:
+ *   - ties go to the lower shape index, then to the lower triangle index inside the model;
+ *   - a primitive is taken only when distance < max_distance, strictly, as the cast treats tmax;
+ *   - a NaN distance is never taken: a non-finite or collinear triangle may give one, a plane with a zero or non-finite normal
+ *     does;
+ *   - skip_shape (per call; SRT_HIT_NONE: none) is left out entirely: usually the object being dragged, which would always be
+ *     its own nearest.
+ * The array scan, the host's SAH hierarchy, the device-built Morton and median hierarchies and a refitted hierarchy therefore
+ * give the same 32 bytes.
+ * ARITHMETIC. float32, every product, sum, difference, IEEE quotient and correctly rounded square root rounded by itself
+ * (nothing fused), in the order written. dot3(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z; cross(a, b) = (a.y * b.z - a.z * b.y,
+ * a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); vector forms are per component. q is the query point. One implementation,
+ * csrc/nearest_math.h, is compiled into the kernels and into the host exports below.
+ *   Sphere (centre c, r = |radius|): v = q - c, len = sqrt(dot3(v, v)), distance = |len - r|. point = c + v * (r / len) when
+ *     len > 0, else c + (r, 0, 0). BACK when len < r. Feature 0.
+ *   Plane (p, n as stored, not assumed unit): nn = dot3(n, n), k = dot3(q - p, n), distance = |k / sqrt(nn)|,
+ *     point = q - n * (k / nn). BACK when k < 0. Feature 0.
+ *   Triangle, over the pre-pass's world record {v0, e1, e2} (the bits the kernels hold; v1 and v2 are NOT recomputed from model
+ *     space): Ericson's closest point on a triangle (Real-Time Collision Detection 5.1.5) with a = v0, ab = e1, ac = e2:
+ *       ap = q - a, bp = ap - e1, cp = ap - e2,
+ *       d1 = dot3(ab, ap), d2 = dot3(ac, ap), d3 = dot3(ab, bp), d4 = dot3(ac, bp), d5 = dot3(ab, cp), d6 = dot3(ac, cp),
+ *       vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+ *     the first region of this list that holds is taken, and its number is the feature code:
+ *       1  vertex v0:  d1 <= 0 and d2 <= 0                          point = a
+ *       2  vertex v1:  d3 >= 0 and d4 <= d3                         point = a + e1
+ *       4  edge v0v1:  vc <= 0 and d1 >= 0 and d3 <= 0              point = a + e1 * (d1 / (d1 - d3))
+ *       3  vertex v2:  d6 >= 0 and d5 <= d6                         point = a + e2
+ *       5  edge v0v2:  vb <= 0 and d2 >= 0 and d6 <= 0              point = a + e2 * (d2 / (d2 - d6))
+ *       6  edge v1v2:  va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0    point = (a + e1) + (e2 - e1) * ((d4 - d3) / ((d4 - d3) + (d5 - d6)))
+ *       0  the face:   otherwise; denom = 1 / ((va + vb) + vc)      point = (a + e1 * (vb * denom)) + e2 * (vc * denom)
+ *     distance = sqrt(dot3(q - point, q - point)). BACK when dot3(q - point, cross(e1, e2)) < 0. A triangle whose e1 and e2 are
+ *     both zero is its vertex v0.
+ * THE RECORD.
+ *   - found: distance, shape (the index srt_update_scene was given), triangle (inside its model; SRT_HIT_NONE for a sphere or a
+ *     plane), point, flags = SRT_NEAREST_FOUND | SRT_NEAREST_BACK if so | feature << SRT_NEAREST_FEATURE_SHIFT;
+ *   - material: the cast's rule: the per-triangle index where srt_set_triangle_materials gave one that is not -1, else the
+ *     shape's; a shape WITHOUT a material (index < 0) IS REPORTED, with material = -1;
+ *   - nothing within max_distance: distance = +inf, shape = triangle = SRT_HIT_NONE, material = -1, a zero point, flags 0.
+ * HOSTILE QUERIES, decided on the device. A non-finite point component or a NaN max_distance: the nothing record with
+ * SRT_NEAREST_INVALID, and the scene is not traversed. max_distance <= 0 (-0 and -inf included): a valid nothing record, not
+ * traversed. No query makes the walk run on or read outside the scene's buffers, and the call still returns SRT_OK. Before any
+ * scene is set every query finds nothing.
+ * STATE. A query reads the scene as the last srt_update_scene left it, ordered on the handle's stream behind the pre-pass,
+ * refit and build that update enqueued: a query after a device refit sees the refitted boxes. It writes nothing but its outputs
+ * and the queries' shared staging allocation (bringing the per-triangle material table up to date, as the cast does, aside):
+ * canvas, counters, denoiser planes, exposure and noise state stay as they were, and so does every srt_last_trace_* answer.
+ * srt_last_ray_query_ms covers the launch.
+ * COUNTS AND ERRORS. n == 0: SRT_OK, no launch. A null pointer with n > 0, n >= 2^31, a device pointer not aligned to 16 bytes,
+ * a skip_shape that is neither SRT_HIT_NONE nor below the scene's shape count: SRT_ERR_INVALID.
+ *
+ * srt_nearest_points: host arrays, blocking. srt_nearest_points_device: n srt_point_query / n srt_nearest in device memory of the
+ * handle's device, each 16-byte aligned, asynchronous on the handle's stream. srt_group_nearest_points: on the group's first
+ * member (every member holds the scene). */
+int srt_nearest_points(srt_tracer *t, const srt_point_query *queries, size_t n, uint32_t skip_shape, srt_nearest *out);
+int srt_nearest_points_device(srt_tracer *t, const void *queries_dev, size_t n, uint32_t skip_shape, void *out_dev);
+int srt_group_nearest_points(srt_group *g, const srt_point_query *queries, size_t n, uint32_t skip_shape, srt_nearest *out);
+/* Host-only, no device and no handle: the three distance functions as the kernels compile them (csrc/nearest_math.h). wtri: a
+ * world record {v0, e1, e2}; *flags: SRT_NEAREST_BACK if so | feature << SRT_NEAREST_FEATURE_SHIFT (never FOUND: that is the
+ * minimum's word). SRT_ERR_INVALID for a NULL argument. */
+int srt_nearest_triangle_host(const float wtri[9], const float q[3], float *distance, float point[3], uint32_t *flags);
+int srt_nearest_sphere_host(const float centre[3], float radius, const float q[3], float *distance, float point[3], uint32_t *flags);
+int srt_nearest_plane_host(const float position[3], const float normal[3], const float q[3], float *distance, float point[3], uint32_t *flags);
+/* Host-only: out = {sizeof(srt_point_query), sizeof(srt_nearest)} as the library was built. */
+int srt_nearest_sizes(size_t out[2]);
+
 /* ---- occlusion queries (new): any-hit rays and segments with early exit ---------------------------------------------------- */
 
 /* Is anything in the handle's scene closer than tmax along each of n rays -- is B visible from A, does a place have a clear

@@ -274,6 +274,26 @@ typedef struct srt_ao_params {
 	uint32_t reserved[3]; /* must be 0 */
 } srt_ao_params;
 
+/* Nearest-surface queries (srt_nearest_points; include/srt_abi.h "nearest-surface queries"). The query is 16 bytes, one 128-bit
+ * load on the device; the answer 32 bytes, two 128-bit stores. */
+typedef struct srt_point_query {
+	float point[3];
+	float max_distance; /* the surface must be closer than this, strictly; +inf allowed */
+} srt_point_query;
+typedef struct srt_nearest {
+	float distance;    /* +inf: nothing within max_distance */
+	uint32_t shape;    /* index into srt_update_scene's shapes; SRT_HIT_NONE: nothing */
+	uint32_t triangle; /* index inside its model; SRT_HIT_NONE: a sphere, a plane, nothing */
+	int32_t material;  /* the cast's rule; -1: nothing, or a shape without one */
+	float point[3];    /* the closest point on the surface; 0 for nothing */
+	uint32_t flags;    /* SRT_NEAREST_* | feature << SRT_NEAREST_FEATURE_SHIFT */
+} srt_nearest;
+#define SRT_NEAREST_FOUND 1u
+#define SRT_NEAREST_BACK 2u    /* the query point is behind the surface: inside a sphere, under a plane, behind a triangle's cross(e1, e2) */
+#define SRT_NEAREST_INVALID 4u /* a non-finite point component or a NaN max_distance: not traversed */
+#define SRT_NEAREST_FEATURE_SHIFT 8 /* bits 8..10: 0 the face, 1/2/3 vertex v0/v1/v2, 4/5/6 edge v0v1 / v0v2 / v1v2; spheres and planes 0 */
+#define SRT_NEAREST_FEATURE_MASK 0x700u
+
 #ifdef __cplusplus
 }
 #endif
@@ -356,5 +376,11 @@ SRT_STATIC_ASSERT(offsetof(srt_selection_params, outline_argb) == 8, "SelectionP
 SRT_STATIC_ASSERT(offsetof(srt_selection_params, reserved) == 16, "SelectionParams.reserved@16");
 SRT_STATIC_ASSERT(sizeof(srt_ao_params) == 32, "AoParams 32 B");
 SRT_STATIC_ASSERT(offsetof(srt_ao_params, background) == 16, "AoParams.background@16");
+SRT_STATIC_ASSERT(sizeof(srt_point_query) == 16, "PointQuery 16 B");
+SRT_STATIC_ASSERT(offsetof(srt_point_query, max_distance) == 12, "PointQuery.max_distance@12");
+SRT_STATIC_ASSERT(sizeof(srt_nearest) == 32, "Nearest 32 B");
+SRT_STATIC_ASSERT(offsetof(srt_nearest, material) == 12, "Nearest.material@12");
+SRT_STATIC_ASSERT(offsetof(srt_nearest, point) == 16, "Nearest.point@16");
+SRT_STATIC_ASSERT(offsetof(srt_nearest, flags) == 28, "Nearest.flags@28");
 
 #endif /* SRT_TYPES_H */

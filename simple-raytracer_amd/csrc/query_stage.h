@@ -7,6 +7,9 @@
 //                   segs      n srt_segment (srt_occluded_segments, srt_segment_rays) | no call has hits and segments
 //   [64 n, ...)     xy        n points of 8 bytes (srt_pick)            | the same bytes:
 //                   occluded, invalid   ceil(n / 64) words of 8 bytes each (srt_occluded_rays, srt_occluded_segments) | no call has points and masks
+// srt_nearest_points (nearest.hip) uses the first two regions under names of its own (NearestStage below):
+//   [0, 16 n)       points    n srt_point_query: half of `rays`
+//   [32 n, 64 n)    nearest   n srt_nearest: the bytes of `hits`
 #ifndef SRT_QUERY_STAGE_H
 #define SRT_QUERY_STAGE_H
 
@@ -43,6 +46,17 @@ static inline QueryStage query_stage(size_t n) { // n < 2^31 (the calls' own che
 	s.invalid = s.occluded + mask;
 	s.total = 64 * n + (8 * n > 2 * mask ? 8 * n : 2 * mask);
 	return s;
+}
+
+struct NearestStage {
+	size_t points, nearest; // byte offsets inside query_stage(n).total
+};
+static inline NearestStage nearest_stage(size_t n) {
+	const QueryStage s = query_stage(n);
+	NearestStage ns;
+	ns.points = s.rays;
+	ns.nearest = s.hits;
+	return ns;
 }
 
 #endif

@@ -978,6 +978,13 @@ int srt_group_pick(srt_group *g, const srt_render_data *options, const float *xy
 	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
 }
 
+// nearest-surface queries (nearest.hip), likewise
+int srt_group_nearest_points(srt_group *g, const srt_point_query *queries, size_t n, uint32_t skip_shape, srt_nearest *out) {
+	if (!g || g->t.empty()) return SRT_ERR_INVALID;
+	const int rc = srt_nearest_points(g->t[0], queries, n, skip_shape, out);
+	return rc == SRT_OK ? SRT_OK : gfail(g, rc, srt_last_error(g->t[0]));
+}
+
 // occlusion queries (occlusion.hip), likewise
 int srt_group_occluded_rays(srt_group *g, const srt_ray *rays, size_t n, uint32_t flags, uint64_t *occluded, uint64_t *invalid) {
 	if (!g || g->t.empty()) return SRT_ERR_INVALID;

@@ -490,6 +490,17 @@ class Tracer {
 		return hits;
 	}
 	srt_ray_hit pick(float x, float y) { return pick(std::vector<float>{x, y})[0]; }
+	/// Nearest-surface queries (srt_nearest_points): the closest scene point to each query point, closer than its max_distance
+	/// -- what snapping and clearance checks ask. skip_shape: a shape left out (the one being dragged). Blocking.
+	std::vector<srt_nearest> nearest(const std::vector<srt_point_query> &queries, uint32_t skip_shape = SRT_HIT_NONE) {
+		std::vector<srt_nearest> out(queries.size());
+		check(group ? srt_group_nearest_points(group, queries.data(), queries.size(), skip_shape, out.data())
+		            : srt_nearest_points(handle, queries.data(), queries.size(), skip_shape, out.data()));
+		return out;
+	}
+	srt_nearest nearest(float x, float y, float z, float max_distance = INFINITY, uint32_t skip_shape = SRT_HIT_NONE) {
+		return nearest(std::vector<srt_point_query>{srt_point_query{{x, y, z}, max_distance}}, skip_shape)[0];
+	}
 	/// Occlusion queries (srt_occluded_rays): is anything closer than tmax along each ray -- true exactly where cast_rays would
 	/// report a hit, without looking for the closest one. invalid (optional): the rays the device refused. Blocking.
 	std::vector<bool> occluded(const std::vector<srt_ray> &rays, bool unit_directions = false, std::vector<bool> *invalid = nullptr) {

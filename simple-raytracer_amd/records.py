@@ -83,6 +83,12 @@ SELECTION_MAX_WIDTH, SELECTION_TABLE_MAX = 8, 129
 AO_PARAMS = np.dtype({"names": ["samples", "radius", "bias", "seed", "background", "reserved"],
                       "formats": [np.uint32, np.float32, np.float32, np.uint32, np.uint32, (np.uint32, 3)], "offsets": [0, 4, 8, 12, 16, 20], "itemsize": 32})
 AO_MAX_SAMPLES = 64
+# srt_point_query / srt_nearest (nearest-surface queries: Tracer.nearest_points), 16 and 32 bytes
+POINT_QUERY = np.dtype({"names": ["point", "max_distance"], "formats": [F3, np.float32], "offsets": [0, 12], "itemsize": 16})
+NEAREST = np.dtype({"names": ["distance", "shape", "triangle", "material", "point", "flags"],
+                    "formats": [np.float32, np.uint32, np.uint32, np.int32, F3, np.uint32], "offsets": [0, 4, 8, 12, 16, 28], "itemsize": 32})
+NEAREST_FOUND, NEAREST_BACK, NEAREST_INVALID = 1, 2, 4
+NEAREST_FEATURE_SHIFT, NEAREST_FEATURE_MASK = 8, 0x700
 
 SHAPE_SPHERE, SHAPE_PLANE, SHAPE_MODEL = 0, 1, 2
 
@@ -111,6 +117,15 @@ def segments(start, to, end_gap=0.0):
     s["from"], s["to"] = a, b
     s["end_gap"] = np.asarray(end_gap, np.float32)
     return s
+
+
+def point_queries(points, max_distance=np.inf):
+    """POINT_QUERY records from (n, 3) or (3,) points and a scalar or (n,) max_distance."""
+    p = np.atleast_2d(np.asarray(points, np.float32))
+    q = np.zeros(len(p), POINT_QUERY)
+    q["point"] = p
+    q["max_distance"] = np.asarray(max_distance, np.float32)
+    return q
 
 
 def mask_bits(words, n):

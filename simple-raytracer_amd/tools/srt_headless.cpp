@@ -32,6 +32,9 @@
 // --pick X,Y (may be given several times): after the scene is loaded, the hit under the image point (X, Y) -- continuous pixel
 //                coordinates, a pixel's centre is (px + 0.5, py + 0.5) -- through the first frame's camera (Tracer::pick); one line
 //                per pick: shape, triangle, material (-1: none), t, position, normal. Then the frames render as before.
+// --nearest X,Y,Z[:RADIUS[:SKIP]] (may be given several times): the closest surface to the world point within RADIUS (default:
+//                any distance), shape SKIP left out (Tracer::nearest); one line each: shape, triangle, material, distance, the
+//                closest point, the feature it lies on (face, vertexN, edgeNM) and the side (front / back).
 // --line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP] (may be given several times): after the scene is loaded, is the point GAP (default 0)
 //                short of (X1, Y1, Z1) visible from (X0, Y0, Z0) (Tracer::occluded); one line per question: `visible`, `occluded`
 //                or `invalid`. Then the frames render as before.
@@ -176,6 +179,8 @@ int main(int argc, char **argv) {
 	uint32_t bvh_build_min = 0;
 	int bvh_order = SRT_BUILD_ORDER_MORTON;
 	std::vector<float> picks; // --pick X,Y: x0, y0, x1, y1, ...
+	std::vector<srt_point_query> nearests; // --nearest X,Y,Z[:RADIUS[:SKIP]]
+	std::vector<uint32_t> nearest_skips;   // ... its SKIP (SRT_HIT_NONE: none)
 	std::vector<srt_segment> sights; // --line-of-sight
 	for (int i = 1; i < argc; i++) {
 		std::string a = argv[i];
@@ -328,6 +333,15 @@ int main(int argc, char **argv) {
 			}
 			picks.push_back(x), picks.push_back(y);
 		}
+		else if (a == "--nearest") { // X,Y,Z[:RADIUS[:SKIP]]
+			srt_point_query pq{{0.f, 0.f, 0.f}, INFINITY};
+			unsigned skip = SRT_HIT_NONE;
+			if (std::sscanf(next(), "%f,%f,%f:%f:%u", &pq.point[0], &pq.point[1], &pq.point[2], &pq.max_distance, &skip) < 3) {
+				std::cerr << "--nearest takes X,Y,Z[:RADIUS[:SKIP]]\n";
+				return 2;
+			}
+			nearests.push_back(pq), nearest_skips.push_back(skip);
+		}
 		else if (a == "--line-of-sight") { // X0,Y0,Z0:X1,Y1,Z1[:GAP]
 			srt_segment sg{};
 			if (std::sscanf(next(), "%f,%f,%f:%f,%f,%f:%f", &sg.from[0], &sg.from[1], &sg.from[2], &sg.to[0], &sg.to[1], &sg.to[2], &sg.end_gap) < 6) {
@@ -341,7 +355,7 @@ int main(int argc, char **argv) {
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--ao S[:RADIUS[:BIAS]]] [--ao-view f.ppm] [--select I[,J...][:WIDTH[:RRGGBBAA]]] [--pick X,Y]... [--line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP]]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
+			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--ao S[:RADIUS[:BIAS]]] [--ao-view f.ppm] [--select I[,J...][:WIDTH[:RRGGBBAA]]] [--pick X,Y]... [--nearest X,Y,Z[:RADIUS[:SKIP]]]... [--line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP]]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
@@ -607,6 +621,22 @@ int main(int argc, char **argv) {
 			std::printf("pick %g,%g: shape %u triangle %d material %d t %.9g position %.9g %.9g %.9g normal %.9g %.9g %.9g\n", picks[2 * k], picks[2 * k + 1],
 			            h.shape, h.triangle == SRT_HIT_NONE ? -1 : (int)h.triangle, h.material, h.t, r.origin[0] + r.direction[0] * h.t,
 			            r.origin[1] + r.direction[1] * h.t, r.origin[2] + r.direction[2] * h.t, h.normal[0], h.normal[1], h.normal[2]);
+		}
+	}
+
+	if (!nearests.empty()) { // --nearest: the closest surface to these points, answered without rendering
+		tracer.update_scene(shapes, triangles, materials.list);
+		static const char *const features[7] = {"face", "vertex0", "vertex1", "vertex2", "edge01", "edge02", "edge12"};
+		for (size_t k = 0; k < nearests.size(); k++) {
+			const srt_point_query &pq = nearests[k];
+			const srt_nearest r = tracer.nearest(std::vector<srt_point_query>{pq}, nearest_skips[k])[0];
+			if (!(r.flags & SRT_NEAREST_FOUND)) {
+				std::printf("nearest %g,%g,%g: %s\n", pq.point[0], pq.point[1], pq.point[2], (r.flags & SRT_NEAREST_INVALID) ? "invalid" : "nothing");
+				continue;
+			}
+			std::printf("nearest %g,%g,%g: shape %u triangle %d material %d distance %.9g point %.9g %.9g %.9g %s %s\n", pq.point[0], pq.point[1], pq.point[2],
+			            r.shape, r.triangle == SRT_HIT_NONE ? -1 : (int)r.triangle, r.material, r.distance, r.point[0], r.point[1], r.point[2],
+			            features[(r.flags & SRT_NEAREST_FEATURE_MASK) >> SRT_NEAREST_FEATURE_SHIFT], (r.flags & SRT_NEAREST_BACK) ? "back" : "front");
 		}
 	}
 

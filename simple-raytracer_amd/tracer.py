@@ -81,6 +81,8 @@ ABI_SYMBOLS = [
     "srt_ao_defaults", "srt_ao_check_host", "srt_ao_sizes", "srt_ao_table_host", "srt_render_ao", "srt_read_ao", "srt_ao_rays",
     "srt_resolve_ao_view", "srt_group_render_ao", "srt_group_read_ao", "srt_group_ao_rays", "srt_group_resolve_ao_view",
     "srt_group_read_ao_view",
+    "srt_nearest_points", "srt_nearest_points_device", "srt_group_nearest_points", "srt_nearest_triangle_host", "srt_nearest_sphere_host",
+    "srt_nearest_plane_host", "srt_nearest_sizes",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -899,6 +901,16 @@ def _bind(lib):
         lib.srt_occlusion_sizes.argtypes = [C.POINTER(sz)]
         sizes = (sz * 2)()
         assert lib.srt_occlusion_sizes(sizes) == 0 and (sizes[0], sizes[1]) == (R.SEGMENT.itemsize, 8), tuple(sizes)
+    if hasattr(lib, "srt_nearest_points"):  # (likewise)
+        for pre in ("srt_", "srt_group_"):
+            getattr(lib, pre + "nearest_points").argtypes = [vp, vp, sz, C.c_uint32, vp]
+        lib.srt_nearest_points_device.argtypes = [vp, vp, sz, C.c_uint32, vp]
+        lib.srt_nearest_triangle_host.argtypes = [vp, vp, vp, vp, vp]
+        lib.srt_nearest_sphere_host.argtypes = [vp, C.c_float, vp, vp, vp, vp]
+        lib.srt_nearest_plane_host.argtypes = [vp, vp, vp, vp, vp, vp]
+        lib.srt_nearest_sizes.argtypes = [C.POINTER(sz)]
+        sizes = (sz * 2)()
+        assert lib.srt_nearest_sizes(sizes) == 0 and (sizes[0], sizes[1]) == (R.POINT_QUERY.itemsize, R.NEAREST.itemsize), tuple(sizes)
     if hasattr(lib, "srt_set_selection"):  # (likewise)
         ip = C.POINTER(C.c_int)
         lib.srt_selection_defaults.argtypes = [vp]
@@ -1172,6 +1184,17 @@ class _RayQuery:
         hits = np.zeros(len(xy), R.RAY_HIT)
         self._check(self._dn("pick", _ptr(rd), _ptr(xy) if len(xy) else None, len(xy), _ptr(hits) if len(xy) else None))
         return hits
+
+    # ---- nearest-surface queries (include/srt_abi.h "nearest-surface queries") ----
+    def nearest_points(self, points, max_distance=np.inf, skip_shape=None):
+        """The closest scene point to each point -> records.NEAREST array. points: (n, 3) or (3,) with a scalar or (n,)
+        max_distance, or a records.POINT_QUERY array alone; skip_shape: a shape index left out of the search. Blocking."""
+        pts = np.asarray(points)
+        qs = R.as_records(pts, R.POINT_QUERY) if pts.dtype.names else R.point_queries(pts, max_distance)
+        out = np.zeros(len(qs), R.NEAREST)
+        self._check(self._dn("nearest_points", _ptr(qs) if len(qs) else None, len(qs), R.HIT_NONE if skip_shape is None else int(skip_shape),
+                             _ptr(out) if len(qs) else None))
+        return out
 
     # ---- occlusion queries (include/srt_abi.h "occlusion queries") ----
     def occluded_rays(self, origins, directions=None, tmax=np.inf, unit=False, with_invalid=False):
@@ -1723,6 +1746,12 @@ class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection, _Ambien
         """cast_rays over device arrays (n records.RAY at rays_ptr, n records.RAY_HIT at hits_ptr, 16-byte aligned), enqueued
         on the handle's stream: synchronize() before the hits are read."""
         self._check(self.lib.srt_cast_rays_device(self._h, C.c_void_p(rays_ptr), n, R.RAYS_UNIT_DIRECTIONS if unit else 0, C.c_void_p(hits_ptr)))
+
+    def nearest_points_device(self, queries_ptr, n, out_ptr, skip_shape=None):
+        """nearest_points over device arrays (n records.POINT_QUERY at queries_ptr, n records.NEAREST at out_ptr, 16-byte
+        aligned), enqueued on the handle's stream: synchronize() before the records are read."""
+        self._check(self.lib.srt_nearest_points_device(self._h, C.c_void_p(queries_ptr), n, R.HIT_NONE if skip_shape is None else int(skip_shape),
+                                                       C.c_void_p(out_ptr)))
 
     def occluded_rays_device(self, rays_ptr, n, occluded_ptr, invalid_ptr=None, unit=False):
         """occluded_rays over device arrays (n records.RAY at rays_ptr, 16-byte aligned; ceil(n / 64) 64-bit words at
