@@ -94,7 +94,7 @@ def child(a):
     g.close()
     # ---- one handle of the same size ----
     t = setup(TR.Tracer(w, h))
-    t.bind_stream(sptr)
+    t.bind_stream(sptr.value)
 
     def single_frame(on):
         def frame(i, mark):

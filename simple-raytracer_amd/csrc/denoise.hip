@@ -554,7 +554,7 @@ int srt_denoise_after_trace(srt_tracer *t, const TraceParams &p, int num_samples
 	const uint32_t fs = want < ns ? want : ns;
 	FeatureParams fp;
 	fp.tp = p;
-	// a group member (gd_on): its own rows into the planes behind its canvas rows; the counts are the group's (srt_collect.hip)
+	// a group member (gd_on): its own rows into the planes behind its canvas rows; the counts are the group's (srt_group.hip)
 	fp.normal_depth = t->gd_on ? gd_normal_depth(t) : t->dn_nd.ptr;
 	fp.albedo_hits = t->gd_on ? gd_albedo_hits(t) : t->dn_ah.ptr;
 	fp.num_pixels = (uint32_t)(t->gd_on ? owned_pixels(t) : full_pixels(t));

@@ -183,6 +183,7 @@ void srt_destroy(srt_tracer *t) {
 	(void)hipSetDevice(t->device);
 	if (t->own_stream) (void)hipStreamSynchronize(t->own_stream);
 	srt_collect_release(t);
+	srt_pipeline_release(t);
 	t->canvas_own.release();
 	t->gd_pack.release();
 	t->argb.release();

@@ -1,6 +1,6 @@
 // srt_internal.h — the handle behind `srt_tracer *` and the small helpers the translation units of
 // libsrt_hip.so share (srt_abi.hip: life cycle, scene upload, trace; accel_device.hip: BVH upkeep on the device;
-// srt_collect.hip: multi-GPU collection, frame pipeline). What of the host side needs no handle and no HIP is not here: bvh_host.h, scene_prep.h, trace_plan.h, denoise_plan.h.
+// srt_collect.hip: multi-GPU collection; srt_group.hip: the device group; frame_pipeline.hip: the frame pipeline). What of the host side needs no handle and no HIP is not here: bvh_host.h, scene_prep.h, trace_plan.h, denoise_plan.h.
 // Not part of the public ABI.
 #ifndef SRT_INTERNAL_H
 #define SRT_INTERNAL_H
@@ -220,11 +220,13 @@ struct AoState {
 	void release() { surfaces.release(), occluded.release(), table.release(); }
 };
 
-struct SrtCollect; // srt_collect.hip: RCCL communicator, gathered canvases, frame pipeline
+struct SrtCollect;  // collect_internal.h (srt_collect.hip): RCCL communicator, gathered canvases
+struct SrtPipeline; // frame_pipeline.hip: copy stream, the two frames in flight
 
 struct srt_tracer {
 	int width = 0, height = 0, device = 0;
 	SrtCollect *collect = nullptr;
+	SrtPipeline *pipeline = nullptr;
 	hipStream_t own_stream = nullptr, stream = nullptr;
 	DevBuf<float> canvas_own;
 	float *canvas = nullptr;
@@ -321,7 +323,7 @@ struct srt_tracer {
 	std::vector<uint32_t> vm_first;
 	DevBuf<uint32_t> vm_first_dev;
 	uint64_t vm_scene_ver = 1, vm_ver[2] = {0, 0};
-	// group denoiser (srt_collect.hip srt_group_set_denoise): a member of a device group accumulates the denoiser's inputs for
+	// group denoiser (srt_group.hip srt_group_set_denoise): a member of a device group accumulates the denoiser's inputs for
 	// its OWN rows, packed as its canvas rows are. gd_pack is ONE allocation of srt_planes_slot_floats() floats that one collective
 	// sends: the canvas rows (bound as the canvas, the way srt_bind_canvas does), the normal_depth and albedo_hits planes
 	// (float4 per pixel of the padded rows each) and the moments plane. The filter runs on the group's full-frame resolver
@@ -352,7 +354,7 @@ struct srt_tracer {
 	bool last_trace_textured = false; // srt_last_trace_textured
 	int last_trace_class = 0;         // srt_last_trace_class
 	ExposureState ex_own;             // exposure.hip ...
-	ExposureState *ex = &ex_own;      // ... through this: a group's full-frame resolver handle shares the first member's (srt_collect.hip resolver_of)
+	ExposureState *ex = &ex_own;      // ... through this: a group's full-frame resolver handle shares the first member's (srt_group.hip resolver_of)
 	BloomState bl_own;                // bloom.hip ...
 	BloomState *bl = &bl_own;         // ... shared the same way
 	NoiseState nz_own;                // noise_meter.hip ...
@@ -396,7 +398,8 @@ static inline float *gd_moments(const srt_tracer *t) { return t->gd_pack.ptr + 1
 	} while (0)
 
 
-void srt_collect_release(srt_tracer *t);
+void srt_collect_release(srt_tracer *t); /* srt_destroy: the communicator srt_comm_init made, the gathered buffers */
+__attribute__((visibility("hidden"))) void srt_pipeline_release(srt_tracer *t); /* ... then the copy stream (waited for), the frames' buffers, the events */
 int srt_accel_deform_consume(srt_tracer *t, BvhCache *cache); /* accel_device.hip, before the host pass: the last upload's cost sums become ratios, here and in `cache` (the handle's own, a group's first member's) */
 int srt_accel_build_consume(srt_tracer *t, BvhCache *cache);  /* before the host pass: the last upload's sorted order goes to its entries of `cache` */
 int srt_accel_before_prepass(srt_tracer *t, const ScenePrep &sp); /* SRT_BUILD_DEVICE: the order of the models this upload builds */

@@ -1,6 +1,6 @@
-"""GPU (MI355X): what happens to a frame after the trace kernel beyond one blocking device (csrc/srt_collect.hip):
-the in-library RCCL gather (one process per GPU: srt_comm_* / srt_gather; one process, several GPUs: srt_group_*)
-and the two-deep frame pipeline. One GPU is what the test box has: RCCL itself runs with world = 1 (the communicator, the
+"""GPU (MI355X): what happens to a frame after the trace kernel beyond one blocking device:
+the in-library RCCL gather (one process per GPU: srt_comm_* / srt_gather, csrc/srt_collect.hip; one process, several GPUs:
+srt_group_*, csrc/srt_group.hip) and the two-deep frame pipeline (csrc/frame_pipeline.hip). One GPU is what the test box has: RCCL itself runs with world = 1 (the communicator, the
 ncclGather call, the unpermute kernel and the resolve of the gathered image are the real ones), and the N > 1 code of
 srt_group_* runs on VIRTUAL devices -- N members on the one GPU, collected by device-to-device copies where ncclGather
 would be (round 4). No run on more than one GPU exists yet."""

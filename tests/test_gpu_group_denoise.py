@@ -1,4 +1,4 @@
-"""GPU (MI355X): the denoiser on a device group (srt_group_set_denoise and friends; csrc/srt_collect.hip).
+"""GPU (MI355X): the denoiser on a device group (srt_group_set_denoise and friends; csrc/srt_group.hip).
 
 The members accumulate the filter's inputs for their own rows, one collective brings canvas rows and inputs to the first
 device, one unpermute launch puts them in image order and the single handle's filter runs there. Nothing of that has an

@@ -18,7 +18,7 @@ The expression is written out three times in the device code; which test reaches
     srt_denoise_atrous_demod_kernel<true>                ...[demod-*]
     srt_temporal_kernel<0, false, false> (csrc/temporal.hip)   ...[temporal-0]: iterations = 0 with a valid history
 
-Sites that share one of these and are covered through it (read in csrc/srt_collect.hip and csrc/srt_abi.hip):
+Sites that share one of these and are covered through it (read in csrc/srt_collect.hip, csrc/srt_group.hip, csrc/frame_pipeline.hip and csrc/srt_abi.hip):
 srt_resolve_gathered calls srt_resolve_external; srt_group_render calls srt_resolve_gathered, or with the group's denoiser on
 srt_resolve_denoised on its resolver handle (srt_denoise_filter, the kernels above); a group member's srt_render with the
 group's denoiser on resolves through launch_resolve (srt_resolve_kernel); srt_render with the handle's denoiser on runs
