@@ -1417,6 +1417,87 @@ int srt_group_ao_rays(srt_group *g, const srt_render_data *options, const srt_ao
 int srt_group_resolve_ao_view(srt_group *g);
 int srt_group_read_ao_view(srt_group *g, uint8_t *argb_out);
 
+/* ---- area selection (new; no counterpart in the reference) ------------------------------------------------------------------
+ * The rubber band of an editor: which shapes, or which faces of one mesh, are VISIBLE inside a rectangle or a lasso, and how
+ * many pixels of each -- counted on the device from the ID pass's planes (above), which are already there. A few hundred
+ * integers come back instead of 12 bytes per pixel. Records: srt_area, srt_area_summary (srt_types.h). Everything is an integer.
+ *
+ * THE AREA is the half-open pixel rectangle [x0, x1) x [y0, y1), optionally intersected with a lasso.
+ *   - The rectangle is clipped to the ID planes' frame; it may lie partly or wholly outside; an empty one gives all zeros.
+ *   - The lasso is a polygon of n_vertices in {0, 3..SRT_AREA_MAX_VERTICES}, 0 meaning the rectangle alone, closed implicitly,
+ *     even-odd rule. Self-intersecting, clockwise, counter-clockwise and zero-area polygons are legal.
+ *   - Vertices are int32 pairs {vx, vy} in pixel-CORNER coordinates: (vx, vy) is the corner shared by pixels (vx - 1 .. vx,
+ *     vy - 1 .. vy). Each coordinate lies in [-2^20, 2^20].
+ * Pixel (px, py) is inside the lasso by exact integer arithmetic on doubled coordinates. With C = (2 px + 1, 2 py + 1) and, for
+ * edge i, A = 2 v[i], B = 2 v[(i + 1) % n]:
+ *   - the edge SPANS THE ROW when (A.y < C.y) != (B.y < C.y). C.y is odd and A.y, B.y are even: equality cannot occur, so there
+ *     is no vertex-on-row case;
+ *   - cross = (B.x - A.x) * (C.y - A.y) - (B.y - A.y) * (C.x - A.x) in int64;
+ *   - a spanning edge COUNTS when cross > 0 for B.y > A.y, or cross < 0 for B.y < A.y. A pixel centre exactly on an edge
+ *     (cross == 0) does not count for that edge;
+ *   - the pixel is inside when the number of counting edges is odd.
+ * The mask M(p) is "rectangle and frame and (no lasso or inside)". One implementation, csrc/area_host.h, is compiled into the
+ * counting kernel and into srt_area_mask_host.
+ * SHAPE COVERAGE over the shape plane S, n_shapes = the scene's shape count:
+ *   counts[s] = #{p : M(p), S(p) == s} for s < n_shapes;  area_pixels = #M;  miss_pixels = #{M, S == SRT_HIT_NONE};
+ *   hit_pixels = area_pixels - miss_pixels (= sum(counts));  distinct = #{s : counts[s] > 0};  target_pixels = 0.
+ * TRIANGLE COVERAGE of one model shape s0 over the triangle plane T, n_tri = the triangles of the shape's model:
+ *   counts[k] = #{p : M(p), S(p) == s0, T(p) == k} for k < n_tri;  target_pixels = sum(counts);  distinct = #{k : counts[k] > 0};
+ *   area_pixels, miss_pixels and hit_pixels as above. s0 not a model shape: SRT_ERR_INVALID.
+ * THE KERNEL (csrc/area.hip) covers the clipped rectangle only, a wave per 64 pixels of one row; a wave adds the lanes that
+ * share a key with one atomic, SRT_AREA_AGG_ROUNDS times, and what is left lane by lane. Every key is compared with the count
+ * array's length before its atomic: whatever the planes hold, nothing is written outside `counts`.
+ * THE PLANES. options != NULL: the handle's ID planes are brought up to date for that camera and frame first, under the overlay's
+ * key -- an unchanged camera and scene run no ID pass, and an overlay behind the call reuses the planes. options == NULL: the
+ * planes the handle holds; SRT_ERR_STATE when there are none, or when the scene's revision has moved on since they were made
+ * (counts of a stale plane would index another scene).
+ * STATE. A coverage call writes its own result buffers on the handle and nothing else: canvas, counters, denoiser, exposure,
+ * bloom, noise and AO state stay as they were and, unless it is srt_select_area, so does the selection. A handle that never
+ * calls any of this launches exactly what it launched before.
+ * ERRORS. SRT_ERR_INVALID: a NULL handle, area, counts (with a capacity needed) or summary; what srt_area_check_host refuses; a
+ * capacity below n_shapes / n_tri (nothing is launched); options with a frame that is not positive or has 2^31 pixels or more. */
+/* Host-only: out = {sizeof(srt_area), sizeof(srt_area_summary)} as the library was built. */
+int srt_area_sizes(size_t out[2]);
+/* Host-only: the validation every call below applies. SRT_ERR_INVALID: n_vertices 1, 2 or above SRT_AREA_MAX_VERTICES; a
+ * coordinate outside [-2^20, 2^20]; vertices NULL with n_vertices > 0; flags or a reserved field not 0; x1 < x0 or y1 < y0. */
+int srt_area_check_host(const srt_area *area, const int32_t *vertices);
+/* Host-only: M(p) of a w x h frame as defined above, one byte (0 or 1) per pixel into mask of cap bytes. SRT_ERR_INVALID as
+ * srt_area_check_host; w or h not positive; w * h >= 2^31; mask NULL or cap < w * h. */
+int srt_area_mask_host(const srt_area *area, const int32_t *vertices, int w, int h, uint8_t *mask, size_t cap);
+/* Blocking. counts: cap_shapes >= n_shapes words, of which n_shapes are written (NULL allowed when n_shapes == 0). The counts and
+ * the summary come back as one copy through pinned memory behind an event. */
+int srt_area_coverage(srt_tracer *t, const srt_render_data *options, const srt_area *area, const int32_t *vertices, uint32_t *counts, size_t cap_shapes,
+                      srt_area_summary *out);
+int srt_area_triangle_coverage(srt_tracer *t, const srt_render_data *options, const srt_area *area, const int32_t *vertices, uint32_t shape, uint32_t *counts,
+                               size_t cap_triangles, srt_area_summary *out);
+/* Shape coverage left in device memory of the handle's device, asynchronous on the handle's stream: d_counts of n >= n_shapes
+ * words (all n are zeroed, n_shapes counted), d_summary of 8 words laid out as srt_area_summary; both 4-byte aligned. */
+int srt_area_coverage_device(srt_tracer *t, const srt_render_data *options, const srt_area *area, const int32_t *vertices, uint32_t *d_counts, size_t n,
+                             uint32_t *d_summary);
+/* Blocking. Shape coverage, then the shapes with counts[s] >= max(min_pixels, 1) combined with the handle's current selection
+ * (srt_read_selection) by mode -- SRT_SELECT_REPLACE: they alone; ADD: the union; SUBTRACT: the current ones that are not
+ * among them; TOGGLE: those in exactly one of the two -- and set as srt_set_selection sets a list, with the parameters last given
+ * to it (never given: srt_selection_defaults) and the overlay enabled. An empty result switches the overlay off, as
+ * srt_set_selection does for n == 0. *n_selected (may be NULL) = the length of the new list. SRT_ERR_INVALID: an unknown mode. */
+int srt_select_area(srt_tracer *t, const srt_render_data *options, const srt_area *area, const int32_t *vertices, int mode, uint32_t min_pixels,
+                    size_t *n_selected);
+/* The current selection: the list the overlay shows (srt_set_selection's, or srt_select_area's), ascending and unique, *n of
+ * them; empty while the overlay is off. shapes NULL: the length alone. SRT_ERR_INVALID: cap < *n. Host state only. */
+int srt_read_selection(srt_tracer *t, uint32_t *shapes, size_t cap, size_t *n);
+/* On the group's first device, which holds the group's one ID / selection state and the whole scene. */
+int srt_group_area_coverage(srt_group *g, const srt_render_data *options, const srt_area *area, const int32_t *vertices, uint32_t *counts, size_t cap_shapes,
+                            srt_area_summary *out);
+int srt_group_area_triangle_coverage(srt_group *g, const srt_render_data *options, const srt_area *area, const int32_t *vertices, uint32_t shape,
+                                     uint32_t *counts, size_t cap_triangles, srt_area_summary *out);
+int srt_group_select_area(srt_group *g, const srt_render_data *options, const srt_area *area, const int32_t *vertices, int mode, uint32_t min_pixels,
+                          size_t *n_selected);
+int srt_group_read_selection(srt_group *g, uint32_t *shapes, size_t cap, size_t *n);
+/* With srt_set_kernel_timers on: the device time of the last coverage call's clear and counting launches (its ID pass excluded),
+ * in milliseconds; 0 when the timers were off or nothing was launched. Blocking, as srt_last_ray_query_ms. */
+int srt_last_area_ms(srt_tracer *t, float *ms);
+/* For tests: *id_pass_ran = 1 when the last coverage call on the handle had to make the ID planes first. */
+int srt_last_area_id_pass(const srt_tracer *t, int *id_pass_ran);
+
 /* Library / build identification, e.g. "srt-hip gfx950 parity fp-contract=off". */
 const char *srt_version(void);
 

@@ -294,6 +294,28 @@ typedef struct srt_nearest {
 #define SRT_NEAREST_FEATURE_SHIFT 8 /* bits 8..10: 0 the face, 1/2/3 vertex v0/v1/v2, 4/5/6 edge v0v1 / v0v2 / v1v2; spheres and planes 0 */
 #define SRT_NEAREST_FEATURE_MASK 0x700u
 
+/* Area selection (srt_area_coverage, srt_select_area; include/srt_abi.h "area selection"). */
+typedef struct srt_area {
+	int32_t x0, y0, x1, y1; /* the half-open pixel rectangle [x0, x1) x [y0, y1); x0 <= x1, y0 <= y1; clipped to the frame */
+	uint32_t n_vertices;    /* 0: the rectangle alone; else 3..SRT_AREA_MAX_VERTICES lasso vertices */
+	uint32_t flags;         /* must be 0 */
+	uint32_t reserved[2];   /* must be 0 */
+} srt_area;
+typedef struct srt_area_summary {
+	uint32_t area_pixels;   /* #M */
+	uint32_t hit_pixels;    /* area_pixels - miss_pixels */
+	uint32_t miss_pixels;   /* #{M, shape == SRT_HIT_NONE} */
+	uint32_t distinct;      /* #{k : counts[k] > 0} */
+	uint32_t target_pixels; /* triangle coverage: sum(counts); shape coverage: 0 */
+	uint32_t reserved[3];   /* written as 0 */
+} srt_area_summary;
+#define SRT_AREA_MAX_VERTICES 256u
+#define SRT_AREA_AGG_ROUNDS 4u /* the counting kernel's wave-aggregated rounds before its per-lane atomics */
+#define SRT_SELECT_REPLACE 0
+#define SRT_SELECT_ADD 1
+#define SRT_SELECT_SUBTRACT 2
+#define SRT_SELECT_TOGGLE 3
+
 #ifdef __cplusplus
 }
 #endif
@@ -382,5 +404,9 @@ SRT_STATIC_ASSERT(sizeof(srt_nearest) == 32, "Nearest 32 B");
 SRT_STATIC_ASSERT(offsetof(srt_nearest, material) == 12, "Nearest.material@12");
 SRT_STATIC_ASSERT(offsetof(srt_nearest, point) == 16, "Nearest.point@16");
 SRT_STATIC_ASSERT(offsetof(srt_nearest, flags) == 28, "Nearest.flags@28");
+SRT_STATIC_ASSERT(sizeof(srt_area) == 32, "Area 32 B");
+SRT_STATIC_ASSERT(offsetof(srt_area, n_vertices) == 16, "Area.n_vertices@16");
+SRT_STATIC_ASSERT(sizeof(srt_area_summary) == 32, "AreaSummary 32 B");
+SRT_STATIC_ASSERT(offsetof(srt_area_summary, target_pixels) == 16, "AreaSummary.target_pixels@16");
 
 #endif /* SRT_TYPES_H */

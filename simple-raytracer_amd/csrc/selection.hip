@@ -278,6 +278,17 @@ int srt_selection_apply(srt_tracer *t, uint32_t w, uint32_t h, bool picture, uin
 	return SRT_OK;
 }
 
+int srt_selection_ids_current(srt_tracer *t, const srt_render_data *rd, bool *ran) {
+	*ran = false;
+	if (rd->width <= 0 || rd->height <= 0) return fail(t, SRT_ERR_INVALID, "area selection: options->width and height must be positive");
+	if ((uint64_t)rd->width * (uint64_t)rd->height >= (1ull << 31)) return fail(t, SRT_ERR_INVALID, "area selection: the frame must stay below 2^31 pixels");
+	if (const int rc = srt_texture_sync(t)) return rc; // the per-triangle material table (a part of the key) as the next dispatch would see it
+	const SelectionKey key = key_of(t, *rd);
+	if (t->sel->ids_valid && memcmp(&key, &t->sel->ids_key, sizeof key) == 0) return SRT_OK;
+	*ran = true;
+	return enqueue_id_pass(t, t, *rd);
+}
+
 extern "C" {
 
 int srt_selection_defaults(srt_selection_params *out) {

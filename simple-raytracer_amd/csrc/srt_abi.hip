@@ -225,6 +225,7 @@ void srt_destroy(srt_tracer *t) {
 	t->rq_stage.release();
 	t->rq_span.release();
 	t->ao.release();
+	t->ar.release();
 	srt_texture_release(t);
 	if (t->ev_t0) (void)hipEventDestroy(t->ev_t0);
 	if (t->ev_t1) (void)hipEventDestroy(t->ev_t1);

@@ -220,6 +220,17 @@ struct AoState {
 	void release() { surfaces.release(), occluded.release(), table.release(); }
 };
 
+// Area selection (area.hip; srt_area_coverage ...): the result of the last coverage call on the device -- the 8 words of an
+// srt_area_summary, then the counts -- its pinned copy, the timers' span around the last call's clear and launches, and whether
+// that call had to make the ID planes (srt_last_area_id_pass). All made on first use
+struct AreaState {
+	DevBuf<uint32_t> out;
+	PinnedReadback<uint32_t> back;
+	TimedSpan span;
+	bool last_id_ran = false;
+	void release() { out.release(), back.release(), span.release(); }
+};
+
 struct SrtCollect;  // collect_internal.h (srt_collect.hip): RCCL communicator, gathered canvases
 struct SrtPipeline; // frame_pipeline.hip: copy stream, the two frames in flight
 
@@ -370,6 +381,7 @@ struct srt_tracer {
 	DevBuf<uint8_t> rq_stage;
 	TimedSpan rq_span;
 	AoState ao; // ao.hip
+	AreaState ar; // area.hip
 	hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr, ev_r0 = nullptr, ev_r1 = nullptr;
 	bool have_trace_ev = false, have_resolve_ev = false, have_kernel_ev = false;
 	std::string err;
@@ -486,6 +498,10 @@ static inline int srt_selection_apply_frame(srt_tracer *t, uint8_t *argb) {
 	if (t->dn.on && t->dn_filtered) return srt_selection_apply(t, (uint32_t)t->width, (uint32_t)t->height, true, argb);
 	return srt_selection_apply(t, (uint32_t)t->width, (uint32_t)t->owned_rows, t->world == 1, argb);
 }
+/* ... for area.hip: the handle's ID planes brought up to date for its own scene under rd's camera and frame, by the overlay's
+ * key -- planes made under an equal key are kept and nothing is launched; *ran = whether the pass was enqueued. rd is checked
+ * as srt_render_ids checks it */
+int srt_selection_ids_current(srt_tracer *t, const srt_render_data *rd, bool *ran);
 /* bloom.hip: whether a site's resolve of num_pixels is bloomed (the feature on, a picture, not empty); sets last_bloomed */
 bool srt_bloom_begin(srt_tracer *t, bool picture, size_t num_pixels);
 /* ... and its launches on the handle's stream: the pyramid of (source / divisor) * *exposure (NULL: 1.0f) and the composite

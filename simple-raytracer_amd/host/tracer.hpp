@@ -340,6 +340,37 @@ class Tracer {
 		argb(outline_rrggbbaa, p.outline_argb), argb(fill_rrggbbaa, p.fill_argb);
 		check(group ? srt_group_set_selection(group, &p, shapes.data(), shapes.size()) : srt_set_selection(handle, &p, shapes.data(), shapes.size()));
 	}
+	/// Area selection (srt_area_coverage): the visible pixels of every shape inside the half-open pixel rectangle of `area`,
+	/// optionally cut by a lasso (pixel-corner vertices x0, y0, x1, y1, ...; even-odd rule), counted on the device from the ID
+	/// planes of the camera of `options` -- what a rubber band asks. summary (optional): the area's totals. Blocking.
+	std::vector<uint32_t> area_coverage(srt_area area, const std::vector<int32_t> &lasso = {}, srt_area_summary *summary = nullptr) {
+		std::vector<uint32_t> counts((size_t)scene_data.num_shapes);
+		srt_area_summary s;
+		area.n_vertices = uint32_t(lasso.size() / 2);
+		const srt_render_data *rd = reinterpret_cast<const srt_render_data *>(&options);
+		check(group ? srt_group_area_coverage(group, rd, &area, lasso.data(), counts.data(), counts.size(), &s)
+		            : srt_area_coverage(handle, rd, &area, lasso.data(), counts.data(), counts.size(), &s));
+		if (summary) *summary = s;
+		return counts;
+	}
+	/// ... and the shapes with at least min_pixels visible pixels combined with the current selection (mode: SRT_SELECT_REPLACE,
+	/// ADD, SUBTRACT, TOGGLE) and overlaid as set_selection overlays a list, with the parameters it was last given. Returns the
+	/// new list's length. One call per mouse-move of a drag: under an unchanged camera and scene no ID pass runs. Blocking.
+	size_t select_area(srt_area area, const std::vector<int32_t> &lasso = {}, int mode = SRT_SELECT_REPLACE, uint32_t min_pixels = 1) {
+		size_t n = 0;
+		area.n_vertices = uint32_t(lasso.size() / 2);
+		const srt_render_data *rd = reinterpret_cast<const srt_render_data *>(&options);
+		check(group ? srt_group_select_area(group, rd, &area, lasso.data(), mode, min_pixels, &n) : srt_select_area(handle, rd, &area, lasso.data(), mode, min_pixels, &n));
+		return n;
+	}
+	/// The current selection, ascending and unique; empty while the overlay is off
+	std::vector<uint32_t> read_selection() {
+		size_t n = 0;
+		check(group ? srt_group_read_selection(group, nullptr, 0, &n) : srt_read_selection(handle, nullptr, 0, &n));
+		std::vector<uint32_t> list(n);
+		check(group ? srt_group_read_selection(group, list.data(), list.size(), &n) : srt_read_selection(handle, list.data(), list.size(), &n));
+		return list;
+	}
 	/// ... off: the sites resolve as they do without it
 	void clear_selection() { check(group ? srt_group_set_selection(group, nullptr, nullptr, 0) : srt_set_selection(handle, nullptr, nullptr, 0)); }
 	/// The ID pass alone for the camera of `options` (srt_render_ids): shape, triangle and material per pixel, for read_id_pass.

@@ -89,6 +89,13 @@ NEAREST = np.dtype({"names": ["distance", "shape", "triangle", "material", "poin
                     "formats": [np.float32, np.uint32, np.uint32, np.int32, F3, np.uint32], "offsets": [0, 4, 8, 12, 16, 28], "itemsize": 32})
 NEAREST_FOUND, NEAREST_BACK, NEAREST_INVALID = 1, 2, 4
 NEAREST_FEATURE_SHIFT, NEAREST_FEATURE_MASK = 8, 0x700
+# srt_area / srt_area_summary (area selection: Tracer.area_coverage, Tracer.select_area), 32 bytes each
+AREA = np.dtype({"names": ["x0", "y0", "x1", "y1", "n_vertices", "flags", "reserved"],
+                 "formats": [np.int32, np.int32, np.int32, np.int32, np.uint32, np.uint32, (np.uint32, 2)], "offsets": [0, 4, 8, 12, 16, 20, 24], "itemsize": 32})
+AREA_SUMMARY = np.dtype({"names": ["area_pixels", "hit_pixels", "miss_pixels", "distinct", "target_pixels", "reserved"],
+                         "formats": [np.uint32] * 5 + [(np.uint32, 3)], "offsets": [0, 4, 8, 12, 16, 20], "itemsize": 32})
+AREA_MAX_VERTICES, AREA_COORD_MAX, AREA_AGG_ROUNDS = 256, 1 << 20, 4
+SELECT_REPLACE, SELECT_ADD, SELECT_SUBTRACT, SELECT_TOGGLE = 0, 1, 2, 3
 
 SHAPE_SPHERE, SHAPE_PLANE, SHAPE_MODEL = 0, 1, 2
 

@@ -160,6 +160,11 @@ int main(int argc, char **argv) {
 	float exposure_ev = 0.0f;
 	bool bloom = false;
 	std::vector<uint32_t> selected; // --select
+	srt_area area{};                // --select-area, --lasso
+	bool select_area = false;
+	int area_mode = SRT_SELECT_REPLACE;
+	unsigned area_min_pixels = 1;
+	std::vector<int32_t> lasso;
 	float select_width = 0.0f;      // (0: the library's default)
 	uint32_t select_colour = 0xffa000ffu;
 	float bloom_threshold = -1.0f, bloom_intensity = -1.0f; // (negative: the library's default)
@@ -325,6 +330,32 @@ int main(int argc, char **argv) {
 				return 2;
 			}
 		}
+		else if (a == "--select-area") { // X0,Y0:X1,Y1[:MODE[:MINPIXELS]]
+			char mode[16] = "replace";
+			const int got = std::sscanf(next(), "%d,%d:%d,%d:%15[a-z]:%u", &area.x0, &area.y0, &area.x1, &area.y1, mode, &area_min_pixels);
+			const std::string m = mode;
+			area_mode = m == "replace" ? SRT_SELECT_REPLACE : m == "add" ? SRT_SELECT_ADD : m == "subtract" ? SRT_SELECT_SUBTRACT : m == "toggle" ? SRT_SELECT_TOGGLE : -1;
+			if (got < 4 || area_mode < 0 || area.x1 < area.x0 || area.y1 < area.y0) {
+				std::cerr << "--select-area takes X0,Y0:X1,Y1[:MODE[:MINPIXELS]], X0 <= X1, Y0 <= Y1, MODE replace, add, subtract or toggle\n";
+				return 2;
+			}
+			select_area = true;
+		}
+		else if (a == "--lasso") { // X,Y;X,Y;...
+			const std::string v = next();
+			const char *c = v.c_str();
+			int x = 0, y = 0, used = 0;
+			while (std::sscanf(c, "%d,%d%n", &x, &y, &used) == 2) {
+				lasso.push_back(x), lasso.push_back(y);
+				c += used;
+				if (*c != ';') break;
+				c++;
+			}
+			if (*c || lasso.size() < 6 || lasso.size() > 2 * SRT_AREA_MAX_VERTICES) {
+				std::cerr << "--lasso takes X,Y;X,Y;... with 3 to 256 pixel-corner vertices\n";
+				return 2;
+			}
+		}
 		else if (a == "--pick") { // X,Y
 			float x = 0.f, y = 0.f;
 			if (std::sscanf(next(), "%f,%f", &x, &y) != 2) {
@@ -355,7 +386,7 @@ int main(int argc, char **argv) {
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--ao S[:RADIUS[:BIAS]]] [--ao-view f.ppm] [--select I[,J...][:WIDTH[:RRGGBBAA]]] [--pick X,Y]... [--nearest X,Y,Z[:RADIUS[:SKIP]]]... [--line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP]]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
+			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--ao S[:RADIUS[:BIAS]]] [--ao-view f.ppm] [--select I[,J...][:WIDTH[:RRGGBBAA]]] [--select-area X0,Y0:X1,Y1[:MODE[:MINPIXELS]] [--lasso X,Y;X,Y;...]] [--pick X,Y]... [--nearest X,Y,Z[:RADIUS[:SKIP]]]... [--line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP]]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
@@ -593,6 +624,26 @@ int main(int argc, char **argv) {
 	if (!dump_prefix.empty()) dump(dump_prefix + ".sky.bin", sky.data(), sky.size());
 
 	std::vector<uint8_t> pixels((size_t)width * height * 4);
+
+	if (!lasso.empty() && !select_area) {
+		std::cerr << "--lasso needs --select-area\n";
+		return 2;
+	}
+	if (select_area) { // --select-area: the shapes visible inside the area through the first frame's camera, combined with --select's
+		tracer.update_scene(shapes, triangles, materials.list);
+		auto &options = tracer.options;
+		options.aspect_ratio = (float)width / (float)height;
+		options.fov_scale = 1.0f;
+		options.camera_to_world = moving ? eye_matrix(glm::vec3(0.0f, 0.5f, 5.0f), 0.0f, 0.0f) : camera_to_world;
+		srt_area_summary sum;
+		const std::vector<uint32_t> counts = tracer.area_coverage(area, lasso, &sum);
+		std::printf("area: %u pixel(s), %u on shapes, %u miss, %u shape(s)\n", sum.area_pixels, sum.hit_pixels, sum.miss_pixels, sum.distinct);
+		for (size_t i = 0; i < counts.size(); i++)
+			if (counts[i]) std::printf("shape %zu count %u\n", i, counts[i]);
+		const size_t n = tracer.select_area(area, lasso, area_mode, area_min_pixels);
+		selected = tracer.read_selection();
+		std::printf("area selection: %zu shape(s)\n", n);
+	}
 
 	if (!picks.empty()) { // --pick: what is under these image points, through the first frame's camera
 		tracer.update_scene(shapes, triangles, materials.list);

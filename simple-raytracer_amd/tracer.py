@@ -83,6 +83,9 @@ ABI_SYMBOLS = [
     "srt_group_read_ao_view",
     "srt_nearest_points", "srt_nearest_points_device", "srt_group_nearest_points", "srt_nearest_triangle_host", "srt_nearest_sphere_host",
     "srt_nearest_plane_host", "srt_nearest_sizes",
+    "srt_area_sizes", "srt_area_check_host", "srt_area_mask_host", "srt_area_coverage", "srt_area_triangle_coverage",
+    "srt_area_coverage_device", "srt_select_area", "srt_read_selection", "srt_group_area_coverage", "srt_group_area_triangle_coverage",
+    "srt_group_select_area", "srt_group_read_selection", "srt_last_area_ms", "srt_last_area_id_pass",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -528,6 +531,36 @@ def selection_alpha_table_host(**kw):
     return table[:2 * radius.value ** 2 + 1].copy(), radius.value
 
 
+def area_record(rect, lasso=None):
+    """(records.AREA record, (n, 2) int32 vertex array or None) of rect = (x0, y0, x1, y1) and an optional lasso: n pixel-corner
+    vertices (x, y). Nothing is checked here: the library does that."""
+    a = np.zeros((), R.AREA)
+    a["x0"], a["y0"], a["x1"], a["y1"] = (int(v) for v in rect)
+    if lasso is None or len(lasso) == 0:
+        return a, None
+    v = np.ascontiguousarray(np.asarray(lasso, np.int64).reshape(-1, 2).astype(np.int32))
+    a["n_vertices"] = len(v)
+    return a, v
+
+
+def area_check_host(rect, lasso=None, **fields):
+    """srt_area_check_host (host only): True when the coverage calls would accept the area. fields: overrides of the record's
+    fields (flags, reserved, n_vertices), for the tests."""
+    a, v = area_record(rect, lasso)
+    for k, val in fields.items():
+        a[k] = val
+    return load_library().srt_area_check_host(_ptr(a), _ptr(v) if v is not None else None) == 0
+
+
+def area_mask(rect, lasso=None, width=0, height=0):
+    """srt_area_mask_host (host only): M(p) of a width x height frame -> (height, width) bool, the rule the device counts by."""
+    a, v = area_record(rect, lasso)
+    mask = np.zeros((max(height, 0), max(width, 0)), np.uint8)
+    if load_library().srt_area_mask_host(_ptr(a), _ptr(v) if v is not None else None, width, height, _ptr(mask) if mask.size else None, mask.size):
+        raise SrtError("srt_area_mask_host refused the area or the frame")
+    return mask.astype(bool)
+
+
 def _ao_params(kw, who):
     """srt_ao_defaults() overridden by kw (samples, radius, bias, seed, background = 0xAARRGGBB) -> a records.AO_PARAMS record."""
     d = np.zeros((), R.AO_PARAMS)
@@ -939,6 +972,21 @@ def _bind(lib):
         lib.srt_group_read_ao_view.argtypes = [vp, vp]
         sizes = (sz * 1)()
         assert lib.srt_ao_sizes(sizes) == 0 and sizes[0] == R.AO_PARAMS.itemsize, tuple(sizes)
+    if hasattr(lib, "srt_area_coverage"):  # (likewise)
+        ip, szp = C.POINTER(C.c_int), C.POINTER(sz)
+        lib.srt_area_sizes.argtypes = [szp]
+        lib.srt_area_check_host.argtypes = [vp, vp]
+        lib.srt_area_mask_host.argtypes = [vp, vp, C.c_int, C.c_int, vp, sz]
+        for pre in ("srt_", "srt_group_"):
+            getattr(lib, pre + "area_coverage").argtypes = [vp, vp, vp, vp, vp, sz, vp]
+            getattr(lib, pre + "area_triangle_coverage").argtypes = [vp, vp, vp, vp, C.c_uint32, vp, sz, vp]
+            getattr(lib, pre + "select_area").argtypes = [vp, vp, vp, vp, C.c_int, C.c_uint32, szp]
+            getattr(lib, pre + "read_selection").argtypes = [vp, vp, sz, szp]
+        lib.srt_area_coverage_device.argtypes = [vp, vp, vp, vp, vp, sz, vp]
+        lib.srt_last_area_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        lib.srt_last_area_id_pass.argtypes = [vp, ip]
+        sizes = (sz * 2)()
+        assert lib.srt_area_sizes(sizes) == 0 and (sizes[0], sizes[1]) == (R.AREA.itemsize, R.AREA_SUMMARY.itemsize), tuple(sizes)
     return lib
 
 
@@ -1252,6 +1300,52 @@ class _Selection:
         return bool(a.value), bool(r.value)
 
 
+class _Area:
+    """Area selection (include/srt_abi.h "area selection"), shared by Tracer and TracerGroup (the group: its first member's planes,
+    scene and selection). rect = (x0, y0, x1, y1), half open, clipped to the frame; lasso: pixel-corner vertices (x, y) or None;
+    options: the camera and frame the ID planes are brought up to date for (default: self.options), False: the planes the handle
+    holds."""
+
+    def _area_args(self, rect, lasso, options):
+        a, v = area_record(rect, lasso)
+        rd = None if options is False else R.as_records(self.options if options is None else options, R.RENDER_DATA)
+        self._area_keep = (a, v, rd)
+        return (_ptr(rd) if rd is not None else None), _ptr(a), (_ptr(v) if v is not None else None)
+
+    def area_coverage(self, rect, lasso=None, options=None, n_shapes=None):
+        """Visible pixels per shape inside the area -> (counts (n_shapes,) uint32, summary dict). n_shapes: the scene's shape
+        count (default: self.scene_data's). Blocking."""
+        n = int(self.scene_data["num_shapes"]) if n_shapes is None else int(n_shapes)
+        counts, summary = np.zeros(n, np.uint32), np.zeros((), R.AREA_SUMMARY)
+        self._check(self._dn("area_coverage", *self._area_args(rect, lasso, options), _ptr(counts) if n else None, n, _ptr(summary)))
+        return counts, {k: int(summary[k]) for k in R.AREA_SUMMARY.names[:5]}
+
+    def area_triangle_coverage(self, shape, n_triangles, rect, lasso=None, options=None):
+        """Visible pixels per triangle of the model shape inside the area -> (counts (n_triangles,) uint32, summary dict).
+        n_triangles: at least the model's triangle count. Blocking."""
+        counts, summary = np.zeros(int(n_triangles), np.uint32), np.zeros((), R.AREA_SUMMARY)
+        self._check(self._dn("area_triangle_coverage", *self._area_args(rect, lasso, options), int(shape), _ptr(counts) if len(counts) else None,
+                             len(counts), _ptr(summary)))
+        return counts, {k: int(summary[k]) for k in R.AREA_SUMMARY.names[:5]}
+
+    def select_area(self, rect, lasso=None, mode=R.SELECT_REPLACE, min_pixels=1, options=None):
+        """Combine the shapes with at least min_pixels visible pixels inside the area with the current selection (mode:
+        records.SELECT_REPLACE, SELECT_ADD, SELECT_SUBTRACT, SELECT_TOGGLE) and overlay the result -> its length. Blocking."""
+        n = C.c_size_t(0)
+        self._check(self._dn("select_area", *self._area_args(rect, lasso, options), int(mode), int(min_pixels), C.byref(n)))
+        return n.value
+
+    def read_selection(self):
+        """The current selection -> (n,) uint32, ascending and unique; empty while the overlay is off."""
+        n = C.c_size_t(0)
+        self._check(self._dn("read_selection", None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint32)
+        self._check(self._dn("read_selection", _ptr(out) if n.value else None, n.value, C.byref(n)))
+        return out
+
+    area_mask = staticmethod(area_mask)
+
+
 class _AmbientOcclusion:
     """The ambient-occlusion pass (include/srt_abi.h "ambient-occlusion pass"), shared by Tracer and TracerGroup (the group: on
     its first member, which holds the whole scene). kw: srt_ao_defaults() overridden (samples, radius, bias, seed, background)."""
@@ -1287,7 +1381,7 @@ class _AmbientOcclusion:
     ao_table = staticmethod(ao_table)
 
 
-class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection, _AmbientOcclusion):
+class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection, _Area, _AmbientOcclusion):
     """Mirror of the reference's `class Tracer`. Field and method names are the
     reference's; records are numpy scalars of records.RENDER_DATA / SCENE_DATA."""
 
@@ -1771,6 +1865,23 @@ class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection, _Ambien
         self._check(self.lib.srt_read_selection_alpha(self._h, _ptr(out), out.size))
         return out
 
+    def area_coverage_device(self, counts_ptr, n, summary_ptr, rect, lasso=None, options=None):
+        """area_coverage left in device memory (n >= the scene's shape count uint32 at counts_ptr, 8 uint32 laid out as
+        records.AREA_SUMMARY at summary_ptr), enqueued on the handle's stream: synchronize() before they are read."""
+        self._check(self.lib.srt_area_coverage_device(self._h, *self._area_args(rect, lasso, options), C.c_void_p(counts_ptr), n, C.c_void_p(summary_ptr)))
+
+    def last_area_ms(self):
+        """Device time of the last coverage call's clear and counting launches under set_kernel_timers (0 without)."""
+        ms = C.c_float(0)
+        self._check(self.lib.srt_last_area_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def last_area_id_pass(self):
+        """Whether the last coverage call had to make the ID planes first."""
+        ran = C.c_int(0)
+        self._check(self.lib.srt_last_area_id_pass(self._h, C.byref(ran)))
+        return bool(ran.value)
+
     def last_ray_query_ms(self):
         """Device time of the last query's launches under set_kernel_timers (0 without)."""
         ms = C.c_float(0)
@@ -1782,7 +1893,7 @@ class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection, _Ambien
         self.owned_rows = self.lib.srt_partition_owned_rows(self.height, rank, world, rows_per_block)
 
 
-class TracerGroup(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection, _AmbientOcclusion):
+class TracerGroup(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection, _Area, _AmbientOcclusion):
     """One process driving several GPUs (srt_group_*): the reference's Tracer interface over a row partition,
     collected with one ncclGather per frame."""
 
