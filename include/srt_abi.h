@@ -1498,6 +1498,67 @@ int srt_last_area_ms(srt_tracer *t, float *ms);
 /* For tests: *id_pass_ran = 1 when the last coverage call on the handle had to make the ID planes first. */
 int srt_last_area_id_pass(const srt_tracer *t, int *id_pass_ran);
 
+/* ---- multi-hit ray queries (new): the first K hits along caller rays -------------------------------------------------------- */
+
+/* For each of n rays, the first k surfaces along it in order, not only the closest: click-through selection (the object under
+ * the one already selected, the shape seen through the glass sphere, the list for an "objects under the cursor" pop-up),
+ * dropping a dragged object along a ray while ignoring itself (the first record whose shape is not the dragged one), entry and
+ * exit distances of a body, and the number of surface crossings, whose parity says whether the origin is inside a closed mesh.
+ * Repeated casts cannot give this: a cast has no lower limit and no exclusion, and restarting the ray "a bit past" the last hit
+ * changes the ray's bits and loses coincident surfaces. Records: srt_ray, srt_ray_hit (srt_types.h), k of the latter per ray,
+ * k in 1 .. SRT_MULTI_HIT_MAX (8).
+ *
+ * THE ANSWER IS A SET OVER PRIMITIVES, ORDERED, so it does not depend on how the scene is traversed: the array scan, the host's
+ * SAH hierarchy, the device-built hierarchies and a refitted hierarchy give the same bytes.
+ * THE RAY is the cast's ("ray queries" above): the same validity rule, decided on the device; the same normalisation unless
+ * SRT_RAYS_UNIT_DIRECTIONS is given; tmax strict, and tmax <= 0 (-0 and -inf included) gives no hits.
+ * THE CANDIDATES of a ray are the primitives whose own intersector accepts the ray and for whose t the comparison t < tmax is
+ * true (so a NaN t is no candidate):
+ *   - every sphere, by intersect_sphere (render.cl:180-204): ONE hit per sphere, the nearer root when it is not negative, else
+ *     the farther one -- the exit when the origin is inside;
+ *   - every plane, by intersect_plane (render.cl:206-221);
+ *   - every triangle, by intersect_triangle (render.cl:243-275) on the world triangle, of every model whose bounding box passes
+ *     intersection_aabb(bounds, origin, 1 / direction, tmax) (render.cl:279-290) with the CALLER'S tmax as the limit.
+ *     The cast tests a model's box against its SHRINKING closest distance instead; that is a different statement. The two can
+ *     differ only when a box's entry distance rounds past a hit that lies on the box's surface: the cast then skips the model,
+ *     this query, whose limit for the box does not depend on what was found before, keeps the hit. With k = 1 record 0 is
+ *     otherwise the cast's record.
+ * THE ORDER. Candidates are ordered by t compared as floats; equal t (-0 == +0) goes to the lower shape index; inside a model
+ * equal t goes to the lower triangle index inside the model. Two triangles that share an edge the ray passes through are two
+ * candidates and two records.
+ * THE RECORDS. hits[q * k + j] is candidate j of ray q in that order, for j < min(k, #candidates), with the cast's fields: t as
+ * the intersector computed it, the winner_normal of the primitive at origin + direction * t turned to face the ray,
+ * SRT_HIT_HIT, SRT_HIT_FRONT by the cast's rule, the triangle index inside its model, the per-triangle material rule, and a
+ * shape WITHOUT a material reported with material = -1. The remaining slots hold the cast's miss record. An invalid ray has
+ * the miss record with SRT_HIT_INVALID_RAY in all k slots and count 0.
+ * COUNTS. counts[q] (counts may be NULL: not written) is the number of records written, min(k, #candidates). With
+ * SRT_RAYS_COUNT_ALL it is #candidates, which may exceed k; the records are the same bytes either way. (The flag keeps the
+ * walk's limit at tmax: every candidate has to be met to be counted.)
+ * STATE, HOSTILE RAYS. As a cast: the scene as the last srt_update_scene left it, ordered on the handle's stream; nothing is
+ * written but the outputs and the queries' shared staging allocation; before any scene is set every valid ray has no hits.
+ * srt_last_ray_query_ms covers the launches.
+ * COUNTS AND ERRORS. n == 0: SRT_OK, no launch. k outside 1 .. SRT_MULTI_HIT_MAX, flag bits other than
+ * SRT_RAYS_UNIT_DIRECTIONS | SRT_RAYS_COUNT_ALL, a null rays or hits pointer with n > 0, n >= 2^31, device rays or hits not
+ * aligned to 16 bytes, device counts not aligned to 4: SRT_ERR_INVALID. The host forms use the handle's one staging allocation
+ * (per ray 32 B of rays, 32 k B of records, 4 B of counts -- that region rounded up to 8 bytes -- and the 8 B of a picked point,
+ * reserved by both forms though only srt_pick_through writes them: 44 B + 32 k B), grown as needed; what the other calls get of
+ * it does not change.
+ *
+ * srt_cast_rays_multi: host arrays, blocking. srt_cast_rays_multi_device: n srt_ray, n * k srt_ray_hit and n words in device
+ * memory of the handle's device, asynchronous on the handle's stream. srt_pick_through: srt_pick's rays (the same small kernel,
+ * the same `options` and xy), then this query with unit directions and tmax = +inf; blocking. */
+int srt_cast_rays_multi(srt_tracer *t, const srt_ray *rays, size_t n, uint32_t k, uint32_t flags, srt_ray_hit *hits /* n * k */,
+                        uint32_t *counts /* n, may be NULL */);
+int srt_cast_rays_multi_device(srt_tracer *t, const void *rays_dev, size_t n, uint32_t k, uint32_t flags, void *hits_dev, void *counts_dev /* may be NULL */);
+int srt_pick_through(srt_tracer *t, const srt_render_data *options, const float *xy, size_t n, uint32_t k, srt_ray_hit *hits, uint32_t *counts /* may be NULL */);
+/* On the group's first member, as srt_group_cast_rays. */
+int srt_group_cast_rays_multi(srt_group *g, const srt_ray *rays, size_t n, uint32_t k, uint32_t flags, srt_ray_hit *hits, uint32_t *counts);
+int srt_group_pick_through(srt_group *g, const srt_render_data *options, const float *xy, size_t n, uint32_t k, srt_ray_hit *hits, uint32_t *counts);
+/* Host-only: the argument check every call above applies to k and flags. */
+int srt_multi_hit_check_host(uint32_t k, uint32_t flags);
+/* Host-only: out = {sizeof(srt_ray), sizeof(srt_ray_hit), SRT_MULTI_HIT_MAX} as the library was built. */
+int srt_multi_hit_sizes(size_t out[3]);
+
 /* Library / build identification, e.g. "srt-hip gfx950 parity fp-contract=off". */
 const char *srt_version(void);
 

@@ -239,6 +239,10 @@ typedef struct srt_ray_hit {
 #define SRT_HIT_HIT 1u
 #define SRT_HIT_FRONT 2u
 #define SRT_HIT_INVALID_RAY 4u
+/* Multi-hit ray queries (srt_cast_rays_multi, srt_pick_through; include/srt_abi.h "multi-hit ray queries"): the same two
+ * records, k srt_ray_hit per ray. */
+#define SRT_MULTI_HIT_MAX 8u  /* the largest k */
+#define SRT_RAYS_COUNT_ALL 2u /* per call, multi-hit only: counts[q] is the size of the whole candidate set, not min(k, that) */
 
 /* Occlusion queries (srt_occluded_segments, srt_segment_rays; include/srt_abi.h "occlusion queries"): is anything between
  * `from` and the point end_gap short of `to`. 32 bytes, read by the device as two 128-bit words. */

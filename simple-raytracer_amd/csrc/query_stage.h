@@ -48,6 +48,25 @@ static inline QueryStage query_stage(size_t n) { // n < 2^31 (the calls' own che
 	return s;
 }
 
+// srt_cast_rays_multi and srt_pick_through (multi_hit.hip) lay the same allocation out for n rays of k records each:
+//   [0, 32 n)               rays     n srt_ray
+//   [32 n, 32 n + 32 n k)   hits     n k srt_ray_hit
+//   [.., + 4 n)             counts   n words
+//   [.., + 8 n)             xy       n points of 8 bytes (srt_pick_through), 8-byte aligned
+struct MultiStage {
+	size_t rays, hits, counts, xy; // byte offsets
+	size_t total;                  // bytes
+};
+static inline MultiStage multi_stage(size_t n, size_t k) { // n < 2^31, k <= 8 (the calls' own checks)
+	MultiStage s;
+	s.rays = 0;
+	s.hits = 32 * n;
+	s.counts = s.hits + 32 * n * k;
+	s.xy = s.counts + 8 * ((n + 1) / 2);
+	s.total = s.xy + 8 * n;
+	return s;
+}
+
 struct NearestStage {
 	size_t points, nearest; // byte offsets inside query_stage(n).total
 };

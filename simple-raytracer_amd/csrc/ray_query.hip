@@ -130,6 +130,18 @@ int enqueue_cast(srt_tracer *t, const void *rays_dev, size_t n, uint32_t flags, 
 
 } // namespace
 
+int srt_enqueue_pick_rays(srt_tracer *t, const srt_render_data *options, const void *xy_dev, size_t n, void *rays_dev) {
+	PickParams pp;
+	memset(&pp, 0, sizeof pp);
+	pp.tp = srt_trace_params_for_query(t, options);
+	pp.xy = static_cast<const float2 *>(xy_dev);
+	pp.rays = static_cast<float4 *>(rays_dev);
+	pp.n = (uint32_t)n;
+	query_launch(srt_pick_rays_kernel, pp, pp.n, t->stream);
+	SRT_HIP(t, hipGetLastError());
+	return SRT_OK;
+}
+
 extern "C" {
 
 int srt_ray_query_sizes(size_t out[2]) {
@@ -181,14 +193,7 @@ int srt_pick(srt_tracer *t, const srt_render_data *options, const float *xy, siz
 	uint8_t *const stage = t->rq_stage.ptr;
 	SRT_HIP(t, hipMemcpyAsync(stage + st.xy, xy, n * 2 * sizeof(float), hipMemcpyHostToDevice, t->stream));
 	if (const int rc = query_span_begin(t)) return rc;
-	PickParams pp;
-	memset(&pp, 0, sizeof pp);
-	pp.tp = srt_trace_params_for_query(t, options);
-	pp.xy = reinterpret_cast<const float2 *>(stage + st.xy);
-	pp.rays = reinterpret_cast<float4 *>(stage + st.rays);
-	pp.n = (uint32_t)n;
-	query_launch(srt_pick_rays_kernel, pp, pp.n, t->stream);
-	SRT_HIP(t, hipGetLastError());
+	if (const int rc = srt_enqueue_pick_rays(t, options, stage + st.xy, n, stage + st.rays)) return rc;
 	if (const int rc = enqueue_cast(t, stage + st.rays, n, SRT_RAYS_UNIT_DIRECTIONS, stage + st.hits)) return rc;
 	if (const int rc = query_span_end(t)) return rc;
 	SRT_HIP(t, hipMemcpyAsync(hits, stage + st.hits, n * sizeof(srt_ray_hit), hipMemcpyDeviceToHost, t->stream));

@@ -572,6 +572,12 @@ int srt_group_read_selection(srt_group *g, uint32_t *shapes, size_t cap, size_t 
 // ---- the first member again: every member holds the whole scene, and a query ignores the partition. Ray queries (ray_query.hip),
 // nearest-surface queries (nearest.hip), occlusion queries (occlusion.hip), the ambient-occlusion pass (ao.hip) ----
 int srt_group_cast_rays(srt_group *g, const srt_ray *rays, size_t n, uint32_t flags, srt_ray_hit *hits) { return first_member(g, srt_cast_rays, rays, n, flags, hits); }
+int srt_group_cast_rays_multi(srt_group *g, const srt_ray *rays, size_t n, uint32_t k, uint32_t flags, srt_ray_hit *hits, uint32_t *counts) {
+	return first_member(g, srt_cast_rays_multi, rays, n, k, flags, hits, counts);
+}
+int srt_group_pick_through(srt_group *g, const srt_render_data *options, const float *xy, size_t n, uint32_t k, srt_ray_hit *hits, uint32_t *counts) {
+	return first_member(g, srt_pick_through, options, xy, n, k, hits, counts);
+}
 int srt_group_pick(srt_group *g, const srt_render_data *options, const float *xy, size_t n, srt_ray_hit *hits) {
 	return first_member(g, srt_pick, options, xy, n, hits);
 }

@@ -514,6 +514,9 @@ extern "C" int srt_trace_fused(srt_tracer *t, const srt_render_data *options, ui
 /* srt_abi.hip: trace_params_of for a caller outside it (ray_query.hip) -- the scene buffers and camera set-up a dispatch of
  * `options` over the handle's current scene would be handed; the batch's fields stay zero */
 TraceParams srt_trace_params_for_query(const srt_tracer *t, const srt_render_data *options);
+/* ray_query.hip: srt_pick's ray set-up for a caller outside it (multi_hit.hip) -- srt_pick_rays_kernel over n points at xy_dev
+ * into n srt_ray at rays_dev, enqueued on the handle's stream (the caller has checked `options` and set the device) */
+int srt_enqueue_pick_rays(srt_tracer *t, const srt_render_data *options, const void *xy_dev, size_t n, void *rays_dev);
 /* one scene for several handles: the host pass once (members[0]'s acceleration mode and hierarchy cache), the uploads of all
  * members enqueued before the first is waited for (srt_abi.hip; srt_group_update_scene). *failed_member = the member an error came from */
 extern "C" int srt_update_scene_many(srt_tracer *const *members, size_t n_members, const srt_shape *shapes, size_t n_shapes, const srt_triangle *triangles,

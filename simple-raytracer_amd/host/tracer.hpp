@@ -521,6 +521,29 @@ class Tracer {
 		return hits;
 	}
 	srt_ray_hit pick(float x, float y) { return pick(std::vector<float>{x, y})[0]; }
+	/// Multi-hit ray queries (srt_cast_rays_multi): the first k hits along each ray in order, hits[q * k + j] the j-th of ray q,
+	/// the slots past a ray's last hit holding the miss record; counts (may be null) gets the records written per ray, or with
+	/// count_all the size of the ray's whole candidate set. k in 1 .. SRT_MULTI_HIT_MAX. Blocking.
+	std::vector<srt_ray_hit> cast_multi(const std::vector<srt_ray> &rays, uint32_t k, std::vector<uint32_t> *counts = nullptr, bool unit_directions = false,
+	                                    bool count_all = false) {
+		std::vector<srt_ray_hit> hits(rays.size() * k);
+		if (counts) counts->assign(rays.size(), 0u);
+		const uint32_t flags = (unit_directions ? SRT_RAYS_UNIT_DIRECTIONS : 0u) | (count_all ? SRT_RAYS_COUNT_ALL : 0u);
+		uint32_t *c = counts ? counts->data() : nullptr;
+		check(group ? srt_group_cast_rays_multi(group, rays.data(), rays.size(), k, flags, hits.data(), c)
+		            : srt_cast_rays_multi(handle, rays.data(), rays.size(), k, flags, hits.data(), c));
+		return hits;
+	}
+	/// Click-through picking (srt_pick_through): the first k hits under image points, xy as pick takes it. Blocking.
+	std::vector<srt_ray_hit> pick_through(const std::vector<float> &xy, uint32_t k, std::vector<uint32_t> *counts = nullptr) {
+		const size_t n = xy.size() / 2;
+		std::vector<srt_ray_hit> hits(n * k);
+		if (counts) counts->assign(n, 0u);
+		const srt_render_data *rd = reinterpret_cast<const srt_render_data *>(&options);
+		uint32_t *c = counts ? counts->data() : nullptr;
+		check(group ? srt_group_pick_through(group, rd, xy.data(), n, k, hits.data(), c) : srt_pick_through(handle, rd, xy.data(), n, k, hits.data(), c));
+		return hits;
+	}
 	/// Nearest-surface queries (srt_nearest_points): the closest scene point to each query point, closer than its max_distance
 	/// -- what snapping and clearance checks ask. skip_shape: a shape left out (the one being dragged). Blocking.
 	std::vector<srt_nearest> nearest(const std::vector<srt_point_query> &queries, uint32_t skip_shape = SRT_HIT_NONE) {

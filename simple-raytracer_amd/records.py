@@ -71,6 +71,8 @@ RAY_HIT = np.dtype({"names": ["t", "shape", "triangle", "material", "normal", "f
                     "formats": [np.float32, np.uint32, np.uint32, np.int32, F3, np.uint32], "offsets": [0, 4, 8, 12, 16, 28], "itemsize": 32})
 HIT_NONE = 0xFFFFFFFF  # RAY_HIT shape / triangle of a miss (triangle: also of a sphere or a plane)
 RAYS_UNIT_DIRECTIONS = 1
+RAYS_COUNT_ALL = 2  # multi-hit queries: counts are the whole candidate set's size
+MULTI_HIT_MAX = 8  # the largest k of a multi-hit query
 HIT_HIT, HIT_FRONT, HIT_INVALID_RAY = 1, 2, 4
 # srt_segment (occlusion queries: Tracer.occluded_segments, Tracer.segment_rays), 32 bytes; "from" is the start point
 SEGMENT = np.dtype({"names": ["from", "end_gap", "to", "reserved"], "formats": [F3, np.float32, F3, np.float32],

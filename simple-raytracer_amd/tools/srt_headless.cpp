@@ -29,6 +29,8 @@
 //                One device only.
 // --noise-view f.ppm: the heat map of the final accumulation's noise (Tracer::resolve_noise_view): green four octaves below the
 //                threshold, red four above, magenta where the estimate is not finite. Turns the denoiser on like --until-noise.
+// --pick-through X,Y[:K] (may be given several times): the first K (default 8, 1 .. 8) hits under the image point in order
+//                (Tracer::pick_through): one line per record in --pick's format, then the count. Click-through selection.
 // --pick X,Y (may be given several times): after the scene is loaded, the hit under the image point (X, Y) -- continuous pixel
 //                coordinates, a pixel's centre is (px + 0.5, py + 0.5) -- through the first frame's camera (Tracer::pick); one line
 //                per pick: shape, triangle, material (-1: none), t, position, normal. Then the frames render as before.
@@ -184,6 +186,8 @@ int main(int argc, char **argv) {
 	uint32_t bvh_build_min = 0;
 	int bvh_order = SRT_BUILD_ORDER_MORTON;
 	std::vector<float> picks; // --pick X,Y: x0, y0, x1, y1, ...
+	std::vector<float> through;      // --pick-through X,Y[:K]: x0, y0, x1, y1, ...
+	std::vector<unsigned> through_k; // ... its K
 	std::vector<srt_point_query> nearests; // --nearest X,Y,Z[:RADIUS[:SKIP]]
 	std::vector<uint32_t> nearest_skips;   // ... its SKIP (SRT_HIT_NONE: none)
 	std::vector<srt_segment> sights; // --line-of-sight
@@ -364,6 +368,15 @@ int main(int argc, char **argv) {
 			}
 			picks.push_back(x), picks.push_back(y);
 		}
+		else if (a == "--pick-through") { // X,Y[:K]
+			float x = 0.f, y = 0.f;
+			unsigned k = SRT_MULTI_HIT_MAX;
+			if (std::sscanf(next(), "%f,%f:%u", &x, &y, &k) < 2 || k < 1u || k > SRT_MULTI_HIT_MAX) {
+				std::cerr << "--pick-through takes X,Y[:K] with K in 1 .. 8\n";
+				return 2;
+			}
+			through.push_back(x), through.push_back(y), through_k.push_back(k);
+		}
 		else if (a == "--nearest") { // X,Y,Z[:RADIUS[:SKIP]]
 			srt_point_query pq{{0.f, 0.f, 0.f}, INFINITY};
 			unsigned skip = SRT_HIT_NONE;
@@ -386,7 +399,7 @@ int main(int argc, char **argv) {
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--ao S[:RADIUS[:BIAS]]] [--ao-view f.ppm] [--select I[,J...][:WIDTH[:RRGGBBAA]]] [--select-area X0,Y0:X1,Y1[:MODE[:MINPIXELS]] [--lasso X,Y;X,Y;...]] [--pick X,Y]... [--nearest X,Y,Z[:RADIUS[:SKIP]]]... [--line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP]]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
+			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--ao S[:RADIUS[:BIAS]]] [--ao-view f.ppm] [--select I[,J...][:WIDTH[:RRGGBBAA]]] [--select-area X0,Y0:X1,Y1[:MODE[:MINPIXELS]] [--lasso X,Y;X,Y;...]] [--pick X,Y]... [--pick-through X,Y[:K]]... [--nearest X,Y,Z[:RADIUS[:SKIP]]]... [--line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP]]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
@@ -645,7 +658,7 @@ int main(int argc, char **argv) {
 		std::printf("area selection: %zu shape(s)\n", n);
 	}
 
-	if (!picks.empty()) { // --pick: what is under these image points, through the first frame's camera
+	if (!picks.empty() || !through.empty()) { // --pick, --pick-through: what is under these image points, through the first frame's camera
 		tracer.update_scene(shapes, triangles, materials.list);
 		auto &options = tracer.options;
 		options.aspect_ratio = (float)width / (float)height;
@@ -661,17 +674,26 @@ int main(int argc, char **argv) {
 			srt_ray r{{o.x, o.y, o.z}, INFINITY, {d.x, d.y, d.z}, 0u};
 			return r;
 		};
-		const std::vector<srt_ray_hit> hits = tracer.pick(picks);
+		auto print_hit = [&](const char *what, float x, float y, const srt_ray_hit &h) {
+			const srt_ray r = ray_of(x, y);
+			std::printf("%s %g,%g: shape %u triangle %d material %d t %.9g position %.9g %.9g %.9g normal %.9g %.9g %.9g\n", what, x, y, h.shape,
+			            h.triangle == SRT_HIT_NONE ? -1 : (int)h.triangle, h.material, h.t, r.origin[0] + r.direction[0] * h.t,
+			            r.origin[1] + r.direction[1] * h.t, r.origin[2] + r.direction[2] * h.t, h.normal[0], h.normal[1], h.normal[2]);
+		};
+		const std::vector<srt_ray_hit> hits = picks.empty() ? std::vector<srt_ray_hit>() : tracer.pick(picks);
 		for (size_t k = 0; k < hits.size(); k++) {
-			const srt_ray_hit &h = hits[k];
-			if (!(h.flags & SRT_HIT_HIT)) {
+			if (!(hits[k].flags & SRT_HIT_HIT)) {
 				std::printf("pick %g,%g: miss\n", picks[2 * k], picks[2 * k + 1]);
 				continue;
 			}
-			const srt_ray r = ray_of(picks[2 * k], picks[2 * k + 1]);
-			std::printf("pick %g,%g: shape %u triangle %d material %d t %.9g position %.9g %.9g %.9g normal %.9g %.9g %.9g\n", picks[2 * k], picks[2 * k + 1],
-			            h.shape, h.triangle == SRT_HIT_NONE ? -1 : (int)h.triangle, h.material, h.t, r.origin[0] + r.direction[0] * h.t,
-			            r.origin[1] + r.direction[1] * h.t, r.origin[2] + r.direction[2] * h.t, h.normal[0], h.normal[1], h.normal[2]);
+			print_hit("pick", picks[2 * k], picks[2 * k + 1], hits[k]);
+		}
+		for (size_t q = 0; q < through_k.size(); q++) { // one record per line, nearest first, then how many there were
+			const float x = through[2 * q], y = through[2 * q + 1];
+			std::vector<uint32_t> counts;
+			const std::vector<srt_ray_hit> recs = tracer.pick_through(std::vector<float>{x, y}, through_k[q], &counts);
+			for (uint32_t j = 0; j < counts[0]; j++) print_hit("pick-through", x, y, recs[j]);
+			std::printf("pick-through %g,%g: %u hit(s)\n", x, y, counts[0]);
 		}
 	}
 

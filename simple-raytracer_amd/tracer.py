@@ -86,6 +86,8 @@ ABI_SYMBOLS = [
     "srt_area_sizes", "srt_area_check_host", "srt_area_mask_host", "srt_area_coverage", "srt_area_triangle_coverage",
     "srt_area_coverage_device", "srt_select_area", "srt_read_selection", "srt_group_area_coverage", "srt_group_area_triangle_coverage",
     "srt_group_select_area", "srt_group_read_selection", "srt_last_area_ms", "srt_last_area_id_pass",
+    "srt_cast_rays_multi", "srt_cast_rays_multi_device", "srt_pick_through", "srt_group_cast_rays_multi", "srt_group_pick_through",
+    "srt_multi_hit_check_host", "srt_multi_hit_sizes",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -987,6 +989,15 @@ def _bind(lib):
         lib.srt_last_area_id_pass.argtypes = [vp, ip]
         sizes = (sz * 2)()
         assert lib.srt_area_sizes(sizes) == 0 and (sizes[0], sizes[1]) == (R.AREA.itemsize, R.AREA_SUMMARY.itemsize), tuple(sizes)
+    if hasattr(lib, "srt_cast_rays_multi"):  # (likewise)
+        for pre in ("srt_", "srt_group_"):
+            getattr(lib, pre + "cast_rays_multi").argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp]
+            getattr(lib, pre + "pick_through").argtypes = [vp, vp, vp, sz, C.c_uint32, vp, vp]
+        lib.srt_cast_rays_multi_device.argtypes = [vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp]
+        lib.srt_multi_hit_check_host.argtypes = [C.c_uint32, C.c_uint32]
+        lib.srt_multi_hit_sizes.argtypes = [C.POINTER(sz)]
+        sizes = (sz * 3)()
+        assert lib.srt_multi_hit_sizes(sizes) == 0 and tuple(sizes) == (R.RAY.itemsize, R.RAY_HIT.itemsize, R.MULTI_HIT_MAX), tuple(sizes)
     return lib
 
 
@@ -1232,6 +1243,34 @@ class _RayQuery:
         hits = np.zeros(len(xy), R.RAY_HIT)
         self._check(self._dn("pick", _ptr(rd), _ptr(xy) if len(xy) else None, len(xy), _ptr(hits) if len(xy) else None))
         return hits
+
+    # ---- multi-hit ray queries (include/srt_abi.h "multi-hit ray queries") ----
+    def cast_rays_multi(self, origins, directions=None, k=1, tmax=np.inf, unit=False, count_all=False):
+        """The first k hits along each ray in order -> (hits, counts): a records.RAY_HIT array of shape (n, k), the slots past
+        a ray's last hit holding the miss record, and counts (n,) uint32 -- the records written, or with count_all=True the
+        size of the ray's whole candidate set, which may exceed k. Rays as cast_rays takes them; k in 1 .. MULTI_HIT_MAX.
+        Blocking."""
+        rays = R.as_records(origins, R.RAY) if directions is None else R.rays(origins, directions, tmax)
+        n, k = len(rays), int(k)
+        hits, counts = np.zeros((n, max(k, 0)), R.RAY_HIT), np.zeros(n, np.uint32)
+        self._check(self._dn("cast_rays_multi", _ptr(rays) if n else None, n, k, self._multi_flags(unit, count_all), _ptr(hits) if n else None,
+                             _ptr(counts) if n else None))
+        return hits, counts
+
+    def pick_through(self, xy, k, options=None):
+        """The first k hits under image points -> (hits (n, k), counts (n,)), as cast_rays_multi; xy and options as pick.
+        Blocking."""
+        xy = np.ascontiguousarray(np.atleast_2d(np.asarray(xy, np.float32)))
+        assert xy.ndim == 2 and xy.shape[1] == 2, xy.shape
+        rd = R.as_records(self.options if options is None else options, R.RENDER_DATA)
+        n, k = len(xy), int(k)
+        hits, counts = np.zeros((n, max(k, 0)), R.RAY_HIT), np.zeros(n, np.uint32)
+        self._check(self._dn("pick_through", _ptr(rd), _ptr(xy) if n else None, n, k, _ptr(hits) if n else None, _ptr(counts) if n else None))
+        return hits, counts
+
+    @staticmethod
+    def _multi_flags(unit, count_all):
+        return (R.RAYS_UNIT_DIRECTIONS if unit else 0) | (R.RAYS_COUNT_ALL if count_all else 0)
 
     # ---- nearest-surface queries (include/srt_abi.h "nearest-surface queries") ----
     def nearest_points(self, points, max_distance=np.inf, skip_shape=None):
@@ -1840,6 +1879,12 @@ class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection, _Area, 
         """cast_rays over device arrays (n records.RAY at rays_ptr, n records.RAY_HIT at hits_ptr, 16-byte aligned), enqueued
         on the handle's stream: synchronize() before the hits are read."""
         self._check(self.lib.srt_cast_rays_device(self._h, C.c_void_p(rays_ptr), n, R.RAYS_UNIT_DIRECTIONS if unit else 0, C.c_void_p(hits_ptr)))
+
+    def cast_rays_multi_device(self, rays_ptr, n, k, hits_ptr, counts_ptr=None, unit=False, count_all=False):
+        """cast_rays_multi over device arrays (n records.RAY at rays_ptr, n * k records.RAY_HIT at hits_ptr, 16-byte aligned;
+        if given, n uint32 at counts_ptr), enqueued on the handle's stream: synchronize() before they are read."""
+        self._check(self.lib.srt_cast_rays_multi_device(self._h, C.c_void_p(rays_ptr), n, int(k), self._multi_flags(unit, count_all), C.c_void_p(hits_ptr),
+                                                        C.c_void_p(counts_ptr) if counts_ptr else None))
 
     def nearest_points_device(self, queries_ptr, n, out_ptr, skip_shape=None):
         """nearest_points over device arrays (n records.POINT_QUERY at queries_ptr, n records.NEAREST at out_ptr, 16-byte
