@@ -1559,6 +1559,65 @@ int srt_multi_hit_check_host(uint32_t k, uint32_t flags);
 /* Host-only: out = {sizeof(srt_ray), sizeof(srt_ray_hit), SRT_MULTI_HIT_MAX} as the library was built. */
 int srt_multi_hit_sizes(size_t out[3]);
 
+/* ---- area selection, through (new): coverage of shapes hidden behind others -------------------------------------------------
+ * The selection mode modellers call X-ray or "select through": every shape, or every face of one mesh, that lies inside the
+ * marquee or lasso, the ones BEHIND other shapes included -- back faces, objects inside a glass sphere, a mesh behind a wall.
+ * "area selection" above counts what is visible, from the ID planes; this counts over each pixel ray's whole candidate set, so
+ * there are no ID planes and no key. Records as above. Everything is an integer.
+ *
+ * THE AREA M(p) is the one "area selection" defines: the same srt_area (flags still 0), the same srt_area_check_host, the same
+ * integer lasso (csrc/area_host.h, compiled into these kernels too).
+ * THE FRAME comes from `options`, which is REQUIRED (NULL: SRT_ERR_INVALID): the rectangle is clipped against options->width x
+ * options->height, which must be positive and below 2^31 pixels.
+ * THE RAY OF p is the ID pass's: the image point (px + 0.5, py + 0.5) through srt_pick's ray set-up (device_math.h camera_ray),
+ * refused by the cast's validity rule on the device, unit direction, tmax = +inf. srt_pick_rays returns exactly these rays.
+ * CANDIDATES. cand(p) is the candidate set of that ray exactly as "multi-hit ray queries" defines it: each primitive's own
+ * intersector with t < tmax true, a model's triangles only when intersection_aabb passes with the caller's tmax (+inf here). A
+ * refused ray has no candidates.
+ * SHAPE COVERAGE, THROUGH, n_shapes = the scene's shape count:
+ *   counts[s] = #{p : M(p), some candidate of p belongs to shape s} -- a pixel counts a shape ONCE however many of its triangles
+ *   the ray crosses;  area_pixels = #M;  miss_pixels = #{M, cand(p) empty};  hit_pixels = area_pixels - miss_pixels (NOT
+ *   sum(counts): a pixel may count several shapes);  distinct = #{s : counts[s] > 0};  target_pixels = 0.
+ * TRIANGLE COVERAGE, THROUGH, of one model shape s0, n_tri = the triangles of the shape's model:
+ *   counts[k] = #{p : M(p), triangle k of s0 is a candidate of p} -- back-facing and hidden faces included; only s0 is walked;
+ *   miss_pixels = #{M, s0 has no candidate on p};  hit_pixels = target_pixels = area_pixels - miss_pixels, which counts PIXELS,
+ *   not sum(counts), which may be larger;  distinct = #{k : counts[k] > 0}. s0 not a model shape: SRT_ERR_INVALID.
+ * ACCELERATION MODES. Both coverages are sets over primitives: the array scan, the host's SAH hierarchy, the device-built
+ * Morton and median hierarchies and refitted hierarchies give the same integers.
+ * INFINITE PLANES. A plane the frame faces is a candidate of most pixels, visible or not -- the floor under everything, the wall
+ * behind everything. Front-ends that select through filter such planes with min_pixels or by the shape's type.
+ * THE KERNELS (csrc/area_through.hip) use the area kernel's mapping (the clipped rectangle only, a wave per 64 pixels of one
+ * row). Per shape and wave ONE atomic adds the popcount of a ballot; a model is asked for existence only (the any-hit walk). In
+ * triangle mode every accepted triangle is one atomic on its index. Every index is compared with the count array's length
+ * before its atomic.
+ * STATE. As a cast: the scene as the last srt_update_scene left it, ordered on the handle's stream. The calls write their own
+ * result buffers (shared with "area selection") and nothing else: ID planes, selection (except srt_select_area_through), canvas,
+ * counters, denoiser, exposure, bloom, noise and AO state stay untouched. A handle that never calls these launches what it
+ * launched before. Before any scene is set every pixel is a miss. srt_last_area_ms covers these launches;
+ * srt_last_area_id_pass answers 0 after them.
+ * ERRORS. As "area selection", and options == NULL. flags = 1 in the srt_area stays refused. */
+int srt_area_coverage_through(srt_tracer *t, const srt_render_data *options, const srt_area *area, const int32_t *vertices, uint32_t *counts, size_t cap_shapes,
+                              srt_area_summary *out);
+int srt_area_triangle_coverage_through(srt_tracer *t, const srt_render_data *options, const srt_area *area, const int32_t *vertices, uint32_t shape,
+                                       uint32_t *counts, size_t cap_triangles, srt_area_summary *out);
+/* As srt_area_coverage_device: all n >= n_shapes words of d_counts are zeroed, n_shapes counted; asynchronous. */
+int srt_area_coverage_through_device(srt_tracer *t, const srt_render_data *options, const srt_area *area, const int32_t *vertices, uint32_t *d_counts, size_t n,
+                                     uint32_t *d_summary);
+/* Blocking. srt_select_area's four modes and rules applied to the through counts. Mind the infinite planes (above). */
+int srt_select_area_through(srt_tracer *t, const srt_render_data *options, const srt_area *area, const int32_t *vertices, int mode, uint32_t min_pixels,
+                            size_t *n_selected);
+/* On the group's first member, as srt_group_area_coverage. */
+int srt_group_area_coverage_through(srt_group *g, const srt_render_data *options, const srt_area *area, const int32_t *vertices, uint32_t *counts,
+                                    size_t cap_shapes, srt_area_summary *out);
+int srt_group_area_triangle_coverage_through(srt_group *g, const srt_render_data *options, const srt_area *area, const int32_t *vertices, uint32_t shape,
+                                             uint32_t *counts, size_t cap_triangles, srt_area_summary *out);
+int srt_group_select_area_through(srt_group *g, const srt_render_data *options, const srt_area *area, const int32_t *vertices, int mode, uint32_t min_pixels,
+                                  size_t *n_selected);
+/* The rays srt_pick would cast for n image points xy (its small kernel, the same `options`): n srt_ray with unit directions and
+ * tmax = +inf into rays_out; cast them with SRT_RAYS_UNIT_DIRECTIONS. Blocking; counts, errors and staging as srt_pick. */
+int srt_pick_rays(srt_tracer *t, const srt_render_data *options, const float *xy, size_t n, srt_ray *rays_out);
+int srt_group_pick_rays(srt_group *g, const srt_render_data *options, const float *xy, size_t n, srt_ray *rays_out);
+
 /* Library / build identification, e.g. "srt-hip gfx950 parity fp-contract=off". */
 const char *srt_version(void);
 

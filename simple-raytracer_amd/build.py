@@ -23,8 +23,8 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIBDIR = PKG / "lib"
 LIB = LIBDIR / "libsrt_hip.so"
-SOURCES = ["kernels.hip", "kernels_tex.hip", "frame.hip", "selftest.hip", "srt_abi.hip", "accel_device.hip", "bvh_refit.hip", "bvh_build.hip", "bvh_host.cpp", "scene_prep.cpp", "srt_texture.hip", "srt_collect.hip", "srt_group.hip", "frame_pipeline.hip", "denoise.hip", "temporal.hip", "exposure.hip", "bloom.hip", "noise_meter.hip", "ray_query.hip", "occlusion.hip", "selection.hip", "ao.hip", "nearest.hip", "area.hip", "multi_hit.hip"]
-HEADERS = ["detmath.h", "device_types.h", "device_math.h", "device_intersect.h", "device_anyhit.h", "device_multihit.h", "device_shading.h", "device_nearest.h", "nearest_math.h", "trace_regions.h", "srt_internal.h", "collect_internal.h", "bvh_device.h", "bvh_host.h", "scene_prep.h", "trace_plan.h", "denoise_plan.h", "selection_host.h", "ao_host.h", "area_host.h", "query_host.h", "query_stage.h", "tonemap.h", "issue_probe.h", "features_body.inc", "trace_body.inc", "closest_hit.inc", "ray_valid.inc", "../../include/srt_abi.h", "../../include/srt_types.h"]
+SOURCES = ["kernels.hip", "kernels_tex.hip", "frame.hip", "selftest.hip", "srt_abi.hip", "accel_device.hip", "bvh_refit.hip", "bvh_build.hip", "bvh_host.cpp", "scene_prep.cpp", "srt_texture.hip", "srt_collect.hip", "srt_group.hip", "frame_pipeline.hip", "denoise.hip", "temporal.hip", "exposure.hip", "bloom.hip", "noise_meter.hip", "ray_query.hip", "occlusion.hip", "selection.hip", "ao.hip", "nearest.hip", "area.hip", "multi_hit.hip", "area_through.hip"]
+HEADERS = ["detmath.h", "device_types.h", "device_math.h", "device_intersect.h", "device_anyhit.h", "device_multihit.h", "device_shading.h", "device_nearest.h", "nearest_math.h", "trace_regions.h", "srt_internal.h", "collect_internal.h", "bvh_device.h", "bvh_host.h", "scene_prep.h", "trace_plan.h", "denoise_plan.h", "selection_host.h", "ao_host.h", "area_host.h", "area_through_host.h", "query_host.h", "query_stage.h", "tonemap.h", "issue_probe.h", "features_body.inc", "trace_body.inc", "closest_hit.inc", "ray_valid.inc", "../../include/srt_abi.h", "../../include/srt_types.h"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-fno-gpu-rdc", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-pthread", "-Rpass-analysis=kernel-resource-usage"]  # -pthread: the host BVH build runs subtrees on std::async threads

@@ -14,6 +14,8 @@
 //    each per workgroup.
 //  * srt_area_finish_kernel: distinct = the counts that are not zero, hit_pixels = area_pixels - miss_pixels.
 // Counts and summary are cleared by hipMemsetAsync on the handle's stream ahead of the launches.
+// area_through.hip (X-ray coverage: other counting kernels, the same result) shares the clear, the finish launch, the blocking
+// read-back and the selection rule through srt_internal.h (srt_area_clear ... srt_area_select_counts below).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -174,17 +176,11 @@ int area_begin(srt_tracer *t, const char *who, const srt_render_data *options, c
 int enqueue_count(srt_tracer *t, const srt_area &area, const int32_t *vertices, bool by_triangle, uint32_t target, uint32_t *counts, size_t n, uint32_t n_counts,
                   uint32_t *summary, bool one_block) {
 	const SelectionState *s = t->sel;
-	t->ar.span.timed = false;
-	if (t->timers_in_render) SRT_HIP(t, t->ar.span.begin(t->stream));
-	if (one_block) { // summary, then the counts, in one allocation
-		SRT_HIP(t, hipMemsetAsync(summary, 0, (8 + n) * sizeof(uint32_t), t->stream));
-	} else {
-		SRT_HIP(t, hipMemsetAsync(summary, 0, 8 * sizeof(uint32_t), t->stream));
-		if (n) SRT_HIP(t, hipMemsetAsync(counts, 0, n * sizeof(uint32_t), t->stream));
-	}
+	if (const int rc = srt_area_clear(t, counts, n, summary, one_block)) return rc;
 	int32_t c[4];
 	area_clip(area, s->ids_w, s->ids_h, c);
-	if (c[0] < c[2] && c[1] < c[3]) { // else: all zeros, nothing to launch
+	const bool launched = c[0] < c[2] && c[1] < c[3];
+	if (launched) { // else: all zeros, nothing to launch
 		AreaParams ap;
 		memset(&ap, 0, sizeof ap);
 		const size_t px = (size_t)s->ids_w * (size_t)s->ids_h;
@@ -208,30 +204,16 @@ int enqueue_count(srt_tracer *t, const srt_area &area, const int32_t *vertices, 
 			else launch_count<false, false>(ap, nullptr, blocks, t->stream);
 		}
 		SRT_HIP(t, hipGetLastError());
-		const uint32_t finish_blocks = n_counts == 0u ? 1u : std::min<uint32_t>((n_counts + 255u) / 256u, 1024u);
-		hipLaunchKernelGGL(srt_area_finish_kernel, dim3(finish_blocks), dim3(256), 0, t->stream, counts, n_counts, summary);
-		SRT_HIP(t, hipGetLastError());
 	}
-	if (t->timers_in_render) SRT_HIP(t, t->ar.span.end(t->stream));
-	return SRT_OK;
+	return srt_area_finish(t, counts, n_counts, summary, launched);
 }
 
 // the blocking forms: into the handle's own buffer, back as ONE copy through pinned memory behind its event
 int coverage_host(srt_tracer *t, const srt_area &area, const int32_t *vertices, bool by_triangle, uint32_t target, uint32_t n_counts, uint32_t *counts,
                   srt_area_summary *out) {
-	AreaState &ar = t->ar;
-	const size_t words = 8 + (size_t)n_counts;
-	if (ar.out.cap < words || ar.back.cap < words) { // (a grown buffer replaces one a queued launch may still use)
-		SRT_HIP(t, hipStreamSynchronize(t->stream));
-		SRT_HIP(t, ar.out.reserve(words));
-	}
-	SRT_HIP(t, ar.back.reserve(words));
-	if (const int rc = enqueue_count(t, area, vertices, by_triangle, target, ar.out.ptr + 8, n_counts, n_counts, ar.out.ptr, true)) return rc;
-	SRT_HIP(t, ar.back.copy(ar.out.ptr, words, t->stream));
-	SRT_HIP(t, ar.back.wait());
-	memcpy(out, ar.back.host, sizeof *out);
-	if (n_counts) memcpy(counts, ar.back.host + 8, (size_t)n_counts * sizeof(uint32_t));
-	return SRT_OK;
+	return srt_area_result_host(t, n_counts, counts, out, [&](uint32_t *d_counts, uint32_t *d_summary) {
+		return enqueue_count(t, area, vertices, by_triangle, target, d_counts, n_counts, n_counts, d_summary, true);
+	});
 }
 
 uint32_t scene_shapes(const srt_tracer *t) { return t->scene_set ? (uint32_t)t->sd.num_shapes : 0u; }
@@ -243,6 +225,58 @@ std::vector<uint32_t> sorted_unique(std::vector<uint32_t> v) {
 }
 
 } // namespace
+
+// ---- what area_through.hip shares (srt_internal.h): the same result buffers, span, finish kernel and selection rule ----
+int srt_area_clear(srt_tracer *t, uint32_t *counts, size_t n, uint32_t *summary, bool one_block) {
+	t->ar.span.timed = false;
+	if (t->timers_in_render) SRT_HIP(t, t->ar.span.begin(t->stream));
+	if (one_block) { // summary, then the counts, in one allocation
+		SRT_HIP(t, hipMemsetAsync(summary, 0, (8 + n) * sizeof(uint32_t), t->stream));
+	} else {
+		SRT_HIP(t, hipMemsetAsync(summary, 0, 8 * sizeof(uint32_t), t->stream));
+		if (n) SRT_HIP(t, hipMemsetAsync(counts, 0, n * sizeof(uint32_t), t->stream));
+	}
+	return SRT_OK;
+}
+
+int srt_area_finish(srt_tracer *t, const uint32_t *counts, uint32_t n_counts, uint32_t *summary, bool launched) {
+	if (launched) {
+		const uint32_t finish_blocks = n_counts == 0u ? 1u : std::min<uint32_t>((n_counts + 255u) / 256u, 1024u);
+		hipLaunchKernelGGL(srt_area_finish_kernel, dim3(finish_blocks), dim3(256), 0, t->stream, counts, n_counts, summary);
+		SRT_HIP(t, hipGetLastError());
+	}
+	if (t->timers_in_render) SRT_HIP(t, t->ar.span.end(t->stream));
+	return SRT_OK;
+}
+
+int srt_area_model_triangles(srt_tracer *t, const char *who, uint32_t shape, uint32_t *n_triangles) {
+	if (shape >= scene_shapes(t)) return fail(t, SRT_ERR_INVALID, std::string(who) + ": shape is not a shape of the scene");
+	SRT_HIP(t, hipSetDevice(t->device));
+	uint32_t head[6]; // the shape's record as uploaded: type, material, pad x 2, model.triangle_index, model.num_triangles
+	SRT_HIP(t, hipMemcpyAsync(head, t->shapes.ptr + shape, sizeof head, hipMemcpyDeviceToHost, t->stream));
+	SRT_HIP(t, hipStreamSynchronize(t->stream));
+	if ((int32_t)head[0] != SRT_SHAPE_MODEL) return fail(t, SRT_ERR_INVALID, std::string(who) + ": shape is not a model");
+	*n_triangles = head[5];
+	return SRT_OK;
+}
+
+int srt_area_select_counts(srt_tracer *t, const uint32_t *counts, size_t n, int mode, uint32_t min_pixels, size_t *n_selected) {
+	std::vector<uint32_t> hit, next;
+	const uint32_t need = min_pixels > 1u ? min_pixels : 1u;
+	for (size_t i = 0; i < n; i++)
+		if (counts[i] >= need) hit.push_back((uint32_t)i); // ascending
+	SelectionState *s = t->sel;
+	const std::vector<uint32_t> cur = s->on ? sorted_unique(s->shapes) : std::vector<uint32_t>();
+	if (mode == SRT_SELECT_REPLACE) next = hit;
+	else if (mode == SRT_SELECT_ADD) std::set_union(cur.begin(), cur.end(), hit.begin(), hit.end(), std::back_inserter(next));
+	else if (mode == SRT_SELECT_SUBTRACT) std::set_difference(cur.begin(), cur.end(), hit.begin(), hit.end(), std::back_inserter(next));
+	else std::set_symmetric_difference(cur.begin(), cur.end(), hit.begin(), hit.end(), std::back_inserter(next));
+	if (n_selected) *n_selected = next.size();
+	srt_selection_params p = s->p;
+	if (p.enabled == 0 && p.outline_width == 0.0f) srt_selection_defaults(&p); // srt_set_selection never stored a block
+	p.enabled = 1;
+	return srt_set_selection(t, &p, next.empty() ? nullptr : next.data(), next.size()); // (n == 0: off, as the call documents)
+}
 
 extern "C" {
 
@@ -278,14 +312,9 @@ int srt_area_triangle_coverage(srt_tracer *t, const srt_render_data *options, co
 	if (!t) return SRT_ERR_INVALID;
 	if (!area || !out) return fail(t, SRT_ERR_INVALID, "srt_area_triangle_coverage: NULL argument");
 	if (area_check(area, vertices) != SRT_OK) return fail(t, SRT_ERR_INVALID, "srt_area_triangle_coverage: the area is refused (srt_area_check_host)");
-	if (shape >= scene_shapes(t)) return fail(t, SRT_ERR_INVALID, "srt_area_triangle_coverage: shape is not a shape of the scene");
 	try {
-		SRT_HIP(t, hipSetDevice(t->device));
-		uint32_t head[6]; // the shape's record as uploaded: type, material, pad x 2, model.triangle_index, model.num_triangles
-		SRT_HIP(t, hipMemcpyAsync(head, t->shapes.ptr + shape, sizeof head, hipMemcpyDeviceToHost, t->stream));
-		SRT_HIP(t, hipStreamSynchronize(t->stream));
-		if ((int32_t)head[0] != SRT_SHAPE_MODEL) return fail(t, SRT_ERR_INVALID, "srt_area_triangle_coverage: shape is not a model");
-		const uint32_t n = head[5];
+		uint32_t n = 0;
+		if (const int rc = srt_area_model_triangles(t, "srt_area_triangle_coverage", shape, &n)) return rc;
 		if (cap_triangles < n || (n && !counts)) return fail(t, SRT_ERR_INVALID, "srt_area_triangle_coverage: counts is smaller than the model's triangle count");
 		if (const int rc = area_begin(t, "srt_area_triangle_coverage", options, area, vertices)) return rc;
 		return coverage_host(t, *area, vertices, true, shape, n, counts, out);
@@ -328,23 +357,10 @@ int srt_select_area(srt_tracer *t, const srt_render_data *options, const srt_are
 	if (mode < SRT_SELECT_REPLACE || mode > SRT_SELECT_TOGGLE) return fail(t, SRT_ERR_INVALID, "srt_select_area: mode is SRT_SELECT_REPLACE, ADD, SUBTRACT or TOGGLE");
 	if (!area) return fail(t, SRT_ERR_INVALID, "srt_select_area: NULL argument");
 	try {
-		std::vector<uint32_t> counts(scene_shapes(t)), hit, next;
+		std::vector<uint32_t> counts(scene_shapes(t));
 		srt_area_summary sum;
 		if (const int rc = srt_area_coverage(t, options, area, vertices, counts.data(), counts.size(), &sum)) return rc;
-		const uint32_t need = min_pixels > 1u ? min_pixels : 1u;
-		for (size_t i = 0; i < counts.size(); i++)
-			if (counts[i] >= need) hit.push_back((uint32_t)i); // ascending
-		SelectionState *s = t->sel;
-		const std::vector<uint32_t> cur = s->on ? sorted_unique(s->shapes) : std::vector<uint32_t>();
-		if (mode == SRT_SELECT_REPLACE) next = hit;
-		else if (mode == SRT_SELECT_ADD) std::set_union(cur.begin(), cur.end(), hit.begin(), hit.end(), std::back_inserter(next));
-		else if (mode == SRT_SELECT_SUBTRACT) std::set_difference(cur.begin(), cur.end(), hit.begin(), hit.end(), std::back_inserter(next));
-		else std::set_symmetric_difference(cur.begin(), cur.end(), hit.begin(), hit.end(), std::back_inserter(next));
-		if (n_selected) *n_selected = next.size();
-		srt_selection_params p = s->p;
-		if (p.enabled == 0 && p.outline_width == 0.0f) srt_selection_defaults(&p); // srt_set_selection never stored a block
-		p.enabled = 1;
-		return srt_set_selection(t, &p, next.empty() ? nullptr : next.data(), next.size()); // (n == 0: off, as the call documents)
+		return srt_area_select_counts(t, counts.data(), counts.size(), mode, min_pixels, n_selected);
 	} catch (...) {
 		return fail(t, SRT_ERR_INVALID, "out of host memory");
 	}

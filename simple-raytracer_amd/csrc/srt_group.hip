@@ -568,6 +568,22 @@ int srt_group_select_area(srt_group *g, const srt_render_data *options, const sr
 	return first_member(g, srt_select_area, options, area, vertices, mode, min_pixels, n_selected);
 }
 int srt_group_read_selection(srt_group *g, uint32_t *shapes, size_t cap, size_t *n) { return first_member(g, srt_read_selection, shapes, cap, n); }
+// X-ray area selection (area_through.hip): likewise
+int srt_group_area_coverage_through(srt_group *g, const srt_render_data *options, const srt_area *area, const int32_t *vertices, uint32_t *counts,
+                                    size_t cap_shapes, srt_area_summary *out) {
+	return first_member(g, srt_area_coverage_through, options, area, vertices, counts, cap_shapes, out);
+}
+int srt_group_area_triangle_coverage_through(srt_group *g, const srt_render_data *options, const srt_area *area, const int32_t *vertices, uint32_t shape,
+                                             uint32_t *counts, size_t cap_triangles, srt_area_summary *out) {
+	return first_member(g, srt_area_triangle_coverage_through, options, area, vertices, shape, counts, cap_triangles, out);
+}
+int srt_group_select_area_through(srt_group *g, const srt_render_data *options, const srt_area *area, const int32_t *vertices, int mode, uint32_t min_pixels,
+                                  size_t *n_selected) {
+	return first_member(g, srt_select_area_through, options, area, vertices, mode, min_pixels, n_selected);
+}
+int srt_group_pick_rays(srt_group *g, const srt_render_data *options, const float *xy, size_t n, srt_ray *rays_out) {
+	return first_member(g, srt_pick_rays, options, xy, n, rays_out);
+}
 
 // ---- the first member again: every member holds the whole scene, and a query ignores the partition. Ray queries (ray_query.hip),
 // nearest-surface queries (nearest.hip), occlusion queries (occlusion.hip), the ambient-occlusion pass (ao.hip) ----

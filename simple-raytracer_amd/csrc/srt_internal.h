@@ -502,6 +502,32 @@ static inline int srt_selection_apply_frame(srt_tracer *t, uint8_t *argb) {
  * key -- planes made under an equal key are kept and nothing is launched; *ran = whether the pass was enqueued. rd is checked
  * as srt_render_ids checks it */
 int srt_selection_ids_current(srt_tracer *t, const srt_render_data *rd, bool *ran);
+/* area.hip for area_through.hip, which counts by other kernels into the same result buffers (t->ar), on the handle's stream:
+ * the span's start and the clear of summary (8 words) and counts (n words; one_block: one allocation, the summary first); behind
+ * the counting launches srt_area_finish_kernel over counts[0 .. n_counts) (launched: there were any) and the span's end; a
+ * blocking call's frame -- the handle's buffer reserved, enqueue(d_counts, d_summary), one copy back through pinned memory;
+ * the triangle count of a model shape (SRT_ERR_INVALID: beyond the scene, or no model; reads the uploaded record, blocking);
+ * srt_select_area's rule applied to counts that are on the host */
+int srt_area_clear(srt_tracer *t, uint32_t *counts, size_t n, uint32_t *summary, bool one_block);
+int srt_area_finish(srt_tracer *t, const uint32_t *counts, uint32_t n_counts, uint32_t *summary, bool launched);
+template <class Enqueue>
+static inline int srt_area_result_host(srt_tracer *t, uint32_t n_counts, uint32_t *counts, srt_area_summary *out, Enqueue enqueue) {
+	AreaState &ar = t->ar;
+	const size_t words = 8 + (size_t)n_counts;
+	if (ar.out.cap < words || ar.back.cap < words) { // (a grown buffer replaces one a queued launch may still use)
+		SRT_HIP(t, hipStreamSynchronize(t->stream));
+		SRT_HIP(t, ar.out.reserve(words));
+	}
+	SRT_HIP(t, ar.back.reserve(words));
+	if (const int rc = enqueue(ar.out.ptr + 8, ar.out.ptr)) return rc; // the counts, the summary
+	SRT_HIP(t, ar.back.copy(ar.out.ptr, words, t->stream));
+	SRT_HIP(t, ar.back.wait());
+	memcpy(out, ar.back.host, sizeof *out);
+	if (n_counts) memcpy(counts, ar.back.host + 8, (size_t)n_counts * sizeof(uint32_t));
+	return SRT_OK;
+}
+int srt_area_model_triangles(srt_tracer *t, const char *who, uint32_t shape, uint32_t *n_triangles);
+int srt_area_select_counts(srt_tracer *t, const uint32_t *counts, size_t n, int mode, uint32_t min_pixels, size_t *n_selected);
 /* bloom.hip: whether a site's resolve of num_pixels is bloomed (the feature on, a picture, not empty); sets last_bloomed */
 bool srt_bloom_begin(srt_tracer *t, bool picture, size_t num_pixels);
 /* ... and its launches on the handle's stream: the pyramid of (source / divisor) * *exposure (NULL: 1.0f) and the composite

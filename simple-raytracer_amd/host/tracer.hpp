@@ -343,24 +343,51 @@ class Tracer {
 	/// Area selection (srt_area_coverage): the visible pixels of every shape inside the half-open pixel rectangle of `area`,
 	/// optionally cut by a lasso (pixel-corner vertices x0, y0, x1, y1, ...; even-odd rule), counted on the device from the ID
 	/// planes of the camera of `options` -- what a rubber band asks. summary (optional): the area's totals. Blocking.
-	std::vector<uint32_t> area_coverage(srt_area area, const std::vector<int32_t> &lasso = {}, srt_area_summary *summary = nullptr) {
+	/// through = true (srt_area_coverage_through): X-ray coverage -- the pixels whose ray meets the shape at all, hidden or not.
+	std::vector<uint32_t> area_coverage(srt_area area, const std::vector<int32_t> &lasso = {}, srt_area_summary *summary = nullptr, bool through = false) {
 		std::vector<uint32_t> counts((size_t)scene_data.num_shapes);
 		srt_area_summary s;
 		area.n_vertices = uint32_t(lasso.size() / 2);
 		const srt_render_data *rd = reinterpret_cast<const srt_render_data *>(&options);
-		check(group ? srt_group_area_coverage(group, rd, &area, lasso.data(), counts.data(), counts.size(), &s)
-		            : srt_area_coverage(handle, rd, &area, lasso.data(), counts.data(), counts.size(), &s));
+		if (through)
+			check(group ? srt_group_area_coverage_through(group, rd, &area, lasso.data(), counts.data(), counts.size(), &s)
+			            : srt_area_coverage_through(handle, rd, &area, lasso.data(), counts.data(), counts.size(), &s));
+		else
+			check(group ? srt_group_area_coverage(group, rd, &area, lasso.data(), counts.data(), counts.size(), &s)
+			            : srt_area_coverage(handle, rd, &area, lasso.data(), counts.data(), counts.size(), &s));
+		if (summary) *summary = s;
+		return counts;
+	}
+	/// The pixels per triangle of model `shape` inside the area (srt_area_triangle_coverage; through = true:
+	/// srt_area_triangle_coverage_through, back-facing and hidden faces included). n_triangles: the model's triangle count. Blocking.
+	std::vector<uint32_t> area_triangle_coverage(uint32_t shape, size_t n_triangles, srt_area area, const std::vector<int32_t> &lasso = {},
+	                                             srt_area_summary *summary = nullptr, bool through = false) {
+		std::vector<uint32_t> counts(n_triangles);
+		srt_area_summary s;
+		area.n_vertices = uint32_t(lasso.size() / 2);
+		const srt_render_data *rd = reinterpret_cast<const srt_render_data *>(&options);
+		if (through)
+			check(group ? srt_group_area_triangle_coverage_through(group, rd, &area, lasso.data(), shape, counts.data(), counts.size(), &s)
+			            : srt_area_triangle_coverage_through(handle, rd, &area, lasso.data(), shape, counts.data(), counts.size(), &s));
+		else
+			check(group ? srt_group_area_triangle_coverage(group, rd, &area, lasso.data(), shape, counts.data(), counts.size(), &s)
+			            : srt_area_triangle_coverage(handle, rd, &area, lasso.data(), shape, counts.data(), counts.size(), &s));
 		if (summary) *summary = s;
 		return counts;
 	}
 	/// ... and the shapes with at least min_pixels visible pixels combined with the current selection (mode: SRT_SELECT_REPLACE,
 	/// ADD, SUBTRACT, TOGGLE) and overlaid as set_selection overlays a list, with the parameters it was last given. Returns the
 	/// new list's length. One call per mouse-move of a drag: under an unchanged camera and scene no ID pass runs. Blocking.
-	size_t select_area(srt_area area, const std::vector<int32_t> &lasso = {}, int mode = SRT_SELECT_REPLACE, uint32_t min_pixels = 1) {
+	/// through = true (srt_select_area_through): by the through counts; an infinite plane the frame faces is met by most pixels --
+	/// filter it with min_pixels or by type.
+	size_t select_area(srt_area area, const std::vector<int32_t> &lasso = {}, int mode = SRT_SELECT_REPLACE, uint32_t min_pixels = 1, bool through = false) {
 		size_t n = 0;
 		area.n_vertices = uint32_t(lasso.size() / 2);
 		const srt_render_data *rd = reinterpret_cast<const srt_render_data *>(&options);
-		check(group ? srt_group_select_area(group, rd, &area, lasso.data(), mode, min_pixels, &n) : srt_select_area(handle, rd, &area, lasso.data(), mode, min_pixels, &n));
+		if (through)
+			check(group ? srt_group_select_area_through(group, rd, &area, lasso.data(), mode, min_pixels, &n)
+			            : srt_select_area_through(handle, rd, &area, lasso.data(), mode, min_pixels, &n));
+		else check(group ? srt_group_select_area(group, rd, &area, lasso.data(), mode, min_pixels, &n) : srt_select_area(handle, rd, &area, lasso.data(), mode, min_pixels, &n));
 		return n;
 	}
 	/// The current selection, ascending and unique; empty while the overlay is off
@@ -564,6 +591,14 @@ class Tracer {
 		            : srt_occluded_rays(handle, rays.data(), rays.size(), flags, occ.data(), invalid ? inv.data() : nullptr));
 		if (invalid) *invalid = mask_bits(inv, rays.size());
 		return mask_bits(occ, rays.size());
+	}
+	/// The rays pick would cast for image points (srt_pick_rays), xy as pick takes it: unit directions, tmax = +inf. Blocking.
+	std::vector<srt_ray> pick_rays(const std::vector<float> &xy) {
+		const size_t n = xy.size() / 2;
+		std::vector<srt_ray> rays(n);
+		const srt_render_data *rd = reinterpret_cast<const srt_render_data *>(&options);
+		check(group ? srt_group_pick_rays(group, rd, xy.data(), n, rays.data()) : srt_pick_rays(handle, rd, xy.data(), n, rays.data()));
+		return rays;
 	}
 	/// ... between `from` and the point end_gap short of `to` of each segment (srt_occluded_segments): a line of sight.
 	std::vector<bool> occluded(const std::vector<srt_segment> &segments, std::vector<bool> *invalid = nullptr) {

@@ -164,6 +164,7 @@ int main(int argc, char **argv) {
 	std::vector<uint32_t> selected; // --select
 	srt_area area{};                // --select-area, --lasso
 	bool select_area = false;
+	bool area_through = false;      // --through: the X-ray counts (srt_area_coverage_through)
 	int area_mode = SRT_SELECT_REPLACE;
 	unsigned area_min_pixels = 1;
 	std::vector<int32_t> lasso;
@@ -345,6 +346,7 @@ int main(int argc, char **argv) {
 			}
 			select_area = true;
 		}
+		else if (a == "--through") area_through = true;
 		else if (a == "--lasso") { // X,Y;X,Y;...
 			const std::string v = next();
 			const char *c = v.c_str();
@@ -399,7 +401,7 @@ int main(int argc, char **argv) {
 		else {
 			std::cerr << "usage: srt_headless [--scene spheres|meshes|empty] [--obj f]... [--stl f]... [--width W --height H --spp S "
 			             "--bounces B --frames N --time T] [--out f.ppm] [--dump prefix] [--parse-only] [--bvh] [--bvh-build device[:MIN]] [--bvh-order morton|median] [--gpus N] [--pipelined] [--skybox sky.ppm] "
-			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--ao S[:RADIUS[:BIAS]]] [--ao-view f.ppm] [--select I[,J...][:WIDTH[:RRGGBBAA]]] [--select-area X0,Y0:X1,Y1[:MODE[:MINPIXELS]] [--lasso X,Y;X,Y;...]] [--pick X,Y]... [--pick-through X,Y[:K]]... [--nearest X,Y,Z[:RADIUS[:SKIP]]]... [--line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP]]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
+			             "[--denoise K] [--demodulate] [--spatial-variance N] [--temporal] [--history-illumination] [--history-clamp G] [--history-feedback] [--exposure auto[:EVBIAS]|EV] [--bloom [THRESHOLD[:INTENSITY[:LEVELS]]]] [--until-noise THRESHOLD[:MAXDISPATCHES[:PERMILLE]]] [--noise-view f.ppm] [--ao S[:RADIUS[:BIAS]]] [--ao-view f.ppm] [--select I[,J...][:WIDTH[:RRGGBBAA]]] [--select-area X0,Y0:X1,Y1[:MODE[:MINPIXELS]] [--lasso X,Y;X,Y;...] [--through]] [--pick X,Y]... [--pick-through X,Y[:K]]... [--nearest X,Y,Z[:RADIUS[:SKIP]]]... [--line-of-sight X0,Y0,Z0:X1,Y1,Z1[:GAP]]... [--move DX] [--move-shape I DX] [--texture img.ppm --texture-material N [--texture-scale S] [--texture-nearest]] [--obj-materials]\n";
 			return 2;
 		}
 	}
@@ -638,8 +640,8 @@ int main(int argc, char **argv) {
 
 	std::vector<uint8_t> pixels((size_t)width * height * 4);
 
-	if (!lasso.empty() && !select_area) {
-		std::cerr << "--lasso needs --select-area\n";
+	if ((!lasso.empty() || area_through) && !select_area) {
+		std::cerr << "--lasso and --through need --select-area\n";
 		return 2;
 	}
 	if (select_area) { // --select-area: the shapes visible inside the area through the first frame's camera, combined with --select's
@@ -649,11 +651,11 @@ int main(int argc, char **argv) {
 		options.fov_scale = 1.0f;
 		options.camera_to_world = moving ? eye_matrix(glm::vec3(0.0f, 0.5f, 5.0f), 0.0f, 0.0f) : camera_to_world;
 		srt_area_summary sum;
-		const std::vector<uint32_t> counts = tracer.area_coverage(area, lasso, &sum);
+		const std::vector<uint32_t> counts = tracer.area_coverage(area, lasso, &sum, area_through);
 		std::printf("area: %u pixel(s), %u on shapes, %u miss, %u shape(s)\n", sum.area_pixels, sum.hit_pixels, sum.miss_pixels, sum.distinct);
 		for (size_t i = 0; i < counts.size(); i++)
 			if (counts[i]) std::printf("shape %zu count %u\n", i, counts[i]);
-		const size_t n = tracer.select_area(area, lasso, area_mode, area_min_pixels);
+		const size_t n = tracer.select_area(area, lasso, area_mode, area_min_pixels, area_through);
 		selected = tracer.read_selection();
 		std::printf("area selection: %zu shape(s)\n", n);
 	}

@@ -88,6 +88,8 @@ ABI_SYMBOLS = [
     "srt_group_select_area", "srt_group_read_selection", "srt_last_area_ms", "srt_last_area_id_pass",
     "srt_cast_rays_multi", "srt_cast_rays_multi_device", "srt_pick_through", "srt_group_cast_rays_multi", "srt_group_pick_through",
     "srt_multi_hit_check_host", "srt_multi_hit_sizes",
+    "srt_area_coverage_through", "srt_area_triangle_coverage_through", "srt_area_coverage_through_device", "srt_select_area_through",
+    "srt_group_area_coverage_through", "srt_group_area_triangle_coverage_through", "srt_group_select_area_through", "srt_pick_rays", "srt_group_pick_rays",
 ]
 
 ACCEL_NONE, ACCEL_BVH = 0, 1
@@ -998,6 +1000,13 @@ def _bind(lib):
         lib.srt_multi_hit_sizes.argtypes = [C.POINTER(sz)]
         sizes = (sz * 3)()
         assert lib.srt_multi_hit_sizes(sizes) == 0 and tuple(sizes) == (R.RAY.itemsize, R.RAY_HIT.itemsize, R.MULTI_HIT_MAX), tuple(sizes)
+    if hasattr(lib, "srt_area_coverage_through"):  # (likewise)
+        for pre in ("srt_", "srt_group_"):
+            getattr(lib, pre + "area_coverage_through").argtypes = [vp, vp, vp, vp, vp, sz, vp]
+            getattr(lib, pre + "area_triangle_coverage_through").argtypes = [vp, vp, vp, vp, C.c_uint32, vp, sz, vp]
+            getattr(lib, pre + "select_area_through").argtypes = [vp, vp, vp, vp, C.c_int, C.c_uint32, C.POINTER(sz)]
+            getattr(lib, pre + "pick_rays").argtypes = [vp, vp, vp, sz, vp]
+        lib.srt_area_coverage_through_device.argtypes = [vp, vp, vp, vp, vp, sz, vp]
     return lib
 
 
@@ -1268,6 +1277,16 @@ class _RayQuery:
         self._check(self._dn("pick_through", _ptr(rd), _ptr(xy) if n else None, n, k, _ptr(hits) if n else None, _ptr(counts) if n else None))
         return hits, counts
 
+    def pick_rays(self, xy, options=None):
+        """The rays pick would cast for image points -> records.RAY array (unit directions, tmax = +inf: cast them with
+        unit=True); xy and options as pick. Blocking."""
+        xy = np.ascontiguousarray(np.atleast_2d(np.asarray(xy, np.float32)))
+        assert xy.ndim == 2 and xy.shape[1] == 2, xy.shape
+        rd = R.as_records(self.options if options is None else options, R.RENDER_DATA)
+        rays = np.zeros(len(xy), R.RAY)
+        self._check(self._dn("pick_rays", _ptr(rd), _ptr(xy) if len(xy) else None, len(xy), _ptr(rays) if len(xy) else None))
+        return rays
+
     @staticmethod
     def _multi_flags(unit, count_all):
         return (R.RAYS_UNIT_DIRECTIONS if unit else 0) | (R.RAYS_COUNT_ALL if count_all else 0)
@@ -1343,7 +1362,8 @@ class _Area:
     """Area selection (include/srt_abi.h "area selection"), shared by Tracer and TracerGroup (the group: its first member's planes,
     scene and selection). rect = (x0, y0, x1, y1), half open, clipped to the frame; lasso: pixel-corner vertices (x, y) or None;
     options: the camera and frame the ID planes are brought up to date for (default: self.options), False: the planes the handle
-    holds."""
+    holds. through=True (include/srt_abi.h "area selection, through"): X-ray coverage -- the shapes and faces hidden behind
+    others count too, over each pixel ray's whole candidate set; no ID planes are used, so options=False is refused."""
 
     def _area_args(self, rect, lasso, options):
         a, v = area_record(rect, lasso)
@@ -1351,27 +1371,30 @@ class _Area:
         self._area_keep = (a, v, rd)
         return (_ptr(rd) if rd is not None else None), _ptr(a), (_ptr(v) if v is not None else None)
 
-    def area_coverage(self, rect, lasso=None, options=None, n_shapes=None):
+    def area_coverage(self, rect, lasso=None, options=None, n_shapes=None, through=False):
         """Visible pixels per shape inside the area -> (counts (n_shapes,) uint32, summary dict). n_shapes: the scene's shape
-        count (default: self.scene_data's). Blocking."""
+        count (default: self.scene_data's). through=True: pixels whose ray meets the shape at all, visible or not. Blocking."""
         n = int(self.scene_data["num_shapes"]) if n_shapes is None else int(n_shapes)
         counts, summary = np.zeros(n, np.uint32), np.zeros((), R.AREA_SUMMARY)
-        self._check(self._dn("area_coverage", *self._area_args(rect, lasso, options), _ptr(counts) if n else None, n, _ptr(summary)))
+        self._check(self._dn("area_coverage_through" if through else "area_coverage", *self._area_args(rect, lasso, options), _ptr(counts) if n else None, n, _ptr(summary)))
         return counts, {k: int(summary[k]) for k in R.AREA_SUMMARY.names[:5]}
 
-    def area_triangle_coverage(self, shape, n_triangles, rect, lasso=None, options=None):
+    def area_triangle_coverage(self, shape, n_triangles, rect, lasso=None, options=None, through=False):
         """Visible pixels per triangle of the model shape inside the area -> (counts (n_triangles,) uint32, summary dict).
-        n_triangles: at least the model's triangle count. Blocking."""
+        n_triangles: at least the model's triangle count. through=True: pixels whose ray crosses the triangle, back-facing and
+        hidden ones included. Blocking."""
         counts, summary = np.zeros(int(n_triangles), np.uint32), np.zeros((), R.AREA_SUMMARY)
-        self._check(self._dn("area_triangle_coverage", *self._area_args(rect, lasso, options), int(shape), _ptr(counts) if len(counts) else None,
+        self._check(self._dn("area_triangle_coverage_through" if through else "area_triangle_coverage", *self._area_args(rect, lasso, options), int(shape), _ptr(counts) if len(counts) else None,
                              len(counts), _ptr(summary)))
         return counts, {k: int(summary[k]) for k in R.AREA_SUMMARY.names[:5]}
 
-    def select_area(self, rect, lasso=None, mode=R.SELECT_REPLACE, min_pixels=1, options=None):
+    def select_area(self, rect, lasso=None, mode=R.SELECT_REPLACE, min_pixels=1, options=None, through=False):
         """Combine the shapes with at least min_pixels visible pixels inside the area with the current selection (mode:
-        records.SELECT_REPLACE, SELECT_ADD, SELECT_SUBTRACT, SELECT_TOGGLE) and overlay the result -> its length. Blocking."""
+        records.SELECT_REPLACE, SELECT_ADD, SELECT_SUBTRACT, SELECT_TOGGLE) and overlay the result -> its length. through=True:
+        by the through counts (an infinite plane the frame faces is met by most pixels: filter it with min_pixels or by type).
+        Blocking."""
         n = C.c_size_t(0)
-        self._check(self._dn("select_area", *self._area_args(rect, lasso, options), int(mode), int(min_pixels), C.byref(n)))
+        self._check(self._dn("select_area_through" if through else "select_area", *self._area_args(rect, lasso, options), int(mode), int(min_pixels), C.byref(n)))
         return n.value
 
     def read_selection(self):
@@ -1910,10 +1933,11 @@ class Tracer(_Denoise, _Exposure, _Bloom, _Noise, _RayQuery, _Selection, _Area, 
         self._check(self.lib.srt_read_selection_alpha(self._h, _ptr(out), out.size))
         return out
 
-    def area_coverage_device(self, counts_ptr, n, summary_ptr, rect, lasso=None, options=None):
+    def area_coverage_device(self, counts_ptr, n, summary_ptr, rect, lasso=None, options=None, through=False):
         """area_coverage left in device memory (n >= the scene's shape count uint32 at counts_ptr, 8 uint32 laid out as
         records.AREA_SUMMARY at summary_ptr), enqueued on the handle's stream: synchronize() before they are read."""
-        self._check(self.lib.srt_area_coverage_device(self._h, *self._area_args(rect, lasso, options), C.c_void_p(counts_ptr), n, C.c_void_p(summary_ptr)))
+        fn = self.lib.srt_area_coverage_through_device if through else self.lib.srt_area_coverage_device
+        self._check(fn(self._h, *self._area_args(rect, lasso, options), C.c_void_p(counts_ptr), n, C.c_void_p(summary_ptr)))
 
     def last_area_ms(self):
         """Device time of the last coverage call's clear and counting launches under set_kernel_timers (0 without)."""
