@@ -275,6 +275,51 @@ class Oracle:
             out[i] = self._f("random_float")(C.byref(s))
         return out, s.value
 
+    def random_direction(self, seed):
+        """random_direction (oracle only) -> (the unit vector (3,) float32, the seed advanced by its six draws)"""
+        s = C.c_uint32(seed)
+        out = np.zeros(3, np.float32)
+        self.lib.orc_random_direction.restype = None
+        self.lib.orc_random_direction(C.byref(s), _p(out))
+        return out, s.value
+
+    def normalize3(self, v):
+        """vnormalize (oracle only): (3,) -> (3,) float32, or (n, 3) -> (n, 3) row by row"""
+        a = np.ascontiguousarray(v, np.float32)
+        out = np.zeros_like(a)
+        self.lib.orc_normalize3.restype = None
+        fn, pa, po = self.lib.orc_normalize3, a.ctypes.data, out.ctypes.data
+        for k in range(a.size // 3):
+            fn(C.c_void_p(pa + 12 * k), C.c_void_p(po + 12 * k))
+        return out
+
+    def closest_hits(self, shapes, tris, mats, rays):
+        """closest_intersection over caller rays (records.RAY, directions used as given; oracle only) -> dict: t (n,) (inf:
+        nothing hit), normal (n, 3) turned to face the ray, shape and triangle (n,) int32 (-1: none). A shape without a
+        material is a hit."""
+        R = _rec()
+        rays = np.ascontiguousarray(R.as_records(rays, R.RAY))
+        shapes, tris, mats = R.as_records(shapes, R.SHAPE), R.as_records(tris, R.TRIANGLE), R.as_records(mats, R.MATERIAL)
+        sd = R.as_records(R.scene_data(len(shapes)), R.SCENE_DATA)
+        out = np.zeros((len(rays), 8), np.float32)
+        self.lib.orc_closest_hits.restype = None
+        with np.errstate(all="ignore"):
+            self.lib.orc_closest_hits(_p(sd), _p(shapes), _p(tris), _p(mats), _p(rays), C.c_int(len(rays)), _p(out))
+        ids = out[:, 4:6].view(np.int32)
+        return {"t": out[:, 0].copy(), "normal": out[:, 1:4].copy(), "shape": ids[:, 0].copy(), "triangle": ids[:, 1].copy()}
+
+    def any_hit(self, shapes, tris, rays):
+        """The occlusion contract over caller rays with unit directions (oracle only) -> (n,) bool: some primitive's
+        intersector accepts the ray with t < tmax; validity is the caller's business."""
+        R = _rec()
+        rays = np.ascontiguousarray(R.as_records(rays, R.RAY))
+        shapes, tris = R.as_records(shapes, R.SHAPE), R.as_records(tris, R.TRIANGLE)
+        sd = R.as_records(R.scene_data(len(shapes)), R.SCENE_DATA)
+        out = np.zeros(len(rays), np.uint8)
+        self.lib.orc_any_hit.restype = None
+        self.lib.orc_any_hit(_p(sd), _p(shapes), _p(tris), _p(rays), C.c_int(len(rays)), _p(out))
+        return out.astype(bool)
+
     def shlick(self, mu, c):
         return np.float32(self._f("shlick_reflectance")(C.c_float(mu), C.c_float(c)))
 

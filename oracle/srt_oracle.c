@@ -690,6 +690,79 @@ void orc_primary_hits(const srt_render_data *data, const srt_scene_data *scene_d
 	}
 }
 
+/* ---- what tests/ao_ref.py states the ambient-occlusion pass with (include/srt_abi.h "ambient-occlusion pass"): the statics
+ * above under exported names, and the loops above over caller rays. No arithmetic of their own. ---- */
+void orc_random_direction(uint32_t *seed, float out[3]) { /* random_direction: the unit vector, *seed advanced by its six draws */
+	v3 d = random_direction(seed);
+	out[0] = d.x, out[1] = d.y, out[2] = d.z;
+}
+
+void orc_normalize3(const float in[3], float out[3]) { /* vnormalize */
+	v3 d = vnormalize(V(in[0], in[1], in[2]));
+	out[0] = d.x, out[1] = d.y, out[2] = d.z;
+}
+
+/* closest_intersection over n caller rays (srt_ray: origin, tmax -- not read --, direction -- used as given --, reserved) ->
+ * 8 words per ray: t (+inf: nothing hit), the winner's normal turned to face the ray (0 without a hit), the shape's index and
+ * the triangle's inside its model as int32 (-1: none; a shape WITHOUT a material is a hit here, unlike orc_primary_hits'
+ * material), 0, 0. */
+void orc_closest_hits(const srt_scene_data *scene_data, const srt_shape *shapes, const srt_triangle *triangles,
+                      const srt_material *materials, const float *rays, int n, float *out) {
+	scene_t scene = {scene_data, shapes, triangles, materials, NULL, 0, 0, NULL};
+	uint64_t ctr[ORC_C_COUNT];
+	memset(ctr, 0, sizeof ctr);
+	for (int k = 0; k < n; k++) {
+		const float *r = rays + 8 * (size_t)k;
+		hit_t hit;
+		memset(&hit, 0, sizeof hit);
+		(void)closest_intersection(&scene, V(r[0], r[1], r[2]), V(r[4], r[5], r[6]), &hit, ctr);
+		const int found = hit.t < DM_INF_F;
+		float *o = out + 8 * (size_t)k;
+		int32_t ids[2] = {found ? hit.shape : -1, found && shapes[hit.shape].type == SRT_SHAPE_MODEL ? (int32_t)hit.tri : -1};
+		o[0] = hit.t;
+		o[1] = found ? hit.normal.x : 0.f, o[2] = found ? hit.normal.y : 0.f, o[3] = found ? hit.normal.z : 0.f;
+		memcpy(o + 4, ids, sizeof ids);
+		o[6] = o[7] = 0.f;
+	}
+}
+
+/* The occlusion contract (include/srt_abi.h "occlusion queries") over n caller rays with unit directions: out[k] = 1 when, in
+ * array order, a sphere's, a plane's or a triangle's intersector accepts the ray with t < tmax true -- the strict bound;
+ * materials are not looked at, so glass and shapes without one occlude --, a model's triangles (world positions made as
+ * closest_intersection makes them) only when its box passes orc_intersection_aabb against the ray's tmax. Which rays are
+ * valid is the caller's business (tests/ao_ref.py). */
+void orc_any_hit(const srt_scene_data *scene_data, const srt_shape *shapes, const srt_triangle *triangles, const float *rays,
+                 int n, uint8_t *out) {
+	for (int k = 0; k < n; k++) {
+		const float *r = rays + 8 * (size_t)k;
+		const float o[3] = {r[0], r[1], r[2]}, d[3] = {r[4], r[5], r[6]}, tmax = r[3];
+		const float inv_dir[3] = {1.0f / d[0], 1.0f / d[1], 1.0f / d[2]};
+		int occluded = 0;
+		for (int i = 0; i < scene_data->num_shapes && !occluded; i++) {
+			const srt_shape *shape = &shapes[i];
+			float t_i;
+			if (shape->type == SRT_SHAPE_SPHERE) {
+				occluded = orc_intersect_sphere(&shape->shape.sphere, o, d, &t_i) && t_i < tmax;
+			} else if (shape->type == SRT_SHAPE_PLANE) {
+				occluded = orc_intersect_plane(&shape->shape.plane, o, d, &t_i) && t_i < tmax;
+			} else if (shape->type == SRT_SHAPE_MODEL) {
+				const srt_model *model = &shape->shape.model;
+				float bmin[3] = {model->bounding_min.x, model->bounding_min.y, model->bounding_min.z};
+				float bmax[3] = {model->bounding_max.x, model->bounding_max.y, model->bounding_max.z};
+				if (!orc_intersection_aabb(bmin, bmax, o, inv_dir, tmax)) continue;
+				for (size_t j = 0; j < model->num_triangles && !occluded; j++) {
+					const srt_triangle *tri = &triangles[model->triangle_index + j];
+					v3 p0 = mat_by_vec(model->transform, f3(&tri->vertices[0].pos), 1.0f);
+					v3 p1 = mat_by_vec(model->transform, f3(&tri->vertices[1].pos), 1.0f);
+					v3 p2 = mat_by_vec(model->transform, f3(&tri->vertices[2].pos), 1.0f);
+					occluded = intersect_triangle(p0, p1, p2, V(o[0], o[1], o[2]), V(d[0], d[1], d[2]), &t_i, NULL) && t_i < tmax;
+				}
+			}
+		}
+		out[k] = (uint8_t)occluded;
+	}
+}
+
 /* One dispatch's guide sums, as the denoiser's feature pass adds them (kernels.hip srt_features_kernel): for each pixel
  * its samples 0 .. min(feature_samples, max(num_samples, 0)) - 1 in order, float32 partial sums of {front-facing normal,
  * tmin} and {material colour, 1} over the hits and {1, 1, 1, 0} over the misses, then added into normal_depth and

@@ -21,6 +21,67 @@ VIEWS = {"spheres": (CAMERAS["spheres"][1], 1.0), "mesh_smooth": (R.camera_matri
 CASES = [(n, a) for n in VIEWS for a in ACCELS[n]]
 
 
+# ---- the cases pinned to the CPU reference (tests/ao_ref.py; tests/test_ao_reference.py, tests/test_gpu_ao.py) ----------------
+# scene -> (camera, fov, the shapes the scene was added for, the radius of its count cases). Cameras chosen with the reference on
+# the CPU; tests/test_ao_reference.py asserts what each frame has to show.
+#   boxes          shapes 3 and 4 are the rotated, non-uniformly scaled instances, whose normal is the reference's (the vertex
+#                  normals through the forward matrix), not the geometric one
+#   mesh_flat      shape 1, the flat-shaded mesh
+#   glass_inside   the camera inside glass sphere 1: every pixel's winner is that sphere from behind, its normal turned to face
+#                  the ray. A closed sphere around the camera leaves no pixel without a surface, and no ray from its inside
+#                  travels further than its diameter 2.4 before it meets it again: the counts are taken at radius 1.5, where a
+#                  ray more than acos(1.5 / 2.4) off the normal stays open
+#   spheres_bare   the sphere scene with shape 4's material index -1: a surface for the pass, an occluder for its rays
+REF_VIEWS = {
+    "spheres": (VIEWS["spheres"][0], 1.0, (), np.inf),
+    "boxes": (R.camera_matrix((1.0, 2.0, 5.0), 0.0, -0.3), 0.8, (3, 4), np.inf),
+    "mesh_smooth": (VIEWS["mesh_smooth"][0], 0.5, (), np.inf),
+    "mesh_flat": (R.camera_matrix((0.0, 0.3, 2.0), 0.0, 0.0), 0.5, (1,), np.inf),
+    "glass_inside": (CAMERAS["spheres"][0], 1.0, (1,), 1.5),
+    "spheres_bare": (VIEWS["spheres"][0], 1.0, (4,), np.inf),
+}
+REF_ACCELS = dict(ACCELS, glass_inside=("scan",), spheres_bare=("scan",))
+REF_CASES = [(n, a) for n in REF_VIEWS for a in REF_ACCELS[n]]
+REF_FRAMES = ((13, 7), (24, 16))
+REF_SAMPLES = (1, 4, 64)
+SMALL_FRAMES = ((1, 1), (3, 2))  # on "spheres" (1 x 1: a surface) and "mesh_smooth" (1 x 1: none)
+SEEDS = (0, 0xFFFFFFFF, 0x9E3779B9)
+RADII = (2.5, np.inf)
+BIASES = (0.0, 0.001, 0.01)
+ENCLOSED = ("glass_inside",)  # no pixel without a surface can exist
+
+
+def ref_scene(name):
+    if name == "glass_inside":
+        import cases
+        return cases.glass_scene()
+    if name == "spheres_bare":
+        sh, tr, ma = scene("spheres")
+        sh = sh.copy()
+        sh["material"][4] = -1
+        return sh, tr, ma
+    return scene(name)
+
+
+def ref_rd(name, w, h):
+    cam, fov = REF_VIEWS[name][:2]
+    return frame_rd(cam, w, h, 1, fov=fov)
+
+
+def hostile_rd(rdata, value, component=0):
+    """rdata with one coordinate of the camera's origin (camera_to_world[3]) replaced by a NaN or an infinity"""
+    out = np.array(rdata, copy=True)
+    cam = np.array(out["camera_to_world"], F).reshape(4, 4)
+    cam[3, component] = value
+    out["camera_to_world"] = cam.reshape(np.shape(out["camera_to_world"]))
+    return out
+
+
+def ray_parameters(k):
+    """the k-th (seed, radius, bias) of the ray cases: every seed, radius and bias comes by within any six cases in a row"""
+    return SEEDS[k % 3], RADII[k % 2], BIASES[(k // 2) % 3]
+
+
 def rd(name, w, h):
     cam, fov = VIEWS[name]
     return frame_rd(cam, w, h, 1, fov=fov)
@@ -76,6 +137,7 @@ def centre_dirs64(rdata):
 #   u (|cam| + t + bias). Together with t |dir32 - dir64|:
 #       |O32 - O64| <= u ((E_DIR + 1) t + 2 (|cam| + t) + 2 bias) <= (E_DIR + 3) u (|cam| + t) + 2 u bias
 #   with |cam| the largest camera coordinate in magnitude.
+# (The exact statement -- O's three words from the pick's own words, no bound -- is tests/ao_ref.py origins().)
 def origin_bound(rdata, t, bias):
     aspect_fov = max(1.0, float(rdata["aspect_ratio"]) * float(rdata["fov_scale"]))
     e_dir = 17.0 * aspect_fov + 7.0

@@ -1,13 +1,14 @@
-"""The ambient-occlusion pass on the device (include/srt_abi.h "ambient-occlusion pass"; csrc/ao.hip): the counts against the
-occlusion query over the pass's own rays -- the pinned reference --, the rays against their definition, their distribution,
-scenes with known answers, the view's bytes, what the pass leaves untouched, its order behind scene updates, its errors, and
-the group and headless routes."""
+"""The ambient-occlusion pass on the device (include/srt_abi.h "ambient-occlusion pass"; csrc/ao.hip): the rays word for word and
+the counts integer for integer against the CPU reference (tests/ao_ref.py, section 11) -- the pinned reference --, the counts
+against the occlusion query over the pass's own rays, the rays' properties, their distribution, scenes with known answers, the
+view's bytes, what the pass leaves untouched, its order behind scene updates, its errors, and the group and headless routes."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import ao_cases as A
+import ao_ref as AR
 import gpu_harness as G
 from gpu_harness import T  # noqa: F401 (the fixture)
 from simple_raytracer_amd import records as R, scenes as S
@@ -413,4 +414,181 @@ def test_headless_prints_what_python_computes(T, tmp_path):
     assert raw.startswith(header)
     t.resolve_ao_view()
     assert np.array_equal(np.frombuffer(raw[len(header):], np.uint8).reshape(h, w, 3), t.read_argb().reshape(h, w, 4)[..., 1:])
+    t.close()
+
+
+# ---- 11. the CPU reference (tests/ao_ref.py): rays word for word, counts integer for integer --------------------------------------
+# Everything below is an equality of uint32 words or of integers with what tests/ao_ref.py states on the CPU oracle from the
+# pick's rays; nothing of the expected side comes from the library's AO or occlusion entry points.
+_ref_surfaces, _ref_words = {}, {}  # computed once per key and never changed; shared by the acceleration modes
+
+
+def ref_surfaces(t, oracle, name, rd, scn=None):
+    w, h = int(rd["width"]), int(rd["height"])
+    key = (name, w, h)
+    if key not in _ref_surfaces:
+        _ref_surfaces[key] = AR.surfaces(oracle, A.ref_scene(name) if scn is None else scn, t.pick_rays(A.centres(w, h), rd))
+    return _ref_surfaces[key]
+
+
+def ref_words(t, oracle, name, rd, s, seed=0, radius=np.inf, bias=0.001, scn=None):
+    key = (name, int(rd["width"]), int(rd["height"]), s, seed, float(radius), float(bias))
+    if key not in _ref_words:
+        _ref_words[key] = AR.records(oracle, ref_surfaces(t, oracle, name, rd, scn), s, seed=seed, radius=radius, bias=bias)
+    return _ref_words[key]
+
+
+def assert_words(got, want, what):
+    got = np.ascontiguousarray(got).view(np.uint32).reshape(-1, 8)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert not len(bad), (what, f"{len(bad)} of {len(got)} records differ; the first, record {bad[0]}:", [hex(x) for x in got[bad[0]]], [hex(x) for x in want[bad[0]]])
+
+
+@pytest.mark.parametrize("name,accel", A.REF_CASES)
+def test_the_rays_equal_the_reference_word_for_word(name, accel, T, oracle):
+    scn = A.ref_scene(name)
+    for fi, (w, h) in enumerate(A.REF_FRAMES):
+        rd = A.ref_rd(name, w, h)
+        t = handle(T, scn, accel, w, h)
+        surf = ref_surfaces(t, oracle, name, rd)
+        assert 2 * surf["has"].sum() >= w * h and (name in A.ENCLOSED or not surf["has"].all())
+        for shape in A.REF_VIEWS[name][2]:
+            assert (surf["shape"] == shape).any(), (name, shape)
+        for si, s in enumerate(A.REF_SAMPLES):
+            seed, radius, bias = A.ray_parameters(4 * fi + si)
+            got = t.ao_rays(rd, samples=s, seed=seed, radius=radius, bias=bias)
+            assert_words(got, ref_words(t, oracle, name, rd, s, seed, radius, bias), (name, accel, w, h, s, hex(seed), radius, bias))
+        assert t.counters()["watchdog"] == 0
+        t.close()
+
+
+def test_every_seed_radius_and_bias_of_the_ray_cases(T, oracle):
+    name, w, h, s = "spheres", 13, 7, 4
+    rd = A.ref_rd(name, w, h)
+    t = handle(T, A.ref_scene(name), "scan", w, h)
+    for seed in A.SEEDS:
+        for radius in A.RADII:
+            for bias in A.BIASES:
+                got = t.ao_rays(rd, samples=s, seed=seed, radius=radius, bias=bias)
+                assert_words(got, ref_words(t, oracle, name, rd, s, seed, radius, bias), (hex(seed), radius, bias))
+    t.close()
+
+
+@pytest.mark.parametrize("name,accel", [("spheres", "scan"), ("mesh_smooth", "sah")])
+def test_small_frames_and_windows_equal_the_reference(name, accel, T, oracle):
+    scn = A.ref_scene(name)
+    seen = set()
+    for w, h in A.SMALL_FRAMES:  # one pixel, and fewer rays than a wave
+        rd = A.ref_rd(name, w, h)
+        t = handle(T, scn, accel, w, h)
+        seen |= set(ref_surfaces(t, oracle, name, rd)["has"].tolist())
+        for s in (64, 1):
+            got = t.ao_rays(rd, samples=s, seed=0x9E3779B9, radius=2.5, bias=0.01)
+            assert_words(got, ref_words(t, oracle, name, rd, s, 0x9E3779B9, 2.5, 0.01), (name, w, h, s))
+            t.render_ao(rd, samples=s, seed=0x9E3779B9, radius=2.5, bias=0.01)
+            want = AR.counts(oracle, scn, ref_words(t, oracle, name, rd, s, 0x9E3779B9, 2.5, 0.01), s)
+            assert np.array_equal(t.read_ao()[0].reshape(-1), want), (name, w, h, s)
+        t.close()
+    assert seen == {True, False}
+    # windows whose first item is no multiple of 64: the item index, not the lane's, seeds the ray
+    w, h = 13, 7
+    rd = A.ref_rd(name, w, h)
+    t = handle(T, scn, accel, w, h)
+    for s in (1, 2):
+        whole = ref_words(t, oracle, name, rd, s, 0xFFFFFFFF, np.inf, 0.001)
+        for first in (1, w * h - 2):
+            assert (first * s) % 64 != 0
+            got = t.ao_rays(rd, first=first, n=2, samples=s, seed=0xFFFFFFFF)
+            assert_words(got, whole[first * s:(first + 2) * s], (name, s, first))
+            mine = AR.records(oracle, ref_surfaces(t, oracle, name, rd), s, seed=0xFFFFFFFF, first=first, n=2)  # the reference's own window
+            assert_words(got, mine, (name, s, first, "window"))
+    t.close()
+
+
+def count_cases(name):
+    """(seed, radius, bias) per sample count: the scene's radius at the default bias, and a short radius from the surface itself"""
+    radius = A.REF_VIEWS[name][3]
+    return {1: [(1, radius, 0.001), (0xFFFFFFFF, min(radius, 2.5), 0.0)], 4: [(4, radius, 0.001), (0x9E3779B9, min(radius, 2.5), 0.01)],
+            64: [(64, radius, 0.001), (0, min(radius, 2.5), 0.0)]}
+
+
+@pytest.mark.parametrize("name,accel", A.REF_CASES)
+def test_the_counts_equal_the_reference_integer_for_integer(name, accel, T, oracle):
+    scn, (w, h) = A.ref_scene(name), (13, 7)
+    rd = A.ref_rd(name, w, h)
+    t = handle(T, scn, accel, w, h)
+    has = ref_surfaces(t, oracle, name, rd)["has"].reshape(h, w)
+    partial = 0
+    for s in A.REF_SAMPLES:
+        for seed, radius, bias in count_cases(name)[s]:
+            kw = dict(samples=s, seed=seed, radius=radius, bias=bias)
+            want = AR.counts(oracle, scn, ref_words(t, oracle, name, rd, s, seed, radius, bias), s).reshape(h, w)
+            t.render_ao(rd, **kw)
+            got, samples = t.read_ao()
+            assert samples == s and got.dtype == np.uint32
+            bad = np.flatnonzero(got != want)
+            assert not len(bad), (name, accel, kw, bad[:8].tolist(), got.reshape(-1)[bad[:8]].tolist(), want.reshape(-1)[bad[:8]].tolist())
+            assert np.array_equal(got == NONE, ~has)
+            assert np.array_equal(got, reference_counts(t, rd, **kw)[0]), (name, accel, kw)  # and the occlusion query beside it
+            partial += int(((want > 0) & (want < s)).sum()) if s > 1 else 0
+    assert partial > 0 and t.counters()["watchdog"] == 0
+    t.close()
+
+
+def test_the_counts_of_a_refitted_tree_equal_the_reference(T, oracle):
+    sh, tr, ma = A.ref_scene("mesh_smooth")
+    w, h, s = 13, 7, 4
+    rd = A.ref_rd("mesh_smooth", w, h)
+    t = handle(T, (sh, tr, ma), "sah", w, h, refit=True)
+    t.render_ao(rd, samples=s)
+    first, _ = t.read_ao()
+    moved = sh.copy()
+    m = int(np.flatnonzero(sh["type"] == R.SHAPE_MODEL)[0])
+    moved[m] = R.model(int(sh["material"][m]), tr, int(sh["triangle_index"][m]), int(sh["num_triangles"][m]),
+                       R.mat_mul(R.translate((0.3, 0.15, -0.25)), sh["transform"][m]))
+    t.update_scene(moved, tr, ma)
+    assert t.acceleration_refit_info()["models"] >= 1
+    words = ref_words(t, oracle, "mesh_smooth moved", rd, s, scn=(moved, tr, ma))
+    assert_words(t.ao_rays(rd, samples=s), words, "refit")
+    t.render_ao(rd, samples=s)
+    second, _ = t.read_ao()
+    want = AR.counts(oracle, (moved, tr, ma), words, s).reshape(h, w)
+    assert np.array_equal(second, want) and not np.array_equal(first, second)
+    assert np.array_equal(first, AR.counts(oracle, (sh, tr, ma), ref_words(t, oracle, "mesh_smooth", rd, s), s).reshape(h, w))
+    t.close()
+
+
+def test_a_groups_counts_and_rays_equal_the_reference(T, oracle):
+    name, w, h, s = "boxes", 13, 7, 4
+    scn = A.ref_scene(name)
+    rd = A.ref_rd(name, w, h)
+    t = handle(T, scn, "sah", w, h)
+    words = ref_words(t, oracle, name, rd, s, 0x9E3779B9, 2.5, 0.01)
+    t.close()
+    g = T.TracerGroup(w, h, n_devices=2, devices=[0, 0], rows_per_block=1)
+    g.set_acceleration(1)
+    g.scene_data = R.scene_data(len(scn[0]))
+    g.update_scene(*scn)
+    kw = dict(samples=s, seed=0x9E3779B9, radius=2.5, bias=0.01)
+    assert_words(g.ao_rays(rd, **kw), words, "group")
+    g.render_ao(rd, **kw)
+    got, samples = g.read_ao()
+    assert samples == s and np.array_equal(got, AR.counts(oracle, scn, words, s).reshape(h, w))
+    g.close()
+
+
+@pytest.mark.parametrize("value,component", [(np.nan, 0), (np.inf, 1), (-np.inf, 2)])
+def test_a_hostile_camera_has_no_surface(value, component, T, oracle):
+    name, w, h, s = "spheres", 13, 7, 4
+    scn = A.ref_scene(name)
+    rd = A.hostile_rd(A.ref_rd(name, w, h), value, component)
+    t = handle(T, scn, "scan", w, h)
+    none = np.tile(np.array([0, 0, 0, AR.NAN_BITS, 0, 0, 0, 0], np.uint32), (w * h * s, 1))
+    surf = AR.surfaces(oracle, scn, t.pick_rays(A.centres(w, h), rd))
+    assert not surf["has"].any() and np.array_equal(AR.records(oracle, surf, s), none)  # so says the reference
+    assert_words(t.ao_rays(rd, samples=s), none, (value, component))
+    t.render_ao(rd, samples=s)
+    got, _ = t.read_ao()
+    assert (got == NONE).all() and t.counters()["watchdog"] == 0
     t.close()
